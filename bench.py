@@ -13,7 +13,12 @@ copied to the host (for N > 1: RCCL gather of the device-resident records to ran
 to the host there).  Weak scaling: every rank processes its own shard of `--batch` images of the global batch
 (BASELINE.json config "Batch 256 sharded 8 x 32"); value = all images / max-rank time.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+A plain run sets up, warms up, times the K steps (`ms_per_step`: milliseconds of one timed step) and prints the line; with
+--dump-outputs DIR it also writes what the last timed step computed to DIR/<name>.npy (step_outputs).  Everything else it can
+measure or check runs only with --full: the per-launch profile behind the two objects below, the side legs (upload-inclusive,
+single image, direct kernels only, 368x496 / 496x368, mixed sizes, precise), the CPU baseline and the keypoint match.
+
+Prints ONE JSON line on rank 0 (contract in the task statement); with --full it carries two extra objects (null otherwise):
   roofline      the dominant kernel (the 7x7 Winograd kernel, two branch groups per launch): FLOP per launch the kernel
                 ISSUES to the matrix cores (engine profile) / its average launch duration, measured live with HIP events
                 on the stream the kernels run on (per-launch event pairs inside the timed region), against the dense
@@ -124,7 +129,17 @@ def parse():
                     'after the timed region (0 = the whole shard)')
     ap.add_argument('--force-gather', action='store_true', help='N = 1: still create a one-rank process group and route the records '
                     'through the RCCL gather (dist.RecordPipe), the code path of N > 1')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true', help='everything beyond the headline: per-launch profile (roofline, step_roofline, '
+                    '--dump-profile), the side legs (upload-inclusive, single image, direct kernels, 368x496, mixed sizes, precise, --bf16x3), '
+                    'the CPU baseline and the keypoint match against the oracle.  Off: set up, warm up, time the steps, print the line')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='rank 0 writes what the last timed step computed as DIR/<name>.npy '
+                    '(float32 / float64): the result records, the peaks and the network maps (write_outputs)')
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if not a.full and (a.dump_profile or a.bf16x3):
+        ap.error('--dump-profile and --bf16x3 belong to the full run: add --full')
+    return a
 
 
 def self_launch(a):
@@ -283,6 +298,46 @@ def dominant_kernel(prof):
     return (name,) + tuple(by_kernel[name][:4]) + (sorted(by_kernel[name][4]),)
 
 
+OUTPUTS_MAX_BYTES = 64 << 20
+
+
+def step_outputs(eng, rec, n_local, max_bytes=OUTPUTS_MAX_BYTES):
+    """What a caller of the timed path receives from its last step, as float32 / float64 arrays for --dump-outputs:
+      records_*       the result records of every image of the (global) batch: counts and status per image, scores (B, people) and
+                      poses (B, people, 18, 3); the slots beyond an image's n_people are zeroed (the library leaves them unspecified)
+      peaks           (n, 6): image index + the image's peak rows (pmx_get_peaks) for the images this rank ran
+      paf, heat       the network maps of this rank's images (B, 38 | 19, h/8, w/8); if they do not fit in `max_bytes` with the rest, the
+                      maps of a fixed, seeded sample of the images (map_images names them)"""
+    out = {}
+    n_people = rec['n_people'].astype(np.int64)
+    for k in ('n_people', 'n_peaks', 'status', 'n_subsets_raw'):
+        out['records_' + k] = rec[k].astype(np.float64)
+    scores = np.array(rec['scores'], dtype=np.float64)
+    poses = np.array(rec['poses'], dtype=np.float64)
+    for i, n in enumerate(n_people):
+        scores[i, n:] = 0.0
+        poses[i, n:] = 0.0
+    out['records_scores'], out['records_poses'] = scores, poses
+    rows = [np.concatenate([np.full((len(p_), 1), i, np.float64), p_], axis=1) for i, p_ in enumerate(eng.peaks(i) for i in range(n_local))]
+    out['peaks'] = np.concatenate(rows) if rows else np.zeros((0, 6), np.float64)
+    paf, heat = eng.get_maps()
+    room = max_bytes - sum(v.nbytes for v in out.values()) - 8 * len(paf)
+    per_image = paf[0].nbytes + heat[0].nbytes
+    keep = np.arange(len(paf))
+    if per_image * len(paf) > room:
+        keep = np.sort(np.random.default_rng(0).choice(len(paf), max(0, room // per_image), replace=False))
+    out['map_images'] = keep.astype(np.float64)
+    out['paf'], out['heat'] = np.ascontiguousarray(paf[keep]), np.ascontiguousarray(heat[keep])
+    return out
+
+
+def write_outputs(directory, outputs):
+    os.makedirs(directory, exist_ok=True)
+    for name, v in outputs.items():
+        assert v.dtype in (np.float32, np.float64), (name, v.dtype)
+        np.save(os.path.join(directory, name + '.npy'), v)
+
+
 def main():
     a = parse()
     if a.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -410,7 +465,7 @@ def main():
 
     if a.warmup:
         rec = run_steps(a.warmup)
-    profile = not a.no_profile
+    profile = a.full and not a.no_profile
     if profile:
         # inside the timed region only the dominant kernel's launches carry HIP-event pairs (25 of ~60 launches per step: the
         # events cost ~5 us of idle each); the per-kernel split of a whole step is measured on one extra, untimed step below
@@ -431,6 +486,8 @@ def main():
         dist.barrier()
     dt = time.perf_counter() - t0
     n_coll = (pipe.collectives - n_coll0) if pipe else 0
+    # what the last timed step computed, read before anything else runs on the engine
+    outputs = step_outputs(eng, rec, hi - lo) if a.dump_outputs and rank == 0 else None
     per_rank = [B * a.steps / dt_local]
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=coll_dev)
@@ -466,6 +523,8 @@ def main():
         status_bits = int(np.bitwise_or.reduce(rec['status'])) if len(rec) else 0
         if a.dump_records:
             np.save(a.dump_records, rec)
+        if outputs is not None:
+            write_outputs(a.dump_outputs, outputs)
         out = {
             'metric': 'frames/sec at 368x368 batch (1/2/4/8 GPU) + keypoint-match vs reference',
             'value': frames / dt, 'unit': 'frames/s', 'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup,
@@ -571,7 +630,8 @@ def main():
                     json.dump({'batch': B, 'steps': 1, 'entries': prof_all}, f, indent=1)
         out['roofline'] = roof
         eng.profile_enable(False)
-        if world == 1 and not a.no_extras:
+        out['full'] = a.full
+        if world == 1 and a.full and not a.no_extras:
             # the side legs (other workloads of the same path, after the timed region): a leg that fails reports its error under its key and
             # must never cost the run its line -- the headline above is already measured
             def leg(key, fn, *args, **kw):
@@ -596,7 +656,7 @@ def main():
                 out['precise']['hw_queues'] = 'GPU_MAX_HW_QUEUES=%s' % os.environ.get('GPU_MAX_HW_QUEUES')
             eng.detect_batch(device_ptr=d_imgs.data_ptr(), shape=(B, S, S), map_h=map_s, map_w=map_s)     # restore the batch state
             rec = eng.results()                                                                             # for keypoint_match
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             oracle_results = None
             try:
                 out['cpu_baseline'], oracle_results = cpu_baseline(weights, imgs, (map_s, map_s), a.cpu_budget)

@@ -1,8 +1,8 @@
 """TEST INFRASTRUCTURE -- runs the *verbatim* reference code from /root/reference (read-only, imported where it lies).
 
-Used only by `oracle/make_golden.py` and the `tests/test_oracle_vs_reference.py` / `tests/test_reference_network.py`
-CPU tests, and only in the authoring container (where /root/reference exists).  It never runs on the GPU box and is
-never imported by the product package.
+Used only by the golden generators (`oracle/make_golden.py`, `oracle/make_golden_net.py`, `oracle/ref_goldens.py`) and
+`tools/time_reference_cpu.py`, and only where the reference exists (REFERENCE_DIR below).  The tests read what those generators recorded under tests/golden/; neither
+they nor the product package import this module.
 
 The reference cannot be imported as-is here: chainer, cupy, cv2 and pycocotools are not installed.  Its own code is
 pure Python on top of a handful of third-party calls, so those calls -- and only those -- are backed by stand-ins in

@@ -108,3 +108,44 @@ def test_hardware_queue_default_follows_the_rank_count(monkeypatch):
     assert f(['--gpus', '2']) and f(['--gpus=8', '--steps', '3']) and f(['--force-gather'])
     monkeypatch.setenv('WORLD_SIZE', '4')
     assert f([]) and f(['--gpus', '4'])
+
+
+def test_step_outputs_are_float_arrays_within_the_budget(tmp_path):
+    """--dump-outputs: every array float32 / float64, the person slots beyond n_people zeroed, peaks tagged with their image, and maps
+    that do not fit in the budget replaced by the maps of a seeded sample of the images (the same sample on every run)."""
+    import numpy as np
+    native = importlib.import_module(bench.PKG + '.native')
+
+    class Eng(object):
+        def peaks(self, i):
+            return np.arange(10, dtype=np.float64).reshape(2, 5) + i
+
+        def get_maps(self):
+            return np.ones((8, 38, 46, 46), np.float32), np.full((8, 19, 46, 46), 2, np.float32)
+    rec = np.zeros(8, native.result_dtype(64))
+    rec['n_people'] = 3
+    rec['poses'] = 7.0
+    rec['scores'] = 0.5
+    out = bench.step_outputs(Eng(), rec, 8)
+    assert all(v.dtype in (np.float32, np.float64) for v in out.values())
+    assert out['records_n_people'].tolist() == [3.0] * 8
+    assert (out['records_poses'][:, :3] == 7).all() and not out['records_poses'][:, 3:].any() and not out['records_scores'][:, 3:].any()
+    assert out['peaks'].shape == (16, 6) and out['peaks'][:, 0].tolist() == [i for i in range(8) for _ in range(2)]
+    assert out['map_images'].tolist() == list(range(8)) and out['paf'].shape == (8, 38, 46, 46)
+    small = bench.step_outputs(Eng(), rec, 8, max_bytes=2 << 20)
+    assert sum(v.nbytes for v in small.values()) <= 2 << 20
+    assert 0 < len(small['map_images']) < 8 and small['paf'].shape[0] == small['heat'].shape[0] == len(small['map_images'])
+    assert np.array_equal(small['map_images'], bench.step_outputs(Eng(), rec, 8, max_bytes=2 << 20)['map_images'])
+    bench.write_outputs(str(tmp_path / 'o'), out)
+    assert sorted(os.listdir(str(tmp_path / 'o'))) == sorted(k + '.npy' for k in out)
+
+
+def test_full_only_options_need_full(monkeypatch):
+    import pytest
+    for argv in (['--bf16x3'], ['--dump-profile', 'p.json'], ['--steps', '0'], ['--warmup', '-1']):
+        monkeypatch.setattr('sys.argv', ['bench.py'] + argv)
+        with pytest.raises(SystemExit):
+            bench.parse()
+    monkeypatch.setattr('sys.argv', ['bench.py', '--full', '--bf16x3', '--steps', '3'])
+    a = bench.parse()
+    assert a.full and a.bf16x3 and a.steps == 3 and a.dump_outputs is None

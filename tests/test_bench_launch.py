@@ -103,3 +103,23 @@ def test_one_rank_through_the_rccl_gather_equals_plain_run(tmp_path):
     a, b = np.load(fg), np.load(fp)
     assert a.dtype == b.dtype and a.tobytes() == b.tobytes() and int(a['n_peaks'].sum()) > 0
 
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_what_its_last_step_computed(tmp_path):
+    """A plain run (no --full): the headline only -- `--steps` timed steps, `ms_per_step`, no profile, side legs or CPU baseline -- and
+    --dump-outputs writes the arrays of the last timed step: the same records --dump-records saves, float32 / float64 only."""
+    d, f = tmp_path / 'out', str(tmp_path / 'rec.npy')
+    r = _run(['--gpus', '1', '--batch', '4', '--steps', '2', '--warmup', '1', '--dump-outputs', str(d), '--dump-records', f], timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
+    assert line['steps'] == 2 and line['ms_per_step'] > 0 and line['full'] is False
+    assert abs(line['value'] - 4 * 1e3 / line['ms_per_step']) <= 1e-6 * line['value']
+    assert line['roofline'] is None and line['cpu_baseline'] is None and 'single_image' not in line and 'precise' not in line
+    out = {p.name[:-4]: np.load(str(p)) for p in d.iterdir()}
+    assert all(v.dtype in (np.float32, np.float64) for v in out.values()) and sum(v.nbytes for v in out.values()) <= 64 << 20
+    rec = np.load(f)
+    assert np.array_equal(out['records_n_people'], rec['n_people']) and np.array_equal(out['records_n_peaks'], rec['n_peaks'])
+    for i, n in enumerate(rec['n_people']):
+        assert np.array_equal(out['records_poses'][i, :n], rec['poses'][i, :n]) and np.array_equal(out['records_scores'][i, :n], rec['scores'][i, :n])
+    assert out['paf'].shape == (4, 38, 46, 46) and out['heat'].shape == (4, 19, 46, 46) and len(out['peaks']) == int(rec['n_peaks'].sum())

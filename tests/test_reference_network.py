@@ -1,10 +1,11 @@
 """CPU: the network half of the oracle pinned to the reference's OWN model code.
 
-Authoring container (where /root/reference exists): `oracle/_refimport.py` executes models/CocoPoseNet.py, models/FaceNet.py,
-models/HandNet.py, pose_detector.py, face_detector.py and hand_detector.py verbatim on torch-backed stand-ins for the few
-Chainer / OpenCV calls they make; the restatements in oracle/ (network_ref, face_hand_ref, postprocess_ref, precise_ref) and the
-product's layer tables must agree with them exactly.  Everywhere (also on the GPU box's CPU): the restatements reproduce the
-committed goldens those reference runs wrote (tests/golden/net_*.npz, e2e_*.npz, kp_*.npz; generator oracle/make_golden_net.py).
+Where the reference exists, `oracle/_refimport.py` executes models/CocoPoseNet.py, models/FaceNet.py, models/HandNet.py,
+pose_detector.py, face_detector.py and hand_detector.py verbatim on torch-backed stand-ins for the few Chainer / OpenCV calls they
+make; what they returned on the inputs of the reference checks below is recorded in tests/golden/ref_checks.* (oracle/ref_goldens.py,
+one torch thread), and the restatements in oracle/ (network_ref, face_hand_ref, postprocess_ref, precise_ref) and the product's layer
+tables must agree with it exactly.  The restatements also reproduce the committed goldens of larger reference runs
+(tests/golden/net_*.npz, e2e_*.npz, kp_*.npz; generator oracle/make_golden_net.py) within tolerance.
 """
 import os
 import tempfile
@@ -13,14 +14,13 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, pkg
-from oracle import _refimport as R
 from oracle import face_hand_ref as FH
 from oracle import network_ref as N
 from oracle import postprocess_ref as P
 from oracle import precise_ref
+from oracle import ref_goldens as G
 from oracle import resize_ref
 
-needs_reference = pytest.mark.skipif(not R.reference_available(), reason='/root/reference not present')
 HEAD = ('Mconv7_stage6_L1', 'Mconv7_stage6_L2')
 
 
@@ -41,13 +41,21 @@ def load_e2e(name):
     return d
 
 
-# ---- against the reference's own code (authoring container) ---------------------------------------------------------------
-@needs_reference
+@pytest.fixture
+def one_thread():
+    """The recorded reference maps were computed with one torch thread (oneDNN's summation order depends on the thread count)."""
+    import torch
+    n = G.one_thread()
+    yield
+    torch.set_num_threads(n)
+
+
+# ---- against what the reference's own code returned (tests/golden/ref_checks.*) ----------------------------------------------
 @pytest.mark.parametrize('arch', ['posenet', 'facenet', 'handnet'])
 def test_layer_tables_equal_the_reference_chain(arch):
     """Names, order, shapes, stride and padding read off the instantiated reference Chain == the product's layer table
     (weights.py, which pmx_set_layer checks every upload against) == the oracle's."""
-    ref = R.ref_layer_table(arch)
+    ref = [tuple(t) for t in G.load()[1]['layer_tables'][arch]]
     assert [(n, ci, co, k) for n, ci, co, k, s, p in ref] == [tuple(t) for t in pkg('weights').layer_table(arch)]
     assert all(s == 1 and p == k // 2 for _, _, _, k, s, p in ref)
     if arch == 'posenet':
@@ -56,37 +64,35 @@ def test_layer_tables_equal_the_reference_chain(arch):
         assert [(n, ci, co, k) for n, ci, co, k, s, p in ref] == FH.layer_table({'facenet': 71, 'handnet': 22}[arch])
 
 
-@needs_reference
-def test_network_restatement_equals_reference_posenet_bit_for_bit():
+def test_network_restatement_equals_reference_posenet_bit_for_bit(one_thread):
     """oracle/network_ref.forward == the reference's CocoPoseNet.__call__ (models/CocoPoseNet.py:132-262) executed verbatim, all
     six stages, same conv primitive -> identical bits.  A swapped concat order, a misplaced pool or a missing ReLU in the
     restatement cannot pass."""
     w = pkg('weights').synthetic_weights(0)
     _, x = _x('posenet', 7, 64, 96)
-    rp, rh = R.ref_network_forward('posenet', w, x, all_stages=True)
+    arr, _ = G.load()
+    rp, rh = [arr['net_posenet_stage%d_paf' % s] for s in range(6)], [arr['net_posenet_stage%d_heat' % s] for s in range(6)]
     mine = N.forward(w, x, all_stages=True)
     assert len(rp) == len(rh) == len(mine) == 6
     for s in range(6):
         assert np.array_equal(rp[s], mine[s][0]) and np.array_equal(rh[s], mine[s][1]), s
 
 
-@needs_reference
 @pytest.mark.parametrize('arch,n', [('facenet', 71), ('handnet', 22)])
-def test_network_restatement_equals_reference_cpm_bit_for_bit(arch, n):
+def test_network_restatement_equals_reference_cpm_bit_for_bit(arch, n, one_thread):
     w = pkg('weights').synthetic_weights(1, arch)
     _, x = _x(arch, 8, 56, 72)
-    ref = R.ref_network_forward(arch, w, x, all_stages=True)
+    ref = [G.load()[0]['net_%s_stage%d_heat' % (arch, s)] for s in range(6)]
     mine = FH.cpm_forward(w, x)
     assert len(ref) == len(mine) == 6 and ref[-1].shape == (1, n, 7, 9)
     for a, b in zip(ref, mine):
         assert np.array_equal(a, b)
 
 
-@needs_reference
-def test_reference_call_equals_oracle_pipeline_and_npz_round_trip():
+def test_reference_call_equals_oracle_pipeline_and_npz_round_trip(one_thread):
     """The whole reference `PoseDetector('posenet', weights_file)(img)` (its own load_npz path, :23-26, and __call__, :484-517)
     == resize_ref + preprocess + network_ref + postprocess_ref; the NPZ written by the product's writer loads into the
-    reference Chain."""
+    reference Chain (the recording loaded the NPZ this writer wrote; here the writer's file must read back as the weights)."""
     W = pkg('weights')
     w = W.synthetic_weights(3)
     img = np.random.default_rng(5).integers(0, 256, (70, 90, 3), dtype=np.uint8)
@@ -98,8 +104,11 @@ def test_reference_call_equals_oracle_pipeline_and_npz_round_trip():
     with tempfile.TemporaryDirectory() as td:
         path = os.path.join(td, 'coco_posenet.npz')
         W.save_npz(path, w)
-        det = R.ref_pose_detector(weights_file=path)
-    poses, scores = R.ref_call(det, img)
+        z = np.load(path)
+        assert sorted(z.files) == sorted('%s/%s' % (n, k) for n in w for k in 'Wb')
+        assert all(np.array_equal(z[n + '/W'], w[n][0]) and np.array_equal(z[n + '/b'], w[n][1]) for n in w)
+    arr, _ = G.load()
+    poses, scores = arr['call_poses'], arr['call_scores']
     paf, heat = N.forward(w, P.preprocess(small))
     mine = P.postprocess_from_net_output(paf[0], heat[0], map_h, map_w, orig_w=90, orig_h=70)
     assert len(mine['all_peaks']) > 20 and len(mine['poses']) > 0
@@ -107,47 +116,31 @@ def test_reference_call_equals_oracle_pipeline_and_npz_round_trip():
     assert np.allclose(scores, mine['scores'], rtol=0, atol=1e-12)
 
 
-@needs_reference
-def test_reference_detect_precise_equals_oracle_pipeline():
+def test_reference_detect_precise_equals_oracle_pipeline(one_thread):
     """pose_detector.py:433-482 run verbatim (four scales) == oracle/precise_ref.py on the same network."""
     W = pkg('weights')
     w = W.synthetic_weights(2)
     img = np.random.default_rng(6).integers(0, 256, (40, 56, 3), dtype=np.uint8)
     paf, heat = N.forward(w, P.preprocess(resize_ref.resize_linear_u8(img, 368 * 56 // 40 // 8 * 8, 368)))
     w = W.calibrate_head(w, paf[0], heat[0], heat_s=0.2, heat_t=-0.2, paf_s=1.2)
-    det = R.ref_pose_detector(w, precise=True)
-    poses, scores = R.ref_call(det, img)
+    arr, _ = G.load()
+    poses = arr['precise_poses']
     pafs, heats, _ = precise_ref.averaged_maps(lambda x: N.forward(w, x), img)
-    assert np.array_equal(det.pafs, pafs) and np.array_equal(det.heatmaps, heats)
+    assert np.array_equal(arr['precise_pafs'], pafs) and np.array_equal(arr['precise_heats'], heats)
     mine = precise_ref.detect_precise_from_maps(pafs, heats)
     assert len(mine['all_peaks']) > 0
     assert np.array_equal(np.asarray(poses).reshape(-1, 18, 3), np.asarray(mine['poses']).reshape(-1, 18, 3))
 
 
-@needs_reference
 @pytest.mark.parametrize('arch,hand_type', [('facenet', None), ('handnet', 'right'), ('handnet', 'left')])
-def test_reference_keypoint_detectors_equal_oracle(arch, hand_type):
-    """face_detector.py:28-40 / hand_detector.py:28-50 run verbatim == oracle/face_hand_ref.detect."""
-    m = R.import_reference_modules()
-    W = pkg('weights')
-    w = W.synthetic_weights(4, arch)
+def test_reference_keypoint_detectors_equal_oracle(arch, hand_type, one_thread):
+    """face_detector.py:28-40 / hand_detector.py:28-50 run verbatim == oracle/face_hand_ref.detect.  The full-size (368 x 368) network
+    is slow on the CPU: the recording ran the reference with its inference size shrunk to 64, the restatement sees the same."""
+    _, js = G.load()
+    w = pkg('weights').synthetic_weights(4, arch)
     img = np.random.default_rng(9).integers(0, 256, (60, 52, 3), dtype=np.uint8)
-    import contextlib
-    import io
-    with tempfile.TemporaryDirectory() as td:
-        path = os.path.join(td, 'w.npz')
-        W.save_npz(path, w)
-        with contextlib.redirect_stdout(io.StringIO()):
-            det = (m['face_detector'].FaceDetector if arch == 'facenet' else m['hand_detector'].HandDetector)(arch, path, device=-1)
-    # the full-size (368 x 368) network is slow on the CPU; both sides see the same shrunken inference size
-    key = 'face_inference_img_size' if arch == 'facenet' else 'hand_inference_img_size'
-    thresh = m['entity'].params['face_heatmap_peak_thresh' if arch == 'facenet' else 'hand_heatmap_peak_thresh']
-    old = m['entity'].params[key]
-    m['entity'].params[key] = 64
-    try:
-        ref = det(img) if hand_type is None else det(img, hand_type=hand_type)
-    finally:
-        m['entity'].params[key] = old
+    thresh = js['keypoint_thresh'][arch]
+    ref = js['keypoints']['%s-%s' % (arch, hand_type)]
     mine, _ = FH.detect(lambda x: FH.cpm_forward(w, x)[-1], img, thresh, size=64, hand_type=hand_type or 'right')
     assert len(ref) == len(mine)
     for a, b in zip(ref, mine):

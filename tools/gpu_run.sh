@@ -8,8 +8,8 @@
 #   python tools/summarize_profiles.py <tag> <rNN>     -> profiles/<rNN>_*
 # Steps (each under its own `timeout`, none aborts the call):
 #   tests[:<pytest -k expr>]   the GPU suite (or a subset)            smoke            __graft_entry__.smoke()
-#   bench                      python bench.py (full line)            bench_gather     bench.py --force-gather (one-rank RCCL record path)
-#   bench_fast                 bench.py --no-cpu-baseline --no-extras bench_ranks:<n>  bench.py --gpus n over gloo on this one GPU
+#   bench                      python bench.py --full (full line)     bench_gather     bench.py --full --force-gather (one-rank RCCL record path)
+#   bench_fast                 bench.py --full --no-cpu-baseline --no-extras (roofline only)   bench_ranks:<n>  bench.py --gpus n over gloo on one GPU
 #   census  census1  census_rect  census_modes    the margin census: 512 frames batch 32 | 128 frames batch 1 | 368x496 + 496x368 |
 #                              512 frames with the conv1-direct and direct-kernel engine modes next to the default (drift attribution)
 #   rp_bench rp_drv rp_b1 rp_rect rp_precise rp_mixed   rocprofv3 --kernel-trace --stats of bench.py / the batch-32 driver / batch 1 /
@@ -45,16 +45,16 @@ for STEP in "$@"; do
   case $S in
     tests) if [ -n "$A" ]; then (timeout 1500 python -m pytest tests -m gpu -q -p no:cacheprovider -k "$A") > $O/pytest_gpu.log 2>&1; else (timeout 1500 python -m pytest tests -m gpu -q -p no:cacheprovider) > $O/pytest_gpu.log 2>&1; fi; note tests $?; tail -5 $O/pytest_gpu.log ;;
     smoke) (timeout 300 python -c "import __graft_entry__ as g; g.smoke()") > $O/smoke.log 2>&1; note smoke $? ;;
-    bench) (timeout 900 python bench.py --steps 20 --warmup 3 --dump-profile $O/prof_bench.json) > $O/bench.log 2> $O/bench.err; note bench $? ;;
-    bench_fast) (timeout 400 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras) > $O/bench_fast.log 2> $O/bench_fast.err; note bench_fast $?; tail -c 600 $O/bench_fast.log ;;
-    bench_gather) (timeout 400 python bench.py --steps 10 --warmup 2 --force-gather --no-cpu-baseline --no-extras) > $O/bench_force_gather.log 2> $O/bench_force_gather.err; note bench_gather $? ;;
+    bench) (timeout 900 python bench.py --full --steps 20 --warmup 3 --dump-profile $O/prof_bench.json) > $O/bench.log 2> $O/bench.err; note bench $? ;;
+    bench_fast) (timeout 400 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras) > $O/bench_fast.log 2> $O/bench_fast.err; note bench_fast $?; tail -c 600 $O/bench_fast.log ;;
+    bench_gather) (timeout 400 python bench.py --full --steps 10 --warmup 2 --force-gather --no-cpu-baseline --no-extras) > $O/bench_force_gather.log 2> $O/bench_force_gather.err; note bench_gather $? ;;
     bench_ranks) (timeout 900 python bench.py --gpus $A --steps 4 --warmup 1 --backend gloo --no-cpu-baseline --no-profile --no-extras) > $O/bench_${A}ranks.log 2> $O/bench_${A}ranks.err; note bench_ranks_$A $? ;;
     census) (timeout 1200 python tools/parity_census.py --frames 512 --out $O/parity_census.json) > $O/census.log 2> $O/census.err; note census $? ;;
     census1) (timeout 900 python tools/parity_census.py --frames 128 --batch 1 --out $O/parity_census_single_image.json) > $O/census1.log 2> $O/census1.err; note census1 $? ;;
     census_rect) (timeout 900 python tools/parity_census.py --frames 128 --h 368 --w 496 --out $O/parity_census_368x496.json) > $O/census_r1.log 2> $O/census_r1.err; note census_368x496 $?
                  (timeout 900 python tools/parity_census.py --frames 96 --h 496 --w 368 --out $O/parity_census_496x368.json) > $O/census_r2.log 2> $O/census_r2.err; note census_496x368 $? ;;
     census_modes) (timeout 1500 python tools/parity_census.py --frames 512 --mode conv1_direct:conv1_wino=0 --mode direct_kernels:conv_algo=0 --out $O/parity_census_modes.json) > $O/census_modes.log 2> $O/census_modes.err; note census_modes $? ;;
-    rp_bench) rp bench 600 python $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras ;;
+    rp_bench) rp bench 600 python $R/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras ;;
     rp_drv) rp drv 300 python $R/tools/profile_driver.py --batch 32 --steps 3 ;;
     rp_b1) rp b1 300 python $R/tools/profile_driver.py --batch 1 --steps 20 ;;
     rp_rect) rp rect 300 python $R/tools/rect_time.py --h 368 --w 496 --batch 32 --steps 3 ;;

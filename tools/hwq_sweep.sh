@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; cd $R; O=$R/gpurun_out/${1:-hwq}; mkdir -p $O
 for Q in ${HWQ_LIST:-2 4 8 2 4 8}; do
   export GPU_MAX_HW_QUEUES=$Q
   A=$(timeout 300 python tools/precise_bench_leg.py 1 2>/dev/null | tail -1)
-  timeout 600 python bench.py --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_q$Q.log 2>/dev/null
+  timeout 600 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_q$Q.log 2>/dev/null
   B=$(python - <<PY
 import json
 d=json.loads([l for l in open("$O/bench_q$Q.log") if l.startswith("{")][-1])
