@@ -228,6 +228,10 @@ static int prof_begin(pmx_ctx* c, const std::string& name0, double flops, double
     c->prof_open = (int)c->pending.size() - 1;
     return PMX_OK;
 }
+static int prof_end(pmx_ctx* c);
+// the profiler for the other translation units (pmx_boxes.hip): a labelled launch of `bytes` compulsory bytes
+int pmx_prof_begin(pmx_ctx* c, const char* name, double bytes) { return c->prof_on == 1 ? prof_begin(c, name, 0, bytes) : PMX_OK; }
+int pmx_prof_end(pmx_ctx* c) { return prof_end(c); }
 static int prof_end(pmx_ctx* c)
 {
     if (!c->prof_on || c->prof_open < 0) return PMX_OK;
@@ -408,6 +412,7 @@ extern "C" void pmx_destroy(pmx_ctx* c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
+    pmx_boxes_free(c);
     for (auto& l : c->layers) { if (l.d_w) (void)hipFree(l.d_w); if (l.d_b) (void)hipFree(l.d_b); if (l.d_w3) (void)hipFree(l.d_w3); if (l.d_ww) (void)hipFree(l.d_ww); }
     pp_free(c);
     void* ptrs[] = {c->sk_scratch, c->sk_zero_bias, c->pr_tmp, c->d_kp, c->u8_src, c->rs_tab, c->in16, c->act0, c->act1, c->cat, c->brA, c->brB, c->brT, c->nchw_tmp, c->u8_tmp, c->ext_paf, c->ext_heat,
@@ -1361,6 +1366,10 @@ static void make_grid(int in, int out, std::vector<int>& i0, std::vector<int>& i
         i1[k] = f + 1 > in - 1 ? in - 1 : (f + 1 < 0 ? 0 : f + 1);
         lo[k] = wl; hi[k] = wh;
     }
+}
+void pmx_make_upsample_grid(int in, int out, std::vector<int>& i0, std::vector<int>& i1, std::vector<double>& lo, std::vector<double>& hi)
+{
+    make_grid(in, out, i0, i1, lo, hi);
 }
 
 int pmx_ensure_tables(pmx_ctx* c, int in_h, int in_w, int out_h, int out_w, int flip_x)

@@ -1,0 +1,517 @@
+// pmx_boxes.hip -- face / hand key points for many boxes of ONE image (the loop of the reference's demo.py:30-55 over the people of a
+// picture: a face crop and two hand crops per person, each through FaceNet / HandNet), batched:
+//
+//   pmx_forward_u8_boxes      box_gather_resize_u8_kernel: crop_image (pose_detector.py:401-424: zero outside the image) + the optional
+//                             cv2.flip(img, 1) of a left hand (hand_detector.py:29-30) + cv2.resize to the network input, OpenCV's
+//                             fixed-point INTER_LINEAR (prep.hip::resize_linear_u8_kernel's arithmetic), every crop of a chunk in one
+//                             launch, straight from the full image -- no crop is materialised; then the network at batch n.
+//   pmx_keypoints_images      kp_tiles_kernel<10>: F.resize_images of the last stage to the crop's own size, the optional left / right mirror
+//                             of the maps (hand_detector.py:46-47), the SciPy-order Gaussian -- pp_smooth.h, the same text as
+//                             pp_peaks_fast_kernel<10> -- over a flat list of 32 x 32 tiles of crops of different sizes, each block
+//                             leaving an arg-max record per (tile, channel) instead of the smoothed map; kp_merge_kernel merges the
+//                             records of a crop (argmax_merge is exact) into the reference's key point, tie quirk included.
+//   pmx_keypoints_boxes       both, chunked by the context's batch capacity, enqueued back to back: one image upload, one staging copy,
+//                             one D2H copy and one stream synchronisation per call.
+//
+// Bit-identity: per crop the bytes of the network input equal host crop_image (+ [:, ::-1]) + pmx_forward_u8_resized, and the key points
+// equal pmx_keypoints on the same maps with the crop's size and "kp_flip_x" (tests/test_gpu_face_hand_boxes.py).  Gaussian radii other
+// than 10, the reference's GPU peak branch and the "pp_generic" switch take a per-crop loop over pp_keypoints_launch instead.
+#include "pmx_ctx.h"
+#include "pp_smooth.h"
+
+#include <algorithm>
+#include <climits>
+#include <cstring>
+
+namespace {
+
+struct BoxDesc { int left, top, w, h, flip, pad0, pad1, pad2; };       // crop of the image (w x h from (left, top)), mirrored if flip
+
+struct KpCrop {                 // one crop of pmx_keypoints_images: its up-sampling tables (device pointers into the staging buffer)
+    PPTables tab;
+    int h, w, tiles_x, tile0;   // output size, tiles per row, first tile in the call's flat tile list
+};
+
+// crop pixel (yy, xx) of box d, mirrored when d.flip (column xx reads crop column w - 1 - xx), 0 outside the image
+__device__ __forceinline__ int box_px(const uint8_t* __restrict__ img, int img_h, int img_w, const BoxDesc& d, int yy, int xx, int c)
+{
+    const long long iy = (long long)d.top + yy;
+    const long long ix = (long long)d.left + (d.flip ? d.w - 1 - xx : xx);
+    if (iy < 0 || iy >= img_h || ix < 0 || ix >= img_w) return 0;
+    return (int)img[(iy * img_w + ix) * 3 + c];
+}
+
+// one thread per output pixel (3 channels) of n crops resized to dh x dw; tables per crop [x: idx0 | idx1 | coef0 | coef1 (dw each) |
+// y: the same (dh each)], pmx_make_resize_table of (dst, crop extent).  Arithmetic of prep.hip::resize_linear_u8_kernel.
+__global__ __launch_bounds__(256) void box_gather_resize_u8_kernel(const uint8_t* __restrict__ img, int img_h, int img_w,
+                                                                   const BoxDesc* __restrict__ desc, const int* __restrict__ tabs,
+                                                                   int n, int dh, int dw, uint8_t* __restrict__ dst)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long npix = (long long)n * dh * dw;
+    if (i >= npix) return;
+    const int x = (int)(i % dw);
+    const long long t = i / dw;
+    const int y = (int)(t % dh);
+    const int b = (int)(t / dh);
+    const BoxDesc d = desc[b];
+    const int* xtab = tabs + (long long)b * 4 * (dw + dh);
+    const int* ytab = xtab + 4 * dw;
+    const int sx0 = xtab[x], sx1 = xtab[dw + x], a0 = xtab[2 * dw + x], a1 = xtab[3 * dw + x];
+    const int sy0 = ytab[y], sy1 = ytab[dh + y], b0 = ytab[2 * dh + y], b1 = ytab[3 * dh + y];
+    uint8_t* o = dst + i * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int S0 = box_px(img, img_h, img_w, d, sy0, sx0, c) * a0 + box_px(img, img_h, img_w, d, sy0, sx1, c) * a1;
+        const int S1 = box_px(img, img_h, img_w, d, sy1, sx0, c) * a0 + box_px(img, img_h, img_w, d, sy1, sx1, c) * a1;
+        int v = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2;
+        v = v < 0 ? 0 : (v > 255 ? 255 : v);
+        o[c] = (uint8_t)v;
+    }
+}
+
+// grid (tiles of the chunk, n_ch): tile list entry (crop, tile of the crop); crops [crop0, ...) are images crop - crop0 of `maps`.
+// The smoothed tile is pp_smooth.h's (do_nms = keep_smoothed = 0: no pruning, nothing stored); the block leaves the arg-max record of
+// its 32 x 32 outputs (row-major indices of the crop's map) at rec[tile * n_ch + ch].
+template <int R>
+__global__ __launch_bounds__(256) void kp_tiles_kernel(PPMaps maps, const KpCrop* __restrict__ crops, const int2* __restrict__ tiles,
+                                                       int tile0, int crop0, int n_ch, ArgMax* __restrict__ rec)
+{
+    PP_SMOOTH_FAST_DECL(R)
+    __shared__ ArgMax sred[4];
+
+    const int tid = threadIdx.x;
+    const int ch = blockIdx.y;
+    const int2 tl = tiles[tile0 + blockIdx.x];
+    const PPTables tab = crops[tl.x].tab;
+    const int map_h = crops[tl.x].h, map_w = crops[tl.x].w, tiles_x = crops[tl.x].tiles_x;
+    const int b = tl.x - crop0;
+    const int ty = tl.y / tiles_x, tx = tl.y - ty * tiles_x;
+    const int y0 = ty * PK_TS, x0 = tx * PK_TS;
+    const int keep_smoothed = 0, do_nms = 0;
+    PPBuffers buf{};
+
+    PP_SMOOTH_FAST_BODY(R)
+
+    ArgMax a;
+    a.v = -INFINITY; a.cnt = 0; a.i0 = INT_MAX; a.i1 = INT_MAX;
+    for (int i = tid; i < PK_TS * PK_TS; i += 256) {
+        const int r = i / PK_TS, c = i - r * PK_TS;
+        const int y = y0 + r, x = x0 + c;
+        if (y < map_h && x < map_w) {
+            const float v = sS[(r + 1) * SW + (c + 1)];
+            const int idx = y * map_w + x;
+            if (v > a.v) { a.v = v; a.cnt = 1; a.i0 = idx; a.i1 = INT_MAX; }
+            else if (v == a.v) {
+                a.cnt += 1;
+                if (idx < a.i0) { a.i1 = a.i0; a.i0 = idx; } else if (idx < a.i1) a.i1 = idx;
+            }
+        }
+    }
+    const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        ArgMax o;
+        o.v = __shfl_xor(a.v, off); o.cnt = __shfl_xor(a.cnt, off); o.i0 = __shfl_xor(a.i0, off); o.i1 = __shfl_xor(a.i1, off);
+        a = argmax_merge(a, o);
+    }
+    if (lane == 0) sred[wave] = a;
+    __syncthreads();
+    if (tid == 0) {
+        ArgMax r = sred[0];
+        for (int w = 1; w < 4; ++w) r = argmax_merge(r, sred[w]);
+        rec[(long long)(tile0 + blockIdx.x) * n_ch + ch] = r;
+    }
+}
+
+// grid (n_ch, crops): merge the tile records of (crop, channel) and write the key point row exactly as pp_argmax_kernel does
+__global__ __launch_bounds__(256) void kp_merge_kernel(const ArgMax* __restrict__ rec, const KpCrop* __restrict__ crops,
+                                                       const int* __restrict__ tile_end, int n_ch, double thresh, double* __restrict__ out)
+{
+    __shared__ ArgMax sred[4];
+    const int ch = blockIdx.x, k = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int t0 = crops[k].tile0, t1 = tile_end[k], map_w = crops[k].w;
+    ArgMax a;
+    a.v = -INFINITY; a.cnt = 0; a.i0 = INT_MAX; a.i1 = INT_MAX;
+    for (int t = t0 + tid; t < t1; t += 256) a = argmax_merge(a, rec[(long long)t * n_ch + ch]);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        ArgMax o;
+        o.v = __shfl_xor(a.v, off); o.cnt = __shfl_xor(a.cnt, off); o.i0 = __shfl_xor(a.i0, off); o.i1 = __shfl_xor(a.i1, off);
+        a = argmax_merge(a, o);
+    }
+    if (lane == 0) sred[wave] = a;
+    __syncthreads();
+    if (tid == 0) {
+        ArgMax r = sred[0];
+        for (int w = 1; w < 4; ++w) r = argmax_merge(r, sred[w]);
+        double* o = out + ((long long)k * n_ch + ch) * 4;
+        const bool valid = (double)r.v > thresh;        // np.float32 scalar > python float: float64 comparison
+        int x = r.i0 % map_w, y = r.i0 / map_w;
+        if (r.cnt >= 2) { x = r.i1 / map_w; }            // (sic) coords[1] is the SECOND maximum's row when k >= 2 (pp_argmax_kernel)
+        o[0] = valid ? (double)x : 0.0;
+        o[1] = valid ? (double)y : 0.0;
+        o[2] = (double)r.v;
+        o[3] = valid ? 1.0 : 0.0;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------ host
+// the staging of one call, built on the host, copied in one piece; offsets are bytes from the start
+struct Stage {
+    std::vector<char> h;
+    size_t put(const void* p, size_t bytes)
+    {
+        const size_t off = (h.size() + 15) / 16 * 16;
+        h.resize(off + bytes);
+        if (bytes) memcpy(h.data() + off, p, bytes);
+        return off;
+    }
+    size_t reserve(size_t bytes) { const size_t off = (h.size() + 15) / 16 * 16; h.resize(off + bytes); return off; }
+};
+
+template <class T>
+int grow(pmx_ctx* c, T** p, size_t* cap, size_t bytes)
+{
+    if (bytes <= *cap) return PMX_OK;
+    PMX_HIP(hipStreamSynchronize(c->stream));      // (queued work may still read the old buffer)
+    if (*p) (void)hipFree(*p);
+    *p = nullptr; *cap = 0;
+    PMX_HIP(hipMalloc((void**)p, bytes));
+    *cap = bytes;
+    return PMX_OK;
+}
+
+// one H2D copy of the staging; the device copy is valid for the kernels enqueued after it on the context's stream
+int stage_upload(pmx_ctx* c, const Stage& st)
+{
+    const size_t bytes = st.h.size();
+    if (!bytes) return PMX_OK;
+    if (c->bx_pending) { PMX_HIP(hipEventSynchronize(c->bx_copied)); c->bx_pending = false; }     // the pinned buffer is free again
+    if (bytes > c->bx_host_cap) {
+        if (c->bx_host) (void)hipHostFree(c->bx_host);
+        c->bx_host = nullptr; c->bx_host_cap = 0;
+        PMX_HIP(hipHostMalloc((void**)&c->bx_host, bytes, hipHostMallocDefault));
+        c->bx_host_cap = bytes;
+    }
+    int rc;
+    if ((rc = grow(c, &c->bx_dev, &c->bx_dev_cap, bytes))) return rc;
+    if (!c->bx_copied) PMX_HIP(hipEventCreateWithFlags(&c->bx_copied, hipEventDisableTiming));
+    memcpy(c->bx_host, st.h.data(), bytes);
+    PMX_HIP(hipMemcpyAsync(c->bx_dev, c->bx_host, bytes, hipMemcpyHostToDevice, c->stream));
+    PMX_HIP(hipEventRecord(c->bx_copied, c->stream));
+    c->bx_pending = true;
+    return PMX_OK;
+}
+
+int check_boxes(const int* boxes, int n)
+{
+    PMX_CHECK(n >= 0, PMX_ERR_INVALID, "boxes: n = %d", n);
+    PMX_CHECK(n == 0 || boxes, PMX_ERR_INVALID, "boxes: null pointer");
+    for (int i = 0; i < n; ++i) {
+        const int* b = boxes + 5 * i;
+        const long long w = (long long)b[2] - b[0], h = (long long)b[3] - b[1];
+        PMX_CHECK(w >= 1 && h >= 1, PMX_ERR_INVALID, "box %d: empty (left %d, top %d, right %d, bottom %d)", i, b[0], b[1], b[2], b[3]);
+        PMX_CHECK(w <= INT_MAX && h <= INT_MAX && w * h < (1ll << 31), PMX_ERR_INVALID, "box %d: extent %lld x %lld outside int32", i, w, h);
+        PMX_CHECK(b[4] == 0 || b[4] == 1, PMX_ERR_INVALID, "box %d: flip must be 0 or 1 (got %d)", i, b[4]);
+    }
+    return PMX_OK;
+}
+
+// gather + resize tables of n boxes (staged) -> offsets of the descriptors and tables
+void stage_boxes(Stage& st, const int* boxes, int n, int dh, int dw, size_t* desc_off, size_t* tab_off)
+{
+    std::vector<BoxDesc> d(n);
+    std::vector<int> tabs((size_t)n * 4 * (dw + dh));
+    for (int i = 0; i < n; ++i) {
+        const int* b = boxes + 5 * i;
+        d[i] = BoxDesc{b[0], b[1], b[2] - b[0], b[3] - b[1], b[4], 0, 0, 0};
+        int* t = tabs.data() + (size_t)i * 4 * (dw + dh);
+        pmx_make_resize_table(dw, d[i].w, t);
+        pmx_make_resize_table(dh, d[i].h, t + 4 * dw);
+    }
+    *desc_off = st.put(d.data(), d.size() * sizeof(BoxDesc));
+    *tab_off = st.put(tabs.data(), tabs.size() * sizeof(int));
+}
+
+// key-point tables of n crops (h, w, flip): KpCrop[n] (device pointers relative to the staging's device copy), the flat tile list, the
+// per-crop tile ends and the up-sampling grids
+struct KpStage { size_t crops_off = 0, tiles_off = 0, ends_off = 0; int n_tiles = 0; std::vector<int> crop_tile0; };
+
+void stage_keypoints(pmx_ctx* c, Stage& st, const int* hwf, int n, int in_h, int in_w, KpStage* ks)
+{
+    // grids first (their offsets go into the KpCrop records), then the records and the tile list
+    std::vector<int> i0, i1; std::vector<double> lo, hi;
+    std::vector<KpCrop> crops(n);
+    std::vector<int2> tiles;
+    std::vector<int> ends(n);
+    const size_t g_off = st.put(c->gauss.data(), c->gauss.size() * sizeof(double));
+    std::vector<size_t> offs(n * 8);
+    for (int k = 0; k < n; ++k) {
+        const int h = hwf[3 * k], w = hwf[3 * k + 1], flip = hwf[3 * k + 2];
+        pmx_make_upsample_grid(in_w, w, i0, i1, lo, hi);
+        if (flip) {       // column x of the mirrored map = column w - 1 - x of the resized one (pmx_ensure_tables)
+            std::reverse(i0.begin(), i0.end()); std::reverse(i1.begin(), i1.end());
+            std::reverse(lo.begin(), lo.end()); std::reverse(hi.begin(), hi.end());
+        }
+        size_t* o = &offs[8 * k];
+        o[0] = st.put(i0.data(), w * sizeof(int)); o[1] = st.put(i1.data(), w * sizeof(int));
+        o[2] = st.put(lo.data(), w * sizeof(double)); o[3] = st.put(hi.data(), w * sizeof(double));
+        pmx_make_upsample_grid(in_h, h, i0, i1, lo, hi);
+        o[4] = st.put(i0.data(), h * sizeof(int)); o[5] = st.put(i1.data(), h * sizeof(int));
+        o[6] = st.put(lo.data(), h * sizeof(double)); o[7] = st.put(hi.data(), h * sizeof(double));
+        const int tx = (w + PK_TS - 1) / PK_TS, ty = (h + PK_TS - 1) / PK_TS;
+        crops[k].h = h; crops[k].w = w; crops[k].tiles_x = tx; crops[k].tile0 = (int)tiles.size();
+        for (int t = 0; t < tx * ty; ++t) tiles.push_back(make_int2(k, t));
+        ends[k] = (int)tiles.size();
+    }
+    ks->crops_off = st.reserve(n * sizeof(KpCrop));
+    ks->tiles_off = st.put(tiles.data(), tiles.size() * sizeof(int2));
+    ks->ends_off = st.put(ends.data(), ends.size() * sizeof(int));
+    ks->n_tiles = (int)tiles.size();
+    ks->crop_tile0.resize(n + 1);
+    for (int k = 0; k < n; ++k) ks->crop_tile0[k] = crops[k].tile0;
+    ks->crop_tile0[n] = ks->n_tiles;
+    // the device pointers of the grids are filled in once the device buffer is known (stage_fix_pointers)
+    char* dev = nullptr;     // placeholder base: offsets only; fixed up below
+    for (int k = 0; k < n; ++k) {
+        const size_t* o = &offs[8 * k];
+        PPTables& t = crops[k].tab;
+        t.xi0 = reinterpret_cast<int*>(dev + o[0]); t.xi1 = reinterpret_cast<int*>(dev + o[1]);
+        t.xlo = reinterpret_cast<double*>(dev + o[2]); t.xhi = reinterpret_cast<double*>(dev + o[3]);
+        t.yi0 = reinterpret_cast<int*>(dev + o[4]); t.yi1 = reinterpret_cast<int*>(dev + o[5]);
+        t.ylo = reinterpret_cast<double*>(dev + o[6]); t.yhi = reinterpret_cast<double*>(dev + o[7]);
+        t.gauss = reinterpret_cast<double*>(dev + g_off);
+        t.radius = ((int)c->gauss.size() - 1) / 2; t.border_zero = 0; t.nms_ge = 0;
+    }
+    memcpy(st.h.data() + ks->crops_off, crops.data(), n * sizeof(KpCrop));
+}
+
+// the staged KpCrop records hold offsets: add the device base (before the upload)
+int stage_fix_pointers(pmx_ctx* c, Stage& st, const KpStage& ks, int n)
+{
+    int rc;
+    if ((rc = grow(c, &c->bx_dev, &c->bx_dev_cap, st.h.size()))) return rc;
+    KpCrop* k = reinterpret_cast<KpCrop*>(st.h.data() + ks.crops_off);
+    const uintptr_t base = reinterpret_cast<uintptr_t>(c->bx_dev);
+    for (int i = 0; i < n; ++i) {
+        PPTables& t = k[i].tab;
+        t.xi0 = reinterpret_cast<int*>(base + reinterpret_cast<uintptr_t>(t.xi0)); t.xi1 = reinterpret_cast<int*>(base + reinterpret_cast<uintptr_t>(t.xi1));
+        t.xlo = reinterpret_cast<double*>(base + reinterpret_cast<uintptr_t>(t.xlo)); t.xhi = reinterpret_cast<double*>(base + reinterpret_cast<uintptr_t>(t.xhi));
+        t.yi0 = reinterpret_cast<int*>(base + reinterpret_cast<uintptr_t>(t.yi0)); t.yi1 = reinterpret_cast<int*>(base + reinterpret_cast<uintptr_t>(t.yi1));
+        t.ylo = reinterpret_cast<double*>(base + reinterpret_cast<uintptr_t>(t.ylo)); t.yhi = reinterpret_cast<double*>(base + reinterpret_cast<uintptr_t>(t.yhi));
+        t.gauss = reinterpret_cast<double*>(base + reinterpret_cast<uintptr_t>(t.gauss));
+    }
+    return PMX_OK;
+}
+
+// the current network maps (uniform batch) as the post-process sees them (pmx_keypoints)
+PPMaps current_maps(pmx_ctx* c)
+{
+    const long long fhw = (long long)c->cur_fh * c->cur_fw;
+    PPMaps m;
+    if (c->maps_external) {
+        m.heat = c->ext_heat; m.paf = nullptr; m.sx = 1; m.sy = c->cur_fw; m.sc = fhw; m.sbh = c->n_heat * fhw; m.sbp = 0;
+    } else {
+        m.heat = c->cat + c->cat_heat; m.paf = nullptr; m.sc = 1; m.sx = c->cat_c; m.sy = (long long)c->cur_fw * c->cat_c;
+        m.sbh = fhw * c->cat_c; m.sbp = 0;
+    }
+    m.fh = c->cur_fh; m.fw = c->cur_fw;
+    return m;
+}
+
+bool kp_fast(pmx_ctx* c)
+{
+    return c->gauss.size() == 21 && !c->opt_gpu_branch_peaks && !pp_get_generic();
+}
+
+// key points of crops [k0, k0 + B) of the call, on the current maps (images 0 .. B - 1): enqueue only
+int kp_enqueue_chunk(pmx_ctx* c, const KpStage& ks, const int* hwf, int k0, int B, double thresh)
+{
+    const int n_ch = c->n_heat - 1;
+    const PPMaps m = current_maps(c);
+    int rc;
+    if (kp_fast(c)) {
+        const int t0 = ks.crop_tile0[k0], t1 = ks.crop_tile0[k0 + B];
+        if ((rc = pmx_prof_begin(c, "kp_boxes|kp_tiles_kernel", (double)m.sbh * 4 * B))) return rc;
+        hipLaunchKernelGGL(kp_tiles_kernel<10>, dim3(t1 - t0, n_ch), dim3(256), 0, c->stream, m,
+                           reinterpret_cast<const KpCrop*>(c->bx_dev + ks.crops_off), reinterpret_cast<const int2*>(c->bx_dev + ks.tiles_off),
+                           t0, k0, n_ch, static_cast<ArgMax*>(c->bx_rec));
+        PMX_HIP(hipGetLastError());
+        return pmx_prof_end(c);
+    }
+    // fallback: one crop at a time through the post-process's own key-point launch (tables per crop, smoothed map materialised)
+    for (int k = k0; k < k0 + B; ++k) {
+        const int h = hwf[3 * k], w = hwf[3 * k + 1], flip = hwf[3 * k + 2];
+        if ((rc = pmx_ensure_tables(c, c->cur_fh, c->cur_fw, h, w, flip))) return rc;
+        const size_t need = (size_t)n_ch * h * w;      // (smoothed_cap counts floats, pmx_keypoints)
+        if (need > c->smoothed_cap) {
+            PMX_HIP(hipStreamSynchronize(c->stream));
+            if (c->pp.smoothed) (void)hipFree(c->pp.smoothed);
+            c->pp.smoothed = nullptr; c->smoothed_cap = 0;
+            PMX_HIP(hipMalloc((void**)&c->pp.smoothed, need * sizeof(float)));
+            c->smoothed_cap = need;
+        }
+        PPMaps mk = m;
+        mk.heat = m.heat + (long long)(k - k0) * m.sbh;
+        if ((rc = pp_keypoints_launch(mk, c->tab, c->pp, 1, n_ch, h, w, thresh, c->d_kp + (size_t)k * n_ch * 4, c->stream))) return rc;
+    }
+    return PMX_OK;
+}
+
+int kp_prepare(pmx_ctx* c, Stage& st, const int* hwf, int n, KpStage* ks)
+{
+    const int n_ch = c->n_heat - 1;
+    int rc;
+    for (int k = 0; k < n; ++k)
+        PMX_CHECK(hwf[3 * k] >= 1 && hwf[3 * k + 1] >= 1 && (long long)hwf[3 * k] * hwf[3 * k + 1] < (1ll << 31) &&
+                  (hwf[3 * k + 2] == 0 || hwf[3 * k + 2] == 1), PMX_ERR_INVALID, "key points: crop %d has a bad (h, w, flip) = (%d, %d, %d)",
+                  k, hwf[3 * k], hwf[3 * k + 1], hwf[3 * k + 2]);
+    stage_keypoints(c, st, hwf, n, c->cur_fh, c->cur_fw, ks);
+    const size_t nkp = (size_t)n * n_ch * 4;
+    if (nkp > c->kp_cap) {
+        PMX_HIP(hipStreamSynchronize(c->stream));
+        if (c->d_kp) (void)hipFree(c->d_kp);
+        c->d_kp = nullptr; c->kp_cap = 0;
+        PMX_HIP(hipMalloc((void**)&c->d_kp, nkp * sizeof(double)));
+        c->kp_cap = nkp;
+    }
+    if (kp_fast(c) && (rc = grow(c, &c->bx_rec, &c->bx_rec_cap, (size_t)ks->n_tiles * n_ch * sizeof(ArgMax)))) return rc;
+    return PMX_OK;
+}
+
+int kp_finish(pmx_ctx* c, const KpStage& ks, int n, double thresh, double* out)
+{
+    const int n_ch = c->n_heat - 1;
+    int rc;
+    if (kp_fast(c)) {
+        if ((rc = pmx_prof_begin(c, "kp_boxes|kp_merge_kernel", (double)ks.n_tiles * n_ch * sizeof(ArgMax)))) return rc;
+        hipLaunchKernelGGL(kp_merge_kernel, dim3(n_ch, n), dim3(256), 0, c->stream, static_cast<const ArgMax*>(c->bx_rec),
+                           reinterpret_cast<const KpCrop*>(c->bx_dev + ks.crops_off), reinterpret_cast<const int*>(c->bx_dev + ks.ends_off),
+                           n_ch, thresh, c->d_kp);
+        PMX_HIP(hipGetLastError());
+        if ((rc = pmx_prof_end(c))) return rc;
+    }
+    PMX_HIP(hipMemcpyAsync(out, c->d_kp, (size_t)n * n_ch * 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    PMX_HIP(hipStreamSynchronize(c->stream));
+    return PMX_OK;
+}
+
+// the image on the device (uploaded once per call unless it already is there)
+int image_on_device(pmx_ctx* c, const uint8_t* img, int img_h, int img_w, int on_device, const uint8_t** d)
+{
+    PMX_CHECK(img && img_h >= 1 && img_w >= 1, PMX_ERR_INVALID, "boxes: bad image (%d x %d)", img_h, img_w);
+    if (on_device) { *d = img; return PMX_OK; }
+    const size_t nsrc = (size_t)img_h * img_w * 3;
+    int rc;
+    if ((rc = grow(c, &c->u8_src, &c->u8_src_cap, nsrc))) return rc;
+    PMX_HIP(hipMemcpyAsync(c->u8_src, img, nsrc, hipMemcpyHostToDevice, c->stream));
+    c->pr_src = nullptr;      // (u8_src no longer holds a detect_precise original)
+    *d = c->u8_src;
+    return PMX_OK;
+}
+
+// gather + resize of boxes [k0, k0 + B) into u8_tmp, then the network
+int forward_chunk(pmx_ctx* c, const uint8_t* d_img, int img_h, int img_w, size_t desc_off, size_t tab_off, int k0, int B)
+{
+    const int dh = c->max_h, dw = c->max_w;
+    int rc;
+    const long long npix = (long long)B * dh * dw;
+    if ((rc = pmx_prof_begin(c, "resize_boxes|box_gather_resize_u8_kernel", (double)npix * 3 * 2))) return rc;
+    hipLaunchKernelGGL(box_gather_resize_u8_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, c->stream, d_img, img_h, img_w,
+                       reinterpret_cast<const BoxDesc*>(c->bx_dev + desc_off) + k0,
+                       reinterpret_cast<const int*>(c->bx_dev + tab_off) + (size_t)k0 * 4 * (dw + dh), B, dh, dw, c->u8_tmp);
+    PMX_HIP(hipGetLastError());
+    if ((rc = pmx_prof_end(c))) return rc;
+    return pmx_forward_u8(c, c->u8_tmp, B, dh, dw, 1);
+}
+
+}  // namespace
+
+void pmx_boxes_free(pmx_ctx* c)
+{
+    if (c->bx_host) (void)hipHostFree(c->bx_host);
+    if (c->bx_dev) (void)hipFree(c->bx_dev);
+    if (c->bx_rec) (void)hipFree(c->bx_rec);
+    if (c->bx_copied) (void)hipEventDestroy(c->bx_copied);
+    c->bx_host = nullptr; c->bx_dev = nullptr; c->bx_rec = nullptr; c->bx_copied = nullptr;
+    c->bx_host_cap = c->bx_dev_cap = c->bx_rec_cap = 0;
+    c->bx_pending = false;
+}
+
+extern "C" int pmx_forward_u8_boxes(pmx_ctx* c, const uint8_t* img, int img_h, int img_w, int on_device, const int* boxes, int n)
+{
+    PMX_CHECK(c, PMX_ERR_INVALID, "null ctx");
+    PMX_CHECK(c->kind != NET_POSE, PMX_ERR_STATE, "pmx_forward_u8_boxes: facenet / handnet only");
+    PMX_CHECK(n >= 1 && n <= c->max_batch, PMX_ERR_CAPACITY, "pmx_forward_u8_boxes: %d boxes outside 1..%d", n, c->max_batch);
+    int rc;
+    if ((rc = check_boxes(boxes, n))) return rc;
+    PMX_CHECK(img && img_h >= 1 && img_w >= 1, PMX_ERR_INVALID, "pmx_forward_u8_boxes: bad image (%d x %d)", img_h, img_w);
+    PMX_DEV(c);
+    Stage st;
+    size_t desc_off, tab_off;
+    stage_boxes(st, boxes, n, c->max_h, c->max_w, &desc_off, &tab_off);
+    const uint8_t* d = nullptr;
+    if ((rc = image_on_device(c, img, img_h, img_w, on_device, &d))) return rc;
+    if ((rc = stage_upload(c, st))) return rc;
+    return forward_chunk(c, d, img_h, img_w, desc_off, tab_off, 0, n);
+}
+
+extern "C" int pmx_keypoints_images(pmx_ctx* c, int B, const int* hwf, double thresh, double* out)
+{
+    PMX_CHECK(c && hwf && out, PMX_ERR_INVALID, "null arg");
+    PMX_CHECK(c->kind != NET_POSE, PMX_ERR_STATE, "pmx_keypoints_images: facenet / handnet only");
+    PMX_CHECK(c->maps_valid && B == c->cur_B && B >= 1, PMX_ERR_STATE, "pmx_keypoints_images: no network output for batch %d", B);
+    PMX_CHECK(c->cur_segs.empty(), PMX_ERR_STATE, "pmx_keypoints_images: the current maps are those of a mixed-size batch");
+    PMX_DEV(c);
+    int rc;
+    Stage st;
+    KpStage ks;
+    if ((rc = kp_prepare(c, st, hwf, B, &ks))) return rc;
+    if ((rc = stage_fix_pointers(c, st, ks, B))) return rc;
+    if ((rc = stage_upload(c, st))) return rc;
+    if ((rc = kp_enqueue_chunk(c, ks, hwf, 0, B, thresh))) return rc;
+    return kp_finish(c, ks, B, thresh, out);
+}
+
+extern "C" int pmx_keypoints_boxes(pmx_ctx* c, const uint8_t* img, int img_h, int img_w, int on_device, const int* boxes, int n,
+                                   double thresh, double* out)
+{
+    PMX_CHECK(c, PMX_ERR_INVALID, "null ctx");
+    PMX_CHECK(c->kind != NET_POSE, PMX_ERR_STATE, "pmx_keypoints_boxes: facenet / handnet only");
+    int rc;
+    if ((rc = check_boxes(boxes, n))) return rc;
+    if (n == 0) return PMX_OK;
+    PMX_CHECK(out, PMX_ERR_INVALID, "pmx_keypoints_boxes: null output");
+    PMX_CHECK(img && img_h >= 1 && img_w >= 1, PMX_ERR_INVALID, "pmx_keypoints_boxes: bad image (%d x %d)", img_h, img_w);
+    if ((rc = pmx_check_weights(c))) return rc;
+    PMX_DEV(c);
+    const int fh = c->max_h / 8, fw = c->max_w / 8;      // the maps of a max_h x max_w input
+    std::vector<int> hwf(3 * (size_t)n);
+    for (int i = 0; i < n; ++i) {
+        hwf[3 * i] = boxes[5 * i + 3] - boxes[5 * i + 1]; hwf[3 * i + 1] = boxes[5 * i + 2] - boxes[5 * i]; hwf[3 * i + 2] = boxes[5 * i + 4];
+    }
+    Stage st;
+    size_t desc_off, tab_off;
+    stage_boxes(st, boxes, n, c->max_h, c->max_w, &desc_off, &tab_off);
+    KpStage ks;
+    {
+        // kp_prepare builds the grids against the maps' size: that of the forward below
+        const int sh = c->cur_fh, sw = c->cur_fw;
+        c->cur_fh = fh; c->cur_fw = fw;
+        rc = kp_prepare(c, st, hwf.data(), n, &ks);
+        c->cur_fh = sh; c->cur_fw = sw;
+        if (rc) return rc;
+    }
+    if ((rc = stage_fix_pointers(c, st, ks, n))) return rc;
+    const uint8_t* d = nullptr;
+    if ((rc = image_on_device(c, img, img_h, img_w, on_device, &d))) return rc;
+    if ((rc = stage_upload(c, st))) return rc;
+    for (int k0 = 0; k0 < n; k0 += c->max_batch) {
+        const int B = n - k0 < c->max_batch ? n - k0 : c->max_batch;
+        if ((rc = forward_chunk(c, d, img_h, img_w, desc_off, tab_off, k0, B))) return rc;
+        PMX_CHECK(c->cur_fh == fh && c->cur_fw == fw, PMX_ERR_STATE, "pmx_keypoints_boxes: maps of %d x %d, expected %d x %d", c->cur_fh, c->cur_fw, fh, fw);
+        if ((rc = kp_enqueue_chunk(c, ks, hwf.data(), k0, B, thresh))) return rc;
+    }
+    return kp_finish(c, ks, n, thresh, out);
+}

@@ -284,6 +284,7 @@ struct PPBuffers {
 #define PMX_LDS_SUBSETS 896         // subset rows in the LDS fast path (20 doubles each, dynamic LDS: 140 KB at most; the initial capacity is 128)
 #define PMX_LDS_USED 4096           // peaks per joint type whose "used" flags fit the LDS fast path
 void pp_set_generic(int on);
+int pp_get_generic();      // the "pp_generic" ablation switch (pmx_boxes.hip falls back to per-crop pp_keypoints_launch under it)
 int pp_keypoints_launch(const PPMaps& maps, const PPTables& tab, const PPBuffers& buf, int B, int n_ch, int map_h, int map_w,
                         double thresh, double* d_out, hipStream_t stream);
 int pp_launch(const PPMaps& maps, const PPTables& tab, const PPBuffers& buf, int B, int map_h, int map_w,

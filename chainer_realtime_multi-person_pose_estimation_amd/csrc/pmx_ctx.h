@@ -178,6 +178,12 @@ struct pmx_ctx {
     std::vector<ProfPending> pending;
     std::vector<hipEvent_t> ev_pool;   // recycled events (creating two per launch inside the timed region costs ~0.5 %)
     int prof_open = -1;
+    // pmx_boxes.hip (key points for many boxes of one image): the per-call staging (resize tables, crop / tile tables, up-sampling grids) goes
+    // over in ONE copy from pinned memory; `bx_copied` marks when the host side may be rewritten.  Per-tile arg-max records of the key points.
+    char* bx_host = nullptr; size_t bx_host_cap = 0;
+    hipEvent_t bx_copied = nullptr; bool bx_pending = false;
+    char* bx_dev = nullptr; size_t bx_dev_cap = 0;
+    void* bx_rec = nullptr; size_t bx_rec_cap = 0;
 };
 
 #define PMX_DEV(c) PMX_HIP(hipSetDevice((c)->device))
@@ -190,4 +196,10 @@ int pmx_forward_from_in16(pmx_ctx* c, int B, int H, int W);      // the network 
 int pmx_ensure_tables(pmx_ctx* c, int in_h, int in_w, int out_h, int out_w, int flip_x = 0);   // up-sampling tables of the post-process
 PPBuffers pmx_pp_view(const PPBuffers& p, int base);         // the post-process buffers of the images [base, ...) (every per-image array offset)
 void pmx_make_resize_table(int dst, int src, int* tab);      // OpenCV INTER_LINEAR uint8 table of one axis: [idx0 | idx1 | coef0 | coef1] x dst
-int pmx_check_weights(pmx_ctx* c);                            // PMX_ERR_WEIGHTS unless every layer has weights
+int pmx_check_weights(pmx_ctx* c);
+// corner-aligned up-sampling grid of one axis (F.resize_images, np.linspace semantics): the tables pmx_ensure_tables uploads
+void pmx_make_upsample_grid(int in, int out, std::vector<int>& i0, std::vector<int>& i1, std::vector<double>& lo, std::vector<double>& hi);
+int pmx_prof_begin(pmx_ctx* c, const char* name, double bytes);   // per-launch profiler (option 1 only) around one launch
+int pmx_prof_end(pmx_ctx* c);
+// pmx_boxes.hip
+void pmx_boxes_free(pmx_ctx* c);                            // PMX_ERR_WEIGHTS unless every layer has weights

@@ -3,6 +3,8 @@ the same MI355X conv kernels as the pose network (single-branch CPM, models/Face
 
     FaceDetector(arch='facenet', weights_file=None, model=None, device=-1)(face_img, fast_mode=False) -> 70 key points
     HandDetector(arch='handnet', weights_file=None, model=None, device=-1)(hand_img, fast_mode=False, hand_type="right") -> 21
+    FaceDetector.detect_boxes(img, bboxes) / HandDetector.detect_boxes(img, bboxes, hand_types) -> one such list per box of ONE image
+    detect_person_parts(pose_detector, face_detector, hand_detector, img, poses) -> the face / hand key points of every person (demo.py)
 
 A key point is `[x, y, confidence]` (ints, np.float32) or `None` when the smoothed maximum does not exceed the threshold,
 in the pixel frame of the crop that was passed in -- exactly the reference's return value.  The whole path runs on the
@@ -23,20 +25,59 @@ class _KeypointDetector(object):
     SIZE_KEY = None
     THRESH_KEY = None
 
-    def __init__(self, arch=None, weights_file=None, model=None, device=-1, weights=None):
+    def __init__(self, arch=None, weights_file=None, model=None, device=-1, weights=None, max_batch=16):
         self.arch = arch or self.ARCH
         if self.arch != self.ARCH:
             raise ValueError('%s needs arch=%r' % (type(self).__name__, self.ARCH))
+        if int(max_batch) < 1:
+            raise ValueError('max_batch must be >= 1')
         self.device = device
         self.model = model if callable(model) else None
         w = model if isinstance(model, dict) else weights
         if w is None and weights_file:
             w = weights_mod.load_npz(weights_file, self.ARCH)          # serializers.load_npz (face_detector.py:16)
+        self._weights = w
+        self.max_batch = int(max_batch)       # what detect_boxes may grow the engine to; __call__ alone keeps the batch-1 engine
+        self.engine = None
+        self._cap = 0
+        self._make_engine(1)
+
+    def _make_engine(self, batch):
+        # as PoseDetector._make_engine: the state (weights, options, stream, capacities) is taken from the old context, which is destroyed
+        # BEFORE the larger one is created; a failed growth rebuilds the previous context and re-raises
+        st = None
+        if self.engine is not None:
+            st = self.engine.state()
+            self.engine.close()
+            self.engine = None
+        try:
+            self.engine = self._new_engine(batch, st)
+        except Exception:
+            self.engine = None
+            if st is not None:
+                self.engine = self._new_engine(self._cap, st)
+            raise
+        self._cap = batch
+
+    def _new_engine(self, batch, st):
         size = params[self.SIZE_KEY]
-        self.engine = native.Engine(device if device >= 0 else 0, max_batch=1, max_h=size, max_w=size,
-                                    gaussian_sigma=params['gaussian_sigma'], arch=self.ARCH)
-        if w is not None:
-            self.engine.set_weights(w)
+        eng = native.Engine(self.device if self.device >= 0 else 0, max_batch=batch, max_h=size, max_w=size,
+                            gaussian_sigma=params['gaussian_sigma'], arch=self.ARCH)
+        try:
+            if st is not None:
+                eng.load_state(st)
+            elif self._weights is not None:
+                eng.set_weights(self._weights)
+        except Exception:
+            eng.close()
+            raise
+        return eng
+
+    def _grow(self, n):
+        """More boxes than the engine's batch: re-create it for min(n, max_batch) crops (larger calls run in chunks of that)."""
+        want = min(n, self.max_batch)
+        if want > self._cap:
+            self._make_engine(want)
 
     def _detect(self, img, flip_maps=False):
         img = np.ascontiguousarray(img, dtype=np.uint8)
@@ -53,10 +94,56 @@ class _KeypointDetector(object):
             self.engine.set_heat(np.asarray(getattr(hs[-1], 'data', hs[-1]), dtype=np.float32))
         self.engine.set_option('kp_flip_x', int(flip_maps))               # cv2.flip(heatmaps, 1) for left hands (hand_detector.py:46-47)
         kp = self.engine.keypoints(h, w, params[self.THRESH_KEY])[0]      # F.resize_images + peaks (:37-38)
-        out = []
-        for x, y, conf, valid in kp:
-            out.append([int(x), int(y), np.float32(conf)] if valid else None)
-        return out
+        return _keypoint_list(kp)
+
+    def _detect_boxes(self, img, bboxes, flips):
+        """Key points of many boxes of ONE image, one list per box: what `self._detect(crop_image(img, box)[, ::-1])` returns for it.
+        All crops are cut, mirrored and resized on the device and run through the network as one batch (chunks of the engine's batch)."""
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError('detect_boxes needs one uint8 H x W x 3 image')
+        boxes = [(int(b[0]), int(b[1]), int(b[2]), int(b[3]), int(f)) for b, f in zip(bboxes, flips)]
+        if len(boxes) != len(bboxes):
+            raise ValueError('one hand type per box')
+        for i, b in enumerate(boxes):          # (the library checks too; here before the engine may grow)
+            if b[2] <= b[0] or b[3] <= b[1]:
+                raise native.PmxError(1, 'box %d: empty (left %d, top %d, right %d, bottom %d)' % ((i,) + b[:4]))
+        if not boxes:
+            return []
+        thresh = params[self.THRESH_KEY]
+        if self.model is None:
+            if self.engine.weights_missing():
+                raise RuntimeError('%s has no weights: pass weights_file=, weights= or model=' % type(self).__name__)
+            self._grow(len(boxes))
+            kps = self.engine.keypoints_boxes(img, boxes, thresh)
+        else:
+            # `model=` seam: crops resized on the device one by one, the callable per crop (as __call__), the key points of all maps in
+            # one pmx_keypoints_images call
+            from .pose_detector import PoseDetector
+            size = params[self.SIZE_KEY]
+            heats = []
+            for b in boxes:
+                crop = PoseDetector.crop_image(None, img, b[:4])
+                if b[4]:
+                    crop = crop[:, ::-1]
+                resized = self.engine.resize_u8(np.ascontiguousarray(crop)[None], size, size)[0]
+                x = np.array(resized[np.newaxis], dtype=np.float32).transpose(0, 3, 1, 2) / 256 - 0.5
+                hs = self.model(x)
+                heats.append(np.asarray(getattr(hs[-1], 'data', hs[-1]), dtype=np.float32)[0])
+            kps = []
+            for k0 in range(0, len(boxes), self.max_batch):
+                chunk = boxes[k0:k0 + self.max_batch]
+                self._grow(len(chunk))
+                self.engine.set_heat(np.stack(heats[k0:k0 + self.max_batch]))
+                kps.extend(self.engine.keypoints_images([(b[3] - b[1], b[2] - b[0], b[4]) for b in chunk], thresh))
+        return [_keypoint_list(kp) for kp in kps]
+
+
+def _keypoint_list(kp):
+    out = []
+    for x, y, conf, valid in kp:
+        out.append([int(x), int(y), np.float32(conf)] if valid else None)
+    return out
 
 
 class FaceDetector(_KeypointDetector):
@@ -65,6 +152,11 @@ class FaceDetector(_KeypointDetector):
     def __call__(self, face_img, fast_mode=False):
         """reference face_detector.py:28-40 (`fast_mode` is unused there as well)"""
         return self._detect(face_img)
+
+    def detect_boxes(self, img, bboxes):
+        """`[self(PoseDetector.crop_image(img, bbox)) for bbox in bboxes]` in one batched call (boxes (left, top, right, bottom) in image
+        pixels, zero padding outside the image): one list of 70 key points (or None) per box, in the box's own pixel frame."""
+        return self._detect_boxes(img, bboxes, [0] * len(bboxes))
 
 
 class HandDetector(_KeypointDetector):
@@ -78,6 +170,13 @@ class HandDetector(_KeypointDetector):
         if hand_type == "left":
             return self._detect(hand_img[:, ::-1], flip_maps=True)
         return self._detect(hand_img)
+
+    def detect_boxes(self, img, bboxes, hand_types):
+        """`[self(PoseDetector.crop_image(img, bbox), hand_type=t) for bbox, t in zip(bboxes, hand_types)]` in one batched call: a left
+        hand's crop is mirrored on the device, its maps mirrored back."""
+        if len(hand_types) != len(bboxes):
+            raise ValueError('one hand type per box')
+        return self._detect_boxes(img, bboxes, [1 if t == "left" else 0 for t in hand_types])
 
 
 # ---- visualisation / crop helpers of the reference modules (host-only; cv2.circle / cv2.line rasters are stand-ins) -----------
@@ -131,3 +230,43 @@ def crop_face(img, rect):
     out = np.zeros((edge, edge, face.shape[2]), dtype=np.uint8)
     out[:face.shape[0], :face.shape[1]] = face
     return out, (left, top)
+
+
+# ---- demo.py:30-55 for all people of an image at once ---------------------------------------------------------------------------------
+def _serial_box_check(bbox):
+    """The exception the serial chain raises for a box with no pixels: crop_image's np.zeros for a negative extent, the library for an
+    empty crop."""
+    if bbox[2] - bbox[0] < 0 or bbox[3] - bbox[1] < 0:
+        raise ValueError('negative dimensions are not allowed')
+    if bbox[2] == bbox[0] or bbox[3] == bbox[1]:
+        raise native.PmxError(1, 'empty crop %r' % (tuple(bbox),))
+
+
+def detect_person_parts(pose_detector, face_detector, hand_detector, img, poses):
+    """What the reference demo's loop (demo.py:30-55) computes for every person, with ONE detect_boxes call per detector (two network
+    calls however many people).  Per person: {'unit_length', 'face': {'bbox', 'keypoints'} | None, 'left': ..., 'right': ...}.
+    Works on a copy of `poses` (the reference's crop_hands moves the wrists in place); every box is computed, and every error the loop
+    would raise (e.g. int(nan) for a person without a measurable limb) is raised, before anything runs on the device."""
+    poses = np.array(poses, copy=True)
+    persons, face_boxes, face_owner, hand_boxes, hand_types, hand_owner = [], [], [], [], [], []
+    for p, pose in enumerate(poses):
+        unit = pose_detector.get_unit_length(pose)                       # demo.py:32
+        rec = {'unit_length': unit, 'face': None, 'left': None, 'right': None}
+        fb = pose_detector.face_bbox(pose, unit)                          # :36
+        if fb is not None:
+            _serial_box_check(fb)
+            face_boxes.append(fb)
+            face_owner.append(p)
+        hb = pose_detector.hand_bboxes(pose, unit)                        # :44
+        for side in ('left', 'right'):
+            if hb[side] is not None:
+                _serial_box_check(hb[side])
+                hand_boxes.append(hb[side])
+                hand_types.append(side)
+                hand_owner.append((p, side))
+        persons.append(rec)
+    for p, bbox, kps in zip(face_owner, face_boxes, face_detector.detect_boxes(img, face_boxes)):
+        persons[p]['face'] = {'bbox': bbox, 'keypoints': kps}
+    for (p, side), bbox, kps in zip(hand_owner, hand_boxes, hand_detector.detect_boxes(img, hand_boxes, hand_types)):
+        persons[p][side] = {'bbox': bbox, 'keypoints': kps}
+    return persons

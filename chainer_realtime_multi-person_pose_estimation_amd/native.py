@@ -26,13 +26,13 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB_PATH = os.path.join(CSRC, 'libpose_mi355x.so')
 HEADER = os.path.join(os.path.dirname(HERE), 'include', 'pose_mi355x.h')
 SOURCES = [('pmx_api.hip', []), ('pmx_precise.hip', []), ('pmx_multi.hip', []), ('conv_mfma.hip', []), ('conv_wino.hip', ['-mllvm', '-pragma-unroll-threshold=200000']), ('conv1_wino.hip', []), ('conv_select.hip', []), ('prep.hip', ['-ffp-contract=off']),
-           ('postproc.hip', ['-ffp-contract=off'])]
+           ('postproc.hip', ['-ffp-contract=off']), ('pmx_boxes.hip', ['-ffp-contract=off'])]
 # the opt-in bf16x3 kernels (option "precision" = 1; DESIGN.md 4.1.5: frozen, slower than the fp32 Winograd path) are NOT part of the
 # default library: PMX_BUILD_BF16X3=1 in the environment of the build adds their translation unit (the stamp then differs, so the
 # library is rebuilt when the variable changes)
 if os.environ.get('PMX_BUILD_BF16X3', '') not in ('', '0'):
     SOURCES.append(('conv_bf16x3.hip', []))
-HEADERS = ['pmx_common.h', 'pmx_ctx.h', 'wino_util.h', 'conv_direct.h', HEADER]
+HEADERS = ['pmx_common.h', 'pmx_ctx.h', 'wino_util.h', 'conv_direct.h', 'pp_smooth.h', HEADER]
 
 N_JOINTS, N_LIMBS, N_PAF, N_HEAT = 18, 19, 38, 19
 # initial capacities of a context (PMX_INIT_* in the header); they grow on demand, results are never truncated
@@ -243,6 +243,9 @@ def load():
         'pmx_create': (ci, [C.POINTER(vp), ci, ci, ci, ci]),
         'pmx_create_net': (ci, [C.POINTER(vp), C.c_char_p, ci, ci, ci, ci]),
         'pmx_keypoints': (ci, [vp, ci, ci, ci, cd, vp]),
+        'pmx_forward_u8_boxes': (ci, [vp, vp, ci, ci, ci, vp, ci]),
+        'pmx_keypoints_images': (ci, [vp, ci, vp, cd, vp]),
+        'pmx_keypoints_boxes': (ci, [vp, vp, ci, ci, ci, vp, ci, cd, vp]),
         'pmx_precise_begin': (ci, [vp, ci, ci]),
         'pmx_precise_add_scale': (ci, [vp, vp, ci, ci]),
         'pmx_precise_finish': (ci, [vp]),
@@ -507,6 +510,43 @@ class Engine(object):
         out = np.empty((self._B, self.n_heat - 1, 4), np.float64)
         self._check(self.lib.pmx_keypoints(self._ctx, self._B, int(out_h), int(out_w), float(thresh), _ptr(out)))
         self._map = (int(out_h), int(out_w))
+        return out
+
+    # ---- face / hand key points for many boxes of one image (pmx_forward_u8_boxes / pmx_keypoints_images / pmx_keypoints_boxes) ----
+    @staticmethod
+    def _boxes(boxes):
+        """(n, 5) int32 rows (left, top, right, bottom, flip); ValueError for values outside int32."""
+        b = np.asarray(boxes, dtype=np.int64).reshape(-1, 5)
+        if b.size and (b.min() < -2 ** 31 or b.max() > 2 ** 31 - 1):
+            raise ValueError('box coordinates outside int32')
+        return np.ascontiguousarray(b, dtype=np.int32)
+
+    def forward_u8_boxes(self, img, boxes):
+        """img (H, W, 3) uint8 BGR; boxes (n, 5): every box cropped (zero outside the image), mirrored where flip, resized to
+        max_h x max_w on the device, then the network at batch n (n <= max_batch).  get_resized(max_h, max_w) reads the input back."""
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        b = self._boxes(boxes)
+        self._check(self.lib.pmx_forward_u8_boxes(self._ctx, _ptr(img), img.shape[0], img.shape[1], 0, _ptr(b), len(b)))
+        self._B = len(b)
+        self._fhw = (self.max_h // 8, self.max_w // 8)
+
+    def keypoints_images(self, hwf, thresh):
+        """keypoints() for the B current maps, each with its own (out_h, out_w, flip): (B, maps - 1, 4) float64."""
+        hwf = np.ascontiguousarray(np.asarray(hwf, dtype=np.int64).reshape(-1, 3), dtype=np.int32)
+        out = np.empty((len(hwf), self.n_heat - 1, 4), np.float64)
+        self._check(self.lib.pmx_keypoints_images(self._ctx, len(hwf), _ptr(hwf), float(thresh), _ptr(out)))
+        return out
+
+    def keypoints_boxes(self, img, boxes, thresh):
+        """The one-call form: (n, maps - 1, 4) float64 key-point rows, in each box's own pixel frame."""
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        b = self._boxes(boxes)
+        out = np.empty((len(b), self.n_heat - 1, 4), np.float64)
+        self._check(self.lib.pmx_keypoints_boxes(self._ctx, _ptr(img), img.shape[0], img.shape[1], 0, _ptr(b), len(b), float(thresh),
+                                                 _ptr(out)))
+        if len(b):
+            self._B = min(len(b) - (len(b) - 1) // self.max_batch * self.max_batch, self.max_batch)
+            self._fhw = (self.max_h // 8, self.max_w // 8)
         return out
 
     def set_maps(self, paf, heat):

@@ -349,6 +349,29 @@ class PoseDetector(object):
                 hands[side] = {"img": hand_img, "bbox": bbox}
         return hands
 
+    def face_bbox(self, person_pose, unit_length):
+        """The box crop_face cuts, without the pixels: (left, top, right, bottom) or None when the nose is not visible."""
+        nose = person_pose[JointType.Nose]
+        if not nose[2] > 0:
+            return None
+        return (int(nose[0] - unit_length), int(nose[1] - unit_length * 1.2),
+                int(nose[0] + unit_length), int(nose[1] + unit_length * 0.8))
+
+    def hand_bboxes(self, person_pose, unit_length):
+        """The boxes crop_hands cuts, without the pixels: {"left": box | None, "right": box | None}.  Unlike crop_hands (and the
+        reference) the pose is NOT modified: the moved wrist is a copy."""
+        boxes = {"left": None, "right": None}
+        for side, wrist_j, elbow_j in (("left", JointType.LeftHand, JointType.LeftElbow),
+                                       ("right", JointType.RightHand, JointType.RightElbow)):
+            if person_pose[wrist_j][2] > 0:
+                center = np.array(person_pose[wrist_j][:-1], copy=True)
+                if person_pose[elbow_j][2] > 0:
+                    center += (0.3 * (person_pose[wrist_j][:-1] - person_pose[elbow_j][:-1])).astype(center.dtype)
+                x, y = center
+                crop_size = unit_length * 0.95
+                boxes[side] = (int(x - crop_size), int(y - crop_size), int(x + crop_size), int(y + crop_size))
+        return boxes
+
     def detect_batch(self, imgs):
         """Batched `__call__`: list of H x W x 3 uint8 BGR images -> list of (poses, scores), one per image in the order given (the
         reference handles one image per call).  Images of ONE common size run as a uniform batch; images of DIFFERENT sizes (the

@@ -227,6 +227,24 @@ int pmx_precise_table_stats(pmx_ctx* ctx, int* cached, int* trims);
  * float64 rows (x, y, confidence, valid); valid = 0 where the reference appends None.  Synchronises. */
 int pmx_keypoints(pmx_ctx* ctx, int batch, int out_h, int out_w, double thresh, double* out);
 
+/* ---- face / hand key points for many boxes of ONE image (demo.py:30-55: per person a face crop and two hand crops) ------------------
+ * facenet / handnet contexts.  boxes: n x 5 int32 (left, top, right, bottom, flip) in image pixels; a box may extend past the image (those
+ * pixels are 0: PoseDetector.crop_image, pose_detector.py:401-424); flip = 1 mirrors the crop left-right (cv2.flip(img, 1) of a left hand,
+ * hand_detector.py:29-30).  Every box must be non-empty with int32 extents, else PMX_ERR_INVALID naming the box, before anything runs.
+ * The network input is the context's max_h x max_w (368 x 368 for the detectors): per box crop + mirror + cv2.resize INTER_LINEAR, the same
+ * bytes as crop_image (+ [:, ::-1]) followed by pmx_forward_u8_resized.  img: img_h x img_w x 3 uint8 BGR, host (uploaded once per call;
+ * read before the call returns) or device memory (on_device != 0).
+ * pmx_forward_u8_boxes: gather + resize + forward of n <= max_batch boxes (pmx_get_resized reads the network input back); asynchronous. */
+int pmx_forward_u8_boxes(pmx_ctx* ctx, const uint8_t* img, int img_h, int img_w, int on_device, const int* boxes, int n);
+/* pmx_keypoints for the B images of the current maps (a forward or pmx_set_maps), each with its own output size and mirror:
+ * out_hwf: B x 3 int32 (out_h, out_w, flip); out as pmx_keypoints (B x (maps - 1) x 4 float64).  Bit-identical per image to pmx_keypoints with
+ * that size and option "kp_flip_x" = flip.  Synchronises. */
+int pmx_keypoints_images(pmx_ctx* ctx, int batch, const int* out_hwf, double thresh, double* out);
+/* the one-call form: boxes -> key points in each box's own pixel frame (out: n x (maps - 1) x 4 float64, as pmx_keypoints), in chunks of
+ * max_batch enqueued back to back; one image upload, one D2H copy and one stream synchronisation per call.  n == 0: nothing, PMX_OK. */
+int pmx_keypoints_boxes(pmx_ctx* ctx, const uint8_t* img, int img_h, int img_w, int on_device, const int* boxes, int n,
+                        double thresh, double* out);
+
 /* fused: forward_u8 + postprocess (PoseDetector.__call__, pose_detector.py:484-517, for images already
  * at the network input size; cv2.resize at :493 is the identity for them) */
 int pmx_detect_batch(pmx_ctx* ctx, const uint8_t* bgr_nhwc, int batch, int h, int w, int on_device,
