@@ -176,6 +176,32 @@ static void pack_bf16x3(const std::vector<float>& wp, int T, int nch, int cout_p
             }
 }
 
+// fp32 -> f16 bits, round-to-nearest-even, saturating at +-65504 (the f16 mode's f16(v): conv_f16_kernel rounds the activations the same
+// way); NaN stays NaN
+static inline uint16_t f16_rn_sat(float x)
+{
+    uint32_t u;
+    memcpy(&u, &x, 4);
+    const uint32_t sign = (u >> 16) & 0x8000u, ax = u & 0x7fffffffu;
+    if (ax > 0x7f800000u) return (uint16_t)(sign | 0x7e00u);
+    if (ax >= 0x477fe000u) return (uint16_t)(sign | 0x7bffu);          // |x| >= 65504 (and what would round above it): the largest finite
+    if (ax < 0x38800000u) {                                             // below 2^-14: subnormal f16 (or zero), in units of 2^-24
+        if (ax < 0x33000000u) return (uint16_t)sign;                    // below 2^-25: rounds to zero (2^-25 itself is the tie -> even = 0)
+        const uint32_t e = ax >> 23, m = (ax & 0x7fffffu) | 0x800000u;
+        const uint32_t shift = 126 - e;                                 // value = m * 2^(e - 150) = (m >> (126 - e)) * 2^-24
+        const uint32_t q = m >> shift, rem = m & ((1u << shift) - 1), half = 1u << (shift - 1);
+        return (uint16_t)(sign | (q + (rem > half || (rem == half && (q & 1)))));
+    }
+    const uint32_t r = ax + 0xfffu + ((ax >> 13) & 1u);                 // round the 23-bit mantissa to 10 bits (a carry bumps the exponent)
+    return (uint16_t)(sign | (((r >> 13) - (112u << 10)) & 0x7fffu));
+}
+// packed fp32 weights [tap][chunk][cout_pad][16] -> f16 in the same layout (so the concat channel map comes along)
+static void pack_f16(const std::vector<float>& wp, std::vector<uint16_t>& out)
+{
+    out.resize(wp.size());
+    for (size_t i = 0; i < wp.size(); ++i) out[i] = f16_rn_sat(wp[i]);
+}
+
 static std::vector<int> identity_map(int cin)
 {
     std::vector<int> m(round_up(cin, CK), -1);
@@ -413,7 +439,7 @@ extern "C" void pmx_destroy(pmx_ctx* c)
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
     pmx_boxes_free(c);
-    for (auto& l : c->layers) { if (l.d_w) (void)hipFree(l.d_w); if (l.d_b) (void)hipFree(l.d_b); if (l.d_w3) (void)hipFree(l.d_w3); if (l.d_ww) (void)hipFree(l.d_ww); }
+    for (auto& l : c->layers) { if (l.d_w) (void)hipFree(l.d_w); if (l.d_b) (void)hipFree(l.d_b); if (l.d_w3) (void)hipFree(l.d_w3); if (l.d_w16) (void)hipFree(l.d_w16); if (l.d_ww) (void)hipFree(l.d_ww); }
     pp_free(c);
     void* ptrs[] = {c->sk_scratch, c->sk_zero_bias, c->pr_tmp, c->d_kp, c->u8_src, c->rs_tab, c->in16, c->act0, c->act1, c->cat, c->brA, c->brB, c->brT, c->nchw_tmp, c->u8_tmp, c->ext_paf, c->ext_heat,
                     c->pp.smoothed, c->d_scale, c->tab.xi0, c->tab.xi1, c->tab.xlo, c->tab.xhi, c->tab.yi0, c->tab.yi1,
@@ -481,7 +507,9 @@ extern "C" int pmx_set_option(pmx_ctx* c, const char* key, int value)
     else if (!strcmp(key, "precise_table_cap")) c->opt_precise_table_cap = value < 1 ? 1 : value;
     else if (!strcmp(key, "cubic_rows")) prep_set_cubic_rows(value);      // (process-wide, like the other kernel-form switches of prep / post-process)
     else if (!strcmp(key, "precision")) {
-        PMX_CHECK(value == 0 || conv_bf16x3_launch != nullptr, PMX_ERR_INVALID,
+        PMX_CHECK(value >= 0 && value <= 2, PMX_ERR_INVALID,
+                  "pmx_set_option: \"precision\" = %d: 0 (fp32), 1 (bf16x3, opt-in build) or 2 (f16 mode)", value);
+        PMX_CHECK(value != 1 || conv_bf16x3_launch != nullptr, PMX_ERR_INVALID,
                   "pmx_set_option: \"precision\" = %d needs the opt-in bf16x3 kernels, which this build does not carry (rebuild with PMX_BUILD_BF16X3=1)", value);
         c->opt_precision = value;
     }
@@ -530,6 +558,7 @@ extern "C" int pmx_set_layer(pmx_ctx* c, const char* name, const float* w, const
     // the bf16x3 pack (1.5x the fp32 weights) and the Winograd pack (16/9 x for 3x3, 81/49 x for 7x7) are derived from the packed fp32
     // weights on first use (ensure_*_pack): a context that never runs those kernels neither holds nor computes them
     if (L.d_w3) { (void)hipFree(L.d_w3); L.d_w3 = nullptr; }
+    if (L.d_w16) { (void)hipFree(L.d_w16); L.d_w16 = nullptr; }
     if (L.d_ww) { (void)hipFree(L.d_ww); L.d_ww = nullptr; }
     L.set = true; L.cin = cin; L.cout = cout; L.ks = ks;
     L.cin_pad = (int)cmap.size(); L.cout_pad = cpad; L.nch = L.cin_pad / CK;
@@ -613,6 +642,25 @@ static int ensure_bf16x3_pack(PackedLayer& L)
         return PMX_ERR_HIP;
     }
     L.d_w3 = d;
+    return PMX_OK;
+}
+
+// the f16 pack (half the fp32 weights' bytes): every 3x3 / 7x7 layer in f16 mode
+static int ensure_f16_pack(PackedLayer& L)
+{
+    if (L.d_w16) return PMX_OK;
+    std::vector<float> wp;
+    std::vector<uint16_t> w16;
+    if (int rc = fetch_packed(L, wp)) return rc;
+    pack_f16(wp, w16);
+    void* d = nullptr;
+    PMX_HIP(hipMalloc(&d, w16.size() * sizeof(uint16_t)));
+    if (hipMemcpy(d, w16.data(), w16.size() * sizeof(uint16_t), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(d);
+        pmx_set_error("f16 weight pack: host-to-device copy failed: %s", hipGetErrorString(hipGetLastError()));
+        return PMX_ERR_HIP;
+    }
+    L.d_w16 = d;
     return PMX_OK;
 }
 
@@ -794,6 +842,51 @@ static int wino_mode(const pmx_ctx* c, int ks, int cin_pad, int cout_pad, int co
     return wino_select(wino_opts(c, ks, groups, lda), ks, cin_pad, cout_pad, cout, ldc, images, H, W, pool, unit_g, run, tail_g);
 }
 
+// f16 mode (option "precision" = 2): a 3x3 / 7x7 layer as ONE conv_f16_kernel launch, whatever the batch (no Winograd, no split-K, no cut by
+// images: the per-output summation order must not depend on the launch); heterogeneous forwards on the 8 x 16 rectangle table of the level
+static int run_conv_f16(pmx_ctx* c, const char* label, int li0, int li1, const float* in0, const float* in1, int lda,
+                        float* out0, float* out1, int ldc, int B, int H, int W, int relu, int pool, int level)
+{
+    const PackedLayer& L0 = c->layers[li0];
+    const int groups = li1 >= 0 ? 2 : 1;
+    const bool seg = !c->segs.empty() && level >= 0;
+    PMX_CHECK(c->segs.empty() || seg, PMX_ERR_INVALID, "heterogeneous forward: layer %s without a resolution level", label);
+    PMX_CHECK(groups == 1 || (c->layers[li1].ks == L0.ks && c->layers[li1].nch == L0.nch && c->layers[li1].cout_pad == L0.cout_pad), PMX_ERR_INVALID,
+              "conv f16: the two groups of %s differ in shape", label);
+    int rc;
+    if ((rc = ensure_f16_pack(c->layers[li0])) || (groups == 2 && (rc = ensure_f16_pack(c->layers[li1])))) return rc;
+    ConvArgs a;
+    memset(&a, 0, sizeof a);
+    a.g[0].in = in0; a.g[0].w = (const float*)L0.d_w16; a.g[0].bias = L0.d_b; a.g[0].out = out0; a.g[0].cout = L0.cout;
+    if (groups == 2) {
+        const PackedLayer& L1 = c->layers[li1];
+        a.g[1].in = in1; a.g[1].w = (const float*)L1.d_w16; a.g[1].bias = L1.d_b; a.g[1].out = out1; a.g[1].cout = L1.cout;
+    }
+    a.B = B; a.H = H; a.W = W; a.lda = lda; a.ldc = ldc; a.nch = L0.nch; a.cout_pad = L0.cout_pad; a.relu = relu; a.pool = pool;
+    long long tiles = (long long)B * ((H + 7) / 8) * ((W + 15) / 16);
+    if (seg) {
+        const int t = PMX_SEG_RECT(level, pool);
+        a.nseg = (int)c->segs.size(); a.segs = c->d_segs + (size_t)t * c->segs.size(); a.seg_tiles = c->seg_tiles[t];
+        tiles = a.seg_tiles;
+    }
+    const bool prof_this = c->prof_on == 1 || (c->prof_on == 2 && L0.ks == 7);
+    if (prof_this) {
+        const double npix = seg ? (double)c->seg_pix[level] : (double)B * H * W;
+        double flops = 0;
+        for (int g = 0; g < groups; ++g) {
+            const PackedLayer& L = c->layers[g ? li1 : li0];
+            flops += 2.0 * npix * (double)L.cout * L.cin * L.ks * L.ks;
+        }
+        // issued: every MFMA of the launch -- the tile padding of the map edges, the channel padding of cin and of the block's BN columns
+        const int bn = conv_f16_bn(L0.cout_pad, (int)std::min<long long>(tiles, 1 << 30), groups);
+        const double issued = 2.0 * (double)tiles * 128.0 * (double)round_up(L0.cout, bn) * (L0.nch * CK) * L0.ks * L0.ks * groups;
+        const double bytes = 4.0 * npix * ((double)L0.cin * groups + (double)L0.cout * groups / (pool ? 4 : 1));
+        if ((rc = prof_begin(c, std::string(label) + (L0.ks == 7 ? "|conv_f16_7x7" : "|conv_f16_3x3"), flops, bytes, issued))) return rc;
+    }
+    if ((rc = conv_f16_launch(L0.ks, a, groups, c->stream))) return rc;
+    return prof_this ? prof_end(c) : PMX_OK;
+}
+
 // one launch of 1 or 2 groups (same geometry); in/out pointers are already offset to the group's channels
 // `level` (heterogeneous forward only, c->segs non-empty): the resolution level of the layer's input, 0 = network input .. 3 = 1/8; B, H, W
 // then carry the image count and the LARGEST map of the level (launch checks), the geometry comes from the segment table of the level
@@ -803,6 +896,7 @@ static int run_conv(pmx_ctx* c, const char* label, int li0, int li1, const float
     const PackedLayer& L0 = c->layers[li0];
     const int groups = li1 >= 0 ? 2 : 1;
     const bool seg = !c->segs.empty() && level >= 0;
+    if (c->opt_precision == 2 && L0.ks > 1) return run_conv_f16(c, label, li0, li1, in0, in1, lda, out0, out1, ldc, B, H, W, relu, pool, level);
     // a batch whose plain launch would end in a part-filled round of the CUs: the images of the whole rounds first, then the rest through
     // the selection of THEIR count (conv_select.hip::wino_split_images); each half is an ordinary run_conv on its images
     if (!seg && c->split_suffix.empty() && c->opt_wino_split && B >= 2 && L0.ks > 1 && wino_eligible(L0.ks, L0.cin_pad, L0.cout_pad) &&
@@ -836,7 +930,7 @@ static int run_conv(pmx_ctx* c, const char* label, int li0, int li1, const float
     if (seg) {
         // heterogeneous launch: the plain Winograd kernel on 8 x 16 rectangles over all segments (every 3x3 / 7x7 layer of the pose network
         // qualifies; its per-pixel arithmetic is that of a plain launch of each image alone -- oracle/conv_fma_ref::conv_wino)
-        PMX_CHECK(wino_eligible(L0.ks, L0.cin_pad, L0.cout_pad) && c->opt_precision == 0 &&
+        PMX_CHECK(wino_eligible(L0.ks, L0.cin_pad, L0.cout_pad) && (c->opt_precision == 0 || c->opt_precision == 2) &&
                   (groups == 1 || (wino_eligible(c->layers[li1].ks, c->layers[li1].cin_pad, c->layers[li1].cout_pad) && c->layers[li1].cout == L0.cout)),
                   PMX_ERR_INVALID, "heterogeneous forward: layer %s has no Winograd form", label);
         if ((rc = ensure_wino_pack(c->layers[li0])) || (groups == 2 && (rc = ensure_wino_pack(c->layers[li1])))) return rc;
@@ -990,8 +1084,14 @@ static int run_conv1(pmx_ctx* c, int B, int H, int W)
     const uint8_t* in_u8 = c->in_u8;
     c->in_u8 = nullptr;                                   // (valid for this forward only)
     PMX_CHECK(!in_u8 || wino1, PMX_ERR_STATE, "conv1: a uint8 input without the kernel that preprocesses it");
-    PMX_CHECK(!seg || (wino1 && in_u8), PMX_ERR_INVALID, "heterogeneous forward: needs conv1 as conv1_wino_kernel on a uint8 input");
     int rc;
+    if (seg && c->opt_precision == 2) {
+        // f16 mode: pmx_forward_from_u8 has preprocessed the segments' pixels into in16; both layers on the level-0 rectangle tables
+        PMX_CHECK(!in_u8, PMX_ERR_STATE, "conv1: a uint8 input in f16 mode");
+        if ((rc = run_conv(c, "conv1_1", i1, -1, c->in16, nullptr, PMX_IN_C, c->act0, nullptr, 64, B, H, W, 1, 0, 0))) return rc;
+        return run_conv(c, "conv1_2", i2, -1, c->act0, nullptr, 64, c->act1, nullptr, 64, B, H, W, 1, 1, 0);
+    }
+    PMX_CHECK(!seg || (wino1 && in_u8), PMX_ERR_INVALID, "heterogeneous forward: needs conv1 as conv1_wino_kernel on a uint8 input");
     if (!fuse && !wino1) {
         if ((rc = run_conv(c, "conv1_1", i1, -1, c->in16, nullptr, PMX_IN_C, c->act0, nullptr, 64, B, H, W, 1, 0))) return rc;
         return run_conv(c, "conv1_2", i2, -1, c->act0, nullptr, 64, c->act1, nullptr, 64, B, H, W, 1, 1);
@@ -1174,6 +1274,17 @@ extern "C" int pmx_forward_u8(pmx_ctx* c, const uint8_t* img, int B, int H, int 
 int pmx_forward_from_u8(pmx_ctx* c, const uint8_t* d, int B, int H, int W, float divisor)
 {
     int rc;
+    if (!c->segs.empty() && c->opt_precision == 2) {
+        // f16 mode, heterogeneous forward: the segments' uint8 pixels lie end to end in `d` (forward_segments), so the preprocessing is one
+        // per-pixel pass over the flat run of seg_pix[0] pixels; conv1_1 then reads in16 through the level-0 rectangle table
+        const long long np0 = c->seg_pix[0];
+        PMX_CHECK(np0 >= 1 && np0 <= (long long)c->max_batch * c->max_h * c->max_w && np0 < (1ll << 31), PMX_ERR_CAPACITY,
+                  "heterogeneous forward: %lld input pixels", np0);
+        if (c->prof_on == 1 && (rc = prof_begin(c, "prep_u8|prep_u8", 0, (double)np0 * (3 + 64)))) return rc;
+        if ((rc = launch_prep_u8(d, c->in16, 1, 1, (int)np0, divisor, c->stream))) return rc;
+        if ((rc = prof_end(c))) return rc;
+        return pmx_forward_from_in16(c, B, H, W);
+    }
     if (!c->segs.empty() || conv1_form(c, B, H, W, nullptr)) {                // conv1_wino_kernel reads the uint8 pixels and preprocesses them in its patch load
         c->in_u8 = d; c->in_div = divisor;
         rc = pmx_forward_from_in16(c, B, H, W);
@@ -1910,11 +2021,19 @@ extern "C" int pmx_conv2d(pmx_ctx* c, const float* x, const float* w, const floa
         a.g[0].w = (const float*)d_w3;
         v_run = conv_bf16x3_twin(v);
     }
+    if (c->opt_precision == 2 && ks > 1) {          // f16 mode: the f16 kernel, whatever the shape
+        std::vector<uint16_t> w16;
+        pack_f16(wp, w16);
+        PMX_HIP(hipMalloc(&d_w3, w16.size() * sizeof(uint16_t)));
+        PMX_HIP(hipMemcpy(d_w3, w16.data(), w16.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+        a.g[0].w = (const float*)d_w3;
+    }
     SplitPlan plan = conv_pick_ksplit(v_run, H, W, B, 1, cpad, cin_pad / CK, pool, c->opt_ksplit);
     if (cout % 4 != 0) plan.S = 1;
     float* d_ww = nullptr;
     int ug = 0, wrun = 0, wtail = 0;
-    const int wmode = wino_mode(c, ks, cin_pad, cpad, cout, cout, B, H, W, pool, &ug, &wrun, &wtail, 1, a.lda);
+    const bool f16 = c->opt_precision == 2 && ks > 1;
+    const int wmode = f16 ? 0 : wino_mode(c, ks, cin_pad, cpad, cout, cout, B, H, W, pool, &ug, &wrun, &wtail, 1, a.lda);
     const bool wino = wmode == 1;
     if (wino) {
         std::vector<float> ww;
@@ -1931,6 +2050,7 @@ extern "C" int pmx_conv2d(pmx_ctx* c, const float* x, const float* w, const floa
         a.g[0].w = d_ww; a.nch = cin_pad / 32;
     }
     auto launch_conv = [&](pmx_ctx* cc, const ConvArgs& aa, int gg, int vv, const SplitPlan& pp) {
+        if (f16) return conv_f16_launch(ks, aa, gg, cc->stream);
         if (ug) return launch_wino_units(cc, aa, ks, gg, ug);
         if (wino && wrun) return launch_wino_run(cc, aa, ks, gg, wtail);
         return wino ? conv_wino_launch(aa, ks, gg, cc->stream) : ::launch_conv(cc, aa, gg, vv, pp);

@@ -20,6 +20,7 @@ struct PackedLayer {
     float* d_b = nullptr;
     float* d_ww = nullptr;       // Winograd F(2x2,3x3) pack [freq 16][chunk32][cout_pad][32] = G g G^T (3x3 layers; option "conv_algo" = 1)
     void* d_w3 = nullptr;        // bf16x3 pack [tap][chunk][plane hi|mid|lo][cout_pad][16] (3x3 / 7x7 layers; option "precision" = 1)
+    void* d_w16 = nullptr;       // f16 pack [tap][chunk][cout_pad][16] (3x3 / 7x7 layers; option "precision" = 2)
     int cin = 0, cout = 0, ks = 0, cin_pad = 0, cout_pad = 0, nch = 0;
 };
 
@@ -57,8 +58,12 @@ struct PrLane {
 // belong to which segment (pmx_common.h::ConvSeg).  Tables of one forward: conv1's 16 x 16 squares at level 0 (output = level 1), the
 // 8 x 16 rectangles of levels 1, 2 (un-pooled / pooled output) and 3.
 struct SegDesc { int n, H, W; };
-enum { PMX_SEG_CONV1 = 0, PMX_SEG_L1 = 1, PMX_SEG_L1P = 2, PMX_SEG_L2 = 3, PMX_SEG_L2P = 4, PMX_SEG_L3 = 5, PMX_SEG_TABLES = 6 };
-#define PMX_SEG_RECT(level, pool) ((level) == 1 ? ((pool) ? PMX_SEG_L1P : PMX_SEG_L1) : (level) == 2 ? ((pool) ? PMX_SEG_L2P : PMX_SEG_L2) : PMX_SEG_L3)
+// f16 mode (option "precision" = 2) runs conv1_1 / conv1_2 on 8 x 16 rectangles of level 0 as well: tables L0 (output at level 0) and L0P
+// (pooled: output at level 1).
+enum { PMX_SEG_CONV1 = 0, PMX_SEG_L1 = 1, PMX_SEG_L1P = 2, PMX_SEG_L2 = 3, PMX_SEG_L2P = 4, PMX_SEG_L3 = 5, PMX_SEG_L0 = 6, PMX_SEG_L0P = 7,
+       PMX_SEG_TABLES = 8 };
+#define PMX_SEG_RECT(level, pool) ((level) == 0 ? ((pool) ? PMX_SEG_L0P : PMX_SEG_L0) : (level) == 1 ? ((pool) ? PMX_SEG_L1P : PMX_SEG_L1) \
+                                   : (level) == 2 ? ((pool) ? PMX_SEG_L2P : PMX_SEG_L2) : PMX_SEG_L3)
 // one post-process launch set of the current results: a uniform batch is one call (base 0), a mixed batch one per segment
 struct PPCall { PPMaps maps; PPTables tab; int base, B, map_h, map_w; double img_len; bool has_scale; int limbs_slices; };
 
@@ -162,7 +167,8 @@ struct pmx_ctx {
     std::string split_suffix;        // run_conv inside a split: "@<first image>+<count>", appended to the profile labels
     int opt_wino_unit_g = 0;         // tuning: chunks per pass-1 unit of a launch in unit mode (0 = automatic, -1 = as many units as 8 slabs allow)
     int opt_precision = 0;           // 0: fp32 MFMA everywhere (the path whose results are specified); 1: bf16x3 kernels where a
-                                     // v6 kernel would run (fp32-grade accuracy at 2.67x the matrix rate, NOT the fp32 FMA chain)
+                                     // v6 kernel would run (fp32-grade accuracy at 2.67x the matrix rate, NOT the fp32 FMA chain);
+                                     // 2: f16 mode -- every 3x3 / 7x7 layer on conv_f16_kernel (f16 operands, fp32 sums; the 1x1 layers stay fp32)
     int opt_conv1_wino = 1;          // fused conv1_1 + conv1_2 with conv1_2 as Winograd F(2x2, 3x3) (conv1_wino_kernel) where conv_algo allows Winograd
     int opt_fuse_conv1 = 1;          // conv1_1 recomputed on conv1_2's halo tile, one launch (conv1_fused_kernel); identical bits
     int opt_fuse_pairs = 1;          // the two 1x1 layers that end every stage run as one launch (conv1x1_pair_kernel)

@@ -41,8 +41,8 @@ int build_seg_tables(pmx_ctx* c, const std::vector<Geo>& g)
     int tiles[PMX_SEG_TABLES] = {};
     for (size_t s = 0; s < ns; ++s) {
         for (int tab = 0; tab < PMX_SEG_TABLES; ++tab) {
-            const int level = tab == PMX_SEG_CONV1 ? 0 : tab <= PMX_SEG_L1P ? 1 : tab <= PMX_SEG_L2P ? 2 : 3;
-            const bool pooled = tab == PMX_SEG_CONV1 || tab == PMX_SEG_L1P || tab == PMX_SEG_L2P;
+            const int level = tab == PMX_SEG_CONV1 || tab == PMX_SEG_L0 || tab == PMX_SEG_L0P ? 0 : tab <= PMX_SEG_L1P ? 1 : tab <= PMX_SEG_L2P ? 2 : 3;
+            const bool pooled = tab == PMX_SEG_CONV1 || tab == PMX_SEG_L1P || tab == PMX_SEG_L2P || tab == PMX_SEG_L0P;
             const int th = tab == PMX_SEG_CONV1 ? 16 : 8, tw = 16;
             ConvSeg& q = t[tab * ns + s];
             q.H = g[s].H >> level; q.W = g[s].W >> level;

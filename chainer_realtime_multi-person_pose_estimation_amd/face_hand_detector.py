@@ -25,12 +25,15 @@ class _KeypointDetector(object):
     SIZE_KEY = None
     THRESH_KEY = None
 
-    def __init__(self, arch=None, weights_file=None, model=None, device=-1, weights=None, max_batch=16):
+    def __init__(self, arch=None, weights_file=None, model=None, device=-1, weights=None, max_batch=16, precision='f32'):
         self.arch = arch or self.ARCH
         if self.arch != self.ARCH:
             raise ValueError('%s needs arch=%r' % (type(self).__name__, self.ARCH))
         if int(max_batch) < 1:
             raise ValueError('max_batch must be >= 1')
+        if precision not in native.PRECISIONS:
+            raise ValueError('precision must be one of %s, got %r' % (', '.join(repr(p) for p in native.PRECISIONS), precision))
+        self._precision = precision
         self.device = device
         self.model = model if callable(model) else None
         w = model if isinstance(model, dict) else weights
@@ -68,6 +71,8 @@ class _KeypointDetector(object):
                 eng.load_state(st)
             elif self._weights is not None:
                 eng.set_weights(self._weights)
+            if self._precision != 'f32':
+                eng.set_option('precision', native.PRECISIONS[self._precision])
         except Exception:
             eng.close()
             raise

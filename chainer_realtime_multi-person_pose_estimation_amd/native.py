@@ -25,7 +25,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB_PATH = os.path.join(CSRC, 'libpose_mi355x.so')
 HEADER = os.path.join(os.path.dirname(HERE), 'include', 'pose_mi355x.h')
-SOURCES = [('pmx_api.hip', []), ('pmx_precise.hip', []), ('pmx_multi.hip', []), ('conv_mfma.hip', []), ('conv_wino.hip', ['-mllvm', '-pragma-unroll-threshold=200000']), ('conv1_wino.hip', []), ('conv_select.hip', []), ('prep.hip', ['-ffp-contract=off']),
+SOURCES = [('pmx_api.hip', []), ('pmx_precise.hip', []), ('pmx_multi.hip', []), ('conv_mfma.hip', []), ('conv_wino.hip', ['-mllvm', '-pragma-unroll-threshold=200000']), ('conv1_wino.hip', []), ('conv_f16.hip', []), ('conv_select.hip', []), ('prep.hip', ['-ffp-contract=off']),
            ('postproc.hip', ['-ffp-contract=off']), ('pmx_boxes.hip', ['-ffp-contract=off'])]
 # the opt-in bf16x3 kernels (option "precision" = 1; DESIGN.md 4.1.5: frozen, slower than the fp32 Winograd path) are NOT part of the
 # default library: PMX_BUILD_BF16X3=1 in the environment of the build adds their translation unit (the stamp then differs, so the
@@ -35,6 +35,8 @@ if os.environ.get('PMX_BUILD_BF16X3', '') not in ('', '0'):
 HEADERS = ['pmx_common.h', 'pmx_ctx.h', 'wino_util.h', 'conv_direct.h', 'pp_smooth.h', HEADER]
 
 N_JOINTS, N_LIMBS, N_PAF, N_HEAT = 18, 19, 38, 19
+# the detectors' precision= keyword -> engine option "precision" (include/pose_mi355x.h): fp32 (default), bf16x3 (opt-in build), f16 mode
+PRECISIONS = {'f32': 0, 'bf16x3': 1, 'f16': 2}
 # initial capacities of a context (PMX_INIT_* in the header); they grow on demand, results are never truncated
 INIT_PEAKS_PER_JOINT, INIT_SUBSETS, INIT_PEOPLE = 128, 128, 64
 SNAPSHOT_SLOTS = 4                             # PMX_SNAPSHOT_SLOTS: results_snapshot slots of a context

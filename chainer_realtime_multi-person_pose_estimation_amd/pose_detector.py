@@ -59,10 +59,12 @@ class PoseDetector(object):
         mh, mw = (size, size) if max_size is None else max_size
         self._weights = w
         self._gpu_branch_peaks = bool(gpu_branch_peaks)
-        if precision not in ('f32', 'bf16x3'):
-            raise ValueError("precision must be 'f32' (default: the fp32 arithmetic the parity tests specify) or 'bf16x3' (opt-in, frozen: "
-                             "3x3 / 7x7 layers on the bf16 matrix cores with three-term splits, fp32-grade accuracy, SLOWER than the fp32 "
-                             "Winograd path since round 5; needs a library built with PMX_BUILD_BF16X3=1)")
+        if precision not in native.PRECISIONS:
+            raise ValueError("precision must be one of %s, got %r: 'f32' (default: the fp32 arithmetic the parity tests specify), 'f16' (opt-in "
+                             "inference mode: 3x3 / 7x7 layers on the f16 matrix cores, f16 operands, fp32 sums; accuracy contract in "
+                             "INTEGRATION.md section 4) or 'bf16x3' (opt-in, frozen: 3x3 / 7x7 layers on the bf16 matrix cores with three-term "
+                             "splits, fp32-grade accuracy, SLOWER than the fp32 Winograd path since round 5; needs a library built with "
+                             "PMX_BUILD_BF16X3=1)" % (', '.join(repr(p) for p in native.PRECISIONS), precision))
         self._precision = precision
         self.engine = None
         self._make_engine(max_batch, mh, mw)
@@ -94,8 +96,8 @@ class PoseDetector(object):
                 eng.load_state(st)
             elif self._weights is not None:
                 eng.set_weights(self._weights)
-            if self._precision == 'bf16x3':
-                eng.set_option('precision', 1)
+            if self._precision != 'f32':
+                eng.set_option('precision', native.PRECISIONS[self._precision])
             if self._gpu_branch_peaks:
                 # the reference's own GPU branch of compute_peaks_from_heatmaps (:111-133): 17x17 un-normalised kernel, zero
                 # padding, '>=' NMS -- NOT the golden CPU semantics; off by default
@@ -618,8 +620,10 @@ def main(argv=None):
     parser.add_argument('--gpu', '-g', type=int, default=-1, help='GPU ID (negative value selects GPU 0: there is no CPU path)')
     parser.add_argument('--precise', action='store_true', help='do precise inference')
     parser.add_argument('--out', '-o', default='result.png', help='output image path')
+    parser.add_argument('--precision', choices=['f32', 'f16'], default='f32',
+                        help='f32 (default) or f16: the opt-in f16 inference mode (faster, accuracy contract in INTEGRATION.md section 4)')
     args = parser.parse_args(argv)
-    pose_detector = PoseDetector(args.arch, args.weights, device=args.gpu, precise=args.precise)
+    pose_detector = PoseDetector(args.arch, args.weights, device=args.gpu, precise=args.precise, precision=args.precision)
     img = imread_bgr(args.img)
     poses, _ = pose_detector(img)
     img = draw_person_pose(img, poses)

@@ -131,10 +131,19 @@ int pmx_synchronize(pmx_ctx* ctx);                    /* cuda.get_device_from_id
  *   "wino_tail_merge" 1 | 0    batches of 46-wide maps whose tail lies in one tile row (46 x 46: 17 tiles per image): 1 (default) = the
  *                              tails of all images of the launch as one stream of tiles, 32 per block (every MFMA row a real tile);
  *                              0 = one part-filled block per image.  Same units, same bits; profile label "...r/t<g>m"
- *   "precision" 0 | 1          0 (default): every convolution is the fp32 FMA chain the parity tests specify.  1: the 3x3 / 7x7
+ *   "precision" 0 | 1 | 2      0 (default): every convolution is the fp32 FMA chain the parity tests specify.  1: the 3x3 / 7x7
  *                              layers that run on the one-block-per-CU kernels use the bf16 matrix cores with every fp32 value
  *                              split into three bf16 terms (six products, fp32 accumulate): fp32-grade accuracy, 2.67x the
- *                              matrix rate, results equal to the fp32 path only to summation-order-sized noise
+ *                              matrix rate, results equal to the fp32 path only to summation-order-sized noise (opt-in build only).
+ *                              2: the f16 inference mode.  Every 3x3 / 7x7 layer (conv1_1 included; FaceNet / HandNet alike) runs on
+ *                              the f16 matrix cores: per output y = sum over (16-channel chunk, tap) of f16(x) * f16(w), summed in
+ *                              fp32 on v_mfma_f32_32x32x16_f16 in an order fixed per layer (chunk-major, taps row-major, no split-K),
+ *                              then the fp32 epilogue (2x2 max-pool, + bias, ReLU).  f16(v) = round-to-nearest-even saturating at
+ *                              +-65504 (no inf); weights are rounded once, on the host; activations stay fp32 in device memory and
+ *                              are rounded while a kernel stages them.  The 1x1 layers stay fp32.  The order does not depend on the
+ *                              batch, the image's position or the segment layout: an image gives the same maps bit for bit alone,
+ *                              anywhere in a uniform batch and inside a mixed-size batch (pmx_detect_images).  Accuracy against
+ *                              the fp32 path: INTEGRATION.md section 4.  Any other value: PMX_ERR_INVALID, the option unchanged
  *   "fuse_conv1" 1 | 0         conv1_1 recomputed on conv1_2's halo tiles, one launch instead of two (default 1); identical bits
  *   "precise_lanes" 1..4       detect_precise: inference scales in flight at once, each on its own stream and working set (default 4;
  *                              1: one after the other on the context's stream); same bits
