@@ -447,7 +447,7 @@ extern "C" void pmx_destroy(pmx_ctx* c)
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (auto& kv : c->pr_tabs) (void)hipFree(kv.second);
     for (auto& kv : c->tab_cache) (void)hipFree(kv.second.xi0);        // (one allocation per cached table set: pmx_multi.hip)
-    void* mptrs[] = {c->d_segs, c->mi_src, c->mi_tab};
+    void* mptrs[] = {c->d_segs, c->mi_src, c->mi_tab, c->pi_dev, c->pi_src, c->pi_tmp, c->pi_maps};
     for (void* p : mptrs) if (p) (void)hipFree(p);
     for (float* q : c->pr_part) if (q) (void)hipFree(q);
     for (int i = 1; i < PMX_PR_LANES; ++i) {
@@ -1483,6 +1483,22 @@ void pmx_make_upsample_grid(int in, int out, std::vector<int>& i0, std::vector<i
     make_grid(in, out, i0, i1, lo, hi);
 }
 
+void pmx_pp_gauss(const pmx_ctx* c, std::vector<double>& g, PPTables& t)
+{
+    if (c->opt_gpu_branch_peaks) {
+        // create_gaussian_kernel(sigma, ksize = 17) (pose_detector.py:38-44): 1/(2 pi sigma^2) exp(-d^2 / 2 sigma^2), NOT
+        // normalised to sum 1, applied as a 17x17 zero-padded convolution (:112-113); separable factor per axis
+        const int r = 8;
+        g.assign(2 * r + 1, 0.0);
+        const double s2 = PMX_GAUSS_SIGMA * PMX_GAUSS_SIGMA;
+        for (int i = -r; i <= r; ++i) g[i + r] = sqrt(1.0 / (s2 * 2.0 * M_PI)) * exp(-0.5 * (double)(i * i) / s2);
+        t.radius = r; t.border_zero = 1; t.nms_ge = 1;
+    } else {
+        g = c->gauss;
+        t.radius = ((int)c->gauss.size() - 1) / 2; t.border_zero = 0; t.nms_ge = 0;
+    }
+}
+
 int pmx_ensure_tables(pmx_ctx* c, int in_h, int in_w, int out_h, int out_w, int flip_x)
 {
     if (c->tab_in_h == in_h && c->tab_in_w == in_w && c->tab_out_h == out_h && c->tab_out_w == out_w && c->tab_flip == flip_x) return PMX_OK;
@@ -1515,19 +1531,9 @@ int pmx_ensure_tables(pmx_ctx* c, int in_h, int in_w, int out_h, int out_w, int 
     PMX_HIP(hipMemcpy(t.yi1, i1.data(), out_h * sizeof(int), hipMemcpyHostToDevice));
     PMX_HIP(hipMemcpy(t.ylo, lo.data(), out_h * sizeof(double), hipMemcpyHostToDevice));
     PMX_HIP(hipMemcpy(t.yhi, hi.data(), out_h * sizeof(double), hipMemcpyHostToDevice));
-    if (c->opt_gpu_branch_peaks) {
-        // create_gaussian_kernel(sigma, ksize = 17) (pose_detector.py:38-44): 1/(2 pi sigma^2) exp(-d^2 / 2 sigma^2), NOT
-        // normalised to sum 1, applied as a 17x17 zero-padded convolution (:112-113); separable factor per axis
-        const int r = 8;
-        std::vector<double> g(2 * r + 1);
-        const double s2 = PMX_GAUSS_SIGMA * PMX_GAUSS_SIGMA;
-        for (int i = -r; i <= r; ++i) g[i + r] = sqrt(1.0 / (s2 * 2.0 * M_PI)) * exp(-0.5 * (double)(i * i) / s2);
-        PMX_HIP(hipMemcpy(t.gauss, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice));
-        t.radius = r; t.border_zero = 1; t.nms_ge = 1;
-    } else {
-        PMX_HIP(hipMemcpy(t.gauss, c->gauss.data(), c->gauss.size() * sizeof(double), hipMemcpyHostToDevice));
-        t.radius = ((int)c->gauss.size() - 1) / 2; t.border_zero = 0; t.nms_ge = 0;
-    }
+    std::vector<double> g;
+    pmx_pp_gauss(c, g, t);
+    PMX_HIP(hipMemcpy(t.gauss, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice));
     c->tab_in_h = in_h; c->tab_in_w = in_w; c->tab_out_h = out_h; c->tab_out_w = out_w; c->tab_flip = flip_x;
     return PMX_OK;
 }

@@ -64,6 +64,8 @@ enum { PMX_SEG_CONV1 = 0, PMX_SEG_L1 = 1, PMX_SEG_L1P = 2, PMX_SEG_L2 = 3, PMX_S
        PMX_SEG_TABLES = 8 };
 #define PMX_SEG_RECT(level, pool) ((level) == 0 ? ((pool) ? PMX_SEG_L0P : PMX_SEG_L0) : (level) == 1 ? ((pool) ? PMX_SEG_L1P : PMX_SEG_L1) \
                                    : (level) == 2 ? ((pool) ? PMX_SEG_L2P : PMX_SEG_L2) : PMX_SEG_L3)
+// the host description of one segment: n images of network input H x W (mh x mw: the up-sampled map size of pmx_detect_images, else 0)
+struct SegGeo { int n, H, W, mh, mw; };
 // one post-process launch set of the current results: a uniform batch is one call (base 0), a mixed batch one per segment
 struct PPCall { PPMaps maps; PPTables tab; int base, B, map_h, map_w; double img_len; bool has_scale; int limbs_slices; };
 
@@ -79,6 +81,15 @@ struct pmx_ctx {
     std::map<std::tuple<int, int, int, int>, PPTables> tab_cache;   // up-sampling tables per (in_h, in_w, out_h, out_w) of the per-segment calls
     uint8_t* mi_src = nullptr; size_t mi_src_cap = 0;     // pmx_detect_images: original-size images awaiting the device resize
     int* mi_tab = nullptr; size_t mi_tab_cap = 0;         // ... and their resize tables
+    // pmx_detect_precise_images (pmx_precise_images.hip): per-call buffers, grown on demand and never keyed by size.  pi_dev holds the
+    // call's descriptors, cubic tables and post-process tables (ONE upload); it stays untouched until the next call, so a grow-and-re-run
+    // of the post-process (pp_calls) still finds its tables there.
+    char* pi_dev = nullptr; size_t pi_dev_cap = 0;
+    uint8_t* pi_src = nullptr; size_t pi_src_cap = 0;     // the original images, end to end
+    float* pi_tmp = nullptr; size_t pi_tmp_cap = 0;       // x8 up-sampled maps per (image, scale) pair, planar [57][ph][pw]
+    float* pi_maps = nullptr; size_t pi_maps_cap = 0;     // averaged full-resolution maps per image, planar [38 PAF | 19 heat][orig_h][orig_w]
+    std::vector<long long> pi_off;                        // first float of image i's maps in pi_maps
+    std::vector<int> pi_hw;                               // (orig_h, orig_w) of image i
     int kind = NET_POSE;             // architecture: posenet | facenet | handnet
     int n_heat = PMX_N_HEAT;         // heat-map channels of the last layer (19 | 71 | 22)
     int cat_c = PMX_CAT_C;           // channels of the cat buffer (192 | 208 | 160)
@@ -207,5 +218,14 @@ int pmx_check_weights(pmx_ctx* c);
 void pmx_make_upsample_grid(int in, int out, std::vector<int>& i0, std::vector<int>& i1, std::vector<double>& lo, std::vector<double>& hi);
 int pmx_prof_begin(pmx_ctx* c, const char* name, double bytes);   // per-launch profiler (option 1 only) around one launch
 int pmx_prof_end(pmx_ctx* c);
+// the Gaussian taps and border / NMS flags of the post-process tables (pmx_ensure_tables): taps -> g, the flags -> t
+void pmx_pp_gauss(const pmx_ctx* c, std::vector<double>& g, PPTables& t);
+// pmx_precise.hip: the cubic table of one axis for (src -> dst), 8 * dst ints [4 x dst indices | 4 x dst coefficients: float32 bits, or
+// OpenCV's 11-bit fixed point for the uint8 resize when `fixed`]
+void pmx_cubic_table(int src, int dst, bool fixed, int* out);
+// pmx_multi.hip: the segment tables of a forward -> device (synchronises the stream once), and the network over the segments whose uint8
+// pixels lie end to end at d_u8 (on the device)
+int build_seg_tables(pmx_ctx* c, const std::vector<SegGeo>& g);
+int forward_segments(pmx_ctx* c, const uint8_t* d_u8, const std::vector<SegGeo>& g, int B);
 // pmx_boxes.hip
 void pmx_boxes_free(pmx_ctx* c);                            // PMX_ERR_WEIGHTS unless every layer has weights

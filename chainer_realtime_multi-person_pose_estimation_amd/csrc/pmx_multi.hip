@@ -16,7 +16,7 @@
 
 namespace {
 
-struct Geo { int n, H, W, mh, mw; };       // a segment: n images, network input H x W, up-sampled map mh x mw
+using Geo = SegGeo;
 
 int seg_capacity_check(pmx_ctx* c, const std::vector<Geo>& g, int B)
 {
@@ -31,6 +31,8 @@ int seg_capacity_check(pmx_ctx* c, const std::vector<Geo>& g, int B)
               "mixed batch: %zu network-input pixels exceed the context capacity %d x %d x %d", px, c->max_batch, c->max_h, c->max_w);
     return PMX_OK;
 }
+
+}  // namespace
 
 // the six segment tables of a forward (pmx_ctx.h) -> device
 int build_seg_tables(pmx_ctx* c, const std::vector<Geo>& g)
@@ -73,6 +75,8 @@ int build_seg_tables(pmx_ctx* c, const std::vector<Geo>& g)
     PMX_HIP(hipStreamSynchronize(c->stream));
     return PMX_OK;
 }
+
+namespace {
 
 // up-sampling tables of one (network map, up-sampled map) size pair, built once per context and kept (a fresh allocation: nothing in
 // flight reads it; the cache is started over only by pmx_detect_images / pmx_postprocess_images behind a device synchronisation)
@@ -130,6 +134,8 @@ std::vector<Geo> segments_of(const int* net_hw, const int* map_hw, int B)
     return g;
 }
 
+}  // namespace
+
 // network forward over the segments; d_u8: the images' uint8 pixels end to end, on the device
 int forward_segments(pmx_ctx* c, const uint8_t* d_u8, const std::vector<Geo>& g, int B)
 {
@@ -144,8 +150,6 @@ int forward_segments(pmx_ctx* c, const uint8_t* d_u8, const std::vector<Geo>& g,
     if (rc) { c->cur_segs.clear(); c->maps_valid = false; }
     return rc;
 }
-
-}  // namespace
 
 // The network on a mixed batch.  bgr: the B images' uint8 BGR pixels end to end (image i: net_hw[2 i] x net_hw[2 i + 1] x 3), host or
 // device memory.  Consecutive images of one size form a segment.

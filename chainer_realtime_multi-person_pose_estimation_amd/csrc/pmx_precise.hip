@@ -36,6 +36,23 @@ static void make_cubic_table(int dst, int src, int* idx, float* coef)
     }
 }
 
+// The cubic table of ONE axis for (src -> dst) as the kernels read it: [4 dst indices | 4 dst coefficients (float32 bits, or 11-bit fixed
+// point when `fixed`)] = 8 * dst ints at `out`
+void pmx_cubic_table(int src, int dst, bool fixed, int* out)
+{
+    const size_t n = (size_t)4 * dst;
+    std::vector<float> hc(n);
+    make_cubic_table(dst, src, out, hc.data());
+    if (fixed) {
+        for (size_t k = 0; k < n; ++k) {
+            long v = lrintf(hc[k] * 2048.0f);              // saturate_cast<short>(coef * INTER_RESIZE_COEF_SCALE)
+            out[n + k] = (int)(v < -32768 ? -32768 : (v > 32767 ? 32767 : v));
+        }
+    } else {
+        memcpy(out + n, hc.data(), n * sizeof(float));
+    }
+}
+
 // Device copy of the cubic table of ONE axis for (src -> dst): [4 dst indices | 4 dst coefficients (float32, or 11-bit fixed point when
 // `fixed`)].  Tables are a pure function of (src, dst, fixed) and detect_precise asks for the same dozen on every call (4 scales x 3 resizes x
 // 2 axes), so they are built once and kept: no stream synchronisation and no blocking copy per scale (round 4 rebuilt and re-uploaded
@@ -50,16 +67,7 @@ static int cubic_table(pmx_ctx* c, int src, int dst, bool fixed, const int** idx
     if (it == c->pr_tabs.end()) {
         const size_t n = (size_t)4 * dst;
         std::vector<int> hi(2 * n);
-        std::vector<float> hc(n);
-        make_cubic_table(dst, src, hi.data(), hc.data());
-        if (fixed) {
-            for (size_t k = 0; k < n; ++k) {
-                long v = lrintf(hc[k] * 2048.0f);              // saturate_cast<short>(coef * INTER_RESIZE_COEF_SCALE)
-                hi[n + k] = (int)(v < -32768 ? -32768 : (v > 32767 ? 32767 : v));
-            }
-        } else {
-            memcpy(hi.data() + n, hc.data(), n * sizeof(float));
-        }
+        pmx_cubic_table(src, dst, fixed, hi.data());
         int* d = nullptr;
         PMX_HIP(hipMalloc((void**)&d, 2 * n * sizeof(int)));
         if (hipMemcpy(d, hi.data(), 2 * n * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {

@@ -25,7 +25,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB_PATH = os.path.join(CSRC, 'libpose_mi355x.so')
 HEADER = os.path.join(os.path.dirname(HERE), 'include', 'pose_mi355x.h')
-SOURCES = [('pmx_api.hip', []), ('pmx_precise.hip', []), ('pmx_multi.hip', []), ('conv_mfma.hip', []), ('conv_wino.hip', ['-mllvm', '-pragma-unroll-threshold=200000']), ('conv1_wino.hip', []), ('conv_f16.hip', []), ('conv_select.hip', []), ('prep.hip', ['-ffp-contract=off']),
+SOURCES = [('pmx_api.hip', []), ('pmx_precise.hip', []), ('pmx_multi.hip', []), ('pmx_precise_images.hip', ['-ffp-contract=off']), ('conv_mfma.hip', []), ('conv_wino.hip', ['-mllvm', '-pragma-unroll-threshold=200000']), ('conv1_wino.hip', []), ('conv_f16.hip', []), ('conv_select.hip', []), ('prep.hip', ['-ffp-contract=off']),
            ('postproc.hip', ['-ffp-contract=off']), ('pmx_boxes.hip', ['-ffp-contract=off'])]
 # the opt-in bf16x3 kernels (option "precision" = 1; DESIGN.md 4.1.5: frozen, slower than the fp32 Winograd path) are NOT part of the
 # default library: PMX_BUILD_BF16X3=1 in the environment of the build adds their translation unit (the stamp then differs, so the
@@ -58,6 +58,11 @@ class PmxImage(C.Structure):
     """include/pose_mi355x.h::pmx_image -- one image of a mixed-size batch (pmx_detect_images)."""
     _fields_ = [('bgr', C.c_void_p), ('src_h', C.c_int), ('src_w', C.c_int), ('net_h', C.c_int), ('net_w', C.c_int),
                 ('map_h', C.c_int), ('map_w', C.c_int)]
+
+
+class PmxPreciseImage(C.Structure):
+    """include/pose_mi355x.h::pmx_precise_image -- one image of a detect_precise list (pmx_detect_precise_images)."""
+    _fields_ = [('bgr', C.c_void_p), ('orig_h', C.c_int), ('orig_w', C.c_int), ('n_scales', C.c_int), ('scaled_hw', C.c_int * 16)]
 
 
 class PmxError(RuntimeError):
@@ -274,6 +279,9 @@ def load():
         'pmx_forward_u8_images': (ci, [vp, vp, vp, ci, ci]),
         'pmx_postprocess_images': (ci, [vp, vp, ci, vp]),
         'pmx_get_image_maps': (ci, [vp, ci, vp, vp, ci, ci]),
+        'pmx_detect_precise_images': (ci, [vp, vp, ci]),
+        'pmx_get_precise_image_maps': (ci, [vp, ci, vp, vp, ci, ci]),
+        'pmx_precise_images_table_bytes': (ci, [vp, C.POINTER(C.c_size_t)]),
         'pmx_results_layout': (ci, [vp, ip, C.POINTER(C.c_size_t)]),
         'pmx_get_results': (ci, [vp, ci, vp, C.c_size_t]),
         'pmx_results_device_ptr': (ci, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
@@ -506,6 +514,43 @@ class Engine(object):
         self._check(self.lib.pmx_precise_finish(self._ctx))
         self._B = self._precise_n
         self._fhw = self._precise_hw
+
+    def detect_precise_images(self, imgs, scaled_sizes):
+        """detect_precise for a list of uint8 BGR images of ANY sizes in one call (include/pose_mi355x.h::pmx_detect_precise_images).
+        scaled_sizes[i]: the (h, w) of each inference scale of image i in the reference's loop order (1 .. 8 of them).  Records
+        (results()) in image order; precise_image_maps(i) returns image i's averaged maps."""
+        keep = [np.ascontiguousarray(im, dtype=np.uint8) for im in imgs]
+        n = len(keep)
+        arr = (PmxPreciseImage * n)()
+        for i, im in enumerate(keep):
+            assert im.ndim == 3 and im.shape[2] == 3
+            sz = list(scaled_sizes[i])
+            if not 1 <= len(sz) <= 8:
+                raise ValueError('image %d: %d scales (1 .. 8)' % (i, len(sz)))
+            arr[i].bgr = im.ctypes.data
+            arr[i].orig_h, arr[i].orig_w = im.shape[0], im.shape[1]
+            arr[i].n_scales = len(sz)
+            for k, (h, w) in enumerate(sz):
+                arr[i].scaled_hw[2 * k], arr[i].scaled_hw[2 * k + 1] = int(h), int(w)
+        self._check(self.lib.pmx_detect_precise_images(self._ctx, arr, n))
+        self._B = n
+        self._fhw = None
+        self._map = None
+        self._precise_img_hw = [(k.shape[0], k.shape[1]) for k in keep]
+
+    def precise_image_maps(self, image):
+        """(paf 38 x H x W, heat 19 x H x W) float32: the averaged maps of image `image` of the last detect_precise_images call."""
+        h, w = self._precise_img_hw[image]
+        paf = np.empty((N_PAF, h, w), np.float32)
+        heat = np.empty((N_HEAT, h, w), np.float32)
+        self._check(self.lib.pmx_get_precise_image_maps(self._ctx, int(image), _ptr(paf), _ptr(heat), int(h), int(w)))
+        return paf, heat
+
+    def precise_images_table_bytes(self):
+        """bytes of the per-call table buffer of detect_precise_images (bounded by the largest call, not by the sizes seen)"""
+        v = C.c_size_t(0)
+        self._check(self.lib.pmx_precise_images_table_bytes(self._ctx, C.byref(v)))
+        return v.value
 
     def keypoints(self, out_h, out_w, thresh):
         """facenet / handnet: (B, maps - 1, 4) float64 rows (x, y, confidence, valid)."""

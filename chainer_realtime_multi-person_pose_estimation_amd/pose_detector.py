@@ -203,14 +203,27 @@ class PoseDetector(object):
             if fetch_maps and getattr(self, 'pafs', None) is not None and np.ndim(self.pafs) == 4:
                 self.pafs, self.heatmaps = self.pafs[0], self.heatmaps[0]
 
+    precise_images_per_call = 8       # images of different sizes per detect_precise call (sets the pixel budget the context grows to once)
+
+    def precise_scaled_sizes(self, shape):
+        """(h, w) of every inference scale of an image of `shape` in the reference's loop order (:441-443)."""
+        sizes = []
+        for scale in params['inference_scales']:
+            multiplier = scale * params['inference_img_size'] / min(shape[:2])                     # :442
+            sizes.append((math.ceil(shape[0] * multiplier), math.ceil(shape[1] * multiplier)))
+        return sizes
+
     def detect_precise_batch(self, imgs, fetch_maps=False, return_exceptions=False):
-        """`detect_precise` (reference pose_detector.py:433-482) for a list of uint8 BGR images of ONE common size -> list of (poses, scores).
-        The reference handles one image per call; here every inference scale runs the n images as ONE batch through the network (a single
-        0.5x input is 23 x 31 feature maps -- too little for 256 CUs), the cubic resizes and the accumulation stay on the device per image,
-        and the full-resolution post-process runs on the n averaged map sets at once.  Per image the result equals the single-image call up
-        to the network's kernel-choice-by-launch-size rounding.  Native network only (`model=` callables: loop).
-        Where the reference would raise for ONE image (IndexError, :197) the default raises as it does; `return_exceptions=True` puts the
-        exception object into that image's slot and returns everybody else's result (a per-image loop over the reference loses nothing)."""
+        """`detect_precise` (reference pose_detector.py:433-482) for a list of uint8 BGR images -> list of (poses, scores), in the order given.
+        The reference handles one image per call.  Images of ONE common size: every inference scale runs the n images as ONE batch through
+        the network (a single 0.5x input is 23 x 31 feature maps -- too little for 256 CUs), the cubic resizes and the accumulation stay on
+        the device per image, and the full-resolution post-process runs on the n averaged map sets at once.  Per image the result equals the
+        single-image call up to the network's kernel-choice-by-launch-size rounding.  Images of DIFFERENT sizes
+        (a data set): every (image, scale) pair is a segment of one network forward, as many images per call as the pixel budget allows
+        (include/pose_mi355x.h::pmx_detect_precise_images); with fetch_maps, self.pafs / self.heatmaps are then lists of per-image arrays.
+        Native network only (`model=` callables: loop).  Where the reference would raise for ONE image (IndexError, :197) the default
+        raises as it does; `return_exceptions=True` puts the exception object into that image's slot and returns everybody else's result
+        (a per-image loop over the reference loses nothing)."""
         if len(imgs) == 0:
             raise ValueError('detect_precise_batch needs at least one image')
         if self.model is not None:
@@ -218,16 +231,15 @@ class PoseDetector(object):
         if self._weights is None:
             raise RuntimeError('PoseDetector has no weights: pass weights_file=, weights= or model=')
         imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in imgs]
-        shape = imgs[0].shape
         for im in imgs:
-            if im.shape != shape or im.ndim != 3 or im.shape[2] != 3:
-                raise ValueError('detect_precise_batch needs uint8 H x W x 3 images of one common size')
+            if im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError('detect_precise_batch needs uint8 H x W x 3 images')
+        shape = imgs[0].shape
+        if any(im.shape != shape for im in imgs):
+            return self._detect_precise_mixed(imgs, fetch_maps, return_exceptions)
         orig_img_h, orig_img_w, _ = shape
         n = len(imgs)
-        sizes = []
-        for scale in params['inference_scales']:
-            multiplier = scale * params['inference_img_size'] / min(shape[:2])                     # :442
-            sizes.append((math.ceil(orig_img_h * multiplier), math.ceil(orig_img_w * multiplier)))
+        sizes = self.precise_scaled_sizes(shape)
         ds = params['downscale']
         big = max(sizes)
         self._grow(n, -(-big[0] // ds) * ds, -(-big[1] // ds) * ds)
@@ -245,6 +257,39 @@ class PoseDetector(object):
         rec = self.engine.results()
         self.all_peaks = self.engine.peaks(0) if n == 1 else None                                    # :475 (kept as the reference keeps it; a batch has no single set)
         return unpack_results(rec, return_exceptions=return_exceptions)
+
+    def _detect_precise_mixed(self, imgs, fetch_maps, return_exceptions):
+        """detect_precise_batch for images of different sizes: chunks within the context's pixel budget, each chunk one
+        pmx_detect_precise_images call; results (and maps) in the caller's order."""
+        ds = params['downscale']
+        sizes = [self.precise_scaled_sizes(im.shape) for im in imgs]
+        px = [sum((-(-h // ds) * ds) * (-(-w // ds) * ds) for h, w in sz) for sz in sizes]       # padded network-input pixels (:445)
+        # grow ONCE: room for the precise_images_per_call largest images of the list (at least the largest one)
+        per = max(1, min(len(imgs), int(self.precise_images_per_call)))
+        want = sum(sorted(px, reverse=True)[:per])
+        mb, mh, mw = self._cap
+        if per > mb or want > mb * mh * mw:
+            nb = max(mb, per)
+            side = max(mh * mw, -(-want // nb))
+            self._make_engine(nb, mh, -(-side // (mh * 8)) * 8)          # (max_w: a multiple of 8)
+        mb, mh, mw = self._cap
+        res = [None] * len(imgs)
+        pafs, heats = [None] * len(imgs), [None] * len(imgs)
+        for chunk in precise_chunks(px, mb * mh * mw, mb):
+            self.engine.detect_precise_images([imgs[i] for i in chunk], [sizes[i] for i in chunk])   # :433-470 per image
+            if fetch_maps:
+                for k, i in enumerate(chunk):
+                    pafs[i], heats[i] = self.engine.precise_image_maps(k)
+            for k, r in enumerate(unpack_results(self.engine.results(), return_exceptions=True)):   # :475-481 per image
+                res[chunk[k]] = r
+        if fetch_maps:
+            self.pafs, self.heatmaps = pafs, heats
+        self.all_peaks = None                        # (several images: no single set, as for a same-size batch)
+        if not return_exceptions:
+            for r in res:                            # (the reference would have raised on that image's call)
+                if isinstance(r, Exception):
+                    raise r
+        return res
 
     # ---- demo-chain helpers (reference pose_detector.py:267-424): host geometry that feeds the face / hand detectors -------
     _UNIT_BASE_LIMBS = (14, 3, 0, 13, 9)            # nose-neck, neck-left hip, neck-right hip, shoulder-ear (left, right)
@@ -450,6 +495,21 @@ class PoseDetector(object):
         self.engine.set_maps(paf, heat)
         self.engine.postprocess(map_h, map_w, img_len=map_w if img_len is None else img_len, scale_xy=scale_xy)
         return unpack_results(self.engine.results())
+
+
+def precise_chunks(pixels, budget, max_images):
+    """Cut a list of images (their network-input pixels, all scales) into consecutive runs of at most `max_images` images whose pixels fit
+    `budget`; an image larger than the budget alone is a run of its own (the library refuses it with a capacity error)."""
+    chunks, cur, used = [], [], 0
+    for i, p in enumerate(pixels):
+        if cur and (used + p > budget or len(cur) >= max_images):
+            chunks.append(cur)
+            cur, used = [], 0
+        cur.append(i)
+        used += p
+    if cur:
+        chunks.append(cur)
+    return chunks
 
 
 def _data(v):

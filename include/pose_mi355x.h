@@ -286,6 +286,35 @@ int pmx_postprocess_images(pmx_ctx* ctx, const int* map_hw, int batch, const dou
  * 19 x fh x fw (either may be NULL); fh x fw must be the image's map size (network size / 8).  Synchronises. */
 int pmx_get_image_maps(pmx_ctx* ctx, int image, float* paf, float* heat, int fh, int fw);
 
+/* ---- detect_precise for a LIST of images of any sizes (pose_detector.py:433-482 per image) ------------------------------------
+ * Per image exactly detect_precise: each scale k does the uint8 cubic resize of the original to scaled_hw[2 k] x scaled_hw[2 k + 1] (a copy
+ * when that is the original size), the pad to a multiple of 8 with (104, 117, 123), the forward, the x8 cubic up-sampling, the crop and the
+ * cubic resize to the original size; the parts are summed left to right from 0.f in slot order and divided by n_scales; the post-process
+ * runs at the original size with img_len = orig_w and no rescale.  Results in image order through pmx_get_results / pmx_get_peaks /
+ * pmx_get_connections / pmx_get_subsets (image index = position in `images`).
+ * Every (image, scale) pair is a segment of ONE network forward on the context's stream (pairs of equal network size merge; no lanes,
+ * no stream priorities): the maps do not depend on GPU_MAX_HW_QUEUES.  In fp32 they equal, bit for bit, the pmx_precise_begin / add_scale /
+ * finish sequence of each image alone with options "precise_plain" 1 and "conv1_wino" 2 (the plain Winograd kernels a segmented forward
+ * runs); in f16 mode ("precision" 2) the default sequence.  "precision" 1 (bf16x3) is refused with PMX_ERR_INVALID.
+ * Capacity, checked before anything is enqueued (PMX_ERR_CAPACITY naming what overflowed): n <= max_batch, the network-input pixels of
+ * all pairs (sum of padded h x w) <= max_batch x max_h x max_w, the level-3 pixels (sum of h/8 x w/8) within the cat / branch buffers,
+ * 32-bit offsets and buffer extents.  The call's planar temporaries, full-resolution maps and tables live in per-call buffers that grow
+ * on demand and are never cached by size; the tables stay valid until the next call (a capacity grow-and-re-run of the post-process
+ * inside pmx_get_results uses them).  Synchronises once.  The caller's images are read before the call returns. */
+typedef struct pmx_precise_image {
+    const uint8_t* bgr;      /* orig_h x orig_w x 3 uint8 BGR, host memory */
+    int orig_h, orig_w;
+    int n_scales;            /* 1 .. 8 */
+    int scaled_hw[16];       /* (h, w) per scale in the reference's loop order (:441-443): ceil(orig * multiplier), computed by the caller */
+} pmx_precise_image;
+int pmx_detect_precise_images(pmx_ctx* ctx, const pmx_precise_image* images, int n);
+/* the averaged maps of image `image` of the last pmx_detect_precise_images call as NCHW float32: paf 38 x h x w, heat 19 x h x w (either
+ * may be NULL); h x w must be the image's original size.  Synchronises. */
+int pmx_get_precise_image_maps(pmx_ctx* ctx, int image, float* paf, float* heat, int h, int w);
+/* bytes of the per-call table buffer the context holds for pmx_detect_precise_images (diagnostics: bounded by the largest call, not by
+ * the number of distinct sizes seen) */
+int pmx_precise_images_table_bytes(pmx_ctx* ctx, size_t* bytes);
+
 /* results.  pmx_results_layout synchronises, grows the capacities and re-runs the post-process if an image overflowed them,
  * and returns the layout of the (now final) records; pmx_get_results does the same and copies `batch` records to `out`
  * (out_bytes >= batch * bytes_per_record, else PMX_ERR_CAPACITY). */
