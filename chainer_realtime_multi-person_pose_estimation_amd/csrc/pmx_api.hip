@@ -288,59 +288,31 @@ static void pp_prof_cb(void* vc, const char* name, int begin)
 }
 
 
-template <typename T>
-static int dev_alloc(T** p, size_t count)
+// Allocates the post-process arrays for B images at the capacities in p (cap_pk, cap_sub, cap_cand, cap_ppl): ONE allocation, `store`, with
+// the arrays of the table below carved out of it at 256-byte-aligned offsets.  An array of no elements (the candidate store and the subset
+// work table outside their large modes) stays null.  p.smoothed is not part of the set.
+static int pp_alloc(PPBuffers& p, DevBuf<char>& store, size_t B)
 {
-    PMX_HIP(hipMalloc((void**)p, count * sizeof(T) ? count * sizeof(T) : 16));
-    return PMX_OK;
-}
-
-// (re)allocates every post-process buffer whose size depends on the capacities in c->pp (cap_pk, cap_sub, cap_cand)
-static void pp_free(pmx_ctx* c)
-{
-    PPBuffers& p = c->pp;
-    void* ptrs[] = {p.pk_raw_key, p.pk_raw_score, p.pk_count, p.pk_x, p.pk_y, p.pk_score, p.pk_start, p.cn_a, p.cn_b, p.cn_score,
-                    p.cn_count, p.cn_need, p.cand_score, p.cand_idx, p.cand_used, p.sub_work, p.subsets, p.status, p.results,
-                    p.scan_score, p.scan_idx, p.scan_cnt};
-    for (void* q : ptrs) if (q) (void)hipFree(q);
-    p.pk_raw_key = nullptr; p.pk_raw_score = nullptr; p.pk_count = nullptr; p.pk_x = p.pk_y = nullptr; p.pk_score = nullptr;
-    p.pk_start = nullptr; p.cn_a = p.cn_b = nullptr; p.cn_score = nullptr; p.cn_count = p.cn_need = nullptr;
-    p.cand_score = nullptr; p.cand_idx = nullptr; p.cand_used = nullptr; p.sub_work = p.subsets = nullptr; p.status = nullptr;
-    p.results = nullptr;
-    p.scan_score = nullptr; p.scan_idx = nullptr; p.scan_cnt = nullptr;
-}
-
-static int pp_alloc(pmx_ctx* c)
-{
-    PPBuffers& p = c->pp;
-    const size_t B = c->max_batch, npk = (size_t)PMX_N_JOINTS * p.cap_pk;
-    int rc;
+    const size_t npk = (size_t)PMX_N_JOINTS * p.cap_pk, nl = PMX_N_LIMBS, ncn = nl * p.cap_pk, ncand = nl * p.cap_cand;
     p.rec_bytes = PMX_RECORD_BYTES(p.cap_ppl);
-    if ((rc = dev_alloc(&p.pk_raw_key, B * npk))) return rc;
-    if ((rc = dev_alloc(&p.pk_raw_score, B * npk))) return rc;
-    if ((rc = dev_alloc(&p.pk_count, B * PMX_N_JOINTS))) return rc;
-    if ((rc = dev_alloc(&p.pk_x, B * npk))) return rc;
-    if ((rc = dev_alloc(&p.pk_y, B * npk))) return rc;
-    if ((rc = dev_alloc(&p.pk_score, B * npk))) return rc;
-    if ((rc = dev_alloc(&p.pk_start, B * (PMX_N_JOINTS + 1)))) return rc;
-    if ((rc = dev_alloc(&p.cn_a, B * PMX_N_LIMBS * p.cap_pk))) return rc;
-    if ((rc = dev_alloc(&p.cn_b, B * PMX_N_LIMBS * p.cap_pk))) return rc;
-    if ((rc = dev_alloc(&p.cn_score, B * PMX_N_LIMBS * p.cap_pk))) return rc;
-    if ((rc = dev_alloc(&p.cn_count, B * PMX_N_LIMBS))) return rc;
-    if ((rc = dev_alloc(&p.cn_need, B * PMX_N_LIMBS))) return rc;
     p.scan_cap = p.cap_cand > PMX_LDS_CANDIDATES ? p.cap_cand : PMX_LDS_CANDIDATES;
-    if ((rc = dev_alloc(&p.scan_score, B * PMX_N_LIMBS * p.scan_cap))) return rc;
-    if ((rc = dev_alloc(&p.scan_idx, B * PMX_N_LIMBS * p.scan_cap))) return rc;
-    if ((rc = dev_alloc(&p.scan_cnt, B * PMX_N_LIMBS))) return rc;
-    if (p.cap_cand > 0) {
-        if ((rc = dev_alloc(&p.cand_score, B * PMX_N_LIMBS * p.cap_cand))) return rc;
-        if ((rc = dev_alloc(&p.cand_idx, B * PMX_N_LIMBS * p.cap_cand))) return rc;
-        if ((rc = dev_alloc(&p.cand_used, B * PMX_N_LIMBS * 2 * p.cap_pk))) return rc;
+    struct Part { void** q; size_t bytes; };
+    auto part = [B](auto*& q, size_t per_image) { return Part{(void**)&q, B * per_image * sizeof(*q)}; };
+    const Part parts[] = {
+        part(p.pk_raw_key, npk), part(p.pk_raw_score, npk), part(p.pk_count, PMX_N_JOINTS), part(p.pk_x, npk), part(p.pk_y, npk),
+        part(p.pk_score, npk), part(p.pk_start, PMX_N_JOINTS + 1), part(p.cn_a, ncn), part(p.cn_b, ncn), part(p.cn_score, ncn),
+        part(p.cn_count, nl), part(p.cn_need, nl), part(p.scan_score, nl * p.scan_cap), part(p.scan_idx, nl * p.scan_cap), part(p.scan_cnt, nl),
+        part(p.cand_score, ncand), part(p.cand_idx, ncand), part(p.cand_used, p.cap_cand > 0 ? 2 * ncn : 0),
+        part(p.sub_work, p.cap_sub > PMX_LDS_SUBSETS ? (size_t)p.cap_sub * 20 : 0), part(p.subsets, (size_t)p.cap_sub * 20),
+        part(p.status, 1), part(p.results, p.rec_bytes)};
+    size_t total = 0;
+    for (const Part& s : parts) total += (s.bytes + 255) / 256 * 256;
+    if (int rc = store.alloc(total)) return rc;
+    size_t off = 0;
+    for (const Part& s : parts) {
+        *s.q = s.bytes ? store + off : nullptr;
+        off += (s.bytes + 255) / 256 * 256;
     }
-    if (p.cap_sub > PMX_LDS_SUBSETS && (rc = dev_alloc(&p.sub_work, B * p.cap_sub * 20))) return rc;
-    if ((rc = dev_alloc(&p.subsets, B * p.cap_sub * 20))) return rc;
-    if ((rc = dev_alloc(&p.status, B))) return rc;
-    if ((rc = dev_alloc(&p.results, B * p.rec_bytes))) return rc;
     return PMX_OK;
 }
 
@@ -394,24 +366,20 @@ extern "C" int pmx_create_net(pmx_ctx** out, const char* arch, int device, int m
         c->stream = c->own_stream;
         PMX_HIP(hipEventCreate(&c->t0));
         PMX_HIP(hipEventCreate(&c->t1));
-        if ((rc = dev_alloc(&c->in16, B * HW * PMX_IN_C))) return rc;
-        if ((rc = dev_alloc(&c->act0, B * HW * 64))) return rc;      // conv1_1 out is the largest activation
-        if ((rc = dev_alloc(&c->act1, B * HW * 16))) return rc;      // (H/2)(W/2) x 64 = (H/4)(W/4) x 256
-        if ((rc = dev_alloc(&c->cat, B * hw8 * c->cat_c))) return rc;
-        if ((rc = dev_alloc(&c->brA, B * hw8 * 256))) return rc;
-        if ((rc = dev_alloc(&c->brB, B * hw8 * 256))) return rc;
-        if ((rc = dev_alloc(&c->brT, B * hw8 * 1024))) return rc;
+        if ((rc = c->in16.alloc(B * HW * PMX_IN_C))) return rc;
+        if ((rc = c->act0.alloc(B * HW * 64))) return rc;      // conv1_1 out is the largest activation
+        if ((rc = c->act1.alloc(B * HW * 16))) return rc;      // (H/2)(W/2) x 64 = (H/4)(W/4) x 256
+        if ((rc = c->cat.alloc(B * hw8 * c->cat_c))) return rc;
+        if ((rc = c->brA.alloc(B * hw8 * 256))) return rc;
+        if ((rc = c->brB.alloc(B * hw8 * 256))) return rc;
+        if ((rc = c->brT.alloc(B * hw8 * 1024))) return rc;
         PMX_HIP(hipMemsetAsync(c->cat, 0, B * hw8 * c->cat_c * sizeof(float), c->stream));   // pad channels stay zero forever (stream-ordered)
-        c->nchw_tmp_bytes = B * HW * 3 * sizeof(float);
-        if (c->nchw_tmp_bytes < B * hw8 * 80 * sizeof(float)) c->nchw_tmp_bytes = B * hw8 * 80 * sizeof(float);
-        PMX_HIP(hipMalloc((void**)&c->nchw_tmp, c->nchw_tmp_bytes));
-        PMX_HIP(hipMalloc((void**)&c->u8_tmp, B * HW * 3));
+        if ((rc = c->nchw_tmp.alloc(B * HW * 3 < B * hw8 * 80 ? B * hw8 * 80 : B * HW * 3))) return rc;
+        if ((rc = c->u8_tmp.alloc(B * HW * 3))) return rc;
         // post-process buffers at the initial capacities
         c->pp.cap_pk = PMX_INIT_PEAKS_PER_JOINT; c->pp.cap_sub = PMX_INIT_SUBSETS; c->pp.cap_ppl = PMX_INIT_PEOPLE; c->pp.cap_cand = 0;
-        if ((rc = pp_alloc(c))) return rc;
-        if ((rc = dev_alloc(&c->d_scale, B * 2))) return rc;
-        c->pp.smoothed = nullptr;
-        return PMX_OK;
+        if ((rc = pp_alloc(c->pp, c->pp_store, B))) return rc;
+        return c->d_scale.alloc(B * 2);
     };
     if (int rc = build()) { pmx_destroy(c); return rc; }
 
@@ -438,34 +406,15 @@ extern "C" void pmx_destroy(pmx_ctx* c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    pmx_boxes_free(c);
-    for (auto& l : c->layers) { if (l.d_w) (void)hipFree(l.d_w); if (l.d_b) (void)hipFree(l.d_b); if (l.d_w3) (void)hipFree(l.d_w3); if (l.d_w16) (void)hipFree(l.d_w16); if (l.d_ww) (void)hipFree(l.d_ww); }
-    pp_free(c);
-    void* ptrs[] = {c->sk_scratch, c->sk_zero_bias, c->pr_tmp, c->d_kp, c->u8_src, c->rs_tab, c->in16, c->act0, c->act1, c->cat, c->brA, c->brB, c->brT, c->nchw_tmp, c->u8_tmp, c->ext_paf, c->ext_heat,
-                    c->pp.smoothed, c->d_scale, c->tab.xi0, c->tab.xi1, c->tab.xlo, c->tab.xhi, c->tab.yi0, c->tab.yi1,
-                    c->tab.ylo, c->tab.yhi, c->tab.gauss};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    for (auto& kv : c->pr_tabs) (void)hipFree(kv.second);
-    for (auto& kv : c->tab_cache) (void)hipFree(kv.second.xi0);        // (one allocation per cached table set: pmx_multi.hip)
-    void* mptrs[] = {c->d_segs, c->mi_src, c->mi_tab, c->pi_dev, c->pi_src, c->pi_tmp, c->pi_maps};
-    for (void* p : mptrs) if (p) (void)hipFree(p);
-    for (float* q : c->pr_part) if (q) (void)hipFree(q);
-    for (int i = 1; i < PMX_PR_LANES; ++i) {
-        PrLane& l = c->pr_lane[i];
-        void* lp[] = {l.in16, l.act0, l.act1, l.cat, l.brA, l.brB, l.brT, l.u8_tmp, l.pr_tmp, l.sk_scratch};
-        for (void* q : lp) if (q) (void)hipFree(q);
-        if (l.stream) (void)hipStreamDestroy(l.stream);
-    }
+    // streams and events by hand; every buffer is a DevBuf member and goes with the context (after the synchronisation above)
+    for (int i = 1; i < PMX_PR_LANES; ++i) if (c->pr_lane[i].stream) (void)hipStreamDestroy(c->pr_lane[i].stream);
     for (int i = 0; i < PMX_PR_LANES; ++i) if (c->pr_lane[i].done) (void)hipEventDestroy(c->pr_lane[i].done);
     if (c->pr_src_ready) (void)hipEventDestroy(c->pr_src_ready);
     if (c->pr_fin) (void)hipEventDestroy(c->pr_fin);
+    if (c->bx_copied) (void)hipEventDestroy(c->bx_copied);
     for (auto& p : c->pending) { (void)hipEventDestroy(p.e0); (void)hipEventDestroy(p.e1); }
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
-    if (c->h_results) (void)hipHostFree(c->h_results);
-    for (int i = 0; i < PMX_SNAPSHOT_SLOTS; ++i) {
-        if (c->snap_ev[i]) (void)hipEventDestroy(c->snap_ev[i]);
-        if (c->snap_status[i]) (void)hipHostFree(c->snap_status[i]);
-    }
+    for (hipEvent_t e : c->snap_ev) if (e) (void)hipEventDestroy(e);
     if (c->t0) (void)hipEventDestroy(c->t0);
     if (c->t1) (void)hipEventDestroy(c->t1);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -551,15 +500,14 @@ extern "C" int pmx_set_layer(pmx_ctx* c, const char* name, const float* w, const
     const int cpad = cout_pad_of(cout);
     pack_weights(w, bias, cout, cin, ks, cmap, cpad, wp, bp);
     PMX_HIP(hipStreamSynchronize(c->stream));     // layer may be in use by queued work
-    if (!L.d_w) PMX_HIP(hipMalloc((void**)&L.d_w, wp.size() * sizeof(float)));
-    if (!L.d_b) PMX_HIP(hipMalloc((void**)&L.d_b, bp.size() * sizeof(float)));
+    int rc;
+    if (!L.d_w && (rc = L.d_w.alloc(wp.size()))) return rc;
+    if (!L.d_b && (rc = L.d_b.alloc(bp.size()))) return rc;
     PMX_HIP(hipMemcpy(L.d_w, wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice));
     PMX_HIP(hipMemcpy(L.d_b, bp.data(), bp.size() * sizeof(float), hipMemcpyHostToDevice));
     // the bf16x3 pack (1.5x the fp32 weights) and the Winograd pack (16/9 x for 3x3, 81/49 x for 7x7) are derived from the packed fp32
     // weights on first use (ensure_*_pack): a context that never runs those kernels neither holds nor computes them
-    if (L.d_w3) { (void)hipFree(L.d_w3); L.d_w3 = nullptr; }
-    if (L.d_w16) { (void)hipFree(L.d_w16); L.d_w16 = nullptr; }
-    if (L.d_ww) { (void)hipFree(L.d_ww); L.d_ww = nullptr; }
+    L.d_w3.reset(); L.d_w16.reset(); L.d_ww.reset();
     L.set = true; L.cin = cin; L.cout = cout; L.ks = ks;
     L.cin_pad = (int)cmap.size(); L.cout_pad = cpad; L.nch = L.cin_pad / CK;
     return PMX_OK;
@@ -591,14 +539,13 @@ static int ensure_wino_pack(PackedLayer& L)
     if (int rc = fetch_packed(L, wp)) return rc;
     pack_wino(wp, L.ks, L.nch, L.cout_pad, ww);
     // (the pack becomes visible only once it is complete: a failed copy must not leave a non-null pointer to garbage behind)
-    float* d = nullptr;
-    PMX_HIP(hipMalloc((void**)&d, ww.size() * sizeof(float)));
+    DevBuf<float> d;
+    if (int rc = d.alloc(ww.size())) return rc;
     if (hipMemcpy(d, ww.data(), ww.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(d);
         pmx_set_error("winograd weight pack: host-to-device copy failed: %s", hipGetErrorString(hipGetLastError()));
         return PMX_ERR_HIP;
     }
-    L.d_ww = d;
+    L.d_ww = std::move(d);
     return PMX_OK;
 }
 // conv1_1's weights in the order conv1_wino_kernel's lanes want them: [channel half 2][k-pair 14][k of the pair 2][channel 32] (the 28th k is
@@ -617,14 +564,13 @@ static int ensure_conv1_pack(PackedLayer& L)
                     const int k = 2 * sp + kk;
                     if (k < 27) w1[((hf * 14 + sp) * 2 + kk) * 32 + n] = wp[((size_t)(k / 3) * L.cout_pad + hf * 32 + n) * CK + k % 3];
                 }
-    float* d = nullptr;
-    PMX_HIP(hipMalloc((void**)&d, w1.size() * sizeof(float)));
+    DevBuf<float> d;
+    if (int rc = d.alloc(w1.size())) return rc;
     if (hipMemcpy(d, w1.data(), w1.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(d);
         pmx_set_error("conv1_1 weight pack: host-to-device copy failed: %s", hipGetErrorString(hipGetLastError()));
         return PMX_ERR_HIP;
     }
-    L.d_ww = d;
+    L.d_ww = std::move(d);
     return PMX_OK;
 }
 static int ensure_bf16x3_pack(PackedLayer& L)
@@ -634,14 +580,13 @@ static int ensure_bf16x3_pack(PackedLayer& L)
     std::vector<uint16_t> w3;
     if (int rc = fetch_packed(L, wp)) return rc;
     pack_bf16x3(wp, L.ks * L.ks, L.nch, L.cout_pad, w3);
-    void* d = nullptr;
-    PMX_HIP(hipMalloc(&d, w3.size() * sizeof(uint16_t)));
+    DevBuf<uint16_t> d;
+    if (int rc = d.alloc(w3.size())) return rc;
     if (hipMemcpy(d, w3.data(), w3.size() * sizeof(uint16_t), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(d);
         pmx_set_error("bf16x3 weight pack: host-to-device copy failed: %s", hipGetErrorString(hipGetLastError()));
         return PMX_ERR_HIP;
     }
-    L.d_w3 = d;
+    L.d_w3 = std::move(d);
     return PMX_OK;
 }
 
@@ -653,14 +598,13 @@ static int ensure_f16_pack(PackedLayer& L)
     std::vector<uint16_t> w16;
     if (int rc = fetch_packed(L, wp)) return rc;
     pack_f16(wp, w16);
-    void* d = nullptr;
-    PMX_HIP(hipMalloc(&d, w16.size() * sizeof(uint16_t)));
+    DevBuf<uint16_t> d;
+    if (int rc = d.alloc(w16.size())) return rc;
     if (hipMemcpy(d, w16.data(), w16.size() * sizeof(uint16_t), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(d);
         pmx_set_error("f16 weight pack: host-to-device copy failed: %s", hipGetErrorString(hipGetLastError()));
         return PMX_ERR_HIP;
     }
-    L.d_w16 = d;
+    L.d_w16 = std::move(d);
     return PMX_OK;
 }
 
@@ -668,6 +612,19 @@ static int ensure_f16_pack(PackedLayer& L)
 // With S > 1 K slices the slice blocks write raw partial sums into the context's slab scratch and conv_splitk_reduce
 // produces the final result (slabs added in slice order, then bias, ReLU, pool).
 static const int SK_ZERO_BIAS = PMX_SK_ZERO_BIAS;
+// the slab scratch at `need` floats at least, and the zero bias vector of the slice blocks (made on first use)
+static int sk_reserve(pmx_ctx* c, size_t need)
+{
+    int rc;
+    if ((rc = c->sk_scratch.ensure(need, c->stream))) return rc;
+    if (!c->sk_zero_bias) {
+        if ((rc = c->sk_zero_bias.alloc(SK_ZERO_BIAS))) return rc;
+        // stream-ordered: a null-stream hipMemset is not ordered against this (non-blocking) stream and may still be in flight
+        // when the first slice kernel reads the vector
+        PMX_HIP(hipMemsetAsync(c->sk_zero_bias, 0, SK_ZERO_BIAS * sizeof(float), c->stream));
+    }
+    return PMX_OK;
+}
 static int launch_conv(pmx_ctx* c, const ConvArgs& a0, int groups, int v, const SplitPlan& plan)
 {
     const int S = plan.S;
@@ -679,19 +636,7 @@ static int launch_conv(pmx_ctx* c, const ConvArgs& a0, int groups, int v, const 
     PMX_CHECK(a0.cout_pad <= SK_ZERO_BIAS, PMX_ERR_INVALID, "split-K: cout_pad %d too large", a0.cout_pad);
     const size_t slab = (size_t)a0.B * a0.H * a0.W * a0.cout_pad;
     const size_t need = slab * S * groups;
-    if (need > c->sk_floats) {
-        PMX_HIP(hipStreamSynchronize(c->stream));
-        if (c->sk_scratch) (void)hipFree(c->sk_scratch);
-        c->sk_scratch = nullptr; c->sk_floats = 0;
-        PMX_HIP(hipMalloc((void**)&c->sk_scratch, need * sizeof(float)));
-        c->sk_floats = need;
-    }
-    if (!c->sk_zero_bias) {
-        PMX_HIP(hipMalloc((void**)&c->sk_zero_bias, SK_ZERO_BIAS * sizeof(float)));
-        // stream-ordered: a null-stream hipMemset is not ordered against this (non-blocking) stream and may still be in flight
-        // when the first slice kernel reads the vector
-        PMX_HIP(hipMemsetAsync(c->sk_zero_bias, 0, SK_ZERO_BIAS * sizeof(float), c->stream));
-    }
+    if (int rc = sk_reserve(c, need)) return rc;
     ConvArgs a = a0;
     SplitKReduceArgs r;
     memset(&r, 0, sizeof r);
@@ -718,17 +663,7 @@ static int launch_wino_units(pmx_ctx* c, const ConvArgs& a0, int ks, int groups,
     PMX_CHECK(a0.cout_pad <= SK_ZERO_BIAS, PMX_ERR_INVALID, "split-K: cout_pad %d too large", a0.cout_pad);
     const size_t slab = (size_t)a0.B * a0.H * a0.W * a0.cout_pad;
     const size_t need = slab * S * groups;
-    if (need > c->sk_floats) {
-        PMX_HIP(hipStreamSynchronize(c->stream));
-        if (c->sk_scratch) (void)hipFree(c->sk_scratch);
-        c->sk_scratch = nullptr; c->sk_floats = 0;
-        PMX_HIP(hipMalloc((void**)&c->sk_scratch, need * sizeof(float)));
-        c->sk_floats = need;
-    }
-    if (!c->sk_zero_bias) {
-        PMX_HIP(hipMalloc((void**)&c->sk_zero_bias, SK_ZERO_BIAS * sizeof(float)));
-        PMX_HIP(hipMemsetAsync(c->sk_zero_bias, 0, SK_ZERO_BIAS * sizeof(float), c->stream));
-    }
+    if (int rc = sk_reserve(c, need)) return rc;
     ConvArgs a = a0;
     SplitKReduceArgs r;
     memset(&r, 0, sizeof r);
@@ -792,17 +727,7 @@ static int launch_wino_run(pmx_ctx* c, const ConvArgs& a0, int ks, int groups, i
     const size_t slab = merged ? (size_t)wino_tail_merged_blocks(a0.B, a0.H) * PMX_WINO_RUN_TILES * 4 * a0.cout_pad      // [block of the stream][tile][pixel][cout_pad]
                                : (size_t)a0.B * nslab * PMX_WINO_RUN_TILES * 4 * a0.cout_pad;      // one block per (image, slab): [image][slab][tile][pixel][cout_pad]
     const size_t need = slab * S * groups;
-    if (need > c->sk_floats) {
-        PMX_HIP(hipStreamSynchronize(c->stream));
-        if (c->sk_scratch) (void)hipFree(c->sk_scratch);
-        c->sk_scratch = nullptr; c->sk_floats = 0;
-        PMX_HIP(hipMalloc((void**)&c->sk_scratch, need * sizeof(float)));
-        c->sk_floats = need;
-    }
-    if (!c->sk_zero_bias) {
-        PMX_HIP(hipMalloc((void**)&c->sk_zero_bias, SK_ZERO_BIAS * sizeof(float)));
-        PMX_HIP(hipMemsetAsync(c->sk_zero_bias, 0, SK_ZERO_BIAS * sizeof(float), c->stream));
-    }
+    if (int rc = sk_reserve(c, need)) return rc;
     WinoTailReduceArgs r;
     memset(&r, 0, sizeof r);
     for (int gi = 0; gi < groups; ++gi) {
@@ -857,10 +782,10 @@ static int run_conv_f16(pmx_ctx* c, const char* label, int li0, int li1, const f
     if ((rc = ensure_f16_pack(c->layers[li0])) || (groups == 2 && (rc = ensure_f16_pack(c->layers[li1])))) return rc;
     ConvArgs a;
     memset(&a, 0, sizeof a);
-    a.g[0].in = in0; a.g[0].w = (const float*)L0.d_w16; a.g[0].bias = L0.d_b; a.g[0].out = out0; a.g[0].cout = L0.cout;
+    a.g[0].in = in0; a.g[0].w = (const float*)L0.d_w16.get(); a.g[0].bias = L0.d_b; a.g[0].out = out0; a.g[0].cout = L0.cout;
     if (groups == 2) {
         const PackedLayer& L1 = c->layers[li1];
-        a.g[1].in = in1; a.g[1].w = (const float*)L1.d_w16; a.g[1].bias = L1.d_b; a.g[1].out = out1; a.g[1].cout = L1.cout;
+        a.g[1].in = in1; a.g[1].w = (const float*)L1.d_w16.get(); a.g[1].bias = L1.d_b; a.g[1].out = out1; a.g[1].cout = L1.cout;
     }
     a.B = B; a.H = H; a.W = W; a.lda = lda; a.ldc = ldc; a.nch = L0.nch; a.cout_pad = L0.cout_pad; a.relu = relu; a.pool = pool;
     long long tiles = (long long)B * ((H + 7) / 8) * ((W + 15) / 16);
@@ -953,8 +878,8 @@ static int run_conv(pmx_ctx* c, const char* label, int li0, int li1, const float
     if (c->opt_precision == 1 && L0.ks > 1 && conv_bf16x3_twin(v) >= 0) {
         if ((rc = ensure_bf16x3_pack(c->layers[li0])) || (groups == 2 && (rc = ensure_bf16x3_pack(c->layers[li1])))) return rc;
         v = conv_bf16x3_twin(v);
-        a.g[0].w = (const float*)L0.d_w3;
-        if (groups == 2) a.g[1].w = (const float*)c->layers[li1].d_w3;
+        a.g[0].w = (const float*)L0.d_w3.get();
+        if (groups == 2) a.g[1].w = (const float*)c->layers[li1].d_w3.get();
     }
     const bool prof_this = c->prof_on == 1 || (c->prof_on == 2 && L0.ks == 7);
     const bool wino_ok = wino_eligible(L0.ks, L0.cin_pad, L0.cout_pad) &&
@@ -1344,24 +1269,12 @@ extern "C" int pmx_forward_u8_resized(pmx_ctx* c, const uint8_t* img, int B, int
     const size_t nsrc = (size_t)B * src_h * src_w * 3;
     const uint8_t* d = img;
     if (!on_device) {
-        if (nsrc > c->u8_src_cap) {
-            PMX_HIP(hipStreamSynchronize(c->stream));
-            if (c->u8_src) (void)hipFree(c->u8_src);
-            c->u8_src = nullptr;
-            PMX_HIP(hipMalloc((void**)&c->u8_src, nsrc));
-            c->u8_src_cap = nsrc;
-        }
+        if ((rc = c->u8_src.ensure(nsrc, c->stream))) return rc;
         PMX_HIP(hipMemcpyAsync(c->u8_src, img, nsrc, hipMemcpyHostToDevice, c->stream));
         d = c->u8_src;
     }
     const size_t ntab = (size_t)4 * (w + h);
-    if (ntab > c->rs_tab_cap) {
-        PMX_HIP(hipStreamSynchronize(c->stream));
-        if (c->rs_tab) (void)hipFree(c->rs_tab);
-        c->rs_tab = nullptr;
-        PMX_HIP(hipMalloc((void**)&c->rs_tab, ntab * sizeof(int)));
-        c->rs_tab_cap = ntab;
-    }
+    if ((rc = c->rs_tab.ensure(ntab, c->stream))) return rc;
     std::vector<int> tab(ntab);
     make_resize_table(w, src_w, tab.data());
     make_resize_table(h, src_h, tab.data() + 4 * w);
@@ -1419,15 +1332,8 @@ extern "C" int pmx_set_maps(pmx_ctx* c, const float* paf, const float* heat, int
     PMX_CHECK(fh >= 1 && fw >= 1, PMX_ERR_INVALID, "pmx_set_maps: bad size");
     PMX_DEV(c);
     const size_t need = (size_t)B * fh * fw;
-    if (need > c->ext_cap) {
-        PMX_HIP(hipStreamSynchronize(c->stream));
-        if (c->ext_paf) (void)hipFree(c->ext_paf);
-        if (c->ext_heat) (void)hipFree(c->ext_heat);
-        c->ext_paf = c->ext_heat = nullptr;
-        PMX_HIP(hipMalloc((void**)&c->ext_paf, need * PMX_N_PAF * 4));
-        PMX_HIP(hipMalloc((void**)&c->ext_heat, need * c->n_heat * 4));
-        c->ext_cap = need;
-    }
+    int rc;
+    if ((rc = c->ext_paf.ensure(need * PMX_N_PAF, c->stream)) || (rc = c->ext_heat.ensure(need * c->n_heat, c->stream))) return rc;
     if (paf) PMX_HIP(hipMemcpyAsync(c->ext_paf, paf, need * PMX_N_PAF * 4, hipMemcpyHostToDevice, c->stream));
     PMX_HIP(hipMemcpyAsync(c->ext_heat, heat, need * c->n_heat * 4, hipMemcpyHostToDevice, c->stream));
     PMX_HIP(hipStreamSynchronize(c->stream));    // host buffers may be released by the caller
@@ -1448,7 +1354,6 @@ extern "C" int pmx_set_gaussian(pmx_ctx* c, const double* taps, int radius)
     if (!c->tab_cache.empty()) {      // the per-size table sets of mixed batches carry the old taps (a setup call: synchronising is fine)
         PMX_DEV(c);
         PMX_HIP(hipDeviceSynchronize());
-        for (auto& kv : c->tab_cache) (void)hipFree(kv.second.xi0);
         c->tab_cache.clear();
     }
     return PMX_OK;
@@ -1499,22 +1404,33 @@ void pmx_pp_gauss(const pmx_ctx* c, std::vector<double>& g, PPTables& t)
     }
 }
 
+int pmx_ensure_smoothed(pmx_ctx* c, size_t floats)
+{
+    const int rc = c->smoothed.ensure(floats, c->stream);
+    c->pp.smoothed = c->smoothed;       // (null after a failed growth)
+    return rc;
+}
+
+// The table set of the context for one (network map, up-sampled map) size pair.  A failure anywhere in here (the one allocation of a larger
+// set, an upload) leaves the context consistent: c->tab points into what c->tab_store holds, or nowhere, and tab_in_h stays invalid, so
+// the next call builds the set again
 int pmx_ensure_tables(pmx_ctx* c, int in_h, int in_w, int out_h, int out_w, int flip_x)
 {
     if (c->tab_in_h == in_h && c->tab_in_w == in_w && c->tab_out_h == out_h && c->tab_out_w == out_w && c->tab_flip == flip_x) return PMX_OK;
-    const int cap = out_h > out_w ? out_h : out_w;
+    // one allocation for the set: [gauss | xlo | xhi | ylo | yhi] doubles, then [xi0 | xi1 | yi0 | yi1] ints, the axis arrays `cap` long
+    const size_t cap = out_h > out_w ? out_h : out_w, ng = 2 * PMX_GAUSS_MAX_RADIUS + 1;
+    const size_t bytes = (ng + 4 * cap) * sizeof(double) + 4 * cap * sizeof(int);
     PPTables& t = c->tab;
-    if (cap > c->tab_cap) {
-        PMX_HIP(hipStreamSynchronize(c->stream));
-        void* olds[] = {t.xi0, t.xi1, t.xlo, t.xhi, t.yi0, t.yi1, t.ylo, t.yhi};
-        for (void* p : olds) if (p) (void)hipFree(p);
-        PMX_HIP(hipMalloc((void**)&t.xi0, cap * sizeof(int)));  PMX_HIP(hipMalloc((void**)&t.xi1, cap * sizeof(int)));
-        PMX_HIP(hipMalloc((void**)&t.xlo, cap * sizeof(double))); PMX_HIP(hipMalloc((void**)&t.xhi, cap * sizeof(double)));
-        PMX_HIP(hipMalloc((void**)&t.yi0, cap * sizeof(int)));  PMX_HIP(hipMalloc((void**)&t.yi1, cap * sizeof(int)));
-        PMX_HIP(hipMalloc((void**)&t.ylo, cap * sizeof(double))); PMX_HIP(hipMalloc((void**)&t.yhi, cap * sizeof(double)));
-        c->tab_cap = cap;
+    c->tab_in_h = -1;       // until the upload below is complete
+    if (bytes > c->tab_store.capacity()) {
+        if (int rc = c->tab_store.ensure(bytes, c->stream)) {
+            if (!c->tab_store) t = PPTables{};      // (the old set went before the new allocation failed)
+            return rc;
+        }
+        t.gauss = reinterpret_cast<double*>(c->tab_store.get());
+        t.xlo = t.gauss + ng; t.xhi = t.xlo + cap; t.ylo = t.xhi + cap; t.yhi = t.ylo + cap;
+        t.xi0 = reinterpret_cast<int*>(t.yhi + cap); t.xi1 = t.xi0 + cap; t.yi0 = t.xi1 + cap; t.yi1 = t.yi0 + cap;
     }
-    if (!t.gauss) PMX_HIP(hipMalloc((void**)&t.gauss, (2 * PMX_GAUSS_MAX_RADIUS + 1) * sizeof(double)));
     std::vector<int> i0, i1; std::vector<double> lo, hi;
     PMX_HIP(hipStreamSynchronize(c->stream));
     make_grid(in_w, out_w, i0, i1, lo, hi);
@@ -1562,14 +1478,7 @@ extern "C" int pmx_postprocess(pmx_ctx* c, int B, int map_h, int map_w, double i
     }
     m.fh = c->cur_fh; m.fw = c->cur_fw;
     if (c->opt_keep_smoothed) {
-        const size_t need = (size_t)B * PMX_N_JOINTS * map_h * map_w;
-        if (need > c->smoothed_cap) {
-            PMX_HIP(hipStreamSynchronize(c->stream));
-            if (c->pp.smoothed) (void)hipFree(c->pp.smoothed);
-            c->pp.smoothed = nullptr;
-            PMX_HIP(hipMalloc((void**)&c->pp.smoothed, need * sizeof(float)));
-            c->smoothed_cap = need;
-        }
+        if ((rc = pmx_ensure_smoothed(c, (size_t)B * PMX_N_JOINTS * map_h * map_w))) return rc;
     }
     const double* dscale = nullptr;
     if (scale_xy) {
@@ -1622,21 +1531,13 @@ static int next_pow2(long long v)
 // of memory on a crowd image, an absurd user capacity) the context keeps its old buffers and capacities and stays usable
 static int pp_realloc(pmx_ctx* c, int cap_pk, int cap_sub, int cap_cand, int cap_ppl)
 {
-    const PPBuffers old = c->pp;
     PPBuffers fresh{};
+    DevBuf<char> store;
     fresh.cap_pk = cap_pk; fresh.cap_sub = cap_sub; fresh.cap_cand = cap_cand; fresh.cap_ppl = cap_ppl;
-    fresh.smoothed = old.smoothed;               // (owned by the context, sized separately)
+    fresh.smoothed = c->pp.smoothed;             // (c->smoothed, sized separately)
+    if (int rc = pp_alloc(fresh, store, c->max_batch)) return rc;
     c->pp = fresh;
-    const int rc = pp_alloc(c);
-    if (rc) {
-        pp_free(c);                              // whatever part of the new set exists
-        c->pp = old;
-        return rc;
-    }
-    const PPBuffers neu = c->pp;
-    c->pp = old;
-    pp_free(c);
-    c->pp = neu;
+    c->pp_store.swap(store);                     // (the old set goes with `store`)
     return PMX_OK;
 }
 
@@ -1752,13 +1653,8 @@ extern "C" int pmx_get_results(pmx_ctx* c, int B, void* out, size_t out_bytes)
         const size_t rec = c->pp.rec_bytes, need = rec * (size_t)B;
         PMX_CHECK(out_bytes >= need, PMX_ERR_CAPACITY, "pmx_get_results: %zu bytes for %d records of %zu bytes (see pmx_results_layout)",
                   out_bytes, B, rec);
-        if (need > c->h_results_bytes) {
-            if (c->h_results) (void)hipHostFree(c->h_results);
-            c->h_results = nullptr; c->h_results_bytes = 0;
-            const size_t want = rec * (size_t)c->max_batch;
-            PMX_HIP(hipHostMalloc((void**)&c->h_results, want, hipHostMallocDefault));
-            c->h_results_bytes = want;
-        }
+        if (need > c->h_results.capacity())
+            if (int rc = c->h_results.alloc(rec * (size_t)c->max_batch)) return rc;
         PMX_HIP(hipMemcpyAsync(c->h_results, c->pp.results, need, hipMemcpyDeviceToHost, c->stream));
         PMX_HIP(hipStreamSynchronize(c->stream));
         if (!c->pp_final) {
@@ -1797,7 +1693,8 @@ extern "C" int pmx_results_snapshot(pmx_ctx* c, int slot, void* dst_device, size
     const size_t need = c->pp.rec_bytes * (size_t)c->pp_B;
     PMX_CHECK(dst_bytes >= need, PMX_ERR_CAPACITY, "pmx_results_snapshot: %zu bytes for %d records of %zu bytes", dst_bytes, c->pp_B, c->pp.rec_bytes);
     if (!c->snap_ev[slot]) PMX_HIP(hipEventCreateWithFlags(&c->snap_ev[slot], hipEventDisableTiming));
-    if (!c->snap_status[slot]) PMX_HIP(hipHostMalloc((void**)&c->snap_status[slot], sizeof(int) * (size_t)c->max_batch, hipHostMallocDefault));
+    if (!c->snap_status[slot])
+        if (int rc = c->snap_status[slot].alloc(c->max_batch)) return rc;
     PMX_HIP(hipMemcpyAsync(dst_device, c->pp.results, need, hipMemcpyDeviceToDevice, c->stream));
     PMX_HIP(hipMemcpyAsync(c->snap_status[slot], c->pp.status, sizeof(int) * (size_t)c->pp_B, hipMemcpyDeviceToHost, c->stream));
     PMX_HIP(hipEventRecord(c->snap_ev[slot], c->stream));
@@ -1997,46 +1894,42 @@ extern "C" int pmx_conv2d(pmx_ctx* c, const float* x, const float* w, const floa
     std::vector<float> wp, bp;
     pack_weights(w, bias, cout, cin, ks, cmap, cpad, wp, bp);
     const int Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W;
-    float *d_x = nullptr, *d_xn = nullptr, *d_w = nullptr, *d_b = nullptr, *d_y = nullptr, *d_yn = nullptr;
+    DevBuf<float> d_x, d_xn, d_w, d_b, d_y, d_yn, d_ww;      // (freed on every way out)
+    DevBuf<uint16_t> d_w3;
     const size_t nx = (size_t)B * cin * H * W, nxn = (size_t)B * H * W * cin_pad, ny = (size_t)B * cout * Ho * Wo;
-    PMX_HIP(hipMalloc((void**)&d_x, nx * 4));
-    PMX_HIP(hipMalloc((void**)&d_xn, nxn * 4));
-    PMX_HIP(hipMalloc((void**)&d_w, wp.size() * 4));
-    PMX_HIP(hipMalloc((void**)&d_b, bp.size() * 4));
-    PMX_HIP(hipMalloc((void**)&d_y, ny * 4));
-    PMX_HIP(hipMalloc((void**)&d_yn, ny * 4));
+    int rc;
+    if ((rc = d_x.alloc(nx)) || (rc = d_xn.alloc(nxn)) || (rc = d_w.alloc(wp.size())) || (rc = d_b.alloc(bp.size())) ||
+        (rc = d_y.alloc(ny)) || (rc = d_yn.alloc(ny))) return rc;
     PMX_HIP(hipMemcpy(d_x, x, nx * 4, hipMemcpyHostToDevice));
     PMX_HIP(hipMemsetAsync(d_xn, 0, nxn * 4, c->stream));
     PMX_HIP(hipMemcpy(d_w, wp.data(), wp.size() * 4, hipMemcpyHostToDevice));
     PMX_HIP(hipMemcpy(d_b, bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
     // poison the output so that unwritten elements are caught by the test
     PMX_HIP(hipMemsetAsync(d_yn, 0xFF, ny * 4, c->stream));
-    int rc = launch_nchw_to_nhwc(d_x, d_xn, B, cin, H, W, cin_pad, 0, c->stream);
+    rc = launch_nchw_to_nhwc(d_x, d_xn, B, cin, H, W, cin_pad, 0, c->stream);
     ConvArgs a;
     memset(&a, 0, sizeof a);
     a.g[0].in = d_xn; a.g[0].w = d_w; a.g[0].bias = d_b; a.g[0].out = d_yn; a.g[0].cout = cout;
     a.B = B; a.H = H; a.W = W; a.lda = cin_pad; a.ldc = cout; a.nch = cin_pad / CK; a.cout_pad = cpad; a.relu = relu; a.pool = pool;
     const int v = conv_pick_variant(ks, cpad, H, W, B, c->opt_force[ks], c->opt_kernel_gen, pool, cin, c->opt_precision == 1 && ks > 1);
-    void* d_w3 = nullptr;
     int v_run = v;
     if (c->opt_precision == 1 && conv_bf16x3_twin(v) >= 0 && ks > 1) {
         std::vector<uint16_t> w3;
         pack_bf16x3(wp, ks * ks, cin_pad / CK, cpad, w3);
-        PMX_HIP(hipMalloc(&d_w3, w3.size() * sizeof(uint16_t)));
+        if ((rc = d_w3.alloc(w3.size()))) return rc;
         PMX_HIP(hipMemcpy(d_w3, w3.data(), w3.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        a.g[0].w = (const float*)d_w3;
+        a.g[0].w = (const float*)d_w3.get();
         v_run = conv_bf16x3_twin(v);
     }
     if (c->opt_precision == 2 && ks > 1) {          // f16 mode: the f16 kernel, whatever the shape
         std::vector<uint16_t> w16;
         pack_f16(wp, w16);
-        PMX_HIP(hipMalloc(&d_w3, w16.size() * sizeof(uint16_t)));
+        if ((rc = d_w3.alloc(w16.size()))) return rc;
         PMX_HIP(hipMemcpy(d_w3, w16.data(), w16.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        a.g[0].w = (const float*)d_w3;
+        a.g[0].w = (const float*)d_w3.get();
     }
     SplitPlan plan = conv_pick_ksplit(v_run, H, W, B, 1, cpad, cin_pad / CK, pool, c->opt_ksplit);
     if (cout % 4 != 0) plan.S = 1;
-    float* d_ww = nullptr;
     int ug = 0, wrun = 0, wtail = 0;
     const bool f16 = c->opt_precision == 2 && ks > 1;
     const int wmode = f16 ? 0 : wino_mode(c, ks, cin_pad, cpad, cout, cout, B, H, W, pool, &ug, &wrun, &wtail, 1, a.lda);
@@ -2044,14 +1937,14 @@ extern "C" int pmx_conv2d(pmx_ctx* c, const float* x, const float* w, const floa
     if (wino) {
         std::vector<float> ww;
         pack_wino(wp, ks, cin_pad / CK, cpad, ww);
-        PMX_HIP(hipMalloc((void**)&d_ww, ww.size() * sizeof(float)));
+        if ((rc = d_ww.alloc(ww.size()))) return rc;
         PMX_HIP(hipMemcpy(d_ww, ww.data(), ww.size() * sizeof(float), hipMemcpyHostToDevice));
         a.g[0].w = d_ww; a.nch = cin_pad / 32;
     }
     if (ug) {
         std::vector<float> ww;
         pack_wino(wp, ks, cin_pad / CK, cpad, ww);
-        PMX_HIP(hipMalloc((void**)&d_ww, ww.size() * sizeof(float)));
+        if ((rc = d_ww.alloc(ww.size()))) return rc;
         PMX_HIP(hipMemcpy(d_ww, ww.data(), ww.size() * sizeof(float), hipMemcpyHostToDevice));
         a.g[0].w = d_ww; a.nch = cin_pad / 32;
     }
@@ -2083,8 +1976,5 @@ extern "C" int pmx_conv2d(pmx_ctx* c, const float* x, const float* w, const floa
         hipError_t e = hipMemcpy(y, d_y, ny * 4, hipMemcpyDeviceToHost);
         if (e != hipSuccess) { pmx_set_error("pmx_conv2d: %s", hipGetErrorString(e)); rc = PMX_ERR_HIP; }
     }
-    (void)hipFree(d_x); (void)hipFree(d_xn); (void)hipFree(d_w); (void)hipFree(d_b); (void)hipFree(d_y); (void)hipFree(d_yn);
-    if (d_w3) (void)hipFree(d_w3);
-    if (d_ww) (void)hipFree(d_ww);
     return rc;
 }

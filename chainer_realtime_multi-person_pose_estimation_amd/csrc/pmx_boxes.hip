@@ -170,32 +170,15 @@ struct Stage {
     size_t reserve(size_t bytes) { const size_t off = (h.size() + 15) / 16 * 16; h.resize(off + bytes); return off; }
 };
 
-template <class T>
-int grow(pmx_ctx* c, T** p, size_t* cap, size_t bytes)
-{
-    if (bytes <= *cap) return PMX_OK;
-    PMX_HIP(hipStreamSynchronize(c->stream));      // (queued work may still read the old buffer)
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; *cap = 0;
-    PMX_HIP(hipMalloc((void**)p, bytes));
-    *cap = bytes;
-    return PMX_OK;
-}
-
 // one H2D copy of the staging; the device copy is valid for the kernels enqueued after it on the context's stream
 int stage_upload(pmx_ctx* c, const Stage& st)
 {
     const size_t bytes = st.h.size();
     if (!bytes) return PMX_OK;
     if (c->bx_pending) { PMX_HIP(hipEventSynchronize(c->bx_copied)); c->bx_pending = false; }     // the pinned buffer is free again
-    if (bytes > c->bx_host_cap) {
-        if (c->bx_host) (void)hipHostFree(c->bx_host);
-        c->bx_host = nullptr; c->bx_host_cap = 0;
-        PMX_HIP(hipHostMalloc((void**)&c->bx_host, bytes, hipHostMallocDefault));
-        c->bx_host_cap = bytes;
-    }
     int rc;
-    if ((rc = grow(c, &c->bx_dev, &c->bx_dev_cap, bytes))) return rc;
+    if (bytes > c->bx_host.capacity() && (rc = c->bx_host.alloc(bytes))) return rc;
+    if ((rc = c->bx_dev.ensure(bytes, c->stream))) return rc;      // (queued work may still read the old buffer)
     if (!c->bx_copied) PMX_HIP(hipEventCreateWithFlags(&c->bx_copied, hipEventDisableTiming));
     memcpy(c->bx_host, st.h.data(), bytes);
     PMX_HIP(hipMemcpyAsync(c->bx_dev, c->bx_host, bytes, hipMemcpyHostToDevice, c->stream));
@@ -291,9 +274,9 @@ void stage_keypoints(pmx_ctx* c, Stage& st, const int* hwf, int n, int in_h, int
 int stage_fix_pointers(pmx_ctx* c, Stage& st, const KpStage& ks, int n)
 {
     int rc;
-    if ((rc = grow(c, &c->bx_dev, &c->bx_dev_cap, st.h.size()))) return rc;
+    if ((rc = c->bx_dev.ensure(st.h.size(), c->stream))) return rc;
     KpCrop* k = reinterpret_cast<KpCrop*>(st.h.data() + ks.crops_off);
-    const uintptr_t base = reinterpret_cast<uintptr_t>(c->bx_dev);
+    const uintptr_t base = reinterpret_cast<uintptr_t>(c->bx_dev.get());
     for (int i = 0; i < n; ++i) {
         PPTables& t = k[i].tab;
         t.xi0 = reinterpret_cast<int*>(base + reinterpret_cast<uintptr_t>(t.xi0)); t.xi1 = reinterpret_cast<int*>(base + reinterpret_cast<uintptr_t>(t.xi1));
@@ -336,7 +319,7 @@ int kp_enqueue_chunk(pmx_ctx* c, const KpStage& ks, const int* hwf, int k0, int 
         if ((rc = pmx_prof_begin(c, "kp_boxes|kp_tiles_kernel", (double)m.sbh * 4 * B))) return rc;
         hipLaunchKernelGGL(kp_tiles_kernel<10>, dim3(t1 - t0, n_ch), dim3(256), 0, c->stream, m,
                            reinterpret_cast<const KpCrop*>(c->bx_dev + ks.crops_off), reinterpret_cast<const int2*>(c->bx_dev + ks.tiles_off),
-                           t0, k0, n_ch, static_cast<ArgMax*>(c->bx_rec));
+                           t0, k0, n_ch, reinterpret_cast<ArgMax*>(c->bx_rec.get()));
         PMX_HIP(hipGetLastError());
         return pmx_prof_end(c);
     }
@@ -344,14 +327,7 @@ int kp_enqueue_chunk(pmx_ctx* c, const KpStage& ks, const int* hwf, int k0, int 
     for (int k = k0; k < k0 + B; ++k) {
         const int h = hwf[3 * k], w = hwf[3 * k + 1], flip = hwf[3 * k + 2];
         if ((rc = pmx_ensure_tables(c, c->cur_fh, c->cur_fw, h, w, flip))) return rc;
-        const size_t need = (size_t)n_ch * h * w;      // (smoothed_cap counts floats, pmx_keypoints)
-        if (need > c->smoothed_cap) {
-            PMX_HIP(hipStreamSynchronize(c->stream));
-            if (c->pp.smoothed) (void)hipFree(c->pp.smoothed);
-            c->pp.smoothed = nullptr; c->smoothed_cap = 0;
-            PMX_HIP(hipMalloc((void**)&c->pp.smoothed, need * sizeof(float)));
-            c->smoothed_cap = need;
-        }
+        if ((rc = pmx_ensure_smoothed(c, (size_t)n_ch * h * w))) return rc;
         PPMaps mk = m;
         mk.heat = m.heat + (long long)(k - k0) * m.sbh;
         if ((rc = pp_keypoints_launch(mk, c->tab, c->pp, 1, n_ch, h, w, thresh, c->d_kp + (size_t)k * n_ch * 4, c->stream))) return rc;
@@ -369,14 +345,8 @@ int kp_prepare(pmx_ctx* c, Stage& st, const int* hwf, int n, KpStage* ks)
                   k, hwf[3 * k], hwf[3 * k + 1], hwf[3 * k + 2]);
     stage_keypoints(c, st, hwf, n, c->cur_fh, c->cur_fw, ks);
     const size_t nkp = (size_t)n * n_ch * 4;
-    if (nkp > c->kp_cap) {
-        PMX_HIP(hipStreamSynchronize(c->stream));
-        if (c->d_kp) (void)hipFree(c->d_kp);
-        c->d_kp = nullptr; c->kp_cap = 0;
-        PMX_HIP(hipMalloc((void**)&c->d_kp, nkp * sizeof(double)));
-        c->kp_cap = nkp;
-    }
-    if (kp_fast(c) && (rc = grow(c, &c->bx_rec, &c->bx_rec_cap, (size_t)ks->n_tiles * n_ch * sizeof(ArgMax)))) return rc;
+    if ((rc = c->d_kp.ensure(nkp, c->stream))) return rc;
+    if (kp_fast(c) && (rc = c->bx_rec.ensure((size_t)ks->n_tiles * n_ch * sizeof(ArgMax), c->stream))) return rc;
     return PMX_OK;
 }
 
@@ -386,9 +356,9 @@ int kp_finish(pmx_ctx* c, const KpStage& ks, int n, double thresh, double* out)
     int rc;
     if (kp_fast(c)) {
         if ((rc = pmx_prof_begin(c, "kp_boxes|kp_merge_kernel", (double)ks.n_tiles * n_ch * sizeof(ArgMax)))) return rc;
-        hipLaunchKernelGGL(kp_merge_kernel, dim3(n_ch, n), dim3(256), 0, c->stream, static_cast<const ArgMax*>(c->bx_rec),
+        hipLaunchKernelGGL(kp_merge_kernel, dim3(n_ch, n), dim3(256), 0, c->stream, reinterpret_cast<const ArgMax*>(c->bx_rec.get()),
                            reinterpret_cast<const KpCrop*>(c->bx_dev + ks.crops_off), reinterpret_cast<const int*>(c->bx_dev + ks.ends_off),
-                           n_ch, thresh, c->d_kp);
+                           n_ch, thresh, c->d_kp.get());
         PMX_HIP(hipGetLastError());
         if ((rc = pmx_prof_end(c))) return rc;
     }
@@ -404,7 +374,7 @@ int image_on_device(pmx_ctx* c, const uint8_t* img, int img_h, int img_w, int on
     if (on_device) { *d = img; return PMX_OK; }
     const size_t nsrc = (size_t)img_h * img_w * 3;
     int rc;
-    if ((rc = grow(c, &c->u8_src, &c->u8_src_cap, nsrc))) return rc;
+    if ((rc = c->u8_src.ensure(nsrc, c->stream))) return rc;
     PMX_HIP(hipMemcpyAsync(c->u8_src, img, nsrc, hipMemcpyHostToDevice, c->stream));
     c->pr_src = nullptr;      // (u8_src no longer holds a detect_precise original)
     *d = c->u8_src;
@@ -420,24 +390,13 @@ int forward_chunk(pmx_ctx* c, const uint8_t* d_img, int img_h, int img_w, size_t
     if ((rc = pmx_prof_begin(c, "resize_boxes|box_gather_resize_u8_kernel", (double)npix * 3 * 2))) return rc;
     hipLaunchKernelGGL(box_gather_resize_u8_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, c->stream, d_img, img_h, img_w,
                        reinterpret_cast<const BoxDesc*>(c->bx_dev + desc_off) + k0,
-                       reinterpret_cast<const int*>(c->bx_dev + tab_off) + (size_t)k0 * 4 * (dw + dh), B, dh, dw, c->u8_tmp);
+                       reinterpret_cast<const int*>(c->bx_dev + tab_off) + (size_t)k0 * 4 * (dw + dh), B, dh, dw, c->u8_tmp.get());
     PMX_HIP(hipGetLastError());
     if ((rc = pmx_prof_end(c))) return rc;
     return pmx_forward_u8(c, c->u8_tmp, B, dh, dw, 1);
 }
 
 }  // namespace
-
-void pmx_boxes_free(pmx_ctx* c)
-{
-    if (c->bx_host) (void)hipHostFree(c->bx_host);
-    if (c->bx_dev) (void)hipFree(c->bx_dev);
-    if (c->bx_rec) (void)hipFree(c->bx_rec);
-    if (c->bx_copied) (void)hipEventDestroy(c->bx_copied);
-    c->bx_host = nullptr; c->bx_dev = nullptr; c->bx_rec = nullptr; c->bx_copied = nullptr;
-    c->bx_host_cap = c->bx_dev_cap = c->bx_rec_cap = 0;
-    c->bx_pending = false;
-}
 
 extern "C" int pmx_forward_u8_boxes(pmx_ctx* c, const uint8_t* img, int img_h, int img_w, int on_device, const int* boxes, int n)
 {

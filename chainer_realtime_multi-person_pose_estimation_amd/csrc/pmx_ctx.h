@@ -6,7 +6,54 @@
 #include <map>
 #include <tuple>
 #include <string>
+#include <utility>
 #include <vector>
+
+// The one owner of a device allocation (Host = true: of pinned host memory).  Every buffer of a context is a member of this type, so
+// ~pmx_ctx frees them all and no list of pointers exists anywhere.  `cap` counts elements of T.  Move-only; pointer and capacity always
+// travel together.  Converts to T*, so launches and pointer arithmetic read as with a raw pointer.
+template <typename T, bool Host = false>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept { swap(o); }
+    DevBuf& operator=(DevBuf&& o) noexcept { reset(); swap(o); return *this; }
+    ~DevBuf() { reset(); }
+    void swap(DevBuf& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); }
+    T* get() const { return p; }
+    operator T*() const { return p; }
+    size_t capacity() const { return cap; }
+    void reset()
+    {
+        if (p) (void)(Host ? hipHostFree(p) : hipFree(p));
+        p = nullptr; cap = 0;
+    }
+    // frees what it holds, then allocates exactly `count` elements (16 bytes for none); holds nothing after a failure
+    int alloc(size_t count)
+    {
+        reset();
+        const size_t bytes = count * sizeof(T) ? count * sizeof(T) : 16;
+        const hipError_t e = Host ? hipHostMalloc((void**)&p, bytes, hipHostMallocDefault) : hipMalloc((void**)&p, bytes);
+        if (e != hipSuccess) {
+            p = nullptr;
+            pmx_set_error("DevBuf: %s of %zu bytes -> %s", Host ? "hipHostMalloc" : "hipMalloc", bytes, hipGetErrorString(e));
+            return PMX_ERR_HIP;
+        }
+        cap = count;
+        return PMX_OK;
+    }
+    // grows to `count` elements once `stream` no longer uses the old buffer; a site that needs another synchronisation (or none) calls alloc
+    int ensure(size_t count, hipStream_t stream)
+    {
+        if (count <= cap) return PMX_OK;
+        PMX_HIP(hipStreamSynchronize(stream));
+        return alloc(count);
+    }
+};
+template <typename T> using HostBuf = DevBuf<T, true>;
 
 struct LayerDesc { std::string name; int cin, cout, ks; };
 
@@ -16,11 +63,10 @@ static const int CK = 16;   // channel chunk of every kernel variant
 
 struct PackedLayer {
     bool set = false;
-    float* d_w = nullptr;
-    float* d_b = nullptr;
-    float* d_ww = nullptr;       // Winograd F(2x2,3x3) pack [freq 16][chunk32][cout_pad][32] = G g G^T (3x3 layers; option "conv_algo" = 1)
-    void* d_w3 = nullptr;        // bf16x3 pack [tap][chunk][plane hi|mid|lo][cout_pad][16] (3x3 / 7x7 layers; option "precision" = 1)
-    void* d_w16 = nullptr;       // f16 pack [tap][chunk][cout_pad][16] (3x3 / 7x7 layers; option "precision" = 2)
+    DevBuf<float> d_w, d_b;
+    DevBuf<float> d_ww;          // Winograd F(2x2,3x3) pack [freq 16][chunk32][cout_pad][32] = G g G^T (3x3 layers; option "conv_algo" = 1)
+    DevBuf<uint16_t> d_w3;       // bf16x3 pack [tap][chunk][plane hi|mid|lo][cout_pad][16] (3x3 / 7x7 layers; option "precision" = 1)
+    DevBuf<uint16_t> d_w16;      // f16 pack [tap][chunk][cout_pad][16] (3x3 / 7x7 layers; option "precision" = 2)
     int cin = 0, cout = 0, ks = 0, cin_pad = 0, cout_pad = 0, nch = 0;
 };
 
@@ -46,11 +92,10 @@ constexpr int PMX_SK_ZERO_BIAS = 1024;      // floats of the shared zero-bias ve
 struct PrLane {
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
-    float *in16 = nullptr, *act0 = nullptr, *act1 = nullptr, *cat = nullptr, *brA = nullptr, *brB = nullptr, *brT = nullptr;
-    uint8_t* u8_tmp = nullptr;
+    DevBuf<float> in16, act0, act1, cat, brA, brB, brT;
+    DevBuf<uint8_t> u8_tmp;
     size_t cap_px = 0;                       // n * padded_h * padded_w the activation buffers hold
-    float* pr_tmp = nullptr; size_t pr_tmp_cap = 0;
-    float* sk_scratch = nullptr; size_t sk_floats = 0;
+    DevBuf<float> pr_tmp, sk_scratch;
 };
 
 // Heterogeneous batches (pmx_multi.hip): a SEGMENT = n images of one network-input size.  The segments of a forward lie end to end in
@@ -74,20 +119,21 @@ struct pmx_ctx {
     // heterogeneous forward / post-process state
     std::vector<SegDesc> segs;       // non-empty only WHILE a heterogeneous forward is being enqueued (run_conv / run_pair / run_conv1 look at it)
     std::vector<SegDesc> cur_segs;   // layout of the current network output when it came from a heterogeneous forward (else empty)
-    ConvSeg* d_segs = nullptr; size_t d_segs_cap = 0;     // device: PMX_SEG_TABLES tables of segs.size() entries
+    DevBuf<ConvSeg> d_segs;                               // device: PMX_SEG_TABLES tables of segs.size() entries
     int seg_tiles[PMX_SEG_TABLES] = {};                   // tiles per launch, per table
     long long seg_pix[4] = {};                            // pixels of all segments, per level
     std::vector<PPCall> pp_calls;                         // non-empty: the post-process of the current results ran per segment
-    std::map<std::tuple<int, int, int, int>, PPTables> tab_cache;   // up-sampling tables per (in_h, in_w, out_h, out_w) of the per-segment calls
-    uint8_t* mi_src = nullptr; size_t mi_src_cap = 0;     // pmx_detect_images: original-size images awaiting the device resize
-    int* mi_tab = nullptr; size_t mi_tab_cap = 0;         // ... and their resize tables
+    // up-sampling tables per (in_h, in_w, out_h, out_w) of the per-segment calls: the kernel-argument struct and the one allocation it points into
+    std::map<std::tuple<int, int, int, int>, std::pair<PPTables, DevBuf<char>>> tab_cache;
+    DevBuf<uint8_t> mi_src;                               // pmx_detect_images: original-size images awaiting the device resize
+    DevBuf<int> mi_tab;                                   // ... and their resize tables
     // pmx_detect_precise_images (pmx_precise_images.hip): per-call buffers, grown on demand and never keyed by size.  pi_dev holds the
     // call's descriptors, cubic tables and post-process tables (ONE upload); it stays untouched until the next call, so a grow-and-re-run
     // of the post-process (pp_calls) still finds its tables there.
-    char* pi_dev = nullptr; size_t pi_dev_cap = 0;
-    uint8_t* pi_src = nullptr; size_t pi_src_cap = 0;     // the original images, end to end
-    float* pi_tmp = nullptr; size_t pi_tmp_cap = 0;       // x8 up-sampled maps per (image, scale) pair, planar [57][ph][pw]
-    float* pi_maps = nullptr; size_t pi_maps_cap = 0;     // averaged full-resolution maps per image, planar [38 PAF | 19 heat][orig_h][orig_w]
+    DevBuf<char> pi_dev;
+    DevBuf<uint8_t> pi_src;                               // the original images, end to end
+    DevBuf<float> pi_tmp;                                 // x8 up-sampled maps per (image, scale) pair, planar [57][ph][pw]
+    DevBuf<float> pi_maps;                                // averaged full-resolution maps per image, planar [38 PAF | 19 heat][orig_h][orig_w]
     std::vector<long long> pi_off;                        // first float of image i's maps in pi_maps
     std::vector<int> pi_hw;                               // (orig_h, orig_w) of image i
     int kind = NET_POSE;             // architecture: posenet | facenet | handnet
@@ -97,19 +143,18 @@ struct pmx_ctx {
     // detect_precise accumulation state (pmx_precise_*)
     int pr_h = 0, pr_w = 0, pr_scales = 0, pr_n = 0;      // original size, scales accumulated so far, images of the batch
     unsigned pr_mask = 0;                                 // slots (positions in the reference's scale loop) filled so far
-    float* pr_tmp = nullptr; size_t pr_tmp_cap = 0;      // x8 up-sampled maps of one scale, planar [n][38][ph][pw] | [n][19][ph][pw]
-    std::map<std::tuple<int, int, int>, int*> pr_tabs;   // cubic tables per axis, keyed (src, dst, fixed point?): built once, kept
+    DevBuf<float> pr_tmp;                                // x8 up-sampled maps of one scale, planar [n][38][ph][pw] | [n][19][ph][pw]
+    std::map<std::tuple<int, int, int>, DevBuf<int>> pr_tabs; // cubic tables per axis, keyed (src, dst, fixed point?): built once, kept
     const uint8_t* pr_src = nullptr;                     // host images of the current begin / finish sequence already in u8_src
     PrLane pr_lane[PMX_PR_LANES];                        // lanes 1 .. : own buffers; lane 0 = the context's own stream and buffers
-    std::vector<float*> pr_part; size_t pr_part_cap = 0; // per scale: [n][57][orig_h][orig_w] (PAF planes, then heat planes of every image)
+    std::vector<DevBuf<float>> pr_part;                  // per scale: [n][57][orig_h][orig_w] (PAF planes, then heat planes of every image)
     hipEvent_t pr_src_ready = nullptr, pr_fin = nullptr; // originals uploaded / parts consumed by the last finish
     int opt_precise_lanes = PMX_PR_LANES;                // 1: every scale on the context's own stream (A/B, tests)
     int opt_precise_plain = -1;                          // detect_precise's forwards on the plain Winograd kernels: -1 = when all four lanes are in use, 0 never, 1 always
     int opt_precise_lane_priority = 1;                   // lane streams with priorities (largest scale first); read when a lane's stream is created
     int opt_precise_table_cap = 208;                     // cached cubic tables at which the next pmx_precise_begin* starts the cache over (256 - 48)
     int pr_tabs_trims = 0;                               // how often that happened (diagnostics: option query "precise_table_trims")
-    double* d_kp = nullptr;          // key-point records of pmx_keypoints
-    size_t kp_cap = 0;
+    DevBuf<double> d_kp;             // key-point records of pmx_keypoints
     int device = 0;
     hipStream_t stream = nullptr, own_stream = nullptr;
     int max_batch = 0, max_h = 0, max_w = 0;
@@ -117,32 +162,29 @@ struct pmx_ctx {
     std::map<std::string, int> index;
     std::vector<PackedLayer> layers;
     // buffers
-    float *in16 = nullptr, *act0 = nullptr, *act1 = nullptr, *cat = nullptr, *brA = nullptr, *brB = nullptr, *brT = nullptr;
-    float* nchw_tmp = nullptr;       // staging for NCHW host <-> NHWC device conversions
-    size_t nchw_tmp_bytes = 0;
-    uint8_t* u8_tmp = nullptr;
+    DevBuf<float> in16, act0, act1, cat, brA, brB, brT;
+    DevBuf<float> nchw_tmp;          // staging for NCHW host <-> NHWC device conversions
+    DevBuf<uint8_t> u8_tmp;
     const uint8_t* in_u8 = nullptr; float in_div = 255.0f;      // set for ONE forward: conv1_wino_kernel preprocesses this uint8 batch itself
-    uint8_t* u8_src = nullptr;       // original-size images awaiting the on-device resize
-    size_t u8_src_cap = 0;
-    int* rs_tab = nullptr;           // resize tables: x (4 * dw ints) then y (4 * dh ints)
-    size_t rs_tab_cap = 0;
+    DevBuf<uint8_t> u8_src;          // original-size images awaiting the on-device resize
+    DevBuf<int> rs_tab;              // resize tables: x (4 * dw ints) then y (4 * dh ints)
     // state of the last forward / set_maps
     bool maps_valid = false, maps_external = false;
     int cur_B = 0, cur_fh = 0, cur_fw = 0;
-    float *ext_paf = nullptr, *ext_heat = nullptr;   // NCHW copies installed by pmx_set_maps
-    size_t ext_cap = 0;
+    DevBuf<float> ext_paf, ext_heat;                 // NCHW copies installed by pmx_set_maps
     // post-process
-    PPTables tab{};
-    int tab_cap = 0;
+    PPTables tab{};                  // kernel arguments: raw pointers into tab_store (pmx_ensure_tables)
+    DevBuf<char> tab_store;
     int tab_in_h = -1, tab_in_w = -1, tab_out_h = -1, tab_out_w = -1;
     std::vector<double> gauss;
-    PPBuffers pp{};
-    double* d_scale = nullptr;
-    unsigned char* h_results = nullptr;         // pinned staging for pmx_get_results (pageable D2H is slow and jittery)
-    size_t h_results_bytes = 0;
+    PPBuffers pp{};                  // kernel arguments: raw pointers into pp_store (pp_alloc) and, pp.smoothed, to `smoothed`
+    DevBuf<char> pp_store;
+    DevBuf<float> smoothed;          // optional smoothed maps, sized on demand (pmx_ensure_smoothed)
+    DevBuf<double> d_scale;
+    HostBuf<unsigned char> h_results;           // pinned staging for pmx_get_results (pageable D2H is slow and jittery)
     // pmx_results_snapshot / pmx_snapshot_wait: PMX_SNAPSHOT_SLOTS slots (event, pinned status words, layout at snapshot time)
     hipEvent_t snap_ev[PMX_SNAPSHOT_SLOTS] = {};
-    int* snap_status[PMX_SNAPSHOT_SLOTS] = {};
+    HostBuf<int> snap_status[PMX_SNAPSHOT_SLOTS];
     int snap_B[PMX_SNAPSHOT_SLOTS] = {}, snap_cap_ppl[PMX_SNAPSHOT_SLOTS] = {};
     size_t snap_rec[PMX_SNAPSHOT_SLOTS] = {};
     bool pp_valid = false;
@@ -153,7 +195,6 @@ struct pmx_ctx {
     double pp_img_len = 0;
     bool pp_has_scale = false;
     int pp_regrown = 0;                         // number of capacity growths so far (diagnostics)
-    size_t smoothed_cap = 0;
     // options
     int opt_force[8] = {-1, -1, -1, -1, -1, -1, -1, -1};   // by ksize
     int opt_gpu_branch_peaks = 0;    // reference GPU-branch peak extraction (non-golden variant)
@@ -185,8 +226,7 @@ struct pmx_ctx {
     int opt_fuse_pairs = 1;          // the two 1x1 layers that end every stage run as one launch (conv1x1_pair_kernel)
     int opt_ksplit = 0;              // 0: automatic split-K for small launches; n > 0: force n K slices where split-K applies
     // split-K scratch: partial-sum slabs of the current launch + a zero bias vector for the slice blocks
-    float* sk_scratch = nullptr; size_t sk_floats = 0;
-    float* sk_zero_bias = nullptr;
+    DevBuf<float> sk_scratch, sk_zero_bias;
     // timing / profiling
     hipEvent_t t0 = nullptr, t1 = nullptr;
     int prof_on = 0;                 // 0 off | 1 every launch | 2 only the 7x7 convolutions (the dominant kernel: fewest events in a timed region)
@@ -197,10 +237,9 @@ struct pmx_ctx {
     int prof_open = -1;
     // pmx_boxes.hip (key points for many boxes of one image): the per-call staging (resize tables, crop / tile tables, up-sampling grids) goes
     // over in ONE copy from pinned memory; `bx_copied` marks when the host side may be rewritten.  Per-tile arg-max records of the key points.
-    char* bx_host = nullptr; size_t bx_host_cap = 0;
+    HostBuf<char> bx_host;
     hipEvent_t bx_copied = nullptr; bool bx_pending = false;
-    char* bx_dev = nullptr; size_t bx_dev_cap = 0;
-    void* bx_rec = nullptr; size_t bx_rec_cap = 0;
+    DevBuf<char> bx_dev, bx_rec;
 };
 
 #define PMX_DEV(c) PMX_HIP(hipSetDevice((c)->device))
@@ -210,10 +249,12 @@ struct pmx_ctx {
 // preprocessing happens inside it (no float copy of the input), else prep_u8 fills c->in16 first
 int pmx_forward_from_u8(pmx_ctx* c, const uint8_t* d_u8, int B, int H, int W, float divisor);
 int pmx_forward_from_in16(pmx_ctx* c, int B, int H, int W);      // the network on the padded float input already in c->in16
-int pmx_ensure_tables(pmx_ctx* c, int in_h, int in_w, int out_h, int out_w, int flip_x = 0);   // up-sampling tables of the post-process
+// up-sampling tables of the post-process.  On any failure the context stays consistent: c->tab points into whatever c->tab_store holds (or
+// nowhere) and tab_in_h is invalid, so the next call rebuilds
+int pmx_ensure_tables(pmx_ctx* c, int in_h, int in_w, int out_h, int out_w, int flip_x = 0);
 PPBuffers pmx_pp_view(const PPBuffers& p, int base);         // the post-process buffers of the images [base, ...) (every per-image array offset)
 void pmx_make_resize_table(int dst, int src, int* tab);      // OpenCV INTER_LINEAR uint8 table of one axis: [idx0 | idx1 | coef0 | coef1] x dst
-int pmx_check_weights(pmx_ctx* c);
+int pmx_check_weights(pmx_ctx* c);                          // PMX_ERR_WEIGHTS unless every layer has weights
 // corner-aligned up-sampling grid of one axis (F.resize_images, np.linspace semantics): the tables pmx_ensure_tables uploads
 void pmx_make_upsample_grid(int in, int out, std::vector<int>& i0, std::vector<int>& i1, std::vector<double>& lo, std::vector<double>& hi);
 int pmx_prof_begin(pmx_ctx* c, const char* name, double bytes);   // per-launch profiler (option 1 only) around one launch
@@ -227,5 +268,5 @@ void pmx_cubic_table(int src, int dst, bool fixed, int* out);
 // pixels lie end to end at d_u8 (on the device)
 int build_seg_tables(pmx_ctx* c, const std::vector<SegGeo>& g);
 int forward_segments(pmx_ctx* c, const uint8_t* d_u8, const std::vector<SegGeo>& g, int B);
-// pmx_boxes.hip
-void pmx_boxes_free(pmx_ctx* c);                            // PMX_ERR_WEIGHTS unless every layer has weights
+// c->smoothed (and c->pp.smoothed) at `floats` floats at least, grown to exactly that once the stream no longer uses the old maps
+int pmx_ensure_smoothed(pmx_ctx* c, size_t floats);

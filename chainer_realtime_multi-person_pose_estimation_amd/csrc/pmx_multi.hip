@@ -62,13 +62,7 @@ int build_seg_tables(pmx_ctx* c, const std::vector<Geo>& g)
     }
     for (int tab = 0; tab < PMX_SEG_TABLES; ++tab) c->seg_tiles[tab] = tiles[tab];
     for (int level = 0; level < 4; ++level) c->seg_pix[level] = pix[level];
-    if (t.size() > c->d_segs_cap) {
-        PMX_HIP(hipStreamSynchronize(c->stream));
-        if (c->d_segs) (void)hipFree(c->d_segs);
-        c->d_segs = nullptr; c->d_segs_cap = 0;
-        PMX_HIP(hipMalloc((void**)&c->d_segs, t.size() * sizeof(ConvSeg)));
-        c->d_segs_cap = t.size();
-    }
+    if (int rc = c->d_segs.ensure(t.size(), c->stream)) return rc;
     // (stream-ordered: the kernels of an earlier forward that still read the table run before this copy; the source is pageable
     //  memory, which the runtime stages before the call returns)
     PMX_HIP(hipMemcpyAsync(c->d_segs, t.data(), t.size() * sizeof(ConvSeg), hipMemcpyHostToDevice, c->stream));
@@ -86,7 +80,7 @@ int cached_tables(pmx_ctx* c, int in_h, int in_w, int out_h, int out_w, PPTables
     //  is not -- the mirror sets the taps once, right after pmx_create)
     const auto key = std::make_tuple(in_h, in_w, out_h, c->opt_gpu_branch_peaks ? -out_w : out_w);
     auto it = c->tab_cache.find(key);
-    if (it != c->tab_cache.end()) { *out = it->second; return PMX_OK; }
+    if (it != c->tab_cache.end()) { *out = it->second.first; return PMX_OK; }
     // the context's own single-size machinery builds the grids (np.linspace semantics, Gaussian taps, peak-branch flags) ...
     int rc = pmx_ensure_tables(c, in_h, in_w, out_h, out_w);
     if (rc) return rc;
@@ -94,10 +88,10 @@ int cached_tables(pmx_ctx* c, int in_h, int in_w, int out_h, int out_w, PPTables
     const PPTables& src = c->tab;
     const size_t ni = (size_t)2 * out_w + (size_t)2 * out_h, nd = (size_t)2 * out_w + (size_t)2 * out_h + (2 * PMX_GAUSS_MAX_RADIUS + 1);
     const size_t ibytes = (ni * sizeof(int) + 7) / 8 * 8;
-    char* base = nullptr;
-    PMX_HIP(hipMalloc((void**)&base, ibytes + nd * sizeof(double)));
+    DevBuf<char> base;
+    if ((rc = base.alloc(ibytes + nd * sizeof(double)))) return rc;
     PPTables t = src;
-    int* ip = reinterpret_cast<int*>(base);
+    int* ip = reinterpret_cast<int*>(base.get());
     double* dp = reinterpret_cast<double*>(base + ibytes);
     t.xi0 = ip; t.xi1 = ip + out_w; t.yi0 = ip + 2 * out_w; t.yi1 = ip + 2 * out_w + out_h;
     t.xlo = dp; t.xhi = dp + out_w; t.ylo = dp + 2 * out_w; t.yhi = dp + 2 * out_w + out_h; t.gauss = dp + 2 * out_w + 2 * out_h;
@@ -108,8 +102,8 @@ int cached_tables(pmx_ctx* c, int in_h, int in_w, int out_h, int out_w, PPTables
     cp(t.xlo, src.xlo, out_w * sizeof(double)); cp(t.xhi, src.xhi, out_w * sizeof(double));
     cp(t.ylo, src.ylo, out_h * sizeof(double)); cp(t.yhi, src.yhi, out_h * sizeof(double));
     cp(t.gauss, src.gauss, (2 * PMX_GAUSS_MAX_RADIUS + 1) * sizeof(double));
-    if (e != hipSuccess) { (void)hipFree(base); pmx_set_error("post-process table copy failed: %s", hipGetErrorString(e)); return PMX_ERR_HIP; }
-    c->tab_cache.emplace(key, t);
+    if (e != hipSuccess) { pmx_set_error("post-process table copy failed: %s", hipGetErrorString(e)); return PMX_ERR_HIP; }
+    c->tab_cache.emplace(key, std::make_pair(t, std::move(base)));
     *out = t;
     return PMX_OK;
 }
@@ -118,7 +112,6 @@ int trim_table_cache(pmx_ctx* c)
 {
     if (c->tab_cache.size() < 512) return PMX_OK;
     PMX_HIP(hipDeviceSynchronize());
-    for (auto& kv : c->tab_cache) (void)hipFree(kv.second.xi0);
     c->tab_cache.clear();
     return PMX_OK;
 }
@@ -243,21 +236,7 @@ extern "C" int pmx_detect_images(pmx_ctx* c, const pmx_image* imgs, int B)
     int rc = seg_capacity_check(c, g, B);
     if (rc || (rc = pmx_check_weights(c))) return rc;
     PMX_DEV(c);
-    if (src_bytes > c->mi_src_cap || tab_ints > c->mi_tab_cap) {
-        PMX_HIP(hipStreamSynchronize(c->stream));
-        if (src_bytes > c->mi_src_cap) {
-            if (c->mi_src) (void)hipFree(c->mi_src);
-            c->mi_src = nullptr; c->mi_src_cap = 0;
-            PMX_HIP(hipMalloc((void**)&c->mi_src, src_bytes));
-            c->mi_src_cap = src_bytes;
-        }
-        if (tab_ints > c->mi_tab_cap) {
-            if (c->mi_tab) (void)hipFree(c->mi_tab);
-            c->mi_tab = nullptr; c->mi_tab_cap = 0;
-            PMX_HIP(hipMalloc((void**)&c->mi_tab, tab_ints * sizeof(int)));
-            c->mi_tab_cap = tab_ints;
-        }
-    }
+    if ((rc = c->mi_src.ensure(src_bytes, c->stream)) || (rc = c->mi_tab.ensure(tab_ints, c->stream))) return rc;
     // resize tables of all images in one upload, then per image: upload + resize into its place of the network-input run (identity: straight in)
     std::vector<int> tabs(tab_ints);
     {
@@ -314,7 +293,7 @@ extern "C" int pmx_get_image_maps(pmx_ctx* c, int image, float* paf, float* heat
     int rc;
     const float* src = c->cat + (size_t)pix * PMX_CAT_C;
     const size_t np = (size_t)PMX_N_PAF * fh * fw, nh = (size_t)PMX_N_HEAT * fh * fw;
-    PMX_CHECK((np + nh) * sizeof(float) <= c->nchw_tmp_bytes, PMX_ERR_CAPACITY, "pmx_get_image_maps: staging buffer too small");
+    PMX_CHECK(np + nh <= c->nchw_tmp.capacity(), PMX_ERR_CAPACITY, "pmx_get_image_maps: staging buffer too small");
     if (paf) {
         if ((rc = launch_nhwc_to_nchw(src, c->nchw_tmp, 1, PMX_N_PAF, fh, fw, PMX_CAT_C, PMX_CAT_PAF, c->stream))) return rc;
         PMX_HIP(hipMemcpyAsync(paf, c->nchw_tmp, np * 4, hipMemcpyDeviceToHost, c->stream));

@@ -68,14 +68,13 @@ static int cubic_table(pmx_ctx* c, int src, int dst, bool fixed, const int** idx
         const size_t n = (size_t)4 * dst;
         std::vector<int> hi(2 * n);
         pmx_cubic_table(src, dst, fixed, hi.data());
-        int* d = nullptr;
-        PMX_HIP(hipMalloc((void**)&d, 2 * n * sizeof(int)));
+        DevBuf<int> d;
+        if (int rc = d.alloc(2 * n)) return rc;
         if (hipMemcpy(d, hi.data(), 2 * n * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
             pmx_set_error("cubic table upload failed");
             return PMX_ERR_HIP;
         }
-        it = c->pr_tabs.emplace(key, d).first;
+        it = c->pr_tabs.emplace(key, std::move(d)).first;
     }
     *idx = it->second;
     *coef = (const void*)(it->second + (size_t)4 * dst);
@@ -90,21 +89,12 @@ static int cubic_tables_trim(pmx_ctx* c)
 {
     if ((int)c->pr_tabs.size() < c->opt_precise_table_cap) return PMX_OK;
     PMX_HIP(hipDeviceSynchronize());
-    for (auto& kv : c->pr_tabs) (void)hipFree(kv.second);
     c->pr_tabs.clear();
     c->pr_tabs_trims += 1;
     return PMX_OK;
 }
 
 // ---- lanes: one inference scale in flight per lane (pmx_ctx.h::PrLane) --------------------------------------------------------------
-template <typename T>
-static int lane_alloc(T** q, size_t count)
-{
-    if (*q) (void)hipFree(*q);
-    *q = nullptr;
-    PMX_HIP(hipMalloc((void**)q, count * sizeof(T)));
-    return PMX_OK;
-}
 // lane i >= 1 holds n x ph x pw pixels of working set (the sizes pmx_create gives the context's own buffers); lane 0 IS the context
 static int lane_ensure(pmx_ctx* c, int i, size_t n, size_t ph, size_t pw)
 {
@@ -130,9 +120,9 @@ static int lane_ensure(pmx_ctx* c, int i, size_t n, size_t ph, size_t pw)
     l.cap_px = 0;
     const size_t px8 = px / 64;
     int rc;
-    if ((rc = lane_alloc(&l.in16, px * PMX_IN_C)) || (rc = lane_alloc(&l.act0, px * 64)) || (rc = lane_alloc(&l.act1, px * 16)) ||
-        (rc = lane_alloc(&l.cat, px8 * PMX_CAT_C)) || (rc = lane_alloc(&l.brA, px8 * 256)) || (rc = lane_alloc(&l.brB, px8 * 256)) ||
-        (rc = lane_alloc(&l.brT, px8 * 1024)) || (rc = lane_alloc(&l.u8_tmp, px * 3))) return rc;
+    if ((rc = l.in16.alloc(px * PMX_IN_C)) || (rc = l.act0.alloc(px * 64)) || (rc = l.act1.alloc(px * 16)) ||
+        (rc = l.cat.alloc(px8 * PMX_CAT_C)) || (rc = l.brA.alloc(px8 * 256)) || (rc = l.brB.alloc(px8 * 256)) ||
+        (rc = l.brT.alloc(px8 * 1024)) || (rc = l.u8_tmp.alloc(px * 3))) return rc;
     PMX_HIP(hipMemsetAsync(l.cat, 0, px8 * PMX_CAT_C * sizeof(float), l.stream));      // pad channels stay zero (stream-ordered)
     l.cap_px = px;
     return PMX_OK;
@@ -143,10 +133,9 @@ static void lane_swap(pmx_ctx* c, int i)
     if (i == 0) return;
     PrLane& l = c->pr_lane[i];
     std::swap(c->stream, l.stream);
-    std::swap(c->in16, l.in16); std::swap(c->act0, l.act0); std::swap(c->act1, l.act1); std::swap(c->cat, l.cat);
-    std::swap(c->brA, l.brA); std::swap(c->brB, l.brB); std::swap(c->brT, l.brT); std::swap(c->u8_tmp, l.u8_tmp);
-    std::swap(c->pr_tmp, l.pr_tmp); std::swap(c->pr_tmp_cap, l.pr_tmp_cap);
-    std::swap(c->sk_scratch, l.sk_scratch); std::swap(c->sk_floats, l.sk_floats);
+    c->in16.swap(l.in16); c->act0.swap(l.act0); c->act1.swap(l.act1); c->cat.swap(l.cat);
+    c->brA.swap(l.brA); c->brB.swap(l.brB); c->brT.swap(l.brT); c->u8_tmp.swap(l.u8_tmp);
+    c->pr_tmp.swap(l.pr_tmp); c->sk_scratch.swap(l.sk_scratch);
 }
 
 // detect_precise (pose_detector.py:433-470) on the device, for a batch of n images of ONE original size (the reference handles one image
@@ -161,20 +150,13 @@ extern "C" int pmx_precise_begin_batch(pmx_ctx* c, int n_images, int orig_h, int
     PMX_DEV(c);
     if (int rc = cubic_tables_trim(c)) return rc;
     const size_t need = (size_t)n_images * orig_h * orig_w;
-    if (need > c->ext_cap) {
-        PMX_HIP(hipStreamSynchronize(c->stream));
-        if (c->ext_paf) (void)hipFree(c->ext_paf);
-        if (c->ext_heat) (void)hipFree(c->ext_heat);
-        c->ext_paf = c->ext_heat = nullptr; c->ext_cap = 0;
-        PMX_HIP(hipMalloc((void**)&c->ext_paf, need * PMX_N_PAF * 4));
-        PMX_HIP(hipMalloc((void**)&c->ext_heat, need * PMX_N_HEAT * 4));
-        c->ext_cap = need;
-    }
+    int rc;
+    if ((rc = c->ext_paf.ensure(need * PMX_N_PAF, c->stream)) || (rc = c->ext_heat.ensure(need * PMX_N_HEAT, c->stream))) return rc;
     if (!c->pr_src_ready) PMX_HIP(hipEventCreateWithFlags(&c->pr_src_ready, hipEventDisableTiming));
     if (!c->pr_fin) PMX_HIP(hipEventCreateWithFlags(&c->pr_fin, hipEventDisableTiming));
     // the zero-bias vector of the unit-mode / split-K launches is shared by all lanes: it must exist (and be zero) before two streams can meet it
     if (!c->sk_zero_bias) {
-        PMX_HIP(hipMalloc((void**)&c->sk_zero_bias, PMX_SK_ZERO_BIAS * sizeof(float)));
+        if ((rc = c->sk_zero_bias.alloc(PMX_SK_ZERO_BIAS))) return rc;
         PMX_HIP(hipMemset(c->sk_zero_bias, 0, PMX_SK_ZERO_BIAS * sizeof(float)));
     }
     c->pr_h = orig_h; c->pr_w = orig_w; c->pr_scales = 0; c->pr_mask = 0; c->pr_n = n_images; c->pr_src = nullptr;
@@ -240,12 +222,9 @@ static int precise_add_scale(pmx_ctx* c, const uint8_t* imgs, int scaled_h, int 
     // caller passes the same images to every pmx_precise_add_scale* of a sequence -- include/pose_mi355x.h)
     const size_t img_bytes = (size_t)oh * ow * 3, nsrc = img_bytes * n;
     if (first || c->pr_src != imgs) {
-        if (nsrc > c->u8_src_cap) {
+        if (nsrc > c->u8_src.capacity()) {
             PMX_HIP(hipDeviceSynchronize());          // (lanes of an earlier sequence may still read the old buffer)
-            if (c->u8_src) (void)hipFree(c->u8_src);
-            c->u8_src = nullptr; c->u8_src_cap = 0;
-            PMX_HIP(hipMalloc((void**)&c->u8_src, nsrc));
-            c->u8_src_cap = nsrc;
+            if ((rc = c->u8_src.alloc(nsrc))) return rc;
         }
         if (!first) {                                 // (a different buffer mid-sequence: the lanes still reading the old copy finish first)
             for (int i = 1; i < PMX_PR_LANES; ++i)
@@ -257,16 +236,15 @@ static int precise_add_scale(pmx_ctx* c, const uint8_t* imgs, int scaled_h, int 
     }
     // this scale's part: [n][38][oh][ow] | [n][19][oh][ow]
     const size_t opx = (size_t)oh * ow, part_floats = opx * 57 * n;
-    if (part_floats > c->pr_part_cap || (size_t)k >= c->pr_part.size()) {
-        if (part_floats > c->pr_part_cap) {           // a larger sequence than any before: all parts are re-made (nothing of the old ones is pending: k == 0 or synced)
-            PMX_HIP(hipDeviceSynchronize());
-            for (float*& q : c->pr_part) { if (q) (void)hipFree(q); q = nullptr; }
-            c->pr_part_cap = part_floats;
-        }
-        if ((size_t)k >= c->pr_part.size()) c->pr_part.resize(k + 1, nullptr);
+    size_t part_cap = c->pr_part.empty() ? 0 : c->pr_part[0].capacity();      // (every part there is has the size of the first)
+    if (part_floats > part_cap) {                     // a larger sequence than any before: all parts are re-made (nothing of the old ones is pending: k == 0 or synced)
+        PMX_HIP(hipDeviceSynchronize());
+        for (auto& q : c->pr_part) q.reset();
+        part_cap = part_floats;
     }
+    if ((size_t)k >= c->pr_part.size()) c->pr_part.resize(k + 1);
     for (size_t j = 0; j <= (size_t)k; ++j)
-        if (!c->pr_part[j]) PMX_HIP(hipMalloc((void**)&c->pr_part[j], c->pr_part_cap * sizeof(float)));
+        if (!c->pr_part[j] && (rc = c->pr_part[j].alloc(part_cap))) return rc;
     float* const part_paf = c->pr_part[k];
     float* const part_heat = part_paf + opx * PMX_N_PAF * n;
     if ((rc = lane_ensure(c, li, (size_t)n, (size_t)ph, (size_t)pw))) return rc;
@@ -311,13 +289,7 @@ static int precise_add_scale(pmx_ctx* c, const uint8_t* imgs, int scaled_h, int 
         // (3) x8 cubic up-sampling of the PAF (38) and heat (19) channels of all images into PLANAR temporaries [n][38][ph][pw] | [n][19][ph][pw]
         // (two cv2.resize calls per image in the reference; planar so that step (4) reads rows of one channel and both steps store full rows)
         const size_t ppx = (size_t)ph * pw, ntmp = ppx * 57 * n;
-        if (ntmp > c->pr_tmp_cap) {
-            PMX_HIP(hipStreamSynchronize(c->stream));
-            if (c->pr_tmp) (void)hipFree(c->pr_tmp);
-            c->pr_tmp = nullptr; c->pr_tmp_cap = 0;
-            PMX_HIP(hipMalloc((void**)&c->pr_tmp, ntmp * sizeof(float)));
-            c->pr_tmp_cap = ntmp;
-        }
+        if ((rc2 = c->pr_tmp.ensure(ntmp, c->stream))) return rc2;
         float* const t_paf = c->pr_tmp;
         float* const t_heat = c->pr_tmp + ppx * PMX_N_PAF * n;
         const long long sy = (long long)fw * PMX_CAT_C, sx = PMX_CAT_C, sb = (long long)fh * fw * PMX_CAT_C;
@@ -359,8 +331,10 @@ extern "C" int pmx_precise_finish(pmx_ctx* c)
         if (c->pr_lane[i].done) PMX_HIP(hipStreamWaitEvent(c->stream, c->pr_lane[i].done, 0));
     PMX_CHECK(c->pr_scales <= 8, PMX_ERR_CAPACITY, "pmx_precise_finish: %d scales (at most 8 per sequence)", c->pr_scales);
     PMX_CHECK(c->pr_mask == (1u << c->pr_scales) - 1u, PMX_ERR_STATE, "pmx_precise_finish: the slots of the sequence have gaps (mask 0x%x, %d scales)", c->pr_mask, c->pr_scales);
-    if ((rc = launch_sum_parts_f32(c->ext_paf, c->pr_part.data(), c->pr_scales, 0, n * PMX_N_PAF, (float)c->pr_scales, c->stream))) return rc;
-    if ((rc = launch_sum_parts_f32(c->ext_heat, c->pr_part.data(), c->pr_scales, n * PMX_N_PAF, n * PMX_N_HEAT, (float)c->pr_scales, c->stream))) return rc;
+    const float* parts[8];
+    for (int k = 0; k < c->pr_scales; ++k) parts[k] = c->pr_part[k];
+    if ((rc = launch_sum_parts_f32(c->ext_paf, parts, c->pr_scales, 0, n * PMX_N_PAF, (float)c->pr_scales, c->stream))) return rc;
+    if ((rc = launch_sum_parts_f32(c->ext_heat, parts, c->pr_scales, n * PMX_N_PAF, n * PMX_N_HEAT, (float)c->pr_scales, c->stream))) return rc;
     PMX_HIP(hipEventRecord(c->pr_fin, c->stream));
     c->maps_valid = true; c->maps_external = true;
     c->cur_B = c->pr_n; c->cur_fh = c->pr_h; c->cur_fw = c->pr_w;
@@ -391,22 +365,8 @@ extern "C" int pmx_keypoints(pmx_ctx* c, int B, int out_h, int out_w, double thr
         m.sbh = fhw * c->cat_c; m.sbp = 0;
     }
     m.fh = c->cur_fh; m.fw = c->cur_fw;
-    const size_t need = (size_t)B * n_ch * out_h * out_w;
-    if (need > c->smoothed_cap) {
-        PMX_HIP(hipStreamSynchronize(c->stream));
-        if (c->pp.smoothed) (void)hipFree(c->pp.smoothed);
-        c->pp.smoothed = nullptr;
-        PMX_HIP(hipMalloc((void**)&c->pp.smoothed, need * sizeof(float)));
-        c->smoothed_cap = need;
-    }
     const size_t nkp = (size_t)B * n_ch * 4;
-    if (nkp > c->kp_cap) {
-        PMX_HIP(hipStreamSynchronize(c->stream));
-        if (c->d_kp) (void)hipFree(c->d_kp);
-        c->d_kp = nullptr;
-        PMX_HIP(hipMalloc((void**)&c->d_kp, nkp * sizeof(double)));
-        c->kp_cap = nkp;
-    }
+    if ((rc = pmx_ensure_smoothed(c, (size_t)B * n_ch * out_h * out_w)) || (rc = c->d_kp.ensure(nkp, c->stream))) return rc;
     if ((rc = pp_keypoints_launch(m, c->tab, c->pp, B, n_ch, out_h, out_w, thresh, c->d_kp, c->stream))) return rc;
     PMX_HIP(hipMemcpyAsync(out, c->d_kp, nkp * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     PMX_HIP(hipStreamSynchronize(c->stream));

@@ -211,19 +211,6 @@ __global__ __launch_bounds__(256) void pi_average_kernel(const float* __restrict
     }
 }
 
-template <typename T>
-int grow(T** p, size_t* cap, size_t need, hipStream_t s)
-{
-    if (need <= *cap) return PMX_OK;
-    PMX_HIP(hipStreamSynchronize(s));             // (launches of the previous call may still read the old buffer)
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; *cap = 0;
-    const size_t want = need + need / 4;
-    PMX_HIP(hipMalloc((void**)p, want * sizeof(T)));
-    *cap = want;
-    return PMX_OK;
-}
-
 struct HostPair { int img, slot, ph, pw; };
 
 }  // namespace
@@ -388,8 +375,10 @@ extern "C" int pmx_detect_precise_images(pmx_ctx* c, const pmx_precise_image* im
 
     // ---- device buffers (grown on demand; the context's own buffers were checked above)
     PMX_DEV(c);
-    if ((rc = grow(&c->pi_dev, &c->pi_dev_cap, total, c->stream)) || (rc = grow(&c->pi_src, &c->pi_src_cap, (size_t)src_bytes, c->stream)) ||
-        (rc = grow(&c->pi_tmp, &c->pi_tmp_cap, (size_t)tmp_floats, c->stream)) || (rc = grow(&c->pi_maps, &c->pi_maps_cap, (size_t)maps_floats, c->stream)))
+    // a buffer too small grows to a quarter more than asked (launches of the previous call may still read the old one: ensure synchronises)
+    auto grow = [c](auto& b, size_t need) { return need <= b.capacity() ? PMX_OK : b.ensure(need + need / 4, c->stream); };
+    if ((rc = grow(c->pi_dev, total)) || (rc = grow(c->pi_src, (size_t)src_bytes)) || (rc = grow(c->pi_tmp, (size_t)tmp_floats)) ||
+        (rc = grow(c->pi_maps, (size_t)maps_floats)))
         return rc;
     const PiPair* d_pairs = reinterpret_cast<const PiPair*>(c->pi_dev + o_pairs);
     const PiImage* d_imgs = reinterpret_cast<const PiImage*>(c->pi_dev + o_imgs);
@@ -403,7 +392,7 @@ extern "C" int pmx_detect_precise_images(pmx_ctx* c, const pmx_precise_image* im
             PMX_HIP(hipMemcpyAsync(c->pi_src + src_off[i], imgs[i].bgr, (size_t)imgs[i].orig_h * imgs[i].orig_w * 3, hipMemcpyHostToDevice, c->stream));
         int r;
         if ((r = pmx_prof_begin(c, "precise_input|pi_input_kernel", (double)px0 * 3 * 2))) return r;
-        hipLaunchKernelGGL(pi_input_kernel, dim3((unsigned)((px0 + 255) / 256)), dim3(256), 0, c->stream, c->pi_src, c->u8_tmp, d_pairs, np, d_tab, px0);
+        hipLaunchKernelGGL(pi_input_kernel, dim3((unsigned)((px0 + 255) / 256)), dim3(256), 0, c->stream, c->pi_src.get(), c->u8_tmp.get(), d_pairs, np, d_tab, px0);
         PMX_HIP(hipGetLastError());
         return pmx_prof_end(c);
     };
@@ -414,11 +403,11 @@ extern "C" int pmx_detect_precise_images(pmx_ctx* c, const pmx_precise_image* im
     c->maps_valid = false;                            // the cat buffer holds single scales: the averaged maps are pmx_get_precise_image_maps'
     c->cur_segs.clear();
     if ((rc = pmx_prof_begin(c, "precise_upsample|pi_upsample_kernel", (double)px3 * PI_CH * 4 + (double)tmp_floats * 4))) return rc;
-    hipLaunchKernelGGL(pi_upsample_kernel, dim3((unsigned)up_blocks), dim3(256), 0, c->stream, c->cat, c->pi_tmp, d_pairs, np, d_tab);
+    hipLaunchKernelGGL(pi_upsample_kernel, dim3((unsigned)up_blocks), dim3(256), 0, c->stream, c->cat.get(), c->pi_tmp.get(), d_pairs, np, d_tab);
     PMX_HIP(hipGetLastError());
     if ((rc = pmx_prof_end(c))) return rc;
     if ((rc = pmx_prof_begin(c, "precise_average|pi_average_kernel", (double)maps_floats * 4))) return rc;
-    hipLaunchKernelGGL(pi_average_kernel, dim3((unsigned)dn_blocks), dim3(256), 0, c->stream, c->pi_tmp, c->pi_maps, d_pairs, d_imgs, n, d_tab);
+    hipLaunchKernelGGL(pi_average_kernel, dim3((unsigned)dn_blocks), dim3(256), 0, c->stream, c->pi_tmp.get(), c->pi_maps.get(), d_pairs, d_imgs, n, d_tab);
     PMX_HIP(hipGetLastError());
     if ((rc = pmx_prof_end(c))) return rc;
     c->pi_off.assign(n, 0); c->pi_hw.assign(2 * (size_t)n, 0);
@@ -482,6 +471,6 @@ extern "C" int pmx_get_precise_image_maps(pmx_ctx* c, int image, float* paf, flo
 extern "C" int pmx_precise_images_table_bytes(pmx_ctx* c, size_t* bytes)
 {
     PMX_CHECK(c && bytes, PMX_ERR_INVALID, "null arg");
-    *bytes = c->pi_dev_cap;
+    *bytes = c->pi_dev.capacity();
     return PMX_OK;
 }
