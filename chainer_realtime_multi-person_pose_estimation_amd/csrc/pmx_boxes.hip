@@ -13,6 +13,12 @@
 //   pmx_keypoints_boxes       both, chunked by the context's batch capacity, enqueued back to back: one image upload, one staging copy,
 //                             one D2H copy and one stream synchronisation per call.
 //
+//   pmx_forward_u8_boxes_images / pmx_keypoints_boxes_images
+//                             the same for boxes of MANY images (the people of a batch of frames): a sixth box column names the box's
+//                             image, box_gather_resize_u8_images_kernel reads it through a device table (address, height, width per
+//                             image) that travels in the call's staging copy, and chunks of the batch capacity are taken in box order
+//                             across image borders.  One upload per referenced image, enqueued back to back, no synchronisation between.
+//
 // Bit-identity: per crop the bytes of the network input equal host crop_image (+ [:, ::-1]) + pmx_forward_u8_resized, and the key points
 // equal pmx_keypoints on the same maps with the crop's size and "kp_flip_x" (tests/test_gpu_face_hand_boxes.py).  Gaussian radii other
 // than 10, the reference's GPU peak branch and the "pp_generic" switch take a per-crop loop over pp_keypoints_launch instead.
@@ -25,7 +31,9 @@
 
 namespace {
 
-struct BoxDesc { int left, top, w, h, flip, pad0, pad1, pad2; };       // crop of the image (w x h from (left, top)), mirrored if flip
+struct BoxDesc { int left, top, w, h, flip, img, pad1, pad2; };        // crop of image `img` (w x h from (left, top)), mirrored if flip
+
+struct BoxImg { const uint8_t* px; int h, w; };                        // one image of a many-image call: h x w x 3 uint8 on the device
 
 struct KpCrop {                 // one crop of pmx_keypoints_images: its up-sampling tables (device pointers into the staging buffer)
     PPTables tab;
@@ -64,6 +72,36 @@ __global__ __launch_bounds__(256) void box_gather_resize_u8_kernel(const uint8_t
     for (int c = 0; c < 3; ++c) {
         const int S0 = box_px(img, img_h, img_w, d, sy0, sx0, c) * a0 + box_px(img, img_h, img_w, d, sy0, sx1, c) * a1;
         const int S1 = box_px(img, img_h, img_w, d, sy1, sx0, c) * a0 + box_px(img, img_h, img_w, d, sy1, sx1, c) * a1;
+        int v = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2;
+        v = v < 0 ? 0 : (v > 255 ? 255 : v);
+        o[c] = (uint8_t)v;
+    }
+}
+
+// the same for crops of many images: crop b reads image desc[b].img of the table `imgs` (index checked on the host).  One launch per chunk
+// whatever images its crops come from; per crop the arithmetic, and so the bytes, of box_gather_resize_u8_kernel on that image alone.
+__global__ __launch_bounds__(256) void box_gather_resize_u8_images_kernel(const BoxImg* __restrict__ imgs, const BoxDesc* __restrict__ desc,
+                                                                          const int* __restrict__ tabs, int n, int dh, int dw,
+                                                                          uint8_t* __restrict__ dst)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long npix = (long long)n * dh * dw;
+    if (i >= npix) return;
+    const int x = (int)(i % dw);
+    const long long t = i / dw;
+    const int y = (int)(t % dh);
+    const int b = (int)(t / dh);
+    const BoxDesc d = desc[b];
+    const BoxImg im = imgs[d.img];
+    const int* xtab = tabs + (long long)b * 4 * (dw + dh);
+    const int* ytab = xtab + 4 * dw;
+    const int sx0 = xtab[x], sx1 = xtab[dw + x], a0 = xtab[2 * dw + x], a1 = xtab[3 * dw + x];
+    const int sy0 = ytab[y], sy1 = ytab[dh + y], b0 = ytab[2 * dh + y], b1 = ytab[3 * dh + y];
+    uint8_t* o = dst + i * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int S0 = box_px(im.px, im.h, im.w, d, sy0, sx0, c) * a0 + box_px(im.px, im.h, im.w, d, sy0, sx1, c) * a1;
+        const int S1 = box_px(im.px, im.h, im.w, d, sy1, sx0, c) * a0 + box_px(im.px, im.h, im.w, d, sy1, sx1, c) * a1;
         int v = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2;
         v = v < 0 ? 0 : (v > 255 ? 255 : v);
         o[c] = (uint8_t)v;
@@ -187,12 +225,13 @@ int stage_upload(pmx_ctx* c, const Stage& st)
     return PMX_OK;
 }
 
-int check_boxes(const int* boxes, int n)
+// rows of `stride` ints: 5 (left, top, right, bottom, flip) or 6 (+ image index, checked by check_box_images)
+int check_boxes(const int* boxes, int n, int stride = 5)
 {
     PMX_CHECK(n >= 0, PMX_ERR_INVALID, "boxes: n = %d", n);
     PMX_CHECK(n == 0 || boxes, PMX_ERR_INVALID, "boxes: null pointer");
     for (int i = 0; i < n; ++i) {
-        const int* b = boxes + 5 * i;
+        const int* b = boxes + stride * i;
         const long long w = (long long)b[2] - b[0], h = (long long)b[3] - b[1];
         PMX_CHECK(w >= 1 && h >= 1, PMX_ERR_INVALID, "box %d: empty (left %d, top %d, right %d, bottom %d)", i, b[0], b[1], b[2], b[3]);
         PMX_CHECK(w <= INT_MAX && h <= INT_MAX && w * h < (1ll << 31), PMX_ERR_INVALID, "box %d: extent %lld x %lld outside int32", i, w, h);
@@ -202,13 +241,13 @@ int check_boxes(const int* boxes, int n)
 }
 
 // gather + resize tables of n boxes (staged) -> offsets of the descriptors and tables
-void stage_boxes(Stage& st, const int* boxes, int n, int dh, int dw, size_t* desc_off, size_t* tab_off)
+void stage_boxes(Stage& st, const int* boxes, int n, int dh, int dw, size_t* desc_off, size_t* tab_off, int stride = 5)
 {
     std::vector<BoxDesc> d(n);
     std::vector<int> tabs((size_t)n * 4 * (dw + dh));
     for (int i = 0; i < n; ++i) {
-        const int* b = boxes + 5 * i;
-        d[i] = BoxDesc{b[0], b[1], b[2] - b[0], b[3] - b[1], b[4], 0, 0, 0};
+        const int* b = boxes + stride * i;
+        d[i] = BoxDesc{b[0], b[1], b[2] - b[0], b[3] - b[1], b[4], stride == 6 ? b[5] : 0, 0, 0};
         int* t = tabs.data() + (size_t)i * 4 * (dw + dh);
         pmx_make_resize_table(dw, d[i].w, t);
         pmx_make_resize_table(dh, d[i].h, t + 4 * dw);
@@ -396,6 +435,71 @@ int forward_chunk(pmx_ctx* c, const uint8_t* d_img, int img_h, int img_w, size_t
     return pmx_forward_u8(c, c->u8_tmp, B, dh, dw, 1);
 }
 
+// ---- boxes of many images
+// every box names an image of the list, and every image a box names exists (an image no box refers to is never looked at)
+int check_box_images(const pmx_box_image* images, int n_images, const int* boxes6, int n)
+{
+    PMX_CHECK(n_images >= 1 && images, PMX_ERR_INVALID, "boxes: %d images for %d boxes", images ? n_images : 0, n);
+    for (int i = 0; i < n; ++i) {
+        const int k = boxes6[6 * i + 5];
+        PMX_CHECK(k >= 0 && k < n_images, PMX_ERR_INVALID, "box %d: image index %d outside 0..%d", i, k, n_images - 1);
+        PMX_CHECK(images[k].bgr && images[k].h >= 1 && images[k].w >= 1, PMX_ERR_INVALID, "image %d (of box %d): %s, %d x %d", k, i,
+                  images[k].bgr ? "bad size" : "null pointer", images[k].h, images[k].w);
+    }
+    return PMX_OK;
+}
+
+// the image table of a call, staged (-> *imgs_off), and the uploads it needs: host images that a box refers to get a place in u8_src
+// (64-bit byte offsets, 256-aligned), device images are used where they are
+struct ImageCopy { size_t off; const uint8_t* src; size_t bytes; };
+
+int stage_images(pmx_ctx* c, Stage& st, const pmx_box_image* images, int n_images, int on_device, const int* boxes6, int n,
+                 size_t* imgs_off, std::vector<ImageCopy>* copies)
+{
+    std::vector<char> used(n_images, 0);
+    for (int i = 0; i < n; ++i) used[boxes6[6 * i + 5]] = 1;
+    size_t total = 0;
+    copies->clear();
+    if (!on_device)
+        for (int k = 0; k < n_images; ++k)
+            if (used[k]) {
+                const size_t bytes = (size_t)images[k].h * images[k].w * 3;
+                copies->push_back(ImageCopy{total, images[k].bgr, bytes});
+                total += (bytes + 255) / 256 * 256;
+            }
+    int rc;
+    if (total && (rc = c->u8_src.ensure(total, c->stream))) return rc;
+    std::vector<BoxImg> tab(n_images, BoxImg{nullptr, 0, 0});
+    size_t next = 0;
+    for (int k = 0; k < n_images; ++k)
+        if (used[k]) tab[k] = BoxImg{on_device ? images[k].bgr : c->u8_src + (*copies)[next++].off, images[k].h, images[k].w};
+    *imgs_off = st.put(tab.data(), tab.size() * sizeof(BoxImg));
+    return PMX_OK;
+}
+
+// one copy per referenced host image, back to back on the context's stream: nothing waits in between
+int upload_images(pmx_ctx* c, const std::vector<ImageCopy>& copies)
+{
+    for (const ImageCopy& cp : copies) PMX_HIP(hipMemcpyAsync(c->u8_src + cp.off, cp.src, cp.bytes, hipMemcpyHostToDevice, c->stream));
+    if (!copies.empty()) c->pr_src = nullptr;      // (u8_src no longer holds a detect_precise original)
+    return PMX_OK;
+}
+
+// forward_chunk for boxes of many images
+int forward_chunk_images(pmx_ctx* c, size_t imgs_off, size_t desc_off, size_t tab_off, int k0, int B)
+{
+    const int dh = c->max_h, dw = c->max_w;
+    int rc;
+    const long long npix = (long long)B * dh * dw;
+    if ((rc = pmx_prof_begin(c, "resize_boxes|box_gather_resize_u8_images_kernel", (double)npix * 3 * 2))) return rc;
+    hipLaunchKernelGGL(box_gather_resize_u8_images_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, c->stream,
+                       reinterpret_cast<const BoxImg*>(c->bx_dev + imgs_off), reinterpret_cast<const BoxDesc*>(c->bx_dev + desc_off) + k0,
+                       reinterpret_cast<const int*>(c->bx_dev + tab_off) + (size_t)k0 * 4 * (dw + dh), B, dh, dw, c->u8_tmp.get());
+    PMX_HIP(hipGetLastError());
+    if ((rc = pmx_prof_end(c))) return rc;
+    return pmx_forward_u8(c, c->u8_tmp, B, dh, dw, 1);
+}
+
 }  // namespace
 
 extern "C" int pmx_forward_u8_boxes(pmx_ctx* c, const uint8_t* img, int img_h, int img_w, int on_device, const int* boxes, int n)
@@ -470,6 +574,69 @@ extern "C" int pmx_keypoints_boxes(pmx_ctx* c, const uint8_t* img, int img_h, in
         const int B = n - k0 < c->max_batch ? n - k0 : c->max_batch;
         if ((rc = forward_chunk(c, d, img_h, img_w, desc_off, tab_off, k0, B))) return rc;
         PMX_CHECK(c->cur_fh == fh && c->cur_fw == fw, PMX_ERR_STATE, "pmx_keypoints_boxes: maps of %d x %d, expected %d x %d", c->cur_fh, c->cur_fw, fh, fw);
+        if ((rc = kp_enqueue_chunk(c, ks, hwf.data(), k0, B, thresh))) return rc;
+    }
+    return kp_finish(c, ks, n, thresh, out);
+}
+
+extern "C" int pmx_forward_u8_boxes_images(pmx_ctx* c, const pmx_box_image* images, int n_images, int on_device, const int* boxes6, int n)
+{
+    PMX_CHECK(c, PMX_ERR_INVALID, "null ctx");
+    PMX_CHECK(c->kind != NET_POSE, PMX_ERR_STATE, "pmx_forward_u8_boxes_images: facenet / handnet only");
+    PMX_CHECK(n >= 1 && n <= c->max_batch, PMX_ERR_CAPACITY, "pmx_forward_u8_boxes_images: %d boxes outside 1..%d", n, c->max_batch);
+    int rc;
+    if ((rc = check_boxes(boxes6, n, 6))) return rc;
+    if ((rc = check_box_images(images, n_images, boxes6, n))) return rc;
+    PMX_DEV(c);
+    Stage st;
+    size_t desc_off, tab_off, imgs_off;
+    std::vector<ImageCopy> copies;
+    stage_boxes(st, boxes6, n, c->max_h, c->max_w, &desc_off, &tab_off, 6);
+    if ((rc = stage_images(c, st, images, n_images, on_device, boxes6, n, &imgs_off, &copies))) return rc;
+    if ((rc = upload_images(c, copies))) return rc;
+    if ((rc = stage_upload(c, st))) return rc;
+    return forward_chunk_images(c, imgs_off, desc_off, tab_off, 0, n);
+}
+
+extern "C" int pmx_keypoints_boxes_images(pmx_ctx* c, const pmx_box_image* images, int n_images, int on_device, const int* boxes6, int n,
+                                          double thresh, double* out)
+{
+    PMX_CHECK(c, PMX_ERR_INVALID, "null ctx");
+    PMX_CHECK(c->kind != NET_POSE, PMX_ERR_STATE, "pmx_keypoints_boxes_images: facenet / handnet only");
+    int rc;
+    if ((rc = check_boxes(boxes6, n, 6))) return rc;
+    if (n == 0) return PMX_OK;
+    if ((rc = check_box_images(images, n_images, boxes6, n))) return rc;
+    PMX_CHECK(out, PMX_ERR_INVALID, "pmx_keypoints_boxes_images: null output");
+    if ((rc = pmx_check_weights(c))) return rc;
+    PMX_DEV(c);
+    const int fh = c->max_h / 8, fw = c->max_w / 8;      // the maps of a max_h x max_w input
+    std::vector<int> hwf(3 * (size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const int* b = boxes6 + 6 * i;
+        hwf[3 * i] = b[3] - b[1]; hwf[3 * i + 1] = b[2] - b[0]; hwf[3 * i + 2] = b[4];
+    }
+    Stage st;
+    size_t desc_off, tab_off, imgs_off;
+    std::vector<ImageCopy> copies;
+    stage_boxes(st, boxes6, n, c->max_h, c->max_w, &desc_off, &tab_off, 6);
+    KpStage ks;
+    {
+        // kp_prepare builds the grids against the maps' size: that of the forwards below
+        const int sh = c->cur_fh, sw = c->cur_fw;
+        c->cur_fh = fh; c->cur_fw = fw;
+        rc = kp_prepare(c, st, hwf.data(), n, &ks);
+        c->cur_fh = sh; c->cur_fw = sw;
+        if (rc) return rc;
+    }
+    if ((rc = stage_images(c, st, images, n_images, on_device, boxes6, n, &imgs_off, &copies))) return rc;
+    if ((rc = stage_fix_pointers(c, st, ks, n))) return rc;
+    if ((rc = upload_images(c, copies))) return rc;
+    if ((rc = stage_upload(c, st))) return rc;
+    for (int k0 = 0; k0 < n; k0 += c->max_batch) {       // chunks in box order, across image borders
+        const int B = n - k0 < c->max_batch ? n - k0 : c->max_batch;
+        if ((rc = forward_chunk_images(c, imgs_off, desc_off, tab_off, k0, B))) return rc;
+        PMX_CHECK(c->cur_fh == fh && c->cur_fw == fw, PMX_ERR_STATE, "pmx_keypoints_boxes_images: maps of %d x %d, expected %d x %d", c->cur_fh, c->cur_fw, fh, fw);
         if ((rc = kp_enqueue_chunk(c, ks, hwf.data(), k0, B, thresh))) return rc;
     }
     return kp_finish(c, ks, n, thresh, out);

@@ -4,7 +4,10 @@ the same MI355X conv kernels as the pose network (single-branch CPM, models/Face
     FaceDetector(arch='facenet', weights_file=None, model=None, device=-1)(face_img, fast_mode=False) -> 70 key points
     HandDetector(arch='handnet', weights_file=None, model=None, device=-1)(hand_img, fast_mode=False, hand_type="right") -> 21
     FaceDetector.detect_boxes(img, bboxes) / HandDetector.detect_boxes(img, bboxes, hand_types) -> one such list per box of ONE image
+    FaceDetector.detect_boxes_batch(imgs, bboxes_per_image) / HandDetector.detect_boxes_batch(imgs, bboxes_per_image, hand_types_per_image)
+        -> per image what detect_boxes returns, all boxes of all images in one call (full network batches across image borders)
     detect_person_parts(pose_detector, face_detector, hand_detector, img, poses) -> the face / hand key points of every person (demo.py)
+    detect_people_parts(pose_detector, face_detector, hand_detector, imgs, poses_per_image) -> the same for a list of images at once
 
 A key point is `[x, y, confidence]` (ints, np.float32) or `None` when the smoothed maximum does not exceed the threshold,
 in the pixel frame of the crop that was passed in -- exactly the reference's return value.  The whole path runs on the
@@ -144,6 +147,59 @@ class _KeypointDetector(object):
         return [_keypoint_list(kp) for kp in kps]
 
 
+    def _detect_boxes_batch(self, imgs, bboxes_per_image, flips_per_image):
+        """_detect_boxes for the boxes of MANY images (any sizes) in one call: one list per image of one key-point list per box.  The
+        crops of all images run through the network in chunks of the engine's batch, taken in box order across image borders."""
+        if len(bboxes_per_image) != len(imgs) or len(flips_per_image) != len(imgs):
+            raise ValueError('one list of boxes (and of hand types) per image')
+        imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in imgs]
+        for im in imgs:
+            if im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError('detect_boxes_batch needs uint8 H x W x 3 images')
+        boxes = []
+        for i, (bbs, flips) in enumerate(zip(bboxes_per_image, flips_per_image)):
+            if len(flips) != len(bbs):
+                raise ValueError('one hand type per box')
+            boxes.extend((int(b[0]), int(b[1]), int(b[2]), int(b[3]), int(f), i) for b, f in zip(bbs, flips))
+        for k, b in enumerate(boxes):          # (the library checks too; here before the engine may grow)
+            if b[2] <= b[0] or b[3] <= b[1]:
+                raise native.PmxError(1, 'box %d (image %d): empty (left %d, top %d, right %d, bottom %d)' % ((k, b[5]) + b[:4]))
+        counts = [len(bbs) for bbs in bboxes_per_image]
+        if not boxes:
+            return [[] for _ in imgs]
+        thresh = params[self.THRESH_KEY]
+        if self.model is None:
+            if self.engine.weights_missing():
+                raise RuntimeError('%s has no weights: pass weights_file=, weights= or model=' % type(self).__name__)
+            self._grow(len(boxes))
+            # (an image without boxes is not handed over: the library neither reads nor uploads it)
+            kps = self.engine.keypoints_boxes_images([im if n else None for im, n in zip(imgs, counts)], boxes, thresh)
+        else:
+            # `model=` seam as in _detect_boxes: the callable per crop, the key points of all crops in chunks of pmx_keypoints_images
+            from .pose_detector import PoseDetector
+            size = params[self.SIZE_KEY]
+            heats = []
+            for b in boxes:
+                crop = PoseDetector.crop_image(None, imgs[b[5]], b[:4])
+                if b[4]:
+                    crop = crop[:, ::-1]
+                resized = self.engine.resize_u8(np.ascontiguousarray(crop)[None], size, size)[0]
+                x = np.array(resized[np.newaxis], dtype=np.float32).transpose(0, 3, 1, 2) / 256 - 0.5
+                hs = self.model(x)
+                heats.append(np.asarray(getattr(hs[-1], 'data', hs[-1]), dtype=np.float32)[0])
+            kps = []
+            for k0 in range(0, len(boxes), self.max_batch):
+                chunk = boxes[k0:k0 + self.max_batch]
+                self._grow(len(chunk))
+                self.engine.set_heat(np.stack(heats[k0:k0 + self.max_batch]))
+                kps.extend(self.engine.keypoints_images([(b[3] - b[1], b[2] - b[0], b[4]) for b in chunk], thresh))
+        out, k = [], 0
+        for n in counts:
+            out.append([_keypoint_list(kp) for kp in kps[k:k + n]])
+            k += n
+        return out
+
+
 def _keypoint_list(kp):
     out = []
     for x, y, conf, valid in kp:
@@ -162,6 +218,11 @@ class FaceDetector(_KeypointDetector):
         """`[self(PoseDetector.crop_image(img, bbox)) for bbox in bboxes]` in one batched call (boxes (left, top, right, bottom) in image
         pixels, zero padding outside the image): one list of 70 key points (or None) per box, in the box's own pixel frame."""
         return self._detect_boxes(img, bboxes, [0] * len(bboxes))
+
+    def detect_boxes_batch(self, imgs, bboxes_per_image):
+        """`[self.detect_boxes(img, bboxes) for img, bboxes in zip(imgs, bboxes_per_image)]` in ONE call: the crops of all images (of
+        any sizes) fill the network's batches together."""
+        return self._detect_boxes_batch(imgs, bboxes_per_image, [[0] * len(b) for b in bboxes_per_image])
 
 
 class HandDetector(_KeypointDetector):
@@ -182,6 +243,13 @@ class HandDetector(_KeypointDetector):
         if len(hand_types) != len(bboxes):
             raise ValueError('one hand type per box')
         return self._detect_boxes(img, bboxes, [1 if t == "left" else 0 for t in hand_types])
+
+    def detect_boxes_batch(self, imgs, bboxes_per_image, hand_types_per_image):
+        """`[self.detect_boxes(img, bboxes, types) for img, bboxes, types in zip(...)]` in ONE call: the crops of all images (of any
+        sizes) fill the network's batches together."""
+        if len(hand_types_per_image) != len(bboxes_per_image) or any(len(t) != len(b) for t, b in zip(hand_types_per_image, bboxes_per_image)):
+            raise ValueError('one hand type per box')
+        return self._detect_boxes_batch(imgs, bboxes_per_image, [[1 if t == "left" else 0 for t in ts] for ts in hand_types_per_image])
 
 
 # ---- visualisation / crop helpers of the reference modules (host-only; cv2.circle / cv2.line rasters are stand-ins) -----------
@@ -275,3 +343,44 @@ def detect_person_parts(pose_detector, face_detector, hand_detector, img, poses)
     for (p, side), bbox, kps in zip(hand_owner, hand_boxes, hand_detector.detect_boxes(img, hand_boxes, hand_types)):
         persons[p][side] = {'bbox': bbox, 'keypoints': kps}
     return persons
+
+
+def detect_people_parts(pose_detector, face_detector, hand_detector, imgs, poses_per_image):
+    """`[detect_person_parts(pose_detector, face_detector, hand_detector, img, poses) for img, poses in zip(imgs, poses_per_image)]` with
+    ONE detect_boxes_batch call per detector for the whole list (images of any sizes): the face crops of all frames fill the face net's
+    batches together, the hand crops the hand net's.  Works on copies of the poses; every box of every image is computed, and the first
+    error the loop of per-image calls would raise -- in (image, person, face, left, right) order -- is raised, before anything runs on
+    the device."""
+    if len(poses_per_image) != len(imgs):
+        raise ValueError('one array of poses per image')
+    people, face_boxes, face_owner, hand_boxes, hand_types, hand_owner = [], [], [], [], [], []
+    for poses in poses_per_image:
+        poses = np.array(poses, copy=True)
+        persons, fb_i, fo_i, hb_i, ht_i, ho_i = [], [], [], [], [], []
+        for p, pose in enumerate(poses):
+            unit = pose_detector.get_unit_length(pose)                       # demo.py:32
+            persons.append({'unit_length': unit, 'face': None, 'left': None, 'right': None})
+            fb = pose_detector.face_bbox(pose, unit)                          # :36
+            if fb is not None:
+                _serial_box_check(fb)
+                fb_i.append(fb)
+                fo_i.append(p)
+            hb = pose_detector.hand_bboxes(pose, unit)                        # :44
+            for side in ('left', 'right'):
+                if hb[side] is not None:
+                    _serial_box_check(hb[side])
+                    hb_i.append(hb[side])
+                    ht_i.append(side)
+                    ho_i.append((p, side))
+        people.append(persons)
+        face_boxes.append(fb_i); face_owner.append(fo_i)
+        hand_boxes.append(hb_i); hand_types.append(ht_i); hand_owner.append(ho_i)
+    face_kps = face_detector.detect_boxes_batch(imgs, face_boxes)
+    hand_kps = hand_detector.detect_boxes_batch(imgs, hand_boxes, hand_types)
+    for persons, owners, boxes, kps in zip(people, face_owner, face_boxes, face_kps):
+        for p, bbox, kp in zip(owners, boxes, kps):
+            persons[p]['face'] = {'bbox': bbox, 'keypoints': kp}
+    for persons, owners, boxes, kps in zip(people, hand_owner, hand_boxes, hand_kps):
+        for (p, side), bbox, kp in zip(owners, boxes, kps):
+            persons[p][side] = {'bbox': bbox, 'keypoints': kp}
+    return people

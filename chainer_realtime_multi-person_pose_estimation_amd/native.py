@@ -65,6 +65,11 @@ class PmxPreciseImage(C.Structure):
     _fields_ = [('bgr', C.c_void_p), ('orig_h', C.c_int), ('orig_w', C.c_int), ('n_scales', C.c_int), ('scaled_hw', C.c_int * 16)]
 
 
+class PmxBoxImage(C.Structure):
+    """include/pose_mi355x.h::pmx_box_image -- one image of a many-image box call (pmx_keypoints_boxes_images)."""
+    _fields_ = [('bgr', C.c_void_p), ('h', C.c_int), ('w', C.c_int)]
+
+
 class PmxError(RuntimeError):
     def __init__(self, code, msg):
         RuntimeError.__init__(self, 'libpose_mi355x error %d: %s' % (code, msg))
@@ -253,6 +258,8 @@ def load():
         'pmx_forward_u8_boxes': (ci, [vp, vp, ci, ci, ci, vp, ci]),
         'pmx_keypoints_images': (ci, [vp, ci, vp, cd, vp]),
         'pmx_keypoints_boxes': (ci, [vp, vp, ci, ci, ci, vp, ci, cd, vp]),
+        'pmx_forward_u8_boxes_images': (ci, [vp, vp, ci, ci, vp, ci]),
+        'pmx_keypoints_boxes_images': (ci, [vp, vp, ci, ci, vp, ci, cd, vp]),
         'pmx_precise_begin': (ci, [vp, ci, ci]),
         'pmx_precise_add_scale': (ci, [vp, vp, ci, ci]),
         'pmx_precise_finish': (ci, [vp]),
@@ -591,6 +598,61 @@ class Engine(object):
         out = np.empty((len(b), self.n_heat - 1, 4), np.float64)
         self._check(self.lib.pmx_keypoints_boxes(self._ctx, _ptr(img), img.shape[0], img.shape[1], 0, _ptr(b), len(b), float(thresh),
                                                  _ptr(out)))
+        if len(b):
+            self._B = min(len(b) - (len(b) - 1) // self.max_batch * self.max_batch, self.max_batch)
+            self._fhw = (self.max_h // 8, self.max_w // 8)
+        return out
+
+    # ---- the same for boxes of many images (pmx_forward_u8_boxes_images / pmx_keypoints_boxes_images) ----
+    @staticmethod
+    def _boxes6(boxes6):
+        """(n, 6) int32 rows (left, top, right, bottom, flip, image); ValueError for values outside int32."""
+        b = np.asarray(boxes6, dtype=np.int64).reshape(-1, 6)
+        if b.size and (b.min() < -2 ** 31 or b.max() > 2 ** 31 - 1):
+            raise ValueError('box coordinates outside int32')
+        return np.ascontiguousarray(b, dtype=np.int32)
+
+    @staticmethod
+    def _box_images(imgs):
+        """imgs: (H, W, 3) uint8 BGR host arrays, torch device tensors of that shape (uint8, contiguous) or None for an image no box
+        refers to -> (the pmx_box_image array, on_device, what keeps the memory alive).  All on the host or all on the device."""
+        keep, arr, dev = [], (PmxBoxImage * max(1, len(imgs)))(), []
+        for i, im in enumerate(imgs):
+            if im is None:
+                continue
+            on = hasattr(im, 'data_ptr')
+            if on:
+                if str(im.dtype) != 'torch.uint8' or not im.is_cuda or not im.is_contiguous():
+                    raise ValueError('image %d: a device image is a contiguous uint8 tensor on the GPU' % i)
+                ptr = im.data_ptr()
+            else:
+                im = np.ascontiguousarray(im, dtype=np.uint8)
+                ptr = im.ctypes.data
+            if len(im.shape) != 3 or im.shape[2] != 3:
+                raise ValueError('image %d: H x W x 3 expected, got %r' % (i, tuple(im.shape)))
+            keep.append(im)
+            dev.append(on)
+            arr[i].bgr, arr[i].h, arr[i].w = ptr, int(im.shape[0]), int(im.shape[1])
+        if dev and any(dev) != all(dev):
+            raise ValueError('the images of one call are all host arrays or all device tensors')
+        return arr, int(bool(dev) and dev[0]), keep
+
+    def forward_u8_boxes_images(self, imgs, boxes6):
+        """forward_u8_boxes for boxes of many images: imgs a list of (H, W, 3) uint8 BGR images of any sizes, boxes6 (n, 6) with the
+        image's index in the last column (n <= max_batch)."""
+        b = self._boxes6(boxes6)
+        arr, on_device, keep = self._box_images(imgs)
+        self._check(self.lib.pmx_forward_u8_boxes_images(self._ctx, arr, len(imgs), on_device, _ptr(b), len(b)))
+        self._B = len(b)
+        self._fhw = (self.max_h // 8, self.max_w // 8)
+
+    def keypoints_boxes_images(self, imgs, boxes6, thresh):
+        """keypoints_boxes for boxes of many images: (n, maps - 1, 4) float64 key-point rows in box order, each in its box's own pixel
+        frame; chunks of max_batch crops in box order across image borders, one synchronisation per call."""
+        b = self._boxes6(boxes6)
+        arr, on_device, keep = self._box_images(imgs)
+        out = np.empty((len(b), self.n_heat - 1, 4), np.float64)
+        self._check(self.lib.pmx_keypoints_boxes_images(self._ctx, arr, len(imgs), on_device, _ptr(b), len(b), float(thresh), _ptr(out)))
         if len(b):
             self._B = min(len(b) - (len(b) - 1) // self.max_batch * self.max_batch, self.max_batch)
             self._fhw = (self.max_h // 8, self.max_w // 8)

@@ -254,6 +254,27 @@ int pmx_keypoints_images(pmx_ctx* ctx, int batch, const int* out_hwf, double thr
 int pmx_keypoints_boxes(pmx_ctx* ctx, const uint8_t* img, int img_h, int img_w, int on_device, const int* boxes, int n,
                         double thresh, double* out);
 
+/* ---- the same for boxes of MANY images (the people of a batch of frames) -----------------------------------------------------------------
+ * images: n_images images of any, differing sizes; host memory (read before the call returns) or, with on_device != 0, device memory on the
+ * context's device.  boxes6: n x 6 int32 (left, top, right, bottom, flip, image): columns 0..4 as above, image = index into `images`.  An
+ * image that no box refers to is allowed; it is neither looked at nor uploaded.  Checked before anything is enqueued, PMX_ERR_INVALID with
+ * the box or the image named: n_images < 1 with n > 0, an image index outside 0 .. n_images - 1, a null or non-positive-size image that a
+ * box refers to, an empty box, a bad flip.  A posenet context: PMX_ERR_STATE.  Per box the network input holds the same bytes, and the key
+ * points are those, of the one-image entries called with that box and its own image alone (same kernels chosen: bit-identical; the f16 mode
+ * makes an image's maps independent of batch size and position). */
+typedef struct pmx_box_image { const uint8_t* bgr; int h, w; } pmx_box_image;   /* h x w x 3 uint8 BGR */
+/* gather + resize + forward of n <= max_batch boxes (1 .. max_batch, else PMX_ERR_CAPACITY); asynchronous. */
+int pmx_forward_u8_boxes_images(pmx_ctx* ctx, const pmx_box_image* images, int n_images, int on_device, const int* boxes6, int n);
+/* boxes -> key points, out: n x (maps - 1) x 4 float64 rows in box order, each in its box's own pixel frame (as pmx_keypoints).  Chunks of
+ * max_batch crops are taken in box order ACROSS image borders: 70 boxes on a batch-32 context are network calls of 32, 32 and 6 crops
+ * whatever images they belong to, each with one gather launch.  Per call, however many images: one staging copy (it carries the image
+ * table -- address, height, width per image; host images are placed in one device store at 64-bit byte offsets -- next to the crop
+ * descriptors and tables), one upload per referenced host image enqueued back to back with no synchronisation between them, one D2H copy
+ * and ONE stream synchronisation.  n == 0: nothing, PMX_OK.  Gaussian radii other than 10, "peaks_gpu_branch" and "pp_generic" fall back to
+ * a per-crop key-point loop as in pmx_keypoints_boxes. */
+int pmx_keypoints_boxes_images(pmx_ctx* ctx, const pmx_box_image* images, int n_images, int on_device, const int* boxes6, int n,
+                               double thresh, double* out);
+
 /* fused: forward_u8 + postprocess (PoseDetector.__call__, pose_detector.py:484-517, for images already
  * at the network input size; cv2.resize at :493 is the identity for them) */
 int pmx_detect_batch(pmx_ctx* ctx, const uint8_t* bgr_nhwc, int batch, int h, int w, int on_device,
