@@ -1,23 +1,24 @@
-// pmx_boxes.hip -- face / hand key points for many boxes of ONE image (the loop of the reference's demo.py:30-55 over the people of a
-// picture: a face crop and two hand crops per person, each through FaceNet / HandNet), batched:
+// pmx_boxes.hip -- face / hand key points for many boxes (the loop of the reference's demo.py:30-55 over the people of a picture: a face
+// crop and two hand crops per person, each through FaceNet / HandNet), batched, for the boxes of any number of images in one call:
 //
-//   pmx_forward_u8_boxes      box_gather_resize_u8_kernel: crop_image (pose_detector.py:401-424: zero outside the image) + the optional
-//                             cv2.flip(img, 1) of a left hand (hand_detector.py:29-30) + cv2.resize to the network input, OpenCV's
+//   pmx_forward_u8_boxes_images   box_gather_resize_u8_images_kernel: crop_image (pose_detector.py:401-424: zero outside the image) + the
+//                             optional cv2.flip(img, 1) of a left hand (hand_detector.py:29-30) + cv2.resize to the network input, OpenCV's
 //                             fixed-point INTER_LINEAR (prep.hip::resize_linear_u8_kernel's arithmetic), every crop of a chunk in one
-//                             launch, straight from the full image -- no crop is materialised; then the network at batch n.
+//                             launch, straight from the full images -- no crop is materialised; then the network at batch n.  A sixth
+//                             box column names the box's image; the kernel reads it through a device table (address, height, width per
+//                             image) that travels in the call's staging copy.
 //   pmx_keypoints_images      kp_tiles_kernel<10>: F.resize_images of the last stage to the crop's own size, the optional left / right mirror
 //                             of the maps (hand_detector.py:46-47), the SciPy-order Gaussian -- pp_smooth.h, the same text as
 //                             pp_peaks_fast_kernel<10> -- over a flat list of 32 x 32 tiles of crops of different sizes, each block
 //                             leaving an arg-max record per (tile, channel) instead of the smoothed map; kp_merge_kernel merges the
 //                             records of a crop (argmax_merge is exact) into the reference's key point, tie quirk included.
-//   pmx_keypoints_boxes       both, chunked by the context's batch capacity, enqueued back to back: one image upload, one staging copy,
-//                             one D2H copy and one stream synchronisation per call.
+//   pmx_keypoints_boxes_images    both, in chunks of the context's batch capacity taken in box order across image borders, enqueued back
+//                             to back: one upload per referenced host image, one staging copy, one D2H copy and one stream
+//                             synchronisation per call.
 //
-//   pmx_forward_u8_boxes_images / pmx_keypoints_boxes_images
-//                             the same for boxes of MANY images (the people of a batch of frames): a sixth box column names the box's
-//                             image, box_gather_resize_u8_images_kernel reads it through a device table (address, height, width per
-//                             image) that travels in the call's staging copy, and chunks of the batch capacity are taken in box order
-//                             across image borders.  One upload per referenced image, enqueued back to back, no synchronisation between.
+//   pmx_forward_u8_boxes / pmx_keypoints_boxes
+//                             the boxes of ONE image: adapters that hand the image over as a table of one, with image 0 on every box.
+//                             There is one implementation (forward_boxes, keypoints_boxes) and one box layout, six columns, in this file.
 //
 // Bit-identity: per crop the bytes of the network input equal host crop_image (+ [:, ::-1]) + pmx_forward_u8_resized, and the key points
 // equal pmx_keypoints on the same maps with the crop's size and "kp_flip_x" (tests/test_gpu_face_hand_boxes.py).  Gaussian radii other
@@ -50,36 +51,8 @@ __device__ __forceinline__ int box_px(const uint8_t* __restrict__ img, int img_h
 }
 
 // one thread per output pixel (3 channels) of n crops resized to dh x dw; tables per crop [x: idx0 | idx1 | coef0 | coef1 (dw each) |
-// y: the same (dh each)], pmx_make_resize_table of (dst, crop extent).  Arithmetic of prep.hip::resize_linear_u8_kernel.
-__global__ __launch_bounds__(256) void box_gather_resize_u8_kernel(const uint8_t* __restrict__ img, int img_h, int img_w,
-                                                                   const BoxDesc* __restrict__ desc, const int* __restrict__ tabs,
-                                                                   int n, int dh, int dw, uint8_t* __restrict__ dst)
-{
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long npix = (long long)n * dh * dw;
-    if (i >= npix) return;
-    const int x = (int)(i % dw);
-    const long long t = i / dw;
-    const int y = (int)(t % dh);
-    const int b = (int)(t / dh);
-    const BoxDesc d = desc[b];
-    const int* xtab = tabs + (long long)b * 4 * (dw + dh);
-    const int* ytab = xtab + 4 * dw;
-    const int sx0 = xtab[x], sx1 = xtab[dw + x], a0 = xtab[2 * dw + x], a1 = xtab[3 * dw + x];
-    const int sy0 = ytab[y], sy1 = ytab[dh + y], b0 = ytab[2 * dh + y], b1 = ytab[3 * dh + y];
-    uint8_t* o = dst + i * 3;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const int S0 = box_px(img, img_h, img_w, d, sy0, sx0, c) * a0 + box_px(img, img_h, img_w, d, sy0, sx1, c) * a1;
-        const int S1 = box_px(img, img_h, img_w, d, sy1, sx0, c) * a0 + box_px(img, img_h, img_w, d, sy1, sx1, c) * a1;
-        int v = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2;
-        v = v < 0 ? 0 : (v > 255 ? 255 : v);
-        o[c] = (uint8_t)v;
-    }
-}
-
-// the same for crops of many images: crop b reads image desc[b].img of the table `imgs` (index checked on the host).  One launch per chunk
-// whatever images its crops come from; per crop the arithmetic, and so the bytes, of box_gather_resize_u8_kernel on that image alone.
+// y: the same (dh each)], pmx_make_resize_table of (dst, crop extent).  Arithmetic of prep.hip::resize_linear_u8_kernel.  Crop b reads
+// image desc[b].img of the table `imgs` (index checked on the host): one launch per chunk whatever images its crops come from.
 __global__ __launch_bounds__(256) void box_gather_resize_u8_images_kernel(const BoxImg* __restrict__ imgs, const BoxDesc* __restrict__ desc,
                                                                           const int* __restrict__ tabs, int n, int dh, int dw,
                                                                           uint8_t* __restrict__ dst)
@@ -195,21 +168,31 @@ __global__ __launch_bounds__(256) void kp_merge_kernel(const ArgMax* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host
+// key-point tables of the crops of a call: where stage_keypoints put them (byte offsets into the staging) and the KpCrop records, whose
+// table pointers stage_upload fills in
+struct KpStage {
+    size_t crops_off = 0, tiles_off = 0, ends_off = 0, gauss_off = 0;
+    int n_tiles = 0;
+    std::vector<int> crop_tile0;        // first tile per crop, n_tiles at the end
+    std::vector<size_t> grid_off;       // per crop: xi0, xi1, xlo, xhi, yi0, yi1, ylo, yhi
+    std::vector<KpCrop> crops;
+};
+
 // the staging of one call, built on the host, copied in one piece; offsets are bytes from the start
 struct Stage {
     std::vector<char> h;
     size_t put(const void* p, size_t bytes)
     {
-        const size_t off = (h.size() + 15) / 16 * 16;
-        h.resize(off + bytes);
+        const size_t off = reserve(bytes);
         if (bytes) memcpy(h.data() + off, p, bytes);
         return off;
     }
     size_t reserve(size_t bytes) { const size_t off = (h.size() + 15) / 16 * 16; h.resize(off + bytes); return off; }
 };
 
-// one H2D copy of the staging; the device copy is valid for the kernels enqueued after it on the context's stream
-int stage_upload(pmx_ctx* c, const Stage& st)
+// one H2D copy of the staging; the device copy is valid for the kernels enqueued after it on the context's stream.  The KpCrop records of
+// `ks` are written here, where the device copy's address is known: their tables are device pointers into it.
+int stage_upload(pmx_ctx* c, Stage& st, KpStage* ks = nullptr)
 {
     const size_t bytes = st.h.size();
     if (!bytes) return PMX_OK;
@@ -217,6 +200,19 @@ int stage_upload(pmx_ctx* c, const Stage& st)
     int rc;
     if (bytes > c->bx_host.capacity() && (rc = c->bx_host.alloc(bytes))) return rc;
     if ((rc = c->bx_dev.ensure(bytes, c->stream))) return rc;      // (queued work may still read the old buffer)
+    if (ks) {
+        char* dev = c->bx_dev.get();
+        for (size_t k = 0; k < ks->crops.size(); ++k) {
+            const size_t* o = &ks->grid_off[8 * k];
+            PPTables& t = ks->crops[k].tab;
+            t.xi0 = reinterpret_cast<int*>(dev + o[0]); t.xi1 = reinterpret_cast<int*>(dev + o[1]);
+            t.xlo = reinterpret_cast<double*>(dev + o[2]); t.xhi = reinterpret_cast<double*>(dev + o[3]);
+            t.yi0 = reinterpret_cast<int*>(dev + o[4]); t.yi1 = reinterpret_cast<int*>(dev + o[5]);
+            t.ylo = reinterpret_cast<double*>(dev + o[6]); t.yhi = reinterpret_cast<double*>(dev + o[7]);
+            t.gauss = reinterpret_cast<double*>(dev + ks->gauss_off);
+        }
+        memcpy(st.h.data() + ks->crops_off, ks->crops.data(), ks->crops.size() * sizeof(KpCrop));
+    }
     if (!c->bx_copied) PMX_HIP(hipEventCreateWithFlags(&c->bx_copied, hipEventDisableTiming));
     memcpy(c->bx_host, st.h.data(), bytes);
     PMX_HIP(hipMemcpyAsync(c->bx_dev, c->bx_host, bytes, hipMemcpyHostToDevice, c->stream));
@@ -225,13 +221,13 @@ int stage_upload(pmx_ctx* c, const Stage& st)
     return PMX_OK;
 }
 
-// rows of `stride` ints: 5 (left, top, right, bottom, flip) or 6 (+ image index, checked by check_box_images)
-int check_boxes(const int* boxes, int n, int stride = 5)
+// rows of 6 ints (left, top, right, bottom, flip, image): the one box layout of this file; the image index is checked by check_box_images
+int check_boxes(const int* boxes6, int n)
 {
     PMX_CHECK(n >= 0, PMX_ERR_INVALID, "boxes: n = %d", n);
-    PMX_CHECK(n == 0 || boxes, PMX_ERR_INVALID, "boxes: null pointer");
+    PMX_CHECK(n == 0 || boxes6, PMX_ERR_INVALID, "boxes: null pointer");
     for (int i = 0; i < n; ++i) {
-        const int* b = boxes + stride * i;
+        const int* b = boxes6 + 6 * i;
         const long long w = (long long)b[2] - b[0], h = (long long)b[3] - b[1];
         PMX_CHECK(w >= 1 && h >= 1, PMX_ERR_INVALID, "box %d: empty (left %d, top %d, right %d, bottom %d)", i, b[0], b[1], b[2], b[3]);
         PMX_CHECK(w <= INT_MAX && h <= INT_MAX && w * h < (1ll << 31), PMX_ERR_INVALID, "box %d: extent %lld x %lld outside int32", i, w, h);
@@ -240,14 +236,37 @@ int check_boxes(const int* boxes, int n, int stride = 5)
     return PMX_OK;
 }
 
+// every box names an image of the list, and every image a box names exists (an image no box refers to is never looked at)
+int check_box_images(const pmx_box_image* images, int n_images, const int* boxes6, int n)
+{
+    PMX_CHECK(n_images >= 1 && images, PMX_ERR_INVALID, "boxes: %d images for %d boxes", images ? n_images : 0, n);
+    for (int i = 0; i < n; ++i) {
+        const int k = boxes6[6 * i + 5];
+        PMX_CHECK(k >= 0 && k < n_images, PMX_ERR_INVALID, "box %d: image index %d outside 0..%d", i, k, n_images - 1);
+        PMX_CHECK(images[k].bgr && images[k].h >= 1 && images[k].w >= 1, PMX_ERR_INVALID, "image %d (of box %d): %s, %d x %d", k, i,
+                  images[k].bgr ? "bad size" : "null pointer", images[k].h, images[k].w);
+    }
+    return PMX_OK;
+}
+
+// the rows of a one-image entry (left, top, right, bottom, flip) in this file's layout: image 0 on every box
+int boxes_of_image0(const int* boxes, int n, std::vector<int>* boxes6)
+{
+    PMX_CHECK(n >= 0, PMX_ERR_INVALID, "boxes: n = %d", n);
+    PMX_CHECK(n == 0 || boxes, PMX_ERR_INVALID, "boxes: null pointer");
+    boxes6->assign(6 * (size_t)n, 0);
+    for (int i = 0; i < n; ++i) memcpy(boxes6->data() + 6 * (size_t)i, boxes + 5 * (size_t)i, 5 * sizeof(int));
+    return PMX_OK;
+}
+
 // gather + resize tables of n boxes (staged) -> offsets of the descriptors and tables
-void stage_boxes(Stage& st, const int* boxes, int n, int dh, int dw, size_t* desc_off, size_t* tab_off, int stride = 5)
+void stage_boxes(Stage& st, const int* boxes6, int n, int dh, int dw, size_t* desc_off, size_t* tab_off)
 {
     std::vector<BoxDesc> d(n);
     std::vector<int> tabs((size_t)n * 4 * (dw + dh));
     for (int i = 0; i < n; ++i) {
-        const int* b = boxes + stride * i;
-        d[i] = BoxDesc{b[0], b[1], b[2] - b[0], b[3] - b[1], b[4], stride == 6 ? b[5] : 0, 0, 0};
+        const int* b = boxes6 + 6 * i;
+        d[i] = BoxDesc{b[0], b[1], b[2] - b[0], b[3] - b[1], b[4], b[5], 0, 0};
         int* t = tabs.data() + (size_t)i * 4 * (dw + dh);
         pmx_make_resize_table(dw, d[i].w, t);
         pmx_make_resize_table(dh, d[i].h, t + 4 * dw);
@@ -256,75 +275,41 @@ void stage_boxes(Stage& st, const int* boxes, int n, int dh, int dw, size_t* des
     *tab_off = st.put(tabs.data(), tabs.size() * sizeof(int));
 }
 
-// key-point tables of n crops (h, w, flip): KpCrop[n] (device pointers relative to the staging's device copy), the flat tile list, the
-// per-crop tile ends and the up-sampling grids
-struct KpStage { size_t crops_off = 0, tiles_off = 0, ends_off = 0; int n_tiles = 0; std::vector<int> crop_tile0; };
-
-void stage_keypoints(pmx_ctx* c, Stage& st, const int* hwf, int n, int in_h, int in_w, KpStage* ks)
+// key-point tables of n crops (h, w, flip) on maps of fh x fw: the up-sampling grids, the flat tile list and the per-crop tile ends are
+// staged, room for the KpCrop[n] records is reserved
+void stage_keypoints(pmx_ctx* c, Stage& st, const int* hwf, int n, int fh, int fw, KpStage* ks)
 {
-    // grids first (their offsets go into the KpCrop records), then the records and the tile list
     std::vector<int> i0, i1; std::vector<double> lo, hi;
-    std::vector<KpCrop> crops(n);
     std::vector<int2> tiles;
     std::vector<int> ends(n);
-    const size_t g_off = st.put(c->gauss.data(), c->gauss.size() * sizeof(double));
-    std::vector<size_t> offs(n * 8);
+    ks->gauss_off = st.put(c->gauss.data(), c->gauss.size() * sizeof(double));
+    ks->grid_off.resize(8 * (size_t)n);
+    ks->crops.resize(n);
+    ks->crop_tile0.resize(n + 1);
     for (int k = 0; k < n; ++k) {
         const int h = hwf[3 * k], w = hwf[3 * k + 1], flip = hwf[3 * k + 2];
-        pmx_make_upsample_grid(in_w, w, i0, i1, lo, hi);
+        pmx_make_upsample_grid(fw, w, i0, i1, lo, hi);
         if (flip) {       // column x of the mirrored map = column w - 1 - x of the resized one (pmx_ensure_tables)
             std::reverse(i0.begin(), i0.end()); std::reverse(i1.begin(), i1.end());
             std::reverse(lo.begin(), lo.end()); std::reverse(hi.begin(), hi.end());
         }
-        size_t* o = &offs[8 * k];
+        size_t* o = &ks->grid_off[8 * (size_t)k];
         o[0] = st.put(i0.data(), w * sizeof(int)); o[1] = st.put(i1.data(), w * sizeof(int));
         o[2] = st.put(lo.data(), w * sizeof(double)); o[3] = st.put(hi.data(), w * sizeof(double));
-        pmx_make_upsample_grid(in_h, h, i0, i1, lo, hi);
+        pmx_make_upsample_grid(fh, h, i0, i1, lo, hi);
         o[4] = st.put(i0.data(), h * sizeof(int)); o[5] = st.put(i1.data(), h * sizeof(int));
         o[6] = st.put(lo.data(), h * sizeof(double)); o[7] = st.put(hi.data(), h * sizeof(double));
         const int tx = (w + PK_TS - 1) / PK_TS, ty = (h + PK_TS - 1) / PK_TS;
-        crops[k].h = h; crops[k].w = w; crops[k].tiles_x = tx; crops[k].tile0 = (int)tiles.size();
+        KpCrop& kc = ks->crops[k];
+        kc.tab.radius = ((int)c->gauss.size() - 1) / 2; kc.tab.border_zero = 0; kc.tab.nms_ge = 0;
+        kc.h = h; kc.w = w; kc.tiles_x = tx; kc.tile0 = ks->crop_tile0[k] = (int)tiles.size();
         for (int t = 0; t < tx * ty; ++t) tiles.push_back(make_int2(k, t));
         ends[k] = (int)tiles.size();
     }
+    ks->n_tiles = ks->crop_tile0[n] = (int)tiles.size();
     ks->crops_off = st.reserve(n * sizeof(KpCrop));
     ks->tiles_off = st.put(tiles.data(), tiles.size() * sizeof(int2));
     ks->ends_off = st.put(ends.data(), ends.size() * sizeof(int));
-    ks->n_tiles = (int)tiles.size();
-    ks->crop_tile0.resize(n + 1);
-    for (int k = 0; k < n; ++k) ks->crop_tile0[k] = crops[k].tile0;
-    ks->crop_tile0[n] = ks->n_tiles;
-    // the device pointers of the grids are filled in once the device buffer is known (stage_fix_pointers)
-    char* dev = nullptr;     // placeholder base: offsets only; fixed up below
-    for (int k = 0; k < n; ++k) {
-        const size_t* o = &offs[8 * k];
-        PPTables& t = crops[k].tab;
-        t.xi0 = reinterpret_cast<int*>(dev + o[0]); t.xi1 = reinterpret_cast<int*>(dev + o[1]);
-        t.xlo = reinterpret_cast<double*>(dev + o[2]); t.xhi = reinterpret_cast<double*>(dev + o[3]);
-        t.yi0 = reinterpret_cast<int*>(dev + o[4]); t.yi1 = reinterpret_cast<int*>(dev + o[5]);
-        t.ylo = reinterpret_cast<double*>(dev + o[6]); t.yhi = reinterpret_cast<double*>(dev + o[7]);
-        t.gauss = reinterpret_cast<double*>(dev + g_off);
-        t.radius = ((int)c->gauss.size() - 1) / 2; t.border_zero = 0; t.nms_ge = 0;
-    }
-    memcpy(st.h.data() + ks->crops_off, crops.data(), n * sizeof(KpCrop));
-}
-
-// the staged KpCrop records hold offsets: add the device base (before the upload)
-int stage_fix_pointers(pmx_ctx* c, Stage& st, const KpStage& ks, int n)
-{
-    int rc;
-    if ((rc = c->bx_dev.ensure(st.h.size(), c->stream))) return rc;
-    KpCrop* k = reinterpret_cast<KpCrop*>(st.h.data() + ks.crops_off);
-    const uintptr_t base = reinterpret_cast<uintptr_t>(c->bx_dev.get());
-    for (int i = 0; i < n; ++i) {
-        PPTables& t = k[i].tab;
-        t.xi0 = reinterpret_cast<int*>(base + reinterpret_cast<uintptr_t>(t.xi0)); t.xi1 = reinterpret_cast<int*>(base + reinterpret_cast<uintptr_t>(t.xi1));
-        t.xlo = reinterpret_cast<double*>(base + reinterpret_cast<uintptr_t>(t.xlo)); t.xhi = reinterpret_cast<double*>(base + reinterpret_cast<uintptr_t>(t.xhi));
-        t.yi0 = reinterpret_cast<int*>(base + reinterpret_cast<uintptr_t>(t.yi0)); t.yi1 = reinterpret_cast<int*>(base + reinterpret_cast<uintptr_t>(t.yi1));
-        t.ylo = reinterpret_cast<double*>(base + reinterpret_cast<uintptr_t>(t.ylo)); t.yhi = reinterpret_cast<double*>(base + reinterpret_cast<uintptr_t>(t.yhi));
-        t.gauss = reinterpret_cast<double*>(base + reinterpret_cast<uintptr_t>(t.gauss));
-    }
-    return PMX_OK;
 }
 
 // the current network maps (uniform batch) as the post-process sees them (pmx_keypoints)
@@ -374,7 +359,8 @@ int kp_enqueue_chunk(pmx_ctx* c, const KpStage& ks, const int* hwf, int k0, int 
     return PMX_OK;
 }
 
-int kp_prepare(pmx_ctx* c, Stage& st, const int* hwf, int n, KpStage* ks)
+// the key-point half of a call for n crops (h, w, flip) on maps of fh x fw: checks, staging, device buffers
+int kp_prepare(pmx_ctx* c, Stage& st, const int* hwf, int n, int fh, int fw, KpStage* ks)
 {
     const int n_ch = c->n_heat - 1;
     int rc;
@@ -382,7 +368,7 @@ int kp_prepare(pmx_ctx* c, Stage& st, const int* hwf, int n, KpStage* ks)
         PMX_CHECK(hwf[3 * k] >= 1 && hwf[3 * k + 1] >= 1 && (long long)hwf[3 * k] * hwf[3 * k + 1] < (1ll << 31) &&
                   (hwf[3 * k + 2] == 0 || hwf[3 * k + 2] == 1), PMX_ERR_INVALID, "key points: crop %d has a bad (h, w, flip) = (%d, %d, %d)",
                   k, hwf[3 * k], hwf[3 * k + 1], hwf[3 * k + 2]);
-    stage_keypoints(c, st, hwf, n, c->cur_fh, c->cur_fw, ks);
+    stage_keypoints(c, st, hwf, n, fh, fw, ks);
     const size_t nkp = (size_t)n * n_ch * 4;
     if ((rc = c->d_kp.ensure(nkp, c->stream))) return rc;
     if (kp_fast(c) && (rc = c->bx_rec.ensure((size_t)ks->n_tiles * n_ch * sizeof(ArgMax), c->stream))) return rc;
@@ -403,49 +389,6 @@ int kp_finish(pmx_ctx* c, const KpStage& ks, int n, double thresh, double* out)
     }
     PMX_HIP(hipMemcpyAsync(out, c->d_kp, (size_t)n * n_ch * 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     PMX_HIP(hipStreamSynchronize(c->stream));
-    return PMX_OK;
-}
-
-// the image on the device (uploaded once per call unless it already is there)
-int image_on_device(pmx_ctx* c, const uint8_t* img, int img_h, int img_w, int on_device, const uint8_t** d)
-{
-    PMX_CHECK(img && img_h >= 1 && img_w >= 1, PMX_ERR_INVALID, "boxes: bad image (%d x %d)", img_h, img_w);
-    if (on_device) { *d = img; return PMX_OK; }
-    const size_t nsrc = (size_t)img_h * img_w * 3;
-    int rc;
-    if ((rc = c->u8_src.ensure(nsrc, c->stream))) return rc;
-    PMX_HIP(hipMemcpyAsync(c->u8_src, img, nsrc, hipMemcpyHostToDevice, c->stream));
-    c->pr_src = nullptr;      // (u8_src no longer holds a detect_precise original)
-    *d = c->u8_src;
-    return PMX_OK;
-}
-
-// gather + resize of boxes [k0, k0 + B) into u8_tmp, then the network
-int forward_chunk(pmx_ctx* c, const uint8_t* d_img, int img_h, int img_w, size_t desc_off, size_t tab_off, int k0, int B)
-{
-    const int dh = c->max_h, dw = c->max_w;
-    int rc;
-    const long long npix = (long long)B * dh * dw;
-    if ((rc = pmx_prof_begin(c, "resize_boxes|box_gather_resize_u8_kernel", (double)npix * 3 * 2))) return rc;
-    hipLaunchKernelGGL(box_gather_resize_u8_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, c->stream, d_img, img_h, img_w,
-                       reinterpret_cast<const BoxDesc*>(c->bx_dev + desc_off) + k0,
-                       reinterpret_cast<const int*>(c->bx_dev + tab_off) + (size_t)k0 * 4 * (dw + dh), B, dh, dw, c->u8_tmp.get());
-    PMX_HIP(hipGetLastError());
-    if ((rc = pmx_prof_end(c))) return rc;
-    return pmx_forward_u8(c, c->u8_tmp, B, dh, dw, 1);
-}
-
-// ---- boxes of many images
-// every box names an image of the list, and every image a box names exists (an image no box refers to is never looked at)
-int check_box_images(const pmx_box_image* images, int n_images, const int* boxes6, int n)
-{
-    PMX_CHECK(n_images >= 1 && images, PMX_ERR_INVALID, "boxes: %d images for %d boxes", images ? n_images : 0, n);
-    for (int i = 0; i < n; ++i) {
-        const int k = boxes6[6 * i + 5];
-        PMX_CHECK(k >= 0 && k < n_images, PMX_ERR_INVALID, "box %d: image index %d outside 0..%d", i, k, n_images - 1);
-        PMX_CHECK(images[k].bgr && images[k].h >= 1 && images[k].w >= 1, PMX_ERR_INVALID, "image %d (of box %d): %s, %d x %d", k, i,
-                  images[k].bgr ? "bad size" : "null pointer", images[k].h, images[k].w);
-    }
     return PMX_OK;
 }
 
@@ -485,8 +428,8 @@ int upload_images(pmx_ctx* c, const std::vector<ImageCopy>& copies)
     return PMX_OK;
 }
 
-// forward_chunk for boxes of many images
-int forward_chunk_images(pmx_ctx* c, size_t imgs_off, size_t desc_off, size_t tab_off, int k0, int B)
+// gather + resize of boxes [k0, k0 + B) into u8_tmp, then the network
+int forward_chunk(pmx_ctx* c, size_t imgs_off, size_t desc_off, size_t tab_off, int k0, int B)
 {
     const int dh = c->max_h, dw = c->max_w;
     int rc;
@@ -500,25 +443,59 @@ int forward_chunk_images(pmx_ctx* c, size_t imgs_off, size_t desc_off, size_t ta
     return pmx_forward_u8(c, c->u8_tmp, B, dh, dw, 1);
 }
 
-}  // namespace
-
-extern "C" int pmx_forward_u8_boxes(pmx_ctx* c, const uint8_t* img, int img_h, int img_w, int on_device, const int* boxes, int n)
+// the two forward entries once the context and n in 1 .. max_batch are checked
+int forward_boxes(pmx_ctx* c, const pmx_box_image* images, int n_images, int on_device, const int* boxes6, int n)
 {
-    PMX_CHECK(c, PMX_ERR_INVALID, "null ctx");
-    PMX_CHECK(c->kind != NET_POSE, PMX_ERR_STATE, "pmx_forward_u8_boxes: facenet / handnet only");
-    PMX_CHECK(n >= 1 && n <= c->max_batch, PMX_ERR_CAPACITY, "pmx_forward_u8_boxes: %d boxes outside 1..%d", n, c->max_batch);
     int rc;
-    if ((rc = check_boxes(boxes, n))) return rc;
-    PMX_CHECK(img && img_h >= 1 && img_w >= 1, PMX_ERR_INVALID, "pmx_forward_u8_boxes: bad image (%d x %d)", img_h, img_w);
+    if ((rc = check_boxes(boxes6, n))) return rc;
+    if ((rc = check_box_images(images, n_images, boxes6, n))) return rc;
     PMX_DEV(c);
     Stage st;
-    size_t desc_off, tab_off;
-    stage_boxes(st, boxes, n, c->max_h, c->max_w, &desc_off, &tab_off);
-    const uint8_t* d = nullptr;
-    if ((rc = image_on_device(c, img, img_h, img_w, on_device, &d))) return rc;
+    size_t desc_off, tab_off, imgs_off;
+    std::vector<ImageCopy> copies;
+    stage_boxes(st, boxes6, n, c->max_h, c->max_w, &desc_off, &tab_off);
+    if ((rc = stage_images(c, st, images, n_images, on_device, boxes6, n, &imgs_off, &copies))) return rc;
+    if ((rc = upload_images(c, copies))) return rc;
     if ((rc = stage_upload(c, st))) return rc;
-    return forward_chunk(c, d, img_h, img_w, desc_off, tab_off, 0, n);
+    return forward_chunk(c, imgs_off, desc_off, tab_off, 0, n);
 }
+
+// the two one-call entries once the context is checked
+int keypoints_boxes(pmx_ctx* c, const pmx_box_image* images, int n_images, int on_device, const int* boxes6, int n, double thresh,
+                    double* out)
+{
+    int rc;
+    if ((rc = check_boxes(boxes6, n))) return rc;
+    if (n == 0) return PMX_OK;
+    if ((rc = check_box_images(images, n_images, boxes6, n))) return rc;
+    PMX_CHECK(out, PMX_ERR_INVALID, "boxes: null output");
+    if ((rc = pmx_check_weights(c))) return rc;
+    PMX_DEV(c);
+    const int fh = c->max_h / 8, fw = c->max_w / 8;      // the maps of a max_h x max_w input: those of the forwards below
+    std::vector<int> hwf(3 * (size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const int* b = boxes6 + 6 * i;
+        hwf[3 * i] = b[3] - b[1]; hwf[3 * i + 1] = b[2] - b[0]; hwf[3 * i + 2] = b[4];
+    }
+    Stage st;
+    size_t desc_off, tab_off, imgs_off;
+    std::vector<ImageCopy> copies;
+    KpStage ks;
+    stage_boxes(st, boxes6, n, c->max_h, c->max_w, &desc_off, &tab_off);
+    if ((rc = kp_prepare(c, st, hwf.data(), n, fh, fw, &ks))) return rc;
+    if ((rc = stage_images(c, st, images, n_images, on_device, boxes6, n, &imgs_off, &copies))) return rc;
+    if ((rc = upload_images(c, copies))) return rc;
+    if ((rc = stage_upload(c, st, &ks))) return rc;
+    for (int k0 = 0; k0 < n; k0 += c->max_batch) {       // chunks in box order, across image borders
+        const int B = n - k0 < c->max_batch ? n - k0 : c->max_batch;
+        if ((rc = forward_chunk(c, imgs_off, desc_off, tab_off, k0, B))) return rc;
+        PMX_CHECK(c->cur_fh == fh && c->cur_fw == fw, PMX_ERR_STATE, "boxes: maps of %d x %d, expected %d x %d", c->cur_fh, c->cur_fw, fh, fw);
+        if ((rc = kp_enqueue_chunk(c, ks, hwf.data(), k0, B, thresh))) return rc;
+    }
+    return kp_finish(c, ks, n, thresh, out);
+}
+
+}  // namespace
 
 extern "C" int pmx_keypoints_images(pmx_ctx* c, int B, const int* hwf, double thresh, double* out)
 {
@@ -530,11 +507,39 @@ extern "C" int pmx_keypoints_images(pmx_ctx* c, int B, const int* hwf, double th
     int rc;
     Stage st;
     KpStage ks;
-    if ((rc = kp_prepare(c, st, hwf, B, &ks))) return rc;
-    if ((rc = stage_fix_pointers(c, st, ks, B))) return rc;
-    if ((rc = stage_upload(c, st))) return rc;
+    if ((rc = kp_prepare(c, st, hwf, B, c->cur_fh, c->cur_fw, &ks))) return rc;
+    if ((rc = stage_upload(c, st, &ks))) return rc;
     if ((rc = kp_enqueue_chunk(c, ks, hwf, 0, B, thresh))) return rc;
     return kp_finish(c, ks, B, thresh, out);
+}
+
+extern "C" int pmx_forward_u8_boxes_images(pmx_ctx* c, const pmx_box_image* images, int n_images, int on_device, const int* boxes6, int n)
+{
+    PMX_CHECK(c, PMX_ERR_INVALID, "null ctx");
+    PMX_CHECK(c->kind != NET_POSE, PMX_ERR_STATE, "pmx_forward_u8_boxes_images: facenet / handnet only");
+    PMX_CHECK(n >= 1 && n <= c->max_batch, PMX_ERR_CAPACITY, "pmx_forward_u8_boxes_images: %d boxes outside 1..%d", n, c->max_batch);
+    return forward_boxes(c, images, n_images, on_device, boxes6, n);
+}
+
+extern "C" int pmx_keypoints_boxes_images(pmx_ctx* c, const pmx_box_image* images, int n_images, int on_device, const int* boxes6, int n,
+                                          double thresh, double* out)
+{
+    PMX_CHECK(c, PMX_ERR_INVALID, "null ctx");
+    PMX_CHECK(c->kind != NET_POSE, PMX_ERR_STATE, "pmx_keypoints_boxes_images: facenet / handnet only");
+    return keypoints_boxes(c, images, n_images, on_device, boxes6, n, thresh, out);
+}
+
+// ---- the one-image entries: the image as a table of one, image 0 on every box
+extern "C" int pmx_forward_u8_boxes(pmx_ctx* c, const uint8_t* img, int img_h, int img_w, int on_device, const int* boxes, int n)
+{
+    PMX_CHECK(c, PMX_ERR_INVALID, "null ctx");
+    PMX_CHECK(c->kind != NET_POSE, PMX_ERR_STATE, "pmx_forward_u8_boxes: facenet / handnet only");
+    PMX_CHECK(n >= 1 && n <= c->max_batch, PMX_ERR_CAPACITY, "pmx_forward_u8_boxes: %d boxes outside 1..%d", n, c->max_batch);
+    int rc;
+    std::vector<int> boxes6;
+    if ((rc = boxes_of_image0(boxes, n, &boxes6))) return rc;
+    const pmx_box_image image{img, img_h, img_w};
+    return forward_boxes(c, &image, 1, on_device, boxes6.data(), n);
 }
 
 extern "C" int pmx_keypoints_boxes(pmx_ctx* c, const uint8_t* img, int img_h, int img_w, int on_device, const int* boxes, int n,
@@ -543,101 +548,8 @@ extern "C" int pmx_keypoints_boxes(pmx_ctx* c, const uint8_t* img, int img_h, in
     PMX_CHECK(c, PMX_ERR_INVALID, "null ctx");
     PMX_CHECK(c->kind != NET_POSE, PMX_ERR_STATE, "pmx_keypoints_boxes: facenet / handnet only");
     int rc;
-    if ((rc = check_boxes(boxes, n))) return rc;
-    if (n == 0) return PMX_OK;
-    PMX_CHECK(out, PMX_ERR_INVALID, "pmx_keypoints_boxes: null output");
-    PMX_CHECK(img && img_h >= 1 && img_w >= 1, PMX_ERR_INVALID, "pmx_keypoints_boxes: bad image (%d x %d)", img_h, img_w);
-    if ((rc = pmx_check_weights(c))) return rc;
-    PMX_DEV(c);
-    const int fh = c->max_h / 8, fw = c->max_w / 8;      // the maps of a max_h x max_w input
-    std::vector<int> hwf(3 * (size_t)n);
-    for (int i = 0; i < n; ++i) {
-        hwf[3 * i] = boxes[5 * i + 3] - boxes[5 * i + 1]; hwf[3 * i + 1] = boxes[5 * i + 2] - boxes[5 * i]; hwf[3 * i + 2] = boxes[5 * i + 4];
-    }
-    Stage st;
-    size_t desc_off, tab_off;
-    stage_boxes(st, boxes, n, c->max_h, c->max_w, &desc_off, &tab_off);
-    KpStage ks;
-    {
-        // kp_prepare builds the grids against the maps' size: that of the forward below
-        const int sh = c->cur_fh, sw = c->cur_fw;
-        c->cur_fh = fh; c->cur_fw = fw;
-        rc = kp_prepare(c, st, hwf.data(), n, &ks);
-        c->cur_fh = sh; c->cur_fw = sw;
-        if (rc) return rc;
-    }
-    if ((rc = stage_fix_pointers(c, st, ks, n))) return rc;
-    const uint8_t* d = nullptr;
-    if ((rc = image_on_device(c, img, img_h, img_w, on_device, &d))) return rc;
-    if ((rc = stage_upload(c, st))) return rc;
-    for (int k0 = 0; k0 < n; k0 += c->max_batch) {
-        const int B = n - k0 < c->max_batch ? n - k0 : c->max_batch;
-        if ((rc = forward_chunk(c, d, img_h, img_w, desc_off, tab_off, k0, B))) return rc;
-        PMX_CHECK(c->cur_fh == fh && c->cur_fw == fw, PMX_ERR_STATE, "pmx_keypoints_boxes: maps of %d x %d, expected %d x %d", c->cur_fh, c->cur_fw, fh, fw);
-        if ((rc = kp_enqueue_chunk(c, ks, hwf.data(), k0, B, thresh))) return rc;
-    }
-    return kp_finish(c, ks, n, thresh, out);
-}
-
-extern "C" int pmx_forward_u8_boxes_images(pmx_ctx* c, const pmx_box_image* images, int n_images, int on_device, const int* boxes6, int n)
-{
-    PMX_CHECK(c, PMX_ERR_INVALID, "null ctx");
-    PMX_CHECK(c->kind != NET_POSE, PMX_ERR_STATE, "pmx_forward_u8_boxes_images: facenet / handnet only");
-    PMX_CHECK(n >= 1 && n <= c->max_batch, PMX_ERR_CAPACITY, "pmx_forward_u8_boxes_images: %d boxes outside 1..%d", n, c->max_batch);
-    int rc;
-    if ((rc = check_boxes(boxes6, n, 6))) return rc;
-    if ((rc = check_box_images(images, n_images, boxes6, n))) return rc;
-    PMX_DEV(c);
-    Stage st;
-    size_t desc_off, tab_off, imgs_off;
-    std::vector<ImageCopy> copies;
-    stage_boxes(st, boxes6, n, c->max_h, c->max_w, &desc_off, &tab_off, 6);
-    if ((rc = stage_images(c, st, images, n_images, on_device, boxes6, n, &imgs_off, &copies))) return rc;
-    if ((rc = upload_images(c, copies))) return rc;
-    if ((rc = stage_upload(c, st))) return rc;
-    return forward_chunk_images(c, imgs_off, desc_off, tab_off, 0, n);
-}
-
-extern "C" int pmx_keypoints_boxes_images(pmx_ctx* c, const pmx_box_image* images, int n_images, int on_device, const int* boxes6, int n,
-                                          double thresh, double* out)
-{
-    PMX_CHECK(c, PMX_ERR_INVALID, "null ctx");
-    PMX_CHECK(c->kind != NET_POSE, PMX_ERR_STATE, "pmx_keypoints_boxes_images: facenet / handnet only");
-    int rc;
-    if ((rc = check_boxes(boxes6, n, 6))) return rc;
-    if (n == 0) return PMX_OK;
-    if ((rc = check_box_images(images, n_images, boxes6, n))) return rc;
-    PMX_CHECK(out, PMX_ERR_INVALID, "pmx_keypoints_boxes_images: null output");
-    if ((rc = pmx_check_weights(c))) return rc;
-    PMX_DEV(c);
-    const int fh = c->max_h / 8, fw = c->max_w / 8;      // the maps of a max_h x max_w input
-    std::vector<int> hwf(3 * (size_t)n);
-    for (int i = 0; i < n; ++i) {
-        const int* b = boxes6 + 6 * i;
-        hwf[3 * i] = b[3] - b[1]; hwf[3 * i + 1] = b[2] - b[0]; hwf[3 * i + 2] = b[4];
-    }
-    Stage st;
-    size_t desc_off, tab_off, imgs_off;
-    std::vector<ImageCopy> copies;
-    stage_boxes(st, boxes6, n, c->max_h, c->max_w, &desc_off, &tab_off, 6);
-    KpStage ks;
-    {
-        // kp_prepare builds the grids against the maps' size: that of the forwards below
-        const int sh = c->cur_fh, sw = c->cur_fw;
-        c->cur_fh = fh; c->cur_fw = fw;
-        rc = kp_prepare(c, st, hwf.data(), n, &ks);
-        c->cur_fh = sh; c->cur_fw = sw;
-        if (rc) return rc;
-    }
-    if ((rc = stage_images(c, st, images, n_images, on_device, boxes6, n, &imgs_off, &copies))) return rc;
-    if ((rc = stage_fix_pointers(c, st, ks, n))) return rc;
-    if ((rc = upload_images(c, copies))) return rc;
-    if ((rc = stage_upload(c, st))) return rc;
-    for (int k0 = 0; k0 < n; k0 += c->max_batch) {       // chunks in box order, across image borders
-        const int B = n - k0 < c->max_batch ? n - k0 : c->max_batch;
-        if ((rc = forward_chunk_images(c, imgs_off, desc_off, tab_off, k0, B))) return rc;
-        PMX_CHECK(c->cur_fh == fh && c->cur_fw == fw, PMX_ERR_STATE, "pmx_keypoints_boxes_images: maps of %d x %d, expected %d x %d", c->cur_fh, c->cur_fw, fh, fw);
-        if ((rc = kp_enqueue_chunk(c, ks, hwf.data(), k0, B, thresh))) return rc;
-    }
-    return kp_finish(c, ks, n, thresh, out);
+    std::vector<int> boxes6;
+    if ((rc = boxes_of_image0(boxes, n, &boxes6))) return rc;
+    const pmx_box_image image{img, img_h, img_w};
+    return keypoints_boxes(c, &image, 1, on_device, boxes6.data(), n, thresh, out);
 }

@@ -106,46 +106,13 @@ class _KeypointDetector(object):
 
     def _detect_boxes(self, img, bboxes, flips):
         """Key points of many boxes of ONE image, one list per box: what `self._detect(crop_image(img, box)[, ::-1])` returns for it.
-        All crops are cut, mirrored and resized on the device and run through the network as one batch (chunks of the engine's batch)."""
-        img = np.ascontiguousarray(img, dtype=np.uint8)
-        if img.ndim != 3 or img.shape[2] != 3:
+        All crops are cut, mirrored and resized on the device and run through the network as one batch (chunks of the engine's batch):
+        _detect_boxes_batch for a list of one image."""
+        if np.ndim(img) != 3 or np.shape(img)[2] != 3:
             raise ValueError('detect_boxes needs one uint8 H x W x 3 image')
-        boxes = [(int(b[0]), int(b[1]), int(b[2]), int(b[3]), int(f)) for b, f in zip(bboxes, flips)]
-        if len(boxes) != len(bboxes):
+        if len(flips) != len(bboxes):
             raise ValueError('one hand type per box')
-        for i, b in enumerate(boxes):          # (the library checks too; here before the engine may grow)
-            if b[2] <= b[0] or b[3] <= b[1]:
-                raise native.PmxError(1, 'box %d: empty (left %d, top %d, right %d, bottom %d)' % ((i,) + b[:4]))
-        if not boxes:
-            return []
-        thresh = params[self.THRESH_KEY]
-        if self.model is None:
-            if self.engine.weights_missing():
-                raise RuntimeError('%s has no weights: pass weights_file=, weights= or model=' % type(self).__name__)
-            self._grow(len(boxes))
-            kps = self.engine.keypoints_boxes(img, boxes, thresh)
-        else:
-            # `model=` seam: crops resized on the device one by one, the callable per crop (as __call__), the key points of all maps in
-            # one pmx_keypoints_images call
-            from .pose_detector import PoseDetector
-            size = params[self.SIZE_KEY]
-            heats = []
-            for b in boxes:
-                crop = PoseDetector.crop_image(None, img, b[:4])
-                if b[4]:
-                    crop = crop[:, ::-1]
-                resized = self.engine.resize_u8(np.ascontiguousarray(crop)[None], size, size)[0]
-                x = np.array(resized[np.newaxis], dtype=np.float32).transpose(0, 3, 1, 2) / 256 - 0.5
-                hs = self.model(x)
-                heats.append(np.asarray(getattr(hs[-1], 'data', hs[-1]), dtype=np.float32)[0])
-            kps = []
-            for k0 in range(0, len(boxes), self.max_batch):
-                chunk = boxes[k0:k0 + self.max_batch]
-                self._grow(len(chunk))
-                self.engine.set_heat(np.stack(heats[k0:k0 + self.max_batch]))
-                kps.extend(self.engine.keypoints_images([(b[3] - b[1], b[2] - b[0], b[4]) for b in chunk], thresh))
-        return [_keypoint_list(kp) for kp in kps]
-
+        return self._detect_boxes_batch([img], [bboxes], [flips])[0]
 
     def _detect_boxes_batch(self, imgs, bboxes_per_image, flips_per_image):
         """_detect_boxes for the boxes of MANY images (any sizes) in one call: one list per image of one key-point list per box.  The
@@ -175,7 +142,8 @@ class _KeypointDetector(object):
             # (an image without boxes is not handed over: the library neither reads nor uploads it)
             kps = self.engine.keypoints_boxes_images([im if n else None for im, n in zip(imgs, counts)], boxes, thresh)
         else:
-            # `model=` seam as in _detect_boxes: the callable per crop, the key points of all crops in chunks of pmx_keypoints_images
+            # `model=` seam: crops resized on the device one by one, the callable per crop (as __call__), the key points of all crops in
+            # chunks of pmx_keypoints_images
             from .pose_detector import PoseDetector
             size = params[self.SIZE_KEY]
             heats = []
@@ -315,16 +283,13 @@ def _serial_box_check(bbox):
         raise native.PmxError(1, 'empty crop %r' % (tuple(bbox),))
 
 
-def detect_person_parts(pose_detector, face_detector, hand_detector, img, poses):
-    """What the reference demo's loop (demo.py:30-55) computes for every person, with ONE detect_boxes call per detector (two network
-    calls however many people).  Per person: {'unit_length', 'face': {'bbox', 'keypoints'} | None, 'left': ..., 'right': ...}.
-    Works on a copy of `poses` (the reference's crop_hands moves the wrists in place); every box is computed, and every error the loop
-    would raise (e.g. int(nan) for a person without a measurable limb) is raised, before anything runs on the device."""
-    poses = np.array(poses, copy=True)
+def _person_boxes(pose_detector, poses):
+    """The host half of demo.py:30-55 for the people of one image: (persons, face boxes, their owners, hand boxes, hand types, their
+    owners), on a copy of `poses`; raises what the reference's loop would, in (person, face, left, right) order."""
     persons, face_boxes, face_owner, hand_boxes, hand_types, hand_owner = [], [], [], [], [], []
-    for p, pose in enumerate(poses):
+    for p, pose in enumerate(np.array(poses, copy=True)):
         unit = pose_detector.get_unit_length(pose)                       # demo.py:32
-        rec = {'unit_length': unit, 'face': None, 'left': None, 'right': None}
+        persons.append({'unit_length': unit, 'face': None, 'left': None, 'right': None})
         fb = pose_detector.face_bbox(pose, unit)                          # :36
         if fb is not None:
             _serial_box_check(fb)
@@ -337,12 +302,25 @@ def detect_person_parts(pose_detector, face_detector, hand_detector, img, poses)
                 hand_boxes.append(hb[side])
                 hand_types.append(side)
                 hand_owner.append((p, side))
-        persons.append(rec)
-    for p, bbox, kps in zip(face_owner, face_boxes, face_detector.detect_boxes(img, face_boxes)):
+    return persons, face_boxes, face_owner, hand_boxes, hand_types, hand_owner
+
+
+def _assign_parts(persons, face_owner, face_boxes, face_kps, hand_owner, hand_boxes, hand_kps):
+    for p, bbox, kps in zip(face_owner, face_boxes, face_kps):
         persons[p]['face'] = {'bbox': bbox, 'keypoints': kps}
-    for (p, side), bbox, kps in zip(hand_owner, hand_boxes, hand_detector.detect_boxes(img, hand_boxes, hand_types)):
+    for (p, side), bbox, kps in zip(hand_owner, hand_boxes, hand_kps):
         persons[p][side] = {'bbox': bbox, 'keypoints': kps}
     return persons
+
+
+def detect_person_parts(pose_detector, face_detector, hand_detector, img, poses):
+    """What the reference demo's loop (demo.py:30-55) computes for every person, with ONE detect_boxes call per detector (two network
+    calls however many people).  Per person: {'unit_length', 'face': {'bbox', 'keypoints'} | None, 'left': ..., 'right': ...}.
+    Works on a copy of `poses` (the reference's crop_hands moves the wrists in place); every box is computed, and every error the loop
+    would raise (e.g. int(nan) for a person without a measurable limb) is raised, before anything runs on the device."""
+    persons, face_boxes, face_owner, hand_boxes, hand_types, hand_owner = _person_boxes(pose_detector, poses)
+    return _assign_parts(persons, face_owner, face_boxes, face_detector.detect_boxes(img, face_boxes),
+                         hand_owner, hand_boxes, hand_detector.detect_boxes(img, hand_boxes, hand_types))
 
 
 def detect_people_parts(pose_detector, face_detector, hand_detector, imgs, poses_per_image):
@@ -353,34 +331,7 @@ def detect_people_parts(pose_detector, face_detector, hand_detector, imgs, poses
     the device."""
     if len(poses_per_image) != len(imgs):
         raise ValueError('one array of poses per image')
-    people, face_boxes, face_owner, hand_boxes, hand_types, hand_owner = [], [], [], [], [], []
-    for poses in poses_per_image:
-        poses = np.array(poses, copy=True)
-        persons, fb_i, fo_i, hb_i, ht_i, ho_i = [], [], [], [], [], []
-        for p, pose in enumerate(poses):
-            unit = pose_detector.get_unit_length(pose)                       # demo.py:32
-            persons.append({'unit_length': unit, 'face': None, 'left': None, 'right': None})
-            fb = pose_detector.face_bbox(pose, unit)                          # :36
-            if fb is not None:
-                _serial_box_check(fb)
-                fb_i.append(fb)
-                fo_i.append(p)
-            hb = pose_detector.hand_bboxes(pose, unit)                        # :44
-            for side in ('left', 'right'):
-                if hb[side] is not None:
-                    _serial_box_check(hb[side])
-                    hb_i.append(hb[side])
-                    ht_i.append(side)
-                    ho_i.append((p, side))
-        people.append(persons)
-        face_boxes.append(fb_i); face_owner.append(fo_i)
-        hand_boxes.append(hb_i); hand_types.append(ht_i); hand_owner.append(ho_i)
-    face_kps = face_detector.detect_boxes_batch(imgs, face_boxes)
-    hand_kps = hand_detector.detect_boxes_batch(imgs, hand_boxes, hand_types)
-    for persons, owners, boxes, kps in zip(people, face_owner, face_boxes, face_kps):
-        for p, bbox, kp in zip(owners, boxes, kps):
-            persons[p]['face'] = {'bbox': bbox, 'keypoints': kp}
-    for persons, owners, boxes, kps in zip(people, hand_owner, hand_boxes, hand_kps):
-        for (p, side), bbox, kp in zip(owners, boxes, kps):
-            persons[p][side] = {'bbox': bbox, 'keypoints': kp}
-    return people
+    per = [_person_boxes(pose_detector, poses) for poses in poses_per_image]
+    face_kps = face_detector.detect_boxes_batch(imgs, [b[1] for b in per])
+    hand_kps = hand_detector.detect_boxes_batch(imgs, [b[3] for b in per], [b[4] for b in per])
+    return [_assign_parts(persons, fo, fb, fk, ho, hb, hk) for (persons, fb, fo, hb, _, ho), fk, hk in zip(per, face_kps, hand_kps)]

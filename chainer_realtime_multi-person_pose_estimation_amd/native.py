@@ -566,48 +566,12 @@ class Engine(object):
         self._map = (int(out_h), int(out_w))
         return out
 
-    # ---- face / hand key points for many boxes of one image (pmx_forward_u8_boxes / pmx_keypoints_images / pmx_keypoints_boxes) ----
+    # ---- face / hand key points for many boxes: of many images (pmx_forward_u8_boxes_images / pmx_keypoints_boxes_images) and, as the
+    # case of one image, pmx_forward_u8_boxes / pmx_keypoints_boxes; pmx_keypoints_images for the maps of any forward ----
     @staticmethod
-    def _boxes(boxes):
-        """(n, 5) int32 rows (left, top, right, bottom, flip); ValueError for values outside int32."""
-        b = np.asarray(boxes, dtype=np.int64).reshape(-1, 5)
-        if b.size and (b.min() < -2 ** 31 or b.max() > 2 ** 31 - 1):
-            raise ValueError('box coordinates outside int32')
-        return np.ascontiguousarray(b, dtype=np.int32)
-
-    def forward_u8_boxes(self, img, boxes):
-        """img (H, W, 3) uint8 BGR; boxes (n, 5): every box cropped (zero outside the image), mirrored where flip, resized to
-        max_h x max_w on the device, then the network at batch n (n <= max_batch).  get_resized(max_h, max_w) reads the input back."""
-        img = np.ascontiguousarray(img, dtype=np.uint8)
-        b = self._boxes(boxes)
-        self._check(self.lib.pmx_forward_u8_boxes(self._ctx, _ptr(img), img.shape[0], img.shape[1], 0, _ptr(b), len(b)))
-        self._B = len(b)
-        self._fhw = (self.max_h // 8, self.max_w // 8)
-
-    def keypoints_images(self, hwf, thresh):
-        """keypoints() for the B current maps, each with its own (out_h, out_w, flip): (B, maps - 1, 4) float64."""
-        hwf = np.ascontiguousarray(np.asarray(hwf, dtype=np.int64).reshape(-1, 3), dtype=np.int32)
-        out = np.empty((len(hwf), self.n_heat - 1, 4), np.float64)
-        self._check(self.lib.pmx_keypoints_images(self._ctx, len(hwf), _ptr(hwf), float(thresh), _ptr(out)))
-        return out
-
-    def keypoints_boxes(self, img, boxes, thresh):
-        """The one-call form: (n, maps - 1, 4) float64 key-point rows, in each box's own pixel frame."""
-        img = np.ascontiguousarray(img, dtype=np.uint8)
-        b = self._boxes(boxes)
-        out = np.empty((len(b), self.n_heat - 1, 4), np.float64)
-        self._check(self.lib.pmx_keypoints_boxes(self._ctx, _ptr(img), img.shape[0], img.shape[1], 0, _ptr(b), len(b), float(thresh),
-                                                 _ptr(out)))
-        if len(b):
-            self._B = min(len(b) - (len(b) - 1) // self.max_batch * self.max_batch, self.max_batch)
-            self._fhw = (self.max_h // 8, self.max_w // 8)
-        return out
-
-    # ---- the same for boxes of many images (pmx_forward_u8_boxes_images / pmx_keypoints_boxes_images) ----
-    @staticmethod
-    def _boxes6(boxes6):
-        """(n, 6) int32 rows (left, top, right, bottom, flip, image); ValueError for values outside int32."""
-        b = np.asarray(boxes6, dtype=np.int64).reshape(-1, 6)
+    def _boxes(boxes, cols):
+        """(n, cols) int32 rows (left, top, right, bottom, flip[, image]); ValueError for values outside int32."""
+        b = np.asarray(boxes, dtype=np.int64).reshape(-1, cols)
         if b.size and (b.min() < -2 ** 31 or b.max() > 2 ** 31 - 1):
             raise ValueError('box coordinates outside int32')
         return np.ascontiguousarray(b, dtype=np.int32)
@@ -637,26 +601,50 @@ class Engine(object):
             raise ValueError('the images of one call are all host arrays or all device tensors')
         return arr, int(bool(dev) and dev[0]), keep
 
+    def _box_call(self, imgs, boxes, thresh=None, one=False):
+        """The four box entries.  one: `imgs` is [the image] and the boxes have 5 columns (the one-image entries), else 6 (the many-image
+        entries); thresh None -> the forward alone, else -> the (n, maps - 1, 4) key-point rows."""
+        b = self._boxes(boxes, 5 if one else 6)
+        arr, on_device, keep = self._box_images(imgs)
+        image = (C.c_void_p(arr[0].bgr), arr[0].h, arr[0].w) if one else (arr, len(imgs))
+        out = None
+        if thresh is None:
+            fn = self.lib.pmx_forward_u8_boxes if one else self.lib.pmx_forward_u8_boxes_images
+            self._check(fn(self._ctx, *image, on_device, _ptr(b), len(b)))
+        else:
+            out = np.empty((len(b), self.n_heat - 1, 4), np.float64)
+            fn = self.lib.pmx_keypoints_boxes if one else self.lib.pmx_keypoints_boxes_images
+            self._check(fn(self._ctx, *image, on_device, _ptr(b), len(b), float(thresh), _ptr(out)))
+        if len(b):          # the current maps are those of the last chunk
+            self._B = min(len(b) - (len(b) - 1) // self.max_batch * self.max_batch, self.max_batch)
+            self._fhw = (self.max_h // 8, self.max_w // 8)
+        return out
+
+    def forward_u8_boxes(self, img, boxes):
+        """img (H, W, 3) uint8 BGR; boxes (n, 5): every box cropped (zero outside the image), mirrored where flip, resized to
+        max_h x max_w on the device, then the network at batch n (n <= max_batch).  get_resized(max_h, max_w) reads the input back."""
+        self._box_call([img], boxes, one=True)
+
+    def keypoints_images(self, hwf, thresh):
+        """keypoints() for the B current maps, each with its own (out_h, out_w, flip): (B, maps - 1, 4) float64."""
+        hwf = np.ascontiguousarray(np.asarray(hwf, dtype=np.int64).reshape(-1, 3), dtype=np.int32)
+        out = np.empty((len(hwf), self.n_heat - 1, 4), np.float64)
+        self._check(self.lib.pmx_keypoints_images(self._ctx, len(hwf), _ptr(hwf), float(thresh), _ptr(out)))
+        return out
+
+    def keypoints_boxes(self, img, boxes, thresh):
+        """The one-call form: (n, maps - 1, 4) float64 key-point rows, in each box's own pixel frame."""
+        return self._box_call([img], boxes, thresh, one=True)
+
     def forward_u8_boxes_images(self, imgs, boxes6):
         """forward_u8_boxes for boxes of many images: imgs a list of (H, W, 3) uint8 BGR images of any sizes, boxes6 (n, 6) with the
         image's index in the last column (n <= max_batch)."""
-        b = self._boxes6(boxes6)
-        arr, on_device, keep = self._box_images(imgs)
-        self._check(self.lib.pmx_forward_u8_boxes_images(self._ctx, arr, len(imgs), on_device, _ptr(b), len(b)))
-        self._B = len(b)
-        self._fhw = (self.max_h // 8, self.max_w // 8)
+        self._box_call(imgs, boxes6)
 
     def keypoints_boxes_images(self, imgs, boxes6, thresh):
         """keypoints_boxes for boxes of many images: (n, maps - 1, 4) float64 key-point rows in box order, each in its box's own pixel
         frame; chunks of max_batch crops in box order across image borders, one synchronisation per call."""
-        b = self._boxes6(boxes6)
-        arr, on_device, keep = self._box_images(imgs)
-        out = np.empty((len(b), self.n_heat - 1, 4), np.float64)
-        self._check(self.lib.pmx_keypoints_boxes_images(self._ctx, arr, len(imgs), on_device, _ptr(b), len(b), float(thresh), _ptr(out)))
-        if len(b):
-            self._B = min(len(b) - (len(b) - 1) // self.max_batch * self.max_batch, self.max_batch)
-            self._fhw = (self.max_h // 8, self.max_w // 8)
-        return out
+        return self._box_call(imgs, boxes6, thresh)
 
     def set_maps(self, paf, heat):
         paf = np.ascontiguousarray(paf, dtype=np.float32)

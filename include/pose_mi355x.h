@@ -237,7 +237,8 @@ int pmx_precise_table_stats(pmx_ctx* ctx, int* cached, int* trims);
 int pmx_keypoints(pmx_ctx* ctx, int batch, int out_h, int out_w, double thresh, double* out);
 
 /* ---- face / hand key points for many boxes of ONE image (demo.py:30-55: per person a face crop and two hand crops) ------------------
- * facenet / handnet contexts.  boxes: n x 5 int32 (left, top, right, bottom, flip) in image pixels; a box may extend past the image (those
+ * The two entries of this form are adapters onto the many-image entries below (one implementation): the image as a list of one, image 0 on
+ * every box; same checks, same PMX_ERR_* codes, same bytes.  facenet / handnet contexts.  boxes: n x 5 int32 (left, top, right, bottom, flip) in image pixels; a box may extend past the image (those
  * pixels are 0: PoseDetector.crop_image, pose_detector.py:401-424); flip = 1 mirrors the crop left-right (cv2.flip(img, 1) of a left hand,
  * hand_detector.py:29-30).  Every box must be non-empty with int32 extents, else PMX_ERR_INVALID naming the box, before anything runs.
  * The network input is the context's max_h x max_w (368 x 368 for the detectors): per box crop + mirror + cv2.resize INTER_LINEAR, the same
@@ -254,14 +255,14 @@ int pmx_keypoints_images(pmx_ctx* ctx, int batch, const int* out_hwf, double thr
 int pmx_keypoints_boxes(pmx_ctx* ctx, const uint8_t* img, int img_h, int img_w, int on_device, const int* boxes, int n,
                         double thresh, double* out);
 
-/* ---- the same for boxes of MANY images (the people of a batch of frames) -----------------------------------------------------------------
+/* ---- boxes of MANY images (the people of a batch of frames): the implementation of both forms --------------------------------------------
  * images: n_images images of any, differing sizes; host memory (read before the call returns) or, with on_device != 0, device memory on the
  * context's device.  boxes6: n x 6 int32 (left, top, right, bottom, flip, image): columns 0..4 as above, image = index into `images`.  An
  * image that no box refers to is allowed; it is neither looked at nor uploaded.  Checked before anything is enqueued, PMX_ERR_INVALID with
  * the box or the image named: n_images < 1 with n > 0, an image index outside 0 .. n_images - 1, a null or non-positive-size image that a
  * box refers to, an empty box, a bad flip.  A posenet context: PMX_ERR_STATE.  Per box the network input holds the same bytes, and the key
- * points are those, of the one-image entries called with that box and its own image alone (same kernels chosen: bit-identical; the f16 mode
- * makes an image's maps independent of batch size and position). */
+ * points are those, of a call with that box and its own image alone (same kernels chosen: bit-identical; the f16 mode makes an image's maps
+ * independent of batch size and position). */
 typedef struct pmx_box_image { const uint8_t* bgr; int h, w; } pmx_box_image;   /* h x w x 3 uint8 BGR */
 /* gather + resize + forward of n <= max_batch boxes (1 .. max_batch, else PMX_ERR_CAPACITY); asynchronous. */
 int pmx_forward_u8_boxes_images(pmx_ctx* ctx, const pmx_box_image* images, int n_images, int on_device, const int* boxes6, int n);
@@ -271,7 +272,7 @@ int pmx_forward_u8_boxes_images(pmx_ctx* ctx, const pmx_box_image* images, int n
  * table -- address, height, width per image; host images are placed in one device store at 64-bit byte offsets -- next to the crop
  * descriptors and tables), one upload per referenced host image enqueued back to back with no synchronisation between them, one D2H copy
  * and ONE stream synchronisation.  n == 0: nothing, PMX_OK.  Gaussian radii other than 10, "peaks_gpu_branch" and "pp_generic" fall back to
- * a per-crop key-point loop as in pmx_keypoints_boxes. */
+ * a per-crop key-point loop (so does pmx_keypoints_boxes). */
 int pmx_keypoints_boxes_images(pmx_ctx* ctx, const pmx_box_image* images, int n_images, int on_device, const int* boxes6, int n,
                                double thresh, double* out);
 

@@ -233,3 +233,32 @@ def test_empty_calls_errors_and_growth(native):
     assert hdet._cap == 16 and hdet.engine.max_batch == 16
     assert hdet(crop, hand_type='left') == want            # after growth: what a fresh batch-1 detector returns
     hdet.engine.close(); fresh.engine.close()
+
+
+@pytest.mark.parametrize('device_image', [False, True])
+def test_one_image_entries_equal_the_many_image_entries(native, device_image):
+    """pmx_forward_u8_boxes / pmx_keypoints_boxes are adapters onto the many-image implementation: on the same image and boxes both C
+    entries of a pair leave the same network input bytes and return the same key-point rows, host image or device image"""
+    rng = np.random.default_rng(9)
+    img = rng.integers(0, 256, (300, 420, 3), dtype=np.uint8)
+    boxes5 = [b for b in _boxes_mixed(*img.shape[:2]) if (b[2] - b[0]) * (b[3] - b[1]) < 400 * 400][:10]
+    boxes6 = [b + (0,) for b in boxes5]
+    assert len(boxes5) == 10 and any(b[4] for b in boxes5)
+    src = img
+    if device_image:
+        import torch
+        src = torch.from_numpy(img).to('cuda:0')
+        torch.cuda.synchronize()                                         # (the context's stream is not torch's)
+    det = _detectors(native, 'handnet', 8, max_batch=4)
+    det._grow(4)
+    eng = det.engine
+    one = eng.keypoints_boxes(src, boxes5, 0.05)                         # three chunks: 4, 4, 2
+    many = eng.keypoints_boxes_images([src], boxes6, 0.05)
+    assert one.shape == (10, 21, 4) and np.array_equal(one, many)
+    if device_image:
+        assert np.array_equal(one, eng.keypoints_boxes(img, boxes5, 0.05))
+    eng.forward_u8_boxes(src, boxes5[:4])
+    got_one, maps_one = eng.get_resized(SIZE, SIZE), eng.get_maps()
+    eng.forward_u8_boxes_images([src], boxes6[:4])
+    assert np.array_equal(got_one, eng.get_resized(SIZE, SIZE)) and np.array_equal(maps_one, eng.get_maps())
+    eng.close()
