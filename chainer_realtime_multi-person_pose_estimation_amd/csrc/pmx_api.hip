@@ -202,6 +202,21 @@ static void pack_f16(const std::vector<float>& wp, std::vector<uint16_t>& out)
     for (size_t i = 0; i < wp.size(); ++i) out[i] = f16_rn_sat(wp[i]);
 }
 
+// conv1_1's weights in the order conv1_wino_kernel's lanes want them: [channel half 2][k-pair 14][k of the pair 2][channel 32] (the 28th k is
+// zero) -- one contiguous 256-byte run per wave and k-pair.  Read out of the direct pack [tap][1 chunk][64][16] each lane gathered 14 dwords
+// 64 bytes apart: 1.7 us of a 25 us block (profiles/r05_conv1_wino_ablation.json).
+static void pack_conv1(const std::vector<float>& wp, int cout_pad, std::vector<float>& out)
+{
+    out.assign(2 * 14 * 2 * 32, 0.f);
+    for (int hf = 0; hf < 2; ++hf)
+        for (int sp = 0; sp < 14; ++sp)
+            for (int kk = 0; kk < 2; ++kk)
+                for (int n = 0; n < 32; ++n) {
+                    const int k = 2 * sp + kk;
+                    if (k < 27) out[((hf * 14 + sp) * 2 + kk) * 32 + n] = wp[((size_t)(k / 3) * cout_pad + hf * 32 + n) * CK + k % 3];
+                }
+}
+
 static std::vector<int> identity_map(int cin)
 {
     std::vector<int> m(round_up(cin, CK), -1);
@@ -523,90 +538,40 @@ extern "C" int pmx_weights_missing(pmx_ctx* c, int* n)
 }
 
 // ------------------------------------------------------------------------------------------ forward
-struct ConvIO { const float* in; int lda; float* out; int ldc; };
-
-// derived weight packs, built from the device-resident packed fp32 weights when a kernel first needs them
-static int fetch_packed(const PackedLayer& L, std::vector<float>& wp)
+// Derived weight packs, built from the device-resident packed fp32 weights when a kernel first needs them: fetch, `pack`, allocate, copy.
+// The slot takes the buffer only once the copy is complete: a failed copy must not leave a non-null pointer to garbage behind.
+template <typename T, typename Pack>
+static int derive_pack(const PackedLayer& L, DevBuf<T>& slot, const char* what, Pack pack)
 {
-    wp.resize((size_t)L.ks * L.ks * L.nch * L.cout_pad * CK);
+    if (slot) return PMX_OK;
+    std::vector<float> wp((size_t)L.ks * L.ks * L.nch * L.cout_pad * CK);
     PMX_HIP(hipMemcpy(wp.data(), L.d_w, wp.size() * sizeof(float), hipMemcpyDeviceToHost));
+    std::vector<T> out;
+    pack(wp, out);
+    DevBuf<T> d;
+    if (int rc = d.alloc(out.size())) return rc;
+    if (hipMemcpy(d, out.data(), out.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
+        pmx_set_error("%s weight pack: host-to-device copy failed: %s", what, hipGetErrorString(hipGetLastError()));
+        return PMX_ERR_HIP;
+    }
+    slot = std::move(d);
     return PMX_OK;
 }
 static int ensure_wino_pack(PackedLayer& L)
 {
-    if (L.d_ww) return PMX_OK;
-    std::vector<float> wp, ww;
-    if (int rc = fetch_packed(L, wp)) return rc;
-    pack_wino(wp, L.ks, L.nch, L.cout_pad, ww);
-    // (the pack becomes visible only once it is complete: a failed copy must not leave a non-null pointer to garbage behind)
-    DevBuf<float> d;
-    if (int rc = d.alloc(ww.size())) return rc;
-    if (hipMemcpy(d, ww.data(), ww.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        pmx_set_error("winograd weight pack: host-to-device copy failed: %s", hipGetErrorString(hipGetLastError()));
-        return PMX_ERR_HIP;
-    }
-    L.d_ww = std::move(d);
-    return PMX_OK;
+    return derive_pack(L, L.d_ww, "winograd", [&](const std::vector<float>& wp, std::vector<float>& o) { pack_wino(wp, L.ks, L.nch, L.cout_pad, o); });
 }
-// conv1_1's weights in the order conv1_wino_kernel's lanes want them: [channel half 2][k-pair 14][k of the pair 2][channel 32] (the 28th k is
-// zero) -- one contiguous 256-byte run per wave and k-pair.  Read out of the direct pack [tap][1 chunk][64][16] each lane gathered 14 dwords
-// 64 bytes apart: 1.7 us of a 25 us block (profiles/r05_conv1_wino_ablation.json).  Lives in the layer's otherwise unused Winograd slot.
+// (lives in conv1_1's otherwise unused Winograd slot)
 static int ensure_conv1_pack(PackedLayer& L)
 {
-    if (L.d_ww) return PMX_OK;
-    std::vector<float> wp;
-    if (int rc = fetch_packed(L, wp)) return rc;
-    std::vector<float> w1(2 * 14 * 2 * 32, 0.f);
-    for (int hf = 0; hf < 2; ++hf)
-        for (int sp = 0; sp < 14; ++sp)
-            for (int kk = 0; kk < 2; ++kk)
-                for (int n = 0; n < 32; ++n) {
-                    const int k = 2 * sp + kk;
-                    if (k < 27) w1[((hf * 14 + sp) * 2 + kk) * 32 + n] = wp[((size_t)(k / 3) * L.cout_pad + hf * 32 + n) * CK + k % 3];
-                }
-    DevBuf<float> d;
-    if (int rc = d.alloc(w1.size())) return rc;
-    if (hipMemcpy(d, w1.data(), w1.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        pmx_set_error("conv1_1 weight pack: host-to-device copy failed: %s", hipGetErrorString(hipGetLastError()));
-        return PMX_ERR_HIP;
-    }
-    L.d_ww = std::move(d);
-    return PMX_OK;
+    return derive_pack(L, L.d_ww, "conv1_1", [&](const std::vector<float>& wp, std::vector<float>& o) { pack_conv1(wp, L.cout_pad, o); });
 }
 static int ensure_bf16x3_pack(PackedLayer& L)
 {
-    if (L.d_w3) return PMX_OK;
-    std::vector<float> wp;
-    std::vector<uint16_t> w3;
-    if (int rc = fetch_packed(L, wp)) return rc;
-    pack_bf16x3(wp, L.ks * L.ks, L.nch, L.cout_pad, w3);
-    DevBuf<uint16_t> d;
-    if (int rc = d.alloc(w3.size())) return rc;
-    if (hipMemcpy(d, w3.data(), w3.size() * sizeof(uint16_t), hipMemcpyHostToDevice) != hipSuccess) {
-        pmx_set_error("bf16x3 weight pack: host-to-device copy failed: %s", hipGetErrorString(hipGetLastError()));
-        return PMX_ERR_HIP;
-    }
-    L.d_w3 = std::move(d);
-    return PMX_OK;
+    return derive_pack(L, L.d_w3, "bf16x3", [&](const std::vector<float>& wp, std::vector<uint16_t>& o) { pack_bf16x3(wp, L.ks * L.ks, L.nch, L.cout_pad, o); });
 }
-
 // the f16 pack (half the fp32 weights' bytes): every 3x3 / 7x7 layer in f16 mode
-static int ensure_f16_pack(PackedLayer& L)
-{
-    if (L.d_w16) return PMX_OK;
-    std::vector<float> wp;
-    std::vector<uint16_t> w16;
-    if (int rc = fetch_packed(L, wp)) return rc;
-    pack_f16(wp, w16);
-    DevBuf<uint16_t> d;
-    if (int rc = d.alloc(w16.size())) return rc;
-    if (hipMemcpy(d, w16.data(), w16.size() * sizeof(uint16_t), hipMemcpyHostToDevice) != hipSuccess) {
-        pmx_set_error("f16 weight pack: host-to-device copy failed: %s", hipGetErrorString(hipGetLastError()));
-        return PMX_ERR_HIP;
-    }
-    L.d_w16 = std::move(d);
-    return PMX_OK;
-}
+static int ensure_f16_pack(PackedLayer& L) { return derive_pack(L, L.d_w16, "f16", pack_f16); }
 
 // Launches one convolution (1 or 2 groups) whose ConvArgs describe the FINAL result (real bias, ReLU, pool, output slices).
 // With S > 1 K slices the slice blocks write raw partial sums into the context's slab scratch and conv_splitk_reduce
@@ -625,31 +590,37 @@ static int sk_reserve(pmx_ctx* c, size_t need)
     }
     return PMX_OK;
 }
-static int launch_conv(pmx_ctx* c, const ConvArgs& a0, int groups, int v, const SplitPlan& plan)
+// The slab form of a launch (K slices, Winograd units): S x groups slabs of `slab` floats in the scratch.  `a` (a copy of a0) is pointed at
+// them -- raw sums of all cout_pad columns: zero bias, no ReLU, no pool -- and `r`, the arguments of the kernel that adds the slabs of a
+// group (r.slabs[]), takes over what a0 says about the final result; its slab count and whatever else is its own are the caller's.
+template <typename Reduce>
+static int slab_redirect(pmx_ctx* c, const ConvArgs& a0, int groups, int S, size_t slab, unsigned long long kbounds, ConvArgs& a, Reduce& r)
 {
-    const int S = plan.S;
-    if (S <= 1) {
-        ConvArgs a = a0;
-        a.ksplit = 1; a.slab_stride = 0;
-        return conv_launch(v, a, groups, c->stream);
-    }
     PMX_CHECK(a0.cout_pad <= SK_ZERO_BIAS, PMX_ERR_INVALID, "split-K: cout_pad %d too large", a0.cout_pad);
-    const size_t slab = (size_t)a0.B * a0.H * a0.W * a0.cout_pad;
-    const size_t need = slab * S * groups;
-    if (int rc = sk_reserve(c, need)) return rc;
-    ConvArgs a = a0;
-    SplitKReduceArgs r;
+    if (int rc = sk_reserve(c, slab * S * groups)) return rc;
     memset(&r, 0, sizeof r);
     for (int g = 0; g < groups; ++g) {
         float* base = c->sk_scratch + (size_t)g * S * slab;
         r.slabs[g] = base; r.bias[g] = a0.g[g].bias; r.out[g] = a0.g[g].out; r.cout[g] = a0.g[g].cout;
         a.g[g].out = base; a.g[g].bias = c->sk_zero_bias; a.g[g].cout = a0.cout_pad;
     }
-    a.ldc = a0.cout_pad; a.relu = 0; a.pool = 0; a.ksplit = S; a.slab_stride = (long long)slab; a.kbounds = plan.bounds;
-    r.slab_stride = (long long)slab; r.ksplit = S; r.B = a0.B; r.H = a0.H; r.W = a0.W; r.ld_slab = a0.cout_pad; r.ldc = a0.ldc;
+    a.ldc = a0.cout_pad; a.relu = 0; a.pool = 0; a.ksplit = S; a.slab_stride = (long long)slab; a.kbounds = kbounds;
+    r.slab_stride = (long long)slab; r.B = a0.B; r.H = a0.H; r.W = a0.W; r.ld_slab = a0.cout_pad; r.ldc = a0.ldc;
     r.relu = a0.relu; r.pool = a0.pool;
-    int rc = conv_launch(v, a, groups, c->stream);
+    return PMX_OK;
+}
+static int launch_conv(pmx_ctx* c, const ConvArgs& a0, int groups, int v, const SplitPlan& plan)
+{
+    ConvArgs a = a0;
+    if (plan.S <= 1) {
+        a.ksplit = 1; a.slab_stride = 0;
+        return conv_launch(v, a, groups, c->stream);
+    }
+    SplitKReduceArgs r;
+    int rc = slab_redirect(c, a0, groups, plan.S, (size_t)a0.B * a0.H * a0.W * a0.cout_pad, plan.bounds, a, r);
     if (rc) return rc;
+    r.ksplit = plan.S;
+    if ((rc = conv_launch(v, a, groups, c->stream))) return rc;
     return conv_splitk_reduce(r, groups, c->stream);
 }
 
@@ -660,23 +631,12 @@ static int launch_wino_units(pmx_ctx* c, const ConvArgs& a0, int ks, int groups,
 {
     const int S = (a0.nch + g - 1) / g + (ks == 7 ? 3 : 0);
     PMX_CHECK(S >= 2 && S <= 8, PMX_ERR_INVALID, "winograd units: %d slabs", S);
-    PMX_CHECK(a0.cout_pad <= SK_ZERO_BIAS, PMX_ERR_INVALID, "split-K: cout_pad %d too large", a0.cout_pad);
-    const size_t slab = (size_t)a0.B * a0.H * a0.W * a0.cout_pad;
-    const size_t need = slab * S * groups;
-    if (int rc = sk_reserve(c, need)) return rc;
     ConvArgs a = a0;
     SplitKReduceArgs r;
-    memset(&r, 0, sizeof r);
-    for (int gi = 0; gi < groups; ++gi) {
-        float* base = c->sk_scratch + (size_t)gi * S * slab;
-        r.slabs[gi] = base; r.bias[gi] = a0.g[gi].bias; r.out[gi] = a0.g[gi].out; r.cout[gi] = a0.g[gi].cout;
-        a.g[gi].out = base; a.g[gi].bias = c->sk_zero_bias; a.g[gi].cout = a0.cout_pad;
-    }
-    a.ldc = a0.cout_pad; a.relu = 0; a.pool = 0; a.ksplit = S; a.slab_stride = (long long)slab; a.kbounds = (unsigned long long)g;
-    r.slab_stride = (long long)slab; r.ksplit = S; r.B = a0.B; r.H = a0.H; r.W = a0.W; r.ld_slab = a0.cout_pad; r.ldc = a0.ldc;
-    r.relu = a0.relu; r.pool = a0.pool;
-    int rc = conv_wino_launch(a, ks, groups, c->stream);
+    int rc = slab_redirect(c, a0, groups, S, (size_t)a0.B * a0.H * a0.W * a0.cout_pad, (unsigned long long)g, a, r);
     if (rc) return rc;
+    r.ksplit = S;
+    if ((rc = conv_wino_launch(a, ks, groups, c->stream))) return rc;
     return conv_splitk_reduce(r, groups, c->stream);
 }
 
@@ -684,13 +644,13 @@ static int launch_wino_units(pmx_ctx* c, const ConvArgs& a0, int ks, int groups,
 // last block of every image in unit mode (S units of g pass-1 chunks (+ row 6, column 6, tap (6, 6)) writing compact slabs) + the combine
 // kernel.  B = 32 at 46 x 46: 16 x 32 x 2 = 1024 full blocks = exactly 4 rounds of the 256 CUs, then 64 x 7 short unit blocks, instead of
 // 5 rounds of 18 x 32 x 2 rectangles.  tail_g = 0: every block (also the part-filled one) in the plain launch.
-struct WinoProf { std::string name; double flops, bytes, issued; };      // profile entry of the layer (null: not profiled)
+struct ConvProf { std::string name; double flops, bytes, issued; };      // profile entry of a layer's launch
 // the tails of all images of the launch as one stream of tiles, 32 per block (conv_wino_kernel<KS, 0, 1, 3>)?
 static bool wino_tail_merged(const pmx_ctx* c, const ConvArgs& a)
 {
     return c->opt_wino_tail_merge != 0 && wino_tail_mergeable(a.B, a.H, a.W, a.lda);
 }
-static int launch_wino_run(pmx_ctx* c, const ConvArgs& a0, int ks, int groups, int tail_g, const WinoProf* pf = nullptr)
+static int launch_wino_run(pmx_ctx* c, const ConvArgs& a0, int ks, int groups, int tail_g, const ConvProf* pf)      // (pf null: not profiled)
 {
     const int ntiles = PMX_WINO_RUN_TX * ((a0.H + 1) / 2), nblk = (ntiles + PMX_WINO_RUN_TILES - 1) / PMX_WINO_RUN_TILES, nfull = ntiles / PMX_WINO_RUN_TILES;
     ConvArgs a = a0;
@@ -720,25 +680,15 @@ static int launch_wino_run(pmx_ctx* c, const ConvArgs& a0, int ks, int groups, i
     PMX_CHECK(nfull >= 1 && nfull < nblk, PMX_ERR_INVALID, "winograd tail: no part-filled block (%d tiles)", ntiles);
     const int S = (a0.nch + tail_g - 1) / tail_g + (ks == 7 ? 3 : 0);
     PMX_CHECK(S >= 2 && S <= 8, PMX_ERR_INVALID, "winograd tail: %d slabs", S);
-    PMX_CHECK(a0.cout_pad <= SK_ZERO_BIAS, PMX_ERR_INVALID, "split-K: cout_pad %d too large", a0.cout_pad);
     const int nslab = a0.W / (2 * PMX_WINO_RUN_TX);
     // merged: the tails of all images as one stream of tiles, 32 per block (46 x 46: 17 tiles per image -- every MFMA row a real tile)
     const bool merged = wino_tail_merged(c, a0);
     const size_t slab = merged ? (size_t)wino_tail_merged_blocks(a0.B, a0.H) * PMX_WINO_RUN_TILES * 4 * a0.cout_pad      // [block of the stream][tile][pixel][cout_pad]
                                : (size_t)a0.B * nslab * PMX_WINO_RUN_TILES * 4 * a0.cout_pad;      // one block per (image, slab): [image][slab][tile][pixel][cout_pad]
-    const size_t need = slab * S * groups;
-    if (int rc = sk_reserve(c, need)) return rc;
     WinoTailReduceArgs r;
-    memset(&r, 0, sizeof r);
-    for (int gi = 0; gi < groups; ++gi) {
-        float* base = c->sk_scratch + (size_t)gi * S * slab;
-        r.slabs[gi] = base; r.bias[gi] = a0.g[gi].bias; r.out[gi] = a0.g[gi].out; r.cout[gi] = a0.g[gi].cout;
-        a.g[gi].out = base; a.g[gi].bias = c->sk_zero_bias; a.g[gi].cout = a0.cout_pad;
-    }
-    a.ldc = a0.cout_pad; a.relu = 0; a.pool = 0; a.ksplit = S; a.slab_stride = (long long)slab; a.kbounds = (unsigned long long)tail_g;
+    if ((rc = slab_redirect(c, a0, groups, S, slab, (unsigned long long)tail_g, a, r))) return rc;
     a.run_j0 = nfull; a.run_nb = 1;
-    r.slab_stride = (long long)slab; r.S = S; r.B = a0.B; r.H = a0.H; r.W = a0.W; r.ld_slab = a0.cout_pad; r.ldc = a0.ldc;
-    r.relu = a0.relu; r.run_j0 = nfull; r.run_nb = 1; r.nslab = nslab; r.pool = a0.pool; r.merged = merged;
+    r.S = S; r.run_j0 = nfull; r.run_nb = 1; r.nslab = nslab; r.merged = merged;
     // (profile mode 2 -- the dominant kernel only, inside timed regions -- leaves these two short launches without events: an event pair
     //  costs ~5 us of idle stream)
     const bool pf_all = pf && c->prof_on == 1;
@@ -750,8 +700,7 @@ static int launch_wino_run(pmx_ctx* c, const ConvArgs& a0, int ks, int groups, i
     return pf_all ? prof_end(c) : PMX_OK;
 }
 
-// Which form a 3x3 / 7x7 layer takes (conv_select.hip): 0 = direct kernels (+ split-K), 1 = the Winograd kernel (*run: in the run geometry,
-// *tail_g > 0: its part-filled last blocks in unit mode), 2 = the Winograd kernel in unit mode (*unit_g = chunks per pass-1 unit)
+// the context options the choice of a 3x3 / 7x7 layer's form depends on (conv_select.hip)
 static WinoSelectOpts wino_opts(const pmx_ctx* c, int ks, int groups, int lda)
 {
     WinoSelectOpts o;
@@ -761,195 +710,186 @@ static WinoSelectOpts wino_opts(const pmx_ctx* c, int ks, int groups, int lda)
     o.wino_split = c->opt_wino_split;
     return o;
 }
-static int wino_mode(const pmx_ctx* c, int ks, int cin_pad, int cout_pad, int cout, int ldc, int images, int H, int W, int pool, int* unit_g,
-                     int* run, int* tail_g, int groups = 1, int lda = 0)
+// every group of the launch has a Winograd form, and the groups agree in what the launch shares?
+static bool wino_layers_ok(const PackedLayer* L0, const PackedLayer* L1)
 {
-    return wino_select(wino_opts(c, ks, groups, lda), ks, cin_pad, cout_pad, cout, ldc, images, H, W, pool, unit_g, run, tail_g);
+    return wino_eligible(L0->ks, L0->cin_pad, L0->cout_pad) && (!L1 || (wino_eligible(L1->ks, L1->cin_pad, L1->cout_pad) && L1->cout == L0->cout));
 }
 
-// f16 mode (option "precision" = 2): a 3x3 / 7x7 layer as ONE conv_f16_kernel launch, whatever the batch (no Winograd, no split-K, no cut by
-// images: the per-output summation order must not depend on the launch); heterogeneous forwards on the 8 x 16 rectangle table of the level
-static int run_conv_f16(pmx_ctx* c, const char* label, int li0, int li1, const float* in0, const float* in1, int lda,
-                        float* out0, float* out1, int ldc, int B, int H, int W, int relu, int pool, int level)
+// What one convolution launch (1 or 2 groups of the same geometry) will do: the ONE place that knows which kernel form a layer shape takes
+// under the context options and which weight pack that form reads.  The network (run_conv) and the single-layer entry (pmx_conv2d) both
+// plan, then launch.
+//   FORM_DIRECT      the direct kernels: `variant` (+ its bf16x3 twin with option "precision" = 1), `split` = the K slices
+//   FORM_WINO        the Winograd kernel on 8 x 16 rectangles (a heterogeneous forward: over the segment table of the level)
+//   FORM_WINO_RUN    ... in the run geometry; tail_g > 0: the part-filled last blocks in unit mode, tail_g chunks per pass-1 unit
+//   FORM_WINO_UNITS  ... in unit mode, unit_g chunks per pass-1 unit
+//   FORM_F16         f16 mode (option "precision" = 2): a 3x3 / 7x7 layer as ONE conv_f16_kernel launch, whatever the batch (no Winograd, no
+//                    split-K, no cut by images: the per-output summation order must not depend on the launch)
+enum ConvForm { FORM_DIRECT, FORM_WINO, FORM_WINO_RUN, FORM_WINO_UNITS, FORM_F16 };
+struct ConvPlan {
+    ConvForm form = FORM_DIRECT;
+    ConvArgs a;                      // the FINAL result (real bias, ReLU, pool, output slices), weights = the pack of the form
+    int ks = 0, groups = 1, variant = 0, unit_g = 0, tail_g = 0;
+    SplitPlan split{};
+    bool prof = false;               // profiled under c->prof_on (never without a label)
+    ConvProf pf;
+};
+
+// in/out pointers are already offset to the group's channels; L1 null: one group; label null: never profiled
+// `level` (heterogeneous forward only, c->segs non-empty): the resolution level of the layer's input, 0 = network input .. 3 = 1/8; B, H, W
+// then carry the image count and the LARGEST map of the level (launch checks), the geometry comes from the segment table of the level.
+// Makes sure the derived pack of the form exists.
+static int plan_conv(pmx_ctx* c, ConvPlan& p, const char* label, PackedLayer* L0, PackedLayer* L1, const float* in0, const float* in1, int lda,
+                     float* out0, float* out1, int ldc, int B, int H, int W, int relu, int pool, int level)
 {
-    const PackedLayer& L0 = c->layers[li0];
-    const int groups = li1 >= 0 ? 2 : 1;
+    const PackedLayer& L = *L0;
+    const int ks = L.ks, groups = L1 ? 2 : 1;
+    const char* who = label ? label : "pmx_conv2d";
     const bool seg = !c->segs.empty() && level >= 0;
-    PMX_CHECK(c->segs.empty() || seg, PMX_ERR_INVALID, "heterogeneous forward: layer %s without a resolution level", label);
-    PMX_CHECK(groups == 1 || (c->layers[li1].ks == L0.ks && c->layers[li1].nch == L0.nch && c->layers[li1].cout_pad == L0.cout_pad), PMX_ERR_INVALID,
-              "conv f16: the two groups of %s differ in shape", label);
-    int rc;
-    if ((rc = ensure_f16_pack(c->layers[li0])) || (groups == 2 && (rc = ensure_f16_pack(c->layers[li1])))) return rc;
-    ConvArgs a;
+    const double npix = seg ? (double)c->seg_pix[level] : (double)B * H * W;
+    PackedLayer* const Lg[2] = {L0, L1};
+    auto ensure = [&](int (*fn)(PackedLayer&)) { const int rc = fn(*L0); return rc || !L1 ? rc : fn(*L1); };
+    p.ks = ks; p.groups = groups;
+    p.prof = label && (c->prof_on == 1 || (c->prof_on == 2 && ks == 7));
+    ConvArgs& a = p.a;
     memset(&a, 0, sizeof a);
-    a.g[0].in = in0; a.g[0].w = (const float*)L0.d_w16.get(); a.g[0].bias = L0.d_b; a.g[0].out = out0; a.g[0].cout = L0.cout;
-    if (groups == 2) {
-        const PackedLayer& L1 = c->layers[li1];
-        a.g[1].in = in1; a.g[1].w = (const float*)L1.d_w16.get(); a.g[1].bias = L1.d_b; a.g[1].out = out1; a.g[1].cout = L1.cout;
+    a.B = B; a.H = H; a.W = W; a.lda = lda; a.ldc = ldc; a.nch = L.nch; a.cout_pad = L.cout_pad; a.relu = relu; a.pool = pool;
+    double flops = 0;
+    for (int g = 0; g < groups; ++g) {
+        const PackedLayer& G = *Lg[g];
+        a.g[g].in = g ? in1 : in0; a.g[g].w = G.d_w; a.g[g].bias = G.d_b; a.g[g].out = g ? out1 : out0; a.g[g].cout = G.cout;
+        flops += 2.0 * npix * (double)G.cout * G.cin * G.ks * G.ks;
     }
-    a.B = B; a.H = H; a.W = W; a.lda = lda; a.ldc = ldc; a.nch = L0.nch; a.cout_pad = L0.cout_pad; a.relu = relu; a.pool = pool;
-    long long tiles = (long long)B * ((H + 7) / 8) * ((W + 15) / 16);
+    int rc;
+    if (c->opt_precision == 2 && ks > 1) {
+        p.form = FORM_F16;
+        PMX_CHECK(c->segs.empty() || seg, PMX_ERR_INVALID, "heterogeneous forward: layer %s without a resolution level", who);
+        PMX_CHECK(!L1 || (L1->ks == ks && L1->nch == L.nch && L1->cout_pad == L.cout_pad), PMX_ERR_INVALID, "conv f16: the two groups of %s differ in shape", who);
+        if ((rc = ensure(ensure_f16_pack))) return rc;
+        for (int g = 0; g < groups; ++g) a.g[g].w = (const float*)Lg[g]->d_w16.get();
+    } else if (seg) {
+        // heterogeneous launch: the plain Winograd kernel on 8 x 16 rectangles over all segments (every 3x3 / 7x7 layer of the pose network
+        // qualifies; its per-pixel arithmetic is that of a plain launch of each image alone -- oracle/conv_fma_ref::conv_wino)
+        PMX_CHECK(wino_layers_ok(L0, L1) && (c->opt_precision == 0 || c->opt_precision == 2), PMX_ERR_INVALID,
+                  "heterogeneous forward: layer %s has no Winograd form", who);
+        p.form = FORM_WINO;
+    } else {
+        p.variant = conv_pick_variant(ks, L.cout_pad, H, W, B * groups, c->opt_force[ks], c->opt_kernel_gen, pool, groups == 1 ? L.cin : 9999,
+                                      c->opt_precision == 1 && ks > 1);
+        if (c->opt_precision == 1 && ks > 1 && conv_bf16x3_twin(p.variant) >= 0) {
+            if ((rc = ensure(ensure_bf16x3_pack))) return rc;
+            p.variant = conv_bf16x3_twin(p.variant);
+            for (int g = 0; g < groups; ++g) a.g[g].w = (const float*)Lg[g]->d_w3.get();
+        }
+        int wrun = 0;
+        const int wmode = wino_layers_ok(L0, L1) ? wino_select(wino_opts(c, ks, groups, lda), ks, L.cin_pad, L.cout_pad, L.cout, ldc, B * groups, H, W,
+                                                               pool, &p.unit_g, &wrun, &p.tail_g) : 0;
+        p.form = wmode == 2 ? FORM_WINO_UNITS : wmode == 1 ? (wrun ? FORM_WINO_RUN : FORM_WINO) : FORM_DIRECT;
+    }
+    const bool wino = p.form == FORM_WINO || p.form == FORM_WINO_RUN || p.form == FORM_WINO_UNITS;
+    if (wino) {
+        if ((rc = ensure(ensure_wino_pack))) return rc;
+        a.nch = L.cin_pad / 32;
+        for (int g = 0; g < groups; ++g) a.g[g].w = Lg[g]->d_ww;
+    }
     if (seg) {
         const int t = PMX_SEG_RECT(level, pool);
         a.nseg = (int)c->segs.size(); a.segs = c->d_segs + (size_t)t * c->segs.size(); a.seg_tiles = c->seg_tiles[t];
-        tiles = a.seg_tiles;
     }
-    const bool prof_this = c->prof_on == 1 || (c->prof_on == 2 && L0.ks == 7);
-    if (prof_this) {
-        const double npix = seg ? (double)c->seg_pix[level] : (double)B * H * W;
-        double flops = 0;
-        for (int g = 0; g < groups; ++g) {
-            const PackedLayer& L = c->layers[g ? li1 : li0];
-            flops += 2.0 * npix * (double)L.cout * L.cin * L.ks * L.ks;
-        }
+    if (p.form == FORM_DIRECT) {
+        p.split = conv_pick_ksplit(p.variant, H, W, B, groups, L.cout_pad, L.nch, pool, c->opt_ksplit);
+        if (L.cout % 4 != 0 || ldc % 4 != 0 || (L1 && L1->cout != L.cout)) p.split.S = 1;
+    }
+    if (!p.prof) return PMX_OK;
+    // the profile entry: "<layer>|<kernel><what the form adds>", algorithmic FLOP, compulsory bytes (a whole launch in unit mode is
+    // entered without the pool's share), FLOP issued to the matrix cores
+    std::string kn;
+    double issued = flops;
+    if (p.form == FORM_F16) {
+        kn = ks == 7 ? "conv_f16_7x7" : "conv_f16_3x3";
         // issued: every MFMA of the launch -- the tile padding of the map edges, the channel padding of cin and of the block's BN columns
-        const int bn = conv_f16_bn(L0.cout_pad, (int)std::min<long long>(tiles, 1 << 30), groups);
-        const double issued = 2.0 * (double)tiles * 128.0 * (double)round_up(L0.cout, bn) * (L0.nch * CK) * L0.ks * L0.ks * groups;
-        const double bytes = 4.0 * npix * ((double)L0.cin * groups + (double)L0.cout * groups / (pool ? 4 : 1));
-        if ((rc = prof_begin(c, std::string(label) + (L0.ks == 7 ? "|conv_f16_7x7" : "|conv_f16_3x3"), flops, bytes, issued))) return rc;
+        const long long tiles = seg ? a.seg_tiles : (long long)B * ((H + 7) / 8) * ((W + 15) / 16);
+        const int bn = conv_f16_bn(L.cout_pad, (int)std::min<long long>(tiles, 1 << 30), groups);
+        issued = 2.0 * (double)tiles * 128.0 * (double)round_up(L.cout, bn) * (L.nch * CK) * ks * ks * groups;
+    } else if (wino) {
+        kn = ks == 7 ? "conv_wino_f2x2_7x7" : "conv_wino_f2x2_3x3";
+        // "r": run geometry; "/t<g>": its part-filled last blocks in unit mode, g chunks per pass-1 unit (part of the arithmetic), "m": merged tails
+        if (seg) kn += "/seg";
+        if (p.form == FORM_WINO_UNITS) kn += "/u" + std::to_string(p.unit_g);
+        if (p.form == FORM_WINO_RUN) kn += "r";
+        if (p.tail_g) kn += "/t" + std::to_string(p.tail_g) + (p.form == FORM_WINO_RUN && wino_tail_merged(c, a) ? "m" : "");
+        // products per 2 x 2 output tile and channel pair: 3x3: 16 of 36; 7x7: 4 x 16 + 4 x 8 + 4 = 100 of 196
+        issued = flops * (ks == 7 ? 100.0 / 196.0 : 16.0 / 36.0);
+    } else {
+        kn = conv_variant(p.variant).name;
+        if (p.split.S > 1) {       // "/k<chunks of slice 0>-<slice 1>-...": the K slices (+ the combine kernel) are part of the launch
+            kn += "/k";
+            for (int i = 0; i < p.split.S; ++i) kn += (i ? "-" : "") + std::to_string(p.split.sizes[i]);
+        }
     }
-    if ((rc = conv_f16_launch(L0.ks, a, groups, c->stream))) return rc;
-    return prof_this ? prof_end(c) : PMX_OK;
+    const double bytes = 4.0 * npix * ((double)L.cin * groups + (double)L.cout * groups / (pool && p.form != FORM_WINO_UNITS ? 4 : 1));
+    p.pf = ConvProf{std::string(label) + "|" + kn, flops, bytes, issued};
+    return PMX_OK;
 }
 
-// one launch of 1 or 2 groups (same geometry); in/out pointers are already offset to the group's channels
-// `level` (heterogeneous forward only, c->segs non-empty): the resolution level of the layer's input, 0 = network input .. 3 = 1/8; B, H, W
-// then carry the image count and the LARGEST map of the level (launch checks), the geometry comes from the segment table of the level
-static int run_conv(pmx_ctx* c, const char* label, int li0, int li1, const float* in0, const float* in1, int lda,
+// profile begin, the launch sequence of the plan's form, profile end
+static int launch_plan(pmx_ctx* c, const ConvPlan& p)
+{
+    const ConvProf* pf = p.prof ? &p.pf : nullptr;
+    if (p.form == FORM_WINO_RUN) return launch_wino_run(c, p.a, p.ks, p.groups, p.tail_g, pf);      // (up to three launches, an entry each)
+    int rc;
+    if (pf && (rc = prof_begin(c, pf->name, pf->flops, pf->bytes, pf->issued))) return rc;
+    switch (p.form) {
+    case FORM_F16: rc = conv_f16_launch(p.ks, p.a, p.groups, c->stream); break;
+    case FORM_WINO_UNITS: rc = launch_wino_units(c, p.a, p.ks, p.groups, p.unit_g); break;
+    case FORM_WINO: rc = conv_wino_launch(p.a, p.ks, p.groups, c->stream); break;
+    default: rc = launch_conv(c, p.a, p.groups, p.variant, p.split); break;
+    }
+    if (rc) return rc;
+    return pf ? prof_end(c) : PMX_OK;
+}
+
+// one layer of a forward: plan + launch.  A batch whose plain launch would end in a part-filled round of the CUs is cut in two first: the
+// images of the whole rounds, then the rest through the selection of THEIR count (conv_select.hip::wino_split_images); each half is an
+// ordinary run_conv on its images
+static int run_conv(pmx_ctx* c, const char* label, PackedLayer* L0, PackedLayer* L1, const float* in0, const float* in1, int lda,
                     float* out0, float* out1, int ldc, int B, int H, int W, int relu, int pool, int level = -1)
 {
-    const PackedLayer& L0 = c->layers[li0];
-    const int groups = li1 >= 0 ? 2 : 1;
     const bool seg = !c->segs.empty() && level >= 0;
-    if (c->opt_precision == 2 && L0.ks > 1) return run_conv_f16(c, label, li0, li1, in0, in1, lda, out0, out1, ldc, B, H, W, relu, pool, level);
-    // a batch whose plain launch would end in a part-filled round of the CUs: the images of the whole rounds first, then the rest through
-    // the selection of THEIR count (conv_select.hip::wino_split_images); each half is an ordinary run_conv on its images
-    if (!seg && c->split_suffix.empty() && c->opt_wino_split && B >= 2 && L0.ks > 1 && wino_eligible(L0.ks, L0.cin_pad, L0.cout_pad) &&
-        (groups == 1 || (wino_eligible(c->layers[li1].ks, c->layers[li1].cin_pad, c->layers[li1].cout_pad) && c->layers[li1].cout == L0.cout))) {
-        const int n0 = wino_split_images(wino_opts(c, L0.ks, groups, lda), L0.ks, L0.cin_pad, L0.cout_pad, L0.cout, ldc, B, groups, H, W, pool);
+    int rc;
+    if (!seg && c->split_suffix.empty() && c->opt_wino_split && B >= 2 && L0->ks > 1 && c->opt_precision != 2 && wino_layers_ok(L0, L1)) {
+        const int n0 = wino_split_images(wino_opts(c, L0->ks, L1 ? 2 : 1, lda), L0->ks, L0->cin_pad, L0->cout_pad, L0->cout, ldc, B, L1 ? 2 : 1, H, W, pool);
         if (n0 > 0 && n0 < B) {
             const size_t pin = (size_t)n0 * H * W * lda, pout = (size_t)n0 * (pool ? H / 2 : H) * (pool ? W / 2 : W) * ldc;
             c->split_suffix = "@0+" + std::to_string(n0);
-            int rc = run_conv(c, label, li0, li1, in0, in1, lda, out0, out1, ldc, n0, H, W, relu, pool, level);
+            rc = run_conv(c, label, L0, L1, in0, in1, lda, out0, out1, ldc, n0, H, W, relu, pool, level);
             if (!rc) {
                 c->split_suffix = "@" + std::to_string(n0) + "+" + std::to_string(B - n0);
-                rc = run_conv(c, label, li0, li1, in0 + pin, in1 ? in1 + pin : nullptr, lda, out0 + pout, out1 ? out1 + pout : nullptr, ldc, B - n0, H, W, relu, pool, level);
+                rc = run_conv(c, label, L0, L1, in0 + pin, in1 ? in1 + pin : nullptr, lda, out0 + pout, out1 ? out1 + pout : nullptr, ldc, B - n0, H, W, relu, pool, level);
             }
             c->split_suffix.clear();
             return rc;
         }
     }
-    const double npix = seg ? (double)c->seg_pix[level] : (double)B * H * W;
-    ConvArgs a;
-    memset(&a, 0, sizeof a);
-    a.g[0].in = in0; a.g[0].w = L0.d_w; a.g[0].bias = L0.d_b; a.g[0].out = out0; a.g[0].cout = L0.cout;
-    double flops = 2.0 * npix * (double)L0.cout * L0.cin * L0.ks * L0.ks;
-    if (groups == 2) {
-        const PackedLayer& L1 = c->layers[li1];
-        a.g[1].in = in1; a.g[1].w = L1.d_w; a.g[1].bias = L1.d_b; a.g[1].out = out1; a.g[1].cout = L1.cout;
-        flops += 2.0 * npix * (double)L1.cout * L1.cin * L1.ks * L1.ks;
-    }
-    a.B = B; a.H = H; a.W = W; a.lda = lda; a.ldc = ldc; a.nch = L0.nch; a.cout_pad = L0.cout_pad;
-    a.relu = relu; a.pool = pool;
-    int rc;
-    if (seg) {
-        // heterogeneous launch: the plain Winograd kernel on 8 x 16 rectangles over all segments (every 3x3 / 7x7 layer of the pose network
-        // qualifies; its per-pixel arithmetic is that of a plain launch of each image alone -- oracle/conv_fma_ref::conv_wino)
-        PMX_CHECK(wino_eligible(L0.ks, L0.cin_pad, L0.cout_pad) && (c->opt_precision == 0 || c->opt_precision == 2) &&
-                  (groups == 1 || (wino_eligible(c->layers[li1].ks, c->layers[li1].cin_pad, c->layers[li1].cout_pad) && c->layers[li1].cout == L0.cout)),
-                  PMX_ERR_INVALID, "heterogeneous forward: layer %s has no Winograd form", label);
-        if ((rc = ensure_wino_pack(c->layers[li0])) || (groups == 2 && (rc = ensure_wino_pack(c->layers[li1])))) return rc;
-        a.nch = L0.cin_pad / 32;
-        a.g[0].w = L0.d_ww;
-        if (groups == 2) a.g[1].w = c->layers[li1].d_ww;
-        const int t = PMX_SEG_RECT(level, pool);
-        a.nseg = (int)c->segs.size(); a.segs = c->d_segs + (size_t)t * c->segs.size(); a.seg_tiles = c->seg_tiles[t];
-        const bool prof_seg = c->prof_on == 1 || (c->prof_on == 2 && L0.ks == 7);
-        if (prof_seg) {
-            const double bytes = 4.0 * npix * ((double)L0.cin * groups + (double)L0.cout * groups / (pool ? 4 : 1));
-            if ((rc = prof_begin(c, std::string(label) + (L0.ks == 7 ? "|conv_wino_f2x2_7x7/seg" : "|conv_wino_f2x2_3x3/seg"), flops, bytes,
-                                 flops * (L0.ks == 7 ? 100.0 / 196.0 : 16.0 / 36.0)))) return rc;
-        }
-        if ((rc = conv_wino_launch(a, L0.ks, groups, c->stream))) return rc;
-        return prof_seg ? prof_end(c) : PMX_OK;
-    }
-    int v = conv_pick_variant(L0.ks, L0.cout_pad, H, W, B * groups, c->opt_force[L0.ks], c->opt_kernel_gen, pool, groups == 1 ? L0.cin : 9999,
-                              c->opt_precision == 1 && L0.ks > 1);
-    if (c->opt_precision == 1 && L0.ks > 1 && conv_bf16x3_twin(v) >= 0) {
-        if ((rc = ensure_bf16x3_pack(c->layers[li0])) || (groups == 2 && (rc = ensure_bf16x3_pack(c->layers[li1])))) return rc;
-        v = conv_bf16x3_twin(v);
-        a.g[0].w = (const float*)L0.d_w3.get();
-        if (groups == 2) a.g[1].w = (const float*)c->layers[li1].d_w3.get();
-    }
-    const bool prof_this = c->prof_on == 1 || (c->prof_on == 2 && L0.ks == 7);
-    const bool wino_ok = wino_eligible(L0.ks, L0.cin_pad, L0.cout_pad) &&
-                         (groups == 1 || (wino_eligible(c->layers[li1].ks, c->layers[li1].cin_pad, c->layers[li1].cout_pad) && c->layers[li1].cout == L0.cout));
-    int ug = 0, wrun = 0, wtail = 0;
-    const int wmode = wino_ok ? wino_mode(c, L0.ks, L0.cin_pad, L0.cout_pad, L0.cout, ldc, B * groups, H, W, pool, &ug, &wrun, &wtail, groups, lda) : 0;
-    const bool wino_plain = wmode == 1;
-    if (wmode && ((rc = ensure_wino_pack(c->layers[li0])) || (groups == 2 && (rc = ensure_wino_pack(c->layers[li1]))))) return rc;
-    if (wmode == 2) {
-        a.nch = L0.cin_pad / 32;
-        a.g[0].w = L0.d_ww;
-        if (groups == 2) a.g[1].w = c->layers[li1].d_ww;
-        if (prof_this) {
-            const double bytes = 4.0 * B * H * W * ((double)L0.cin * groups + (double)L0.cout * groups);
-            if ((rc = prof_begin(c, std::string(label) + (L0.ks == 7 ? "|conv_wino_f2x2_7x7/u" : "|conv_wino_f2x2_3x3/u") + std::to_string(ug), flops, bytes,
-                                 flops * (L0.ks == 7 ? 100.0 / 196.0 : 16.0 / 36.0)))) return rc;
-        }
-        if ((rc = launch_wino_units(c, a, L0.ks, groups, ug))) return rc;
-        return prof_this ? prof_end(c) : PMX_OK;
-    }
-    if (wino_plain) {
-        a.nch = L0.cin_pad / 32;
-        a.g[0].w = L0.d_ww;
-        if (groups == 2) a.g[1].w = c->layers[li1].d_ww;
-        if (prof_this) {
-            const double bytes = 4.0 * B * H * W * ((double)L0.cin * groups + (double)L0.cout * groups / (pool ? 4 : 1));
-            // "r": run geometry; "/t<g>": its part-filled last blocks in unit mode, g chunks per pass-1 unit (part of the arithmetic)
-            std::string kn = L0.ks == 7 ? "|conv_wino_f2x2_7x7" : "|conv_wino_f2x2_3x3";
-            if (wrun) kn += "r";
-            if (wtail) kn += "/t" + std::to_string(wtail) + (wrun && wino_tail_merged(c, a) ? "m" : "");      // "m": merged tails
-            // products per 2 x 2 output tile and channel pair: 3x3: 16 of 36; 7x7: 4 x 16 + 4 x 8 + 4 = 100 of 196
-            const double issued = flops * (L0.ks == 7 ? 100.0 / 196.0 : 16.0 / 36.0);
-            if (wrun) {
-                const WinoProf pf{std::string(label) + kn, flops, bytes, issued};
-                return launch_wino_run(c, a, L0.ks, groups, wtail, &pf);
-            }
-            if ((rc = prof_begin(c, std::string(label) + kn, flops, bytes, issued))) return rc;
-        }
-        if ((rc = wrun ? launch_wino_run(c, a, L0.ks, groups, wtail) : conv_wino_launch(a, L0.ks, groups, c->stream))) return rc;
-        return prof_this ? prof_end(c) : PMX_OK;
-    }
-    SplitPlan plan = conv_pick_ksplit(v, H, W, B, groups, L0.cout_pad, L0.nch, pool, c->opt_ksplit);
-    if (L0.cout % 4 != 0 || ldc % 4 != 0 || (groups == 2 && c->layers[li1].cout != L0.cout)) plan.S = 1;
-    if (prof_this) {
-        const double bytes = 4.0 * B * H * W * ((double)L0.cin * groups + (double)L0.cout * groups / (pool ? 4 : 1));
-        std::string kn = conv_variant(v).name;
-        if (plan.S > 1) {       // "/k<chunks of slice 0>-<slice 1>-...": the K slices (+ the combine kernel) are part of the launch
-            kn += "/k";
-            for (int i = 0; i < plan.S; ++i) kn += (i ? "-" : "") + std::to_string(plan.sizes[i]);
-        }
-        if ((rc = prof_begin(c, std::string(label) + "|" + kn, flops, bytes))) return rc;
-    }
-    if ((rc = launch_conv(c, a, groups, v, plan))) return rc;
-    return prof_this ? prof_end(c) : PMX_OK;
+    ConvPlan p;
+    if ((rc = plan_conv(c, p, label, L0, L1, in0, in1, lda, out0, out1, ldc, B, H, W, relu, pool, level))) return rc;
+    return launch_plan(c, p);
 }
 
 // the two 1x1 layers that end a stage (A: 128 -> cmid + ReLU, B: cmid -> cout [+ ReLU]) as ONE launch when the shapes allow
 // (else, or with option fuse_pairs = 0, as two run_conv launches through `mid`): bit-identical either way
-static int run_pair(pmx_ctx* c, const char* labelA, const char* labelB, int a0, int a1, int b0, int b1, const float* in0,
-                    const float* in1, int lda, float* mid0, float* mid1, int ldm, float* out0, float* out1, int ldc, int B, int H,
-                    int W, int reluB, int level = -1)
+static int run_pair(pmx_ctx* c, const char* labelA, const char* labelB, PackedLayer* a0, PackedLayer* a1, PackedLayer* b0, PackedLayer* b1,
+                    const float* in0, const float* in1, int lda, float* mid0, float* mid1, int ldm, float* out0, float* out1, int ldc, int B,
+                    int H, int W, int reluB, int level = -1)
 {
-    const PackedLayer& LA = c->layers[a0];
-    const PackedLayer& LB = c->layers[b0];
-    const int groups = a1 >= 0 ? 2 : 1;
+    const PackedLayer& LA = *a0;
+    const PackedLayer& LB = *b0;
+    const int groups = a1 ? 2 : 1;
     // (heterogeneous forward: a 1x1 layer only sees pixels -- the segments' maps are one run of seg_pix[level] pixels)
     const bool seg = !c->segs.empty() && level >= 0;
     const long long npix = seg ? c->seg_pix[level] : (long long)B * H * W;
     const bool ok = c->opt_fuse_pairs && c->opt_kernel_gen >= 6 && LA.ks == 1 && LB.ks == 1 && LA.cin_pad == 128 && LB.cin == LA.cout &&
-                    conv_pair_supported(LA.cin, LA.cout, LB.cout_pad) && (groups == 1 || c->layers[b1].cout_pad == LB.cout_pad);
+                    conv_pair_supported(LA.cin, LA.cout, LB.cout_pad) && (groups == 1 || b1->cout_pad == LB.cout_pad);
     int rc;
     PMX_CHECK(ok || !seg, PMX_ERR_INVALID, "heterogeneous forward: the 1x1 pair %s + %s has no fused form", labelA, labelB);
     if (!ok) {
@@ -960,8 +900,8 @@ static int run_pair(pmx_ctx* c, const char* labelA, const char* labelB, int a0, 
     memset(&p, 0, sizeof p);
     double flops = 0;
     for (int g = 0; g < groups; ++g) {
-        const PackedLayer& A = c->layers[g ? a1 : a0];
-        const PackedLayer& Bl = c->layers[g ? b1 : b0];
+        const PackedLayer& A = *(g ? a1 : a0);
+        const PackedLayer& Bl = *(g ? b1 : b0);
         p.g[g].in = g ? in1 : in0; p.g[g].w1 = A.d_w; p.g[g].b1 = A.d_b; p.g[g].w2 = Bl.d_w; p.g[g].b2 = Bl.d_b;
         p.g[g].out = g ? out1 : out0; p.g[g].cout = Bl.cout;
         flops += 2.0 * (double)npix * ((double)A.cout * A.cin + (double)Bl.cout * Bl.cin);
@@ -1000,9 +940,8 @@ static bool conv1_form(const pmx_ctx* c, int B, int H, int W, bool* fuse_out)
 
 static int run_conv1(pmx_ctx* c, int B, int H, int W)
 {
-    const int i1 = c->index.at("conv1_1"), i2 = c->index.at("conv1_2");
-    const PackedLayer& L1 = c->layers[i1];
-    const PackedLayer& L2 = c->layers[i2];
+    PackedLayer& L1 = c->layers[c->index.at("conv1_1")];
+    PackedLayer& L2 = c->layers[c->index.at("conv1_2")];
     bool fuse = false;
     const bool seg = !c->segs.empty();
     const bool wino1 = seg ? conv1_pairable(c) : conv1_form(c, B, H, W, &fuse);
@@ -1013,13 +952,13 @@ static int run_conv1(pmx_ctx* c, int B, int H, int W)
     if (seg && c->opt_precision == 2) {
         // f16 mode: pmx_forward_from_u8 has preprocessed the segments' pixels into in16; both layers on the level-0 rectangle tables
         PMX_CHECK(!in_u8, PMX_ERR_STATE, "conv1: a uint8 input in f16 mode");
-        if ((rc = run_conv(c, "conv1_1", i1, -1, c->in16, nullptr, PMX_IN_C, c->act0, nullptr, 64, B, H, W, 1, 0, 0))) return rc;
-        return run_conv(c, "conv1_2", i2, -1, c->act0, nullptr, 64, c->act1, nullptr, 64, B, H, W, 1, 1, 0);
+        if ((rc = run_conv(c, "conv1_1", &L1, nullptr, c->in16, nullptr, PMX_IN_C, c->act0, nullptr, 64, B, H, W, 1, 0, 0))) return rc;
+        return run_conv(c, "conv1_2", &L2, nullptr, c->act0, nullptr, 64, c->act1, nullptr, 64, B, H, W, 1, 1, 0);
     }
     PMX_CHECK(!seg || (wino1 && in_u8), PMX_ERR_INVALID, "heterogeneous forward: needs conv1 as conv1_wino_kernel on a uint8 input");
     if (!fuse && !wino1) {
-        if ((rc = run_conv(c, "conv1_1", i1, -1, c->in16, nullptr, PMX_IN_C, c->act0, nullptr, 64, B, H, W, 1, 0))) return rc;
-        return run_conv(c, "conv1_2", i2, -1, c->act0, nullptr, 64, c->act1, nullptr, 64, B, H, W, 1, 1);
+        if ((rc = run_conv(c, "conv1_1", &L1, nullptr, c->in16, nullptr, PMX_IN_C, c->act0, nullptr, 64, B, H, W, 1, 0))) return rc;
+        return run_conv(c, "conv1_2", &L2, nullptr, c->act0, nullptr, 64, c->act1, nullptr, 64, B, H, W, 1, 1);
     }
     ConvArgs a;
     memset(&a, 0, sizeof a);
@@ -1027,7 +966,7 @@ static int run_conv1(pmx_ctx* c, int B, int H, int W)
     a.g[1].w = L1.d_w; a.g[1].bias = L1.d_b;
     a.B = B; a.H = H; a.W = W; a.lda = PMX_IN_C; a.ldc = 64; a.nch = L2.nch; a.cout_pad = L2.cout_pad; a.relu = 1; a.pool = 1;
     if (wino1) {
-        if ((rc = ensure_wino_pack(c->layers[i2])) || (rc = ensure_conv1_pack(c->layers[i1]))) return rc;
+        if ((rc = ensure_wino_pack(L2)) || (rc = ensure_conv1_pack(L1))) return rc;
         a.g[0].w = L2.d_ww;
         a.g[1].w = L1.d_ww;
         if (in_u8) {                                      // the kernel preprocesses the uint8 batch itself (pmx_forward_from_u8)
@@ -1051,33 +990,44 @@ static int run_conv1(pmx_ctx* c, int B, int H, int W)
     return prof_end(c);
 }
 
+// conv1_1 ... conv4_2, the VGG stem all three networks share (CocoPoseNet.py:136-149, FaceNet.py:78-92): act1 and act0 in turn, the three
+// F.max_pooling_2d fused into conv1_2, conv2_2, conv3_4; the result (1/8 resolution, 512 channels) in act1
+// (level = the resolution level of the layer's input, read only by a heterogeneous forward: pmx_multi.hip)
+static int run_stem(pmx_ctx* c, int B, int H, int W)
+{
+    static const struct { const char* name; int cin, cout, level, pool; } stem[] = {
+        {"conv2_1", 64, 128, 1, 0}, {"conv2_2", 128, 128, 1, 1}, {"conv3_1", 128, 256, 2, 0}, {"conv3_2", 256, 256, 2, 0},
+        {"conv3_3", 256, 256, 2, 0}, {"conv3_4", 256, 256, 2, 1}, {"conv4_1", 256, 512, 3, 0}, {"conv4_2", 512, 512, 3, 0}};
+    int rc = run_conv1(c, B, H, W);
+    float* in = c->act1;
+    float* out = c->act0;
+    for (const auto& s : stem) {
+        if (rc) break;
+        rc = run_conv(c, s.name, &c->layers[c->index.at(s.name)], nullptr, in, nullptr, s.cin, out, nullptr, s.cout, B, H >> s.level, W >> s.level, 1, s.pool, s.level);
+        std::swap(in, out);
+    }
+    return rc;
+}
+
 // FaceNet / HandNet forward (models/FaceNet.py:78-160): one branch, groups = 1 everywhere
 static int forward_cpm(pmx_ctx* c, int B, int H, int W)
 {
-    auto id = [&](const char* n) { return c->index.at(n); };
+    auto L = [&](const char* n) { return &c->layers[c->index.at(n)]; };
     int rc;
-    const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4, H8 = H / 8, W8 = W / 8;
+    const int H8 = H / 8, W8 = W / 8;
     const int CC = c->cat_c;
     float* cat = c->cat;
     float* heat = cat + c->cat_heat;
-#define RUN1(name, in, lda, out, ldc, h, w, relu, pool) \
-    do { if ((rc = run_conv(c, name, id(name), -1, in, nullptr, lda, out, nullptr, ldc, B, h, w, relu, pool))) return rc; } while (0)
-    if ((rc = run_conv1(c, B, H, W))) return rc;
-    RUN1("conv2_1", c->act1, 64, c->act0, 128, H2, W2, 1, 0);
-    RUN1("conv2_2", c->act0, 128, c->act1, 128, H2, W2, 1, 1);
-    RUN1("conv3_1", c->act1, 128, c->act0, 256, H4, W4, 1, 0);
-    RUN1("conv3_2", c->act0, 256, c->act1, 256, H4, W4, 1, 0);
-    RUN1("conv3_3", c->act1, 256, c->act0, 256, H4, W4, 1, 0);
-    RUN1("conv3_4", c->act0, 256, c->act1, 256, H4, W4, 1, 1);
-    RUN1("conv4_1", c->act1, 256, c->act0, 512, H8, W8, 1, 0);
-    RUN1("conv4_2", c->act0, 512, c->act1, 512, H8, W8, 1, 0);
-    RUN1("conv4_3", c->act1, 512, c->act0, 512, H8, W8, 1, 0);
-    RUN1("conv4_4", c->act0, 512, c->act1, 512, H8, W8, 1, 0);
-    RUN1("conv5_1", c->act1, 512, c->act0, 512, H8, W8, 1, 0);
-    RUN1("conv5_2", c->act0, 512, c->act1, 512, H8, W8, 1, 0);
-    RUN1("conv5_3_CPM", c->act1, 512, cat, CC, H8, W8, 1, 0);               // feature_map -> cat[:, 0:128]
+#define RUN1(name, in, lda, out, ldc) \
+    do { if ((rc = run_conv(c, name, L(name), nullptr, in, nullptr, lda, out, nullptr, ldc, B, H8, W8, 1, 0))) return rc; } while (0)
+    if ((rc = run_stem(c, B, H, W))) return rc;
+    RUN1("conv4_3", c->act1, 512, c->act0, 512);
+    RUN1("conv4_4", c->act0, 512, c->act1, 512);
+    RUN1("conv5_1", c->act1, 512, c->act0, 512);
+    RUN1("conv5_2", c->act0, 512, c->act1, 512);
+    RUN1("conv5_3_CPM", c->act1, 512, cat, CC);               // feature_map -> cat[:, 0:128]
     // conv6_1_CPM (reads the 128 feature channels) -> conv6_2_CPM (stage-1 heat maps -> cat[:, 128:128+C])
-    if ((rc = run_pair(c, "conv6_1_CPM", "conv6_2_CPM", id("conv6_1_CPM"), -1, id("conv6_2_CPM"), -1, cat, nullptr, CC, c->brT, nullptr, 512,
+    if ((rc = run_pair(c, "conv6_1_CPM", "conv6_2_CPM", L("conv6_1_CPM"), nullptr, L("conv6_2_CPM"), nullptr, cat, nullptr, CC, c->brT, nullptr, 512,
                        heat, nullptr, CC, B, H8, W8, 0))) return rc;
     char nm[48], nm2[48];
     for (int s = 2; s <= 6 && s <= c->opt_stop_stage; ++s) {
@@ -1088,11 +1038,11 @@ static int forward_cpm(pmx_ctx* c, int B, int H, int W)
             else if (i % 2 == 0) { in = c->brA; lda = 128; }
             else { in = c->brB; lda = 128; }
             out = i % 2 == 1 ? c->brA : c->brB;
-            RUN1(nm, in, lda, out, 128, H8, W8, 1, 0);
+            RUN1(nm, in, lda, out, 128);
         }
         snprintf(nm, sizeof nm, "Mconv6_stage%d", s);
         snprintf(nm2, sizeof nm2, "Mconv7_stage%d", s);
-        if ((rc = run_pair(c, nm, nm2, id(nm), -1, id(nm2), -1, c->brA, nullptr, 128, c->brB, nullptr, 128, heat, nullptr, CC, B, H8, W8, 0)))
+        if ((rc = run_pair(c, nm, nm2, L(nm), nullptr, L(nm2), nullptr, c->brA, nullptr, 128, c->brB, nullptr, 128, heat, nullptr, CC, B, H8, W8, 0)))
             return rc;
     }
 #undef RUN1
@@ -1107,30 +1057,22 @@ int pmx_forward_from_in16(pmx_ctx* c, int B, int H, int W)
 {
     PMX_CHECK(c->segs.empty() || c->kind == NET_POSE, PMX_ERR_INVALID, "heterogeneous forward: posenet only");
     if (c->kind != NET_POSE) return forward_cpm(c, B, H, W);
-    auto id = [&](const char* n) { return c->index.at(n); };
+    auto L = [&](const char* n) { return &c->layers[c->index.at(n)]; };
     int rc;
-    const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4, H8 = H / 8, W8 = W / 8;
+    const int H8 = H / 8, W8 = W / 8;
 #define RUN(...) do { if ((rc = run_conv(c, __VA_ARGS__))) return rc; } while (0)
     // stem (CocoPoseNet.py:136-151)
     // (the last argument = the resolution level, read only by a heterogeneous forward: pmx_multi.hip)
-    if ((rc = run_conv1(c, B, H, W))) return rc;
-    RUN("conv2_1", id("conv2_1"), -1, c->act1, nullptr, 64, c->act0, nullptr, 128, B, H2, W2, 1, 0, 1);
-    RUN("conv2_2", id("conv2_2"), -1, c->act0, nullptr, 128, c->act1, nullptr, 128, B, H2, W2, 1, 1, 1);
-    RUN("conv3_1", id("conv3_1"), -1, c->act1, nullptr, 128, c->act0, nullptr, 256, B, H4, W4, 1, 0, 2);
-    RUN("conv3_2", id("conv3_2"), -1, c->act0, nullptr, 256, c->act1, nullptr, 256, B, H4, W4, 1, 0, 2);
-    RUN("conv3_3", id("conv3_3"), -1, c->act1, nullptr, 256, c->act0, nullptr, 256, B, H4, W4, 1, 0, 2);
-    RUN("conv3_4", id("conv3_4"), -1, c->act0, nullptr, 256, c->act1, nullptr, 256, B, H4, W4, 1, 1, 2);
-    RUN("conv4_1", id("conv4_1"), -1, c->act1, nullptr, 256, c->act0, nullptr, 512, B, H8, W8, 1, 0, 3);
-    RUN("conv4_2", id("conv4_2"), -1, c->act0, nullptr, 512, c->act1, nullptr, 512, B, H8, W8, 1, 0, 3);
-    RUN("conv4_3_CPM", id("conv4_3_CPM"), -1, c->act1, nullptr, 512, c->act0, nullptr, 256, B, H8, W8, 1, 0, 3);
-    RUN("conv4_4_CPM", id("conv4_4_CPM"), -1, c->act0, nullptr, 256, c->cat + PMX_CAT_FEAT, nullptr, PMX_CAT_C, B, H8, W8, 1, 0, 3);
+    if ((rc = run_stem(c, B, H, W))) return rc;
+    RUN("conv4_3_CPM", L("conv4_3_CPM"), nullptr, c->act1, nullptr, 512, c->act0, nullptr, 256, B, H8, W8, 1, 0, 3);
+    RUN("conv4_4_CPM", L("conv4_4_CPM"), nullptr, c->act0, nullptr, 256, c->cat + PMX_CAT_FEAT, nullptr, PMX_CAT_C, B, H8, W8, 1, 0, 3);
     // stage 1 (CocoPoseNet.py:154-165); L1 = PAF branch, L2 = heat-map branch
     float* cat = c->cat;
-    RUN("conv5_1_CPM", id("conv5_1_CPM_L1"), id("conv5_1_CPM_L2"), cat, cat, PMX_CAT_C, c->brA, c->brA + 128, 256, B, H8, W8, 1, 0, 3);
-    RUN("conv5_2_CPM", id("conv5_2_CPM_L1"), id("conv5_2_CPM_L2"), c->brA, c->brA + 128, 256, c->brB, c->brB + 128, 256, B, H8, W8, 1, 0, 3);
-    RUN("conv5_3_CPM", id("conv5_3_CPM_L1"), id("conv5_3_CPM_L2"), c->brB, c->brB + 128, 256, c->brA, c->brA + 128, 256, B, H8, W8, 1, 0, 3);
+    RUN("conv5_1_CPM", L("conv5_1_CPM_L1"), L("conv5_1_CPM_L2"), cat, cat, PMX_CAT_C, c->brA, c->brA + 128, 256, B, H8, W8, 1, 0, 3);
+    RUN("conv5_2_CPM", L("conv5_2_CPM_L1"), L("conv5_2_CPM_L2"), c->brA, c->brA + 128, 256, c->brB, c->brB + 128, 256, B, H8, W8, 1, 0, 3);
+    RUN("conv5_3_CPM", L("conv5_3_CPM_L1"), L("conv5_3_CPM_L2"), c->brB, c->brB + 128, 256, c->brA, c->brA + 128, 256, B, H8, W8, 1, 0, 3);
     // conv5_4 (128 -> 512, ReLU) -> conv5_5 (512 -> 38 | 19): one launch
-    if ((rc = run_pair(c, "conv5_4_CPM", "conv5_5_CPM", id("conv5_4_CPM_L1"), id("conv5_4_CPM_L2"), id("conv5_5_CPM_L1"), id("conv5_5_CPM_L2"),
+    if ((rc = run_pair(c, "conv5_4_CPM", "conv5_5_CPM", L("conv5_4_CPM_L1"), L("conv5_4_CPM_L2"), L("conv5_5_CPM_L1"), L("conv5_5_CPM_L2"),
                        c->brA, c->brA + 128, 256, c->brT, c->brT + 512, 1024, cat + PMX_CAT_PAF, cat + PMX_CAT_HEAT, PMX_CAT_C, B, H8, W8, 0, 3)))
         return rc;
     // stages 2-6 (CocoPoseNet.py:168-260)
@@ -1146,13 +1088,13 @@ int pmx_forward_from_in16(pmx_ctx* c, int B, int H, int W)
             else { in0 = c->brB; in1 = c->brB + 128; lda = 256; }
             if (i % 2 == 1) { o0 = c->brA; o1 = c->brA + 128; }
             else { o0 = c->brB; o1 = c->brB + 128; }
-            RUN(lab, id(n1), id(n2), in0, in1, lda, o0, o1, 256, B, H8, W8, 1, 0, 3);
+            RUN(lab, L(n1), L(n2), in0, in1, lda, o0, o1, 256, B, H8, W8, 1, 0, 3);
         }
         // Mconv6 (1x1 128 -> 128, ReLU; reads Mconv5's output in brA) -> Mconv7 (1x1 128 -> 38 | 19, into the cat slices): one launch
         snprintf(n1, sizeof n1, "Mconv6_stage%d_L1", s); snprintf(n2, sizeof n2, "Mconv6_stage%d_L2", s);
         snprintf(m1, sizeof m1, "Mconv7_stage%d_L1", s); snprintf(m2, sizeof m2, "Mconv7_stage%d_L2", s);
         snprintf(lab, sizeof lab, "Mconv6_stage%d", s); snprintf(lab2, sizeof lab2, "Mconv7_stage%d", s);
-        if ((rc = run_pair(c, lab, lab2, id(n1), id(n2), id(m1), id(m2), c->brA, c->brA + 128, 256, c->brB, c->brB + 128, 256,
+        if ((rc = run_pair(c, lab, lab2, L(n1), L(n2), L(m1), L(m2), c->brA, c->brA + 128, 256, c->brB, c->brB + 128, 256,
                            cat + PMX_CAT_PAF, cat + PMX_CAT_HEAT, PMX_CAT_C, B, H8, W8, 0, 3))) return rc;
     }
 #undef RUN
@@ -1177,10 +1119,7 @@ static int check_forward_args(pmx_ctx* c, const void* p, int B, int H, int W)
     PMX_CHECK(H >= 8 && W >= 8 && H % 8 == 0 && W % 8 == 0, PMX_ERR_INVALID, "forward: H, W must be multiples of 8 (got %d x %d)", H, W);
     PMX_CHECK((size_t)H * W <= (size_t)c->max_h * c->max_w, PMX_ERR_CAPACITY, "forward: %d x %d exceeds the context capacity %d x %d",
               H, W, c->max_h, c->max_w);
-    int missing = 0;
-    for (auto& l : c->layers) missing += l.set ? 0 : 1;
-    PMX_CHECK(missing == 0, PMX_ERR_WEIGHTS, "forward: %d of %d layers have no weights", missing, (int)c->layers.size());
-    return PMX_OK;
+    return pmx_check_weights(c);
 }
 
 extern "C" int pmx_forward_u8(pmx_ctx* c, const uint8_t* img, int B, int H, int W, int on_device)
@@ -1239,8 +1178,6 @@ extern "C" int pmx_forward_f32(pmx_ctx* c, const float* x, int B, int H, int W, 
 // OpenCV INTER_LINEAR uint8 tables for one axis: [idx0 | idx1 | coef0 | coef1], each `dst` ints.
 // fx = float((d + 0.5) * scale - 0.5) with scale = 1 / (dst / src) in double; s = floor(fx); fx -= s;
 // s < 0 -> (0, fx = 0); s >= src - 1 -> (src - 1, fx = 0); coefficients cvRound((1 - fx) * 2048), cvRound(fx * 2048).
-void pmx_make_resize_table(int dst, int src, int* tab);
-static void make_resize_table(int dst, int src, int* tab) { pmx_make_resize_table(dst, src, tab); }
 void pmx_make_resize_table(int dst, int src, int* tab)
 {
     const double scale = 1.0 / ((double)dst / (double)src);
@@ -1276,8 +1213,8 @@ extern "C" int pmx_forward_u8_resized(pmx_ctx* c, const uint8_t* img, int B, int
     const size_t ntab = (size_t)4 * (w + h);
     if ((rc = c->rs_tab.ensure(ntab, c->stream))) return rc;
     std::vector<int> tab(ntab);
-    make_resize_table(w, src_w, tab.data());
-    make_resize_table(h, src_h, tab.data() + 4 * w);
+    pmx_make_resize_table(w, src_w, tab.data());
+    pmx_make_resize_table(h, src_h, tab.data() + 4 * w);
     PMX_HIP(hipStreamSynchronize(c->stream));     // the table buffer may still be in use by a queued resize
     PMX_HIP(hipMemcpy(c->rs_tab, tab.data(), ntab * sizeof(int), hipMemcpyHostToDevice));
     if (c->prof_on == 1 && (rc = prof_begin(c, "resize_u8|resize_linear_u8", 0, (double)nsrc + (double)B * h * w * 3))) return rc;
@@ -1360,7 +1297,7 @@ extern "C" int pmx_set_gaussian(pmx_ctx* c, const double* taps, int radius)
 }
 
 // np.linspace(0, in-1, num=out) grid + the corner indices / weights of Chainer's ResizeImages (see oracle)
-static void make_grid(int in, int out, std::vector<int>& i0, std::vector<int>& i1, std::vector<double>& lo, std::vector<double>& hi)
+void pmx_make_upsample_grid(int in, int out, std::vector<int>& i0, std::vector<int>& i1, std::vector<double>& lo, std::vector<double>& hi)
 {
     i0.resize(out); i1.resize(out); lo.resize(out); hi.resize(out);
     const double start = 0.0, stop = (double)(in - 1);
@@ -1382,10 +1319,6 @@ static void make_grid(int in, int out, std::vector<int>& i0, std::vector<int>& i
         i1[k] = f + 1 > in - 1 ? in - 1 : (f + 1 < 0 ? 0 : f + 1);
         lo[k] = wl; hi[k] = wh;
     }
-}
-void pmx_make_upsample_grid(int in, int out, std::vector<int>& i0, std::vector<int>& i1, std::vector<double>& lo, std::vector<double>& hi)
-{
-    make_grid(in, out, i0, i1, lo, hi);
 }
 
 void pmx_pp_gauss(const pmx_ctx* c, std::vector<double>& g, PPTables& t)
@@ -1433,7 +1366,7 @@ int pmx_ensure_tables(pmx_ctx* c, int in_h, int in_w, int out_h, int out_w, int 
     }
     std::vector<int> i0, i1; std::vector<double> lo, hi;
     PMX_HIP(hipStreamSynchronize(c->stream));
-    make_grid(in_w, out_w, i0, i1, lo, hi);
+    pmx_make_upsample_grid(in_w, out_w, i0, i1, lo, hi);
     if (flip_x) {       // column x of the mirrored map = column out_w - 1 - x of the resized one: same samples, same arithmetic
         std::reverse(i0.begin(), i0.end()); std::reverse(i1.begin(), i1.end());
         std::reverse(lo.begin(), lo.end()); std::reverse(hi.begin(), hi.end());
@@ -1442,7 +1375,7 @@ int pmx_ensure_tables(pmx_ctx* c, int in_h, int in_w, int out_h, int out_w, int 
     PMX_HIP(hipMemcpy(t.xi1, i1.data(), out_w * sizeof(int), hipMemcpyHostToDevice));
     PMX_HIP(hipMemcpy(t.xlo, lo.data(), out_w * sizeof(double), hipMemcpyHostToDevice));
     PMX_HIP(hipMemcpy(t.xhi, hi.data(), out_w * sizeof(double), hipMemcpyHostToDevice));
-    make_grid(in_h, out_h, i0, i1, lo, hi);
+    pmx_make_upsample_grid(in_h, out_h, i0, i1, lo, hi);
     PMX_HIP(hipMemcpy(t.yi0, i0.data(), out_h * sizeof(int), hipMemcpyHostToDevice));
     PMX_HIP(hipMemcpy(t.yi1, i1.data(), out_h * sizeof(int), hipMemcpyHostToDevice));
     PMX_HIP(hipMemcpy(t.ylo, lo.data(), out_h * sizeof(double), hipMemcpyHostToDevice));
@@ -1881,6 +1814,8 @@ extern "C" int pmx_profile_entry(pmx_ctx* c, int i, char* name, int cap, double*
 }
 
 // ---------------------------------------------------------------------------- single-layer test entry
+// One layer that is not in the context's table, through the dispatcher of the network (plan_conv + launch_plan) under the context's options:
+// the whole batch as ONE plan (no cut by images), never profiled; avg_ms = `iters` launches of that plan between two events.
 extern "C" int pmx_conv2d(pmx_ctx* c, const float* x, const float* w, const float* bias, int B, int cin, int H, int W, int cout,
                           int ks, int relu, int pool, float* y, int iters, double* avg_ms)
 {
@@ -1890,82 +1825,44 @@ extern "C" int pmx_conv2d(pmx_ctx* c, const float* x, const float* w, const floa
     PMX_CHECK(!pool || (H % 2 == 0 && W % 2 == 0), PMX_ERR_INVALID, "pmx_conv2d: pool needs even H, W");
     PMX_DEV(c);
     std::vector<int> cmap = identity_map(cin);
-    const int cin_pad = (int)cmap.size(), cpad = cout_pad_of(cout);
+    PackedLayer L;                                           // (its buffers, derived packs included, are freed on every way out)
+    L.set = true; L.cin = cin; L.cout = cout; L.ks = ks;
+    L.cin_pad = (int)cmap.size(); L.cout_pad = cout_pad_of(cout); L.nch = L.cin_pad / CK;
     std::vector<float> wp, bp;
-    pack_weights(w, bias, cout, cin, ks, cmap, cpad, wp, bp);
+    pack_weights(w, bias, cout, cin, ks, cmap, L.cout_pad, wp, bp);
     const int Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W;
-    DevBuf<float> d_x, d_xn, d_w, d_b, d_y, d_yn, d_ww;      // (freed on every way out)
-    DevBuf<uint16_t> d_w3;
-    const size_t nx = (size_t)B * cin * H * W, nxn = (size_t)B * H * W * cin_pad, ny = (size_t)B * cout * Ho * Wo;
+    DevBuf<float> d_x, d_xn, d_y, d_yn;
+    const size_t nx = (size_t)B * cin * H * W, nxn = (size_t)B * H * W * L.cin_pad, ny = (size_t)B * cout * Ho * Wo;
     int rc;
-    if ((rc = d_x.alloc(nx)) || (rc = d_xn.alloc(nxn)) || (rc = d_w.alloc(wp.size())) || (rc = d_b.alloc(bp.size())) ||
+    if ((rc = d_x.alloc(nx)) || (rc = d_xn.alloc(nxn)) || (rc = L.d_w.alloc(wp.size())) || (rc = L.d_b.alloc(bp.size())) ||
         (rc = d_y.alloc(ny)) || (rc = d_yn.alloc(ny))) return rc;
     PMX_HIP(hipMemcpy(d_x, x, nx * 4, hipMemcpyHostToDevice));
     PMX_HIP(hipMemsetAsync(d_xn, 0, nxn * 4, c->stream));
-    PMX_HIP(hipMemcpy(d_w, wp.data(), wp.size() * 4, hipMemcpyHostToDevice));
-    PMX_HIP(hipMemcpy(d_b, bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
+    PMX_HIP(hipMemcpy(L.d_w, wp.data(), wp.size() * 4, hipMemcpyHostToDevice));
+    PMX_HIP(hipMemcpy(L.d_b, bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
     // poison the output so that unwritten elements are caught by the test
     PMX_HIP(hipMemsetAsync(d_yn, 0xFF, ny * 4, c->stream));
-    rc = launch_nchw_to_nhwc(d_x, d_xn, B, cin, H, W, cin_pad, 0, c->stream);
-    ConvArgs a;
-    memset(&a, 0, sizeof a);
-    a.g[0].in = d_xn; a.g[0].w = d_w; a.g[0].bias = d_b; a.g[0].out = d_yn; a.g[0].cout = cout;
-    a.B = B; a.H = H; a.W = W; a.lda = cin_pad; a.ldc = cout; a.nch = cin_pad / CK; a.cout_pad = cpad; a.relu = relu; a.pool = pool;
-    const int v = conv_pick_variant(ks, cpad, H, W, B, c->opt_force[ks], c->opt_kernel_gen, pool, cin, c->opt_precision == 1 && ks > 1);
-    int v_run = v;
-    if (c->opt_precision == 1 && conv_bf16x3_twin(v) >= 0 && ks > 1) {
-        std::vector<uint16_t> w3;
-        pack_bf16x3(wp, ks * ks, cin_pad / CK, cpad, w3);
-        if ((rc = d_w3.alloc(w3.size()))) return rc;
-        PMX_HIP(hipMemcpy(d_w3, w3.data(), w3.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        a.g[0].w = (const float*)d_w3.get();
-        v_run = conv_bf16x3_twin(v);
-    }
-    if (c->opt_precision == 2 && ks > 1) {          // f16 mode: the f16 kernel, whatever the shape
-        std::vector<uint16_t> w16;
-        pack_f16(wp, w16);
-        if ((rc = d_w3.alloc(w16.size()))) return rc;
-        PMX_HIP(hipMemcpy(d_w3, w16.data(), w16.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        a.g[0].w = (const float*)d_w3.get();
-    }
-    SplitPlan plan = conv_pick_ksplit(v_run, H, W, B, 1, cpad, cin_pad / CK, pool, c->opt_ksplit);
-    if (cout % 4 != 0) plan.S = 1;
-    int ug = 0, wrun = 0, wtail = 0;
-    const bool f16 = c->opt_precision == 2 && ks > 1;
-    const int wmode = f16 ? 0 : wino_mode(c, ks, cin_pad, cpad, cout, cout, B, H, W, pool, &ug, &wrun, &wtail, 1, a.lda);
-    const bool wino = wmode == 1;
-    if (wino) {
-        std::vector<float> ww;
-        pack_wino(wp, ks, cin_pad / CK, cpad, ww);
-        if ((rc = d_ww.alloc(ww.size()))) return rc;
-        PMX_HIP(hipMemcpy(d_ww, ww.data(), ww.size() * sizeof(float), hipMemcpyHostToDevice));
-        a.g[0].w = d_ww; a.nch = cin_pad / 32;
-    }
-    if (ug) {
-        std::vector<float> ww;
-        pack_wino(wp, ks, cin_pad / CK, cpad, ww);
-        if ((rc = d_ww.alloc(ww.size()))) return rc;
-        PMX_HIP(hipMemcpy(d_ww, ww.data(), ww.size() * sizeof(float), hipMemcpyHostToDevice));
-        a.g[0].w = d_ww; a.nch = cin_pad / 32;
-    }
-    auto launch_conv = [&](pmx_ctx* cc, const ConvArgs& aa, int gg, int vv, const SplitPlan& pp) {
-        if (f16) return conv_f16_launch(ks, aa, gg, cc->stream);
-        if (ug) return launch_wino_units(cc, aa, ks, gg, ug);
-        if (wino && wrun) return launch_wino_run(cc, aa, ks, gg, wtail);
-        return wino ? conv_wino_launch(aa, ks, gg, cc->stream) : ::launch_conv(cc, aa, gg, vv, pp);
-    };
-    if (!rc) rc = launch_conv(c, a, 1, v_run, plan);
+    if ((rc = launch_nchw_to_nhwc(d_x, d_xn, B, cin, H, W, L.cin_pad, 0, c->stream))) return rc;
+    ConvPlan p;
+    if ((rc = plan_conv(c, p, nullptr, &L, nullptr, d_xn, nullptr, L.cin_pad, d_yn, nullptr, cout, B, H, W, relu, pool, -1))) return rc;
+    rc = launch_plan(c, p);
     if (!rc && iters > 0) {
-        hipEvent_t e0, e1;
-        PMX_HIP(hipEventCreate(&e0)); PMX_HIP(hipEventCreate(&e1));
-        PMX_HIP(hipEventRecord(e0, c->stream));
-        for (int i = 0; i < iters && !rc; ++i) rc = launch_conv(c, a, 1, v_run, plan);
-        PMX_HIP(hipEventRecord(e1, c->stream));
-        PMX_HIP(hipEventSynchronize(e1));
-        float ms = 0.f;
-        PMX_HIP(hipEventElapsedTime(&ms, e0, e1));
-        if (avg_ms) *avg_ms = ms / iters;
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        auto timed = [&]() -> int {
+            PMX_HIP(hipEventCreate(&e0)); PMX_HIP(hipEventCreate(&e1));
+            PMX_HIP(hipEventRecord(e0, c->stream));
+            int r = PMX_OK;
+            for (int i = 0; i < iters && !r; ++i) r = launch_plan(c, p);
+            PMX_HIP(hipEventRecord(e1, c->stream));
+            PMX_HIP(hipEventSynchronize(e1));
+            float ms = 0.f;
+            PMX_HIP(hipEventElapsedTime(&ms, e0, e1));
+            if (avg_ms) *avg_ms = ms / iters;
+            return r;
+        };
+        rc = timed();
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
     }
     if (!rc) rc = launch_nhwc_to_nchw(d_yn, d_y, B, cout, Ho, Wo, cout, 0, c->stream);
     if (!rc) {

@@ -1,7 +1,7 @@
 """TEST INFRASTRUCTURE -- NumPy restatement of `cv2.resize(img, (w, h))` (INTER_LINEAR, uint8) used at reference
 pose_detector.py:493.  PARITY UNPINNED: OpenCV is an unpinned third-party dependency of the reference that cannot be
 installed here, so this follows OpenCV's published fixed-point algorithm; the product's HIP kernel
-(csrc/prep.hip::resize_linear_u8_kernel, tables from pmx_api.hip::make_resize_table) is tested bit-exactly against it.
+(csrc/prep.hip::resize_linear_u8_kernel, tables from pmx_api.hip::pmx_make_resize_table) is tested bit-exactly against it.
 Only tests/ may import this module."""
 import numpy as np
 
