@@ -1075,6 +1075,10 @@ int pmx_forward_from_in16(pmx_ctx* c, int B, int H, int W)
     if ((rc = run_pair(c, "conv5_4_CPM", "conv5_5_CPM", L("conv5_4_CPM_L1"), L("conv5_4_CPM_L2"), L("conv5_5_CPM_L1"), L("conv5_5_CPM_L2"),
                        c->brA, c->brA + 128, 256, c->brT, c->brT + 512, 1024, cat + PMX_CAT_PAF, cat + PMX_CAT_HEAT, PMX_CAT_C, B, H8, W8, 0, 3)))
         return rc;
+    // validation-loss hook (pmx_loss.hip; uniform batches): the stage's outputs lie in the cat slices until the next stage's last launch
+    const bool hook = c->ls_on && c->segs.empty();
+    int n_stages = 1;
+    if (hook && (rc = pmx_loss_stage(c, 1, B, H8, W8))) return rc;
     // stages 2-6 (CocoPoseNet.py:168-260)
     char n1[48], n2[48], m1[48], m2[48], lab[48], lab2[48];
     for (int s = 2; s <= 6 && s <= c->opt_stop_stage; ++s) {
@@ -1096,7 +1100,10 @@ int pmx_forward_from_in16(pmx_ctx* c, int B, int H, int W)
         snprintf(lab, sizeof lab, "Mconv6_stage%d", s); snprintf(lab2, sizeof lab2, "Mconv7_stage%d", s);
         if ((rc = run_pair(c, lab, lab2, L(n1), L(n2), L(m1), L(m2), c->brA, c->brA + 128, 256, c->brB, c->brB + 128, 256,
                            cat + PMX_CAT_PAF, cat + PMX_CAT_HEAT, PMX_CAT_C, B, H8, W8, 0, 3))) return rc;
+        n_stages = s;
+        if (hook && (rc = pmx_loss_stage(c, s, B, H8, W8))) return rc;
     }
+    if (hook && (rc = pmx_loss_finish(c, n_stages, B, H8, W8))) return rc;
 #undef RUN
     c->maps_valid = true; c->maps_external = false;
     c->cur_B = B; c->cur_fh = H8; c->cur_fw = W8;
@@ -1119,7 +1126,8 @@ static int check_forward_args(pmx_ctx* c, const void* p, int B, int H, int W)
     PMX_CHECK(H >= 8 && W >= 8 && H % 8 == 0 && W % 8 == 0, PMX_ERR_INVALID, "forward: H, W must be multiples of 8 (got %d x %d)", H, W);
     PMX_CHECK((size_t)H * W <= (size_t)c->max_h * c->max_w, PMX_ERR_CAPACITY, "forward: %d x %d exceeds the context capacity %d x %d",
               H, W, c->max_h, c->max_w);
-    return pmx_check_weights(c);
+    if (int rc = pmx_check_weights(c)) return rc;
+    return c->ls_on ? pmx_loss_check(c, B, H, W) : PMX_OK;
 }
 
 extern "C" int pmx_forward_u8(pmx_ctx* c, const uint8_t* img, int B, int H, int W, int on_device)

@@ -240,7 +240,25 @@ struct pmx_ctx {
     HostBuf<char> bx_host;
     hipEvent_t bx_copied = nullptr; bool bx_pending = false;
     DevBuf<char> bx_dev, bx_rec;
+    // pmx_loss.hip (validation loss).  Targets at h/8 x w/8, [image][map pixel][38 PAF | 19 heat] (the cat slices' order), the resized ignore
+    // mask [image][map pixel]; the poses they came from (device: label kernel; host: pmx_get_labels); the corner-aligned grid of (h, w) ->
+    // (h/8, w/8); per (stage slot, block, branch) partial sums and the 2 x PMX_LOSS_SLOTS means.  Slot PMX_LOSS_SLOTS - 1 = pmx_loss_current_maps.
+    DevBuf<float> ls_tgt, ls_full;                        // ls_full: 57 full-resolution planes of ONE image (pmx_get_labels, pmx_loss_set_targets)
+    DevBuf<uint8_t> ls_mask, ls_mask_in;
+    DevBuf<double> ls_poses, ls_part, ls_out;
+    DevBuf<int> ls_off;                                   // first person of image b (batch + 1 entries)
+    DevBuf<char> ls_grid;                                 // [xlo | xhi | ylo | yhi] doubles, [xi0 | xi1 | yi0 | yi1] ints
+    std::vector<double> ls_h_poses; std::vector<int> ls_h_off;
+    std::vector<uint8_t> ls_h_mask;                       // the caller's ignore mask, copied before the call returns (the upload reads this copy)
+    double ls_sigma = 0, ls_width = 0;
+    int ls_grid_h = 0, ls_grid_w = 0;
+    int ls_on = 0;                                        // pmx_loss_enable
+    int ls_B = 0, ls_h = 0, ls_w = 0;                     // the targets' batch and network-input size (0: no targets)
+    bool ls_have_poses = false;
+    int ls_stages = 0;                                    // stages of the last hooked forward (0: none yet)
 };
+constexpr int PMX_LOSS_SLOTS = 7;
+constexpr int PMX_LOSS_MAX_BLOCKS = 256;
 
 #define PMX_DEV(c) PMX_HIP(hipSetDevice((c)->device))
 
@@ -268,5 +286,13 @@ void pmx_cubic_table(int src, int dst, bool fixed, int* out);
 // pixels lie end to end at d_u8 (on the device)
 int build_seg_tables(pmx_ctx* c, const std::vector<SegGeo>& g);
 int forward_segments(pmx_ctx* c, const uint8_t* d_u8, const std::vector<SegGeo>& g, int B);
+// pmx_loss.hip: the hook of the uniform forward.  pmx_loss_check runs with the forward's argument checks (hook on: targets of this batch and
+// size, else PMX_ERR_STATE); pmx_loss_stage enqueues the loss launch of stage `stage` (1 .. 6) over the cat slices, pmx_loss_finish the
+// final launch.  PMX_LOSS_NO_MIXED: the refusal of the mixed-size and precise entries while the hook is on.
+int pmx_loss_check(pmx_ctx* c, int B, int H, int W);
+int pmx_loss_stage(pmx_ctx* c, int stage, int B, int fh, int fw);
+int pmx_loss_finish(pmx_ctx* c, int n_stages, int B, int fh, int fw);
+#define PMX_LOSS_NO_MIXED(c, what) \
+    PMX_CHECK(!(c)->ls_on, PMX_ERR_STATE, what ": the validation-loss hook is on (pmx_loss_enable) and covers uniform batches only")
 // c->smoothed (and c->pp.smoothed) at `floats` floats at least, grown to exactly that once the stream no longer uses the old maps
 int pmx_ensure_smoothed(pmx_ctx* c, size_t floats);

@@ -150,6 +150,7 @@ extern "C" int pmx_forward_u8_images(pmx_ctx* c, const uint8_t* bgr, const int* 
 {
     PMX_CHECK(c && bgr && net_hw, PMX_ERR_INVALID, "pmx_forward_u8_images: null arg");
     PMX_CHECK(c->kind == NET_POSE, PMX_ERR_STATE, "pmx_forward_u8_images: posenet contexts only");
+    PMX_LOSS_NO_MIXED(c, "pmx_forward_u8_images");
     const std::vector<Geo> g = segments_of(net_hw, nullptr, B > 0 ? B : 0);
     int rc = seg_capacity_check(c, g, B);
     if (rc || (rc = pmx_check_weights(c))) return rc;
@@ -221,6 +222,7 @@ extern "C" int pmx_detect_images(pmx_ctx* c, const pmx_image* imgs, int B)
 {
     PMX_CHECK(c && imgs, PMX_ERR_INVALID, "pmx_detect_images: null arg");
     PMX_CHECK(c->kind == NET_POSE, PMX_ERR_STATE, "pmx_detect_images: posenet contexts only");
+    PMX_LOSS_NO_MIXED(c, "pmx_detect_images");
     PMX_CHECK(B >= 1 && B <= c->max_batch, PMX_ERR_CAPACITY, "pmx_detect_images: %d images outside 1..%d", B, c->max_batch);
     std::vector<int> net_hw(2 * (size_t)B), map_hw(2 * (size_t)B);
     std::vector<double> scale(2 * (size_t)B);

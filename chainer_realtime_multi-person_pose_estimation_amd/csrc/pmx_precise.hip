@@ -144,6 +144,7 @@ static void lane_swap(pmx_ctx* c, int i)
 extern "C" int pmx_precise_begin_batch(pmx_ctx* c, int n_images, int orig_h, int orig_w)
 {
     PMX_CHECK(c && c->kind == NET_POSE, PMX_ERR_INVALID, "pmx_precise_begin: posenet context required");
+    PMX_LOSS_NO_MIXED(c, "pmx_precise_begin");
     PMX_CHECK(orig_h >= 1 && orig_w >= 1, PMX_ERR_INVALID, "pmx_precise_begin: bad size");
     PMX_CHECK(n_images >= 1 && n_images <= c->max_batch, PMX_ERR_CAPACITY, "pmx_precise_begin: %d images outside 1..%d (the context's batch capacity)",
               n_images, c->max_batch);
@@ -193,6 +194,7 @@ extern "C" int pmx_precise_add_scale_at(pmx_ctx* c, const uint8_t* imgs, int sca
 static int precise_add_scale(pmx_ctx* c, const uint8_t* imgs, int scaled_h, int scaled_w, int slot)
 {
     PMX_CHECK(c && imgs && c->pr_h > 0 && c->pr_n > 0, PMX_ERR_STATE, "pmx_precise_add_scale: call pmx_precise_begin first");
+    PMX_LOSS_NO_MIXED(c, "pmx_precise_add_scale");
     PMX_CHECK(scaled_h >= 1 && scaled_w >= 1, PMX_ERR_INVALID, "bad size");
     PMX_DEV(c);
     const int oh = c->pr_h, ow = c->pr_w, n = c->pr_n;

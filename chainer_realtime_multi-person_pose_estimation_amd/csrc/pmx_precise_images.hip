@@ -219,6 +219,7 @@ extern "C" int pmx_detect_precise_images(pmx_ctx* c, const pmx_precise_image* im
 {
     PMX_CHECK(c && imgs, PMX_ERR_INVALID, "pmx_detect_precise_images: null arg");
     PMX_CHECK(c->kind == NET_POSE, PMX_ERR_STATE, "pmx_detect_precise_images: posenet contexts only");
+    PMX_LOSS_NO_MIXED(c, "pmx_detect_precise_images");
     PMX_CHECK(n >= 1 && n <= c->max_batch, PMX_ERR_CAPACITY, "pmx_detect_precise_images: %d images outside 1..%d (the context's batch capacity)", n,
               c->max_batch);
     PMX_CHECK(c->opt_precision == 0 || c->opt_precision == 2, PMX_ERR_INVALID,

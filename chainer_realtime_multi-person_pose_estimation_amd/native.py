@@ -26,7 +26,7 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB_PATH = os.path.join(CSRC, 'libpose_mi355x.so')
 HEADER = os.path.join(os.path.dirname(HERE), 'include', 'pose_mi355x.h')
 SOURCES = [('pmx_api.hip', []), ('pmx_precise.hip', []), ('pmx_multi.hip', []), ('pmx_precise_images.hip', ['-ffp-contract=off']), ('conv_mfma.hip', []), ('conv_wino.hip', ['-mllvm', '-pragma-unroll-threshold=200000']), ('conv1_wino.hip', []), ('conv_f16.hip', []), ('conv_select.hip', []), ('prep.hip', ['-ffp-contract=off']),
-           ('postproc.hip', ['-ffp-contract=off']), ('pmx_boxes.hip', ['-ffp-contract=off'])]
+           ('postproc.hip', ['-ffp-contract=off']), ('pmx_boxes.hip', ['-ffp-contract=off']), ('pmx_loss.hip', ['-ffp-contract=off'])]
 # the opt-in bf16x3 kernels (option "precision" = 1; DESIGN.md 4.1.5: frozen, slower than the fp32 Winograd path) are NOT part of the
 # default library: PMX_BUILD_BF16X3=1 in the environment of the build adds their translation unit (the stamp then differs, so the
 # library is rebuilt when the variable changes)
@@ -308,6 +308,14 @@ def load():
         'pmx_profile_entry': (ci, [vp, ci, C.c_char_p, ci, dp, C.POINTER(C.c_int64), dp, dp]),
         'pmx_profile_issued': (ci, [vp, ci, dp]),
         'pmx_conv2d': (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, ci, dp]),
+        'pmx_loss_set_poses': (ci, [vp, vp, vp, ci, ci, ci, vp, cd, cd]),
+        'pmx_loss_set_targets': (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci]),
+        'pmx_loss_enable': (ci, [vp, ci]),
+        'pmx_loss_get': (ci, [vp, dp, dp, ip]),
+        'pmx_loss_current_maps': (ci, [vp, dp, dp]),
+        'pmx_validate_batch': (ci, [vp, vp, ci, ci, ci, ci, vp]),
+        'pmx_get_labels': (ci, [vp, ci, vp, vp, ci, ci]),
+        'pmx_get_loss_targets': (ci, [vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)     # AttributeError if the .so lacks a declared symbol
@@ -356,6 +364,7 @@ class Engine(object):
         self._B = 0
         # host-side record of what was installed, so that a larger context can take over (PoseDetector._grow)
         self._layers, self._options, self._stream_ptr, self._caps_set = {}, {}, None, None
+        self._loss_shape = None              # (batch, h, w) of the current loss targets
 
     def _check(self, rc):
         if rc != 0:
@@ -813,6 +822,94 @@ class Engine(object):
         out = np.empty((h, w), np.float32)
         self._check(self.lib.pmx_get_smoothed(self._ctx, image, joint, _ptr(out), h, w))
         return out
+
+    # ---- validation loss (include/pose_mi355x.h: Validator.evaluate, train_coco_pose_estimation.py:129-159) ----------
+    @staticmethod
+    def _poses_arg(poses_per_image):
+        """a list of (n_i, 18, 3) pose arrays -> (flat float64 rows, int32 counts)"""
+        per = [np.asarray(p, dtype=np.float64).reshape(-1, N_JOINTS, 3) for p in poses_per_image]
+        n = np.ascontiguousarray([len(p) for p in per], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate(per) if per else np.zeros((0, N_JOINTS, 3)), dtype=np.float64)
+        return flat, n
+
+    def _mask_arg(self, ignore_mask, shape):
+        if ignore_mask is None:
+            return None
+        m = np.ascontiguousarray(np.asarray(ignore_mask) != 0, dtype=np.uint8)
+        if m.shape != tuple(shape):
+            raise ValueError('ignore mask of shape %r, expected %r' % (m.shape, tuple(shape)))
+        return m
+
+    def loss_set_poses(self, poses_per_image, h, w, ignore_mask=None, heat_sigma=7, paf_width=8):
+        """Targets of the next hooked forwards from poses: per image an (n, 18, 3) array of (x, y, v) rows in network-input pixels;
+        ignore_mask (B, h, w), non-zero = ignored.  Asynchronous."""
+        flat, n = self._poses_arg(poses_per_image)
+        m = self._mask_arg(ignore_mask, (len(n), int(h), int(w)))
+        self._check(self.lib.pmx_loss_set_poses(self._ctx, _ptr(flat), _ptr(n), len(n), int(h), int(w), None if m is None else _ptr(m),
+                                                float(heat_sigma), float(paf_width)))
+        self._loss_shape = (len(n), int(h), int(w))
+
+    def loss_set_targets(self, paf_t, heat_t, h, w, ignore_mask=None):
+        """Targets the caller made: (B, 38, th, tw) / (B, 19, th, tw) float32 at th x tw = h x w (resized on the device) or h/8 x w/8."""
+        paf_t = np.ascontiguousarray(paf_t, dtype=np.float32)
+        heat_t = np.ascontiguousarray(heat_t, dtype=np.float32)
+        B, cp, th, tw = paf_t.shape
+        if cp != N_PAF or heat_t.shape != (B, N_HEAT, th, tw):
+            raise ValueError('targets of shapes %r / %r' % (paf_t.shape, heat_t.shape))
+        m = self._mask_arg(ignore_mask, (B, th, tw))
+        self._check(self.lib.pmx_loss_set_targets(self._ctx, _ptr(paf_t), _ptr(heat_t), None if m is None else _ptr(m), B, th, tw, int(h), int(w)))
+        self._loss_shape = (B, int(h), int(w))
+
+    def loss_enable(self, on=True):
+        """on: every uniform forward / detect_batch accumulates the six stage losses against the targets (no synchronisation)."""
+        self._check(self.lib.pmx_loss_enable(self._ctx, int(bool(on))))
+
+    def loss_get(self):
+        """(paf_losses (6,), heat_losses (6,), n_stages) of the last hooked forward (synchronises)."""
+        p, h, n = np.zeros(6), np.zeros(6), C.c_int(0)
+        self._check(self.lib.pmx_loss_get(self._ctx, p.ctypes.data_as(C.POINTER(C.c_double)), h.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n)))
+        return p, h, n.value
+
+    def loss_current_maps(self):
+        """(paf_loss, heat_loss) of the current maps (forward or set_maps) against the targets (synchronises)."""
+        p, h = C.c_double(0), C.c_double(0)
+        self._check(self.lib.pmx_loss_current_maps(self._ctx, C.byref(p), C.byref(h)))
+        return p.value, h.value
+
+    def validate_batch(self, imgs=None, device_ptr=None, shape=None):
+        """forward_u8 with the hook + loss_get -> (total, paf_losses (6,), heat_losses (6,))."""
+        out = np.zeros(13)
+        if device_ptr is not None:
+            B, H, W = shape
+            p, on_dev = C.c_void_p(device_ptr), 1
+        else:
+            imgs = np.ascontiguousarray(imgs, dtype=np.uint8)
+            B, H, W, c3 = imgs.shape
+            assert c3 == 3
+            p, on_dev = _ptr(imgs), 0
+        self._check(self.lib.pmx_validate_batch(self._ctx, p, B, H, W, on_dev, _ptr(out)))
+        self._B = B
+        self._fhw = (H // 8, W // 8)
+        return float(out[0]), out[1:7].copy(), out[7:13].copy()
+
+    def labels(self, image=0):
+        """(pafs (38, h, w), heatmaps (19, h, w)) float32: the full-resolution labels of image `image` of the last loss_set_poses."""
+        if self._loss_shape is None:          # the library reports the call-sequence error
+            self._check(self.lib.pmx_get_labels(self._ctx, int(image), None, None, 0, 0))
+        _, h, w = self._loss_shape
+        paf, heat = np.empty((N_PAF, h, w), np.float32), np.empty((N_HEAT, h, w), np.float32)
+        self._check(self.lib.pmx_get_labels(self._ctx, int(image), _ptr(paf), _ptr(heat), h, w))
+        return paf, heat
+
+    def loss_targets(self):
+        """(paf_t (B, 38, h/8, w/8), heat_t (B, 19, h/8, w/8) float32, mask (B, h/8, w/8) bool): the current targets."""
+        if self._loss_shape is None:
+            self._check(self.lib.pmx_get_loss_targets(self._ctx, None, None, None))
+        B, h, w = self._loss_shape
+        paf, heat = np.empty((B, N_PAF, h // 8, w // 8), np.float32), np.empty((B, N_HEAT, h // 8, w // 8), np.float32)
+        mask = np.empty((B, h // 8, w // 8), np.uint8)
+        self._check(self.lib.pmx_get_loss_targets(self._ctx, _ptr(paf), _ptr(heat), _ptr(mask)))
+        return paf, heat, mask.astype(bool)
 
     # ---- measurement -------------------------------------------------------------------------------
     def timer_start(self):

@@ -490,6 +490,96 @@ class PoseDetector(object):
                 raise r
         return out
 
+    # ---- validation loss (reference train_coco_pose_estimation.py:129-159, labels coco_data_loader.py:208-268) --------------------
+    @staticmethod
+    def _check_poses(poses, what='poses'):
+        """-> (n, 18, 3) float64 rows (x, y, v); ValueError for another shape or a visible joint at a non-finite position"""
+        try:
+            p = np.asarray(poses, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError('%s: an (n, 18, 3) array of (x, y, v) rows expected' % what)
+        if p.size == 0:
+            return np.zeros((0, len(JointType), 3))
+        if p.ndim != 3 or p.shape[1:] != (len(JointType), 3):
+            raise ValueError('%s: an (n, 18, 3) array of (x, y, v) rows expected, got shape %r' % (what, p.shape))
+        if not np.isfinite(p[..., :2][p[..., 2] > 0]).all():
+            raise ValueError('%s: a visible joint (v > 0) at a non-finite position' % what)
+        return p
+
+    @staticmethod
+    def _check_label_shape(shape_hw):
+        try:
+            h, w = (int(v) for v in shape_hw)
+        except (TypeError, ValueError):
+            raise ValueError('shape_hw: (h, w) expected, got %r' % (shape_hw,))
+        if h < 8 or w < 8 or h % 8 or w % 8:
+            raise ValueError('shape_hw: positive multiples of 8 expected (the network input size), got %d x %d' % (h, w))
+        return h, w
+
+    def generate_labels(self, shape_hw, poses):
+        """The reference's label maps for one image of `shape_hw` = (h, w) network-input pixels (multiples of 8) and `poses` (n, 18, 3) rows
+        (x, y, v): `generate_pafs` (params['paf_sigma']) and `generate_heatmaps` (params['heatmap_sigma']) of coco_data_loader.py:208-268,
+        evaluated on the device -> (pafs (38, h, w), heatmaps (19, h, w)) float32."""
+        h, w = self._check_label_shape(shape_hw)
+        poses = self._check_poses(poses)
+        self._grow(1, h, w)
+        self.engine.loss_set_poses([poses], h, w, None, params['heatmap_sigma'], params['paf_sigma'])
+        return self.engine.labels(0)
+
+    @classmethod
+    def _check_validation_args(cls, imgs, poses_per_image, ignore_masks):
+        imgs = [np.asarray(im) for im in imgs]
+        if len(imgs) == 0:
+            raise ValueError('validation_loss needs at least one image')
+        shape = imgs[0].shape
+        for im in imgs:
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError('validation_loss needs uint8 H x W x 3 images')
+            if im.shape != shape:
+                raise ValueError('validation_loss needs images of one size (the validation loader yields insize x insize), got %r and %r'
+                                 % (shape, im.shape))
+        cls._check_label_shape(shape[:2])
+        if len(poses_per_image) != len(imgs):
+            raise ValueError('validation_loss: %d images but poses for %d' % (len(imgs), len(poses_per_image)))
+        poses = [cls._check_poses(p, 'poses of image %d' % i) for i, p in enumerate(poses_per_image)]
+        masks = None
+        if ignore_masks is not None:
+            if len(ignore_masks) != len(imgs):
+                raise ValueError('validation_loss: %d images but %d ignore masks' % (len(imgs), len(ignore_masks)))
+            masks = [np.asarray(m) for m in ignore_masks]
+            for i, m in enumerate(masks):
+                if m.shape != shape[:2]:
+                    raise ValueError('ignore mask %d: shape %r, expected %r' % (i, m.shape, shape[:2]))
+        return imgs, poses, masks
+
+    def validation_loss(self, imgs, poses_per_image, ignore_masks=None):
+        """What `Validator.evaluate` reports for one batch (train_coco_pose_estimation.py:146-157): the forward pass and compute_loss, the
+        masked mean squared error of all six stages against the label maps of the poses -- on the device.  imgs: B uint8 BGR images of one
+        size (multiples of 8; already at the network input size); poses_per_image: per image (n, 18, 3) rows (x, y, v) in those pixels;
+        ignore_masks: per image an (h, w) array, non-zero = ignored (already dilated, coco_data_loader.py:340).  More images than the
+        engine's batch run in chunks, averaged weighted by their sizes.  -> {'val/loss', 'val/paf', 'val/heat'} (floats) and
+        'paf_stages', 'heat_stages' (six floats each).  Honours `precision=`."""
+        imgs, poses, masks = self._check_validation_args(imgs, poses_per_image, ignore_masks)
+        if self.model is not None:
+            raise RuntimeError('validation_loss runs the built-in network: not available with a model= callable')
+        if self.engine.weights_missing():
+            raise RuntimeError('PoseDetector has no weights: pass weights_file=, weights= or model=')
+        h, w = imgs[0].shape[:2]
+        self._grow(1, h, w)
+        mb = self._cap[0]
+        total, paf, heat = 0.0, np.zeros(6), np.zeros(6)
+        for i in range(0, len(imgs), mb):
+            n = len(imgs[i:i + mb])
+            self.engine.loss_set_poses(poses[i:i + n], h, w, None if masks is None else np.stack(masks[i:i + n]),
+                                       params['heatmap_sigma'], params['paf_sigma'])
+            t, p, q = self.engine.validate_batch(np.stack(imgs[i:i + n]))
+            total += n * t
+            paf += n * p
+            heat += n * q
+        total, paf, heat = total / len(imgs), paf / len(imgs), heat / len(imgs)
+        return {'val/loss': float(total), 'val/paf': float(paf.sum()), 'val/heat': float(heat.sum()),
+                'paf_stages': [float(v) for v in paf], 'heat_stages': [float(v) for v in heat]}
+
     def detect_maps(self, paf, heat, map_h, map_w, img_len=None, scale_xy=None):
         """Post-process only (pose_detector.py:501-517) on network outputs paf (B,38,h,w), heat (B,19,h,w)."""
         self.engine.set_maps(paf, heat)

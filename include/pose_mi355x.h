@@ -337,6 +337,61 @@ int pmx_get_precise_image_maps(pmx_ctx* ctx, int image, float* paf, float* heat,
  * the number of distinct sizes seen) */
 int pmx_precise_images_table_bytes(pmx_ctx* ctx, size_t* bytes);
 
+/* ---- validation loss: Validator.evaluate (train_coco_pose_estimation.py:129-159) without the data loader ------------------------
+ * The forward under no_backprop_mode (:147-150) followed by compute_loss (:41-73): per stage the mean squared error of the PAF and of the
+ * heat-map output against the label maps, ignored pixels excluded by overwriting the target with the output (:62-63).  Forward only: no
+ * backward pass, no optimiser, no augmentation; the 16 x 16 dilation of the ignore mask (coco_data_loader.py:340) and the image / mask
+ * resizes stay with the caller.  posenet contexts (facenet / handnet: PMX_ERR_STATE), uniform batches, fp32 and f16 mode.  With the hook off
+ * (the default) no call of this header launches, allocates or synchronises anything more than before.
+ *
+ * Targets.  pmx_loss_set_poses evaluates generate_heatmaps + generate_pafs (coco_data_loader.py:208-268) on the device in float64, product
+ * by product as NumPy does (no fused multiply-add), and casts to float32 (:229, :268): heat of a joint type = max over the people with v > 0
+ * of exp(-0.5 * d2 / heat_sigma**2), channel 18 = 1 - the max over all joints; PAF of a limb = the sum of the unit vectors of the people
+ * whose band (0 <= hor <= dist, |ver| <= paf_width, `ver` through the reference's rotation by pi / 2 with its cos = 6.123233995736766e-17,
+ * :238-246) covers the pixel, divided by their number (:266); a person whose joint has v <= 0 (:260) or whose joints coincide (:233) is
+ * skipped.  The labels are evaluated only at the four corner pixels each map pixel of h/8 x w/8 needs and combined as F.resize_images does
+ * (:57-58: float64 weight products cast to float32, four float32 products summed left to right); the batch x 57 x h x w maps never exist.
+ *   poses        sum(n_people) x 18 x 3 float64 rows (x, y, v) in network-input pixels, image after image
+ *   n_people     batch ints (>= 0)
+ *   ignore_mask  batch x h x w uint8, non-zero = ignored, or NULL (nothing ignored); resized with the same float32 weighted sum, a map
+ *                pixel is ignored when that sum is > 0 (:59-60)
+ *   heat_sigma   params['heatmap_sigma'] (entity.py: 7), paf_width: params['paf_sigma'] (8)
+ * Asynchronous; the host arrays are read before the call returns.
+ * pmx_loss_set_targets installs label maps the caller made: float32 NCHW host maps (batch x 38 / 19 x th x tw) either at th x tw = h x w
+ * (resized on the device as :57-60 do) or already at h/8 x w/8 (taken as they are, :56); ignore_mask: batch x th x tw uint8 or NULL.
+ * Errors of both (checked before anything is enqueued; the context stays usable): PMX_ERR_INVALID for null arguments, n_people < 0, a
+ * non-finite x or y of a visible joint, heat_sigma <= 0, paf_width < 0, h or w no multiple of 8, th x tw neither of the two sizes;
+ * PMX_ERR_CAPACITY for batch > max_batch or h * w > max_h * max_w. */
+int pmx_loss_set_poses(pmx_ctx* ctx, const double* poses, const int* n_people, int batch, int h, int w,
+                       const uint8_t* ignore_mask, double heat_sigma, double paf_width);
+int pmx_loss_set_targets(pmx_ctx* ctx, const float* paf_t, const float* heat_t, const uint8_t* ignore_mask,
+                         int batch, int th, int tw, int h, int w);
+/* on != 0: every uniform forward (pmx_forward_u8 / _f32 / _u8_resized, pmx_detect_batch) enqueues, right after the last launch of each
+ * stage, one launch that reads the stage's output where the network left it and accumulates, per branch, the float64 sum of
+ * ((double)d * d) with d = y - t in float32 (F.mean_squared_error's difference), ignored pixels contributing 0 -- a wave-64 reduction, then
+ * LDS across the block's waves, one partial per block and branch in a fixed slot -- and after the last stage one launch that adds the
+ * partials in slot order and divides by batch * 38 * h/8 * w/8 and batch * 19 * h/8 * w/8 (the mean over ALL elements, :65-66).  No
+ * floating-point atomics: the same bits on every run.  No synchronisation and no host copy between the stages; the maps of a hooked
+ * forward are bit-identical to an unhooked one (the hook only reads).  With the hook on, PMX_ERR_STATE (before anything is enqueued) for
+ * a forward without targets or with targets of another batch, h or w, and for every mixed-size or precise entry (pmx_forward_u8_images,
+ * pmx_detect_images, pmx_precise_*, pmx_detect_precise_images). */
+int pmx_loss_enable(pmx_ctx* ctx, int on);
+/* the losses of the last hooked forward: paf_loss6[s], heat_loss6[s] = paf_loss_log[s], heatmap_loss_log[s] of compute_loss (:70-71) for
+ * stage s + 1; n_stages = 6, or option "stop_stage" (the later entries are 0).  PMX_ERR_STATE before any hooked forward.  Synchronises. */
+int pmx_loss_get(pmx_ctx* ctx, double* paf_loss6, double* heat_loss6, int* n_stages);
+/* one stage of compute_loss for the CURRENT maps (a forward's last stage, or pmx_set_maps) against the targets (PMX_ERR_STATE unless both
+ * exist with the same batch and map size).  Synchronises. */
+int pmx_loss_current_maps(pmx_ctx* ctx, double* paf_loss, double* heat_loss);
+/* Validator.evaluate for one batch (:146-157): pmx_forward_u8 with the hook on (whatever pmx_loss_enable set, which it leaves unchanged) +
+ * pmx_loss_get.  out13 = total (`val/loss`: the stages' paf + heat added in stage order), paf[6], heat[6].  Synchronises. */
+int pmx_validate_batch(pmx_ctx* ctx, const uint8_t* bgr_nhwc, int batch, int h, int w, int on_device, double* out13);
+/* the public label generator / parity accessor: generate_pafs (38 x h x w) and generate_heatmaps (19 x h x w) of image `image` of the
+ * poses of the last pmx_loss_set_poses, float32 at full resolution (h x w as set there).  Either pointer may be NULL.  Synchronises. */
+int pmx_get_labels(pmx_ctx* ctx, int image, float* paf, float* heat, int h, int w);
+/* parity accessor: the current targets as NCHW float32 (batch x 38 | 19 x h/8 x w/8) and the resized ignore mask (batch x h/8 x w/8, 0 | 1);
+ * any pointer may be NULL.  Synchronises. */
+int pmx_get_loss_targets(pmx_ctx* ctx, float* paf_t, float* heat_t, uint8_t* mask);
+
 /* results.  pmx_results_layout synchronises, grows the capacities and re-runs the post-process if an image overflowed them,
  * and returns the layout of the (now final) records; pmx_get_results does the same and copies `batch` records to `out`
  * (out_bytes >= batch * bytes_per_record, else PMX_ERR_CAPACITY). */
