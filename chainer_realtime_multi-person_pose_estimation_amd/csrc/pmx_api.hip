@@ -1304,44 +1304,18 @@ extern "C" int pmx_set_gaussian(pmx_ctx* c, const double* taps, int radius)
     return PMX_OK;
 }
 
-// np.linspace(0, in-1, num=out) grid + the corner indices / weights of Chainer's ResizeImages (see oracle)
-void pmx_make_upsample_grid(int in, int out, std::vector<int>& i0, std::vector<int>& i1, std::vector<double>& lo, std::vector<double>& hi)
-{
-    i0.resize(out); i1.resize(out); lo.resize(out); hi.resize(out);
-    const double start = 0.0, stop = (double)(in - 1);
-    const int div = out - 1;
-    const double delta = stop - start;
-    const double step = div > 0 ? delta / (double)div : 0.0;
-    for (int k = 0; k < out; ++k) {
-        double u;
-        if (div > 0) {
-            if (step == 0.0) u = ((double)k / (double)div) * delta + start;
-            else u = (double)k * step + start;
-            if (k == out - 1 && out > 1) u = stop;
-        } else {
-            u = start;     // num == 1 -> [start]
-        }
-        const int f = (int)floor(u);
-        const double wl = (double)(f + 1) - u, wh = u - (double)f;
-        i0[k] = f < 0 ? 0 : (f > in - 1 ? in - 1 : f);
-        i1[k] = f + 1 > in - 1 ? in - 1 : (f + 1 < 0 ? 0 : f + 1);
-        lo[k] = wl; hi[k] = wh;
-    }
-}
-
-void pmx_pp_gauss(const pmx_ctx* c, std::vector<double>& g, PPTables& t)
+void pmx_pp_gauss(const pmx_ctx* c, void* host, void* dev, PPTables& t)
 {
     if (c->opt_gpu_branch_peaks) {
         // create_gaussian_kernel(sigma, ksize = 17) (pose_detector.py:38-44): 1/(2 pi sigma^2) exp(-d^2 / 2 sigma^2), NOT
         // normalised to sum 1, applied as a 17x17 zero-padded convolution (:112-113); separable factor per axis
         const int r = 8;
-        g.assign(2 * r + 1, 0.0);
+        double g[2 * r + 1];
         const double s2 = PMX_GAUSS_SIGMA * PMX_GAUSS_SIGMA;
         for (int i = -r; i <= r; ++i) g[i + r] = sqrt(1.0 / (s2 * 2.0 * M_PI)) * exp(-0.5 * (double)(i * i) / s2);
-        t.radius = r; t.border_zero = 1; t.nms_ge = 1;
+        pp_taps_build(g, 2 * r + 1, 1, 1, host, dev, t);
     } else {
-        g = c->gauss;
-        t.radius = ((int)c->gauss.size() - 1) / 2; t.border_zero = 0; t.nms_ge = 0;
+        pp_taps_build(c->gauss.data(), (int)c->gauss.size(), 0, 0, host, dev, t);
     }
 }
 
@@ -1352,47 +1326,43 @@ int pmx_ensure_smoothed(pmx_ctx* c, size_t floats)
     return rc;
 }
 
-// The table set of the context for one (network map, up-sampled map) size pair.  A failure anywhere in here (the one allocation of a larger
-// set, an upload) leaves the context consistent: c->tab points into what c->tab_store holds, or nowhere, and tab_in_h stays invalid, so
-// the next call builds the set again
+// The table set of the context for one (network map, up-sampled map) size pair: [grid | taps] (pp_tables.h), built on the host, one upload.
+// A failure anywhere in here (the one allocation of a larger set, the upload) leaves the context consistent: c->tab points into what
+// c->tab_store holds, or nowhere, and tab_in_h stays invalid, so the next call builds the set again
 int pmx_ensure_tables(pmx_ctx* c, int in_h, int in_w, int out_h, int out_w, int flip_x)
 {
     if (c->tab_in_h == in_h && c->tab_in_w == in_w && c->tab_out_h == out_h && c->tab_out_w == out_w && c->tab_flip == flip_x) return PMX_OK;
-    // one allocation for the set: [gauss | xlo | xhi | ylo | yhi] doubles, then [xi0 | xi1 | yi0 | yi1] ints, the axis arrays `cap` long
-    const size_t cap = out_h > out_w ? out_h : out_w, ng = 2 * PMX_GAUSS_MAX_RADIUS + 1;
-    const size_t bytes = (ng + 4 * cap) * sizeof(double) + 4 * cap * sizeof(int);
-    PPTables& t = c->tab;
+    const size_t grid = pp_grid_bytes(out_h, out_w), bytes = grid + pp_taps_bytes();
     c->tab_in_h = -1;       // until the upload below is complete
-    if (bytes > c->tab_store.capacity()) {
-        if (int rc = c->tab_store.ensure(bytes, c->stream)) {
-            if (!c->tab_store) t = PPTables{};      // (the old set went before the new allocation failed)
-            return rc;
-        }
-        t.gauss = reinterpret_cast<double*>(c->tab_store.get());
-        t.xlo = t.gauss + ng; t.xhi = t.xlo + cap; t.ylo = t.xhi + cap; t.yhi = t.ylo + cap;
-        t.xi0 = reinterpret_cast<int*>(t.yhi + cap); t.xi1 = t.xi0 + cap; t.yi0 = t.xi1 + cap; t.yi1 = t.yi0 + cap;
+    if (int rc = c->tab_store.ensure(bytes, c->stream)) {
+        if (!c->tab_store) c->tab = PPTables{};      // (the old set went before the new allocation failed)
+        return rc;
     }
-    std::vector<int> i0, i1; std::vector<double> lo, hi;
+    std::vector<double> host(bytes / sizeof(double));
+    pp_grid_build(in_h, in_w, out_h, out_w, flip_x, host.data(), c->tab_store.get(), c->tab);
+    pmx_pp_gauss(c, host.data() + grid / sizeof(double), c->tab_store + grid, c->tab);
     PMX_HIP(hipStreamSynchronize(c->stream));
-    pmx_make_upsample_grid(in_w, out_w, i0, i1, lo, hi);
-    if (flip_x) {       // column x of the mirrored map = column out_w - 1 - x of the resized one: same samples, same arithmetic
-        std::reverse(i0.begin(), i0.end()); std::reverse(i1.begin(), i1.end());
-        std::reverse(lo.begin(), lo.end()); std::reverse(hi.begin(), hi.end());
-    }
-    PMX_HIP(hipMemcpy(t.xi0, i0.data(), out_w * sizeof(int), hipMemcpyHostToDevice));
-    PMX_HIP(hipMemcpy(t.xi1, i1.data(), out_w * sizeof(int), hipMemcpyHostToDevice));
-    PMX_HIP(hipMemcpy(t.xlo, lo.data(), out_w * sizeof(double), hipMemcpyHostToDevice));
-    PMX_HIP(hipMemcpy(t.xhi, hi.data(), out_w * sizeof(double), hipMemcpyHostToDevice));
-    pmx_make_upsample_grid(in_h, out_h, i0, i1, lo, hi);
-    PMX_HIP(hipMemcpy(t.yi0, i0.data(), out_h * sizeof(int), hipMemcpyHostToDevice));
-    PMX_HIP(hipMemcpy(t.yi1, i1.data(), out_h * sizeof(int), hipMemcpyHostToDevice));
-    PMX_HIP(hipMemcpy(t.ylo, lo.data(), out_h * sizeof(double), hipMemcpyHostToDevice));
-    PMX_HIP(hipMemcpy(t.yhi, hi.data(), out_h * sizeof(double), hipMemcpyHostToDevice));
-    std::vector<double> g;
-    pmx_pp_gauss(c, g, t);
-    PMX_HIP(hipMemcpy(t.gauss, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice));
+    PMX_HIP(hipMemcpy(c->tab_store, host.data(), bytes, hipMemcpyHostToDevice));
     c->tab_in_h = in_h; c->tab_in_w = in_w; c->tab_out_h = out_h; c->tab_out_w = out_w; c->tab_flip = flip_x;
     return PMX_OK;
+}
+
+PPMaps pmx_current_maps(const pmx_ctx* c)
+{
+    const long long fhw = (long long)c->cur_fh * c->cur_fw;
+    const bool paf = c->kind == NET_POSE;
+    PPMaps m;
+    if (c->maps_external) {          // NCHW copies installed by pmx_set_maps
+        m.heat = c->ext_heat; m.paf = paf ? c->ext_paf.get() : nullptr;
+        m.sx = 1; m.sy = c->cur_fw; m.sc = fhw;
+        m.sbh = c->n_heat * fhw; m.sbp = paf ? PMX_N_PAF * fhw : 0;
+    } else {                         // channel slices of the NHWC cat buffer written by the last stage
+        m.heat = c->cat + c->cat_heat; m.paf = paf ? c->cat + PMX_CAT_PAF : nullptr;
+        m.sc = 1; m.sx = c->cat_c; m.sy = (long long)c->cur_fw * c->cat_c;
+        m.sbh = fhw * c->cat_c; m.sbp = paf ? m.sbh : 0;
+    }
+    m.fh = c->cur_fh; m.fw = c->cur_fw;
+    return m;
 }
 
 extern "C" int pmx_postprocess(pmx_ctx* c, int B, int map_h, int map_w, double img_len, const double* scale_xy)
@@ -1406,18 +1376,7 @@ extern "C" int pmx_postprocess(pmx_ctx* c, int B, int map_h, int map_w, double i
     PMX_DEV(c);
     int rc;
     if ((rc = pmx_ensure_tables(c, c->cur_fh, c->cur_fw, map_h, map_w))) return rc;
-    const long long fhw = (long long)c->cur_fh * c->cur_fw;
-    PPMaps m;
-    if (c->maps_external) {          // NCHW copies installed by pmx_set_maps
-        m.heat = c->ext_heat; m.paf = c->ext_paf;
-        m.sx = 1; m.sy = c->cur_fw; m.sc = fhw;
-        m.sbh = PMX_N_HEAT * fhw; m.sbp = PMX_N_PAF * fhw;
-    } else {                         // channel slices of the NHWC cat buffer written by the last stage
-        m.heat = c->cat + PMX_CAT_HEAT; m.paf = c->cat + PMX_CAT_PAF;
-        m.sc = 1; m.sx = PMX_CAT_C; m.sy = (long long)c->cur_fw * PMX_CAT_C;
-        m.sbh = m.sbp = fhw * PMX_CAT_C;
-    }
-    m.fh = c->cur_fh; m.fw = c->cur_fw;
+    const PPMaps m = pmx_current_maps(c);
     if (c->opt_keep_smoothed) {
         if ((rc = pmx_ensure_smoothed(c, (size_t)B * PMX_N_JOINTS * map_h * map_w))) return rc;
     }

@@ -26,7 +26,6 @@
 #include "pmx_ctx.h"
 #include "pp_smooth.h"
 
-#include <algorithm>
 #include <climits>
 #include <cstring>
 
@@ -168,13 +167,14 @@ __global__ __launch_bounds__(256) void kp_merge_kernel(const ArgMax* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host
-// key-point tables of the crops of a call: where stage_keypoints put them (byte offsets into the staging) and the KpCrop records, whose
-// table pointers stage_upload fills in
+// key-point tables of the crops of a call: where stage_keypoints reserved them (byte offsets into the staging) and the KpCrop records,
+// whose table sets stage_upload builds
 struct KpStage {
-    size_t crops_off = 0, tiles_off = 0, ends_off = 0, gauss_off = 0;
-    int n_tiles = 0;
+    size_t crops_off = 0, tiles_off = 0, ends_off = 0, taps_off = 0;
+    int n_tiles = 0, fh = 0, fw = 0;    // tiles of all crops; the maps' size
+    const int* hwf = nullptr;           // the call's (h, w, flip) rows
     std::vector<int> crop_tile0;        // first tile per crop, n_tiles at the end
-    std::vector<size_t> grid_off;       // per crop: xi0, xi1, xlo, xhi, yi0, yi1, ylo, yhi
+    std::vector<size_t> grid_off;       // per crop: its grid block (pp_tables.h)
     std::vector<KpCrop> crops;
 };
 
@@ -190,8 +190,8 @@ struct Stage {
     size_t reserve(size_t bytes) { const size_t off = (h.size() + 15) / 16 * 16; h.resize(off + bytes); return off; }
 };
 
-// one H2D copy of the staging; the device copy is valid for the kernels enqueued after it on the context's stream.  The KpCrop records of
-// `ks` are written here, where the device copy's address is known: their tables are device pointers into it.
+// one H2D copy of the staging; the device copy is valid for the kernels enqueued after it on the context's stream.  The table sets of
+// `ks` (one taps block, a grid block per crop) are built here, where the device copy's address is known: they hold device pointers into it.
 int stage_upload(pmx_ctx* c, Stage& st, KpStage* ks = nullptr)
 {
     const size_t bytes = st.h.size();
@@ -201,17 +201,15 @@ int stage_upload(pmx_ctx* c, Stage& st, KpStage* ks = nullptr)
     if (bytes > c->bx_host.capacity() && (rc = c->bx_host.alloc(bytes))) return rc;
     if ((rc = c->bx_dev.ensure(bytes, c->stream))) return rc;      // (queued work may still read the old buffer)
     if (ks) {
-        char* dev = c->bx_dev.get();
+        char *host = st.h.data(), *dev = c->bx_dev.get();
+        PPTables taps{};
+        pmx_pp_gauss(c, host + ks->taps_off, dev + ks->taps_off, taps);
         for (size_t k = 0; k < ks->crops.size(); ++k) {
-            const size_t* o = &ks->grid_off[8 * k];
-            PPTables& t = ks->crops[k].tab;
-            t.xi0 = reinterpret_cast<int*>(dev + o[0]); t.xi1 = reinterpret_cast<int*>(dev + o[1]);
-            t.xlo = reinterpret_cast<double*>(dev + o[2]); t.xhi = reinterpret_cast<double*>(dev + o[3]);
-            t.yi0 = reinterpret_cast<int*>(dev + o[4]); t.yi1 = reinterpret_cast<int*>(dev + o[5]);
-            t.ylo = reinterpret_cast<double*>(dev + o[6]); t.yhi = reinterpret_cast<double*>(dev + o[7]);
-            t.gauss = reinterpret_cast<double*>(dev + ks->gauss_off);
+            KpCrop& kc = ks->crops[k];
+            kc.tab = taps;
+            pp_grid_build(ks->fh, ks->fw, kc.h, kc.w, ks->hwf[3 * k + 2], host + ks->grid_off[k], dev + ks->grid_off[k], kc.tab);
         }
-        memcpy(st.h.data() + ks->crops_off, ks->crops.data(), ks->crops.size() * sizeof(KpCrop));
+        memcpy(host + ks->crops_off, ks->crops.data(), ks->crops.size() * sizeof(KpCrop));
     }
     if (!c->bx_copied) PMX_HIP(hipEventCreateWithFlags(&c->bx_copied, hipEventDisableTiming));
     memcpy(c->bx_host, st.h.data(), bytes);
@@ -275,33 +273,22 @@ void stage_boxes(Stage& st, const int* boxes6, int n, int dh, int dw, size_t* de
     *tab_off = st.put(tabs.data(), tabs.size() * sizeof(int));
 }
 
-// key-point tables of n crops (h, w, flip) on maps of fh x fw: the up-sampling grids, the flat tile list and the per-crop tile ends are
-// staged, room for the KpCrop[n] records is reserved
-void stage_keypoints(pmx_ctx* c, Stage& st, const int* hwf, int n, int fh, int fw, KpStage* ks)
+// key-point tables of n crops (h, w, flip) on maps of fh x fw: the flat tile list and the per-crop tile ends are staged, room for the taps,
+// a grid per crop and the KpCrop[n] records is reserved
+void stage_keypoints(Stage& st, const int* hwf, int n, int fh, int fw, KpStage* ks)
 {
-    std::vector<int> i0, i1; std::vector<double> lo, hi;
     std::vector<int2> tiles;
     std::vector<int> ends(n);
-    ks->gauss_off = st.put(c->gauss.data(), c->gauss.size() * sizeof(double));
-    ks->grid_off.resize(8 * (size_t)n);
+    ks->hwf = hwf; ks->fh = fh; ks->fw = fw;
+    ks->taps_off = st.reserve(pp_taps_bytes());
+    ks->grid_off.resize(n);
     ks->crops.resize(n);
     ks->crop_tile0.resize(n + 1);
     for (int k = 0; k < n; ++k) {
-        const int h = hwf[3 * k], w = hwf[3 * k + 1], flip = hwf[3 * k + 2];
-        pmx_make_upsample_grid(fw, w, i0, i1, lo, hi);
-        if (flip) {       // column x of the mirrored map = column w - 1 - x of the resized one (pmx_ensure_tables)
-            std::reverse(i0.begin(), i0.end()); std::reverse(i1.begin(), i1.end());
-            std::reverse(lo.begin(), lo.end()); std::reverse(hi.begin(), hi.end());
-        }
-        size_t* o = &ks->grid_off[8 * (size_t)k];
-        o[0] = st.put(i0.data(), w * sizeof(int)); o[1] = st.put(i1.data(), w * sizeof(int));
-        o[2] = st.put(lo.data(), w * sizeof(double)); o[3] = st.put(hi.data(), w * sizeof(double));
-        pmx_make_upsample_grid(fh, h, i0, i1, lo, hi);
-        o[4] = st.put(i0.data(), h * sizeof(int)); o[5] = st.put(i1.data(), h * sizeof(int));
-        o[6] = st.put(lo.data(), h * sizeof(double)); o[7] = st.put(hi.data(), h * sizeof(double));
+        const int h = hwf[3 * k], w = hwf[3 * k + 1];
+        ks->grid_off[k] = st.reserve(pp_grid_bytes(h, w));
         const int tx = (w + PK_TS - 1) / PK_TS, ty = (h + PK_TS - 1) / PK_TS;
         KpCrop& kc = ks->crops[k];
-        kc.tab.radius = ((int)c->gauss.size() - 1) / 2; kc.tab.border_zero = 0; kc.tab.nms_ge = 0;
         kc.h = h; kc.w = w; kc.tiles_x = tx; kc.tile0 = ks->crop_tile0[k] = (int)tiles.size();
         for (int t = 0; t < tx * ty; ++t) tiles.push_back(make_int2(k, t));
         ends[k] = (int)tiles.size();
@@ -310,21 +297,6 @@ void stage_keypoints(pmx_ctx* c, Stage& st, const int* hwf, int n, int fh, int f
     ks->crops_off = st.reserve(n * sizeof(KpCrop));
     ks->tiles_off = st.put(tiles.data(), tiles.size() * sizeof(int2));
     ks->ends_off = st.put(ends.data(), ends.size() * sizeof(int));
-}
-
-// the current network maps (uniform batch) as the post-process sees them (pmx_keypoints)
-PPMaps current_maps(pmx_ctx* c)
-{
-    const long long fhw = (long long)c->cur_fh * c->cur_fw;
-    PPMaps m;
-    if (c->maps_external) {
-        m.heat = c->ext_heat; m.paf = nullptr; m.sx = 1; m.sy = c->cur_fw; m.sc = fhw; m.sbh = c->n_heat * fhw; m.sbp = 0;
-    } else {
-        m.heat = c->cat + c->cat_heat; m.paf = nullptr; m.sc = 1; m.sx = c->cat_c; m.sy = (long long)c->cur_fw * c->cat_c;
-        m.sbh = fhw * c->cat_c; m.sbp = 0;
-    }
-    m.fh = c->cur_fh; m.fw = c->cur_fw;
-    return m;
 }
 
 bool kp_fast(pmx_ctx* c)
@@ -336,7 +308,7 @@ bool kp_fast(pmx_ctx* c)
 int kp_enqueue_chunk(pmx_ctx* c, const KpStage& ks, const int* hwf, int k0, int B, double thresh)
 {
     const int n_ch = c->n_heat - 1;
-    const PPMaps m = current_maps(c);
+    const PPMaps m = pmx_current_maps(c);
     int rc;
     if (kp_fast(c)) {
         const int t0 = ks.crop_tile0[k0], t1 = ks.crop_tile0[k0 + B];
@@ -368,7 +340,7 @@ int kp_prepare(pmx_ctx* c, Stage& st, const int* hwf, int n, int fh, int fw, KpS
         PMX_CHECK(hwf[3 * k] >= 1 && hwf[3 * k + 1] >= 1 && (long long)hwf[3 * k] * hwf[3 * k + 1] < (1ll << 31) &&
                   (hwf[3 * k + 2] == 0 || hwf[3 * k + 2] == 1), PMX_ERR_INVALID, "key points: crop %d has a bad (h, w, flip) = (%d, %d, %d)",
                   k, hwf[3 * k], hwf[3 * k + 1], hwf[3 * k + 2]);
-    stage_keypoints(c, st, hwf, n, fh, fw, ks);
+    stage_keypoints(st, hwf, n, fh, fw, ks);
     const size_t nkp = (size_t)n * n_ch * 4;
     if ((rc = c->d_kp.ensure(nkp, c->stream))) return rc;
     if (kp_fast(c) && (rc = c->bx_rec.ensure((size_t)ks->n_tiles * n_ch * sizeof(ArgMax), c->stream))) return rc;

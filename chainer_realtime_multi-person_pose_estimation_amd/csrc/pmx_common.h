@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/pose_mi355x.h"
+#include "pp_tables.h"
 
 // ---- constants of the inference path (reference entity.py:71-105); the Python copy lives in entity.py --
 #define PMX_HEATMAP_PEAK_THRESH 0.05f       // entity.py:79 (compared in float32, see pose_detector.py:97)
@@ -18,7 +19,6 @@
 #define PMX_N_SUBSET_LIMBS_THRESH 3.0       // entity.py:83
 #define PMX_SUBSET_SCORE_THRESH 0.2         // entity.py:84
 #define PMX_GAUSS_SIGMA 2.5                 // entity.py:75
-#define PMX_GAUSS_MAX_RADIUS 16
 
 // limb table (entity.py:85-105): joint indices (from, to) of limb i; PAF channels (2i, 2i+1) = (x, y)
 static const int PMX_LIMBS[PMX_N_LIMBS][2] = {
@@ -240,15 +240,7 @@ int launch_sum_parts_f32(float* out, const float* const* parts, int nparts, long
 int launch_nchw_to_nhwc(const float* src, float* dst, int B, int C, int H, int W, int ldc, int coff, hipStream_t s);
 int launch_nhwc_to_nchw(const float* src, float* dst, int B, int C, int H, int W, int lda, int coff, hipStream_t s);
 
-// ---- post-process interface (postproc.hip) -------------------------------------------------------
-struct PPTables {            // device pointers, per context, sized for the largest map
-    int* xi0; int* xi1; double* xlo; double* xhi;   // per output column
-    int* yi0; int* yi1; double* ylo; double* yhi;   // per output row
-    double* gauss;                                   // 2r+1 taps
-    int radius;
-    int border_zero;   // 0: scipy 'reflect' (CPU branch, golden); 1: zero padding (reference GPU branch, :112-113)
-    int nms_ge;        // 0: strict '>' against the 4 neighbours (:98-101); 1: '>=' (GPU branch, :123-126)
-};
+// ---- post-process interface (postproc.hip); PPTables, the table set of a launch: pp_tables.h --------
 struct PPMaps {              // where the low-resolution network outputs live
     const float* heat; const float* paf;
     long long sbh, sbp;          // batch strides (floats) of the heat / PAF maps

@@ -123,7 +123,7 @@ struct pmx_ctx {
     int seg_tiles[PMX_SEG_TABLES] = {};                   // tiles per launch, per table
     long long seg_pix[4] = {};                            // pixels of all segments, per level
     std::vector<PPCall> pp_calls;                         // non-empty: the post-process of the current results ran per segment
-    // up-sampling tables per (in_h, in_w, out_h, out_w) of the per-segment calls: the kernel-argument struct and the one allocation it points into
+    // table sets per (in_h, in_w, out_h, out_w) of the per-segment calls: the kernel-argument struct and the one allocation [grid | taps] it points into
     std::map<std::tuple<int, int, int, int>, std::pair<PPTables, DevBuf<char>>> tab_cache;
     DevBuf<uint8_t> mi_src;                               // pmx_detect_images: original-size images awaiting the device resize
     DevBuf<int> mi_tab;                                   // ... and their resize tables
@@ -174,7 +174,7 @@ struct pmx_ctx {
     DevBuf<float> ext_paf, ext_heat;                 // NCHW copies installed by pmx_set_maps
     // post-process
     PPTables tab{};                  // kernel arguments: raw pointers into tab_store (pmx_ensure_tables)
-    DevBuf<char> tab_store;
+    DevBuf<char> tab_store;          // [grid of (tab_out_h, tab_out_w) | taps] (pp_tables.h)
     int tab_in_h = -1, tab_in_w = -1, tab_out_h = -1, tab_out_w = -1;
     std::vector<double> gauss;
     PPBuffers pp{};                  // kernel arguments: raw pointers into pp_store (pp_alloc) and, pp.smoothed, to `smoothed`
@@ -247,7 +247,8 @@ struct pmx_ctx {
     DevBuf<uint8_t> ls_mask, ls_mask_in;
     DevBuf<double> ls_poses, ls_part, ls_out;
     DevBuf<int> ls_off;                                   // first person of image b (batch + 1 entries)
-    DevBuf<char> ls_grid;                                 // [xlo | xhi | ylo | yhi] doubles, [xi0 | xi1 | yi0 | yi1] ints
+    DevBuf<char> ls_grid;                                 // the grid block of (h, w) -> (h/8, w/8) (pp_tables.h), ls_tab its pointers
+    PPTables ls_tab{};
     std::vector<double> ls_h_poses; std::vector<int> ls_h_off;
     std::vector<uint8_t> ls_h_mask;                       // the caller's ignore mask, copied before the call returns (the upload reads this copy)
     double ls_sigma = 0, ls_width = 0;
@@ -273,12 +274,14 @@ int pmx_ensure_tables(pmx_ctx* c, int in_h, int in_w, int out_h, int out_w, int 
 PPBuffers pmx_pp_view(const PPBuffers& p, int base);         // the post-process buffers of the images [base, ...) (every per-image array offset)
 void pmx_make_resize_table(int dst, int src, int* tab);      // OpenCV INTER_LINEAR uint8 table of one axis: [idx0 | idx1 | coef0 | coef1] x dst
 int pmx_check_weights(pmx_ctx* c);                          // PMX_ERR_WEIGHTS unless every layer has weights
-// corner-aligned up-sampling grid of one axis (F.resize_images, np.linspace semantics): the tables pmx_ensure_tables uploads
-void pmx_make_upsample_grid(int in, int out, std::vector<int>& i0, std::vector<int>& i1, std::vector<double>& lo, std::vector<double>& hi);
 int pmx_prof_begin(pmx_ctx* c, const char* name, double bytes);   // per-launch profiler (option 1 only) around one launch
 int pmx_prof_end(pmx_ctx* c);
-// the Gaussian taps and border / NMS flags of the post-process tables (pmx_ensure_tables): taps -> g, the flags -> t
-void pmx_pp_gauss(const pmx_ctx* c, std::vector<double>& g, PPTables& t);
+// the taps block of the context's post-process tables (pp_tables.h::pp_taps_build) -> host; t.gauss -> dev, and t's radius, border and
+// NMS flags: pmx_set_gaussian's taps with the reflected border and the strict NMS, or the reference's GPU peak branch
+void pmx_pp_gauss(const pmx_ctx* c, void* host, void* dev, PPTables& t);
+// the current network output of a uniform batch as the post-process reads it: the NCHW copies of pmx_set_maps / pmx_precise_finish or the
+// NHWC cat slices of the last stage; the PAF fields only on a posenet context
+PPMaps pmx_current_maps(const pmx_ctx* c);
 // pmx_precise.hip: the cubic table of one axis for (src -> dst), 8 * dst ints [4 x dst indices | 4 x dst coefficients: float32 bits, or
 // OpenCV's 11-bit fixed point for the uint8 resize when `fixed`]
 void pmx_cubic_table(int src, int dst, bool fixed, int* out);

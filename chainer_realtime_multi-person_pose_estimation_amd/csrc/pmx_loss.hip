@@ -215,35 +215,23 @@ __global__ void loss_final_kernel(const double* part, double* out, int slot0, in
     out[slot * 2 + br] = s;
 }
 
-LossGrid grid_view(const pmx_ctx* c, int fh, int fw)
+LossGrid grid_view(const pmx_ctx* c)
 {
-    LossGrid g;
-    const double* d = reinterpret_cast<const double*>(c->ls_grid.get());
-    g.xlo = d; g.xhi = g.xlo + fw; g.ylo = g.xhi + fw; g.yhi = g.ylo + fh;
-    const int* i = reinterpret_cast<const int*>(g.yhi + fh);
-    g.xi0 = i; g.xi1 = g.xi0 + fw; g.yi0 = g.xi1 + fw; g.yi1 = g.yi0 + fh;
-    return g;
+    const PPTables& t = c->ls_tab;
+    return LossGrid{t.xlo, t.xhi, t.ylo, t.yhi, t.xi0, t.xi1, t.yi0, t.yi1};
 }
 
-// the grid of (h, w) -> (h/8, w/8) on the device (uploaded when the size changes: a setup step, synchronises then)
+// the grid block (pp_tables.h) of (h, w) -> (h/8, w/8) on the device (uploaded when the size changes: a setup step, synchronises then)
 int ensure_grid(pmx_ctx* c, int h, int w)
 {
     if (c->ls_grid_h == h && c->ls_grid_w == w) return PMX_OK;
     const int fh = h / 8, fw = w / 8;
-    const size_t nd = 2 * (size_t)(fw + fh), bytes = nd * sizeof(double) + nd * sizeof(int);
-    std::vector<char> host(bytes);
-    double* d = reinterpret_cast<double*>(host.data());
-    int* i = reinterpret_cast<int*>(d + nd);
-    std::vector<int> i0, i1; std::vector<double> lo, hi;
-    pmx_make_upsample_grid(w, fw, i0, i1, lo, hi);
-    memcpy(d, lo.data(), fw * sizeof(double)); memcpy(d + fw, hi.data(), fw * sizeof(double));
-    memcpy(i, i0.data(), fw * sizeof(int)); memcpy(i + fw, i1.data(), fw * sizeof(int));
-    pmx_make_upsample_grid(h, fh, i0, i1, lo, hi);
-    memcpy(d + 2 * fw, lo.data(), fh * sizeof(double)); memcpy(d + 2 * fw + fh, hi.data(), fh * sizeof(double));
-    memcpy(i + 2 * fw, i0.data(), fh * sizeof(int)); memcpy(i + 2 * fw + fh, i1.data(), fh * sizeof(int));
+    const size_t bytes = pp_grid_bytes(fh, fw);
     c->ls_grid_h = 0;
     PMX_HIP(hipStreamSynchronize(c->stream));          // a queued label launch may still read the old grid
     if (bytes > c->ls_grid.capacity()) if (int rc = c->ls_grid.alloc(bytes)) return rc;
+    std::vector<double> host(bytes / sizeof(double));
+    pp_grid_build(h, w, fh, fw, 0, host.data(), c->ls_grid.get(), c->ls_tab);
     PMX_HIP(hipMemcpy(c->ls_grid, host.data(), bytes, hipMemcpyHostToDevice));
     c->ls_grid_h = h; c->ls_grid_w = w;
     return PMX_OK;
@@ -368,7 +356,7 @@ extern "C" int pmx_loss_set_poses(pmx_ctx* c, const double* poses, const int* n_
     }
     if ((rc = pmx_prof_begin(c, "loss_labels|pmx_labels", (double)batch * fh * fw * (N_CH * 4 + 1)))) return rc;
     hipLaunchKernelGGL(loss_targets_kernel, dim3(blocks_for((long long)fh * fw), PMX_N_LIMBS + PMX_N_HEAT + 1, batch), dim3(256), 0, c->stream,
-                       (const double*)c->ls_poses, (const int*)c->ls_off, grid_view(c, fh, fw), ignore_mask ? (const uint8_t*)c->ls_mask_in : nullptr,
+                       (const double*)c->ls_poses, (const int*)c->ls_off, grid_view(c), ignore_mask ? (const uint8_t*)c->ls_mask_in : nullptr,
                        (float*)c->ls_tgt, (uint8_t*)c->ls_mask, h, w, fh, fw, heat_sigma * heat_sigma, paf_width);
     PMX_HIP(hipGetLastError());
     if ((rc = pmx_prof_end(c))) return rc;
@@ -404,7 +392,7 @@ extern "C" int pmx_loss_set_targets(pmx_ctx* c, const float* paf_t, const float*
             PMX_HIP(hipMemcpyAsync(c->ls_full + PMX_N_PAF * hw, heat_t + b * PMX_N_HEAT * hw, PMX_N_HEAT * hw * sizeof(float), hipMemcpyHostToDevice,
                                    c->stream));
             hipLaunchKernelGGL(loss_resize_kernel, dim3(blocks_for((long long)fhw), N_CH + 1), dim3(256), 0, c->stream, (const float*)c->ls_full,
-                               grid_view(c, fh, fw), ignore_mask ? (const uint8_t*)c->ls_mask_in : nullptr, (float*)c->ls_tgt, (uint8_t*)c->ls_mask, b,
+                               grid_view(c), ignore_mask ? (const uint8_t*)c->ls_mask_in : nullptr, (float*)c->ls_tgt, (uint8_t*)c->ls_mask, b,
                                h, w, fh, fw);
             PMX_HIP(hipGetLastError());
         }

@@ -72,8 +72,9 @@ int build_seg_tables(pmx_ctx* c, const std::vector<Geo>& g)
 
 namespace {
 
-// up-sampling tables of one (network map, up-sampled map) size pair, built once per context and kept (a fresh allocation: nothing in
-// flight reads it; the cache is started over only by pmx_detect_images / pmx_postprocess_images behind a device synchronisation)
+// the table set [grid | taps] (pp_tables.h) of one (network map, up-sampled map) size pair, built once per context and kept (a fresh
+// allocation: nothing in flight reads it; the cache is started over only by pmx_detect_images / pmx_postprocess_images behind a device
+// synchronisation)
 int cached_tables(pmx_ctx* c, int in_h, int in_w, int out_h, int out_w, PPTables* out)
 {
     // (the peak-branch option changes the Gaussian taps / border flags the table set carries: part of the key; a changed pmx_set_gaussian
@@ -81,28 +82,14 @@ int cached_tables(pmx_ctx* c, int in_h, int in_w, int out_h, int out_w, PPTables
     const auto key = std::make_tuple(in_h, in_w, out_h, c->opt_gpu_branch_peaks ? -out_w : out_w);
     auto it = c->tab_cache.find(key);
     if (it != c->tab_cache.end()) { *out = it->second.first; return PMX_OK; }
-    // the context's own single-size machinery builds the grids (np.linspace semantics, Gaussian taps, peak-branch flags) ...
-    int rc = pmx_ensure_tables(c, in_h, in_w, out_h, out_w);
-    if (rc) return rc;
-    // ... and the cache keeps a private copy: one allocation [xi0 | xi1 | yi0 | yi1 | xlo | xhi | ylo | yhi | gauss]
-    const PPTables& src = c->tab;
-    const size_t ni = (size_t)2 * out_w + (size_t)2 * out_h, nd = (size_t)2 * out_w + (size_t)2 * out_h + (2 * PMX_GAUSS_MAX_RADIUS + 1);
-    const size_t ibytes = (ni * sizeof(int) + 7) / 8 * 8;
+    const size_t grid = pp_grid_bytes(out_h, out_w), bytes = grid + pp_taps_bytes();
     DevBuf<char> base;
-    if ((rc = base.alloc(ibytes + nd * sizeof(double)))) return rc;
-    PPTables t = src;
-    int* ip = reinterpret_cast<int*>(base.get());
-    double* dp = reinterpret_cast<double*>(base + ibytes);
-    t.xi0 = ip; t.xi1 = ip + out_w; t.yi0 = ip + 2 * out_w; t.yi1 = ip + 2 * out_w + out_h;
-    t.xlo = dp; t.xhi = dp + out_w; t.ylo = dp + 2 * out_w; t.yhi = dp + 2 * out_w + out_h; t.gauss = dp + 2 * out_w + 2 * out_h;
-    hipError_t e = hipSuccess;
-    auto cp = [&](void* d, const void* s, size_t n) { if (e == hipSuccess) e = hipMemcpy(d, s, n, hipMemcpyDeviceToDevice); };
-    cp(t.xi0, src.xi0, out_w * sizeof(int)); cp(t.xi1, src.xi1, out_w * sizeof(int));
-    cp(t.yi0, src.yi0, out_h * sizeof(int)); cp(t.yi1, src.yi1, out_h * sizeof(int));
-    cp(t.xlo, src.xlo, out_w * sizeof(double)); cp(t.xhi, src.xhi, out_w * sizeof(double));
-    cp(t.ylo, src.ylo, out_h * sizeof(double)); cp(t.yhi, src.yhi, out_h * sizeof(double));
-    cp(t.gauss, src.gauss, (2 * PMX_GAUSS_MAX_RADIUS + 1) * sizeof(double));
-    if (e != hipSuccess) { pmx_set_error("post-process table copy failed: %s", hipGetErrorString(e)); return PMX_ERR_HIP; }
+    if (int rc = base.alloc(bytes)) return rc;
+    std::vector<double> host(bytes / sizeof(double));
+    PPTables t{};
+    pp_grid_build(in_h, in_w, out_h, out_w, 0, host.data(), base.get(), t);
+    pmx_pp_gauss(c, host.data() + grid / sizeof(double), base + grid, t);
+    PMX_HIP(hipMemcpy(base, host.data(), bytes, hipMemcpyHostToDevice));
     c->tab_cache.emplace(key, std::make_pair(t, std::move(base)));
     *out = t;
     return PMX_OK;
@@ -204,7 +191,6 @@ extern "C" int pmx_postprocess_images(pmx_ctx* c, const int* map_hw, int B, cons
     }
     for (PPCall& q : calls)
         if ((rc = cached_tables(c, q.maps.fh, q.maps.fw, q.map_h, q.map_w, &q.tab))) return rc;
-    c->tab_in_h = -1;                 // (the context's single-size table was used as scratch by cached_tables)
     if (scale_xy) PMX_HIP(hipMemcpyAsync(c->d_scale, scale_xy, sizeof(double) * 2 * B, hipMemcpyHostToDevice, c->stream));
     for (const PPCall& q : calls)
         if ((rc = pp_launch(q.maps, q.tab, pmx_pp_view(c->pp, q.base), q.B, q.map_h, q.map_w, q.img_len, scale_xy ? c->d_scale + 2 * q.base : nullptr, 0,

@@ -358,15 +358,7 @@ extern "C" int pmx_keypoints(pmx_ctx* c, int B, int out_h, int out_w, double thr
     int rc;
     if ((rc = pmx_ensure_tables(c, c->cur_fh, c->cur_fw, out_h, out_w, c->opt_kp_flip_x))) return rc;
     const int n_ch = c->n_heat - 1;
-    const long long fhw = (long long)c->cur_fh * c->cur_fw;
-    PPMaps m;
-    if (c->maps_external) {
-        m.heat = c->ext_heat; m.paf = nullptr; m.sx = 1; m.sy = c->cur_fw; m.sc = fhw; m.sbh = c->n_heat * fhw; m.sbp = 0;
-    } else {
-        m.heat = c->cat + c->cat_heat; m.paf = nullptr; m.sc = 1; m.sx = c->cat_c; m.sy = (long long)c->cur_fw * c->cat_c;
-        m.sbh = fhw * c->cat_c; m.sbp = 0;
-    }
-    m.fh = c->cur_fh; m.fw = c->cur_fw;
+    const PPMaps m = pmx_current_maps(c);
     const size_t nkp = (size_t)B * n_ch * 4;
     if ((rc = pmx_ensure_smoothed(c, (size_t)B * n_ch * out_h * out_w)) || (rc = c->d_kp.ensure(nkp, c->stream))) return rc;
     if ((rc = pp_keypoints_launch(m, c->tab, c->pp, B, n_ch, out_h, out_w, thresh, c->d_kp, c->stream))) return rc;

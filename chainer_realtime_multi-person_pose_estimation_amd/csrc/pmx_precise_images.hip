@@ -275,7 +275,7 @@ extern "C" int pmx_detect_precise_images(pmx_ctx* c, const pmx_precise_image* im
     PMX_CHECK(maps_floats < (1ll << 40) && dn_blocks < (1ll << 31), PMX_ERR_CAPACITY,
               "pmx_detect_precise_images: full-resolution maps of %lld floats / %lld blocks too large", maps_floats, dn_blocks);
 
-    // ---- host staging: [pairs | images | int tables | (8-aligned) post-process grids + Gaussian taps]
+    // ---- host staging: [pairs | images | int tables | post-process taps, grids (pp_tables.h)]
     std::vector<PiPair> pairs(np);
     std::vector<PiImage> pim(n);
     std::vector<SegGeo> segs;
@@ -334,45 +334,16 @@ extern "C" int pmx_detect_precise_images(pmx_ctx* c, const pmx_precise_image* im
         }
     }
     PMX_CHECK(itab.size() < (1ull << 31), PMX_ERR_CAPACITY, "pmx_detect_precise_images: %zu table ints exceed the 32-bit table offsets", itab.size());
-    // post-process grids per distinct original size (the identity up-sampling of pmx_postprocess at full resolution) + one set of taps
-    std::map<std::pair<int, int>, size_t> grid_at;       // (oh, ow) -> byte offset of [xi0 | xi1 | yi0 | yi1] ints, then doubles
-    std::vector<char> gbytes;
-    PPTables tmpl{};
-    std::vector<double> taps;
-    pmx_pp_gauss(c, taps, tmpl);
-    const size_t taps_bytes = (size_t)(2 * PMX_GAUSS_MAX_RADIUS + 1) * sizeof(double);
-    PMX_CHECK(taps.size() <= (size_t)(2 * PMX_GAUSS_MAX_RADIUS + 1), PMX_ERR_STATE, "pmx_detect_precise_images: %zu Gaussian taps", taps.size());
-    gbytes.resize(taps_bytes, 0);
-    memcpy(gbytes.data(), taps.data(), taps.size() * sizeof(double));
-    {
-        std::vector<int> i0, i1;
-        std::vector<double> lo, hi;
-        for (int i = 0; i < n; ++i) {
-            const auto key = std::make_pair(imgs[i].orig_h, imgs[i].orig_w);
-            if (grid_at.count(key)) continue;
-            const int oh = key.first, ow = key.second;
-            const size_t o = gbytes.size(), ib = ((size_t)2 * (ow + oh) * sizeof(int) + 7) / 8 * 8;
-            gbytes.resize(o + ib + (size_t)2 * (ow + oh) * sizeof(double), 0);
-            int* ip = reinterpret_cast<int*>(gbytes.data() + o);
-            double* dp = reinterpret_cast<double*>(gbytes.data() + o + ib);
-            pmx_make_upsample_grid(ow, ow, i0, i1, lo, hi);
-            memcpy(ip, i0.data(), ow * sizeof(int)); memcpy(ip + ow, i1.data(), ow * sizeof(int));
-            memcpy(dp, lo.data(), ow * sizeof(double)); memcpy(dp + ow, hi.data(), ow * sizeof(double));
-            pmx_make_upsample_grid(oh, oh, i0, i1, lo, hi);
-            memcpy(ip + 2 * ow, i0.data(), oh * sizeof(int)); memcpy(ip + 2 * ow + oh, i1.data(), oh * sizeof(int));
-            memcpy(dp + 2 * ow, lo.data(), oh * sizeof(double)); memcpy(dp + 2 * ow + oh, hi.data(), oh * sizeof(double));
-            grid_at[key] = o;
-        }
-    }
+    // post-process tables (pp_tables.h): one taps block, then one grid per distinct original size (the identity up-sampling of
+    // pmx_postprocess at full resolution)
+    std::map<std::pair<int, int>, PPTables> tab_of;      // (oh, ow) -> its table set; the grids lie in the order of this map
+    size_t pp_bytes = pp_taps_bytes();
+    for (int i = 0; i < n; ++i)
+        if (tab_of.emplace(std::make_pair(imgs[i].orig_h, imgs[i].orig_w), PPTables{}).second) pp_bytes += pp_grid_bytes(imgs[i].orig_h, imgs[i].orig_w);
     const size_t o_pairs = 0, o_imgs = o_pairs + ((size_t)np * sizeof(PiPair) + 15) / 16 * 16;
     const size_t o_tab = o_imgs + ((size_t)n * sizeof(PiImage) + 15) / 16 * 16;
     const size_t o_pp = o_tab + (itab.size() * sizeof(int) + 15) / 16 * 16;
-    const size_t total = o_pp + gbytes.size();
-    std::vector<char> stage(total, 0);
-    memcpy(stage.data() + o_pairs, pairs.data(), (size_t)np * sizeof(PiPair));
-    memcpy(stage.data() + o_imgs, pim.data(), (size_t)n * sizeof(PiImage));
-    memcpy(stage.data() + o_tab, itab.data(), itab.size() * sizeof(int));
-    memcpy(stage.data() + o_pp, gbytes.data(), gbytes.size());
+    const size_t total = o_pp + pp_bytes;
 
     // ---- device buffers (grown on demand; the context's own buffers were checked above)
     PMX_DEV(c);
@@ -381,6 +352,21 @@ extern "C" int pmx_detect_precise_images(pmx_ctx* c, const pmx_precise_image* im
     if ((rc = grow(c->pi_dev, total)) || (rc = grow(c->pi_src, (size_t)src_bytes)) || (rc = grow(c->pi_tmp, (size_t)tmp_floats)) ||
         (rc = grow(c->pi_maps, (size_t)maps_floats)))
         return rc;
+    // (the tables hold device addresses: filled once pi_dev is where this call's copy will lie)
+    std::vector<double> stage((total + 7) / 8);
+    char* const hs = reinterpret_cast<char*>(stage.data());
+    memcpy(hs + o_pairs, pairs.data(), (size_t)np * sizeof(PiPair));
+    memcpy(hs + o_imgs, pim.data(), (size_t)n * sizeof(PiImage));
+    memcpy(hs + o_tab, itab.data(), itab.size() * sizeof(int));
+    PPTables taps{};
+    pmx_pp_gauss(c, hs + o_pp, c->pi_dev + o_pp, taps);
+    size_t o_grid = o_pp + pp_taps_bytes();
+    for (auto& g : tab_of) {
+        const int oh = g.first.first, ow = g.first.second;
+        g.second = taps;
+        pp_grid_build(oh, ow, oh, ow, 0, hs + o_grid, c->pi_dev + o_grid, g.second);
+        o_grid += pp_grid_bytes(oh, ow);
+    }
     const PiPair* d_pairs = reinterpret_cast<const PiPair*>(c->pi_dev + o_pairs);
     const PiImage* d_imgs = reinterpret_cast<const PiImage*>(c->pi_dev + o_imgs);
     const int* d_tab = reinterpret_cast<const int*>(c->pi_dev + o_tab);
@@ -388,7 +374,7 @@ extern "C" int pmx_detect_precise_images(pmx_ctx* c, const pmx_precise_image* im
     c->pp_valid = false;
     c->pp_calls.clear();
     auto enqueue = [&]() -> int {
-        PMX_HIP(hipMemcpyAsync(c->pi_dev, stage.data(), total, hipMemcpyHostToDevice, c->stream));
+        PMX_HIP(hipMemcpyAsync(c->pi_dev, hs, total, hipMemcpyHostToDevice, c->stream));
         for (int i = 0; i < n; ++i)
             PMX_HIP(hipMemcpyAsync(c->pi_src + src_off[i], imgs[i].bgr, (size_t)imgs[i].orig_h * imgs[i].orig_w * 3, hipMemcpyHostToDevice, c->stream));
         int r;
@@ -426,15 +412,7 @@ extern "C" int pmx_detect_precise_images(pmx_ctx* c, const pmx_precise_image* im
         q.maps.sx = 1; q.maps.sy = ow; q.maps.sc = hw;
         q.maps.sbh = q.maps.sbp = PI_CH * hw;
         q.maps.fh = oh; q.maps.fw = ow;
-        PPTables t = tmpl;
-        char* g = c->pi_dev + o_pp + grid_at[std::make_pair(oh, ow)];
-        const size_t ib = ((size_t)2 * (ow + oh) * sizeof(int) + 7) / 8 * 8;
-        int* ip = reinterpret_cast<int*>(g);
-        double* dp = reinterpret_cast<double*>(g + ib);
-        t.xi0 = ip; t.xi1 = ip + ow; t.yi0 = ip + 2 * ow; t.yi1 = ip + 2 * ow + oh;
-        t.xlo = dp; t.xhi = dp + ow; t.ylo = dp + 2 * ow; t.yhi = dp + 2 * ow + oh;
-        t.gauss = reinterpret_cast<double*>(c->pi_dev + o_pp);
-        q.tab = t;
+        q.tab = tab_of[std::make_pair(oh, ow)];
         q.base = i; q.B = 1; q.map_h = oh; q.map_w = ow; q.img_len = (double)ow; q.has_scale = false;
         q.limbs_slices = c->opt_limbs_slices >= 0 ? c->opt_limbs_slices : 8;      // (pmx_postprocess on full-resolution maps)
         calls.push_back(q);
