@@ -257,6 +257,15 @@ struct pmx_ctx {
     int ls_B = 0, ls_h = 0, ls_w = 0;                     // the targets' batch and network-input size (0: no targets)
     bool ls_have_poses = false;
     int ls_stages = 0;                                    // stages of the last hooked forward (0: none yet)
+    // pmx_samples.hip (sample preparation).  sp_host / sp_dev: the per-call block [descriptors | resize tables | host sources], ONE copy from
+    // pinned memory (`sp_copied` marks when the host side may be rewritten); sp_a: the resized intermediates of the training samples; sp_out:
+    // max_batch x insize x insize x 3 prepared images; sp_mask_raw / sp_mask_tmp / sp_mask: the mask before, between and after the two
+    // dilation passes; sp_const: the weight and division tables of the contract (uploaded once).
+    HostBuf<char> sp_host;
+    hipEvent_t sp_copied = nullptr; bool sp_pending = false;
+    DevBuf<char> sp_dev, sp_const;
+    DevBuf<uint8_t> sp_a, sp_out, sp_mask_raw, sp_mask_tmp, sp_mask;
+    int sp_n = 0, sp_insize = 0;                          // the prepared samples (0: none)
 };
 constexpr int PMX_LOSS_SLOTS = 7;
 constexpr int PMX_LOSS_MAX_BLOCKS = 256;
@@ -295,6 +304,9 @@ int forward_segments(pmx_ctx* c, const uint8_t* d_u8, const std::vector<SegGeo>&
 int pmx_loss_check(pmx_ctx* c, int B, int H, int W);
 int pmx_loss_stage(pmx_ctx* c, int stage, int B, int fh, int fw);
 int pmx_loss_finish(pmx_ctx* c, int n_stages, int B, int fh, int fw);
+// pmx_loss_set_poses with the ignore mask either on the host (copied before return) or already on the device (read where it lies)
+int pmx_loss_set_poses_masked(pmx_ctx* c, const double* poses, const int* n_people, int batch, int h, int w, const uint8_t* ignore_mask,
+                              bool mask_on_device, double heat_sigma, double paf_width);
 #define PMX_LOSS_NO_MIXED(c, what) \
     PMX_CHECK(!(c)->ls_on, PMX_ERR_STATE, what ": the validation-loss hook is on (pmx_loss_enable) and covers uniform batches only")
 // c->smoothed (and c->pp.smoothed) at `floats` floats at least, grown to exactly that once the stream no longer uses the old maps

@@ -320,6 +320,12 @@ int pmx_loss_finish(pmx_ctx* c, int n_stages, int B, int fh, int fw)
 extern "C" int pmx_loss_set_poses(pmx_ctx* c, const double* poses, const int* n_people, int batch, int h, int w, const uint8_t* ignore_mask,
                                   double heat_sigma, double paf_width)
 {
+    return pmx_loss_set_poses_masked(c, poses, n_people, batch, h, w, ignore_mask, false, heat_sigma, paf_width);
+}
+
+int pmx_loss_set_poses_masked(pmx_ctx* c, const double* poses, const int* n_people, int batch, int h, int w, const uint8_t* ignore_mask,
+                              bool mask_on_device, double heat_sigma, double paf_width)
+{
     PMX_CHECK(c && n_people, PMX_ERR_INVALID, "pmx_loss_set_poses: null arg");
     LOSS_POSENET(c, "pmx_loss_set_poses");
     if (int rc = check_common(c, "pmx_loss_set_poses", batch, h, w)) return rc;
@@ -344,19 +350,19 @@ extern "C" int pmx_loss_set_poses(pmx_ctx* c, const double* poses, const int* n_
     int rc;
     if ((rc = ensure_target_buffers(c)) || (rc = ensure_grid(c, h, w))) return rc;
     if ((rc = c->ls_poses.ensure((size_t)total * POSE_D, c->stream)) || (rc = c->ls_off.ensure((size_t)c->max_batch + 1, c->stream))) return rc;
-    if (ignore_mask && (rc = c->ls_mask_in.ensure((size_t)batch * h * w, c->stream))) return rc;
+    if (ignore_mask && !mask_on_device && (rc = c->ls_mask_in.ensure((size_t)batch * h * w, c->stream))) return rc;
     c->ls_B = 0; c->ls_have_poses = false;                  // until everything below is enqueued
     c->ls_h_off = off;
     c->ls_h_poses.assign(poses, poses + (size_t)total * POSE_D);
     if (total) PMX_HIP(hipMemcpyAsync(c->ls_poses, c->ls_h_poses.data(), (size_t)total * POSE_D * sizeof(double), hipMemcpyHostToDevice, c->stream));
     PMX_HIP(hipMemcpyAsync(c->ls_off, c->ls_h_off.data(), (size_t)(batch + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    if (ignore_mask) {      // staged like the poses: the caller's array is read here, whatever kind of memory it is
+    if (ignore_mask && !mask_on_device) {      // staged like the poses: the caller's array is read here, whatever kind of memory it is
         c->ls_h_mask.assign(ignore_mask, ignore_mask + (size_t)batch * h * w);
         PMX_HIP(hipMemcpyAsync(c->ls_mask_in, c->ls_h_mask.data(), c->ls_h_mask.size(), hipMemcpyHostToDevice, c->stream));
     }
     if ((rc = pmx_prof_begin(c, "loss_labels|pmx_labels", (double)batch * fh * fw * (N_CH * 4 + 1)))) return rc;
     hipLaunchKernelGGL(loss_targets_kernel, dim3(blocks_for((long long)fh * fw), PMX_N_LIMBS + PMX_N_HEAT + 1, batch), dim3(256), 0, c->stream,
-                       (const double*)c->ls_poses, (const int*)c->ls_off, grid_view(c), ignore_mask ? (const uint8_t*)c->ls_mask_in : nullptr,
+                       (const double*)c->ls_poses, (const int*)c->ls_off, grid_view(c), !ignore_mask ? nullptr : mask_on_device ? ignore_mask : (const uint8_t*)c->ls_mask_in,
                        (float*)c->ls_tgt, (uint8_t*)c->ls_mask, h, w, fh, fw, heat_sigma * heat_sigma, paf_width);
     PMX_HIP(hipGetLastError());
     if ((rc = pmx_prof_end(c))) return rc;

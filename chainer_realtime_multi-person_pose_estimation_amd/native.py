@@ -26,7 +26,8 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB_PATH = os.path.join(CSRC, 'libpose_mi355x.so')
 HEADER = os.path.join(os.path.dirname(HERE), 'include', 'pose_mi355x.h')
 SOURCES = [('pmx_api.hip', []), ('pmx_precise.hip', []), ('pmx_multi.hip', []), ('pmx_precise_images.hip', ['-ffp-contract=off']), ('conv_mfma.hip', []), ('conv_wino.hip', ['-mllvm', '-pragma-unroll-threshold=200000']), ('conv1_wino.hip', []), ('conv_f16.hip', []), ('conv_select.hip', []), ('prep.hip', ['-ffp-contract=off']),
-           ('postproc.hip', ['-ffp-contract=off']), ('pmx_boxes.hip', ['-ffp-contract=off']), ('pmx_loss.hip', ['-ffp-contract=off'])]
+           ('postproc.hip', ['-ffp-contract=off']), ('pmx_boxes.hip', ['-ffp-contract=off']), ('pmx_loss.hip', ['-ffp-contract=off']),
+           ('pmx_samples.hip', ['-ffp-contract=off'])]
 # the opt-in bf16x3 kernels (option "precision" = 1; DESIGN.md 4.1.5: frozen, slower than the fp32 Winograd path) are NOT part of the
 # default library: PMX_BUILD_BF16X3=1 in the environment of the build adds their translation unit (the stamp then differs, so the
 # library is rebuilt when the variable changes)
@@ -68,6 +69,14 @@ class PmxPreciseImage(C.Structure):
 class PmxBoxImage(C.Structure):
     """include/pose_mi355x.h::pmx_box_image -- one image of a many-image box call (pmx_keypoints_boxes_images)."""
     _fields_ = [('bgr', C.c_void_p), ('h', C.c_int), ('w', C.c_int)]
+
+
+class PmxSample(C.Structure):
+    """include/pose_mi355x.h::pmx_sample -- one sample of pmx_samples_prepare."""
+    _fields_ = [('bgr', C.c_void_p), ('mask', C.c_void_p), ('src_h', C.c_int32), ('src_w', C.c_int32), ('resized_w', C.c_int32),
+                ('resized_h', C.c_int32), ('has_rotate', C.c_int32), ('rot_w', C.c_int32), ('rot_h', C.c_int32), ('has_crop', C.c_int32),
+                ('off_x', C.c_int32), ('off_y', C.c_int32), ('has_distort', C.c_int32), ('delta', C.c_int32 * 3), ('flip', C.c_int32),
+                ('inv', C.c_double * 6)]
 
 
 class PmxError(RuntimeError):
@@ -316,6 +325,10 @@ def load():
         'pmx_validate_batch': (ci, [vp, vp, ci, ci, ci, ci, vp]),
         'pmx_get_labels': (ci, [vp, ci, vp, vp, ci, ci]),
         'pmx_get_loss_targets': (ci, [vp, vp, vp, vp]),
+        'pmx_samples_prepare': (ci, [vp, vp, ci, ci, ci]),
+        'pmx_samples_device_ptrs': (ci, [vp, C.POINTER(vp), C.POINTER(vp)]),
+        'pmx_get_samples': (ci, [vp, vp, vp, ci, ci]),
+        'pmx_validate_samples': (ci, [vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)     # AttributeError if the .so lacks a declared symbol
@@ -910,6 +923,65 @@ class Engine(object):
         mask = np.empty((B, h // 8, w // 8), np.uint8)
         self._check(self.lib.pmx_get_loss_targets(self._ctx, _ptr(paf), _ptr(heat), _ptr(mask)))
         return paf, heat, mask.astype(bool)
+
+    # ---- sample preparation (include/pose_mi355x.h: pmx_samples_*) ---------------------------------------------------
+    def samples_prepare(self, imgs, masks, records, insize):
+        """imgs: uint8 (h, w, 3) arrays of any sizes; masks: per image an (h, w) array (non-zero = ignored) or None; records:
+        samples.SampleRecord per image.  The prepared samples stay on the device (samples_get, validate_samples).  Asynchronous."""
+        from . import samples as S
+        n = len(imgs)
+        arr = (PmxSample * max(n, 1))()
+        keep = []
+        for i in range(n):
+            img = np.ascontiguousarray(imgs[i], dtype=np.uint8)
+            rec = records[i]
+            s = arr[i]
+            keep.append(img)
+            s.bgr, s.src_h, s.src_w = _ptr(img), img.shape[0], img.shape[1]
+            if masks is not None and masks[i] is not None:
+                m = np.ascontiguousarray(np.asarray(masks[i]) != 0, dtype=np.uint8)
+                keep.append(m)
+                s.mask = _ptr(m)
+            if rec.resized is not None:
+                s.resized_w, s.resized_h = rec.resized
+            if rec.R is not None:
+                s.has_rotate, s.rot_w, s.rot_h = 1, rec.rotated[0], rec.rotated[1]
+                s.inv = (C.c_double * 6)(*S.invert_affine(rec.R))
+            if rec.offset is not None:
+                s.has_crop, s.off_x, s.off_y = 1, rec.offset[0], rec.offset[1]
+            if rec.distort is not None:
+                s.has_distort, s.delta = 1, (C.c_int32 * 3)(*rec.distort)
+            s.flip = int(rec.flip)
+        self._check(self.lib.pmx_samples_prepare(self._ctx, C.cast(arr, C.c_void_p), n, int(insize), 0))
+        self._samples = (n, int(insize))
+
+    def samples_get(self):
+        """(images (n, insize, insize, 3) uint8, dilated masks (n, insize, insize) bool) of the last samples_prepare (synchronises)."""
+        if getattr(self, '_samples', None) is None:          # the library reports the call-sequence error
+            self._check(self.lib.pmx_get_samples(self._ctx, None, None, 0, 0))
+        n, s = self._samples
+        img, mask = np.empty((n, s, s, 3), np.uint8), np.empty((n, s, s), np.uint8)
+        self._check(self.lib.pmx_get_samples(self._ctx, _ptr(img), _ptr(mask), n, s))
+        return img, mask.astype(bool)
+
+    def samples_device_ptrs(self):
+        a, b = C.c_void_p(), C.c_void_p()
+        self._check(self.lib.pmx_samples_device_ptrs(self._ctx, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def validate_samples(self, poses_per_image):
+        """loss_set_poses with the prepared device mask + the hooked forward on the prepared device images + loss_get ->
+        (total, paf_losses (6,), heat_losses (6,))."""
+        flat, n = self._poses_arg(poses_per_image)
+        out = np.zeros(13)
+        if getattr(self, '_samples', None) is not None and len(n) != self._samples[0]:
+            raise ValueError('validate_samples: poses for %d images, %d samples prepared' % (len(n), self._samples[0]))
+        self._check(self.lib.pmx_validate_samples(self._ctx, _ptr(flat), _ptr(n), _ptr(out)))
+        B, s = self._samples
+        self._loss_shape = (B, s, s)
+        self._B = B
+        self._fhw = (s // 8, s // 8)
+        return float(out[0]), out[1:7].copy(), out[7:13].copy()
 
     # ---- measurement -------------------------------------------------------------------------------
     def timer_start(self):

@@ -580,6 +580,103 @@ class PoseDetector(object):
         return {'val/loss': float(total), 'val/paf': float(paf.sum()), 'val/heat': float(heat.sum()),
                 'paf_stages': [float(v) for v in paf], 'heat_stages': [float(v) for v in heat]}
 
+    # ---- sample preparation (reference coco_data_loader.py:61-205, 334-341) ----------------------------------------------------------
+    @staticmethod
+    def _check_sample_args(imgs, poses_per_image, ignore_masks, insize, mode, records):
+        from . import samples as S
+        imgs = [np.asarray(im) for im in imgs]
+        if len(imgs) == 0:
+            raise ValueError('prepare_samples needs at least one image')
+        if mode not in ('val', 'train'):
+            raise ValueError("prepare_samples: mode must be 'val' or 'train'")
+        try:
+            insize = int(insize)
+        except (TypeError, ValueError):
+            raise ValueError('prepare_samples: insize %r' % (insize,))
+        if insize < 8 or insize % 8:
+            raise ValueError('prepare_samples: insize must be a positive multiple of 8, got %d' % insize)
+        for im in imgs:
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 or min(im.shape[:2]) < 1:
+                raise ValueError('prepare_samples needs uint8 H x W x 3 images')
+        if len(poses_per_image) != len(imgs):
+            raise ValueError('prepare_samples: %d images but poses for %d' % (len(imgs), len(poses_per_image)))
+        poses = [S.check_int_poses(np.zeros((0, len(JointType), 3), np.int32) if np.size(p) == 0 else p, 'poses of image %d' % i)
+                 for i, p in enumerate(poses_per_image)]
+        masks = None
+        if ignore_masks is not None:
+            if len(ignore_masks) != len(imgs):
+                raise ValueError('prepare_samples: %d images but %d ignore masks' % (len(imgs), len(ignore_masks)))
+            masks = [None if m is None else np.asarray(m) for m in ignore_masks]
+            for i, m in enumerate(masks):
+                if m is not None and m.shape != imgs[i].shape[:2]:
+                    raise ValueError('ignore mask %d: shape %r, expected %r' % (i, m.shape, imgs[i].shape[:2]))
+        if records is not None:
+            if len(records) != len(imgs):
+                raise ValueError('prepare_samples: %d images but %d records' % (len(imgs), len(records)))
+            for i, r in enumerate(records):
+                if not isinstance(r, S.SampleRecord):
+                    raise ValueError('record %d is no SampleRecord' % i)
+                r.check()
+                if r.src_hw != imgs[i].shape[:2] or r.insize != insize:
+                    raise ValueError('record %d is for a %r image at insize %d, the image is %r at %d'
+                                     % (i, r.src_hw, r.insize, imgs[i].shape[:2], insize))
+        return imgs, poses, masks, insize
+
+    def _records_for(self, imgs, poses, insize, mode, records):
+        from . import samples as S
+        if records is not None:
+            return list(records)
+        if mode == 'val':
+            return [S.SampleRecord.val(im.shape[:2], insize) for im in imgs]
+        return [S.draw_augmentation(im.shape[:2], p, insize) for im, p in zip(imgs, poses)]
+
+    def prepare_samples(self, imgs, poses_per_image, ignore_masks=None, insize=368, mode='val', records=None):
+        """`CocoDataLoader.generate_labels` without the label maps (coco_data_loader.py:334-341): the pixels on the device, the poses on the
+        host.  imgs: uint8 BGR images of any sizes; poses_per_image: per image (n, 18, 3) INTEGER rows (x, y, v) in that image's pixels (the
+        reference keeps int32 poses); ignore_masks: per image an (h, w) array at the image's size (non-zero = ignored) or None.
+        mode 'val': the resize to insize x insize; mode 'train': the reference's augmentation, drawn from `random` / `np.random` in its
+        order (samples.draw_augmentation) unless `records` (samples.SampleRecord per image) gives every step.
+        -> (images (B, insize, insize, 3) uint8, list of int32 poses in the samples' pixels, dilated masks (B, insize, insize) bool)."""
+        from . import samples as S
+        imgs, poses, masks, insize = self._check_sample_args(imgs, poses_per_image, ignore_masks, insize, mode, records)
+        if self.model is not None:
+            raise RuntimeError('prepare_samples runs on the built-in engine: not available with a model= callable')
+        recs = self._records_for(imgs, poses, insize, mode, records)
+        self._grow(1, insize, insize)
+        mb = self._cap[0]
+        out_i, out_m = [], []
+        for i in range(0, len(imgs), mb):
+            self.engine.samples_prepare(imgs[i:i + mb], None if masks is None else masks[i:i + mb], recs[i:i + mb], insize)
+            a, m = self.engine.samples_get()
+            out_i.append(a)
+            out_m.append(m)
+        return np.concatenate(out_i), [S.transform_poses(p, r) for p, r in zip(poses, recs)], np.concatenate(out_m)
+
+    def validation_loss_raw(self, imgs, poses_per_image, ignore_masks=None, insize=368):
+        """`validation_loss` for raw validation data: images of any sizes, integer poses in each image's pixels, ignore masks at each
+        image's size.  The resize to insize x insize, the mask's resize and 16 x 16 dilation, the label maps, the forward and the loss all
+        run on the device; only the poses (n x 18 x 3 numbers) are scaled on the host.  -> the dictionary of validation_loss."""
+        from . import samples as S
+        imgs, poses, masks, insize = self._check_sample_args(imgs, poses_per_image, ignore_masks, insize, 'val', None)
+        if self.model is not None:
+            raise RuntimeError('validation_loss_raw runs the built-in network: not available with a model= callable')
+        if self.engine.weights_missing():
+            raise RuntimeError('PoseDetector has no weights: pass weights_file=, weights= or model=')
+        recs = self._records_for(imgs, poses, insize, 'val', None)
+        self._grow(1, insize, insize)
+        mb = self._cap[0]
+        total, paf, heat = 0.0, np.zeros(6), np.zeros(6)
+        for i in range(0, len(imgs), mb):
+            n = len(imgs[i:i + mb])
+            self.engine.samples_prepare(imgs[i:i + n], None if masks is None else masks[i:i + n], recs[i:i + n], insize)
+            t, p, q = self.engine.validate_samples([S.transform_poses(a, r) for a, r in zip(poses[i:i + n], recs[i:i + n])])
+            total += n * t
+            paf += n * p
+            heat += n * q
+        total, paf, heat = total / len(imgs), paf / len(imgs), heat / len(imgs)
+        return {'val/loss': float(total), 'val/paf': float(paf.sum()), 'val/heat': float(heat.sum()),
+                'paf_stages': [float(v) for v in paf], 'heat_stages': [float(v) for v in heat]}
+
     def detect_maps(self, paf, heat, map_h, map_w, img_len=None, scale_xy=None):
         """Post-process only (pose_detector.py:501-517) on network outputs paf (B,38,h,w), heat (B,19,h,w)."""
         self.engine.set_maps(paf, heat)

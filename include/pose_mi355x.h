@@ -340,8 +340,8 @@ int pmx_precise_images_table_bytes(pmx_ctx* ctx, size_t* bytes);
 /* ---- validation loss: Validator.evaluate (train_coco_pose_estimation.py:129-159) without the data loader ------------------------
  * The forward under no_backprop_mode (:147-150) followed by compute_loss (:41-73): per stage the mean squared error of the PAF and of the
  * heat-map output against the label maps, ignored pixels excluded by overwriting the target with the output (:62-63).  Forward only: no
- * backward pass, no optimiser, no augmentation; the 16 x 16 dilation of the ignore mask (coco_data_loader.py:340) and the image / mask
- * resizes stay with the caller.  posenet contexts (facenet / handnet: PMX_ERR_STATE), uniform batches, fp32 and f16 mode.  With the hook off
+ * backward pass, no optimiser.  These entries take images that are already samples (insize x insize, mask resized and dilated); the
+ * resizes, the 16 x 16 dilation of the ignore mask (coco_data_loader.py:340) and the augmentation are pmx_samples_prepare, below.  posenet contexts (facenet / handnet: PMX_ERR_STATE), uniform batches, fp32 and f16 mode.  With the hook off
  * (the default) no call of this header launches, allocates or synchronises anything more than before.
  *
  * Targets.  pmx_loss_set_poses evaluates generate_heatmaps + generate_pafs (coco_data_loader.py:208-268) on the device in float64, product
@@ -391,6 +391,64 @@ int pmx_get_labels(pmx_ctx* ctx, int image, float* paf, float* heat, int h, int 
 /* parity accessor: the current targets as NCHW float32 (batch x 38 | 19 x h/8 x w/8) and the resized ignore mask (batch x h/8 x w/8, 0 | 1);
  * any pointer may be NULL.  Synchronises. */
 int pmx_get_loss_targets(pmx_ctx* ctx, float* paf_t, float* heat_t, uint8_t* mask);
+
+/* ---- sample preparation: the pixel side of CocoDataLoader.generate_labels (coco_data_loader.py:72-205, 334-341) ---------------------
+ * One call prepares up to max_batch samples from images of different sizes: one launch per step over all samples, every kernel a gather
+ * (no atomics: the same bits on every run).  The NUMBERS of a sample (scale, matrix, crop offset, colour offsets, flip) come from the
+ * caller; the reference's random policy and its int32 pose arithmetic are host code (samples.py).  Steps, in the reference's order:
+ *   resize   (resized_w, resized_h) != (0, 0): cv2.resize (linear, uint8; the contract of pmx_forward_u8_resized) of the image, and of the
+ *            mask as 0/1 bytes followed by != 0 (:76-77)
+ *   rotate   has_rotate: cv2.warpAffine of the resized image to rot_w x rot_h, cubic with constant border 128 (round-half-even of 127.5),
+ *            and of the mask x 255, linear with border 0, followed by > 0 (:115-117).  OUR contract, modelled on OpenCV's fixed-point scheme;
+ *            no equality with an OpenCV build is claimed.  `inv` = the INVERSE matrix M0 .. M5 in float64.  For destination (x, y):
+ *            X = (rint((M1*y + M2)*1024) + 16 + rint(M0*x*1024)) >> 5 and Y alike from M3, M4, M5, rint = round-half-even in float64 without
+ *            fused multiply-add; source pixel X >> 5, fraction X & 31.  Cubic: taps -1 .. +2, per fraction f/32 four float32 coefficients
+ *            of the Keys kernel with A = -0.75; linear: taps 0 .. +1 with (1 - f/32, f/32).  2-D weights rint(cy[i]*cx[j]*32768) (float32
+ *            product) as int16, their sum corrected to exactly 32768 at the largest weight (the first in row-major order among equals).
+ *            Pixel = clamp((sum w*p + 16384) >> 15, 0, 255); a tap outside the source reads the border value.
+ *   crop     has_crop: the insize x insize window whose first pixel is (off_x, off_y) of the rotated image; outside it the image is 127
+ *            (uint8(127.5), :137) and the mask 0.  Only the window is computed; the rotated image as a whole never exists.  Window pixels
+ *            outside the rotated image are 127, rotated-image pixels outside the source 128: the reference's seam, kept.
+ *   distort  has_distort: BGR -> HSV in integers (v = max, d = v - min, s = (d*sdiv[v] + 2048) >> 12 with sdiv[v] = rint(255*4096/v);
+ *            h = g-b | b-r+2d | r-g+4d tested in the order v == r, v == g, else, then (h*hdiv[d] + 2048) >> 12 with hdiv[d] =
+ *            rint(180*4096/(6d)), + 180 if negative; both tables 0 at 0), delta[0..2] added to h, s, v, each clamped to 0 .. 255 (the hue is
+ *            clamped, not wrapped, :167; a hue >= 180 then counts modulo 180), HSV -> BGR by the float32 six-sector formula
+ *            (h*(6/180), s/255, v/255 as float32 products with the float32 constants), clamp(rint(x*255)).  |delta| <= 10, 40, 30.
+ *   flip     the window mirrored left-right (:176-177)
+ *   has_crop = 0: a VALIDATION sample -- only resize_data to insize x insize (:336); every other step must be off.
+ * Then, for every sample, the 16 x 16 MORPH_DILATE of the mask (:340): out[y, x] = max in[y-8 .. y+7, x-8 .. x+7] inside the image.
+ * Results stay on the device: batch x insize x insize x 3 uint8 BGR and the dilated mask batch x insize x insize (0 | 1), which
+ * pmx_validate_samples hands to the label, forward and loss entries without a host round trip.
+ * bgr: src_h x src_w x 3 uint8; mask: src_h x src_w uint8 (non-zero = ignored) or NULL; host pointers, or device pointers when on_device
+ * (they must then stay valid until the stream has run the call).  Asynchronous; host arrays are read before the call returns.
+ * The workspace (sources, resized intermediates, results) grows on demand up to PMX_SAMPLES_WORKSPACE_BYTES.
+ * Errors (checked before anything is enqueued; the context stays usable): PMX_ERR_INVALID for null pointers, n <= 0, insize no positive
+ * multiple of 8, non-positive sizes or sides above 16384, non-finite matrix entries, a singular matrix, colour offsets outside the ranges,
+ * a validation sample with another step on; PMX_ERR_CAPACITY for n > max_batch, insize * insize > max_h * max_w, a workspace above the
+ * budget; PMX_ERR_STATE on facenet / handnet contexts. */
+#define PMX_SAMPLES_WORKSPACE_BYTES ((size_t)1 << 30)
+typedef struct pmx_sample {
+    const uint8_t* bgr;
+    const uint8_t* mask;
+    int32_t src_h, src_w;
+    int32_t resized_w, resized_h;     /* 0, 0: no resize */
+    int32_t has_rotate, rot_w, rot_h;
+    int32_t has_crop, off_x, off_y;
+    int32_t has_distort, delta[3];
+    int32_t flip;
+    double inv[6];
+} pmx_sample;
+int pmx_samples_prepare(pmx_ctx* ctx, const pmx_sample* samples, int n, int insize, int on_device);
+/* device pointers of the prepared images and dilated masks (either may be NULL); valid until the next pmx_samples_prepare or pmx_destroy.
+ * PMX_ERR_STATE without prepared samples.  Does not synchronise. */
+int pmx_samples_device_ptrs(pmx_ctx* ctx, void** bgr_nhwc, void** mask);
+/* parity accessor: the prepared images (n x insize x insize x 3) and dilated masks (n x insize x insize) -> host; either may be NULL; n and
+ * insize as prepared (else PMX_ERR_INVALID).  Synchronises. */
+int pmx_get_samples(pmx_ctx* ctx, uint8_t* bgr, uint8_t* mask, int n, int insize);
+/* Validator.evaluate for the prepared samples: pmx_loss_set_poses (heat_sigma 7, paf_width 8: the reference's params) with the prepared
+ * device mask, pmx_validate_batch on the prepared device images.  poses / n_people as pmx_loss_set_poses takes them, in the pixels of the
+ * prepared samples; out13 as pmx_validate_batch.  PMX_ERR_STATE without prepared samples.  Synchronises. */
+int pmx_validate_samples(pmx_ctx* ctx, const double* poses, const int* n_people, double* out13);
 
 /* results.  pmx_results_layout synchronises, grows the capacities and re-runs the post-process if an image overflowed them,
  * and returns the layout of the (now final) records; pmx_get_results does the same and copies `batch` records to `out`
