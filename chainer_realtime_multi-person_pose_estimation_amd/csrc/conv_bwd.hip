@@ -1,0 +1,265 @@
+// conv_bwd.hip -- the launches of pmx_conv2d_backward that are not the dispatcher's: the mask kernel (g from dy and z), the bias gradient
+// and the weight gradient.  Semantics and the summation orders: include/pose_mi355x.h (pmx_conv2d_backward); tiling: DESIGN.md 4.7.
+//
+//   weight gradient  per tap (ky, kx) a GEMM  dw[co][ci] = sum over pixels p of g[p][co] * x[p + (ky-pad, kx-pad)][ci]:  M = cout, N = cin,
+//                    K = B * H * W.  NHWC puts the channels of a pixel side by side, which is the operand layout of v_mfma_f32_32x32x2_f32
+//                    as it stands: A = 32 consecutive co of pixel p (lanes 0-31) and of pixel p + 1 (lanes 32-63), B = 32 consecutive ci of
+//                    the two tap-shifted pixels; each lane loads ONE float per operand, a half-wave reads one 128-byte run.
+//                    A wave owns one UNIT = (tap row ky, 32 co, NCI x 32 ci) and keeps the KS taps of the row for NCI ci tiles in
+//                    NCI x KS accumulators (7x7: 7 x 16 registers; 3x3: 2 x 3; 1x1: 4 x 1), so a g fragment feeds NCI * KS MFMAs and an x
+//                    fragment is fetched once per (pixel pair, kx).  The four waves of a block are four consecutive units: they differ in
+//                    the co tile (or the tap row) and read the same x pixels, which the vector L1 serves.  The operands are NOT staged in
+//                    LDS: one dword per lane per MFMA is 4 bytes / lane / 64 cycles, far below what the L1 delivers, and a tap outside
+//                    the image is a select on the loaded value, not a halo.
+//                    K is cut into strips of image rows (blockIdx.y); a strip's accumulators go to its own slot [strip][tap][co][ci] of the
+//                    workspace and conv_wgrad_combine_kernel adds the slots left to right and writes OIHW.  No atomics.
+//   order            an accumulator element sees fmaf(g, x, acc) for the pixels of its strip in row-major order: the MFMA adds its two K
+//                    slots in order (pixel p, then p + 1) and consecutive MFMAs of an accumulator are consecutive pixel pairs.
+#include "pmx_ctx.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+struct WgradArgs {
+    const float* g; const float* x; float* ws;
+    int H, W, cg, cx, nco, nci, n_units, rows;      // nco / nci: 32-channel tiles of g / x; rows: image rows per strip
+    long long total_rows;                           // B * H
+};
+
+template <int KS, int NCI>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) conv_wgrad_kernel(WgradArgs a)      // (two waves per SIMD hide the loads' latency)
+{
+    constexpr int PAD = KS / 2;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, half = lane >> 5, l = lane & 31;
+    const int unit = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave);       // (wave-uniform, and the compiler is told so)
+    if (unit >= a.n_units) return;                  // (no barrier anywhere below: a wave may leave alone)
+    const int co_t = unit % a.nco, ky = (unit / a.nco) % KS, cig = unit / (a.nco * KS);
+    const long long r0 = (long long)blockIdx.y * a.rows;
+    const long long r1 = r0 + a.rows < a.total_rows ? r0 + a.rows : a.total_rows;
+    const long long p0 = r0 * a.W, p1 = r1 * a.W;   // the strip's pixels [p0, p1) of the batch's B * H * W
+    const int H = a.H, W = a.W;
+
+    f32x16 acc[NCI][KS];
+#pragma unroll
+    for (int j = 0; j < NCI; ++j)
+#pragma unroll
+        for (int k = 0; k < KS; ++k)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[j][k][e] = 0.f;
+
+    // this half-wave's pixel q = p0 + half, p0 + half + 2, ...: (yq, xq) inside its image, tracked without divisions in the loop
+    long long q = p0 + half;
+    int xq = (int)(q % W), yq = (int)((q / W) % H);
+    const float* gq = a.g + q * a.cg + co_t * 32 + l;
+    const float* xq_p = a.x + q * a.cx + (cig * NCI) * 32 + l;
+    const int dy = ky - PAD;
+    const long long row_off = (long long)dy * W * a.cx;
+
+    // The operands of the NEXT pixel pair are fetched before the MFMAs of the current one are issued.  Every lane always loads: a lane
+    // without an operand (tap outside the image, pad pixel, ci tile past the layer's last) reads its channel of pixel 0, which is in
+    // bounds, and the value is replaced by 0 when it is USED -- no branch per load, and no wait for a load inside the iteration that
+    // issued it.  `m`: bit 0 = the g operand is real, bit 1 + j * KS + kx = that x operand is real.
+    auto fetch = [&](float& av, float (&bv)[NCI][KS], unsigned& m) {
+        const bool live = q < p1;                   // (false for the pad pixel of an odd strip and for the fetch past the last pair)
+        const bool yok = live && (unsigned)(yq + dy) < (unsigned)H;
+        av = *(live ? gq : a.g + l);
+        m = live ? 1u : 0u;
+#pragma unroll
+        for (int kx = 0; kx < KS; ++kx) {
+            const bool ok = yok && (unsigned)(xq + kx - PAD) < (unsigned)W;
+            const float* px = xq_p + row_off + (long long)(kx - PAD) * a.cx;
+#pragma unroll
+            for (int j = 0; j < NCI; ++j) {
+                const bool okj = ok && cig * NCI + j < a.nci;
+                bv[j][kx] = *(okj ? px + j * 32 : a.x + l);
+                m |= okj ? 2u << (j * KS + kx) : 0u;
+            }
+        }
+        q += 2; gq += 2 * a.cg; xq_p += 2 * a.cx;
+        xq += 2;
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+            if (xq >= W) { xq -= W; yq = yq + 1 == H ? 0 : yq + 1; }
+    };
+    float av, bv[NCI][KS];
+    unsigned mv;
+    fetch(av, bv, mv);
+    const long long pairs = (p1 - p0 + 1) / 2;
+    for (long long it = 0; it < pairs; ++it) {
+        float an, bn[NCI][KS];
+        unsigned mn;
+        fetch(an, bn, mn);
+        const float ag = mv & 1u ? av : 0.f;
+#pragma unroll
+        for (int kx = 0; kx < KS; ++kx)
+#pragma unroll
+            for (int j = 0; j < NCI; ++j)          // (a ci tile past the layer's last multiplies zeros and is not written back)
+                acc[j][kx] = __builtin_amdgcn_mfma_f32_32x32x2f32(ag, mv & (2u << (j * KS + kx)) ? bv[j][kx] : 0.f, acc[j][kx], 0, 0, 0);
+        av = an; mv = mn;
+#pragma unroll
+        for (int j = 0; j < NCI; ++j)
+#pragma unroll
+            for (int kx = 0; kx < KS; ++kx) bv[j][kx] = bn[j][kx];
+    }
+
+    // D[i][j]: i = co (the A rows), j = ci (the B columns); lane: j = l, i = (e & 3) + 8 * (e >> 2) + 4 * half
+    const size_t tile = (size_t)a.cg * a.cx;
+#pragma unroll
+    for (int j = 0; j < NCI; ++j) {
+        if (cig * NCI + j >= a.nci) continue;
+#pragma unroll
+        for (int kx = 0; kx < KS; ++kx) {
+            float* o = a.ws + ((size_t)blockIdx.y * (KS * KS) + ky * KS + kx) * tile + (size_t)(co_t * 32) * a.cx + (cig * NCI + j) * 32 + l;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) o[(size_t)((e & 3) + 8 * (e >> 2) + 4 * half) * a.cx] = acc[j][kx][e];
+        }
+    }
+}
+
+// dw[co][ci][tap] = the strips' slots added left to right; one thread per real element, consecutive threads = consecutive ci
+__global__ void __launch_bounds__(256) conv_wgrad_combine_kernel(const float* ws, float* dw, int strips, int T, int cout, int cin, int cg, int cx)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)T * cout * cin) return;
+    const int ci = (int)(i % cin), co = (int)((i / cin) % cout), tap = (int)(i / ((long long)cin * cout));
+    const size_t slot = (size_t)T * cg * cx;
+    const float* p = ws + ((size_t)tap * cg + co) * cx + ci;
+    float s = p[0];
+    for (int k = 1; k < strips; ++k) s = s + p[(size_t)k * slot];
+    dw[((size_t)co * cin + ci) * T + tap] = s;
+}
+
+// one thread per (pixel of dy, channel of g's cg): without pool the pixel itself, with pool the 2 x 2 window it came from
+__global__ void __launch_bounds__(256) conv_bwd_mask_kernel(const float* dy, const float* z, int ldz, float* g, int B, int H, int W, int cout, int cg,
+                                                            int relu, int pool)
+{
+    const int Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)B * Ho * Wo * cg) return;
+    const int c = (int)(i % cg);
+    const long long op = i / cg;
+    const int ox = (int)(op % Wo), oy = (int)((op / Wo) % Ho), n = (int)(op / ((long long)Wo * Ho));
+    const bool real = c < cout;
+    const float d = real ? dy[(((size_t)n * cout + c) * Ho + oy) * Wo + ox] : 0.f;
+    if (!pool) {
+        const size_t p = ((size_t)n * H + oy) * W + ox;
+        float v = d;
+        if (real && relu && !(z[p * ldz + c] > 0.f)) v = 0.f;
+        g[p * cg + c] = v;
+        return;
+    }
+    float zz[4] = {0.f, 0.f, 0.f, 0.f};
+    int best = 0;
+    if (real) {
+        float am = 0.f;
+        for (int k = 0; k < 4; ++k) {
+            const size_t p = ((size_t)n * H + 2 * oy + (k >> 1)) * W + 2 * ox + (k & 1);
+            zz[k] = z[p * ldz + c];
+            const float av = relu ? fmaxf(zz[k], 0.f) : zz[k];
+            if (k == 0 || av > am) { am = av; best = k; }      // strictly greater: the first of equal maxima stays
+        }
+    }
+    for (int k = 0; k < 4; ++k) {
+        const size_t p = ((size_t)n * H + 2 * oy + (k >> 1)) * W + 2 * ox + (k & 1);
+        float v = k == best ? d : 0.f;
+        if (real && relu && !(zz[k] > 0.f)) v = 0.f;
+        g[p * cg + c] = v;
+    }
+}
+
+// grid (slots, cg / 32), 256 threads = 8 pixel lanes x 32 channels: float64 sums, the 8 pixel lanes added in lane order through LDS
+__global__ void __launch_bounds__(256) conv_bwd_db_kernel(const float* g, double* part, long long npix, int cg)
+{
+    const int l = threadIdx.x & 31, pr = threadIdx.x >> 5, c = blockIdx.y * 32 + l;
+    double s = 0.0;
+    for (long long p = (long long)blockIdx.x * 8 + pr; p < npix; p += (long long)gridDim.x * 8) s += (double)g[p * cg + c];
+    __shared__ double lds[8][32];
+    lds[pr][l] = s;
+    __syncthreads();
+    if (pr == 0) {
+        double t = lds[0][l];
+        for (int k = 1; k < 8; ++k) t += lds[k][l];
+        part[(size_t)blockIdx.x * cg + c] = t;
+    }
+}
+__global__ void conv_bwd_db_final_kernel(const double* part, float* db, int slots, int cout, int cg)
+{
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= cout) return;
+    double s = 0.0;
+    for (int k = 0; k < slots; ++k) s += part[(size_t)k * cg + c];
+    db[c] = (float)s;
+}
+
+int db_slots(long long npix) { const long long n = (npix + 7) / 8; return n < PMX_DB_SLOTS ? (int)n : PMX_DB_SLOTS; }
+
+}  // namespace
+
+int conv_bwd_mask_launch(const float* dy, const float* z, int ldz, float* g, int B, int H, int W, int cout, int cg, int relu, int pool, hipStream_t stream)
+{
+    PMX_CHECK(cg % 32 == 0 && cg >= cout && (z || !(relu || pool)), PMX_ERR_INVALID, "conv_bwd_mask: bad arguments");
+    const long long n = (long long)B * (pool ? H / 2 : H) * (pool ? W / 2 : W) * cg;
+    hipLaunchKernelGGL(conv_bwd_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, dy, z, ldz, g, B, H, W, cout, cg, relu, pool);
+    PMX_HIP(hipGetLastError());
+    return PMX_OK;
+}
+
+int conv_bwd_db_launch(const float* g, double* part, float* db, long long npix, int cout, int cg, hipStream_t stream)
+{
+    PMX_CHECK(cg % 32 == 0 && cg >= cout && npix >= 1, PMX_ERR_INVALID, "conv_bwd_db: bad arguments");
+    const int slots = db_slots(npix);
+    hipLaunchKernelGGL(conv_bwd_db_kernel, dim3(slots, cg / 32), dim3(256), 0, stream, g, part, npix, cg);
+    PMX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(conv_bwd_db_final_kernel, dim3((cout + 63) / 64), dim3(64), 0, stream, (const double*)part, db, slots, cout, cg);
+    PMX_HIP(hipGetLastError());
+    return PMX_OK;
+}
+
+constexpr long long PMX_WGRAD_WAVES = 2048;      // 256 CUs x 4 SIMDs x 2
+static int wgrad_nci(int ks) { return ks == 7 ? 1 : ks == 3 ? 2 : 4; }
+static int wgrad_units(int cg, int cx, int ks)
+{
+    const int nci = cx / 32, per = wgrad_nci(ks);
+    return (nci + per - 1) / per * ks * (cg / 32);
+}
+
+int conv_wgrad_strips(int B, int H, int cg, int cx, int ks, int forced, int* rows)
+{
+    const long long total = (long long)B * H;
+    long long s0 = forced;
+    if (s0 <= 0) {      // as many strips as give every SIMD of an MI355X two waves (a constant: the order must not depend on the device)
+        const long long units = wgrad_units(cg, cx, ks);
+        s0 = (PMX_WGRAD_WAVES + units - 1) / units;
+    }
+    if (s0 > PMX_WGRAD_MAX_STRIPS) s0 = PMX_WGRAD_MAX_STRIPS;
+    if (s0 > total) s0 = total;
+    if (s0 < 1) s0 = 1;
+    const long long r = (total + s0 - 1) / s0;
+    *rows = (int)r;
+    return (int)((total + r - 1) / r);
+}
+
+int conv_wgrad_launch(const float* g, const float* x, float* ws, float* dw, int B, int H, int W, int cout, int cg, int cin, int cx, int ks, int strips,
+                      int rows, hipStream_t stream)
+{
+    const long long total = (long long)B * H;
+    PMX_CHECK(cg % 32 == 0 && cx % 32 == 0 && cg >= cout && cx >= cin && (ks == 1 || ks == 3 || ks == 7), PMX_ERR_INVALID, "conv_wgrad: bad channels / ksize");
+    PMX_CHECK(rows >= 1 && strips >= 1 && strips <= PMX_WGRAD_MAX_STRIPS && (long long)(strips - 1) * rows < total && (long long)strips * rows >= total,
+              PMX_ERR_INVALID, "conv_wgrad: %d strips of %d rows do not cover %lld rows", strips, rows, total);
+    PMX_CHECK((long long)W * cx * 4 < (1ll << 31), PMX_ERR_INVALID, "conv_wgrad: row of %d x %d floats too long", W, cx);
+    WgradArgs a;
+    a.g = g; a.x = x; a.ws = ws; a.H = H; a.W = W; a.cg = cg; a.cx = cx; a.nco = cg / 32; a.nci = cx / 32;
+    a.n_units = wgrad_units(cg, cx, ks); a.rows = rows; a.total_rows = total;
+    const dim3 grid((a.n_units + 3) / 4, strips);
+    if (ks == 7) hipLaunchKernelGGL((conv_wgrad_kernel<7, 1>), grid, dim3(256), 0, stream, a);
+    else if (ks == 3) hipLaunchKernelGGL((conv_wgrad_kernel<3, 2>), grid, dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((conv_wgrad_kernel<1, 4>), grid, dim3(256), 0, stream, a);
+    PMX_HIP(hipGetLastError());
+    const long long n = (long long)ks * ks * cout * cin;
+    hipLaunchKernelGGL(conv_wgrad_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const float*)ws, dw, strips, ks * ks, cout, cin, cg, cx);
+    PMX_HIP(hipGetLastError());
+    return PMX_OK;
+}

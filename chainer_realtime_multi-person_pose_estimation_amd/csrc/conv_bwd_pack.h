@@ -1,0 +1,17 @@
+/* conv_bwd_pack.h -- host side of pmx_conv2d_backward that needs no device: the layer whose FORWARD is the data gradient.  Plain C, so that
+ * the tests can compile it into a stand-alone program. */
+#ifndef PMX_CONV_BWD_PACK_H
+#define PMX_CONV_BWD_PACK_H
+#include <stddef.h>
+
+/* wt[ci][co][ky][kx] = w[co][ci][ks-1-ky][ks-1-kx]: OIHW (cout, cin, ks, ks) -> OIHW (cin, cout, ks, ks), transposed and rotated by 180
+ * degrees.  A stride-1 convolution of g with wt, padded by ks/2, is the gradient of the convolution with w at its input. */
+static inline void pmx_conv_flip_weights(const float* w, int cout, int cin, int ks, float* wt)
+{
+    for (int co = 0; co < cout; ++co)
+        for (int ci = 0; ci < cin; ++ci)
+            for (int ky = 0; ky < ks; ++ky)
+                for (int kx = 0; kx < ks; ++kx)
+                    wt[(((size_t)ci * cout + co) * ks + ky) * ks + kx] = w[(((size_t)co * cin + ci) * ks + (ks - 1 - ky)) * ks + (ks - 1 - kx)];
+}
+#endif

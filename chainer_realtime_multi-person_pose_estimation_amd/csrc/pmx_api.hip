@@ -6,12 +6,14 @@
 //   of a stage are the two groups (blockIdx.z) of one launch; F.concat (:168,...) is replaced by channel-slice
 //   writes into the 192-channel "cat" buffer (layout in pmx_common.h).
 #include "pmx_ctx.h"
+#include "conv_bwd_pack.h"
 
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
 #include <algorithm>
+#include <functional>
 #include <map>
 
 // ------------------------------------------------------------------------------------------- errors
@@ -495,6 +497,7 @@ extern "C" int pmx_set_option(pmx_ctx* c, const char* key, int value)
     else if (!strcmp(key, "pp_limbs_slices")) c->opt_limbs_slices = value;
     else if (!strcmp(key, "peaks_gpu_branch")) { c->opt_gpu_branch_peaks = value; c->tab_in_h = -1; }
     else if (!strcmp(key, "kp_flip_x")) c->opt_kp_flip_x = value != 0;
+    else if (!strcmp(key, "wgrad_strips")) c->opt_wgrad_strips = value;
     else { pmx_set_error("pmx_set_option: unknown key '%s'", key); return PMX_ERR_INVALID; }
     return PMX_OK;
 }
@@ -1841,5 +1844,124 @@ extern "C" int pmx_conv2d(pmx_ctx* c, const float* x, const float* w, const floa
         hipError_t e = hipMemcpy(y, d_y, ny * 4, hipMemcpyDeviceToHost);
         if (e != hipSuccess) { pmx_set_error("pmx_conv2d: %s", hipGetErrorString(e)); rc = PMX_ERR_HIP; }
     }
+    return rc;
+}
+
+// The backward twin of pmx_conv2d (include/pose_mi355x.h).  z and dx are plans of the dispatcher, each the whole batch as ONE plan as in
+// pmx_conv2d; the mask, the bias gradient and the weight gradient are conv_bwd.hip's launches.  Every buffer is a DevBuf or lives in a
+// PackedLayer: freed on every way out.
+extern "C" int pmx_conv2d_backward(pmx_ctx* c, const float* x, const float* w, const float* bias, const float* dy, int B, int cin, int H, int W,
+                                   int cout, int ks, int relu, int pool, float* dx, float* dw, float* db, float* z, int iters, double* avg_ms3)
+{
+    PMX_CHECK(c && x && w && dy, PMX_ERR_INVALID, "pmx_conv2d_backward: null x, w or dy");
+    PMX_CHECK(dx || dw || db || z, PMX_ERR_INVALID, "pmx_conv2d_backward: all four outputs are NULL");
+    PMX_CHECK(ks == 1 || ks == 3 || ks == 7, PMX_ERR_INVALID, "pmx_conv2d_backward: ksize must be 1, 3 or 7");
+    PMX_CHECK(B >= 1 && cin >= 1 && cout >= 1 && H >= 1 && W >= 1, PMX_ERR_INVALID, "pmx_conv2d_backward: bad shape");
+    PMX_CHECK(!pool || (H % 2 == 0 && W % 2 == 0), PMX_ERR_INVALID, "pmx_conv2d_backward: pool needs even H, W");
+    PMX_CHECK(c->opt_precision == 0, PMX_ERR_STATE,
+              "pmx_conv2d_backward: option \"precision\" is %d; the gradients are fp32 only (the f16 and bf16x3 modes are inference modes)", c->opt_precision);
+    PMX_DEV(c);
+    const bool need_z = z || relu || pool, need_g = dx || dw || db;
+    const int Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W, cg = round_up(cout, 32), cx = round_up(cin, 32), T = ks * ks;
+    const size_t npix = (size_t)B * H * W, nx = npix * cin, nz = npix * cout, ndy = (size_t)B * cout * Ho * Wo, ndw = (size_t)cout * cin * T;
+    if (avg_ms3) avg_ms3[0] = avg_ms3[1] = avg_ms3[2] = 0.0;
+    // L: the layer itself (z); Lt: the layer whose forward is the data gradient
+    PackedLayer L, Lt;
+    std::vector<float> wp, bp;
+    DevBuf<float> d_x, d_xn, d_x32, d_zn, d_z, d_dy, d_g, d_dxn, d_dx, d_ws, d_dw, d_db;
+    DevBuf<double> d_part;
+    int rc;
+    if ((rc = d_x.alloc(nx))) return rc;
+    PMX_HIP(hipMemcpy(d_x, x, nx * 4, hipMemcpyHostToDevice));
+    auto to_nhwc = [&](DevBuf<float>& dst, int ld) -> int {      // x as NHWC with ld channels per pixel, the padding channels zero
+        if (int r = dst.alloc(npix * ld)) return r;
+        PMX_HIP(hipMemsetAsync(dst, 0, npix * ld * 4, c->stream));
+        return launch_nchw_to_nhwc(d_x, dst, B, cin, H, W, ld, 0, c->stream);
+    };
+    ConvPlan pz, pt;
+    if (need_z) {
+        const std::vector<int> cmap = identity_map(cin);
+        L.set = true; L.cin = cin; L.cout = cout; L.ks = ks;
+        L.cin_pad = (int)cmap.size(); L.cout_pad = cout_pad_of(cout); L.nch = L.cin_pad / CK;
+        pack_weights(w, bias, cout, cin, ks, cmap, L.cout_pad, wp, bp);
+        if ((rc = to_nhwc(d_xn, L.cin_pad)) || (rc = L.d_w.alloc(wp.size())) || (rc = L.d_b.alloc(bp.size())) || (rc = d_zn.alloc(nz))) return rc;
+        PMX_HIP(hipMemcpy(L.d_w, wp.data(), wp.size() * 4, hipMemcpyHostToDevice));
+        PMX_HIP(hipMemcpy(L.d_b, bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
+        PMX_HIP(hipMemsetAsync(d_zn, 0xFF, nz * 4, c->stream));
+        if ((rc = plan_conv(c, pz, nullptr, &L, nullptr, d_xn, nullptr, L.cin_pad, d_zn, nullptr, cout, B, H, W, 0, 0, -1))) return rc;
+        if ((rc = launch_plan(c, pz))) return rc;
+    }
+    if (need_g) {
+        if ((rc = d_dy.alloc(ndy)) || (rc = d_g.alloc(npix * cg))) return rc;
+        PMX_HIP(hipMemcpy(d_dy, dy, ndy * 4, hipMemcpyHostToDevice));
+    }
+    if (db && ((rc = d_part.alloc((size_t)PMX_DB_SLOTS * cg)) || (rc = d_db.alloc(cout)))) return rc;
+    if (dx) {
+        const std::vector<int> cmap = identity_map(cout);
+        std::vector<float> wt((size_t)cin * cout * T);
+        pmx_conv_flip_weights(w, cout, cin, ks, wt.data());
+        Lt.set = true; Lt.cin = cout; Lt.cout = cin; Lt.ks = ks;
+        Lt.cin_pad = (int)cmap.size(); Lt.cout_pad = cout_pad_of(cin); Lt.nch = Lt.cin_pad / CK;
+        pack_weights(wt.data(), nullptr, cin, cout, ks, cmap, Lt.cout_pad, wp, bp);
+        if ((rc = Lt.d_w.alloc(wp.size())) || (rc = Lt.d_b.alloc(bp.size())) || (rc = d_dxn.alloc(nx)) || (rc = d_dx.alloc(nx))) return rc;
+        PMX_HIP(hipMemcpy(Lt.d_w, wp.data(), wp.size() * 4, hipMemcpyHostToDevice));
+        PMX_HIP(hipMemcpy(Lt.d_b, bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
+        PMX_HIP(hipMemsetAsync(d_dxn, 0xFF, nx * 4, c->stream));       // poison: an unwritten element is caught by the test
+        // g has cg >= Lt.cin_pad channels per pixel, the padding channels zero
+        if ((rc = plan_conv(c, pt, nullptr, &Lt, nullptr, d_g, nullptr, cg, d_dxn, nullptr, cin, B, H, W, 0, 0, -1))) return rc;
+    }
+    int strips = 0, rows = 0;
+    if (dw) {
+        strips = conv_wgrad_strips(B, H, cg, cx, ks, c->opt_wgrad_strips, &rows);
+        if ((rc = to_nhwc(d_x32, cx)) || (rc = d_ws.alloc((size_t)strips * T * cg * cx)) || (rc = d_dw.alloc(ndw))) return rc;
+        PMX_HIP(hipMemsetAsync(d_dw, 0xFF, ndw * 4, c->stream));
+    }
+    // the three parts; each is timed on its own between two events
+    auto mask_db = [&]() -> int {
+        if (!need_g) return PMX_OK;
+        if (int r = conv_bwd_mask_launch(d_dy, d_zn, cout, d_g, B, H, W, cout, cg, relu, pool, c->stream)) return r;
+        return db ? conv_bwd_db_launch(d_g, d_part, d_db, (long long)npix, cout, cg, c->stream) : PMX_OK;
+    };
+    auto data_grad = [&]() -> int { return dx ? launch_plan(c, pt) : PMX_OK; };
+    auto weight_grad = [&]() -> int {
+        return dw ? conv_wgrad_launch(d_g, d_x32, d_ws, d_dw, B, H, W, cout, cg, cin, cx, ks, strips, rows, c->stream) : PMX_OK;
+    };
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto timed = [&](const std::function<int()>& part, double* ms_out) -> int {
+        PMX_HIP(hipEventRecord(e0, c->stream));
+        int r = PMX_OK;
+        for (int i = 0; i < iters && !r; ++i) r = part();
+        PMX_HIP(hipEventRecord(e1, c->stream));
+        PMX_HIP(hipEventSynchronize(e1));
+        float ms = 0.f;
+        PMX_HIP(hipEventElapsedTime(&ms, e0, e1));
+        if (ms_out) *ms_out = ms / iters;
+        return r;
+    };
+    auto run = [&]() -> int {
+        int r;
+        if ((r = mask_db()) || (r = data_grad()) || (r = weight_grad())) return r;
+        if (iters > 0) {
+            PMX_HIP(hipEventCreate(&e0)); PMX_HIP(hipEventCreate(&e1));
+            if (dx && (r = timed(data_grad, avg_ms3 ? avg_ms3 + 0 : nullptr))) return r;
+            if (dw && (r = timed(weight_grad, avg_ms3 ? avg_ms3 + 1 : nullptr))) return r;
+            if (need_g && (r = timed(mask_db, avg_ms3 ? avg_ms3 + 2 : nullptr))) return r;
+        }
+        if (dx && (r = launch_nhwc_to_nchw(d_dxn, d_dx, B, cin, H, W, cin, 0, c->stream))) return r;
+        if (z) {
+            if ((r = d_z.alloc(nz))) return r;
+            if ((r = launch_nhwc_to_nchw(d_zn, d_z, B, cout, H, W, cout, 0, c->stream))) return r;
+        }
+        PMX_HIP(hipStreamSynchronize(c->stream));
+        if (dx) PMX_HIP(hipMemcpy(dx, d_dx, nx * 4, hipMemcpyDeviceToHost));
+        if (dw) PMX_HIP(hipMemcpy(dw, d_dw, ndw * 4, hipMemcpyDeviceToHost));
+        if (db) PMX_HIP(hipMemcpy(db, d_db, (size_t)cout * 4, hipMemcpyDeviceToHost));
+        if (z) PMX_HIP(hipMemcpy(z, d_z, nz * 4, hipMemcpyDeviceToHost));
+        return PMX_OK;
+    };
+    rc = run();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (rc) (void)hipStreamSynchronize(c->stream);        // nothing in flight may outlive the buffers
     return rc;
 }

@@ -257,6 +257,12 @@ struct pmx_ctx {
     int ls_B = 0, ls_h = 0, ls_w = 0;                     // the targets' batch and network-input size (0: no targets)
     bool ls_have_poses = false;
     int ls_stages = 0;                                    // stages of the last hooked forward (0: none yet)
+    // pmx_loss_grad_enable: d(total_loss)/dy of every stage, [stage][image][map pixel][38 PAF | 19 heat], allocated when first switched on
+    DevBuf<float> ls_grad;
+    int lg_on = 0;
+    int lg_stages = 0, lg_B = 0, lg_fh = 0, lg_fw = 0;    // the hooked forward whose gradients ls_grad holds (lg_stages 0: none)
+    // pmx_conv2d_backward: test-only, S0 of the weight-gradient strips (0: automatic); include/pose_mi355x.h
+    int opt_wgrad_strips = 0;
     // pmx_samples.hip (sample preparation).  sp_host / sp_dev: the per-call block [descriptors | resize tables | host sources], ONE copy from
     // pinned memory (`sp_copied` marks when the host side may be rewritten); sp_a: the resized intermediates of the training samples; sp_out:
     // max_batch x insize x insize x 3 prepared images; sp_mask_raw / sp_mask_tmp / sp_mask: the mask before, between and after the two
@@ -309,5 +315,17 @@ int pmx_loss_set_poses_masked(pmx_ctx* c, const double* poses, const int* n_peop
                               bool mask_on_device, double heat_sigma, double paf_width);
 #define PMX_LOSS_NO_MIXED(c, what) \
     PMX_CHECK(!(c)->ls_on, PMX_ERR_STATE, what ": the validation-loss hook is on (pmx_loss_enable) and covers uniform batches only")
+// conv_bwd.hip: the launches of pmx_conv2d_backward besides the dispatcher's (the entry itself is in pmx_api.hip, next to pmx_conv2d).
+// g and x are NHWC with cg = round_up(cout, 32) and cx = round_up(cin, 32) channels per pixel, the padding channels zero.
+//   mask   g from dy (NCHW, pooled size if pool) and z (NHWC, ldz floats per pixel): include/pose_mi355x.h; writes all cg channels
+//   db     part: slots x cg doubles of workspace; db[co] = (float)(the slots added in slot order)
+//   wgrad  strips of `rows` image rows each (`strips` of them cover B * H rows); ws: strips x ks^2 x cg x cx floats; dw OIHW
+constexpr int PMX_DB_SLOTS = 64;
+int conv_bwd_mask_launch(const float* dy_nchw, const float* z_nhwc, int ldz, float* g, int B, int H, int W, int cout, int cg, int relu, int pool,
+                         hipStream_t stream);
+int conv_bwd_db_launch(const float* g, double* part, float* db, long long npix, int cout, int cg, hipStream_t stream);
+int conv_wgrad_launch(const float* g, const float* x, float* ws, float* dw, int B, int H, int W, int cout, int cg, int cin, int cx, int ks,
+                      int strips, int rows, hipStream_t stream);
+int conv_wgrad_strips(int B, int H, int cg, int cx, int ks, int forced, int* rows);      // S and, in *rows, R of the header's rule
 // c->smoothed (and c->pp.smoothed) at `floats` floats at least, grown to exactly that once the stream no longer uses the old maps
 int pmx_ensure_smoothed(pmx_ctx* c, size_t floats);

@@ -200,6 +200,25 @@ __global__ void __launch_bounds__(256) loss_stage_kernel(LossSrc y, const float*
     if (threadIdx.x < 2) part[blockIdx.x * 2 + threadIdx.x] = ((lds[threadIdx.x][0] + lds[threadIdx.x][1]) + lds[threadIdx.x][2]) + lds[threadIdx.x][3];
 }
 
+// d(total_loss)/dy of one stage (pmx_loss_grad_enable): F.mean_squared_error's backward with gy = 1, one thread per element of
+// grad[image][map pixel][38 | 19]: c * (y - t) as ONE float32 product, +0.0f where the resized mask is set
+__global__ void __launch_bounds__(256) loss_grad_kernel(LossSrc y, const float* tgt, const uint8_t* mask, float* grad, long long npix, int fhw,
+                                                        float c_paf, float c_heat)
+{
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= npix * N_CH) return;
+    const long long pix = e / N_CH;
+    float gv = 0.0f;
+    if (!mask[pix]) {
+        const int ch = (int)(e - pix * N_CH);
+        const long long b = pix / fhw, p = pix - b * fhw;
+        const float yv = ch < PMX_N_PAF ? y.paf[b * y.sb_p + p * y.sp + ch * y.sc] : y.heat[b * y.sb_h + p * y.sp + (ch - PMX_N_PAF) * y.sc];
+        const float d = yv - tgt[e];
+        gv = (ch < PMX_N_PAF ? c_paf : c_heat) * d;
+    }
+    grad[e] = gv;
+}
+
 // out[slot][branch] for the slots [slot0, slot1): the partials of the first `nb` blocks added in block order, / elements; slots >= valid: 0
 __global__ void loss_final_kernel(const double* part, double* out, int slot0, int slot1, int valid, int nb, double n_paf, double n_heat)
 {
@@ -306,13 +325,27 @@ int pmx_loss_stage(pmx_ctx* c, int stage, int B, int fh, int fw)
     snprintf(label, sizeof label, "loss_stage%d|pmx_loss", stage);
     const long long fhw = (long long)fh * fw;
     const LossSrc src = {c->cat + PMX_CAT_PAF, c->cat + PMX_CAT_HEAT, fhw * PMX_CAT_C, fhw * PMX_CAT_C, PMX_CAT_C, 1};
-    return launch_stage(c, label, stage - 1, src, B, fh, fw);
+    if (int rc = launch_stage(c, label, stage - 1, src, B, fh, fw)) return rc;
+    if (!c->lg_on) return PMX_OK;
+    // the stage's gradient, a launch of its own
+    const long long npix = (long long)B * fhw;
+    PMX_CHECK(c->ls_grad.capacity() >= (size_t)(PMX_LOSS_SLOTS - 1) * npix * N_CH, PMX_ERR_STATE, "pmx_loss_stage: no gradient buffer");
+    if (stage == 1) c->lg_stages = 0;                       // until pmx_loss_finish: the buffer is being rewritten
+    snprintf(label, sizeof label, "loss_grad%d|pmx_loss_grad", stage);
+    int rc;
+    if ((rc = pmx_prof_begin(c, label, (double)npix * (3 * N_CH * 4 + 1)))) return rc;
+    hipLaunchKernelGGL(loss_grad_kernel, dim3(blocks_for(npix * N_CH)), dim3(256), 0, c->stream, src, (const float*)c->ls_tgt,
+                       (const uint8_t*)c->ls_mask, c->ls_grad + (size_t)(stage - 1) * npix * N_CH, npix, fh * fw,
+                       (float)(2.0 / ((double)npix * PMX_N_PAF)), (float)(2.0 / ((double)npix * PMX_N_HEAT)));
+    PMX_HIP(hipGetLastError());
+    return pmx_prof_end(c);
 }
 
 int pmx_loss_finish(pmx_ctx* c, int n_stages, int B, int fh, int fw)
 {
     if (int rc = launch_final(c, 0, PMX_LOSS_SLOTS - 1, n_stages, B, fh, fw)) return rc;
     c->ls_stages = n_stages;
+    if (c->lg_on) { c->lg_stages = n_stages; c->lg_B = B; c->lg_fh = fh; c->lg_fw = fw; }
     return PMX_OK;
 }
 
@@ -426,6 +459,43 @@ extern "C" int pmx_loss_enable(pmx_ctx* c, int on)
     PMX_CHECK(c, PMX_ERR_INVALID, "null ctx");
     LOSS_POSENET(c, "pmx_loss_enable");
     c->ls_on = on != 0;
+    return PMX_OK;
+}
+
+extern "C" int pmx_loss_grad_enable(pmx_ctx* c, int on)
+{
+    PMX_CHECK(c, PMX_ERR_INVALID, "null ctx");
+    LOSS_POSENET(c, "pmx_loss_grad_enable");
+    if (on) {           // six stages at the context's capacity, allocated by the first use of the feature
+        PMX_DEV(c);
+        const size_t npix = (size_t)c->max_batch * ((size_t)c->max_h * c->max_w / 64);
+        if (int rc = c->ls_grad.ensure((PMX_LOSS_SLOTS - 1) * npix * N_CH, c->stream)) return rc;
+    }
+    c->lg_on = on != 0;
+    if (!on) c->lg_stages = 0;
+    return PMX_OK;
+}
+
+extern "C" int pmx_get_loss_grads(pmx_ctx* c, int stage, float* gpaf, float* gheat)
+{
+    PMX_CHECK(c, PMX_ERR_INVALID, "null ctx");
+    LOSS_POSENET(c, "pmx_get_loss_grads");
+    PMX_CHECK(stage >= 0 && stage < PMX_LOSS_SLOTS - 1, PMX_ERR_INVALID, "pmx_get_loss_grads: stage %d outside 0..%d", stage, PMX_LOSS_SLOTS - 2);
+    PMX_CHECK(c->lg_on && c->lg_stages > 0, PMX_ERR_STATE,
+              "pmx_get_loss_grads: no forward with the validation-loss hook and the gradients on yet (pmx_loss_enable, pmx_loss_grad_enable)");
+    PMX_CHECK(stage < c->lg_stages, PMX_ERR_STATE, "pmx_get_loss_grads: stage %d: the last hooked forward ran %d stages (option \"stop_stage\")",
+              stage, c->lg_stages);
+    PMX_DEV(c);
+    const size_t fhw = (size_t)c->lg_fh * c->lg_fw, npix = c->lg_B * fhw;
+    std::vector<float> t(npix * N_CH);
+    PMX_HIP(hipMemcpyAsync(t.data(), c->ls_grad + (size_t)stage * npix * N_CH, t.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    PMX_HIP(hipStreamSynchronize(c->stream));
+    for (int b = 0; b < c->lg_B; ++b)
+        for (size_t p = 0; p < fhw; ++p) {
+            const float* q = &t[(b * fhw + p) * N_CH];
+            if (gpaf) for (int ch = 0; ch < PMX_N_PAF; ++ch) gpaf[(b * PMX_N_PAF + ch) * fhw + p] = q[ch];
+            if (gheat) for (int ch = 0; ch < PMX_N_HEAT; ++ch) gheat[(b * PMX_N_HEAT + ch) * fhw + p] = q[PMX_N_PAF + ch];
+        }
     return PMX_OK;
 }
 

@@ -27,13 +27,13 @@ LIB_PATH = os.path.join(CSRC, 'libpose_mi355x.so')
 HEADER = os.path.join(os.path.dirname(HERE), 'include', 'pose_mi355x.h')
 SOURCES = [('pmx_api.hip', []), ('pmx_precise.hip', []), ('pmx_multi.hip', []), ('pmx_precise_images.hip', ['-ffp-contract=off']), ('conv_mfma.hip', []), ('conv_wino.hip', ['-mllvm', '-pragma-unroll-threshold=200000']), ('conv1_wino.hip', []), ('conv_f16.hip', []), ('conv_select.hip', []), ('prep.hip', ['-ffp-contract=off']),
            ('postproc.hip', ['-ffp-contract=off']), ('pmx_boxes.hip', ['-ffp-contract=off']), ('pmx_loss.hip', ['-ffp-contract=off']),
-           ('pmx_samples.hip', ['-ffp-contract=off'])]
+           ('pmx_samples.hip', ['-ffp-contract=off']), ('conv_bwd.hip', ['-ffp-contract=off'])]
 # the opt-in bf16x3 kernels (option "precision" = 1; DESIGN.md 4.1.5: frozen, slower than the fp32 Winograd path) are NOT part of the
 # default library: PMX_BUILD_BF16X3=1 in the environment of the build adds their translation unit (the stamp then differs, so the
 # library is rebuilt when the variable changes)
 if os.environ.get('PMX_BUILD_BF16X3', '') not in ('', '0'):
     SOURCES.append(('conv_bf16x3.hip', []))
-HEADERS = ['pmx_common.h', 'pmx_ctx.h', 'pp_tables.h', 'wino_util.h', 'conv_direct.h', 'pp_smooth.h', HEADER]
+HEADERS = ['pmx_common.h', 'pmx_ctx.h', 'pp_tables.h', 'wino_util.h', 'conv_direct.h', 'pp_smooth.h', 'conv_bwd_pack.h', HEADER]
 
 N_JOINTS, N_LIMBS, N_PAF, N_HEAT = 18, 19, 38, 19
 # the detectors' precision= keyword -> engine option "precision" (include/pose_mi355x.h): fp32 (default), bf16x3 (opt-in build), f16 mode
@@ -317,6 +317,9 @@ def load():
         'pmx_profile_entry': (ci, [vp, ci, C.c_char_p, ci, dp, C.POINTER(C.c_int64), dp, dp]),
         'pmx_profile_issued': (ci, [vp, ci, dp]),
         'pmx_conv2d': (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, ci, dp]),
+        'pmx_conv2d_backward': (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, dp]),
+        'pmx_loss_grad_enable': (ci, [vp, ci]),
+        'pmx_get_loss_grads': (ci, [vp, ci, vp, vp]),
         'pmx_loss_set_poses': (ci, [vp, vp, vp, ci, ci, ci, vp, cd, cd]),
         'pmx_loss_set_targets': (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci]),
         'pmx_loss_enable': (ci, [vp, ci]),
@@ -378,6 +381,8 @@ class Engine(object):
         # host-side record of what was installed, so that a larger context can take over (PoseDetector._grow)
         self._layers, self._options, self._stream_ptr, self._caps_set = {}, {}, None, None
         self._loss_shape = None              # (batch, h, w) of the current loss targets
+        self._loss_on = self._grad_on = False
+        self._grad_shape = None              # (batch, h, w) of the hooked forward whose gradients the context holds
 
     def _check(self, rc):
         if rc != 0:
@@ -455,6 +460,7 @@ class Engine(object):
             self._check(self.lib.pmx_forward_u8(self._ctx, _ptr(imgs), B, H, W, 0))
         self._B = B
         self._fhw = (H // 8, W // 8)
+        self._hooked()
 
     def forward_u8_resized(self, imgs, h, w):
         """imgs (B, H0, W0, 3) uint8 -> cv2.resize(INTER_LINEAR)-equivalent to (h, w) on the device -> forward."""
@@ -464,6 +470,7 @@ class Engine(object):
         self._check(self.lib.pmx_forward_u8_resized(self._ctx, _ptr(imgs), B, H0, W0, int(h), int(w), 0))
         self._B = B
         self._fhw = (int(h) // 8, int(w) // 8)
+        self._hooked()
 
     def get_resized(self, h, w):
         out = np.empty((self._B, int(h), int(w), 3), np.uint8)
@@ -488,6 +495,7 @@ class Engine(object):
         self._check(self.lib.pmx_forward_f32(self._ctx, _ptr(x), B, H, W, 0))
         self._B = B
         self._fhw = (H // 8, W // 8)
+        self._hooked()
 
     def get_maps(self):
         """posenet: (paf, heat); facenet / handnet: heat only (B, 71 | 22, h, w)."""
@@ -753,6 +761,7 @@ class Engine(object):
         self._B = B
         self._fhw = (H // 8, W // 8)
         self._map = (int(map_h), int(map_w))
+        self._hooked()
 
     def set_capacities(self, peaks_per_joint=0, subsets=0, people=0, candidates=0):
         """Pre-size the post-process buffers (0 keeps a value; candidates 0 = LDS store).  Tests shrink them to exercise the
@@ -876,12 +885,33 @@ class Engine(object):
     def loss_enable(self, on=True):
         """on: every uniform forward / detect_batch accumulates the six stage losses against the targets (no synchronisation)."""
         self._check(self.lib.pmx_loss_enable(self._ctx, int(bool(on))))
+        self._loss_on = bool(on)
 
     def loss_get(self):
         """(paf_losses (6,), heat_losses (6,), n_stages) of the last hooked forward (synchronises)."""
         p, h, n = np.zeros(6), np.zeros(6), C.c_int(0)
         self._check(self.lib.pmx_loss_get(self._ctx, p.ctypes.data_as(C.POINTER(C.c_double)), h.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n)))
         return p, h, n.value
+
+    def loss_grad_enable(self, on=True):
+        """on: every hooked uniform forward also writes d(total_loss)/dy of each stage (one more launch per stage; no synchronisation)."""
+        self._check(self.lib.pmx_loss_grad_enable(self._ctx, int(bool(on))))
+        self._grad_on = bool(on)
+        if not on:
+            self._grad_shape = None
+
+    def _hooked(self, hook=False):
+        """after a uniform forward: it was hooked (the targets are those of its batch and size), so the gradients are its"""
+        if self._grad_on and (hook or self._loss_on):
+            self._grad_shape = self._loss_shape
+
+    def loss_grads(self, stage):
+        """(gpaf (B, 38, h/8, w/8), gheat (B, 19, h/8, w/8)) float32: the gradient of the total loss at the outputs of stage + 1
+        (stage 0 .. 5) of the last hooked forward with the gradients on (synchronises)."""
+        B, h, w = self._grad_shape if self._grad_shape is not None else (1, 8, 8)      # (no such forward yet: the library reports the error)
+        gp, gh = np.empty((B, N_PAF, h // 8, w // 8), np.float32), np.empty((B, N_HEAT, h // 8, w // 8), np.float32)
+        self._check(self.lib.pmx_get_loss_grads(self._ctx, int(stage), _ptr(gp), _ptr(gh)))
+        return gp, gh
 
     def loss_current_maps(self):
         """(paf_loss, heat_loss) of the current maps (forward or set_maps) against the targets (synchronises)."""
@@ -903,6 +933,7 @@ class Engine(object):
         self._check(self.lib.pmx_validate_batch(self._ctx, p, B, H, W, on_dev, _ptr(out)))
         self._B = B
         self._fhw = (H // 8, W // 8)
+        self._hooked(True)
         return float(out[0]), out[1:7].copy(), out[7:13].copy()
 
     def labels(self, image=0):
@@ -981,6 +1012,7 @@ class Engine(object):
         self._loss_shape = (B, s, s)
         self._B = B
         self._fhw = (s // 8, s // 8)
+        self._hooked(True)
         return float(out[0]), out[1:7].copy(), out[7:13].copy()
 
     # ---- measurement -------------------------------------------------------------------------------
@@ -1033,3 +1065,31 @@ class Engine(object):
         self._check(self.lib.pmx_conv2d(self._ctx, _ptr(x), _ptr(W), bp, B, ci, H, Wd, co, k, int(relu), int(pool),
                                         _ptr(y), int(iters), C.byref(ms)))
         return (y, ms.value) if iters else y
+
+    def conv2d_backward(self, x, W, b, dy, relu=False, pool=False, want=('dx', 'dw', 'db', 'z'), iters=0):
+        """The gradients of one convolution layer (include/pose_mi355x.h::pmx_conv2d_backward): a dict with the arrays named in `want`
+        ('dx' like x, 'dw' like W, 'db' (cout,), 'z' (B, cout, H, W): the convolution's output before ReLU and pool) and, with iters > 0,
+        'ms' = the mean milliseconds of (data gradient, weight gradient, mask + bias gradient)."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        W = np.ascontiguousarray(W, dtype=np.float32)
+        dy = np.ascontiguousarray(dy, dtype=np.float32)
+        B, ci, H, Wd = x.shape
+        co, ci2, k, k2 = W.shape
+        assert ci == ci2 and k == k2
+        assert dy.shape == (B, co, H // 2 if pool else H, Wd // 2 if pool else Wd), dy.shape
+        bp = None
+        if b is not None:
+            b = np.ascontiguousarray(b, dtype=np.float32)
+            bp = _ptr(b)
+        unknown = set(want) - {'dx', 'dw', 'db', 'z'}
+        if unknown:
+            raise ValueError('conv2d_backward: unknown outputs %r' % sorted(unknown))
+        shapes = {'dx': x.shape, 'dw': W.shape, 'db': (co,), 'z': (B, co, H, Wd)}
+        out = {k_: np.empty(shapes[k_], np.float32) for k_ in want}
+        ptr = lambda k_: _ptr(out[k_]) if k_ in out else None
+        ms = (C.c_double * 3)()
+        self._check(self.lib.pmx_conv2d_backward(self._ctx, _ptr(x), _ptr(W), bp, _ptr(dy), B, ci, H, Wd, co, k, int(relu), int(pool),
+                                                 ptr('dx'), ptr('dw'), ptr('db'), ptr('z'), int(iters), ms))
+        if iters:
+            out['ms'] = tuple(ms)
+        return out

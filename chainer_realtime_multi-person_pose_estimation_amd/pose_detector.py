@@ -580,6 +580,32 @@ class PoseDetector(object):
         return {'val/loss': float(total), 'val/paf': float(paf.sum()), 'val/heat': float(heat.sum()),
                 'paf_stages': [float(v) for v in paf], 'heat_stages': [float(v) for v in heat]}
 
+    def loss_gradients(self, imgs, poses_per_image, ignore_masks=None):
+        """`validation_loss` plus where `loss.backward()` starts (train_coco_pose_estimation.py:90-126): the gradient of the total loss at
+        the twelve stage outputs, on the device in the same forward.  Arguments as validation_loss.  -> its dictionary plus 'paf_grads' /
+        'heat_grads': lists of six (B, 38 | 19, h/8, w/8) float32 arrays.  The gradient's scale 2 / N depends on the batch, so chunks
+        cannot be merged: more images than the engine's batch raise ValueError."""
+        imgs, poses, masks = self._check_validation_args(imgs, poses_per_image, ignore_masks)
+        if self.model is not None:
+            raise RuntimeError('loss_gradients runs the built-in network: not available with a model= callable')
+        if self.engine.weights_missing():
+            raise RuntimeError('PoseDetector has no weights: pass weights_file=, weights= or model=')
+        h, w = imgs[0].shape[:2]
+        self._grow(1, h, w)
+        if len(imgs) > self._cap[0]:
+            raise ValueError('loss_gradients: %d images, the engine holds batches of %d (the gradients of chunks cannot be merged)'
+                             % (len(imgs), self._cap[0]))
+        self.engine.loss_set_poses(poses, h, w, None if masks is None else np.stack(masks), params['heatmap_sigma'], params['paf_sigma'])
+        self.engine.loss_grad_enable(True)
+        try:
+            total, paf, heat = self.engine.validate_batch(np.stack(imgs))
+            grads = [self.engine.loss_grads(s) for s in range(6)]
+        finally:
+            self.engine.loss_grad_enable(False)
+        return {'val/loss': float(total), 'val/paf': float(paf.sum()), 'val/heat': float(heat.sum()),
+                'paf_stages': [float(v) for v in paf], 'heat_stages': [float(v) for v in heat],
+                'paf_grads': [g[0] for g in grads], 'heat_grads': [g[1] for g in grads]}
+
     # ---- sample preparation (reference coco_data_loader.py:61-205, 334-341) ----------------------------------------------------------
     @staticmethod
     def _check_sample_args(imgs, poses_per_image, ignore_masks, insize, mode, records):

@@ -391,6 +391,18 @@ int pmx_get_labels(pmx_ctx* ctx, int image, float* paf, float* heat, int h, int 
 /* parity accessor: the current targets as NCHW float32 (batch x 38 | 19 x h/8 x w/8) and the resized ignore mask (batch x h/8 x w/8, 0 | 1);
  * any pointer may be NULL.  Synchronises. */
 int pmx_get_loss_targets(pmx_ctx* ctx, float* paf_t, float* heat_t, uint8_t* mask);
+/* The gradient of compute_loss at the twelve stage outputs, where loss.backward() starts (train_coco_pose_estimation.py:90-126).  on != 0:
+ * while the loss hook is on as well, every hooked uniform forward enqueues, after each stage's loss launch, one more launch that writes
+ * d(total_loss)/dy of that stage into a context buffer [stage][image][map pixel][38 | 19].  total_loss is the plain sum over stages and
+ * branches (:68), so this is F.mean_squared_error's backward with gy = 1: d = y - t in float32, c = (float)(2.0 / N) with
+ * N = batch * 38 * h/8 * w/8 (PAF) or batch * 19 * h/8 * w/8 (heat), gradient = c * d (one float32 product) where the resized ignore mask
+ * is 0 and +0.0f where it is set (:62-63 make the difference zero there).  The maps and losses of the forward keep their bits.  Off (the
+ * default): nothing more is launched or allocated. */
+int pmx_loss_grad_enable(pmx_ctx* ctx, int on);
+/* the gradients of stage + 1 (stage 0 .. 5) of the last hooked forward, NCHW float32 (batch x 38 | 19 x h/8 x w/8); either pointer may be
+ * NULL.  PMX_ERR_INVALID for a stage outside 0 .. 5; PMX_ERR_STATE before a hooked forward with the gradients on, and for a stage that
+ * forward did not run (option "stop_stage").  Synchronises. */
+int pmx_get_loss_grads(pmx_ctx* ctx, int stage, float* gpaf_nchw, float* gheat_nchw);
 
 /* ---- sample preparation: the pixel side of CocoDataLoader.generate_labels (coco_data_loader.py:72-205, 334-341) ---------------------
  * One call prepares up to max_batch samples from images of different sizes: one launch per step over all samples, every kernel a gather
@@ -508,6 +520,40 @@ int pmx_profile_issued(pmx_ctx* ctx, int i, double* issued_flop_per_launch);
 int pmx_conv2d(pmx_ctx* ctx, const float* x_nchw, const float* w_oihw, const float* bias,
                int batch, int cin, int h, int w, int cout, int ksize, int relu, int pool,
                float* y_nchw, int iters, double* avg_ms);
+
+/* ---- the backward twin of pmx_conv2d: the gradients of one convolution layer ---------------------
+ * Host pointers, float32, the layouts of pmx_conv2d: x (B, cin, h, w), w OIHW, dy (B, cout, h', w') with h' = h/2, w' = w/2 if pool.
+ * Semantics = Chainer's backward of L.Convolution2D(ksize, 1, ksize/2) [+ F.relu] [+ F.max_pooling_2d(2, 2)].  fp32 only.
+ *   z    z = conv(x, w) + bias, computed by ONE plan of the dispatcher with relu = 0, pool = 0 under the context's options; returned in
+ *        z_nchw (B, cout, h, w) when that pointer is given.  a = relu ? max(z, 0) : z.
+ *   g    the gradient at the convolution's output, (B, cout, h, w).  Without pool g = dy.  With pool, dy[n,c,i,j] goes to the FIRST position
+ *        of the window (2i+di, 2j+dj), in the order (0,0), (0,1), (1,0), (1,1), whose a equals the window's maximum; the other three get 0
+ *        (the first-argmax of Chainer and torch).  With relu, g is then zeroed where z > 0 is false (strict, as in gy * (y > 0)).
+ *   dx   (B, cin, h, w): the dispatcher run on g with the packed layer w'[ci][co][ky][kx] = w[co][ci][ks-1-ky][ks-1-kx], no bias, no ReLU,
+ *        no pool.  It takes whatever form the options select for that layer shape, as pmx_conv2d would.
+ *   dw   OIHW: dw[co][ci][ky][kx] = sum over (n, y, x) of g[n,co,y,x] * x[n,ci,y+ky-p,x+kx-p], p = ksize/2, out-of-image taps as zeros.
+ *        One launch of the weight-gradient kernel (csrc/conv_bwd.hip, v_mfma_f32_32x32x2_f32) + one combine launch.  The B*h image rows are
+ *        cut into S strips of R = ceil(B*h / S0) consecutive rows (S0 = option "wgrad_strips" if > 0, else as many as fill the device;
+ *        S0 <= PMX_WGRAD_MAX_STRIPS and <= B*h; S = ceil(B*h / R)); every strip writes its partial sums to its own slot of a workspace of
+ *        S * round_up(cout, 32) * round_up(cin, 32) * ksize^2 floats, i.e. at most PMX_WGRAD_MAX_STRIPS * 4 * round_up(cout, 32) *
+ *        round_up(cin, 32) * ksize^2 bytes (302 MB for a 512 -> 512 3x3 layer, 103 MB for 128 -> 128 7x7).  No floating-point atomics.
+ *        THE ORDER, per (co, ci, ky, kx), is that of this host twin (tests/conv_wgrad_twin.c), bit for bit, whatever the options:
+ *            for strip s = 0 .. S-1:  acc = +0;  for every pixel (n, y, x) of the strip's rows in row-major order:
+ *                                         acc = fmaf(g[n,co,y,x], tap inside the image ? x[n,ci,y+ky-p,x+kx-p] : 0, acc);
+ *                                     if the strip has an odd number of pixels: acc = fmaf(0, 0, acc);      (the MFMA's second K slot)
+ *                                     part[s] = acc;
+ *            dw = part[0];  for s = 1 .. S-1: dw = dw + part[s];                                            (float32 adds, left to right)
+ *   db   db[co] = sum over (n, y, x) of g[n,co,y,x]: float64 sums in fixed slots added in slot order, cast to float32.
+ * Each of dx, dw, db, z may be NULL; a NULL output's work is skipped (z is still computed when relu or pool need it).  avg_ms3 may be NULL;
+ * with iters > 0 it receives the mean time over `iters` repetitions of [0] the data-gradient plan, [1] the weight-gradient launches
+ * (combine included), [2] the mask + bias-gradient launches, each timed on its own between two events (0 for a part that was skipped).
+ * Errors, checked before anything is enqueued (the context stays usable): PMX_ERR_INVALID for a null x, w or dy, for all four outputs NULL,
+ * for ksize outside {1, 3, 7}, for a non-positive shape or pool with odd h or w; PMX_ERR_STATE when option "precision" is not 0 (the f16
+ * and bf16x3 modes are inference modes).  Option "wgrad_strips" (0 = automatic) exists for the tests: it only moves the strip borders. */
+#define PMX_WGRAD_MAX_STRIPS 32
+int pmx_conv2d_backward(pmx_ctx* ctx, const float* x_nchw, const float* w_oihw, const float* bias, const float* dy_nchw,
+                        int batch, int cin, int h, int w, int cout, int ksize, int relu, int pool,
+                        float* dx_nchw, float* dw_oihw, float* db, float* z_nchw, int iters, double* avg_ms3);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,146 @@
+"""CPU: the host side of pmx_conv2d_backward / pmx_get_loss_grads (include/pose_mi355x.h).  The order-defined twin of the weight-gradient
+kernel (tests/conv_wgrad_twin.c) and the NumPy mask / bias-gradient rules (tests/conv_bwd_ref.py) against torch-CPU float64 autograd of
+conv2d [+ relu] [+ max_pool2d(2, 2)]; the C ABI surface; the stand-alone program (twin + the host-side weight repacking), plain and with
+-fsanitize=address,undefined."""
+import subprocess
+
+import numpy as np
+import pytest
+
+import conv_bwd_ref as R
+from conftest import pkg
+
+ENTRIES = ['pmx_conv2d_backward', 'pmx_loss_grad_enable', 'pmx_get_loss_grads']
+
+# (k, B, cin, cout, H, W): small enough that a draw without near-ties exists within a few seeds; odd sizes, a map smaller than the kernel
+SHAPES = [(3, 2, 5, 6, 6, 8), (7, 1, 3, 4, 3, 2), (1, 3, 4, 3, 4, 4), (7, 1, 2, 3, 8, 6), (3, 1, 33, 2, 5, 3)]
+CASES = [(s, relu, pool) for s in SHAPES for relu, pool in ((0, 0), (1, 0), (1, 1)) if not pool or (s[4] % 2 == 0 and s[5] % 2 == 0)]
+MARGIN = 1e-3
+
+
+def _draw(k, B, cin, cout, H, W, relu, pool, seed0):
+    """x, w, b, dy (float32) whose float64 z has no |z| < MARGIN and no pool window whose two largest a differ by less than MARGIN: the
+    next seed is drawn until that holds."""
+    for seed in range(seed0, seed0 + 200):
+        rng = np.random.default_rng(seed)
+        x = rng.standard_normal((B, cin, H, W)).astype('f')
+        w = (rng.standard_normal((cout, cin, k, k)) / np.sqrt(cin * k * k)).astype('f')
+        b = (1.0 + 0.3 * rng.standard_normal(cout)).astype('f')          # most z positive: few windows with nothing above zero
+        dy = rng.standard_normal((B, cout, H // 2 if pool else H, W // 2 if pool else W)).astype('f')
+        ref = R.autograd64(x, w, b, dy, relu, pool)
+        if _margin(ref['z'], relu, pool) >= MARGIN:
+            return x, w, b, dy, ref
+    raise AssertionError('no draw without near-ties in 200 seeds')
+
+
+def _margin(z, relu, pool):
+    m = np.abs(z).min()
+    if pool:
+        a = np.maximum(z, 0) if relu else z
+        B, c, H, W = a.shape
+        win = np.sort(a.reshape(B, c, H // 2, 2, W // 2, 2).transpose(0, 1, 2, 4, 3, 5).reshape(-1, 4), axis=1)
+        m = min(m, (win[:, 3] - win[:, 2]).min())
+    return m
+
+
+@pytest.mark.parametrize('shape,relu,pool', CASES)
+def test_twin_and_mask_rule_match_float64_autograd(shape, relu, pool):
+    k, B, cin, cout, H, W = shape
+    x, w, b, dy, ref = _draw(k, B, cin, cout, H, W, relu, pool, seed0=1000 * k + cin)
+    assert _margin(ref['z'], relu, pool) >= MARGIN          # so the comparison below leaves out no element
+    g = R.mask_rule(dy, ref['z'].astype('f'), relu, pool)
+    dx64, dw64, db64 = R.conv_grads64(g, x, w)
+    # the mask rule: the gradient that reaches the convolution is autograd's, element for element
+    assert np.allclose(dw64, ref['dw'], rtol=1e-12, atol=1e-13) and np.allclose(db64, ref['db'], rtol=1e-12, atol=1e-13)
+    assert np.allclose(dx64, ref['dx'], rtol=1e-12, atol=1e-13)
+    bound = R.dw_bound(g, x, w, ref['dw'])
+    for s0 in (0, 1, 3):
+        dw = R.wgrad_twin(g, x, k, s0)
+        err = np.abs(dw.astype(np.float64) - ref['dw'])
+        assert (err <= bound).all(), (s0, float((err - bound).max()))
+    db = R.db_rule(g)
+    assert (np.abs(db.astype(np.float64) - ref['db']) <= 2.0 ** -23 * np.abs(ref['db'])).all()
+
+
+def test_mask_rule_takes_the_first_of_equal_maxima_and_a_strict_relu():
+    z = np.array([[[[1, 1, -2, 0], [1, 0, 0, -1]]]], 'f')          # window 0: three equal maxima; window 1: nothing above zero
+    dy = np.array([[[[5, 7]]]], 'f')
+    g = R.mask_rule(dy, z, relu=True, pool=True)
+    assert np.array_equal(g, np.array([[[[5, 0, 0, 0], [0, 0, 0, 0]]]], 'f'))
+    g = R.mask_rule(dy, z, relu=False, pool=True)
+    assert np.array_equal(g, np.array([[[[5, 0, 0, 7], [0, 0, 0, 0]]]], 'f'))
+    assert np.array_equal(R.mask_rule(z, z, relu=True, pool=False), z * (z > 0))
+    import torch
+    zt = torch.tensor(z, dtype=torch.float64, requires_grad=True)
+    torch.nn.functional.max_pool2d(torch.relu(zt), 2, 2).backward(torch.tensor(dy, dtype=torch.float64))
+    assert np.array_equal(zt.grad.numpy(), R.mask_rule(dy, z, relu=True, pool=True))
+
+
+def test_flipped_weights_give_the_data_gradient():
+    import torch
+    rng = np.random.default_rng(5)
+    for k, cin, cout in ((3, 4, 5), (7, 2, 3), (1, 6, 2)):
+        x = rng.standard_normal((2, cin, 5, 4))
+        w = rng.standard_normal((cout, cin, k, k))
+        g = rng.standard_normal((2, cout, 5, 4))
+        dx64, _, _ = R.conv_grads64(g, x, w)
+        wt = R.flip_weights(w)
+        assert wt.shape == (cin, cout, k, k)
+        dx = torch.nn.functional.conv2d(torch.tensor(g), torch.tensor(wt), padding=k // 2).numpy()
+        assert np.allclose(dx, dx64, rtol=1e-12, atol=1e-12)
+
+
+def test_strip_rule():
+    assert R.strips_for(3, 46, 32, 32, 3, 5) == (5, 28)              # 138 rows: strips end inside images (28, 56, 84, 112)
+    assert R.strips_for(3, 46, 32, 32, 3, 0) == (28, 5)              # automatic: capped at 32 -> 5 rows -> 28 strips
+    assert R.strips_for(1, 3, 32, 16, 7, 100) == (3, 1)
+    assert R.strips_for(8, 46, 128, 128, 7, 0) == (19, 20)           # 112 units: 19 strips asked -> 20 rows each -> 19 strips
+    rng = np.random.default_rng(3)
+    g = rng.standard_normal((3, 2, 4, 3)).astype('f')
+    x = rng.standard_normal((3, 3, 4, 3)).astype('f')
+    a, b = R.wgrad_twin(g, x, 3, 1), R.wgrad_twin(g, x, 3, 5)
+    assert not np.array_equal(a, b) and np.allclose(a, b, rtol=1e-4, atol=1e-5)
+
+
+def test_loss_gradient_formula_is_the_backward_of_mean_squared_error():
+    import torch
+    rng = np.random.default_rng(11)
+    y = rng.standard_normal((2, 38, 6, 8)).astype('f')
+    t = rng.standard_normal((2, 38, 6, 8)).astype('f')
+    mask = rng.random((2, 6, 8)) < 0.3
+    g = R.loss_grad_formula(y, t, mask, 2)
+    yt = torch.tensor(y, dtype=torch.float64, requires_grad=True)
+    tt = torch.tensor(t, dtype=torch.float64)
+    tt = torch.where(torch.tensor(mask)[:, None], yt.detach(), tt)          # :62-63
+    torch.nn.functional.mse_loss(yt, tt).backward()
+    ref = yt.grad.numpy()
+    assert np.abs(g - ref).max() <= 4 * 2.0 ** -24 * np.abs(ref).max()
+    sel = np.broadcast_to(mask[:, None], g.shape)
+    assert (g[sel] == 0).all() and not np.signbit(g[sel]).any()
+
+
+def test_backward_entries_declared_exported_and_bound(native):
+    """The C ABI surface: the three new symbols are declared in the header, exported by the library and bound with their argument counts."""
+    syms = native.header_symbols()
+    lib = native.load()
+    for s in ENTRIES:
+        assert s in syms, s
+        assert hasattr(lib, s), s
+        assert s in lib._pmx_sig
+    assert len(lib._pmx_sig['pmx_conv2d_backward'][1]) == 19
+    for m in ('conv2d_backward', 'loss_grad_enable', 'loss_grads'):
+        assert callable(getattr(native.Engine, m))
+    assert callable(pkg('pose_detector').PoseDetector.loss_gradients)
+
+
+def test_stand_alone_program_plain_and_sanitized_print_the_same(tmp_path):
+    """A program with its own main (twin + the host-side repacking w -> w'), built plainly and with -fsanitize=address,undefined."""
+    def run(exe):
+        r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr[-2000:])
+        return r.stdout
+    plain = run(R.build_main(tmp_path, 'wgrad_main', []))
+    san = run(R.build_main(tmp_path, 'wgrad_main_san', ['-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-fno-omit-frame-pointer']))
+    assert plain.count('\n') == 18 and plain.encode() == san.encode()
+    lines = plain.splitlines()
+    assert lines[3].startswith('case 1 strips 3 rows 4')
