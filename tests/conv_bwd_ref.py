@@ -1,8 +1,10 @@
 """Host references of pmx_conv2d_backward and pmx_get_loss_grads (include/pose_mi355x.h), shared by the host and the GPU tests:
 the order-defined twin of the weight-gradient kernel (tests/conv_wgrad_twin.c: fmaf, built here with the host compiler and
 -ffp-contract=off), the mask rule (first-argmax, strict z > 0) and the bias-gradient rule in NumPy, the loss-gradient formula in NumPy, and
-the float64 autograd references with the error bound of a float32 sum of products."""
+the float64 autograd references with the error bound of a float32 sum of products; and the integer lattice on which every fp32 summation
+order gives the same bits, with the census of the ties and zeros that a lattice case holds."""
 import ctypes as C
+import functools
 import os
 import shutil
 import subprocess
@@ -152,3 +154,98 @@ def dw_bound(g, x, w, dw64):
     gamma = n * U / (1.0 - n * U)
     _, dwa, _ = conv_grads64(np.abs(g), np.abs(x), w)
     return gamma * dwa + U * np.abs(dw64)
+
+
+# ---- the integer lattice ------------------------------------------------------------------------------------------------------------------
+# x, w, b in {-1, 0, 1} and dy in {-2, -1, 1, 2}, stored as float32.  Every product is an integer of magnitude <= 2, so z (|z| <= cin k k + 1),
+# dx (<= 2 cout k k), dw (<= 2 B H W) and db are integers far below 2^24 and every partial sum of every order is exact: the FMA chains of the
+# direct kernels, their split-K slabs, the weight-gradient MFMAs and any strip count give the same bits.  So do the F(2x2, 3x3) Winograd forms:
+# the transformed weights are multiples of 1/4 (G has halves), the transformed inputs are sums of four lattice values, and multiples of 1/4
+# below 2^22 add exactly.  w keeps only a share `w_density` of its entries: z = b + (a few terms of +-1) is what makes equal maxima, exact
+# zeros and windows with nothing above zero frequent enough to count (lattice_census); x stays dense, so every weight gradient is a full sum.
+LATTICE_FLOOR = 100          # members that every census class of a lattice case must hold
+
+# (k, cin, cout, H, W, B) -> (seed, w_density): fixed.  Chosen on the CPU from the float64 reference alone: dense where the floors hold
+# dense, else thinned until the scarcest class of the shape's windows (B * cout * H * W / 4 of them: only 1140 in the 1x1 / cin 100 case, of
+# which the classes below claim most) clears the floor, at a seed at which it does.  A dense 7x7 / cin 16 layer has |z| ~ 20 and ties in 2 %
+# of its 1536 windows; with 6 of its 784 taps kept, |z| <= 7 and every class has its hundred.
+LATTICE_CASES = {
+    (3, 3, 64, 20, 24, 2): (1, 1.0), (3, 70, 64, 14, 10, 2): (6, 0.03), (1, 4, 38, 8, 12, 2): (5, 1.0), (1, 100, 38, 10, 12, 1): (9, 0.045),
+    (7, 16, 32, 8, 12, 2): (7, 0.008),
+    # the shapes of the forward-option sweep; the third is a 3x3 layer that has a Winograd form, as has the layer of its data gradient
+    (3, 64, 64, 16, 24, 2): (3, 0.12), (7, 32, 128, 12, 46, 2): (3, 0.25), (3, 128, 128, 8, 12, 2): (4, 0.03),
+    (3, 32, 32, 46, 8, 3): (6, 0.12),                                               # the shape of the forced strips
+}
+LATTICE_TIE_SHAPES = list(LATTICE_CASES)[:5]
+LATTICE_SWEEP_SHAPES = list(LATTICE_CASES)[5:8]
+LATTICE_VARIANTS = ((1, 1), (0, 1), (1, 0))          # (relu, pool)
+LATTICE_IDENTITY = (1, 32, 32, 4, 6, 1)          # w = I: dx is g itself
+
+
+def lattice_inputs(k, cin, cout, H, W, B, pool, seed, w_density=1.0):
+    """x, w, b, dy (float32) on the lattice.  dy is drawn last: x, w, b (and so z) are the same with and without pool."""
+    rng = np.random.default_rng(seed)
+    x = rng.integers(-1, 2, (B, cin, H, W)).astype('f')
+    w = (rng.integers(-1, 2, (cout, cin, k, k)) * (rng.random((cout, cin, k, k)) < w_density)).astype('f')
+    b = rng.integers(-1, 2, cout).astype('f')
+    dy = rng.choice(np.array([-2, -1, 1, 2], 'f'), (B, cout, H // 2 if pool else H, W // 2 if pool else W))
+    return x, w, b, dy
+
+
+def _windows(a):
+    """(B, c, H, W) -> (B, c, H / 2, W / 2, 4): the 2 x 2 windows in the order (0,0), (0,1), (1,0), (1,1)"""
+    B, c, H, W = a.shape
+    return a.reshape(B, c, H // 2, 2, W // 2, 2).transpose(0, 1, 2, 4, 3, 5).reshape(B, c, H // 2, W // 2, 4)
+
+
+def lattice_census(z, dy, relu, pool):
+    """What a lattice case holds of the values on which the mask rule can go wrong, counted from the float64 z of the reference (H, W even).
+    With a = relu ? max(z, 0) : z --
+      tied            windows whose maximum of a is attained more than once and is live (> 0 when relu)            } pooled cases
+      tied_not_first  ... those whose first maximum is not at (0,0)                                                 }
+      unique_1/2/3    windows with a unique maximum at (0,1) / (1,0) / (1,1)                                        }
+      zeros           elements with z == 0
+      dead_windows    windows with nothing above zero (relu cases)
+      zero_selected   elements with z == 0 that the pool selects and whose dy is non-zero (pooled relu cases)
+    Only the classes that apply to (relu, pool) are returned."""
+    z = np.asarray(z, dtype=np.float64)
+    out = {'zeros': int((z == 0).sum())}
+    zw = _windows(z)
+    aw = np.maximum(zw, 0.0) if relu else zw
+    m = aw.max(axis=-1)
+    first = aw.argmax(axis=-1)
+    count = (aw == m[..., None]).sum(axis=-1)
+    if pool:
+        tied = (count > 1) & ((m > 0) if relu else True)
+        out['tied'] = int(tied.sum())
+        out['tied_not_first'] = int((tied & (first != 0)).sum())
+        for pos in (1, 2, 3):
+            out['unique_%d' % pos] = int(((count == 1) & (first == pos)).sum())
+    if relu:
+        out['dead_windows'] = int((zw.max(axis=-1) <= 0).sum())
+    if relu and pool:
+        picked = np.take_along_axis(zw, first[..., None], axis=-1)[..., 0]
+        out['zero_selected'] = int(((picked == 0) & (np.asarray(dy) != 0)).sum())
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def lattice_case(shape, relu, pool, identity=False):
+    """(x, w, b, dy, ref, census) of a lattice case: the inputs at the shape's fixed seed and density (identity: w = I, seed 1), ref =
+    autograd64 on the whole chain cast to float32 (exact: every value is an integer below 2^24), census from ref's float64 z.  Computed
+    once per process and shared: callers do not write to it."""
+    k, cin, cout, H, W, B = shape
+    seed, density = (1, 1.0) if identity else LATTICE_CASES[shape]
+    x, w, b, dy = lattice_inputs(k, cin, cout, H, W, B, pool, seed, density)
+    if identity:
+        assert k == 1 and cin == cout
+        w = np.eye(cin, dtype='f').reshape(cin, cin, 1, 1)
+    ref64 = autograd64(x, w, b, dy, relu, pool)
+    census = lattice_census(ref64['z'], dy, relu, pool)
+    ref = {}
+    for name, a in ref64.items():
+        ref[name] = a.astype('f')
+        assert np.array_equal(ref[name].astype(np.float64), a) and np.abs(a).max() < 2.0 ** 22, name
+    for a in (x, w, b, dy) + tuple(ref.values()):
+        a.setflags(write=False)
+    return x, w, b, dy, ref, census

@@ -1,7 +1,8 @@
 """CPU: the host side of pmx_conv2d_backward / pmx_get_loss_grads (include/pose_mi355x.h).  The order-defined twin of the weight-gradient
 kernel (tests/conv_wgrad_twin.c) and the NumPy mask / bias-gradient rules (tests/conv_bwd_ref.py) against torch-CPU float64 autograd of
 conv2d [+ relu] [+ max_pool2d(2, 2)]; the C ABI surface; the stand-alone program (twin + the host-side weight repacking), plain and with
--fsanitize=address,undefined."""
+-fsanitize=address,undefined.  The integer lattice of the exact GPU tests (tests/test_gpu_conv_backward_exact.py): its census floors, torch's
+tie and zero behaviour against the stated mask rule, and the order twins of every kernel form on it."""
 import subprocess
 
 import numpy as np
@@ -74,6 +75,67 @@ def test_mask_rule_takes_the_first_of_equal_maxima_and_a_strict_relu():
     zt = torch.tensor(z, dtype=torch.float64, requires_grad=True)
     torch.nn.functional.max_pool2d(torch.relu(zt), 2, 2).backward(torch.tensor(dy, dtype=torch.float64))
     assert np.array_equal(zt.grad.numpy(), R.mask_rule(dy, z, relu=True, pool=True))
+
+
+# ---- the integer lattice (conv_bwd_ref.py) ------------------------------------------------------------------------------------------------
+LATTICE = [(s, relu, pool) for s in R.LATTICE_TIE_SHAPES for relu, pool in R.LATTICE_VARIANTS]
+LATTICE_OTHER = [s for s in R.LATTICE_CASES if s not in R.LATTICE_TIE_SHAPES]          # the option sweep and the forced strips: relu and pool on
+
+
+@pytest.mark.parametrize('shape,relu,pool', LATTICE + [(s, 1, 1) for s in LATTICE_OTHER])
+def test_lattice_census_floors(shape, relu, pool):
+    """Every class of ties and zeros that applies to the case holds at least LATTICE_FLOOR members at the case's fixed seed."""
+    census = R.lattice_case(shape, relu, pool)[5]
+    want = {'zeros'} | ({'tied', 'tied_not_first', 'unique_1', 'unique_2', 'unique_3'} if pool else set()) | ({'dead_windows'} if relu else set()) \
+        | ({'zero_selected'} if relu and pool else set())
+    assert set(census) == want
+    assert min(census.values()) >= R.LATTICE_FLOOR, census
+
+
+def test_census_counts_a_hand_made_map():
+    #                window 0: tied at (0,0), (0,1)   window 1: unique at (1,1)   window 2: nothing above zero, z == 0 first   window 3: tied, first at (1,0)
+    z = np.array([[[[2, 2, -1, 0, 0, -1, -3, -3], [1, 0, 0, 3, -2, 0, 1, 1]]]], np.float64)
+    dy = np.ones((1, 1, 1, 4), 'f')
+    assert R.lattice_census(z, dy, 1, 1) == dict(zeros=5, tied=2, tied_not_first=1, unique_1=0, unique_2=0, unique_3=1, dead_windows=1, zero_selected=1)
+    assert R.lattice_census(z, dy, 0, 1) == dict(zeros=5, tied=3, tied_not_first=1, unique_1=0, unique_2=0, unique_3=1)
+    assert R.lattice_census(z, dy, 1, 0) == dict(zeros=5, dead_windows=1)
+    assert R.lattice_census(z, 0 * dy, 1, 1)['zero_selected'] == 0
+
+
+@pytest.mark.parametrize('shape,relu,pool', LATTICE)
+def test_lattice_autograd_is_the_mask_rule_and_the_twin(shape, relu, pool):
+    """torch's CPU max-pool and ReLU backward on ties and exact zeros ARE the stated rule (first of equal maxima, strict z > 0): float64
+    autograd of the whole chain equals mask_rule + the plain convolution's autograd exactly, and the order twin of the weight-gradient kernel
+    equals it for every strip count -- on the lattice no order rounds."""
+    x, w, b, dy, ref, _ = R.lattice_case(shape, relu, pool)
+    g = R.mask_rule(dy, ref['z'], relu, pool)
+    dx64, dw64, db64 = R.conv_grads64(g, x, w)
+    assert np.array_equal(dx64, ref['dx']) and np.array_equal(dw64, ref['dw']) and np.array_equal(db64, ref['db'])
+    assert np.array_equal(R.db_rule(g), ref['db'])
+    for s0 in (0, 1, 3):
+        assert np.array_equal(R.wgrad_twin(g, x, shape[0], s0), ref['dw']), s0
+
+
+@pytest.mark.parametrize('relu,pool', R.LATTICE_VARIANTS)
+def test_identity_weights_make_dx_the_masked_gradient(relu, pool):
+    x, w, b, dy, ref, census = R.lattice_case(R.LATTICE_IDENTITY, relu, pool, identity=True)
+    g = R.mask_rule(dy, ref['z'], relu, pool)
+    assert np.array_equal(ref['dx'], g)
+    assert ((ref['dx'] == 0) == (g == 0)).all() and (g == 0).sum() >= R.LATTICE_FLOOR          # closed gates to look at; dy has no zero
+    assert min(census.values()) >= 1, census          # (192 windows: every class is there to be seen element for element, not by the hundred)
+
+
+@pytest.mark.parametrize('shape', R.LATTICE_SWEEP_SHAPES)
+def test_lattice_is_exact_in_the_order_of_every_forward_form(shape):
+    """The premise of the option sweep on the GPU: the order twins of the direct kernels (plain and split-K) and of the Winograd kernel
+    (oracle/conv_fma_ref.py) give the float64 z on the lattice, bit for bit."""
+    from oracle import conv_fma_ref
+    x, w, b, dy, ref, _ = R.lattice_case(shape, 1, 1)
+    for splitk in (1, 2, 3):
+        assert np.array_equal(conv_fma_ref.conv_fma(x, w, b, splitk=splitk), ref['z']), splitk
+    assert np.array_equal(conv_fma_ref.conv_wino(x, w, b), ref['z'])
+    if shape[0] == 7:
+        assert np.array_equal(conv_fma_ref.conv_wino(x, w, b, unit_g=1), ref['z'])
 
 
 def test_flipped_weights_give_the_data_gradient():

@@ -15,7 +15,12 @@ TOL = 2e-5          # tests/test_gpu_conv.py: err <= TOL * max(1, |ref|max)
 # (k, cin, cout, H, W, B, forced strips)
 SHAPES = [(7, 40, 128, 12, 15, 1, 0), (3, 70, 64, 14, 10, 2, 0), (1, 100, 38, 9, 13, 1, 0), (3, 3, 64, 20, 24, 1, 0),
           (7, 185, 128, 6, 9, 2, 0), (1, 128, 19, 8, 6, 1, 0), (7, 16, 32, 3, 2, 1, 0),
-          (3, 32, 32, 46, 8, 3, 5)]          # 138 rows in 5 strips of 28: borders inside images (28, 56, 84, 112) -- and with 3 strips at 46, 92
+          (3, 32, 32, 46, 8, 3, 5),          # 138 rows in 5 strips of 28: borders inside images (28, 56, 84, 112) -- and with 3 strips at 46, 92
+          # the network's channel extremes (512 -> 512 3x3, 128 -> 512 and 512 -> 38 1x1) on the smallest maps; 1x1 with six ci tiles, the
+          # second group of four half empty; maps one pixel wide or high (W = 1: the half-wave's column wraps twice on every step), a map of
+          # one pixel; 21 one-pixel rows in 2 strips of 11: the border falls inside the second image
+          (3, 512, 512, 4, 6, 1, 0), (1, 128, 512, 6, 4, 2, 0), (1, 512, 38, 6, 4, 1, 0), (1, 185, 19, 5, 7, 1, 0),
+          (3, 20, 40, 9, 1, 2, 0), (7, 33, 32, 1, 11, 1, 0), (3, 5, 7, 1, 1, 3, 0), (3, 32, 32, 7, 1, 3, 2)]
 CASES = [(s, relu, pool) for s in SHAPES for relu, pool in ((0, 0), (1, 0), (1, 1)) if not pool or (s[3] % 2 == 0 and s[4] % 2 == 0)]
 
 
