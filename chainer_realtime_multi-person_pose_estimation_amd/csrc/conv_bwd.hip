@@ -26,6 +26,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 struct WgradArgs {
     const float* g; const float* x; float* ws;
     int H, W, cg, cx, nco, nci, n_units, rows;      // nco / nci: 32-channel tiles of g / x; rows: image rows per strip
+    int ldg, ldx;                                   // floats per pixel of g / x (>= cg / cx: the operands may be slices of wider buffers)
     long long total_rows;                           // B * H
 };
 
@@ -53,10 +54,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) c
     // this half-wave's pixel q = p0 + half, p0 + half + 2, ...: (yq, xq) inside its image, tracked without divisions in the loop
     long long q = p0 + half;
     int xq = (int)(q % W), yq = (int)((q / W) % H);
-    const float* gq = a.g + q * a.cg + co_t * 32 + l;
-    const float* xq_p = a.x + q * a.cx + (cig * NCI) * 32 + l;
+    const float* gq = a.g + q * a.ldg + co_t * 32 + l;
+    const float* xq_p = a.x + q * a.ldx + (cig * NCI) * 32 + l;
     const int dy = ky - PAD;
-    const long long row_off = (long long)dy * W * a.cx;
+    const long long row_off = (long long)dy * W * a.ldx;
 
     // The operands of the NEXT pixel pair are fetched before the MFMAs of the current one are issued.  Every lane always loads: a lane
     // without an operand (tap outside the image, pad pixel, ci tile past the layer's last) reads its channel of pixel 0, which is in
@@ -70,7 +71,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) c
 #pragma unroll
         for (int kx = 0; kx < KS; ++kx) {
             const bool ok = yok && (unsigned)(xq + kx - PAD) < (unsigned)W;
-            const float* px = xq_p + row_off + (long long)(kx - PAD) * a.cx;
+            const float* px = xq_p + row_off + (long long)(kx - PAD) * a.ldx;
 #pragma unroll
             for (int j = 0; j < NCI; ++j) {
                 const bool okj = ok && cig * NCI + j < a.nci;
@@ -78,7 +79,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) c
                 m |= okj ? 2u << (j * KS + kx) : 0u;
             }
         }
-        q += 2; gq += 2 * a.cg; xq_p += 2 * a.cx;
+        q += 2; gq += 2 * a.ldg; xq_p += 2 * a.ldx;
         xq += 2;
 #pragma unroll
         for (int t = 0; t < 2; ++t)
@@ -119,14 +120,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) c
     }
 }
 
-// dw[co][ci][tap] = the strips' slots added left to right; one thread per real element, consecutive threads = consecutive ci
-__global__ void __launch_bounds__(256) conv_wgrad_combine_kernel(const float* ws, float* dw, int strips, int T, int cout, int cin, int cg, int cx)
+// dw[co][ci][tap] = the strips' slots added left to right; one thread per real element, consecutive threads = consecutive ci.
+// cin_map (may be null: identity): the channel of x that holds input channel ci of dw -- Mconv1_*: the cat buffer's order -> the reference's
+__global__ void __launch_bounds__(256) conv_wgrad_combine_kernel(const float* ws, float* dw, int strips, int T, int cout, int cin, int cg, int cx,
+                                                                 const int* cin_map)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long long)T * cout * cin) return;
     const int ci = (int)(i % cin), co = (int)((i / cin) % cout), tap = (int)(i / ((long long)cin * cout));
     const size_t slot = (size_t)T * cg * cx;
-    const float* p = ws + ((size_t)tap * cg + co) * cx + ci;
+    const float* p = ws + ((size_t)tap * cg + co) * cx + (cin_map ? cin_map[ci] : ci);
     float s = p[0];
     for (int k = 1; k < strips; ++k) s = s + p[(size_t)k * slot];
     dw[((size_t)co * cin + ci) * T + tap] = s;
@@ -171,11 +174,11 @@ __global__ void __launch_bounds__(256) conv_bwd_mask_kernel(const float* dy, con
 }
 
 // grid (slots, cg / 32), 256 threads = 8 pixel lanes x 32 channels: float64 sums, the 8 pixel lanes added in lane order through LDS
-__global__ void __launch_bounds__(256) conv_bwd_db_kernel(const float* g, double* part, long long npix, int cg)
+__global__ void __launch_bounds__(256) conv_bwd_db_kernel(const float* g, int ldg, double* part, long long npix, int cg)
 {
     const int l = threadIdx.x & 31, pr = threadIdx.x >> 5, c = blockIdx.y * 32 + l;
     double s = 0.0;
-    for (long long p = (long long)blockIdx.x * 8 + pr; p < npix; p += (long long)gridDim.x * 8) s += (double)g[p * cg + c];
+    for (long long p = (long long)blockIdx.x * 8 + pr; p < npix; p += (long long)gridDim.x * 8) s += (double)g[p * ldg + c];
     __shared__ double lds[8][32];
     lds[pr][l] = s;
     __syncthreads();
@@ -207,11 +210,11 @@ int conv_bwd_mask_launch(const float* dy, const float* z, int ldz, float* g, int
     return PMX_OK;
 }
 
-int conv_bwd_db_launch(const float* g, double* part, float* db, long long npix, int cout, int cg, hipStream_t stream)
+int conv_bwd_db_launch(const float* g, int ldg, double* part, float* db, long long npix, int cout, int cg, hipStream_t stream)
 {
-    PMX_CHECK(cg % 32 == 0 && cg >= cout && npix >= 1, PMX_ERR_INVALID, "conv_bwd_db: bad arguments");
+    PMX_CHECK(cg % 32 == 0 && cg >= cout && ldg >= cg && npix >= 1, PMX_ERR_INVALID, "conv_bwd_db: bad arguments");
     const int slots = db_slots(npix);
-    hipLaunchKernelGGL(conv_bwd_db_kernel, dim3(slots, cg / 32), dim3(256), 0, stream, g, part, npix, cg);
+    hipLaunchKernelGGL(conv_bwd_db_kernel, dim3(slots, cg / 32), dim3(256), 0, stream, g, ldg, part, npix, cg);
     PMX_HIP(hipGetLastError());
     hipLaunchKernelGGL(conv_bwd_db_final_kernel, dim3((cout + 63) / 64), dim3(64), 0, stream, (const double*)part, db, slots, cout, cg);
     PMX_HIP(hipGetLastError());
@@ -242,16 +245,17 @@ int conv_wgrad_strips(int B, int H, int cg, int cx, int ks, int forced, int* row
     return (int)((total + r - 1) / r);
 }
 
-int conv_wgrad_launch(const float* g, const float* x, float* ws, float* dw, int B, int H, int W, int cout, int cg, int cin, int cx, int ks, int strips,
-                      int rows, hipStream_t stream)
+int conv_wgrad_launch(const float* g, int ldg, const float* x, int ldx, float* ws, float* dw, int B, int H, int W, int cout, int cg, int cin, int cx,
+                      int ks, int strips, int rows, const int* cin_map, hipStream_t stream)
 {
     const long long total = (long long)B * H;
-    PMX_CHECK(cg % 32 == 0 && cx % 32 == 0 && cg >= cout && cx >= cin && (ks == 1 || ks == 3 || ks == 7), PMX_ERR_INVALID, "conv_wgrad: bad channels / ksize");
+    PMX_CHECK(cg % 32 == 0 && cx % 32 == 0 && cg >= cout && cx >= cin && ldg >= cg && ldx >= cx && (ks == 1 || ks == 3 || ks == 7), PMX_ERR_INVALID,
+              "conv_wgrad: bad channels / ksize");
     PMX_CHECK(rows >= 1 && strips >= 1 && strips <= PMX_WGRAD_MAX_STRIPS && (long long)(strips - 1) * rows < total && (long long)strips * rows >= total,
               PMX_ERR_INVALID, "conv_wgrad: %d strips of %d rows do not cover %lld rows", strips, rows, total);
-    PMX_CHECK((long long)W * cx * 4 < (1ll << 31), PMX_ERR_INVALID, "conv_wgrad: row of %d x %d floats too long", W, cx);
+    PMX_CHECK((long long)W * ldx * 4 < (1ll << 31), PMX_ERR_INVALID, "conv_wgrad: row of %d x %d floats too long", W, ldx);
     WgradArgs a;
-    a.g = g; a.x = x; a.ws = ws; a.H = H; a.W = W; a.cg = cg; a.cx = cx; a.nco = cg / 32; a.nci = cx / 32;
+    a.g = g; a.x = x; a.ws = ws; a.H = H; a.W = W; a.cg = cg; a.cx = cx; a.nco = cg / 32; a.nci = cx / 32; a.ldg = ldg; a.ldx = ldx;
     a.n_units = wgrad_units(cg, cx, ks); a.rows = rows; a.total_rows = total;
     const dim3 grid((a.n_units + 3) / 4, strips);
     if (ks == 7) hipLaunchKernelGGL((conv_wgrad_kernel<7, 1>), grid, dim3(256), 0, stream, a);
@@ -259,7 +263,99 @@ int conv_wgrad_launch(const float* g, const float* x, float* ws, float* dw, int 
     else hipLaunchKernelGGL((conv_wgrad_kernel<1, 4>), grid, dim3(256), 0, stream, a);
     PMX_HIP(hipGetLastError());
     const long long n = (long long)ks * ks * cout * cin;
-    hipLaunchKernelGGL(conv_wgrad_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const float*)ws, dw, strips, ks * ks, cout, cin, cg, cx);
+    hipLaunchKernelGGL(conv_wgrad_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const float*)ws, dw, strips, ks * ks, cout, cin, cg, cx, cin_map);
+    PMX_HIP(hipGetLastError());
+    return PMX_OK;
+}
+
+// ------------------------------------------------------------------------------------------ head backward (pmx_backward.hip)
+// The elementwise steps between the layers of the chain: NHWC in, NHWC out, one thread per (pixel, channel), every sum a float32 add in
+// the order include/pose_mi355x.h (pmx_backward_head) documents.
+namespace {
+
+// g = u where a > 0, +0.0f elsewhere (a null: no ReLU, g = u)
+__global__ void __launch_bounds__(256) bwd_mask_nhwc_kernel(const float* u, int ldu, const float* a, int lda, float* g, int ldg, long long npix, int nch)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= npix * nch) return;
+    const long long p = i / nch;
+    const int ch = (int)(i % nch);
+    const float v = u[p * ldu + ch];
+    g[p * ldg + ch] = !a || a[p * lda + ch] > 0.f ? v : 0.f;
+}
+
+// the gradient at a stage's outputs, [pixel][38 PAF, zeros to 64 | 19 heat, zeros to 128]: loss_grad, then + dx of the next stage's Mconv1_L1,
+// then + dx of its Mconv1_L2 (d0 / d1: NHWC in cat channel order, ldd floats per pixel; both null for the last stage run)
+__global__ void __launch_bounds__(256) bwd_stage_sum_kernel(const float* lg, const float* d0, const float* d1, int ldd, float* g, long long npix)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= npix * 128) return;
+    const long long p = i >> 7;
+    const int ch = (int)(i & 127), k = ch & 63, heat = ch >> 6;
+    float v = 0.f;
+    if (k < (heat ? PMX_N_HEAT : PMX_N_PAF)) {
+        v = lg[p * (PMX_N_PAF + PMX_N_HEAT) + (heat ? PMX_N_PAF : 0) + k];
+        if (d0) {
+            const int cc = (heat ? PMX_CAT_HEAT : PMX_CAT_PAF) + k;
+            v = v + d0[p * ldd + cc];
+            v = v + d1[p * ldd + cc];
+        }
+    }
+    g[i] = v;
+}
+
+// the gradient at the feature map, [pixel][128]: first ? a + b : (fg + a) + b
+__global__ void __launch_bounds__(256) bwd_feat_sum_kernel(float* fg, const float* a, const float* b, int ld, int first, long long npix)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= npix * 128) return;
+    const long long p = i >> 7;
+    const int ch = (int)(i & 127);
+    const float va = a[p * ld + ch], vb = b[p * ld + ch];
+    fg[i] = first ? va + vb : (fg[i] + va) + vb;
+}
+
+__global__ void __launch_bounds__(256) bwd_copy_cols_kernel(const float* src, int lds, float* dst, int ldd, long long npix, int nch)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= npix * nch) return;
+    const long long p = i / nch;
+    const int ch = (int)(i % nch);
+    dst[p * ldd + ch] = src[p * lds + ch];
+}
+
+unsigned bwd_blocks(long long n) { return (unsigned)((n + 255) / 256); }
+
+}  // namespace
+
+int bwd_mask_nhwc_launch(const float* u, int ldu, const float* a, int lda, float* g, int ldg, long long npix, int nch, hipStream_t stream)
+{
+    PMX_CHECK(u && g && npix >= 1 && nch >= 1 && ldu >= nch && ldg >= nch && (!a || lda >= nch), PMX_ERR_INVALID, "bwd_mask_nhwc: bad arguments");
+    hipLaunchKernelGGL(bwd_mask_nhwc_kernel, dim3(bwd_blocks(npix * nch)), dim3(256), 0, stream, u, ldu, a, lda, g, ldg, npix, nch);
+    PMX_HIP(hipGetLastError());
+    return PMX_OK;
+}
+
+int bwd_stage_sum_launch(const float* lg, const float* d0, const float* d1, int ldd, float* g, long long npix, hipStream_t stream)
+{
+    PMX_CHECK(lg && g && npix >= 1 && !d0 == !d1 && (!d0 || ldd >= PMX_CAT_C), PMX_ERR_INVALID, "bwd_stage_sum: bad arguments");
+    hipLaunchKernelGGL(bwd_stage_sum_kernel, dim3(bwd_blocks(npix * 128)), dim3(256), 0, stream, lg, d0, d1, ldd, g, npix);
+    PMX_HIP(hipGetLastError());
+    return PMX_OK;
+}
+
+int bwd_feat_sum_launch(float* fg, const float* a, const float* b, int ld, int first, long long npix, hipStream_t stream)
+{
+    PMX_CHECK(fg && a && b && npix >= 1 && ld >= 128, PMX_ERR_INVALID, "bwd_feat_sum: bad arguments");
+    hipLaunchKernelGGL(bwd_feat_sum_kernel, dim3(bwd_blocks(npix * 128)), dim3(256), 0, stream, fg, a, b, ld, first, npix);
+    PMX_HIP(hipGetLastError());
+    return PMX_OK;
+}
+
+int bwd_copy_cols_launch(const float* src, int lds, float* dst, int ldd, long long npix, int nch, hipStream_t stream)
+{
+    PMX_CHECK(src && dst && npix >= 1 && nch >= 1 && lds >= nch && ldd >= nch, PMX_ERR_INVALID, "bwd_copy_cols: bad arguments");
+    hipLaunchKernelGGL(bwd_copy_cols_kernel, dim3(bwd_blocks(npix * nch)), dim3(256), 0, stream, src, lds, dst, ldd, npix, nch);
     PMX_HIP(hipGetLastError());
     return PMX_OK;
 }

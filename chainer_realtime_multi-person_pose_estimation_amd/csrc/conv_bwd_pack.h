@@ -14,4 +14,17 @@ static inline void pmx_conv_flip_weights(const float* w, int cout, int cin, int 
                 for (int kx = 0; kx < ks; ++kx)
                     wt[(((size_t)ci * cout + co) * ks + ky) * ks + kx] = w[(((size_t)co * cin + ci) * ks + (ks - 1 - ky)) * ks + (ks - 1 - kx)];
 }
+
+/* The same layer for a convolution whose input is read from a buffer in ANOTHER channel order (Mconv1_*: the concat buffer), so that its data
+ * gradient comes out in the buffer's order: wt[k][co][ky][kx] = w[co][map[k]][ks-1-ky][ks-1-kx] for the nmap buffer channels k, map[k] = the
+ * input channel of w that buffer channel k holds, or -1 for a pad channel, whose nmap-th row is all +0.0f.  wt: OIHW (nmap, cout, ks, ks). */
+static inline void pmx_conv_flip_weights_mapped(const float* w, int cout, int cin, int ks, const int* map, int nmap, float* wt)
+{
+    for (int k = 0; k < nmap; ++k)
+        for (int co = 0; co < cout; ++co)
+            for (int ky = 0; ky < ks; ++ky)
+                for (int kx = 0; kx < ks; ++kx)
+                    wt[(((size_t)k * cout + co) * ks + ky) * ks + kx] =
+                        map[k] >= 0 && map[k] < cin ? w[(((size_t)co * cin + map[k]) * ks + (ks - 1 - ky)) * ks + (ks - 1 - kx)] : 0.0f;
+}
 #endif

@@ -527,6 +527,7 @@ extern "C" int pmx_set_layer(pmx_ctx* c, const char* name, const float* w, const
     // the bf16x3 pack (1.5x the fp32 weights) and the Winograd pack (16/9 x for 3x3, 81/49 x for 7x7) are derived from the packed fp32
     // weights on first use (ensure_*_pack): a context that never runs those kernels neither holds nor computes them
     L.d_w3.reset(); L.d_w16.reset(); L.d_ww.reset();
+    if ((size_t)it->second < c->bw.tl.size()) c->bw.tl[it->second] = PackedLayer();      // the data-gradient pack of the old weights
     L.set = true; L.cin = cin; L.cout = cout; L.ks = ks;
     L.cin_pad = (int)cmap.size(); L.cout_pad = cpad; L.nch = L.cin_pad / CK;
     return PMX_OK;
@@ -884,7 +885,7 @@ static int run_conv(pmx_ctx* c, const char* label, PackedLayer* L0, PackedLayer*
 // (else, or with option fuse_pairs = 0, as two run_conv launches through `mid`): bit-identical either way
 static int run_pair(pmx_ctx* c, const char* labelA, const char* labelB, PackedLayer* a0, PackedLayer* a1, PackedLayer* b0, PackedLayer* b1,
                     const float* in0, const float* in1, int lda, float* mid0, float* mid1, int ldm, float* out0, float* out1, int ldc, int B,
-                    int H, int W, int reluB, int level = -1)
+                    int H, int W, int reluB, int level = -1, bool keep_mid = false)      // keep_mid: `mid` must hold the middle activation: two launches
 {
     const PackedLayer& LA = *a0;
     const PackedLayer& LB = *b0;
@@ -892,7 +893,7 @@ static int run_pair(pmx_ctx* c, const char* labelA, const char* labelB, PackedLa
     // (heterogeneous forward: a 1x1 layer only sees pixels -- the segments' maps are one run of seg_pix[level] pixels)
     const bool seg = !c->segs.empty() && level >= 0;
     const long long npix = seg ? c->seg_pix[level] : (long long)B * H * W;
-    const bool ok = c->opt_fuse_pairs && c->opt_kernel_gen >= 6 && LA.ks == 1 && LB.ks == 1 && LA.cin_pad == 128 && LB.cin == LA.cout &&
+    const bool ok = !keep_mid && c->opt_fuse_pairs && c->opt_kernel_gen >= 6 && LA.ks == 1 && LB.ks == 1 && LA.cin_pad == 128 && LB.cin == LA.cout &&
                     conv_pair_supported(LA.cin, LA.cout, LB.cout_pad) && (groups == 1 || b1->cout_pad == LB.cout_pad);
     int rc;
     PMX_CHECK(ok || !seg, PMX_ERR_INVALID, "heterogeneous forward: the 1x1 pair %s + %s has no fused form", labelA, labelB);
@@ -997,7 +998,8 @@ static int run_conv1(pmx_ctx* c, int B, int H, int W)
 // conv1_1 ... conv4_2, the VGG stem all three networks share (CocoPoseNet.py:136-149, FaceNet.py:78-92): act1 and act0 in turn, the three
 // F.max_pooling_2d fused into conv1_2, conv2_2, conv3_4; the result (1/8 resolution, 512 channels) in act1
 // (level = the resolution level of the layer's input, read only by a heterogeneous forward: pmx_multi.hip)
-static int run_stem(pmx_ctx* c, int B, int H, int W)
+// (last_out: where conv4_2 writes instead -- a retaining forward, pmx_backward_enable)
+static int run_stem(pmx_ctx* c, int B, int H, int W, float* last_out = nullptr)
 {
     static const struct { const char* name; int cin, cout, level, pool; } stem[] = {
         {"conv2_1", 64, 128, 1, 0}, {"conv2_2", 128, 128, 1, 1}, {"conv3_1", 128, 256, 2, 0}, {"conv3_2", 256, 256, 2, 0},
@@ -1007,6 +1009,7 @@ static int run_stem(pmx_ctx* c, int B, int H, int W)
     float* out = c->act0;
     for (const auto& s : stem) {
         if (rc) break;
+        if (last_out && &s == &stem[7]) out = last_out;
         rc = run_conv(c, s.name, &c->layers[c->index.at(s.name)], nullptr, in, nullptr, s.cin, out, nullptr, s.cout, B, H >> s.level, W >> s.level, 1, s.pool, s.level);
         std::swap(in, out);
     }
@@ -1065,49 +1068,68 @@ int pmx_forward_from_in16(pmx_ctx* c, int B, int H, int W)
     int rc;
     const int H8 = H / 8, W8 = W / 8;
 #define RUN(...) do { if ((rc = run_conv(c, __VA_ARGS__))) return rc; } while (0)
-    // stem (CocoPoseNet.py:136-151)
-    // (the last argument = the resolution level, read only by a heterogeneous forward: pmx_multi.hip)
-    if ((rc = run_stem(c, B, H, W))) return rc;
-    RUN("conv4_3_CPM", L("conv4_3_CPM"), nullptr, c->act1, nullptr, 512, c->act0, nullptr, 256, B, H8, W8, 1, 0, 3);
-    RUN("conv4_4_CPM", L("conv4_4_CPM"), nullptr, c->act0, nullptr, 256, c->cat + PMX_CAT_FEAT, nullptr, PMX_CAT_C, B, H8, W8, 1, 0, 3);
-    // stage 1 (CocoPoseNet.py:154-165); L1 = PAF branch, L2 = heat-map branch
-    float* cat = c->cat;
-    RUN("conv5_1_CPM", L("conv5_1_CPM_L1"), L("conv5_1_CPM_L2"), cat, cat, PMX_CAT_C, c->brA, c->brA + 128, 256, B, H8, W8, 1, 0, 3);
-    RUN("conv5_2_CPM", L("conv5_2_CPM_L1"), L("conv5_2_CPM_L2"), c->brA, c->brA + 128, 256, c->brB, c->brB + 128, 256, B, H8, W8, 1, 0, 3);
-    RUN("conv5_3_CPM", L("conv5_3_CPM_L1"), L("conv5_3_CPM_L2"), c->brB, c->brB + 128, 256, c->brA, c->brA + 128, 256, B, H8, W8, 1, 0, 3);
-    // conv5_4 (128 -> 512, ReLU) -> conv5_5 (512 -> 38 | 19): one launch
-    if ((rc = run_pair(c, "conv5_4_CPM", "conv5_5_CPM", L("conv5_4_CPM_L1"), L("conv5_4_CPM_L2"), L("conv5_5_CPM_L1"), L("conv5_5_CPM_L2"),
-                       c->brA, c->brA + 128, 256, c->brT, c->brT + 512, 1024, cat + PMX_CAT_PAF, cat + PMX_CAT_HEAT, PMX_CAT_C, B, H8, W8, 0, 3)))
-        return rc;
     // validation-loss hook (pmx_loss.hip; uniform batches): the stage's outputs lie in the cat slices until the next stage's last launch
     const bool hook = c->ls_on && c->segs.empty();
+    // retention (pmx_backward_enable; include/pose_mi355x.h): every layer writes where the backward will read it -- the slots of c->bw.act
+    // instead of act1 / act0 / brA / brB / brT (same leading dimensions: same plans, same bits), the 1x1 pairs unfused
+    BwState& bw = c->bw;
+    const bool keep = bw.on && hook && c->lg_on && c->opt_precision == 0;
+    bw.valid = bw.done = false;
+    const long long npix8 = (long long)B * H8 * W8;
+    PMX_CHECK(!keep || (size_t)npix8 <= bw.cap_px, PMX_ERR_CAPACITY, "forward: %lld map pixels, the backward store holds %zu", npix8, bw.cap_px);
+    auto slot = [&](int k, float* else_) { return keep ? bw.act + bw.slot[k].a_off : else_; };
+    float* const x42 = slot(PMX_BW_X42, c->act1);
+    float* const a43 = slot(PMX_BW_C43, c->act0);
+    auto keep_stage = [&](int k) {      // the stage's 57 (64) channels of cat -> the store
+        return keep ? bwd_copy_cols_launch(c->cat + PMX_CAT_PAF, PMX_CAT_C, bw.act + bw.slot[k].a_off, 64, npix8, 64, c->stream) : PMX_OK;
+    };
+    // stem (CocoPoseNet.py:136-151)
+    // (the last argument = the resolution level, read only by a heterogeneous forward: pmx_multi.hip)
+    if ((rc = run_stem(c, B, H, W, keep ? x42 : nullptr))) return rc;
+    RUN("conv4_3_CPM", L("conv4_3_CPM"), nullptr, x42, nullptr, 512, a43, nullptr, 256, B, H8, W8, 1, 0, 3);
+    RUN("conv4_4_CPM", L("conv4_4_CPM"), nullptr, a43, nullptr, 256, c->cat + PMX_CAT_FEAT, nullptr, PMX_CAT_C, B, H8, W8, 1, 0, 3);
+    // stage 1 (CocoPoseNet.py:154-165); L1 = PAF branch, L2 = heat-map branch
+    float* cat = c->cat;
+    float* const s51 = slot(PMX_BW_S1 + 0, c->brA);
+    float* const s52 = slot(PMX_BW_S1 + 1, c->brB);
+    float* const s53 = slot(PMX_BW_S1 + 2, c->brA);
+    float* const s54 = slot(PMX_BW_S1 + 3, c->brT);
+    RUN("conv5_1_CPM", L("conv5_1_CPM_L1"), L("conv5_1_CPM_L2"), cat, cat, PMX_CAT_C, s51, s51 + 128, 256, B, H8, W8, 1, 0, 3);
+    RUN("conv5_2_CPM", L("conv5_2_CPM_L1"), L("conv5_2_CPM_L2"), s51, s51 + 128, 256, s52, s52 + 128, 256, B, H8, W8, 1, 0, 3);
+    RUN("conv5_3_CPM", L("conv5_3_CPM_L1"), L("conv5_3_CPM_L2"), s52, s52 + 128, 256, s53, s53 + 128, 256, B, H8, W8, 1, 0, 3);
+    // conv5_4 (128 -> 512, ReLU) -> conv5_5 (512 -> 38 | 19): one launch
+    if ((rc = run_pair(c, "conv5_4_CPM", "conv5_5_CPM", L("conv5_4_CPM_L1"), L("conv5_4_CPM_L2"), L("conv5_5_CPM_L1"), L("conv5_5_CPM_L2"),
+                       s53, s53 + 128, 256, s54, s54 + 512, 1024, cat + PMX_CAT_PAF, cat + PMX_CAT_HEAT, PMX_CAT_C, B, H8, W8, 0, 3, keep)))
+        return rc;
     int n_stages = 1;
     if (hook && (rc = pmx_loss_stage(c, 1, B, H8, W8))) return rc;
+    if ((rc = keep_stage(PMX_BW_S1 + 4))) return rc;
     // stages 2-6 (CocoPoseNet.py:168-260)
     char n1[48], n2[48], m1[48], m2[48], lab[48], lab2[48];
     for (int s = 2; s <= 6 && s <= c->opt_stop_stage; ++s) {
+        const float* in = cat;
         for (int i = 1; i <= 5; ++i) {
             snprintf(n1, sizeof n1, "Mconv%d_stage%d_L1", i, s);
             snprintf(n2, sizeof n2, "Mconv%d_stage%d_L2", i, s);
             snprintf(lab, sizeof lab, "Mconv%d_stage%d", i, s);
-            const float *in0, *in1; float *o0, *o1; int lda;
-            if (i == 1) { in0 = cat; in1 = cat; lda = PMX_CAT_C; }
-            else if (i % 2 == 0) { in0 = c->brA; in1 = c->brA + 128; lda = 256; }
-            else { in0 = c->brB; in1 = c->brB + 128; lda = 256; }
-            if (i % 2 == 1) { o0 = c->brA; o1 = c->brA + 128; }
-            else { o0 = c->brB; o1 = c->brB + 128; }
-            RUN(lab, L(n1), L(n2), in0, in1, lda, o0, o1, 256, B, H8, W8, 1, 0, 3);
+            float* const o = slot(PMX_BW_M(s, i), i % 2 == 1 ? c->brA : c->brB);
+            if (i == 1) RUN(lab, L(n1), L(n2), cat, cat, PMX_CAT_C, o, o + 128, 256, B, H8, W8, 1, 0, 3);
+            else RUN(lab, L(n1), L(n2), in, in + 128, 256, o, o + 128, 256, B, H8, W8, 1, 0, 3);
+            in = o;
         }
         // Mconv6 (1x1 128 -> 128, ReLU; reads Mconv5's output in brA) -> Mconv7 (1x1 128 -> 38 | 19, into the cat slices): one launch
         snprintf(n1, sizeof n1, "Mconv6_stage%d_L1", s); snprintf(n2, sizeof n2, "Mconv6_stage%d_L2", s);
         snprintf(m1, sizeof m1, "Mconv7_stage%d_L1", s); snprintf(m2, sizeof m2, "Mconv7_stage%d_L2", s);
         snprintf(lab, sizeof lab, "Mconv6_stage%d", s); snprintf(lab2, sizeof lab2, "Mconv7_stage%d", s);
-        if ((rc = run_pair(c, lab, lab2, L(n1), L(n2), L(m1), L(m2), c->brA, c->brA + 128, 256, c->brB, c->brB + 128, 256,
-                           cat + PMX_CAT_PAF, cat + PMX_CAT_HEAT, PMX_CAT_C, B, H8, W8, 0, 3))) return rc;
+        float* const m6 = slot(PMX_BW_M(s, 6), c->brB);
+        if ((rc = run_pair(c, lab, lab2, L(n1), L(n2), L(m1), L(m2), in, in + 128, 256, m6, m6 + 128, 256,
+                           cat + PMX_CAT_PAF, cat + PMX_CAT_HEAT, PMX_CAT_C, B, H8, W8, 0, 3, keep))) return rc;
         n_stages = s;
         if (hook && (rc = pmx_loss_stage(c, s, B, H8, W8))) return rc;
+        if ((rc = keep_stage(PMX_BW_M(s, 7)))) return rc;
     }
     if (hook && (rc = pmx_loss_finish(c, n_stages, B, H8, W8))) return rc;
+    if (keep) { bw.valid = true; bw.stages = n_stages; bw.B = B; bw.fh = H8; bw.fw = W8; }
 #undef RUN
     c->maps_valid = true; c->maps_external = false;
     c->cur_B = B; c->cur_fh = H8; c->cur_fw = W8;
@@ -1920,11 +1942,11 @@ extern "C" int pmx_conv2d_backward(pmx_ctx* c, const float* x, const float* w, c
     auto mask_db = [&]() -> int {
         if (!need_g) return PMX_OK;
         if (int r = conv_bwd_mask_launch(d_dy, d_zn, cout, d_g, B, H, W, cout, cg, relu, pool, c->stream)) return r;
-        return db ? conv_bwd_db_launch(d_g, d_part, d_db, (long long)npix, cout, cg, c->stream) : PMX_OK;
+        return db ? conv_bwd_db_launch(d_g, cg, d_part, d_db, (long long)npix, cout, cg, c->stream) : PMX_OK;
     };
     auto data_grad = [&]() -> int { return dx ? launch_plan(c, pt) : PMX_OK; };
     auto weight_grad = [&]() -> int {
-        return dw ? conv_wgrad_launch(d_g, d_x32, d_ws, d_dw, B, H, W, cout, cg, cin, cx, ks, strips, rows, c->stream) : PMX_OK;
+        return dw ? conv_wgrad_launch(d_g, cg, d_x32, cx, d_ws, d_dw, B, H, W, cout, cg, cin, cx, ks, strips, rows, nullptr, c->stream) : PMX_OK;
     };
     hipEvent_t e0 = nullptr, e1 = nullptr;
     auto timed = [&](const std::function<int()>& part, double* ms_out) -> int {
@@ -1964,4 +1986,52 @@ extern "C" int pmx_conv2d_backward(pmx_ctx* c, const float* x, const float* w, c
     if (e1) (void)hipEventDestroy(e1);
     if (rc) (void)hipStreamSynchronize(c->stream);        // nothing in flight may outlive the buffers
     return rc;
+}
+
+// ---------------------------------------------------------------------------- for pmx_backward.hip
+int pmx_run_conv(pmx_ctx* c, const char* label, PackedLayer* L0, PackedLayer* L1, const float* in0, const float* in1, int lda, float* out0,
+                 float* out1, int ldc, int B, int H, int W, int relu)
+{
+    return run_conv(c, label, L0, L1, in0, in1, lda, out0, out1, ldc, B, H, W, relu, 0);
+}
+
+// The layer whose forward is the data gradient of table layer `layer` (conv_bwd_pack.h), packed like any layer.  The OIHW weights come
+// back from the layer's device pack (the context keeps no host copy), in the reference's input order.  Its input is the layer's g: `cout`
+// channels padded with zeros to 64 for the 38 / 19-channel outputs, so that both branches of a launch have the same chunk count.  Its output
+// has the layer's input channels -- for Mconv1_* the 192 channels of the concat buffer in the buffer's order, the pad channels zero.
+int pmx_bw_transposed_pack(pmx_ctx* c, int layer)
+{
+    PMX_CHECK(layer >= 0 && (size_t)layer < c->layers.size() && (size_t)layer < c->bw.tl.size(), PMX_ERR_INVALID, "backward pack: layer %d", layer);
+    PackedLayer& Lt = c->bw.tl[layer];
+    if (Lt.set) return PMX_OK;
+    const PackedLayer& L = c->layers[layer];
+    PMX_CHECK(L.set, PMX_ERR_WEIGHTS, "backward pack: layer '%s' has no weights", c->table[layer].name.c_str());
+    const int T = L.ks * L.ks;
+    const bool cat_in = c->kind == NET_POSE && L.cin == 185;
+    const std::vector<int> cmap = cat_in ? concat_map() : identity_map(L.cin);
+    std::vector<float> wp((size_t)T * L.nch * L.cout_pad * CK), w((size_t)L.cout * L.cin * T);
+    PMX_HIP(hipMemcpy(wp.data(), L.d_w, wp.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (int tap = 0; tap < T; ++tap)
+        for (int k = 0; k < L.cin_pad; ++k) {
+            if (cmap[k] < 0) continue;
+            for (int n = 0; n < L.cout; ++n)
+                w[((size_t)n * L.cin + cmap[k]) * T + tap] = wp[(((size_t)tap * L.nch + k / CK) * L.cout_pad + n) * CK + k % CK];
+        }
+    const int t_cout = cat_in ? PMX_CAT_C : L.cin;
+    std::vector<float> wt((size_t)t_cout * L.cout * T), bp;
+    if (cat_in) pmx_conv_flip_weights_mapped(w.data(), L.cout, L.cin, L.ks, cmap.data(), PMX_CAT_C, wt.data());
+    else pmx_conv_flip_weights(w.data(), L.cout, L.cin, L.ks, wt.data());
+    std::vector<int> gmap(L.cout < 64 ? 64 : round_up(L.cout, CK), -1);
+    for (int i = 0; i < L.cout; ++i) gmap[i] = i;
+    PackedLayer P;
+    P.cin = L.cout; P.cout = t_cout; P.ks = L.ks;
+    P.cin_pad = (int)gmap.size(); P.cout_pad = cout_pad_of(t_cout); P.nch = P.cin_pad / CK;
+    pack_weights(wt.data(), nullptr, t_cout, L.cout, L.ks, gmap, P.cout_pad, wp, bp);
+    int rc;
+    if ((rc = P.d_w.alloc(wp.size())) || (rc = P.d_b.alloc(bp.size()))) return rc;
+    PMX_HIP(hipMemcpy(P.d_w, wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice));
+    PMX_HIP(hipMemcpy(P.d_b, bp.data(), bp.size() * sizeof(float), hipMemcpyHostToDevice));
+    P.set = true;
+    Lt = std::move(P);
+    return PMX_OK;
 }

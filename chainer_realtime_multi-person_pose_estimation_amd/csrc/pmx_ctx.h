@@ -114,6 +114,40 @@ struct SegGeo { int n, H, W, mh, mw; };
 // one post-process launch set of the current results: a uniform batch is one call (base 0), a mixed batch one per segment
 struct PPCall { PPMaps maps; PPTables tab; int base, B, map_h, map_w; double img_len; bool has_scale; int limbs_slices; };
 
+// Head backward (pmx_backward.hip; include/pose_mi355x.h: pmx_backward_head).  The 82 layers after conv4_2 share 42 SLOTS of one layout,
+// used twice: `act` (the retained outputs a) and `g` (the masked gradients).  A slot holds both branches of a layer pair side by side,
+// [pixel][L1 | L2], as the forward's brA / brB / brT do, so a retaining forward writes its outputs straight into `act`.
+//   PMX_BW_C43       conv4_3_CPM, 256 floats per pixel            PMX_BW_C44  conv4_4_CPM: g only (128); a = channels 0 .. 127 of c->cat
+//   PMX_BW_S1 + i    conv5_{i+1}_CPM, i = 0 .. 2: 2 x 128; i = 3: 2 x 512; i = 4 (conv5_5_CPM): a stage output
+//   PMX_BW_M(s, i)   Mconv{i}_stage{s}: i = 1 .. 6: 2 x 128; i = 7: a stage output
+//   PMX_BW_X42       conv4_2's output, 512 (a only)
+// stage output: a = [38 PAF, 2 zeros | 19 heat, 5 zeros] (channels 128 .. 191 of c->cat, copied after the stage's loss launch); g =
+// [38 PAF, zeros to 64 | 19 heat, zeros to 128] (every branch's g starts at a multiple of 32 floats and is zero-padded to one)
+enum { PMX_BW_C43 = 0, PMX_BW_C44 = 1, PMX_BW_S1 = 2, PMX_BW_M2 = 7, PMX_BW_X42 = 42, PMX_BW_SLOTS = 43 };
+#define PMX_BW_M(s, i) (PMX_BW_M2 + ((s) - 2) * 7 + (i) - 1)
+struct BwSlot { size_t a_off = 0, g_off = 0; int lda = 0, ldg = 0; };
+struct BwState {
+    int on = 0;                                           // pmx_backward_enable
+    bool valid = false;                                   // the last forward retained (cleared by every other forward)
+    bool done = false;                                    // pmx_backward_head ran for it
+    int stages = 0, B = 0, fh = 0, fw = 0;                // ... its stages and shape
+    size_t cap_px = 0;                                    // pixels (images x h/8 x w/8) the stores hold
+    BwSlot slot[PMX_BW_SLOTS];
+    DevBuf<float> act, g;                                 // the two stores
+    DevBuf<float> grad;                                   // dw (OIHW) | db of every layer: grad_off[layer], then cout * cin * ks^2 floats further
+    std::vector<size_t> grad_off;                         // by index into c->table (trunk layers: unused)
+    DevBuf<float> u;                                      // dx of the layer just run = the upstream gradient of the one before: [pixel][<= 1024]
+    DevBuf<float> dcat;                                   // dx of Mconv1_stage{s}_L1 | _L2 in concat-buffer order: [pixel][2 x 192]
+    DevBuf<float> fg;                                     // the running sum at the feature map: [pixel][128]
+    DevBuf<float> trunk;                                  // dx of conv4_3_CPM: [pixel][512]
+    DevBuf<float> ws;                                     // weight-gradient workspace (grown before a backward is enqueued)
+    DevBuf<double> part;                                  // bias-gradient slots
+    DevBuf<int> cat_of_ref;                               // concat-buffer channel of the reference's input channel 0 .. 184 of Mconv1_*
+    std::vector<PackedLayer> tl;                          // per layer: the pack whose forward is the data gradient (set = built)
+    int slot_layer[PMX_BW_SLOTS][2] = {};                 // table index of the slot's L1 / L2 layer (one-branch slots: both the same; X42: conv4_2)
+    std::vector<int> layer_slot;                          // by table index: slot * 2 + branch, -1 for the trunk layers before conv4_2
+};
+
 // ------------------------------------------------------------------------------------------- context
 struct pmx_ctx {
     // heterogeneous forward / post-process state
@@ -272,6 +306,7 @@ struct pmx_ctx {
     DevBuf<char> sp_dev, sp_const;
     DevBuf<uint8_t> sp_a, sp_out, sp_mask_raw, sp_mask_tmp, sp_mask;
     int sp_n = 0, sp_insize = 0;                          // the prepared samples (0: none)
+    BwState bw;                                           // pmx_backward.hip
 };
 constexpr int PMX_LOSS_SLOTS = 7;
 constexpr int PMX_LOSS_MAX_BLOCKS = 256;
@@ -323,9 +358,25 @@ int pmx_loss_set_poses_masked(pmx_ctx* c, const double* poses, const int* n_peop
 constexpr int PMX_DB_SLOTS = 64;
 int conv_bwd_mask_launch(const float* dy_nchw, const float* z_nhwc, int ldz, float* g, int B, int H, int W, int cout, int cg, int relu, int pool,
                          hipStream_t stream);
-int conv_bwd_db_launch(const float* g, double* part, float* db, long long npix, int cout, int cg, hipStream_t stream);
-int conv_wgrad_launch(const float* g, const float* x, float* ws, float* dw, int B, int H, int W, int cout, int cg, int cin, int cx, int ks,
-                      int strips, int rows, hipStream_t stream);
+// (ldg / ldx: floats per pixel of g / x, >= cg / cx -- the operands may be slices of wider buffers; cin_map, device memory or null: the
+// channel of x that holds input channel ci of dw)
+int conv_bwd_db_launch(const float* g, int ldg, double* part, float* db, long long npix, int cout, int cg, hipStream_t stream);
+int conv_wgrad_launch(const float* g, int ldg, const float* x, int ldx, float* ws, float* dw, int B, int H, int W, int cout, int cg, int cin, int cx,
+                      int ks, int strips, int rows, const int* cin_map, hipStream_t stream);
 int conv_wgrad_strips(int B, int H, int cg, int cx, int ks, int forced, int* rows);      // S and, in *rows, R of the header's rule
+// conv_bwd.hip: the elementwise steps of the head backward, NHWC (the sums' orders: include/pose_mi355x.h, pmx_backward_head)
+//   mask       g = u where a > 0, +0.0f elsewhere, nch channels of every pixel (a null: g = u)
+//   stage_sum  g [pixel][128] = loss_grad (+ d0 + d1: dx of the next stage's Mconv1_L1 / _L2 in concat-buffer order, both null for the last stage)
+//   feat_sum   fg [pixel][128] = first ? a + b : (fg + a) + b
+//   copy_cols  nch channels of every pixel from one leading dimension to another
+int bwd_mask_nhwc_launch(const float* u, int ldu, const float* a, int lda, float* g, int ldg, long long npix, int nch, hipStream_t stream);
+int bwd_stage_sum_launch(const float* lg, const float* d0, const float* d1, int ldd, float* g, long long npix, hipStream_t stream);
+int bwd_feat_sum_launch(float* fg, const float* a, const float* b, int ld, int first, long long npix, hipStream_t stream);
+int bwd_copy_cols_launch(const float* src, int lds, float* dst, int ldd, long long npix, int nch, hipStream_t stream);
+// pmx_api.hip, for pmx_backward.hip: one layer (pair) through the forward's dispatcher (run_conv: plan_conv + launch_plan), and the pack of
+// c->bw.tl[layer] built from the layer's device weights (no-op when built)
+int pmx_run_conv(pmx_ctx* c, const char* label, PackedLayer* L0, PackedLayer* L1, const float* in0, const float* in1, int lda, float* out0,
+                 float* out1, int ldc, int B, int H, int W, int relu);
+int pmx_bw_transposed_pack(pmx_ctx* c, int layer);
 // c->smoothed (and c->pp.smoothed) at `floats` floats at least, grown to exactly that once the stream no longer uses the old maps
 int pmx_ensure_smoothed(pmx_ctx* c, size_t floats);

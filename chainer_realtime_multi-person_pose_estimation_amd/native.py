@@ -27,7 +27,8 @@ LIB_PATH = os.path.join(CSRC, 'libpose_mi355x.so')
 HEADER = os.path.join(os.path.dirname(HERE), 'include', 'pose_mi355x.h')
 SOURCES = [('pmx_api.hip', []), ('pmx_precise.hip', []), ('pmx_multi.hip', []), ('pmx_precise_images.hip', ['-ffp-contract=off']), ('conv_mfma.hip', []), ('conv_wino.hip', ['-mllvm', '-pragma-unroll-threshold=200000']), ('conv1_wino.hip', []), ('conv_f16.hip', []), ('conv_select.hip', []), ('prep.hip', ['-ffp-contract=off']),
            ('postproc.hip', ['-ffp-contract=off']), ('pmx_boxes.hip', ['-ffp-contract=off']), ('pmx_loss.hip', ['-ffp-contract=off']),
-           ('pmx_samples.hip', ['-ffp-contract=off']), ('conv_bwd.hip', ['-ffp-contract=off'])]
+           ('pmx_samples.hip', ['-ffp-contract=off']), ('conv_bwd.hip', ['-ffp-contract=off']),
+           ('pmx_backward.hip', ['-ffp-contract=off'])]
 # the opt-in bf16x3 kernels (option "precision" = 1; DESIGN.md 4.1.5: frozen, slower than the fp32 Winograd path) are NOT part of the
 # default library: PMX_BUILD_BF16X3=1 in the environment of the build adds their translation unit (the stamp then differs, so the
 # library is rebuilt when the variable changes)
@@ -320,6 +321,11 @@ def load():
         'pmx_conv2d_backward': (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, dp]),
         'pmx_loss_grad_enable': (ci, [vp, ci]),
         'pmx_get_loss_grads': (ci, [vp, ci, vp, vp]),
+        'pmx_backward_enable': (ci, [vp, ci]),
+        'pmx_backward_head': (ci, [vp]),
+        'pmx_get_layer_grad': (ci, [vp, C.c_char_p, vp, vp]),
+        'pmx_get_trunk_grad': (ci, [vp, vp]),
+        'pmx_get_retained': (ci, [vp, C.c_char_p, ci, vp]),
         'pmx_loss_set_poses': (ci, [vp, vp, vp, ci, ci, ci, vp, cd, cd]),
         'pmx_loss_set_targets': (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci]),
         'pmx_loss_enable': (ci, [vp, ci]),
@@ -912,6 +918,47 @@ class Engine(object):
         gp, gh = np.empty((B, N_PAF, h // 8, w // 8), np.float32), np.empty((B, N_HEAT, h // 8, w // 8), np.float32)
         self._check(self.lib.pmx_get_loss_grads(self._ctx, int(stage), _ptr(gp), _ptr(gh)))
         return gp, gh
+
+    # ---- head backward (include/pose_mi355x.h: pmx_backward_*) -----------------------------------------------------------
+    TRUNK_LAYERS = ('conv1_1', 'conv1_2', 'conv2_1', 'conv2_2', 'conv3_1', 'conv3_2', 'conv3_3', 'conv3_4', 'conv4_1', 'conv4_2')
+
+    def head_layers(self, n_stages=6):
+        """Names of the layers after conv4_2 that a forward of n_stages stages runs, in the forward's order (the weights' order)."""
+        def stage(name):
+            return 0 if name.startswith('conv4') else 1 if name.startswith('conv5') else int(name.split('stage')[1][0])
+        return [n for n in self._layers if n not in self.TRUNK_LAYERS and stage(n) <= n_stages]
+
+    def backward_enable(self, on=True):
+        """on: allocates the activation and gradient stores at the context's capacity; from then on a hooked uniform fp32 forward with the
+        loss gradients on retains the outputs of the 82 layers after conv4_2.  off: frees the stores."""
+        self._check(self.lib.pmx_backward_enable(self._ctx, int(bool(on))))
+
+    def backward_head(self):
+        """Enqueue the backward of the 82 layers after conv4_2 for the last retained forward (no synchronisation)."""
+        self._check(self.lib.pmx_backward_head(self._ctx))
+
+    def layer_grad(self, name):
+        """(dW OIHW, db) float32 of one layer after the last backward_head (synchronises)."""
+        W, b = self._layers.get(name, (np.empty((1, 1, 1, 1), np.float32), np.empty(1, np.float32)))      # (unknown: the library reports it)
+        dw, db = np.empty(W.shape, np.float32), np.empty(b.shape, np.float32)
+        self._check(self.lib.pmx_get_layer_grad(self._ctx, name.encode(), _ptr(dw), _ptr(db)))
+        return dw, db
+
+    def trunk_grad(self):
+        """(B, 512, h/8, w/8) float32: the gradient at conv4_2's output, where a trunk backward starts (synchronises)."""
+        B, h, w = self._grad_shape if self._grad_shape is not None else (1, 8, 8)
+        g = np.empty((B, 512, h // 8, w // 8), np.float32)
+        self._check(self.lib.pmx_get_trunk_grad(self._ctx, _ptr(g)))
+        return g
+
+    def retained(self, name, which=0):
+        """Parity accessor: (B, cout, h/8, w/8) float32, which = 0 the retained output of layer `name` ('conv4_2' included), 1 its masked
+        gradient after backward_head (synchronises)."""
+        B, h, w = self._grad_shape if self._grad_shape is not None else (1, 8, 8)
+        cout = self._layers[name][0].shape[0] if name in self._layers else 1
+        out = np.empty((B, cout, h // 8, w // 8), np.float32)
+        self._check(self.lib.pmx_get_retained(self._ctx, name.encode(), int(which), _ptr(out)))
+        return out
 
     def loss_current_maps(self):
         """(paf_loss, heat_loss) of the current maps (forward or set_maps) against the targets (synchronises)."""

@@ -606,6 +606,38 @@ class PoseDetector(object):
                 'paf_stages': [float(v) for v in paf], 'heat_stages': [float(v) for v in heat],
                 'paf_grads': [g[0] for g in grads], 'heat_grads': [g[1] for g in grads]}
 
+    def head_gradients(self, imgs, poses_per_image, ignore_masks=None):
+        """`loss_gradients` plus the backward of the 82 layers after conv4_2 -- the layers the reference updates while conv1_1 .. conv4_2 are
+        frozen (train_coco_pose_estimation.py:219-225) -- on the device.  Arguments as validation_loss.  -> loss_gradients' dictionary plus
+        'grads': {layer name: (dW OIHW, db)} float32 and 'trunk_grad': (B, 512, h/8, w/8), the gradient at conv4_2's output.  More images
+        than the engine's batch raise ValueError."""
+        imgs, poses, masks = self._check_validation_args(imgs, poses_per_image, ignore_masks)
+        if self.model is not None:
+            raise RuntimeError('head_gradients runs the built-in network: not available with a model= callable')
+        if self.engine.weights_missing():
+            raise RuntimeError('PoseDetector has no weights: pass weights_file=, weights= or model=')
+        h, w = imgs[0].shape[:2]
+        self._grow(1, h, w)
+        if len(imgs) > self._cap[0]:
+            raise ValueError('head_gradients: %d images, the engine holds batches of %d (the gradients of chunks cannot be merged)'
+                             % (len(imgs), self._cap[0]))
+        eng = self.engine
+        eng.loss_set_poses(poses, h, w, None if masks is None else np.stack(masks), params['heatmap_sigma'], params['paf_sigma'])
+        eng.loss_grad_enable(True)
+        try:
+            eng.backward_enable(True)
+            total, paf, heat = eng.validate_batch(np.stack(imgs))
+            eng.backward_head()
+            grads = [eng.loss_grads(s) for s in range(6)]
+            layer_grads = {name: eng.layer_grad(name) for name in eng.head_layers()}
+            trunk = eng.trunk_grad()
+        finally:
+            eng.backward_enable(False)
+            eng.loss_grad_enable(False)
+        return {'val/loss': float(total), 'val/paf': float(paf.sum()), 'val/heat': float(heat.sum()),
+                'paf_stages': [float(v) for v in paf], 'heat_stages': [float(v) for v in heat],
+                'paf_grads': [g[0] for g in grads], 'heat_grads': [g[1] for g in grads], 'grads': layer_grads, 'trunk_grad': trunk}
+
     # ---- sample preparation (reference coco_data_loader.py:61-205, 334-341) ----------------------------------------------------------
     @staticmethod
     def _check_sample_args(imgs, poses_per_image, ignore_masks, insize, mode, records):

@@ -555,6 +555,54 @@ int pmx_conv2d_backward(pmx_ctx* ctx, const float* x_nchw, const float* w_oihw, 
                         int batch, int cin, int h, int w, int cout, int ksize, int relu, int pool,
                         float* dx_nchw, float* dw_oihw, float* db, float* z_nchw, int iters, double* avg_ms3);
 
+/* ---- head backward: the gradients of the 82 layers after conv4_2 ------------------------------------
+ * conv4_3_CPM, conv4_4_CPM, the ten layers of stage 1 and the seventy of stages 2 - 6: the layers the reference updates while conv1_1 ..
+ * conv4_2 are frozen (train_coco_pose_estimation.py:219-225).  All live at h/8 x w/8.  posenet contexts, uniform batches, fp32.
+ *
+ * pmx_backward_enable(on != 0) allocates, for max_batch images of max_h x max_w (PMX_ERR_CAPACITY if the device refuses; about 3 GB of
+ * activations at 32 x 368 x 368, as much again for the gradients), and from then on a uniform fp32 forward that runs with the loss hook AND
+ * the loss gradients on RETAINS what the backward reads: the post-ReLU output of each of the 82 layers and conv4_2's output, NHWC, written
+ * by the layers' own launches into the store (never copied afterwards), with two exceptions --
+ *   the feature map     conv4_4_CPM's output stays where every stage reads it, in channels 0 .. 127 of the concat buffer;
+ *   the stage outputs   every stage overwrites the PAF / heat slices of the concat buffer, so after each stage's loss launch one launch copies
+ *                       the 64 channels [38 PAF, 2 zeros | 19 heat, 5 zeros] to the store (the 57 channels per stage; the backward copies
+ *                       them back before the weight gradient of Mconv1_stage{s+1} reads the buffer, and the last stage's at its end, so the
+ *                       current maps stay those of the forward).
+ * The two 1x1 layers that end a stage run as two launches while retaining (the fused launch does not store the middle activation); the
+ * maps, the losses and the loss gradients keep their bits.  With retention off nothing more is launched or allocated.  A ReLU gate is read
+ * from the stored output: a > 0 exactly when z > 0.
+ *
+ * pmx_backward_head enqueues the backward of the last retained forward on the context's stream, in reverse layer order, for the stages
+ * that forward ran (option "stop_stage").  Per layer, with u the gradient at its output:
+ *   g    = u where a > 0, +0.0f elsewhere (Mconv7_* and conv5_5_CPM_*: no ReLU, g = u); kept, one slot per layer
+ *   db   as pmx_conv2d_backward
+ *   dw   as pmx_conv2d_backward (the same kernel, the same order per element, strips cut from the batch * h/8 image rows; option
+ *        "wgrad_strips"), OIHW; for Mconv1_* in the REFERENCE's input order 38 PAF, 19 heat, 128 feature
+ *   dx   the dispatcher on g with the transposed, 180-degree-rotated pack (built on the host on the first backward, kept per layer, dropped
+ *        by pmx_set_layer), two branches per launch where the forward has two; the packs of Mconv1_* write concat-buffer order, zeros in
+ *        the pad channels
+ * THE SUMS.  Every step is one float32 add, left to right:
+ *   stage output   u(stage s PAF | heat) = loss_grad[s] + dx(Mconv1_stage{s+1}_L1) + dx(Mconv1_stage{s+1}_L2); the last stage run: loss_grad alone
+ *   feature map    u(conv4_4_CPM) = the contributions in the order the backward produces them: Mconv1_stage6_L1, Mconv1_stage6_L2,
+ *                  Mconv1_stage5_L1, ..., Mconv1_stage2_L2, conv5_1_CPM_L1, conv5_1_CPM_L2 (the stages that ran), starting from the first
+ *   elsewhere      u = dx of the one layer that reads the output
+ * No floating-point atomics: every run gives the same bits.  The chain ends with dx of conv4_3_CPM, the gradient at conv4_2's output,
+ * where a trunk backward would start (pmx_get_trunk_grad).  Asynchronous.
+ * PMX_ERR_STATE, before anything is enqueued: no retained forward yet, a forward since then that was not retained (any forward without
+ * retention, the hook or the loss gradients), option "precision" != 0, a facenet / handnet context. */
+int pmx_backward_enable(pmx_ctx* ctx, int on);
+int pmx_backward_head(pmx_ctx* ctx);
+/* dw (OIHW, the layer's shape as in pmx_set_layer) and db (cout) of one of the 82 layers after the last pmx_backward_head; either pointer
+ * may be NULL (both: PMX_ERR_INVALID).  PMX_ERR_INVALID for an unknown name or a trunk layer, PMX_ERR_STATE without a backward and for a
+ * layer of a stage that "stop_stage" cut off.  Synchronises. */
+int pmx_get_layer_grad(pmx_ctx* ctx, const char* name, float* dw_oihw, float* db);
+/* the gradient at conv4_2's output, NCHW float32 batch x 512 x h/8 x w/8.  Synchronises. */
+int pmx_get_trunk_grad(pmx_ctx* ctx, float* g_nchw);
+/* parity accessor: which = 0: the retained output a of layer `name` (after a retained forward; `name` may be "conv4_2"), which = 1: its
+ * masked gradient g (after pmx_backward_head; not for "conv4_2"); NCHW float32 batch x cout x h/8 x w/8.  Errors as pmx_get_layer_grad;
+ * which outside {0, 1}: PMX_ERR_INVALID.  Synchronises. */
+int pmx_get_retained(pmx_ctx* ctx, const char* name, int which, float* out_nchw);
+
 #ifdef __cplusplus
 }
 #endif
