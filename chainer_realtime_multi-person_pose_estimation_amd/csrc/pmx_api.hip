@@ -87,7 +87,7 @@ static std::vector<LayerDesc> make_layer_table()   // models/CocoPoseNet.py:26-1
 
 
 
-static int cout_pad_of(int cout) { return cout <= 64 ? 64 : round_up(cout, 128); }
+static int cout_pad_of(int cout) { return pmx_pk_cout_pad(cout); }
 
 // pack OIHW -> [tap][chunk][cout_pad][CK]; cin_map[k] = source input channel of packed channel k (or -1 = zero)
 static void pack_weights(const float* w, const float* bias, int cout, int cin, int ks, const std::vector<int>& cin_map,
@@ -101,9 +101,8 @@ static void pack_weights(const float* w, const float* bias, int cout, int cin, i
         for (int k = 0; k < cin_pad; ++k) {
             const int src = cin_map[k];
             if (src < 0) continue;
-            const int ch = k / CK, c = k % CK;
             for (int n = 0; n < cout; ++n)
-                wp[(((size_t)tap * nch + ch) * cout_pad + n) * CK + c] = w[((size_t)n * cin + src) * T + tap];
+                wp[pmx_pk_direct(tap, k, n, nch, cout_pad)] = w[pmx_pk_oihw(n, src, tap, cin, T)];
         }
 }
 
@@ -134,11 +133,11 @@ static void pack_wino(const std::vector<float>& wp, int ks, int nch16, int cout_
     const int nplanes = ks == 3 ? 16 : 81;      // 7x7: 64 (four 3x3 sub-kernels) + 8 (row 6: two 1x3, G g) + 8 (column 6: two 3x1) + 1 (tap (6, 6))
     out.assign((size_t)nplanes * nch32 * cout_pad * 32, 0.f);
     auto tapw = [&](int ky, int kx, int n, int ci) -> double {
-        return wp[(((size_t)(ky * ks + kx) * nch16 + ci / CK) * cout_pad + n) * CK + ci % CK];
+        return wp[pmx_pk_direct(ky * ks + kx, ci, n, nch16, cout_pad)];
     };
     auto put = [&](int plane, int n, int ci, double v) {
         // [plane][chunk32][cout_pad / 32][k8-step][32][8]: the four k8-steps of a wave's 32 channels are 1 KB apart (an immediate offset of the load)
-        out[(((((size_t)plane * nch32 + ci / 32) * (cout_pad / 32) + n / 32) * 4 + (ci % 32) / 8) * 32 + n % 32) * 8 + ci % 8] = (float)v;
+        out[pmx_pk_wino(plane, n, ci, nch32, cout_pad)] = (float)v;
     };
     for (int n = 0; n < cout_pad; ++n)
         for (int ci = 0; ci < cin_pad; ++ci) {
@@ -218,6 +217,8 @@ static void pack_conv1(const std::vector<float>& wp, int cout_pad, std::vector<f
                     if (k < 27) out[((hf * 14 + sp) * 2 + kk) * 32 + n] = wp[((size_t)(k / 3) * cout_pad + hf * 32 + n) * CK + k % 3];
                 }
 }
+
+int pmx_pack_kind(const pmx_ctx* c, int cin) { return c->kind == NET_POSE ? (cin == 185 ? 1 : 0) : cin == c->n_heat + 128 ? 2 + c->n_heat : 0; }
 
 static std::vector<int> identity_map(int cin)
 {
@@ -430,6 +431,7 @@ extern "C" void pmx_destroy(pmx_ctx* c)
     if (c->pr_fin) (void)hipEventDestroy(c->pr_fin);
     if (c->bx_copied) (void)hipEventDestroy(c->bx_copied);
     if (c->sp_copied) (void)hipEventDestroy(c->sp_copied);
+    if (c->tr.seg_copied) (void)hipEventDestroy(c->tr.seg_copied);
     for (auto& p : c->pending) { (void)hipEventDestroy(p.e0); (void)hipEventDestroy(p.e1); }
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->snap_ev) if (e) (void)hipEventDestroy(e);
@@ -445,6 +447,10 @@ extern "C" int pmx_set_stream(pmx_ctx* c, void* s)
     PMX_DEV(c);
     PMX_HIP(hipStreamSynchronize(c->stream));
     c->stream = s ? (hipStream_t)s : c->own_stream;
+    if (c->tr.on) {      // the lazy pack builders wait for the stream the training steps run on
+        for (PackedLayer& l : c->layers) l.busy_stream = c->stream;
+        for (PackedLayer& l : c->bw.tl) l.busy_stream = c->stream;
+    }
     return PMX_OK;
 }
 
@@ -530,6 +536,8 @@ extern "C" int pmx_set_layer(pmx_ctx* c, const char* name, const float* w, const
     if ((size_t)it->second < c->bw.tl.size()) c->bw.tl[it->second] = PackedLayer();      // the data-gradient pack of the old weights
     L.set = true; L.cin = cin; L.cout = cout; L.ks = ks;
     L.cin_pad = (int)cmap.size(); L.cout_pad = cpad; L.nch = L.cin_pad / CK;
+    L.stale16 = L.stale3 = false;
+    if (c->tr.on) return pmx_train_on_set_layer(c, it->second, w, bias);
     return PMX_OK;
 }
 
@@ -546,13 +554,19 @@ extern "C" int pmx_weights_missing(pmx_ctx* c, int* n)
 // Derived weight packs, built from the device-resident packed fp32 weights when a kernel first needs them: fetch, `pack`, allocate, copy.
 // The slot takes the buffer only once the copy is complete: a failed copy must not leave a non-null pointer to garbage behind.
 template <typename T, typename Pack>
-static int derive_pack(const PackedLayer& L, DevBuf<T>& slot, const char* what, Pack pack)
+static int derive_pack(const PackedLayer& L, DevBuf<T>& slot, const char* what, Pack pack, bool stale = false)
 {
-    if (slot) return PMX_OK;
+    if (slot && !stale) return PMX_OK;
+    if (L.busy) PMX_HIP(hipStreamSynchronize(L.busy_stream));      // a training step may still be writing d_w (or reading the stale pack)
     std::vector<float> wp((size_t)L.ks * L.ks * L.nch * L.cout_pad * CK);
     PMX_HIP(hipMemcpy(wp.data(), L.d_w, wp.size() * sizeof(float), hipMemcpyDeviceToHost));
     std::vector<T> out;
     pack(wp, out);
+    if (slot) {      // stale: the same buffer, the same pointer
+        PMX_CHECK(slot.capacity() == out.size(), PMX_ERR_STATE, "%s weight pack: %zu elements held, %zu needed", what, slot.capacity(), out.size());
+        PMX_HIP(hipMemcpy(slot, out.data(), out.size() * sizeof(T), hipMemcpyHostToDevice));
+        return PMX_OK;
+    }
     DevBuf<T> d;
     if (int rc = d.alloc(out.size())) return rc;
     if (hipMemcpy(d, out.data(), out.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
@@ -573,10 +587,18 @@ static int ensure_conv1_pack(PackedLayer& L)
 }
 static int ensure_bf16x3_pack(PackedLayer& L)
 {
-    return derive_pack(L, L.d_w3, "bf16x3", [&](const std::vector<float>& wp, std::vector<uint16_t>& o) { pack_bf16x3(wp, L.ks * L.ks, L.nch, L.cout_pad, o); });
+    const int rc = derive_pack(L, L.d_w3, "bf16x3", [&](const std::vector<float>& wp, std::vector<uint16_t>& o) { pack_bf16x3(wp, L.ks * L.ks, L.nch, L.cout_pad, o); },
+                               L.stale3);
+    if (!rc) L.stale3 = false;
+    return rc;
 }
 // the f16 pack (half the fp32 weights' bytes): every 3x3 / 7x7 layer in f16 mode
-static int ensure_f16_pack(PackedLayer& L) { return derive_pack(L, L.d_w16, "f16", pack_f16); }
+static int ensure_f16_pack(PackedLayer& L)
+{
+    const int rc = derive_pack(L, L.d_w16, "f16", pack_f16, L.stale16);
+    if (!rc) L.stale16 = false;
+    return rc;
+}
 
 // Launches one convolution (1 or 2 groups) whose ConvArgs describe the FINAL result (real bias, ReLU, pool, output slices).
 // With S > 1 K slices the slice blocks write raw partial sums into the context's slab scratch and conv_splitk_reduce
@@ -2010,6 +2032,7 @@ int pmx_bw_transposed_pack(pmx_ctx* c, int layer)
     const bool cat_in = c->kind == NET_POSE && L.cin == 185;
     const std::vector<int> cmap = cat_in ? concat_map() : identity_map(L.cin);
     std::vector<float> wp((size_t)T * L.nch * L.cout_pad * CK), w((size_t)L.cout * L.cin * T);
+    if (L.busy) PMX_HIP(hipStreamSynchronize(L.busy_stream));      // a training step may still be writing d_w
     PMX_HIP(hipMemcpy(wp.data(), L.d_w, wp.size() * sizeof(float), hipMemcpyDeviceToHost));
     for (int tap = 0; tap < T; ++tap)
         for (int k = 0; k < L.cin_pad; ++k) {
@@ -2031,7 +2054,7 @@ int pmx_bw_transposed_pack(pmx_ctx* c, int layer)
     if ((rc = P.d_w.alloc(wp.size())) || (rc = P.d_b.alloc(bp.size()))) return rc;
     PMX_HIP(hipMemcpy(P.d_w, wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice));
     PMX_HIP(hipMemcpy(P.d_b, bp.data(), bp.size() * sizeof(float), hipMemcpyHostToDevice));
-    P.set = true;
+    P.set = true; P.busy = L.busy; P.busy_stream = L.busy_stream;
     Lt = std::move(P);
     return PMX_OK;
 }

@@ -135,7 +135,7 @@ extern "C" int pmx_backward_enable(pmx_ctx* c, int on)
     PMX_DEV(c);
     BwState& bw = c->bw;
     if (!on) {
-        if (bw.on) { PMX_HIP(hipStreamSynchronize(c->stream)); bw_free(bw); }
+        if (bw.on) { PMX_HIP(hipStreamSynchronize(c->stream)); pmx_train_free(c); bw_free(bw); }      // (training lives on the gradient store)
         bw.on = 0; bw.valid = bw.done = false;
         return PMX_OK;
     }
@@ -254,7 +254,7 @@ extern "C" int pmx_backward_head(pmx_ctx* c)
     // the concat buffer as the forward left it: the current maps are the last stage's again
     if (n > 1) BW(bwd_copy_cols_launch(A(PMX_BW_M(n, 7)), 64, cat + PMX_CAT_PAF, PMX_CAT_C, npix, 64, st));
 #undef BW
-    bw.done = true;
+    bw.done = true; bw.stepped = false;
     return PMX_OK;
 }
 

@@ -2,6 +2,7 @@
 // ABI share (pmx_api.hip: context, weights, forward plan, post-process, results; pmx_precise.hip: detect_precise and the key-point nets).
 #pragma once
 #include "pmx_common.h"
+#include "pack_index.h"
 
 #include <map>
 #include <tuple>
@@ -68,6 +69,11 @@ struct PackedLayer {
     DevBuf<uint16_t> d_w3;       // bf16x3 pack [tap][chunk][plane hi|mid|lo][cout_pad][16] (3x3 / 7x7 layers; option "precision" = 1)
     DevBuf<uint16_t> d_w16;      // f16 pack [tap][chunk][cout_pad][16] (3x3 / 7x7 layers; option "precision" = 2)
     int cin = 0, cout = 0, ks = 0, cin_pad = 0, cout_pad = 0, nch = 0;
+    // training (pmx_train.hip): a step rewrites d_w on `busy_stream` without telling the host, so a lazy builder that reads d_w with a
+    // blocking copy waits for that stream first (busy); the f16 / bf16x3 packs of a layer a step has updated are rebuilt in place, in their
+    // existing buffers, at their next ensure_* (nothing is freed in the middle of an enqueued chain)
+    bool busy = false, stale16 = false, stale3 = false;
+    hipStream_t busy_stream = nullptr;
 };
 
 // ------------------------------------------------------------------------------------------ profiler
@@ -144,8 +150,25 @@ struct BwState {
     DevBuf<double> part;                                  // bias-gradient slots
     DevBuf<int> cat_of_ref;                               // concat-buffer channel of the reference's input channel 0 .. 184 of Mconv1_*
     std::vector<PackedLayer> tl;                          // per layer: the pack whose forward is the data gradient (set = built)
+    bool stepped = false;                                 // pmx_train_step_head consumed the gradients of this backward
     int slot_layer[PMX_BW_SLOTS][2] = {};                 // table index of the slot's L1 / L2 layer (one-branch slots: both the same; X42: conv4_2)
     std::vector<int> layer_slot;                          // by table index: slot * 2 + branch, -1 for the trunk layers before conv4_2
+};
+
+// Head training step (pmx_train.hip; include/pose_mi355x.h: pmx_train_*).  Three stores with the layout of BwState::grad -- per head layer
+// w | b at grad_off[layer], padded to a multiple of 64 floats: the master weights (OIHW, reference input order), Adam's first and second
+// moments.  Per layer of c->table: its step count and gradient scale (trunk layers: unused today; the arrays cover them so that they can join).
+// seg_host / seg_dev: the per-segment table of one step, one copy from pinned memory (`seg_copied` marks when the host side may be rewritten).
+struct AdamSeg { unsigned long long off; unsigned n, blk0; float scale, alpha_t; };      // blk0: first block of the segment in the launch
+struct TrainState {
+    int on = 0;
+    DevBuf<float> w, m, v;
+    std::vector<int> t;
+    std::vector<float> scale;
+    double alpha = 1e-4, beta1 = 0.9, beta2 = 0.999, eps = 1e-8;
+    HostBuf<char> seg_host;
+    DevBuf<char> seg_dev;
+    hipEvent_t seg_copied = nullptr; bool seg_pending = false;
 };
 
 // ------------------------------------------------------------------------------------------- context
@@ -307,6 +330,7 @@ struct pmx_ctx {
     DevBuf<uint8_t> sp_a, sp_out, sp_mask_raw, sp_mask_tmp, sp_mask;
     int sp_n = 0, sp_insize = 0;                          // the prepared samples (0: none)
     BwState bw;                                           // pmx_backward.hip
+    TrainState tr;                                        // pmx_train.hip
 };
 constexpr int PMX_LOSS_SLOTS = 7;
 constexpr int PMX_LOSS_MAX_BLOCKS = 256;
@@ -380,3 +404,8 @@ int pmx_run_conv(pmx_ctx* c, const char* label, PackedLayer* L0, PackedLayer* L1
 int pmx_bw_transposed_pack(pmx_ctx* c, int layer);
 // c->smoothed (and c->pp.smoothed) at `floats` floats at least, grown to exactly that once the stream no longer uses the old maps
 int pmx_ensure_smoothed(pmx_ctx* c, size_t floats);
+// pmx_api.hip, for pmx_train.hip: the channel map kind of a layer's direct pack (pack_index.h), and pmx_set_layer's hook -- with training on,
+// a head layer's new weights also go to the master store (pmx_train.hip)
+int pmx_pack_kind(const pmx_ctx* c, int cin);
+int pmx_train_on_set_layer(pmx_ctx* c, int layer, const float* w, const float* bias);
+void pmx_train_free(pmx_ctx* c);

@@ -1,0 +1,503 @@
+// pmx_train.hip -- the head training step of the C ABI: pmx_train_enable / pmx_train_set_adam / pmx_train_set_grad_scale /
+// pmx_train_step_head / pmx_get_layer / pmx_train_get_state / pmx_train_set_state / pmx_get_pack / pmx_adam_apply.  Semantics:
+// include/pose_mi355x.h; the stores' layout: pmx_ctx.h (TrainState, BwState::grad); where a weight lies in a pack: pack_index.h.
+//
+// THE ADAM CONTRACT is this project's own restatement of Chainer's AdamRule (eta = 1, weight_decay_rate = 0) as a sequence of float32
+// operations, each rounded to nearest -- see adam_one below.  A CUDA build of Chainer may contract a multiply and an add into one FMA, so
+// bit equality with Chainer is NOT claimed; bit equality with tests/adam_twin.py is.  This unit is compiled with -ffp-contract=off (nothing is
+// fused) and -fhip-fp32-correctly-rounded-divide-sqrt (the float32 `/` and sqrt below expand to the correctly rounded sequences whatever the
+// compiler's default is; HIP's __fsqrt_rn is the 1-ulp hardware square root unless OCML's rounded operations are compiled in, so it is not used).
+#include "pmx_ctx.h"
+
+#include <math.h>
+#include <string.h>
+#include <algorithm>
+
+namespace {
+
+constexpr int ADAM_THREADS = 256;
+constexpr int ADAM_ITERS = 4;                                             // 16-byte vectors per lane
+constexpr unsigned ADAM_BLOCK_FLOATS = ADAM_THREADS * ADAM_ITERS * 4;     // floats of a segment one block covers
+
+__device__ __forceinline__ float rn_div(float a, float b) { return __fdiv_rn(a, b); }          // a / b, correctly rounded (flag above)
+__device__ __forceinline__ float rn_sqrt(float a) { return __builtin_sqrtf(a); }               // correctly rounded (flag above)
+
+// one parameter: every line one float32 operation
+__device__ __forceinline__ float adam_one(float grad, float w, float& m, float& v, float scale, float alpha_t, float omb1, float omb2, float eps)
+{
+    const float g = grad * scale;
+    const float d = g - m;
+    const float dm = omb1 * d;
+    m = m + dm;
+    const float q = g * g;
+    const float e = q - v;
+    const float dv = omb2 * e;
+    v = v + dv;
+    const float r = rn_sqrt(v);
+    const float s = r + eps;
+    const float am = alpha_t * m;
+    const float u = rn_div(am, s);
+    return w - u;
+}
+
+// The whole store in one launch.  Block b serves the segment whose [blk0, next blk0) holds b (82 segments: seven steps of a search), floats
+// (b - blk0) * ADAM_BLOCK_FLOATS ... of it.  Every segment starts at a multiple of 64 floats and is padded to one, so each lane moves whole
+// 16-byte vectors; the lanes of the last vector past n keep the bits they loaded (a pad float is never used as a parameter, never changed).
+__global__ __launch_bounds__(ADAM_THREADS) void adam_kernel(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v,
+                                                            const float* __restrict__ grad, const AdamSeg* __restrict__ segs, int nseg,
+                                                            float omb1, float omb2, float eps)
+{
+    int lo = 0, hi = nseg - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (segs[mid].blk0 <= blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const AdamSeg s = segs[lo];
+    const unsigned base = (blockIdx.x - s.blk0) * ADAM_BLOCK_FLOATS;
+#pragma unroll
+    for (int it = 0; it < ADAM_ITERS; ++it) {
+        const unsigned i = base + (unsigned)(it * ADAM_THREADS + threadIdx.x) * 4u;
+        if (i >= s.n) return;
+        const size_t at = (size_t)s.off + i;
+        const float4 g4 = *reinterpret_cast<const float4*>(grad + at);
+        float4 w4 = *reinterpret_cast<const float4*>(w + at);
+        float4 m4 = *reinterpret_cast<const float4*>(m + at);
+        float4 v4 = *reinterpret_cast<const float4*>(v + at);
+        const float gg[4] = {g4.x, g4.y, g4.z, g4.w};
+        float ww[4] = {w4.x, w4.y, w4.z, w4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float mk = mm[k], vk = vv[k];
+            const float wk = adam_one(gg[k], ww[k], mk, vk, s.scale, s.alpha_t, omb1, omb2, eps);
+            if (i + k < s.n) { ww[k] = wk; mm[k] = mk; vv[k] = vk; }
+        }
+        *reinterpret_cast<float4*>(w + at) = make_float4(ww[0], ww[1], ww[2], ww[3]);
+        *reinterpret_cast<float4*>(m + at) = make_float4(mm[0], mm[1], mm[2], mm[3]);
+        *reinterpret_cast<float4*>(v + at) = make_float4(vv[0], vv[1], vv[2], vv[3]);
+    }
+}
+
+// ---- packers: one thread per float of the pack, so the pad positions are written (+0.0f) like everything else --------------------------
+struct PackGeo { int cout, cin, T, kind, nch, cout_pad; };      // of the pack WRITTEN (nch chunks of 16 packed input channels)
+
+// master (w OIHW | b) -> the layer's direct pack and bias, as pack_weights does
+__global__ __launch_bounds__(256) void pack_direct_kernel(const float* __restrict__ w, float* __restrict__ dw, float* __restrict__ db, PackGeo p, unsigned total)
+{
+    const unsigned idx = blockIdx.x * 256u + threadIdx.x;
+    if (idx >= total) return;
+    const int c = idx % PMX_PK_CK, n = (idx / PMX_PK_CK) % p.cout_pad;
+    const unsigned pc = idx / PMX_PK_CK / p.cout_pad;
+    const int ch = pc % p.nch, tap = pc / p.nch, k = ch * PMX_PK_CK + c;
+    const int src = pmx_pk_ref_of_packed(p.kind, k, p.cin);
+    dw[idx] = src >= 0 && n < p.cout ? w[pmx_pk_oihw(n, src, tap, p.cin, p.T)] : 0.0f;
+    if (idx < (unsigned)p.cout_pad) db[idx] = idx < (unsigned)p.cout ? w[(size_t)p.cout * p.cin * p.T + idx] : 0.0f;
+}
+
+// master w -> the direct pack of the layer whose forward is the data gradient: output channel n = the layer's packed input channel, input
+// channel k = the layer's output channel, taps rotated by 180 degrees (conv_bwd_pack.h + pack_weights with the zero-padded g map).  p
+// describes the LAYER (cout, cin, T, kind); nch / cout_pad the transposed pack.
+__global__ __launch_bounds__(256) void pack_transposed_kernel(const float* __restrict__ w, float* __restrict__ dw, PackGeo p, int t_cout, unsigned total)
+{
+    const unsigned idx = blockIdx.x * 256u + threadIdx.x;
+    if (idx >= total) return;
+    const int c = idx % PMX_PK_CK, n = (idx / PMX_PK_CK) % p.cout_pad;
+    const unsigned pc = idx / PMX_PK_CK / p.cout_pad;
+    const int ch = pc % p.nch, tap = pc / p.nch, k = ch * PMX_PK_CK + c;
+    const int src = n < t_cout ? pmx_pk_ref_of_packed(p.kind, n, p.cin) : -1;
+    dw[idx] = src >= 0 && k < p.cout ? w[pmx_pk_oihw(k, src, p.T - 1 - tap, p.cin, p.T)] : 0.0f;
+}
+
+// direct pack -> Winograd pack, as pack_wino does: double, the same association, rounded once
+__global__ __launch_bounds__(256) void pack_wino_kernel(const float* __restrict__ wp, float* __restrict__ out, int ks, int nch16, int cout_pad, unsigned total)
+{
+    const unsigned idx = blockIdx.x * 256u + threadIdx.x;
+    if (idx >= total) return;
+    const int nch32 = nch16 * PMX_PK_CK / 32, nb32 = cout_pad / 32;
+    const int ci8 = idx % 8, n32 = (idx / 8) % 32, k8 = (idx / 256) % 4, nb = (idx / 1024) % nb32;
+    const unsigned pc = idx / 1024 / nb32;
+    const int c32 = pc % nch32, plane = pc / nch32;
+    const int n = nb * 32 + n32, ci = c32 * 32 + k8 * 8 + ci8;
+    const double Gm[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
+    auto tapw = [&](int ky, int kx) -> double { return wp[pmx_pk_direct(ky * ks + kx, ci, n, nch16, cout_pad)]; };
+    double val;
+    if (plane < 64) {
+        const int sub = plane / 16, i = (plane % 16) / 4, j = plane % 4;
+        double gg[3];
+        for (int kx = 0; kx < 3; ++kx)
+            gg[kx] = (Gm[i][0] * tapw(3 * (sub >> 1) + 0, 3 * (sub & 1) + kx) + Gm[i][1] * tapw(3 * (sub >> 1) + 1, 3 * (sub & 1) + kx)) +
+                     Gm[i][2] * tapw(3 * (sub >> 1) + 2, 3 * (sub & 1) + kx);
+        val = (gg[0] * Gm[j][0] + gg[1] * Gm[j][1]) + gg[2] * Gm[j][2];
+    } else if (plane < 72) {
+        const int sub = (plane - 64) / 4, f = (plane - 64) % 4;
+        val = (Gm[f][0] * tapw(6, 3 * sub + 0) + Gm[f][1] * tapw(6, 3 * sub + 1)) + Gm[f][2] * tapw(6, 3 * sub + 2);
+    } else if (plane < 80) {
+        const int sub = (plane - 72) / 4, f = (plane - 72) % 4;
+        val = (Gm[f][0] * tapw(3 * sub + 0, 6) + Gm[f][1] * tapw(3 * sub + 1, 6)) + Gm[f][2] * tapw(3 * sub + 2, 6);
+    } else val = tapw(6, 6);
+    out[idx] = (float)val;
+}
+
+// a layer's direct pack and bias -> (w OIHW, reference input order | b)
+__global__ __launch_bounds__(256) void unpack_kernel(const float* __restrict__ dw, const float* __restrict__ db, float* __restrict__ w, PackGeo p, unsigned total)
+{
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= total) return;
+    const unsigned nw = (unsigned)p.cout * p.cin * p.T;
+    if (i >= nw) { w[i] = db[i - nw]; return; }
+    const int tap = i % p.T, src = (i / p.T) % p.cin, n = i / p.T / p.cin;
+    w[i] = dw[pmx_pk_direct(tap, pmx_pk_packed_of_ref(p.kind, src), n, p.nch, p.cout_pad)];
+}
+
+#define TR_LAUNCHED(what) do { const hipError_t _e = hipGetLastError(); \
+    if (_e != hipSuccess) { pmx_set_error("%s: launch failed: %s", what, hipGetErrorString(_e)); return PMX_ERR_HIP; } } while (0)
+
+unsigned blocks256(size_t total) { return (unsigned)((total + 255) / 256); }
+
+PackGeo geo_of(const pmx_ctx* c, const PackedLayer& L)
+{
+    return PackGeo{L.cout, L.cin, L.ks * L.ks, pmx_pack_kind(c, L.cin), L.nch, L.cout_pad};
+}
+size_t direct_floats(const PackedLayer& L) { return (size_t)L.ks * L.ks * L.nch * L.cout_pad * CK; }
+size_t wino_floats(const PackedLayer& L) { return (size_t)pmx_pk_wino_planes(L.ks) * (L.cin_pad / 32) * L.cout_pad * 32; }
+
+int launch_unpack(const pmx_ctx* c, const PackedLayer& L, float* dst, hipStream_t st)
+{
+    const size_t total = (size_t)L.cout * L.cin * L.ks * L.ks + L.cout;
+    unpack_kernel<<<blocks256(total), 256, 0, st>>>(L.d_w, L.d_b, dst, geo_of(c, L), (unsigned)total);
+    TR_LAUNCHED("unpack");
+    return PMX_OK;
+}
+
+int launch_wino(const PackedLayer& L, hipStream_t st)
+{
+    const size_t total = wino_floats(L);
+    PMX_CHECK(L.d_ww.capacity() == total && L.cin_pad % 32 == 0 && L.cout_pad % 32 == 0, PMX_ERR_STATE,
+              "training step: a Winograd pack of %zu floats where %zu are expected", L.d_ww.capacity(), total);
+    pack_wino_kernel<<<blocks256(total), 256, 0, st>>>(L.d_w, L.d_ww, L.ks, L.nch, L.cout_pad, (unsigned)total);
+    TR_LAUNCHED("pack_wino");
+    return PMX_OK;
+}
+
+// every pack of head layer `idx` that exists, from the master weights at `w`
+int repack_layer(pmx_ctx* c, int idx, const float* w, hipStream_t st)
+{
+    PackedLayer& L = c->layers[idx];
+    const PackGeo g = geo_of(c, L);
+    size_t total = direct_floats(L);
+    PMX_CHECK(L.d_w.capacity() == total && L.d_b.capacity() == (size_t)L.cout_pad, PMX_ERR_STATE, "training step: layer '%s': a pack of %zu floats where %zu are expected",
+              c->table[idx].name.c_str(), L.d_w.capacity(), total);
+    pack_direct_kernel<<<blocks256(total), 256, 0, st>>>(w, L.d_w, L.d_b, g, (unsigned)total);
+    TR_LAUNCHED("pack_direct");
+    int rc;
+    if (L.d_ww && (rc = launch_wino(L, st))) return rc;
+    L.stale16 = (bool)L.d_w16; L.stale3 = (bool)L.d_w3;
+    if ((size_t)idx >= c->bw.tl.size() || !c->bw.tl[idx].set) return PMX_OK;
+    PackedLayer& P = c->bw.tl[idx];
+    total = direct_floats(P);
+    const int t_cout = pmx_pk_t_cout(g.kind, L.cin);
+    PMX_CHECK(P.d_w.capacity() == total && P.cout == t_cout && P.cin_pad == pmx_pk_t_cin_pad(L.cout), PMX_ERR_STATE,
+              "training step: layer '%s': a transposed pack of another shape", c->table[idx].name.c_str());
+    PackGeo gt = g;
+    gt.nch = P.nch; gt.cout_pad = P.cout_pad;
+    pack_transposed_kernel<<<blocks256(total), 256, 0, st>>>(w, P.d_w, gt, t_cout, (unsigned)total);
+    TR_LAUNCHED("pack_transposed");
+    if (P.d_ww && (rc = launch_wino(P, st))) return rc;
+    P.stale16 = (bool)P.d_w16; P.stale3 = (bool)P.d_w3;
+    return PMX_OK;
+}
+
+// the stage of a head layer (0: conv4_3_CPM / conv4_4_CPM), -1 for a layer the head backward does not cover
+int head_stage(const pmx_ctx* c, int idx)
+{
+    if ((size_t)idx >= c->bw.layer_slot.size() || c->bw.layer_slot[idx] < 0) return -1;
+    const int k = c->bw.layer_slot[idx] / 2;
+    return k < PMX_BW_S1 ? 0 : k < PMX_BW_M2 ? 1 : 2 + (k - PMX_BW_M2) / 7;
+}
+
+void mark_busy(pmx_ctx* c, bool on)
+{
+    for (size_t i = 0; i < c->layers.size(); ++i) {
+        if (head_stage(c, (int)i) < 0) continue;
+        c->layers[i].busy = on; c->layers[i].busy_stream = c->stream;
+        if (i < c->bw.tl.size()) { c->bw.tl[i].busy = on; c->bw.tl[i].busy_stream = c->stream; }
+    }
+}
+
+int tr_check(pmx_ctx* c, const char* who, bool need_on)
+{
+    PMX_CHECK(c, PMX_ERR_INVALID, "%s: null ctx", who);
+    PMX_CHECK(c->kind == NET_POSE, PMX_ERR_STATE, "%s: training exists for posenet contexts only", who);
+    PMX_CHECK(c->opt_precision == 0, PMX_ERR_STATE, "%s: option \"precision\" is %d; training is fp32 only", who, c->opt_precision);
+    PMX_CHECK(!need_on || c->tr.on, PMX_ERR_STATE, "%s: training is off (pmx_train_enable)", who);
+    return PMX_OK;
+}
+
+int head_layer(pmx_ctx* c, const char* who, const char* name, int* idx)
+{
+    PMX_CHECK(name, PMX_ERR_INVALID, "%s: null layer name", who);
+    auto it = c->index.find(name);
+    PMX_CHECK(it != c->index.end() && head_stage(c, it->second) >= 0, PMX_ERR_INVALID, "%s: '%s' is not one of the 82 layers after conv4_2", who, name);
+    *idx = it->second;
+    return PMX_OK;
+}
+
+float alpha_t_of(const TrainState& tr, int t)
+{
+    return (float)(tr.alpha * sqrt(1.0 - pow(tr.beta2, (double)t)) / (1.0 - pow(tr.beta1, (double)t)));
+}
+
+int launch_adam(float* w, float* m, float* v, const float* grad, const AdamSeg* d_segs, int nseg, unsigned blocks, float omb1, float omb2, float eps,
+                hipStream_t st)
+{
+    adam_kernel<<<blocks, ADAM_THREADS, 0, st>>>(w, m, v, grad, d_segs, nseg, omb1, omb2, eps);
+    TR_LAUNCHED("adam");
+    return PMX_OK;
+}
+
+}  // namespace
+
+void pmx_train_free(pmx_ctx* c)
+{
+    TrainState& tr = c->tr;
+    if (!tr.on) return;
+    tr.w.reset(); tr.m.reset(); tr.v.reset(); tr.seg_dev.reset(); tr.seg_host.reset();
+    tr.seg_pending = false;
+    mark_busy(c, false);
+    tr.on = 0;
+}
+
+int pmx_train_on_set_layer(pmx_ctx* c, int layer, const float* w, const float* bias)
+{
+    if (head_stage(c, layer) < 0) return PMX_OK;
+    const LayerDesc& d = c->table[layer];
+    const size_t nw = (size_t)d.cout * d.cin * d.ks * d.ks;
+    float* dst = c->tr.w + c->bw.grad_off[layer];
+    c->layers[layer].busy = true; c->layers[layer].busy_stream = c->stream;
+    // (pmx_set_layer has synchronised the stream)
+    PMX_HIP(hipMemcpy(dst, w, nw * sizeof(float), hipMemcpyHostToDevice));
+    if (bias) PMX_HIP(hipMemcpy(dst + nw, bias, (size_t)d.cout * sizeof(float), hipMemcpyHostToDevice));
+    else PMX_HIP(hipMemset(dst + nw, 0, (size_t)d.cout * sizeof(float)));
+    return PMX_OK;
+}
+
+extern "C" int pmx_train_enable(pmx_ctx* c, int on)
+{
+    int rc;
+    PMX_CHECK(c, PMX_ERR_INVALID, "pmx_train_enable: null ctx");
+    PMX_DEV(c);
+    TrainState& tr = c->tr;
+    if (!on) {
+        if (tr.on) { PMX_HIP(hipStreamSynchronize(c->stream)); pmx_train_free(c); }
+        return PMX_OK;
+    }
+    if ((rc = tr_check(c, "pmx_train_enable", false))) return rc;
+    if (tr.on) return PMX_OK;
+    PMX_CHECK(c->bw.on, PMX_ERR_STATE, "pmx_train_enable: the head backward is off (pmx_backward_enable)");
+    if ((rc = pmx_check_weights(c))) return rc;
+    const size_t total = c->bw.grad.capacity();
+    const bool ok = tr.w.alloc(total) == PMX_OK && tr.m.alloc(total) == PMX_OK && tr.v.alloc(total) == PMX_OK &&
+                    tr.seg_dev.alloc(c->table.size() * sizeof(AdamSeg)) == PMX_OK && tr.seg_host.alloc(c->table.size() * sizeof(AdamSeg)) == PMX_OK;
+    if (!ok) {
+        (void)hipGetLastError();
+        tr.w.reset(); tr.m.reset(); tr.v.reset(); tr.seg_dev.reset(); tr.seg_host.reset();
+        pmx_set_error("pmx_train_enable: the device has no room for the master weights and the two moments (3 x %.2f GB)", total * 4e-9);
+        return PMX_ERR_CAPACITY;
+    }
+    hipStream_t st = c->stream;
+    if (!tr.seg_copied) PMX_HIP(hipEventCreateWithFlags(&tr.seg_copied, hipEventDisableTiming));
+    PMX_HIP(hipMemsetAsync(tr.w, 0, total * sizeof(float), st));
+    PMX_HIP(hipMemsetAsync(tr.m, 0, total * sizeof(float), st));
+    PMX_HIP(hipMemsetAsync(tr.v, 0, total * sizeof(float), st));
+    for (size_t i = 0; i < c->layers.size(); ++i)
+        if (head_stage(c, (int)i) >= 0 && (rc = launch_unpack(c, c->layers[i], tr.w + c->bw.grad_off[i], st))) {
+            (void)hipStreamSynchronize(st);
+            tr.w.reset(); tr.m.reset(); tr.v.reset(); tr.seg_dev.reset(); tr.seg_host.reset();
+            return rc;
+        }
+    tr.t.assign(c->table.size(), 0);
+    tr.scale.assign(c->table.size(), 1.0f);
+    tr.alpha = 1e-4; tr.beta1 = 0.9; tr.beta2 = 0.999; tr.eps = 1e-8;
+    tr.seg_pending = false;
+    tr.on = 1;
+    mark_busy(c, true);
+    return PMX_OK;
+}
+
+extern "C" int pmx_train_set_adam(pmx_ctx* c, double alpha, double beta1, double beta2, double eps)
+{
+    int rc;
+    if ((rc = tr_check(c, "pmx_train_set_adam", true))) return rc;
+    PMX_CHECK(alpha > 0 && beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1 && eps > 0 && isfinite(alpha) && isfinite(eps), PMX_ERR_INVALID,
+              "pmx_train_set_adam: alpha %g, beta1 %g, beta2 %g, eps %g (alpha, eps > 0; 0 <= beta < 1)", alpha, beta1, beta2, eps);
+    c->tr.alpha = alpha; c->tr.beta1 = beta1; c->tr.beta2 = beta2; c->tr.eps = eps;
+    return PMX_OK;
+}
+
+extern "C" int pmx_train_set_grad_scale(pmx_ctx* c, const char* name, double scale)
+{
+    int rc, idx;
+    if ((rc = tr_check(c, "pmx_train_set_grad_scale", true)) || (rc = head_layer(c, "pmx_train_set_grad_scale", name, &idx))) return rc;
+    PMX_CHECK(isfinite(scale), PMX_ERR_INVALID, "pmx_train_set_grad_scale: scale %g", scale);
+    c->tr.scale[idx] = (float)scale;
+    return PMX_OK;
+}
+
+extern "C" int pmx_train_step_head(pmx_ctx* c)
+{
+    int rc;
+    if ((rc = tr_check(c, "pmx_train_step_head", true))) return rc;
+    BwState& bw = c->bw;
+    TrainState& tr = c->tr;
+    PMX_CHECK(bw.on && bw.valid && bw.done, PMX_ERR_STATE, "pmx_train_step_head: pmx_backward_head has not run for a retained forward");
+    PMX_CHECK(!bw.stepped, PMX_ERR_STATE, "pmx_train_step_head: a step has consumed these gradients (run a new retained forward and pmx_backward_head)");
+    PMX_DEV(c);
+    hipStream_t st = c->stream;
+    if (tr.seg_pending) { PMX_HIP(hipEventSynchronize(tr.seg_copied)); tr.seg_pending = false; }      // the pinned table is free again
+    AdamSeg* seg = reinterpret_cast<AdamSeg*>(tr.seg_host.get());
+    int nseg = 0;
+    unsigned blocks = 0;
+    double bytes = 0;
+    for (size_t i = 0; i < c->table.size(); ++i) {
+        const int stage = head_stage(c, (int)i);
+        if (stage < 0 || stage > bw.stages) continue;      // (a stage that "stop_stage" cut off received no gradient)
+        const LayerDesc& d = c->table[i];
+        const unsigned n = (unsigned)((size_t)d.cout * d.cin * d.ks * d.ks + d.cout);
+        tr.t[i] += 1;
+        seg[nseg++] = AdamSeg{(unsigned long long)bw.grad_off[i], n, blocks, tr.scale[i], alpha_t_of(tr, tr.t[i])};
+        blocks += (n + ADAM_BLOCK_FLOATS - 1) / ADAM_BLOCK_FLOATS;
+        bytes += 28.0 * n;
+    }
+    bw.stepped = true;
+    mark_busy(c, true);
+    PMX_HIP(hipMemcpyAsync(tr.seg_dev, seg, (size_t)nseg * sizeof(AdamSeg), hipMemcpyHostToDevice, st));
+    PMX_HIP(hipEventRecord(tr.seg_copied, st));
+    tr.seg_pending = true;
+    if ((rc = pmx_prof_begin(c, "train_step|adam", bytes))) return rc;
+    rc = launch_adam(tr.w, tr.m, tr.v, bw.grad, reinterpret_cast<const AdamSeg*>(tr.seg_dev.get()), nseg, blocks, (float)(1.0 - tr.beta1),
+                     (float)(1.0 - tr.beta2), (float)tr.eps, st);
+    if (int r = pmx_prof_end(c)) return r;
+    if (rc) return rc;
+    if ((rc = pmx_prof_begin(c, "train_step|pack", 0))) return rc;
+    for (size_t i = 0; i < c->table.size() && !rc; ++i) {
+        const int stage = head_stage(c, (int)i);
+        if (stage < 0 || stage > bw.stages) continue;
+        rc = repack_layer(c, (int)i, tr.w + bw.grad_off[i], st);
+    }
+    if (int r = pmx_prof_end(c)) return r;
+    return rc;
+}
+
+extern "C" int pmx_get_layer(pmx_ctx* c, const char* name, float* w_oihw, float* bias)
+{
+    PMX_CHECK(c && name, PMX_ERR_INVALID, "pmx_get_layer: null arg");
+    PMX_CHECK(w_oihw || bias, PMX_ERR_INVALID, "pmx_get_layer: both outputs are NULL");
+    auto it = c->index.find(name);
+    PMX_CHECK(it != c->index.end(), PMX_ERR_INVALID, "pmx_get_layer: unknown layer '%s'", name);
+    const int idx = it->second;
+    const PackedLayer& L = c->layers[idx];
+    PMX_CHECK(L.set, PMX_ERR_WEIGHTS, "pmx_get_layer: layer '%s' has no weights", name);
+    PMX_DEV(c);
+    const size_t nw = (size_t)L.cout * L.cin * L.ks * L.ks;
+    DevBuf<float> tmp;
+    const float* src;
+    if (c->tr.on && head_stage(c, idx) >= 0) src = c->tr.w + c->bw.grad_off[idx];
+    else {
+        int rc;
+        if ((rc = tmp.alloc(nw + L.cout)) || (rc = launch_unpack(c, L, tmp, c->stream))) return rc;
+        src = tmp;
+    }
+    PMX_HIP(hipStreamSynchronize(c->stream));
+    if (w_oihw) PMX_HIP(hipMemcpy(w_oihw, src, nw * sizeof(float), hipMemcpyDeviceToHost));
+    if (bias) PMX_HIP(hipMemcpy(bias, src + nw, (size_t)L.cout * sizeof(float), hipMemcpyDeviceToHost));
+    return PMX_OK;
+}
+
+extern "C" int pmx_train_get_state(pmx_ctx* c, const char* name, float* m_w, float* v_w, float* m_b, float* v_b, int* t)
+{
+    int rc, idx;
+    if ((rc = tr_check(c, "pmx_train_get_state", true)) || (rc = head_layer(c, "pmx_train_get_state", name, &idx))) return rc;
+    PMX_DEV(c);
+    const LayerDesc& d = c->table[idx];
+    const size_t nw = (size_t)d.cout * d.cin * d.ks * d.ks, off = c->bw.grad_off[idx];
+    PMX_HIP(hipStreamSynchronize(c->stream));
+    if (m_w) PMX_HIP(hipMemcpy(m_w, c->tr.m + off, nw * sizeof(float), hipMemcpyDeviceToHost));
+    if (v_w) PMX_HIP(hipMemcpy(v_w, c->tr.v + off, nw * sizeof(float), hipMemcpyDeviceToHost));
+    if (m_b) PMX_HIP(hipMemcpy(m_b, c->tr.m + off + nw, (size_t)d.cout * sizeof(float), hipMemcpyDeviceToHost));
+    if (v_b) PMX_HIP(hipMemcpy(v_b, c->tr.v + off + nw, (size_t)d.cout * sizeof(float), hipMemcpyDeviceToHost));
+    if (t) *t = c->tr.t[idx];
+    return PMX_OK;
+}
+
+extern "C" int pmx_train_set_state(pmx_ctx* c, const char* name, const float* m_w, const float* v_w, const float* m_b, const float* v_b, int t)
+{
+    int rc, idx;
+    if ((rc = tr_check(c, "pmx_train_set_state", true)) || (rc = head_layer(c, "pmx_train_set_state", name, &idx))) return rc;
+    PMX_CHECK(m_w && v_w && m_b && v_b, PMX_ERR_INVALID, "pmx_train_set_state: null moments");
+    PMX_CHECK(t >= 0, PMX_ERR_INVALID, "pmx_train_set_state: t = %d", t);
+    PMX_DEV(c);
+    const LayerDesc& d = c->table[idx];
+    const size_t nw = (size_t)d.cout * d.cin * d.ks * d.ks, off = c->bw.grad_off[idx];
+    PMX_HIP(hipStreamSynchronize(c->stream));
+    PMX_HIP(hipMemcpy(c->tr.m + off, m_w, nw * sizeof(float), hipMemcpyHostToDevice));
+    PMX_HIP(hipMemcpy(c->tr.v + off, v_w, nw * sizeof(float), hipMemcpyHostToDevice));
+    PMX_HIP(hipMemcpy(c->tr.m + off + nw, m_b, (size_t)d.cout * sizeof(float), hipMemcpyHostToDevice));
+    PMX_HIP(hipMemcpy(c->tr.v + off + nw, v_b, (size_t)d.cout * sizeof(float), hipMemcpyHostToDevice));
+    c->tr.t[idx] = t;
+    return PMX_OK;
+}
+
+extern "C" int pmx_get_pack(pmx_ctx* c, const char* name, int which, void* out, size_t cap_bytes, size_t* n_bytes)
+{
+    PMX_CHECK(c && name && n_bytes, PMX_ERR_INVALID, "pmx_get_pack: null arg");
+    PMX_CHECK(which >= 0 && which <= 4, PMX_ERR_INVALID, "pmx_get_pack: which = %d outside 0 .. 4", which);
+    auto it = c->index.find(name);
+    PMX_CHECK(it != c->index.end(), PMX_ERR_INVALID, "pmx_get_pack: unknown layer '%s'", name);
+    const int idx = it->second;
+    const PackedLayer* L = &c->layers[idx];
+    if (which >= 3) {
+        PMX_CHECK((size_t)idx < c->bw.tl.size() && c->bw.tl[idx].set, PMX_ERR_STATE, "pmx_get_pack: layer '%s' has no transposed pack", name);
+        L = &c->bw.tl[idx];
+    }
+    const DevBuf<float>& b = which == 0 || which == 3 ? L->d_w : which == 1 ? L->d_b : L->d_ww;
+    PMX_CHECK(L->set && b, PMX_ERR_STATE, "pmx_get_pack: pack %d of layer '%s' does not exist", which, name);
+    *n_bytes = b.capacity() * sizeof(float);
+    PMX_CHECK(out && cap_bytes >= *n_bytes, PMX_ERR_CAPACITY, "pmx_get_pack: %zu bytes needed, %zu given", *n_bytes, cap_bytes);
+    PMX_DEV(c);
+    PMX_HIP(hipStreamSynchronize(c->stream));
+    PMX_HIP(hipMemcpy(out, b, *n_bytes, hipMemcpyDeviceToHost));
+    return PMX_OK;
+}
+
+// test entry: the Adam launch on the caller's arrays (host, `total` floats each, updated in place); segment i covers floats
+// [off[i], off[i] + n[i]), off[i] a multiple of 4, the segments in rising order and apart by whole 16-byte vectors
+extern "C" int pmx_adam_apply(pmx_ctx* c, float* w, float* m, float* v, const float* grad, size_t total, const size_t* off, const unsigned* n,
+                              const float* scale, const float* alpha_t, int nseg, float omb1, float omb2, float eps)
+{
+    PMX_CHECK(c && w && m && v && grad && off && n && scale && alpha_t, PMX_ERR_INVALID, "pmx_adam_apply: null arg");
+    PMX_CHECK(nseg > 0 && nseg <= 4096, PMX_ERR_INVALID, "pmx_adam_apply: %d segments (1 .. 4096)", nseg);
+    std::vector<AdamSeg> segs(nseg);
+    unsigned blocks = 0;
+    size_t end = 0;
+    for (int i = 0; i < nseg; ++i) {
+        PMX_CHECK(n[i] > 0 && off[i] % 4 == 0 && off[i] >= end && off[i] + ((size_t)n[i] + 3) / 4 * 4 <= total, PMX_ERR_INVALID,
+                  "pmx_adam_apply: segment %d (offset %zu, %u floats) of %zu floats", i, off[i], n[i], total);
+        end = off[i] + ((size_t)n[i] + 3) / 4 * 4;
+        segs[i] = AdamSeg{(unsigned long long)off[i], n[i], blocks, scale[i], alpha_t[i]};
+        blocks += (n[i] + ADAM_BLOCK_FLOATS - 1) / ADAM_BLOCK_FLOATS;
+    }
+    PMX_DEV(c);
+    DevBuf<float> d[4];
+    DevBuf<AdamSeg> ds;
+    int rc;
+    for (auto& b : d) if ((rc = b.alloc(total))) return rc;
+    if ((rc = ds.alloc(nseg))) return rc;
+    const float* src[4] = {w, m, v, grad};
+    for (int i = 0; i < 4; ++i) PMX_HIP(hipMemcpy(d[i], src[i], total * sizeof(float), hipMemcpyHostToDevice));
+    PMX_HIP(hipMemcpy(ds, segs.data(), nseg * sizeof(AdamSeg), hipMemcpyHostToDevice));
+    rc = launch_adam(d[0], d[1], d[2], d[3], ds, nseg, blocks, omb1, omb2, eps, c->stream);
+    PMX_HIP(hipStreamSynchronize(c->stream));
+    if (rc) return rc;
+    float* dst[3] = {w, m, v};
+    for (int i = 0; i < 3; ++i) PMX_HIP(hipMemcpy(dst[i], d[i], total * sizeof(float), hipMemcpyDeviceToHost));
+    return PMX_OK;
+}

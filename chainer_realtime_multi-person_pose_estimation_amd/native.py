@@ -28,13 +28,14 @@ HEADER = os.path.join(os.path.dirname(HERE), 'include', 'pose_mi355x.h')
 SOURCES = [('pmx_api.hip', []), ('pmx_precise.hip', []), ('pmx_multi.hip', []), ('pmx_precise_images.hip', ['-ffp-contract=off']), ('conv_mfma.hip', []), ('conv_wino.hip', ['-mllvm', '-pragma-unroll-threshold=200000']), ('conv1_wino.hip', []), ('conv_f16.hip', []), ('conv_select.hip', []), ('prep.hip', ['-ffp-contract=off']),
            ('postproc.hip', ['-ffp-contract=off']), ('pmx_boxes.hip', ['-ffp-contract=off']), ('pmx_loss.hip', ['-ffp-contract=off']),
            ('pmx_samples.hip', ['-ffp-contract=off']), ('conv_bwd.hip', ['-ffp-contract=off']),
-           ('pmx_backward.hip', ['-ffp-contract=off'])]
+           ('pmx_backward.hip', ['-ffp-contract=off']),
+           ('pmx_train.hip', ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt'])]
 # the opt-in bf16x3 kernels (option "precision" = 1; DESIGN.md 4.1.5: frozen, slower than the fp32 Winograd path) are NOT part of the
 # default library: PMX_BUILD_BF16X3=1 in the environment of the build adds their translation unit (the stamp then differs, so the
 # library is rebuilt when the variable changes)
 if os.environ.get('PMX_BUILD_BF16X3', '') not in ('', '0'):
     SOURCES.append(('conv_bf16x3.hip', []))
-HEADERS = ['pmx_common.h', 'pmx_ctx.h', 'pp_tables.h', 'wino_util.h', 'conv_direct.h', 'pp_smooth.h', 'conv_bwd_pack.h', HEADER]
+HEADERS = ['pmx_common.h', 'pmx_ctx.h', 'pp_tables.h', 'wino_util.h', 'conv_direct.h', 'pp_smooth.h', 'conv_bwd_pack.h', 'pack_index.h', HEADER]
 
 N_JOINTS, N_LIMBS, N_PAF, N_HEAT = 18, 19, 38, 19
 # the detectors' precision= keyword -> engine option "precision" (include/pose_mi355x.h): fp32 (default), bf16x3 (opt-in build), f16 mode
@@ -338,6 +339,15 @@ def load():
         'pmx_samples_device_ptrs': (ci, [vp, C.POINTER(vp), C.POINTER(vp)]),
         'pmx_get_samples': (ci, [vp, vp, vp, ci, ci]),
         'pmx_validate_samples': (ci, [vp, vp, vp, vp]),
+        'pmx_train_enable': (ci, [vp, ci]),
+        'pmx_train_set_adam': (ci, [vp, cd, cd, cd, cd]),
+        'pmx_train_set_grad_scale': (ci, [vp, C.c_char_p, cd]),
+        'pmx_train_step_head': (ci, [vp]),
+        'pmx_get_layer': (ci, [vp, C.c_char_p, vp, vp]),
+        'pmx_train_get_state': (ci, [vp, C.c_char_p, vp, vp, vp, vp, ip]),
+        'pmx_train_set_state': (ci, [vp, C.c_char_p, vp, vp, vp, vp, ci]),
+        'pmx_get_pack': (ci, [vp, C.c_char_p, ci, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+        'pmx_adam_apply': (ci, [vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp, ci, C.c_float, C.c_float, C.c_float]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)     # AttributeError if the .so lacks a declared symbol
@@ -416,6 +426,9 @@ class Engine(object):
 
     def state(self):
         """Weights (host copies), options, stream and (grown) capacities of this engine -- what a larger context needs to take over."""
+        if getattr(self, '_trained', False):          # a training step changed the weights on the device: the host copies are stale
+            self._layers = self.get_weights()
+            self._trained = False
         return dict(layers=dict(self._layers), options=dict(self._options), stream=self._stream_ptr, caps=self.capacities())
 
     def load_state(self, st):
@@ -959,6 +972,83 @@ class Engine(object):
         out = np.empty((B, cout, h // 8, w // 8), np.float32)
         self._check(self.lib.pmx_get_retained(self._ctx, name.encode(), int(which), _ptr(out)))
         return out
+
+    # ---- head training step (include/pose_mi355x.h: pmx_train_*) ------------------------------------------------------
+    PACKS = {'w': 0, 'b': 1, 'wino': 2, 't_w': 3, 't_wino': 4}
+
+    def layer_shape(self, name):
+        """(cout, cin, k, k) of layer `name` as installed (KeyError for a layer never set through this engine)."""
+        return self._layers[name][0].shape
+
+    def train_enable(self, on=True):
+        """on: allocates the master weights and Adam's two moments of the 82 layers after conv4_2 (backward_enable first) and fills the
+        weights from the device packs; off: frees them."""
+        self._check(self.lib.pmx_train_enable(self._ctx, int(bool(on))))
+
+    def train_set_adam(self, alpha=1e-4, beta1=0.9, beta2=0.999, eps=1e-8):
+        self._check(self.lib.pmx_train_set_adam(self._ctx, float(alpha), float(beta1), float(beta2), float(eps)))
+
+    def train_set_grad_scale(self, name, scale):
+        self._check(self.lib.pmx_train_set_grad_scale(self._ctx, name.encode(), float(scale)))
+
+    def train_step_head(self):
+        """Adam on the gradients of the last backward_head + every existing weight pack rewritten on the device (no synchronisation)."""
+        self._check(self.lib.pmx_train_step_head(self._ctx))
+        self._trained = True
+
+    def get_layer(self, name):
+        """(W OIHW, b) float32: the current weights of any layer, from the device (synchronises)."""
+        W, b = self._layers.get(name, (np.empty((1, 1, 1, 1), np.float32), np.empty(1, np.float32)))      # (unknown: the library reports it)
+        w, bias = np.empty(W.shape, np.float32), np.empty(b.shape, np.float32)
+        self._check(self.lib.pmx_get_layer(self._ctx, name.encode(), _ptr(w), _ptr(bias)))
+        return w, bias
+
+    def get_weights(self):
+        """{name: (W, b)} of every layer, from the device: what weights.save_npz takes."""
+        return {name: self.get_layer(name) for name in self._layers}
+
+    def train_get_state(self, name):
+        """(m_W, v_W, m_b, v_b, t) of one head layer (synchronises)."""
+        W, b = self._layers.get(name, (np.empty((1, 1, 1, 1), np.float32), np.empty(1, np.float32)))
+        out = [np.empty(W.shape, np.float32), np.empty(W.shape, np.float32), np.empty(b.shape, np.float32), np.empty(b.shape, np.float32)]
+        t = C.c_int(0)
+        self._check(self.lib.pmx_train_get_state(self._ctx, name.encode(), *[_ptr(a) for a in out], C.byref(t)))
+        return tuple(out) + (t.value,)
+
+    def train_set_state(self, name, m_w, v_w, m_b, v_b, t):
+        W, b = self._layers.get(name, (np.empty((1, 1, 1, 1), np.float32), np.empty(1, np.float32)))
+        arrs = [np.ascontiguousarray(a, dtype=np.float32) for a in (m_w, v_w, m_b, v_b)]
+        for a, like in zip(arrs, (W, W, b, b)):
+            if a.shape != like.shape:
+                raise ValueError('train_set_state(%r): an array of shape %r, expected %r' % (name, a.shape, like.shape))
+        self._check(self.lib.pmx_train_set_state(self._ctx, name.encode(), *[_ptr(a) for a in arrs], int(t)))
+
+    def get_pack(self, name, which):
+        """The raw float32 contents of one device pack of a layer ('w', 'b', 'wino', 't_w', 't_wino' or 0 .. 4), None if that pack does
+        not exist now (synchronises)."""
+        which = self.PACKS.get(which, which)
+        n = C.c_size_t(0)
+        rc = self.lib.pmx_get_pack(self._ctx, name.encode(), int(which), None, 0, C.byref(n))
+        if rc == 6:          # PMX_ERR_STATE: no such pack now
+            return None
+        if rc != 5:          # (PMX_ERR_CAPACITY: the size query)
+            self._check(rc)
+        out = np.empty(n.value // 4, np.float32)
+        self._check(self.lib.pmx_get_pack(self._ctx, name.encode(), int(which), _ptr(out), out.nbytes, C.byref(n)))
+        return out
+
+    def adam_apply(self, w, m, v, grad, off, n, scale, alpha_t, omb1, omb2, eps):
+        """Test entry: the step's Adam launch on host arrays (float32, one length); returns the new (w, m, v)."""
+        w, m, v = [np.array(a, dtype=np.float32, order='C') for a in (w, m, v)]
+        grad = np.ascontiguousarray(grad, dtype=np.float32)
+        assert w.ndim == 1 and w.shape == m.shape == v.shape == grad.shape
+        off = np.ascontiguousarray(off, dtype=np.uintp)
+        n = np.ascontiguousarray(n, dtype=np.uint32)
+        scale, alpha_t = np.ascontiguousarray(scale, dtype=np.float32), np.ascontiguousarray(alpha_t, dtype=np.float32)
+        assert len(off) == len(n) == len(scale) == len(alpha_t)
+        self._check(self.lib.pmx_adam_apply(self._ctx, _ptr(w), _ptr(m), _ptr(v), _ptr(grad), w.size, _ptr(off), _ptr(n), _ptr(scale),
+                                            _ptr(alpha_t), len(off), float(omb1), float(omb2), float(eps)))
+        return w, m, v
 
     def loss_current_maps(self):
         """(paf_loss, heat_loss) of the current maps (forward or set_maps) against the targets (synchronises)."""

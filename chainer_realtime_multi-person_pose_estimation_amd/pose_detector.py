@@ -67,14 +67,20 @@ class PoseDetector(object):
                              "PMX_BUILD_BF16X3=1)" % (', '.join(repr(p) for p in native.PRECISIONS), precision))
         self._precision = precision
         self.engine = None
+        self._train_on = False                     # training mode (train_step): the optimiser's stores live in the engine
+        self._adam = dict(alpha=1e-4, beta1=0.9, beta2=0.999, eps=1e-8)
+        self._grad_scales = dict(self.REFERENCE_GRAD_SCALES)
         self._make_engine(max_batch, mh, mw)
 
     def _make_engine(self, max_batch, mh, mw):
         # growth keeps the engine's state: weights (also those installed through detector.engine.set_weights / set_layer), options,
         # stream, capacities -- taken from the old context, which is destroyed BEFORE the larger one is created (the two never hold
         # their buffers and weight packs at the same time)
-        st = None
+        st = opt = None
         if self.engine is not None:
+            if self._train_on:                     # Adam's state moves to the larger context with the weights
+                opt = self.optimizer_state()
+                self._train_on = False
             st = self.engine.state()
             self.engine.close()
             self.engine = None
@@ -86,8 +92,12 @@ class PoseDetector(object):
             self.engine = None
             if st is not None:
                 self.engine = self._new_engine(*self._cap, st)
+                if opt is not None:
+                    self.load_optimizer_state(opt)
             raise
         self._cap = (max_batch, mh, mw)            # only once the new context is complete
+        if opt is not None:
+            self.load_optimizer_state(opt)
 
     def _new_engine(self, max_batch, mh, mw, st):
         eng = native.Engine(self._gpu, max_batch=max_batch, max_h=mh, max_w=mw, gaussian_sigma=params['gaussian_sigma'])
@@ -601,7 +611,8 @@ class PoseDetector(object):
             total, paf, heat = self.engine.validate_batch(np.stack(imgs))
             grads = [self.engine.loss_grads(s) for s in range(6)]
         finally:
-            self.engine.loss_grad_enable(False)
+            if not self._train_on:
+                self.engine.loss_grad_enable(False)
         return {'val/loss': float(total), 'val/paf': float(paf.sum()), 'val/heat': float(heat.sum()),
                 'paf_stages': [float(v) for v in paf], 'heat_stages': [float(v) for v in heat],
                 'paf_grads': [g[0] for g in grads], 'heat_grads': [g[1] for g in grads]}
@@ -632,11 +643,113 @@ class PoseDetector(object):
             layer_grads = {name: eng.layer_grad(name) for name in eng.head_layers()}
             trunk = eng.trunk_grad()
         finally:
-            eng.backward_enable(False)
-            eng.loss_grad_enable(False)
+            if not self._train_on:          # (training lives on the backward's stores: they stay while it is on)
+                eng.backward_enable(False)
+                eng.loss_grad_enable(False)
         return {'val/loss': float(total), 'val/paf': float(paf.sum()), 'val/heat': float(heat.sum()),
                 'paf_stages': [float(v) for v in paf], 'heat_stages': [float(v) for v in heat],
                 'paf_grads': [g[0] for g in grads], 'heat_grads': [g[1] for g in grads], 'grads': layer_grads, 'trunk_grad': trunk}
+
+    # ---- training of the head (reference train_coco_pose_estimation.py:204-235, its first 2000 iterations) -------------------------------
+    REFERENCE_GRAD_SCALES = {'conv4_3_CPM': 0.25, 'conv4_4_CPM': 0.25}      # GradientScaling (train_coco_pose_estimation.py:222-223)
+
+    def _start_training(self):
+        """Training mode of the current engine: loss gradients, retention and the optimiser's stores on (they stay on until stop_training)."""
+        if self._train_on:
+            return
+        if self.model is not None:
+            raise RuntimeError('training runs the built-in network: not available with a model= callable')
+        if self._precision != 'f32':
+            raise RuntimeError("training is fp32: create the detector with precision='f32'")
+        if self.engine.weights_missing():
+            raise RuntimeError('PoseDetector has no weights: pass weights_file=, weights= or model=')
+        eng = self.engine
+        eng.loss_grad_enable(True)
+        try:
+            eng.backward_enable(True)
+            eng.train_enable(True)
+            eng.train_set_adam(**self._adam)
+            for name, sc in self._grad_scales.items():
+                eng.train_set_grad_scale(name, sc)
+        except Exception:
+            eng.backward_enable(False)
+            eng.loss_grad_enable(False)
+            raise
+        self._train_on = True
+
+    def stop_training(self):
+        """Leave training mode: frees the optimiser's and the backward's stores (the weights stay as trained; Adam's state is dropped --
+        optimizer_state() first to keep it)."""
+        if self._train_on:
+            self._train_on = False
+            self.engine.backward_enable(False)
+            self.engine.loss_grad_enable(False)
+
+    def set_optimizer(self, alpha=1e-4, beta1=0.9, beta2=0.999, eps=1e-8, grad_scales=None):
+        """Adam's hyper-parameters from the next train_step on (defaults: Chainer's, which the reference uses; it lowers alpha at 100 000 and
+        200 000 iterations) and the per-layer gradient scales {head layer: scale} (default: the reference's 1/4 for conv4_3_CPM and
+        conv4_4_CPM; layers not named: 1)."""
+        self._adam = dict(alpha=float(alpha), beta1=float(beta1), beta2=float(beta2), eps=float(eps))
+        old = self._grad_scales
+        self._grad_scales = dict(self.REFERENCE_GRAD_SCALES if grad_scales is None else grad_scales)
+        if self._train_on:
+            self.engine.train_set_adam(**self._adam)
+            for name in set(old) | set(self._grad_scales):
+                self.engine.train_set_grad_scale(name, self._grad_scales.get(name, 1.0))
+
+    def train_step(self, imgs, poses_per_image, ignore_masks=None):
+        """One iteration of the reference's training loop while conv1_1 .. conv4_2 are frozen: the forward with compute_loss, the backward of
+        the 82 layers after conv4_2 and Adam with the gradient scales, all on the device -- no gradient and no weight crosses to the host.
+        Arguments as head_gradients (uniform uint8 images at the network-input size; prepare_samples(mode='train') makes them).  ->
+        {'main/loss', 'main/paf', 'main/heat'} (floats) and 'paf_stages', 'heat_stages': validation_loss's numbers of this batch BEFORE the
+        update, under the reference's training names.  More images than the engine's batch raise ValueError."""
+        imgs, poses, masks = self._check_validation_args(imgs, poses_per_image, ignore_masks)
+        h, w = imgs[0].shape[:2]
+        if self.model is None and self.engine.weights_missing():
+            raise RuntimeError('PoseDetector has no weights: pass weights_file=, weights= or model=')
+        self._grow(1, h, w)
+        if len(imgs) > self._cap[0]:
+            raise ValueError('train_step: %d images, the engine holds batches of %d (the gradients of chunks cannot be merged)'
+                             % (len(imgs), self._cap[0]))
+        self._start_training()
+        eng = self.engine
+        eng.loss_set_poses(poses, h, w, None if masks is None else np.stack(masks), params['heatmap_sigma'], params['paf_sigma'])
+        eng.loss_enable(True)
+        try:
+            eng.forward_u8(np.stack(imgs))
+            eng.backward_head()
+            eng.train_step_head()
+            paf, heat, _ = eng.loss_get()          # (the one synchronisation: the whole iteration is enqueued by now)
+        finally:
+            eng.loss_enable(False)
+        return {'main/loss': float(paf.sum() + heat.sum()), 'main/paf': float(paf.sum()), 'main/heat': float(heat.sum()),
+                'paf_stages': [float(v) for v in paf], 'heat_stages': [float(v) for v in heat]}
+
+    def get_weights(self):
+        """{layer name: (W OIHW, b)} float32 of all 92 layers as they are on the device now -- what weights.save_npz takes."""
+        if self.model is not None:
+            raise RuntimeError('get_weights reads the built-in engine: not available with a model= callable')
+        return self.engine.get_weights()
+
+    def optimizer_state(self):
+        """Adam's state as a flat dictionary of NumPy arrays (np.savez takes it): 'adam' = (alpha, beta1, beta2, eps), and per head layer
+        '<name>/m_W', '/v_W', '/m_b', '/v_b', '/t', '/scale'.  With the weights (get_weights) it is what the reference's --resume restores."""
+        self._start_training()
+        out = {'adam': np.array([self._adam[k] for k in ('alpha', 'beta1', 'beta2', 'eps')], np.float64)}
+        for name in self.engine.head_layers():
+            m_w, v_w, m_b, v_b, t = self.engine.train_get_state(name)
+            out.update({name + '/m_W': m_w, name + '/v_W': v_w, name + '/m_b': m_b, name + '/v_b': v_b, name + '/t': np.array(t, np.int64),
+                        name + '/scale': np.array(self._grad_scales.get(name, 1.0), np.float64)})
+        return out
+
+    def load_optimizer_state(self, state):
+        """Install what optimizer_state() returned (or np.load of its np.savez) in this detector: training continues where it stopped."""
+        a = np.asarray(state['adam'], np.float64)
+        names = sorted(k[:-len('/t')] for k in state.keys() if k.endswith('/t'))
+        self.set_optimizer(*[float(x) for x in a], grad_scales={n: float(state[n + '/scale']) for n in names if float(state[n + '/scale']) != 1.0})
+        self._start_training()
+        for n in names:
+            self.engine.train_set_state(n, state[n + '/m_W'], state[n + '/v_W'], state[n + '/m_b'], state[n + '/v_b'], int(state[n + '/t']))
 
     # ---- sample preparation (reference coco_data_loader.py:61-205, 334-341) ----------------------------------------------------------
     @staticmethod

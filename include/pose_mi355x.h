@@ -603,6 +603,70 @@ int pmx_get_trunk_grad(pmx_ctx* ctx, float* g_nchw);
  * which outside {0, 1}: PMX_ERR_INVALID.  Synchronises. */
 int pmx_get_retained(pmx_ctx* ctx, const char* name, int which, float* out_nchw);
 
+/* ---- head training step: Adam on the 82 layers after conv4_2, every weight pack rewritten on the device ----------------------------
+ * What the reference's optimizer.update() does during its first 2000 iterations (train_coco_pose_estimation.py:219-225: Adam, conv1_1 ..
+ * conv4_2 frozen, GradientScaling(conv4_3_CPM / conv4_4_CPM, 1/4)), applied to the gradient store pmx_backward_head leaves.  The weights
+ * never leave the device.  posenet contexts, fp32 ("precision" 0).
+ *
+ * STORES.  pmx_train_enable(on != 0) needs pmx_backward_enable on and every layer's weights set (else PMX_ERR_STATE / PMX_ERR_WEIGHTS).  It
+ * allocates three stores with the layout of the gradient store (per layer dw | db, every layer padded to a multiple of 64 floats; about
+ * 3 x 186 MB): the master weights w (OIHW, the reference's input order), filled by un-pack launches from the layers' current device packs
+ * (the context keeps no host copy), and Adam's moments m = v = 0; the step count t of every head layer becomes 0, its gradient scale 1, the
+ * hyper-parameters alpha = 1e-4, beta1 = 0.9, beta2 = 0.999, eps = 1e-8 (Chainer's and the reference's).  PMX_ERR_CAPACITY if the device
+ * refuses; the context stays usable.  on = 0 frees the stores (so does pmx_backward_enable(0)).  With training off nothing is allocated or
+ * launched that was not before.  While training is on, pmx_set_layer on a head layer also rewrites that layer's master weights (m, v, t stay).
+ *
+ * THE CONTRACT of one parameter, this project's own restatement of Chainer's AdamRule with eta = 1 and weight_decay_rate = 0.  Every line is
+ * ONE float32 operation rounded to nearest, sqrt and / correctly rounded, nothing fused:
+ *     g = grad * scale
+ *     d = g - m;   m = m + omb1 * d                 omb1 = (float)(1 - beta1)
+ *     q = g * g;   e = q - v;   v = v + omb2 * e    omb2 = (float)(1 - beta2)
+ *     s = sqrtf(v) + eps                            eps  = (float)eps
+ *     w = w - (alpha_t * m) / s                     alpha_t = (float)(alpha * sqrt(1 - beta2^t) / (1 - beta1^t)), in double on the host
+ * t is the LAYER's own step count after the increment; scale, alpha_t and t are per layer.  A CUDA build of Chainer may contract a multiply
+ * and an add into one FMA, so bit equality with Chainer is not claimed; tests/adam_twin.py restates the lines in NumPy and is matched bit
+ * for bit.  Pad floats between layers are neither used as parameters nor changed.
+ *
+ * pmx_train_step_head, asynchronous on the context's stream, after pmx_backward_head for the retained forward:
+ *   1. t += 1 for the layers that received a gradient: those of the stages the retained forward ran.  Layers of stages that "stop_stage" cut
+ *      off keep their weights, packs, moments and t (this project's rule: a parameter without a gradient is not updated);
+ *   2. Adam over all those layers in ONE launch (a per-segment table, sent through pinned memory; the call waits only if the previous
+ *      step's table copy has not finished);
+ *   3. the packers: every pack of an updated layer that EXISTS is rewritten in place, same pointer, with the bits the host packers produce
+ *      from the same OIHW weights -- the direct pack and bias (pmx_set_layer), the Winograd pack, the transposed 180-degree-rotated pack of
+ *      the data gradient and its Winograd pack.  A pack that does not exist is not created: its lazy host builder makes it on first use
+ *      from the then-current direct pack, after waiting for the stream.  The f16 / bf16x3 packs of an updated layer are marked stale and
+ *      rebuilt in place when a forward in that mode next needs them.
+ * No host synchronisation, no host <-> device copy but the table.  The step CONSUMES the gradients: a second step without a new retained
+ * forward + pmx_backward_head is PMX_ERR_STATE; pmx_get_layer_grad keeps working until the next forward.
+ * Errors, before anything is enqueued: PMX_ERR_INVALID for a null context; PMX_ERR_STATE for a facenet / handnet context, "precision" != 0,
+ * training off, no backward for the retained forward, consumed gradients. */
+int pmx_train_enable(pmx_ctx* ctx, int on);
+/* Adam's hyper-parameters from the next step on (the reference lowers alpha at 100 000 and 200 000 iterations).  alpha, eps > 0 and
+ * 0 <= beta < 1, else PMX_ERR_INVALID; PMX_ERR_STATE with training off. */
+int pmx_train_set_adam(pmx_ctx* ctx, double alpha, double beta1, double beta2, double eps);
+/* the gradient scale of one head layer (GradientScaling; rounded to float32).  PMX_ERR_INVALID for an unknown name or a trunk layer. */
+int pmx_train_set_grad_scale(pmx_ctx* ctx, const char* name, double scale);
+int pmx_train_step_head(pmx_ctx* ctx);
+/* The current weights (OIHW, the layer's shape as in pmx_set_layer, the reference's input order) and bias of ANY layer; either pointer may
+ * be NULL (both: PMX_ERR_INVALID).  A head layer with training on is read from the master store, anything else is un-packed from its direct
+ * pack on the device -- the same floats, a pack holds them unrounded.  Any context.  PMX_ERR_INVALID for an unknown name, PMX_ERR_WEIGHTS
+ * for a layer without weights.  Synchronises. */
+int pmx_get_layer(pmx_ctx* ctx, const char* name, float* w_oihw, float* bias);
+/* Adam's state of one head layer (the reference's --resume): moments of the weights (OIHW) and of the bias, and the step count.  get: any
+ * pointer may be NULL.  set: all four arrays, t >= 0, else PMX_ERR_INVALID.  PMX_ERR_STATE with training off.  Both synchronise. */
+int pmx_train_get_state(pmx_ctx* ctx, const char* name, float* m_w, float* v_w, float* m_b, float* v_b, int* t);
+int pmx_train_set_state(pmx_ctx* ctx, const char* name, const float* m_w, const float* v_w, const float* m_b, const float* v_b, int t);
+/* parity accessor: the raw bytes of one pack of a layer -- which = 0 the direct pack, 1 the padded bias, 2 the Winograd pack (conv1_1: its
+ * fused-kernel pack), 3 the transposed pack of the data gradient, 4 its Winograd pack.  *n_bytes is the pack's size whenever it exists;
+ * PMX_ERR_STATE if it does not exist now, PMX_ERR_CAPACITY if out is NULL or cap_bytes too small.  Synchronises. */
+int pmx_get_pack(pmx_ctx* ctx, const char* name, int which, void* out, size_t cap_bytes, size_t* n_bytes);
+/* test entry: the Adam launch of pmx_train_step_head on the caller's host arrays of `total` floats each (w, m, v updated in place).  Segment
+ * i covers floats [off[i], off[i] + n[i]); off[i] a multiple of 4, the segments in rising order and not sharing a 16-byte vector, else
+ * PMX_ERR_INVALID.  Floats outside the segments keep their bits.  Synchronises. */
+int pmx_adam_apply(pmx_ctx* ctx, float* w, float* m, float* v, const float* grad, size_t total, const size_t* off, const unsigned* n,
+                   const float* scale, const float* alpha_t, int nseg, float omb1, float omb2, float eps);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,170 @@
+#!/usr/bin/env python
+"""What one head training iteration costs, at 368 x 368, batch 10 (the reference's --batchsize) and 32, in one process ->
+profiles/train_step.json.  Legs, alternated `rounds` times, each figure the mean of `iters` enqueues between two events on the context's
+stream after `warmup` untimed ones (images on the device):
+  (a) hooked retaining forward + pmx_backward_head
+  (b) the same + pmx_train_step_head
+  (c) the Adam launch alone and the packers alone, from the per-launch profiler's labels train_step|adam and train_step|pack (a run of its
+      own: the profiler's events slow everything else down), and a device-to-device hipMemcpyAsync that moves the same bytes as the Adam
+      launch (28 per parameter: a copy of 14 bytes per parameter, read once and written once) -- the yardstick of its bandwidth
+  (d) the host route the step replaces, by wall clock: every gradient fetched, Adam in NumPy, 82 x pmx_set_layer, and the next forward +
+      backward, which rebuilds the derived packs on the host
+
+    python tools/train_step_time.py [--iters N] [--warmup N] [--rounds N] [--batches 10,32] [--out PATH]"""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+PKG = 'chainer_realtime_multi-person_pose_estimation_amd'
+
+
+def timed(eng, fn, iters, warmup):
+    for _ in range(warmup):
+        fn()
+    eng.synchronize()
+    eng.timer_start()
+    for _ in range(iters):
+        fn()
+    return eng.timer_stop() / iters
+
+
+def numpy_adam(w, m, v, g, scale, t, alpha=1e-4, beta1=0.9, beta2=0.999, eps=1e-8):
+    f = np.float32
+    a_t = f(alpha * np.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t))
+    g = g * f(scale)
+    m += f(1.0 - beta1) * (g - m)
+    v += f(1.0 - beta2) * (g * g - v)
+    return w - a_t * m / (np.sqrt(v) + f(eps))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--iters', type=int, default=5)
+    ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--rounds', type=int, default=3)
+    ap.add_argument('--batches', default='10,32')
+    ap.add_argument('--size', type=int, default=368)
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'train_step.json'))
+    args = ap.parse_args()
+    import torch
+    native = importlib.import_module(PKG + '.native')
+    weights = importlib.import_module(PKG + '.weights').synthetic_weights(0)
+    H = W = args.size
+    out = []
+    for B in [int(v) for v in args.batches.split(',')]:
+        rng = np.random.default_rng(B)
+        imgs = rng.integers(0, 256, (B, H, W, 3), dtype=np.uint8)
+        poses = []
+        for _ in range(B):
+            p = np.zeros((2, 18, 3))
+            p[:, :, 0] = rng.uniform(2, W - 2, (2, 18))
+            p[:, :, 1] = rng.uniform(2, H - 2, (2, 18))
+            p[:, :, 2] = rng.integers(0, 3, (2, 18))
+            poses.append(p)
+        masks = np.zeros((B, H, W), bool)
+        masks[0, 40:200, 60:300] = True
+        eng = native.Engine(0, max_batch=B, max_h=H, max_w=W)
+        eng.set_weights(weights)
+        dev = torch.from_numpy(imgs).cuda()
+        torch.cuda.synchronize()
+        eng.loss_set_poses(poses, H, W, masks, 7, 8)
+        eng.loss_enable(True)
+        eng.loss_grad_enable(True)
+        eng.backward_enable(True)
+        eng.train_enable(True)
+        head = eng.head_layers()
+        scales = {'conv4_3_CPM': 0.25, 'conv4_4_CPM': 0.25}
+        for nm, sc in scales.items():
+            eng.train_set_grad_scale(nm, sc)
+        n_params = sum(int(np.prod(eng.layer_shape(nm))) + eng.layer_shape(nm)[0] for nm in head)
+
+        def leg_a():
+            eng.forward_u8(device_ptr=dev.data_ptr(), shape=(B, H, W))
+            eng.backward_head()
+
+        def leg_b():
+            leg_a()
+            eng.train_step_head()
+        a_ms, b_ms = [], []
+        for _ in range(args.rounds):
+            a_ms.append(timed(eng, leg_a, args.iters, args.warmup))
+            b_ms.append(timed(eng, leg_b, args.iters, args.warmup))
+        # (c) the two parts of the step by the profiler's labels, and the copy that moves the same bytes
+        eng.profile_enable(1)
+        for _ in range(args.warmup):
+            leg_b()
+        eng.synchronize()
+        eng.profile_reset()
+        for _ in range(args.iters):
+            leg_b()
+        eng.synchronize()
+        prof = {(p['layer'], p['kernel']): p for p in eng.profile()}
+        eng.profile_enable(0)
+        adam_ms, pack_ms = prof[('train_step', 'adam')]['avg_ms'], prof[('train_step', 'pack')]['avg_ms']
+        src = torch.empty(14 * n_params, dtype=torch.uint8, device='cuda')
+        dst = torch.empty_like(src)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        copies = []
+        for i in range(args.warmup + args.iters):
+            e0.record()
+            dst.copy_(src)          # contiguous, same type, same device: hipMemcpyAsync device to device
+            e1.record()
+            e1.synchronize()
+            if i >= args.warmup:
+                copies.append(e0.elapsed_time(e1))
+        del src, dst
+        copy_ms = float(np.mean(copies))
+        # (d) the host route, by wall clock
+        eng.train_enable(False)
+        state = {nm: [np.zeros(eng.layer_shape(nm), 'f'), np.zeros(eng.layer_shape(nm), 'f'), np.zeros(eng.layer_shape(nm)[0], 'f'),
+                      np.zeros(eng.layer_shape(nm)[0], 'f')] for nm in head}
+        cur = {nm: [a.copy() for a in weights[nm]] for nm in head}
+        leg_a()
+        eng.synchronize()
+        host, parts = [], []
+        for t in (1, 2):
+            t0 = time.perf_counter()
+            grads = {nm: eng.layer_grad(nm) for nm in head}
+            t1 = time.perf_counter()
+            for nm in head:
+                mw, vw, mb, vb = state[nm]
+                cur[nm][0] = numpy_adam(cur[nm][0], mw, vw, grads[nm][0], scales.get(nm, 1.0), t)
+                cur[nm][1] = numpy_adam(cur[nm][1], mb, vb, grads[nm][1], scales.get(nm, 1.0), t)
+            t2 = time.perf_counter()
+            for nm in head:
+                eng.set_layer(nm, cur[nm][0], cur[nm][1])
+            t3 = time.perf_counter()
+            leg_a()
+            eng.synchronize()
+            t4 = time.perf_counter()
+            host.append(1e3 * (t4 - t0))
+            parts.append(dict(fetch_ms=1e3 * (t1 - t0), numpy_adam_ms=1e3 * (t2 - t1), set_layer_ms=1e3 * (t3 - t2),
+                              forward_backward_rebuilding_ms=1e3 * (t4 - t3)))
+        a, b = float(np.mean(a_ms)), float(np.mean(b_ms))
+        e = dict(batch=B, h=H, w=W, iters=args.iters, warmup=args.warmup, rounds=args.rounds, head_parameters=n_params,
+                 forward_backward_ms=a, forward_backward_rounds_ms=a_ms, with_step_ms=b, with_step_rounds_ms=b_ms,
+                 step_cost_ms=b - a, step_cost_percent=100.0 * (b - a) / a,
+                 adam_launch_ms=adam_ms, packers_ms=pack_ms, adam_bytes=28 * n_params, adam_gb_per_s=28e-6 * n_params / adam_ms,
+                 copy_same_bytes_ms=copy_ms, copy_runs_ms=copies, copy_gb_per_s=28e-6 * n_params / copy_ms, adam_over_copy_rate=copy_ms / adam_ms,
+                 host_route_ms=host, host_route_parts=parts)
+        out.append(e)
+        print(json.dumps(e), flush=True)
+        eng.close()
+        del dev
+    with open(args.out, 'w') as f:
+        json.dump(dict(device='MI355X', note='(a) forward_backward = hooked retaining forward + pmx_backward_head; (b) with_step = the same + '
+                       'pmx_train_step_head; (c) adam_launch / packers = the per-launch profiler\'s labels train_step|adam, train_step|pack; '
+                       'copy_same_bytes = hipMemcpyAsync device to device of 14 bytes per parameter (28 moved); (d) host_route = wall clock of '
+                       'gradient fetch + NumPy Adam + 82 x pmx_set_layer + the next forward + backward', entries=out), f, indent=1)
+        f.write('\n')
+
+
+if __name__ == '__main__':
+    main()
