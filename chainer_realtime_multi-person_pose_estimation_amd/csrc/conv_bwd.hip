@@ -16,6 +16,7 @@
 //   order            an accumulator element sees fmaf(g, x, acc) for the pixels of its strip in row-major order: the MFMA adds its two K
 //                    slots in order (pixel p, then p + 1) and consecutive MFMAs of an accumulator are consecutive pixel pairs.
 #include "pmx_ctx.h"
+#include "wgrad_strips.h"
 
 #pragma clang fp contract(off)
 
@@ -221,42 +222,25 @@ int conv_bwd_db_launch(const float* g, int ldg, double* part, float* db, long lo
     return PMX_OK;
 }
 
-constexpr long long PMX_WGRAD_WAVES = 2048;      // 256 CUs x 4 SIMDs x 2
-static int wgrad_nci(int ks) { return ks == 7 ? 1 : ks == 3 ? 2 : 4; }
-static int wgrad_units(int cg, int cx, int ks)
+// the strip rules: wgrad_strips.h (plain C, shared with the tests' stand-alone program)
+int conv_wgrad_strips(int B, int H, int cg, int cx, int ks, int forced, int* rows) { return pmx_wgrad_strips_cap(B, H, cg, cx, ks, forced, PMX_WGRAD_MAX_STRIPS, 0, rows); }
+int conv_wgrad_trunk_strips(int B, int H, int cg, int cx, int forced, int* rows)
 {
-    const int nci = cx / 32, per = wgrad_nci(ks);
-    return (nci + per - 1) / per * ks * (cg / 32);
-}
-
-int conv_wgrad_strips(int B, int H, int cg, int cx, int ks, int forced, int* rows)
-{
-    const long long total = (long long)B * H;
-    long long s0 = forced;
-    if (s0 <= 0) {      // as many strips as give every SIMD of an MI355X two waves (a constant: the order must not depend on the device)
-        const long long units = wgrad_units(cg, cx, ks);
-        s0 = (PMX_WGRAD_WAVES + units - 1) / units;
-    }
-    if (s0 > PMX_WGRAD_MAX_STRIPS) s0 = PMX_WGRAD_MAX_STRIPS;
-    if (s0 > total) s0 = total;
-    if (s0 < 1) s0 = 1;
-    const long long r = (total + s0 - 1) / s0;
-    *rows = (int)r;
-    return (int)((total + r - 1) / r);
+    return pmx_wgrad_strips_cap(B, H, cg, cx, 3, forced, PMX_WGRAD_TRUNK_MAX_STRIPS, 1, rows);
 }
 
 int conv_wgrad_launch(const float* g, int ldg, const float* x, int ldx, float* ws, float* dw, int B, int H, int W, int cout, int cg, int cin, int cx,
-                      int ks, int strips, int rows, const int* cin_map, hipStream_t stream)
+                      int ks, int strips, int rows, const int* cin_map, hipStream_t stream, int max_strips)
 {
     const long long total = (long long)B * H;
     PMX_CHECK(cg % 32 == 0 && cx % 32 == 0 && cg >= cout && cx >= cin && ldg >= cg && ldx >= cx && (ks == 1 || ks == 3 || ks == 7), PMX_ERR_INVALID,
               "conv_wgrad: bad channels / ksize");
-    PMX_CHECK(rows >= 1 && strips >= 1 && strips <= PMX_WGRAD_MAX_STRIPS && (long long)(strips - 1) * rows < total && (long long)strips * rows >= total,
+    PMX_CHECK(rows >= 1 && strips >= 1 && strips <= max_strips && (long long)(strips - 1) * rows < total && (long long)strips * rows >= total,
               PMX_ERR_INVALID, "conv_wgrad: %d strips of %d rows do not cover %lld rows", strips, rows, total);
     PMX_CHECK((long long)W * ldx * 4 < (1ll << 31), PMX_ERR_INVALID, "conv_wgrad: row of %d x %d floats too long", W, ldx);
     WgradArgs a;
     a.g = g; a.x = x; a.ws = ws; a.H = H; a.W = W; a.cg = cg; a.cx = cx; a.nco = cg / 32; a.nci = cx / 32; a.ldg = ldg; a.ldx = ldx;
-    a.n_units = wgrad_units(cg, cx, ks); a.rows = rows; a.total_rows = total;
+    a.n_units = pmx_wgrad_units(cg, cx, ks); a.rows = rows; a.total_rows = total;
     const dim3 grid((a.n_units + 3) / 4, strips);
     if (ks == 7) hipLaunchKernelGGL((conv_wgrad_kernel<7, 1>), grid, dim3(256), 0, stream, a);
     else if (ks == 3) hipLaunchKernelGGL((conv_wgrad_kernel<3, 2>), grid, dim3(256), 0, stream, a);
@@ -356,6 +340,173 @@ int bwd_copy_cols_launch(const float* src, int lds, float* dst, int ldd, long lo
 {
     PMX_CHECK(src && dst && npix >= 1 && nch >= 1 && lds >= nch && ldd >= nch, PMX_ERR_INVALID, "bwd_copy_cols: bad arguments");
     hipLaunchKernelGGL(bwd_copy_cols_kernel, dim3(bwd_blocks(npix * nch)), dim3(256), 0, stream, src, lds, dst, ldd, npix, nch);
+    PMX_HIP(hipGetLastError());
+    return PMX_OK;
+}
+
+// ------------------------------------------------------------------------------------------ trunk backward (pmx_backward.hip)
+// conv1_1's weight gradient, dw[64][3][3][3]: x is the network input at PMX_IN_C = 16 floats per pixel, 3 of them real, so the generic
+// kernel's 32-channel x tiles would be 29 / 32 zeros.  Here the 32 B columns of the MFMA are the 27 (ci, tap) pairs themselves, column
+// l = ci * 9 + ky * 3 + kx -- the OIHW order of one co's 27 weights -- and 5 zero columns: lane l < 27 loads x[p + tap(l)][ci(l)], zero
+// outside the image.  A = 32 co of pixel p (lanes 0-31) and of pixel p + 1 (lanes 32-63), as in conv_wgrad_kernel.  One wave owns one strip
+// and keeps BOTH co tiles (2 x 16 accumulator registers), so x is fetched once per pixel pair: per pair a lane loads one float of x and
+// two of g.  The four waves of a block are four consecutive strips.  A strip's accumulators go to its slot [strip][co 64][32] of the
+// workspace; conv1_wgrad_combine_kernel adds the slots left to right.  The order per element is conv_wgrad_kernel's (the header's twin
+// with cin = 3): fmaf(g, x, acc) over the strip's pixels in row-major order, pixel p before p + 1 inside an MFMA.  No atomics.
+namespace {
+
+struct Wgrad1Args {
+    const float* g; const float* x; float* ws;
+    int H, W, rows, strips, ldg;                    // rows: image rows per strip; ldg: floats per pixel of g (>= 64)
+    long long total_rows;                           // B * H
+};
+
+__global__ void __launch_bounds__(256) conv1_wgrad_kernel(Wgrad1Args a)
+{
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, half = lane >> 5, l = lane & 31;
+    const int strip = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave);
+    if (strip >= a.strips) return;                  // (no barrier below: a wave may leave alone)
+    const long long r0 = (long long)strip * a.rows;
+    const long long r1 = r0 + a.rows < a.total_rows ? r0 + a.rows : a.total_rows;
+    const long long p0 = r0 * a.W, p1 = r1 * a.W;   // the strip's pixels [p0, p1) of the batch's B * H * W
+    const int H = a.H, W = a.W;
+    const bool col = l < 27;                        // (columns 27 .. 31 multiply zeros and are not written back)
+    const int ci = col ? l / 9 : 0, tap = col ? l % 9 : 4, dy = tap / 3 - 1, dx = tap % 3 - 1;
+
+    f32x16 acc[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
+
+    long long q = p0 + half;
+    int xq = (int)(q % W), yq = (int)((q / W) % H);
+    const float* gq = a.g + q * a.ldg + l;
+    const float* xp = a.x + (q + (long long)dy * W + dx) * PMX_IN_C + ci;
+    // as in conv_wgrad_kernel: the operands of the NEXT pixel pair are fetched before the MFMAs of the current one; every lane always
+    // loads -- a lane without an operand reads an address that is in bounds -- and the value is replaced by 0 when it is used
+    auto fetch = [&](float& g0, float& g1, float& xv, unsigned& m) {
+        const bool live = q < p1;
+        const bool ok = live && col && (unsigned)(yq + dy) < (unsigned)H && (unsigned)(xq + dx) < (unsigned)W;
+        const float* gp = live ? gq : a.g + l;
+        g0 = gp[0]; g1 = gp[32];
+        xv = *(ok ? xp : a.x + (l & 15));
+        m = (live ? 1u : 0u) | (ok ? 2u : 0u);
+        q += 2; gq += 2 * a.ldg; xp += 2 * PMX_IN_C;
+        xq += 2;
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+            if (xq >= W) { xq -= W; yq = yq + 1 == H ? 0 : yq + 1; }
+    };
+    float g0, g1, xv;
+    unsigned mv;
+    fetch(g0, g1, xv, mv);
+    const long long pairs = (p1 - p0 + 1) / 2;
+    for (long long it = 0; it < pairs; ++it) {
+        float n0, n1, nx;
+        unsigned mn;
+        fetch(n0, n1, nx, mn);
+        const float b = mv & 2u ? xv : 0.f;
+        acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(mv & 1u ? g0 : 0.f, b, acc[0], 0, 0, 0);
+        acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(mv & 1u ? g1 : 0.f, b, acc[1], 0, 0, 0);
+        g0 = n0; g1 = n1; xv = nx; mv = mn;
+    }
+    // D[i][j]: i = co (the A rows), j = column l; lane: j = l, i = (e & 3) + 8 * (e >> 2) + 4 * half
+    if (!col) return;
+    float* o = a.ws + (size_t)strip * (64 * 32) + l;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) o[(size_t)(t * 32 + (e & 3) + 8 * (e >> 2) + 4 * half) * 32] = acc[t][e];
+}
+
+// dw[co][ci][ky][kx] = dw[co * 27 + l]: the strips' slots added left to right; one thread per element
+__global__ void __launch_bounds__(64) conv1_wgrad_combine_kernel(const float* ws, float* dw, int strips)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= 64 * 27) return;
+    const float* p = ws + (size_t)(i / 27) * 32 + i % 27;
+    float s = p[0];
+    for (int k = 1; k < strips; ++k) s = s + p[(size_t)k * (64 * 32)];
+    dw[i] = s;
+}
+
+// F.max_pooling_2d(a, 2, 2) on NHWC, one thread per (pooled pixel, channel): the first maximum in window order (0,0), (0,1), (1,0), (1,1)
+__global__ void __launch_bounds__(256) maxpool_nhwc_kernel(const float* a, int lda, float* out, int ldo, int B, int H, int W, int nch)
+{
+    const int Ho = H / 2, Wo = W / 2;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)B * Ho * Wo * nch) return;
+    const int ch = (int)(i % nch);
+    const long long op = i / nch;
+    const int ox = (int)(op % Wo), oy = (int)((op / Wo) % Ho), n = (int)(op / ((long long)Wo * Ho));
+    const float* p = a + (((size_t)n * H + 2 * oy) * W + 2 * ox) * lda + ch;
+    float m = p[0];
+    const float v1 = p[lda], v2 = p[(size_t)W * lda], v3 = p[(size_t)(W + 1) * lda];
+    if (v1 > m) m = v1;
+    if (v2 > m) m = v2;
+    if (v3 > m) m = v3;
+    out[(size_t)op * ldo + ch] = m;
+}
+
+// the gradient through relu + 2 x 2 max-pool, read from the post-ReLU, pre-pool output a alone: u (pooled size) goes to the FIRST maximum of
+// its window of a (strictly greater in window order, conv_bwd_mask_kernel's rule) if that a > 0; +0.0f in the other positions.  One thread
+// per (pooled pixel, channel) writes the four elements of its window: every element of g by exactly one thread.
+__global__ void __launch_bounds__(256) pool_bwd_nhwc_kernel(const float* u, int ldu, const float* a, int lda, float* g, int ldg, int B, int H, int W, int nch)
+{
+    const int Ho = H / 2, Wo = W / 2;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)B * Ho * Wo * nch) return;
+    const int ch = (int)(i % nch);
+    const long long op = i / nch;
+    const int ox = (int)(op % Wo), oy = (int)((op / Wo) % Ho), n = (int)(op / ((long long)Wo * Ho));
+    const size_t base = ((size_t)n * H + 2 * oy) * W + 2 * ox;
+    float av[4], am = 0.f;
+    int best = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        av[k] = a[(base + (size_t)(k >> 1) * W + (k & 1)) * lda + ch];
+        if (k == 0 || av[k] > am) { am = av[k]; best = k; }      // strictly greater: the first of equal maxima stays
+    }
+    const float d = u[(size_t)op * ldu + ch];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) g[(base + (size_t)(k >> 1) * W + (k & 1)) * ldg + ch] = k == best && av[k] > 0.f ? d : 0.f;
+}
+
+}  // namespace
+
+int conv1_wgrad_strips(int B, int H, int forced, int* rows) { return pmx_wgrad_conv1_strips(B, H, forced, PMX_WGRAD_CONV1_STRIPS, rows); }
+
+int conv1_wgrad_launch(const float* g, int ldg, const float* x16, float* ws, float* dw, int B, int H, int W, int strips, int rows, hipStream_t stream)
+{
+    const long long total = (long long)B * H;
+    PMX_CHECK(g && x16 && ws && dw && B >= 1 && H >= 1 && W >= 1 && ldg >= 64, PMX_ERR_INVALID, "conv1_wgrad: bad arguments");
+    PMX_CHECK(rows >= 1 && strips >= 1 && strips < 2 * PMX_WGRAD_CONV1_STRIPS && (long long)(strips - 1) * rows < total && (long long)strips * rows >= total,
+              PMX_ERR_INVALID, "conv1_wgrad: %d strips of %d rows do not cover %lld rows", strips, rows, total);
+    PMX_CHECK(total * W >= 2, PMX_ERR_INVALID, "conv1_wgrad: %lld pixels", total * W);      // (a lane without an operand reads floats 0 .. 31 of g, 0 .. 15 of x)
+    Wgrad1Args a;
+    a.g = g; a.x = x16; a.ws = ws; a.H = H; a.W = W; a.rows = rows; a.strips = strips; a.ldg = ldg; a.total_rows = total;
+    hipLaunchKernelGGL(conv1_wgrad_kernel, dim3((strips + 3) / 4), dim3(256), 0, stream, a);
+    PMX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(conv1_wgrad_combine_kernel, dim3(27), dim3(64), 0, stream, (const float*)ws, dw, strips);
+    PMX_HIP(hipGetLastError());
+    return PMX_OK;
+}
+
+int maxpool_nhwc_launch(const float* a, int lda, float* out, int ldo, int B, int H, int W, int nch, hipStream_t stream)
+{
+    PMX_CHECK(a && out && B >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0 && nch >= 1 && lda >= nch && ldo >= nch, PMX_ERR_INVALID,
+              "maxpool_nhwc: bad arguments");
+    hipLaunchKernelGGL(maxpool_nhwc_kernel, dim3(bwd_blocks((long long)B * (H / 2) * (W / 2) * nch)), dim3(256), 0, stream, a, lda, out, ldo, B, H, W, nch);
+    PMX_HIP(hipGetLastError());
+    return PMX_OK;
+}
+
+int pool_bwd_nhwc_launch(const float* u, int ldu, const float* a, int lda, float* g, int ldg, int B, int H, int W, int nch, hipStream_t stream)
+{
+    PMX_CHECK(u && a && g && B >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0 && nch >= 1 && ldu >= nch && lda >= nch && ldg >= nch,
+              PMX_ERR_INVALID, "pool_bwd_nhwc: bad arguments");
+    hipLaunchKernelGGL(pool_bwd_nhwc_kernel, dim3(bwd_blocks((long long)B * (H / 2) * (W / 2) * nch)), dim3(256), 0, stream, u, ldu, a, lda, g, ldg, B, H, W, nch);
     PMX_HIP(hipGetLastError());
     return PMX_OK;
 }

@@ -504,6 +504,7 @@ extern "C" int pmx_set_option(pmx_ctx* c, const char* key, int value)
     else if (!strcmp(key, "peaks_gpu_branch")) { c->opt_gpu_branch_peaks = value; c->tab_in_h = -1; }
     else if (!strcmp(key, "kp_flip_x")) c->opt_kp_flip_x = value != 0;
     else if (!strcmp(key, "wgrad_strips")) c->opt_wgrad_strips = value;
+    else if (!strcmp(key, "trunk_keep_g")) c->opt_trunk_keep_g = value != 0;
     else { pmx_set_error("pmx_set_option: unknown key '%s'", key); return PMX_ERR_INVALID; }
     return PMX_OK;
 }
@@ -952,8 +953,18 @@ static bool conv1_pairable(const pmx_ctx* c)
     const PackedLayer& L2 = c->layers[c->index.at("conv1_2")];
     return c->opt_precision == 0 && c->opt_force[3] < 0 && L1.cin == 3 && L1.cout == 64 && L2.cin == 64 && L2.cout == 64;
 }
+// a forward that retains the trunk (pmx_backward_enable(ctx, 2); the conditions of pmx_forward_from_in16's `keep`): conv1_1 and conv1_2 run
+// as two launches that store both outputs, so neither fused form applies and a uint8 input is preprocessed into in16 first
+static bool trunk_retaining(const pmx_ctx* c)
+{
+    return c->bw.on == 2 && c->kind == NET_POSE && c->ls_on && c->lg_on && c->opt_precision == 0 && c->segs.empty();
+}
 static bool conv1_form(const pmx_ctx* c, int B, int H, int W, bool* fuse_out)
 {
+    if (trunk_retaining(c)) {
+        if (fuse_out) *fuse_out = false;
+        return false;
+    }
     const PackedLayer& L1 = c->layers[c->index.at("conv1_1")];
     const PackedLayer& L2 = c->layers[c->index.at("conv1_2")];
     const int v2 = conv_pick_variant(3, L2.cout_pad, H, W, B, c->opt_force[3], c->opt_kernel_gen, 1, L2.cin, 0);
@@ -1038,6 +1049,35 @@ static int run_stem(pmx_ctx* c, int B, int H, int W, float* last_out = nullptr)
     return rc;
 }
 
+// The stem of a forward that retains the trunk (BwState in pmx_ctx.h; include/pose_mi355x.h: pmx_backward_enable, mode 2): every layer
+// writes its post-ReLU output into its slot of the trunk store with its own launch, the three pooling layers un-pooled, and
+// maxpool_nhwc_kernel writes the pooled map the next layer reads.  conv4_2 writes x42, as in mode 1.
+static int run_stem_retaining(pmx_ctx* c, int B, int H, int W, float* x42)
+{
+    BwState& bw = c->bw;
+    PMX_CHECK(!c->in_u8, PMX_ERR_STATE, "retaining stem: a uint8 input that no kernel preprocesses");
+    PMX_CHECK((size_t)B * H * W <= bw.cap_px * 64, PMX_ERR_CAPACITY, "forward: %d x %d x %d input pixels, the trunk store holds %zu", B, H, W, bw.cap_px * 64);
+    const float* in = c->in16;
+    int lda = PMX_IN_C, pools = 0, rc;
+    for (int t = 0; t < PMX_TRUNK_LAYERS; ++t) {
+        const TrunkDesc& d = pmx_trunk_desc[t];
+        const int h = H >> d.level, w = W >> d.level;
+        float* out = t == PMX_TRUNK_LAYERS - 1 ? x42 : bw.t_act + bw.t_a_off[t];
+        if ((rc = run_conv(c, d.name, &c->layers[bw.t_layer[t]], nullptr, in, nullptr, lda, out, nullptr, d.cout, B, h, w, 1, 0, d.level))) return rc;
+        in = out; lda = d.cout;
+        if (!d.pool) continue;
+        float* pooled = bw.t_act + bw.t_p_off[pools++];
+        if (c->prof_on == 1) {
+            const std::string label = std::string("pool:") + d.name + "|maxpool_nhwc";
+            if ((rc = prof_begin(c, label, 0, 4.0 * B * h * w * d.cout * 1.25))) return rc;
+        }
+        if ((rc = maxpool_nhwc_launch(out, d.cout, pooled, d.cout, B, h, w, d.cout, c->stream))) return rc;
+        if ((rc = prof_end(c))) return rc;
+        in = pooled;
+    }
+    return PMX_OK;
+}
+
 // FaceNet / HandNet forward (models/FaceNet.py:78-160): one branch, groups = 1 everywhere
 static int forward_cpm(pmx_ctx* c, int B, int H, int W)
 {
@@ -1096,7 +1136,7 @@ int pmx_forward_from_in16(pmx_ctx* c, int B, int H, int W)
     // instead of act1 / act0 / brA / brB / brT (same leading dimensions: same plans, same bits), the 1x1 pairs unfused
     BwState& bw = c->bw;
     const bool keep = bw.on && hook && c->lg_on && c->opt_precision == 0;
-    bw.valid = bw.done = false;
+    bw.valid = bw.done = bw.trunk_done = false;
     const long long npix8 = (long long)B * H8 * W8;
     PMX_CHECK(!keep || (size_t)npix8 <= bw.cap_px, PMX_ERR_CAPACITY, "forward: %lld map pixels, the backward store holds %zu", npix8, bw.cap_px);
     auto slot = [&](int k, float* else_) { return keep ? bw.act + bw.slot[k].a_off : else_; };
@@ -1107,7 +1147,7 @@ int pmx_forward_from_in16(pmx_ctx* c, int B, int H, int W)
     };
     // stem (CocoPoseNet.py:136-151)
     // (the last argument = the resolution level, read only by a heterogeneous forward: pmx_multi.hip)
-    if ((rc = run_stem(c, B, H, W, keep ? x42 : nullptr))) return rc;
+    if ((rc = keep && bw.on == 2 ? run_stem_retaining(c, B, H, W, x42) : run_stem(c, B, H, W, keep ? x42 : nullptr))) return rc;
     RUN("conv4_3_CPM", L("conv4_3_CPM"), nullptr, x42, nullptr, 512, a43, nullptr, 256, B, H8, W8, 1, 0, 3);
     RUN("conv4_4_CPM", L("conv4_4_CPM"), nullptr, a43, nullptr, 256, c->cat + PMX_CAT_FEAT, nullptr, PMX_CAT_C, B, H8, W8, 1, 0, 3);
     // stage 1 (CocoPoseNet.py:154-165); L1 = PAF branch, L2 = heat-map branch
@@ -1151,7 +1191,7 @@ int pmx_forward_from_in16(pmx_ctx* c, int B, int H, int W)
         if ((rc = keep_stage(PMX_BW_M(s, 7)))) return rc;
     }
     if (hook && (rc = pmx_loss_finish(c, n_stages, B, H8, W8))) return rc;
-    if (keep) { bw.valid = true; bw.stages = n_stages; bw.B = B; bw.fh = H8; bw.fw = W8; }
+    if (keep) { bw.valid = true; bw.stages = n_stages; bw.B = B; bw.fh = H8; bw.fw = W8; bw.t_H = H; bw.t_W = W; }
 #undef RUN
     c->maps_valid = true; c->maps_external = false;
     c->cur_B = B; c->cur_fh = H8; c->cur_fw = W8;

@@ -133,7 +133,7 @@ enum { PMX_BW_C43 = 0, PMX_BW_C44 = 1, PMX_BW_S1 = 2, PMX_BW_M2 = 7, PMX_BW_X42 
 #define PMX_BW_M(s, i) (PMX_BW_M2 + ((s) - 2) * 7 + (i) - 1)
 struct BwSlot { size_t a_off = 0, g_off = 0; int lda = 0, ldg = 0; };
 struct BwState {
-    int on = 0;                                           // pmx_backward_enable
+    int on = 0;                                           // pmx_backward_enable: 0 off, 1 the head, 2 the head and the trunk
     bool valid = false;                                   // the last forward retained (cleared by every other forward)
     bool done = false;                                    // pmx_backward_head ran for it
     int stages = 0, B = 0, fh = 0, fw = 0;                // ... its stages and shape
@@ -141,7 +141,7 @@ struct BwState {
     BwSlot slot[PMX_BW_SLOTS];
     DevBuf<float> act, g;                                 // the two stores
     DevBuf<float> grad;                                   // dw (OIHW) | db of every layer: grad_off[layer], then cout * cin * ks^2 floats further
-    std::vector<size_t> grad_off;                         // by index into c->table (trunk layers: unused)
+    std::vector<size_t> grad_off;                         // by index into c->table (trunk layers: mode 2 only, after every head layer's)
     DevBuf<float> u;                                      // dx of the layer just run = the upstream gradient of the one before: [pixel][<= 1024]
     DevBuf<float> dcat;                                   // dx of Mconv1_stage{s}_L1 | _L2 in concat-buffer order: [pixel][2 x 192]
     DevBuf<float> fg;                                     // the running sum at the feature map: [pixel][128]
@@ -153,7 +153,21 @@ struct BwState {
     bool stepped = false;                                 // pmx_train_step_head consumed the gradients of this backward
     int slot_layer[PMX_BW_SLOTS][2] = {};                 // table index of the slot's L1 / L2 layer (one-branch slots: both the same; X42: conv4_2)
     std::vector<int> layer_slot;                          // by table index: slot * 2 + branch, -1 for the trunk layers before conv4_2
+    // Trunk backward (mode 2; include/pose_mi355x.h: pmx_backward_trunk).  The ten layers conv1_1 .. conv4_2 in forward order, t = 0 .. 9, at
+    // resolution level 0, 0, 1, 1, 2, 2, 2, 2, 3, 3 (level l: h / 2^l x w / 2^l).  `t_act` holds, NHWC with the layer's own channel count per
+    // pixel: the post-ReLU, PRE-pool output a of t = 0 .. 8 at t_a_off[t] (conv4_2's is slot PMX_BW_X42) and the pooled maps of conv1_2,
+    // conv2_2, conv3_4 at t_p_off[0 .. 2].  One pair of gradient buffers serves the whole chain, each as large as the widest layer (64
+    // floats per input pixel): t_g = the masked gradient g of the layer being run, t_u = its dx, the upstream gradient of the layer before.
+    // t_gk (option "trunk_keep_g" at enable time; tests): a g slot per layer at t_g_off[t] instead of the shared t_g, for pmx_get_retained.
+    bool trunk_done = false;                              // pmx_backward_trunk ran for the retained forward
+    int t_H = 0, t_W = 0;                                 // the retained forward's network-input size
+    int t_layer[10] = {};                                 // table index of trunk layer t
+    size_t t_a_off[10] = {}, t_p_off[3] = {}, t_g_off[10] = {};
+    DevBuf<float> t_act, t_u, t_g, t_gk;
 };
+constexpr int PMX_TRUNK_LAYERS = 10;
+struct TrunkDesc { const char* name; int cin, cout, level, pool; };      // pool: the forward pools this layer's output
+extern const TrunkDesc pmx_trunk_desc[PMX_TRUNK_LAYERS];
 
 // Head training step (pmx_train.hip; include/pose_mi355x.h: pmx_train_*).  Three stores with the layout of BwState::grad -- per head layer
 // w | b at grad_off[layer], padded to a multiple of 64 floats: the master weights (OIHW, reference input order), Adam's first and second
@@ -320,6 +334,7 @@ struct pmx_ctx {
     int lg_stages = 0, lg_B = 0, lg_fh = 0, lg_fw = 0;    // the hooked forward whose gradients ls_grad holds (lg_stages 0: none)
     // pmx_conv2d_backward: test-only, S0 of the weight-gradient strips (0: automatic); include/pose_mi355x.h
     int opt_wgrad_strips = 0;
+    int opt_trunk_keep_g = 0;        // read by pmx_backward_enable(2): keep the masked gradient of every trunk layer for pmx_get_retained (tests)
     // pmx_samples.hip (sample preparation).  sp_host / sp_dev: the per-call block [descriptors | resize tables | host sources], ONE copy from
     // pinned memory (`sp_copied` marks when the host side may be rewritten); sp_a: the resized intermediates of the training samples; sp_out:
     // max_batch x insize x insize x 3 prepared images; sp_mask_raw / sp_mask_tmp / sp_mask: the mask before, between and after the two
@@ -383,11 +398,21 @@ constexpr int PMX_DB_SLOTS = 64;
 int conv_bwd_mask_launch(const float* dy_nchw, const float* z_nhwc, int ldz, float* g, int B, int H, int W, int cout, int cg, int relu, int pool,
                          hipStream_t stream);
 // (ldg / ldx: floats per pixel of g / x, >= cg / cx -- the operands may be slices of wider buffers; cin_map, device memory or null: the
-// channel of x that holds input channel ci of dw)
+// channel of x that holds input channel ci of dw; max_strips: the largest strip count the caller's rule can give)
 int conv_bwd_db_launch(const float* g, int ldg, double* part, float* db, long long npix, int cout, int cg, hipStream_t stream);
 int conv_wgrad_launch(const float* g, int ldg, const float* x, int ldx, float* ws, float* dw, int B, int H, int W, int cout, int cg, int cin, int cx,
-                      int ks, int strips, int rows, const int* cin_map, hipStream_t stream);
+                      int ks, int strips, int rows, const int* cin_map, hipStream_t stream, int max_strips = PMX_WGRAD_MAX_STRIPS);
 int conv_wgrad_strips(int B, int H, int cg, int cx, int ks, int forced, int* rows);      // S and, in *rows, R of the header's rule
+int conv_wgrad_trunk_strips(int B, int H, int cg, int cx, int forced, int* rows);        // ... of the trunk chain's rule (3x3 layers)
+// conv_bwd.hip: the trunk backward's own launches (include/pose_mi355x.h: pmx_backward_trunk)
+//   conv1_wgrad  dw[64][3][3][3] of conv1_1 from g (ldg >= 64 floats per pixel) and the prepared input x16 (PMX_IN_C floats per pixel);
+//                ws: strips x 64 x 32 floats; (strips, rows) from conv1_wgrad_strips (forced <= 0: the rule)
+//   maxpool      out [B][H/2][W/2][nch] = the 2 x 2 maximum of a [B][H][W][nch]
+//   pool_bwd     g [B][H][W][nch] from u [B][H/2][W/2][nch] and a: u at the first maximum of each window where a > 0, +0.0f elsewhere
+int conv1_wgrad_strips(int B, int H, int forced, int* rows);
+int conv1_wgrad_launch(const float* g, int ldg, const float* x16, float* ws, float* dw, int B, int H, int W, int strips, int rows, hipStream_t stream);
+int maxpool_nhwc_launch(const float* a, int lda, float* out, int ldo, int B, int H, int W, int nch, hipStream_t stream);
+int pool_bwd_nhwc_launch(const float* u, int ldu, const float* a, int lda, float* g, int ldg, int B, int H, int W, int nch, hipStream_t stream);
 // conv_bwd.hip: the elementwise steps of the head backward, NHWC (the sums' orders: include/pose_mi355x.h, pmx_backward_head)
 //   mask       g = u where a > 0, +0.0f elsewhere, nch channels of every pixel (a null: g = u)
 //   stage_sum  g [pixel][128] = loss_grad (+ d0 + d1: dx of the next stage's Mconv1_L1 / _L2 in concat-buffer order, both null for the last stage)

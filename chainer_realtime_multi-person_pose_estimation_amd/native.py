@@ -35,7 +35,7 @@ SOURCES = [('pmx_api.hip', []), ('pmx_precise.hip', []), ('pmx_multi.hip', []), 
 # library is rebuilt when the variable changes)
 if os.environ.get('PMX_BUILD_BF16X3', '') not in ('', '0'):
     SOURCES.append(('conv_bf16x3.hip', []))
-HEADERS = ['pmx_common.h', 'pmx_ctx.h', 'pp_tables.h', 'wino_util.h', 'conv_direct.h', 'pp_smooth.h', 'conv_bwd_pack.h', 'pack_index.h', HEADER]
+HEADERS = ['pmx_common.h', 'pmx_ctx.h', 'pp_tables.h', 'wino_util.h', 'conv_direct.h', 'pp_smooth.h', 'conv_bwd_pack.h', 'pack_index.h', 'wgrad_strips.h', HEADER]
 
 N_JOINTS, N_LIMBS, N_PAF, N_HEAT = 18, 19, 38, 19
 # the detectors' precision= keyword -> engine option "precision" (include/pose_mi355x.h): fp32 (default), bf16x3 (opt-in build), f16 mode
@@ -324,6 +324,9 @@ def load():
         'pmx_get_loss_grads': (ci, [vp, ci, vp, vp]),
         'pmx_backward_enable': (ci, [vp, ci]),
         'pmx_backward_head': (ci, [vp]),
+        'pmx_backward_trunk': (ci, [vp]),
+        'pmx_conv1_wgrad': (ci, [vp, vp, vp, ci, ci, ci, ci, vp, ip, ip]),
+        'pmx_pool_backward_test': (ci, [vp, vp, vp, ci, ci, ci, ci, vp, vp]),
         'pmx_get_layer_grad': (ci, [vp, C.c_char_p, vp, vp]),
         'pmx_get_trunk_grad': (ci, [vp, vp]),
         'pmx_get_retained': (ci, [vp, C.c_char_p, ci, vp]),
@@ -941,10 +944,37 @@ class Engine(object):
             return 0 if name.startswith('conv4') else 1 if name.startswith('conv5') else int(name.split('stage')[1][0])
         return [n for n in self._layers if n not in self.TRUNK_LAYERS and stage(n) <= n_stages]
 
+    TRUNK_LEVEL = dict(zip(TRUNK_LAYERS, (0, 0, 1, 1, 2, 2, 2, 2, 3, 3)))      # resolution level of a trunk layer's output before any pool
+    POOLED_LAYERS = ('conv1_2', 'conv2_2', 'conv3_4')
+
     def backward_enable(self, on=True):
-        """on: allocates the activation and gradient stores at the context's capacity; from then on a hooked uniform fp32 forward with the
-        loss gradients on retains the outputs of the 82 layers after conv4_2.  off: frees the stores."""
-        self._check(self.lib.pmx_backward_enable(self._ctx, int(bool(on))))
+        """on (True / 1): allocates the activation and gradient stores at the context's capacity; from then on a hooked uniform fp32 forward
+        with the loss gradients on retains the outputs of the 82 layers after conv4_2.  on = 2: the trunk's stores as well, and such a
+        forward also retains conv1_1 .. conv4_1 and the pooled maps (backward_trunk).  off: frees the stores."""
+        self._check(self.lib.pmx_backward_enable(self._ctx, 2 if on == 2 else int(bool(on))))
+
+    def backward_trunk(self):
+        """Enqueue the backward of conv4_2 .. conv1_1 after backward_head for the same retained forward (mode 2; no synchronisation)."""
+        self._check(self.lib.pmx_backward_trunk(self._ctx))
+
+    def conv1_wgrad(self, x, g, strips=0):
+        """Test entry: conv1_1's weight-gradient kernel on x (B, 3, H, W) and g (B, 64, H, W) -> (dw (64, 3, 3, 3), strips, rows)."""
+        x, g = np.ascontiguousarray(x, dtype=np.float32), np.ascontiguousarray(g, dtype=np.float32)
+        B, _, H, W = x.shape
+        assert x.shape == (B, 3, H, W) and g.shape == (B, 64, H, W)
+        dw = np.empty((64, 3, 3, 3), np.float32)
+        s, r = C.c_int(0), C.c_int(0)
+        self._check(self.lib.pmx_conv1_wgrad(self._ctx, _ptr(x), _ptr(g), B, H, W, int(strips), _ptr(dw), C.byref(s), C.byref(r)))
+        return dw, s.value, r.value
+
+    def pool_backward_test(self, a, u):
+        """Test entry: the NHWC max-pool kernel and the pooled layers' g kernel on a (B, C, H, W) and u (B, C, H/2, W/2) -> (pooled, g)."""
+        a, u = np.ascontiguousarray(a, dtype=np.float32), np.ascontiguousarray(u, dtype=np.float32)
+        B, ch, H, W = a.shape
+        assert u.shape == (B, ch, H // 2, W // 2)
+        pooled, g = np.empty(u.shape, np.float32), np.empty(a.shape, np.float32)
+        self._check(self.lib.pmx_pool_backward_test(self._ctx, _ptr(a), _ptr(u), B, ch, H, W, _ptr(pooled), _ptr(g)))
+        return pooled, g
 
     def backward_head(self):
         """Enqueue the backward of the 82 layers after conv4_2 for the last retained forward (no synchronisation)."""
@@ -966,10 +996,12 @@ class Engine(object):
 
     def retained(self, name, which=0):
         """Parity accessor: (B, cout, h/8, w/8) float32, which = 0 the retained output of layer `name` ('conv4_2' included), 1 its masked
-        gradient after backward_head (synchronises)."""
+        gradient after backward_head (synchronises).  With backward_enable(2) also the trunk layers at their own resolution (which = 0 the
+        pre-pool output, 1 g after backward_trunk with option 'trunk_keep_g', 2 the pooled map of a pooled layer) and 'input' (B, 3, h, w)."""
         B, h, w = self._grad_shape if self._grad_shape is not None else (1, 8, 8)
-        cout = self._layers[name][0].shape[0] if name in self._layers else 1
-        out = np.empty((B, cout, h // 8, w // 8), np.float32)
+        cout = 3 if name == 'input' else self._layers[name][0].shape[0] if name in self._layers else 1
+        down = 1 if name == 'input' else 8 >> (3 - self.TRUNK_LEVEL.get(name, 3)) << (1 if which == 2 else 0)
+        out = np.empty((B, cout, h // down, w // down), np.float32)
         self._check(self.lib.pmx_get_retained(self._ctx, name.encode(), int(which), _ptr(out)))
         return out
 

@@ -650,6 +650,41 @@ class PoseDetector(object):
                 'paf_stages': [float(v) for v in paf], 'heat_stages': [float(v) for v in heat],
                 'paf_grads': [g[0] for g in grads], 'heat_grads': [g[1] for g in grads], 'grads': layer_grads, 'trunk_grad': trunk}
 
+    def network_gradients(self, imgs, poses_per_image, ignore_masks=None):
+        """`head_gradients` continued through conv4_2 .. conv1_1: the gradients of all 92 layers, what the reference's loss.backward() gives
+        once it has un-frozen the trunk (train_coco_pose_estimation.py:96-101, from iteration 2000 on).  Arguments and result as
+        head_gradients, 'grads' with 92 entries.  The forward retains the trunk (engine mode 2), so its stem runs unfused.  More images than
+        the engine's batch raise ValueError; not available while the head is being trained (stop_training first)."""
+        imgs, poses, masks = self._check_validation_args(imgs, poses_per_image, ignore_masks)
+        if self.model is not None:
+            raise RuntimeError('network_gradients runs the built-in network: not available with a model= callable')
+        if self._train_on:
+            raise RuntimeError('network_gradients needs the trunk retained, training retains the head alone: call stop_training() first')
+        if self.engine.weights_missing():
+            raise RuntimeError('PoseDetector has no weights: pass weights_file=, weights= or model=')
+        h, w = imgs[0].shape[:2]
+        self._grow(1, h, w)
+        if len(imgs) > self._cap[0]:
+            raise ValueError('network_gradients: %d images, the engine holds batches of %d (the gradients of chunks cannot be merged)'
+                             % (len(imgs), self._cap[0]))
+        eng = self.engine
+        eng.loss_set_poses(poses, h, w, None if masks is None else np.stack(masks), params['heatmap_sigma'], params['paf_sigma'])
+        eng.loss_grad_enable(True)
+        try:
+            eng.backward_enable(2)
+            total, paf, heat = eng.validate_batch(np.stack(imgs))
+            eng.backward_head()
+            eng.backward_trunk()
+            grads = [eng.loss_grads(s) for s in range(6)]
+            layer_grads = {name: eng.layer_grad(name) for name in list(eng.TRUNK_LAYERS) + eng.head_layers()}
+            trunk = eng.trunk_grad()
+        finally:
+            eng.backward_enable(False)
+            eng.loss_grad_enable(False)
+        return {'val/loss': float(total), 'val/paf': float(paf.sum()), 'val/heat': float(heat.sum()),
+                'paf_stages': [float(v) for v in paf], 'heat_stages': [float(v) for v in heat],
+                'paf_grads': [g[0] for g in grads], 'heat_grads': [g[1] for g in grads], 'grads': layer_grads, 'trunk_grad': trunk}
+
     # ---- training of the head (reference train_coco_pose_estimation.py:204-235, its first 2000 iterations) -------------------------------
     REFERENCE_GRAD_SCALES = {'conv4_3_CPM': 0.25, 'conv4_4_CPM': 0.25}      # GradientScaling (train_coco_pose_estimation.py:222-223)
 

@@ -559,7 +559,7 @@ int pmx_conv2d_backward(pmx_ctx* ctx, const float* x_nchw, const float* w_oihw, 
  * conv4_3_CPM, conv4_4_CPM, the ten layers of stage 1 and the seventy of stages 2 - 6: the layers the reference updates while conv1_1 ..
  * conv4_2 are frozen (train_coco_pose_estimation.py:219-225).  All live at h/8 x w/8.  posenet contexts, uniform batches, fp32.
  *
- * pmx_backward_enable(on != 0) allocates, for max_batch images of max_h x max_w (PMX_ERR_CAPACITY if the device refuses; about 3 GB of
+ * pmx_backward_enable(on != 0; on = 2: the trunk as well, see "trunk backward" below) allocates, for max_batch images of max_h x max_w (PMX_ERR_CAPACITY if the device refuses; about 3 GB of
  * activations at 32 x 368 x 368, as much again for the gradients), and from then on a uniform fp32 forward that runs with the loss hook AND
  * the loss gradients on RETAINS what the backward reads: the post-ReLU output of each of the 82 layers and conv4_2's output, NHWC, written
  * by the layers' own launches into the store (never copied afterwards), with two exceptions --
@@ -602,6 +602,74 @@ int pmx_get_trunk_grad(pmx_ctx* ctx, float* g_nchw);
  * masked gradient g (after pmx_backward_head; not for "conv4_2"); NCHW float32 batch x cout x h/8 x w/8.  Errors as pmx_get_layer_grad;
  * which outside {0, 1}: PMX_ERR_INVALID.  Synchronises. */
 int pmx_get_retained(pmx_ctx* ctx, const char* name, int which, float* out_nchw);
+
+/* ---- trunk backward: the gradients of conv1_1 .. conv4_2 -----------------------------------------------------------------------------
+ * From iteration 2000 on the reference updates all 92 layers (train_coco_pose_estimation.py:96-101: enable_update on the ten trunk
+ * layers).  This chain continues where pmx_backward_head stops: at the gradient at conv4_2's output.  posenet, uniform batches, fp32.
+ *
+ * RETENTION.  pmx_backward_enable(ctx, 2) allocates what pmx_backward_enable(ctx, 1) allocates plus the trunk's stores; value 1 (and any
+ * other non-zero value) is the head alone, exactly as above -- its allocations, launches and bits, and the refusal of trunk names by the
+ * accessors; 0 frees everything.  Asking for 2 while 1 is on, or for 1 while 2 is on, is PMX_ERR_STATE: switch retention off first.
+ * PMX_ERR_CAPACITY, with the sizes in the message, if the device refuses.  With mode 2 on, under the conditions of the head (hook and loss
+ * gradients on, uniform batch, fp32), the stem writes into the trunk store with the layers' own launches, nothing copied afterwards:
+ *   conv1_1, conv1_2     two launches (neither fused conv1 kernel stores conv1_1's output); a uint8 input is preprocessed into the
+ *                        16-float input buffer first, which nothing overwrites before the backward
+ *   conv1_2, conv2_2,    run with pool = 0 and store their post-ReLU, PRE-pool output a; one launch of maxpool_nhwc_kernel each writes the
+ *   conv3_4              pooled map the next layer reads.  A maximum of four floats is exact; the gate and the argmax are read from a alone:
+ *                        a > 0 exactly when z > 0, and the first maximum of a = relu(z) is the first maximum F.max_pooling_2d(F.relu(z)) sees
+ * Retained, NHWC at the layer's own channel count: a of conv1_1 .. conv4_1 (conv4_2's is the head's slot), the three pooled maps, the
+ * prepared input (16 floats per pixel, where the forward holds it anyway).  With P = max_batch * max_h * max_w input pixels the store is
+ *   (64 + 64 + 128/4 + 128/4 + 4 * 256/16 + 512/64 + 64/4 + 128/16 + 256/64) * P = 292 * P floats      5.06 GB at 32 x 368 x 368,
+ * next to it the gradient pair u | g of 2 * 64 * P floats (2.22 GB; the widest layer, conv1_*; every other layer of the chain reuses the
+ * pair) and the ten gradient segments (5.9 M floats).  Per-layer g slots are NOT kept: they would cost 272 * P floats (4.71 GB at
+ * 32 x 368 x 368) for an accessor only the tests use.  Option "trunk_keep_g" = 1, read by pmx_backward_enable(ctx, 2), allocates them
+ * instead of the shared g buffer, so that pmx_get_retained(name, 1) can return a trunk layer's g; it changes no arithmetic.
+ * BITS.  A mode-2 forward takes other kernel forms in the stem than a non-retaining forward (unfused conv1, un-pooled launches + the pool
+ * kernel), so its maps and losses are not promised to equal those of modes 0 / 1 bit for bit (INTEGRATION.md section 5 records what was
+ * found); the backward differentiates the forward that ran.  Modes 0 and 1 keep their bits, launches and allocations.
+ *
+ * pmx_backward_trunk, asynchronous on the context's stream, after pmx_backward_head for the same retained forward, walks conv4_2 ..
+ * conv1_1.  NO SUMS: every trunk output has exactly one consumer, so u of a layer is the dx of the layer after it (conv4_2: the head's
+ * trunk gradient).  Per layer, at the layer's own resolution:
+ *   g    un-pooled layers: u where a > 0, +0.0f elsewhere (the head's mask launch).  Pooled layers: u has the pooled size; it goes to the
+ *        FIRST maximum of its 2 x 2 window of a, strictly greater in the order (0,0), (0,1), (1,0), (1,1) (pmx_conv2d_backward's rule), if
+ *        that a > 0, and the other positions get +0.0f.  One thread writes the four elements of a window; no atomics.
+ *   db   as pmx_conv2d_backward
+ *   dw   conv1_2 .. conv4_2: as pmx_conv2d_backward -- the same kernel and order per element -- with a strip rule of its own: S0 as
+ *        there (option "wgrad_strips" if > 0, else ceil(2048 / the layer's units of one wave each)), S0 <= PMX_WGRAD_TRUNK_MAX_STRIPS and
+ *        <= batch * h, but R = FLOOR(batch * h / S0) rows per strip, S = ceil(batch * h / R), so that S0 <= S < 2 * S0.  pmx_conv2d_backward's
+ *        R = ceil(...) gives S <= S0 and would leave conv1_2 (6 units; S0 = 342) with 335 strips = 2010 waves at 10 x 368 x 368; rounding R
+ *        down gives every trunk layer its 2048 waves wherever batch * h >= S0.  The workspace is S * 9 * cout * cin floats: below 57 MB per layer where
+ *        S = S0, below 114 MB at any size.  The head chain and pmx_conv2d_backward keep their rule, PMX_WGRAD_MAX_STRIPS and
+ *        their bits.
+ *        conv1_1: its own kernel (csrc/conv_bwd.hip: conv1_wgrad_kernel), which reads the input at its 16 floats per pixel: the 32 B
+ *        columns of v_mfma_f32_32x32x2_f32 are the 27 (ci, ky, kx) of one co and 5 zeros; one wave per strip keeps both 32-co tiles.
+ *        Its strip rule is the same with S0 = PMX_WGRAD_CONV1_STRIPS (or option "wgrad_strips"): at least 2048 waves whenever
+ *        batch * h >= 2048; workspace S * 64 * 32 floats (< 33.6 MB).
+ *        THE ORDER per element is the twin's of pmx_conv2d_backward (tests/conv_wgrad_twin.c with cin = 3 and the same (S, R)): fmaf over
+ *        the strip's pixels in row-major order, the odd strip's closing fmaf(0, 0, acc), the strips added left to right.  No atomics.
+ *        Option "wgrad_strips" forces S0 for all ten layers.
+ *   dx   the dispatcher on g with the transposed, 180-degree-rotated pack, relu = 0, pool = 0 (conv1_1: none, and no pack is built)
+ * The ten dw | db segments follow the head's in the gradient store, each padded to 64 floats; every head offset is as in mode 1, so
+ * pmx_train_enable / pmx_train_step_head work in mode 2 as in mode 1 and update the 82 head layers only (their stores are as large as
+ * the gradient store, so 3 x 23.5 MB larger).  A trunk training step does not exist yet.
+ * PMX_ERR_STATE, before anything is enqueued: mode is not 2, no retained forward, pmx_backward_head has not run for it, option "precision"
+ * != 0, a facenet / handnet context.
+ * With mode 2 on, pmx_get_layer_grad also takes the ten trunk names after pmx_backward_trunk (before: PMX_ERR_STATE; mode 1:
+ * PMX_ERR_INVALID as ever), and pmx_get_retained takes them with which = 0: a (pre-pool) at the layer's own resolution; 1: g, after
+ * pmx_backward_trunk and with "trunk_keep_g" (else PMX_ERR_STATE); 2: the pooled map of conv1_2 / conv2_2 / conv3_4 (any other layer:
+ * PMX_ERR_INVALID); and the name "input" with which = 0: the prepared input, batch x 3 x h x w. */
+#define PMX_WGRAD_TRUNK_MAX_STRIPS 512
+#define PMX_WGRAD_CONV1_STRIPS 2048
+int pmx_backward_trunk(pmx_ctx* ctx);
+/* test entry: conv1_1's weight-gradient kernel on the caller's host arrays x (B, 3, h, w) and g (B, 64, h, w) -> dw (64, 3, 3, 3).
+ * strips: S0 (0 = the rule); the S and R used come back in strips_out / rows_out (either may be NULL).  Synchronises. */
+int pmx_conv1_wgrad(pmx_ctx* ctx, const float* x_nchw, const float* g_nchw, int batch, int h, int w, int strips, float* dw_oihw,
+                    int* strips_out, int* rows_out);
+/* test entry: the max-pool kernel and the pooled layers' g kernel on host arrays a (B, C, h, w; h, w even) and u (B, C, h/2, w/2) ->
+ * pooled (B, C, h/2, w/2) and g (B, C, h, w).  Synchronises. */
+int pmx_pool_backward_test(pmx_ctx* ctx, const float* a_nchw, const float* u_nchw, int batch, int channels, int h, int w, float* pooled_out,
+                           float* g_out);
 
 /* ---- head training step: Adam on the 82 layers after conv4_2, every weight pack rewritten on the device ----------------------------
  * What the reference's optimizer.update() does during its first 2000 iterations (train_coco_pose_estimation.py:219-225: Adam, conv1_1 ..
