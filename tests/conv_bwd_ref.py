@@ -1,8 +1,9 @@
 """Host references of pmx_conv2d_backward and pmx_get_loss_grads (include/pose_mi355x.h), shared by the host and the GPU tests:
 the order-defined twin of the weight-gradient kernel (tests/conv_wgrad_twin.c: fmaf, built here with the host compiler and
 -ffp-contract=off), the mask rule (first-argmax, strict z > 0) and the bias-gradient rule in NumPy, the loss-gradient formula in NumPy, and
-the float64 autograd references with the error bound of a float32 sum of products; and the integer lattice on which every fp32 summation
-order gives the same bits, with the census of the ties and zeros that a lattice case holds."""
+the float64 autograd references with the error bound of a float32 sum of products; the float64 / float32 reference pairs of a data gradient
+and of a forward layer with the error ratio that compares a result with torch's own float32; and the integer lattice on which every fp32
+summation order gives the same bits, with the census of the ties and zeros that a lattice case holds."""
 import ctypes as C
 import functools
 import os
@@ -18,6 +19,8 @@ CSRC = os.path.join(ROOT, 'chainer_realtime_multi-person_pose_estimation_amd', '
 TWIN_SRC = os.path.join(HERE, 'conv_wgrad_twin.c')
 MAIN_SRC = os.path.join(HERE, 'conv_wgrad_main.c')
 U = 2.0 ** -24          # unit roundoff of float32
+MARGIN = 16.0           # ratio(): the error of a kernel form over that of torch's float32 for the same operation on the same inputs (other
+                        # summation orders and kernel forms than a direct fp32 sum); a path of lower precision is thousands of times off
 
 _twin = None
 _tmp = None
@@ -146,6 +149,49 @@ def conv_grads64(g, x, w):
     return xt.grad.numpy(), wt.grad.numpy(), bt.grad.numpy()
 
 
+def _dx(g, w, dtype):
+    import torch
+    import torch.nn.functional as F
+    k = w.shape[-1]
+    with torch.no_grad():
+        dx = F.conv_transpose2d(torch.tensor(np.asarray(g)).to(dtype), torch.tensor(np.asarray(w)).to(dtype), padding=k // 2)
+    return dx.double().numpy()
+
+
+def dx_pair(g, w):
+    """(dx64, dx32) of the plain convolution for a GIVEN output gradient g (B, cout, H, W) and weights w (cout, cin, k, k): torch on the CPU
+    in float64 (the reference) and in float32 (the yardstick: the same inputs and operation in the precision the kernels work in), both
+    returned as float64."""
+    import torch
+    return _dx(g, w, torch.float64), _dx(g, w, torch.float32)
+
+
+def fwd_pair(x, w, b, relu):
+    """(a64, a32) of [relu](conv2d(x, w) + b), as dx_pair."""
+    import torch
+    import torch.nn.functional as F
+    out = []
+    for dtype in (torch.float64, torch.float32):
+        with torch.no_grad():
+            a = F.conv2d(torch.tensor(np.asarray(x)).to(dtype), torch.tensor(np.asarray(w)).to(dtype), torch.tensor(np.asarray(b)).to(dtype),
+                         padding=w.shape[-1] // 2)
+            out.append((F.relu(a) if relu else a).double().numpy())
+    return tuple(out)
+
+
+def ratio(lib, ref64, yard):
+    """(r_l2, r_max, e_lib): the error of `lib` against the float64 reference over the error of the yardstick (torch's float32 result of the
+    same operation on the same inputs), as L2 norms and as maxima over the whole array, and lib's own relative L2 error.  A yardstick without
+    error or a zero reference is refused: the ratio would say nothing."""
+    lib, ref64, yard = (np.asarray(a, dtype=np.float64) for a in (lib, ref64, yard))
+    assert lib.shape == ref64.shape == yard.shape, (lib.shape, ref64.shape, yard.shape)
+    e_lib, e_yard = lib - ref64, yard - ref64
+    n_ref, n_yard, m_yard = np.sqrt((ref64 ** 2).sum()), np.sqrt((e_yard ** 2).sum()), np.abs(e_yard).max()
+    assert n_ref > 0 and n_yard > 0 and m_yard > 0, (n_ref, n_yard, m_yard)
+    n_lib = np.sqrt((e_lib ** 2).sum())
+    return n_lib / n_yard, np.abs(e_lib).max() / m_yard, n_lib / n_ref
+
+
 def dw_bound(g, x, w, dw64):
     """Elementwise bound of |dw - dw64| for ANY summation order of float32 products over K = B * H * W pixels:
     gamma_(K+1) * autograd_dw(|g|, |x|) + 2^-24 * |dw64|, gamma_n = n u / (1 - n u)."""
@@ -180,6 +226,11 @@ LATTICE_TIE_SHAPES = list(LATTICE_CASES)[:5]
 LATTICE_SWEEP_SHAPES = list(LATTICE_CASES)[5:8]
 LATTICE_VARIANTS = ((1, 1), (0, 1), (1, 0))          # (relu, pool)
 LATTICE_IDENTITY = (1, 32, 32, 4, 6, 1)          # w = I: dx is g itself
+
+
+# the transposed layers of conv4_1 and conv4_2 at a 5 x 7 and a 6 x 10 map (partial Winograd tiles, 256 and 512 output channels of the data
+# gradient's launch), for dx alone: dense weights, no relu, no pool, so no census.  |dx| <= 2 * 512 * 9.  (k, cin, cout, H, W, B) -> seed
+LATTICE_WIDE = {(3, 256, 512, 6, 10, 2): 21, (3, 512, 512, 5, 7, 3): 22}
 
 
 def lattice_inputs(k, cin, cout, H, W, B, pool, seed, w_density=1.0):
@@ -249,3 +300,17 @@ def lattice_case(shape, relu, pool, identity=False):
     for a in (x, w, b, dy) + tuple(ref.values()):
         a.setflags(write=False)
     return x, w, b, dy, ref, census
+
+
+@functools.lru_cache(maxsize=None)
+def lattice_wide_case(shape):
+    """(x, w, dy, dx) of a LATTICE_WIDE case: dense lattice inputs, dx = float64 autograd of the plain convolution cast to float32 (exact:
+    integers below 2^22).  Shared: callers do not write to it."""
+    k, cin, cout, H, W, B = shape
+    x, w, _, dy = lattice_inputs(k, cin, cout, H, W, B, 0, LATTICE_WIDE[shape])
+    dx64 = conv_grads64(dy, x, w)[0]
+    dx = dx64.astype('f')
+    assert np.array_equal(dx.astype(np.float64), dx64) and np.abs(dx64).max() <= 2 * cout * k * k < 2.0 ** 22
+    for a in (x, w, dy, dx):
+        a.setflags(write=False)
+    return x, w, dy, dx

@@ -2,7 +2,9 @@
 kernel (tests/conv_wgrad_twin.c) and the NumPy mask / bias-gradient rules (tests/conv_bwd_ref.py) against torch-CPU float64 autograd of
 conv2d [+ relu] [+ max_pool2d(2, 2)]; the C ABI surface; the stand-alone program (twin + the host-side weight repacking), plain and with
 -fsanitize=address,undefined.  The integer lattice of the exact GPU tests (tests/test_gpu_conv_backward_exact.py): its census floors, torch's
-tie and zero behaviour against the stated mask rule, and the order twins of every kernel form on it."""
+tie and zero behaviour against the stated mask rule, and the order twins of every kernel form on it.  The float64 / float32 reference pair of
+a data gradient and the error ratio the GPU tests measure with (conv_bwd_ref.dx_pair, ratio): what the ratio catches that the elementwise
+bound TOL * max(1, |ref|max) lets through at the size of a gradient."""
 import subprocess
 
 import numpy as np
@@ -150,6 +152,68 @@ def test_flipped_weights_give_the_data_gradient():
         assert wt.shape == (cin, cout, k, k)
         dx = torch.nn.functional.conv2d(torch.tensor(g), torch.tensor(wt), padding=k // 2).numpy()
         assert np.allclose(dx, dx64, rtol=1e-12, atol=1e-12)
+
+
+# ---- the reference pair and the error ratio ----------------------------------------------------------------------------------------------
+def test_dx_pair_is_the_autograd_data_gradient():
+    rng = np.random.default_rng(8)
+    for k, cin, cout in ((3, 5, 6), (7, 3, 4), (1, 6, 2)):
+        x = rng.standard_normal((2, cin, 5, 7)).astype('f')
+        w = rng.standard_normal((cout, cin, k, k)).astype('f')
+        g = rng.standard_normal((2, cout, 5, 7)).astype('f')
+        dx64, dx32 = R.dx_pair(g, w)
+        ref = R.conv_grads64(g, x, w)[0]
+        assert dx64.dtype == dx32.dtype == np.float64 and dx64.shape == dx32.shape == x.shape
+        assert np.array_equal(dx64, ref), np.abs(dx64 - ref).max()
+        assert np.array_equal(dx32, dx32.astype('f').astype(np.float64)) and not np.array_equal(dx32, dx64)          # float32 values
+        r_l2, r_max, e = R.ratio(dx32, dx64, dx32)
+        assert (r_l2, r_max) == (1.0, 1.0) and 0 < e < 1e-6
+        a64, a32 = R.fwd_pair(x, w, np.arange(cout, dtype='f'), relu=True)
+        z64 = R.autograd64(x, w, np.arange(cout, dtype='f'), np.zeros((2, cout, 5, 7)), False, False)['z']
+        assert np.array_equal(a64, np.maximum(z64, 0)) and R.ratio(a32, a64, a32)[:2] == (1.0, 1.0)
+    with pytest.raises(AssertionError):
+        R.ratio(dx64, dx64, dx64)          # a yardstick without error measures nothing
+    with pytest.raises(AssertionError):
+        R.ratio(dx32, 0 * dx64, dx32)
+
+
+def test_ratio_catches_what_the_elementwise_bound_lets_through():
+    """The data gradient of a 64 -> 64, 3x3 layer at 2 x 16 x 12 for an output gradient of the size the backward chains carry (1e-3), and
+    three wrong versions of its float32 result: the weights rounded to bfloat16 (a path of lower precision), the left border column copied
+    from its neighbour, one element -- the largest -- half as large again.  The ratio puts each far above the margin; the bound
+    |dx - ref| <= 2e-5 * max(1, |ref|max), made for maps of size O(1), passes the first: its floor is an absolute 2e-5 and the whole
+    gradient is smaller than that many times over."""
+    import torch
+    rng = np.random.default_rng(40)
+    w = (rng.standard_normal((64, 64, 3, 3)) / np.sqrt(64 * 9)).astype('f')
+    g = (1e-3 * rng.standard_normal((2, 64, 16, 12))).astype('f')
+    dx64, dx32 = R.dx_pair(g, w)
+    assert 1e-4 < np.abs(dx64).max() < 1e-2
+    old = lambda dx: np.abs(dx - dx64).max() <= 2e-5 * max(1.0, np.abs(dx64).max())
+    assert old(dx32) and R.ratio(dx32, dx64, dx32)[:2] == (1.0, 1.0)
+    bf16 = R.dx_pair(g, torch.tensor(w).bfloat16().float().numpy())[1]
+    column = dx32.copy()
+    column[..., 0] = column[..., 1]
+    element = dx32.copy()
+    element.reshape(-1)[np.abs(dx64).argmax()] *= 1.5
+    passes_old = {}
+    for name, wrong in (('bf16', bf16), ('column', column), ('element', element)):
+        r_l2, r_max, e = R.ratio(wrong, dx64, dx32)
+        passes_old[name] = bool(old(wrong))
+        print(name, 'r_l2 %.3g r_max %.3g rel. L2 %.3g, passes the elementwise bound: %s' % (r_l2, r_max, e, passes_old[name]))
+        assert r_l2 > R.MARGIN and r_max > R.MARGIN, (name, r_l2, r_max)
+    assert passes_old['bf16']
+
+
+def test_wide_lattice_cases_are_exact():
+    """The premise of the GPU test on them: dx is a field of integers below 2^22 (the bound of the lattice: 2 * cout * k * k), so its cast
+    to float32 is exact and every fp32 summation order, Winograd's included, gives its bits."""
+    for shape in R.LATTICE_WIDE:
+        k, cin, cout, H, W, B = shape
+        x, w, dy, dx = R.lattice_wide_case(shape)
+        assert dx.shape == x.shape == (B, cin, H, W) and w.shape == (cout, cin, 3, 3) and (w != 0).mean() > 0.6
+        assert np.array_equal(dx, np.rint(dx)) and 0 < np.abs(dx).max() <= 2 * 512 * 9 < 2 ** 22
+        assert np.array_equal(R.dx_pair(dy, w)[1], dx)          # torch's float32 order is exact on it as well
 
 
 def test_strip_rule():

@@ -1,6 +1,7 @@
 """GPU: pmx_conv2d_backward (include/pose_mi355x.h) -- the gradients of one convolution layer through the C ABI.  z against the torch
 reference of pmx_conv2d's own test, dw bit for bit against the order-defined host twin (tests/conv_wgrad_twin.c) and within the bound of a
-float32 sum of products against float64 autograd, db and dx against float64 autograd.  The masks of the references are computed from the z
+float32 sum of products against float64 autograd, db and dx against float64 autograd, dx also by its error over that of torch's float32
+data gradient for the same g (conv_bwd_ref.ratio, at most MARGIN; figures: EXPERIMENTS.md E40).  The masks of the references are computed from the z
 the call returned (tests/conv_bwd_ref.py::mask_rule), so no element is left out for a near-tie."""
 import numpy as np
 import pytest
@@ -11,6 +12,7 @@ from oracle import network_ref as N
 pytestmark = pytest.mark.gpu
 
 TOL = 2e-5          # tests/test_gpu_conv.py: err <= TOL * max(1, |ref|max)
+MARGIN = R.MARGIN
 
 # (k, cin, cout, H, W, B, forced strips)
 SHAPES = [(7, 40, 128, 12, 15, 1, 0), (3, 70, 64, 14, 10, 2, 0), (1, 100, 38, 9, 13, 1, 0), (3, 3, 64, 20, 24, 1, 0),
@@ -53,13 +55,15 @@ def _check(engine, shape, relu, pool, out, x, w, b, dy):
     bound = R.dw_bound(g, x, w, dw64)
     edb = np.abs(out['db'].astype(np.float64) - db64)
     edx = np.abs(out['dx'] - dx64).max()
+    rdx = R.ratio(out['dx'], dx64, R.dx_pair(g, w)[1])
     print(shape, relu, pool, 'z', ez, 'dw != twin', int((out['dw'] != twin).sum()), 'dw err / bound', float((err / np.maximum(bound, 1e-300)).max()),
-          'db', float((edb / np.maximum(np.abs(db64), 1e-300)).max()), 'dx', edx, np.abs(dx64).max())
+          'db', float((edb / np.maximum(np.abs(db64), 1e-300)).max()), 'dx', edx, np.abs(dx64).max(), 'dx r_l2 %.3f r_max %.3f rel. L2 %.3e' % rdx)
     assert ez <= TOL * max(1.0, np.abs(zref).max())
     assert np.array_equal(out['dw'], twin), (int((out['dw'] != twin).sum()), np.abs(out['dw'] - twin).max())
     assert (err <= bound).all()
     assert (edb <= 2.0 ** -23 * np.abs(db64)).all()
     assert edx <= TOL * max(1.0, np.abs(dx64).max())
+    assert rdx[0] <= MARGIN and rdx[1] <= MARGIN, rdx
 
 
 @pytest.mark.parametrize('shape,relu,pool', CASES)
@@ -103,7 +107,7 @@ def test_dw_and_db_keep_their_bits_under_the_forward_options(engine, k, cin, cou
     x, w, b, dy = _inputs(k, cin, cout, H, W, 2, False, seed=31 + k)
     _reset(engine)
     base = engine.conv2d_backward(x, w, b, dy)
-    dx64, _, _ = R.conv_grads64(dy, x, w)
+    dx64, dx32 = R.dx_pair(dy, w)
     settings = [('conv_algo', 0, 1), ('conv_algo', 2, 1), ('wino_tail', 1, -1), ('wino_geom', 0, -1), ('ksplit', 2, 0)]
     try:
         for key, val, default in settings:
@@ -113,6 +117,9 @@ def test_dw_and_db_keep_their_bits_under_the_forward_options(engine, k, cin, cou
             engine.set_option(key, default)
             assert np.array_equal(out['dw'], base['dw']) and np.array_equal(out['db'], base['db']), (key, val)
             assert np.abs(out['dx'] - dx64).max() <= TOL * max(1.0, np.abs(dx64).max()), (key, val)
+            rdx = R.ratio(out['dx'], dx64, dx32)
+            print(k, key, val, 'dx r_l2 %.3f r_max %.3f rel. L2 %.3e' % rdx)
+            assert rdx[0] <= MARGIN and rdx[1] <= MARGIN, (key, val, rdx)
         engine.set_option('conv_algo', 1)
         for variant in {3: (2, 6, 14, 16), 7: (0, 5, 12, 15, 17, 21)}[k]:          # (conv_mfma.hip g_variants; one that does not fit a plan is not taken)
             engine.set_option('force_variant_k%d' % k, variant)

@@ -3,7 +3,8 @@ the same bits.  All four outputs are compared for EQUALITY with torch-CPU float6
 (conv_bwd_ref.autograd64; neither mask_rule nor the order twin takes part), on inputs that hold pooling windows with equal maxima, exact
 zeros of z and windows with nothing above zero by the hundred (conv_bwd_ref.lattice_census; the floors are asserted before anything is
 compared, and tests/test_conv_backward_host.py pins torch's behaviour on them to the stated rule).  So conv_bwd_mask_kernel's first-of-equal-
-maxima choice and its strict z > 0 gate are checked on the device, on the z of every forward plan."""
+maxima choice and its strict z > 0 gate are checked on the device, on the z of every forward plan.  The data gradient alone at the width of
+the trunk's last layers (256 and 512 channels on maps with partial Winograd tiles), under every conv_algo, for the same equality."""
 import numpy as np
 import pytest
 
@@ -91,6 +92,25 @@ def test_mask_reads_the_z_of_every_plan(engine, shape):
         for key, val, default in settings:
             engine.set_option(key, default)
         _reset(engine)
+
+
+@pytest.mark.parametrize('algo', (0, 1, 2))
+@pytest.mark.parametrize('shape', list(R.LATTICE_WIDE))
+def test_wide_data_gradients_are_exact_in_every_form(engine, shape, algo):
+    """dx of the transposed layers of conv4_1 (512 -> 256 at 6 x 10) and conv4_2 (512 -> 512 at 5 x 7, batch 3), dense lattice weights, no
+    relu, no pool: direct, split-K and Winograd launches give the bits of float64 autograd (|dx| <= 2 * 512 * 9 < 2^22; the cast is checked
+    in tests/test_conv_backward_host.py)."""
+    x, w, dy, dx = R.lattice_wide_case(shape)
+    _reset(engine)
+    engine.set_option('conv_algo', algo)
+    try:
+        out = engine.conv2d_backward(x, w, None, dy, want=('dx',))
+    finally:
+        engine.set_option('conv_algo', 1)
+    assert set(out) == {'dx'} and out['dx'].shape == dx.shape and np.isfinite(out['dx']).all()
+    ne = out['dx'] != dx
+    print(shape, algo, 'dx != float64 autograd', int(ne.sum()), 'max |dx|', np.abs(dx).max())
+    assert not ne.any(), 'dx differs from float64 autograd in %d elements, first at %r' % (int(ne.sum()), tuple(np.argwhere(ne)[0]))
 
 
 def test_lattice_under_forced_strips(engine):

@@ -1,7 +1,12 @@
 """GPU: the head backward (include/pose_mi355x.h: pmx_backward_enable / pmx_backward_head) -- the gradients of the 82 layers after conv4_2.
 Per layer, from the library's own retained arrays: dw bit for bit against the order-defined host twin and within the bound of a float32 sum
 of products, db and the upstream gradients against float64, the ReLU gates by bits.  The whole chain against float64 torch autograd, with
-torch's own float32 autograd as the yardstick (the figures of a run: EXPERIMENTS.md E37)."""
+torch's own float32 autograd as the yardstick (the figures of a run: EXPERIMENTS.md E37).
+Pinned per layer, in every run (primary, stop_stage 2 with forced strips, the four option sweeps; figures: E40): the upstream gradient g of
+every layer that has a consumer, over its open gates, and the trunk gradient, against the float64 sum of the consumers' data gradients with
+the same sum of torch's float32 data gradients, added in float32 in the documented order, as the yardstick (conv_bwd_ref.ratio, at most
+MARGIN in L2 and in the maximum).  The elementwise bound n * TOL * max(1, |u|max) stays beside it; gradients here are 1e-4 .. 5e-3 in size,
+so its floor is an absolute 2e-5 that a data gradient through a path of lower precision would pass."""
 import collections
 
 import numpy as np
@@ -13,7 +18,7 @@ from conftest import pkg
 pytestmark = pytest.mark.gpu
 
 TOL = 2e-5          # tests/test_gpu_conv.py: one dispatcher result, err <= TOL * max(1, |ref|max)
-MARGIN = 16.0       # whole chain: relative L2 error of a dw over that of torch's float32 autograd
+MARGIN = R.MARGIN    # 16: relative L2 error over that of torch's float32 -- of a dw over the whole chain, of a data gradient per layer
 MAX_B, MAX_H, MAX_W = 3, 64, 48
 PRIMARY = dict(B=2, H=64, W=48, stages=6, strips=0, seed=2024)
 SECONDARY = dict(B=3, H=48, W=40, stages=2, strips=4, seed=2025)          # 18 map rows in strips of 5: every border inside an image
@@ -123,7 +128,9 @@ def _cached(eng, key):
 
 def _refs(run):
     """float64 references of every layer of a run, from the run's own retained arrays (computed once per run): x, (dx64, dw64, db64) of
-    conv_grads64(g, x, w) and u64 = the sum of the consumers' dx64 slices + the loss gradient at a stage output, n = the consumers."""
+    conv_grads64(g, x, w) and u64 = the sum of the consumers' dx64 slices + the loss gradient at a stage output, n = the consumers; dx32 =
+    torch's float32 data gradient for the same g, and u32 = the same sum of dx32 slices made of float32 adds in the order of THE SUMS of the
+    header: the loss gradient first, then the consumers as the backward reaches them (the last stage first, L1 before L2)."""
     if 'refs' in run:
         return run['refs']
     W = _weights()
@@ -131,11 +138,12 @@ def _refs(run):
     refs = {}
     for nm, d in head.items():
         x = np.concatenate([run['a'][p] for p in d['x']], axis=1)
-        refs[nm] = dict(x=x, grads=R.conv_grads64(run['g'][nm], x, W[nm][0]), n=0)
+        refs[nm] = dict(x=x, grads=R.conv_grads64(run['g'][nm], x, W[nm][0]), n=0, dx32=R.dx_pair(run['g'][nm], W[nm][0])[1].astype(np.float32))
     for nm, d in head.items():
         if d['out'] is not None:
             s, b = d['out']
             refs[nm]['u64'] = run['lg'][s - 1][b].astype(np.float64)
+            refs[nm]['u32'] = run['lg'][s - 1][b].copy()
         else:
             refs[nm]['u64'] = np.zeros(run['a'][nm].shape)
     for nm, d in head.items():
@@ -145,6 +153,15 @@ def _refs(run):
             if p in refs:
                 refs[p]['u64'] = refs[p]['u64'] + refs[nm]['grads'][0][:, off:off + c]
                 refs[p]['n'] += 1
+            off += c
+    for nm in sorted(head, key=lambda nm: (-head[nm]['stage'], nm.endswith('_L2'))):          # (stable: the forward's order within a branch)
+        off = 0
+        for p in head[nm]['x']:
+            c = run['a'][p].shape[1]
+            if p in refs:
+                part = refs[nm]['dx32'][:, off:off + c]
+                refs[p]['u32'] = refs[p]['u32'] + part if 'u32' in refs[p] else part.copy()
+                assert refs[p]['u32'].dtype == np.float32
             off += c
     run['refs'] = refs
     return refs
@@ -174,8 +191,11 @@ def _check_layers(run, stage):
         u64 = r['u64']
         eu = np.abs(g.astype(np.float64) - u64)[sel].max() if sel.any() else 0.0
         ubound = r['n'] * TOL * max(1.0, np.abs(u64).max())
+        # g over torch's float32 against float64, on the open gates (closed: zero in all three)
+        ur = R.ratio(np.where(sel, g, 0), np.where(sel, u64, 0), np.where(sel, r['u32'], 0)) if r['n'] else (0.0, 0.0, 0.0)
         print(nm, 'dw != twin', int((dw != twin).sum()), 'dw err / bound', float((err / np.maximum(bound, 1e-300)).max()),
-              'db', float((edb / np.maximum(np.abs(db64), 1e-300)).max()), 'u', eu, 'bound', ubound, 'n', r['n'], 'gates open', float(sel.mean()))
+              'db', float((edb / np.maximum(np.abs(db64), 1e-300)).max()), 'u', eu, 'bound', ubound, 'n', r['n'], 'gates open', float(sel.mean()),
+              'u r_l2 %.3f r_max %.3f rel. L2 %.3e' % ur)
         assert np.array_equal(dw, twin), (nm, int((dw != twin).sum()))
         assert (err <= bound).all(), nm
         assert (edb <= 2.0 ** -23 * np.abs(db64)).all(), nm
@@ -187,12 +207,15 @@ def _check_layers(run, stage):
         else:
             assert r['n'] == (2 if d['out'] is not None else 2 * cfg['stages'] if nm == 'conv4_4_CPM' else 1), (nm, r['n'])
             assert eu <= ubound, (nm, eu, ubound)
+            assert ur[0] <= MARGIN and ur[1] <= MARGIN, (nm, ur)
     if stage == 0:
         dx64 = refs['conv4_3_CPM']['grads'][0]
         et = np.abs(run['trunk'] - dx64).max()
-        print('trunk_grad', et, np.abs(dx64).max())
+        tr = R.ratio(run['trunk'], dx64, refs['conv4_3_CPM']['dx32'])
+        print('trunk_grad', et, np.abs(dx64).max(), 'r_l2 %.3f r_max %.3f rel. L2 %.3e' % tr)
         assert np.isfinite(run['trunk']).all() and run['trunk'].shape == dx64.shape
         assert et <= TOL * max(1.0, np.abs(dx64).max())
+        assert tr[0] <= MARGIN and tr[1] <= MARGIN, tr
 
 
 @pytest.mark.parametrize('stage', range(7))

@@ -1,7 +1,12 @@
 """GPU: the trunk backward (include/pose_mi355x.h: pmx_backward_enable(ctx, 2) / pmx_backward_trunk) -- the gradients of conv1_1 .. conv4_2.
 The whole chain against float64 torch autograd of the full network with torch's own float32 autograd as the yardstick; per layer, from the
 library's own retained arrays, dw bit for bit against the order-defined host twin; the pool kernels and conv1_1's weight-gradient kernel
-through their test entries on the integer lattice (the figures of a run: EXPERIMENTS.md E39)."""
+through their test entries on the integer lattice (the figures of a run: EXPERIMENTS.md E39).
+Pinned per layer, under conv_algo 1, 0 and 2 in both cases (test_every_trunk_layer_s_output_and_upstream_gradient; figures: E40): the
+prepared input by bits against the documented formula; every retained output a against relu(conv(x) + b) of the layer's own input x, and
+every upstream gradient g against the masked or pool-scattered data gradient of the layer after it, both in float64 torch with torch's
+float32 result as the yardstick (conv_bwd_ref.ratio, at most MARGIN in L2 and in the maximum); g of conv4_2 by bits against the masked
+trunk gradient of the head."""
 import numpy as np
 import pytest
 
@@ -10,10 +15,13 @@ import conv_bwd_ref as R
 import test_gpu_head_backward as HB
 import trunk_backward_ref as T
 from conftest import pkg
+from oracle import postprocess_ref as P
 
 pytestmark = pytest.mark.gpu
 
-MARGIN = HB.MARGIN      # whole chain: relative L2 error of a gradient over that of torch's float32 autograd (the head test's margin)
+MARGIN = HB.MARGIN      # relative L2 error over that of torch's float32 (the head test's margin): of a gradient over the whole chain, of an
+                        # output or an upstream gradient per layer
+TOL = HB.TOL            # one dispatcher result: err <= TOL * max(1, |ref|max)
 MAX_B, MAX_H, MAX_W = 3, 64, 48
 CASES = {'primary': dict(B=2, H=64, W=48, stages=6, seed=2024),          # the head test's primary case
          'secondary': dict(B=3, H=40, W=56, stages=6, seed=2026)}        # level 3 is 5 x 7: every level has partial tiles
@@ -149,7 +157,7 @@ def test_every_trunk_layer_against_the_twin(eng, case, strips, algo):
     assert np.isfinite(run['input']).all() and run['input'].shape == (B, 3, H, cfg['W'])
     for t, (nm, cin, cout, level, pool) in enumerate(T.TRUNK):
         a, g, dw, db = run['a'][nm], run['g'][nm], run['dw'][nm], run['db'][nm]
-        x = run['input'] if t == 0 else run['pooled'][T.NAMES[t - 1]] if T.TRUNK[t - 1][4] else run['a'][T.NAMES[t - 1]]
+        x = _x_of(run, t)
         assert a.shape == g.shape == (B, cout, H >> level, cfg['W'] >> level) and x.shape[1] == cin and dw.shape == (cout, cin, 3, 3), nm
         for what, arr in (('a', a), ('g', g), ('dw', dw), ('db', db)):
             assert np.isfinite(arr).all(), 'unwritten (poisoned) or non-finite %s of %s' % (what, nm)
@@ -171,6 +179,63 @@ def test_every_trunk_layer_against_the_twin(eng, case, strips, algo):
             assert not np.where(np.arange(4) == first[..., None], 0, gw).any(), nm
     if strips and (case, strips) != ('secondary', 3):          # (three strips of three images end where the images do)
         assert T.trunk_strips('conv1_2', B, H, strips)[1] % H != 0          # a strip border inside an image
+
+
+# ---- 2b. every layer's output and upstream gradient against float64, torch's float32 as the yardstick ------------------------------------------
+def _x_of(run, t):
+    """the input of trunk layer t: the prepared input, the pooled map or the output of the layer before it"""
+    return run['input'] if t == 0 else run['pooled'][T.NAMES[t - 1]] if T.TRUNK[t - 1][4] else run['a'][T.NAMES[t - 1]]
+
+
+def _layer_refs(run):
+    """(reference, yardstick) pairs of a run from the run's own retained arrays, computed once per run: 'a' of every layer from its own
+    input, 'g' of conv1_1 .. conv4_1 from g of the layer after it, gated or scattered by the library's own a (nothing can flip)."""
+    if 'layer_refs' not in run:
+        W = HB._weights()
+        refs = {'a': {}, 'g': {}}
+        for t, nm in enumerate(T.NAMES):
+            refs['a'][nm] = R.fwd_pair(_x_of(run, t), W[nm][0], W[nm][1], relu=True)
+        for t in range(len(T.NAMES) - 2, -1, -1):
+            nm, nxt = T.NAMES[t], T.NAMES[t + 1]
+            a = run['a'][nm]
+            rule = (lambda dx: T.pool_scatter(a, dx)) if T.TRUNK[t][4] else (lambda dx: np.where(a > 0, dx, 0.0))
+            refs['g'][nm] = tuple(rule(dx) for dx in R.dx_pair(run['g'][nxt], W[nxt][0]))
+        run['layer_refs'] = refs
+    return run['layer_refs']
+
+
+@pytest.mark.parametrize('case,algo', [(c, a) for c in CASES for a in (1, 0, 2)])
+def test_every_trunk_layer_s_output_and_upstream_gradient(eng, case, algo):
+    """What test_every_trunk_layer_against_the_twin takes as given.  Each quantity is checked on the layer's own inputs as the library
+    retained them, so no error carries from layer to layer and no gate or arg-maximum can differ between library, reference and yardstick.
+    The prepared input: no other test pins it per element (tests/test_gpu_network.py sees it through the maps), so it is compared here by
+    bits with the float32 evaluation of the documented formula, divide by 255, then subtract 0.5 (csrc/prep.hip promises exactly that)."""
+    run = _cached(eng, (case, 0, algo))
+    cfg = CASES[case]
+    imgs = HB._data(**cfg)[0]
+    want = np.concatenate([P.preprocess(im) for im in imgs])
+    assert want.dtype == np.float32 and np.array_equal(_bits(run['input']), _bits(want)), int((_bits(run['input']) != _bits(want)).sum())
+    refs = _layer_refs(run)
+    bad = []
+    for nm in T.NAMES:
+        a = run['a'][nm]
+        a64, a32 = refs['a'][nm]
+        r_l2, r_max, e = R.ratio(a, a64, a32)
+        ea = np.abs(a - a64).max()
+        print('%s algo %d %s a: r_l2 %.3f r_max %.3f rel. L2 %.3e max err %.3e |a|max %.3g' % (case, algo, nm, r_l2, r_max, e, ea, np.abs(a64).max()))
+        if not (r_l2 <= MARGIN and r_max <= MARGIN and ea <= TOL * max(1.0, np.abs(a64).max())):
+            bad.append((nm, 'a', r_l2, r_max, ea))
+    top = T.NAMES[-1]
+    assert run['trunk'].shape == run['a'][top].shape
+    link = np.where(run['a'][top] > 0, run['trunk'], np.float32(0))
+    assert link.dtype == np.float32 and np.array_equal(_bits(run['g'][top]), _bits(link)), int((_bits(run['g'][top]) != _bits(link)).sum())
+    for nm in T.NAMES[-2::-1]:
+        g64, g32 = refs['g'][nm]
+        r_l2, r_max, e = R.ratio(run['g'][nm], g64, g32)
+        print('%s algo %d %s g: r_l2 %.3f r_max %.3f rel. L2 %.3e |g|max %.3g' % (case, algo, nm, r_l2, r_max, e, np.abs(g64).max()))
+        if not (r_l2 <= MARGIN and r_max <= MARGIN):
+            bad.append((nm, 'g', r_l2, r_max))
+    assert not bad, bad
 
 
 # ---- 3. the pool kernels on the lattice -------------------------------------------------------------------------------------------------------

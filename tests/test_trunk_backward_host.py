@@ -1,6 +1,6 @@
 """CPU: the host side of the trunk backward (include/pose_mi355x.h: pmx_backward_trunk) -- the C ABI surface, the strip rules of
 csrc/wgrad_strips.h through a stand-alone program (tests/trunk_strips_main.c, host compiler) against their restatement in Python, the
-2048 waves the rules promise at the training shapes, and the NumPy twin of the pooled layers against float64 autograd on the lattice."""
+2048 waves the rules promise at the training shapes, the NumPy twin of the pooled layers against float64 autograd on the lattice, and its scatter in the dtype of the gradient."""
 import os
 import shutil
 import subprocess
@@ -100,3 +100,18 @@ def test_pool_twin_equals_float64_autograd_on_the_lattice(C_, H, W):
     assert np.array_equal(g.astype(np.float64), zt.grad.numpy()), census
     assert np.array_equal(g, R.mask_rule(u, z, 1, 1))
     assert census['tied'] and census['dead_windows'] and census['zeros'], census
+
+
+@pytest.mark.parametrize('C_,H,W', [(32, 2, 2), (64, 6, 10), (96, 16, 12)])
+def test_pool_scatter_is_pool_twin_s_scatter_in_the_dtype_of_u(C_, H, W):
+    rng = np.random.default_rng(200 + C_)
+    a = np.maximum(rng.integers(-2, 3, (2, C_, H, W)), 0).astype('f')          # ties and dead windows in plenty
+    u = rng.standard_normal((2, C_, H // 2, W // 2))
+    want = T.pool_twin(a, u.astype('f'))[1]
+    g32 = T.pool_scatter(a, u.astype('f'))
+    assert g32.dtype == np.float32 and np.array_equal(g32.view(np.uint32), want.view(np.uint32))
+    g64 = T.pool_scatter(a, u)
+    assert g64.dtype == np.float64 and np.array_equal(g64 != 0, want != 0) 
+    live = T.windows(g64 != 0).any(axis=-1)
+    assert np.array_equal(T.windows(g64).sum(axis=-1), np.where(live, u, 0.0))          # one non-zero per window: u itself, not rounded
+    assert not np.signbit(g64[g64 == 0]).any()

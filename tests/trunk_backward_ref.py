@@ -66,6 +66,20 @@ def pool_twin(a, u):
     return np.ascontiguousarray(pooled), np.ascontiguousarray(g)
 
 
+def pool_scatter(a, u):
+    """pool_twin's g in the dtype of u (a float64 dx is scattered by the same rule as the float32 one): u at the FIRST maximum of each
+    2 x 2 window of a where that a > 0, +0.0 elsewhere."""
+    a = np.asarray(a, dtype=np.float32)
+    u = np.asarray(u)
+    B, c, H, W = a.shape
+    assert u.shape == (B, c, H // 2, W // 2)
+    win = windows(a)
+    sel = np.zeros(win.shape, bool)
+    np.put_along_axis(sel, np.argmax(win, axis=-1)[..., None], True, axis=-1)
+    g = np.where(sel & (win > 0), u[..., None], u.dtype.type(0))
+    return np.ascontiguousarray(g.reshape(B, c, H // 2, W // 2, 2, 2).transpose(0, 1, 2, 4, 3, 5).reshape(B, c, H, W))
+
+
 def windows(a):
     B, c, H, W = a.shape
     return a.reshape(B, c, H // 2, 2, W // 2, 2).transpose(0, 1, 2, 4, 3, 5).reshape(B, c, H // 2, W // 2, 4)
