@@ -17,8 +17,6 @@
 // LDS per MFMA (BN = 128): 1 KiB of A per wave and MFMA, 4 waves -> 4 KiB per 32 cycles = 128 B/clk/CU, half the 256 B/clk of ds_read_b128.
 #include "conv_direct.h"
 
-#include <algorithm>
-
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
@@ -32,8 +30,21 @@ struct F16Cfg {
     static constexpr int NHF = (UNITS + 255) / 256;
 };
 
-// saturating round-to-nearest-even fp32 -> f16 (the clamp first: v_cvt_f16_f32 would turn |v| >= 65520 into inf)
-__device__ __forceinline__ _Float16 f16_sat(float v) { return (_Float16)fminf(fmaxf(v, -65504.f), 65504.f); }
+// saturating round-to-nearest-even fp32 -> f16 of a staged float4 (the clamp first: v_cvt_f16_f32 would turn |v| >= 65520 into inf).  NaN stays
+// NaN, as in the host's f16_rn_sat: a clamp alone makes a finite value of it (fmaxf / fminf and v_med3_f32 return a non-NaN operand), so the
+// rare float4 that holds one converts those elements again, unclamped.  One v_med3_f32 per element, one unordered compare per pair
+__device__ __forceinline__ f16x4 f16_sat4(const float4 v)
+{
+    f16x4 h = {(_Float16)__builtin_amdgcn_fmed3f(v.x, -65504.f, 65504.f), (_Float16)__builtin_amdgcn_fmed3f(v.y, -65504.f, 65504.f),
+               (_Float16)__builtin_amdgcn_fmed3f(v.z, -65504.f, 65504.f), (_Float16)__builtin_amdgcn_fmed3f(v.w, -65504.f, 65504.f)};
+    if (__builtin_expect((v.x != v.x) | (v.y != v.y) | (v.z != v.z) | (v.w != v.w), 0)) {
+        if (v.x != v.x) h.x = (_Float16)v.x;
+        if (v.y != v.y) h.y = (_Float16)v.y;
+        if (v.z != v.z) h.z = (_Float16)v.z;
+        if (v.w != v.w) h.w = (_Float16)v.w;
+    }
+    return h;
+}
 
 template <int KS, typename OP, int BN>
 __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvArgs a)
@@ -105,8 +116,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvArgs a)
 #pragma unroll
         for (int r = 0; r < C::NHF; ++r) {
             if (h_lds[r] < 0) continue;
-            const f16x4 h = {f16_sat(hv[r].x), f16_sat(hv[r].y), f16_sat(hv[r].z), f16_sat(hv[r].w)};
-            *reinterpret_cast<f16x4*>(buf + h_lds[r]) = h;
+            *reinterpret_cast<f16x4*>(buf + h_lds[r]) = f16_sat4(hv[r]);
         }
     };
 
@@ -198,14 +208,22 @@ static int launch_f16(const ConvArgs& a0, int groups, hipStream_t stream)
     return PMX_OK;
 }
 
-// blocks of 128 channels where the launch fills the chip with them, else 64 (the per-output K order is the same either way)
-int conv_f16_bn(int cout_pad, int tiles, int groups)
+// 8 x 16 pixel tiles of a launch (the segment table's count in a heterogeneous forward)
+long long conv_f16_tiles(const ConvArgs& a)
 {
-    if (cout_pad % 128) return 64;
-    return (long long)tiles * (cout_pad / 128) * groups >= conv_num_cus() ? 128 : 64;
+    return a.nseg ? a.seg_tiles : (long long)a.B * ((a.W + 15) / 16) * ((a.H + 7) / 8);
 }
 
-int conv_f16_launch(int ks, const ConvArgs& a, int groups, hipStream_t stream)
+// blocks of 128 channels where the launch fills the chip with them, else 64 (the per-output K order is the same either way).  f16_bn: the
+// context's option "f16_bn" -- 0 = that rule, 64 | 128 = that width instead of the rule's answer (128 only where the layer has blocks of 128)
+int conv_f16_bn(const ConvArgs& a, int groups, int f16_bn)
+{
+    if (a.cout_pad % 128) return 64;
+    if (f16_bn) return f16_bn;
+    return conv_f16_tiles(a) * (a.cout_pad / 128) * groups >= conv_num_cus() ? 128 : 64;
+}
+
+int conv_f16_launch(int ks, const ConvArgs& a, int groups, int f16_bn, hipStream_t stream)
 {
     PMX_CHECK(ks == 3 || ks == 7, PMX_ERR_INVALID, "conv f16: kernel size %d (3 or 7)", ks);
     PMX_CHECK(groups == 1 || groups == 2, PMX_ERR_INVALID, "conv f16: %d groups", groups);
@@ -215,8 +233,8 @@ int conv_f16_launch(int ks, const ConvArgs& a, int groups, hipStream_t stream)
     PMX_CHECK(!a.pool || (a.H % 2 == 0 && a.W % 2 == 0), PMX_ERR_INVALID, "conv f16: pooled layer needs even H, W");
     PMX_CHECK((long long)a.H * a.W * a.lda < (1ll << 31) && (long long)a.H * a.W * a.ldc < (1ll << 31), PMX_ERR_INVALID,
               "conv f16: image too large for 32-bit offsets");
-    const long long tiles = a.nseg ? a.seg_tiles : (long long)a.B * ((a.W + 15) / 16) * ((a.H + 7) / 8);
-    const int bn = conv_f16_bn(a.cout_pad, (int)std::min<long long>(tiles, 1 << 30), groups);
+    PMX_CHECK(f16_bn == 0 || f16_bn == 64 || f16_bn == 128, PMX_ERR_INVALID, "conv f16: block width %d (0, 64 or 128)", f16_bn);
+    const int bn = conv_f16_bn(a, groups, f16_bn);
     if (ks == 7) return bn == 128 ? launch_f16<7, 128>(a, groups, stream) : launch_f16<7, 64>(a, groups, stream);
     return bn == 128 ? launch_f16<3, 128>(a, groups, stream) : launch_f16<3, 64>(a, groups, stream);
 }

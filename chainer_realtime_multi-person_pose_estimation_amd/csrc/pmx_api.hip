@@ -7,6 +7,7 @@
 //   writes into the 192-channel "cat" buffer (layout in pmx_common.h).
 #include "pmx_ctx.h"
 #include "conv_bwd_pack.h"
+#include "f16_round.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -177,25 +178,6 @@ static void pack_bf16x3(const std::vector<float>& wp, int T, int nch, int cout_p
             }
 }
 
-// fp32 -> f16 bits, round-to-nearest-even, saturating at +-65504 (the f16 mode's f16(v): conv_f16_kernel rounds the activations the same
-// way); NaN stays NaN
-static inline uint16_t f16_rn_sat(float x)
-{
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    const uint32_t sign = (u >> 16) & 0x8000u, ax = u & 0x7fffffffu;
-    if (ax > 0x7f800000u) return (uint16_t)(sign | 0x7e00u);
-    if (ax >= 0x477fe000u) return (uint16_t)(sign | 0x7bffu);          // |x| >= 65504 (and what would round above it): the largest finite
-    if (ax < 0x38800000u) {                                             // below 2^-14: subnormal f16 (or zero), in units of 2^-24
-        if (ax < 0x33000000u) return (uint16_t)sign;                    // below 2^-25: rounds to zero (2^-25 itself is the tie -> even = 0)
-        const uint32_t e = ax >> 23, m = (ax & 0x7fffffu) | 0x800000u;
-        const uint32_t shift = 126 - e;                                 // value = m * 2^(e - 150) = (m >> (126 - e)) * 2^-24
-        const uint32_t q = m >> shift, rem = m & ((1u << shift) - 1), half = 1u << (shift - 1);
-        return (uint16_t)(sign | (q + (rem > half || (rem == half && (q & 1)))));
-    }
-    const uint32_t r = ax + 0xfffu + ((ax >> 13) & 1u);                 // round the 23-bit mantissa to 10 bits (a carry bumps the exponent)
-    return (uint16_t)(sign | (((r >> 13) - (112u << 10)) & 0x7fffu));
-}
 // packed fp32 weights [tap][chunk][cout_pad][16] -> f16 in the same layout (so the concat channel map comes along)
 static void pack_f16(const std::vector<float>& wp, std::vector<uint16_t>& out)
 {
@@ -485,6 +467,11 @@ extern "C" int pmx_set_option(pmx_ctx* c, const char* key, int value)
         PMX_CHECK(value != 1 || conv_bf16x3_launch != nullptr, PMX_ERR_INVALID,
                   "pmx_set_option: \"precision\" = %d needs the opt-in bf16x3 kernels, which this build does not carry (rebuild with PMX_BUILD_BF16X3=1)", value);
         c->opt_precision = value;
+    }
+    else if (!strcmp(key, "f16_bn")) {
+        PMX_CHECK(value == 0 || value == 64 || value == 128, PMX_ERR_INVALID,
+                  "pmx_set_option: \"f16_bn\" = %d: 0 (the launch-size rule), 64 or 128 output channels per block", value);
+        c->opt_f16_bn = value;
     }
     else if (!strcmp(key, "conv_algo")) c->opt_conv_algo = value;
     else if (!strcmp(key, "wino_min_fill")) c->opt_wino_min_fill = value;
@@ -836,8 +823,8 @@ static int plan_conv(pmx_ctx* c, ConvPlan& p, const char* label, PackedLayer* L0
     if (p.form == FORM_F16) {
         kn = ks == 7 ? "conv_f16_7x7" : "conv_f16_3x3";
         // issued: every MFMA of the launch -- the tile padding of the map edges, the channel padding of cin and of the block's BN columns
-        const long long tiles = seg ? a.seg_tiles : (long long)B * ((H + 7) / 8) * ((W + 15) / 16);
-        const int bn = conv_f16_bn(L.cout_pad, (int)std::min<long long>(tiles, 1 << 30), groups);
+        const long long tiles = conv_f16_tiles(a);
+        const int bn = conv_f16_bn(a, groups, c->opt_f16_bn);
         issued = 2.0 * (double)tiles * 128.0 * (double)round_up(L.cout, bn) * (L.nch * CK) * ks * ks * groups;
     } else if (wino) {
         kn = ks == 7 ? "conv_wino_f2x2_7x7" : "conv_wino_f2x2_3x3";
@@ -868,7 +855,7 @@ static int launch_plan(pmx_ctx* c, const ConvPlan& p)
     int rc;
     if (pf && (rc = prof_begin(c, pf->name, pf->flops, pf->bytes, pf->issued))) return rc;
     switch (p.form) {
-    case FORM_F16: rc = conv_f16_launch(p.ks, p.a, p.groups, c->stream); break;
+    case FORM_F16: rc = conv_f16_launch(p.ks, p.a, p.groups, c->opt_f16_bn, c->stream); break;
     case FORM_WINO_UNITS: rc = launch_wino_units(c, p.a, p.ks, p.groups, p.unit_g); break;
     case FORM_WINO: rc = conv_wino_launch(p.a, p.ks, p.groups, c->stream); break;
     default: rc = launch_conv(c, p.a, p.groups, p.variant, p.split); break;
@@ -1868,7 +1855,39 @@ extern "C" int pmx_profile_entry(pmx_ctx* c, int i, char* name, int cap, double*
     return PMX_OK;
 }
 
-// ---------------------------------------------------------------------------- single-layer test entry
+// ---------------------------------------------------------------------------- single-layer test entries
+// a layer that is not in the context's table: packed as set_layer packs one (identity channel map) and uploaded; its buffers, derived packs
+// included, are freed with it
+static int test_layer(PackedLayer& L, const float* w, const float* bias, int cout, int cin, int ks)
+{
+    std::vector<int> cmap = identity_map(cin);
+    L.set = true; L.cin = cin; L.cout = cout; L.ks = ks;
+    L.cin_pad = (int)cmap.size(); L.cout_pad = cout_pad_of(cout); L.nch = L.cin_pad / CK;
+    std::vector<float> wp, bp;
+    pack_weights(w, bias, cout, cin, ks, cmap, L.cout_pad, wp, bp);
+    int rc;
+    if ((rc = L.d_w.alloc(wp.size())) || (rc = L.d_b.alloc(bp.size()))) return rc;
+    PMX_HIP(hipMemcpy(L.d_w, wp.data(), wp.size() * 4, hipMemcpyHostToDevice));
+    PMX_HIP(hipMemcpy(L.d_b, bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
+    return PMX_OK;
+}
+// host NCHW x -> channels [coff, coff + cin) of the NHWC buffer d_xn (channel stride lda), through the staging buffer d_x
+static int test_upload(pmx_ctx* c, const float* x, DevBuf<float>& d_x, float* d_xn, int B, int cin, int H, int W, int lda, int coff)
+{
+    PMX_HIP(hipMemcpy(d_x, x, (size_t)B * cin * H * W * 4, hipMemcpyHostToDevice));
+    return launch_nchw_to_nhwc(d_x, d_xn, B, cin, H, W, lda, coff, c->stream);
+}
+// channels [coff, coff + cout) of the NHWC result d_yn (channel stride ldc) -> host NCHW y, through the staging buffer d_y; synchronises
+static int test_fetch(pmx_ctx* c, const char* who, const float* d_yn, DevBuf<float>& d_y, float* y, int B, int cout, int Ho, int Wo, int ldc, int coff)
+{
+    int rc = launch_nhwc_to_nchw(d_yn, d_y, B, cout, Ho, Wo, ldc, coff, c->stream);
+    if (rc) return rc;
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(y, d_y, (size_t)B * cout * Ho * Wo * 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { pmx_set_error("%s: %s", who, hipGetErrorString(e)); return PMX_ERR_HIP; }
+    return PMX_OK;
+}
+
 // One layer that is not in the context's table, through the dispatcher of the network (plan_conv + launch_plan) under the context's options:
 // the whole batch as ONE plan (no cut by images), never profiled; avg_ms = `iters` launches of that plan between two events.
 extern "C" int pmx_conv2d(pmx_ctx* c, const float* x, const float* w, const float* bias, int B, int cin, int H, int W, int cout,
@@ -1879,25 +1898,17 @@ extern "C" int pmx_conv2d(pmx_ctx* c, const float* x, const float* w, const floa
     PMX_CHECK(B >= 1 && cin >= 1 && cout >= 1 && H >= 1 && W >= 1, PMX_ERR_INVALID, "pmx_conv2d: bad shape");
     PMX_CHECK(!pool || (H % 2 == 0 && W % 2 == 0), PMX_ERR_INVALID, "pmx_conv2d: pool needs even H, W");
     PMX_DEV(c);
-    std::vector<int> cmap = identity_map(cin);
-    PackedLayer L;                                           // (its buffers, derived packs included, are freed on every way out)
-    L.set = true; L.cin = cin; L.cout = cout; L.ks = ks;
-    L.cin_pad = (int)cmap.size(); L.cout_pad = cout_pad_of(cout); L.nch = L.cin_pad / CK;
-    std::vector<float> wp, bp;
-    pack_weights(w, bias, cout, cin, ks, cmap, L.cout_pad, wp, bp);
+    PackedLayer L;
+    int rc;
+    if ((rc = test_layer(L, w, bias, cout, cin, ks))) return rc;
     const int Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W;
     DevBuf<float> d_x, d_xn, d_y, d_yn;
     const size_t nx = (size_t)B * cin * H * W, nxn = (size_t)B * H * W * L.cin_pad, ny = (size_t)B * cout * Ho * Wo;
-    int rc;
-    if ((rc = d_x.alloc(nx)) || (rc = d_xn.alloc(nxn)) || (rc = L.d_w.alloc(wp.size())) || (rc = L.d_b.alloc(bp.size())) ||
-        (rc = d_y.alloc(ny)) || (rc = d_yn.alloc(ny))) return rc;
-    PMX_HIP(hipMemcpy(d_x, x, nx * 4, hipMemcpyHostToDevice));
+    if ((rc = d_x.alloc(nx)) || (rc = d_xn.alloc(nxn)) || (rc = d_y.alloc(ny)) || (rc = d_yn.alloc(ny))) return rc;
     PMX_HIP(hipMemsetAsync(d_xn, 0, nxn * 4, c->stream));
-    PMX_HIP(hipMemcpy(L.d_w, wp.data(), wp.size() * 4, hipMemcpyHostToDevice));
-    PMX_HIP(hipMemcpy(L.d_b, bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
     // poison the output so that unwritten elements are caught by the test
     PMX_HIP(hipMemsetAsync(d_yn, 0xFF, ny * 4, c->stream));
-    if ((rc = launch_nchw_to_nhwc(d_x, d_xn, B, cin, H, W, L.cin_pad, 0, c->stream))) return rc;
+    if ((rc = test_upload(c, x, d_x, d_xn, B, cin, H, W, L.cin_pad, 0))) return rc;
     ConvPlan p;
     if ((rc = plan_conv(c, p, nullptr, &L, nullptr, d_xn, nullptr, L.cin_pad, d_yn, nullptr, cout, B, H, W, relu, pool, -1))) return rc;
     rc = launch_plan(c, p);
@@ -1919,16 +1930,45 @@ extern "C" int pmx_conv2d(pmx_ctx* c, const float* x, const float* w, const floa
         if (e0) (void)hipEventDestroy(e0);
         if (e1) (void)hipEventDestroy(e1);
     }
-    if (!rc) rc = launch_nhwc_to_nchw(d_yn, d_y, B, cout, Ho, Wo, cout, 0, c->stream);
-    if (!rc) {
-        hipError_t e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { pmx_set_error("pmx_conv2d: %s", hipGetErrorString(e)); rc = PMX_ERR_HIP; }
+    return rc ? rc : test_fetch(c, "pmx_conv2d", d_yn, d_y, y, B, cout, Ho, Wo, cout, 0);
+}
+
+// pmx_conv2d for two layers as the two groups of ONE plan (include/pose_mi355x.h), laid out the way run_conv's callers lay out the L1 / L2
+// branches: both inputs are channel slices of one NHWC buffer, both outputs channel slices of another, with channels of nobody between
+// and after them.  x1 null: both groups read x0's slice.
+extern "C" int pmx_conv2d_pair(pmx_ctx* c, const float* x0, const float* x1, const float* w0, const float* bias0, int cout0, const float* w1,
+                               const float* bias1, int cout1, int B, int cin, int H, int W, int ks, int relu, int pool, float* y0, float* y1)
+{
+    PMX_CHECK(c && x0 && w0 && w1 && y0 && y1, PMX_ERR_INVALID, "pmx_conv2d_pair: null arg");
+    PMX_CHECK(ks == 1 || ks == 3 || ks == 7, PMX_ERR_INVALID, "pmx_conv2d_pair: ksize must be 1, 3 or 7");
+    PMX_CHECK(B >= 1 && cin >= 1 && cout0 >= 1 && cout1 >= 1 && H >= 1 && W >= 1, PMX_ERR_INVALID, "pmx_conv2d_pair: bad shape");
+    PMX_CHECK(cout_pad_of(cout0) == cout_pad_of(cout1), PMX_ERR_INVALID, "pmx_conv2d_pair: %d and %d output channels do not pad to the same count",
+              cout0, cout1);
+    PMX_CHECK(!pool || (H % 2 == 0 && W % 2 == 0), PMX_ERR_INVALID, "pmx_conv2d_pair: pool needs even H, W");
+    PMX_DEV(c);
+    PackedLayer L[2];
+    int rc;
+    if ((rc = test_layer(L[0], w0, bias0, cout0, cin, ks)) || (rc = test_layer(L[1], w1, bias1, cout1, cin, ks))) return rc;
+    const int cin_pad = L[0].cin_pad, Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W;
+    // input slices at channels 16 and 16 + cin_pad of lda, output slices at 0 and cout0 (rounded up to 4) of ldc: 4 channels of nobody at the end
+    const int ioff[2] = {CK, x1 ? CK + cin_pad : CK}, lda = ioff[1] + cin_pad + CK;
+    const int ooff[2] = {0, round_up(cout0, 4)}, ldc = ooff[1] + round_up(cout1, 4) + 4, cmax = std::max(cout0, cout1);
+    DevBuf<float> d_x, d_xn, d_y, d_yn;
+    const size_t nx = (size_t)B * cin * H * W, nxn = (size_t)B * H * W * lda, ny = (size_t)B * cmax * Ho * Wo, nyn = (size_t)B * Ho * Wo * ldc;
+    if ((rc = d_x.alloc(nx)) || (rc = d_xn.alloc(nxn)) || (rc = d_y.alloc(ny)) || (rc = d_yn.alloc(nyn))) return rc;
+    PMX_HIP(hipMemsetAsync(d_xn, 0, nxn * 4, c->stream));
+    PMX_HIP(hipMemsetAsync(d_yn, 0xFF, nyn * 4, c->stream));                    // poison, as in pmx_conv2d
+    if ((rc = test_upload(c, x0, d_x, d_xn, B, cin, H, W, lda, ioff[0]))) return rc;
+    if (x1) {
+        PMX_HIP(hipStreamSynchronize(c->stream));                               // (d_x is staged into again)
+        if ((rc = test_upload(c, x1, d_x, d_xn, B, cin, H, W, lda, ioff[1]))) return rc;
     }
-    if (!rc) {
-        hipError_t e = hipMemcpy(y, d_y, ny * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { pmx_set_error("pmx_conv2d: %s", hipGetErrorString(e)); rc = PMX_ERR_HIP; }
-    }
-    return rc;
+    ConvPlan p;
+    if ((rc = plan_conv(c, p, nullptr, &L[0], &L[1], d_xn.get() + ioff[0], d_xn.get() + ioff[1], lda, d_yn.get() + ooff[0], d_yn.get() + ooff[1], ldc,
+                        B, H, W, relu, pool, -1))) return rc;
+    if ((rc = launch_plan(c, p))) return rc;
+    if ((rc = test_fetch(c, "pmx_conv2d_pair", d_yn, d_y, y0, B, cout0, Ho, Wo, ldc, ooff[0]))) return rc;
+    return test_fetch(c, "pmx_conv2d_pair", d_yn, d_y, y1, B, cout1, Ho, Wo, ldc, ooff[1]);
 }
 
 // The backward twin of pmx_conv2d (include/pose_mi355x.h).  z and dx are plans of the dispatcher, each the whole batch as ONE plan as in

@@ -213,8 +213,9 @@ int conv_bf16x3_launch(int ks, int mt, int pool, const ConvArgs& a, int groups, 
 int conv_bf16x3_twin(int variant);      // the bf16x3 kernel with the geometry of a v6 variant, or -1
 // conv_f16.hip (option "precision" = 2): the 3x3 / 7x7 layers as direct convolutions on v_mfma_f32_32x32x16_f16, 8 x 16 pixel tiles
 // (a.nseg > 0: the PMX_SEG_RECT tables of a heterogeneous forward); a.g[].w = the layer's f16 pack [tap][chunk][cout_pad][16]
-int conv_f16_launch(int ks, const ConvArgs& a, int groups, hipStream_t stream);
-int conv_f16_bn(int cout_pad, int tiles, int groups);     // output channels per block the launch takes (128 | 64)
+int conv_f16_launch(int ks, const ConvArgs& a, int groups, int f16_bn, hipStream_t stream);     // f16_bn: option "f16_bn" (0 | 64 | 128)
+long long conv_f16_tiles(const ConvArgs& a);                 // 8 x 16 pixel tiles of the launch
+int conv_f16_bn(const ConvArgs& a, int groups, int f16_bn);  // output channels per block the launch takes (128 | 64)
 void conv_set_num_cus(int n);     // compute units of the device the contexts run on (tile / kernel selection heuristics)
 int conv_num_cus();
 // packed weight geometry helpers

@@ -292,6 +292,7 @@ struct pmx_ctx {
     int opt_precision = 0;           // 0: fp32 MFMA everywhere (the path whose results are specified); 1: bf16x3 kernels where a
                                      // v6 kernel would run (fp32-grade accuracy at 2.67x the matrix rate, NOT the fp32 FMA chain);
                                      // 2: f16 mode -- every 3x3 / 7x7 layer on conv_f16_kernel (f16 operands, fp32 sums; the 1x1 layers stay fp32)
+    int opt_f16_bn = 0;              // f16 mode: output channels per block, 0 = conv_f16_bn's rule, 64 | 128 = that width (same bits; tests)
     int opt_conv1_wino = 1;          // fused conv1_1 + conv1_2 with conv1_2 as Winograd F(2x2, 3x3) (conv1_wino_kernel) where conv_algo allows Winograd
     int opt_fuse_conv1 = 1;          // conv1_1 recomputed on conv1_2's halo tile, one launch (conv1_fused_kernel); identical bits
     int opt_fuse_pairs = 1;          // the two 1x1 layers that end every stage run as one launch (conv1x1_pair_kernel)

@@ -35,7 +35,7 @@ SOURCES = [('pmx_api.hip', []), ('pmx_precise.hip', []), ('pmx_multi.hip', []), 
 # library is rebuilt when the variable changes)
 if os.environ.get('PMX_BUILD_BF16X3', '') not in ('', '0'):
     SOURCES.append(('conv_bf16x3.hip', []))
-HEADERS = ['pmx_common.h', 'pmx_ctx.h', 'pp_tables.h', 'wino_util.h', 'conv_direct.h', 'pp_smooth.h', 'conv_bwd_pack.h', 'pack_index.h', 'wgrad_strips.h', HEADER]
+HEADERS = ['pmx_common.h', 'pmx_ctx.h', 'pp_tables.h', 'wino_util.h', 'conv_direct.h', 'pp_smooth.h', 'conv_bwd_pack.h', 'pack_index.h', 'wgrad_strips.h', 'f16_round.h', HEADER]
 
 N_JOINTS, N_LIMBS, N_PAF, N_HEAT = 18, 19, 38, 19
 # the detectors' precision= keyword -> engine option "precision" (include/pose_mi355x.h): fp32 (default), bf16x3 (opt-in build), f16 mode
@@ -319,6 +319,7 @@ def load():
         'pmx_profile_entry': (ci, [vp, ci, C.c_char_p, ci, dp, C.POINTER(C.c_int64), dp, dp]),
         'pmx_profile_issued': (ci, [vp, ci, dp]),
         'pmx_conv2d': (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, ci, dp]),
+        'pmx_conv2d_pair': (ci, [vp, vp, vp, vp, vp, ci, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp]),
         'pmx_conv2d_backward': (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, dp]),
         'pmx_loss_grad_enable': (ci, [vp, ci]),
         'pmx_get_loss_grads': (ci, [vp, ci, vp, vp]),
@@ -1234,6 +1235,27 @@ class Engine(object):
         self._check(self.lib.pmx_conv2d(self._ctx, _ptr(x), _ptr(W), bp, B, ci, H, Wd, co, k, int(relu), int(pool),
                                         _ptr(y), int(iters), C.byref(ms)))
         return (y, ms.value) if iters else y
+
+    def conv2d_pair(self, x0, W0, b0, W1, b1, x1=None, relu=False, pool=False):
+        """conv2d for two layers of equal kernel size and input channels as the two groups of ONE launch (include/pose_mi355x.h::
+        pmx_conv2d_pair): (y0, y1).  x1 None: both groups read x0."""
+        x0 = np.ascontiguousarray(x0, dtype=np.float32)
+        W0 = np.ascontiguousarray(W0, dtype=np.float32)
+        W1 = np.ascontiguousarray(W1, dtype=np.float32)
+        B, ci, H, Wd = x0.shape
+        k = W0.shape[2]
+        assert W0.shape[1:] == (ci, k, k) and W1.shape[1:] == (ci, k, k)
+        x1p = None
+        if x1 is not None:
+            x1 = np.ascontiguousarray(x1, dtype=np.float32)
+            assert x1.shape == x0.shape
+            x1p = _ptr(x1)
+        bs = [None if b is None else np.ascontiguousarray(b, dtype=np.float32) for b in (b0, b1)]
+        bp = [None if b is None else _ptr(b) for b in bs]
+        ys = [np.empty((B, Wg.shape[0], H // 2 if pool else H, Wd // 2 if pool else Wd), np.float32) for Wg in (W0, W1)]
+        self._check(self.lib.pmx_conv2d_pair(self._ctx, _ptr(x0), x1p, _ptr(W0), bp[0], W0.shape[0], _ptr(W1), bp[1], W1.shape[0],
+                                             B, ci, H, Wd, k, int(relu), int(pool), _ptr(ys[0]), _ptr(ys[1])))
+        return ys[0], ys[1]
 
     def conv2d_backward(self, x, W, b, dy, relu=False, pool=False, want=('dx', 'dw', 'db', 'z'), iters=0):
         """The gradients of one convolution layer (include/pose_mi355x.h::pmx_conv2d_backward): a dict with the arrays named in `want`

@@ -139,11 +139,16 @@ int pmx_synchronize(pmx_ctx* ctx);                    /* cuda.get_device_from_id
  *                              the f16 matrix cores: per output y = sum over (16-channel chunk, tap) of f16(x) * f16(w), summed in
  *                              fp32 on v_mfma_f32_32x32x16_f16 in an order fixed per layer (chunk-major, taps row-major, no split-K),
  *                              then the fp32 epilogue (2x2 max-pool, + bias, ReLU).  f16(v) = round-to-nearest-even saturating at
- *                              +-65504 (no inf); weights are rounded once, on the host; activations stay fp32 in device memory and
+ *                              +-65504 (no inf; f16 subnormals are kept, NaN stays NaN); weights are rounded once, on the host; activations stay fp32 in device memory and
  *                              are rounded while a kernel stages them.  The 1x1 layers stay fp32.  The order does not depend on the
  *                              batch, the image's position or the segment layout: an image gives the same maps bit for bit alone,
  *                              anywhere in a uniform batch and inside a mixed-size batch (pmx_detect_images).  Accuracy against
  *                              the fp32 path: INTEGRATION.md section 4.  Any other value: PMX_ERR_INVALID, the option unchanged
+ *   "f16_bn" 0 | 64 | 128      f16 mode, a test seam: output channels per block of a 3x3 / 7x7 launch.  0 (default): 128 where the launch
+ *                              then still has a block per CU, else 64.  64 | 128: that width whatever the launch size (128 only for
+ *                              layers whose padded channel count is a multiple of 128; the others stay at 64).  Same bits either way
+ *                              (the order above does not depend on it); per context; profile labels unchanged.  Any other value:
+ *                              PMX_ERR_INVALID, the option unchanged
  *   "fuse_conv1" 1 | 0         conv1_1 recomputed on conv1_2's halo tiles, one launch instead of two (default 1); identical bits
  *   "precise_lanes" 1..4       detect_precise: inference scales in flight at once, each on its own stream and working set (default 4;
  *                              1: one after the other on the context's stream); same bits
@@ -520,6 +525,18 @@ int pmx_profile_issued(pmx_ctx* ctx, int i, double* issued_flop_per_launch);
 int pmx_conv2d(pmx_ctx* ctx, const float* x_nchw, const float* w_oihw, const float* bias,
                int batch, int cin, int h, int w, int cout, int ksize, int relu, int pool,
                float* y_nchw, int iters, double* avg_ms);
+
+/* ---- kernel unit-test entry: two layers as the two groups of one launch ---------------------------
+ * pmx_conv2d for two layers of equal ksize and cin whose output channels pad to the same count (both <= 64, or the same multiple of 128;
+ * cout0 and cout1 themselves may differ), planned as ONE launch of two groups under the context's options -- the form the PAF / heat-map
+ * branches of the network run in.  On the device the inputs are channel slices of one NHWC buffer and the outputs channel slices of
+ * another, each with a channel stride larger than a group's own channels, as the branches' buffers are; the output buffer is poisoned
+ * (all bits set) first.  x1 null: both groups read x0.  Host pointers; x (B, cin, h, w), w OIHW, y0 (B, cout0, h', w'), y1 (B, cout1, h',
+ * w'); not timed.  PMX_ERR_INVALID for a null pointer, a ksize outside {1, 3, 7}, a non-positive shape, pool with odd h or w, or output
+ * channel counts that pad differently. */
+int pmx_conv2d_pair(pmx_ctx* ctx, const float* x0_nchw, const float* x1_nchw, const float* w0_oihw, const float* bias0, int cout0,
+                    const float* w1_oihw, const float* bias1, int cout1, int batch, int cin, int h, int w, int ksize, int relu, int pool,
+                    float* y0_nchw, float* y1_nchw);
 
 /* ---- the backward twin of pmx_conv2d: the gradients of one convolution layer ---------------------
  * Host pointers, float32, the layouts of pmx_conv2d: x (B, cin, h, w), w OIHW, dy (B, cout, h', w') with h' = h/2, w' = w/2 if pool.

@@ -81,6 +81,40 @@ def forward_f16(weights, x, acc='f64'):
     return h1, h2
 
 
+def lattice_case(kind, ks, cin, seed, cout=128, B=2, H=10, W=18):
+    """(x, W, b) on which every fp32 summation order of the f16 mode is exact, so that a kernel must EQUAL conv_f16.
+    'a': x = k * 2^-24, integer |k| <= 1023 -- every nonzero activation an f16 subnormal -- and W = m * 2^8, integer |m| <= 4.
+    'b': the roles swapped, and the weights unrounded: half of them at ties, (k + 1/2) * 2^-24, and a few below the smallest f16
+    subnormal's half: 2^-25 (the tie to zero), its float32 successor (rounds up to 2^-24) and -2^-26 (rounds to -0).
+    'c': 'a' with the unrounded small values of 'b' as the activations (the device's conversion at subnormal ties).
+    After f16() every operand is q * 2^-24, |q| <= 1023, or m * 2^8: a product is an integer multiple of 2^-16 of at most
+    1023 * 4 * 2^-16, and a sum of the cin * ks * ks <= 48 * 49 of them stays below 147; with a bias that is a multiple of 2^-16 of at
+    most 1 every partial result is a multiple of 2^-16 below 2^8 = 2^-16 * 2^24: representable in fp32, so no addition rounds.
+    'd': the device's conversion at ties of normal numbers: x = +-(1 + (2 j + 1) * 2^-11), halfway between two f16 values of [1, 2], and
+    W = m, integer |m| <= 2.  f16(x) is a multiple of 2^-10 of at most 2, a sum stays below 48 * 49 * 2 * 2 = 9408, the bias is a
+    multiple of 2^-10 of at most 1: multiples of 2^-10 below 2^14 = 2^-10 * 2^24, exact again."""
+    rng = np.random.default_rng(seed)
+    xs, ws = (B, cin, H, W), (cout, cin, ks, ks)
+    if kind == 'd':
+        x = ((1 + (2 * rng.integers(0, 1024, xs) + 1) * 2.0 ** -11) * rng.choice([-1.0, 1.0], xs)).astype(np.float32)
+        Wt = rng.integers(-2, 3, ws).astype(np.float32)
+        return x, Wt, (rng.integers(-1024, 1025, cout) * 2.0 ** -10).astype(np.float32)
+    sub = (rng.integers(-1023, 1024, xs if kind in 'ac' else ws) * 2.0 ** -24).astype(np.float32)
+    big = (rng.integers(-4, 5, ws if kind in 'ac' else xs) * 2.0 ** 8).astype(np.float32)
+    if kind != 'a':
+        ties = rng.random(sub.shape) < 0.5
+        ties &= sub < np.float32(1023 * 2.0 ** -24)                     # (so that a tie never rounds past 1023 * 2^-24)
+        sub = np.where(ties, sub + np.float32(2.0 ** -25), sub).astype(np.float32)
+        flat = sub.reshape(-1)
+        at = rng.choice(flat.size, 12, replace=False)
+        flat[at[0:4]] = np.float32(2.0 ** -25)
+        flat[at[4:8]] = np.nextafter(np.float32(2.0 ** -25), np.float32(1))
+        flat[at[8:12]] = np.float32(-2.0 ** -26)
+    x, Wt = (sub, big) if kind in 'ac' else (big, sub)
+    b = np.zeros(cout, np.float32) if cin == 16 else (rng.integers(-65536, 65537, cout) * 2.0 ** -16).astype(np.float32)
+    return x, Wt, b
+
+
 def rel_err(a, b):
     """max |a - b| relative to max(1, max |b|) (the suite's network-map measure)."""
     return float(np.abs(np.asarray(a, np.float64) - b).max() / max(1.0, float(np.abs(b).max())))

@@ -1,6 +1,12 @@
 """GPU: the opt-in f16 inference mode (engine option "precision" = 2, `precision='f16'` on the detectors) against its arithmetic
 contract (tests/f16_emulation.py; include/pose_mi355x.h): single layers, saturation, whole-network maps,
-invariance of an image's bits to the launch it is part of, the detectors' entry points, and the option's edges."""
+invariance of an image's bits to the launch it is part of, the detectors' entry points, and the option's edges.
+
+The launch forms of conv_f16_kernel -- KS 3 | 7, BN 64 | 128 channels per block (option "f16_bn" forces either at any size), one or two
+groups (Engine.conv2d_pair), pooled or not, with or without the segment table of a mixed-size forward -- each under a tight check:
+test_forms_single_layer, test_forms_pairs, test_forms_network; the operand edges (f16 subnormals, ties, NaN, infinities) in
+test_subnormal_lattice_is_exact and test_nan_and_infinities."""
+import functools
 import os
 
 import numpy as np
@@ -8,6 +14,8 @@ import pytest
 
 import f16_emulation as E
 from conftest import GOLDEN, pkg
+from oracle import network_ref
+from test_gpu_winograd import TOL as F32_TOL
 from test_reference_network import _x, load_e2e
 
 pytestmark = pytest.mark.gpu
@@ -46,13 +54,24 @@ LAYER_CASES = [
 ]
 
 
-@pytest.mark.parametrize('case', LAYER_CASES, ids=lambda c: 'k%d_ci%d_co%d_r%d_p%d_b%d_%dx%d' % tuple(int(v) for v in c))
-def test_single_layer_matches_emulation(engine, case):
+def _case_id(c):
+    return 'k%d_ci%d_co%d_r%d_p%d_b%d_%dx%d' % tuple(int(v) for v in c)
+
+
+def _layer_data(case, salt=0):
+    """The file's operand distribution for a case (ks, cin, cout, relu, pool, B, H, W)."""
     ks, cin, cout, relu, pool, B, H, W = case
-    rng = np.random.default_rng(ks * 1000 + cin + cout + H)
+    rng = np.random.default_rng(ks * 1000 + cin + cout + H + salt)
     x = rng.uniform(-1, 1, (B, cin, H, W)).astype(np.float32)
     Wt = (rng.standard_normal((cout, cin, ks, ks)) / np.sqrt(cin * ks * ks)).astype(np.float32)
     b = rng.uniform(-0.1, 0.1, cout).astype(np.float32)
+    return x, Wt, b
+
+
+@pytest.mark.parametrize('case', LAYER_CASES, ids=_case_id)
+def test_single_layer_matches_emulation(engine, case):
+    ks, cin, cout, relu, pool, B, H, W = case
+    x, Wt, b = _layer_data(case)
     ref = E.conv_f16(x, Wt, b, relu, pool)
     unrounded = E.conv_f16(x, Wt, b, relu, pool, rounded=False)
     tol = 2e-5 * max(1.0, float(np.abs(ref).max()))
@@ -83,6 +102,202 @@ def test_saturation(engine):
         _f32(engine)
     assert np.isfinite(y).all()
     assert float(np.abs(y - ref).max()) <= 2e-5 * float(np.abs(ref).max())
+
+
+# ---- the launch forms, forced at small shapes (option "f16_bn", Engine.conv2d_pair) ------------------------------------------------------
+FORM_CASES = [
+    # (ks, cin, cout, relu, pool, B, H, W)
+    (7, 48, 128, 1, 0, 2, 13, 21),                # ragged on both edges
+    (7, 185, 130, 1, 0, 1, 9, 17),                # partial chunk, a part-used channel block (cout_pad 256)
+    (3, 64, 128, 1, 1, 3, 10, 18),                # pooled, ragged
+    (3, 3, 128, 0, 0, 1, 8, 16),                  # exactly one tile, one chunk
+    (7, 32, 256, 0, 0, 1, 3, 5),                  # the image is smaller than the kernel
+    (7, 64, 128, 1, 1, 2, 12, 20),                # 7x7 pooled, ragged
+    (3, 32, 64, 1, 0, 2, 9, 17),                  # cout_pad 64: "f16_bn" = 128 does not apply, the launch stays at 64
+]
+
+
+@functools.lru_cache(maxsize=None)
+def _form_ref(case):
+    """(x, W, b, emulation with float64 sums, the same on unrounded operands, tol): computed once per case; nobody writes to them."""
+    x, Wt, b = _layer_data(case)
+    ref = E.conv_f16(x, Wt, b, case[3], case[4])
+    unrounded = E.conv_f16(x, Wt, b, case[3], case[4], rounded=False)
+    return x, Wt, b, ref, unrounded, 2e-5 * max(1.0, float(np.abs(ref).max()))
+
+
+def _with_f16(engine, bn, fn):
+    engine.set_option('precision', 2)
+    engine.set_option('f16_bn', bn)
+    try:
+        return fn()
+    finally:
+        engine.set_option('f16_bn', 0)
+        engine.set_option('precision', 0)
+
+
+@pytest.mark.parametrize('case', FORM_CASES, ids=_case_id)
+def test_forms_single_layer(engine, case):
+    """conv_f16_kernel<KS, 64> and <KS, 128> on the same small layer: each within the single-layer bound of the emulation, finite
+    everywhere (the output is poisoned), the operand rounding visible -- and the two bit-equal (the contract: nothing depends on BN)."""
+    ks, cin, cout, relu, pool, B, H, W = case
+    x, Wt, b, ref, unrounded, tol = _form_ref(case)
+    ys = {bn: _with_f16(engine, bn, lambda: engine.conv2d(x, Wt, b, relu=bool(relu), pool=bool(pool))) for bn in (64, 128)}
+    for bn, y in ys.items():
+        assert y.shape == ref.shape and np.isfinite(y).all(), bn
+        err, ctl = float(np.abs(y - ref).max()), float(np.abs(y - unrounded).max())
+        print('f16_bn %d: err %.3g = %.3g tol, control %.3g tol' % (bn, err, err / tol, ctl / tol))
+        assert err <= tol, (bn, err, tol)
+        assert ctl > 10 * tol, (bn, ctl, tol)
+    assert np.array_equal(ys[64], ys[128]), (float(np.abs(ys[64] - ys[128]).max()), int((ys[64] != ys[128]).sum()))
+
+
+def test_f16_bn_option_values(engine):
+    for bad in (-1, 1, 32, 96, 256):
+        with pytest.raises(Exception):
+            engine.set_option('f16_bn', bad)
+    for good in (64, 128, 0):
+        engine.set_option('f16_bn', good)
+
+
+# (single-layer case, couts of the two groups)
+PAIR_CASES = [(FORM_CASES[0], (128, 128)), (FORM_CASES[2], (128, 128)), ((3, 48, 128, 1, 0, 2, 9, 17), (100, 128))]
+
+
+def _pair_data(case, couts):
+    """Group 0: the case's own operands (its first couts[0] output channels); group 1: a second draw of the same distribution."""
+    x0, W0, b0 = _layer_data(case)
+    x1, W1, b1 = _layer_data(case, salt=7)
+    return x0, W0[:couts[0]], b0[:couts[0]], x1, W1[:couts[1]], b1[:couts[1]]
+
+
+@pytest.mark.parametrize('case,couts', PAIR_CASES, ids=lambda v: _case_id(v) if len(v) == 8 else 'co%d_%d' % v)
+def test_forms_pairs(engine, case, couts):
+    """Two groups in one launch (blockIdx.z = 1; inputs and outputs as channel slices of wider buffers), shared and separate inputs,
+    BN 64 and 128: each group's output is bit-equal to conv2d of that group alone, and swapping the groups swaps the outputs."""
+    relu, pool = bool(case[3]), bool(case[4])
+    x0, W0, b0, x1, W1, b1 = _pair_data(case, couts)
+
+    def run():
+        alone = {(g, i): engine.conv2d(x, Wg, bg, relu=relu, pool=pool) for g, i, x, Wg, bg in ((0, 0, x0, W0, b0), (1, 0, x0, W1, b1), (1, 1, x1, W1, b1))}
+        out = {}
+        for bn in (64, 128):
+            engine.set_option('f16_bn', bn)
+            out[bn, 'shared'] = engine.conv2d_pair(x0, W0, b0, W1, b1, relu=relu, pool=pool)
+            out[bn, 'separate'] = engine.conv2d_pair(x0, W0, b0, W1, b1, x1=x1, relu=relu, pool=pool)
+            out[bn, 'shared swapped'] = engine.conv2d_pair(x0, W1, b1, W0, b0, relu=relu, pool=pool)[::-1]
+            out[bn, 'separate swapped'] = engine.conv2d_pair(x1, W1, b1, W0, b0, x1=x0, relu=relu, pool=pool)[::-1]
+        return alone, out
+    alone, out = _with_f16(engine, 64, run)
+    assert not np.array_equal(alone[0, 0][:, :min(couts)], alone[1, 0][:, :min(couts)])
+    for (bn, how), (y0, y1) in out.items():
+        i1 = int(how.startswith('separate'))
+        assert np.isfinite(y0).all() and np.isfinite(y1).all(), (bn, how)
+        assert np.array_equal(y0, alone[0, 0]), (bn, how, float(np.abs(y0 - alone[0, 0]).max()))
+        assert np.array_equal(y1, alone[1, i1]), (bn, how, float(np.abs(y1 - alone[1, i1]).max()))
+
+
+def test_pair_entry_fp32(engine):
+    """conv2d_pair outside the f16 mode: the direct fp32 kernels with two groups, against the float64 reference at the fp32 bound."""
+    case, couts = PAIR_CASES[2]
+    x0, W0, b0, x1, W1, b1 = _pair_data(case, couts)
+    engine.set_option('precision', 0)
+    engine.set_option('conv_algo', 0)
+    engine.set_option('ksplit', 1)
+    try:
+        y0, y1 = engine.conv2d_pair(x0, W0, b0, W1, b1, x1=x1, relu=True)
+        s0, s1 = engine.conv2d_pair(x0, W0, b0, W1, b1, relu=True)
+    finally:
+        engine.set_option('ksplit', 0)
+    for y, x, Wg, bg in ((y0, x0, W0, b0), (y1, x1, W1, b1), (s0, x0, W0, b0), (s1, x0, W1, b1)):
+        t = network_ref.conv2d_ref(x, Wg, bg, relu=True, pool=False)
+        assert y.shape == t.shape and np.isfinite(y).all()
+        assert np.abs(y - t).max() <= F32_TOL * max(1.0, np.abs(t).max())
+
+
+def test_forms_network(native):
+    """The segment table of a mixed-size forward and the two-group stage launches at BN = 128, at the smallest sizes: an image's maps
+    are bit-equal alone (BN 64 and 128), inside a uniform batch of 3 and inside a mixed list, at both widths."""
+    rng = np.random.default_rng(33)
+    imgs = [rng.integers(0, 256, (h, w, 3), dtype=np.uint8) for h, w in ((24, 40), (40, 24), (16, 16))]
+    eng = native.Engine(0, max_batch=4, max_h=40, max_w=40)
+    try:
+        eng.set_weights(pkg('weights').synthetic_weights(0))
+        eng.set_option('precision', 2)
+        eng.set_option('f16_bn', 64)
+        alone = []
+        for img in imgs:
+            eng.forward_u8(img[None])
+            alone.append([m[0] for m in eng.get_maps()])
+            assert all(np.isfinite(m).all() and np.abs(m).max() > 0 for m in alone[-1])
+        for bn in (64, 128):
+            eng.set_option('f16_bn', bn)
+            for i, img in enumerate(imgs):
+                for pos, B in ((0, 1), (1, 3)):
+                    batch = rng.integers(0, 256, (B,) + img.shape, dtype=np.uint8)
+                    batch[pos] = img
+                    eng.forward_u8(batch)
+                    paf, heat = eng.get_maps()
+                    assert np.array_equal(paf[pos], alone[i][0]) and np.array_equal(heat[pos], alone[i][1]), (bn, i, B)
+            eng.forward_u8_images(imgs)
+            for i in range(len(imgs)):
+                paf, heat = eng.image_maps(i)
+                assert np.array_equal(paf, alone[i][0]) and np.array_equal(heat, alone[i][1]), (bn, i, 'mixed')
+    finally:
+        eng.close()
+
+
+# ---- operand edges ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('kind', ['a', 'b', 'c', 'd'])
+@pytest.mark.parametrize('ks,cin', [(3, 16), (3, 48), (7, 16), (7, 48)])
+def test_subnormal_lattice_is_exact(engine, kind, ks, cin):
+    """Zero tolerance, by derivation (f16_emulation.lattice_case; its premise is tests/test_f16_host.py::
+    test_emulation_is_exact_on_the_lattice): every product and every partial sum is exactly representable in fp32, so the kernel must
+    EQUAL the float64 convolution of the f16-rounded operands, whatever its summation order.  'a': every activation an f16 subnormal --
+    the kernel's conversion and the matrix core must keep them; 'b': every weight one, half of them at ties and a few below 2^-25 --
+    the host packer's subnormal / tie branch, through the device; 'c': those unrounded values as activations, 'd': activations at the
+    ties of [1, 2] -- the kernel's conversion rounds to nearest even, subnormals included."""
+    x, Wt, b = E.lattice_case(kind, ks, cin, seed=ks * 100 + cin)
+    ref = E.conv_f16(x, Wt, b)
+    assert np.abs(ref).max() > 0.01
+    for bn in (64, 128):
+        y = _with_f16(engine, bn, lambda: engine.conv2d(x, Wt, b))
+        bad = y != ref
+        assert not bad.any(), (bn, int(bad.sum()), float(np.abs(y - ref).max()))
+    if kind != 'a':
+        assert not np.array_equal(y, E.conv_f16(x, Wt, b, rounded=False))
+
+
+@pytest.mark.parametrize('ks', [3, 7])
+def test_nan_and_infinities(engine, ks):
+    """f16(NaN) is NaN and f16(+-inf) is +-65504, for activations (the kernel's conversion) and weights (the host packer): the NaN
+    pattern of the output equals the emulation's, every other output is finite and within the single-layer bound.  relu = 0 and
+    pool = 0 only: the fmaxf of the ReLU and of the pool in the epilogue every kernel shares drops a NaN as every fp32 kernel of this
+    library does; that is outside the f16 contract and out of scope here."""
+    case = (ks, 32, 64, 0, 0, 2, 12, 36)
+    x, Wt, b = _layer_data(case)
+    x[0, 3, 4, 5] = np.nan
+    x[0, 17, 5, 18] = np.inf
+    x[1, 8, 6, 30] = -np.inf
+    ref = E.conv_f16(x, Wt, b)
+    nan = np.isnan(ref)
+    assert nan.sum() == 64 * ks * ks and not nan[1].any() and not np.isinf(ref).any()
+    for bn in (64, 128):
+        y = _with_f16(engine, bn, lambda: engine.conv2d(x, Wt, b))
+        assert np.array_equal(np.isnan(y), nan), (bn, int(np.isnan(y).sum()), int(nan.sum()))
+        assert not np.isinf(y).any()
+        tol = 2e-5 * max(1.0, float(np.abs(ref[~nan]).max()))
+        assert float(np.abs(y[~nan] - ref[~nan]).max()) <= tol
+    # one NaN weight (centre tap: no output's window leaves it to the padding): exactly that output channel is NaN
+    x, Wt, b = _layer_data(case)
+    Wt[37, 5, ks // 2, ks // 2] = np.nan
+    ref = E.conv_f16(x, Wt, b)
+    nan = np.zeros(ref.shape, bool)
+    nan[:, 37] = True
+    assert np.array_equal(np.isnan(ref), nan)
+    y = _with_f16(engine, 0, lambda: engine.conv2d(x, Wt, b))
+    assert np.array_equal(np.isnan(y), nan) and not np.isinf(y).any()
+    assert float(np.abs(y[~nan] - ref[~nan]).max()) <= 2e-5 * max(1.0, float(np.abs(ref[~nan]).max()))
 
 
 def _net_maps(native, seed, h, w, precision):
