@@ -1,4 +1,4 @@
-/* pack_index.h -- the index arithmetic of the weight packs, shared by the host packers (pmx_api.hip: pack_weights, pack_wino), the device
+/* pack_index.h -- the index arithmetic of the weight packs, shared by the host packers (pmx_api.hip: pack_weights, pack_wino, pack_conv1), the device
  * packers of the training step (pmx_train.hip) and the tests, which compile it into a stand-alone program.  Plain C; every function is
  * `static inline` and, under hipcc, callable from both sides.  Nothing here touches a weight: only where a weight goes. */
 #ifndef PMX_PACK_INDEX_H
@@ -61,4 +61,13 @@ static inline PMX_HD size_t pmx_pk_wino(int plane, int n, int ci, int nch32, int
     return (((((size_t)plane * nch32 + ci / 32) * (cout_pad / 32) + n / 32) * 4 + (ci % 32) / 8) * 32 + n % 32) * 8 + ci % 8;
 }
 static inline PMX_HD int pmx_pk_wino_planes(int ks) { return ks == 3 ? 16 : 81; }
+
+/* conv1_1's fused-kernel pack [channel half 2][k-pair 14][k of the pair 2][channel 32], k = tap * 3 + input channel: the float of conv1_1's
+ * direct pack [tap 9][1 chunk][cout_pad][16] that position idx holds, -1 for the 28th k of a channel (a zero) */
+#define PMX_PK_CONV1_FLOATS (2 * 14 * 2 * 32)
+static inline PMX_HD long long pmx_pk_conv1_src(int idx, int cout_pad)
+{
+    const int n = idx % 32, kk = (idx / 32) % 2, sp = (idx / 64) % 14, hf = idx / 896, k = 2 * sp + kk;
+    return k < 27 ? (long long)pmx_pk_direct(k / 3, k % 3, hf * 32 + n, 1, cout_pad) : -1;
+}
 #endif

@@ -190,14 +190,11 @@ static void pack_f16(const std::vector<float>& wp, std::vector<uint16_t>& out)
 // 64 bytes apart: 1.7 us of a 25 us block (profiles/r05_conv1_wino_ablation.json).
 static void pack_conv1(const std::vector<float>& wp, int cout_pad, std::vector<float>& out)
 {
-    out.assign(2 * 14 * 2 * 32, 0.f);
-    for (int hf = 0; hf < 2; ++hf)
-        for (int sp = 0; sp < 14; ++sp)
-            for (int kk = 0; kk < 2; ++kk)
-                for (int n = 0; n < 32; ++n) {
-                    const int k = 2 * sp + kk;
-                    if (k < 27) out[((hf * 14 + sp) * 2 + kk) * 32 + n] = wp[((size_t)(k / 3) * cout_pad + hf * 32 + n) * CK + k % 3];
-                }
+    out.assign(PMX_PK_CONV1_FLOATS, 0.f);
+    for (int i = 0; i < PMX_PK_CONV1_FLOATS; ++i) {
+        const long long src = pmx_pk_conv1_src(i, cout_pad);      // (pack_index.h: the training step's device packer shares it)
+        if (src >= 0) out[i] = wp[src];
+    }
 }
 
 int pmx_pack_kind(const pmx_ctx* c, int cin) { return c->kind == NET_POSE ? (cin == 185 ? 1 : 0) : cin == c->n_heat + 128 ? 2 + c->n_heat : 0; }

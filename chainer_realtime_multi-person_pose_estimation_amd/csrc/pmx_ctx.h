@@ -150,7 +150,7 @@ struct BwState {
     DevBuf<double> part;                                  // bias-gradient slots
     DevBuf<int> cat_of_ref;                               // concat-buffer channel of the reference's input channel 0 .. 184 of Mconv1_*
     std::vector<PackedLayer> tl;                          // per layer: the pack whose forward is the data gradient (set = built)
-    bool stepped = false;                                 // pmx_train_step_head consumed the gradients of this backward
+    bool stepped = false;                                 // pmx_train_step_head or pmx_train_step consumed the gradients of this backward
     int slot_layer[PMX_BW_SLOTS][2] = {};                 // table index of the slot's L1 / L2 layer (one-branch slots: both the same; X42: conv4_2)
     std::vector<int> layer_slot;                          // by table index: slot * 2 + branch, -1 for the trunk layers before conv4_2
     // Trunk backward (mode 2; include/pose_mi355x.h: pmx_backward_trunk).  The ten layers conv1_1 .. conv4_2 in forward order, t = 0 .. 9, at
@@ -169,10 +169,11 @@ constexpr int PMX_TRUNK_LAYERS = 10;
 struct TrunkDesc { const char* name; int cin, cout, level, pool; };      // pool: the forward pools this layer's output
 extern const TrunkDesc pmx_trunk_desc[PMX_TRUNK_LAYERS];
 
-// Head training step (pmx_train.hip; include/pose_mi355x.h: pmx_train_*).  Three stores with the layout of BwState::grad -- per head layer
-// w | b at grad_off[layer], padded to a multiple of 64 floats: the master weights (OIHW, reference input order), Adam's first and second
-// moments.  Per layer of c->table: its step count and gradient scale (trunk layers: unused today; the arrays cover them so that they can join).
-// seg_host / seg_dev: the per-segment table of one step, one copy from pinned memory (`seg_copied` marks when the host side may be rewritten).
+// Training steps (pmx_train.hip; include/pose_mi355x.h: pmx_train_*).  Three stores with the layout of BwState::grad -- per head layer, in
+// mode 2 per trunk layer as well, w | b at grad_off[layer], padded to a multiple of 64 floats: the master weights (OIHW, reference input
+// order), Adam's first and second moments.  Per layer of c->table: its step count and gradient scale (trunk layers: used in mode 2).
+// seg_host / seg_dev: the tables of one step -- the Adam segments, then the packers' jobs (pmx_train.hip: jobs_at) -- one copy from pinned
+// memory (`seg_copied` marks when the host side may be rewritten).
 struct AdamSeg { unsigned long long off; unsigned n, blk0; float scale, alpha_t; };      // blk0: first block of the segment in the launch
 struct TrainState {
     int on = 0;
@@ -431,7 +432,7 @@ int pmx_bw_transposed_pack(pmx_ctx* c, int layer);
 // c->smoothed (and c->pp.smoothed) at `floats` floats at least, grown to exactly that once the stream no longer uses the old maps
 int pmx_ensure_smoothed(pmx_ctx* c, size_t floats);
 // pmx_api.hip, for pmx_train.hip: the channel map kind of a layer's direct pack (pack_index.h), and pmx_set_layer's hook -- with training on,
-// a head layer's new weights also go to the master store (pmx_train.hip)
+// the new weights of a layer with a segment (head; mode 2: trunk too) also go to the master store (pmx_train.hip)
 int pmx_pack_kind(const pmx_ctx* c, int cin);
 int pmx_train_on_set_layer(pmx_ctx* c, int layer, const float* w, const float* bias);
 void pmx_train_free(pmx_ctx* c);

@@ -1,5 +1,5 @@
-// pmx_train.hip -- the head training step of the C ABI: pmx_train_enable / pmx_train_set_adam / pmx_train_set_grad_scale /
-// pmx_train_step_head / pmx_get_layer / pmx_train_get_state / pmx_train_set_state / pmx_get_pack / pmx_adam_apply.  Semantics:
+// pmx_train.hip -- the training steps of the C ABI: pmx_train_enable / pmx_train_set_adam / pmx_train_set_grad_scale /
+// pmx_train_step_head / pmx_train_step / pmx_get_layer / pmx_train_get_state / pmx_train_set_state / pmx_get_pack / pmx_adam_apply.  Semantics:
 // include/pose_mi355x.h; the stores' layout: pmx_ctx.h (TrainState, BwState::grad); where a weight lies in a pack: pack_index.h.
 //
 // THE ADAM CONTRACT is this project's own restatement of Chainer's AdamRule (eta = 1, weight_decay_rate = 0) as a sequence of float32
@@ -40,7 +40,7 @@ __device__ __forceinline__ float adam_one(float grad, float w, float& m, float& 
     return w - u;
 }
 
-// The whole store in one launch.  Block b serves the segment whose [blk0, next blk0) holds b (82 segments: seven steps of a search), floats
+// The whole store in one launch.  Block b serves the segment whose [blk0, next blk0) holds b (at most 92 segments: seven steps of a search), floats
 // (b - blk0) * ADAM_BLOCK_FLOATS ... of it.  Every segment starts at a multiple of 64 floats and is padded to one, so each lane moves whole
 // 16-byte vectors; the lanes of the last vector past n keep the bits they loaded (a pad float is never used as a parameter, never changed).
 __global__ __launch_bounds__(ADAM_THREADS) void adam_kernel(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v,
@@ -78,40 +78,71 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_kernel(float* __restrict__ 
 }
 
 // ---- packers: one thread per float of the pack, so the pad positions are written (+0.0f) like everything else --------------------------
+// A step makes ONE launch per kind of pack over all updated layers (direct + bias, transposed, Winograd, conv1_1's fused pack), each driven
+// by a table of PackJob that travels with the Adam table.  A job owns the blocks [blk0, next blk0), 256 floats of its pack each, so no block
+// straddles two layers; a block finds its job by the search the Adam kernel uses.  The table is read through indices that are uniform
+// over the block, so the loads are scalar.  Per float of a pack the arithmetic is that of the host packers.
 struct PackGeo { int cout, cin, T, kind, nch, cout_pad; };      // of the pack WRITTEN (nch chunks of 16 packed input channels)
+struct PackJob {
+    const float* src;      // direct / transposed: the layer's master weights (w OIHW | b); Winograd / conv1_1: the direct pack it derives from
+    float* dst;
+    float* bias;           // direct: the padded bias
+    PackGeo p;
+    int t_cout, ks;        // transposed: output channels of the transposed layer; Winograd: the kernel size
+    unsigned total, blk0;  // floats of the pack, first block of the job in the launch
+};
+
+__device__ __forceinline__ PackJob job_of_block(const PackJob* __restrict__ jobs, int njobs)
+{
+    int lo = 0, hi = njobs - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (jobs[mid].blk0 <= blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    return jobs[lo];
+}
 
 // master (w OIHW | b) -> the layer's direct pack and bias, as pack_weights does
-__global__ __launch_bounds__(256) void pack_direct_kernel(const float* __restrict__ w, float* __restrict__ dw, float* __restrict__ db, PackGeo p, unsigned total)
+__global__ __launch_bounds__(256) void pack_direct_kernel(const PackJob* __restrict__ jobs, int njobs)
 {
-    const unsigned idx = blockIdx.x * 256u + threadIdx.x;
-    if (idx >= total) return;
+    const PackJob j = job_of_block(jobs, njobs);
+    const PackGeo p = j.p;
+    const float* __restrict__ w = j.src;
+    const unsigned idx = (blockIdx.x - j.blk0) * 256u + threadIdx.x;
+    if (idx >= j.total) return;
     const int c = idx % PMX_PK_CK, n = (idx / PMX_PK_CK) % p.cout_pad;
     const unsigned pc = idx / PMX_PK_CK / p.cout_pad;
     const int ch = pc % p.nch, tap = pc / p.nch, k = ch * PMX_PK_CK + c;
     const int src = pmx_pk_ref_of_packed(p.kind, k, p.cin);
-    dw[idx] = src >= 0 && n < p.cout ? w[pmx_pk_oihw(n, src, tap, p.cin, p.T)] : 0.0f;
-    if (idx < (unsigned)p.cout_pad) db[idx] = idx < (unsigned)p.cout ? w[(size_t)p.cout * p.cin * p.T + idx] : 0.0f;
+    j.dst[idx] = src >= 0 && n < p.cout ? w[pmx_pk_oihw(n, src, tap, p.cin, p.T)] : 0.0f;
+    if (idx < (unsigned)p.cout_pad) j.bias[idx] = idx < (unsigned)p.cout ? w[(size_t)p.cout * p.cin * p.T + idx] : 0.0f;
 }
 
 // master w -> the direct pack of the layer whose forward is the data gradient: output channel n = the layer's packed input channel, input
 // channel k = the layer's output channel, taps rotated by 180 degrees (conv_bwd_pack.h + pack_weights with the zero-padded g map).  p
 // describes the LAYER (cout, cin, T, kind); nch / cout_pad the transposed pack.
-__global__ __launch_bounds__(256) void pack_transposed_kernel(const float* __restrict__ w, float* __restrict__ dw, PackGeo p, int t_cout, unsigned total)
+__global__ __launch_bounds__(256) void pack_transposed_kernel(const PackJob* __restrict__ jobs, int njobs)
 {
-    const unsigned idx = blockIdx.x * 256u + threadIdx.x;
-    if (idx >= total) return;
+    const PackJob j = job_of_block(jobs, njobs);
+    const PackGeo p = j.p;
+    const float* __restrict__ w = j.src;
+    const unsigned idx = (blockIdx.x - j.blk0) * 256u + threadIdx.x;
+    if (idx >= j.total) return;
     const int c = idx % PMX_PK_CK, n = (idx / PMX_PK_CK) % p.cout_pad;
     const unsigned pc = idx / PMX_PK_CK / p.cout_pad;
     const int ch = pc % p.nch, tap = pc / p.nch, k = ch * PMX_PK_CK + c;
-    const int src = n < t_cout ? pmx_pk_ref_of_packed(p.kind, n, p.cin) : -1;
-    dw[idx] = src >= 0 && k < p.cout ? w[pmx_pk_oihw(k, src, p.T - 1 - tap, p.cin, p.T)] : 0.0f;
+    const int src = n < j.t_cout ? pmx_pk_ref_of_packed(p.kind, n, p.cin) : -1;
+    j.dst[idx] = src >= 0 && k < p.cout ? w[pmx_pk_oihw(k, src, p.T - 1 - tap, p.cin, p.T)] : 0.0f;
 }
 
 // direct pack -> Winograd pack, as pack_wino does: double, the same association, rounded once
-__global__ __launch_bounds__(256) void pack_wino_kernel(const float* __restrict__ wp, float* __restrict__ out, int ks, int nch16, int cout_pad, unsigned total)
+__global__ __launch_bounds__(256) void pack_wino_kernel(const PackJob* __restrict__ jobs, int njobs)
 {
-    const unsigned idx = blockIdx.x * 256u + threadIdx.x;
-    if (idx >= total) return;
+    const PackJob j = job_of_block(jobs, njobs);
+    const float* __restrict__ wp = j.src;
+    const int ks = j.ks, nch16 = j.p.nch, cout_pad = j.p.cout_pad;
+    const unsigned idx = (blockIdx.x - j.blk0) * 256u + threadIdx.x;
+    if (idx >= j.total) return;
     const int nch32 = nch16 * PMX_PK_CK / 32, nb32 = cout_pad / 32;
     const int ci8 = idx % 8, n32 = (idx / 8) % 32, k8 = (idx / 256) % 4, nb = (idx / 1024) % nb32;
     const unsigned pc = idx / 1024 / nb32;
@@ -121,12 +152,12 @@ __global__ __launch_bounds__(256) void pack_wino_kernel(const float* __restrict_
     auto tapw = [&](int ky, int kx) -> double { return wp[pmx_pk_direct(ky * ks + kx, ci, n, nch16, cout_pad)]; };
     double val;
     if (plane < 64) {
-        const int sub = plane / 16, i = (plane % 16) / 4, j = plane % 4;
+        const int sub = plane / 16, i = (plane % 16) / 4, jj = plane % 4;
         double gg[3];
         for (int kx = 0; kx < 3; ++kx)
             gg[kx] = (Gm[i][0] * tapw(3 * (sub >> 1) + 0, 3 * (sub & 1) + kx) + Gm[i][1] * tapw(3 * (sub >> 1) + 1, 3 * (sub & 1) + kx)) +
                      Gm[i][2] * tapw(3 * (sub >> 1) + 2, 3 * (sub & 1) + kx);
-        val = (gg[0] * Gm[j][0] + gg[1] * Gm[j][1]) + gg[2] * Gm[j][2];
+        val = (gg[0] * Gm[jj][0] + gg[1] * Gm[jj][1]) + gg[2] * Gm[jj][2];
     } else if (plane < 72) {
         const int sub = (plane - 64) / 4, f = (plane - 64) % 4;
         val = (Gm[f][0] * tapw(6, 3 * sub + 0) + Gm[f][1] * tapw(6, 3 * sub + 1)) + Gm[f][2] * tapw(6, 3 * sub + 2);
@@ -134,7 +165,17 @@ __global__ __launch_bounds__(256) void pack_wino_kernel(const float* __restrict_
         const int sub = (plane - 72) / 4, f = (plane - 72) % 4;
         val = (Gm[f][0] * tapw(3 * sub + 0, 6) + Gm[f][1] * tapw(3 * sub + 1, 6)) + Gm[f][2] * tapw(3 * sub + 2, 6);
     } else val = tapw(6, 6);
-    out[idx] = (float)val;
+    j.dst[idx] = (float)val;
+}
+
+// conv1_1's direct pack -> its fused-kernel pack, as pack_conv1 does (the 28th k of every channel: +0.0f)
+__global__ __launch_bounds__(256) void pack_conv1_kernel(const PackJob* __restrict__ jobs, int njobs)
+{
+    const PackJob j = job_of_block(jobs, njobs);
+    const unsigned idx = (blockIdx.x - j.blk0) * 256u + threadIdx.x;
+    if (idx >= j.total) return;
+    const long long src = pmx_pk_conv1_src((int)idx, j.p.cout_pad);
+    j.dst[idx] = src >= 0 ? j.src[src] : 0.0f;
 }
 
 // a layer's direct pack and bias -> (w OIHW, reference input order | b)
@@ -168,44 +209,6 @@ int launch_unpack(const pmx_ctx* c, const PackedLayer& L, float* dst, hipStream_
     return PMX_OK;
 }
 
-int launch_wino(const PackedLayer& L, hipStream_t st)
-{
-    const size_t total = wino_floats(L);
-    PMX_CHECK(L.d_ww.capacity() == total && L.cin_pad % 32 == 0 && L.cout_pad % 32 == 0, PMX_ERR_STATE,
-              "training step: a Winograd pack of %zu floats where %zu are expected", L.d_ww.capacity(), total);
-    pack_wino_kernel<<<blocks256(total), 256, 0, st>>>(L.d_w, L.d_ww, L.ks, L.nch, L.cout_pad, (unsigned)total);
-    TR_LAUNCHED("pack_wino");
-    return PMX_OK;
-}
-
-// every pack of head layer `idx` that exists, from the master weights at `w`
-int repack_layer(pmx_ctx* c, int idx, const float* w, hipStream_t st)
-{
-    PackedLayer& L = c->layers[idx];
-    const PackGeo g = geo_of(c, L);
-    size_t total = direct_floats(L);
-    PMX_CHECK(L.d_w.capacity() == total && L.d_b.capacity() == (size_t)L.cout_pad, PMX_ERR_STATE, "training step: layer '%s': a pack of %zu floats where %zu are expected",
-              c->table[idx].name.c_str(), L.d_w.capacity(), total);
-    pack_direct_kernel<<<blocks256(total), 256, 0, st>>>(w, L.d_w, L.d_b, g, (unsigned)total);
-    TR_LAUNCHED("pack_direct");
-    int rc;
-    if (L.d_ww && (rc = launch_wino(L, st))) return rc;
-    L.stale16 = (bool)L.d_w16; L.stale3 = (bool)L.d_w3;
-    if ((size_t)idx >= c->bw.tl.size() || !c->bw.tl[idx].set) return PMX_OK;
-    PackedLayer& P = c->bw.tl[idx];
-    total = direct_floats(P);
-    const int t_cout = pmx_pk_t_cout(g.kind, L.cin);
-    PMX_CHECK(P.d_w.capacity() == total && P.cout == t_cout && P.cin_pad == pmx_pk_t_cin_pad(L.cout), PMX_ERR_STATE,
-              "training step: layer '%s': a transposed pack of another shape", c->table[idx].name.c_str());
-    PackGeo gt = g;
-    gt.nch = P.nch; gt.cout_pad = P.cout_pad;
-    pack_transposed_kernel<<<blocks256(total), 256, 0, st>>>(w, P.d_w, gt, t_cout, (unsigned)total);
-    TR_LAUNCHED("pack_transposed");
-    if (P.d_ww && (rc = launch_wino(P, st))) return rc;
-    P.stale16 = (bool)P.d_w16; P.stale3 = (bool)P.d_w3;
-    return PMX_OK;
-}
-
 // the stage of a head layer (0: conv4_3_CPM / conv4_4_CPM), -1 for a layer the head backward does not cover
 int head_stage(const pmx_ctx* c, int idx)
 {
@@ -214,10 +217,80 @@ int head_stage(const pmx_ctx* c, int idx)
     return k < PMX_BW_S1 ? 0 : k < PMX_BW_M2 ? 1 : 2 + (k - PMX_BW_M2) / 7;
 }
 
+// the position 0 .. 9 of a trunk layer (conv1_1 .. conv4_2) while the trunk is retained (mode 2: it has a gradient segment), else -1
+int trunk_pos(const pmx_ctx* c, int idx)
+{
+    if (c->bw.on != 2) return -1;
+    for (int t = 0; t < PMX_TRUNK_LAYERS; ++t)
+        if (c->bw.t_layer[t] == idx) return t;
+    return -1;
+}
+
+// a layer with a segment in the stores: the 82 head layers, in mode 2 the ten trunk layers as well
+bool has_segment(const pmx_ctx* c, int idx) { return head_stage(c, idx) >= 0 || trunk_pos(c, idx) >= 0; }
+
+// The tables of one step in the pinned block (and, at the same offsets, in its device copy): the Adam segments, then the jobs of the four
+// packer launches.  N = layers of the context; a layer gives at most one direct, one transposed and two Winograd jobs.
+enum { JOB_DIRECT = 0, JOB_TRANSPOSED = 1, JOB_WINO = 2, JOB_CONV1 = 3, JOB_KINDS = 4 };
+size_t jobs_at(size_t N, int kind) { return N * sizeof(AdamSeg) + (kind == JOB_DIRECT ? 0 : kind == JOB_TRANSPOSED ? N : kind == JOB_WINO ? 2 * N : 4 * N) * sizeof(PackJob); }
+size_t table_bytes(size_t N) { return jobs_at(N, JOB_CONV1) + sizeof(PackJob); }
+
+struct JobList { PackJob* job; int n = 0; unsigned blocks = 0; };
+void add_job(JobList& l, PackJob j, size_t total)
+{
+    j.total = (unsigned)total; j.blk0 = l.blocks;
+    l.job[l.n++] = j;
+    l.blocks += blocks256(total);
+}
+
+int wino_job(JobList& l, const PackedLayer& L)
+{
+    const size_t total = wino_floats(L);
+    PMX_CHECK(L.d_ww.capacity() == total && L.cin_pad % 32 == 0 && L.cout_pad % 32 == 0, PMX_ERR_STATE,
+              "training step: a Winograd pack of %zu floats where %zu are expected", L.d_ww.capacity(), total);
+    PackJob j{};
+    j.src = L.d_w; j.dst = L.d_ww; j.ks = L.ks; j.p.nch = L.nch; j.p.cout_pad = L.cout_pad;
+    add_job(l, j, total);
+    return PMX_OK;
+}
+
+// the jobs of every pack of layer `idx` that exists, from the master weights at `w`; nothing is enqueued and no flag is set
+int repack_jobs(pmx_ctx* c, int idx, const float* w, JobList* jl)
+{
+    const PackedLayer& L = c->layers[idx];
+    const PackGeo g = geo_of(c, L);
+    size_t total = direct_floats(L);
+    PMX_CHECK(L.d_w.capacity() == total && L.d_b.capacity() == (size_t)L.cout_pad, PMX_ERR_STATE, "training step: layer '%s': a pack of %zu floats where %zu are expected",
+              c->table[idx].name.c_str(), L.d_w.capacity(), total);
+    PackJob j{};
+    j.src = w; j.dst = L.d_w; j.bias = L.d_b; j.p = g;
+    add_job(jl[JOB_DIRECT], j, total);
+    int rc;
+    if (L.d_ww && trunk_pos(c, idx) == 0) {      // conv1_1's Winograd slot holds its fused-kernel pack
+        PMX_CHECK(L.d_ww.capacity() == (size_t)PMX_PK_CONV1_FLOATS && L.nch == 1 && L.cout_pad == 64, PMX_ERR_STATE,
+                  "training step: conv1_1's fused-kernel pack has %zu floats where %d are expected", L.d_ww.capacity(), PMX_PK_CONV1_FLOATS);
+        PackJob jc{};
+        jc.src = L.d_w; jc.dst = L.d_ww; jc.p = g;
+        add_job(jl[JOB_CONV1], jc, PMX_PK_CONV1_FLOATS);
+    } else if (L.d_ww && (rc = wino_job(jl[JOB_WINO], L))) return rc;
+    if ((size_t)idx >= c->bw.tl.size() || !c->bw.tl[idx].set) return PMX_OK;
+    const PackedLayer& P = c->bw.tl[idx];
+    total = direct_floats(P);
+    const int t_cout = pmx_pk_t_cout(g.kind, L.cin);
+    PMX_CHECK(P.d_w.capacity() == total && P.cout == t_cout && P.cin_pad == pmx_pk_t_cin_pad(L.cout), PMX_ERR_STATE,
+              "training step: layer '%s': a transposed pack of another shape", c->table[idx].name.c_str());
+    PackJob jt{};
+    jt.src = w; jt.dst = P.d_w; jt.p = g; jt.p.nch = P.nch; jt.p.cout_pad = P.cout_pad; jt.t_cout = t_cout;
+    add_job(jl[JOB_TRANSPOSED], jt, total);
+    if (P.d_ww && (rc = wino_job(jl[JOB_WINO], P))) return rc;
+    return PMX_OK;
+}
+
+// the packs a step rewrites behind the host's back, and the lazy host builders that must wait for it: every layer with a segment
 void mark_busy(pmx_ctx* c, bool on)
 {
     for (size_t i = 0; i < c->layers.size(); ++i) {
-        if (head_stage(c, (int)i) < 0) continue;
+        if (!has_segment(c, (int)i)) continue;
         c->layers[i].busy = on; c->layers[i].busy_stream = c->stream;
         if (i < c->bw.tl.size()) { c->bw.tl[i].busy = on; c->bw.tl[i].busy_stream = c->stream; }
     }
@@ -232,11 +305,13 @@ int tr_check(pmx_ctx* c, const char* who, bool need_on)
     return PMX_OK;
 }
 
-int head_layer(pmx_ctx* c, const char* who, const char* name, int* idx)
+// a layer with Adam state: one of the 82 head layers, in mode 2 one of the ten trunk layers as well
+int state_layer(pmx_ctx* c, const char* who, const char* name, int* idx)
 {
     PMX_CHECK(name, PMX_ERR_INVALID, "%s: null layer name", who);
     auto it = c->index.find(name);
-    PMX_CHECK(it != c->index.end() && head_stage(c, it->second) >= 0, PMX_ERR_INVALID, "%s: '%s' is not one of the 82 layers after conv4_2", who, name);
+    PMX_CHECK(it != c->index.end() && has_segment(c, it->second), PMX_ERR_INVALID, "%s: '%s' is not one of the 82 layers after conv4_2%s", who, name,
+              c->bw.on == 2 ? " or the ten trunk layers" : " (the trunk layers have state with pmx_backward_enable(ctx, 2) only)");
     *idx = it->second;
     return PMX_OK;
 }
@@ -268,7 +343,7 @@ void pmx_train_free(pmx_ctx* c)
 
 int pmx_train_on_set_layer(pmx_ctx* c, int layer, const float* w, const float* bias)
 {
-    if (head_stage(c, layer) < 0) return PMX_OK;
+    if (!has_segment(c, layer)) return PMX_OK;      // (a trunk layer in mode 1: no segment, no step ever touches it)
     const LayerDesc& d = c->table[layer];
     const size_t nw = (size_t)d.cout * d.cin * d.ks * d.ks;
     float* dst = c->tr.w + c->bw.grad_off[layer];
@@ -296,7 +371,7 @@ extern "C" int pmx_train_enable(pmx_ctx* c, int on)
     if ((rc = pmx_check_weights(c))) return rc;
     const size_t total = c->bw.grad.capacity();
     const bool ok = tr.w.alloc(total) == PMX_OK && tr.m.alloc(total) == PMX_OK && tr.v.alloc(total) == PMX_OK &&
-                    tr.seg_dev.alloc(c->table.size() * sizeof(AdamSeg)) == PMX_OK && tr.seg_host.alloc(c->table.size() * sizeof(AdamSeg)) == PMX_OK;
+                    tr.seg_dev.alloc(table_bytes(c->table.size())) == PMX_OK && tr.seg_host.alloc(table_bytes(c->table.size())) == PMX_OK;
     if (!ok) {
         (void)hipGetLastError();
         tr.w.reset(); tr.m.reset(); tr.v.reset(); tr.seg_dev.reset(); tr.seg_host.reset();
@@ -309,7 +384,7 @@ extern "C" int pmx_train_enable(pmx_ctx* c, int on)
     PMX_HIP(hipMemsetAsync(tr.m, 0, total * sizeof(float), st));
     PMX_HIP(hipMemsetAsync(tr.v, 0, total * sizeof(float), st));
     for (size_t i = 0; i < c->layers.size(); ++i)
-        if (head_stage(c, (int)i) >= 0 && (rc = launch_unpack(c, c->layers[i], tr.w + c->bw.grad_off[i], st))) {
+        if (has_segment(c, (int)i) && (rc = launch_unpack(c, c->layers[i], tr.w + c->bw.grad_off[i], st))) {
             (void)hipStreamSynchronize(st);
             tr.w.reset(); tr.m.reset(); tr.v.reset(); tr.seg_dev.reset(); tr.seg_host.reset();
             return rc;
@@ -336,56 +411,92 @@ extern "C" int pmx_train_set_adam(pmx_ctx* c, double alpha, double beta1, double
 extern "C" int pmx_train_set_grad_scale(pmx_ctx* c, const char* name, double scale)
 {
     int rc, idx;
-    if ((rc = tr_check(c, "pmx_train_set_grad_scale", true)) || (rc = head_layer(c, "pmx_train_set_grad_scale", name, &idx))) return rc;
+    if ((rc = tr_check(c, "pmx_train_set_grad_scale", true)) || (rc = state_layer(c, "pmx_train_set_grad_scale", name, &idx))) return rc;
     PMX_CHECK(isfinite(scale), PMX_ERR_INVALID, "pmx_train_set_grad_scale: scale %g", scale);
     c->tr.scale[idx] = (float)scale;
     return PMX_OK;
 }
 
-extern "C" int pmx_train_step_head(pmx_ctx* c)
+// Both steps: `full` adds the ten trunk layers (mode 2, after pmx_backward_trunk).  Everything that can refuse does so before a launch.
+static int train_step(pmx_ctx* c, const char* who, bool full)
 {
     int rc;
-    if ((rc = tr_check(c, "pmx_train_step_head", true))) return rc;
+    if ((rc = tr_check(c, who, true))) return rc;
     BwState& bw = c->bw;
     TrainState& tr = c->tr;
-    PMX_CHECK(bw.on && bw.valid && bw.done, PMX_ERR_STATE, "pmx_train_step_head: pmx_backward_head has not run for a retained forward");
-    PMX_CHECK(!bw.stepped, PMX_ERR_STATE, "pmx_train_step_head: a step has consumed these gradients (run a new retained forward and pmx_backward_head)");
+    PMX_CHECK(!full || bw.on == 2, PMX_ERR_STATE, "%s: the trunk is not retained (pmx_backward_enable(ctx, 2) before pmx_train_enable)", who);
+    PMX_CHECK(bw.on && bw.valid && bw.done, PMX_ERR_STATE, "%s: pmx_backward_head has not run for a retained forward", who);
+    PMX_CHECK(!full || bw.trunk_done, PMX_ERR_STATE, "%s: pmx_backward_trunk has not run for the retained forward", who);
+    PMX_CHECK(!bw.stepped, PMX_ERR_STATE, "%s: a step has consumed these gradients (run a new retained forward and the backward)", who);
     PMX_DEV(c);
     hipStream_t st = c->stream;
     if (tr.seg_pending) { PMX_HIP(hipEventSynchronize(tr.seg_copied)); tr.seg_pending = false; }      // the pinned table is free again
-    AdamSeg* seg = reinterpret_cast<AdamSeg*>(tr.seg_host.get());
+    const size_t N = c->table.size();
+    char* const host = tr.seg_host.get();
+    const char* const dev = tr.seg_dev.get();
+    AdamSeg* seg = reinterpret_cast<AdamSeg*>(host);
+    JobList jl[JOB_KINDS];
+    for (int k = 0; k < JOB_KINDS; ++k) jl[k].job = reinterpret_cast<PackJob*>(host + jobs_at(N, k));
+    auto updated = [&](int i) {      // (a stage that "stop_stage" cut off received no gradient; the trunk always does)
+        const int stage = head_stage(c, i);
+        return stage >= 0 ? stage <= bw.stages : full && trunk_pos(c, i) >= 0;
+    };
+    for (size_t i = 0; i < N; ++i)
+        if (updated((int)i) && (rc = repack_jobs(c, (int)i, tr.w + bw.grad_off[i], jl))) return rc;
     int nseg = 0;
     unsigned blocks = 0;
     double bytes = 0;
-    for (size_t i = 0; i < c->table.size(); ++i) {
-        const int stage = head_stage(c, (int)i);
-        if (stage < 0 || stage > bw.stages) continue;      // (a stage that "stop_stage" cut off received no gradient)
+    for (size_t i = 0; i < N; ++i) {
+        if (!updated((int)i)) continue;
         const LayerDesc& d = c->table[i];
         const unsigned n = (unsigned)((size_t)d.cout * d.cin * d.ks * d.ks + d.cout);
         tr.t[i] += 1;
         seg[nseg++] = AdamSeg{(unsigned long long)bw.grad_off[i], n, blocks, tr.scale[i], alpha_t_of(tr, tr.t[i])};
         blocks += (n + ADAM_BLOCK_FLOATS - 1) / ADAM_BLOCK_FLOATS;
         bytes += 28.0 * n;
+        PackedLayer& L = c->layers[i];
+        L.stale16 = (bool)L.d_w16; L.stale3 = (bool)L.d_w3;
+        if (i < bw.tl.size() && bw.tl[i].set) { PackedLayer& P = bw.tl[i]; P.stale16 = (bool)P.d_w16; P.stale3 = (bool)P.d_w3; }
     }
     bw.stepped = true;
     mark_busy(c, true);
-    PMX_HIP(hipMemcpyAsync(tr.seg_dev, seg, (size_t)nseg * sizeof(AdamSeg), hipMemcpyHostToDevice, st));
+    PMX_HIP(hipMemcpyAsync(tr.seg_dev, host, table_bytes(N), hipMemcpyHostToDevice, st));
     PMX_HIP(hipEventRecord(tr.seg_copied, st));
     tr.seg_pending = true;
     if ((rc = pmx_prof_begin(c, "train_step|adam", bytes))) return rc;
-    rc = launch_adam(tr.w, tr.m, tr.v, bw.grad, reinterpret_cast<const AdamSeg*>(tr.seg_dev.get()), nseg, blocks, (float)(1.0 - tr.beta1),
+    rc = launch_adam(tr.w, tr.m, tr.v, bw.grad, reinterpret_cast<const AdamSeg*>(dev), nseg, blocks, (float)(1.0 - tr.beta1),
                      (float)(1.0 - tr.beta2), (float)tr.eps, st);
     if (int r = pmx_prof_end(c)) return r;
     if (rc) return rc;
+    // the packers, in the order of their inputs: the direct and transposed packs read the master weights, the Winograd and conv1_1 packs the
+    // direct packs just written
     if ((rc = pmx_prof_begin(c, "train_step|pack", 0))) return rc;
-    for (size_t i = 0; i < c->table.size() && !rc; ++i) {
-        const int stage = head_stage(c, (int)i);
-        if (stage < 0 || stage > bw.stages) continue;
-        rc = repack_layer(c, (int)i, tr.w + bw.grad_off[i], st);
-    }
+    rc = [&]() -> int {
+        auto d_jobs = [&](int k) { return reinterpret_cast<const PackJob*>(dev + jobs_at(N, k)); };
+        if (jl[JOB_DIRECT].n) {
+            pack_direct_kernel<<<jl[JOB_DIRECT].blocks, 256, 0, st>>>(d_jobs(JOB_DIRECT), jl[JOB_DIRECT].n);
+            TR_LAUNCHED("pack_direct");
+        }
+        if (jl[JOB_TRANSPOSED].n) {
+            pack_transposed_kernel<<<jl[JOB_TRANSPOSED].blocks, 256, 0, st>>>(d_jobs(JOB_TRANSPOSED), jl[JOB_TRANSPOSED].n);
+            TR_LAUNCHED("pack_transposed");
+        }
+        if (jl[JOB_WINO].n) {
+            pack_wino_kernel<<<jl[JOB_WINO].blocks, 256, 0, st>>>(d_jobs(JOB_WINO), jl[JOB_WINO].n);
+            TR_LAUNCHED("pack_wino");
+        }
+        if (jl[JOB_CONV1].n) {
+            pack_conv1_kernel<<<jl[JOB_CONV1].blocks, 256, 0, st>>>(d_jobs(JOB_CONV1), jl[JOB_CONV1].n);
+            TR_LAUNCHED("pack_conv1");
+        }
+        return PMX_OK;
+    }();
     if (int r = pmx_prof_end(c)) return r;
     return rc;
 }
+
+extern "C" int pmx_train_step_head(pmx_ctx* c) { return train_step(c, "pmx_train_step_head", false); }
+extern "C" int pmx_train_step(pmx_ctx* c) { return train_step(c, "pmx_train_step", true); }
 
 extern "C" int pmx_get_layer(pmx_ctx* c, const char* name, float* w_oihw, float* bias)
 {
@@ -415,7 +526,7 @@ extern "C" int pmx_get_layer(pmx_ctx* c, const char* name, float* w_oihw, float*
 extern "C" int pmx_train_get_state(pmx_ctx* c, const char* name, float* m_w, float* v_w, float* m_b, float* v_b, int* t)
 {
     int rc, idx;
-    if ((rc = tr_check(c, "pmx_train_get_state", true)) || (rc = head_layer(c, "pmx_train_get_state", name, &idx))) return rc;
+    if ((rc = tr_check(c, "pmx_train_get_state", true)) || (rc = state_layer(c, "pmx_train_get_state", name, &idx))) return rc;
     PMX_DEV(c);
     const LayerDesc& d = c->table[idx];
     const size_t nw = (size_t)d.cout * d.cin * d.ks * d.ks, off = c->bw.grad_off[idx];
@@ -431,7 +542,7 @@ extern "C" int pmx_train_get_state(pmx_ctx* c, const char* name, float* m_w, flo
 extern "C" int pmx_train_set_state(pmx_ctx* c, const char* name, const float* m_w, const float* v_w, const float* m_b, const float* v_b, int t)
 {
     int rc, idx;
-    if ((rc = tr_check(c, "pmx_train_set_state", true)) || (rc = head_layer(c, "pmx_train_set_state", name, &idx))) return rc;
+    if ((rc = tr_check(c, "pmx_train_set_state", true)) || (rc = state_layer(c, "pmx_train_set_state", name, &idx))) return rc;
     PMX_CHECK(m_w && v_w && m_b && v_b, PMX_ERR_INVALID, "pmx_train_set_state: null moments");
     PMX_CHECK(t >= 0, PMX_ERR_INVALID, "pmx_train_set_state: t = %d", t);
     PMX_DEV(c);

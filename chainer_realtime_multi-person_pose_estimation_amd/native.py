@@ -347,6 +347,7 @@ def load():
         'pmx_train_set_adam': (ci, [vp, cd, cd, cd, cd]),
         'pmx_train_set_grad_scale': (ci, [vp, C.c_char_p, cd]),
         'pmx_train_step_head': (ci, [vp]),
+        'pmx_train_step': (ci, [vp]),
         'pmx_get_layer': (ci, [vp, C.c_char_p, vp, vp]),
         'pmx_train_get_state': (ci, [vp, C.c_char_p, vp, vp, vp, vp, ip]),
         'pmx_train_set_state': (ci, [vp, C.c_char_p, vp, vp, vp, vp, ci]),
@@ -1006,7 +1007,7 @@ class Engine(object):
         self._check(self.lib.pmx_get_retained(self._ctx, name.encode(), int(which), _ptr(out)))
         return out
 
-    # ---- head training step (include/pose_mi355x.h: pmx_train_*) ------------------------------------------------------
+    # ---- training steps (include/pose_mi355x.h: pmx_train_*) ----- ------------------------------------------------------
     PACKS = {'w': 0, 'b': 1, 'wino': 2, 't_w': 3, 't_wino': 4}
 
     def layer_shape(self, name):
@@ -1014,8 +1015,8 @@ class Engine(object):
         return self._layers[name][0].shape
 
     def train_enable(self, on=True):
-        """on: allocates the master weights and Adam's two moments of the 82 layers after conv4_2 (backward_enable first) and fills the
-        weights from the device packs; off: frees them."""
+        """on: allocates the master weights and Adam's two moments of the 82 layers after conv4_2 -- after backward_enable(2) of all 92 --
+        and fills the weights from the device packs (backward_enable first); off: frees them."""
         self._check(self.lib.pmx_train_enable(self._ctx, int(bool(on))))
 
     def train_set_adam(self, alpha=1e-4, beta1=0.9, beta2=0.999, eps=1e-8):
@@ -1027,6 +1028,11 @@ class Engine(object):
     def train_step_head(self):
         """Adam on the gradients of the last backward_head + every existing weight pack rewritten on the device (no synchronisation)."""
         self._check(self.lib.pmx_train_step_head(self._ctx))
+        self._trained = True
+
+    def train_step(self):
+        """train_step_head over all 92 layers: after backward_head and backward_trunk with backward_enable(2) (no synchronisation)."""
+        self._check(self.lib.pmx_train_step(self._ctx))
         self._trained = True
 
     def get_layer(self, name):
@@ -1041,7 +1047,7 @@ class Engine(object):
         return {name: self.get_layer(name) for name in self._layers}
 
     def train_get_state(self, name):
-        """(m_W, v_W, m_b, v_b, t) of one head layer (synchronises)."""
+        """(m_W, v_W, m_b, v_b, t) of one head layer, with backward_enable(2) also of a trunk layer (synchronises)."""
         W, b = self._layers.get(name, (np.empty((1, 1, 1, 1), np.float32), np.empty(1, np.float32)))
         out = [np.empty(W.shape, np.float32), np.empty(W.shape, np.float32), np.empty(b.shape, np.float32), np.empty(b.shape, np.float32)]
         t = C.c_int(0)

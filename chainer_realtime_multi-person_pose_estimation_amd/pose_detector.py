@@ -68,6 +68,8 @@ class PoseDetector(object):
         self._precision = precision
         self.engine = None
         self._train_on = False                     # training mode (train_step): the optimiser's stores live in the engine
+        self._trunk = False                        # set_trainable: train_step updates conv1_1 .. conv4_2 as well
+        self._mode2 = False                        # training retains the trunk (engine backward mode 2); stays once the trunk was trainable
         self._adam = dict(alpha=1e-4, beta1=0.9, beta2=0.999, eps=1e-8)
         self._grad_scales = dict(self.REFERENCE_GRAD_SCALES)
         self._make_engine(max_batch, mh, mw)
@@ -654,12 +656,12 @@ class PoseDetector(object):
         """`head_gradients` continued through conv4_2 .. conv1_1: the gradients of all 92 layers, what the reference's loss.backward() gives
         once it has un-frozen the trunk (train_coco_pose_estimation.py:96-101, from iteration 2000 on).  Arguments and result as
         head_gradients, 'grads' with 92 entries.  The forward retains the trunk (engine mode 2), so its stem runs unfused.  More images than
-        the engine's batch raise ValueError; not available while the head is being trained (stop_training first)."""
+        the engine's batch raise ValueError; not available while training is on (stop_training first)."""
         imgs, poses, masks = self._check_validation_args(imgs, poses_per_image, ignore_masks)
         if self.model is not None:
             raise RuntimeError('network_gradients runs the built-in network: not available with a model= callable')
         if self._train_on:
-            raise RuntimeError('network_gradients needs the trunk retained, training retains the head alone: call stop_training() first')
+            raise RuntimeError('network_gradients switches retention on and off itself, training keeps it on: call stop_training() first')
         if self.engine.weights_missing():
             raise RuntimeError('PoseDetector has no weights: pass weights_file=, weights= or model=')
         h, w = imgs[0].shape[:2]
@@ -685,8 +687,27 @@ class PoseDetector(object):
                 'paf_stages': [float(v) for v in paf], 'heat_stages': [float(v) for v in heat],
                 'paf_grads': [g[0] for g in grads], 'heat_grads': [g[1] for g in grads], 'grads': layer_grads, 'trunk_grad': trunk}
 
-    # ---- training of the head (reference train_coco_pose_estimation.py:204-235, its first 2000 iterations) -------------------------------
+    # ---- training (reference train_coco_pose_estimation.py:204-235; head only as in its first 2000 iterations, or all 92 layers) -----------
     REFERENCE_GRAD_SCALES = {'conv4_3_CPM': 0.25, 'conv4_4_CPM': 0.25}      # GradientScaling (train_coco_pose_estimation.py:222-223)
+    # ... and of the ten trunk layers (:213-217); in force once the trunk is trainable
+    REFERENCE_TRUNK_GRAD_SCALES = dict.fromkeys(native.Engine.TRUNK_LAYERS, 0.25)
+
+    def set_trainable(self, trunk=False):
+        """Which layers train_step updates: the 82 layers after conv4_2 (default, the reference's first 2000 iterations) or, trunk=True, all 92
+        (the reference from iteration 2000 on, enable_update on conv1_1 .. conv4_2).  The first trunk=True moves training to the engine's
+        backward mode 2 (the forward retains the trunk, so its stem runs unfused); weights and Adam's state of the head carry over, the trunk
+        joins with m = v = 0 and t = 0 and the reference's gradient scale 1/4 (REFERENCE_TRUNK_GRAD_SCALES).  trunk=False afterwards goes back
+        to head-only steps and keeps the trunk's state in the stores, as Chainer's disable_update does."""
+        trunk = bool(trunk)
+        if trunk and not self._mode2:
+            opt = self.optimizer_state() if self._train_on else None
+            self.stop_training()
+            self._mode2 = True
+            scales = dict(self.REFERENCE_TRUNK_GRAD_SCALES, **self._grad_scales)
+            if opt is not None:
+                self.load_optimizer_state(opt)          # (a head-only state: it names the head's scales alone)
+            self.set_optimizer(grad_scales=scales, **self._adam)
+        self._trunk = trunk
 
     def _start_training(self):
         """Training mode of the current engine: loss gradients, retention and the optimiser's stores on (they stay on until stop_training)."""
@@ -701,7 +722,7 @@ class PoseDetector(object):
         eng = self.engine
         eng.loss_grad_enable(True)
         try:
-            eng.backward_enable(True)
+            eng.backward_enable(2 if self._mode2 else True)
             eng.train_enable(True)
             eng.train_set_adam(**self._adam)
             for name, sc in self._grad_scales.items():
@@ -722,19 +743,22 @@ class PoseDetector(object):
 
     def set_optimizer(self, alpha=1e-4, beta1=0.9, beta2=0.999, eps=1e-8, grad_scales=None):
         """Adam's hyper-parameters from the next train_step on (defaults: Chainer's, which the reference uses; it lowers alpha at 100 000 and
-        200 000 iterations) and the per-layer gradient scales {head layer: scale} (default: the reference's 1/4 for conv4_3_CPM and
-        conv4_4_CPM; layers not named: 1)."""
+        200 000 iterations) and the per-layer gradient scales {layer: scale} (default: the reference's 1/4 for conv4_3_CPM and
+        conv4_4_CPM and, once set_trainable(trunk=True) was called, for the ten trunk layers; layers not named: 1).  Trunk layers may be
+        named only then."""
         self._adam = dict(alpha=float(alpha), beta1=float(beta1), beta2=float(beta2), eps=float(eps))
         old = self._grad_scales
-        self._grad_scales = dict(self.REFERENCE_GRAD_SCALES if grad_scales is None else grad_scales)
+        default = dict(self.REFERENCE_GRAD_SCALES, **(self.REFERENCE_TRUNK_GRAD_SCALES if self._mode2 else {}))
+        self._grad_scales = dict(default if grad_scales is None else grad_scales)
         if self._train_on:
             self.engine.train_set_adam(**self._adam)
             for name in set(old) | set(self._grad_scales):
                 self.engine.train_set_grad_scale(name, self._grad_scales.get(name, 1.0))
 
     def train_step(self, imgs, poses_per_image, ignore_masks=None):
-        """One iteration of the reference's training loop while conv1_1 .. conv4_2 are frozen: the forward with compute_loss, the backward of
-        the 82 layers after conv4_2 and Adam with the gradient scales, all on the device -- no gradient and no weight crosses to the host.
+        """One iteration of the reference's training loop: the forward with compute_loss, the backward and Adam with the gradient scales,
+        all on the device -- no gradient and no weight crosses to the host.  By default conv1_1 .. conv4_2 are frozen and the 82 layers after
+        conv4_2 are updated; after set_trainable(trunk=True) the backward continues through the trunk and all 92 layers are.
         Arguments as head_gradients (uniform uint8 images at the network-input size; prepare_samples(mode='train') makes them).  ->
         {'main/loss', 'main/paf', 'main/heat'} (floats) and 'paf_stages', 'heat_stages': validation_loss's numbers of this batch BEFORE the
         update, under the reference's training names.  More images than the engine's batch raise ValueError."""
@@ -753,7 +777,11 @@ class PoseDetector(object):
         try:
             eng.forward_u8(np.stack(imgs))
             eng.backward_head()
-            eng.train_step_head()
+            if self._trunk:
+                eng.backward_trunk()
+                eng.train_step()
+            else:
+                eng.train_step_head()
             paf, heat, _ = eng.loss_get()          # (the one synchronisation: the whole iteration is enqueued by now)
         finally:
             eng.loss_enable(False)
@@ -768,19 +796,24 @@ class PoseDetector(object):
 
     def optimizer_state(self):
         """Adam's state as a flat dictionary of NumPy arrays (np.savez takes it): 'adam' = (alpha, beta1, beta2, eps), and per head layer
-        '<name>/m_W', '/v_W', '/m_b', '/v_b', '/t', '/scale'.  With the weights (get_weights) it is what the reference's --resume restores."""
+        '<name>/m_W', '/v_W', '/m_b', '/v_b', '/t', '/scale' -- once the trunk was made trainable per layer of all 92.  With the weights
+        (get_weights) it is what the reference's --resume restores."""
         self._start_training()
         out = {'adam': np.array([self._adam[k] for k in ('alpha', 'beta1', 'beta2', 'eps')], np.float64)}
-        for name in self.engine.head_layers():
+        for name in (list(self.engine.TRUNK_LAYERS) if self._mode2 else []) + self.engine.head_layers():
             m_w, v_w, m_b, v_b, t = self.engine.train_get_state(name)
             out.update({name + '/m_W': m_w, name + '/v_W': v_w, name + '/m_b': m_b, name + '/v_b': v_b, name + '/t': np.array(t, np.int64),
                         name + '/scale': np.array(self._grad_scales.get(name, 1.0), np.float64)})
         return out
 
     def load_optimizer_state(self, state):
-        """Install what optimizer_state() returned (or np.load of its np.savez) in this detector: training continues where it stopped."""
+        """Install what optimizer_state() returned (or np.load of its np.savez) in this detector: training continues where it stopped.  A
+        state that covers the trunk layers makes the trunk trainable in a detector that trained the head alone."""
         a = np.asarray(state['adam'], np.float64)
         names = sorted(k[:-len('/t')] for k in state.keys() if k.endswith('/t'))
+        if not self._mode2 and any(n in self.engine.TRUNK_LAYERS for n in names):
+            self.stop_training()
+            self._mode2 = self._trunk = True
         self.set_optimizer(*[float(x) for x in a], grad_scales={n: float(state[n + '/scale']) for n in names if float(state[n + '/scale']) != 1.0})
         self._start_training()
         for n in names:

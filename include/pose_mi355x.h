@@ -669,7 +669,7 @@ int pmx_get_retained(pmx_ctx* ctx, const char* name, int which, float* out_nchw)
  *   dx   the dispatcher on g with the transposed, 180-degree-rotated pack, relu = 0, pool = 0 (conv1_1: none, and no pack is built)
  * The ten dw | db segments follow the head's in the gradient store, each padded to 64 floats; every head offset is as in mode 1, so
  * pmx_train_enable / pmx_train_step_head work in mode 2 as in mode 1 and update the 82 head layers only (their stores are as large as
- * the gradient store, so 3 x 23.5 MB larger).  A trunk training step does not exist yet.
+ * the gradient store, so 3 x 23.5 MB larger); pmx_train_step updates all 92 layers (the training steps, below).
  * PMX_ERR_STATE, before anything is enqueued: mode is not 2, no retained forward, pmx_backward_head has not run for it, option "precision"
  * != 0, a facenet / handnet context.
  * With mode 2 on, pmx_get_layer_grad also takes the ten trunk names after pmx_backward_trunk (before: PMX_ERR_STATE; mode 1:
@@ -688,10 +688,11 @@ int pmx_conv1_wgrad(pmx_ctx* ctx, const float* x_nchw, const float* g_nchw, int 
 int pmx_pool_backward_test(pmx_ctx* ctx, const float* a_nchw, const float* u_nchw, int batch, int channels, int h, int w, float* pooled_out,
                            float* g_out);
 
-/* ---- head training step: Adam on the 82 layers after conv4_2, every weight pack rewritten on the device ----------------------------
- * What the reference's optimizer.update() does during its first 2000 iterations (train_coco_pose_estimation.py:219-225: Adam, conv1_1 ..
- * conv4_2 frozen, GradientScaling(conv4_3_CPM / conv4_4_CPM, 1/4)), applied to the gradient store pmx_backward_head leaves.  The weights
- * never leave the device.  posenet contexts, fp32 ("precision" 0).
+/* ---- training steps: Adam on the 82 layers after conv4_2 or on all 92, every weight pack rewritten on the device ----------------------
+ * What the reference's optimizer.update() does: during its first 2000 iterations (train_coco_pose_estimation.py:219-225: Adam, conv1_1 ..
+ * conv4_2 frozen, GradientScaling(conv4_3_CPM / conv4_4_CPM, 1/4)) pmx_train_step_head, applied to the gradient store pmx_backward_head
+ * leaves; from iteration 2000 on (:96-101, enable_update on the ten trunk layers) pmx_train_step, applied to what pmx_backward_head and
+ * pmx_backward_trunk leave.  The weights never leave the device.  posenet contexts, fp32 ("precision" 0).
  *
  * STORES.  pmx_train_enable(on != 0) needs pmx_backward_enable on and every layer's weights set (else PMX_ERR_STATE / PMX_ERR_WEIGHTS).  It
  * allocates three stores with the layout of the gradient store (per layer dw | db, every layer padded to a multiple of 64 floats; about
@@ -700,6 +701,9 @@ int pmx_pool_backward_test(pmx_ctx* ctx, const float* a_nchw, const float* u_nch
  * hyper-parameters alpha = 1e-4, beta1 = 0.9, beta2 = 0.999, eps = 1e-8 (Chainer's and the reference's).  PMX_ERR_CAPACITY if the device
  * refuses; the context stays usable.  on = 0 frees the stores (so does pmx_backward_enable(0)).  With training off nothing is allocated or
  * launched that was not before.  While training is on, pmx_set_layer on a head layer also rewrites that layer's master weights (m, v, t stay).
+ * With pmx_backward_enable(ctx, 2) the ten trunk layers conv1_1 .. conv4_2 have all of this too -- master weights, moments, t, scale, the
+ * pmx_set_layer rule -- in the ten segments that follow the head's; pmx_train_set_grad_scale / pmx_train_get_state / pmx_train_set_state
+ * then take their names.
  *
  * THE CONTRACT of one parameter, this project's own restatement of Chainer's AdamRule with eta = 1 and weight_decay_rate = 0.  Every line is
  * ONE float32 operation rounded to nearest, sqrt and / correctly rounded, nothing fused:
@@ -721,24 +725,38 @@ int pmx_pool_backward_test(pmx_ctx* ctx, const float* a_nchw, const float* u_nch
  *      from the same OIHW weights -- the direct pack and bias (pmx_set_layer), the Winograd pack, the transposed 180-degree-rotated pack of
  *      the data gradient and its Winograd pack.  A pack that does not exist is not created: its lazy host builder makes it on first use
  *      from the then-current direct pack, after waiting for the stream.  The f16 / bf16x3 packs of an updated layer are marked stale and
- *      rebuilt in place when a forward in that mode next needs them.
+ *      rebuilt in place when a forward in that mode next needs them.  ONE launch per kind of pack serves all updated layers (direct + bias,
+ *      transposed, Winograd of both, conv1_1's fused-kernel pack): four launches at most, driven by per-layer tables that travel with
+ *      Adam's in the same pinned copy.
  * No host synchronisation, no host <-> device copy but the table.  The step CONSUMES the gradients: a second step without a new retained
  * forward + pmx_backward_head is PMX_ERR_STATE; pmx_get_layer_grad keeps working until the next forward.
  * Errors, before anything is enqueued: PMX_ERR_INVALID for a null context; PMX_ERR_STATE for a facenet / handnet context, "precision" != 0,
- * training off, no backward for the retained forward, consumed gradients. */
+ * training off, no backward for the retained forward, consumed gradients.
+ *
+ * pmx_train_step, asynchronous on the context's stream, after pmx_backward_head AND pmx_backward_trunk for the retained forward (mode 2):
+ * the same three phases over every layer that received a gradient -- the head layers of the stages the forward ran and all ten trunk layers,
+ * whatever "stop_stage" is.  t is per layer, so a trunk layer that joins at iteration 2000 takes its first step with t = 1 while the head
+ * layers are at t = 2001 (Chainer's per-parameter UpdateRule.t).  Still one Adam launch (92 segments at most).  A trunk layer's packs are
+ * re-packed like a head layer's: the direct pack and bias, conv1_2's Winograd pack, the transposed packs and their Winograd packs
+ * (conv1_1 has none), and conv1_1's fused-kernel pack (pmx_get_pack which = 2).  Either step consumes the gradients for both:
+ * pmx_train_step after pmx_train_step_head for the same backward is PMX_ERR_STATE, and the reverse.  pmx_train_step_head in mode 2 leaves
+ * the trunk's weights, packs, moments and t alone.
+ * Errors as pmx_train_step_head's, and PMX_ERR_STATE in mode 1 and before pmx_backward_trunk. */
 int pmx_train_enable(pmx_ctx* ctx, int on);
 /* Adam's hyper-parameters from the next step on (the reference lowers alpha at 100 000 and 200 000 iterations).  alpha, eps > 0 and
  * 0 <= beta < 1, else PMX_ERR_INVALID; PMX_ERR_STATE with training off. */
 int pmx_train_set_adam(pmx_ctx* ctx, double alpha, double beta1, double beta2, double eps);
-/* the gradient scale of one head layer (GradientScaling; rounded to float32).  PMX_ERR_INVALID for an unknown name or a trunk layer. */
+/* the gradient scale of one head layer, in mode 2 also of a trunk layer (GradientScaling; rounded to float32).  PMX_ERR_INVALID for an
+ * unknown name, and in mode 1 for a trunk layer. */
 int pmx_train_set_grad_scale(pmx_ctx* ctx, const char* name, double scale);
 int pmx_train_step_head(pmx_ctx* ctx);
+int pmx_train_step(pmx_ctx* ctx);
 /* The current weights (OIHW, the layer's shape as in pmx_set_layer, the reference's input order) and bias of ANY layer; either pointer may
  * be NULL (both: PMX_ERR_INVALID).  A head layer with training on is read from the master store, anything else is un-packed from its direct
  * pack on the device -- the same floats, a pack holds them unrounded.  Any context.  PMX_ERR_INVALID for an unknown name, PMX_ERR_WEIGHTS
  * for a layer without weights.  Synchronises. */
 int pmx_get_layer(pmx_ctx* ctx, const char* name, float* w_oihw, float* bias);
-/* Adam's state of one head layer (the reference's --resume): moments of the weights (OIHW) and of the bias, and the step count.  get: any
+/* Adam's state of one head layer, in mode 2 also of a trunk layer (the reference's --resume): moments of the weights (OIHW) and of the bias, and the step count.  get: any
  * pointer may be NULL.  set: all four arrays, t >= 0, else PMX_ERR_INVALID.  PMX_ERR_STATE with training off.  Both synchronise. */
 int pmx_train_get_state(pmx_ctx* ctx, const char* name, float* m_w, float* v_w, float* m_b, float* v_b, int* t);
 int pmx_train_set_state(pmx_ctx* ctx, const char* name, const float* m_w, const float* v_w, const float* m_b, const float* v_b, int t);
@@ -746,7 +764,7 @@ int pmx_train_set_state(pmx_ctx* ctx, const char* name, const float* m_w, const 
  * fused-kernel pack), 3 the transposed pack of the data gradient, 4 its Winograd pack.  *n_bytes is the pack's size whenever it exists;
  * PMX_ERR_STATE if it does not exist now, PMX_ERR_CAPACITY if out is NULL or cap_bytes too small.  Synchronises. */
 int pmx_get_pack(pmx_ctx* ctx, const char* name, int which, void* out, size_t cap_bytes, size_t* n_bytes);
-/* test entry: the Adam launch of pmx_train_step_head on the caller's host arrays of `total` floats each (w, m, v updated in place).  Segment
+/* test entry: the Adam launch of the training steps on the caller's host arrays of `total` floats each (w, m, v updated in place).  Segment
  * i covers floats [off[i], off[i] + n[i]); off[i] a multiple of 4, the segments in rising order and not sharing a 16-byte vector, else
  * PMX_ERR_INVALID.  Floats outside the segments keep their bits.  Synchronises. */
 int pmx_adam_apply(pmx_ctx* ctx, float* w, float* m, float* v, const float* grad, size_t total, const size_t* off, const unsigned* n,

@@ -1,6 +1,9 @@
 #!/usr/bin/env python
-"""What one head training iteration costs, at 368 x 368, batch 10 (the reference's --batchsize) and 32, in one process ->
-profiles/train_step.json.  Legs, alternated `rounds` times, each figure the mean of `iters` enqueues between two events on the context's
+"""What one training iteration costs, at 368 x 368, batch 10 (the reference's --batchsize) and 32, in one process ->
+profiles/train_step.json (the head step) or, with --full, profiles/train_step_full.json (the step over all 92 layers: the engine in
+backward mode 2, legs (a) and (b) with pmx_backward_trunk and pmx_train_step, the copy yardstick over the 92 layers' parameters, the packs
+in existence and the packer launches a step makes; the head step's legs (a) and (b) are measured in the same process, interleaved with
+the full ones, and (d) is left out).  --no-host leaves (d) out of a head run as well.  Legs, alternated `rounds` times, each figure the mean of `iters` enqueues between two events on the context's
 stream after `warmup` untimed ones (images on the device):
   (a) hooked retaining forward + pmx_backward_head
   (b) the same + pmx_train_step_head
@@ -10,8 +13,9 @@ stream after `warmup` untimed ones (images on the device):
   (d) the host route the step replaces, by wall clock: every gradient fetched, Adam in NumPy, 82 x pmx_set_layer, and the next forward +
       backward, which rebuilds the derived packs on the host
 
-    python tools/train_step_time.py [--iters N] [--warmup N] [--rounds N] [--batches 10,32] [--out PATH]"""
+    python tools/train_step_time.py [--full] [--no-host] [--iters N] [--warmup N] [--rounds N] [--batches 10,32] [--out PATH]"""
 import argparse
+import ctypes
 import importlib
 import json
 import os
@@ -51,8 +55,12 @@ def main():
     ap.add_argument('--rounds', type=int, default=3)
     ap.add_argument('--batches', default='10,32')
     ap.add_argument('--size', type=int, default=368)
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'train_step.json'))
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--full', action='store_true', help='the step over all 92 layers (backward mode 2)')
+    ap.add_argument('--no-host', action='store_true', help='leave out (d), the host route')
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, 'profiles', 'train_step_full.json' if args.full else 'train_step.json')
     import torch
     native = importlib.import_module(PKG + '.native')
     weights = importlib.import_module(PKG + '.weights').synthetic_weights(0)
@@ -77,25 +85,40 @@ def main():
         eng.loss_set_poses(poses, H, W, masks, 7, 8)
         eng.loss_enable(True)
         eng.loss_grad_enable(True)
-        eng.backward_enable(True)
+        eng.backward_enable(2 if args.full else True)
         eng.train_enable(True)
         head = eng.head_layers()
         scales = {'conv4_3_CPM': 0.25, 'conv4_4_CPM': 0.25}
+        if args.full:
+            scales.update(dict.fromkeys(eng.TRUNK_LAYERS, 0.25))
         for nm, sc in scales.items():
             eng.train_set_grad_scale(nm, sc)
-        n_params = sum(int(np.prod(eng.layer_shape(nm))) + eng.layer_shape(nm)[0] for nm in head)
+        stepped = (list(eng.TRUNK_LAYERS) if args.full else []) + head
+        n_params = sum(int(np.prod(eng.layer_shape(nm))) + eng.layer_shape(nm)[0] for nm in stepped)
 
-        def leg_a():
+        def head_a():
             eng.forward_u8(device_ptr=dev.data_ptr(), shape=(B, H, W))
             eng.backward_head()
 
+        def head_b():
+            head_a()
+            eng.train_step_head()
+
+        def leg_a():
+            head_a()
+            if args.full:
+                eng.backward_trunk()
+
         def leg_b():
             leg_a()
-            eng.train_step_head()
-        a_ms, b_ms = [], []
+            eng.train_step() if args.full else eng.train_step_head()
+        a_ms, b_ms, ha_ms, hb_ms = [], [], [], []
         for _ in range(args.rounds):
             a_ms.append(timed(eng, leg_a, args.iters, args.warmup))
             b_ms.append(timed(eng, leg_b, args.iters, args.warmup))
+            if args.full:          # the head step in mode 2, interleaved
+                ha_ms.append(timed(eng, head_a, args.iters, args.warmup))
+                hb_ms.append(timed(eng, head_b, args.iters, args.warmup))
         # (c) the two parts of the step by the profiler's labels, and the copy that moves the same bytes
         eng.profile_enable(1)
         for _ in range(args.warmup):
@@ -121,6 +144,17 @@ def main():
                 copies.append(e0.elapsed_time(e1))
         del src, dst
         copy_ms = float(np.mean(copies))
+        def exists(nm, k):          # (the size query of pmx_get_pack: PMX_ERR_CAPACITY where the pack exists, PMX_ERR_STATE where not)
+            n = ctypes.c_size_t(0)
+            return eng.lib.pmx_get_pack(eng._ctx, nm.encode(), eng.PACKS[k], None, 0, ctypes.byref(n)) == 5
+        kinds = {k: sum(exists(nm, k) for nm in stepped) for k in ('w', 'wino', 't_w', 't_wino')}
+        fused = int(args.full and exists('conv1_1', 'wino'))
+        launches = int(kinds['w'] > 0) + int(kinds['t_w'] > 0) + int(kinds['wino'] - fused + kinds['t_wino'] > 0) + fused
+        extra = dict(packs_in_existence=kinds, pack_launches_per_step=launches, adam_launches_per_step=1)
+        if args.full:
+            ha, hb = float(np.mean(ha_ms)), float(np.mean(hb_ms))
+            extra.update(head_forward_backward_ms=ha, head_forward_backward_rounds_ms=ha_ms, head_with_step_ms=hb, head_with_step_rounds_ms=hb_ms,
+                         head_step_cost_ms=hb - ha)
         # (d) the host route, by wall clock
         eng.train_enable(False)
         state = {nm: [np.zeros(eng.layer_shape(nm), 'f'), np.zeros(eng.layer_shape(nm), 'f'), np.zeros(eng.layer_shape(nm)[0], 'f'),
@@ -129,7 +163,7 @@ def main():
         leg_a()
         eng.synchronize()
         host, parts = [], []
-        for t in (1, 2):
+        for t in (() if args.full or args.no_host else (1, 2)):
             t0 = time.perf_counter()
             grads = {nm: eng.layer_grad(nm) for nm in head}
             t1 = time.perf_counter()
@@ -148,7 +182,9 @@ def main():
             parts.append(dict(fetch_ms=1e3 * (t1 - t0), numpy_adam_ms=1e3 * (t2 - t1), set_layer_ms=1e3 * (t3 - t2),
                               forward_backward_rebuilding_ms=1e3 * (t4 - t3)))
         a, b = float(np.mean(a_ms)), float(np.mean(b_ms))
-        e = dict(batch=B, h=H, w=W, iters=args.iters, warmup=args.warmup, rounds=args.rounds, head_parameters=n_params,
+        e = dict(batch=B, h=H, w=W, iters=args.iters, warmup=args.warmup, rounds=args.rounds, full=bool(args.full), parameters=n_params,
+                 **extra)
+        e.update(**{'head_parameters' if not args.full else 'network_parameters': n_params},
                  forward_backward_ms=a, forward_backward_rounds_ms=a_ms, with_step_ms=b, with_step_rounds_ms=b_ms,
                  step_cost_ms=b - a, step_cost_percent=100.0 * (b - a) / a,
                  adam_launch_ms=adam_ms, packers_ms=pack_ms, adam_bytes=28 * n_params, adam_gb_per_s=28e-6 * n_params / adam_ms,
@@ -159,7 +195,9 @@ def main():
         eng.close()
         del dev
     with open(args.out, 'w') as f:
-        json.dump(dict(device='MI355X', note='(a) forward_backward = hooked retaining forward + pmx_backward_head; (b) with_step = the same + '
+        json.dump(dict(device='MI355X', note=('--full: (a) and (b) with pmx_backward_trunk and pmx_train_step in backward mode 2, head_* the head '
+                                              'step\'s (a) and (b) in the same process; ' if args.full else '') +
+                       '(a) forward_backward = hooked retaining forward + pmx_backward_head; (b) with_step = the same + '
                        'pmx_train_step_head; (c) adam_launch / packers = the per-launch profiler\'s labels train_step|adam, train_step|pack; '
                        'copy_same_bytes = hipMemcpyAsync device to device of 14 bytes per parameter (28 moved); (d) host_route = wall clock of '
                        'gradient fetch + NumPy Adam + 82 x pmx_set_layer + the next forward + backward', entries=out), f, indent=1)
