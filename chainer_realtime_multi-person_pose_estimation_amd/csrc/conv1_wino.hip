@@ -127,7 +127,7 @@ __global__ __launch_bounds__(256, 1) void conv1_wino_kernel(const ConvArgs a)
     float wv[14];
     int koff[14];
     {
-        const float* wp = a.g[1].w + chh * (14 * 64) + lane;      // packed for this kernel [half][k-pair 14][k of the pair 2][32] (pmx_api.hip::ensure_conv1_pack)
+        const float* wp = a.g[1].w + chh * (14 * 64) + lane;      // packed for this kernel [half][k-pair 14][k of the pair 2][32] (pack_index.h::pmx_pk_conv1_value)
 #pragma unroll
         for (int s = 0; s < 14; ++s) {
             const int k = 2 * s + kh, kk = k < 27 ? k : 26;
@@ -140,7 +140,7 @@ __global__ __launch_bounds__(256, 1) void conv1_wino_kernel(const ConvArgs a)
 #pragma unroll
     for (int q = 0; q < 4; ++q) b1[q] = *reinterpret_cast<const f32x4*>(a.g[1].bias + chh * 32 + 8 * q + 4 * kh);
     if (tid < 64) s_bias[tid] = a.g[0].bias[tid];
-    // conv1_2's transformed weights [plane 16][chunk 2][channel half 2][k8-step 4][32][8] (pmx_api.hip::pack_wino, cout_pad = 64): a ring of
+    // conv1_2's transformed weights [plane 16][chunk 2][channel half 2][k8-step 4][32][8] (pack_index.h::pmx_pk_wino_value, cout_pad = 64): a ring of
     // 16 fragments, requested 8 steps (32 MFMAs) ahead across all phase boundaries
     const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.g[0].w), 0, 0x7fffffff, 0x00020000);
     const unsigned b_off = (unsigned)((chh * 1024 + li * 8 + kh * 4) * 4);
@@ -362,8 +362,8 @@ __global__ __launch_bounds__(256, 1) void conv1_wino_kernel(const ConvArgs a)
     }
 }
 
-// a.g[0] = conv1_2 (in = the 16-channel padded network input, w = its TRANSFORMED weights, pack_wino with cout_pad 64), a.g[1].w = conv1_1's
-// weights in lane order (pmx_api.hip::ensure_conv1_pack), a.g[1].bias = its bias; a.g[1].in != null: the uint8 BGR batch (B x H x W x 3) to
+// a.g[0] = conv1_2 (in = the 16-channel padded network input, w = its TRANSFORMED weights, pmx_pk_wino_value with cout_pad 64), a.g[1].w = conv1_1's
+// weights in lane order (pack_index.h::pmx_pk_conv1_value), a.g[1].bias = its bias; a.g[1].in != null: the uint8 BGR batch (B x H x W x 3) to
 // preprocess on the fly instead of reading a.g[0].in, a.kbounds = the bits of the float32 divisor (255 | 256)
 int conv1_wino_launch(const ConvArgs& a0, hipStream_t stream)
 {

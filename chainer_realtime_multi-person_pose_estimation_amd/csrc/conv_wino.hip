@@ -132,7 +132,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino_kernel(const ConvArgs a)
     const bool g1 = (UNIT ? bz % a.ngroups : bz) != 0;
     ConvGroupArgs G;
     G.in = g1 ? a.g[1].in : a.g[0].in;
-    G.w = g1 ? a.g[1].w : a.g[0].w;              // transformed weights [plane][chunk32][k8-step][cout_pad][8] (pmx_api.hip::pack_wino)
+    G.w = g1 ? a.g[1].w : a.g[0].w;              // transformed weights [plane][chunk32][k8-step][cout_pad][8] (pack_index.h::pmx_pk_wino_value)
     G.bias = g1 ? a.g[1].bias : a.g[0].bias;
     G.out = g1 ? a.g[1].out : a.g[0].out;
     G.cout = g1 ? a.g[1].cout : a.g[0].cout;
@@ -849,7 +849,7 @@ static int launch_wino(const ConvArgs& a0, int groups, hipStream_t stream)
     return PMX_OK;
 }
 
-// a.nch = input channels / 32 (chunks of the Winograd kernel), a.g[].w = transformed weights (pmx_api.hip::pack_wino)
+// a.nch = input channels / 32 (chunks of the Winograd kernel), a.g[].w = transformed weights (pack_index.h::pmx_pk_wino_value)
 // a.ksplit > 1: unit mode -- a.ksplit = ceil(nch / g) (+ 3 for 7x7: row 6, column 6, tap (6, 6)) slabs at a.g[].out + unit * a.slab_stride, g = a.kbounds
 int conv_wino_launch(const ConvArgs& a, int ks, int groups, hipStream_t stream)
 {

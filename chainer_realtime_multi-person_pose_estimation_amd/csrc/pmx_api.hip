@@ -6,7 +6,6 @@
 //   of a stage are the two groups (blockIdx.z) of one launch; F.concat (:168,...) is replaced by channel-slice
 //   writes into the 192-channel "cat" buffer (layout in pmx_common.h).
 #include "pmx_ctx.h"
-#include "conv_bwd_pack.h"
 #include "f16_round.h"
 
 #include <math.h>
@@ -90,23 +89,6 @@ static std::vector<LayerDesc> make_layer_table()   // models/CocoPoseNet.py:26-1
 
 static int cout_pad_of(int cout) { return pmx_pk_cout_pad(cout); }
 
-// pack OIHW -> [tap][chunk][cout_pad][CK]; cin_map[k] = source input channel of packed channel k (or -1 = zero)
-static void pack_weights(const float* w, const float* bias, int cout, int cin, int ks, const std::vector<int>& cin_map,
-                         int cout_pad, std::vector<float>& wp, std::vector<float>& bp)
-{
-    const int cin_pad = (int)cin_map.size(), nch = cin_pad / CK, T = ks * ks;
-    wp.assign((size_t)T * nch * cout_pad * CK, 0.f);
-    bp.assign((size_t)cout_pad, 0.f);
-    for (int n = 0; n < cout; ++n) bp[n] = bias ? bias[n] : 0.f;
-    for (int tap = 0; tap < T; ++tap)
-        for (int k = 0; k < cin_pad; ++k) {
-            const int src = cin_map[k];
-            if (src < 0) continue;
-            for (int n = 0; n < cout; ++n)
-                wp[pmx_pk_direct(tap, k, n, nch, cout_pad)] = w[pmx_pk_oihw(n, src, tap, cin, T)];
-        }
-}
-
 // fp32 -> three bf16 terms, each the round-to-nearest-even bf16 of what is left (as conv_bf16x3_kernel splits the activations)
 static inline uint16_t bf16_rn(float x)
 {
@@ -123,45 +105,6 @@ static inline float bf16_f(uint16_t h)
     return f;
 }
 // packed fp32 weights [tap][chunk][cout_pad][16] -> bf16x3 [tap][chunk][plane][cout_pad][16]
-// Winograd F(2x2, 3x3) weights: U = G g G^T per (cout, cin), G = [[1,0,0],[1/2,1/2,1/2],[1/2,-1/2,1/2],[0,0,1]], evaluated in double and
-// rounded once to fp32 (oracle/conv_fma_ref.c::conv_wino_ref does the same); layout [plane = sub-kernel * 16 + 4i + j][chunk of 32
-// cin][k8-step 4][cout_pad][8].  ks = 3: one sub-kernel; ks = 7: four, sub-kernel (sy, sx) = taps (3 sy .. 3 sy + 2, 3 sx .. 3 sx + 2); row 6 and
-// column 6 of the 7x7 kernel are two 1x3 / two 3x1 sub-kernels with the 1-D transform G g (planes 64.., 72..), tap (6, 6) is plane 80
-static void pack_wino(const std::vector<float>& wp, int ks, int nch16, int cout_pad, std::vector<float>& out)
-{
-    static const double Gm[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-    const int cin_pad = nch16 * CK, nch32 = cin_pad / 32, nsub = ks == 3 ? 1 : 4;
-    const int nplanes = ks == 3 ? 16 : 81;      // 7x7: 64 (four 3x3 sub-kernels) + 8 (row 6: two 1x3, G g) + 8 (column 6: two 3x1) + 1 (tap (6, 6))
-    out.assign((size_t)nplanes * nch32 * cout_pad * 32, 0.f);
-    auto tapw = [&](int ky, int kx, int n, int ci) -> double {
-        return wp[pmx_pk_direct(ky * ks + kx, ci, n, nch16, cout_pad)];
-    };
-    auto put = [&](int plane, int n, int ci, double v) {
-        // [plane][chunk32][cout_pad / 32][k8-step][32][8]: the four k8-steps of a wave's 32 channels are 1 KB apart (an immediate offset of the load)
-        out[pmx_pk_wino(plane, n, ci, nch32, cout_pad)] = (float)v;
-    };
-    for (int n = 0; n < cout_pad; ++n)
-        for (int ci = 0; ci < cin_pad; ++ci) {
-            for (int sub = 0; sub < nsub; ++sub) {
-                double gg[4][3];
-                for (int i = 0; i < 4; ++i)
-                    for (int kx = 0; kx < 3; ++kx)
-                        gg[i][kx] = (Gm[i][0] * tapw(3 * (sub >> 1) + 0, 3 * (sub & 1) + kx, n, ci) + Gm[i][1] * tapw(3 * (sub >> 1) + 1, 3 * (sub & 1) + kx, n, ci)) +
-                                    Gm[i][2] * tapw(3 * (sub >> 1) + 2, 3 * (sub & 1) + kx, n, ci);
-                for (int i = 0; i < 4; ++i)
-                    for (int j = 0; j < 4; ++j) put(sub * 16 + 4 * i + j, n, ci, (gg[i][0] * Gm[j][0] + gg[i][1] * Gm[j][1]) + gg[i][2] * Gm[j][2]);
-            }
-            if (ks == 7) {
-                for (int sub = 0; sub < 2; ++sub)
-                    for (int f = 0; f < 4; ++f) {
-                        put(64 + sub * 4 + f, n, ci, (Gm[f][0] * tapw(6, 3 * sub + 0, n, ci) + Gm[f][1] * tapw(6, 3 * sub + 1, n, ci)) + Gm[f][2] * tapw(6, 3 * sub + 2, n, ci));
-                        put(72 + sub * 4 + f, n, ci, (Gm[f][0] * tapw(3 * sub + 0, 6, n, ci) + Gm[f][1] * tapw(3 * sub + 1, 6, n, ci)) + Gm[f][2] * tapw(3 * sub + 2, 6, n, ci));
-                    }
-                put(80, n, ci, tapw(6, 6, n, ci));
-            }
-        }
-}
-
 static void pack_bf16x3(const std::vector<float>& wp, int T, int nch, int cout_pad, std::vector<uint16_t>& out)
 {
     out.assign((size_t)T * nch * 3 * cout_pad * CK, 0);
@@ -185,48 +128,39 @@ static void pack_f16(const std::vector<float>& wp, std::vector<uint16_t>& out)
     for (size_t i = 0; i < wp.size(); ++i) out[i] = f16_rn_sat(wp[i]);
 }
 
-// conv1_1's weights in the order conv1_wino_kernel's lanes want them: [channel half 2][k-pair 14][k of the pair 2][channel 32] (the 28th k is
-// zero) -- one contiguous 256-byte run per wave and k-pair.  Read out of the direct pack [tap][1 chunk][64][16] each lane gathered 14 dwords
-// 64 bytes apart: 1.7 us of a 25 us block (profiles/r05_conv1_wino_ablation.json).
-static void pack_conv1(const std::vector<float>& wp, int cout_pad, std::vector<float>& out)
-{
-    out.assign(PMX_PK_CONV1_FLOATS, 0.f);
-    for (int i = 0; i < PMX_PK_CONV1_FLOATS; ++i) {
-        const long long src = pmx_pk_conv1_src(i, cout_pad);      // (pack_index.h: the training step's device packer shares it)
-        if (src >= 0) out[i] = wp[src];
-    }
-}
-
+// the channel map of a layer's input (pack_index.h): the concat layers of the pose network (1) and of the face / hand networks (2 + C), else 0
 int pmx_pack_kind(const pmx_ctx* c, int cin) { return c->kind == NET_POSE ? (cin == 185 ? 1 : 0) : cin == c->n_heat + 128 ? 2 + c->n_heat : 0; }
 
-static std::vector<int> identity_map(int cin)
+// ---- building packs: everything goes through the device packers (pmx_packs.hip); these calls return when the pack is complete ----------------
+// host (w OIHW, bias or null) -> master (w | b) on the device, b zero without a bias; ordered before what `st` runs next
+static int upload_master(float* master, const float* w, const float* bias, int cout, int cin, int ks, hipStream_t st)
 {
-    std::vector<int> m(round_up(cin, CK), -1);
-    for (int i = 0; i < cin; ++i) m[i] = i;
-    return m;
+    const size_t nw = (size_t)cout * cin * ks * ks;
+    PMX_HIP(hipMemcpy(master, w, nw * sizeof(float), hipMemcpyHostToDevice));
+    if (bias) PMX_HIP(hipMemcpy(master + nw, bias, (size_t)cout * sizeof(float), hipMemcpyHostToDevice));
+    else PMX_HIP(hipMemsetAsync(master + nw, 0, (size_t)cout * sizeof(float), st));
+    return PMX_OK;
 }
-
-// F.concat((h1, h2, feature_map)) channel c of the reference (0..37 PAF, 38..56 heat, 57..184 feature) lives at
-// cat-buffer channel: feature -> 0..127, PAF -> 128..165, heat -> 168..186
-static std::vector<int> concat_map()
+// L (geometry filled) gets its direct pack and bias from master weights on the device; allocates what it does not hold
+static int build_direct(PackedLayer& L, int kind, const float* master, hipStream_t st)
 {
-    std::vector<int> m(PMX_CAT_C, -1);
-    for (int i = 0; i < 128; ++i) m[PMX_CAT_FEAT + i] = 57 + i;
-    for (int i = 0; i < 38; ++i) m[PMX_CAT_PAF + i] = i;
-    for (int i = 0; i < 19; ++i) m[PMX_CAT_HEAT + i] = 38 + i;
-    return m;
+    int rc;
+    if (!L.d_w && (rc = L.d_w.alloc((size_t)L.ks * L.ks * L.nch * L.cout_pad * CK))) return rc;
+    if (!L.d_b && (rc = L.d_b.alloc((size_t)L.cout_pad))) return rc;
+    if ((rc = pmx_pack_launch_one(PMX_PACK_DIRECT, pmx_pack_job_direct(master, L, kind), st))) return rc;
+    PMX_HIP(hipStreamSynchronize(st));
+    return PMX_OK;
 }
-
-// F.concat((h, feature_map)) of FaceNet / HandNet (models/FaceNet.py:107): reference channel c (0..C-1 heat, C..C+127
-// feature) lives at cat-buffer channel: feature -> 0..127, heat -> 128..128+C-1, zero pad up to a multiple of 16
-static std::vector<int> concat_map_cpm(int C)
+// P (geometry filled): the layer whose forward is the data gradient of the layer (cout, cin, ks, kind) with these master weights; no bias
+static int build_transposed(PackedLayer& P, int cout, int cin, int ks, int kind, const float* master, hipStream_t st)
 {
-    std::vector<int> m(round_up(128 + C, CK), -1);
-    for (int i = 0; i < 128; ++i) m[i] = C + i;
-    for (int i = 0; i < C; ++i) m[128 + i] = i;
-    return m;
+    int rc;
+    if ((rc = P.d_w.alloc((size_t)ks * ks * P.nch * P.cout_pad * CK)) || (rc = P.d_b.alloc((size_t)P.cout_pad))) return rc;
+    PMX_HIP(hipMemsetAsync(P.d_b, 0, (size_t)P.cout_pad * sizeof(float), st));
+    if ((rc = pmx_pack_launch_one(PMX_PACK_TRANSPOSED, pmx_pack_job_transposed(master, cout, cin, ks, kind, P), st))) return rc;
+    PMX_HIP(hipStreamSynchronize(st));
+    return PMX_OK;
 }
-
 
 static int prof_begin(pmx_ctx* c, const std::string& name0, double flops, double bytes, double issued = -1.0, bool record = true)
 {
@@ -504,25 +438,26 @@ extern "C" int pmx_set_layer(pmx_ctx* c, const char* name, const float* w, const
     PMX_CHECK(d.cin == cin && d.cout == cout && d.ks == ks, PMX_ERR_WEIGHTS,
               "pmx_set_layer: '%s' expects (cout %d, cin %d, k %d), got (%d, %d, %d)", name, d.cout, d.cin, d.ks, cout, cin, ks);
     PackedLayer& L = c->layers[it->second];
-    std::vector<int> cmap = (c->kind == NET_POSE && cin == 185) ? concat_map()
-                            : (c->kind != NET_POSE && cin == c->n_heat + 128) ? concat_map_cpm(c->n_heat) : identity_map(cin);
-    std::vector<float> wp, bp;
-    const int cpad = cout_pad_of(cout);
-    pack_weights(w, bias, cout, cin, ks, cmap, cpad, wp, bp);
+    const int kind = pmx_pack_kind(c, cin);
     PMX_HIP(hipStreamSynchronize(c->stream));     // layer may be in use by queued work
+    // (w | b) goes up once: into the layer's master segment while training is on (the next step packs from there), else into a staging buffer
     int rc;
-    if (!L.d_w && (rc = L.d_w.alloc(wp.size()))) return rc;
-    if (!L.d_b && (rc = L.d_b.alloc(bp.size()))) return rc;
-    PMX_HIP(hipMemcpy(L.d_w, wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice));
-    PMX_HIP(hipMemcpy(L.d_b, bp.data(), bp.size() * sizeof(float), hipMemcpyHostToDevice));
+    DevBuf<float> staging;
+    float* master = pmx_train_master(c, it->second);
+    if (master) { L.busy = true; L.busy_stream = c->stream; }
+    else {
+        if ((rc = staging.alloc((size_t)cout * cin * ks * ks + cout))) return rc;
+        master = staging;
+    }
+    if ((rc = upload_master(master, w, bias, cout, cin, ks, c->stream))) return rc;
+    pmx_layer_geometry(L, cout, cin, ks, pmx_pk_cin_pad(kind, cin));
+    if ((rc = build_direct(L, kind, master, c->stream))) return rc;
     // the bf16x3 pack (1.5x the fp32 weights) and the Winograd pack (16/9 x for 3x3, 81/49 x for 7x7) are derived from the packed fp32
     // weights on first use (ensure_*_pack): a context that never runs those kernels neither holds nor computes them
     L.d_w3.reset(); L.d_w16.reset(); L.d_ww.reset();
     if ((size_t)it->second < c->bw.tl.size()) c->bw.tl[it->second] = PackedLayer();      // the data-gradient pack of the old weights
-    L.set = true; L.cin = cin; L.cout = cout; L.ks = ks;
-    L.cin_pad = (int)cmap.size(); L.cout_pad = cpad; L.nch = L.cin_pad / CK;
+    L.set = true;
     L.stale16 = L.stale3 = false;
-    if (c->tr.on) return pmx_train_on_set_layer(c, it->second, w, bias);
     return PMX_OK;
 }
 
@@ -536,7 +471,8 @@ extern "C" int pmx_weights_missing(pmx_ctx* c, int* n)
 }
 
 // ------------------------------------------------------------------------------------------ forward
-// Derived weight packs, built from the device-resident packed fp32 weights when a kernel first needs them: fetch, `pack`, allocate, copy.
+// Derived weight packs, built from the device-resident packed fp32 weights when a kernel first needs them.  The f16 and bf16x3 packs are
+// rounded on the host: fetch, `pack`, allocate, copy.
 // The slot takes the buffer only once the copy is complete: a failed copy must not leave a non-null pointer to garbage behind.
 template <typename T, typename Pack>
 static int derive_pack(const PackedLayer& L, DevBuf<T>& slot, const char* what, Pack pack, bool stale = false)
@@ -561,16 +497,26 @@ static int derive_pack(const PackedLayer& L, DevBuf<T>& slot, const char* what, 
     slot = std::move(d);
     return PMX_OK;
 }
-static int ensure_wino_pack(PackedLayer& L)
+// The Winograd pack and conv1_1's fused-kernel pack (which lives in conv1_1's otherwise unused Winograd slot) are built on the device from
+// the direct pack: allocate, launch on the context's current stream, wait for it.  derive_pack's rule holds: the slot takes the buffer only
+// when it is complete, so the lanes of detect_precise may share the pack from their own streams as soon as this returns.
+static int derive_on_device(pmx_ctx* c, PackedLayer& L, int kind)
 {
-    return derive_pack(L, L.d_ww, "winograd", [&](const std::vector<float>& wp, std::vector<float>& o) { pack_wino(wp, L.ks, L.nch, L.cout_pad, o); });
+    if (L.d_ww) return PMX_OK;
+    if (L.busy) PMX_HIP(hipStreamSynchronize(L.busy_stream));      // a training step may still be writing d_w
+    PackJob j = kind == PMX_PACK_WINO ? pmx_pack_job_wino(L, nullptr) : pmx_pack_job_conv1(L, nullptr);
+    DevBuf<float> d;
+    int rc;
+    if ((rc = d.alloc(j.total))) return rc;
+    j.dst = d;
+    if ((rc = pmx_pack_launch_one(kind, j, c->stream))) return rc;
+    PMX_HIP(hipStreamSynchronize(c->stream));
+    L.d_ww = std::move(d);
+    return PMX_OK;
 }
-// (lives in conv1_1's otherwise unused Winograd slot)
-static int ensure_conv1_pack(PackedLayer& L)
-{
-    return derive_pack(L, L.d_ww, "conv1_1", [&](const std::vector<float>& wp, std::vector<float>& o) { pack_conv1(wp, L.cout_pad, o); });
-}
-static int ensure_bf16x3_pack(PackedLayer& L)
+static int ensure_wino_pack(pmx_ctx* c, PackedLayer& L) { return derive_on_device(c, L, PMX_PACK_WINO); }
+static int ensure_conv1_pack(pmx_ctx* c, PackedLayer& L) { return derive_on_device(c, L, PMX_PACK_CONV1); }
+static int ensure_bf16x3_pack(pmx_ctx*, PackedLayer& L)
 {
     const int rc = derive_pack(L, L.d_w3, "bf16x3", [&](const std::vector<float>& wp, std::vector<uint16_t>& o) { pack_bf16x3(wp, L.ks * L.ks, L.nch, L.cout_pad, o); },
                                L.stale3);
@@ -578,7 +524,7 @@ static int ensure_bf16x3_pack(PackedLayer& L)
     return rc;
 }
 // the f16 pack (half the fp32 weights' bytes): every 3x3 / 7x7 layer in f16 mode
-static int ensure_f16_pack(PackedLayer& L)
+static int ensure_f16_pack(pmx_ctx*, PackedLayer& L)
 {
     const int rc = derive_pack(L, L.d_w16, "f16", pack_f16, L.stale16);
     if (!rc) L.stale16 = false;
@@ -760,7 +706,7 @@ static int plan_conv(pmx_ctx* c, ConvPlan& p, const char* label, PackedLayer* L0
     const bool seg = !c->segs.empty() && level >= 0;
     const double npix = seg ? (double)c->seg_pix[level] : (double)B * H * W;
     PackedLayer* const Lg[2] = {L0, L1};
-    auto ensure = [&](int (*fn)(PackedLayer&)) { const int rc = fn(*L0); return rc || !L1 ? rc : fn(*L1); };
+    auto ensure = [&](int (*fn)(pmx_ctx*, PackedLayer&)) { const int rc = fn(c, *L0); return rc || !L1 ? rc : fn(c, *L1); };
     p.ks = ks; p.groups = groups;
     p.prof = label && (c->prof_on == 1 || (c->prof_on == 2 && ks == 7));
     ConvArgs& a = p.a;
@@ -988,7 +934,7 @@ static int run_conv1(pmx_ctx* c, int B, int H, int W)
     a.g[1].w = L1.d_w; a.g[1].bias = L1.d_b;
     a.B = B; a.H = H; a.W = W; a.lda = PMX_IN_C; a.ldc = 64; a.nch = L2.nch; a.cout_pad = L2.cout_pad; a.relu = 1; a.pool = 1;
     if (wino1) {
-        if ((rc = ensure_wino_pack(L2)) || (rc = ensure_conv1_pack(L1))) return rc;
+        if ((rc = ensure_wino_pack(c, L2)) || (rc = ensure_conv1_pack(c, L1))) return rc;
         a.g[0].w = L2.d_ww;
         a.g[1].w = L1.d_ww;
         if (in_u8) {                                      // the kernel preprocesses the uint8 batch itself (pmx_forward_from_u8)
@@ -1853,19 +1799,16 @@ extern "C" int pmx_profile_entry(pmx_ctx* c, int i, char* name, int cap, double*
 }
 
 // ---------------------------------------------------------------------------- single-layer test entries
-// a layer that is not in the context's table: packed as set_layer packs one (identity channel map) and uploaded; its buffers, derived packs
-// included, are freed with it
-static int test_layer(PackedLayer& L, const float* w, const float* bias, int cout, int cin, int ks)
+// a layer that is not in the context's table: packed as set_layer packs one (identity channel map); its buffers, derived packs included,
+// are freed with it
+static int test_layer(pmx_ctx* c, PackedLayer& L, const float* w, const float* bias, int cout, int cin, int ks)
 {
-    std::vector<int> cmap = identity_map(cin);
-    L.set = true; L.cin = cin; L.cout = cout; L.ks = ks;
-    L.cin_pad = (int)cmap.size(); L.cout_pad = cout_pad_of(cout); L.nch = L.cin_pad / CK;
-    std::vector<float> wp, bp;
-    pack_weights(w, bias, cout, cin, ks, cmap, L.cout_pad, wp, bp);
+    DevBuf<float> master;
     int rc;
-    if ((rc = L.d_w.alloc(wp.size())) || (rc = L.d_b.alloc(bp.size()))) return rc;
-    PMX_HIP(hipMemcpy(L.d_w, wp.data(), wp.size() * 4, hipMemcpyHostToDevice));
-    PMX_HIP(hipMemcpy(L.d_b, bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
+    if ((rc = master.alloc((size_t)cout * cin * ks * ks + cout)) || (rc = upload_master(master, w, bias, cout, cin, ks, c->stream))) return rc;
+    pmx_layer_geometry(L, cout, cin, ks, pmx_pk_cin_pad(0, cin));
+    if ((rc = build_direct(L, 0, master, c->stream))) return rc;
+    L.set = true;
     return PMX_OK;
 }
 // host NCHW x -> channels [coff, coff + cin) of the NHWC buffer d_xn (channel stride lda), through the staging buffer d_x
@@ -1897,7 +1840,7 @@ extern "C" int pmx_conv2d(pmx_ctx* c, const float* x, const float* w, const floa
     PMX_DEV(c);
     PackedLayer L;
     int rc;
-    if ((rc = test_layer(L, w, bias, cout, cin, ks))) return rc;
+    if ((rc = test_layer(c, L, w, bias, cout, cin, ks))) return rc;
     const int Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W;
     DevBuf<float> d_x, d_xn, d_y, d_yn;
     const size_t nx = (size_t)B * cin * H * W, nxn = (size_t)B * H * W * L.cin_pad, ny = (size_t)B * cout * Ho * Wo;
@@ -1945,7 +1888,7 @@ extern "C" int pmx_conv2d_pair(pmx_ctx* c, const float* x0, const float* x1, con
     PMX_DEV(c);
     PackedLayer L[2];
     int rc;
-    if ((rc = test_layer(L[0], w0, bias0, cout0, cin, ks)) || (rc = test_layer(L[1], w1, bias1, cout1, cin, ks))) return rc;
+    if ((rc = test_layer(c, L[0], w0, bias0, cout0, cin, ks)) || (rc = test_layer(c, L[1], w1, bias1, cout1, cin, ks))) return rc;
     const int cin_pad = L[0].cin_pad, Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W;
     // input slices at channels 16 and 16 + cin_pad of lda, output slices at 0 and cout0 (rounded up to 4) of ldc: 4 channels of nobody at the end
     const int ioff[2] = {CK, x1 ? CK + cin_pad : CK}, lda = ioff[1] + cin_pad + CK;
@@ -1988,7 +1931,6 @@ extern "C" int pmx_conv2d_backward(pmx_ctx* c, const float* x, const float* w, c
     if (avg_ms3) avg_ms3[0] = avg_ms3[1] = avg_ms3[2] = 0.0;
     // L: the layer itself (z); Lt: the layer whose forward is the data gradient
     PackedLayer L, Lt;
-    std::vector<float> wp, bp;
     DevBuf<float> d_x, d_xn, d_x32, d_zn, d_z, d_dy, d_g, d_dxn, d_dx, d_ws, d_dw, d_db;
     DevBuf<double> d_part;
     int rc;
@@ -2001,13 +1943,7 @@ extern "C" int pmx_conv2d_backward(pmx_ctx* c, const float* x, const float* w, c
     };
     ConvPlan pz, pt;
     if (need_z) {
-        const std::vector<int> cmap = identity_map(cin);
-        L.set = true; L.cin = cin; L.cout = cout; L.ks = ks;
-        L.cin_pad = (int)cmap.size(); L.cout_pad = cout_pad_of(cout); L.nch = L.cin_pad / CK;
-        pack_weights(w, bias, cout, cin, ks, cmap, L.cout_pad, wp, bp);
-        if ((rc = to_nhwc(d_xn, L.cin_pad)) || (rc = L.d_w.alloc(wp.size())) || (rc = L.d_b.alloc(bp.size())) || (rc = d_zn.alloc(nz))) return rc;
-        PMX_HIP(hipMemcpy(L.d_w, wp.data(), wp.size() * 4, hipMemcpyHostToDevice));
-        PMX_HIP(hipMemcpy(L.d_b, bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
+        if ((rc = test_layer(c, L, w, bias, cout, cin, ks)) || (rc = to_nhwc(d_xn, L.cin_pad)) || (rc = d_zn.alloc(nz))) return rc;
         PMX_HIP(hipMemsetAsync(d_zn, 0xFF, nz * 4, c->stream));
         if ((rc = plan_conv(c, pz, nullptr, &L, nullptr, d_xn, nullptr, L.cin_pad, d_zn, nullptr, cout, B, H, W, 0, 0, -1))) return rc;
         if ((rc = launch_plan(c, pz))) return rc;
@@ -2018,15 +1954,12 @@ extern "C" int pmx_conv2d_backward(pmx_ctx* c, const float* x, const float* w, c
     }
     if (db && ((rc = d_part.alloc((size_t)PMX_DB_SLOTS * cg)) || (rc = d_db.alloc(cout)))) return rc;
     if (dx) {
-        const std::vector<int> cmap = identity_map(cout);
-        std::vector<float> wt((size_t)cin * cout * T);
-        pmx_conv_flip_weights(w, cout, cin, ks, wt.data());
-        Lt.set = true; Lt.cin = cout; Lt.cout = cin; Lt.ks = ks;
-        Lt.cin_pad = (int)cmap.size(); Lt.cout_pad = cout_pad_of(cin); Lt.nch = Lt.cin_pad / CK;
-        pack_weights(wt.data(), nullptr, cin, cout, ks, cmap, Lt.cout_pad, wp, bp);
-        if ((rc = Lt.d_w.alloc(wp.size())) || (rc = Lt.d_b.alloc(bp.size())) || (rc = d_dxn.alloc(nx)) || (rc = d_dx.alloc(nx))) return rc;
-        PMX_HIP(hipMemcpy(Lt.d_w, wp.data(), wp.size() * 4, hipMemcpyHostToDevice));
-        PMX_HIP(hipMemcpy(Lt.d_b, bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
+        // (its input padding is its own: g has only cg channels per pixel, so cout rounded up to 16 and not pmx_pk_t_cin_pad's 64 at least)
+        DevBuf<float> master;
+        if ((rc = master.alloc(ndw + cout)) || (rc = upload_master(master, w, nullptr, cout, cin, ks, c->stream))) return rc;
+        pmx_layer_geometry(Lt, cin, cout, ks, round_up(cout, CK));
+        if ((rc = build_transposed(Lt, cout, cin, ks, 0, master, c->stream)) || (rc = d_dxn.alloc(nx)) || (rc = d_dx.alloc(nx))) return rc;
+        Lt.set = true;
         PMX_HIP(hipMemsetAsync(d_dxn, 0xFF, nx * 4, c->stream));       // poison: an unwritten element is caught by the test
         // g has cg >= Lt.cin_pad channels per pixel, the padding channels zero
         if ((rc = plan_conv(c, pt, nullptr, &Lt, nullptr, d_g, nullptr, cg, d_dxn, nullptr, cin, B, H, W, 0, 0, -1))) return rc;
@@ -2094,10 +2027,11 @@ int pmx_run_conv(pmx_ctx* c, const char* label, PackedLayer* L0, PackedLayer* L1
     return run_conv(c, label, L0, L1, in0, in1, lda, out0, out1, ldc, B, H, W, relu, 0);
 }
 
-// The layer whose forward is the data gradient of table layer `layer` (conv_bwd_pack.h), packed like any layer.  The OIHW weights come
-// back from the layer's device pack (the context keeps no host copy), in the reference's input order.  Its input is the layer's g: `cout`
-// channels padded with zeros to 64 for the 38 / 19-channel outputs, so that both branches of a launch have the same chunk count.  Its output
-// has the layer's input channels -- for Mconv1_* the 192 channels of the concat buffer in the buffer's order, the pad channels zero.
+// The layer whose forward is the data gradient of table layer `layer` (pack_index.h: the transposed pack), packed like any layer, from the
+// layer's master weights -- those of the training stores, else the layer's direct pack un-packed into a temporary (the context keeps no
+// other copy).  Its input is the layer's g: `cout` channels padded with zeros to 64 for the 38 / 19-channel outputs, so that both branches
+// of a launch have the same chunk count.  Its output has the layer's input channels -- for Mconv1_* the 192 channels of the concat buffer
+// in the buffer's order, the pad channels zero.
 int pmx_bw_transposed_pack(pmx_ctx* c, int layer)
 {
     PMX_CHECK(layer >= 0 && (size_t)layer < c->layers.size() && (size_t)layer < c->bw.tl.size(), PMX_ERR_INVALID, "backward pack: layer %d", layer);
@@ -2105,32 +2039,18 @@ int pmx_bw_transposed_pack(pmx_ctx* c, int layer)
     if (Lt.set) return PMX_OK;
     const PackedLayer& L = c->layers[layer];
     PMX_CHECK(L.set, PMX_ERR_WEIGHTS, "backward pack: layer '%s' has no weights", c->table[layer].name.c_str());
-    const int T = L.ks * L.ks;
-    const bool cat_in = c->kind == NET_POSE && L.cin == 185;
-    const std::vector<int> cmap = cat_in ? concat_map() : identity_map(L.cin);
-    std::vector<float> wp((size_t)T * L.nch * L.cout_pad * CK), w((size_t)L.cout * L.cin * T);
-    if (L.busy) PMX_HIP(hipStreamSynchronize(L.busy_stream));      // a training step may still be writing d_w
-    PMX_HIP(hipMemcpy(wp.data(), L.d_w, wp.size() * sizeof(float), hipMemcpyDeviceToHost));
-    for (int tap = 0; tap < T; ++tap)
-        for (int k = 0; k < L.cin_pad; ++k) {
-            if (cmap[k] < 0) continue;
-            for (int n = 0; n < L.cout; ++n)
-                w[((size_t)n * L.cin + cmap[k]) * T + tap] = wp[(((size_t)tap * L.nch + k / CK) * L.cout_pad + n) * CK + k % CK];
-        }
-    const int t_cout = cat_in ? PMX_CAT_C : L.cin;
-    std::vector<float> wt((size_t)t_cout * L.cout * T), bp;
-    if (cat_in) pmx_conv_flip_weights_mapped(w.data(), L.cout, L.cin, L.ks, cmap.data(), PMX_CAT_C, wt.data());
-    else pmx_conv_flip_weights(w.data(), L.cout, L.cin, L.ks, wt.data());
-    std::vector<int> gmap(L.cout < 64 ? 64 : round_up(L.cout, CK), -1);
-    for (int i = 0; i < L.cout; ++i) gmap[i] = i;
-    PackedLayer P;
-    P.cin = L.cout; P.cout = t_cout; P.ks = L.ks;
-    P.cin_pad = (int)gmap.size(); P.cout_pad = cout_pad_of(t_cout); P.nch = P.cin_pad / CK;
-    pack_weights(wt.data(), nullptr, t_cout, L.cout, L.ks, gmap, P.cout_pad, wp, bp);
+    if (L.busy) PMX_HIP(hipStreamSynchronize(L.busy_stream));      // a training step may still be writing d_w and the master weights
+    const int kind = pmx_pack_kind(c, L.cin);
+    const float* master = pmx_train_master(c, layer);
+    DevBuf<float> tmp;
     int rc;
-    if ((rc = P.d_w.alloc(wp.size())) || (rc = P.d_b.alloc(bp.size()))) return rc;
-    PMX_HIP(hipMemcpy(P.d_w, wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice));
-    PMX_HIP(hipMemcpy(P.d_b, bp.data(), bp.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (!master) {
+        if ((rc = tmp.alloc((size_t)L.cout * L.cin * L.ks * L.ks + L.cout)) || (rc = pmx_unpack_launch(L, kind, tmp, c->stream))) return rc;
+        master = tmp;
+    }
+    PackedLayer P;
+    pmx_layer_geometry(P, pmx_pk_t_cout(kind, L.cin), L.cout, L.ks, pmx_pk_t_cin_pad(L.cout));
+    if ((rc = build_transposed(P, L.cout, L.cin, L.ks, kind, master, c->stream))) return rc;
     P.set = true; P.busy = L.busy; P.busy_stream = L.busy_stream;
     Lt = std::move(P);
     return PMX_OK;

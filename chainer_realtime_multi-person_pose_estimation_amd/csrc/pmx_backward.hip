@@ -110,9 +110,7 @@ int bw_layout(pmx_ctx* c, int mode)
     PMX_HIP(hipMemsetAsync(bw.grad, 0xFF, off * sizeof(float), c->stream));
     PMX_HIP(hipMemsetAsync(bw.trunk, 0xFF, bw.cap_px * 512 * sizeof(float), c->stream));
     int map[185];
-    for (int i = 0; i < 38; ++i) map[i] = PMX_CAT_PAF + i;
-    for (int i = 0; i < 19; ++i) map[38 + i] = PMX_CAT_HEAT + i;
-    for (int i = 0; i < 128; ++i) map[57 + i] = PMX_CAT_FEAT + i;
+    for (int i = 0; i < 185; ++i) map[i] = pmx_pk_packed_of_ref(1, i);
     PMX_HIP(hipMemcpy(bw.cat_of_ref, map, sizeof map, hipMemcpyHostToDevice));
     return PMX_OK;
 }

@@ -96,7 +96,7 @@ struct ConvArgs {
     int nseg, seg_tiles;
     const ConvSeg* segs;     // device memory
 };
-// Transformed Winograd weights (pmx_api.hip::pack_wino -> conv_wino_kernel): [plane][chunk32][cout_pad / 32][k8-step 4][32][8] -- the four
+// Transformed Winograd weights (pack_index.h::pmx_pk_wino_value -> conv_wino_kernel): [plane][chunk32][cout_pad / 32][k8-step 4][32][8] -- the four
 // k8-steps of a wave's 32 channels are 1 KB apart, an immediate offset of the load
 // Winograd run geometry: tile columns of a 46-pixel-wide map / tiles per block
 #define PMX_WINO_RUN_TX 23
@@ -187,7 +187,7 @@ bool conv_pair_supported(int cin, int cmid, int cout_pad);
 // conv1_1 (3 -> 64) recomputed on the halo + conv1_2 (64 -> 64 [+ pool]) in one launch: a.g[0] = conv1_2 (in = padded network input),
 // a.g[1].w / .bias = conv1_1's packed weights / bias
 int conv1_fused_launch(const ConvArgs& a, hipStream_t stream);
-// the same pair with conv1_2 in Winograd F(2x2, 3x3) (conv1_wino.hip): a.g[0].w = conv1_2's TRANSFORMED weights (pack_wino, cout_pad 64)
+// the same pair with conv1_2 in Winograd F(2x2, 3x3) (conv1_wino.hip): a.g[0].w = conv1_2's TRANSFORMED weights (pmx_pk_wino_value, cout_pad 64)
 int conv1_wino_launch(const ConvArgs& a, hipStream_t stream);
 // Winograd F(2x2, 3x3): a.nch = cin / 32, a.g[].w = transformed weights [plane][chunk32][k8-step][cout_pad][8] (G g G^T, host);
 // ks = 7: planes 0..63 = four 3x3 sub-kernels (taps 0..5 x 0..5), 64..71 row 6, 72..79 column 6 (1-D G g), 80 = tap (6, 6)

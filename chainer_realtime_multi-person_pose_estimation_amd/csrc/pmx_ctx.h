@@ -431,8 +431,22 @@ int pmx_run_conv(pmx_ctx* c, const char* label, PackedLayer* L0, PackedLayer* L1
 int pmx_bw_transposed_pack(pmx_ctx* c, int layer);
 // c->smoothed (and c->pp.smoothed) at `floats` floats at least, grown to exactly that once the stream no longer uses the old maps
 int pmx_ensure_smoothed(pmx_ctx* c, size_t floats);
-// pmx_api.hip, for pmx_train.hip: the channel map kind of a layer's direct pack (pack_index.h), and pmx_set_layer's hook -- with training on,
-// the new weights of a layer with a segment (head; mode 2: trunk too) also go to the master store (pmx_train.hip)
+// pmx_api.hip: the channel map kind of a layer's direct pack (pack_index.h).  pmx_train.hip: the master weights (w OIHW | b) of a layer with
+// a segment while training is on (head; mode 2: trunk too), else null
 int pmx_pack_kind(const pmx_ctx* c, int cin);
-int pmx_train_on_set_layer(pmx_ctx* c, int layer, const float* w, const float* bias);
+float* pmx_train_master(const pmx_ctx* c, int layer);
 void pmx_train_free(pmx_ctx* c);
+// pmx_packs.hip: the packers, the only way a pack gets built.  pmx_layer_geometry fills a layer's shape (cin_pad: pmx_pk_cin_pad of the
+// layer's kind, pmx_pk_t_cin_pad for a transposed layer).  pmx_pack_job_* describe one pack to write (total set, blk0 = 0): the direct pack
+// and bias of L from master weights; the transposed pack P of the layer (cout, cin, ks, kind) from its master weights; the Winograd pack and
+// conv1_1's fused-kernel pack from L's direct pack into dst.  A job is enqueued alone (pmx_pack_launch_one, by value) or as one of a device
+// table's (pmx_pack_launch_table: the jobs' blk0 ascending, `blocks` their sum).  pmx_unpack_launch: L's direct pack and bias -> (w OIHW | b).
+enum { PMX_PACK_DIRECT = 0, PMX_PACK_TRANSPOSED = 1, PMX_PACK_WINO = 2, PMX_PACK_CONV1 = 3, PMX_PACK_KINDS = 4 };
+void pmx_layer_geometry(PackedLayer& L, int cout, int cin, int ks, int cin_pad);
+PackJob pmx_pack_job_direct(const float* master, const PackedLayer& L, int kind);
+PackJob pmx_pack_job_transposed(const float* master, int cout, int cin, int ks, int kind, const PackedLayer& P);
+PackJob pmx_pack_job_wino(const PackedLayer& L, float* dst);
+PackJob pmx_pack_job_conv1(const PackedLayer& L, float* dst);
+int pmx_pack_launch_one(int kind, const PackJob& job, hipStream_t st);
+int pmx_pack_launch_table(int kind, const PackJob* d_jobs, int njobs, unsigned blocks, hipStream_t st);
+int pmx_unpack_launch(const PackedLayer& L, int kind, float* dst, hipStream_t st);

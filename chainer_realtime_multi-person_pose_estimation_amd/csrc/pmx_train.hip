@@ -1,6 +1,6 @@
 // pmx_train.hip -- the training steps of the C ABI: pmx_train_enable / pmx_train_set_adam / pmx_train_set_grad_scale /
 // pmx_train_step_head / pmx_train_step / pmx_get_layer / pmx_train_get_state / pmx_train_set_state / pmx_get_pack / pmx_adam_apply.  Semantics:
-// include/pose_mi355x.h; the stores' layout: pmx_ctx.h (TrainState, BwState::grad); where a weight lies in a pack: pack_index.h.
+// include/pose_mi355x.h; the stores' layout: pmx_ctx.h (TrainState, BwState::grad); every pack: pack_index.h, built by pmx_packs.hip.
 //
 // THE ADAM CONTRACT is this project's own restatement of Chainer's AdamRule (eta = 1, weight_decay_rate = 0) as a sequence of float32
 // operations, each rounded to nearest -- see adam_one below.  A CUDA build of Chainer may contract a multiply and an add into one FMA, so
@@ -77,137 +77,8 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_kernel(float* __restrict__ 
     }
 }
 
-// ---- packers: one thread per float of the pack, so the pad positions are written (+0.0f) like everything else --------------------------
-// A step makes ONE launch per kind of pack over all updated layers (direct + bias, transposed, Winograd, conv1_1's fused pack), each driven
-// by a table of PackJob that travels with the Adam table.  A job owns the blocks [blk0, next blk0), 256 floats of its pack each, so no block
-// straddles two layers; a block finds its job by the search the Adam kernel uses.  The table is read through indices that are uniform
-// over the block, so the loads are scalar.  Per float of a pack the arithmetic is that of the host packers.
-struct PackGeo { int cout, cin, T, kind, nch, cout_pad; };      // of the pack WRITTEN (nch chunks of 16 packed input channels)
-struct PackJob {
-    const float* src;      // direct / transposed: the layer's master weights (w OIHW | b); Winograd / conv1_1: the direct pack it derives from
-    float* dst;
-    float* bias;           // direct: the padded bias
-    PackGeo p;
-    int t_cout, ks;        // transposed: output channels of the transposed layer; Winograd: the kernel size
-    unsigned total, blk0;  // floats of the pack, first block of the job in the launch
-};
-
-__device__ __forceinline__ PackJob job_of_block(const PackJob* __restrict__ jobs, int njobs)
-{
-    int lo = 0, hi = njobs - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (jobs[mid].blk0 <= blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    return jobs[lo];
-}
-
-// master (w OIHW | b) -> the layer's direct pack and bias, as pack_weights does
-__global__ __launch_bounds__(256) void pack_direct_kernel(const PackJob* __restrict__ jobs, int njobs)
-{
-    const PackJob j = job_of_block(jobs, njobs);
-    const PackGeo p = j.p;
-    const float* __restrict__ w = j.src;
-    const unsigned idx = (blockIdx.x - j.blk0) * 256u + threadIdx.x;
-    if (idx >= j.total) return;
-    const int c = idx % PMX_PK_CK, n = (idx / PMX_PK_CK) % p.cout_pad;
-    const unsigned pc = idx / PMX_PK_CK / p.cout_pad;
-    const int ch = pc % p.nch, tap = pc / p.nch, k = ch * PMX_PK_CK + c;
-    const int src = pmx_pk_ref_of_packed(p.kind, k, p.cin);
-    j.dst[idx] = src >= 0 && n < p.cout ? w[pmx_pk_oihw(n, src, tap, p.cin, p.T)] : 0.0f;
-    if (idx < (unsigned)p.cout_pad) j.bias[idx] = idx < (unsigned)p.cout ? w[(size_t)p.cout * p.cin * p.T + idx] : 0.0f;
-}
-
-// master w -> the direct pack of the layer whose forward is the data gradient: output channel n = the layer's packed input channel, input
-// channel k = the layer's output channel, taps rotated by 180 degrees (conv_bwd_pack.h + pack_weights with the zero-padded g map).  p
-// describes the LAYER (cout, cin, T, kind); nch / cout_pad the transposed pack.
-__global__ __launch_bounds__(256) void pack_transposed_kernel(const PackJob* __restrict__ jobs, int njobs)
-{
-    const PackJob j = job_of_block(jobs, njobs);
-    const PackGeo p = j.p;
-    const float* __restrict__ w = j.src;
-    const unsigned idx = (blockIdx.x - j.blk0) * 256u + threadIdx.x;
-    if (idx >= j.total) return;
-    const int c = idx % PMX_PK_CK, n = (idx / PMX_PK_CK) % p.cout_pad;
-    const unsigned pc = idx / PMX_PK_CK / p.cout_pad;
-    const int ch = pc % p.nch, tap = pc / p.nch, k = ch * PMX_PK_CK + c;
-    const int src = n < j.t_cout ? pmx_pk_ref_of_packed(p.kind, n, p.cin) : -1;
-    j.dst[idx] = src >= 0 && k < p.cout ? w[pmx_pk_oihw(k, src, p.T - 1 - tap, p.cin, p.T)] : 0.0f;
-}
-
-// direct pack -> Winograd pack, as pack_wino does: double, the same association, rounded once
-__global__ __launch_bounds__(256) void pack_wino_kernel(const PackJob* __restrict__ jobs, int njobs)
-{
-    const PackJob j = job_of_block(jobs, njobs);
-    const float* __restrict__ wp = j.src;
-    const int ks = j.ks, nch16 = j.p.nch, cout_pad = j.p.cout_pad;
-    const unsigned idx = (blockIdx.x - j.blk0) * 256u + threadIdx.x;
-    if (idx >= j.total) return;
-    const int nch32 = nch16 * PMX_PK_CK / 32, nb32 = cout_pad / 32;
-    const int ci8 = idx % 8, n32 = (idx / 8) % 32, k8 = (idx / 256) % 4, nb = (idx / 1024) % nb32;
-    const unsigned pc = idx / 1024 / nb32;
-    const int c32 = pc % nch32, plane = pc / nch32;
-    const int n = nb * 32 + n32, ci = c32 * 32 + k8 * 8 + ci8;
-    const double Gm[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-    auto tapw = [&](int ky, int kx) -> double { return wp[pmx_pk_direct(ky * ks + kx, ci, n, nch16, cout_pad)]; };
-    double val;
-    if (plane < 64) {
-        const int sub = plane / 16, i = (plane % 16) / 4, jj = plane % 4;
-        double gg[3];
-        for (int kx = 0; kx < 3; ++kx)
-            gg[kx] = (Gm[i][0] * tapw(3 * (sub >> 1) + 0, 3 * (sub & 1) + kx) + Gm[i][1] * tapw(3 * (sub >> 1) + 1, 3 * (sub & 1) + kx)) +
-                     Gm[i][2] * tapw(3 * (sub >> 1) + 2, 3 * (sub & 1) + kx);
-        val = (gg[0] * Gm[jj][0] + gg[1] * Gm[jj][1]) + gg[2] * Gm[jj][2];
-    } else if (plane < 72) {
-        const int sub = (plane - 64) / 4, f = (plane - 64) % 4;
-        val = (Gm[f][0] * tapw(6, 3 * sub + 0) + Gm[f][1] * tapw(6, 3 * sub + 1)) + Gm[f][2] * tapw(6, 3 * sub + 2);
-    } else if (plane < 80) {
-        const int sub = (plane - 72) / 4, f = (plane - 72) % 4;
-        val = (Gm[f][0] * tapw(3 * sub + 0, 6) + Gm[f][1] * tapw(3 * sub + 1, 6)) + Gm[f][2] * tapw(3 * sub + 2, 6);
-    } else val = tapw(6, 6);
-    j.dst[idx] = (float)val;
-}
-
-// conv1_1's direct pack -> its fused-kernel pack, as pack_conv1 does (the 28th k of every channel: +0.0f)
-__global__ __launch_bounds__(256) void pack_conv1_kernel(const PackJob* __restrict__ jobs, int njobs)
-{
-    const PackJob j = job_of_block(jobs, njobs);
-    const unsigned idx = (blockIdx.x - j.blk0) * 256u + threadIdx.x;
-    if (idx >= j.total) return;
-    const long long src = pmx_pk_conv1_src((int)idx, j.p.cout_pad);
-    j.dst[idx] = src >= 0 ? j.src[src] : 0.0f;
-}
-
-// a layer's direct pack and bias -> (w OIHW, reference input order | b)
-__global__ __launch_bounds__(256) void unpack_kernel(const float* __restrict__ dw, const float* __restrict__ db, float* __restrict__ w, PackGeo p, unsigned total)
-{
-    const unsigned i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= total) return;
-    const unsigned nw = (unsigned)p.cout * p.cin * p.T;
-    if (i >= nw) { w[i] = db[i - nw]; return; }
-    const int tap = i % p.T, src = (i / p.T) % p.cin, n = i / p.T / p.cin;
-    w[i] = dw[pmx_pk_direct(tap, pmx_pk_packed_of_ref(p.kind, src), n, p.nch, p.cout_pad)];
-}
-
 #define TR_LAUNCHED(what) do { const hipError_t _e = hipGetLastError(); \
     if (_e != hipSuccess) { pmx_set_error("%s: launch failed: %s", what, hipGetErrorString(_e)); return PMX_ERR_HIP; } } while (0)
-
-unsigned blocks256(size_t total) { return (unsigned)((total + 255) / 256); }
-
-PackGeo geo_of(const pmx_ctx* c, const PackedLayer& L)
-{
-    return PackGeo{L.cout, L.cin, L.ks * L.ks, pmx_pack_kind(c, L.cin), L.nch, L.cout_pad};
-}
-size_t direct_floats(const PackedLayer& L) { return (size_t)L.ks * L.ks * L.nch * L.cout_pad * CK; }
-size_t wino_floats(const PackedLayer& L) { return (size_t)pmx_pk_wino_planes(L.ks) * (L.cin_pad / 32) * L.cout_pad * 32; }
-
-int launch_unpack(const pmx_ctx* c, const PackedLayer& L, float* dst, hipStream_t st)
-{
-    const size_t total = (size_t)L.cout * L.cin * L.ks * L.ks + L.cout;
-    unpack_kernel<<<blocks256(total), 256, 0, st>>>(L.d_w, L.d_b, dst, geo_of(c, L), (unsigned)total);
-    TR_LAUNCHED("unpack");
-    return PMX_OK;
-}
 
 // the stage of a head layer (0: conv4_3_CPM / conv4_4_CPM), -1 for a layer the head backward does not cover
 int head_stage(const pmx_ctx* c, int idx)
@@ -230,27 +101,28 @@ int trunk_pos(const pmx_ctx* c, int idx)
 bool has_segment(const pmx_ctx* c, int idx) { return head_stage(c, idx) >= 0 || trunk_pos(c, idx) >= 0; }
 
 // The tables of one step in the pinned block (and, at the same offsets, in its device copy): the Adam segments, then the jobs of the four
-// packer launches.  N = layers of the context; a layer gives at most one direct, one transposed and two Winograd jobs.
-enum { JOB_DIRECT = 0, JOB_TRANSPOSED = 1, JOB_WINO = 2, JOB_CONV1 = 3, JOB_KINDS = 4 };
-size_t jobs_at(size_t N, int kind) { return N * sizeof(AdamSeg) + (kind == JOB_DIRECT ? 0 : kind == JOB_TRANSPOSED ? N : kind == JOB_WINO ? 2 * N : 4 * N) * sizeof(PackJob); }
-size_t table_bytes(size_t N) { return jobs_at(N, JOB_CONV1) + sizeof(PackJob); }
-
-struct JobList { PackJob* job; int n = 0; unsigned blocks = 0; };
-void add_job(JobList& l, PackJob j, size_t total)
+// packer launches (pmx_packs.hip).  N = layers of the context; a layer gives at most one direct, one transposed and two Winograd jobs.
+size_t jobs_at(size_t N, int kind)
 {
-    j.total = (unsigned)total; j.blk0 = l.blocks;
+    return N * sizeof(AdamSeg) + (kind == PMX_PACK_DIRECT ? 0 : kind == PMX_PACK_TRANSPOSED ? N : kind == PMX_PACK_WINO ? 2 * N : 4 * N) * sizeof(PackJob);
+}
+size_t table_bytes(size_t N) { return jobs_at(N, PMX_PACK_CONV1) + sizeof(PackJob); }
+
+// a job owns the blocks [blk0, next blk0) of its launch, 256 floats of its pack each
+struct JobList { PackJob* job; int n = 0; unsigned blocks = 0; };
+void add_job(JobList& l, PackJob j)
+{
+    j.blk0 = l.blocks;
     l.job[l.n++] = j;
-    l.blocks += blocks256(total);
+    l.blocks += (j.total + 255) / 256;
 }
 
 int wino_job(JobList& l, const PackedLayer& L)
 {
-    const size_t total = wino_floats(L);
-    PMX_CHECK(L.d_ww.capacity() == total && L.cin_pad % 32 == 0 && L.cout_pad % 32 == 0, PMX_ERR_STATE,
-              "training step: a Winograd pack of %zu floats where %zu are expected", L.d_ww.capacity(), total);
-    PackJob j{};
-    j.src = L.d_w; j.dst = L.d_ww; j.ks = L.ks; j.p.nch = L.nch; j.p.cout_pad = L.cout_pad;
-    add_job(l, j, total);
+    const PackJob j = pmx_pack_job_wino(L, L.d_ww);
+    PMX_CHECK(L.d_ww.capacity() == j.total && L.cin_pad % 32 == 0 && L.cout_pad % 32 == 0, PMX_ERR_STATE,
+              "training step: a Winograd pack of %zu floats where %u are expected", L.d_ww.capacity(), j.total);
+    add_job(l, j);
     return PMX_OK;
 }
 
@@ -258,31 +130,24 @@ int wino_job(JobList& l, const PackedLayer& L)
 int repack_jobs(pmx_ctx* c, int idx, const float* w, JobList* jl)
 {
     const PackedLayer& L = c->layers[idx];
-    const PackGeo g = geo_of(c, L);
-    size_t total = direct_floats(L);
-    PMX_CHECK(L.d_w.capacity() == total && L.d_b.capacity() == (size_t)L.cout_pad, PMX_ERR_STATE, "training step: layer '%s': a pack of %zu floats where %zu are expected",
-              c->table[idx].name.c_str(), L.d_w.capacity(), total);
-    PackJob j{};
-    j.src = w; j.dst = L.d_w; j.bias = L.d_b; j.p = g;
-    add_job(jl[JOB_DIRECT], j, total);
+    const int kind = pmx_pack_kind(c, L.cin);
+    const PackJob j = pmx_pack_job_direct(w, L, kind);
+    PMX_CHECK(L.d_w.capacity() == j.total && L.d_b.capacity() == (size_t)L.cout_pad, PMX_ERR_STATE, "training step: layer '%s': a pack of %zu floats where %u are expected",
+              c->table[idx].name.c_str(), L.d_w.capacity(), j.total);
+    add_job(jl[PMX_PACK_DIRECT], j);
     int rc;
     if (L.d_ww && trunk_pos(c, idx) == 0) {      // conv1_1's Winograd slot holds its fused-kernel pack
         PMX_CHECK(L.d_ww.capacity() == (size_t)PMX_PK_CONV1_FLOATS && L.nch == 1 && L.cout_pad == 64, PMX_ERR_STATE,
                   "training step: conv1_1's fused-kernel pack has %zu floats where %d are expected", L.d_ww.capacity(), PMX_PK_CONV1_FLOATS);
-        PackJob jc{};
-        jc.src = L.d_w; jc.dst = L.d_ww; jc.p = g;
-        add_job(jl[JOB_CONV1], jc, PMX_PK_CONV1_FLOATS);
-    } else if (L.d_ww && (rc = wino_job(jl[JOB_WINO], L))) return rc;
+        add_job(jl[PMX_PACK_CONV1], pmx_pack_job_conv1(L, L.d_ww));
+    } else if (L.d_ww && (rc = wino_job(jl[PMX_PACK_WINO], L))) return rc;
     if ((size_t)idx >= c->bw.tl.size() || !c->bw.tl[idx].set) return PMX_OK;
     const PackedLayer& P = c->bw.tl[idx];
-    total = direct_floats(P);
-    const int t_cout = pmx_pk_t_cout(g.kind, L.cin);
-    PMX_CHECK(P.d_w.capacity() == total && P.cout == t_cout && P.cin_pad == pmx_pk_t_cin_pad(L.cout), PMX_ERR_STATE,
+    const PackJob jt = pmx_pack_job_transposed(w, L.cout, L.cin, L.ks, kind, P);
+    PMX_CHECK(P.d_w.capacity() == jt.total && P.cout == pmx_pk_t_cout(kind, L.cin) && P.cin_pad == pmx_pk_t_cin_pad(L.cout), PMX_ERR_STATE,
               "training step: layer '%s': a transposed pack of another shape", c->table[idx].name.c_str());
-    PackJob jt{};
-    jt.src = w; jt.dst = P.d_w; jt.p = g; jt.p.nch = P.nch; jt.p.cout_pad = P.cout_pad; jt.t_cout = t_cout;
-    add_job(jl[JOB_TRANSPOSED], jt, total);
-    if (P.d_ww && (rc = wino_job(jl[JOB_WINO], P))) return rc;
+    add_job(jl[PMX_PACK_TRANSPOSED], jt);
+    if (P.d_ww && (rc = wino_job(jl[PMX_PACK_WINO], P))) return rc;
     return PMX_OK;
 }
 
@@ -341,18 +206,9 @@ void pmx_train_free(pmx_ctx* c)
     tr.on = 0;
 }
 
-int pmx_train_on_set_layer(pmx_ctx* c, int layer, const float* w, const float* bias)
+float* pmx_train_master(const pmx_ctx* c, int layer)
 {
-    if (!has_segment(c, layer)) return PMX_OK;      // (a trunk layer in mode 1: no segment, no step ever touches it)
-    const LayerDesc& d = c->table[layer];
-    const size_t nw = (size_t)d.cout * d.cin * d.ks * d.ks;
-    float* dst = c->tr.w + c->bw.grad_off[layer];
-    c->layers[layer].busy = true; c->layers[layer].busy_stream = c->stream;
-    // (pmx_set_layer has synchronised the stream)
-    PMX_HIP(hipMemcpy(dst, w, nw * sizeof(float), hipMemcpyHostToDevice));
-    if (bias) PMX_HIP(hipMemcpy(dst + nw, bias, (size_t)d.cout * sizeof(float), hipMemcpyHostToDevice));
-    else PMX_HIP(hipMemset(dst + nw, 0, (size_t)d.cout * sizeof(float)));
-    return PMX_OK;
+    return c->tr.on && has_segment(c, layer) ? c->tr.w + c->bw.grad_off[layer] : nullptr;      // (a trunk layer in mode 1: no segment, no step ever touches it)
 }
 
 extern "C" int pmx_train_enable(pmx_ctx* c, int on)
@@ -384,7 +240,7 @@ extern "C" int pmx_train_enable(pmx_ctx* c, int on)
     PMX_HIP(hipMemsetAsync(tr.m, 0, total * sizeof(float), st));
     PMX_HIP(hipMemsetAsync(tr.v, 0, total * sizeof(float), st));
     for (size_t i = 0; i < c->layers.size(); ++i)
-        if (has_segment(c, (int)i) && (rc = launch_unpack(c, c->layers[i], tr.w + c->bw.grad_off[i], st))) {
+        if (has_segment(c, (int)i) && (rc = pmx_unpack_launch(c->layers[i], pmx_pack_kind(c, c->layers[i].cin), tr.w + c->bw.grad_off[i], st))) {
             (void)hipStreamSynchronize(st);
             tr.w.reset(); tr.m.reset(); tr.v.reset(); tr.seg_dev.reset(); tr.seg_host.reset();
             return rc;
@@ -435,8 +291,8 @@ static int train_step(pmx_ctx* c, const char* who, bool full)
     char* const host = tr.seg_host.get();
     const char* const dev = tr.seg_dev.get();
     AdamSeg* seg = reinterpret_cast<AdamSeg*>(host);
-    JobList jl[JOB_KINDS];
-    for (int k = 0; k < JOB_KINDS; ++k) jl[k].job = reinterpret_cast<PackJob*>(host + jobs_at(N, k));
+    JobList jl[PMX_PACK_KINDS];
+    for (int k = 0; k < PMX_PACK_KINDS; ++k) jl[k].job = reinterpret_cast<PackJob*>(host + jobs_at(N, k));
     auto updated = [&](int i) {      // (a stage that "stop_stage" cut off received no gradient; the trunk always does)
         const int stage = head_stage(c, i);
         return stage >= 0 ? stage <= bw.stages : full && trunk_pos(c, i) >= 0;
@@ -469,28 +325,10 @@ static int train_step(pmx_ctx* c, const char* who, bool full)
     if (int r = pmx_prof_end(c)) return r;
     if (rc) return rc;
     // the packers, in the order of their inputs: the direct and transposed packs read the master weights, the Winograd and conv1_1 packs the
-    // direct packs just written
+    // direct packs just written (the order of PMX_PACK_*)
     if ((rc = pmx_prof_begin(c, "train_step|pack", 0))) return rc;
-    rc = [&]() -> int {
-        auto d_jobs = [&](int k) { return reinterpret_cast<const PackJob*>(dev + jobs_at(N, k)); };
-        if (jl[JOB_DIRECT].n) {
-            pack_direct_kernel<<<jl[JOB_DIRECT].blocks, 256, 0, st>>>(d_jobs(JOB_DIRECT), jl[JOB_DIRECT].n);
-            TR_LAUNCHED("pack_direct");
-        }
-        if (jl[JOB_TRANSPOSED].n) {
-            pack_transposed_kernel<<<jl[JOB_TRANSPOSED].blocks, 256, 0, st>>>(d_jobs(JOB_TRANSPOSED), jl[JOB_TRANSPOSED].n);
-            TR_LAUNCHED("pack_transposed");
-        }
-        if (jl[JOB_WINO].n) {
-            pack_wino_kernel<<<jl[JOB_WINO].blocks, 256, 0, st>>>(d_jobs(JOB_WINO), jl[JOB_WINO].n);
-            TR_LAUNCHED("pack_wino");
-        }
-        if (jl[JOB_CONV1].n) {
-            pack_conv1_kernel<<<jl[JOB_CONV1].blocks, 256, 0, st>>>(d_jobs(JOB_CONV1), jl[JOB_CONV1].n);
-            TR_LAUNCHED("pack_conv1");
-        }
-        return PMX_OK;
-    }();
+    for (int k = 0; k < PMX_PACK_KINDS && !rc; ++k)
+        if (jl[k].n) rc = pmx_pack_launch_table(k, reinterpret_cast<const PackJob*>(dev + jobs_at(N, k)), jl[k].n, jl[k].blocks, st);
     if (int r = pmx_prof_end(c)) return r;
     return rc;
 }
@@ -510,11 +348,10 @@ extern "C" int pmx_get_layer(pmx_ctx* c, const char* name, float* w_oihw, float*
     PMX_DEV(c);
     const size_t nw = (size_t)L.cout * L.cin * L.ks * L.ks;
     DevBuf<float> tmp;
-    const float* src;
-    if (c->tr.on && head_stage(c, idx) >= 0) src = c->tr.w + c->bw.grad_off[idx];
-    else {
+    const float* src = pmx_train_master(c, idx);
+    if (!src) {
         int rc;
-        if ((rc = tmp.alloc(nw + L.cout)) || (rc = launch_unpack(c, L, tmp, c->stream))) return rc;
+        if ((rc = tmp.alloc(nw + L.cout)) || (rc = pmx_unpack_launch(L, pmx_pack_kind(c, L.cin), tmp, c->stream))) return rc;
         src = tmp;
     }
     PMX_HIP(hipStreamSynchronize(c->stream));

@@ -28,14 +28,14 @@ HEADER = os.path.join(os.path.dirname(HERE), 'include', 'pose_mi355x.h')
 SOURCES = [('pmx_api.hip', []), ('pmx_precise.hip', []), ('pmx_multi.hip', []), ('pmx_precise_images.hip', ['-ffp-contract=off']), ('conv_mfma.hip', []), ('conv_wino.hip', ['-mllvm', '-pragma-unroll-threshold=200000']), ('conv1_wino.hip', []), ('conv_f16.hip', []), ('conv_select.hip', []), ('prep.hip', ['-ffp-contract=off']),
            ('postproc.hip', ['-ffp-contract=off']), ('pmx_boxes.hip', ['-ffp-contract=off']), ('pmx_loss.hip', ['-ffp-contract=off']),
            ('pmx_samples.hip', ['-ffp-contract=off']), ('conv_bwd.hip', ['-ffp-contract=off']),
-           ('pmx_backward.hip', ['-ffp-contract=off']),
+           ('pmx_backward.hip', ['-ffp-contract=off']), ('pmx_packs.hip', ['-ffp-contract=off']),
            ('pmx_train.hip', ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt'])]
 # the opt-in bf16x3 kernels (option "precision" = 1; DESIGN.md 4.1.5: frozen, slower than the fp32 Winograd path) are NOT part of the
 # default library: PMX_BUILD_BF16X3=1 in the environment of the build adds their translation unit (the stamp then differs, so the
 # library is rebuilt when the variable changes)
 if os.environ.get('PMX_BUILD_BF16X3', '') not in ('', '0'):
     SOURCES.append(('conv_bf16x3.hip', []))
-HEADERS = ['pmx_common.h', 'pmx_ctx.h', 'pp_tables.h', 'wino_util.h', 'conv_direct.h', 'pp_smooth.h', 'conv_bwd_pack.h', 'pack_index.h', 'wgrad_strips.h', 'f16_round.h', HEADER]
+HEADERS = ['pmx_common.h', 'pmx_ctx.h', 'pp_tables.h', 'wino_util.h', 'conv_direct.h', 'pp_smooth.h', 'pack_index.h', 'wgrad_strips.h', 'f16_round.h', HEADER]
 
 N_JOINTS, N_LIMBS, N_PAF, N_HEAT = 18, 19, 38, 19
 # the detectors' precision= keyword -> engine option "precision" (include/pose_mi355x.h): fp32 (default), bf16x3 (opt-in build), f16 mode

@@ -595,7 +595,7 @@ int pmx_conv2d_backward(pmx_ctx* ctx, const float* x_nchw, const float* w_oihw, 
  *   db   as pmx_conv2d_backward
  *   dw   as pmx_conv2d_backward (the same kernel, the same order per element, strips cut from the batch * h/8 image rows; option
  *        "wgrad_strips"), OIHW; for Mconv1_* in the REFERENCE's input order 38 PAF, 19 heat, 128 feature
- *   dx   the dispatcher on g with the transposed, 180-degree-rotated pack (built on the host on the first backward, kept per layer, dropped
+ *   dx   the dispatcher on g with the transposed, 180-degree-rotated pack (built by the device packers on the first backward, kept per layer, dropped
  *        by pmx_set_layer), two branches per launch where the forward has two; the packs of Mconv1_* write concat-buffer order, zeros in
  *        the pad channels
  * THE SUMS.  Every step is one float32 add, left to right:
@@ -721,9 +721,9 @@ int pmx_pool_backward_test(pmx_ctx* ctx, const float* a_nchw, const float* u_nch
  *      off keep their weights, packs, moments and t (this project's rule: a parameter without a gradient is not updated);
  *   2. Adam over all those layers in ONE launch (a per-segment table, sent through pinned memory; the call waits only if the previous
  *      step's table copy has not finished);
- *   3. the packers: every pack of an updated layer that EXISTS is rewritten in place, same pointer, with the bits the host packers produce
- *      from the same OIHW weights -- the direct pack and bias (pmx_set_layer), the Winograd pack, the transposed 180-degree-rotated pack of
- *      the data gradient and its Winograd pack.  A pack that does not exist is not created: its lazy host builder makes it on first use
+ *   3. the packers: every pack of an updated layer that EXISTS is rewritten in place, same pointer, with the bits a one-off build gives
+ *      from the same OIHW weights (csrc/pack_index.h defines every float of every pack) -- the direct pack and bias (pmx_set_layer), the Winograd pack, the transposed 180-degree-rotated pack of
+ *      the data gradient and its Winograd pack.  A pack that does not exist is not created: its lazy builder makes it on first use
  *      from the then-current direct pack, after waiting for the stream.  The f16 / bf16x3 packs of an updated layer are marked stale and
  *      rebuilt in place when a forward in that mode next needs them.  ONE launch per kind of pack serves all updated layers (direct + bias,
  *      transposed, Winograd of both, conv1_1's fused-kernel pack): four launches at most, driven by per-layer tables that travel with

@@ -116,7 +116,7 @@ def conv_wino(x, w, b, relu=False, pool=False, unit_g=0, unit_from=0, run_tx=Non
 
 # ---- the whole network in the kernels' order ---------------------------------------------------------------------------
 # Stage inputs are the "cat" buffer of the HIP path: [feature 0..127 | PAF 128..165 | 0, 0 | heat 168..186 | 0 x 5]
-# (csrc/pmx_api.hip::concat_map); the reference concatenates (PAF, heat, feature) (models/CocoPoseNet.py:168).  K is walked
+# (csrc/pack_index.h::pmx_pk_ref_of_packed, kind 1); the reference concatenates (PAF, heat, feature) (models/CocoPoseNet.py:168).  K is walked
 # in buffer order, so the Mconv1 weights are permuted (and zero-padded) accordingly.
 CAT_C, CAT_PAF, CAT_HEAT = 192, 128, 168
 

@@ -1,5 +1,5 @@
-/* conv_bwd_pack.h -- host side of pmx_conv2d_backward that needs no device: the layer whose FORWARD is the data gradient.  Plain C, so that
- * the tests can compile it into a stand-alone program. */
+/* conv_bwd_pack.h -- the layer whose FORWARD is a convolution's data gradient, as an independent host restatement of the library's transposed
+ * pack (csrc/pack_index.h::pmx_pk_transposed_value): the tests' stand-alone programs compile it.  Plain C. */
 #ifndef PMX_CONV_BWD_PACK_H
 #define PMX_CONV_BWD_PACK_H
 #include <stddef.h>

@@ -51,7 +51,7 @@ def twin_lib():
 
 
 def build_main(out_dir, name, extra):
-    """The stand-alone program (its own main: twin + the host-side weight repacking of csrc/conv_bwd_pack.h) -> path of the executable."""
+    """The stand-alone program (its own main: twin + the host restatement of the weight repacking, tests/conv_bwd_pack.h) -> path of the executable."""
     exe = os.path.join(str(out_dir), name)
     cmd = [_cc(), '-O1', '-g', '-ffp-contract=off', '-Wall', '-Wextra', '-Werror', '-I', CSRC] + list(extra) + [MAIN_SRC, TWIN_SRC, '-o', exe, '-lm']
     r = subprocess.run(cmd, capture_output=True, text=True)

@@ -1,4 +1,4 @@
-/* conv_flip_cat_main.c -- stand-alone driver of csrc/conv_bwd_pack.h::pmx_conv_flip_weights_mapped: the layer whose forward is the data
+/* conv_flip_cat_main.c -- stand-alone driver of conv_bwd_pack.h::pmx_conv_flip_weights_mapped: the layer whose forward is the data
  * gradient of a 185-input layer (Mconv1_*), with its output channels in the concat buffer's order.  Fixed pseudo-random weights; the map,
  * the weights and the result are printed (the floats as hexadecimal words).  The tests build it once plainly and once with
  * -fsanitize=address,undefined; the two must print the same bytes. */

@@ -1,5 +1,5 @@
 /* conv_wgrad_main.c -- stand-alone driver of the weight-gradient twin (conv_wgrad_twin.c) and of the host-side repacking of the data
- * gradient's layer (csrc/conv_bwd_pack.h): fixed pseudo-random cases, every result printed as hexadecimal words.  The tests build it once
+ * gradient's layer (conv_bwd_pack.h): fixed pseudo-random cases, every result printed as hexadecimal words.  The tests build it once
  * plainly and once with -fsanitize=address,undefined; the two must print the same bytes. */
 #include <stdint.h>
 #include <stdio.h>

@@ -13,7 +13,7 @@ def cat_of_ref():
 
 
 def ref_of_cat():
-    """(192,) the reference channel a concat-buffer channel holds, -1 for the pad channels (pmx_api.hip::concat_map)"""
+    """(192,) the reference channel a concat-buffer channel holds, -1 for the pad channels (csrc/pack_index.h::pmx_pk_ref_of_packed, kind 1)"""
     m = np.full(CAT_C, -1)
     m[cat_of_ref()] = np.arange(REF_C)
     return m
@@ -38,7 +38,7 @@ def to_cat(a_ref, axis=1):
 
 def flip_weights_cat(w):
     """OIHW (cout, 185, k, k) -> (192, cout, k, k): the transposed, 180-degree-rotated layer with its output channels in concat-buffer order,
-    zero rows for the pad channels (csrc/conv_bwd_pack.h::pmx_conv_flip_weights_mapped)"""
+    zero rows for the pad channels (tests/conv_bwd_pack.h::pmx_conv_flip_weights_mapped)"""
     import conv_bwd_ref as R
     return np.ascontiguousarray(to_cat(R.flip_weights(w), axis=0))
 

@@ -1,6 +1,6 @@
 """GPU: the head training step (include/pose_mi355x.h: pmx_train_*) -- Adam on the 82 layers after conv4_2 and the weight packs rewritten on
 the device.  The Adam launch bit for bit against tests/adam_twin.py from the library's own gradients; every pack bit for bit against the
-packs a fresh context builds on the host from the fetched weights; what a step must not touch; the loss trajectory of five steps against
+packs a fresh context builds by one-off launches from the fetched weights; what a step must not touch; the loss trajectory of five steps against
 float64 torch; the state round trip; the error codes.  Batch 2 at 64 x 48 (the network fixes the weight shapes)."""
 import ctypes as C
 import hashlib
@@ -193,7 +193,7 @@ def seq(native):
 @pytest.fixture(scope='module')
 def fresh(native, seq):
     """A context that never trains: it gets the weights the training context holds after step 3 through pmx_set_layer and builds every
-    pack on the host, lazily, under the same options.  Made when the training context stands at step 3, with what the tests compare: the
+    pack by a one-off launch, lazily, under the same options.  Made when the training context stands at step 3, with what the tests compare: the
     next forward + backward of both contexts under conv_algo 2 and 0, and every pack of every head layer of both."""
     seq.upto(3)
     assert len(seq.records) == 3          # (every test that goes further asks for this fixture first)
@@ -257,7 +257,7 @@ def test_adam_kernel_on_crafted_segments(seq):
 
 
 # ---- 2. pack bits ------------------------------------------------------------------------------------------------------------------------
-def test_every_pack_equals_the_host_packers(seq, fresh):
+def test_every_pack_equals_one_off_launches(seq, fresh):
     mine, theirs = fresh.packs
     exist = {k: sum(mine[(nm, k)] is not None for nm in seq.head) for k in PACKS}
     print('packs in existence', exist)
@@ -289,7 +289,7 @@ def test_stop_stage_keeps_the_later_stages(seq, fresh):
     assert not _diff_packs({k: v for k, v in now.items() if k[0] in late}, {k: v for k, v in seq.packs3.items() if k[0] in late})
     assert len(_diff_packs({k: v for k, v in now.items() if k[0] in rec['names'] and k[1] == 'w'},
                            {k: v for k, v in seq.packs3.items() if k[0] in rec['names'] and k[1] == 'w'})) == len(rec['names'])
-    for nm in rec['names']:          # the fresh context follows through pmx_set_layer and rebuilds its packs on the host
+    for nm in rec['names']:          # the fresh context follows through pmx_set_layer and rebuilds its packs by one-off launches
         fresh.set_layer(nm, *e.get_layer(nm))
     b = _fb(fresh, stages=2, grads=True)
     assert not _diff_packs(now, _packs(fresh, seq.head)), _diff_packs(now, _packs(fresh, seq.head))[:10]

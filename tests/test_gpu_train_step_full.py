@@ -1,8 +1,9 @@
 """GPU: the full-network training step (include/pose_mi355x.h: pmx_train_step) -- Adam on all 92 layers with a step count per layer, and
 every pack of every layer rewritten on the device by the table-driven packers.  The Adam launch bit for bit against tests/adam_twin.py from
 the library's own gradients, head and trunk at different t; every pack of all 92 layers -- conv1_1's fused-kernel pack and conv1_2's
-Winograd pack among them -- bit for bit against the packs a fresh context builds on the host; the next forward and backward against that
-context's; what a head-only step between full steps must leave alone; five steps of PoseDetector with the trunk trainable against float64
+Winograd pack among them -- bit for bit against the packs a fresh context builds by one-off launches of the same packers, and those against
+the NumPy restatement tests/pack_ref.py (as are the concat layers of a facenet and a handnet context); the next forward and backward
+against that context's; what a head-only step between full steps must leave alone; five steps of PoseDetector with the trunk trainable against float64
 torch; the switch from head-only training, the state round trip, train_loop and the error codes.  Batch 2 at 64 x 48, and 3 x 40 x 56
 where partial tiles at every level matter.  Option "conv1_wino" = 2 makes the un-retained forward of these small batches run the fused
 stem kernel that reads conv1_1's fused-kernel pack (by the launch-size rule only batches that fill the chip do)."""
@@ -10,6 +11,7 @@ import numpy as np
 import pytest
 
 import adam_twin as A
+import pack_ref
 import test_gpu_head_backward as HB
 import test_gpu_train_step as TS
 import train_full_ref as TF
@@ -151,11 +153,13 @@ def seq(native):
 @pytest.fixture(scope='module')
 def fresh(native, seq):
     """A context that never trains: it gets the weights the training context holds after step 4 through pmx_set_layer and builds every
-    pack on the host, lazily, by the same calls.  Made when the training context stands at step 4, with what the tests compare: every
+    pack by a one-off launch of its packer, lazily, by the same calls.  Made when the training context stands at step 4, with what the tests compare: every
     pack of all 92 layers of both, and the next forwards and backwards of both under conv_algo 1, 0 and 2."""
     seq.upto(4)
     assert len(seq.records) == 4          # (every test that goes further asks for this fixture first)
-    e = _engine(native, weights=seq.eng.get_weights(), train=False)
+    given = seq.eng.get_weights()
+    e = _engine(native, weights=given, train=False)
+    e.given = given
     e.first = _build_packs(e)
     e.packs = (TS._packs(seq.eng, seq.all), TS._packs(e, seq.all))
     e.cmp = {}
@@ -218,7 +222,8 @@ def test_adam_kernel_on_92_segments_keeps_the_pads(seq):
 
 
 # ---- 2. pack bits ------------------------------------------------------------------------------------------------------------------------------
-def test_every_pack_of_every_layer_equals_the_host_packers(seq, fresh):
+def test_every_pack_of_every_layer_equals_one_off_launches(seq, fresh):
+    """the step's in-place job-table launches against the packs a fresh context builds from the same weights, one launch per pack"""
     mine, theirs = fresh.packs
     exist = {k: sum(mine[(nm, k)] is not None for nm in seq.all) for k in PACKS}
     print('packs in existence', exist)
@@ -237,6 +242,38 @@ def test_every_pack_of_every_layer_equals_the_host_packers(seq, fresh):
     assert not k[:, 13, 1].any() and k[:, :13].any()          # the 28th k of every channel is zero, the rest is not
     w0 = _weights()
     assert all(not _same(seq.state[nm][0], w0[nm][0]) for nm in seq.all)          # (and none of it is the untrained network's)
+
+
+def test_every_pack_of_a_fresh_context_equals_numpy(seq, fresh):
+    """Every pack of all 92 layers of the fresh context -- direct, bias, Winograd, transposed, its Winograd pack, conv1_1's fused-kernel
+    pack -- against tests/pack_ref.py applied to the weights it was given: every float, pads included, bit for bit."""
+    _, theirs = fresh.packs
+    compared = 0
+    for nm in seq.all:
+        W, b = fresh.given[nm]
+        want = pack_ref.layer_packs(W, b, 1 if W.shape[1] == 185 else 0)
+        for k in PACKS:
+            got = theirs[(nm, k)]
+            if got is not None:
+                assert k in want and _same(got, want[k]), (nm, k)
+                compared += 1
+    wino = sum(seq.eng.layer_shape(nm)[-1] > 1 for nm in seq.head)
+    assert compared == 92 + 92 + (wino + 10) + 91 + (wino + 7)
+
+
+@pytest.mark.parametrize('arch,C', [('facenet', 71), ('handnet', 22)])
+def test_concat_layer_packs_of_face_and_hand_equal_numpy(native, arch, C):
+    """the first 7x7 layer of stage 2 (cin = C heat + 128 feature channels, packed as [feature | heat | pad]): direct pack and bias"""
+    rng = np.random.default_rng(C)
+    W = rng.normal(0, 0.05, (128, 128 + C, 7, 7)).astype('f')
+    b = rng.normal(0, 0.05, 128).astype('f')
+    e = native.Engine(0, max_batch=1, max_h=8, max_w=8, arch=arch)
+    try:
+        e.set_layer('Mconv1_stage2', W, b)
+        want = pack_ref.direct_pack(W, b, 2 + C)
+        assert _same(e.get_pack('Mconv1_stage2', 'w'), want[0]) and _same(e.get_pack('Mconv1_stage2', 'b'), want[1])
+    finally:
+        e.close()
 
 
 # ---- 3. the next forward and backward -------------------------------------------------------------------------------------------------------------

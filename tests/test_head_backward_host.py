@@ -1,6 +1,6 @@
 """CPU: the host side of the head backward (include/pose_mi355x.h: pmx_backward_head).  The NumPy twin of the documented sums and of the
 Mconv1 channel map (tests/head_backward_twin.py) on examples where a wrong order or a wrong permutation changes the result; the transposed
-pack in concat-buffer order from a stand-alone program (tests/conv_flip_cat_main.c + csrc/conv_bwd_pack.h, host compiler), built plainly and
+pack in concat-buffer order from a stand-alone program (tests/conv_flip_cat_main.c + tests/conv_bwd_pack.h, host compiler), built plainly and
 with -fsanitize=address,undefined; the C ABI surface."""
 import os
 import re

@@ -1,7 +1,7 @@
 """Host side of the head training step, no GPU: the NumPy twin of the Adam contract (tests/adam_twin.py) against a float64 evaluation of
-Chainer's formula, alpha_t against its closed form, the zero-gradient case, and the index arithmetic the host and device weight packers
-share (csrc/pack_index.h, through the stand-alone program tests/pack_index_main.c) against NumPy restatements of pack_weights /
-concat_map / the transposed pack / pack_wino's layout."""
+Chainer's formula, alpha_t against its closed form, the zero-gradient case, and the definition of the weight packs the device packers
+evaluate (csrc/pack_index.h, through the stand-alone program tests/pack_index_main.c): its index arithmetic and, on seeded weights, every
+float of every pack bit for bit against the NumPy restatement tests/pack_ref.py."""
 import math
 import os
 import shutil
@@ -12,6 +12,7 @@ import pytest
 
 import adam_twin as A
 import conv_bwd_ref as R
+import pack_ref as P
 from conftest import pkg
 
 ENTRIES = ['pmx_train_enable', 'pmx_train_set_adam', 'pmx_train_set_grad_scale', 'pmx_train_step_head', 'pmx_get_layer',
@@ -72,7 +73,7 @@ def _index_program(tmp_path_factory):
     cc = shutil.which('gcc') or shutil.which('cc')
     assert cc, 'no host C compiler'
     exe = os.path.join(str(tmp_path_factory.mktemp('pack_index')), 'pack_index_main')
-    r = subprocess.run([cc, '-O1', '-g', '-Wall', '-Wextra', '-Werror', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-I', R.CSRC,
+    r = subprocess.run([cc, '-O1', '-g', '-ffp-contract=off', '-Wall', '-Wextra', '-Werror', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-I', R.CSRC,
                         os.path.join(R.HERE, 'pack_index_main.c'), '-o', exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     return exe
@@ -83,26 +84,6 @@ def index_exe(tmp_path_factory):
     return _index_program(tmp_path_factory)
 
 
-def _concat_map():
-    """pmx_api.hip::concat_map restated: concat-buffer channel -> the reference's input channel of Mconv1_* (38 PAF, 19 heat, 128 feature)"""
-    m = np.full(192, -1)
-    m[0:128] = 57 + np.arange(128)
-    m[128:128 + 38] = np.arange(38)
-    m[168:168 + 19] = 38 + np.arange(19)
-    return m
-
-
-def _pack_weights(w, cin_map, cout_pad):
-    """pmx_api.hip::pack_weights restated: OIHW ids -> [tap][chunk][cout_pad][16], -1 where the host packer leaves its zero"""
-    cout, cin, T = w.shape
-    nch = len(cin_map) // 16
-    wp = np.full((T, nch, cout_pad, 16), -1, np.int64)
-    for k, src in enumerate(cin_map):
-        if src >= 0:
-            wp[:, k // 16, :cout, k % 16] = w[:, src, :].T
-    return wp.reshape(-1)
-
-
 @pytest.mark.parametrize('cout,cin,ks,kind', [(128, 128, 3, 0), (128, 185, 7, 1), (38, 512, 1, 0)])
 def test_index_maps_against_numpy_packers(index_exe, cout, cin, ks, kind):
     T = ks * ks
@@ -110,26 +91,23 @@ def test_index_maps_against_numpy_packers(index_exe, cout, cin, ks, kind):
     assert r.returncode == 0, r.stderr[-2000:]
     words = np.frombuffer(r.stdout, np.int64)
     nch, cout_pad, cin_pad, t_nch, t_cout_pad, t_cout, planes = words[:7]
-    cmap = _concat_map() if kind == 1 else np.concatenate([np.arange(cin), np.full((-cin) % 16, -1)])
+    cmap = P.channel_map(kind, cin)
     assert cout_pad == (64 if cout <= 64 else -(-cout // 128) * 128) and cin_pad == len(cmap) and nch * 16 == cin_pad
     assert np.array_equal(words[7:7 + cin_pad], cmap)
     nw = cout * cin * T
     pairs = words[7 + cin_pad:7 + cin_pad + 2 * nw].reshape(nw, 2)
     ids = np.arange(nw, dtype=np.int64).reshape(cout, cin, T)
     # the forward pack
-    wp = _pack_weights(ids, cmap, cout_pad)
+    wp = P.pack_weights(ids, cmap, cout_pad)
     assert np.array_equal(wp[pairs[:, 0]], ids.reshape(-1)) and (wp >= 0).sum() == nw
-    # the transposed pack: conv_bwd_pack.h (transposed, rotated by 180 degrees, rows in the packed order of the layer's input) through
-    # pack_weights with the g map (cout channels, padded to 64 at least)
-    wt = np.full((len(cmap) if kind == 1 else cin, cout, T), -1, np.int64)
-    for k in range(wt.shape[0]):
-        if cmap[k] >= 0:
-            wt[k] = ids[:, cmap[k], ::-1]
+    # the transposed pack: transposed, rotated by 180 degrees, rows in the packed order of the layer's input, through pack_weights with the
+    # g map (cout channels, padded to 64 at least)
+    wt = P.transposed_weights(ids, cmap, len(cmap) if kind == 1 else cin)
     gmap = np.concatenate([np.arange(cout), np.full(max(64, -(-cout // 16) * 16) - cout, -1)])
     assert t_cout == wt.shape[0] and t_nch * 16 == len(gmap)
-    wpt = _pack_weights(wt, gmap, t_cout_pad)
+    wpt = P.pack_weights(wt, gmap, t_cout_pad)
     assert np.array_equal(wpt[pairs[:, 1]], ids.reshape(-1)) and (wpt >= 0).sum() == nw
-    # the Winograd pack's layout (pack_wino's `put`): [plane][chunk32][cout_pad / 32][k8-step][32][8]
+    # the Winograd pack's layout: [plane][chunk32][cout_pad / 32][k8-step][32][8]
     if ks > 1:
         wi = words[7 + cin_pad + 2 * nw:].reshape(planes, cout_pad, cin_pad)
         assert planes == (16 if ks == 3 else 81)
@@ -141,6 +119,38 @@ def test_index_maps_against_numpy_packers(index_exe, cout, cin, ks, kind):
         assert planes == 0 and len(words) == 7 + cin_pad + 2 * nw
 
 
+@pytest.mark.parametrize('cout,cin,ks,kind', [(128, 128, 3, 0), (128, 185, 7, 1), (38, 512, 1, 0), (64, 3, 3, 0), (128, 199, 7, 2 + 71),
+                                              (128, 150, 7, 2 + 22), (100, 20, 3, 0), (19, 128, 1, 0)])
+def test_pack_values_against_numpy_packers(index_exe, tmp_path, cout, cin, ks, kind):
+    """Every float of every pack, pads included, from the header's value functions on seeded weights == tests/pack_ref.py, bit for bit: the
+    direct pack and bias, the transposed pack, the Winograd packs of both (float64, one rounding), conv1_1's fused-kernel pack; and the
+    un-pack of the direct pack is the identity."""
+    T = ks * ks
+    rng = np.random.default_rng(cout * 1000 + cin + ks)
+    W = rng.normal(0, 0.05, (cout, cin, ks, ks)).astype('f')
+    b = rng.normal(0, 0.05, cout).astype('f')
+    path = str(tmp_path / 'master.f32')
+    np.concatenate([W.reshape(-1), b]).tofile(path)
+    r = subprocess.run([index_exe, str(cout), str(cin), str(ks), str(kind), path], capture_output=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    cp, cin_pad = P.cout_pad(cout), len(P.channel_map(kind, cin))
+    words = 7 + cin_pad + 2 * cout * cin * T + (P.G.shape[0] ** 2 if ks == 3 else 81 if ks == 7 else 0) * cp * cin_pad
+    got = np.frombuffer(r.stdout[8 * words:], np.float32)
+    want = P.layer_packs(W, b, kind)
+    conv1 = (cout, cin, ks) == (64, 3, 3)          # ('wino' of that layer is its fused-kernel pack, emitted after the Winograd packs)
+    assert ('wino' in want) == (conv1 or (ks > 1 and cin_pad % 32 == 0)) and ('t_wino' in want) == (ks > 1 and max(64, -(-cout // 16) * 16) % 32 == 0)
+    assert want['wino'].size == 2 * 14 * 2 * 32 if conv1 else True
+    order = ['w', 'b', 't_w', 't_wino', 'wino'] if conv1 else ['w', 'b', 't_w', 'wino', 't_wino']
+    parts = [want[k] for k in order if k in want]
+    parts += [W.reshape(-1), b]
+    assert got.size == sum(x.size for x in parts)
+    at = 0
+    for i, x in enumerate(parts):
+        assert x.dtype == np.float32 and np.array_equal(got[at:at + x.size].view(np.uint32), x.view(np.uint32)), (i, x.size)
+        at += x.size
+    assert np.abs(want['w']).max() > 0 and (want['w'] == 0).sum() == want['w'].size - W.size
+
+
 def test_c_abi_surface():
     native = pkg('native')
     names = native.header_symbols()
@@ -148,4 +158,5 @@ def test_c_abi_surface():
         assert e in names, e
     srcs = dict(native.SOURCES)
     assert '-ffp-contract=off' in srcs['pmx_train.hip']
+    assert '-ffp-contract=off' in srcs['pmx_packs.hip']          # (the Winograd transform's double multiplies and adds stay apart)
     assert 'pack_index.h' in native.HEADERS

@@ -2,7 +2,7 @@
  * would have -- input transform V = B^T d B in float32 (fixed order: rows first, zero coefficients skipped, fmaf chains in index
  * order), per frequency one SEQUENTIAL fmaf chain over the input channels (what v_mfma_f32_32x32x2_f32 does with its k's,
  * tools/mfma_order.hip), output transform Y = A^T M A in float32 (fixed order).  The transformed weights U = G g G^T come from the host
- * (computed in double, rounded once), as pmx_api.hip::pack_wino does for F(2x2, 3x3).
+ * (computed in double, rounded once), as csrc/pack_index.h::pmx_pk_wino_value does for F(2x2, 3x3).
  * tools/wino_f4_check.py drives it: per-layer error against a float64 convolution next to the direct fp32 chain and F(2x2, 3x3).
  * n = m + 2 points; BT is n x n, AT is m x n (row-major); tf64 = 1: the input transform is computed in double and rounded once. */
 #include <math.h>

@@ -11,7 +11,7 @@ stream after `warmup` untimed ones (images on the device):
       own: the profiler's events slow everything else down), and a device-to-device hipMemcpyAsync that moves the same bytes as the Adam
       launch (28 per parameter: a copy of 14 bytes per parameter, read once and written once) -- the yardstick of its bandwidth
   (d) the host route the step replaces, by wall clock: every gradient fetched, Adam in NumPy, 82 x pmx_set_layer, and the next forward +
-      backward, which rebuilds the derived packs on the host
+      backward, which rebuilds the derived packs (one-off launches of the device packers)
 
     python tools/train_step_time.py [--full] [--no-host] [--iters N] [--warmup N] [--rounds N] [--batches 10,32] [--out PATH]"""
 import argparse
