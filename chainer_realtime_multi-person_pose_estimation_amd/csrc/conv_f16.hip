@@ -12,8 +12,8 @@
 // waves of two tiles each.  MFMA row m of tile t <-> pixel of 2 x 2 window (8 t + m / 4): the pool happens on the four registers of a
 // window, as in conv_direct.h.  Activations stay fp32 NHWC in HBM; the halo of one 16-channel chunk is converted to f16 while it is
 // staged into LDS ([row][pixel][16 ch] f16, 32 bytes per pixel, rows padded by 16 bytes so that the two pixel rows a 16-lane group of
-// ds_read_b128 touches fall on different bank halves: conflict-free), double-buffered, one barrier per chunk.  Weights (rounded once on
-// the host, [tap][chunk][cout_pad][16] f16 = the fp32 pack's layout) come straight from L2, one tap ahead.
+// ds_read_b128 touches fall on different bank halves: conflict-free), double-buffered, one barrier per chunk.  Weights (rounded once by
+// the f16 packer of pmx_packs.hip, [tap][chunk][cout_pad][16] f16 = the fp32 pack's layout) come straight from L2, one tap ahead.
 // LDS per MFMA (BN = 128): 1 KiB of A per wave and MFMA, 4 waves -> 4 KiB per 32 cycles = 128 B/clk/CU, half the 256 B/clk of ds_read_b128.
 #include "conv_direct.h"
 

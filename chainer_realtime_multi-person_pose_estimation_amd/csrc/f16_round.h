@@ -1,14 +1,21 @@
-/* f16_round.h -- the f16 mode's f16(v) on the host (option "precision" = 2, include/pose_mi355x.h): fp32 -> f16 bits, round-to-nearest-even,
- * saturating at +-65504; NaN stays NaN.  pmx_api.hip rounds the weights of a layer with it once (pack_f16); conv_f16_kernel rounds the
- * activations the same way on the device.  Plain C, no dependency: tests/f16_round_main.c compiles it with the host compiler and compares
- * it with numpy.float16 over every f16 value, its neighbours and every midpoint (tests/test_f16_host.py). */
+/* f16_round.h -- the f16 mode's f16(v) (option "precision" = 2, include/pose_mi355x.h): fp32 -> f16 bits, round-to-nearest-even, saturating
+ * at +-65504; NaN stays NaN.  The f16 weight pack is this function of the direct pack, float by float (pack_index.h::pmx_pk_f16_value,
+ * evaluated on the device by pmx_packs.hip); conv_f16_kernel rounds the activations the same way.  Plain C, no dependency, and under hipcc
+ * callable from both sides: tests/f16_round_main.c compiles it with the host compiler and compares it with numpy.float16 over every f16
+ * value, its neighbours and every midpoint (tests/test_f16_host.py). */
 #ifndef PMX_F16_ROUND_H
 #define PMX_F16_ROUND_H
 
 #include <stdint.h>
 #include <string.h>
 
-static inline uint16_t f16_rn_sat(float x)
+#if defined(__HIPCC__)
+#define PMX_HD __host__ __device__
+#else
+#define PMX_HD
+#endif
+
+static inline PMX_HD uint16_t f16_rn_sat(float x)
 {
     uint32_t u;
     memcpy(&u, &x, 4);

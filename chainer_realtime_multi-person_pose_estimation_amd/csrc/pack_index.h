@@ -1,16 +1,12 @@
-/* pack_index.h -- the definition of every weight pack: where a weight goes (the index functions) and, per float of a pack, what it holds as a
- * function of the pack's source (the value functions at the end).  The device packers (pmx_packs.hip) are `dst[idx] = value(idx)` over these;
- * the tests compile the header into a stand-alone host program.  Plain C; every function is `static inline` and, under hipcc, callable from
- * both sides. */
+/* pack_index.h -- the definition of every weight pack: where a weight goes (the index functions) and, per element of a pack, what it holds
+ * as a function of the pack's source (the value functions at the end).  The device packers (pmx_packs.hip) are `dst[idx] = value(idx)` over
+ * these; the tests compile the header into a stand-alone host program.  Plain C; every function is `static inline` and, under hipcc,
+ * callable from both sides (PMX_HD, f16_round.h). */
 #ifndef PMX_PACK_INDEX_H
 #define PMX_PACK_INDEX_H
 #include <stddef.h>
 
-#if defined(__HIPCC__)
-#define PMX_HD __host__ __device__
-#else
-#define PMX_HD
-#endif
+#include "f16_round.h"
 
 #define PMX_PK_CK 16              /* input channels per chunk of the direct pack */
 #define PMX_PK_CAT_C 192          /* channels of the pose network's concat buffer: [feature 128 | PAF 38, 2 pad | heat 19, 5 pad] */
@@ -72,17 +68,18 @@ static inline PMX_HD long long pmx_pk_conv1_src(int idx, int cout_pad)
     return k < 27 ? (long long)pmx_pk_direct(k / 3, k % 3, hf * 32 + n, 1, cout_pad) : -1;
 }
 
-/* ---- the value of float idx of every pack ------------------------------------------------------------------------------------------------
- * One evaluation per float of the pack, so the pad positions are written (+0.0f) like everything else.  A PackJob names one pack to write:
- * a step's table-driven launch gives a job the blocks [blk0, next blk0), 256 floats of its pack each; a one-off build is a single job. */
+/* ---- the value of element idx of every pack ----------------------------------------------------------------------------------------------
+ * One evaluation per element of the pack (a float; a uint16 of the f16 and bf16x3 packs), so the pad positions are written (+0) like
+ * everything else.  A PackJob names one pack to write: a step's table-driven launch gives a job the blocks [blk0, next blk0), 256 elements
+ * of its pack each; a one-off build is a single job. */
 typedef struct { int cout, cin, T, kind, nch, cout_pad; } PackGeo;      /* of the pack WRITTEN (nch chunks of 16 packed input channels) */
 typedef struct {
-    const float* src;      /* direct / transposed: the layer's master weights (w OIHW | b); Winograd / conv1_1: the direct pack it derives from */
-    float* dst;
+    const float* src;      /* direct / transposed: the layer's master weights (w OIHW | b); every other pack: the direct pack it derives from */
+    void* dst;             /* float; f16 / bf16x3: uint16_t */
     float* bias;           /* direct: the padded bias */
     PackGeo p;
     int t_cout, ks;        /* transposed: output channels of the transposed layer; Winograd: the kernel size */
-    unsigned total, blk0;  /* floats of the pack, first block of the job in the launch */
+    unsigned total, blk0;  /* elements of the pack, first block of the job in the launch */
 } PackJob;
 
 /* master (w OIHW | b) -> the layer's direct pack and its padded bias (idx < cout_pad) */
@@ -147,6 +144,38 @@ static inline PMX_HD float pmx_pk_wino_value(const PackJob* j, unsigned idx)
     } else val = PMX_PK_TAPW(6, 6);
 #undef PMX_PK_TAPW
     return (float)val;
+}
+
+/* direct pack -> f16 pack, the direct pack's own layout [tap][chunk][cout_pad][16] (so the concat channel map comes along) */
+static inline PMX_HD uint16_t pmx_pk_f16_value(const PackJob* j, unsigned idx) { return f16_rn_sat(j->src[idx]); }
+
+/* fp32 -> bf16 bits, round-to-nearest-even (a NaN stays one: | 0x40), and back */
+static inline PMX_HD uint16_t bf16_rn(float x)
+{
+    uint32_t u;
+    memcpy(&u, &x, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
+    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+static inline PMX_HD float bf16_f(uint16_t h)
+{
+    const uint32_t u = (uint32_t)h << 16;
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+/* direct pack -> bf16x3 pack [tap][chunk][plane hi|mid|lo][cout_pad][16]: three bf16 terms of every weight, each the rounding of what the
+ * terms before it leave (fp32 subtractions), as conv_bf16x3_kernel splits the activations */
+static inline PMX_HD uint16_t pmx_pk_bf16x3_value(const PackJob* j, unsigned idx)
+{
+    const unsigned k = idx % PMX_PK_CK, n = (idx / PMX_PK_CK) % j->p.cout_pad;
+    const unsigned pp = idx / PMX_PK_CK / j->p.cout_pad, plane = pp % 3, pc = pp / 3;
+    const float x = j->src[((size_t)pc * j->p.cout_pad + n) * PMX_PK_CK + k];
+    const uint16_t h = bf16_rn(x);
+    if (plane == 0) return h;
+    { const float r1 = x - bf16_f(h);
+      const uint16_t m = bf16_rn(r1);
+      return plane == 1 ? m : bf16_rn(r1 - bf16_f(m)); }
 }
 
 /* conv1_1's direct pack -> its fused-kernel pack (the 28th k of every channel: +0.0f) */

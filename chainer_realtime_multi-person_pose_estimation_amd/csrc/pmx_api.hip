@@ -6,7 +6,6 @@
 //   of a stage are the two groups (blockIdx.z) of one launch; F.concat (:168,...) is replaced by channel-slice
 //   writes into the 192-channel "cat" buffer (layout in pmx_common.h).
 #include "pmx_ctx.h"
-#include "f16_round.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -88,45 +87,6 @@ static std::vector<LayerDesc> make_layer_table()   // models/CocoPoseNet.py:26-1
 
 
 static int cout_pad_of(int cout) { return pmx_pk_cout_pad(cout); }
-
-// fp32 -> three bf16 terms, each the round-to-nearest-even bf16 of what is left (as conv_bf16x3_kernel splits the activations)
-static inline uint16_t bf16_rn(float x)
-{
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-static inline float bf16_f(uint16_t h)
-{
-    const uint32_t u = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-// packed fp32 weights [tap][chunk][cout_pad][16] -> bf16x3 [tap][chunk][plane][cout_pad][16]
-static void pack_bf16x3(const std::vector<float>& wp, int T, int nch, int cout_pad, std::vector<uint16_t>& out)
-{
-    out.assign((size_t)T * nch * 3 * cout_pad * CK, 0);
-    for (size_t pc = 0; pc < (size_t)T * nch; ++pc)
-        for (int n = 0; n < cout_pad; ++n)
-            for (int k = 0; k < CK; ++k) {
-                const float x = wp[(pc * cout_pad + n) * CK + k];
-                const uint16_t h = bf16_rn(x);
-                const float r1 = x - bf16_f(h);
-                const uint16_t m = bf16_rn(r1);
-                const uint16_t l = bf16_rn(r1 - bf16_f(m));
-                const size_t base = pc * 3 * cout_pad * CK + (size_t)n * CK + k;
-                out[base] = h; out[base + (size_t)cout_pad * CK] = m; out[base + 2 * (size_t)cout_pad * CK] = l;
-            }
-}
-
-// packed fp32 weights [tap][chunk][cout_pad][16] -> f16 in the same layout (so the concat channel map comes along)
-static void pack_f16(const std::vector<float>& wp, std::vector<uint16_t>& out)
-{
-    out.resize(wp.size());
-    for (size_t i = 0; i < wp.size(); ++i) out[i] = f16_rn_sat(wp[i]);
-}
 
 // the channel map of a layer's input (pack_index.h): the concat layers of the pose network (1) and of the face / hand networks (2 + C), else 0
 int pmx_pack_kind(const pmx_ctx* c, int cin) { return c->kind == NET_POSE ? (cin == 185 ? 1 : 0) : cin == c->n_heat + 128 ? 2 + c->n_heat : 0; }
@@ -457,7 +417,6 @@ extern "C" int pmx_set_layer(pmx_ctx* c, const char* name, const float* w, const
     L.d_w3.reset(); L.d_w16.reset(); L.d_ww.reset();
     if ((size_t)it->second < c->bw.tl.size()) c->bw.tl[it->second] = PackedLayer();      // the data-gradient pack of the old weights
     L.set = true;
-    L.stale16 = L.stale3 = false;
     return PMX_OK;
 }
 
@@ -471,65 +430,29 @@ extern "C" int pmx_weights_missing(pmx_ctx* c, int* n)
 }
 
 // ------------------------------------------------------------------------------------------ forward
-// Derived weight packs, built from the device-resident packed fp32 weights when a kernel first needs them.  The f16 and bf16x3 packs are
-// rounded on the host: fetch, `pack`, allocate, copy.
-// The slot takes the buffer only once the copy is complete: a failed copy must not leave a non-null pointer to garbage behind.
-template <typename T, typename Pack>
-static int derive_pack(const PackedLayer& L, DevBuf<T>& slot, const char* what, Pack pack, bool stale = false)
+// Derived weight packs -- Winograd, f16, bf16x3, conv1_1's fused-kernel pack (which lives in conv1_1's otherwise unused Winograd slot) --
+// are built on the device from the direct pack when a kernel first needs them: allocate, launch the kind's packer for job `j` on the
+// context's current stream, wait for it.  The slot takes the buffer only when it is complete: a failure leaves no pointer to garbage
+// behind, and the lanes of detect_precise may share the pack from their own streams as soon as this returns.
+template <typename T>
+static int derive_on_device(pmx_ctx* c, const PackedLayer& L, int kind, DevBuf<T>& slot, PackJob j)
 {
-    if (slot && !stale) return PMX_OK;
-    if (L.busy) PMX_HIP(hipStreamSynchronize(L.busy_stream));      // a training step may still be writing d_w (or reading the stale pack)
-    std::vector<float> wp((size_t)L.ks * L.ks * L.nch * L.cout_pad * CK);
-    PMX_HIP(hipMemcpy(wp.data(), L.d_w, wp.size() * sizeof(float), hipMemcpyDeviceToHost));
-    std::vector<T> out;
-    pack(wp, out);
-    if (slot) {      // stale: the same buffer, the same pointer
-        PMX_CHECK(slot.capacity() == out.size(), PMX_ERR_STATE, "%s weight pack: %zu elements held, %zu needed", what, slot.capacity(), out.size());
-        PMX_HIP(hipMemcpy(slot, out.data(), out.size() * sizeof(T), hipMemcpyHostToDevice));
-        return PMX_OK;
-    }
+    if (slot) return PMX_OK;
+    if (L.busy) PMX_HIP(hipStreamSynchronize(L.busy_stream));      // a training step may still be writing d_w
     DevBuf<T> d;
-    if (int rc = d.alloc(out.size())) return rc;
-    if (hipMemcpy(d, out.data(), out.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
-        pmx_set_error("%s weight pack: host-to-device copy failed: %s", what, hipGetErrorString(hipGetLastError()));
-        return PMX_ERR_HIP;
-    }
+    int rc;
+    if ((rc = d.alloc(j.total))) return rc;
+    j.dst = d.get();
+    if ((rc = pmx_pack_launch_one(kind, j, c->stream))) return rc;
+    PMX_HIP(hipStreamSynchronize(c->stream));
     slot = std::move(d);
     return PMX_OK;
 }
-// The Winograd pack and conv1_1's fused-kernel pack (which lives in conv1_1's otherwise unused Winograd slot) are built on the device from
-// the direct pack: allocate, launch on the context's current stream, wait for it.  derive_pack's rule holds: the slot takes the buffer only
-// when it is complete, so the lanes of detect_precise may share the pack from their own streams as soon as this returns.
-static int derive_on_device(pmx_ctx* c, PackedLayer& L, int kind)
-{
-    if (L.d_ww) return PMX_OK;
-    if (L.busy) PMX_HIP(hipStreamSynchronize(L.busy_stream));      // a training step may still be writing d_w
-    PackJob j = kind == PMX_PACK_WINO ? pmx_pack_job_wino(L, nullptr) : pmx_pack_job_conv1(L, nullptr);
-    DevBuf<float> d;
-    int rc;
-    if ((rc = d.alloc(j.total))) return rc;
-    j.dst = d;
-    if ((rc = pmx_pack_launch_one(kind, j, c->stream))) return rc;
-    PMX_HIP(hipStreamSynchronize(c->stream));
-    L.d_ww = std::move(d);
-    return PMX_OK;
-}
-static int ensure_wino_pack(pmx_ctx* c, PackedLayer& L) { return derive_on_device(c, L, PMX_PACK_WINO); }
-static int ensure_conv1_pack(pmx_ctx* c, PackedLayer& L) { return derive_on_device(c, L, PMX_PACK_CONV1); }
-static int ensure_bf16x3_pack(pmx_ctx*, PackedLayer& L)
-{
-    const int rc = derive_pack(L, L.d_w3, "bf16x3", [&](const std::vector<float>& wp, std::vector<uint16_t>& o) { pack_bf16x3(wp, L.ks * L.ks, L.nch, L.cout_pad, o); },
-                               L.stale3);
-    if (!rc) L.stale3 = false;
-    return rc;
-}
+static int ensure_wino_pack(pmx_ctx* c, PackedLayer& L) { return derive_on_device(c, L, PMX_PACK_WINO, L.d_ww, pmx_pack_job_wino(L, nullptr)); }
+static int ensure_conv1_pack(pmx_ctx* c, PackedLayer& L) { return derive_on_device(c, L, PMX_PACK_CONV1, L.d_ww, pmx_pack_job_conv1(L, nullptr)); }
+static int ensure_bf16x3_pack(pmx_ctx* c, PackedLayer& L) { return derive_on_device(c, L, PMX_PACK_BF16X3, L.d_w3, pmx_pack_job_bf16x3(L, nullptr)); }
 // the f16 pack (half the fp32 weights' bytes): every 3x3 / 7x7 layer in f16 mode
-static int ensure_f16_pack(pmx_ctx*, PackedLayer& L)
-{
-    const int rc = derive_pack(L, L.d_w16, "f16", pack_f16, L.stale16);
-    if (!rc) L.stale16 = false;
-    return rc;
-}
+static int ensure_f16_pack(pmx_ctx* c, PackedLayer& L) { return derive_on_device(c, L, PMX_PACK_F16, L.d_w16, pmx_pack_job_f16(L, nullptr)); }
 
 // Launches one convolution (1 or 2 groups) whose ConvArgs describe the FINAL result (real bias, ReLU, pool, output slices).
 // With S > 1 K slices the slice blocks write raw partial sums into the context's slab scratch and conv_splitk_reduce

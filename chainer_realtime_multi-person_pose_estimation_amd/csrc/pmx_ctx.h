@@ -66,13 +66,12 @@ struct PackedLayer {
     bool set = false;
     DevBuf<float> d_w, d_b;
     DevBuf<float> d_ww;          // Winograd F(2x2,3x3) pack [freq 16][chunk32][cout_pad][32] = G g G^T (3x3 layers; option "conv_algo" = 1)
-    DevBuf<uint16_t> d_w3;       // bf16x3 pack [tap][chunk][plane hi|mid|lo][cout_pad][16] (3x3 / 7x7 layers; option "precision" = 1)
-    DevBuf<uint16_t> d_w16;      // f16 pack [tap][chunk][cout_pad][16] (3x3 / 7x7 layers; option "precision" = 2)
+    DevBuf<uint16_t> d_w3;       // bf16x3 pack [tap][chunk][plane hi|mid|lo][cout_pad][16] of d_w (3x3 / 7x7 layers; option "precision" = 1)
+    DevBuf<uint16_t> d_w16;      // f16 pack [tap][chunk][cout_pad][16] of d_w (3x3 / 7x7 layers; option "precision" = 2)
     int cin = 0, cout = 0, ks = 0, cin_pad = 0, cout_pad = 0, nch = 0;
-    // training (pmx_train.hip): a step rewrites d_w on `busy_stream` without telling the host, so a lazy builder that reads d_w with a
-    // blocking copy waits for that stream first (busy); the f16 / bf16x3 packs of a layer a step has updated are rebuilt in place, in their
-    // existing buffers, at their next ensure_* (nothing is freed in the middle of an enqueued chain)
-    bool busy = false, stale16 = false, stale3 = false;
+    // training (pmx_train.hip): a step rewrites d_w, and every derived pack that exists, in place on `busy_stream` without telling the
+    // host, so a lazy builder that derives a pack from d_w on another stream waits for that stream first (busy)
+    bool busy = false;
     hipStream_t busy_stream = nullptr;
 };
 
@@ -438,12 +437,18 @@ float* pmx_train_master(const pmx_ctx* c, int layer);
 void pmx_train_free(pmx_ctx* c);
 // pmx_packs.hip: the packers, the only way a pack gets built.  pmx_layer_geometry fills a layer's shape (cin_pad: pmx_pk_cin_pad of the
 // layer's kind, pmx_pk_t_cin_pad for a transposed layer).  pmx_pack_job_* describe one pack to write (total set, blk0 = 0): the direct pack
-// and bias of L from master weights; the transposed pack P of the layer (cout, cin, ks, kind) from its master weights; the Winograd pack and
-// conv1_1's fused-kernel pack from L's direct pack into dst.  A job is enqueued alone (pmx_pack_launch_one, by value) or as one of a device
-// table's (pmx_pack_launch_table: the jobs' blk0 ascending, `blocks` their sum).  pmx_unpack_launch: L's direct pack and bias -> (w OIHW | b).
-enum { PMX_PACK_DIRECT = 0, PMX_PACK_TRANSPOSED = 1, PMX_PACK_WINO = 2, PMX_PACK_CONV1 = 3, PMX_PACK_KINDS = 4 };
+// and bias of L from master weights; the transposed pack P of the layer (cout, cin, ks, kind) from its master weights; the f16, bf16x3 and
+// Winograd packs and conv1_1's fused-kernel pack from L's direct pack into dst.  A job is enqueued alone (pmx_pack_launch_one, by value) or
+// as one of a device table's (pmx_pack_launch_table: the jobs' blk0 ascending, `blocks` their sum).  pmx_unpack_launch: L's direct pack and
+// bias -> (w OIHW | b).
+// The kinds in launch order: what reads a direct pack comes after PMX_PACK_DIRECT.  PMX_PACK_JOBS_PER_LAYER: the jobs of a kind one layer
+// gives a step's table at most (Winograd: its own pack and its transposed layer's); 0: one job per context (conv1_1's).
+enum { PMX_PACK_DIRECT = 0, PMX_PACK_F16, PMX_PACK_BF16X3, PMX_PACK_TRANSPOSED, PMX_PACK_WINO, PMX_PACK_CONV1, PMX_PACK_KINDS };
+constexpr int PMX_PACK_JOBS_PER_LAYER[PMX_PACK_KINDS] = {1, 1, 1, 1, 2, 0};
 void pmx_layer_geometry(PackedLayer& L, int cout, int cin, int ks, int cin_pad);
 PackJob pmx_pack_job_direct(const float* master, const PackedLayer& L, int kind);
+PackJob pmx_pack_job_f16(const PackedLayer& L, uint16_t* dst);
+PackJob pmx_pack_job_bf16x3(const PackedLayer& L, uint16_t* dst);
 PackJob pmx_pack_job_transposed(const float* master, int cout, int cin, int ks, int kind, const PackedLayer& P);
 PackJob pmx_pack_job_wino(const PackedLayer& L, float* dst);
 PackJob pmx_pack_job_conv1(const PackedLayer& L, float* dst);

@@ -1,10 +1,10 @@
-// pmx_packs.hip -- the weight packers: the only place a direct, transposed, Winograd or conv1_1 fused-kernel pack gets built, and the un-pack
-// back to OIHW.  One thread per float of a pack, `dst[idx] = value(idx)` over the definitions in pack_index.h, so the pad positions are
-// written (+0.0f) like everything else.  This unit is compiled with -ffp-contract=off: the Winograd transform is a sequence of double
-// multiplies and adds, each rounded (pack_index.h::pmx_pk_wino_value).
+// pmx_packs.hip -- the weight packers: the only place a pack of PackedLayer gets built -- direct, f16, bf16x3, transposed, Winograd, conv1_1's
+// fused-kernel pack -- and the un-pack back to OIHW.  One thread per element of a pack, `dst[idx] = value(idx)` over the definitions in
+// pack_index.h, so the pad positions are written (+0) like everything else.  This unit is compiled with -ffp-contract=off: the Winograd
+// transform is a sequence of double multiplies and adds, each rounded (pack_index.h::pmx_pk_wino_value).
 //
 // A training step makes ONE launch per kind of pack over all updated layers, driven by a table of PackJob on the device: a job owns the
-// blocks [blk0, next blk0), 256 floats of its pack each, so no block straddles two layers; a block finds its job by the search the Adam
+// blocks [blk0, next blk0), 256 elements of its pack each, so no block straddles two layers; a block finds its job by the search the Adam
 // kernel uses, through indices that are uniform over the block, so the loads are scalar.  A one-off build (pmx_set_layer, the lazy builders,
 // the single-layer entries) passes its single job by value: no table, no allocation, no upload.
 #include "pmx_ctx.h"
@@ -26,13 +26,17 @@ __device__ __forceinline__ void pack_block(const PackJob& j)
 {
     const unsigned idx = (blockIdx.x - j.blk0) * 256u + threadIdx.x;
     if (idx >= j.total) return;
+    float* const f = static_cast<float*>(j.dst);
+    uint16_t* const h = static_cast<uint16_t*>(j.dst);
     if (KIND == PMX_PACK_DIRECT) {
-        j.dst[idx] = pmx_pk_direct_value(&j, idx);
+        f[idx] = pmx_pk_direct_value(&j, idx);
         if (idx < (unsigned)j.p.cout_pad) j.bias[idx] = pmx_pk_bias_value(&j, idx);
     }
-    else if (KIND == PMX_PACK_TRANSPOSED) j.dst[idx] = pmx_pk_transposed_value(&j, idx);
-    else if (KIND == PMX_PACK_WINO) j.dst[idx] = pmx_pk_wino_value(&j, idx);
-    else j.dst[idx] = pmx_pk_conv1_value(&j, idx);
+    else if (KIND == PMX_PACK_F16) h[idx] = pmx_pk_f16_value(&j, idx);
+    else if (KIND == PMX_PACK_BF16X3) h[idx] = pmx_pk_bf16x3_value(&j, idx);
+    else if (KIND == PMX_PACK_TRANSPOSED) f[idx] = pmx_pk_transposed_value(&j, idx);
+    else if (KIND == PMX_PACK_WINO) f[idx] = pmx_pk_wino_value(&j, idx);
+    else f[idx] = pmx_pk_conv1_value(&j, idx);
 }
 
 template <int KIND>
@@ -56,7 +60,7 @@ int launched(const char* what)
     return PMX_ERR_HIP;
 }
 
-const char* const kind_name[PMX_PACK_KINDS] = {"pack_direct", "pack_transposed", "pack_wino", "pack_conv1"};
+const char* const kind_name[PMX_PACK_KINDS] = {"pack_direct", "pack_f16", "pack_bf16x3", "pack_transposed", "pack_wino", "pack_conv1"};
 
 size_t direct_floats(const PackedLayer& L) { return (size_t)L.ks * L.ks * L.nch * L.cout_pad * CK; }
 
@@ -87,6 +91,22 @@ PackJob pmx_pack_job_transposed(const float* master, int cout, int cin, int ks, 
     return j;
 }
 
+PackJob pmx_pack_job_f16(const PackedLayer& L, uint16_t* dst)
+{
+    PackJob j{};
+    j.src = L.d_w; j.dst = dst;
+    j.total = (unsigned)direct_floats(L);
+    return j;
+}
+
+PackJob pmx_pack_job_bf16x3(const PackedLayer& L, uint16_t* dst)
+{
+    PackJob j{};
+    j.src = L.d_w; j.dst = dst; j.p.cout_pad = L.cout_pad;
+    j.total = 3 * (unsigned)direct_floats(L);
+    return j;
+}
+
 PackJob pmx_pack_job_wino(const PackedLayer& L, float* dst)
 {
     PackJob j{};
@@ -106,6 +126,8 @@ PackJob pmx_pack_job_conv1(const PackedLayer& L, float* dst)
 int pmx_pack_launch_table(int kind, const PackJob* d_jobs, int njobs, unsigned blocks, hipStream_t st)
 {
     if (kind == PMX_PACK_DIRECT) pack_table_kernel<PMX_PACK_DIRECT><<<blocks, 256, 0, st>>>(d_jobs, njobs);
+    else if (kind == PMX_PACK_F16) pack_table_kernel<PMX_PACK_F16><<<blocks, 256, 0, st>>>(d_jobs, njobs);
+    else if (kind == PMX_PACK_BF16X3) pack_table_kernel<PMX_PACK_BF16X3><<<blocks, 256, 0, st>>>(d_jobs, njobs);
     else if (kind == PMX_PACK_TRANSPOSED) pack_table_kernel<PMX_PACK_TRANSPOSED><<<blocks, 256, 0, st>>>(d_jobs, njobs);
     else if (kind == PMX_PACK_WINO) pack_table_kernel<PMX_PACK_WINO><<<blocks, 256, 0, st>>>(d_jobs, njobs);
     else pack_table_kernel<PMX_PACK_CONV1><<<blocks, 256, 0, st>>>(d_jobs, njobs);
@@ -116,6 +138,8 @@ int pmx_pack_launch_one(int kind, const PackJob& job, hipStream_t st)
 {
     const unsigned blocks = blocks256(job.total);
     if (kind == PMX_PACK_DIRECT) pack_one_kernel<PMX_PACK_DIRECT><<<blocks, 256, 0, st>>>(job);
+    else if (kind == PMX_PACK_F16) pack_one_kernel<PMX_PACK_F16><<<blocks, 256, 0, st>>>(job);
+    else if (kind == PMX_PACK_BF16X3) pack_one_kernel<PMX_PACK_BF16X3><<<blocks, 256, 0, st>>>(job);
     else if (kind == PMX_PACK_TRANSPOSED) pack_one_kernel<PMX_PACK_TRANSPOSED><<<blocks, 256, 0, st>>>(job);
     else if (kind == PMX_PACK_WINO) pack_one_kernel<PMX_PACK_WINO><<<blocks, 256, 0, st>>>(job);
     else pack_one_kernel<PMX_PACK_CONV1><<<blocks, 256, 0, st>>>(job);

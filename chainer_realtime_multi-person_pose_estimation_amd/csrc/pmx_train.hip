@@ -100,13 +100,15 @@ int trunk_pos(const pmx_ctx* c, int idx)
 // a layer with a segment in the stores: the 82 head layers, in mode 2 the ten trunk layers as well
 bool has_segment(const pmx_ctx* c, int idx) { return head_stage(c, idx) >= 0 || trunk_pos(c, idx) >= 0; }
 
-// The tables of one step in the pinned block (and, at the same offsets, in its device copy): the Adam segments, then the jobs of the four
-// packer launches (pmx_packs.hip).  N = layers of the context; a layer gives at most one direct, one transposed and two Winograd jobs.
+// The tables of one step in the pinned block (and, at the same offsets, in its device copy): the Adam segments, then the jobs of the
+// packer launches kind by kind (pmx_packs.hip), each kind with room for what N layers can give it (PMX_PACK_JOBS_PER_LAYER).
 size_t jobs_at(size_t N, int kind)
 {
-    return N * sizeof(AdamSeg) + (kind == PMX_PACK_DIRECT ? 0 : kind == PMX_PACK_TRANSPOSED ? N : kind == PMX_PACK_WINO ? 2 * N : 4 * N) * sizeof(PackJob);
+    size_t jobs = 0;
+    for (int k = 0; k < kind; ++k) jobs += PMX_PACK_JOBS_PER_LAYER[k] ? PMX_PACK_JOBS_PER_LAYER[k] * N : 1;
+    return N * sizeof(AdamSeg) + jobs * sizeof(PackJob);
 }
-size_t table_bytes(size_t N) { return jobs_at(N, PMX_PACK_CONV1) + sizeof(PackJob); }
+size_t table_bytes(size_t N) { return jobs_at(N, PMX_PACK_KINDS); }
 
 // a job owns the blocks [blk0, next blk0) of its launch, 256 floats of its pack each
 struct JobList { PackJob* job; int n = 0; unsigned blocks = 0; };
@@ -117,13 +119,19 @@ void add_job(JobList& l, PackJob j)
     l.blocks += (j.total + 255) / 256;
 }
 
-int wino_job(JobList& l, const PackedLayer& L)
+// a pack derived from a direct pack, rewritten in the buffer of `held` elements that holds it
+int derived_job(JobList& l, const PackJob& j, size_t held, const char* what)
 {
-    const PackJob j = pmx_pack_job_wino(L, L.d_ww);
-    PMX_CHECK(L.d_ww.capacity() == j.total && L.cin_pad % 32 == 0 && L.cout_pad % 32 == 0, PMX_ERR_STATE,
-              "training step: a Winograd pack of %zu floats where %u are expected", L.d_ww.capacity(), j.total);
+    PMX_CHECK(held == j.total, PMX_ERR_STATE, "training step: %s pack of %zu elements where %u are expected", what, held, j.total);
     add_job(l, j);
     return PMX_OK;
+}
+
+int wino_job(JobList& l, const PackedLayer& L)
+{
+    PMX_CHECK(L.cin_pad % 32 == 0 && L.cout_pad % 32 == 0, PMX_ERR_STATE, "training step: a Winograd pack of a layer with %d x %d padded channels",
+              L.cout_pad, L.cin_pad);
+    return derived_job(l, pmx_pack_job_wino(L, L.d_ww), L.d_ww.capacity(), "a Winograd");
 }
 
 // the jobs of every pack of layer `idx` that exists, from the master weights at `w`; nothing is enqueued and no flag is set
@@ -136,6 +144,8 @@ int repack_jobs(pmx_ctx* c, int idx, const float* w, JobList* jl)
               c->table[idx].name.c_str(), L.d_w.capacity(), j.total);
     add_job(jl[PMX_PACK_DIRECT], j);
     int rc;
+    if (L.d_w16 && (rc = derived_job(jl[PMX_PACK_F16], pmx_pack_job_f16(L, L.d_w16), L.d_w16.capacity(), "an f16"))) return rc;
+    if (L.d_w3 && (rc = derived_job(jl[PMX_PACK_BF16X3], pmx_pack_job_bf16x3(L, L.d_w3), L.d_w3.capacity(), "a bf16x3"))) return rc;
     if (L.d_ww && trunk_pos(c, idx) == 0) {      // conv1_1's Winograd slot holds its fused-kernel pack
         PMX_CHECK(L.d_ww.capacity() == (size_t)PMX_PK_CONV1_FLOATS && L.nch == 1 && L.cout_pad == 64, PMX_ERR_STATE,
                   "training step: conv1_1's fused-kernel pack has %zu floats where %d are expected", L.d_ww.capacity(), PMX_PK_CONV1_FLOATS);
@@ -310,9 +320,6 @@ static int train_step(pmx_ctx* c, const char* who, bool full)
         seg[nseg++] = AdamSeg{(unsigned long long)bw.grad_off[i], n, blocks, tr.scale[i], alpha_t_of(tr, tr.t[i])};
         blocks += (n + ADAM_BLOCK_FLOATS - 1) / ADAM_BLOCK_FLOATS;
         bytes += 28.0 * n;
-        PackedLayer& L = c->layers[i];
-        L.stale16 = (bool)L.d_w16; L.stale3 = (bool)L.d_w3;
-        if (i < bw.tl.size() && bw.tl[i].set) { PackedLayer& P = bw.tl[i]; P.stale16 = (bool)P.d_w16; P.stale3 = (bool)P.d_w3; }
     }
     bw.stepped = true;
     mark_busy(c, true);
@@ -324,8 +331,8 @@ static int train_step(pmx_ctx* c, const char* who, bool full)
                      (float)(1.0 - tr.beta2), (float)tr.eps, st);
     if (int r = pmx_prof_end(c)) return r;
     if (rc) return rc;
-    // the packers, in the order of their inputs: the direct and transposed packs read the master weights, the Winograd and conv1_1 packs the
-    // direct packs just written (the order of PMX_PACK_*)
+    // the packers, in the order of their inputs: the direct and transposed packs read the master weights, the f16, bf16x3, Winograd and
+    // conv1_1 packs the direct packs just written (the order of PMX_PACK_*)
     if ((rc = pmx_prof_begin(c, "train_step|pack", 0))) return rc;
     for (int k = 0; k < PMX_PACK_KINDS && !rc; ++k)
         if (jl[k].n) rc = pmx_pack_launch_table(k, reinterpret_cast<const PackJob*>(dev + jobs_at(N, k)), jl[k].n, jl[k].blocks, st);
@@ -397,18 +404,20 @@ extern "C" int pmx_train_set_state(pmx_ctx* c, const char* name, const float* m_
 extern "C" int pmx_get_pack(pmx_ctx* c, const char* name, int which, void* out, size_t cap_bytes, size_t* n_bytes)
 {
     PMX_CHECK(c && name && n_bytes, PMX_ERR_INVALID, "pmx_get_pack: null arg");
-    PMX_CHECK(which >= 0 && which <= 4, PMX_ERR_INVALID, "pmx_get_pack: which = %d outside 0 .. 4", which);
+    PMX_CHECK(which >= 0 && which <= 6, PMX_ERR_INVALID, "pmx_get_pack: which = %d outside 0 .. 6", which);
     auto it = c->index.find(name);
     PMX_CHECK(it != c->index.end(), PMX_ERR_INVALID, "pmx_get_pack: unknown layer '%s'", name);
     const int idx = it->second;
     const PackedLayer* L = &c->layers[idx];
-    if (which >= 3) {
+    if (which == 3 || which == 4) {
         PMX_CHECK((size_t)idx < c->bw.tl.size() && c->bw.tl[idx].set, PMX_ERR_STATE, "pmx_get_pack: layer '%s' has no transposed pack", name);
         L = &c->bw.tl[idx];
     }
-    const DevBuf<float>& b = which == 0 || which == 3 ? L->d_w : which == 1 ? L->d_b : L->d_ww;
+    const DevBuf<uint16_t>& h = which == 5 ? L->d_w16 : L->d_w3;
+    const DevBuf<float>& f = which == 0 || which == 3 ? L->d_w : which == 1 ? L->d_b : L->d_ww;
+    const void* const b = which >= 5 ? (const void*)h.get() : (const void*)f.get();
     PMX_CHECK(L->set && b, PMX_ERR_STATE, "pmx_get_pack: pack %d of layer '%s' does not exist", which, name);
-    *n_bytes = b.capacity() * sizeof(float);
+    *n_bytes = which >= 5 ? h.capacity() * sizeof(uint16_t) : f.capacity() * sizeof(float);
     PMX_CHECK(out && cap_bytes >= *n_bytes, PMX_ERR_CAPACITY, "pmx_get_pack: %zu bytes needed, %zu given", *n_bytes, cap_bytes);
     PMX_DEV(c);
     PMX_HIP(hipStreamSynchronize(c->stream));

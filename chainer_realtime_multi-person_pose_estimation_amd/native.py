@@ -1008,7 +1008,7 @@ class Engine(object):
         return out
 
     # ---- training steps (include/pose_mi355x.h: pmx_train_*) ----- ------------------------------------------------------
-    PACKS = {'w': 0, 'b': 1, 'wino': 2, 't_w': 3, 't_wino': 4}
+    PACKS = {'w': 0, 'b': 1, 'wino': 2, 't_w': 3, 't_wino': 4, 'f16': 5, 'bf16x3': 6}
 
     def layer_shape(self, name):
         """(cout, cin, k, k) of layer `name` as installed (KeyError for a layer never set through this engine)."""
@@ -1063,8 +1063,8 @@ class Engine(object):
         self._check(self.lib.pmx_train_set_state(self._ctx, name.encode(), *[_ptr(a) for a in arrs], int(t)))
 
     def get_pack(self, name, which):
-        """The raw float32 contents of one device pack of a layer ('w', 'b', 'wino', 't_w', 't_wino' or 0 .. 4), None if that pack does
-        not exist now (synchronises)."""
+        """The raw contents of one device pack of a layer -- float32 for 'w', 'b', 'wino', 't_w', 't_wino' (or 0 .. 4), the uint16 words of
+        'f16' and 'bf16x3' (5, 6) -- None if that pack does not exist now (synchronises)."""
         which = self.PACKS.get(which, which)
         n = C.c_size_t(0)
         rc = self.lib.pmx_get_pack(self._ctx, name.encode(), int(which), None, 0, C.byref(n))
@@ -1072,7 +1072,7 @@ class Engine(object):
             return None
         if rc != 5:          # (PMX_ERR_CAPACITY: the size query)
             self._check(rc)
-        out = np.empty(n.value // 4, np.float32)
+        out = np.empty(n.value // 2, np.uint16) if which >= 5 else np.empty(n.value // 4, np.float32)
         self._check(self.lib.pmx_get_pack(self._ctx, name.encode(), int(which), _ptr(out), out.nbytes, C.byref(n)))
         return out
 

@@ -139,7 +139,7 @@ int pmx_synchronize(pmx_ctx* ctx);                    /* cuda.get_device_from_id
  *                              the f16 matrix cores: per output y = sum over (16-channel chunk, tap) of f16(x) * f16(w), summed in
  *                              fp32 on v_mfma_f32_32x32x16_f16 in an order fixed per layer (chunk-major, taps row-major, no split-K),
  *                              then the fp32 epilogue (2x2 max-pool, + bias, ReLU).  f16(v) = round-to-nearest-even saturating at
- *                              +-65504 (no inf; f16 subnormals are kept, NaN stays NaN); weights are rounded once, on the host; activations stay fp32 in device memory and
+ *                              +-65504 (no inf; f16 subnormals are kept, NaN stays NaN); weights are rounded once, on the device, into the layer's f16 pack; activations stay fp32 in device memory and
  *                              are rounded while a kernel stages them.  The 1x1 layers stay fp32.  The order does not depend on the
  *                              batch, the image's position or the segment layout: an image gives the same maps bit for bit alone,
  *                              anywhere in a uniform batch and inside a mixed-size batch (pmx_detect_images).  Accuracy against
@@ -723,11 +723,10 @@ int pmx_pool_backward_test(pmx_ctx* ctx, const float* a_nchw, const float* u_nch
  *      step's table copy has not finished);
  *   3. the packers: every pack of an updated layer that EXISTS is rewritten in place, same pointer, with the bits a one-off build gives
  *      from the same OIHW weights (csrc/pack_index.h defines every float of every pack) -- the direct pack and bias (pmx_set_layer), the Winograd pack, the transposed 180-degree-rotated pack of
- *      the data gradient and its Winograd pack.  A pack that does not exist is not created: its lazy builder makes it on first use
- *      from the then-current direct pack, after waiting for the stream.  The f16 / bf16x3 packs of an updated layer are marked stale and
- *      rebuilt in place when a forward in that mode next needs them.  ONE launch per kind of pack serves all updated layers (direct + bias,
- *      transposed, Winograd of both, conv1_1's fused-kernel pack): four launches at most, driven by per-layer tables that travel with
- *      Adam's in the same pinned copy.
+ *      the data gradient and its Winograd pack, the f16 and bf16x3 packs.  A pack that does not exist is not created: its lazy builder
+ *      makes it on first use from the then-current direct pack, after waiting for the stream.  ONE launch per kind of pack serves all
+ *      updated layers (direct + bias, f16, bf16x3, transposed, Winograd of both, conv1_1's fused-kernel pack): six launches at most, driven
+ *      by per-layer tables that travel with Adam's in the same pinned copy.
  * No host synchronisation, no host <-> device copy but the table.  The step CONSUMES the gradients: a second step without a new retained
  * forward + pmx_backward_head is PMX_ERR_STATE; pmx_get_layer_grad keeps working until the next forward.
  * Errors, before anything is enqueued: PMX_ERR_INVALID for a null context; PMX_ERR_STATE for a facenet / handnet context, "precision" != 0,
@@ -761,8 +760,9 @@ int pmx_get_layer(pmx_ctx* ctx, const char* name, float* w_oihw, float* bias);
 int pmx_train_get_state(pmx_ctx* ctx, const char* name, float* m_w, float* v_w, float* m_b, float* v_b, int* t);
 int pmx_train_set_state(pmx_ctx* ctx, const char* name, const float* m_w, const float* v_w, const float* m_b, const float* v_b, int t);
 /* parity accessor: the raw bytes of one pack of a layer -- which = 0 the direct pack, 1 the padded bias, 2 the Winograd pack (conv1_1: its
- * fused-kernel pack), 3 the transposed pack of the data gradient, 4 its Winograd pack.  *n_bytes is the pack's size whenever it exists;
- * PMX_ERR_STATE if it does not exist now, PMX_ERR_CAPACITY if out is NULL or cap_bytes too small.  Synchronises. */
+ * fused-kernel pack), 3 the transposed pack of the data gradient, 4 its Winograd pack (all float32), 5 the f16 pack, 6 the bf16x3 pack
+ * (uint16 words).  *n_bytes is the pack's size whenever it exists; PMX_ERR_STATE if it does not exist now, PMX_ERR_INVALID for another
+ * `which`, PMX_ERR_CAPACITY if out is NULL or cap_bytes too small.  Synchronises. */
 int pmx_get_pack(pmx_ctx* ctx, const char* name, int which, void* out, size_t cap_bytes, size_t* n_bytes);
 /* test entry: the Adam launch of the training steps on the caller's host arrays of `total` floats each (w, m, v updated in place).  Segment
  * i covers floats [off[i], off[i] + n[i]); off[i] a multiple of 4, the segments in rising order and not sharing a 16-byte vector, else

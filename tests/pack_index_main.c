@@ -1,10 +1,11 @@
 /* pack_index_main.c -- stand-alone driver of csrc/pack_index.h, the definition of the weight packs the device packers evaluate.
- * usage: pack_index_main cout cin ks kind [weights].  Writes int64 words to stdout: [nch, cout_pad, cin_pad, t_nch, t_cout_pad, t_cout, planes],
+ * usage: pack_index_main cout cin ks kind [weights [16]].  Writes int64 words to stdout: [nch, cout_pad, cin_pad, t_nch, t_cout_pad, t_cout, planes],
  * the reference channel of every packed input channel (cin_pad words), then per OIHW element (n, ci, tap) its place in the direct pack
  * and in the transposed pack of the data gradient, then (ks > 1) the place of every (plane, n < cout_pad, ci < cin_pad) in the Winograd pack.
  * With `weights`, a file of cout * cin * ks^2 + cout floats (w OIHW | b), the value functions follow as float32, every float of every pack
  * in index order: the direct pack, the padded bias, the transposed pack, (ks > 1) the Winograd packs of both, (a 64 x 3 x 3 x 3 layer)
- * conv1_1's fused-kernel pack, and the un-pack of the direct pack and bias. */
+ * conv1_1's fused-kernel pack, and the un-pack of the direct pack and bias; then, with `16`, as uint16 words the f16 pack and the bf16x3
+ * pack of the direct pack. */
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -12,6 +13,7 @@
 #include "pack_index.h"
 
 static void put(int64_t v) { fwrite(&v, sizeof v, 1, stdout); }
+static void put16(uint16_t v) { fwrite(&v, sizeof v, 1, stdout); }
 
 /* every float of one pack through its value function */
 static float* build(float (*value)(const PackJob*, unsigned), PackJob* j, size_t total)
@@ -33,7 +35,7 @@ static void wino(const float* direct, int ks, int nch, int cout_pad)
 
 int main(int argc, char** argv)
 {
-    if (argc != 5 && argc != 6) return 2;
+    if (argc < 5 || argc > 7) return 2;
     const int cout = atoi(argv[1]), cin = atoi(argv[2]), ks = atoi(argv[3]), kind = atoi(argv[4]), T = ks * ks;
     const int cin_pad = pmx_pk_cin_pad(kind, cin), nch = cin_pad / PMX_PK_CK, cout_pad = pmx_pk_cout_pad(cout);
     const int t_cin_pad = pmx_pk_t_cin_pad(cout), t_nch = t_cin_pad / PMX_PK_CK, t_cout = pmx_pk_t_cout(kind, cin), t_cout_pad = pmx_pk_cout_pad(t_cout);
@@ -75,6 +77,13 @@ int main(int argc, char** argv)
     for (size_t i = 0; i < nmaster; ++i) {
         const float v = pmx_pk_unpack_value(direct, bias, geo, (unsigned)i);
         fwrite(&v, sizeof v, 1, stdout);
+    }
+    if (argc == 7) {
+        PackJob jh = {0};
+        jh.src = direct; jh.p.cout_pad = cout_pad;
+        const size_t nd = (size_t)T * nch * cout_pad * PMX_PK_CK;
+        for (size_t i = 0; i < nd; ++i) put16(pmx_pk_f16_value(&jh, (unsigned)i));
+        for (size_t i = 0; i < 3 * nd; ++i) put16(pmx_pk_bf16x3_value(&jh, (unsigned)i));
     }
     free(transposed); free(bias); free(direct); free(master);
     return 0;

@@ -1,7 +1,8 @@
 """NumPy restatement of every weight pack of the library (csrc/pack_index.h defines them, csrc/pmx_packs.hip builds them): the channel
-maps, the direct pack and padded bias, the pack of the layer whose forward is the data gradient, the Winograd pack and conv1_1's
-fused-kernel pack.  Written in scatter / whole-array form, independently of the header's one-value-per-index form; nobody's production
-code.  Every function returns flat arrays laid out as the device buffers are, pads included (+0.0f, or `fill` for index arrays)."""
+maps, the direct pack and padded bias, the pack of the layer whose forward is the data gradient, the Winograd pack, conv1_1's
+fused-kernel pack, and the f16 and bf16x3 packs (uint16 bits).  Written in scatter / whole-array form, independently of the header's
+one-value-per-index form; nobody's production code.  Every function returns flat arrays laid out as the device buffers are, pads
+included (+0.0f, or `fill` for index arrays)."""
 import numpy as np
 
 CK = 16
@@ -95,16 +96,17 @@ def wino_pack(wp, ks, nch16, cout_pad):
     cin_pad = nch16 * CK
     g = wp.reshape(ks, ks, nch16, cout_pad, CK).transpose(0, 1, 3, 2, 4).reshape(ks, ks, cout_pad, cin_pad).astype(np.float64)
     planes = []
-    for sy in range(ks // 3):
-        for sx in range(ks // 3):
-            u = _ggt(g[3 * sy:3 * sy + 3, 3 * sx:3 * sx + 3])
-            planes += [u[i][j] for i in range(4) for j in range(4)]
-    if ks == 7:
-        for sub in range(2):
-            planes += _g1(g[6, 3 * sub], g[6, 3 * sub + 1], g[6, 3 * sub + 2])
-        for sub in range(2):
-            planes += _g1(g[3 * sub, 6], g[3 * sub + 1, 6], g[3 * sub + 2, 6])
-        planes.append(g[6, 6])
+    with np.errstate(invalid='ignore'):          # (0 * inf of a weight that is infinite: a NaN, as on the device)
+        for sy in range(ks // 3):
+            for sx in range(ks // 3):
+                u = _ggt(g[3 * sy:3 * sy + 3, 3 * sx:3 * sx + 3])
+                planes += [u[i][j] for i in range(4) for j in range(4)]
+        if ks == 7:
+            for sub in range(2):
+                planes += _g1(g[6, 3 * sub], g[6, 3 * sub + 1], g[6, 3 * sub + 2])
+            for sub in range(2):
+                planes += _g1(g[3 * sub, 6], g[3 * sub + 1, 6], g[3 * sub + 2, 6])
+            planes.append(g[6, 6])
     u = np.stack(planes).astype(np.float32)                                   # (planes, cout_pad, cin_pad)
     u = u.reshape(len(planes), cout_pad // 32, 32, cin_pad // 32, 4, 8).transpose(0, 3, 1, 4, 2, 5)
     return np.ascontiguousarray(u).reshape(-1)
@@ -117,6 +119,59 @@ def conv1_pack(wp, cout_pad=64):
     out = np.zeros((2, 28, 32), np.float32)
     out[:, :27] = w.reshape(2, 32, 27).transpose(0, 2, 1)
     return out.reshape(-1)
+
+
+def edge_values():
+    """float32 values at which a rounding can go wrong: +-0, subnormals, 2^-25 (half the smallest f16 subnormal: a tie to zero) and its
+    neighbours, ties of f16 (1 + 2^-11, 1 + 3 * 2^-11: the even neighbour below / above) and of bf16 (1 + 2^-8, 1 + 3 * 2^-8), the f16
+    saturation edge (65504, the last float32 below 65520, 65520), 1e30, +-inf, a NaN"""
+    t25 = np.float32(2.0 ** -25)
+    v = [0.0, -0.0, 1e-40, -1e-45, np.nextafter(t25, np.float32(0)), t25, np.nextafter(t25, np.float32(1)), -t25,
+         1 + 2.0 ** -11, 1 + 3 * 2.0 ** -11, -(1 + 2.0 ** -11), 1 + 2.0 ** -8, 1 + 3 * 2.0 ** -8, -(1 + 3 * 2.0 ** -8),
+         65504, np.nextafter(np.float32(65520), np.float32(0)), 65520, -65520, 1e30, -1e30, np.inf, -np.inf, np.nan]
+    return np.array(v, np.float32)
+
+
+def splice_edge_values(W):
+    """a copy of the weights W (any shape) with edge_values() at evenly spread places -> (weights, their flat places)"""
+    e = edge_values()
+    at = (np.arange(len(e)) * (W.size // len(e)) + W.size // (2 * len(e))).astype(np.int64)
+    out = np.array(W, np.float32)
+    out.reshape(-1)[at] = e
+    return out, at
+
+
+def f16_pack(wp):
+    """direct pack -> f16 pack (uint16 bits, the same layout): clipped to +-65504, then rounded to nearest even by numpy.float16; a NaN
+    becomes the quiet f16 NaN of its sign"""
+    wp = np.ascontiguousarray(wp, np.float32)
+    sign = (wp.view(np.uint32) >> 16).astype(np.uint16) & np.uint16(0x8000)
+    with np.errstate(invalid='ignore'):
+        h = np.clip(wp, -65504, 65504).astype(np.float16).view(np.uint16)
+    return np.where(np.isnan(wp), sign | np.uint16(0x7e00), h)
+
+
+def _bf16_bits(x):
+    """float32 -> bf16 bits (uint16): integer round-to-nearest-even on the uint32 view; a NaN keeps its upper half with the quiet bit set"""
+    u = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
+    r = (u + 0x7fff + ((u >> 16) & 1)) >> 16
+    return np.where((u & 0x7fffffff) > 0x7f800000, (u >> 16) | 0x40, r).astype(np.uint16)
+
+
+def _bf16_float(h):
+    return (h.astype(np.uint32) << 16).view(np.float32)
+
+
+def bf16x3_pack(wp, T, nch, cout_pad):
+    """direct pack -> bf16x3 pack [tap][chunk][plane hi|mid|lo][cout_pad][16] (uint16 bits): hi = bf16(x), mid = bf16(x - hi),
+    lo = bf16((x - hi) - mid), the subtractions in float32"""
+    x = np.ascontiguousarray(wp, np.float32).reshape(T * nch, cout_pad, CK)
+    with np.errstate(invalid='ignore'):
+        hi = _bf16_bits(x)
+        r1 = x - _bf16_float(hi)
+        mid = _bf16_bits(r1)
+        lo = _bf16_bits(r1 - _bf16_float(mid))
+    return np.stack([hi, mid, lo], axis=1).reshape(-1)
 
 
 def layer_packs(W, b, kind, transposed=True):

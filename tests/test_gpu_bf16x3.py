@@ -118,6 +118,35 @@ def test_bf16x3_network_matches_reference_golden_and_fp32_path(native):
     assert np.abs(h3 - h32).max() <= 1e-4 * max(1.0, np.abs(h32).max())
 
 
+def test_bf16x3_packs_equal_numpy(native):
+    """One 64 x 48 image with the small-tile bf16x3 kernels forced: every layer that then has a bf16x3 pack -- a 3x3 and a 7x7 layer among
+    them -- holds tests/pack_ref.py::bf16x3_pack of its direct pack, bit for bit (three bf16 planes per tap and chunk)."""
+    import pack_ref
+    w = pkg('weights').synthetic_weights(0)
+    eng = native.Engine(0, max_batch=1, max_h=64, max_w=48)
+    try:
+        eng.set_weights(w)
+        eng.set_option('force_variant_k7', 15)
+        eng.set_option('force_variant_k3', 16)
+        eng.set_option('precision', 1)
+        eng.forward_u8(np.random.default_rng(5).integers(0, 256, (1, 64, 48, 3), dtype=np.uint8))
+        eng.get_maps()
+        sizes = set()
+        for nm in sorted(w):
+            got = eng.get_pack(nm, 'bf16x3')
+            if got is None:
+                continue
+            cout, cin, ks, _ = eng.layer_shape(nm)
+            direct = eng.get_pack(nm, 'w')
+            cp = pack_ref.cout_pad(cout)
+            assert ks > 1 and got.dtype == np.uint16 and got.size == 3 * direct.size
+            assert np.array_equal(got, pack_ref.bf16x3_pack(direct, ks * ks, direct.size // (ks * ks * cp * 16), cp)), nm
+            sizes.add(ks)
+        assert sizes == {3, 7}
+    finally:
+        eng.close()
+
+
 @pytest.mark.parametrize('name', ['e2e_person', 'e2e_people'])
 def test_bf16x3_detector_on_reference_images(native, name):
     """The reference's own images replicated to a batch of 32 (so that the bf16x3 kernels are selected): peak indices and poses

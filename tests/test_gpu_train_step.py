@@ -461,7 +461,7 @@ def test_error_codes(native):
         refused(1, e.train_set_adam, -1.0)
         n = C.c_size_t(0)
         assert lib.pmx_get_pack(e._ctx, b'no_such_layer', 0, None, 0, C.byref(n)) == 1
-        assert lib.pmx_get_pack(e._ctx, b'conv4_3_CPM', 5, None, 0, C.byref(n)) == 1
+        assert lib.pmx_get_pack(e._ctx, b'conv4_3_CPM', 7, None, 0, C.byref(n)) == 1
         assert lib.pmx_get_pack(e._ctx, b'conv4_3_CPM', 0, None, 0, None) == 1
         assert lib.pmx_get_pack(e._ctx, b'conv5_4_CPM_L1', 2, None, 0, C.byref(n)) == 6          # a 1x1 layer has no Winograd pack
         assert lib.pmx_train_step_head(None) == 1 and lib.pmx_train_enable(None, 1) == 1

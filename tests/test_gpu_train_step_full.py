@@ -2,7 +2,8 @@
 every pack of every layer rewritten on the device by the table-driven packers.  The Adam launch bit for bit against tests/adam_twin.py from
 the library's own gradients, head and trunk at different t; every pack of all 92 layers -- conv1_1's fused-kernel pack and conv1_2's
 Winograd pack among them -- bit for bit against the packs a fresh context builds by one-off launches of the same packers, and those against
-the NumPy restatement tests/pack_ref.py (as are the concat layers of a facenet and a handnet context); the next forward and backward
+the NumPy restatement tests/pack_ref.py (as are the concat layers of a facenet and a handnet context, and the f16 packs: those an f16
+forward builds in a fresh context, and those a step re-packs, read right after the step); the next forward and backward
 against that context's; what a head-only step between full steps must leave alone; five steps of PoseDetector with the trunk trainable against float64
 torch; the switch from head-only training, the state round trip, train_loop and the error codes.  Batch 2 at 64 x 48, and 3 x 40 x 56
 where partial tiles at every level matter.  Option "conv1_wino" = 2 makes the un-retained forward of these small batches run the fused
@@ -112,7 +113,7 @@ class Seq(object):
         self.first = _build_packs(e)
         self.adam = dict(A.DEFAULTS)
         self.state = self.start = TS._state(e, self.all)
-        self.records, self.digests, self.before = [], [], {}
+        self.records, self.digests, self.before, self.f16 = [], [], {}, {}
 
     def step(self, full=True, stages=6, adam=None):
         e = self.eng
@@ -135,8 +136,33 @@ class Seq(object):
             n = len(self.records)
             if n in (4, 6):          # before the head-only step and the stop_stage 2 step: what they must keep
                 self.before[n] = (TS._packs(self.eng, self.all if n == 6 else TRUNK), self.state)
+            f16 = {nm: self.eng.get_pack(nm, 'f16') for nm in self.all} if n >= 4 else None
             self.step(**self.PLAN[n])
+            if f16 is not None:          # steps 5 (head-only), 6 (full), 7 (stop_stage 2): the f16 packs right after the step, no forward between
+                self.f16[n + 1] = self._f16_record(f16, self.records[n]['names'])
         return self.records[k - 1]
+
+    def _f16_record(self, before, updated):
+        """the f16 packs of all layers now against `before` and against pack_ref.f16_pack of the direct packs now -> the layers that have
+        one, and among them: the updated ones whose pack is not that of their new direct pack, the updated ones whose pack kept its bits,
+        the others whose pack changed"""
+        rec = dict(have=[], wrong=[], unmoved=[], moved=[])
+        for nm in self.all:
+            got = self.eng.get_pack(nm, 'f16')
+            assert (got is None) == (before[nm] is None), nm
+            if got is None:
+                continue
+            rec['have'].append(nm)
+            assert got.dtype == np.uint16 and got.shape == before[nm].shape, nm
+            same = np.array_equal(got, before[nm])
+            if nm in updated:
+                if not np.array_equal(got, pack_ref.f16_pack(self.eng.get_pack(nm, 'w'))):
+                    rec['wrong'].append(nm)
+                if same:
+                    rec['unmoved'].append(nm)
+            elif not same:
+                rec['moved'].append(nm)
+        return rec
 
 
 _seq = {}
@@ -261,6 +287,39 @@ def test_every_pack_of_a_fresh_context_equals_numpy(seq, fresh):
     assert compared == 92 + 92 + (wino + 10) + 91 + (wino + 7)
 
 
+def test_f16_packs_of_a_fresh_context_equal_numpy(native):
+    """No layer has an f16 pack before the first "precision" = 2 forward; after one, every 3x3 / 7x7 layer's f16 pack is
+    pack_ref.f16_pack of its direct pack, bit for bit, and the 1x1 layers still have none.  conv5_1_CPM_L1 is installed through set_layer
+    with pack_ref.edge_values() (+-0, subnormals, rounding ties, the saturation edge, +-inf, a NaN) in real cells, so the maps of that
+    forward are not looked at."""
+    w = _weights()
+    e = native.Engine(0, **MAX)
+    try:
+        e.set_weights(w)
+        nm_edge = 'conv5_1_CPM_L1'
+        W_edge, at = pack_ref.splice_edge_values(w[nm_edge][0])
+        e.set_layer(nm_edge, W_edge, w[nm_edge][1])
+        names = sorted(w)
+        assert len(names) == 92 and all(e.get_pack(nm, 'f16') is None for nm in names)
+        _forward(e, precision=2)
+        compared = 0
+        for nm in names:
+            got = e.get_pack(nm, 'f16')
+            if e.layer_shape(nm)[-1] == 1:
+                assert got is None, nm
+                continue
+            direct = e.get_pack(nm, 'w')
+            assert got is not None and got.dtype == np.uint16 and got.size == direct.size, nm
+            assert np.array_equal(got, pack_ref.f16_pack(direct)), nm
+            compared += 1
+        assert compared == 10 + 2 + 6 + 50
+        direct = e.get_pack(nm_edge, 'w')
+        assert np.isin(_bits(pack_ref.edge_values()), _bits(direct)).all()          # every edge value reached the device, bits intact
+        assert all(e.get_pack(nm, 'bf16x3') is None for nm in names)
+    finally:
+        e.close()
+
+
 @pytest.mark.parametrize('arch,C', [('facenet', 71), ('handnet', 22)])
 def test_concat_layer_packs_of_face_and_hand_equal_numpy(native, arch, C):
     """the first 7x7 layer of stage 2 (cin = C heat + 128 feature channels, packed as [feature | heat | pad]): direct pack and bias"""
@@ -322,6 +381,24 @@ def test_stop_stage_updates_the_trunk_and_the_stages_run(seq, fresh):
     assert not TS._diff_packs({k: v for k, v in now.items() if k[0] in late}, {k: v for k, v in packs6.items() if k[0] in late})
     changed = TS._diff_packs({k: v for k, v in now.items() if k[1] == 'w'}, {k: v for k, v in packs6.items() if k[1] == 'w'})
     assert sorted(k[0] for k in changed) == sorted(rec['names'])
+
+
+def test_a_step_repacks_the_f16_packs(seq, fresh):
+    """The f16 packs exist before the first step (Seq.__init__).  Right after step 5 (head-only), step 6 (full) and step 7 (full,
+    stop_stage 2), with no f16 forward in between (Seq.upto reads the packs around the step), the f16 pack of every updated layer that has
+    one is pack_ref.f16_pack of the layer's new direct pack and differs from its bits before the step; the f16 packs of the layers a step
+    left alone -- the trunk in step 5, the stages past the second in step 7 -- keep their bits.  (After the two tests above: they read the
+    state at steps 5 and 6.)"""
+    seq.upto(7)
+    have = [nm for nm in seq.all if seq.eng.layer_shape(nm)[-1] > 1]
+    assert len(have) == 68
+    for k, updated in ((5, 58), (6, 68), (7, 10 + 2 + 6 + 10)):
+        rec = seq.f16[k]
+        names = seq.records[k - 1]['names']
+        print('step', k, 'layers with an f16 pack', len(rec['have']), 'of them updated', sum(nm in names for nm in rec['have']),
+              {key: rec[key] for key in ('wrong', 'unmoved', 'moved')})
+        assert rec['have'] == have and sum(nm in names for nm in have) == updated
+        assert not rec['wrong'] and not rec['unmoved'] and not rec['moved'], rec
 
 
 # ---- 5, 7. determinism; pmx_set_layer on a trunk layer ---------------------------------------------------------------------------------------------

@@ -69,6 +69,10 @@ def test_zero_gradient_on_fresh_state_leaves_the_weights():
 
 
 # ---- the shared index arithmetic -----------------------------------------------------------------------------------------------------
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
 def _index_program(tmp_path_factory):
     cc = shutil.which('gcc') or shutil.which('cc')
     assert cc, 'no host C compiler'
@@ -122,21 +126,24 @@ def test_index_maps_against_numpy_packers(index_exe, cout, cin, ks, kind):
 @pytest.mark.parametrize('cout,cin,ks,kind', [(128, 128, 3, 0), (128, 185, 7, 1), (38, 512, 1, 0), (64, 3, 3, 0), (128, 199, 7, 2 + 71),
                                               (128, 150, 7, 2 + 22), (100, 20, 3, 0), (19, 128, 1, 0)])
 def test_pack_values_against_numpy_packers(index_exe, tmp_path, cout, cin, ks, kind):
-    """Every float of every pack, pads included, from the header's value functions on seeded weights == tests/pack_ref.py, bit for bit: the
-    direct pack and bias, the transposed pack, the Winograd packs of both (float64, one rounding), conv1_1's fused-kernel pack; and the
-    un-pack of the direct pack is the identity."""
+    """Every element of every pack, pads included, from the header's value functions on seeded weights == tests/pack_ref.py, bit for bit: the
+    direct pack and bias, the transposed pack, the Winograd packs of both (float64, one rounding), conv1_1's fused-kernel pack, the f16
+    pack and the bf16x3 pack; and the un-pack of the direct pack is the identity.  The weights carry pack_ref.edge_values() (+-0,
+    subnormals, rounding ties of f16 and bf16, the f16 saturation edge, +-inf, a NaN) in real cells."""
     T = ks * ks
     rng = np.random.default_rng(cout * 1000 + cin + ks)
-    W = rng.normal(0, 0.05, (cout, cin, ks, ks)).astype('f')
+    W, edge_at = P.splice_edge_values(rng.normal(0, 0.05, (cout, cin, ks, ks)).astype('f'))
     b = rng.normal(0, 0.05, cout).astype('f')
     path = str(tmp_path / 'master.f32')
     np.concatenate([W.reshape(-1), b]).tofile(path)
-    r = subprocess.run([index_exe, str(cout), str(cin), str(ks), str(kind), path], capture_output=True, timeout=300)
+    r = subprocess.run([index_exe, str(cout), str(cin), str(ks), str(kind), path, '16'], capture_output=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     cp, cin_pad = P.cout_pad(cout), len(P.channel_map(kind, cin))
     words = 7 + cin_pad + 2 * cout * cin * T + (P.G.shape[0] ** 2 if ks == 3 else 81 if ks == 7 else 0) * cp * cin_pad
-    got = np.frombuffer(r.stdout[8 * words:], np.float32)
     want = P.layer_packs(W, b, kind)
+    halves = 4 * want['w'].size          # the uint16 words that follow the floats: the f16 pack and the three planes of the bf16x3 pack
+    got = np.frombuffer(r.stdout[8 * words:len(r.stdout) - 2 * halves], np.float32)
+    got16 = np.frombuffer(r.stdout[len(r.stdout) - 2 * halves:], np.uint16)
     conv1 = (cout, cin, ks) == (64, 3, 3)          # ('wino' of that layer is its fused-kernel pack, emitted after the Winograd packs)
     assert ('wino' in want) == (conv1 or (ks > 1 and cin_pad % 32 == 0)) and ('t_wino' in want) == (ks > 1 and max(64, -(-cout // 16) * 16) % 32 == 0)
     assert want['wino'].size == 2 * 14 * 2 * 32 if conv1 else True
@@ -148,7 +155,11 @@ def test_pack_values_against_numpy_packers(index_exe, tmp_path, cout, cin, ks, k
     for i, x in enumerate(parts):
         assert x.dtype == np.float32 and np.array_equal(got[at:at + x.size].view(np.uint32), x.view(np.uint32)), (i, x.size)
         at += x.size
-    assert np.abs(want['w']).max() > 0 and (want['w'] == 0).sum() == want['w'].size - W.size
+    # (the spliced +0 and -0 are the only zeros among the weights; every edge value sits in a real cell of the direct pack)
+    assert (want['w'] != 0).sum() == W.size - 2
+    assert sorted(_bits(W.reshape(-1)[edge_at])) == sorted(_bits(P.edge_values())) and np.isin(_bits(P.edge_values()), _bits(want['w'])).all()
+    want16 = np.concatenate([P.f16_pack(want['w']), P.bf16x3_pack(want['w'], T, cin_pad // 16, cp)])
+    assert want16.dtype == np.uint16 and got16.size == want16.size and np.array_equal(got16, want16), np.flatnonzero(got16 != want16)[:10]
 
 
 def test_c_abi_surface():
