@@ -345,7 +345,14 @@ struct pmx_ctx {
     DevBuf<char> sp_dev, sp_const;
     DevBuf<uint8_t> sp_a, sp_out, sp_mask_raw, sp_mask_tmp, sp_mask;
     int sp_n = 0, sp_insize = 0;                          // the prepared samples (0: none)
-    BwState bw;                                           // pmx_backward.hip
+    // pmx_render.hip (result images).  rd_host / rd_dev: the per-call block [image table | primitives], ONE copy from pinned memory
+    // (`rd_copied` marks when the host side may be rewritten); rd_img: the host images of the call; rd_out: the canvases end to end when
+    // the caller's output is host memory.  All grow on demand (original images are larger than the network input).
+    HostBuf<char> rd_host;
+    hipEvent_t rd_copied = nullptr; bool rd_pending = false;
+    DevBuf<char> rd_dev;
+    DevBuf<uint8_t> rd_img, rd_out;
+    BwState bw;                                          // pmx_backward.hip
     TrainState tr;                                        // pmx_train.hip
 };
 constexpr int PMX_LOSS_SLOTS = 7;

@@ -5,6 +5,8 @@ HandNet call for all people of the image (face_hand_detector.detect_person_parts
 The canvas is the reference's: cv2.addWeighted(img, 0.6, draw_person_pose(img, poses), 0.4, 0) restated in NumPy (float32 weighted sum,
 OpenCV's round-half-even and saturation), then per person the face key points and their white box, the left hand, the right hand, in the
 order of the reference's loop (demo.py:30-55).  The weights files are Chainer NPZ files (the reference's models/*.npz).
+`--render device` draws the same bytes on the GPU in one launch (render_batch: include/pose_mi355x.h::pmx_render); `render` and its
+helpers below stay the default and are that path's contract.
 """
 import argparse
 
@@ -55,6 +57,18 @@ def render(img, poses, parts):
     return res
 
 
+def render_batch(detector, imgs, poses_per_image, parts_per_image):
+    """`[render(img, poses, parts) for ...]` for the lists face_hand_detector.detect_people_parts takes and returns, drawn on the device
+    in one launch through `detector`'s context (any of the three detectors: drawing needs no weights), byte for byte."""
+    if len(parts_per_image) != len(imgs):
+        raise ValueError('one list of person parts per image')
+    flat = []
+    for persons in parts_per_image:
+        flat.append([(kind, person[key]['bbox'], person[key]['keypoints'])
+                     for person in persons for key, kind in (('face', 'face'), ('left', 'hand'), ('right', 'hand')) if person[key] is not None])
+    return detector.engine.render(imgs, poses_per_image, flat, blend=True)
+
+
 def parse_args(argv=None):
     parser = argparse.ArgumentParser(description='Pose, face and hand key points of every person in an image')
     parser.add_argument('--img', required=True, help='image file path')
@@ -63,6 +77,8 @@ def parse_args(argv=None):
     parser.add_argument('--pose-weights', default='models/coco_posenet.npz', help='posenet weights (Chainer NPZ)')
     parser.add_argument('--face-weights', default='models/facenet.npz', help='facenet weights (Chainer NPZ)')
     parser.add_argument('--hand-weights', default='models/handnet.npz', help='handnet weights (Chainer NPZ)')
+    parser.add_argument('--render', choices=['host', 'device'], default='host',
+                        help='where the result image is drawn: host (default, NumPy) or device (one launch; the same bytes)')
     return parser.parse_args(argv)
 
 
@@ -76,7 +92,7 @@ def main(argv=None):
     poses, _ = pose_detector(img)
     print('Estimating face and hand keypoints of %d people...' % len(poses))
     parts = fh.detect_person_parts(pose_detector, face_detector, hand_detector, img, poses)
-    res = render(img, poses, parts)
+    res = render_batch(pose_detector, [img], [poses], [parts])[0] if args.render == 'device' else render(img, poses, parts)
     print('Saving result into %s...' % args.out)
     pd.imwrite_bgr(args.out, res)
     return 0

@@ -220,7 +220,8 @@ class HandDetector(_KeypointDetector):
         return self._detect_boxes_batch(imgs, bboxes_per_image, [[1 if t == "left" else 0 for t in ts] for ts in hand_types_per_image])
 
 
-# ---- visualisation / crop helpers of the reference modules (host-only; cv2.circle / cv2.line rasters are stand-ins) -----------
+# ---- visualisation / crop helpers of the reference modules (host; cv2.circle / cv2.line rasters are stand-ins).  The two drawing
+# functions are the contract of the device form (demo.render_batch: include/pose_mi355x.h::pmx_render) and its oracle in the tests -----
 def _shifted(kp, left_top):
     return (kp[0] + left_top[0], kp[1] + left_top[1])
 

@@ -29,7 +29,8 @@ SOURCES = [('pmx_api.hip', []), ('pmx_precise.hip', []), ('pmx_multi.hip', []), 
            ('postproc.hip', ['-ffp-contract=off']), ('pmx_boxes.hip', ['-ffp-contract=off']), ('pmx_loss.hip', ['-ffp-contract=off']),
            ('pmx_samples.hip', ['-ffp-contract=off']), ('conv_bwd.hip', ['-ffp-contract=off']),
            ('pmx_backward.hip', ['-ffp-contract=off']), ('pmx_packs.hip', ['-ffp-contract=off']),
-           ('pmx_train.hip', ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt'])]
+           ('pmx_train.hip', ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt']),
+           ('pmx_render.hip', ['-ffp-contract=off'])]
 # the opt-in bf16x3 kernels (option "precision" = 1; DESIGN.md 4.1.5: frozen, slower than the fp32 Winograd path) are NOT part of the
 # default library: PMX_BUILD_BF16X3=1 in the environment of the build adds their translation unit (the stamp then differs, so the
 # library is rebuilt when the variable changes)
@@ -71,6 +72,11 @@ class PmxPreciseImage(C.Structure):
 class PmxBoxImage(C.Structure):
     """include/pose_mi355x.h::pmx_box_image -- one image of a many-image box call (pmx_keypoints_boxes_images)."""
     _fields_ = [('bgr', C.c_void_p), ('h', C.c_int), ('w', C.c_int)]
+
+
+class PmxRenderPart(C.Structure):
+    """include/pose_mi355x.h::pmx_render_part -- one face (kind 0) or hand (kind 1) of a pmx_render call."""
+    _fields_ = [('image', C.c_int), ('kind', C.c_int), ('left', C.c_int), ('top', C.c_int), ('right', C.c_int), ('bottom', C.c_int)]
 
 
 class PmxSample(C.Structure):
@@ -271,6 +277,7 @@ def load():
         'pmx_keypoints_boxes': (ci, [vp, vp, ci, ci, ci, vp, ci, cd, vp]),
         'pmx_forward_u8_boxes_images': (ci, [vp, vp, ci, ci, vp, ci]),
         'pmx_keypoints_boxes_images': (ci, [vp, vp, ci, ci, vp, ci, cd, vp]),
+        'pmx_render': (ci, [vp, vp, ci, ci, vp, vp, vp, ci, vp, ci, vp, ci]),
         'pmx_precise_begin': (ci, [vp, ci, ci]),
         'pmx_precise_add_scale': (ci, [vp, vp, ci, ci]),
         'pmx_precise_finish': (ci, [vp]),
@@ -381,6 +388,59 @@ def gaussian_taps(sigma, truncate=4.0):
     x = np.arange(-radius, radius + 1)
     phi = np.exp(-0.5 / sigma2 * x ** 2)
     return phi / phi.sum(), radius
+
+
+RENDER_PART_POINTS = {'face': 70, 'hand': 21}      # kinds of pmx_render_part (0, 1) and their key points
+
+
+def render_args(imgs, poses_per_image, parts_per_image=None, blend=True):
+    """The arguments of Engine.render checked and flattened for pmx_render, without touching the device: (poses (sum n, 18, 3) float64,
+    n_people int32 per image, the pmx_render_part array, its length, the key-point rows (x, y, confidence, valid) float64).  ValueError
+    for lists whose lengths differ, an image that is not uint8 H x W x 3, poses that are not (n, 18, 3), a part of an unknown kind or with
+    the wrong number of key points, parts without the blend."""
+    imgs = list(imgs)
+    if len(poses_per_image) != len(imgs):
+        raise ValueError('one array of poses per image (%d for %d images)' % (len(poses_per_image), len(imgs)))
+    if parts_per_image is not None and len(parts_per_image) != len(imgs):
+        raise ValueError('one list of parts per image (%d for %d images)' % (len(parts_per_image), len(imgs)))
+    for i, im in enumerate(imgs):
+        dtype = str(im.dtype) if hasattr(im, 'dtype') else None
+        if dtype not in ('uint8', 'torch.uint8') or len(im.shape) != 3 or im.shape[2] != 3 or im.shape[0] < 1 or im.shape[1] < 1:
+            raise ValueError('image %d: a uint8 H x W x 3 image expected, got %s %r' % (i, dtype, tuple(getattr(im, 'shape', ()))))
+    poses, n_people = [], []
+    for i, p in enumerate(poses_per_image):
+        p = np.asarray(p, dtype=np.float64)
+        if p.size == 0:
+            n_people.append(0)
+            continue
+        if p.ndim != 3 or p.shape[1:] != (N_JOINTS, 3):
+            raise ValueError('image %d: poses of shape (n, %d, 3) expected, got %r' % (i, N_JOINTS, p.shape))
+        poses.append(p)
+        n_people.append(len(p))
+    poses = np.ascontiguousarray(np.concatenate(poses) if poses else np.zeros((0, N_JOINTS, 3)), dtype=np.float64)
+    flat, rows = [], []
+    for i, plist in enumerate(parts_per_image or []):
+        for kind, bbox, kps in plist:
+            if kind not in RENDER_PART_POINTS:
+                raise ValueError("image %d: a part is 'face' or 'hand', got %r" % (i, kind))
+            n = RENDER_PART_POINTS[kind]
+            if len(kps) != n:
+                raise ValueError('image %d: a %s has %d key points, got %d' % (i, kind, n, len(kps)))
+            if len(bbox) != 4:
+                raise ValueError('image %d: a box is (left, top, right, bottom), got %r' % (i, tuple(bbox)))
+            box = [int(v) for v in bbox]
+            if any(v < -2 ** 31 or v > 2 ** 31 - 1 for v in box):
+                raise ValueError('image %d: box coordinates outside int32' % i)
+            flat.append((i, 0 if kind == 'face' else 1) + tuple(box))
+            rows.append(np.array([(0, 0, 0, 0) if kp is None else tuple(kp) if len(kp) == 4 else (kp[0], kp[1], kp[2], 1)
+                                  for kp in kps], dtype=np.float64).reshape(n, 4))
+    if flat and not blend:
+        raise ValueError('parts are drawn over the blended canvas: blend=False takes none')
+    parts = (PmxRenderPart * max(1, len(flat)))()
+    for k, f in enumerate(flat):
+        parts[k].image, parts[k].kind, parts[k].left, parts[k].top, parts[k].right, parts[k].bottom = f
+    kps = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 4)), dtype=np.float64)
+    return poses, np.ascontiguousarray(n_people, dtype=np.int32), parts, len(flat), kps
 
 
 class Engine(object):
@@ -699,6 +759,35 @@ class Engine(object):
         """keypoints_boxes for boxes of many images: (n, maps - 1, 4) float64 key-point rows in box order, each in its box's own pixel
         frame; chunks of max_batch crops in box order across image borders, one synchronisation per call."""
         return self._box_call(imgs, boxes6, thresh)
+
+    # ---- result images (pmx_render) -----------------------------------------------------------------
+    def render(self, imgs, poses_per_image, parts_per_image=None, blend=True):
+        """The result images of a list of images in one launch: per image `draw_person_pose(img, poses)` (blend=False),
+        `demo.add_weighted(img, 0.6, draw_person_pose(img, poses), 0.4, 0)` (blend=True) or, with parts, `demo.render(img, poses, parts)`,
+        byte for byte.  imgs: (H, W, 3) uint8 BGR host arrays of any sizes -> a list of new arrays; or contiguous uint8 torch tensors on the
+        GPU -> a list of such tensors (views of one allocation; nothing is copied to the host and nothing synchronises: the canvases are
+        complete once the context's stream has run the call -- synchronize(), or the caller's own stream given to set_stream).  poses_per_image:
+        per image (n, 18, 3) rows (x, y, v), or anything empty.  parts_per_image: per image a list of (kind, (left, top, right, bottom),
+        keypoints), kind 'face' (70 key points) or 'hand' (21), keypoints a list of [x, y, confidence] | None in the box's frame or an
+        (n, 4) array of rows (x, y, confidence, valid); drawn in list order.  Argument errors raise ValueError before the device is touched."""
+        imgs = list(imgs)
+        poses, n_people, parts, n_parts, kps = render_args(imgs, poses_per_image, parts_per_image, blend)
+        arr, on_device, keep = self._box_images(imgs)
+        sizes = [int(im.shape[0]) * int(im.shape[1]) * 3 for im in imgs]
+        if on_device:
+            import torch
+            flat = torch.empty(sum(sizes), dtype=torch.uint8, device=imgs[0].device)
+            out_ptr = C.c_void_p(flat.data_ptr())
+        else:
+            flat = np.empty(sum(sizes), np.uint8)
+            out_ptr = _ptr(flat)
+        self._check(self.lib.pmx_render(self._ctx, arr, len(imgs), on_device, _ptr(poses), _ptr(n_people), parts, n_parts,
+                                        _ptr(kps), int(bool(blend)), out_ptr, on_device))
+        out, off = [], 0
+        for im, n in zip(imgs, sizes):
+            out.append(flat[off:off + n].reshape(tuple(im.shape)))
+            off += n
+        return out
 
     def set_maps(self, paf, heat):
         paf = np.ascontiguousarray(paf, dtype=np.float32)

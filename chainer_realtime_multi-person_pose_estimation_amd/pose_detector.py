@@ -502,6 +502,14 @@ class PoseDetector(object):
                 raise r
         return out
 
+    # ---- result images on the device (reference pose_detector.py:520-553, :574) ------------------------------------------------
+    def draw_batch(self, imgs, poses_per_image, blend=False):
+        """`[draw_person_pose(img, poses) for img, poses in zip(imgs, poses_per_image)]` in one launch on the device, byte for byte (an
+        image without people comes back as an equal copy, where the host function returns the input object itself).  blend=True: each
+        canvas as `demo.add_weighted(img, 0.6, canvas, 0.4, 0)`, the image every reference program saves.  Images of any sizes, host
+        arrays or device tensors (native.Engine.render)."""
+        return self.engine.render(imgs, poses_per_image, None, blend)
+
     # ---- validation loss (reference train_coco_pose_estimation.py:129-159, labels coco_data_loader.py:208-268) --------------------
     @staticmethod
     def _check_poses(poses, what='poses'):
@@ -1025,7 +1033,8 @@ def resize_cubic_u8(img, dst_w, dst_h):
     return np.clip(out, 0, 255).astype(np.uint8)
 
 
-# ---- visualisation + CLI (reference pose_detector.py:520-579); host-only, no compute on the hot path ---------------------
+# ---- visualisation + CLI (reference pose_detector.py:520-579).  The host functions below are the contract of the device form
+# (PoseDetector.draw_batch, native.Engine.render: include/pose_mi355x.h::pmx_render) and its oracle in the tests ----------------------
 LIMB_COLORS = [
     [0, 255, 0], [0, 255, 85], [0, 255, 170], [0, 255, 255], [0, 170, 255],
     [0, 85, 255], [255, 0, 0], [255, 85, 0], [255, 170, 0], [255, 255, 0],
@@ -1096,8 +1105,7 @@ def imwrite_bgr(path, img):
     Image.fromarray(np.ascontiguousarray(img[:, :, ::-1])).save(path)
 
 
-def main(argv=None):
-    """`python -m <package>.pose_detector posenet weights.npz --img X [--gpu N] [--precise]` (reference :555-579)."""
+def parse_args(argv=None):
     import argparse
     parser = argparse.ArgumentParser(description='Pose detector')
     parser.add_argument('arch', choices=['posenet'], default='posenet', help='Model architecture')
@@ -1108,11 +1116,18 @@ def main(argv=None):
     parser.add_argument('--out', '-o', default='result.png', help='output image path')
     parser.add_argument('--precision', choices=['f32', 'f16'], default='f32',
                         help='f32 (default) or f16: the opt-in f16 inference mode (faster, accuracy contract in INTEGRATION.md section 4)')
-    args = parser.parse_args(argv)
+    parser.add_argument('--render', choices=['host', 'device'], default='host',
+                        help='where the result image is drawn: host (default, NumPy) or device (one launch; the same bytes)')
+    return parser.parse_args(argv)
+
+
+def main(argv=None):
+    """`python -m <package>.pose_detector posenet weights.npz --img X [--gpu N] [--precise] [--render device]` (reference :555-579)."""
+    args = parse_args(argv)
     pose_detector = PoseDetector(args.arch, args.weights, device=args.gpu, precise=args.precise, precision=args.precision)
     img = imread_bgr(args.img)
     poses, _ = pose_detector(img)
-    img = draw_person_pose(img, poses)
+    img = pose_detector.draw_batch([img], [poses])[0] if args.render == 'device' else draw_person_pose(img, poses)
     print('Saving result into %s...' % args.out)
     imwrite_bgr(args.out, img)
     return 0

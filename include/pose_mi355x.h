@@ -281,6 +281,46 @@ int pmx_forward_u8_boxes_images(pmx_ctx* ctx, const pmx_box_image* images, int n
 int pmx_keypoints_boxes_images(pmx_ctx* ctx, const pmx_box_image* images, int n_images, int on_device, const int* boxes6, int n,
                                double thresh, double* out);
 
+/* ---- result images: draw_person_pose (pose_detector.py:520-553), cv2.addWeighted(img, 0.6, canvas, 0.4, 0) (:574, demo.py:27) and, per
+ * person, draw_face_keypoints / draw_hand_keypoints / cv2.rectangle (demo.py:30-55) for a list of images in ONE launch -----------------------
+ * The contract is the package's own host functions, byte for byte (OpenCV's line and circle rasters are not pinned; the stand-ins are):
+ *   blend == 0      canvas = pose_detector.draw_person_pose(img, poses)
+ *   blend != 0      canvas = demo.add_weighted(img, 0.6, draw_person_pose(img, poses), 0.4, 0), then the image's parts in array order, each
+ *                   opaque over the canvas: a face (kind 0, 70 key points) as face_hand_detector.draw_face_keypoints draws it -- every valid
+ *                   key point a radius-2 disc, then the `face_line_indices` segments whose two ends are valid, thickness 1, colour
+ *                   (255, 255, 0) -- a hand (kind 1, 21 key points) as draw_hand_keypoints does -- per finger and bone the radius-3 discs of
+ *                   its valid ends, then the bone's thickness-1 segment if both are -- and last demo.draw_rectangle((left, top), (right,
+ *                   bottom), white, 1): the one-pixel outline of the box, clipped.  This is demo.render(img, poses, parts).
+ * Every host step assigns its colour to the pixels it covers, one step after the other, so a pixel holds the colour of the LAST step that
+ * covers it -- within the pose layer and within the parts layer separately; the blend sits between the two.
+ *   Poses    np.round (half to even) of x, y and v first, then int32.  Limbs 9 and 13 are skipped; a limb is drawn when the rounded v of both
+ *            joints is non-zero (thickness 2, LIMB_COLORS), all limbs of all people before the joints (radius-3 discs where the rounded v is
+ *            non-zero, JOINT_COLORS).
+ *   Segment  _draw_line in float64, every operation rounded on its own (no fused multiply-add): r = thickness / 2; the box xa = max(0,
+ *            floor(min(x1, x2) - r)) .. xb = min(w - 1, ceil(max(x1, x2) + r)), ya .. yb alike, nothing when it is empty; dx = x2 - x1,
+ *            dy = y2 - y1, L2 = dx * dx + dy * dy; for a pixel (x, y) of the box t = ((x - x1) * dx + (y - y1) * dy) / L2 clipped to [0, 1],
+ *            or 0 when L2 is not > 0; ex = x - (x1 + t * dx), ey = y - (y1 + t * dy); covered when ex * ex + ey * ey <= r * r + 0.25.
+ *   Disc     _draw_disc on the centre truncated toward zero (int()): the pixels of the box max(0, cx - R) .. min(w - 1, cx + R) (y alike)
+ *            with (x - cx)^2 + (y - cy)^2 <= R^2 in integers.
+ *   Key point  the row's (x, y) + (left, top) of its part in float64 (fractional coordinates stay fractional in the segment test).
+ *   Blend    per channel saturate(rint(img * 0.6f + c * 0.4f + 0.0f)): three float32 operations in that order, round half to even; c is the
+ *            pose layer's colour, or the image's own pixel where nothing was drawn (also for an image without people, which the host blends
+ *            with itself).
+ * images: n_images images of any sizes, host memory (read before the call returns) or device memory (on_device != 0).  poses: the people of
+ * image 0, then of image 1, ...; n_people: one count per image (NULL: nobody anywhere).  parts: each names its image; keypoints: the parts'
+ * rows (x, y, confidence, valid) end to end in part order, 70 per face and 21 per hand, in the box's own pixel frame.  out: the canvases end
+ * to end in image order (h x w x 3 bytes each), host memory, or device memory on the context's device (out_on_device != 0; it must not
+ * overlap the images).  Works on a context of any architecture and needs no weights; maps, records and retained state stay untouched.
+ * Per call: the primitive table (built on the host in drawing order, with each step's clipped box) travels with the per-image table in ONE
+ * staging copy; one launch covers the 64 x 16 pixel tiles of all images; host output comes back in one D2H copy behind ONE stream
+ * synchronisation, device input and output synchronise nothing (the buffers grow on demand, which synchronises once).
+ * PMX_ERR_INVALID, before anything is enqueued and with the offender named: a null image or one of non-positive size, a negative count, a
+ * part whose image index or kind is out of range, parts with blend == 0 (the host has no such form), a non-finite v, a non-finite
+ * coordinate or one of magnitude >= 2^30 on a joint or key point that would be drawn.  n_images == 0: nothing, PMX_OK. */
+typedef struct pmx_render_part { int image, kind /* 0 face: 70 points, 1 hand: 21 */, left, top, right, bottom; } pmx_render_part;
+int pmx_render(pmx_ctx* ctx, const pmx_box_image* images, int n_images, int on_device, const double* poses, const int* n_people,
+               const pmx_render_part* parts, int n_parts, const double* keypoints, int blend, uint8_t* out, int out_on_device);
+
 /* fused: forward_u8 + postprocess (PoseDetector.__call__, pose_detector.py:484-517, for images already
  * at the network input size; cv2.resize at :493 is the identity for them) */
 int pmx_detect_batch(pmx_ctx* ctx, const uint8_t* bgr_nhwc, int batch, int h, int w, int on_device,
