@@ -164,7 +164,7 @@ __global__ __launch_bounds__(256, 1) void conv1_wino_kernel(const ConvArgs a)
     // (an eleventh row tile would be two more 14-MFMA jobs for four pixels, on two of the four waves only).
     const float b1s = a.g[1].bias[chh * 32 + li];
     int c1_m[5], c1_pb[5];
-    float c1_hi[5];                                    // upper clamp of the tile's pixel: +inf inside the image, 0 outside (conv1_2's zero padding)
+    unsigned c1_in[5];                                 // bit mask of the tile's pixel: all ones inside the image, 0 outside (conv1_2's zero padding)
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
         const int m = ((wave >> 1) + 2 * i) * 32 + li;
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256, 1) void conv1_wino_kernel(const ConvArgs a)
         c1_m[i] = m;
         c1_pb[i] = (hy * PW + hx) * 3;
         const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
-        c1_hi[i] = ((unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W) ? __builtin_inff() : 0.f;
+        c1_in[i] = ((unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W) ? ~0u : 0u;
     }
     if (!(PMX_C1W_ABLATE & 1)) {
         const f32x16 z16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -182,21 +182,24 @@ __global__ __launch_bounds__(256, 1) void conv1_wino_kernel(const ConvArgs a)
 #pragma unroll
         for (int sg = 0; sg < 14; ++sg) pa[0][sg] = s_patch[c1_pb[0] + koff[sg]];
         // piece `sg` of the epilogue of a finished tile: quad q = sg / 3 of its 16 channels: (0) out of the accumulator + bias, (1) ReLU
-        // and mask in one median -- med3(x, 0, +inf) = max(x, 0), med3(x, 0, 0) = 0 --, (2) the 16-byte store
+        // (NaN-keeping maximum) and the padding mask as a bitwise AND: +0.0f outside the image even where the value computed there is NaN (a
+        // median, med3(x, 0, +inf | 0), did both in one instruction but returns 0 for a NaN x inside the image too) --, (2) the 16-byte store
         auto c1_finish = [&](const f32x16& acc, int i, int sg) {
             const int q = sg / 3, part = sg - 3 * q;
             if (q >= 4) return;
             if (part == 0) ev = pk_add4(f32x4{acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]}, b1[q]);
             else if (part == 1) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) ev[e] = __builtin_amdgcn_fmed3f(ev[e], 0.f, c1_hi[i]);
+                for (int e = 0; e < 4; ++e) ev[e] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, pmx_relu_nan(ev[e])) & c1_in[i]);
             } else *reinterpret_cast<f32x4*>(&s_raw[c1_m[i] * LDA + chh * 32 + 8 * q + 4 * kh]) = ev;
         };
 #pragma unroll
         for (int i = 0; i < 5; ++i) {
 #pragma unroll
             for (int sg = 0; sg < 14; ++sg) {
-                acc1[i & 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[sg], pa[i & 1][sg], sg == 0 ? z16 : acc1[i & 1], 0, 0, 0);
+                // (the 28th k is padding on BOTH sides: 0 (weight) x inf or NaN (pixel) would be NaN; selected at the use, not behind the LDS read)
+                const float pv = (sg == 13 && kh) ? 0.f : pa[i & 1][sg];
+                acc1[i & 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[sg], pv, sg == 0 ? z16 : acc1[i & 1], 0, 0, 0);
                 if (i + 1 < 5) pa[(i + 1) & 1][sg] = s_patch[c1_pb[i + 1] + koff[sg]];
                 if (i > 0) c1_finish(acc1[(i - 1) & 1], i - 1, sg);
                 __builtin_amdgcn_sched_barrier(0);
@@ -217,8 +220,8 @@ __global__ __launch_bounds__(256, 1) void conv1_wino_kernel(const ConvArgs a)
                 if (k1 < 27) accv = __builtin_fmaf(s_patch[pb + ((k1 / 9) * PW + (k1 / 3) % 3) * 3 + k1 % 3], wo, accv);
             }
             const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
-            const float hi = ((unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W) ? __builtin_inff() : 0.f;
-            s_raw[m * LDA + chh * 32 + li] = __builtin_amdgcn_fmed3f(accv + b1s, 0.f, hi);
+            const unsigned in = ((unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W) ? ~0u : 0u;
+            s_raw[m * LDA + chh * 32 + li] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, pmx_relu_nan(accv + b1s)) & in);
         }
 #pragma unroll
         for (int sg = 0; sg < 12; ++sg) c1_finish(acc1[0], 4, sg);      // (tile 4 = acc1[4 & 1])
@@ -343,7 +346,7 @@ __global__ __launch_bounds__(256, 1) void conv1_wino_kernel(const ConvArgs a)
         const f32x2 o0 = pk_add2(pk_add2(t0[0], t0[1]), t0[2]), o1 = pk_sub2(pk_sub2(t0[1], t0[2]), t0[3]);
         const f32x2 o2 = pk_add2(pk_add2(t1[0], t1[1]), t1[2]), o3 = pk_sub2(pk_sub2(t1[1], t1[2]), t1[3]);
 #pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2) pooled[2 * rp + h2] = fmaxf(fmaxf(o0[h2], o1[h2]), fmaxf(o2[h2], o3[h2]));
+        for (int h2 = 0; h2 < 2; ++h2) pooled[2 * rp + h2] = pmx_max4_nan(o0[h2], o1[h2], o2[h2], o3[h2]);
     }
     const int Hp = H >> 1, Wp = W >> 1, ldc_b = a.ldc * 4;
     const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(a.g[0].out + (s_pix_out + (size_t)bimg * Hp * Wp) * a.ldc, 0, (unsigned)(Hp * Wp * ldc_b), 0x00020000);
@@ -356,7 +359,7 @@ __global__ __launch_bounds__(256, 1) void conv1_wino_kernel(const ConvArgs a)
     for (int q = 0; q < 4; ++q) {
         f32x4 v;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = fmaxf(pooled[4 * q + e] + bq[q][e], lo);
+        for (int e = 0; e < 4; ++e) v[e] = pmx_max_nan(pooled[4 * q + e] + bq[q][e], lo);
         if (PMX_C1W_ABLATE & 16) asm volatile("" :: "v"(v));
         else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), orsrc, o + q * 32, 0, 0);
     }

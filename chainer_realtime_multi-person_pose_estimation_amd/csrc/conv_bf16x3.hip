@@ -262,7 +262,7 @@ __global__ __launch_bounds__(256, 1) void conv_bf16x3_kernel(const ConvArgs a)
                 const int p = p0 + t * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kh;
                 const int y = p / SW, x = p - y * SW;
                 float v = (t < MTA ? acc[t < MTA ? t : 0][reg] : accv[reg]) + bias;
-                if (a.relu) v = fmaxf(v, 0.f);
+                if (a.relu) v = pmx_relu_nan(v);
                 if (nok && p < SP) out_b[((size_t)y * W + sx0 + x) * a.ldc] = v;
             }
         }
@@ -276,12 +276,12 @@ __global__ __launch_bounds__(256, 1) void conv_bf16x3_kernel(const ConvArgs a)
                 float v;
                 if (t < MTA) {
                     const f32x16& A = acc[t < MTA ? t : 0];
-                    v = fmaxf(fmaxf(A[4 * g4 + 0], A[4 * g4 + 1]), fmaxf(A[4 * g4 + 2], A[4 * g4 + 3]));
+                    v = pmx_max4_nan(A[4 * g4 + 0], A[4 * g4 + 1], A[4 * g4 + 2], A[4 * g4 + 3]);
                 } else {
-                    v = fmaxf(fmaxf(accv[4 * g4 + 0], accv[4 * g4 + 1]), fmaxf(accv[4 * g4 + 2], accv[4 * g4 + 3]));
+                    v = pmx_max4_nan(accv[4 * g4 + 0], accv[4 * g4 + 1], accv[4 * g4 + 2], accv[4 * g4 + 3]);
                 }
                 v += bias;
-                if (a.relu) v = fmaxf(v, 0.f);
+                if (a.relu) v = pmx_relu_nan(v);
                 const int p = p0 + t * 32 + 8 * g4 + 4 * kh;
                 const int rp = p / (2 * SW), ox = (p - rp * 2 * SW) >> 2;
                 if (nok && p < SP) out_b[((size_t)rp * Wp + (sx0 >> 1) + ox) * a.ldc] = v;

@@ -60,7 +60,7 @@ __device__ __forceinline__ void conv_epilogue(const f32x16 (&acc)[C::MT][C::NT],
                     const int wy = q / (TW / 2), wx = q % (TW / 2);
                     const int gy = y0 + 2 * wy + (r >> 1), gx = x0 + 2 * wx + (r & 1);
                     float v = acc[t][u][reg] + bias;
-                    if (a.relu) v = fmaxf(v, 0.f);
+                    if (a.relu) v = pmx_relu_nan(v);
                     if (nok && (!C::MASK_M || m < C::M) && gy < H && gx < W) out_b[(size_t)(gy * W + gx) * a.ldc] = v;
                 }
             } else {
@@ -68,10 +68,9 @@ __device__ __forceinline__ void conv_epilogue(const f32x16 (&acc)[C::MT][C::NT],
                 float* out_b = gout + (size_t)bimg * Hp * Wp * a.ldc + n;
 #pragma unroll
                 for (int g4 = 0; g4 < 4; ++g4) {
-                    float v = fmaxf(fmaxf(acc[t][u][4 * g4 + 0], acc[t][u][4 * g4 + 1]),
-                                    fmaxf(acc[t][u][4 * g4 + 2], acc[t][u][4 * g4 + 3]));
+                    float v = pmx_max4_nan(acc[t][u][4 * g4 + 0], acc[t][u][4 * g4 + 1], acc[t][u][4 * g4 + 2], acc[t][u][4 * g4 + 3]);
                     v += bias;
-                    if (a.relu) v = fmaxf(v, 0.f);
+                    if (a.relu) v = pmx_relu_nan(v);
                     const int q = (wm * C::MT + t) * 8 + 2 * g4 + kh;
                     const int wy = q / (TW / 2), wx = q % (TW / 2);
                     const int oy = (y0 >> 1) + wy, ox = (x0 >> 1) + wx;

@@ -177,15 +177,15 @@ __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvArgs a)
                 const int q = tm * 8 + 2 * (reg >> 2) + kh, r = reg & 3;
                 const int gy = y0 + 2 * (q / (C::TW / 2)) + (r >> 1), gx = x0 + 2 * (q % (C::TW / 2)) + (r & 1);
                 float v = acc[t][reg] + bias;
-                if (a.relu) v = fmaxf(v, 0.f);
+                if (a.relu) v = pmx_relu_nan(v);
                 if (nok && gy < H && gx < W) out_b[(size_t)(gy * W + gx) * a.ldc + n] = v;
             }
         } else {
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) {
-                float v = fmaxf(fmaxf(acc[t][4 * g4 + 0], acc[t][4 * g4 + 1]), fmaxf(acc[t][4 * g4 + 2], acc[t][4 * g4 + 3]));
+                float v = pmx_max4_nan(acc[t][4 * g4 + 0], acc[t][4 * g4 + 1], acc[t][4 * g4 + 2], acc[t][4 * g4 + 3]);
                 v += bias;
-                if (a.relu) v = fmaxf(v, 0.f);
+                if (a.relu) v = pmx_relu_nan(v);
                 const int q = tm * 8 + 2 * g4 + kh;
                 const int oy = (y0 >> 1) + q / (C::TW / 2), ox = (x0 >> 1) + q % (C::TW / 2);
                 if (nok && oy < Ho && ox < Wo) out_b[(size_t)(oy * Wo + ox) * a.ldc + n] = v;

@@ -634,7 +634,7 @@ __global__ __launch_bounds__(256, 1) void conv_mfma_v6_kernel(const ConvArgs a)
                 const int p = p0 + t * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kh;
                 const int y = p / SW, x = p - y * SW;
                 float v = (t < MTA ? acc[t < MTA ? t : 0][reg] : accv[reg]) + bias;
-                if (a.relu) v = fmaxf(v, 0.f);
+                if (a.relu) v = pmx_relu_nan(v);
                 if (nok && p < SP) out_b[((size_t)y * W + sx0 + x) * a.ldc] = v;
             }
         }
@@ -649,12 +649,12 @@ __global__ __launch_bounds__(256, 1) void conv_mfma_v6_kernel(const ConvArgs a)
                 float v;
                 if (t < MTA) {
                     const f32x16& A = acc[t < MTA ? t : 0];
-                    v = fmaxf(fmaxf(A[4 * g4 + 0], A[4 * g4 + 1]), fmaxf(A[4 * g4 + 2], A[4 * g4 + 3]));
+                    v = pmx_max4_nan(A[4 * g4 + 0], A[4 * g4 + 1], A[4 * g4 + 2], A[4 * g4 + 3]);
                 } else {
-                    v = fmaxf(fmaxf(accv[4 * g4 + 0], accv[4 * g4 + 1]), fmaxf(accv[4 * g4 + 2], accv[4 * g4 + 3]));
+                    v = pmx_max4_nan(accv[4 * g4 + 0], accv[4 * g4 + 1], accv[4 * g4 + 2], accv[4 * g4 + 3]);
                 }
                 v += bias;
-                if (a.relu) v = fmaxf(v, 0.f);
+                if (a.relu) v = pmx_relu_nan(v);
                 const int p = p0 + t * 32 + 8 * g4 + 4 * kh;
                 const int rp = p / (2 * SW), ox = (p - rp * 2 * SW) >> 2;
                 if (nok && p < SP) out_b[((size_t)rp * Wp + (sx0 >> 1) + ox) * a.ldc] = v;
@@ -724,7 +724,8 @@ __global__ __launch_bounds__(256) void conv3x3_c3_kernel(const ConvArgs a)
         for (int s = 0; s < 14; ++s) {
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                const float av = s_patch[aoff[s] + t * 2 * PW * 3];
+                float av = s_patch[aoff[s] + t * 2 * PW * 3];
+                if (s == 13) av = kh ? 0.f : av;        // the 28th k is padding on BOTH sides: 0 (weight) x inf or NaN (pixel) would be NaN
 #pragma unroll
                 for (int u = 0; u < 2; ++u) acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, wv[s][u], acc[t][u], 0, 0, 0);
             }
@@ -740,7 +741,7 @@ __global__ __launch_bounds__(256) void conv3x3_c3_kernel(const ConvArgs a)
                     const int m = (reg & 3) + 8 * (reg >> 2) + 4 * kh;
                     const int gy = y0 + 4 * wave + 2 * t + (m >> 4), gx = x0 + (m & 15);
                     float v = acc[t][u][reg] + biasv[u];
-                    if (a.relu) v = fmaxf(v, 0.f);
+                    if (a.relu) v = pmx_relu_nan(v);
                     if (n < cout && gy < H && gx < W) out_b[((size_t)gy * W + gx) * a.ldc + n] = v;
                 }
             }
@@ -824,14 +825,18 @@ __global__ __launch_bounds__(256, 3) void conv1_fused_kernel(const ConvArgs a)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc1[r] = 0.f;
 #pragma unroll
-        for (int s = 0; s < 14; ++s) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(s_patch[pbase + koff[s]], wv[s], acc1, 0, 0, 0);
+        for (int s = 0; s < 14; ++s) {
+            float av = s_patch[pbase + koff[s]];
+            if (s == 13) av = kh ? 0.f : av;            // the 28th k is padding on BOTH sides: 0 (weight) x inf or NaN (pixel) would be NaN
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av, wv[s], acc1, 0, 0, 0);
+        }
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
             const int mr = rt * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kh;
             if (mr < NPX) {
                 const int ry = mr / HW, rx = mr - ry * HW;
                 const int gy = y0 - 1 + ry, gx = x0 - 1 + rx;
-                float v = fmaxf(acc1[reg] + bias1, 0.f);
+                float v = pmx_relu_nan(acc1[reg] + bias1);
                 if (!((unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W)) v = 0.f;       // conv1_2's zero padding
                 s_act[mr * LDA + ct * 32 + li] = v;
             }
@@ -1278,11 +1283,11 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const SplitKRed
             acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
         }
         if (wi == 0) best = acc;
-        else { best.x = fmaxf(best.x, acc.x); best.y = fmaxf(best.y, acc.y); best.z = fmaxf(best.z, acc.z); best.w = fmaxf(best.w, acc.w); }
+        else { best.x = pmx_max_nan(best.x, acc.x); best.y = pmx_max_nan(best.y, acc.y); best.z = pmx_max_nan(best.z, acc.z); best.w = pmx_max_nan(best.w, acc.w); }
     }
     const float4 bv = *reinterpret_cast<const float4*>(bias + c);
     best.x += bv.x; best.y += bv.y; best.z += bv.z; best.w += bv.w;
-    if (r.relu) { best.x = fmaxf(best.x, 0.f); best.y = fmaxf(best.y, 0.f); best.z = fmaxf(best.z, 0.f); best.w = fmaxf(best.w, 0.f); }
+    if (r.relu) { best.x = pmx_relu_nan(best.x); best.y = pmx_relu_nan(best.y); best.z = pmx_relu_nan(best.z); best.w = pmx_relu_nan(best.w); }
     *reinterpret_cast<float4*>(out + p * r.ldc + c) = best;
 }
 
@@ -1375,7 +1380,7 @@ __global__ __launch_bounds__(256) void conv1x1_pair_kernel(const PairArgs a)
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
             const int row = (reg & 3) + 8 * (reg >> 2) + 4 * kh;
-            sH[row * LDH + (wave * NT1 + u) * 32 + li] = fmaxf(acc[u][reg] + bias1[u], 0.f);
+            sH[row * LDH + (wave * NT1 + u) * 32 + li] = pmx_relu_nan(acc[u][reg] + bias1[u]);
         }
     __syncthreads();
     // second layer: N2T of the four waves take one 32-channel tile each over all CMID hidden channels.  WHICH waves rotates with the block:
@@ -1414,7 +1419,7 @@ __global__ __launch_bounds__(256) void conv1x1_pair_kernel(const PairArgs a)
         for (int reg = 0; reg < 16; ++reg) {
             const int row = (reg & 3) + 8 * (reg >> 2) + 4 * kh;
             float v = y[reg] + bias2;
-            if (a.relu2) v = fmaxf(v, 0.f);
+            if (a.relu2) v = pmx_relu_nan(v);
             if (p0 + row < a.npix) out[(p0 + row) * a.ldc + n] = v;
         }
     }

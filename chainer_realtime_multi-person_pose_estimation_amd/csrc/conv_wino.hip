@@ -802,14 +802,14 @@ __global__ __launch_bounds__(256, 1) void conv_wino_kernel(const ConvArgs a)
                 gy = y0 + 2 * ((mrc >> 3)) ; gx = x0 + 2 * ((mrc & 7) + 4 * kh);
             }
             if (POOL) {
-                float v = fmaxf(fmaxf(y00, y01), fmaxf(y10, y11)) + bias;
-                if (a.relu) v = fmaxf(v, 0.f);
+                float v = pmx_max4_nan(y00, y01, y10, y11) + bias;
+                if (a.relu) v = pmx_relu_nan(v);
                 const int py = gy >> 1, px = gx >> 1;
                 const int o = (py < Hp && px < Wp && nok) ? (int)__umul24(__umul24(py, Wp) + px, ldc_b) + n_b : -1;      // (24-bit operands: full-rate multiplies)
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), orsrc, o, 0, 0);
             } else {
                 y00 += bias; y01 += bias; y10 += bias; y11 += bias;
-                if (a.relu) { y00 = fmaxf(y00, 0.f); y01 = fmaxf(y01, 0.f); y10 = fmaxf(y10, 0.f); y11 = fmaxf(y11, 0.f); }
+                if (a.relu) { y00 = pmx_relu_nan(y00); y01 = pmx_relu_nan(y01); y10 = pmx_relu_nan(y10); y11 = pmx_relu_nan(y11); }
                 const int o00 = (int)__umul24(__umul24(gy, W) + gx, ldc_b) + n_b;      // (24-bit operands: full-rate multiplies; < 2^31 by the launcher's check)
                 // (run geometry: the map is a whole number of 46-column slabs and a tile column is < 23, so both pixel columns are inside)
                 const bool r0 = gy < H && nok, r1 = gy + 1 < H && nok, c0v = GEOM ? true : gx < W, c1v = GEOM ? true : gx + 1 < W;
@@ -976,11 +976,11 @@ __global__ __launch_bounds__(256) void conv_wino_tail_reduce_kernel(const WinoTa
             acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
         }
         if (kk == 0) best = acc;
-        else { best.x = fmaxf(best.x, acc.x); best.y = fmaxf(best.y, acc.y); best.z = fmaxf(best.z, acc.z); best.w = fmaxf(best.w, acc.w); }
+        else { best.x = pmx_max_nan(best.x, acc.x); best.y = pmx_max_nan(best.y, acc.y); best.z = pmx_max_nan(best.z, acc.z); best.w = pmx_max_nan(best.w, acc.w); }
     }
     const float4 bv = *reinterpret_cast<const float4*>(bias + c);
     best.x += bv.x; best.y += bv.y; best.z += bv.z; best.w += bv.w;
-    if (r.relu) { best.x = fmaxf(best.x, 0.f); best.y = fmaxf(best.y, 0.f); best.z = fmaxf(best.z, 0.f); best.w = fmaxf(best.w, 0.f); }
+    if (r.relu) { best.x = pmx_relu_nan(best.x); best.y = pmx_relu_nan(best.y); best.z = pmx_relu_nan(best.z); best.w = pmx_relu_nan(best.w); }
     if (r.pool) {
         const int Hp = r.H >> 1, Wp = r.W >> 1, py = ty, px = (sx0 >> 1) + tx;
         if (py >= Hp || px >= Wp) return;

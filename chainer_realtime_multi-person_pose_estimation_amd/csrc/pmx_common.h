@@ -34,6 +34,14 @@ static const int PMX_LIMBS[PMX_N_LIMBS][2] = {
 #define PMX_CAT_HEAT 168
 #define PMX_IN_C 16            // network input padded 3 -> 16 channels (zeros)
 
+// ---- NaN-keeping maximum (the forward contract of include/pose_mi355x.h: relu(NaN) = NaN, a 2x2 pool with a NaN input is NaN) --------
+// fmaxf and v_med3_f32 return the non-NaN operand, which turns a NaN activation into 0 (ReLU) or into a neighbour (pool); the IEEE-754-2019
+// maximum is NaN if either operand is.  gfx950: one v_maximum3_f32 per ReLU (fmaxf: one v_max_f32, two where the operand is not known to
+// be canonical), two per 4-way pool (fmaxf: three v_max_f32).
+__device__ __forceinline__ float pmx_max_nan(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+__device__ __forceinline__ float pmx_relu_nan(float v) { return __builtin_elementwise_maximum(v, 0.f); }
+__device__ __forceinline__ float pmx_max4_nan(float a, float b, float c, float d) { return pmx_max_nan(pmx_max_nan(a, b), pmx_max_nan(c, d)); }
+
 // ---- error handling ----------------------------------------------------------------------------
 void pmx_set_error(const char* fmt, ...);
 #define PMX_HIP(expr)                                                                           \

@@ -144,6 +144,15 @@ int pmx_synchronize(pmx_ctx* ctx);                    /* cuda.get_device_from_id
  *                              batch, the image's position or the segment layout: an image gives the same maps bit for bit alone,
  *                              anywhere in a uniform batch and inside a mixed-size batch (pmx_detect_images).  Accuracy against
  *                              the fp32 path: INTEGRATION.md section 4.  Any other value: PMX_ERR_INVALID, the option unchanged
+ *                              Non-finite values, all three precisions (the forward contract; tests/test_gpu_nonfinite.py): relu(v) is
+ *                              NaN if v is NaN, else max(v, +0); the 2x2 max-pool is NaN if any of its four inputs is NaN, else their
+ *                              maximum; +-inf follow IEEE arithmetic (f16 mode: saturated to +-65504 first; bf16x3 mode: the split's
+ *                              second term x - bf16(x) is inf - inf = NaN).  A direct kernel's output is non-finite exactly where
+ *                              the float reference's is (relu, max-pool and convolution of PyTorch / NumPy).  A Winograd kernel's
+ *                              output is non-finite at least there, and possibly elsewhere inside the same even-aligned 2x2 output
+ *                              tile: the transforms share the tile's 4 x 4 input patch (7x7 layers: 8 x 8) and compute inf - inf = NaN.
+ *                              No kernel is non-finite anywhere else.  A NaN weight therefore gives NaN maps and a NaN validation
+ *                              loss, never a quietly zeroed channel
  *   "f16_bn" 0 | 64 | 128      f16 mode, a test seam: output channels per block of a 3x3 / 7x7 launch.  0 (default): 128 where the launch
  *                              then still has a block per CU, else 64.  64 | 128: that width whatever the launch size (128 only for
  *                              layers whose padded channel count is a multiple of 128; the others stay at 64).  Same bits either way

@@ -14,6 +14,12 @@
 #include <math.h>
 #include <stddef.h>
 
+/* The kernels' forward contract for non-finite values (include/pose_mi355x.h): relu(v) is NaN if v is NaN, else max(v, +0); the 2x2 pool is
+ * NaN if any of its four inputs is NaN, else their maximum.  Written as comparisons (no fmaxf: it returns the non-NaN operand); on finite data
+ * the same bits as `v > 0 ? v : 0` and `b > a ? b : a`. */
+static inline float relu_nan(float v) { return (v != v || v > 0.f) ? v : 0.f; }
+static inline float max_nan(float a, float b) { return a != a ? a : (b != b || b > a) ? b : a; }
+
 /* x: [B][cin][H][W], w: [cout][cin][ks][ks], bias: [cout], y: [B][cout][Ho][Wo] (Ho = H or H/2), zero padding ks/2 */
 void conv_fma_ref(const float* x, const float* w, const float* bias, float* y, int B, int cin, int H, int W, int cout, int ks,
                   int relu, int pool, int splitk, const int* slice_chunks)
@@ -53,10 +59,10 @@ void conv_fma_ref(const float* x, const float* w, const float* bias, float* y, i
                         total = sl == 0 ? acc : total + acc;
                         }
                         const float acc = total;
-                        if (wi == 0 || acc > best) best = acc;
+                        best = wi == 0 ? acc : max_nan(best, acc);
                     }
                     float v = best + bias[n];
-                    if (relu) v = v > 0.f ? v : 0.f;
+                    if (relu) v = relu_nan(v);
                     y[(((size_t)b * cout + n) * Ho + oy) * Wo + ox] = v;
                 }
 }
@@ -236,12 +242,9 @@ void conv_wino_ref2(const float* x, const float* w, const float* bias, float* y,
                     }
                     if (pool) {
                         if (ty < Ho && tx < Wo) {
-                            float best = yv[0][0];
-                            if (yv[0][1] > best) best = yv[0][1];
-                            if (yv[1][0] > best) best = yv[1][0];
-                            if (yv[1][1] > best) best = yv[1][1];
+                            const float best = max_nan(max_nan(max_nan(yv[0][0], yv[0][1]), yv[1][0]), yv[1][1]);
                             float o = best + bias[n];
-                            if (relu) o = o > 0.f ? o : 0.f;
+                            if (relu) o = relu_nan(o);
                             y[(((size_t)b * cout + n) * Ho + ty) * Wo + tx] = o;
                         }
                     } else {
@@ -250,7 +253,7 @@ void conv_wino_ref2(const float* x, const float* w, const float* bias, float* y,
                                 const int oy = 2 * ty + i, ox = 2 * tx + j;
                                 if (oy >= H || ox >= W) continue;
                                 float o = yv[i][j] + bias[n];
-                                if (relu) o = o > 0.f ? o : 0.f;
+                                if (relu) o = relu_nan(o);
                                 y[(((size_t)b * cout + n) * H + oy) * W + ox] = o;
                             }
                     }

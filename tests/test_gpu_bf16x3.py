@@ -166,3 +166,56 @@ def test_bf16x3_detector_on_reference_images(native, name):
     for poses, scores in (out[0], out[31]):
         assert np.array_equal(np.asarray(poses), g['poses'])
         assert np.abs(np.asarray(scores) - g['scores']).max() <= 1e-4
+
+
+@pytest.mark.parametrize('k,force,W,cout,pools', [(3, 16, 36, 64, (0, 1)), (7, 15, 36, 64, (0,)),         # small-tile kernel: conv_direct.h's epilogue
+                                                  (3, 18, 46, 128, (0,)), (3, 19, 46, 128, (1,)), (7, 17, 46, 128, (0,)),     # conv_bf16x3_kernel's own
+                                                  (3, 23, 46, 128, (1,)), (7, 21, 46, 128, (0,))])                           # ... nine-tile blocks
+def test_bf16x3_nan_and_infinities(native, k, force, W, cout, pools):
+    """The forward contract for non-finite values (include/pose_mi355x.h) in the bf16x3 mode, through the ReLU and the fused 2x2 pool of
+    both epilogues (the small-tile kernel shares conv_direct.h's, the one-block-per-CU kernel conv_bf16x3_kernel -- 46-wide maps, 128
+    output channels -- has its own): a NaN activation splits into three NaN terms, so the output is NaN exactly where the float64
+    reference is; an infinite activation becomes inf - inf = NaN in the split's second term (x - bf16(x)), so the outputs whose window
+    holds it are NaN where the reference has +-inf (or relu(-inf) = 0), and nothing else is non-finite; one NaN weight at a centre tap
+    makes exactly its output channel NaN."""
+    eng = native.Engine(0, max_batch=2, max_h=368, max_w=368)
+    rng = np.random.default_rng(40 + k)
+    x = rng.standard_normal((2, 32, 12, W)).astype('f')
+    wt = (rng.standard_normal((cout, 32, k, k)) / np.sqrt(32 * k * k)).astype('f')
+    b = rng.standard_normal(cout).astype('f')
+    eng.set_option('ksplit', 1)
+    eng.set_option('force_variant_k%d' % k, force)
+    try:
+        y32 = eng.conv2d(x, wt, b, relu=True, pool=bool(pools[0]))
+        eng.set_option('precision', 1)
+        assert not np.array_equal(eng.conv2d(x, wt, b, relu=True, pool=bool(pools[0])), y32), 'the bf16x3 kernel did not run'
+        for relu, pool in ((0, 0), (1, 0), (0, 1), (1, 1)):
+            if pool not in pools:
+                continue
+            xn = x.copy()
+            xn[0, 3, 4, 5] = np.nan
+            ref = _f64_conv(xn, wt, b, bool(relu), bool(pool))
+            y = eng.conv2d(xn, wt, b, relu=bool(relu), pool=bool(pool))
+            assert np.isnan(ref).any() and np.array_equal(np.isnan(y), np.isnan(ref)) and not np.isinf(y).any(), (relu, pool)
+            fin = ~np.isnan(ref)
+            assert np.abs(y[fin] - ref[fin]).max() <= 3e-6 * np.abs(ref[fin]).max()
+            xi = xn.copy()
+            xi[0, 17, 5, 18] = np.inf
+            xi[1, 8, 6, 30] = -np.inf
+            refi = _f64_conv(xi, wt, b, bool(relu), bool(pool))
+            win = np.zeros((2, 12, W), bool)
+            for bi, yy, xx in ((0, 4, 5), (0, 5, 18), (1, 6, 30)):
+                win[bi, max(0, yy - k // 2):yy + k // 2 + 1, max(0, xx - k // 2):xx + k // 2 + 1] = True
+            if pool:
+                win = win.reshape(2, 6, 2, W // 2, 2).any(axis=(2, 4))
+            y = eng.conv2d(xi, wt, b, relu=bool(relu), pool=bool(pool))
+            bad = ~np.isfinite(y)
+            assert not (~np.isfinite(refi) & ~bad).any() and np.array_equal(bad.any(axis=1), win) and bad.all(axis=1)[win].all(), (relu, pool)
+            wn = wt.copy()
+            wn[37, 5, k // 2, k // 2] = np.nan
+            y = eng.conv2d(x, wn, b, relu=bool(relu), pool=bool(pool))
+            nan = np.zeros(y.shape, bool)
+            nan[:, 37] = True
+            assert np.array_equal(np.isnan(y), nan) and not np.isinf(y).any(), (relu, pool)
+    finally:
+        eng.close()

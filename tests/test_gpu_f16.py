@@ -271,33 +271,40 @@ def test_subnormal_lattice_is_exact(engine, kind, ks, cin):
 @pytest.mark.parametrize('ks', [3, 7])
 def test_nan_and_infinities(engine, ks):
     """f16(NaN) is NaN and f16(+-inf) is +-65504, for activations (the kernel's conversion) and weights (the host packer): the NaN
-    pattern of the output equals the emulation's, every other output is finite and within the single-layer bound.  relu = 0 and
-    pool = 0 only: the fmaxf of the ReLU and of the pool in the epilogue every kernel shares drops a NaN as every fp32 kernel of this
-    library does; that is outside the f16 contract and out of scope here."""
-    case = (ks, 32, 64, 0, 0, 2, 12, 36)
-    x, Wt, b = _layer_data(case)
-    x[0, 3, 4, 5] = np.nan
-    x[0, 17, 5, 18] = np.inf
-    x[1, 8, 6, 30] = -np.inf
-    ref = E.conv_f16(x, Wt, b)
-    nan = np.isnan(ref)
-    assert nan.sum() == 64 * ks * ks and not nan[1].any() and not np.isinf(ref).any()
-    for bn in (64, 128):
-        y = _with_f16(engine, bn, lambda: engine.conv2d(x, Wt, b))
-        assert np.array_equal(np.isnan(y), nan), (bn, int(np.isnan(y).sum()), int(nan.sum()))
-        assert not np.isinf(y).any()
-        tol = 2e-5 * max(1.0, float(np.abs(ref[~nan]).max()))
-        assert float(np.abs(y[~nan] - ref[~nan]).max()) <= tol
-    # one NaN weight (centre tap: no output's window leaves it to the padding): exactly that output channel is NaN
-    x, Wt, b = _layer_data(case)
-    Wt[37, 5, ks // 2, ks // 2] = np.nan
-    ref = E.conv_f16(x, Wt, b)
-    nan = np.zeros(ref.shape, bool)
-    nan[:, 37] = True
-    assert np.array_equal(np.isnan(ref), nan)
-    y = _with_f16(engine, 0, lambda: engine.conv2d(x, Wt, b))
-    assert np.array_equal(np.isnan(y), nan) and not np.isinf(y).any()
-    assert float(np.abs(y[~nan] - ref[~nan]).max()) <= 2e-5 * max(1.0, float(np.abs(ref[~nan]).max()))
+    pattern of the output equals the emulation's, every other output is finite and within the single-layer bound -- also through the
+    ReLU (relu(NaN) is NaN) and the fused 2x2 pool (a window with a NaN is NaN), the forward contract of include/pose_mi355x.h, at both
+    block widths."""
+    for relu, pool in ((0, 0), (1, 0), (0, 1), (1, 1)):
+        case = (ks, 32, 64, relu, pool, 2, 12, 36)
+        x, Wt, b = _layer_data(case)
+        x[0, 3, 4, 5] = np.nan
+        x[0, 17, 5, 18] = np.inf
+        x[1, 8, 6, 30] = -np.inf
+        ref = E.conv_f16(x, Wt, b, relu, pool)
+        nan = np.isnan(ref)
+        win = np.zeros((12, 36), bool)                       # the outputs whose window holds the NaN, pooled: any of the four
+        win[max(0, 4 - ks // 2):4 + ks // 2 + 1, max(0, 5 - ks // 2):5 + ks // 2 + 1] = True
+        if pool:
+            win = win.reshape(6, 2, 18, 2).any(axis=(1, 3))
+        assert win.sum() == (ks * ks if not pool else {3: 4, 7: 16}[ks])
+        assert np.array_equal(nan[0], np.broadcast_to(win, nan[0].shape)) and not nan[1].any() and not np.isinf(ref).any()
+        for bn in (64, 128):
+            y = _with_f16(engine, bn, lambda: engine.conv2d(x, Wt, b, relu=bool(relu), pool=bool(pool)))
+            assert np.array_equal(np.isnan(y), nan), (relu, pool, bn, int(np.isnan(y).sum()), int(nan.sum()))
+            assert not np.isinf(y).any()
+            tol = 2e-5 * max(1.0, float(np.abs(ref[~nan]).max()))
+            assert float(np.abs(y[~nan] - ref[~nan]).max()) <= tol, (relu, pool, bn)
+        # one NaN weight (centre tap: no output's window leaves it to the padding): exactly that output channel is NaN
+        x, Wt, b = _layer_data(case)
+        Wt[37, 5, ks // 2, ks // 2] = np.nan
+        ref = E.conv_f16(x, Wt, b, relu, pool)
+        nan = np.zeros(ref.shape, bool)
+        nan[:, 37] = True
+        assert np.array_equal(np.isnan(ref), nan)
+        for bn in (0, 64, 128) if relu or pool else (0,):
+            y = _with_f16(engine, bn, lambda: engine.conv2d(x, Wt, b, relu=bool(relu), pool=bool(pool)))
+            assert np.array_equal(np.isnan(y), nan) and not np.isinf(y).any(), (relu, pool, bn)
+            assert float(np.abs(y[~nan] - ref[~nan]).max()) <= 2e-5 * max(1.0, float(np.abs(ref[~nan]).max()))
 
 
 def _net_maps(native, seed, h, w, precision):
