@@ -921,11 +921,14 @@ int conv_allow_big_lds(const void* kern, bool (&done)[PMX_MAX_DEVICES])
 
 // minimum dynamic LDS per block: caps the number of co-resident blocks per CU (the fp32 MFMA pipe
 // loses ~20% with 3+ waves per SIMD)
-static int g_min_lds = 0;
-void conv_set_min_lds(int bytes) { g_min_lds = bytes; }
-static int g_v5_lds = 56 * 1024;     // dynamic LDS floor of the v5 kernels: 3 x 56 KB > 160 KB -> at most 2 blocks per CU
-void conv_set_v5_lds(int bytes) { g_v5_lds = bytes; }
-int conv_v5_lds() { return g_v5_lds; }
+// process-wide switches, set through any context (pmx_set_option): relaxed atomics, as g_num_cus below -- a set_option in one thread and a
+// launch in another read or write a whole int
+static std::atomic<int> g_min_lds{0};
+void conv_set_min_lds(int bytes) { g_min_lds.store(bytes, std::memory_order_relaxed); }
+static int conv_min_lds() { return g_min_lds.load(std::memory_order_relaxed); }
+static std::atomic<int> g_v5_lds{56 * 1024};    // dynamic LDS floor of the v5 kernels: 3 x 56 KB > 160 KB -> at most 2 blocks per CU
+void conv_set_v5_lds(int bytes) { g_v5_lds.store(bytes, std::memory_order_relaxed); }
+int conv_v5_lds() { return g_v5_lds.load(std::memory_order_relaxed); }
 
 // ---- variant table ---------------------------------------------------------------------------------------
 // {ksize, tile rows (v6: row tiles per block), tile cols (v6: 32), BN, CK, name}
@@ -1218,7 +1221,8 @@ static int launch_cfg(const ConvArgs& a0, int groups, hipStream_t stream)
     auto kern = conv_mfma_kernel<KS, TH, TW, BN, CK, WM, WN>;
     static bool attr_set[PMX_MAX_DEVICES] = {};
     if (int rc = conv_allow_big_lds(reinterpret_cast<const void*>(kern), attr_set)) return rc;
-    const int lds = C::LDS_BYTES > g_min_lds ? C::LDS_BYTES : g_min_lds;
+    const int min_lds = conv_min_lds();
+    const int lds = C::LDS_BYTES > min_lds ? C::LDS_BYTES : min_lds;
     dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.B), (unsigned)(a.cout_pad / BN), (unsigned)groups);
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, a);
     PMX_HIP(hipGetLastError());
@@ -1237,8 +1241,9 @@ static int launch_v5(const ConvArgs& a0, int groups, hipStream_t stream)
     PMX_CHECK((long long)a.H * a.W * a.lda < (1ll << 31), PMX_ERR_INVALID, "conv: image too large for 32-bit offsets");
     auto kern = conv_mfma_v5_kernel<KS, TH, TW, BN, CK, WM, WN>;
     int lds = 2 * C::IN_ELEMS * 4;
-    if (lds < g_v5_lds) lds = g_v5_lds;
-    if (lds < g_min_lds) lds = g_min_lds;
+    const int v5_lds = conv_v5_lds(), min_lds = conv_min_lds();
+    if (lds < v5_lds) lds = v5_lds;
+    if (lds < min_lds) lds = min_lds;
     static bool attr_set[PMX_MAX_DEVICES] = {};
     if (int rc = conv_allow_big_lds(reinterpret_cast<const void*>(kern), attr_set)) return rc;
     if (a.ksplit < 1) a.ksplit = 1;

@@ -1165,8 +1165,13 @@ extern "C" int pmx_forward_u8_resized(pmx_ctx* c, const uint8_t* img, int B, int
     std::vector<int> tab(ntab);
     pmx_make_resize_table(w, src_w, tab.data());
     pmx_make_resize_table(h, src_h, tab.data() + 4 * w);
-    PMX_HIP(hipStreamSynchronize(c->stream));     // the table buffer may still be in use by a queued resize
-    PMX_HIP(hipMemcpy(c->rs_tab, tab.data(), ntab * sizeof(int), hipMemcpyHostToDevice));
+    const int key[4] = {src_h, src_w, h, w};
+    if (memcmp(key, c->rs_key, sizeof key)) {      // a call with the sizes of the last one finds its tables on the device and only enqueues
+        c->rs_key[0] = 0;                          // (until the upload below is complete)
+        PMX_HIP(hipStreamSynchronize(c->stream));     // the table buffer may still be in use by a queued resize
+        PMX_HIP(hipMemcpy(c->rs_tab, tab.data(), ntab * sizeof(int), hipMemcpyHostToDevice));
+        memcpy(c->rs_key, key, sizeof key);
+    }
     if (c->prof_on == 1 && (rc = prof_begin(c, "resize_u8|resize_linear_u8", 0, (double)nsrc + (double)B * h * w * 3))) return rc;
     if ((rc = launch_resize_linear_u8(d, c->u8_tmp, c->rs_tab, c->rs_tab + 4 * w, B, src_h, src_w, h, w, c->stream))) return rc;
     if ((rc = prof_end(c))) return rc;

@@ -239,6 +239,7 @@ struct pmx_ctx {
     const uint8_t* in_u8 = nullptr; float in_div = 255.0f;      // set for ONE forward: conv1_wino_kernel preprocesses this uint8 batch itself
     DevBuf<uint8_t> u8_src;          // original-size images awaiting the on-device resize
     DevBuf<int> rs_tab;              // resize tables: x (4 * dw ints) then y (4 * dh ints)
+    int rs_key[4] = {0, 0, 0, 0};    // (src_h, src_w, h, w) of the tables rs_tab holds; all 0: none
     // state of the last forward / set_maps
     bool maps_valid = false, maps_external = false;
     int cur_B = 0, cur_fh = 0, cur_fw = 0;

@@ -11,7 +11,9 @@
  * Conventions: plain pointers and sizes only (no torch / HIP types in signatures; a HIP stream is
  * passed as void*).  Every function returns PMX_OK (0) or an error code; no exceptions cross the ABI;
  * pmx_last_error() returns a thread-local message for the last failing call.  One context per host
- * thread / stream; calls on a context are stream-ordered and asynchronous unless stated.
+ * thread / stream; calls on a context are stream-ordered and asynchronous unless stated.  Contexts of different host threads may be created,
+ * used and destroyed concurrently (never one context from two threads at once) and give the bits they give alone; the only state they share
+ * is the four process-wide test switches named at pmx_set_option.
  * There is NO CPU fallback: pmx_create fails with PMX_ERR_NO_DEVICE when no gfx950 device is present.
  */
 #ifndef POSE_MI355X_H
@@ -90,7 +92,13 @@ int pmx_create(pmx_ctx** out, int device, int max_batch, int max_h, int max_w);
  * arch = "posenet" (models/CocoPoseNet.py), "facenet" (models/FaceNet.py, 71 maps) or "handnet" (models/HandNet.py, 22 maps). */
 int pmx_create_net(pmx_ctx** out, const char* arch, int device, int max_batch, int max_h, int max_w);
 void pmx_destroy(pmx_ctx* ctx);
-int pmx_set_stream(pmx_ctx* ctx, void* hip_stream);   /* NULL -> the context's own stream */
+/* Puts the context on a stream of the caller's (synchronises the stream it leaves).  From then on every launch and copy of the context --
+ * the lanes of detect_precise fork from and join that stream -- is ordered after what the caller enqueued on it before the call and before
+ * what the caller enqueues after it: device inputs (`on_device`) need no host synchronisation after their producer on that stream, device
+ * outputs (pmx_render canvases, pmx_results_snapshot, the prepared samples) none before their consumer on it.  A handle of 0 / NULL selects
+ * the context's OWN stream (created non-blocking): the legacy default stream cannot be given.  torch's default stream has the handle 0, so
+ * a caller working on it must synchronise around the calls or use a side stream (torch.cuda.Stream()) for them. */
+int pmx_set_stream(pmx_ctx* ctx, void* hip_stream);
 int pmx_synchronize(pmx_ctx* ctx);                    /* cuda.get_device_from_id().synchronize(), :506 */
 /* Test / measurement knobs (defaults are the product configuration):
  *   "kernel_gen" 1 | 5 | 6     conv kernel generation: 1 = LDS-staged weights (v1) everywhere, 5 = v5 for 3x3 / 7x7,
@@ -168,6 +176,7 @@ int pmx_synchronize(pmx_ctx* ctx);                    /* cuda.get_device_from_id
  *                              (default 1; takes effect for lanes created afterwards, i.e. set it before the first detect_precise); same bits
  *   "precise_table_cap" n      detect_precise: cached cubic tables at which the next pmx_precise_begin* starts the cache over (default 208)
  *   "cubic_rows" 1 | 0         detect_precise's float32 cubic resizes: separable through LDS (default) | one thread per element; same bits
+ *                              (process-wide, see the end of this list)
  *   "conv1_wino" 1 | 0 | 2     that launch with conv1_2 as Winograd F(2x2, 3x3) on 16 x 16 squares (default 1: where "conv_algo" >= 1
  *                              and the launch has a block per CU; 2: whatever the launch size); 0: the direct 8 x 16 tiles everywhere
  *   "fuse_pairs" 1 | 0         the two 1x1 layers that end every stage as one launch (default) or as two; identical bits
@@ -183,7 +192,10 @@ int pmx_synchronize(pmx_ctx* ctx);                    /* cuda.get_device_from_id
  *   "peaks_gpu_branch"         the reference's GPU-branch peak extraction (17 x 17 un-normalised kernel, zero pad, >=)
  *   "pp_limbs_slices" -1 | n   blocks per (limb, image) of the candidate-pair scan: -1 (default) = 8 where the maps come at full
  *                              resolution (detect_precise, pmx_set_maps), one block otherwise; 0 / 1 = one block; same results
- *   "conv_min_lds", "conv_v5_lds", "pp_generic"   ablation switches, PROCESS-wide (not per context) */
+ *   "conv_min_lds", "conv_v5_lds", "pp_generic"   ablation switches
+ * PROCESS-wide, not per context: "pp_generic", "conv_min_lds", "conv_v5_lds" and "cubic_rows".  Setting one through any context changes it for
+ * every context of the process, other threads' included, from their next launch on (whole-int atomic reads and writes, no other ordering).
+ * All four choose between kernel forms that compute the same bits: switches for tests and tuning, not configuration. */
 int pmx_set_option(pmx_ctx* ctx, const char* key, int value);
 
 /* ---- weights: serializers.load_npz (pose_detector.py:26) --------------------------------------
