@@ -305,6 +305,7 @@ extern "C" void pmx_destroy(pmx_ctx* c)
     if (c->bx_copied) (void)hipEventDestroy(c->bx_copied);
     if (c->sp_copied) (void)hipEventDestroy(c->sp_copied);
     if (c->rd_copied) (void)hipEventDestroy(c->rd_copied);
+    if (c->mk_copied) (void)hipEventDestroy(c->mk_copied);
     if (c->tr.seg_copied) (void)hipEventDestroy(c->tr.seg_copied);
     for (auto& p : c->pending) { (void)hipEventDestroy(p.e0); (void)hipEventDestroy(p.e1); }
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);

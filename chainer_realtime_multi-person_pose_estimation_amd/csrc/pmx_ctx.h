@@ -353,6 +353,13 @@ struct pmx_ctx {
     hipEvent_t rd_copied = nullptr; bool rd_pending = false;
     DevBuf<char> rd_dev;
     DevBuf<uint8_t> rd_img, rd_out;
+    // pmx_masks.hip (ignore masks).  mk_host / mk_dev: the per-call block [image table | parts | vertices | running sums], ONE copy from
+    // pinned memory (`mk_copied` marks when the host side may be rewritten); mk_out: the masks end to end when the caller's output is host
+    // memory.  All grow on demand.
+    HostBuf<char> mk_host;
+    hipEvent_t mk_copied = nullptr; bool mk_pending = false;
+    DevBuf<char> mk_dev;
+    DevBuf<uint8_t> mk_out;
     BwState bw;                                          // pmx_backward.hip
     TrainState tr;                                        // pmx_train.hip
 };

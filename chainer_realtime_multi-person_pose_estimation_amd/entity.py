@@ -26,6 +26,7 @@ _LIMBS = ('Neck-RightWaist RightWaist-RightKnee RightKnee-RightFoot Neck-LeftWai
 params = dict(
     downscale=8,                                  # reference entity.py:59
     insize=368, paf_sigma=8, heatmap_sigma=7,     # label maps of the validation loss (reference entity.py:58-61)
+    min_keypoints=5, min_area=32 * 32,            # an annotation with fewer key points or no larger area is no training person (entity.py:56-57)
     # inference keys, reference entity.py:71-84
     inference_img_size=368, inference_scales=[0.5, 1, 1.5, 2], heatmap_size=320,
     gaussian_sigma=2.5, ksize=17,

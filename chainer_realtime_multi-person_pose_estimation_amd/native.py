@@ -30,7 +30,7 @@ SOURCES = [('pmx_api.hip', []), ('pmx_precise.hip', []), ('pmx_multi.hip', []), 
            ('pmx_samples.hip', ['-ffp-contract=off']), ('conv_bwd.hip', ['-ffp-contract=off']),
            ('pmx_backward.hip', ['-ffp-contract=off']), ('pmx_packs.hip', ['-ffp-contract=off']),
            ('pmx_train.hip', ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt']),
-           ('pmx_render.hip', ['-ffp-contract=off'])]
+           ('pmx_render.hip', ['-ffp-contract=off']), ('pmx_masks.hip', ['-ffp-contract=off'])]
 # the opt-in bf16x3 kernels (option "precision" = 1; DESIGN.md 4.1.5: frozen, slower than the fp32 Winograd path) are NOT part of the
 # default library: PMX_BUILD_BF16X3=1 in the environment of the build adds their translation unit (the stamp then differs, so the
 # library is rebuilt when the variable changes)
@@ -77,6 +77,16 @@ class PmxBoxImage(C.Structure):
 class PmxRenderPart(C.Structure):
     """include/pose_mi355x.h::pmx_render_part -- one face (kind 0) or hand (kind 1) of a pmx_render call."""
     _fields_ = [('image', C.c_int), ('kind', C.c_int), ('left', C.c_int), ('top', C.c_int), ('right', C.c_int), ('bottom', C.c_int)]
+
+
+class PmxMaskImage(C.Structure):
+    """include/pose_mi355x.h::pmx_mask_image -- one image of a pmx_coco_masks call: its size and its range of the part table."""
+    _fields_ = [('h', C.c_int32), ('w', C.c_int32), ('part0', C.c_int32), ('n_parts', C.c_int32)]
+
+
+class PmxMaskPart(C.Structure):
+    """include/pose_mi355x.h::pmx_mask_part -- one polygon (kind 0) or run-length (kind 1) part of an annotation's segmentation."""
+    _fields_ = [('kind', C.c_int32), ('ann', C.c_int32), ('cls', C.c_int32), ('off', C.c_int32), ('len', C.c_int32), ('reserved', C.c_int32)]
 
 
 class PmxSample(C.Structure):
@@ -278,6 +288,8 @@ def load():
         'pmx_forward_u8_boxes_images': (ci, [vp, vp, ci, ci, vp, ci]),
         'pmx_keypoints_boxes_images': (ci, [vp, vp, ci, ci, vp, ci, cd, vp]),
         'pmx_render': (ci, [vp, vp, ci, ci, vp, vp, vp, ci, vp, ci, vp, ci]),
+        'pmx_coco_masks': (ci, [vp, vp, ci, vp, ci, vp, C.c_size_t, vp, C.c_size_t, vp, vp, ci]),
+        'pmx_coco_masks_strip': (ci, [ci]),
         'pmx_precise_begin': (ci, [vp, ci, ci]),
         'pmx_precise_add_scale': (ci, [vp, vp, ci, ci]),
         'pmx_precise_finish': (ci, [vp]),
@@ -441,6 +453,45 @@ def render_args(imgs, poses_per_image, parts_per_image=None, blend=True):
         parts[k].image, parts[k].kind, parts[k].left, parts[k].top, parts[k].right, parts[k].bottom = f
     kps = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 4)), dtype=np.float64)
     return poses, np.ascontiguousarray(n_people, dtype=np.int32), parts, len(flat), kps
+
+
+def coco_mask_tables(sizes, parts_per_image):
+    """The arguments of Engine.coco_masks checked and flattened for pmx_coco_masks, without touching the device: (images (n, 4) int32 rows
+    (h, w, part0, n_parts), parts (m, 6) int32 rows (kind, ann, cls, off, len, 0), the vertices float64, the counts uint32).  sizes: (h, w) per
+    image; parts_per_image: per image the list coco.mask_parts gives, (kind, annotation index, class, data).  ValueError for lists whose
+    lengths differ or none at all; what a part may hold is the library's to check."""
+    sizes = [(int(h), int(w)) for h, w in sizes]
+    if len(sizes) == 0:
+        raise ValueError('coco_masks needs at least one image')
+    if len(parts_per_image) != len(sizes):
+        raise ValueError('one list of parts per image (%d for %d images)' % (len(parts_per_image), len(sizes)))
+    images, parts, xy, counts = [], [], [], []
+    n_xy = n_counts = 0
+    for (h, w), plist in zip(sizes, parts_per_image):
+        images.append((h, w, len(parts), len(plist)))
+        for kind, ann, cls, data in plist:
+            if int(kind) == 0:
+                data = np.asarray(data, dtype=np.float64).reshape(-1)
+                parts.append((0, int(ann), int(cls), n_xy, data.size, 0))
+                xy.append(data)
+                n_xy += data.size
+            else:
+                data = np.asarray(data, dtype=np.int64).reshape(-1)
+                if data.size and (data.min() < 0 or data.max() >= 2 ** 32):
+                    raise ValueError('run-length counts outside uint32')
+                parts.append((int(kind), int(ann), int(cls), n_counts, data.size, 0))
+                counts.append(data.astype(np.uint32))
+                n_counts += data.size
+    if max(n_xy, n_counts, len(parts)) >= 2 ** 31:
+        raise ValueError('coco_masks: tables beyond int32 offsets')
+    return (np.ascontiguousarray(images, dtype=np.int32).reshape(-1, 4), np.ascontiguousarray(parts, dtype=np.int32).reshape(-1, 6),
+            np.ascontiguousarray(np.concatenate(xy) if xy else np.zeros(0), dtype=np.float64),
+            np.ascontiguousarray(np.concatenate(counts) if counts else np.zeros(0), dtype=np.uint32))
+
+
+def coco_masks_strip(h):
+    """columns one block of pmx_coco_masks owns for an image of height h (tests place widths around it)"""
+    return int(load().pmx_coco_masks_strip(int(h)))
 
 
 class Engine(object):
@@ -787,6 +838,34 @@ class Engine(object):
         for im, n in zip(imgs, sizes):
             out.append(flat[off:off + n].reshape(tuple(im.shape)))
             off += n
+        return out
+
+    # ---- ignore masks (pmx_coco_masks) ----------------------------------------------------------------
+    def coco_masks(self, sizes, parts_per_image, device=False):
+        """gen_masks of the reference's gen_ignore_mask.py for a batch of images in one launch, byte for byte what coco.masks_numpy gives.
+        sizes: (h, w) per image; parts_per_image: per image the list of coco.mask_parts.  -> (mask_miss, mask_all), each a list of (h, w)
+        bool arrays; device=True: lists of uint8 torch tensors (0 | 1) on the context's device, views of one allocation -- nothing is
+        copied to the host and nothing synchronises: the masks are complete once the context's stream has run the call (as render's
+        canvases).  Argument errors raise ValueError before the device is touched."""
+        images, parts, xy, counts = coco_mask_tables(sizes, parts_per_image)
+        n_px = [int(h) * int(w) for h, w in images[:, :2]]
+        total = sum(n_px)
+        if device:
+            import torch
+            flat = torch.empty((2, max(total, 1)), dtype=torch.uint8, device=torch.device('cuda', self.device))
+            ptrs = (C.c_void_p(flat[0].data_ptr()), C.c_void_p(flat[1].data_ptr()))
+        else:
+            flat = np.empty((2, max(total, 1)), np.uint8)
+            ptrs = (_ptr(flat[0]), _ptr(flat[1]))
+        self._check(self.lib.pmx_coco_masks(self._ctx, _ptr(images), len(images), _ptr(parts), len(parts), _ptr(xy), xy.size, _ptr(counts),
+                                            counts.size, ptrs[0], ptrs[1], int(bool(device))))
+        out = ([], [])
+        for k in range(2):
+            off = 0
+            for (h, w), n in zip(images[:, :2], n_px):
+                m = flat[k, off:off + n].reshape(int(h), int(w))
+                out[k].append(m if device else m.astype(bool))
+                off += n
         return out
 
     def set_maps(self, paf, heat):
@@ -1223,21 +1302,40 @@ class Engine(object):
     # ---- sample preparation (include/pose_mi355x.h: pmx_samples_*) ---------------------------------------------------
     def samples_prepare(self, imgs, masks, records, insize):
         """imgs: uint8 (h, w, 3) arrays of any sizes; masks: per image an (h, w) array (non-zero = ignored) or None; records:
-        samples.SampleRecord per image.  The prepared samples stay on the device (samples_get, validate_samples).  Asynchronous."""
+        samples.SampleRecord per image.  The prepared samples stay on the device (samples_get, validate_samples).  Asynchronous.
+        All-device input: every image and every mask a contiguous uint8 torch tensor on the context's device (masks as coco_masks(device=True)
+        gives them); nothing visits the host, and the tensors must stay alive until the stream has run the call.  A mix of host arrays and
+        device tensors raises ValueError."""
         from . import samples as S
         n = len(imgs)
         arr = (PmxSample * max(n, 1))()
         keep = []
+        given = list(imgs) + [m for m in (masks or []) if m is not None]
+        dev = [hasattr(a, 'data_ptr') for a in given]
+        if any(dev) != all(dev):
+            raise ValueError('samples_prepare: the images and masks of one call are all host arrays or all device tensors')
+        on_device = int(bool(dev) and dev[0])
+        for i, a in enumerate(given if on_device else []):
+            if str(a.dtype) != 'torch.uint8' or not a.is_cuda or not a.is_contiguous() or (a.device.index or 0) != self.device:
+                raise ValueError("samples_prepare: device input %d is no contiguous uint8 tensor on the context's device" % i)
         for i in range(n):
-            img = np.ascontiguousarray(imgs[i], dtype=np.uint8)
             rec = records[i]
             s = arr[i]
-            keep.append(img)
-            s.bgr, s.src_h, s.src_w = _ptr(img), img.shape[0], img.shape[1]
-            if masks is not None and masks[i] is not None:
-                m = np.ascontiguousarray(np.asarray(masks[i]) != 0, dtype=np.uint8)
-                keep.append(m)
-                s.mask = _ptr(m)
+            if on_device:
+                img = imgs[i]
+                keep.append(img)
+                s.bgr, s.src_h, s.src_w = img.data_ptr(), int(img.shape[0]), int(img.shape[1])
+                if masks is not None and masks[i] is not None:
+                    keep.append(masks[i])
+                    s.mask = masks[i].data_ptr()
+            else:
+                img = np.ascontiguousarray(imgs[i], dtype=np.uint8)
+                keep.append(img)
+                s.bgr, s.src_h, s.src_w = _ptr(img), img.shape[0], img.shape[1]
+                if masks is not None and masks[i] is not None:
+                    m = np.ascontiguousarray(np.asarray(masks[i]) != 0, dtype=np.uint8)
+                    keep.append(m)
+                    s.mask = _ptr(m)
             if rec.resized is not None:
                 s.resized_w, s.resized_h = rec.resized
             if rec.R is not None:
@@ -1248,8 +1346,9 @@ class Engine(object):
             if rec.distort is not None:
                 s.has_distort, s.delta = 1, (C.c_int32 * 3)(*rec.distort)
             s.flip = int(rec.flip)
-        self._check(self.lib.pmx_samples_prepare(self._ctx, C.cast(arr, C.c_void_p), n, int(insize), 0))
+        self._check(self.lib.pmx_samples_prepare(self._ctx, C.cast(arr, C.c_void_p), n, int(insize), on_device))
         self._samples = (n, int(insize))
+        self._samples_keep = keep if on_device else None          # device sources: alive until the next call replaces them
 
     def samples_get(self):
         """(images (n, insize, insize, 3) uint8, dilated masks (n, insize, insize) bool) of the last samples_prepare (synchronises)."""

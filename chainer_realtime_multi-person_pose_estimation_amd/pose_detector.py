@@ -831,7 +831,18 @@ class PoseDetector(object):
     @staticmethod
     def _check_sample_args(imgs, poses_per_image, ignore_masks, insize, mode, records):
         from . import samples as S
-        imgs = [np.asarray(im) for im in imgs]
+        # all-device input (contiguous uint8 torch tensors on the GPU; native.Engine.samples_prepare checks the rest) stays where it is
+        given = list(imgs) + [m for m in (ignore_masks or []) if m is not None]
+        dev = [hasattr(a, 'data_ptr') for a in given]
+        if any(dev) != all(dev):
+            raise ValueError('prepare_samples: the images and masks of one call are all host arrays or all device tensors')
+        on_device = bool(dev) and dev[0]
+        for a in (given if on_device else []):
+            if str(a.dtype) != 'torch.uint8' or not a.is_cuda or not a.is_contiguous():
+                raise ValueError('prepare_samples: a device image or mask is a contiguous uint8 tensor on the GPU')
+        as_array = (lambda a: a) if on_device else np.asarray
+        is_u8 = (lambda a: True) if on_device else (lambda a: a.dtype == np.uint8)
+        imgs = [as_array(im) for im in imgs]
         if len(imgs) == 0:
             raise ValueError('prepare_samples needs at least one image')
         if mode not in ('val', 'train'):
@@ -843,7 +854,7 @@ class PoseDetector(object):
         if insize < 8 or insize % 8:
             raise ValueError('prepare_samples: insize must be a positive multiple of 8, got %d' % insize)
         for im in imgs:
-            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 or min(im.shape[:2]) < 1:
+            if not is_u8(im) or len(im.shape) != 3 or im.shape[2] != 3 or min(im.shape[:2]) < 1:
                 raise ValueError('prepare_samples needs uint8 H x W x 3 images')
         if len(poses_per_image) != len(imgs):
             raise ValueError('prepare_samples: %d images but poses for %d' % (len(imgs), len(poses_per_image)))
@@ -853,10 +864,10 @@ class PoseDetector(object):
         if ignore_masks is not None:
             if len(ignore_masks) != len(imgs):
                 raise ValueError('prepare_samples: %d images but %d ignore masks' % (len(imgs), len(ignore_masks)))
-            masks = [None if m is None else np.asarray(m) for m in ignore_masks]
+            masks = [None if m is None else as_array(m) for m in ignore_masks]
             for i, m in enumerate(masks):
-                if m is not None and m.shape != imgs[i].shape[:2]:
-                    raise ValueError('ignore mask %d: shape %r, expected %r' % (i, m.shape, imgs[i].shape[:2]))
+                if m is not None and tuple(m.shape) != tuple(imgs[i].shape[:2]):
+                    raise ValueError('ignore mask %d: shape %r, expected %r' % (i, tuple(m.shape), tuple(imgs[i].shape[:2])))
         if records is not None:
             if len(records) != len(imgs):
                 raise ValueError('prepare_samples: %d images but %d records' % (len(imgs), len(records)))
@@ -864,7 +875,7 @@ class PoseDetector(object):
                 if not isinstance(r, S.SampleRecord):
                     raise ValueError('record %d is no SampleRecord' % i)
                 r.check()
-                if r.src_hw != imgs[i].shape[:2] or r.insize != insize:
+                if tuple(r.src_hw) != tuple(imgs[i].shape[:2]) or r.insize != insize:
                     raise ValueError('record %d is for a %r image at insize %d, the image is %r at %d'
                                      % (i, r.src_hw, r.insize, imgs[i].shape[:2], insize))
         return imgs, poses, masks, insize
@@ -874,13 +885,15 @@ class PoseDetector(object):
         if records is not None:
             return list(records)
         if mode == 'val':
-            return [S.SampleRecord.val(im.shape[:2], insize) for im in imgs]
-        return [S.draw_augmentation(im.shape[:2], p, insize) for im, p in zip(imgs, poses)]
+            return [S.SampleRecord.val(tuple(im.shape[:2]), insize) for im in imgs]
+        return [S.draw_augmentation(tuple(im.shape[:2]), p, insize) for im, p in zip(imgs, poses)]
 
     def prepare_samples(self, imgs, poses_per_image, ignore_masks=None, insize=368, mode='val', records=None):
         """`CocoDataLoader.generate_labels` without the label maps (coco_data_loader.py:334-341): the pixels on the device, the poses on the
         host.  imgs: uint8 BGR images of any sizes; poses_per_image: per image (n, 18, 3) INTEGER rows (x, y, v) in that image's pixels (the
         reference keeps int32 poses); ignore_masks: per image an (h, w) array at the image's size (non-zero = ignored) or None.
+        Images and masks may instead ALL be contiguous uint8 torch tensors on the engine's GPU (masks of 0 | 1, as ignore_masks(device=True)
+        gives them): they are read where they are; a mix of host arrays and device tensors raises ValueError.
         mode 'val': the resize to insize x insize; mode 'train': the reference's augmentation, drawn from `random` / `np.random` in its
         order (samples.draw_augmentation) unless `records` (samples.SampleRecord per image) gives every step.
         -> (images (B, insize, insize, 3) uint8, list of int32 poses in the samples' pixels, dilated masks (B, insize, insize) bool)."""
@@ -898,6 +911,19 @@ class PoseDetector(object):
             out_i.append(a)
             out_m.append(m)
         return np.concatenate(out_i), [S.transform_poses(p, r) for p, r in zip(poses, recs)], np.concatenate(out_m)
+
+    def ignore_masks(self, annotations_per_image, sizes, device=False):
+        """The ignore masks `gen_ignore_mask.py` writes as PNG files (gen_masks' mask_miss, :23-37), rasterised on the device in one launch
+        for a batch of images: annotations_per_image: per image ALL its annotation dictionaries in file order (CocoKeypoints.annotations);
+        sizes: (h, w) per image.  -> a list of (h, w) bool arrays, or with device=True of uint8 tensors (0 | 1) on the engine's GPU that
+        prepare_samples takes as they are.  Malformed segmentations raise ValueError (coco.mask_parts)."""
+        from . import coco
+        if self.model is not None:
+            raise RuntimeError('ignore_masks runs on the built-in engine: not available with a model= callable')
+        if len(annotations_per_image) != len(sizes):
+            raise ValueError('ignore_masks: annotations for %d images, %d sizes' % (len(annotations_per_image), len(sizes)))
+        parts = [coco.mask_parts(anns, h, w) for anns, (h, w) in zip(annotations_per_image, sizes)]
+        return self.engine.coco_masks(sizes, parts, device=device)[0]
 
     def validation_loss_raw(self, imgs, poses_per_image, ignore_masks=None, insize=368):
         """`validation_loss` for raw validation data: images of any sizes, integer poses in each image's pixels, ignore masks at each

@@ -528,6 +528,46 @@ int pmx_get_samples(pmx_ctx* ctx, uint8_t* bgr, uint8_t* mask, int n, int insize
  * prepared samples; out13 as pmx_validate_batch.  PMX_ERR_STATE without prepared samples.  Synchronises. */
 int pmx_validate_samples(pmx_ctx* ctx, const double* poses, const int* n_people, double* out13);
 
+/* ---- ignore masks from COCO segmentations (csrc/pmx_masks.hip) ----------------------------------------------------------------------
+ * gen_masks of the reference's gen_ignore_mask.py (:23-37) for a batch of images of any sizes in ONE launch: per image `mask_all` (the
+ * union of every annotation's mask) and `mask_miss` (what the loss ignores: the PNG the reference saves), h x w bytes of 0 | 1 each,
+ * row-major.  The contract is the package's own NumPy functions (coco.py: polygon_mask, rle_mask, masks_numpy), byte for byte.  It
+ * restates annToMask of pycocotools' C part (rleFrPoly + rleMerge + rleDecode) from its published source; that library is no dependency,
+ * and the restatement has NOT been compared with it.
+ *   Polygon part (flat x0, y0, x1, y1, ... of k vertices) -> mask.  C `double` and C `int` arithmetic, every operation rounded on its
+ *   own, (int) truncating toward zero:
+ *     1. X[j] = (int)(5 * x[j] + .5), Y[j] alike; closed: X[k] = X[0], Y[k] = Y[0].
+ *     2. Every edge j -> j + 1 is traced into a dense point list.  dx = |xe - xs|, dy = |ys - ye|, flip = (dx >= dy && xs > xe) ||
+ *        (dx < dy && ys > ye); with flip the end points are swapped.  dx >= dy: s = (double)(ye - ys) / dx, and for d = 0 .. dx,
+ *        t = flip ? dx - d : d, the point (u, v) = (t + xs, (int)(ys + s * t + .5)).  Else s = (double)(xe - xs) / dy, and for d = 0 .. dy,
+ *        t = flip ? dy - d : d, the point ((int)(xs + s * t + .5), t + ys).  The lists of all edges concatenate in order.  A zero-length
+ *        edge gives its vertex once (0 / 0 is not evaluated).
+ *     3. Every consecutive pair p - 1, p of the list with u[p] != u[p-1] gives a candidate: m = u[p] < u[p-1] ? u[p] : u[p] - 1,
+ *        xd = (m + .5) / 5 - .5, kept when xd is an integer with 0 <= xd <= w - 1; yd = (min(v[p], v[p-1]) + .5) / 5 - .5 clamped to
+ *        [0, h], then ceil.  The crossing point is (xd, yd).
+ *     4. Pixel (x, y) is 1 iff the number of crossing points of column x with yd <= y is odd (points with yd == h close a run at the
+ *        column's end; the count of a column is even).
+ *   Run-length part: counts of runs of 0 and 1 in turn, starting with 0, over the column-major index x * h + y.
+ *   An annotation's mask is the union of its parts.  Per image, in part order and with `all` as it was before the annotation:
+ *   class 2 (crowd): miss |= mask & ~all;  class 1 (too few key points / too small): miss |= mask;  class 0: nothing;  then all |= mask.
+ * images: per image its size and its range of `parts`; the parts of one annotation (same `ann`) are consecutive and share `cls`; a part's
+ * (off, len) index `xy` (kind 0: len doubles) or `counts` (kind 1: len counts).  All tables are host memory, read before the call returns;
+ * they travel in ONE staging copy (at most PMX_MASKS_TABLE_BYTES).  mask_miss / mask_all: the masks end to end in image order (h * w bytes
+ * each); either may be NULL; host memory (one synchronisation behind the copies), or device memory on the context's device
+ * (out_on_device != 0: asynchronous on the context's stream, nothing synchronises).  Works on a context of any architecture and needs no
+ * weights; maps, records, samples and retained state stay untouched.
+ * Errors, before anything is enqueued (the context stays usable): PMX_ERR_INVALID for a null table, n_images <= 0, both outputs NULL, a
+ * side < 1 or > 16384, a part range outside the table, an unknown kind or class, annotation indices that go back or one annotation with
+ * two classes, an (off, len) outside its array, a polygon of fewer than 6 numbers or an odd count, a coordinate that is not finite or
+ * outside +-65536, counts that do not sum to h * w; PMX_ERR_CAPACITY for tables above the budget. */
+#define PMX_MASKS_TABLE_BYTES ((size_t)64 << 20)
+typedef struct pmx_mask_image { int32_t h, w, part0, n_parts; } pmx_mask_image;
+typedef struct pmx_mask_part { int32_t kind /* 0 polygon, 1 run-length */, ann, cls /* 0 keep, 1 miss, 2 crowd */, off, len, reserved; } pmx_mask_part;
+int pmx_coco_masks(pmx_ctx* ctx, const pmx_mask_image* images, int n_images, const pmx_mask_part* parts, int n_parts, const double* xy,
+                   size_t n_xy, const uint32_t* counts, size_t n_counts, uint8_t* mask_miss, uint8_t* mask_all, int out_on_device);
+/* the columns one block of pmx_coco_masks owns for an image of height h (1 .. 16384, else 0): a launch-geometry fact for tests */
+int pmx_coco_masks_strip(int h);
+
 /* results.  pmx_results_layout synchronises, grows the capacities and re-runs the post-process if an image overflowed them,
  * and returns the layout of the (now final) records; pmx_get_results does the same and copies `batch` records to `out`
  * (out_bytes >= batch * bytes_per_record, else PMX_ERR_CAPACITY). */
