@@ -136,12 +136,12 @@ static int prof_begin(pmx_ctx* c, const std::string& name0, double flops, double
         c->prof_index[name] = idx;
     } else idx = it->second;
     ProfPending p; p.entry = idx;
-    for (hipEvent_t* e : {&p.e0, &p.e1}) {
-        if (!c->ev_pool.empty()) { *e = c->ev_pool.back(); c->ev_pool.pop_back(); }
-        else PMX_HIP(hipEventCreate(e));
+    for (Event* e : {&p.e0, &p.e1}) {
+        if (!c->ev_pool.empty()) { *e = std::move(c->ev_pool.back()); c->ev_pool.pop_back(); }
+        else if (int rc = e->create(hipEventDefault)) return rc;
     }
     if (record) PMX_HIP(hipEventRecord(p.e0, c->stream));
-    c->pending.push_back(p);
+    c->pending.push_back(std::move(p));
     c->prof_open = (int)c->pending.size() - 1;
     return PMX_OK;
 }
@@ -165,8 +165,8 @@ static int prof_collect(pmx_ctx* c)
         PMX_HIP(hipEventElapsedTime(&ms, p.e0, p.e1));
         c->prof[p.entry].total_ms += ms;
         c->prof[p.entry].launches += 1;
-        c->ev_pool.push_back(p.e0);
-        c->ev_pool.push_back(p.e1);
+        c->ev_pool.push_back(std::move(p.e0));
+        c->ev_pool.push_back(std::move(p.e1));
     }
     c->pending.clear();
     return PMX_OK;
@@ -197,12 +197,12 @@ static int pp_alloc(PPBuffers& p, DevBuf<char>& store, size_t B)
         part(p.sub_work, p.cap_sub > PMX_LDS_SUBSETS ? (size_t)p.cap_sub * 20 : 0), part(p.subsets, (size_t)p.cap_sub * 20),
         part(p.status, 1), part(p.results, p.rec_bytes)};
     size_t total = 0;
-    for (const Part& s : parts) total += (s.bytes + 255) / 256 * 256;
+    for (const Part& s : parts) total += pmx_align_up(s.bytes, 256);
     if (int rc = store.alloc(total)) return rc;
     size_t off = 0;
     for (const Part& s : parts) {
         *s.q = s.bytes ? store + off : nullptr;
-        off += (s.bytes + 255) / 256 * 256;
+        off += pmx_align_up(s.bytes, 256);
     }
     return PMX_OK;
 }
@@ -253,10 +253,9 @@ extern "C" int pmx_create_net(pmx_ctx** out, const char* arch, int device, int m
     // any failure below frees what was created so far (the caller only ever sees a complete context or NULL)
     auto build = [&]() -> int {
         int rc;
-        PMX_HIP(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
+        if ((rc = c->own_stream.create(hipStreamNonBlocking))) return rc;
         c->stream = c->own_stream;
-        PMX_HIP(hipEventCreate(&c->t0));
-        PMX_HIP(hipEventCreate(&c->t1));
+        if ((rc = c->t0.create(hipEventDefault)) || (rc = c->t1.create(hipEventDefault))) return rc;
         if ((rc = c->in16.alloc(B * HW * PMX_IN_C))) return rc;
         if ((rc = c->act0.alloc(B * HW * 64))) return rc;      // conv1_1 out is the largest activation
         if ((rc = c->act1.alloc(B * HW * 16))) return rc;      // (H/2)(W/2) x 64 = (H/4)(W/4) x 256
@@ -297,22 +296,8 @@ extern "C" void pmx_destroy(pmx_ctx* c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    // streams and events by hand; every buffer is a DevBuf member and goes with the context (after the synchronisation above)
-    for (int i = 1; i < PMX_PR_LANES; ++i) if (c->pr_lane[i].stream) (void)hipStreamDestroy(c->pr_lane[i].stream);
-    for (int i = 0; i < PMX_PR_LANES; ++i) if (c->pr_lane[i].done) (void)hipEventDestroy(c->pr_lane[i].done);
-    if (c->pr_src_ready) (void)hipEventDestroy(c->pr_src_ready);
-    if (c->pr_fin) (void)hipEventDestroy(c->pr_fin);
-    if (c->bx_copied) (void)hipEventDestroy(c->bx_copied);
-    if (c->sp_copied) (void)hipEventDestroy(c->sp_copied);
-    if (c->rd_copied) (void)hipEventDestroy(c->rd_copied);
-    if (c->mk_copied) (void)hipEventDestroy(c->mk_copied);
-    if (c->tr.seg_copied) (void)hipEventDestroy(c->tr.seg_copied);
-    for (auto& p : c->pending) { (void)hipEventDestroy(p.e0); (void)hipEventDestroy(p.e1); }
-    for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->snap_ev) if (e) (void)hipEventDestroy(e);
-    if (c->t0) (void)hipEventDestroy(c->t0);
-    if (c->t1) (void)hipEventDestroy(c->t1);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
+    // every buffer, event and stream of the context is a DevBuf, Event, Stream or Staging member and goes with it; the device is idle
+    // after the synchronisation above, so the order in which the members go does not matter
     delete c;
 }
 
@@ -550,8 +535,8 @@ static int launch_wino_run(pmx_ctx* c, const ConvArgs& a0, int ks, int groups, i
         rc = conv_wino_run_launch(a, ks, groups, c->stream);
         conv_set_launch_events(nullptr, nullptr);
         if (rc) {       // nothing was dispatched, so nothing will ever stamp the pair: take it back (prof_collect would fail on it for good)
-            c->ev_pool.push_back(c->pending.back().e0);
-            c->ev_pool.push_back(c->pending.back().e1);
+            c->ev_pool.push_back(std::move(c->pending.back().e0));
+            c->ev_pool.push_back(std::move(c->pending.back().e1));
             c->pending.pop_back();
         }
     } else {
@@ -1540,7 +1525,7 @@ extern "C" int pmx_results_snapshot(pmx_ctx* c, int slot, void* dst_device, size
     PMX_DEV(c);
     const size_t need = c->pp.rec_bytes * (size_t)c->pp_B;
     PMX_CHECK(dst_bytes >= need, PMX_ERR_CAPACITY, "pmx_results_snapshot: %zu bytes for %d records of %zu bytes", dst_bytes, c->pp_B, c->pp.rec_bytes);
-    if (!c->snap_ev[slot]) PMX_HIP(hipEventCreateWithFlags(&c->snap_ev[slot], hipEventDisableTiming));
+    if (int rc = c->snap_ev[slot].create(hipEventDisableTiming)) return rc;
     if (!c->snap_status[slot])
         if (int rc = c->snap_status[slot].alloc(c->max_batch)) return rc;
     PMX_HIP(hipMemcpyAsync(dst_device, c->pp.results, need, hipMemcpyDeviceToDevice, c->stream));
@@ -1783,22 +1768,15 @@ extern "C" int pmx_conv2d(pmx_ctx* c, const float* x, const float* w, const floa
     if ((rc = plan_conv(c, p, nullptr, &L, nullptr, d_xn, nullptr, L.cin_pad, d_yn, nullptr, cout, B, H, W, relu, pool, -1))) return rc;
     rc = launch_plan(c, p);
     if (!rc && iters > 0) {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        auto timed = [&]() -> int {
-            PMX_HIP(hipEventCreate(&e0)); PMX_HIP(hipEventCreate(&e1));
-            PMX_HIP(hipEventRecord(e0, c->stream));
-            int r = PMX_OK;
-            for (int i = 0; i < iters && !r; ++i) r = launch_plan(c, p);
-            PMX_HIP(hipEventRecord(e1, c->stream));
-            PMX_HIP(hipEventSynchronize(e1));
-            float ms = 0.f;
-            PMX_HIP(hipEventElapsedTime(&ms, e0, e1));
-            if (avg_ms) *avg_ms = ms / iters;
-            return r;
-        };
-        rc = timed();
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
+        Event e0, e1;
+        if ((rc = e0.create(hipEventDefault)) || (rc = e1.create(hipEventDefault))) return rc;
+        PMX_HIP(hipEventRecord(e0, c->stream));
+        for (int i = 0; i < iters && !rc; ++i) rc = launch_plan(c, p);
+        PMX_HIP(hipEventRecord(e1, c->stream));
+        PMX_HIP(hipEventSynchronize(e1));
+        float ms = 0.f;
+        PMX_HIP(hipEventElapsedTime(&ms, e0, e1));
+        if (avg_ms) *avg_ms = ms / iters;
     }
     return rc ? rc : test_fetch(c, "pmx_conv2d", d_yn, d_y, y, B, cout, Ho, Wo, cout, 0);
 }
@@ -1910,7 +1888,7 @@ extern "C" int pmx_conv2d_backward(pmx_ctx* c, const float* x, const float* w, c
     auto weight_grad = [&]() -> int {
         return dw ? conv_wgrad_launch(d_g, cg, d_x32, cx, d_ws, d_dw, B, H, W, cout, cg, cin, cx, ks, strips, rows, nullptr, c->stream) : PMX_OK;
     };
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    Event e0, e1;
     auto timed = [&](const std::function<int()>& part, double* ms_out) -> int {
         PMX_HIP(hipEventRecord(e0, c->stream));
         int r = PMX_OK;
@@ -1926,7 +1904,7 @@ extern "C" int pmx_conv2d_backward(pmx_ctx* c, const float* x, const float* w, c
         int r;
         if ((r = mask_db()) || (r = data_grad()) || (r = weight_grad())) return r;
         if (iters > 0) {
-            PMX_HIP(hipEventCreate(&e0)); PMX_HIP(hipEventCreate(&e1));
+            if ((r = e0.create(hipEventDefault)) || (r = e1.create(hipEventDefault))) return r;
             if (dx && (r = timed(data_grad, avg_ms3 ? avg_ms3 + 0 : nullptr))) return r;
             if (dw && (r = timed(weight_grad, avg_ms3 ? avg_ms3 + 1 : nullptr))) return r;
             if (need_g && (r = timed(mask_db, avg_ms3 ? avg_ms3 + 2 : nullptr))) return r;
@@ -1944,8 +1922,6 @@ extern "C" int pmx_conv2d_backward(pmx_ctx* c, const float* x, const float* w, c
         return PMX_OK;
     };
     rc = run();
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
     if (rc) (void)hipStreamSynchronize(c->stream);        // nothing in flight may outlive the buffers
     return rc;
 }

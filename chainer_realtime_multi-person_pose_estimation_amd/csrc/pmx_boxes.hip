@@ -187,7 +187,7 @@ struct Stage {
         if (bytes) memcpy(h.data() + off, p, bytes);
         return off;
     }
-    size_t reserve(size_t bytes) { const size_t off = (h.size() + 15) / 16 * 16; h.resize(off + bytes); return off; }
+    size_t reserve(size_t bytes) { const size_t off = pmx_align_up(h.size(), 16); h.resize(off + bytes); return off; }
 };
 
 // one H2D copy of the staging; the device copy is valid for the kernels enqueued after it on the context's stream.  The table sets of
@@ -196,12 +196,10 @@ int stage_upload(pmx_ctx* c, Stage& st, KpStage* ks = nullptr)
 {
     const size_t bytes = st.h.size();
     if (!bytes) return PMX_OK;
-    if (c->bx_pending) { PMX_HIP(hipEventSynchronize(c->bx_copied)); c->bx_pending = false; }     // the pinned buffer is free again
-    int rc;
-    if (bytes > c->bx_host.capacity() && (rc = c->bx_host.alloc(bytes))) return rc;
-    if ((rc = c->bx_dev.ensure(bytes, c->stream))) return rc;      // (queued work may still read the old buffer)
+    char *pinned, *dev;
+    if (int rc = c->bx.begin(bytes, c->stream, &pinned, &dev)) return rc;
     if (ks) {
-        char *host = st.h.data(), *dev = c->bx_dev.get();
+        char* host = st.h.data();
         PPTables taps{};
         pmx_pp_gauss(c, host + ks->taps_off, dev + ks->taps_off, taps);
         for (size_t k = 0; k < ks->crops.size(); ++k) {
@@ -211,12 +209,8 @@ int stage_upload(pmx_ctx* c, Stage& st, KpStage* ks = nullptr)
         }
         memcpy(host + ks->crops_off, ks->crops.data(), ks->crops.size() * sizeof(KpCrop));
     }
-    if (!c->bx_copied) PMX_HIP(hipEventCreateWithFlags(&c->bx_copied, hipEventDisableTiming));
-    memcpy(c->bx_host, st.h.data(), bytes);
-    PMX_HIP(hipMemcpyAsync(c->bx_dev, c->bx_host, bytes, hipMemcpyHostToDevice, c->stream));
-    PMX_HIP(hipEventRecord(c->bx_copied, c->stream));
-    c->bx_pending = true;
-    return PMX_OK;
+    memcpy(pinned, st.h.data(), bytes);
+    return c->bx.commit(bytes, c->stream);
 }
 
 // rows of 6 ints (left, top, right, bottom, flip, image): the one box layout of this file; the image index is checked by check_box_images
@@ -314,7 +308,7 @@ int kp_enqueue_chunk(pmx_ctx* c, const KpStage& ks, const int* hwf, int k0, int 
         const int t0 = ks.crop_tile0[k0], t1 = ks.crop_tile0[k0 + B];
         if ((rc = pmx_prof_begin(c, "kp_boxes|kp_tiles_kernel", (double)m.sbh * 4 * B))) return rc;
         hipLaunchKernelGGL(kp_tiles_kernel<10>, dim3(t1 - t0, n_ch), dim3(256), 0, c->stream, m,
-                           reinterpret_cast<const KpCrop*>(c->bx_dev + ks.crops_off), reinterpret_cast<const int2*>(c->bx_dev + ks.tiles_off),
+                           reinterpret_cast<const KpCrop*>(c->bx.dev + ks.crops_off), reinterpret_cast<const int2*>(c->bx.dev + ks.tiles_off),
                            t0, k0, n_ch, reinterpret_cast<ArgMax*>(c->bx_rec.get()));
         PMX_HIP(hipGetLastError());
         return pmx_prof_end(c);
@@ -354,7 +348,7 @@ int kp_finish(pmx_ctx* c, const KpStage& ks, int n, double thresh, double* out)
     if (kp_fast(c)) {
         if ((rc = pmx_prof_begin(c, "kp_boxes|kp_merge_kernel", (double)ks.n_tiles * n_ch * sizeof(ArgMax)))) return rc;
         hipLaunchKernelGGL(kp_merge_kernel, dim3(n_ch, n), dim3(256), 0, c->stream, reinterpret_cast<const ArgMax*>(c->bx_rec.get()),
-                           reinterpret_cast<const KpCrop*>(c->bx_dev + ks.crops_off), reinterpret_cast<const int*>(c->bx_dev + ks.ends_off),
+                           reinterpret_cast<const KpCrop*>(c->bx.dev + ks.crops_off), reinterpret_cast<const int*>(c->bx.dev + ks.ends_off),
                            n_ch, thresh, c->d_kp.get());
         PMX_HIP(hipGetLastError());
         if ((rc = pmx_prof_end(c))) return rc;
@@ -380,7 +374,7 @@ int stage_images(pmx_ctx* c, Stage& st, const pmx_box_image* images, int n_image
             if (used[k]) {
                 const size_t bytes = (size_t)images[k].h * images[k].w * 3;
                 copies->push_back(ImageCopy{total, images[k].bgr, bytes});
-                total += (bytes + 255) / 256 * 256;
+                total += pmx_align_up(bytes, 256);
             }
     int rc;
     if (total && (rc = c->u8_src.ensure(total, c->stream))) return rc;
@@ -408,8 +402,8 @@ int forward_chunk(pmx_ctx* c, size_t imgs_off, size_t desc_off, size_t tab_off, 
     const long long npix = (long long)B * dh * dw;
     if ((rc = pmx_prof_begin(c, "resize_boxes|box_gather_resize_u8_images_kernel", (double)npix * 3 * 2))) return rc;
     hipLaunchKernelGGL(box_gather_resize_u8_images_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, c->stream,
-                       reinterpret_cast<const BoxImg*>(c->bx_dev + imgs_off), reinterpret_cast<const BoxDesc*>(c->bx_dev + desc_off) + k0,
-                       reinterpret_cast<const int*>(c->bx_dev + tab_off) + (size_t)k0 * 4 * (dw + dh), B, dh, dw, c->u8_tmp.get());
+                       reinterpret_cast<const BoxImg*>(c->bx.dev + imgs_off), reinterpret_cast<const BoxDesc*>(c->bx.dev + desc_off) + k0,
+                       reinterpret_cast<const int*>(c->bx.dev + tab_off) + (size_t)k0 * 4 * (dw + dh), B, dh, dw, c->u8_tmp.get());
     PMX_HIP(hipGetLastError());
     if ((rc = pmx_prof_end(c))) return rc;
     return pmx_forward_u8(c, c->u8_tmp, B, dh, dw, 1);

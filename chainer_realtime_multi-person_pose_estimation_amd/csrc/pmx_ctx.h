@@ -56,6 +56,71 @@ struct DevBuf {
 };
 template <typename T> using HostBuf = DevBuf<T, true>;
 
+static inline size_t pmx_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// The one owner of a HIP event.  Empty until create(), which keeps the site's flags (0 = timing enabled); destroyed with its owner.
+// Move-only -- a move hands the handle over and calls nothing in HIP; converts to hipEvent_t.
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }
+    Event& operator=(Event&& o) noexcept { std::swap(e, o.e); return *this; }
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    operator hipEvent_t() const { return e; }
+    int create(unsigned flags)      // no-op when it holds one
+    {
+        if (!e) PMX_HIP(hipEventCreateWithFlags(&e, flags));
+        return PMX_OK;
+    }
+};
+
+// The one owner of a HIP stream the context created itself (own_stream, lanes 1 .. 3); a caller's stream stays a plain hipStream_t.
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream&) = delete;
+    Stream& operator=(const Stream&) = delete;
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+    int create(unsigned flags, int priority = 0)      // no-op when it holds one
+    {
+        if (!s) PMX_HIP(hipStreamCreateWithPriority(&s, flags, priority));
+        return PMX_OK;
+    }
+};
+
+// The per-call staging block of a feature: tables built on the host in pinned memory and copied to the device in ONE piece.  The order
+// of the steps is the protocol -- the pinned half is not rewritten before the previous copy has read it (`copied`), the device half is
+// not reallocated under queued launches (DevBuf::ensure) -- and lives here only.
+struct Staging {
+    HostBuf<char> host;
+    DevBuf<char> dev;
+    Event copied;                   // the last copy has left the pinned half
+    bool pending = false;           // ... and nobody has waited for it yet
+    // both halves at `bytes` at least (grown to exactly that), the pinned one free to be written; the device address is final, so the
+    // caller may write it into its tables.  Nothing is pending after a failure.
+    int begin(size_t bytes, hipStream_t stream, char** h, char** d)
+    {
+        if (pending) { pending = false; PMX_HIP(hipEventSynchronize(copied)); }
+        int rc;
+        if (bytes > host.capacity() && (rc = host.alloc(bytes))) return rc;
+        if ((rc = dev.ensure(bytes, stream)) || (rc = copied.create(hipEventDisableTiming))) return rc;
+        *h = host; *d = dev;
+        return PMX_OK;
+    }
+    // the first `bytes` bytes -> device, valid for what `stream` runs next
+    int commit(size_t bytes, hipStream_t stream)
+    {
+        PMX_HIP(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, stream));
+        PMX_HIP(hipEventRecord(copied, stream));
+        pending = true;
+        return PMX_OK;
+    }
+    void reset() { host.reset(); dev.reset(); pending = false; }
+};
+
 struct LayerDesc { std::string name; int cin, cout, ks; };
 
 enum NetKind { NET_POSE = 0, NET_FACE = 1, NET_HAND = 2 };     // params['archs'] (entity.py:50-54)
@@ -84,7 +149,7 @@ struct ProfEntry {
     double issued = 0;             // per launch: FLOP the kernel issues to the matrix cores for real outputs (Winograd forms: 16/36, 100/196 of
                                    // the algorithmic figure; direct kernels: all of it; tile padding is not counted)
 };
-struct ProfPending { int entry; hipEvent_t e0, e1; };
+struct ProfPending { int entry; Event e0, e1; };
 
 // detect_precise runs its inference scales CONCURRENTLY: one image at 0.5x / 1x / 1.5x is 12 ... 108 one-per-CU blocks per layer for 256
 // CUs, so the four forward passes go to four streams ("lanes"), each with its own working set; a lane's fields are swapped into the
@@ -95,8 +160,8 @@ struct ProfPending { int entry; hipEvent_t e0, e1; };
 constexpr int PMX_PR_LANES = 4;
 constexpr int PMX_SK_ZERO_BIAS = 1024;      // floats of the shared zero-bias vector of the split-K / unit-mode launches
 struct PrLane {
-    hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr;
+    Stream stream;                           // lanes 1 .. 3 (lane 0 runs on the context's stream)
+    Event done;
     DevBuf<float> in16, act0, act1, cat, brA, brB, brT;
     DevBuf<uint8_t> u8_tmp;
     size_t cap_px = 0;                       // n * padded_h * padded_w the activation buffers hold
@@ -171,8 +236,7 @@ extern const TrunkDesc pmx_trunk_desc[PMX_TRUNK_LAYERS];
 // Training steps (pmx_train.hip; include/pose_mi355x.h: pmx_train_*).  Three stores with the layout of BwState::grad -- per head layer, in
 // mode 2 per trunk layer as well, w | b at grad_off[layer], padded to a multiple of 64 floats: the master weights (OIHW, reference input
 // order), Adam's first and second moments.  Per layer of c->table: its step count and gradient scale (trunk layers: used in mode 2).
-// seg_host / seg_dev: the tables of one step -- the Adam segments, then the packers' jobs (pmx_train.hip: jobs_at) -- one copy from pinned
-// memory (`seg_copied` marks when the host side may be rewritten).
+// seg: the tables of one step -- the Adam segments, then the packers' jobs (pmx_train.hip: jobs_at).
 struct AdamSeg { unsigned long long off; unsigned n, blk0; float scale, alpha_t; };      // blk0: first block of the segment in the launch
 struct TrainState {
     int on = 0;
@@ -180,9 +244,7 @@ struct TrainState {
     std::vector<int> t;
     std::vector<float> scale;
     double alpha = 1e-4, beta1 = 0.9, beta2 = 0.999, eps = 1e-8;
-    HostBuf<char> seg_host;
-    DevBuf<char> seg_dev;
-    hipEvent_t seg_copied = nullptr; bool seg_pending = false;
+    Staging seg;
 };
 
 // ------------------------------------------------------------------------------------------- context
@@ -219,7 +281,7 @@ struct pmx_ctx {
     const uint8_t* pr_src = nullptr;                     // host images of the current begin / finish sequence already in u8_src
     PrLane pr_lane[PMX_PR_LANES];                        // lanes 1 .. : own buffers; lane 0 = the context's own stream and buffers
     std::vector<DevBuf<float>> pr_part;                  // per scale: [n][57][orig_h][orig_w] (PAF planes, then heat planes of every image)
-    hipEvent_t pr_src_ready = nullptr, pr_fin = nullptr; // originals uploaded / parts consumed by the last finish
+    Event pr_src_ready, pr_fin;                          // originals uploaded / parts consumed by the last finish
     int opt_precise_lanes = PMX_PR_LANES;                // 1: every scale on the context's own stream (A/B, tests)
     int opt_precise_plain = -1;                          // detect_precise's forwards on the plain Winograd kernels: -1 = when all four lanes are in use, 0 never, 1 always
     int opt_precise_lane_priority = 1;                   // lane streams with priorities (largest scale first); read when a lane's stream is created
@@ -227,7 +289,8 @@ struct pmx_ctx {
     int pr_tabs_trims = 0;                               // how often that happened (diagnostics: option query "precise_table_trims")
     DevBuf<double> d_kp;             // key-point records of pmx_keypoints
     int device = 0;
-    hipStream_t stream = nullptr, own_stream = nullptr;
+    hipStream_t stream = nullptr;    // what everything is enqueued on: own_stream or the caller's (pmx_set_stream), never destroyed here
+    Stream own_stream;
     int max_batch = 0, max_h = 0, max_w = 0;
     std::vector<LayerDesc> table;
     std::map<std::string, int> index;
@@ -255,7 +318,7 @@ struct pmx_ctx {
     DevBuf<double> d_scale;
     HostBuf<unsigned char> h_results;           // pinned staging for pmx_get_results (pageable D2H is slow and jittery)
     // pmx_results_snapshot / pmx_snapshot_wait: PMX_SNAPSHOT_SLOTS slots (event, pinned status words, layout at snapshot time)
-    hipEvent_t snap_ev[PMX_SNAPSHOT_SLOTS] = {};
+    Event snap_ev[PMX_SNAPSHOT_SLOTS];
     HostBuf<int> snap_status[PMX_SNAPSHOT_SLOTS];
     int snap_B[PMX_SNAPSHOT_SLOTS] = {}, snap_cap_ppl[PMX_SNAPSHOT_SLOTS] = {};
     size_t snap_rec[PMX_SNAPSHOT_SLOTS] = {};
@@ -301,18 +364,17 @@ struct pmx_ctx {
     // split-K scratch: partial-sum slabs of the current launch + a zero bias vector for the slice blocks
     DevBuf<float> sk_scratch, sk_zero_bias;
     // timing / profiling
-    hipEvent_t t0 = nullptr, t1 = nullptr;
+    Event t0, t1;
     int prof_on = 0;                 // 0 off | 1 every launch | 2 only the 7x7 convolutions (the dominant kernel: fewest events in a timed region)
     std::vector<ProfEntry> prof;
     std::map<std::string, int> prof_index;
     std::vector<ProfPending> pending;
-    std::vector<hipEvent_t> ev_pool;   // recycled events (creating two per launch inside the timed region costs ~0.5 %)
+    std::vector<Event> ev_pool;        // recycled events (creating two per launch inside the timed region costs ~0.5 %)
     int prof_open = -1;
-    // pmx_boxes.hip (key points for many boxes of one image): the per-call staging (resize tables, crop / tile tables, up-sampling grids) goes
-    // over in ONE copy from pinned memory; `bx_copied` marks when the host side may be rewritten.  Per-tile arg-max records of the key points.
-    HostBuf<char> bx_host;
-    hipEvent_t bx_copied = nullptr; bool bx_pending = false;
-    DevBuf<char> bx_dev, bx_rec;
+    // pmx_boxes.hip (key points for many boxes of one image).  bx: [resize tables | crop / tile tables | up-sampling grids]; bx_rec: the
+    // per-tile arg-max records of the key points.
+    Staging bx;
+    DevBuf<char> bx_rec;
     // pmx_loss.hip (validation loss).  Targets at h/8 x w/8, [image][map pixel][38 PAF | 19 heat] (the cat slices' order), the resized ignore
     // mask [image][map pixel]; the poses they came from (device: label kernel; host: pmx_get_labels); the corner-aligned grid of (h, w) ->
     // (h/8, w/8); per (stage slot, block, branch) partial sums and the 2 x PMX_LOSS_SLOTS means.  Slot PMX_LOSS_SLOTS - 1 = pmx_loss_current_maps.
@@ -337,28 +399,20 @@ struct pmx_ctx {
     // pmx_conv2d_backward: test-only, S0 of the weight-gradient strips (0: automatic); include/pose_mi355x.h
     int opt_wgrad_strips = 0;
     int opt_trunk_keep_g = 0;        // read by pmx_backward_enable(2): keep the masked gradient of every trunk layer for pmx_get_retained (tests)
-    // pmx_samples.hip (sample preparation).  sp_host / sp_dev: the per-call block [descriptors | resize tables | host sources], ONE copy from
-    // pinned memory (`sp_copied` marks when the host side may be rewritten); sp_a: the resized intermediates of the training samples; sp_out:
-    // max_batch x insize x insize x 3 prepared images; sp_mask_raw / sp_mask_tmp / sp_mask: the mask before, between and after the two
-    // dilation passes; sp_const: the weight and division tables of the contract (uploaded once).
-    HostBuf<char> sp_host;
-    hipEvent_t sp_copied = nullptr; bool sp_pending = false;
-    DevBuf<char> sp_dev, sp_const;
+    // pmx_samples.hip (sample preparation).  sp: [descriptors | resize tables | host sources]; sp_a: the resized intermediates of the
+    // training samples; sp_out: max_batch x insize x insize x 3 prepared images; sp_mask_raw / sp_mask_tmp / sp_mask: the mask before, between
+    // and after the two dilation passes; sp_const: the weight and division tables of the contract (uploaded once).
+    Staging sp;
+    DevBuf<char> sp_const;
     DevBuf<uint8_t> sp_a, sp_out, sp_mask_raw, sp_mask_tmp, sp_mask;
     int sp_n = 0, sp_insize = 0;                          // the prepared samples (0: none)
-    // pmx_render.hip (result images).  rd_host / rd_dev: the per-call block [image table | primitives], ONE copy from pinned memory
-    // (`rd_copied` marks when the host side may be rewritten); rd_img: the host images of the call; rd_out: the canvases end to end when
-    // the caller's output is host memory.  All grow on demand (original images are larger than the network input).
-    HostBuf<char> rd_host;
-    hipEvent_t rd_copied = nullptr; bool rd_pending = false;
-    DevBuf<char> rd_dev;
+    // pmx_render.hip (result images).  rd: [image table | primitives]; rd_img: the host images of the call; rd_out: the canvases end to
+    // end when the caller's output is host memory.  All grow on demand (original images are larger than the network input).
+    Staging rd;
     DevBuf<uint8_t> rd_img, rd_out;
-    // pmx_masks.hip (ignore masks).  mk_host / mk_dev: the per-call block [image table | parts | vertices | running sums], ONE copy from
-    // pinned memory (`mk_copied` marks when the host side may be rewritten); mk_out: the masks end to end when the caller's output is host
-    // memory.  All grow on demand.
-    HostBuf<char> mk_host;
-    hipEvent_t mk_copied = nullptr; bool mk_pending = false;
-    DevBuf<char> mk_dev;
+    // pmx_masks.hip (ignore masks).  mk: [image table | parts | vertices | running sums]; mk_out: the masks end to end when the caller's
+    // output is host memory.  All grow on demand.
+    Staging mk;
     DevBuf<uint8_t> mk_out;
     BwState bw;                                          // pmx_backward.hip
     TrainState tr;                                        // pmx_train.hip

@@ -187,8 +187,6 @@ __global__ __launch_bounds__(MK_THREADS) void masks_kernel(const MaskImg* __rest
     }
 }
 
-size_t align64(size_t v) { return (v + 63) & ~(size_t)63; }
-
 // everything pmx_coco_masks refuses, before anything is enqueued
 int check_masks(const pmx_mask_image* images, int n_images, const pmx_mask_part* parts, int n_parts, const double* xy, size_t n_xy,
                 const uint32_t* counts, size_t n_counts, const void* mask_miss, const void* mask_all)
@@ -250,10 +248,10 @@ extern "C" int pmx_coco_masks(pmx_ctx* c, const pmx_mask_image* images, int n_im
     if ((rc = check_masks(images, n_images, parts, n_parts, xy, n_xy, counts, n_counts, mask_miss, mask_all))) return rc;
 
     // the layout of the ONE staging block [image table | parts | vertices | running sums of the counts]
-    const size_t img_off = 0, part_off = align64((size_t)n_images * sizeof(MaskImg));
-    const size_t xy_off = align64(part_off + (size_t)n_parts * sizeof(pmx_mask_part));
-    const size_t cum_off = align64(xy_off + n_xy * sizeof(double));
-    const size_t bytes = align64(cum_off + n_counts * sizeof(uint32_t));
+    const size_t img_off = 0, part_off = pmx_align_up((size_t)n_images * sizeof(MaskImg), 64);
+    const size_t xy_off = pmx_align_up(part_off + (size_t)n_parts * sizeof(pmx_mask_part), 64);
+    const size_t cum_off = pmx_align_up(xy_off + n_xy * sizeof(double), 64);
+    const size_t bytes = pmx_align_up(cum_off + n_counts * sizeof(uint32_t), 64);
     PMX_CHECK(bytes <= PMX_MASKS_TABLE_BYTES, PMX_ERR_CAPACITY, "coco_masks: %zu bytes of tables exceed the budget of %zu", bytes, (size_t)PMX_MASKS_TABLE_BYTES);
     long long blocks = 0;
     size_t out_total = 0;
@@ -274,11 +272,8 @@ extern "C" int pmx_coco_masks(pmx_ctx* c, const pmx_mask_image* images, int n_im
     uint8_t* d_miss = to_host ? (mask_miss ? c->mk_out.get() : nullptr) : mask_miss;
     uint8_t* d_all = to_host ? (mask_all ? c->mk_out + (mask_miss ? out_total : 0) : nullptr) : mask_all;
 
-    if (c->mk_pending) { PMX_HIP(hipEventSynchronize(c->mk_copied)); c->mk_pending = false; }      // the pinned block is free again
-    if (bytes > c->mk_host.capacity() && (rc = c->mk_host.alloc(bytes))) return rc;
-    if ((rc = c->mk_dev.ensure(bytes, c->stream))) return rc;
-    if (!c->mk_copied) PMX_HIP(hipEventCreateWithFlags(&c->mk_copied, hipEventDisableTiming));
-    char* host = c->mk_host;
+    char *host, *dev;
+    if ((rc = c->mk.begin(bytes, c->stream, &host, &dev))) return rc;
     memcpy(host + img_off, tab.data(), tab.size() * sizeof(MaskImg));
     if (n_parts) memcpy(host + part_off, parts, (size_t)n_parts * sizeof(pmx_mask_part));
     if (n_xy) memcpy(host + xy_off, xy, n_xy * sizeof(double));
@@ -292,14 +287,12 @@ extern "C" int pmx_coco_masks(pmx_ctx* c, const pmx_mask_image* images, int n_im
             uint32_t sum = 0;
             for (int i = 0; i < pt.len; ++i) { sum += counts[pt.off + i]; cum[pt.off + i] = sum; }
         }
-    PMX_HIP(hipMemcpyAsync(c->mk_dev, c->mk_host, bytes, hipMemcpyHostToDevice, c->stream));
-    PMX_HIP(hipEventRecord(c->mk_copied, c->stream));
-    c->mk_pending = true;
+    if ((rc = c->mk.commit(bytes, c->stream))) return rc;
 
     if ((rc = pmx_prof_begin(c, "coco_masks|masks_kernel", (double)out_total * n_out))) return rc;
     hipLaunchKernelGGL(masks_kernel, dim3((unsigned)blocks), dim3(MK_THREADS), (size_t)lds_words * sizeof(uint32_t), c->stream,
-                       reinterpret_cast<const MaskImg*>(c->mk_dev + img_off), n_images, reinterpret_cast<const pmx_mask_part*>(c->mk_dev + part_off),
-                       reinterpret_cast<const double*>(c->mk_dev + xy_off), reinterpret_cast<const uint32_t*>(c->mk_dev + cum_off), d_miss, d_all);
+                       reinterpret_cast<const MaskImg*>(dev + img_off), n_images, reinterpret_cast<const pmx_mask_part*>(dev + part_off),
+                       reinterpret_cast<const double*>(dev + xy_off), reinterpret_cast<const uint32_t*>(dev + cum_off), d_miss, d_all);
     PMX_HIP(hipGetLastError());
     if ((rc = pmx_prof_end(c))) return rc;
     if (to_host) {

@@ -99,7 +99,7 @@ static int cubic_tables_trim(pmx_ctx* c)
 static int lane_ensure(pmx_ctx* c, int i, size_t n, size_t ph, size_t pw)
 {
     PrLane& l = c->pr_lane[i];
-    if (!l.done) PMX_HIP(hipEventCreateWithFlags(&l.done, hipEventDisableTiming));
+    if (int rc = l.done.create(hipEventDisableTiming)) return rc;
     if (i == 0) return PMX_OK;
     if (!l.stream) {
         // Stream priorities (option "precise_lane_priority", default on): the reference's scale order is 0.5, 1, 1.5, 2, so the last lane carries
@@ -112,7 +112,7 @@ static int lane_ensure(pmx_ctx* c, int i, size_t n, size_t ph, size_t pw)
         PMX_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));          // (lo = numerically greatest = least urgent)
         int prio = 0;
         if (c->opt_precise_lane_priority) prio = i == PMX_PR_LANES - 1 ? hi : i == 1 ? lo : (lo + hi) / 2;
-        PMX_HIP(hipStreamCreateWithPriority(&l.stream, hipStreamNonBlocking, prio));
+        if (int rc = l.stream.create(hipStreamNonBlocking, prio)) return rc;
     }
     const size_t px = n * ph * pw;
     if (px <= l.cap_px) return PMX_OK;
@@ -127,12 +127,13 @@ static int lane_ensure(pmx_ctx* c, int i, size_t n, size_t ph, size_t pw)
     l.cap_px = px;
     return PMX_OK;
 }
-// the lane's stream and working set <-> the context's (called in pairs around the enqueue of one scale; lane 0: nothing to do)
-static void lane_swap(pmx_ctx* c, int i)
+// the lane's working set <-> the context's, which then runs on `stream`: the lane's, afterwards the context's own again (called in pairs
+// around the enqueue of one scale; lane 0: nothing to do)
+static void lane_swap(pmx_ctx* c, int i, hipStream_t stream)
 {
     if (i == 0) return;
     PrLane& l = c->pr_lane[i];
-    std::swap(c->stream, l.stream);
+    c->stream = stream;
     c->in16.swap(l.in16); c->act0.swap(l.act0); c->act1.swap(l.act1); c->cat.swap(l.cat);
     c->brA.swap(l.brA); c->brB.swap(l.brB); c->brT.swap(l.brT); c->u8_tmp.swap(l.u8_tmp);
     c->pr_tmp.swap(l.pr_tmp); c->sk_scratch.swap(l.sk_scratch);
@@ -153,8 +154,7 @@ extern "C" int pmx_precise_begin_batch(pmx_ctx* c, int n_images, int orig_h, int
     const size_t need = (size_t)n_images * orig_h * orig_w;
     int rc;
     if ((rc = c->ext_paf.ensure(need * PMX_N_PAF, c->stream)) || (rc = c->ext_heat.ensure(need * PMX_N_HEAT, c->stream))) return rc;
-    if (!c->pr_src_ready) PMX_HIP(hipEventCreateWithFlags(&c->pr_src_ready, hipEventDisableTiming));
-    if (!c->pr_fin) PMX_HIP(hipEventCreateWithFlags(&c->pr_fin, hipEventDisableTiming));
+    if ((rc = c->pr_src_ready.create(hipEventDisableTiming)) || (rc = c->pr_fin.create(hipEventDisableTiming))) return rc;
     // the zero-bias vector of the unit-mode / split-K launches is shared by all lanes: it must exist (and be zero) before two streams can meet it
     if (!c->sk_zero_bias) {
         if ((rc = c->sk_zero_bias.alloc(PMX_SK_ZERO_BIAS))) return rc;
@@ -261,7 +261,7 @@ static int precise_add_scale(pmx_ctx* c, const uint8_t* imgs, int scaled_h, int 
         (rc = cubic_table(c, scaled_w, ow, false, &t4xi, &t4xc)) || (rc = cubic_table(c, scaled_h, oh, false, &t4yi, &t4yc))) return rc;
     (void)xi; (void)yi; (void)xc; (void)yc;
 
-    lane_swap(c, li);                                 // from here on c->stream / c->in16 / ... are the lane's; every exit swaps back
+    lane_swap(c, li, c->pr_lane[li].stream);          // from here on c->stream / c->in16 / ... are the lane's; every exit swaps back
     auto body = [&]() -> int {
         int rc2;
         PMX_HIP(hipStreamWaitEvent(c->stream, c->pr_src_ready, 0));      // the originals are on the device
@@ -306,7 +306,7 @@ static int precise_add_scale(pmx_ctx* c, const uint8_t* imgs, int scaled_h, int 
         return PMX_OK;
     };
     rc = body();
-    lane_swap(c, li);
+    lane_swap(c, li, main_stream);
     if (rc) return rc;
     c->pr_scales += 1;
     c->pr_mask |= 1u << slot;

@@ -370,7 +370,7 @@ extern "C" int pmx_render(pmx_ctx* c, const pmx_box_image* images, int n_images,
         tab[k] = RenderImg{nullptr, nullptr, h, w, tiles_x, (int)tiles, (int)first, (int)(prims.size() - first)};
         tiles += (long long)tiles_x * tiles_y;
         const size_t bytes = (size_t)h * w * 3;
-        in_off[k] = in_total; in_total += (bytes + 255) / 256 * 256;
+        in_off[k] = in_total; in_total += pmx_align_up(bytes, 256);
         out_off[k] = out_total; out_total += bytes;
     }
     if (!on_device && (rc = c->rd_img.ensure(in_total, c->stream))) return rc;
@@ -381,26 +381,21 @@ extern "C" int pmx_render(pmx_ctx* c, const pmx_box_image* images, int n_images,
         tab[k].dst = d_out + out_off[k];
     }
 
-    // ONE staging copy: [image table | primitives] from pinned memory; rd_copied marks when the pinned block may be rewritten
-    const size_t tab_bytes = (tab.size() * sizeof(RenderImg) + 63) / 64 * 64, prim_bytes = prims.size() * sizeof(RenderPrim);
+    // ONE staging copy: [image table | primitives]
+    const size_t tab_bytes = pmx_align_up(tab.size() * sizeof(RenderImg), 64), prim_bytes = prims.size() * sizeof(RenderPrim);
     const size_t bytes = tab_bytes + prim_bytes;
-    if (c->rd_pending) { PMX_HIP(hipEventSynchronize(c->rd_copied)); c->rd_pending = false; }
-    if (bytes > c->rd_host.capacity() && (rc = c->rd_host.alloc(bytes))) return rc;
-    if ((rc = c->rd_dev.ensure(bytes, c->stream))) return rc;
-    if (!c->rd_copied) PMX_HIP(hipEventCreateWithFlags(&c->rd_copied, hipEventDisableTiming));
-    memcpy(c->rd_host, tab.data(), tab.size() * sizeof(RenderImg));
-    if (prim_bytes) memcpy(c->rd_host + tab_bytes, prims.data(), prim_bytes);
-    PMX_HIP(hipMemcpyAsync(c->rd_dev, c->rd_host, bytes, hipMemcpyHostToDevice, c->stream));
-    PMX_HIP(hipEventRecord(c->rd_copied, c->stream));
-    c->rd_pending = true;
+    char *host, *dev;
+    if ((rc = c->rd.begin(bytes, c->stream, &host, &dev))) return rc;
+    memcpy(host, tab.data(), tab.size() * sizeof(RenderImg));
+    if (prim_bytes) memcpy(host + tab_bytes, prims.data(), prim_bytes);
+    if ((rc = c->rd.commit(bytes, c->stream))) return rc;
     if (!on_device)
         for (int k = 0; k < n_images; ++k)
             PMX_HIP(hipMemcpyAsync(c->rd_img + in_off[k], images[k].bgr, (size_t)images[k].h * images[k].w * 3, hipMemcpyHostToDevice, c->stream));
 
     if ((rc = pmx_prof_begin(c, "render|render_tiles_kernel", (double)out_total * 2))) return rc;
     hipLaunchKernelGGL(render_tiles_kernel, dim3((unsigned)tiles), dim3(RT_THREADS), 0, c->stream,
-                       reinterpret_cast<const RenderImg*>(c->rd_dev.get()), n_images,
-                       reinterpret_cast<const RenderPrim*>(c->rd_dev + tab_bytes), blend ? 1 : 0);
+                       reinterpret_cast<const RenderImg*>(dev), n_images, reinterpret_cast<const RenderPrim*>(dev + tab_bytes), blend ? 1 : 0);
     PMX_HIP(hipGetLastError());
     if ((rc = pmx_prof_end(c))) return rc;
     if (!out_on_device) {

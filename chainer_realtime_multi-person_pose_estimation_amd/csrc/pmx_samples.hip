@@ -261,8 +261,6 @@ __global__ void __launch_bounds__(256) samples_dilate_kernel(const uint8_t* __re
     *reinterpret_cast<uchar4*>(out + row * insize + x0) = o;
 }
 
-size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 }  // namespace
 
 extern "C" int pmx_samples_prepare(pmx_ctx* c, const pmx_sample* samples, int n, int insize, int on_device)
@@ -291,7 +289,7 @@ extern "C" int pmx_samples_prepare(pmx_ctx* c, const pmx_sample* samples, int n,
                       "pmx_samples_prepare: sample %d: a sample without the crop is a validation sample and has only the final resize", i);
             tab_ints += (size_t)8 * insize;
         } else {
-            if (rs) { tab_ints += (size_t)4 * (s.resized_w + s.resized_h); a_bytes += align16((size_t)s.resized_w * s.resized_h * 3) + align16((size_t)s.resized_w * s.resized_h); }
+            if (rs) { tab_ints += (size_t)4 * (s.resized_w + s.resized_h); a_bytes += pmx_align_up((size_t)s.resized_w * s.resized_h * 3, 16) + pmx_align_up((size_t)s.resized_w * s.resized_h, 16); }
             if (s.has_rotate) {
                 PMX_CHECK(s.rot_w >= 1 && s.rot_h >= 1 && s.rot_w <= LIM && s.rot_h <= LIM, PMX_ERR_INVALID, "pmx_samples_prepare: sample %d: rotated size %d x %d",
                           i, s.rot_h, s.rot_w);
@@ -305,9 +303,9 @@ extern "C" int pmx_samples_prepare(pmx_ctx* c, const pmx_sample* samples, int n,
                     PMX_CHECK(abs(s.delta[k]) <= RANGE[k], PMX_ERR_INVALID, "pmx_samples_prepare: sample %d: colour offset %d = %d outside +-%d", i, k, s.delta[k],
                               RANGE[k]);
         }
-        if (!on_device) src_bytes += align16((size_t)s.src_h * s.src_w * 3) + (s.mask ? align16((size_t)s.src_h * s.src_w) : 0);
+        if (!on_device) src_bytes += pmx_align_up((size_t)s.src_h * s.src_w * 3, 16) + (s.mask ? pmx_align_up((size_t)s.src_h * s.src_w, 16) : 0);
     }
-    const size_t desc_off = 0, tab_off = align16((size_t)n * sizeof(SampleDev)), src_off = align16(tab_off + tab_ints * sizeof(int));
+    const size_t desc_off = 0, tab_off = pmx_align_up((size_t)n * sizeof(SampleDev), 16), src_off = pmx_align_up(tab_off + tab_ints * sizeof(int), 16);
     const size_t stage_bytes = src_off + src_bytes;
     const size_t npix = (size_t)c->max_batch * insize * insize;
     const size_t total = stage_bytes + a_bytes + npix * 6 + CONST_BYTES;
@@ -315,10 +313,9 @@ extern "C" int pmx_samples_prepare(pmx_ctx* c, const pmx_sample* samples, int n,
               (size_t)PMX_SAMPLES_WORKSPACE_BYTES);
     PMX_DEV(c);
     int rc;
-    if (c->sp_pending) { PMX_HIP(hipEventSynchronize(c->sp_copied)); c->sp_pending = false; }          // the pinned block is free again
+    char *host, *dev;
     c->sp_n = 0;
-    if (stage_bytes > c->sp_host.capacity() && (rc = c->sp_host.alloc(stage_bytes))) return rc;
-    if ((rc = c->sp_dev.ensure(stage_bytes, c->stream)) || (rc = c->sp_a.ensure(a_bytes, c->stream))) return rc;
+    if ((rc = c->sp.begin(stage_bytes, c->stream, &host, &dev)) || (rc = c->sp_a.ensure(a_bytes, c->stream))) return rc;
     if ((rc = c->sp_out.ensure(npix * 3, c->stream)) || (rc = c->sp_mask_raw.ensure(npix, c->stream)) || (rc = c->sp_mask_tmp.ensure(npix, c->stream)) ||
         (rc = c->sp_mask.ensure(npix, c->stream)))
         return rc;
@@ -331,9 +328,6 @@ extern "C" int pmx_samples_prepare(pmx_ctx* c, const pmx_sample* samples, int n,
             PMX_CHECK(false, PMX_ERR_HIP, "pmx_samples_prepare: upload of the weight tables failed");
         }
     }
-    if (!c->sp_copied) PMX_HIP(hipEventCreateWithFlags(&c->sp_copied, hipEventDisableTiming));
-    char* host = c->sp_host;
-    char* dev = c->sp_dev;
     SampleDev* desc = (SampleDev*)(host + desc_off);
     size_t t = 0, so = src_off, ao = 0;
     int max_rs = 0, any_train = 0;
@@ -347,8 +341,8 @@ extern "C" int pmx_samples_prepare(pmx_ctx* c, const pmx_sample* samples, int n,
             d.src = s.bgr; d.msk = s.mask;
         } else {
             memcpy(host + so, s.bgr, px * 3);
-            d.src = (const uint8_t*)dev + so; so += align16(px * 3);
-            if (s.mask) { memcpy(host + so, s.mask, px); d.msk = (const uint8_t*)dev + so; so += align16(px); }
+            d.src = (const uint8_t*)dev + so; so += pmx_align_up(px * 3, 16);
+            if (s.mask) { memcpy(host + so, s.mask, px); d.msk = (const uint8_t*)dev + so; so += pmx_align_up(px, 16); }
         }
         int* tabs = (int*)(host + tab_off) + t;
         const int* dtabs = (const int*)(dev + tab_off) + t;
@@ -362,8 +356,8 @@ extern "C" int pmx_samples_prepare(pmx_ctx* c, const pmx_sample* samples, int n,
             if (s.resized_w) {
                 d.rs_w = s.resized_w; d.rs_h = s.resized_h;
                 const size_t rp = (size_t)d.rs_w * d.rs_h;
-                d.rs_img = c->sp_a + ao; ao += align16(rp * 3);
-                d.rs_msk = c->sp_a + ao; ao += align16(rp);
+                d.rs_img = c->sp_a + ao; ao += pmx_align_up(rp * 3, 16);
+                d.rs_msk = c->sp_a + ao; ao += pmx_align_up(rp, 16);
                 d.a_img = d.rs_img; d.a_msk = s.mask ? d.rs_msk : nullptr; d.ah = d.rs_h; d.aw = d.rs_w;
             }
             d.rotate = s.has_rotate ? 1 : 0;
@@ -383,9 +377,7 @@ extern "C" int pmx_samples_prepare(pmx_ctx* c, const pmx_sample* samples, int n,
         }
         desc[i] = d;
     }
-    PMX_HIP(hipMemcpyAsync(c->sp_dev, c->sp_host, stage_bytes, hipMemcpyHostToDevice, c->stream));
-    PMX_HIP(hipEventRecord(c->sp_copied, c->stream));
-    c->sp_pending = true;
+    if ((rc = c->sp.commit(stage_bytes, c->stream))) return rc;
     const SampleDev* dd = (const SampleDev*)(dev + desc_off);
     const int32_t* wcub = (const int32_t*)c->sp_const.get();
     const int32_t* wlin = wcub + N_CUBIC;

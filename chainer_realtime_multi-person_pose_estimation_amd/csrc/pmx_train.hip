@@ -210,8 +210,7 @@ void pmx_train_free(pmx_ctx* c)
 {
     TrainState& tr = c->tr;
     if (!tr.on) return;
-    tr.w.reset(); tr.m.reset(); tr.v.reset(); tr.seg_dev.reset(); tr.seg_host.reset();
-    tr.seg_pending = false;
+    tr.w.reset(); tr.m.reset(); tr.v.reset(); tr.seg.reset();
     mark_busy(c, false);
     tr.on = 0;
 }
@@ -236,29 +235,28 @@ extern "C" int pmx_train_enable(pmx_ctx* c, int on)
     PMX_CHECK(c->bw.on, PMX_ERR_STATE, "pmx_train_enable: the head backward is off (pmx_backward_enable)");
     if ((rc = pmx_check_weights(c))) return rc;
     const size_t total = c->bw.grad.capacity();
+    hipStream_t st = c->stream;
+    char *host, *dev;      // (the steps' table is reserved here: a step allocates nothing)
     const bool ok = tr.w.alloc(total) == PMX_OK && tr.m.alloc(total) == PMX_OK && tr.v.alloc(total) == PMX_OK &&
-                    tr.seg_dev.alloc(table_bytes(c->table.size())) == PMX_OK && tr.seg_host.alloc(table_bytes(c->table.size())) == PMX_OK;
+                    tr.seg.begin(table_bytes(c->table.size()), st, &host, &dev) == PMX_OK;
     if (!ok) {
         (void)hipGetLastError();
-        tr.w.reset(); tr.m.reset(); tr.v.reset(); tr.seg_dev.reset(); tr.seg_host.reset();
+        tr.w.reset(); tr.m.reset(); tr.v.reset(); tr.seg.reset();
         pmx_set_error("pmx_train_enable: the device has no room for the master weights and the two moments (3 x %.2f GB)", total * 4e-9);
         return PMX_ERR_CAPACITY;
     }
-    hipStream_t st = c->stream;
-    if (!tr.seg_copied) PMX_HIP(hipEventCreateWithFlags(&tr.seg_copied, hipEventDisableTiming));
     PMX_HIP(hipMemsetAsync(tr.w, 0, total * sizeof(float), st));
     PMX_HIP(hipMemsetAsync(tr.m, 0, total * sizeof(float), st));
     PMX_HIP(hipMemsetAsync(tr.v, 0, total * sizeof(float), st));
     for (size_t i = 0; i < c->layers.size(); ++i)
         if (has_segment(c, (int)i) && (rc = pmx_unpack_launch(c->layers[i], pmx_pack_kind(c, c->layers[i].cin), tr.w + c->bw.grad_off[i], st))) {
             (void)hipStreamSynchronize(st);
-            tr.w.reset(); tr.m.reset(); tr.v.reset(); tr.seg_dev.reset(); tr.seg_host.reset();
+            tr.w.reset(); tr.m.reset(); tr.v.reset(); tr.seg.reset();
             return rc;
         }
     tr.t.assign(c->table.size(), 0);
     tr.scale.assign(c->table.size(), 1.0f);
     tr.alpha = 1e-4; tr.beta1 = 0.9; tr.beta2 = 0.999; tr.eps = 1e-8;
-    tr.seg_pending = false;
     tr.on = 1;
     mark_busy(c, true);
     return PMX_OK;
@@ -296,10 +294,9 @@ static int train_step(pmx_ctx* c, const char* who, bool full)
     PMX_CHECK(!bw.stepped, PMX_ERR_STATE, "%s: a step has consumed these gradients (run a new retained forward and the backward)", who);
     PMX_DEV(c);
     hipStream_t st = c->stream;
-    if (tr.seg_pending) { PMX_HIP(hipEventSynchronize(tr.seg_copied)); tr.seg_pending = false; }      // the pinned table is free again
     const size_t N = c->table.size();
-    char* const host = tr.seg_host.get();
-    const char* const dev = tr.seg_dev.get();
+    char *host, *dev;      // (reserved by pmx_train_enable: this waits for the last step's copy and allocates nothing)
+    if ((rc = tr.seg.begin(table_bytes(N), st, &host, &dev))) return rc;
     AdamSeg* seg = reinterpret_cast<AdamSeg*>(host);
     JobList jl[PMX_PACK_KINDS];
     for (int k = 0; k < PMX_PACK_KINDS; ++k) jl[k].job = reinterpret_cast<PackJob*>(host + jobs_at(N, k));
@@ -323,9 +320,7 @@ static int train_step(pmx_ctx* c, const char* who, bool full)
     }
     bw.stepped = true;
     mark_busy(c, true);
-    PMX_HIP(hipMemcpyAsync(tr.seg_dev, host, table_bytes(N), hipMemcpyHostToDevice, st));
-    PMX_HIP(hipEventRecord(tr.seg_copied, st));
-    tr.seg_pending = true;
+    if ((rc = tr.seg.commit(table_bytes(N), st))) return rc;
     if ((rc = pmx_prof_begin(c, "train_step|adam", bytes))) return rc;
     rc = launch_adam(tr.w, tr.m, tr.v, bw.grad, reinterpret_cast<const AdamSeg*>(dev), nseg, blocks, (float)(1.0 - tr.beta1),
                      (float)(1.0 - tr.beta2), (float)tr.eps, st);

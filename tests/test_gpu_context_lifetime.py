@@ -1,5 +1,6 @@
-"""GPU: a context gives back all the device memory it took.  Every buffer of a context is a DevBuf member (csrc/pmx_ctx.h), freed by
-~pmx_ctx; this test creates and closes engines that have used every growth path and reads the device's free memory between the cycles."""
+"""GPU: a context gives back all the device memory it took.  Every buffer of a context is a DevBuf member, every per-call staging block a
+Staging member, every event and stream an Event or Stream member (csrc/pmx_ctx.h), freed by ~pmx_ctx; this test creates and closes
+engines that have used every growth path and reads the device's free memory between the cycles."""
 import numpy as np
 import pytest
 
@@ -42,6 +43,16 @@ def _pose_cycle(native, weights):
         eng.postprocess(80, 112, img_len=112)
         eng.results()
         assert eng.capacities()['peaks_per_joint'] > 2
+        # the staging blocks of the result images, the ignore masks and the sample preparation (the face cycle grows the boxes')
+        poses = np.zeros((2, 18, 3))
+        poses[:, :, 0], poses[:, :, 1], poses[:, :, 2] = rng.uniform(0, 40, (2, 18)), rng.uniform(0, 30, (2, 18)), 2
+        canvas, = eng.render([u8(30, 40)], [poses], blend=True)
+        assert canvas.shape == (30, 40, 3)
+        miss, all_ = eng.coco_masks([(17, 33)], [[(0, 0, 1, [2, 2, 30, 4, 10, 15])]])
+        assert all_[0].any()
+        imgs = [u8(24, 40), u8(96, 72)]
+        eng.samples_prepare(imgs, None, [pkg('samples').SampleRecord.val(im.shape[:2], 64) for im in imgs], 64)
+        assert eng.samples_get()[0].shape == (2, 64, 64, 3)
     finally:
         eng.close()
 
@@ -60,10 +71,11 @@ def _face_cycle(native, weights):
 
 def test_contexts_return_their_device_memory(native):
     """Four times: a pose engine through detect_batch, a mixed-size detect_images, the detect_precise sequence on four lanes,
-    detect_precise_images on a mixed-size list and a post-process that regrows its capacities, then a face engine through
-    keypoints_boxes; both closed.  The free device memory after cycles 2, 3 and 4 must agree within PARENT_DRIFT (cycle 1 also pays for
-    what the runtime keeps for the process: code objects, streams' scratch).  Parent commit, same test: 308241498112 bytes free after every
-    cycle, drift 0 bytes (EXPERIMENTS.md E30); that figure is PARENT_DRIFT."""
+    detect_precise_images on a mixed-size list, a post-process that regrows its capacities, one render, one coco_masks and one
+    samples_prepare (the staging blocks), then a face engine through keypoints_boxes; both closed.  The free device memory after cycles
+    2, 3 and 4 must agree within PARENT_DRIFT (cycle 1 also pays for what the runtime keeps for the process: code objects, streams'
+    scratch).  Parent commit, same test: 308241498112 bytes free after every cycle, drift 0 bytes (EXPERIMENTS.md E30); that figure is
+    PARENT_DRIFT."""
     import torch
     W = pkg('weights')
     pose_w, face_w = W.synthetic_weights(0), W.synthetic_weights(0, 'facenet')

@@ -6,7 +6,9 @@ of a sequence, and travels with Engine.state().  A3: a call is ordered AFTER the
 synchronisation in between -- the input buffer holds a decoy, and on the stream a long delay, the copy of the real input and the library
 call are enqueued; the results must be those of the real input.  A4: the caller's consumer on that stream is ordered after the call's device
 outputs (prefilled with a sentinel).  A5: the control -- the same chain with the context left on its own stream does return the decoy's
-canvas, so A3 and A4 can tell.
+canvas, so A3 and A4 can tell.  A6: calls enqueued back to back behind unfinished work, with no host synchronisation between them, are
+each drawn from their own tables -- the per-call staging block (csrc/pmx_ctx.h: Staging) is reused by the second call and regrown by the
+third while the first is still queued.
 
 The delay is a chain of torch matmuls on the stream, timed with torch events inside every chain: at least 20 x the device time of the call
 under test, itself measured on the context's own stream (pmx_timer_*).  An unordered reader therefore certainly arrives first."""
@@ -539,6 +541,84 @@ def test_render_canvases_are_ready_for_the_callers_consumer(native, rend, torch,
     assert not (got == SENTINEL).all(), 'the clone ran before the render: it holds the sentinel'
     assert not np.array_equal(got, want_decoy), 'the render read the DECOY images'
     assert np.array_equal(got, want_real)
+
+
+# ---- A6. calls back to back behind unfinished work: each is drawn from its own tables ---------------------------------------------------
+def _back_to_back(native, torch, S, delay, chain, calls, what):
+    """calls: A, B, C, each (engine, chain.bufs) -> the call's device outputs, which live in buffers of the caller's.  A has the larger
+    tables; B, smaller and different, reuses the staging block, so only the wait for A's copy keeps A's tables from being rewritten under
+    it; C, larger than A, regrows both halves of the block.  The reference of each is the same call alone on a fresh context.  Then ONE
+    context, whose block a first A has sized (a growing A would wait for the stream itself), on the caller's stream: the delay, the copy
+    of the real inputs, A, B, C -- and one synchronisation of the stream."""
+    read = lambda out: {'out%d' % i: t.cpu().numpy() for i, t in enumerate(out)}
+    chain.fill(chain.real)
+    want = []
+    for call in calls:
+        e = native.Engine(0, **CS.RENDER)
+        try:
+            out = call(e, chain.bufs)
+            e.synchronize()
+            want.append(read(out))
+            if call is calls[-1]:                            # the device time of the three calls, on this context's own stream
+                e.timer_start()
+                for c in calls:
+                    c(e, chain.bufs)
+                chain.call_ms = e.timer_stop()
+        finally:
+            e.close()
+    flat = [b''.join(w[k].tobytes() for k in sorted(w)) for w in want]
+    assert len(set(flat)) == 3, what + ': two of the three calls give the same bytes: the check would mean nothing'
+    e = native.Engine(0, **CS.RENDER)
+    try:
+        calls[0](e, chain.bufs)
+        e.synchronize()
+        with on_stream(e, S):
+            outs = chain.enqueue(lambda bufs: [call(e, bufs) for call in calls])
+            chain.check_delay(what)                          # (synchronises the stream: the one synchronisation)
+            got = [read(out) for out in outs]
+    finally:
+        e.close()
+    for name, g, w in zip('ABC', got, want):
+        _equal(g, w, '%s: call %s' % (what, name))
+
+
+def _people(seed, n, h, w):
+    rng = np.random.default_rng(seed)
+    p = np.zeros((n, 18, 3))
+    p[:, :, 0], p[:, :, 1] = rng.uniform(-3, w + 3, (n, 18)), rng.uniform(-3, h + 3, (n, 18))
+    p[:, :, 2] = np.where(rng.random((n, 18)) < 0.2, 0, 2)
+    return p
+
+
+def test_renders_back_to_back_are_each_drawn_from_their_own_tables(native, torch, S, delay):
+    """A: two images of 30 x 40 and 24 x 33 with 12 people; B: the 30 x 40 image with one person; C: three images with 40 people"""
+    sizes = [(30, 40), (24, 33), (28, 36)]
+    chain = Chain(torch, S, delay, [CS.u8(250 + i, h, w) for i, (h, w) in enumerate(sizes)], [CS.u8(260 + i, h, w) for i, (h, w) in enumerate(sizes)])
+
+    def call(seed, people):
+        poses = [_people(seed + i, n, *sizes[i]) for i, n in enumerate(people)]
+        return lambda e, bufs: e.render(bufs[:len(people)], poses, blend=True)
+
+    _back_to_back(native, torch, S, delay, chain, [call(270, (7, 5)), call(280, (1,)), call(290, (15, 12, 13))], 'render x 3')
+
+
+def _polygons(seed, h, w, n):
+    """n polygon parts of 3 .. 8 vertices in and around the image, one annotation each: miss, miss, crowd, ..."""
+    rng = np.random.default_rng(seed)
+    return [(0, i, 2 if i % 3 == 2 else 1, np.round(rng.uniform(-0.2, 1.2, (int(rng.integers(3, 9)), 2)) * [w, h], 1).reshape(-1)) for i in range(n)]
+
+
+def test_coco_masks_back_to_back_are_each_drawn_from_their_own_tables(native, torch, S, delay):
+    """A: two images of 17 x 33 and 40 x 21 with ten polygons and one run-length part; B: a 17 x 33 image with one triangle; C: three
+    images with thirty polygons"""
+    A = [(17, 33), (40, 21)], [_polygons(300, 17, 33, 6) + [(1, 6, 1, np.array([100, 50, 200, 211], np.uint32))], _polygons(301, 40, 21, 4)]
+    B = [(17, 33)], [[(0, 0, 1, [2, 2, 30, 4, 10, 15])]]
+    C = [(17, 33), (40, 21), (25, 47)], [_polygons(310, 17, 33, 12), _polygons(311, 40, 21, 9), _polygons(312, 25, 47, 9)]
+    nbytes = lambda sizes, parts: sum(t.nbytes for t in native.coco_mask_tables(sizes, parts))
+    assert nbytes(*B) + 4 * 64 < nbytes(*A) and nbytes(*A) + 4 * 64 < nbytes(*C)          # (the four tables are padded to 64 bytes each)
+    chain = Chain(torch, S, delay, [], [])
+    call = lambda sizes, parts: lambda e, _: [m for masks in e.coco_masks(sizes, parts, device=True) for m in masks]
+    _back_to_back(native, torch, S, delay, chain, [call(*A), call(*B), call(*C)], 'coco_masks x 3')
 
 
 # ---- A2 (continued). the stream travels with the state ----------------------------------------------------------------------------------
