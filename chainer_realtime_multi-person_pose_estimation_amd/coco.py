@@ -10,9 +10,17 @@ batch, so the `ignore_mask_*2017` directories are no prerequisite any more.
   mask_classes / mask_parts           per annotation its class (keep / miss / crowd) and its segmentation as polygon / run-length parts
   polygon_mask / rle_mask / masks_numpy   THE MASK CONTRACT (host NumPy; the oracle of the device entry, like the NumPy drawing functions)
   batches                             annotation file + image directory -> the (imgs, poses, masks) triples of train_loop / train_step
+  detections / ground_truths          what the key-point evaluation sees of a detector's output and of an image's annotations
+  oks_matrix / evaluate_image         THE EVALUATION CONTRACT per image (host NumPy; the oracle of pmx_coco_eval, csrc/pmx_eval.hip)
+  accumulate / summarize              precision / recall over a data set and the ten AP / AR numbers (host only)
+  results                             detections in the COCO results format, for the official tool elsewhere
+  evaluate                            annotation file + image directory + detector -> AP / AR, the per-image part on the device
 
 The mask contract restates `annToMask` of the library's C part (rleFrPoly + rleMerge + rleDecode) from its published source.  The library
 is not a dependency and the restatement has not been compared with it bit for bit: that pin is open.
+The evaluation contract restates `COCOeval` with iouType = 'keypoints' (and `loadRes` for the detections' areas) from the same published
+source, under the same terms: no dependency, and its pin against the real library is open too -- `results` writes the detections in the
+format the official tool reads, so the same detections can be scored there.
 """
 import json
 import os
@@ -251,3 +259,253 @@ def batches(dataset, detector, image_dir, batch, insize=368, mode='train', rng=N
             anns.append(dataset.annotations(img_id))
         masks = detector.ignore_masks(anns, [tuple(im.shape[:2]) for im in imgs], device=True)
         yield detector.prepare_samples(imgs, poses, masks, insize=insize, mode=mode)
+
+
+# ---- the evaluation contract -----------------------------------------------------------------------------------------------------------
+# COCOeval with iouType = 'keypoints' (computeOks, evaluateImg, accumulate, summarize; loadRes for the detections' areas), restated
+# from the library's published source.  The constants are computed with the library's own expressions, in float64, once; the device
+# entry gets these very doubles (eval_consts).
+KP_SIGMAS = np.array([.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89]) / 10.0
+KP_VARS = (KP_SIGMAS * 2) ** 2
+KP_EPS = np.spacing(1)
+IOU_THRS = np.linspace(.5, .95, 10)
+REC_THRS = np.linspace(0, 1, 101)
+MAX_DETS = 20
+AREA_RNGS = [[0, 1e5 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]]
+AREA_LABELS = ('all', 'medium', 'large')
+EVAL_MAX_GT = 512                    # PMX_EVAL_MAX_GT: ground truths of one image the device entry takes
+SUMMARY_KEYS = ('AP', 'AP50', 'AP75', 'AP_medium', 'AP_large', 'AR', 'AR50', 'AR75', 'AR_medium', 'AR_large')
+
+
+def detections(poses, scores):
+    """The detections of one image as the evaluation sees them: {'keypoints' (n, 17, 3) float64, 'score' (n,), 'area' (n,)} from the
+    (n, 18, 3) poses and the scores a detector returns.  COCO key point i is joint params['coco_joint_indices'][i] (the neck is
+    dropped): (x, y, 1) where the joint was found (v != 0), else (0, 0, 0).  The score is the record's score, subsets[:, -2]: the sum of
+    the person's peak and connection scores -- the number the detector itself ranks hypotheses by; the reference publishes no COCO score,
+    and the evaluation only uses the order it gives.  area = (max x - min x) * (max y - min y) over all 17 points, zeros included, as
+    loadRes computes it."""
+    poses = np.asarray(poses, dtype=np.float64)
+    scores = np.asarray(scores, dtype=np.float64).reshape(-1)
+    if poses.size == 0:
+        poses = np.zeros((0, len(JointType), 3))
+    if poses.ndim != 3 or poses.shape[1:] != (len(JointType), 3) or len(poses) != len(scores):
+        raise ValueError('detections: poses (n, 18, 3) and n scores expected, got %r and %r' % (poses.shape, scores.shape))
+    rows = poses[:, [int(j) for j in params['coco_joint_indices']], :]
+    found = rows[:, :, 2] != 0
+    kp = np.zeros((len(poses), 17, 3))
+    kp[:, :, 0] = np.where(found, rows[:, :, 0], 0.0)
+    kp[:, :, 1] = np.where(found, rows[:, :, 1], 0.0)
+    kp[:, :, 2] = found
+    if len(kp):
+        area = (kp[:, :, 0].max(axis=1) - kp[:, :, 0].min(axis=1)) * (kp[:, :, 1].max(axis=1) - kp[:, :, 1].min(axis=1))
+    else:
+        area = np.zeros(0)
+    return {'keypoints': kp, 'score': scores.copy(), 'area': area}
+
+
+def ground_truths(annotations):
+    """Every annotation of one image, in file order, as the evaluation sees it: {'keypoints' (G, 17, 3), 'area', 'bbox' (G, 4), 'iscrowd',
+    'num_keypoints', 'ignore'}; ignore = iscrowd == 1 or num_keypoints == 0, num_keypoints taken from the field.  A dictionary this
+    function made passes through."""
+    if isinstance(annotations, dict):
+        return annotations
+    G = len(annotations)
+    out = {'keypoints': np.zeros((G, 17, 3)), 'area': np.zeros(G), 'bbox': np.zeros((G, 4)), 'iscrowd': np.zeros(G, np.int32),
+           'num_keypoints': np.zeros(G, np.int32)}
+    for g, a in enumerate(annotations):
+        out['keypoints'][g] = np.asarray(a['keypoints'], dtype=np.float64).reshape(17, 3)
+        out['area'][g] = a['area']
+        out['bbox'][g] = a['bbox']
+        out['iscrowd'][g] = int(a.get('iscrowd', 0))
+        out['num_keypoints'][g] = int(a['num_keypoints'])
+    out['ignore'] = (out['iscrowd'] == 1) | (out['num_keypoints'] == 0)
+    return out
+
+
+def detection_order(dets):
+    """indices of the detections that are evaluated: argsort(-score, kind='mergesort') cut to MAX_DETS"""
+    return np.argsort(-dets['score'], kind='mergesort')[:MAX_DETS]
+
+
+def oks_matrix(dets, gts):
+    """computeOks: the (D, G) float64 object-key-point similarities of the ranked detections (detection_order) and the ground truths; an
+    empty array if either side is empty.  The terms exp(-e_i) are added one after the other in ascending key-point order (the
+    accumulator below), which is part of the contract: the device entry adds them the same way."""
+    gts = ground_truths(gts)
+    order = detection_order(dets)
+    D, G = len(order), len(gts['area'])
+    if D == 0 or G == 0:
+        return np.zeros((0, 0))
+    kd = dets['keypoints'][order]
+    xd, yd = kd[:, :, 0], kd[:, :, 1]
+    out = np.zeros((D, G))
+    for g in range(G):
+        xg, yg, vg = gts['keypoints'][g, :, 0], gts['keypoints'][g, :, 1], gts['keypoints'][g, :, 2]
+        k1 = np.count_nonzero(vg > 0)
+        if k1 > 0:
+            dx = xd - xg
+            dy = yd - yg
+        else:
+            bb = gts['bbox'][g]
+            x0, x1, y0, y1 = bb[0] - bb[2], bb[0] + bb[2] * 2, bb[1] - bb[3], bb[1] + bb[3] * 2
+            dx = np.maximum(0, x0 - xd) + np.maximum(0, xd - x1)
+            dy = np.maximum(0, y0 - yd) + np.maximum(0, yd - y1)
+        e = (dx * dx + dy * dy) / KP_VARS / (gts['area'][g] + KP_EPS) / 2
+        term = np.exp(-e)
+        acc, cnt = np.zeros(D), 0
+        for i in range(17):
+            if k1 > 0 and not vg[i] > 0:
+                continue
+            acc = acc + term[:, i]
+            cnt += 1
+        out[:, g] = acc / cnt
+    return out
+
+
+def evaluate_image(dets, gts, oks=None):
+    """evaluateImg for the three area ranges at once.  None if the image has neither detections nor ground truths, else
+    {'order' (D,) indices into the input people, 'scores' (D,), 'areas' (D,), 'dt_match' (3, 10, D) int32 file-order index of the matched
+    ground truth or -1, 'dt_ig' (3, 10, D) bool, 'gt_ig' (3, G) bool}, D = min(n, MAX_DETS).  `oks`: a matrix to use instead of
+    oks_matrix(dets, gts)."""
+    gts = ground_truths(gts)
+    order = detection_order(dets)
+    D, G = len(order), len(gts['area'])
+    if D == 0 and G == 0:
+        return None
+    if oks is None:
+        oks = oks_matrix(dets, gts)
+    d_area = dets['area'][order]
+    crowd = gts['iscrowd'] == 1
+    dt_match = np.full((3, len(IOU_THRS), D), -1, dtype=np.int32)
+    dt_ig = np.zeros((3, len(IOU_THRS), D), dtype=bool)
+    gt_ig = np.zeros((3, G), dtype=bool)
+    for a, (lo, hi) in enumerate(AREA_RNGS):
+        ig = gts['ignore'] | (gts['area'] < lo) | (gts['area'] > hi)
+        gt_ig[a] = ig
+        walk = np.argsort(ig, kind='mergesort')
+        if D and G:
+            for t, thr in enumerate(IOU_THRS):
+                matched = np.zeros(G, dtype=bool)
+                for d in range(D):
+                    iou, m = min(thr, 1 - 1e-10), -1
+                    for g in walk:
+                        if matched[g] and not crowd[g]:
+                            continue
+                        if m > -1 and not ig[m] and ig[g]:
+                            break
+                        if oks[d, g] < iou:
+                            continue
+                        iou, m = oks[d, g], int(g)
+                    if m == -1:
+                        continue
+                    dt_match[a, t, d] = m
+                    dt_ig[a, t, d] = ig[m]
+                    matched[m] = True
+        outside = (d_area < lo) | (d_area > hi)
+        dt_ig[a] |= (dt_match[a] == -1) & outside[None, :]
+    return {'order': order.astype(np.int64), 'scores': dets['score'][order], 'areas': d_area, 'dt_match': dt_match, 'dt_ig': dt_ig, 'gt_ig': gt_ig}
+
+
+def accumulate(per_image):
+    """COCOeval.accumulate over the evaluate_image results of a data set (None entries are skipped): (precision (10, 101, 3), recall
+    (10, 3)), -1 where an area range has no kept ground truth."""
+    per_image = [e for e in per_image if e is not None]
+    T, R = len(IOU_THRS), len(REC_THRS)
+    precision, recall = -np.ones((T, R, 3)), -np.ones((T, 3))
+    for a in range(3):
+        if not per_image:
+            continue
+        scores = np.concatenate([e['scores'] for e in per_image])
+        inds = np.argsort(-scores, kind='mergesort')
+        match = np.concatenate([e['dt_match'][a] >= 0 for e in per_image], axis=1)[:, inds]
+        ig = np.concatenate([e['dt_ig'][a] for e in per_image], axis=1)[:, inds]
+        npig = np.count_nonzero(np.concatenate([e['gt_ig'][a] for e in per_image]) == 0)
+        if npig == 0:
+            continue
+        tp_sum = np.cumsum(match & ~ig, axis=1).astype(dtype=float)
+        fp_sum = np.cumsum(~match & ~ig, axis=1).astype(dtype=float)
+        for t, (tp, fp) in enumerate(zip(tp_sum, fp_sum)):
+            nd = len(tp)
+            rc = tp / npig
+            pr = tp / (fp + tp + KP_EPS)
+            q = np.zeros(R)
+            recall[t, a] = rc[-1] if nd else 0
+            for i in range(nd - 1, 0, -1):
+                if pr[i] > pr[i - 1]:
+                    pr[i - 1] = pr[i]
+            idx = np.searchsorted(rc, REC_THRS, side='left')
+            for r, pi in enumerate(idx):
+                if pi >= nd:
+                    break
+                q[r] = pr[pi]
+            precision[t, :, a] = q
+    return precision, recall
+
+
+def summarize(precision, recall):
+    """The ten numbers of COCOeval.summarize for key points, in its order (a dictionary keeps insertion order): each the mean of the
+    entries > -1 of its slice, -1 if there is none.  AP50 / AP75 are the thresholds IOU_THRS[0] / IOU_THRS[5]."""
+    def mean(s):
+        s = s[s > -1]
+        return float(np.mean(s)) if s.size else -1.0
+    out = {}
+    for name, s in (('AP', precision), ('AR', recall)):
+        out[name] = mean(s[..., 0])
+        out[name + '50'] = mean(s[0, ..., 0])
+        out[name + '75'] = mean(s[5, ..., 0])
+        out[name + '_medium'] = mean(s[..., 1])
+        out[name + '_large'] = mean(s[..., 2])
+    return out
+
+
+def results(img_ids, poses_per_image, scores_per_image):
+    """The detections in the COCO results format: a list of {'image_id', 'category_id': 1, 'keypoints': [51 numbers], 'score'}, the
+    people of every image in the detector's order.  Written to a JSON file, the official tool can score the same detections elsewhere."""
+    out = []
+    for img_id, poses, scores in zip(img_ids, poses_per_image, scores_per_image):
+        d = detections(poses, scores)
+        for kp, s in zip(d['keypoints'], d['score']):
+            out.append({'image_id': img_id, 'category_id': 1, 'keypoints': [float(v) for v in kp.reshape(-1)], 'score': float(s)})
+    return out
+
+
+def eval_consts():
+    """the constant tables as one pmx_eval_consts record (include/pose_mi355x.h): vars[17], iou_thrs[10], area_rngs[3][2], eps, joint[17]"""
+    k = np.zeros(1, dtype=EVAL_CONSTS_DTYPE)
+    k['vars'], k['iou_thrs'], k['area_rngs'], k['eps'] = KP_VARS, IOU_THRS, np.array(AREA_RNGS, dtype=np.float64), KP_EPS
+    k['joint'] = [int(j) for j in params['coco_joint_indices']]
+    return k
+
+
+EVAL_CONSTS_DTYPE = np.dtype([('vars', np.float64, (17,)), ('iou_thrs', np.float64, (10,)), ('area_rngs', np.float64, (3, 2)),
+                              ('eps', np.float64), ('joint', np.int32, (17,)), ('reserved', np.int32)])
+EVAL_GT_DTYPE = np.dtype([('keypoints', np.float64, (17, 3)), ('area', np.float64), ('bbox', np.float64, (4,)), ('iscrowd', np.int32),
+                          ('num_keypoints', np.int32)])      # pmx_eval_gt
+
+
+def evaluate(ds, det, image_dir, batch=8, img_ids=None, precise=False, on_batch=None):
+    """From a detector to its COCO key-point AP: walks the images of the annotation file `ds` (a CocoKeypoints; default every entry of
+    ds.images in id order, the images without annotations included -- their detections are false positives, as in the library), `batch`
+    at a time through det.evaluate_batch (detection and the per-image evaluation on the device), then accumulate and summarize on the
+    host.  -> the ten numbers of summarize plus 'precision', 'recall', 'results' (the COCO results list) and 'per_image'.  An image with
+    more than EVAL_MAX_GT annotations is scored by evaluate_image on the host.  on_batch(done, total), if given, is called after every
+    batch."""
+    from .pose_detector import imread_bgr
+    ids = sorted(ds.images) if img_ids is None else list(img_ids)
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError('evaluate: batch = %d' % batch)
+    per_image, all_poses, all_scores = [], [], []
+    for i in range(0, len(ids), batch):
+        chunk = ids[i:i + batch]
+        imgs = [imread_bgr(os.path.join(image_dir, ds.file_name(k))) for k in chunk]
+        ev, poses, scores = det.evaluate_batch(imgs, [ds.annotations(k) for k in chunk], precise=precise)
+        per_image += ev
+        all_poses += poses
+        all_scores += scores
+        if on_batch is not None:
+            on_batch(min(i + batch, len(ids)), len(ids))
+    precision, recall = accumulate(per_image)
+    out = summarize(precision, recall)
+    out.update(precision=precision, recall=recall, results=results(ids, all_poses, all_scores), per_image=per_image)
+    return out

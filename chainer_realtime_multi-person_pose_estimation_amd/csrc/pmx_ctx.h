@@ -414,6 +414,10 @@ struct pmx_ctx {
     // output is host memory.  All grow on demand.
     Staging mk;
     DevBuf<uint8_t> mk_out;
+    // pmx_eval.hip (COCO key-point evaluation).  ev: [image table | ground truths | constants | scores | poses]; ev_out: every output
+    // table of the call.  Both grow on demand.
+    Staging ev;
+    DevBuf<char> ev_out;
     BwState bw;                                          // pmx_backward.hip
     TrainState tr;                                        // pmx_train.hip
 };

@@ -30,7 +30,8 @@ SOURCES = [('pmx_api.hip', []), ('pmx_precise.hip', []), ('pmx_multi.hip', []), 
            ('pmx_samples.hip', ['-ffp-contract=off']), ('conv_bwd.hip', ['-ffp-contract=off']),
            ('pmx_backward.hip', ['-ffp-contract=off']), ('pmx_packs.hip', ['-ffp-contract=off']),
            ('pmx_train.hip', ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt']),
-           ('pmx_render.hip', ['-ffp-contract=off']), ('pmx_masks.hip', ['-ffp-contract=off'])]
+           ('pmx_render.hip', ['-ffp-contract=off']), ('pmx_masks.hip', ['-ffp-contract=off']),
+           ('pmx_eval.hip', ['-ffp-contract=off'])]
 # the opt-in bf16x3 kernels (option "precision" = 1; DESIGN.md 4.1.5: frozen, slower than the fp32 Winograd path) are NOT part of the
 # default library: PMX_BUILD_BF16X3=1 in the environment of the build adds their translation unit (the stamp then differs, so the
 # library is rebuilt when the variable changes)
@@ -290,6 +291,7 @@ def load():
         'pmx_render': (ci, [vp, vp, ci, ci, vp, vp, vp, ci, vp, ci, vp, ci]),
         'pmx_coco_masks': (ci, [vp, vp, ci, vp, ci, vp, C.c_size_t, vp, C.c_size_t, vp, vp, ci]),
         'pmx_coco_masks_strip': (ci, [ci]),
+        'pmx_coco_eval': (ci, [vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         'pmx_precise_begin': (ci, [vp, ci, ci]),
         'pmx_precise_add_scale': (ci, [vp, vp, ci, ci]),
         'pmx_precise_finish': (ci, [vp]),
@@ -866,6 +868,70 @@ class Engine(object):
                 m = flat[k, off:off + n].reshape(int(h), int(w))
                 out[k].append(m if device else m.astype(bool))
                 off += n
+        return out
+
+    # ---- COCO key-point evaluation (pmx_coco_eval) ------------------------------------------------------
+    def coco_eval(self, gts_per_image, poses_per_image=None, scores_per_image=None, oks=False):
+        """COCOeval's per-image step (OKS, ranking, the 3 x 10 matching walks) for a batch of images in one launch: per image what
+        coco.evaluate_image returns (None for an image with neither detections nor ground truths), with oks=True plus 'oks', the (D, G)
+        matrix.  gts_per_image: per image its annotation dictionaries in file order, or what coco.ground_truths made of them.
+        poses_per_image / scores_per_image: per image (n, 18, 3) rows (x, y, v) and n scores, as a detector returns them; None: the
+        first len(gts_per_image) result records of the last post-process, read where they lie on the device.  Argument errors raise
+        ValueError before the device is touched; what the tables may hold is the library's to check."""
+        from . import coco
+        gts = [coco.ground_truths(g) for g in gts_per_image]
+        n = len(gts)
+        if n == 0:
+            raise ValueError('coco_eval needs at least one image')
+        counts = np.array([len(g['area']) for g in gts], dtype=np.int64)
+        total = int(counts.sum())
+        images = np.zeros((n, 2), dtype=np.int32)
+        images[:, 0], images[:, 1] = np.cumsum(counts) - counts, counts
+        table = np.zeros(max(total, 1), dtype=coco.EVAL_GT_DTYPE)
+        for g, off in zip(gts, images[:, 0]):
+            for key in coco.EVAL_GT_DTYPE.names:
+                table[key][off:off + len(g['area'])] = g[key]
+        consts = coco.eval_consts()
+        p_poses = p_scores = p_people = None
+        if poses_per_image is not None:
+            if scores_per_image is None or len(poses_per_image) != n or len(scores_per_image) != n:
+                raise ValueError('coco_eval: poses and scores for each of the %d images expected' % n)
+            rows, scs, n_people = [], [], []
+            for i, (p, s) in enumerate(zip(poses_per_image, scores_per_image)):
+                p, s = np.asarray(p, dtype=np.float64), np.asarray(s, dtype=np.float64).reshape(-1)
+                if p.size == 0 and s.size == 0:
+                    n_people.append(0)
+                    continue
+                if p.ndim != 3 or p.shape[1:] != (N_JOINTS, 3) or len(p) != len(s):
+                    raise ValueError('image %d: poses (n, %d, 3) and n scores expected, got %r and %r' % (i, N_JOINTS, p.shape, s.shape))
+                rows.append(p)
+                scs.append(s)
+                n_people.append(len(p))
+            poses = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((1, N_JOINTS, 3)), dtype=np.float64)
+            scores = np.ascontiguousarray(np.concatenate(scs) if scs else np.zeros(1), dtype=np.float64)
+            n_people = np.ascontiguousarray(n_people, dtype=np.int32)
+            p_poses, p_scores, p_people = _ptr(poses), _ptr(scores), _ptr(n_people)
+        D = coco.MAX_DETS
+        count, order = np.empty(n, np.int32), np.empty((n, D), np.int32)
+        d_scores, d_areas = np.empty((n, D), np.float64), np.empty((n, D), np.float64)
+        dt_match, dt_ig = np.empty((n, 3, 10, D), np.int32), np.empty((n, 3, 10, D), np.uint8)
+        gt_ig = np.empty((max(total, 1), 3), np.uint8)
+        m_oks = np.empty(max(total, 1) * D, np.float64) if oks else None
+        self._check(self.lib.pmx_coco_eval(self._ctx, _ptr(images), n, _ptr(table), total, _ptr(consts), p_poses, p_scores, p_people,
+                                           _ptr(count), _ptr(order), _ptr(d_scores), _ptr(d_areas), _ptr(dt_match), _ptr(dt_ig), _ptr(gt_ig),
+                                           None if m_oks is None else _ptr(m_oks)))
+        out = []
+        for i in range(n):
+            d, off, G = int(count[i]), int(images[i, 0]), int(images[i, 1])
+            if d == 0 and G == 0:
+                out.append(None)
+                continue
+            e = {'order': order[i, :d].astype(np.int64), 'scores': d_scores[i, :d].copy(), 'areas': d_areas[i, :d].copy(),
+                 'dt_match': dt_match[i, :, :, :d].copy(), 'dt_ig': dt_ig[i, :, :, :d].astype(bool),
+                 'gt_ig': np.ascontiguousarray(gt_ig[off:off + G].T).astype(bool)}
+            if oks:
+                e['oks'] = m_oks[D * off:D * off + d * G].reshape(d, G).copy() if d and G else np.zeros((0, 0))
+            out.append(e)
         return out
 
     def set_maps(self, paf, heat):

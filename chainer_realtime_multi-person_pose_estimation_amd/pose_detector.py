@@ -925,6 +925,35 @@ class PoseDetector(object):
         parts = [coco.mask_parts(anns, h, w) for anns, (h, w) in zip(annotations_per_image, sizes)]
         return self.engine.coco_masks(sizes, parts, device=device)[0]
 
+    def evaluate_batch(self, imgs, annotations_per_image, precise=False):
+        """Detection and COCOeval's per-image step (coco.evaluate_image) for a list of images: `detect_batch` (precise: `detect_precise_batch`),
+        then the OKS matrices and the matching walks on the device, on the result records where the post-process left them -- no pose
+        visits the host on the way to its evaluation.  annotations_per_image: per image ALL its annotation dictionaries in file order
+        (or coco.ground_truths of them).  -> (results per image as coco.evaluate_image gives them, poses per image, scores per image); the
+        last two are what coco.results takes.  Images of one size run as one batch, a list of several sizes as one batch per size.  An image
+        with more than coco.EVAL_MAX_GT annotations is evaluated by the host contract."""
+        from . import coco
+        if self.model is not None:
+            raise RuntimeError('evaluate_batch runs on the built-in engine: not available with a model= callable')
+        imgs = [np.asarray(im) for im in imgs]
+        if len(imgs) == 0 or len(annotations_per_image) != len(imgs):
+            raise ValueError('evaluate_batch: %d images, annotations for %d' % (len(imgs), len(annotations_per_image)))
+        gts = [coco.ground_truths(a) for a in annotations_per_image]
+        none = coco.ground_truths([])
+        groups = {}
+        for i, im in enumerate(imgs):
+            groups.setdefault(tuple(im.shape), []).append(i)
+        ev, poses, scores = [None] * len(imgs), [None] * len(imgs), [None] * len(imgs)
+        for idx in groups.values():
+            sub = [imgs[i] for i in idx]
+            res = self.detect_precise_batch(sub) if precise else self.detect_batch(sub)
+            large = [len(gts[i]['area']) > coco.EVAL_MAX_GT for i in idx]
+            got = self.engine.coco_eval([none if big else gts[i] for i, big in zip(idx, large)])
+            for k, i in enumerate(idx):
+                poses[i], scores[i] = res[k]
+                ev[i] = coco.evaluate_image(coco.detections(*res[k]), gts[i]) if large[k] else got[k]
+        return ev, poses, scores
+
     def validation_loss_raw(self, imgs, poses_per_image, ignore_masks=None, insize=368):
         """`validation_loss` for raw validation data: images of any sizes, integer poses in each image's pixels, ignore masks at each
         image's size.  The resize to insize x insize, the mask's resize and 16 x 16 dilation, the label maps, the forward and the loss all

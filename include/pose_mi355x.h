@@ -568,6 +568,60 @@ int pmx_coco_masks(pmx_ctx* ctx, const pmx_mask_image* images, int n_images, con
 /* the columns one block of pmx_coco_masks owns for an image of height h (1 .. 16384, else 0): a launch-geometry fact for tests */
 int pmx_coco_masks_strip(int h);
 
+/* ---- COCO key-point evaluation: OKS and matching (csrc/pmx_eval.hip) ------------------------------------------------------------------
+ * evaluateImg + computeOks of COCOeval with iouType = 'keypoints', for a batch of images with any mix of detection and ground-truth
+ * counts in ONE launch, one block per image; the accumulation over images (precision / recall, AP / AR) stays on the host.  The contract
+ * is the package's own NumPy functions (coco.py: oks_matrix, evaluate_image): the tables are equal, the OKS values equal up to the exp
+ * of the two sides (about one ulp per term, at most 17 terms <= 1: below 1e-14 absolute).  It restates the published source of
+ * pycocotools; that library is no dependency and the restatement has NOT been compared with it.
+ *   Detections of an image: n people, each a score and 18 rows (x, y, v).  COCO key point i is row consts->joint[i]; it is (x, y) where
+ *   v != 0, else (0, 0).  They are ranked by descending score, equal scores in input order (argsort(-score, kind='mergesort')), and
+ *   cut to the first PMX_EVAL_MAX_DETS = 20: D = min(n, 20).  area = (max x - min x) * (max y - min y) over all 17 points, zeros
+ *   included (loadRes).
+ *   Ground truths of an image: G annotations in file order; ignore = iscrowd == 1 || num_keypoints == 0.
+ *   OKS of (detection d, ground truth g), fp64, every operation rounded on its own: k1 = count(vg > 0).  k1 > 0: dx = xd - xg,
+ *   dy = yd - yg.  Else, bb = bbox: x0 = bb[0] - bb[2], x1 = bb[0] + bb[2] * 2, y0 = bb[1] - bb[3], y1 = bb[1] + bb[3] * 2,
+ *   dx = max(0, x0 - xd) + max(0, xd - x1), dy alike.  e_i = (dx * dx + dy * dy) / vars[i] / (area_g + eps) / 2, left to right.
+ *   oks = (exp(-e_i) added in ascending i, over the i with vg > 0 if k1 > 0, else over all 17) / (number of terms).
+ *   Matching, independently for each area range a = 0 .. 2 ([lo, hi] = area_rngs[a]) and threshold t = 0 .. 9 (the 30 walks run side
+ *   by side): gt_ig[g] = ignore[g] || area_g < lo || area_g > hi; the ground truths are visited kept ones first, file order within
+ *   each group.  For each detection in rank order: iou = min(iou_thrs[t], 1 - 1e-10), m = -1; walk the ground truths: one already
+ *   matched in this walk that is not crowd (iscrowd != 1) is skipped; if m > -1 && !gt_ig[m] && gt_ig[g] the walk stops; if
+ *   oks[d][g] < iou it is skipped; else iou = oks[d][g], m = g (an equal later value replaces an earlier one).  With a match:
+ *   dt_match = m (file-order index), dt_ig = gt_ig[m], m is marked.  Afterwards dt_ig |= dt_match == -1 && (area_d < lo || area_d > hi).
+ * Inputs, all host memory, read before the call returns; they travel in ONE staging copy of at most PMX_EVAL_TABLE_BYTES:
+ *   images[n_images]: per image its range (gt0, n_gt) of gts[n_gts]; consts: the constant tables as the host computed them.
+ *   Detections, form 1 (poses != NULL): poses[sum n][18][3] and scores[sum n] end to end in image order, n_people[n_images].
+ *   Form 2 (poses == NULL; scores, n_people ignored): the first n_images result records of the last post-process are read WHERE THEY LIE
+ *   on the device -- the call finalises them as pmx_results_layout does (synchronises; grows and re-runs if an image overflowed);
+ *   PMX_ERR_STATE before any post-process and when n_images exceeds the records' batch.  detect -> evaluate moves no pose to the host.
+ * Outputs, host memory, each may be NULL but not all; one synchronisation behind the copies.  Unused slots hold -1 (det_order,
+ * dt_match) or 0:
+ *   det_count[n_images] = D; det_order[n_images][20]: index of the ranked detection among the image's people; det_scores, det_areas
+ *   [n_images][20]; dt_match int32 and dt_ig bytes [n_images][3][10][20]; gt_ig: per image n_gt x 3 bytes (row g, column a); oks:
+ *   per image 20 x n_gt doubles (row d, column g, rows from D on are 0); both with the images end to end: image k starts at 3 * s and
+ *   20 * s, s = the sum of n_gt of the images before it.
+ * PMX_EVAL_MAX_GT bounds the ground truths of ONE image: its working set lives in LDS (160 KB per block).  Per ground truth: 20 OKS
+ * doubles (160 bytes), its area (8), its place in the three visiting orders (3 x 2), gt_ig of the three ranges (3), the crowd flag (1) and
+ * the matched flags of the 30 walks (30): 208 bytes; per image 20 x 17 detection points, scores, areas, order: about 6 KB.  512 x 208 + 6 K =
+ * 110 KB fits, 768 x 208 + 6 K = 162 KB does not; 512 is the largest power of two.
+ * Works on a context of any architecture and needs no weights; maps, records, samples and retained state stay untouched; runs on the
+ * context's stream.  No atomics: two calls give the same bytes.
+ * Errors, before anything is enqueued (the context stays usable): PMX_ERR_INVALID for a null table or consts, n_images <= 0, all outputs
+ * NULL, a negative count, a range outside gts, form 1 without scores or n_people, a coordinate, area, box or score that is not finite,
+ * consts that are not finite or a joint outside 0 .. 17; PMX_ERR_CAPACITY for an image with more than PMX_EVAL_MAX_GT ground truths and for
+ * tables above the budget. */
+#define PMX_EVAL_MAX_GT 512
+#define PMX_EVAL_MAX_DETS 20
+#define PMX_EVAL_KEYPOINTS 17
+#define PMX_EVAL_TABLE_BYTES ((size_t)64 << 20)
+typedef struct pmx_eval_image { int32_t gt0, n_gt; } pmx_eval_image;
+typedef struct pmx_eval_gt { double keypoints[PMX_EVAL_KEYPOINTS][3]; double area; double bbox[4]; int32_t iscrowd, num_keypoints; } pmx_eval_gt;
+typedef struct pmx_eval_consts { double vars[PMX_EVAL_KEYPOINTS]; double iou_thrs[10]; double area_rngs[3][2]; double eps; int32_t joint[PMX_EVAL_KEYPOINTS]; int32_t reserved; } pmx_eval_consts;
+int pmx_coco_eval(pmx_ctx* ctx, const pmx_eval_image* images, int n_images, const pmx_eval_gt* gts, int n_gts, const pmx_eval_consts* consts,
+                  const double* poses, const double* scores, const int32_t* n_people, int32_t* det_count, int32_t* det_order,
+                  double* det_scores, double* det_areas, int32_t* dt_match, uint8_t* dt_ig, uint8_t* gt_ig, double* oks);
+
 /* results.  pmx_results_layout synchronises, grows the capacities and re-runs the post-process if an image overflowed them,
  * and returns the layout of the (now final) records; pmx_get_results does the same and copies `batch` records to `out`
  * (out_bytes >= batch * bytes_per_record, else PMX_ERR_CAPACITY). */
