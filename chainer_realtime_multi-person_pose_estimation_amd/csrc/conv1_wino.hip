@@ -379,7 +379,7 @@ int conv1_wino_launch(const ConvArgs& a0, hipStream_t stream)
     a.tiles_y = (a.H + 2 * TT - 1) / (2 * TT);
     a.ksplit = 1;
     if (!a.g[1].in) a.kbounds = 0;
-    static bool attr_set[PMX_MAX_DEVICES] = {};
+    static std::atomic<bool> attr_set[PMX_MAX_DEVICES] = {};
     if (int rc = conv_allow_big_lds(reinterpret_cast<const void*>(conv1_wino_kernel), attr_set)) return rc;
     PMX_CHECK(a.nseg == 0 || (a.segs && a.seg_tiles > 0), PMX_ERR_INVALID, "conv1 winograd: segments without a table");
     hipLaunchKernelGGL(conv1_wino_kernel, dim3(a.nseg ? (unsigned)a.seg_tiles : (unsigned)(a.tiles_x * a.tiles_y * a.B)), dim3(256), LDS_BYTES, stream, a);

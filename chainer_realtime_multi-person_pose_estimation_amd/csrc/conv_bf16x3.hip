@@ -470,7 +470,7 @@ static int launch_v7(const ConvArgs& a0, int groups, hipStream_t stream)
     a.tiles_x = (a.H * C::W + C::M - 1) / C::M;
     a.tiles_y = a.W / C::W;
     auto kern = conv_bf16x3_kernel<KS, MT, POOL>;
-    static bool attr_set[PMX_MAX_DEVICES] = {};
+    static std::atomic<bool> attr_set[PMX_MAX_DEVICES] = {};
     if (int rc = conv_allow_big_lds(reinterpret_cast<const void*>(kern), attr_set)) return rc;
     dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.B), (unsigned)(a.cout_pad / 128), (unsigned)groups);
     hipLaunchKernelGGL(kern, grid, dim3(256), C::LDS_BYTES, stream, a);
@@ -479,7 +479,7 @@ static int launch_v7(const ConvArgs& a0, int groups, hipStream_t stream)
 }
 
 template <int KS>
-static int launch_v8(const ConvArgs& a0, int groups, hipStream_t stream)
+static int launch_v8(const ConvArgs& a0, int groups, int v5_lds, hipStream_t stream)
 {
     using C = ConvCfg<KS, 8, 8, 64, 16, 2, 2>;
     ConvArgs a = a0;
@@ -493,8 +493,8 @@ static int launch_v8(const ConvArgs& a0, int groups, hipStream_t stream)
     PMX_CHECK(a.ksplit <= a.nch && a.ksplit <= 8, PMX_ERR_INVALID, "conv: %d K slices for %d chunks", a.ksplit, a.nch);
     auto kern = conv_bf16x3_small_kernel<KS>;
     int lds = 2 * C::HALO_H * C::HALO_W * 112;
-    if (lds < conv_v5_lds()) lds = conv_v5_lds();         // at most two blocks per CU, as for the v5 kernels
-    static bool attr_set[PMX_MAX_DEVICES] = {};
+    if (lds < v5_lds) lds = v5_lds;         // at most two blocks per CU, as for the v5 kernels
+    static std::atomic<bool> attr_set[PMX_MAX_DEVICES] = {};
     if (int rc = conv_allow_big_lds(reinterpret_cast<const void*>(kern), attr_set)) return rc;
     dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.B), (unsigned)(a.cout_pad / 64), (unsigned)(groups * a.ksplit));
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, a);
@@ -503,9 +503,9 @@ static int launch_v8(const ConvArgs& a0, int groups, hipStream_t stream)
 }
 
 // which = the kernel's block geometry: mt = 17 / 9 (v7: the v6 geometry, one block per CU) or 0 (v8: the small v5 tiles, split-K capable)
-int conv_bf16x3_launch(int ks, int mt, int pool, const ConvArgs& a, int groups, hipStream_t stream)
+int conv_bf16x3_launch(int ks, int mt, int pool, const ConvArgs& a, int groups, int v5_lds, hipStream_t stream)
 {
-    if (mt == 0) return ks == 7 ? launch_v8<7>(a, groups, stream) : launch_v8<3>(a, groups, stream);
+    if (mt == 0) return ks == 7 ? launch_v8<7>(a, groups, v5_lds, stream) : launch_v8<3>(a, groups, v5_lds, stream);
     if (mt == 17) {
         if (ks == 7) return launch_v7<7, 17, 0>(a, groups, stream);
         return pool ? launch_v7<3, 17, 1>(a, groups, stream) : launch_v7<3, 17, 0>(a, groups, stream);

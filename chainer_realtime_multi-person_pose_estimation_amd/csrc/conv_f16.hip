@@ -216,14 +216,14 @@ long long conv_f16_tiles(const ConvArgs& a)
 
 // blocks of 128 channels where the launch fills the chip with them, else 64 (the per-output K order is the same either way).  f16_bn: the
 // context's option "f16_bn" -- 0 = that rule, 64 | 128 = that width instead of the rule's answer (128 only where the layer has blocks of 128)
-int conv_f16_bn(const ConvArgs& a, int groups, int f16_bn)
+int conv_f16_bn(const ConvArgs& a, int groups, int f16_bn, int ncu)
 {
     if (a.cout_pad % 128) return 64;
     if (f16_bn) return f16_bn;
-    return conv_f16_tiles(a) * (a.cout_pad / 128) * groups >= conv_num_cus() ? 128 : 64;
+    return conv_f16_tiles(a) * (a.cout_pad / 128) * groups >= ncu ? 128 : 64;
 }
 
-int conv_f16_launch(int ks, const ConvArgs& a, int groups, int f16_bn, hipStream_t stream)
+int conv_f16_launch(int ks, const ConvArgs& a, int groups, int f16_bn, int ncu, hipStream_t stream)
 {
     PMX_CHECK(ks == 3 || ks == 7, PMX_ERR_INVALID, "conv f16: kernel size %d (3 or 7)", ks);
     PMX_CHECK(groups == 1 || groups == 2, PMX_ERR_INVALID, "conv f16: %d groups", groups);
@@ -234,7 +234,7 @@ int conv_f16_launch(int ks, const ConvArgs& a, int groups, int f16_bn, hipStream
     PMX_CHECK((long long)a.H * a.W * a.lda < (1ll << 31) && (long long)a.H * a.W * a.ldc < (1ll << 31), PMX_ERR_INVALID,
               "conv f16: image too large for 32-bit offsets");
     PMX_CHECK(f16_bn == 0 || f16_bn == 64 || f16_bn == 128, PMX_ERR_INVALID, "conv f16: block width %d (0, 64 or 128)", f16_bn);
-    const int bn = conv_f16_bn(a, groups, f16_bn);
+    const int bn = conv_f16_bn(a, groups, f16_bn, ncu);
     if (ks == 7) return bn == 128 ? launch_f16<7, 128>(a, groups, stream) : launch_f16<7, 64>(a, groups, stream);
     return bn == 128 ? launch_f16<3, 128>(a, groups, stream) : launch_f16<3, 64>(a, groups, stream);
 }

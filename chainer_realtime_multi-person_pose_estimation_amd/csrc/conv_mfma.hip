@@ -30,7 +30,6 @@
 //   grid             x = tiles * batch, y = cout_pad / BN, z = group (the PAF and heat-map branches of a stage
 //                    run as the two groups of one launch).
 #include <hip/hip_ext.h>
-#include <atomic>
 #include <mutex>
 #include <type_traits>
 #include "pmx_common.h"
@@ -906,29 +905,18 @@ static int launch_c3(const ConvArgs& a0, int groups, hipStream_t stream)
 }
 
 // dynamic LDS above 64 KB must be allowed per kernel AND per device (a process may hold contexts on several GPUs)
-// (`done` is a plain flag per kernel and device: two host threads racing here both call hipFuncSetAttribute with the same value -- idempotent)
-int conv_allow_big_lds(const void* kern, bool (&done)[PMX_MAX_DEVICES])
+// (relaxed is enough: the flag orders nothing, two threads that both see it clear both set the same attribute to the same value)
+int conv_allow_big_lds(const void* kern, std::atomic<bool> (&done)[PMX_MAX_DEVICES])
 {
     int dev = 0;
     PMX_HIP(hipGetDevice(&dev));
     PMX_CHECK(dev >= 0 && dev < PMX_MAX_DEVICES, PMX_ERR_INVALID, "device index %d out of range", dev);
-    if (!done[dev]) {
+    if (!done[dev].load(std::memory_order_relaxed)) {
         PMX_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        done[dev] = true;
+        done[dev].store(true, std::memory_order_relaxed);
     }
     return PMX_OK;
 }
-
-// minimum dynamic LDS per block: caps the number of co-resident blocks per CU (the fp32 MFMA pipe
-// loses ~20% with 3+ waves per SIMD)
-// process-wide switches, set through any context (pmx_set_option): relaxed atomics, as g_num_cus below -- a set_option in one thread and a
-// launch in another read or write a whole int
-static std::atomic<int> g_min_lds{0};
-void conv_set_min_lds(int bytes) { g_min_lds.store(bytes, std::memory_order_relaxed); }
-static int conv_min_lds() { return g_min_lds.load(std::memory_order_relaxed); }
-static std::atomic<int> g_v5_lds{56 * 1024};    // dynamic LDS floor of the v5 kernels: 3 x 56 KB > 160 KB -> at most 2 blocks per CU
-void conv_set_v5_lds(int bytes) { g_v5_lds.store(bytes, std::memory_order_relaxed); }
-int conv_v5_lds() { return g_v5_lds.load(std::memory_order_relaxed); }
 
 // ---- variant table ---------------------------------------------------------------------------------------
 // {ksize, tile rows (v6: row tiles per block), tile cols (v6: 32), BN, CK, name}
@@ -995,14 +983,10 @@ int conv_bf16x3_twin(int v)
 int conv_num_variants() { return (int)(sizeof(g_variants) / sizeof(g_variants[0])); }
 const ConvVariant& conv_variant(int idx) { return g_variants[idx]; }
 
-static std::atomic<int> g_num_cus{256};       // process-wide (contexts on different devices of one process are expected to be the same part)
-void conv_set_num_cus(int n) { if (n > 0) g_num_cus.store(n, std::memory_order_relaxed); }
-int conv_num_cus() { return g_num_cus.load(std::memory_order_relaxed); }
-
 // gen: 1 = v1 kernels everywhere, 5 = v5 for 3x3 / 7x7, 6 (default) = v6 / c3 where they apply, else v5
-int conv_pick_variant(int ks, int cout, int H, int W, int B, int forced, int gen, int pool, int cin, int bf16x3)
+// ncu: compute units of the device (256 on an MI355X in SPX mode)
+int conv_pick_variant(int ks, int cout, int H, int W, int B, int forced, int gen, int pool, int cin, int bf16x3, int ncu)
 {
-    const int ncu = g_num_cus;      // compute units of the device (256 on an MI355X in SPX mode)
     // `cout` is the padded channel count of the layer
     const bool forced_v6 = (forced >= V6_K7 && forced <= V6_K3_POOL) || (forced >= V6M9_K7 && forced <= V6M9_K3_POOL);
     if (forced >= V7_K7) forced = -1;       // the bf16x3 kernels are chosen through their v6 twins (they need the bf16x3 weight pack)
@@ -1108,7 +1092,7 @@ static void sk_partitions(int n, int parts, int maxpart, int* cur, int depth, st
     }
 }
 
-SplitPlan conv_pick_ksplit(int variant, int H, int W, int B, int groups, int cout_pad, int nch, int pool, int forced)
+SplitPlan conv_pick_ksplit(int variant, int H, int W, int B, int groups, int cout_pad, int nch, int pool, int forced, int ncu)
 {
     (void)pool;
     SplitPlan none;
@@ -1141,7 +1125,6 @@ SplitPlan conv_pick_ksplit(int variant, int H, int W, int B, int groups, int cou
     }
     const ConvVariant& v = g_variants[variant];
     const long nblk = (long)((H + v.th - 1) / v.th) * ((W + v.tw - 1) / v.tw) * B * (cout_pad / v.bn) * groups;
-    const int ncu = g_num_cus;
     if (nblk >= 8 * ncu) return none;
     // measured plans (tools/splitk_tune.py, in-network HIP-event times on an MI355X, profiles/r02_splitk_tune.txt) for the
     // launch shapes of 368 x 368 inputs at batch 1-6; {ksize, chunks, blocks before the split, slices...}.  How the
@@ -1210,7 +1193,7 @@ SplitPlan conv_pick_ksplit(int variant, int H, int W, int B, int groups, int cou
 }
 
 template <int KS, int TH, int TW, int BN, int CK, int WM, int WN>
-static int launch_cfg(const ConvArgs& a0, int groups, hipStream_t stream)
+static int launch_cfg(const ConvArgs& a0, int groups, int min_lds, hipStream_t stream)
 {
     using C = ConvCfg<KS, TH, TW, BN, CK, WM, WN>;
     ConvArgs a = a0;
@@ -1219,9 +1202,8 @@ static int launch_cfg(const ConvArgs& a0, int groups, hipStream_t stream)
     PMX_CHECK(a.cout_pad % BN == 0, PMX_ERR_INVALID, "conv: cout_pad %d not a multiple of BN %d", a.cout_pad, BN);
     PMX_CHECK(!a.pool || (a.H % 2 == 0 && a.W % 2 == 0), PMX_ERR_INVALID, "conv: pooled layer needs even H, W");
     auto kern = conv_mfma_kernel<KS, TH, TW, BN, CK, WM, WN>;
-    static bool attr_set[PMX_MAX_DEVICES] = {};
+    static std::atomic<bool> attr_set[PMX_MAX_DEVICES] = {};
     if (int rc = conv_allow_big_lds(reinterpret_cast<const void*>(kern), attr_set)) return rc;
-    const int min_lds = conv_min_lds();
     const int lds = C::LDS_BYTES > min_lds ? C::LDS_BYTES : min_lds;
     dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.B), (unsigned)(a.cout_pad / BN), (unsigned)groups);
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, a);
@@ -1230,7 +1212,7 @@ static int launch_cfg(const ConvArgs& a0, int groups, hipStream_t stream)
 }
 
 template <int KS, int TH, int TW, int BN, int CK, int WM, int WN>
-static int launch_v5(const ConvArgs& a0, int groups, hipStream_t stream)
+static int launch_v5(const ConvArgs& a0, int groups, int min_lds, int v5_lds, hipStream_t stream)
 {
     using C = ConvCfg<KS, TH, TW, BN, CK, WM, WN>;
     ConvArgs a = a0;
@@ -1241,10 +1223,9 @@ static int launch_v5(const ConvArgs& a0, int groups, hipStream_t stream)
     PMX_CHECK((long long)a.H * a.W * a.lda < (1ll << 31), PMX_ERR_INVALID, "conv: image too large for 32-bit offsets");
     auto kern = conv_mfma_v5_kernel<KS, TH, TW, BN, CK, WM, WN>;
     int lds = 2 * C::IN_ELEMS * 4;
-    const int v5_lds = conv_v5_lds(), min_lds = conv_min_lds();
     if (lds < v5_lds) lds = v5_lds;
     if (lds < min_lds) lds = min_lds;
-    static bool attr_set[PMX_MAX_DEVICES] = {};
+    static std::atomic<bool> attr_set[PMX_MAX_DEVICES] = {};
     if (int rc = conv_allow_big_lds(reinterpret_cast<const void*>(kern), attr_set)) return rc;
     if (a.ksplit < 1) a.ksplit = 1;
     a.ngroups = groups;
@@ -1440,7 +1421,7 @@ static int launch_pair(const PairArgs& a, int groups, hipStream_t stream)
 {
     constexpr int LDS = 32 * ((CMID > 128 ? CMID : 128) + 4) * 4;       // X tile and hidden tile share the space
     auto kern = conv1x1_pair_kernel<CMID, N2T>;
-    static bool attr_set[PMX_MAX_DEVICES] = {};
+    static std::atomic<bool> attr_set[PMX_MAX_DEVICES] = {};
     if (int rc = conv_allow_big_lds(reinterpret_cast<const void*>(kern), attr_set)) return rc;
     const long long nblk = (a.npix + 31) / 32;
     PMX_CHECK(nblk < (1ll << 31), PMX_ERR_INVALID, "conv pair: too many pixels");
@@ -1470,7 +1451,7 @@ static int launch_v6(const ConvArgs& a0, int groups, hipStream_t stream)
     a.tiles_x = (a.H * C::W + C::M - 1) / C::M;       // blocks per slab
     a.tiles_y = a.W / C::W;                            // slabs per image
     auto kern = conv_mfma_v6_kernel<KS, MT, POOL>;
-    static bool attr_set[PMX_MAX_DEVICES] = {};
+    static std::atomic<bool> attr_set[PMX_MAX_DEVICES] = {};
     if (int rc = conv_allow_big_lds(reinterpret_cast<const void*>(kern), attr_set)) return rc;
     dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.B), (unsigned)(a.cout_pad / 128), (unsigned)groups);
     hipLaunchKernelGGL(kern, grid, dim3(256), C::LDS_BYTES, stream, a);
@@ -1478,7 +1459,7 @@ static int launch_v6(const ConvArgs& a0, int groups, hipStream_t stream)
     return PMX_OK;
 }
 
-int conv_launch(int variant, const ConvArgs& a, int groups, hipStream_t stream)
+int conv_launch(int variant, const ConvArgs& a, int groups, int min_lds, int v5_lds, hipStream_t stream)
 {
     switch (variant) {
         case V8_K7_SMALL: case V8_K3_SMALL: case V7_K7: case V7_K3: case V7_K3_POOL: case V7M9_K7: case V7M9_K3: case V7M9_K3_POOL: {
@@ -1486,25 +1467,25 @@ int conv_launch(int variant, const ConvArgs& a, int groups, hipStream_t stream)
             PMX_CHECK(conv_bf16x3_launch != nullptr, PMX_ERR_INVALID, "conv_launch: this build carries no bf16x3 kernels (PMX_BUILD_BF16X3=1)");
             const int ks = conv_variant(variant).ks;
             const int mt = (variant == V8_K7_SMALL || variant == V8_K3_SMALL) ? 0 : (variant >= V7M9_K7 ? 9 : 17);
-            return conv_bf16x3_launch(ks, mt, variant == V7_K3_POOL || variant == V7M9_K3_POOL, a, groups, stream);
+            return conv_bf16x3_launch(ks, mt, variant == V7_K3_POOL || variant == V7M9_K3_POOL, a, groups, v5_lds, stream);
         }
-        case 0: return launch_cfg<7, 8, 16, 128, 16, 2, 2>(a, groups, stream);
-        case 1: return launch_cfg<3, 8, 16, 128, 16, 2, 2>(a, groups, stream);
-        case 2: return launch_cfg<3, 8, 16, 64, 16, 4, 1>(a, groups, stream);
-        case 3: return launch_cfg<1, 8, 16, 128, 16, 2, 2>(a, groups, stream);
-        case 4: return launch_cfg<1, 8, 16, 64, 16, 4, 1>(a, groups, stream);
-        case 5: return launch_cfg<7, 8, 8, 64, 16, 2, 2>(a, groups, stream);
-        case 6: return launch_cfg<3, 8, 8, 64, 16, 2, 2>(a, groups, stream);
-        case 7: return launch_cfg<1, 8, 8, 64, 16, 2, 2>(a, groups, stream);
-        case 8: return launch_cfg<7, 2, 46, 128, 16, 1, 4>(a, groups, stream);
-        case 9: return launch_cfg<3, 2, 46, 128, 16, 1, 4>(a, groups, stream);
-        case V5_K7_STRIP: return launch_v5<7, 2, 46, 128, 16, 1, 4>(a, groups, stream);
-        case V5_K3_STRIP: return launch_v5<3, 2, 46, 128, 16, 1, 4>(a, groups, stream);
-        case V5_K7: return launch_v5<7, 8, 16, 128, 16, 1, 4>(a, groups, stream);
-        case V5_K3: return launch_v5<3, 8, 16, 128, 16, 1, 4>(a, groups, stream);
-        case V5_K3_N64: return launch_v5<3, 8, 16, 64, 16, 2, 2>(a, groups, stream);
-        case V5_K7_SMALL: return launch_v5<7, 8, 8, 64, 16, 2, 2>(a, groups, stream);
-        case V5_K3_SMALL: return launch_v5<3, 8, 8, 64, 16, 2, 2>(a, groups, stream);
+        case 0: return launch_cfg<7, 8, 16, 128, 16, 2, 2>(a, groups, min_lds, stream);
+        case 1: return launch_cfg<3, 8, 16, 128, 16, 2, 2>(a, groups, min_lds, stream);
+        case 2: return launch_cfg<3, 8, 16, 64, 16, 4, 1>(a, groups, min_lds, stream);
+        case 3: return launch_cfg<1, 8, 16, 128, 16, 2, 2>(a, groups, min_lds, stream);
+        case 4: return launch_cfg<1, 8, 16, 64, 16, 4, 1>(a, groups, min_lds, stream);
+        case 5: return launch_cfg<7, 8, 8, 64, 16, 2, 2>(a, groups, min_lds, stream);
+        case 6: return launch_cfg<3, 8, 8, 64, 16, 2, 2>(a, groups, min_lds, stream);
+        case 7: return launch_cfg<1, 8, 8, 64, 16, 2, 2>(a, groups, min_lds, stream);
+        case 8: return launch_cfg<7, 2, 46, 128, 16, 1, 4>(a, groups, min_lds, stream);
+        case 9: return launch_cfg<3, 2, 46, 128, 16, 1, 4>(a, groups, min_lds, stream);
+        case V5_K7_STRIP: return launch_v5<7, 2, 46, 128, 16, 1, 4>(a, groups, min_lds, v5_lds, stream);
+        case V5_K3_STRIP: return launch_v5<3, 2, 46, 128, 16, 1, 4>(a, groups, min_lds, v5_lds, stream);
+        case V5_K7: return launch_v5<7, 8, 16, 128, 16, 1, 4>(a, groups, min_lds, v5_lds, stream);
+        case V5_K3: return launch_v5<3, 8, 16, 128, 16, 1, 4>(a, groups, min_lds, v5_lds, stream);
+        case V5_K3_N64: return launch_v5<3, 8, 16, 64, 16, 2, 2>(a, groups, min_lds, v5_lds, stream);
+        case V5_K7_SMALL: return launch_v5<7, 8, 8, 64, 16, 2, 2>(a, groups, min_lds, v5_lds, stream);
+        case V5_K3_SMALL: return launch_v5<3, 8, 8, 64, 16, 2, 2>(a, groups, min_lds, v5_lds, stream);
         case V6_K7: return launch_v6<7, 17, 0>(a, groups, stream);
         case V6_K3: return launch_v6<3, 17, 0>(a, groups, stream);
         case V6_K3_POOL: return launch_v6<3, 17, 1>(a, groups, stream);
@@ -1512,9 +1493,9 @@ int conv_launch(int variant, const ConvArgs& a, int groups, hipStream_t stream)
         case V6M9_K7: return launch_v6<7, 9, 0>(a, groups, stream);
         case V6M9_K3: return launch_v6<3, 9, 0>(a, groups, stream);
         case V6M9_K3_POOL: return launch_v6<3, 9, 1>(a, groups, stream);
-        case V5T_K7: return launch_v5<7, 16, 8, 128, 16, 1, 4>(a, groups, stream);
-        case V5T_K3: return launch_v5<3, 16, 8, 128, 16, 1, 4>(a, groups, stream);
-        case V5T_K3_N64: return launch_v5<3, 16, 8, 64, 16, 2, 2>(a, groups, stream);
+        case V5T_K7: return launch_v5<7, 16, 8, 128, 16, 1, 4>(a, groups, min_lds, v5_lds, stream);
+        case V5T_K3: return launch_v5<3, 16, 8, 128, 16, 1, 4>(a, groups, min_lds, v5_lds, stream);
+        case V5T_K3_N64: return launch_v5<3, 16, 8, 64, 16, 2, 2>(a, groups, min_lds, v5_lds, stream);
     }
     pmx_set_error("conv_launch: unknown variant %d", variant);
     return PMX_ERR_INVALID;

@@ -89,7 +89,7 @@ int wino_select(const WinoSelectOpts& o, int ks, int cin_pad, int cout_pad, int 
     *unit_g = 0; *run = 0; *tail_g = 0;
     if (o.conv_algo < 1 || o.precision != 0 || o.forced_variant >= 0 || !wino_eligible(ks, cin_pad, cout_pad)) return 0;
     const int nch = cin_pad / 32, extra = ks == 7 ? 3 : 0;     // 7x7: + row 6, column 6, tap (6, 6)
-    const long long ncu = conv_num_cus(), nb = cout_pad / 128;
+    const long long ncu = o.ncu, nb = cout_pad / 128;
     int g = 0, S = 0;        // the plan with as many units as 8 slabs allow (tails under conv_algo 2; whole launches with wino_unit_g = -1)
     int gu = 0;              // the plan of a whole launch in unit mode (single images, small batches)
     if (o.ksplit == 0 && cout % 4 == 0 && ldc % 4 == 0 && nch >= 2) {
@@ -169,7 +169,7 @@ int wino_split_images(const WinoSelectOpts& o, int ks, int cin_pad, int cout_pad
     int ug = 0, run = 0, tg = 0;
     if (wino_select(o, ks, cin_pad, cout_pad, cout, ldc, B * groups, H, W, pool, &ug, &run, &tg) != 1) return 0;
     const int nch = cin_pad / 32;
-    const long long ncu = conv_num_cus(), nb = cout_pad / 128;
+    const long long ncu = o.ncu, nb = cout_pad / 128;
     const long long rects = (long long)((H + 7) / 8) * ((W + 15) / 16);
     long long bpi;                   // blocks of the main launch per image (all groups)
     if (run) {

@@ -837,10 +837,10 @@ static int launch_wino(const ConvArgs& a0, int groups, hipStream_t stream)
     a.tiles_y = (a.H + C::TH - 1) / C::TH;
     a.run_j0 = a.run_nb = 0;
     auto kern = conv_wino_kernel<KS, POOL, UNIT, 0>;
-    static bool attr_set[PMX_MAX_DEVICES] = {};
+    static std::atomic<bool> attr_set[PMX_MAX_DEVICES] = {};
     if (int rc = conv_allow_big_lds(reinterpret_cast<const void*>(kern), attr_set)) return rc;
     if (UNIT) { a.ngroups = groups; PMX_CHECK(a.ksplit >= 2 && a.ksplit <= 8 && a.kbounds >= 1, PMX_ERR_INVALID, "conv wino: bad unit plan"); }
-    // heterogeneous launch: the caller built the segment table (conv_build_segs: sizes checked there) and says how many tiles it holds
+    // heterogeneous launch: the caller built the segment table (build_seg_tables: sizes checked there) and says how many tiles it holds
     PMX_CHECK(a.nseg == 0 || (!UNIT && a.segs && a.seg_tiles > 0), PMX_ERR_INVALID, "conv wino: segments only in plain mode, with a table");
     const unsigned gx = a.nseg ? (unsigned)a.seg_tiles : (unsigned)(a.tiles_x * a.tiles_y * a.B);
     dim3 grid(gx, (unsigned)(a.cout_pad / 128), (unsigned)(groups * (UNIT ? a.ksplit : 1)));
@@ -859,14 +859,11 @@ int conv_wino_launch(const ConvArgs& a, int ks, int groups, hipStream_t stream)
 }
 
 // run geometry (46-pixel-wide maps): the blocks [a.run_j0, a.run_j0 + a.run_nb) of every image, 32 consecutive Winograd tiles each
-// Events for the NEXT run-geometry launch of this thread (profile mode 2): handed to hipExtLaunchKernelGGL, which stamps them from the
-// dispatch's own completion signal -- the kernel's execution time without the two barrier packets of hipEventRecord (~6 us of idle stream
-// per pair, 25 pairs per step inside bench.py's timed region)
-static thread_local hipEvent_t g_launch_ev0 = nullptr, g_launch_ev1 = nullptr;
-void conv_set_launch_events(hipEvent_t e0, hipEvent_t e1) { g_launch_ev0 = e0; g_launch_ev1 = e1; }
-
+// e0 / e1 (profile mode 2; null: none): handed to hipExtLaunchKernelGGL, which stamps them from the dispatch's own completion signal --
+// the kernel's execution time without the two barrier packets of hipEventRecord (~6 us of idle stream per pair, 25 pairs per step
+// inside bench.py's timed region)
 template <int KS, int POOL, int UNIT, int GEOM>
-static int launch_wino_run_g(const ConvArgs& a0, int groups, hipStream_t stream)
+static int launch_wino_run_g(const ConvArgs& a0, int groups, hipStream_t stream, hipEvent_t e0, hipEvent_t e1)
 {
     using C = WinoCfg<KS, GEOM>;
     ConvArgs a = a0;
@@ -881,23 +878,22 @@ static int launch_wino_run_g(const ConvArgs& a0, int groups, hipStream_t stream)
     a.tiles_x = a.tiles_y = 0;
     PMX_CHECK(GEOM == 2 || a.run_nslab == 1, PMX_ERR_INVALID, "conv wino runs: single-slab kernel on a %d-wide map", a.W);
     auto kern = conv_wino_kernel<KS, POOL, UNIT, GEOM>;
-    static bool attr_set[PMX_MAX_DEVICES] = {};
+    static std::atomic<bool> attr_set[PMX_MAX_DEVICES] = {};
     if (int rc = conv_allow_big_lds(reinterpret_cast<const void*>(kern), attr_set)) return rc;
     if (UNIT) { a.ngroups = groups; PMX_CHECK(a.ksplit >= 2 && a.ksplit <= 8 && a.kbounds >= 1, PMX_ERR_INVALID, "conv wino: bad unit plan"); }
     dim3 grid((unsigned)(a.run_nb * a.B * a.run_nslab), (unsigned)(a.cout_pad / 128), (unsigned)(groups * (UNIT ? a.ksplit : 1)));
-    if (g_launch_ev0) {
-        hipExtLaunchKernelGGL(kern, grid, dim3(256), C::LDS_BYTES, stream, g_launch_ev0, g_launch_ev1, 0, a);
-        g_launch_ev0 = g_launch_ev1 = nullptr;
-    } else
+    if (e0)
+        hipExtLaunchKernelGGL(kern, grid, dim3(256), C::LDS_BYTES, stream, e0, e1, 0, a);
+    else
         hipLaunchKernelGGL(kern, grid, dim3(256), C::LDS_BYTES, stream, a);
     PMX_HIP(hipGetLastError());
     return PMX_OK;
 }
 
 template <int KS, int POOL, int UNIT>
-static int launch_wino_run(const ConvArgs& a, int groups, hipStream_t stream)
+static int launch_wino_run(const ConvArgs& a, int groups, hipStream_t stream, hipEvent_t e0, hipEvent_t e1)
 {
-    return a.W == 2 * PMX_WINO_RUN_TX ? launch_wino_run_g<KS, POOL, UNIT, 1>(a, groups, stream) : launch_wino_run_g<KS, POOL, UNIT, 2>(a, groups, stream);
+    return a.W == 2 * PMX_WINO_RUN_TX ? launch_wino_run_g<KS, POOL, UNIT, 1>(a, groups, stream, e0, e1) : launch_wino_run_g<KS, POOL, UNIT, 2>(a, groups, stream, e0, e1);
 }
 
 template <int KS>
@@ -912,7 +908,7 @@ static int launch_wino_merged(const ConvArgs& a0, int groups, hipStream_t stream
     PMX_CHECK(a.ksplit >= 2 && a.ksplit <= 8 && a.kbounds >= 1, PMX_ERR_INVALID, "conv wino: bad unit plan");
     a.run_nslab = 1; a.run_nb = wino_tail_merged_blocks(a.B, a.H); a.tiles_x = a.tiles_y = 0; a.ngroups = groups;
     auto kern = conv_wino_kernel<KS, 0, 1, 3>;
-    static bool attr_set[PMX_MAX_DEVICES] = {};
+    static std::atomic<bool> attr_set[PMX_MAX_DEVICES] = {};
     if (int rc = conv_allow_big_lds(reinterpret_cast<const void*>(kern), attr_set)) return rc;
     dim3 grid((unsigned)a.run_nb, (unsigned)(a.cout_pad / 128), (unsigned)(groups * a.ksplit));
     hipLaunchKernelGGL(kern, grid, dim3(256), C::LDS_BYTES, stream, a);
@@ -925,11 +921,11 @@ int conv_wino_merged_tail_launch(const ConvArgs& a, int ks, int groups, hipStrea
     return ks == 7 ? launch_wino_merged<7>(a, groups, stream) : launch_wino_merged<3>(a, groups, stream);
 }
 
-int conv_wino_run_launch(const ConvArgs& a, int ks, int groups, hipStream_t stream)
+int conv_wino_run_launch(const ConvArgs& a, int ks, int groups, hipStream_t stream, hipEvent_t e0, hipEvent_t e1)
 {
-    if (a.ksplit > 1) return ks == 7 ? launch_wino_run<7, 0, 1>(a, groups, stream) : launch_wino_run<3, 0, 1>(a, groups, stream);      // (the combine pools)
-    if (ks == 7) return launch_wino_run<7, 0, 0>(a, groups, stream);
-    return a.pool ? launch_wino_run<3, 1, 0>(a, groups, stream) : launch_wino_run<3, 0, 0>(a, groups, stream);
+    if (a.ksplit > 1) return ks == 7 ? launch_wino_run<7, 0, 1>(a, groups, stream, e0, e1) : launch_wino_run<3, 0, 1>(a, groups, stream, e0, e1);      // (the combine pools)
+    if (ks == 7) return launch_wino_run<7, 0, 0>(a, groups, stream, e0, e1);
+    return a.pool ? launch_wino_run<3, 1, 0>(a, groups, stream, e0, e1) : launch_wino_run<3, 0, 0>(a, groups, stream, e0, e1);
 }
 
 // ---- combine of the unit-mode slabs of a block range of the run geometry (see WinoTailReduceArgs) -------------------------------------------

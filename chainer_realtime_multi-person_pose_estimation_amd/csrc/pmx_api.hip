@@ -237,10 +237,10 @@ extern "C" int pmx_create_net(pmx_ctx** out, const char* arch, int device, int m
         pmx_set_error("pmx_create: device %d is %s; this library is built for gfx950 (MI355X) only", device, prop.gcnArchName);
         return PMX_ERR_NO_DEVICE;
     }
-    conv_set_num_cus(prop.multiProcessorCount);      // kernel / tile selection counts blocks against the CUs of this device
     PMX_HIP(hipSetDevice(device));
     pmx_ctx* c = new pmx_ctx();
     c->device = device;
+    c->num_cus = prop.multiProcessorCount;      // kernel / tile selection counts blocks against the CUs of this device
     c->max_batch = max_batch; c->max_h = max_h; c->max_w = max_w;
     c->kind = kind;
     c->n_heat = net_out_channels(kind);
@@ -338,7 +338,7 @@ extern "C" int pmx_set_option(pmx_ctx* c, const char* key, int value)
     else if (!strcmp(key, "precise_plain")) c->opt_precise_plain = value;
     else if (!strcmp(key, "precise_lane_priority")) c->opt_precise_lane_priority = value != 0;
     else if (!strcmp(key, "precise_table_cap")) c->opt_precise_table_cap = value < 1 ? 1 : value;
-    else if (!strcmp(key, "cubic_rows")) prep_set_cubic_rows(value);      // (process-wide, like the other kernel-form switches of prep / post-process)
+    else if (!strcmp(key, "cubic_rows")) c->opt_cubic_rows = value;
     else if (!strcmp(key, "precision")) {
         PMX_CHECK(value >= 0 && value <= 2, PMX_ERR_INVALID,
                   "pmx_set_option: \"precision\" = %d: 0 (fp32), 1 (bf16x3, opt-in build) or 2 (f16 mode)", value);
@@ -362,9 +362,9 @@ extern "C" int pmx_set_option(pmx_ctx* c, const char* key, int value)
     else if (!strcmp(key, "wino_tail_merge")) c->opt_wino_tail_merge = value;
     else if (!strcmp(key, "ksplit")) c->opt_ksplit = value;
     else if (!strcmp(key, "ksplit_plan")) c->opt_ksplit = value > 0 ? -value : 0;     // decimal digits = chunks per slice, e.g. 3221
-    else if (!strcmp(key, "conv_min_lds")) conv_set_min_lds(value);
-    else if (!strcmp(key, "conv_v5_lds")) conv_set_v5_lds(value);
-    else if (!strcmp(key, "pp_generic")) pp_set_generic(value);
+    else if (!strcmp(key, "conv_min_lds")) c->opt_conv_min_lds = value;
+    else if (!strcmp(key, "conv_v5_lds")) c->opt_conv_v5_lds = value;
+    else if (!strcmp(key, "pp_generic")) c->opt_pp_generic = value;
     else if (!strcmp(key, "pp_limbs_slices")) c->opt_limbs_slices = value;
     else if (!strcmp(key, "peaks_gpu_branch")) { c->opt_gpu_branch_peaks = value; c->tab_in_h = -1; }
     else if (!strcmp(key, "kp_flip_x")) c->opt_kp_flip_x = value != 0;
@@ -482,13 +482,13 @@ static int launch_conv(pmx_ctx* c, const ConvArgs& a0, int groups, int v, const 
     ConvArgs a = a0;
     if (plan.S <= 1) {
         a.ksplit = 1; a.slab_stride = 0;
-        return conv_launch(v, a, groups, c->stream);
+        return conv_launch(v, a, groups, c->opt_conv_min_lds, c->opt_conv_v5_lds, c->stream);
     }
     SplitKReduceArgs r;
     int rc = slab_redirect(c, a0, groups, plan.S, (size_t)a0.B * a0.H * a0.W * a0.cout_pad, plan.bounds, a, r);
     if (rc) return rc;
     r.ksplit = plan.S;
-    if ((rc = conv_launch(v, a, groups, c->stream))) return rc;
+    if ((rc = conv_launch(v, a, groups, c->opt_conv_min_lds, c->opt_conv_v5_lds, c->stream))) return rc;
     return conv_splitk_reduce(r, groups, c->stream);
 }
 
@@ -530,10 +530,8 @@ static int launch_wino_run(pmx_ctx* c, const ConvArgs& a0, int ks, int groups, i
     if (pf && c->prof_on == 2) {
         // inside timed regions: the dispatch stamps the two events itself (no hipEventRecord barrier packets around the launch)
         if ((rc = prof_begin(c, pf->name, pf->flops * share, pf->bytes, pf->issued * share, /*record=*/false))) return rc;
-        conv_set_launch_events(c->pending.back().e0, c->pending.back().e1);
         c->prof_open = -1;
-        rc = conv_wino_run_launch(a, ks, groups, c->stream);
-        conv_set_launch_events(nullptr, nullptr);
+        rc = conv_wino_run_launch(a, ks, groups, c->stream, c->pending.back().e0, c->pending.back().e1);
         if (rc) {       // nothing was dispatched, so nothing will ever stamp the pair: take it back (prof_collect would fail on it for good)
             c->ev_pool.push_back(std::move(c->pending.back().e0));
             c->ev_pool.push_back(std::move(c->pending.back().e1));
@@ -575,7 +573,7 @@ static WinoSelectOpts wino_opts(const pmx_ctx* c, int ks, int groups, int lda)
     o.conv_algo = c->opt_conv_algo; o.precision = c->opt_precision; o.forced_variant = c->opt_force[ks]; o.ksplit = c->opt_ksplit;
     o.wino_unit_eff = c->opt_wino_unit_eff; o.wino_min_fill = c->opt_wino_min_fill; o.wino_geom = c->opt_wino_geom; o.wino_tail = c->opt_wino_tail;
     o.wino_tail_g = c->opt_wino_tail_g; o.wino_tail_merge = c->opt_wino_tail_merge; o.groups = groups; o.lda = lda; o.wino_unit_g = c->opt_wino_unit_g;
-    o.wino_split = c->opt_wino_split;
+    o.wino_split = c->opt_wino_split; o.ncu = c->num_cus;
     return o;
 }
 // every group of the launch has a Winograd form, and the groups agree in what the launch shares?
@@ -643,7 +641,7 @@ static int plan_conv(pmx_ctx* c, ConvPlan& p, const char* label, PackedLayer* L0
         p.form = FORM_WINO;
     } else {
         p.variant = conv_pick_variant(ks, L.cout_pad, H, W, B * groups, c->opt_force[ks], c->opt_kernel_gen, pool, groups == 1 ? L.cin : 9999,
-                                      c->opt_precision == 1 && ks > 1);
+                                      c->opt_precision == 1 && ks > 1, c->num_cus);
         if (c->opt_precision == 1 && ks > 1 && conv_bf16x3_twin(p.variant) >= 0) {
             if ((rc = ensure(ensure_bf16x3_pack))) return rc;
             p.variant = conv_bf16x3_twin(p.variant);
@@ -665,7 +663,7 @@ static int plan_conv(pmx_ctx* c, ConvPlan& p, const char* label, PackedLayer* L0
         a.nseg = (int)c->segs.size(); a.segs = c->d_segs + (size_t)t * c->segs.size(); a.seg_tiles = c->seg_tiles[t];
     }
     if (p.form == FORM_DIRECT) {
-        p.split = conv_pick_ksplit(p.variant, H, W, B, groups, L.cout_pad, L.nch, pool, c->opt_ksplit);
+        p.split = conv_pick_ksplit(p.variant, H, W, B, groups, L.cout_pad, L.nch, pool, c->opt_ksplit, c->num_cus);
         if (L.cout % 4 != 0 || ldc % 4 != 0 || (L1 && L1->cout != L.cout)) p.split.S = 1;
     }
     if (!p.prof) return PMX_OK;
@@ -677,7 +675,7 @@ static int plan_conv(pmx_ctx* c, ConvPlan& p, const char* label, PackedLayer* L0
         kn = ks == 7 ? "conv_f16_7x7" : "conv_f16_3x3";
         // issued: every MFMA of the launch -- the tile padding of the map edges, the channel padding of cin and of the block's BN columns
         const long long tiles = conv_f16_tiles(a);
-        const int bn = conv_f16_bn(a, groups, c->opt_f16_bn);
+        const int bn = conv_f16_bn(a, groups, c->opt_f16_bn, c->num_cus);
         issued = 2.0 * (double)tiles * 128.0 * (double)round_up(L.cout, bn) * (L.nch * CK) * ks * ks * groups;
     } else if (wino) {
         kn = ks == 7 ? "conv_wino_f2x2_7x7" : "conv_wino_f2x2_3x3";
@@ -708,7 +706,7 @@ static int launch_plan(pmx_ctx* c, const ConvPlan& p)
     int rc;
     if (pf && (rc = prof_begin(c, pf->name, pf->flops, pf->bytes, pf->issued))) return rc;
     switch (p.form) {
-    case FORM_F16: rc = conv_f16_launch(p.ks, p.a, p.groups, c->opt_f16_bn, c->stream); break;
+    case FORM_F16: rc = conv_f16_launch(p.ks, p.a, p.groups, c->opt_f16_bn, c->num_cus, c->stream); break;
     case FORM_WINO_UNITS: rc = launch_wino_units(c, p.a, p.ks, p.groups, p.unit_g); break;
     case FORM_WINO: rc = conv_wino_launch(p.a, p.ks, p.groups, c->stream); break;
     default: rc = launch_conv(c, p.a, p.groups, p.variant, p.split); break;
@@ -807,13 +805,13 @@ static bool conv1_form(const pmx_ctx* c, int B, int H, int W, bool* fuse_out)
     }
     const PackedLayer& L1 = c->layers[c->index.at("conv1_1")];
     const PackedLayer& L2 = c->layers[c->index.at("conv1_2")];
-    const int v2 = conv_pick_variant(3, L2.cout_pad, H, W, B, c->opt_force[3], c->opt_kernel_gen, 1, L2.cin, 0);
+    const int v2 = conv_pick_variant(3, L2.cout_pad, H, W, B, c->opt_force[3], c->opt_kernel_gen, 1, L2.cin, 0, c->num_cus);
     const bool fuse = c->opt_fuse_conv1 && c->opt_kernel_gen >= 6 && c->opt_precision == 0 && c->opt_force[3] < 0 && L1.cin == 3 && L1.cout == 64 &&
                       L2.cin == 64 && L2.cout == 64 && !strcmp(conv_variant(v2).name, "conv3x3_v5_t8x16_n64");
     const bool pair_ok = c->opt_precision == 0 && c->opt_force[3] < 0 && L1.cin == 3 && L1.cout == 64 && L2.cin == 64 && L2.cout == 64 && H % 2 == 0 && W % 2 == 0;
     if (fuse_out) *fuse_out = fuse;
     return pair_ok && c->opt_conv1_wino && c->opt_conv_algo >= 1 &&
-           (c->opt_conv1_wino == 2 || (fuse && (long long)B * ((H + 15) / 16) * ((W + 15) / 16) >= conv_num_cus()));
+           (c->opt_conv1_wino == 2 || (fuse && (long long)B * ((H + 15) / 16) * ((W + 15) / 16) >= c->num_cus));
 }
 
 static int run_conv1(pmx_ctx* c, int B, int H, int W)
@@ -1321,7 +1319,7 @@ extern "C" int pmx_postprocess(pmx_ctx* c, int B, int map_h, int map_w, double i
     // the candidate scan of a limb over several blocks where the maps come at full resolution (detect_precise, pmx_set_maps: crowds of
     // peaks, 19 blocks per image otherwise); the batch path's low-resolution maps keep the one-block form
     c->pp_limbs_slices = c->opt_limbs_slices >= 0 ? c->opt_limbs_slices : (c->maps_external ? 8 : 0);
-    rc = pp_launch(m, c->tab, c->pp, B, map_h, map_w, img_len, dscale, c->opt_keep_smoothed && c->pp.smoothed, c->stream,
+    rc = pp_launch(m, c->tab, c->pp, B, map_h, map_w, img_len, dscale, c->opt_keep_smoothed && c->pp.smoothed, c->opt_pp_generic, c->stream,
                    c->prof_on == 1 ? pp_prof_cb : nullptr, c, c->pp_limbs_slices);
     if (rc) return rc;
     c->pp_valid = true; c->pp_final = false; c->pp_B = B; c->pp_h = map_h; c->pp_w = map_w;
@@ -1420,11 +1418,11 @@ static int pp_finalize(pmx_ctx* c)
         c->pp_regrown += 1;
         if (c->pp_calls.empty()) {
             rc = pp_launch(c->pp_maps, c->tab, c->pp, B, c->pp_h, c->pp_w, c->pp_img_len, c->pp_has_scale ? c->d_scale : nullptr,
-                           c->opt_keep_smoothed && c->pp.smoothed, c->stream, nullptr, nullptr, c->pp_limbs_slices);
+                           c->opt_keep_smoothed && c->pp.smoothed, c->opt_pp_generic, c->stream, nullptr, nullptr, c->pp_limbs_slices);
         } else {                     // a mixed batch: every segment again, on its own slice of the (new) buffers
             for (const PPCall& q : c->pp_calls)
                 if ((rc = pp_launch(q.maps, q.tab, pmx_pp_view(c->pp, q.base), q.B, q.map_h, q.map_w, q.img_len, q.has_scale ? c->d_scale + 2 * q.base : nullptr,
-                                    0, c->stream, nullptr, nullptr, q.limbs_slices))) break;
+                                    0, c->opt_pp_generic, c->stream, nullptr, nullptr, q.limbs_slices))) break;
         }
         if (rc) { c->pp_valid = false; return rc; }
     }

@@ -295,7 +295,7 @@ void stage_keypoints(Stage& st, const int* hwf, int n, int fh, int fw, KpStage* 
 
 bool kp_fast(pmx_ctx* c)
 {
-    return c->gauss.size() == 21 && !c->opt_gpu_branch_peaks && !pp_get_generic();
+    return c->gauss.size() == 21 && !c->opt_gpu_branch_peaks && !c->opt_pp_generic;
 }
 
 // key points of crops [k0, k0 + B) of the call, on the current maps (images 0 .. B - 1): enqueue only
@@ -320,7 +320,7 @@ int kp_enqueue_chunk(pmx_ctx* c, const KpStage& ks, const int* hwf, int k0, int 
         if ((rc = pmx_ensure_smoothed(c, (size_t)n_ch * h * w))) return rc;
         PPMaps mk = m;
         mk.heat = m.heat + (long long)(k - k0) * m.sbh;
-        if ((rc = pp_keypoints_launch(mk, c->tab, c->pp, 1, n_ch, h, w, thresh, c->d_kp + (size_t)k * n_ch * 4, c->stream))) return rc;
+        if ((rc = pp_keypoints_launch(mk, c->tab, c->pp, 1, n_ch, h, w, thresh, c->d_kp + (size_t)k * n_ch * 4, c->opt_pp_generic, c->stream))) return rc;
     }
     return PMX_OK;
 }

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <atomic>
 #include <string>
 #include <vector>
 
@@ -71,7 +72,7 @@ struct ConvGroupArgs {
 };
 // Heterogeneous launches: a SEGMENT = n images of one map size.  The segments of a launch lie end to end in the activation buffers
 // (segment s, image i at pixel pix0 + i * H * W of the input, pixo + i * (output pixels per image) of the output) and own consecutive
-// tiles of the launch.  The table lives in device memory (one per resolution level and tile shape of a forward: conv_build_segs).
+// tiles of the launch.  The table lives in device memory (one per resolution level and tile shape of a forward: build_seg_tables).
 struct ConvSeg {
     int H, W;            // map size of the segment's images at this layer (before the optional pool)
     int tiles_x;         // tile columns per image
@@ -139,13 +140,12 @@ inline int wino_tail_merged_blocks(int B, int H)
 int conv_wino_tail_reduce(const WinoTailReduceArgs& r, int groups, hipStream_t stream);
 // dynamic LDS above 64 KB must be allowed per kernel AND per device (conv_mfma.hip; shared with conv_wino.hip)
 constexpr int PMX_MAX_DEVICES = 64;
-int conv_allow_big_lds(const void* kern, bool (&done)[PMX_MAX_DEVICES]);
-// launch of the run-geometry Winograd kernel (a.W % 46 == 0); a.ksplit > 1: unit mode writing compact slabs (see WinoTailReduceArgs)
-int conv_wino_run_launch(const ConvArgs& a, int ks, int groups, hipStream_t stream);
+int conv_allow_big_lds(const void* kern, std::atomic<bool> (&done)[PMX_MAX_DEVICES]);
+// launch of the run-geometry Winograd kernel (a.W % 46 == 0); a.ksplit > 1: unit mode writing compact slabs (see WinoTailReduceArgs);
+// e0 / e1: start / stop events stamped by the dispatch itself (hipExtLaunchKernelGGL), null = a plain launch
+int conv_wino_run_launch(const ConvArgs& a, int ks, int groups, hipStream_t stream, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 // launch of the merged-tail kernel (unit mode; a.run_j0 = the number of full blocks per image; wino_tail_mergeable(a.B, a.H, a.W))
 int conv_wino_merged_tail_launch(const ConvArgs& a, int ks, int groups, hipStream_t stream);
-// start / stop events for the next conv_wino_run_launch of this thread (stamped by the dispatch itself: hipExtLaunchKernelGGL)
-void conv_set_launch_events(hipEvent_t e0, hipEvent_t e1);
 // ---- kernel selection for the 3x3 / 7x7 layers (conv_select.hip) ------------------------------------------------------------
 struct WinoSelectOpts {      // the context options the choice depends on (pmx_set_option keys of the same names)
     int conv_algo, precision, forced_variant, ksplit, wino_unit_eff, wino_min_fill, wino_geom, wino_tail, wino_tail_g;
@@ -154,6 +154,7 @@ struct WinoSelectOpts {      // the context options the choice depends on (pmx_s
     int wino_unit_g = 0;         // chunks per pass-1 unit of a launch in unit mode: 0 = the plan that finishes first (dispatch simulation), > 0 = forced, -1 = as many units as 8 slabs allow (the rule until round 6)
     int groups = 1;              // branch groups in the launch (`images` counts images x groups)
     int lda = 0;                 // input channel stride (floats) of the launch: bounds the merged-tail form (wino_tail_mergeable)
+    int ncu;                     // compute units of the context's device
 };
 bool wino_eligible(int ks, int cin_pad, int cout_pad);
 // returns 0 = direct kernels (+ split-K), 1 = the Winograd kernel (*run = 1: run geometry; *tail_g > 0: chunks per pass-1 unit of its
@@ -200,32 +201,28 @@ int conv1_wino_launch(const ConvArgs& a, hipStream_t stream);
 // Winograd F(2x2, 3x3): a.nch = cin / 32, a.g[].w = transformed weights [plane][chunk32][k8-step][cout_pad][8] (G g G^T, host);
 // ks = 7: planes 0..63 = four 3x3 sub-kernels (taps 0..5 x 0..5), 64..71 row 6, 72..79 column 6 (1-D G g), 80 = tap (6, 6)
 int conv_wino_launch(const ConvArgs& a, int ks, int groups, hipStream_t stream);
-// K slices for a launch of `variant` (S = 1: no split); forced > 0 asks for that many (near-)even slices
-SplitPlan conv_pick_ksplit(int variant, int H, int W, int B, int groups, int cout_pad, int nch, int pool, int forced);
+// K slices for a launch of `variant` on a device of ncu compute units (S = 1: no split); forced > 0 asks for that many (near-)even slices
+SplitPlan conv_pick_ksplit(int variant, int H, int W, int B, int groups, int cout_pad, int nch, int pool, int forced, int ncu);
 
 struct ConvVariant {
     int ks, th, tw, bn, ck;
     const char* name;
 };
-// picks a kernel variant for (ksize, cout, B*H*W); returns index into the variant table
-int conv_pick_variant(int ks, int cout, int H, int W, int B, int forced, int gen, int pool, int cin, int bf16x3);
+// picks a kernel variant for (ksize, cout, B*H*W) on a device of ncu compute units; returns index into the variant table
+int conv_pick_variant(int ks, int cout, int H, int W, int B, int forced, int gen, int pool, int cin, int bf16x3, int ncu);
 const ConvVariant& conv_variant(int idx);
 int conv_num_variants();
-// launches the variant; groups = 1 or 2 (blockIdx.z)
-int conv_launch(int variant, const ConvArgs& a, int groups, hipStream_t stream);
-void conv_set_min_lds(int bytes);
-void conv_set_v5_lds(int bytes);        // LDS floor of the v5 / v8 kernels (caps the blocks per CU; tuning)
-int conv_v5_lds();
+// launches the variant; groups = 1 or 2 (blockIdx.z); min_lds / v5_lds: dynamic LDS floors of every direct kernel / of the v5 and v8
+// kernels (options "conv_min_lds" / "conv_v5_lds": they cap the blocks per CU)
+int conv_launch(int variant, const ConvArgs& a, int groups, int min_lds, int v5_lds, hipStream_t stream);
 // conv_bf16x3.hip (opt-in: built only with PMX_BUILD_BF16X3=1; a weak reference, null in the default library)
-int conv_bf16x3_launch(int ks, int mt, int pool, const ConvArgs& a, int groups, hipStream_t stream) __attribute__((weak));
+int conv_bf16x3_launch(int ks, int mt, int pool, const ConvArgs& a, int groups, int v5_lds, hipStream_t stream) __attribute__((weak));
 int conv_bf16x3_twin(int variant);      // the bf16x3 kernel with the geometry of a v6 variant, or -1
 // conv_f16.hip (option "precision" = 2): the 3x3 / 7x7 layers as direct convolutions on v_mfma_f32_32x32x16_f16, 8 x 16 pixel tiles
 // (a.nseg > 0: the PMX_SEG_RECT tables of a heterogeneous forward); a.g[].w = the layer's f16 pack [tap][chunk][cout_pad][16]
-int conv_f16_launch(int ks, const ConvArgs& a, int groups, int f16_bn, hipStream_t stream);     // f16_bn: option "f16_bn" (0 | 64 | 128)
+int conv_f16_launch(int ks, const ConvArgs& a, int groups, int f16_bn, int ncu, hipStream_t stream);     // f16_bn: option "f16_bn" (0 | 64 | 128)
 long long conv_f16_tiles(const ConvArgs& a);                 // 8 x 16 pixel tiles of the launch
-int conv_f16_bn(const ConvArgs& a, int groups, int f16_bn);  // output channels per block the launch takes (128 | 64)
-void conv_set_num_cus(int n);     // compute units of the device the contexts run on (tile / kernel selection heuristics)
-int conv_num_cus();
+int conv_f16_bn(const ConvArgs& a, int groups, int f16_bn, int ncu);  // output channels per block the launch takes (128 | 64) on ncu compute units
 // packed weight geometry helpers
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
@@ -235,10 +232,10 @@ int launch_prep_f32(const float* x_nchw, float* out16, int B, int H, int W, hipS
 int launch_resize_linear_u8(const uint8_t* src, uint8_t* dst, const int* xtab, const int* ytab, int B, int sh, int sw, int dh, int dw,
                             hipStream_t s);
 // cubic resize of B x C planes in one launch: source element (b, c, y, x) = src[b * sb + c * sc + y * sy + x * sx], planar destination
-// dst[((b * C + c) * dh + y) * dw + x] (accumulate: +=)
+// dst[((b * C + c) * dh + y) * dw + x] (accumulate: +=); rows (option "cubic_rows"): 1 separable form through LDS, 0 one thread per
+// element (same bits)
 int launch_resize_cubic_f32_planar(const float* src, long long sb, long long sc, long long sy, long long sx, int B, int C, float* dst, int dh, int dw,
-                                   const int* xi, const float* xc, const int* yi, const float* yc, int accumulate, hipStream_t s);
-void prep_set_cubic_rows(int on);     // 1 (default): separable form through LDS; 0: one thread per element (same bits)
+                                   const int* xi, const float* xc, const int* yi, const float* yc, int accumulate, int rows, hipStream_t s);
 int launch_resize_cubic_u8(const uint8_t* src, int sw, uint8_t* dst, int dh, int dw, int dpitch, const int* xi, const int* xa,
                            const int* yi, const int* ya, int B, long long sbytes, long long dbytes, hipStream_t s);
 // n padded images of ph x pw (dense, one after the other): the pixels outside the top-left sh x sw of each <- (b, g, r)
@@ -288,10 +285,10 @@ struct PPBuffers {
 #define PMX_LDS_CANDIDATES 4096     // candidate slots per limb in the LDS fast path
 #define PMX_LDS_SUBSETS 896         // subset rows in the LDS fast path (20 doubles each, dynamic LDS: 140 KB at most; the initial capacity is 128)
 #define PMX_LDS_USED 4096           // peaks per joint type whose "used" flags fit the LDS fast path
-void pp_set_generic(int on);
-int pp_get_generic();      // the "pp_generic" ablation switch (pmx_boxes.hip falls back to per-crop pp_keypoints_launch under it)
+// generic (option "pp_generic"): 1 = always the generic-radius peaks kernel (same bits; pmx_boxes.hip falls back to per-crop
+// pp_keypoints_launch under it)
 int pp_keypoints_launch(const PPMaps& maps, const PPTables& tab, const PPBuffers& buf, int B, int n_ch, int map_h, int map_w,
-                        double thresh, double* d_out, hipStream_t stream);
+                        double thresh, double* d_out, int generic, hipStream_t stream);
 int pp_launch(const PPMaps& maps, const PPTables& tab, const PPBuffers& buf, int B, int map_h, int map_w,
-              double img_len, const double* d_scale_xy, int keep_smoothed, hipStream_t stream,
+              double img_len, const double* d_scale_xy, int keep_smoothed, int generic, hipStream_t stream,
               void (*prof)(void*, const char*, int), void* prof_ctx, int limbs_slices = 0);      // limbs_slices > 1: the candidate scan of a limb over that many blocks

@@ -289,6 +289,7 @@ struct pmx_ctx {
     int pr_tabs_trims = 0;                               // how often that happened (diagnostics: option query "precise_table_trims")
     DevBuf<double> d_kp;             // key-point records of pmx_keypoints
     int device = 0;
+    int num_cus = 256;               // compute units of `device` (pmx_create_net): what kernel / tile selection counts blocks against
     hipStream_t stream = nullptr;    // what everything is enqueued on: own_stream or the caller's (pmx_set_stream), never destroyed here
     Stream own_stream;
     int max_batch = 0, max_h = 0, max_w = 0;
@@ -361,6 +362,12 @@ struct pmx_ctx {
     int opt_fuse_conv1 = 1;          // conv1_1 recomputed on conv1_2's halo tile, one launch (conv1_fused_kernel); identical bits
     int opt_fuse_pairs = 1;          // the two 1x1 layers that end every stage run as one launch (conv1x1_pair_kernel)
     int opt_ksplit = 0;              // 0: automatic split-K for small launches; n > 0: force n K slices where split-K applies
+    // kernel-form switches for tests and tuning: either setting computes the same bits
+    int opt_conv_min_lds = 0;        // dynamic LDS floor of every direct kernel: caps the co-resident blocks per CU (the fp32 MFMA
+                                     // pipe loses ~20% with 3+ waves per SIMD)
+    int opt_conv_v5_lds = 56 * 1024; // ... of the v5 / v8 kernels: 3 x 56 KB > 160 KB -> at most 2 blocks per CU
+    int opt_pp_generic = 0;          // 1: always the generic-radius peaks kernel
+    int opt_cubic_rows = 1;          // detect_precise's cubic resize: 1 the separable form through LDS, 0 one thread per element
     // split-K scratch: partial-sum slabs of the current launch + a zero bias vector for the slice blocks
     DevBuf<float> sk_scratch, sk_zero_bias;
     // timing / profiling

@@ -300,7 +300,7 @@ extern "C" int pmx_coco_eval(pmx_ctx* c, const pmx_eval_image* images, int n_ima
         if ((rc = pmx_results_layout(c, &cap, &rec))) return rc;       // final records: grows and re-runs the post-process if it must
         a.records = c->pp.results; a.rec_bytes = rec; a.cap_ppl = cap;
     }
-    static bool attr_set[PMX_MAX_DEVICES] = {};
+    static std::atomic<bool> attr_set[PMX_MAX_DEVICES] = {};
     if ((rc = conv_allow_big_lds(reinterpret_cast<const void*>(eval_kernel), attr_set))) return rc;
     if ((rc = c->ev_out.ensure(out_bytes, c->stream))) return rc;
     char *host, *dev;

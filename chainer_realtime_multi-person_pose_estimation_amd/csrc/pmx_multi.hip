@@ -194,7 +194,7 @@ extern "C" int pmx_postprocess_images(pmx_ctx* c, const int* map_hw, int B, cons
     if (scale_xy) PMX_HIP(hipMemcpyAsync(c->d_scale, scale_xy, sizeof(double) * 2 * B, hipMemcpyHostToDevice, c->stream));
     for (const PPCall& q : calls)
         if ((rc = pp_launch(q.maps, q.tab, pmx_pp_view(c->pp, q.base), q.B, q.map_h, q.map_w, q.img_len, scale_xy ? c->d_scale + 2 * q.base : nullptr, 0,
-                            c->stream, nullptr, nullptr, q.limbs_slices))) return rc;
+                            c->opt_pp_generic, c->stream, nullptr, nullptr, q.limbs_slices))) return rc;
     c->pp_calls = calls;
     c->pp_valid = true; c->pp_final = false; c->pp_B = B; c->pp_h = c->pp_w = 0;
     c->pp_has_scale = scale_xy != nullptr;

@@ -295,13 +295,13 @@ static int precise_add_scale(pmx_ctx* c, const uint8_t* imgs, int scaled_h, int 
         float* const t_paf = c->pr_tmp;
         float* const t_heat = c->pr_tmp + ppx * PMX_N_PAF * n;
         const long long sy = (long long)fw * PMX_CAT_C, sx = PMX_CAT_C, sb = (long long)fh * fw * PMX_CAT_C;
-        if ((rc2 = launch_resize_cubic_f32_planar(c->cat + PMX_CAT_PAF, sb, 1, sy, sx, n, PMX_N_PAF, t_paf, ph, pw, t3xi, (const float*)t3xc, t3yi, (const float*)t3yc, 0, c->stream))) return rc2;
-        if ((rc2 = launch_resize_cubic_f32_planar(c->cat + PMX_CAT_HEAT, sb, 1, sy, sx, n, PMX_N_HEAT, t_heat, ph, pw, t3xi, (const float*)t3xc, t3yi, (const float*)t3yc, 0, c->stream))) return rc2;
+        if ((rc2 = launch_resize_cubic_f32_planar(c->cat + PMX_CAT_PAF, sb, 1, sy, sx, n, PMX_N_PAF, t_paf, ph, pw, t3xi, (const float*)t3xc, t3yi, (const float*)t3yc, 0, c->opt_cubic_rows, c->stream))) return rc2;
+        if ((rc2 = launch_resize_cubic_f32_planar(c->cat + PMX_CAT_HEAT, sb, 1, sy, sx, n, PMX_N_HEAT, t_heat, ph, pw, t3xi, (const float*)t3xc, t3yi, (const float*)t3yc, 0, c->opt_cubic_rows, c->stream))) return rc2;
         // (4) crop the padding (source extent scaled_h x scaled_w of the padded maps) and cubic resize to the original size -> this scale's part
         if ((rc2 = launch_resize_cubic_f32_planar(t_paf, (long long)ppx * PMX_N_PAF, (long long)ppx, pw, 1, n, PMX_N_PAF, part_paf, oh, ow, t4xi, (const float*)t4xc, t4yi,
-                                                  (const float*)t4yc, 0, c->stream))) return rc2;
+                                                  (const float*)t4yc, 0, c->opt_cubic_rows, c->stream))) return rc2;
         if ((rc2 = launch_resize_cubic_f32_planar(t_heat, (long long)ppx * PMX_N_HEAT, (long long)ppx, pw, 1, n, PMX_N_HEAT, part_heat, oh, ow, t4xi, (const float*)t4xc, t4yi,
-                                                  (const float*)t4yc, 0, c->stream))) return rc2;
+                                                  (const float*)t4yc, 0, c->opt_cubic_rows, c->stream))) return rc2;
         PMX_HIP(hipEventRecord(c->pr_lane[li].done, c->stream));
         return PMX_OK;
     };
@@ -361,7 +361,7 @@ extern "C" int pmx_keypoints(pmx_ctx* c, int B, int out_h, int out_w, double thr
     const PPMaps m = pmx_current_maps(c);
     const size_t nkp = (size_t)B * n_ch * 4;
     if ((rc = pmx_ensure_smoothed(c, (size_t)B * n_ch * out_h * out_w)) || (rc = c->d_kp.ensure(nkp, c->stream))) return rc;
-    if ((rc = pp_keypoints_launch(m, c->tab, c->pp, B, n_ch, out_h, out_w, thresh, c->d_kp, c->stream))) return rc;
+    if ((rc = pp_keypoints_launch(m, c->tab, c->pp, B, n_ch, out_h, out_w, thresh, c->d_kp, c->opt_pp_generic, c->stream))) return rc;
     PMX_HIP(hipMemcpyAsync(out, c->d_kp, nkp * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     PMX_HIP(hipStreamSynchronize(c->stream));
     c->pp_valid = true; c->pp_final = true; c->pp_B = B; c->pp_h = out_h; c->pp_w = out_w;

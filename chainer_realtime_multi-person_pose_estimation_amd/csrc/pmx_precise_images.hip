@@ -419,7 +419,7 @@ extern "C" int pmx_detect_precise_images(pmx_ctx* c, const pmx_precise_image* im
     }
     for (const PPCall& q : calls) {
         if ((rc = pmx_prof_begin(c, "postprocess|pp_launch", 0))) return rc;
-        if ((rc = pp_launch(q.maps, q.tab, pmx_pp_view(c->pp, q.base), q.B, q.map_h, q.map_w, q.img_len, nullptr, 0, c->stream, nullptr, nullptr,
+        if ((rc = pp_launch(q.maps, q.tab, pmx_pp_view(c->pp, q.base), q.B, q.map_h, q.map_w, q.img_len, nullptr, 0, c->opt_pp_generic, c->stream, nullptr, nullptr,
                             q.limbs_slices))) return rc;
         if ((rc = pmx_prof_end(c))) return rc;
     }

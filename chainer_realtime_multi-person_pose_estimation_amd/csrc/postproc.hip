@@ -19,7 +19,6 @@
 // Bit-exactness: every float32 / float64 operation below is written in the operation order of the
 // reference's NumPy / SciPy code and this file is compiled with -ffp-contract=off (no FMA fusion), so peak
 // coordinates, ids, matching and grouping decisions are reproduced exactly for identical network outputs.
-#include <atomic>
 #include "pmx_common.h"
 
 #pragma clang fp contract(off)
@@ -578,12 +577,9 @@ __global__ __launch_bounds__(256) void pp_clear_kernel(PPBuffers buf, int B, int
 }
 
 // ============================================================================================== host
-static std::atomic<int> g_pp_generic{0};     // 1: always use the generic-radius peaks kernel (tests compare both paths)
-void pp_set_generic(int on) { g_pp_generic.store(on, std::memory_order_relaxed); }      // (process-wide, set through any context: a relaxed atomic)
-int pp_get_generic() { return g_pp_generic.load(std::memory_order_relaxed); }
-
+// generic = 1: always the generic-radius peaks kernel (tests compare both paths)
 int pp_launch(const PPMaps& maps, const PPTables& tab, const PPBuffers& buf, int B, int map_h, int map_w,
-              double img_len, const double* d_scale_xy, int keep_smoothed, hipStream_t stream,
+              double img_len, const double* d_scale_xy, int keep_smoothed, int generic, hipStream_t stream,
               void (*prof)(void*, const char*, int), void* prof_ctx, int limbs_slices)
 {
     // peak counters, status words and records start from zero (unused rows of a record stay zero): one launch instead of three memsets
@@ -596,7 +592,7 @@ int pp_launch(const PPMaps& maps, const PPTables& tab, const PPBuffers& buf, int
     const int tiles_x = (map_w + PK_TS - 1) / PK_TS, tiles_y = (map_h + PK_TS - 1) / PK_TS;
 
     if (prof) prof(prof_ctx, "pp_peaks", 1);
-    if (tab.radius == 10 && !pp_get_generic() && !tab.border_zero && !tab.nms_ge)
+    if (tab.radius == 10 && !generic && !tab.border_zero && !tab.nms_ge)
         hipLaunchKernelGGL(pp_peaks_fast_kernel<10>, dim3(tiles_x * tiles_y, PMX_N_JOINTS, B), dim3(256), 0, stream, maps, tab, buf,
                            map_h, map_w, tiles_x, keep_smoothed, PMX_N_JOINTS, 1);
     else
@@ -628,7 +624,7 @@ int pp_launch(const PPMaps& maps, const PPTables& tab, const PPBuffers& buf, int
     if (buf.cap_sub <= PMX_LDS_SUBSETS) {
         const size_t lds = (size_t)buf.cap_sub * 20 * sizeof(double);
         if (lds > 64 * 1024) {
-            static bool attr_set[PMX_MAX_DEVICES] = {};
+            static std::atomic<bool> attr_set[PMX_MAX_DEVICES] = {};
             if (int rc = conv_allow_big_lds(reinterpret_cast<const void*>(pp_group_kernel<true>), attr_set)) return rc;
         }
         hipLaunchKernelGGL(pp_group_kernel<true>, dim3(B), dim3(64), lds, stream, buf, d_scale_xy);
@@ -685,10 +681,10 @@ __global__ __launch_bounds__(256) void pp_argmax_kernel(const float* __restrict_
 }
 
 int pp_keypoints_launch(const PPMaps& maps, const PPTables& tab, const PPBuffers& buf, int B, int n_ch, int map_h, int map_w,
-                        double thresh, double* d_out, hipStream_t stream)
+                        double thresh, double* d_out, int generic, hipStream_t stream)
 {
     const int tiles_x = (map_w + PK_TS - 1) / PK_TS, tiles_y = (map_h + PK_TS - 1) / PK_TS;
-    if (tab.radius == 10 && !pp_get_generic() && !tab.border_zero)
+    if (tab.radius == 10 && !generic && !tab.border_zero)
         hipLaunchKernelGGL(pp_peaks_fast_kernel<10>, dim3(tiles_x * tiles_y, n_ch, B), dim3(256), 0, stream, maps, tab, buf, map_h, map_w,
                            tiles_x, 1, n_ch, 0);
     else

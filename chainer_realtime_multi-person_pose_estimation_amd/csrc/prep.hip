@@ -6,7 +6,6 @@
 //               each of the 256 possible byte values -> exact by construction (IEEE divide, then subtract).
 //   prep_f32  : the inner seam `model(x)` (pose_detector.py:499): float32 NCHW (B,3,H,W) -> NHWC-16.
 //   nchw<->nhwc: test / accessor helpers (pmx_set_maps, pmx_get_maps, pmx_conv2d).
-#include <atomic>
 #include "pmx_common.h"
 
 __global__ __launch_bounds__(256) void prep_u8_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst,
@@ -309,16 +308,13 @@ int launch_resize_linear_u8(const uint8_t* src, uint8_t* dst, const int* xtab, c
     return PMX_OK;
 }
 
-// 1: the separable form through LDS (default); 0: one thread per element (A/B and tests: the two must agree bit for bit)
-static std::atomic<int> g_cubic_rows{1};      // (process-wide, set through any context: a relaxed atomic)
-void prep_set_cubic_rows(int on) { g_cubic_rows.store(on, std::memory_order_relaxed); }
-
+// rows = 1: the separable form through LDS; 0: one thread per element (A/B and tests: the two must agree bit for bit)
 int launch_resize_cubic_f32_planar(const float* src, long long sb, long long sc, long long sy, long long sx, int B, int C, float* dst, int dh, int dw,
-                                   const int* xi, const float* xc, const int* yi, const float* yc, int accumulate, hipStream_t s)
+                                   const int* xi, const float* xc, const int* yi, const float* yc, int accumulate, int rows, hipStream_t s)
 {
     PMX_CHECK(dh >= 1 && dh <= 65535 && (long long)B * C >= 1 && (long long)B * C <= 65535, PMX_ERR_INVALID,
               "cubic resize: %d rows x %d planes outside the launch grid", dh, B * C);
-    if (g_cubic_rows.load(std::memory_order_relaxed)) {
+    if (rows) {
         constexpr int RB = 16, NR = 32;
         const dim3 grid((unsigned)((dw + 255) / 256), (unsigned)((dh + RB - 1) / RB), (unsigned)(B * C));
         if (accumulate) hipLaunchKernelGGL((resize_cubic_f32_rows_kernel<1, RB, NR>), grid, dim3(256), 0, s, src, sb, sc, sy, sx, C, dst, dh, dw, xi, xc, yi, yc);

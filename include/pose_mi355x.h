@@ -12,8 +12,8 @@
  * passed as void*).  Every function returns PMX_OK (0) or an error code; no exceptions cross the ABI;
  * pmx_last_error() returns a thread-local message for the last failing call.  One context per host
  * thread / stream; calls on a context are stream-ordered and asynchronous unless stated.  Contexts of different host threads may be created,
- * used and destroyed concurrently (never one context from two threads at once) and give the bits they give alone; the only state they share
- * is the four process-wide test switches named at pmx_set_option.
+ * used and destroyed concurrently (never one context from two threads at once) and give the bits they give alone; every option belongs to
+ * the context it was set on.
  * There is NO CPU fallback: pmx_create fails with PMX_ERR_NO_DEVICE when no gfx950 device is present.
  */
 #ifndef POSE_MI355X_H
@@ -176,7 +176,6 @@ int pmx_synchronize(pmx_ctx* ctx);                    /* cuda.get_device_from_id
  *                              (default 1; takes effect for lanes created afterwards, i.e. set it before the first detect_precise); same bits
  *   "precise_table_cap" n      detect_precise: cached cubic tables at which the next pmx_precise_begin* starts the cache over (default 208)
  *   "cubic_rows" 1 | 0         detect_precise's float32 cubic resizes: separable through LDS (default) | one thread per element; same bits
- *                              (process-wide, see the end of this list)
  *   "conv1_wino" 1 | 0 | 2     that launch with conv1_2 as Winograd F(2x2, 3x3) on 16 x 16 squares (default 1: where "conv_algo" >= 1
  *                              and the launch has a block per CU; 2: whatever the launch size); 0: the direct 8 x 16 tiles everywhere
  *   "fuse_pairs" 1 | 0         the two 1x1 layers that end every stage as one launch (default) or as two; identical bits
@@ -193,9 +192,8 @@ int pmx_synchronize(pmx_ctx* ctx);                    /* cuda.get_device_from_id
  *   "pp_limbs_slices" -1 | n   blocks per (limb, image) of the candidate-pair scan: -1 (default) = 8 where the maps come at full
  *                              resolution (detect_precise, pmx_set_maps), one block otherwise; 0 / 1 = one block; same results
  *   "conv_min_lds", "conv_v5_lds", "pp_generic"   ablation switches
- * PROCESS-wide, not per context: "pp_generic", "conv_min_lds", "conv_v5_lds" and "cubic_rows".  Setting one through any context changes it for
- * every context of the process, other threads' included, from their next launch on (whole-int atomic reads and writes, no other ordering).
- * All four choose between kernel forms that compute the same bits: switches for tests and tuning, not configuration. */
+ * "pp_generic", "conv_min_lds", "conv_v5_lds" and "cubic_rows" choose between kernel forms that compute the same bits: switches for tests
+ * and tuning, not configuration. */
 int pmx_set_option(pmx_ctx* ctx, const char* key, int value);
 
 /* ---- weights: serializers.load_npz (pose_detector.py:26) --------------------------------------

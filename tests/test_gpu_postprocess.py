@@ -241,14 +241,16 @@ def test_fast_and_generic_peak_kernels_agree(engine):
     and peaks (both are also compared with the oracle elsewhere)."""
     heat, paf, _ = Fx.synthetic_maps(21, 7, 46, 46, 1.0, 0.9, noise=0.03)
     out = {}
-    for generic in (0, 1):
-        engine.set_option('pp_generic', generic)
-        engine.set_option('keep_smoothed', 1)
-        engine.set_maps(paf[None], heat[None])
-        engine.postprocess(333, 301, img_len=301)
-        out[generic] = (engine.peaks(0), [engine.smoothed(0, j) for j in (0, 5, 17)], engine.results()[0].copy())
-    engine.set_option('pp_generic', 0)
-    engine.set_option('keep_smoothed', 0)
+    try:
+        for generic in (0, 1):
+            engine.set_option('pp_generic', generic)
+            engine.set_option('keep_smoothed', 1)
+            engine.set_maps(paf[None], heat[None])
+            engine.postprocess(333, 301, img_len=301)
+            out[generic] = (engine.peaks(0), [engine.smoothed(0, j) for j in (0, 5, 17)], engine.results()[0].copy())
+    finally:      # (`engine` is the session's: a failure above must not leave the switches set for the tests that follow)
+        engine.set_option('pp_generic', 0)
+        engine.set_option('keep_smoothed', 0)
     assert np.array_equal(out[0][0], out[1][0])
     for a, b in zip(out[0][1], out[1][1]):
         assert np.array_equal(a, b)

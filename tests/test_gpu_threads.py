@@ -112,9 +112,15 @@ def _rounds(eng, script, want, what, barrier, limit, rounds=ROUNDS):
 
 
 # ---- B1. pose contexts side by side ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('own_stream', [True, False], ids=['own_streams', 'torch_streams'])
-@pytest.mark.parametrize('n', [2, 4])
-def test_pose_contexts_on_their_own_threads(native, pose_w, refs, n, own_stream):
+# the four kernel-form switches of a context ("same bits" in the header; both LDS floors below the 160 KB a kernel may be granted)
+FORM_SWITCHES = (('pp_generic', 1), ('cubic_rows', 0), ('conv_v5_lds', 64 * 1024), ('conv_min_lds', 60 * 1024))
+
+
+@pytest.mark.parametrize('n, own_stream, switches', [(2, True, False), (2, False, False), (4, True, False), (4, False, False), (2, True, True)],
+                         ids=['2-own_streams', '2-torch_streams', '4-own_streams', '4-torch_streams', '2-own_streams-form_switches'])
+def test_pose_contexts_on_their_own_threads(native, pose_w, refs, n, own_stream, switches):
+    """switches: thread 1 sets FORM_SWITCHES on ITS context while thread 0 runs at the defaults -- both forms of the peaks kernel, of the
+    cubic resize and of the direct kernels' LDS floors side by side in one process, both equal to the serial default reference"""
     import torch
     torch.cuda.init()
     ref, secs = refs
@@ -129,6 +135,9 @@ def test_pose_contexts_on_their_own_threads(native, pose_w, refs, n, own_stream)
                     stream = torch.cuda.Stream()
                     assert stream.cuda_stream != 0
                     eng.set_stream(stream.cuda_stream)
+                if switches and k == 1:
+                    for key, value in FORM_SWITCHES:
+                        eng.set_option(key, value)
                 _rounds(eng, CS.pose_script, ref['pose'], 'thread %d of %d' % (k, n), barrier, limit)
                 eng.set_stream(0)
             finally:

@@ -148,7 +148,6 @@ def test_device_cubic_path_equals_host_restatement(native, shape, rows):
         assert np.array_equal(np.asarray(res_dev[0]), np.asarray(res_host[0]))
         assert np.array_equal(np.asarray(res_dev[1]), np.asarray(res_host[1]))
     host.engine.close()
-    dev.engine.set_option('cubic_rows', 1)
     dev.engine.close()
 
 
