@@ -122,11 +122,10 @@ static int build_transposed(PackedLayer& P, int cout, int cin, int ks, int kind,
     return PMX_OK;
 }
 
-static int prof_begin(pmx_ctx* c, const std::string& name0, double flops, double bytes, double issued = -1.0, bool record = true)
+// the profile events of a launch are recorded on the stream of its call
+static int prof_begin(pmx_ctx* c, const FwdCall& k, const std::string& name, double flops, double bytes, double issued = -1.0, bool record = true)
 {
     if (!c->prof_on) return PMX_OK;
-    // (one half of a batch cut in two by images, run_conv: the label carries "@<first image>+<count>")
-    const std::string name = c->split_suffix.empty() ? name0 : name0 + c->split_suffix;
     int idx;
     auto it = c->prof_index.find(name);
     if (it == c->prof_index.end()) {
@@ -140,22 +139,21 @@ static int prof_begin(pmx_ctx* c, const std::string& name0, double flops, double
         if (!c->ev_pool.empty()) { *e = std::move(c->ev_pool.back()); c->ev_pool.pop_back(); }
         else if (int rc = e->create(hipEventDefault)) return rc;
     }
-    if (record) PMX_HIP(hipEventRecord(p.e0, c->stream));
+    if (record) PMX_HIP(hipEventRecord(p.e0, k.stream));
     c->pending.push_back(std::move(p));
     c->prof_open = (int)c->pending.size() - 1;
     return PMX_OK;
 }
-static int prof_end(pmx_ctx* c);
-// the profiler for the other translation units (pmx_boxes.hip): a labelled launch of `bytes` compulsory bytes
-int pmx_prof_begin(pmx_ctx* c, const char* name, double bytes) { return c->prof_on == 1 ? prof_begin(c, name, 0, bytes) : PMX_OK; }
-int pmx_prof_end(pmx_ctx* c) { return prof_end(c); }
-static int prof_end(pmx_ctx* c)
+static int prof_end(pmx_ctx* c, const FwdCall& k)
 {
     if (!c->prof_on || c->prof_open < 0) return PMX_OK;
-    PMX_HIP(hipEventRecord(c->pending[c->prof_open].e1, c->stream));
+    PMX_HIP(hipEventRecord(c->pending[c->prof_open].e1, k.stream));
     c->prof_open = -1;
     return PMX_OK;
 }
+// the profiler for the other translation units (pmx_boxes.hip): a labelled launch of `bytes` compulsory bytes
+int pmx_prof_begin(pmx_ctx* c, const char* name, double bytes) { return c->prof_on == 1 ? prof_begin(c, pmx_call(c), name, 0, bytes) : PMX_OK; }
+int pmx_prof_end(pmx_ctx* c) { return prof_end(c, pmx_call(c)); }
 static int prof_collect(pmx_ctx* c)
 {
     if (c->pending.empty()) return PMX_OK;
@@ -174,8 +172,8 @@ static int prof_collect(pmx_ctx* c)
 static void pp_prof_cb(void* vc, const char* name, int begin)
 {
     pmx_ctx* c = (pmx_ctx*)vc;
-    if (begin) (void)prof_begin(c, std::string(name) + "|" + name, 0, 0);
-    else (void)prof_end(c);
+    if (begin) (void)prof_begin(c, pmx_call(c), std::string(name) + "|" + name, 0, 0);
+    else (void)prof_end(c, pmx_call(c));
 }
 
 
@@ -419,10 +417,10 @@ extern "C" int pmx_weights_missing(pmx_ctx* c, int* n)
 // ------------------------------------------------------------------------------------------ forward
 // Derived weight packs -- Winograd, f16, bf16x3, conv1_1's fused-kernel pack (which lives in conv1_1's otherwise unused Winograd slot) --
 // are built on the device from the direct pack when a kernel first needs them: allocate, launch the kind's packer for job `j` on the
-// context's current stream, wait for it.  The slot takes the buffer only when it is complete: a failure leaves no pointer to garbage
+// stream of the call that needs it, wait for it.  The slot takes the buffer only when it is complete: a failure leaves no pointer to garbage
 // behind, and the lanes of detect_precise may share the pack from their own streams as soon as this returns.
 template <typename T>
-static int derive_on_device(pmx_ctx* c, const PackedLayer& L, int kind, DevBuf<T>& slot, PackJob j)
+static int derive_on_device(hipStream_t st, const PackedLayer& L, int kind, DevBuf<T>& slot, PackJob j)
 {
     if (slot) return PMX_OK;
     if (L.busy) PMX_HIP(hipStreamSynchronize(L.busy_stream));      // a training step may still be writing d_w
@@ -430,31 +428,31 @@ static int derive_on_device(pmx_ctx* c, const PackedLayer& L, int kind, DevBuf<T
     int rc;
     if ((rc = d.alloc(j.total))) return rc;
     j.dst = d.get();
-    if ((rc = pmx_pack_launch_one(kind, j, c->stream))) return rc;
-    PMX_HIP(hipStreamSynchronize(c->stream));
+    if ((rc = pmx_pack_launch_one(kind, j, st))) return rc;
+    PMX_HIP(hipStreamSynchronize(st));
     slot = std::move(d);
     return PMX_OK;
 }
-static int ensure_wino_pack(pmx_ctx* c, PackedLayer& L) { return derive_on_device(c, L, PMX_PACK_WINO, L.d_ww, pmx_pack_job_wino(L, nullptr)); }
-static int ensure_conv1_pack(pmx_ctx* c, PackedLayer& L) { return derive_on_device(c, L, PMX_PACK_CONV1, L.d_ww, pmx_pack_job_conv1(L, nullptr)); }
-static int ensure_bf16x3_pack(pmx_ctx* c, PackedLayer& L) { return derive_on_device(c, L, PMX_PACK_BF16X3, L.d_w3, pmx_pack_job_bf16x3(L, nullptr)); }
+static int ensure_wino_pack(hipStream_t st, PackedLayer& L) { return derive_on_device(st, L, PMX_PACK_WINO, L.d_ww, pmx_pack_job_wino(L, nullptr)); }
+static int ensure_conv1_pack(hipStream_t st, PackedLayer& L) { return derive_on_device(st, L, PMX_PACK_CONV1, L.d_ww, pmx_pack_job_conv1(L, nullptr)); }
+static int ensure_bf16x3_pack(hipStream_t st, PackedLayer& L) { return derive_on_device(st, L, PMX_PACK_BF16X3, L.d_w3, pmx_pack_job_bf16x3(L, nullptr)); }
 // the f16 pack (half the fp32 weights' bytes): every 3x3 / 7x7 layer in f16 mode
-static int ensure_f16_pack(pmx_ctx* c, PackedLayer& L) { return derive_on_device(c, L, PMX_PACK_F16, L.d_w16, pmx_pack_job_f16(L, nullptr)); }
+static int ensure_f16_pack(hipStream_t st, PackedLayer& L) { return derive_on_device(st, L, PMX_PACK_F16, L.d_w16, pmx_pack_job_f16(L, nullptr)); }
 
 // Launches one convolution (1 or 2 groups) whose ConvArgs describe the FINAL result (real bias, ReLU, pool, output slices).
-// With S > 1 K slices the slice blocks write raw partial sums into the context's slab scratch and conv_splitk_reduce
+// With S > 1 K slices the slice blocks write raw partial sums into the slab scratch of the call's working set and conv_splitk_reduce
 // produces the final result (slabs added in slice order, then bias, ReLU, pool).
 static const int SK_ZERO_BIAS = PMX_SK_ZERO_BIAS;
 // the slab scratch at `need` floats at least, and the zero bias vector of the slice blocks (made on first use)
-static int sk_reserve(pmx_ctx* c, size_t need)
+static int sk_reserve(pmx_ctx* c, const FwdCall& k, size_t need)
 {
     int rc;
-    if ((rc = c->sk_scratch.ensure(need, c->stream))) return rc;
+    if ((rc = k.ws.sk_scratch.ensure(need, k.stream))) return rc;
     if (!c->sk_zero_bias) {
         if ((rc = c->sk_zero_bias.alloc(SK_ZERO_BIAS))) return rc;
         // stream-ordered: a null-stream hipMemset is not ordered against this (non-blocking) stream and may still be in flight
         // when the first slice kernel reads the vector
-        PMX_HIP(hipMemsetAsync(c->sk_zero_bias, 0, SK_ZERO_BIAS * sizeof(float), c->stream));
+        PMX_HIP(hipMemsetAsync(c->sk_zero_bias, 0, SK_ZERO_BIAS * sizeof(float), k.stream));
     }
     return PMX_OK;
 }
@@ -462,13 +460,13 @@ static int sk_reserve(pmx_ctx* c, size_t need)
 // them -- raw sums of all cout_pad columns: zero bias, no ReLU, no pool -- and `r`, the arguments of the kernel that adds the slabs of a
 // group (r.slabs[]), takes over what a0 says about the final result; its slab count and whatever else is its own are the caller's.
 template <typename Reduce>
-static int slab_redirect(pmx_ctx* c, const ConvArgs& a0, int groups, int S, size_t slab, unsigned long long kbounds, ConvArgs& a, Reduce& r)
+static int slab_redirect(pmx_ctx* c, const FwdCall& k, const ConvArgs& a0, int groups, int S, size_t slab, unsigned long long kbounds, ConvArgs& a, Reduce& r)
 {
     PMX_CHECK(a0.cout_pad <= SK_ZERO_BIAS, PMX_ERR_INVALID, "split-K: cout_pad %d too large", a0.cout_pad);
-    if (int rc = sk_reserve(c, slab * S * groups)) return rc;
+    if (int rc = sk_reserve(c, k, slab * S * groups)) return rc;
     memset(&r, 0, sizeof r);
     for (int g = 0; g < groups; ++g) {
-        float* base = c->sk_scratch + (size_t)g * S * slab;
+        float* base = k.ws.sk_scratch + (size_t)g * S * slab;
         r.slabs[g] = base; r.bias[g] = a0.g[g].bias; r.out[g] = a0.g[g].out; r.cout[g] = a0.g[g].cout;
         a.g[g].out = base; a.g[g].bias = c->sk_zero_bias; a.g[g].cout = a0.cout_pad;
     }
@@ -477,48 +475,53 @@ static int slab_redirect(pmx_ctx* c, const ConvArgs& a0, int groups, int S, size
     r.relu = a0.relu; r.pool = a0.pool;
     return PMX_OK;
 }
-static int launch_conv(pmx_ctx* c, const ConvArgs& a0, int groups, int v, const SplitPlan& plan)
+static int launch_conv(pmx_ctx* c, const FwdCall& k, const ConvArgs& a0, int groups, int v, const SplitPlan& plan)
 {
     ConvArgs a = a0;
     if (plan.S <= 1) {
         a.ksplit = 1; a.slab_stride = 0;
-        return conv_launch(v, a, groups, c->opt_conv_min_lds, c->opt_conv_v5_lds, c->stream);
+        return conv_launch(v, a, groups, c->opt_conv_min_lds, c->opt_conv_v5_lds, k.stream);
     }
     SplitKReduceArgs r;
-    int rc = slab_redirect(c, a0, groups, plan.S, (size_t)a0.B * a0.H * a0.W * a0.cout_pad, plan.bounds, a, r);
+    int rc = slab_redirect(c, k, a0, groups, plan.S, (size_t)a0.B * a0.H * a0.W * a0.cout_pad, plan.bounds, a, r);
     if (rc) return rc;
     r.ksplit = plan.S;
-    if ((rc = conv_launch(v, a, groups, c->opt_conv_min_lds, c->opt_conv_v5_lds, c->stream))) return rc;
-    return conv_splitk_reduce(r, groups, c->stream);
+    if ((rc = conv_launch(v, a, groups, c->opt_conv_min_lds, c->opt_conv_v5_lds, k.stream))) return rc;
+    return conv_splitk_reduce(r, groups, k.stream);
 }
 
 // Unit mode of the Winograd kernel (single images): a (tile, group) is cut into S units -- pass 1 over g chunks each (ceil(nch / g) units)
 // and, for 7x7, row 6, column 6 and tap (6, 6) -- that run as separate blocks writing slabs, combined in unit order by the split-K combine kernel
 // (bias, ReLU, pool there)
-static int launch_wino_units(pmx_ctx* c, const ConvArgs& a0, int ks, int groups, int g)
+static int launch_wino_units(pmx_ctx* c, const FwdCall& k, const ConvArgs& a0, int ks, int groups, int g)
 {
     const int S = (a0.nch + g - 1) / g + (ks == 7 ? 3 : 0);
     PMX_CHECK(S >= 2 && S <= 8, PMX_ERR_INVALID, "winograd units: %d slabs", S);
     ConvArgs a = a0;
     SplitKReduceArgs r;
-    int rc = slab_redirect(c, a0, groups, S, (size_t)a0.B * a0.H * a0.W * a0.cout_pad, (unsigned long long)g, a, r);
+    int rc = slab_redirect(c, k, a0, groups, S, (size_t)a0.B * a0.H * a0.W * a0.cout_pad, (unsigned long long)g, a, r);
     if (rc) return rc;
     r.ksplit = S;
-    if ((rc = conv_wino_launch(a, ks, groups, c->stream))) return rc;
-    return conv_splitk_reduce(r, groups, c->stream);
+    if ((rc = conv_wino_launch(a, ks, groups, k.stream))) return rc;
+    return conv_splitk_reduce(r, groups, k.stream);
 }
 
 // Run geometry of the Winograd kernel (46-pixel-wide maps): the full blocks [0, nfull) of every image as one plain launch; the part-filled
 // last block of every image in unit mode (S units of g pass-1 chunks (+ row 6, column 6, tap (6, 6)) writing compact slabs) + the combine
 // kernel.  B = 32 at 46 x 46: 16 x 32 x 2 = 1024 full blocks = exactly 4 rounds of the 256 CUs, then 64 x 7 short unit blocks, instead of
 // 5 rounds of 18 x 32 x 2 rectangles.  tail_g = 0: every block (also the part-filled one) in the plain launch.
-struct ConvProf { std::string name; double flops, bytes, issued; };      // profile entry of a layer's launch
+// profile entry of a layer's launch.  suffix: "@<first image>+<count>" on one half of a batch cut in two by images (run_conv), the last
+// thing of every label of the launch
+struct ConvProf {
+    std::string name; double flops, bytes, issued; std::string suffix;
+    std::string label(const char* part = "") const { return name + part + suffix; }
+};
 // the tails of all images of the launch as one stream of tiles, 32 per block (conv_wino_kernel<KS, 0, 1, 3>)?
 static bool wino_tail_merged(const pmx_ctx* c, const ConvArgs& a)
 {
     return c->opt_wino_tail_merge != 0 && wino_tail_mergeable(a.B, a.H, a.W, a.lda);
 }
-static int launch_wino_run(pmx_ctx* c, const ConvArgs& a0, int ks, int groups, int tail_g, const ConvProf* pf)      // (pf null: not profiled)
+static int launch_wino_run(pmx_ctx* c, const FwdCall& k, const ConvArgs& a0, int ks, int groups, int tail_g, const ConvProf* pf)      // (pf null: not profiled)
 {
     const int ntiles = PMX_WINO_RUN_TX * ((a0.H + 1) / 2), nblk = (ntiles + PMX_WINO_RUN_TILES - 1) / PMX_WINO_RUN_TILES, nfull = ntiles / PMX_WINO_RUN_TILES;
     ConvArgs a = a0;
@@ -529,18 +532,18 @@ static int launch_wino_run(pmx_ctx* c, const ConvArgs& a0, int ks, int groups, i
     int rc;
     if (pf && c->prof_on == 2) {
         // inside timed regions: the dispatch stamps the two events itself (no hipEventRecord barrier packets around the launch)
-        if ((rc = prof_begin(c, pf->name, pf->flops * share, pf->bytes, pf->issued * share, /*record=*/false))) return rc;
+        if ((rc = prof_begin(c, k, pf->label(), pf->flops * share, pf->bytes, pf->issued * share, /*record=*/false))) return rc;
         c->prof_open = -1;
-        rc = conv_wino_run_launch(a, ks, groups, c->stream, c->pending.back().e0, c->pending.back().e1);
+        rc = conv_wino_run_launch(a, ks, groups, k.stream, c->pending.back().e0, c->pending.back().e1);
         if (rc) {       // nothing was dispatched, so nothing will ever stamp the pair: take it back (prof_collect would fail on it for good)
             c->ev_pool.push_back(std::move(c->pending.back().e0));
             c->ev_pool.push_back(std::move(c->pending.back().e1));
             c->pending.pop_back();
         }
     } else {
-        if (pf && (rc = prof_begin(c, pf->name, pf->flops * share, pf->bytes, pf->issued * share))) return rc;
-        rc = conv_wino_run_launch(a, ks, groups, c->stream);
-        if (pf && !rc) rc = prof_end(c);
+        if (pf && (rc = prof_begin(c, k, pf->label(), pf->flops * share, pf->bytes, pf->issued * share))) return rc;
+        rc = conv_wino_run_launch(a, ks, groups, k.stream);
+        if (pf && !rc) rc = prof_end(c, k);
     }
     if (rc || !tail_g) return rc;
     PMX_CHECK(nfull >= 1 && nfull < nblk, PMX_ERR_INVALID, "winograd tail: no part-filled block (%d tiles)", ntiles);
@@ -552,25 +555,25 @@ static int launch_wino_run(pmx_ctx* c, const ConvArgs& a0, int ks, int groups, i
     const size_t slab = merged ? (size_t)wino_tail_merged_blocks(a0.B, a0.H) * PMX_WINO_RUN_TILES * 4 * a0.cout_pad      // [block of the stream][tile][pixel][cout_pad]
                                : (size_t)a0.B * nslab * PMX_WINO_RUN_TILES * 4 * a0.cout_pad;      // one block per (image, slab): [image][slab][tile][pixel][cout_pad]
     WinoTailReduceArgs r;
-    if ((rc = slab_redirect(c, a0, groups, S, slab, (unsigned long long)tail_g, a, r))) return rc;
+    if ((rc = slab_redirect(c, k, a0, groups, S, slab, (unsigned long long)tail_g, a, r))) return rc;
     a.run_j0 = nfull; a.run_nb = 1;
     r.S = S; r.run_j0 = nfull; r.run_nb = 1; r.nslab = nslab; r.merged = merged;
     // (profile mode 2 -- the dominant kernel only, inside timed regions -- leaves these two short launches without events: an event pair
     //  costs ~5 us of idle stream)
     const bool pf_all = pf && c->prof_on == 1;
-    if (pf_all && (rc = prof_begin(c, pf->name + ":units", pf->flops * (1.0 - share), 0.0, pf->issued * (1.0 - share)))) return rc;
-    if ((rc = merged ? conv_wino_merged_tail_launch(a, ks, groups, c->stream) : conv_wino_run_launch(a, ks, groups, c->stream))) return rc;
-    if (pf_all && (rc = prof_end(c))) return rc;
-    if (pf_all && (rc = prof_begin(c, pf->name + ":combine", 0.0, 0.0, 0.0))) return rc;
-    if ((rc = conv_wino_tail_reduce(r, groups, c->stream))) return rc;
-    return pf_all ? prof_end(c) : PMX_OK;
+    if (pf_all && (rc = prof_begin(c, k, pf->label(":units"), pf->flops * (1.0 - share), 0.0, pf->issued * (1.0 - share)))) return rc;
+    if ((rc = merged ? conv_wino_merged_tail_launch(a, ks, groups, k.stream) : conv_wino_run_launch(a, ks, groups, k.stream))) return rc;
+    if (pf_all && (rc = prof_end(c, k))) return rc;
+    if (pf_all && (rc = prof_begin(c, k, pf->label(":combine"), 0.0, 0.0, 0.0))) return rc;
+    if ((rc = conv_wino_tail_reduce(r, groups, k.stream))) return rc;
+    return pf_all ? prof_end(c, k) : PMX_OK;
 }
 
-// the context options the choice of a 3x3 / 7x7 layer's form depends on (conv_select.hip)
-static WinoSelectOpts wino_opts(const pmx_ctx* c, int ks, int groups, int lda)
+// the context options, and the call's "conv_algo", the choice of a 3x3 / 7x7 layer's form depends on (conv_select.hip)
+static WinoSelectOpts wino_opts(const pmx_ctx* c, const FwdCall& k, int ks, int groups, int lda)
 {
     WinoSelectOpts o;
-    o.conv_algo = c->opt_conv_algo; o.precision = c->opt_precision; o.forced_variant = c->opt_force[ks]; o.ksplit = c->opt_ksplit;
+    o.conv_algo = k.conv_algo; o.precision = c->opt_precision; o.forced_variant = c->opt_force[ks]; o.ksplit = c->opt_ksplit;
     o.wino_unit_eff = c->opt_wino_unit_eff; o.wino_min_fill = c->opt_wino_min_fill; o.wino_geom = c->opt_wino_geom; o.wino_tail = c->opt_wino_tail;
     o.wino_tail_g = c->opt_wino_tail_g; o.wino_tail_merge = c->opt_wino_tail_merge; o.groups = groups; o.lda = lda; o.wino_unit_g = c->opt_wino_unit_g;
     o.wino_split = c->opt_wino_split; o.ncu = c->num_cus;
@@ -602,19 +605,19 @@ struct ConvPlan {
 };
 
 // in/out pointers are already offset to the group's channels; L1 null: one group; label null: never profiled
-// `level` (heterogeneous forward only, c->segs non-empty): the resolution level of the layer's input, 0 = network input .. 3 = 1/8; B, H, W
+// `level` (heterogeneous forward only, k.seg set): the resolution level of the layer's input, 0 = network input .. 3 = 1/8; B, H, W
 // then carry the image count and the LARGEST map of the level (launch checks), the geometry comes from the segment table of the level.
 // Makes sure the derived pack of the form exists.
-static int plan_conv(pmx_ctx* c, ConvPlan& p, const char* label, PackedLayer* L0, PackedLayer* L1, const float* in0, const float* in1, int lda,
+static int plan_conv(pmx_ctx* c, const FwdCall& k, ConvPlan& p, const char* label, PackedLayer* L0, PackedLayer* L1, const float* in0, const float* in1, int lda,
                      float* out0, float* out1, int ldc, int B, int H, int W, int relu, int pool, int level)
 {
     const PackedLayer& L = *L0;
     const int ks = L.ks, groups = L1 ? 2 : 1;
     const char* who = label ? label : "pmx_conv2d";
-    const bool seg = !c->segs.empty() && level >= 0;
-    const double npix = seg ? (double)c->seg_pix[level] : (double)B * H * W;
+    const bool seg = k.seg && level >= 0;
+    const double npix = seg ? (double)k.seg->pix[level] : (double)B * H * W;
     PackedLayer* const Lg[2] = {L0, L1};
-    auto ensure = [&](int (*fn)(pmx_ctx*, PackedLayer&)) { const int rc = fn(c, *L0); return rc || !L1 ? rc : fn(c, *L1); };
+    auto ensure = [&](int (*fn)(hipStream_t, PackedLayer&)) { const int rc = fn(k.stream, *L0); return rc || !L1 ? rc : fn(k.stream, *L1); };
     p.ks = ks; p.groups = groups;
     p.prof = label && (c->prof_on == 1 || (c->prof_on == 2 && ks == 7));
     ConvArgs& a = p.a;
@@ -629,7 +632,7 @@ static int plan_conv(pmx_ctx* c, ConvPlan& p, const char* label, PackedLayer* L0
     int rc;
     if (c->opt_precision == 2 && ks > 1) {
         p.form = FORM_F16;
-        PMX_CHECK(c->segs.empty() || seg, PMX_ERR_INVALID, "heterogeneous forward: layer %s without a resolution level", who);
+        PMX_CHECK(!k.seg || seg, PMX_ERR_INVALID, "heterogeneous forward: layer %s without a resolution level", who);
         PMX_CHECK(!L1 || (L1->ks == ks && L1->nch == L.nch && L1->cout_pad == L.cout_pad), PMX_ERR_INVALID, "conv f16: the two groups of %s differ in shape", who);
         if ((rc = ensure(ensure_f16_pack))) return rc;
         for (int g = 0; g < groups; ++g) a.g[g].w = (const float*)Lg[g]->d_w16.get();
@@ -648,7 +651,7 @@ static int plan_conv(pmx_ctx* c, ConvPlan& p, const char* label, PackedLayer* L0
             for (int g = 0; g < groups; ++g) a.g[g].w = (const float*)Lg[g]->d_w3.get();
         }
         int wrun = 0;
-        const int wmode = wino_layers_ok(L0, L1) ? wino_select(wino_opts(c, ks, groups, lda), ks, L.cin_pad, L.cout_pad, L.cout, ldc, B * groups, H, W,
+        const int wmode = wino_layers_ok(L0, L1) ? wino_select(wino_opts(c, k, ks, groups, lda), ks, L.cin_pad, L.cout_pad, L.cout, ldc, B * groups, H, W,
                                                                pool, &p.unit_g, &wrun, &p.tail_g) : 0;
         p.form = wmode == 2 ? FORM_WINO_UNITS : wmode == 1 ? (wrun ? FORM_WINO_RUN : FORM_WINO) : FORM_DIRECT;
     }
@@ -660,7 +663,7 @@ static int plan_conv(pmx_ctx* c, ConvPlan& p, const char* label, PackedLayer* L0
     }
     if (seg) {
         const int t = PMX_SEG_RECT(level, pool);
-        a.nseg = (int)c->segs.size(); a.segs = c->d_segs + (size_t)t * c->segs.size(); a.seg_tiles = c->seg_tiles[t];
+        a.nseg = (int)k.seg->segs.size(); a.segs = k.seg->table(t); a.seg_tiles = k.seg->tiles[t];
     }
     if (p.form == FORM_DIRECT) {
         p.split = conv_pick_ksplit(p.variant, H, W, B, groups, L.cout_pad, L.nch, pool, c->opt_ksplit, c->num_cus);
@@ -699,68 +702,65 @@ static int plan_conv(pmx_ctx* c, ConvPlan& p, const char* label, PackedLayer* L0
 }
 
 // profile begin, the launch sequence of the plan's form, profile end
-static int launch_plan(pmx_ctx* c, const ConvPlan& p)
+static int launch_plan(pmx_ctx* c, const FwdCall& k, const ConvPlan& p)
 {
     const ConvProf* pf = p.prof ? &p.pf : nullptr;
-    if (p.form == FORM_WINO_RUN) return launch_wino_run(c, p.a, p.ks, p.groups, p.tail_g, pf);      // (up to three launches, an entry each)
+    if (p.form == FORM_WINO_RUN) return launch_wino_run(c, k, p.a, p.ks, p.groups, p.tail_g, pf);      // (up to three launches, an entry each)
     int rc;
-    if (pf && (rc = prof_begin(c, pf->name, pf->flops, pf->bytes, pf->issued))) return rc;
+    if (pf && (rc = prof_begin(c, k, pf->label(), pf->flops, pf->bytes, pf->issued))) return rc;
     switch (p.form) {
-    case FORM_F16: rc = conv_f16_launch(p.ks, p.a, p.groups, c->opt_f16_bn, c->num_cus, c->stream); break;
-    case FORM_WINO_UNITS: rc = launch_wino_units(c, p.a, p.ks, p.groups, p.unit_g); break;
-    case FORM_WINO: rc = conv_wino_launch(p.a, p.ks, p.groups, c->stream); break;
-    default: rc = launch_conv(c, p.a, p.groups, p.variant, p.split); break;
+    case FORM_F16: rc = conv_f16_launch(p.ks, p.a, p.groups, c->opt_f16_bn, c->num_cus, k.stream); break;
+    case FORM_WINO_UNITS: rc = launch_wino_units(c, k, p.a, p.ks, p.groups, p.unit_g); break;
+    case FORM_WINO: rc = conv_wino_launch(p.a, p.ks, p.groups, k.stream); break;
+    default: rc = launch_conv(c, k, p.a, p.groups, p.variant, p.split); break;
     }
     if (rc) return rc;
-    return pf ? prof_end(c) : PMX_OK;
+    return pf ? prof_end(c, k) : PMX_OK;
 }
 
 // one layer of a forward: plan + launch.  A batch whose plain launch would end in a part-filled round of the CUs is cut in two first: the
 // images of the whole rounds, then the rest through the selection of THEIR count (conv_select.hip::wino_split_images); each half is an
-// ordinary run_conv on its images
-static int run_conv(pmx_ctx* c, const char* label, PackedLayer* L0, PackedLayer* L1, const float* in0, const float* in1, int lda,
-                    float* out0, float* out1, int ldc, int B, int H, int W, int relu, int pool, int level = -1)
+// ordinary run_conv on its images, whose profile labels end in `half` = "@<first image>+<count>" (null: a whole batch)
+static int run_conv(pmx_ctx* c, const FwdCall& k, const char* label, PackedLayer* L0, PackedLayer* L1, const float* in0, const float* in1, int lda,
+                    float* out0, float* out1, int ldc, int B, int H, int W, int relu, int pool, int level = -1, const char* half = nullptr)
 {
-    const bool seg = !c->segs.empty() && level >= 0;
+    const bool seg = k.seg && level >= 0;
     int rc;
-    if (!seg && c->split_suffix.empty() && c->opt_wino_split && B >= 2 && L0->ks > 1 && c->opt_precision != 2 && wino_layers_ok(L0, L1)) {
-        const int n0 = wino_split_images(wino_opts(c, L0->ks, L1 ? 2 : 1, lda), L0->ks, L0->cin_pad, L0->cout_pad, L0->cout, ldc, B, L1 ? 2 : 1, H, W, pool);
+    if (!seg && !half && c->opt_wino_split && B >= 2 && L0->ks > 1 && c->opt_precision != 2 && wino_layers_ok(L0, L1)) {
+        const int n0 = wino_split_images(wino_opts(c, k, L0->ks, L1 ? 2 : 1, lda), L0->ks, L0->cin_pad, L0->cout_pad, L0->cout, ldc, B, L1 ? 2 : 1, H, W, pool);
         if (n0 > 0 && n0 < B) {
             const size_t pin = (size_t)n0 * H * W * lda, pout = (size_t)n0 * (pool ? H / 2 : H) * (pool ? W / 2 : W) * ldc;
-            c->split_suffix = "@0+" + std::to_string(n0);
-            rc = run_conv(c, label, L0, L1, in0, in1, lda, out0, out1, ldc, n0, H, W, relu, pool, level);
-            if (!rc) {
-                c->split_suffix = "@" + std::to_string(n0) + "+" + std::to_string(B - n0);
-                rc = run_conv(c, label, L0, L1, in0 + pin, in1 ? in1 + pin : nullptr, lda, out0 + pout, out1 ? out1 + pout : nullptr, ldc, B - n0, H, W, relu, pool, level);
-            }
-            c->split_suffix.clear();
-            return rc;
+            const std::string h0 = "@0+" + std::to_string(n0), h1 = "@" + std::to_string(n0) + "+" + std::to_string(B - n0);
+            if ((rc = run_conv(c, k, label, L0, L1, in0, in1, lda, out0, out1, ldc, n0, H, W, relu, pool, level, h0.c_str()))) return rc;
+            return run_conv(c, k, label, L0, L1, in0 + pin, in1 ? in1 + pin : nullptr, lda, out0 + pout, out1 ? out1 + pout : nullptr, ldc, B - n0, H, W, relu, pool, level,
+                            h1.c_str());
         }
     }
     ConvPlan p;
-    if ((rc = plan_conv(c, p, label, L0, L1, in0, in1, lda, out0, out1, ldc, B, H, W, relu, pool, level))) return rc;
-    return launch_plan(c, p);
+    if ((rc = plan_conv(c, k, p, label, L0, L1, in0, in1, lda, out0, out1, ldc, B, H, W, relu, pool, level))) return rc;
+    if (half && p.prof) p.pf.suffix = half;
+    return launch_plan(c, k, p);
 }
 
 // the two 1x1 layers that end a stage (A: 128 -> cmid + ReLU, B: cmid -> cout [+ ReLU]) as ONE launch when the shapes allow
 // (else, or with option fuse_pairs = 0, as two run_conv launches through `mid`): bit-identical either way
-static int run_pair(pmx_ctx* c, const char* labelA, const char* labelB, PackedLayer* a0, PackedLayer* a1, PackedLayer* b0, PackedLayer* b1,
+static int run_pair(pmx_ctx* c, const FwdCall& k, const char* labelA, const char* labelB, PackedLayer* a0, PackedLayer* a1, PackedLayer* b0, PackedLayer* b1,
                     const float* in0, const float* in1, int lda, float* mid0, float* mid1, int ldm, float* out0, float* out1, int ldc, int B,
                     int H, int W, int reluB, int level = -1, bool keep_mid = false)      // keep_mid: `mid` must hold the middle activation: two launches
 {
     const PackedLayer& LA = *a0;
     const PackedLayer& LB = *b0;
     const int groups = a1 ? 2 : 1;
-    // (heterogeneous forward: a 1x1 layer only sees pixels -- the segments' maps are one run of seg_pix[level] pixels)
-    const bool seg = !c->segs.empty() && level >= 0;
-    const long long npix = seg ? c->seg_pix[level] : (long long)B * H * W;
+    // (heterogeneous forward: a 1x1 layer only sees pixels -- the segments' maps are one run of pix[level] pixels)
+    const bool seg = k.seg && level >= 0;
+    const long long npix = seg ? k.seg->pix[level] : (long long)B * H * W;
     const bool ok = !keep_mid && c->opt_fuse_pairs && c->opt_kernel_gen >= 6 && LA.ks == 1 && LB.ks == 1 && LA.cin_pad == 128 && LB.cin == LA.cout &&
                     conv_pair_supported(LA.cin, LA.cout, LB.cout_pad) && (groups == 1 || b1->cout_pad == LB.cout_pad);
     int rc;
     PMX_CHECK(ok || !seg, PMX_ERR_INVALID, "heterogeneous forward: the 1x1 pair %s + %s has no fused form", labelA, labelB);
     if (!ok) {
-        if ((rc = run_conv(c, labelA, a0, a1, in0, in1, lda, mid0, mid1, ldm, B, H, W, 1, 0))) return rc;
-        return run_conv(c, labelB, b0, b1, mid0, mid1, ldm, out0, out1, ldc, B, H, W, reluB, 0);
+        if ((rc = run_conv(c, k, labelA, a0, a1, in0, in1, lda, mid0, mid1, ldm, B, H, W, 1, 0))) return rc;
+        return run_conv(c, k, labelB, b0, b1, mid0, mid1, ldm, out0, out1, ldc, B, H, W, reluB, 0);
     }
     PairArgs p;
     memset(&p, 0, sizeof p);
@@ -775,10 +775,10 @@ static int run_pair(pmx_ctx* c, const char* labelA, const char* labelB, PackedLa
     p.npix = npix; p.lda = lda; p.ldc = ldc; p.cmid = LA.cout; p.cout_pad = LB.cout_pad; p.relu2 = reluB;
     if (c->prof_on == 1) {
         const std::string kn = "conv1x1_pair_c" + std::to_string(LA.cout) + "_n" + std::to_string(LB.cout_pad);
-        if ((rc = prof_begin(c, std::string(labelA) + "+" + labelB + "|" + kn, flops, 4.0 * (double)npix * groups * (LA.cin + LB.cout)))) return rc;
+        if ((rc = prof_begin(c, k, std::string(labelA) + "+" + labelB + "|" + kn, flops, 4.0 * (double)npix * groups * (LA.cin + LB.cout)))) return rc;
     }
-    if ((rc = conv_pair_launch(p, groups, c->stream))) return rc;
-    return prof_end(c);
+    if ((rc = conv_pair_launch(p, groups, k.stream))) return rc;
+    return prof_end(c, k);
 }
 
 // which form conv1_1 -> conv1_2 (+ pool) takes: *fuse: one launch (direct conv1_2 on 8 x 16 x 64 tiles: large maps); returns true for
@@ -793,13 +793,13 @@ static bool conv1_pairable(const pmx_ctx* c)
 }
 // a forward that retains the trunk (pmx_backward_enable(ctx, 2); the conditions of pmx_forward_from_in16's `keep`): conv1_1 and conv1_2 run
 // as two launches that store both outputs, so neither fused form applies and a uint8 input is preprocessed into in16 first
-static bool trunk_retaining(const pmx_ctx* c)
+static bool trunk_retaining(const pmx_ctx* c, const FwdCall& k)
 {
-    return c->bw.on == 2 && c->kind == NET_POSE && c->ls_on && c->lg_on && c->opt_precision == 0 && c->segs.empty();
+    return c->bw.on == 2 && c->kind == NET_POSE && c->ls_on && c->lg_on && c->opt_precision == 0 && !k.seg;
 }
-static bool conv1_form(const pmx_ctx* c, int B, int H, int W, bool* fuse_out)
+static bool conv1_form(const pmx_ctx* c, const FwdCall& k, int B, int H, int W, bool* fuse_out)
 {
-    if (trunk_retaining(c)) {
+    if (trunk_retaining(c, k)) {
         if (fuse_out) *fuse_out = false;
         return false;
     }
@@ -810,78 +810,78 @@ static bool conv1_form(const pmx_ctx* c, int B, int H, int W, bool* fuse_out)
                       L2.cin == 64 && L2.cout == 64 && !strcmp(conv_variant(v2).name, "conv3x3_v5_t8x16_n64");
     const bool pair_ok = c->opt_precision == 0 && c->opt_force[3] < 0 && L1.cin == 3 && L1.cout == 64 && L2.cin == 64 && L2.cout == 64 && H % 2 == 0 && W % 2 == 0;
     if (fuse_out) *fuse_out = fuse;
-    return pair_ok && c->opt_conv1_wino && c->opt_conv_algo >= 1 &&
+    return pair_ok && c->opt_conv1_wino && k.conv_algo >= 1 &&
            (c->opt_conv1_wino == 2 || (fuse && (long long)B * ((H + 15) / 16) * ((W + 15) / 16) >= c->num_cus));
 }
 
-static int run_conv1(pmx_ctx* c, int B, int H, int W)
+static int run_conv1(pmx_ctx* c, const FwdCall& k, int B, int H, int W)
 {
+    NetBufs& ws = k.ws;
     PackedLayer& L1 = c->layers[c->index.at("conv1_1")];
     PackedLayer& L2 = c->layers[c->index.at("conv1_2")];
     bool fuse = false;
-    const bool seg = !c->segs.empty();
-    const bool wino1 = seg ? conv1_pairable(c) : conv1_form(c, B, H, W, &fuse);
-    const uint8_t* in_u8 = c->in_u8;
-    c->in_u8 = nullptr;                                   // (valid for this forward only)
+    const bool seg = k.seg != nullptr;
+    const bool wino1 = seg ? conv1_pairable(c) : conv1_form(c, k, B, H, W, &fuse);
+    const uint8_t* const in_u8 = k.in_u8;
     PMX_CHECK(!in_u8 || wino1, PMX_ERR_STATE, "conv1: a uint8 input without the kernel that preprocesses it");
     int rc;
     if (seg && c->opt_precision == 2) {
         // f16 mode: pmx_forward_from_u8 has preprocessed the segments' pixels into in16; both layers on the level-0 rectangle tables
         PMX_CHECK(!in_u8, PMX_ERR_STATE, "conv1: a uint8 input in f16 mode");
-        if ((rc = run_conv(c, "conv1_1", &L1, nullptr, c->in16, nullptr, PMX_IN_C, c->act0, nullptr, 64, B, H, W, 1, 0, 0))) return rc;
-        return run_conv(c, "conv1_2", &L2, nullptr, c->act0, nullptr, 64, c->act1, nullptr, 64, B, H, W, 1, 1, 0);
+        if ((rc = run_conv(c, k, "conv1_1", &L1, nullptr, ws.in16, nullptr, PMX_IN_C, ws.act0, nullptr, 64, B, H, W, 1, 0, 0))) return rc;
+        return run_conv(c, k, "conv1_2", &L2, nullptr, ws.act0, nullptr, 64, ws.act1, nullptr, 64, B, H, W, 1, 1, 0);
     }
     PMX_CHECK(!seg || (wino1 && in_u8), PMX_ERR_INVALID, "heterogeneous forward: needs conv1 as conv1_wino_kernel on a uint8 input");
     if (!fuse && !wino1) {
-        if ((rc = run_conv(c, "conv1_1", &L1, nullptr, c->in16, nullptr, PMX_IN_C, c->act0, nullptr, 64, B, H, W, 1, 0))) return rc;
-        return run_conv(c, "conv1_2", &L2, nullptr, c->act0, nullptr, 64, c->act1, nullptr, 64, B, H, W, 1, 1);
+        if ((rc = run_conv(c, k, "conv1_1", &L1, nullptr, ws.in16, nullptr, PMX_IN_C, ws.act0, nullptr, 64, B, H, W, 1, 0))) return rc;
+        return run_conv(c, k, "conv1_2", &L2, nullptr, ws.act0, nullptr, 64, ws.act1, nullptr, 64, B, H, W, 1, 1);
     }
     ConvArgs a;
     memset(&a, 0, sizeof a);
-    a.g[0].in = c->in16; a.g[0].w = L2.d_w; a.g[0].bias = L2.d_b; a.g[0].out = c->act1; a.g[0].cout = L2.cout;
+    a.g[0].in = ws.in16; a.g[0].w = L2.d_w; a.g[0].bias = L2.d_b; a.g[0].out = ws.act1; a.g[0].cout = L2.cout;
     a.g[1].w = L1.d_w; a.g[1].bias = L1.d_b;
     a.B = B; a.H = H; a.W = W; a.lda = PMX_IN_C; a.ldc = 64; a.nch = L2.nch; a.cout_pad = L2.cout_pad; a.relu = 1; a.pool = 1;
     if (wino1) {
-        if ((rc = ensure_wino_pack(c, L2)) || (rc = ensure_conv1_pack(c, L1))) return rc;
+        if ((rc = ensure_wino_pack(k.stream, L2)) || (rc = ensure_conv1_pack(k.stream, L1))) return rc;
         a.g[0].w = L2.d_ww;
         a.g[1].w = L1.d_ww;
         if (in_u8) {                                      // the kernel preprocesses the uint8 batch itself (pmx_forward_from_u8)
             a.g[1].in = reinterpret_cast<const float*>(in_u8);
-            a.kbounds = (unsigned long long)__builtin_bit_cast(unsigned, c->in_div);
+            a.kbounds = (unsigned long long)__builtin_bit_cast(unsigned, k.in_div);
         }
-        if (seg) { a.nseg = (int)c->segs.size(); a.segs = c->d_segs + (size_t)PMX_SEG_CONV1 * c->segs.size(); a.seg_tiles = c->seg_tiles[PMX_SEG_CONV1]; }
+        if (seg) { a.nseg = (int)k.seg->segs.size(); a.segs = k.seg->table(PMX_SEG_CONV1); a.seg_tiles = k.seg->tiles[PMX_SEG_CONV1]; }
         if (c->prof_on == 1) {
-            const double np0 = seg ? (double)c->seg_pix[0] : (double)B * H * W;
+            const double np0 = seg ? (double)k.seg->pix[0] : (double)B * H * W;
             const double f1 = 2.0 * np0 * 9.0 * (double)L1.cout * L1.cin, f2 = 2.0 * np0 * 9.0 * (double)L2.cout * L2.cin;
-            if ((rc = prof_begin(c, "conv1_1+conv1_2|conv_wino1_f2x2_t16x16", f1 + f2, (in_u8 ? 3.0 : 4.0 * 3) * np0 + 4.0 * np0 * (64 / 4), f1 + f2 * 16.0 / 36.0))) return rc;
+            if ((rc = prof_begin(c, k, "conv1_1+conv1_2|conv_wino1_f2x2_t16x16", f1 + f2, (in_u8 ? 3.0 : 4.0 * 3) * np0 + 4.0 * np0 * (64 / 4), f1 + f2 * 16.0 / 36.0))) return rc;
         }
-        if ((rc = conv1_wino_launch(a, c->stream))) return rc;
-        return prof_end(c);
+        if ((rc = conv1_wino_launch(a, k.stream))) return rc;
+        return prof_end(c, k);
     }
     if (c->prof_on == 1) {
         const double flops = 2.0 * B * H * W * 9.0 * ((double)L1.cout * L1.cin + (double)L2.cout * L2.cin);
-        if ((rc = prof_begin(c, "conv1_1+conv1_2|conv1_fused_t8x16_n64", flops, 4.0 * B * H * W * (3 + 64 / 4)))) return rc;
+        if ((rc = prof_begin(c, k, "conv1_1+conv1_2|conv1_fused_t8x16_n64", flops, 4.0 * B * H * W * (3 + 64 / 4)))) return rc;
     }
-    if ((rc = conv1_fused_launch(a, c->stream))) return rc;
-    return prof_end(c);
+    if ((rc = conv1_fused_launch(a, k.stream))) return rc;
+    return prof_end(c, k);
 }
 
 // conv1_1 ... conv4_2, the VGG stem all three networks share (CocoPoseNet.py:136-149, FaceNet.py:78-92): act1 and act0 in turn, the three
 // F.max_pooling_2d fused into conv1_2, conv2_2, conv3_4; the result (1/8 resolution, 512 channels) in act1
 // (level = the resolution level of the layer's input, read only by a heterogeneous forward: pmx_multi.hip)
 // (last_out: where conv4_2 writes instead -- a retaining forward, pmx_backward_enable)
-static int run_stem(pmx_ctx* c, int B, int H, int W, float* last_out = nullptr)
+static int run_stem(pmx_ctx* c, const FwdCall& k, int B, int H, int W, float* last_out = nullptr)
 {
     static const struct { const char* name; int cin, cout, level, pool; } stem[] = {
         {"conv2_1", 64, 128, 1, 0}, {"conv2_2", 128, 128, 1, 1}, {"conv3_1", 128, 256, 2, 0}, {"conv3_2", 256, 256, 2, 0},
         {"conv3_3", 256, 256, 2, 0}, {"conv3_4", 256, 256, 2, 1}, {"conv4_1", 256, 512, 3, 0}, {"conv4_2", 512, 512, 3, 0}};
-    int rc = run_conv1(c, B, H, W);
-    float* in = c->act1;
-    float* out = c->act0;
+    int rc = run_conv1(c, k, B, H, W);
+    float* in = k.ws.act1;
+    float* out = k.ws.act0;
     for (const auto& s : stem) {
         if (rc) break;
         if (last_out && &s == &stem[7]) out = last_out;
-        rc = run_conv(c, s.name, &c->layers[c->index.at(s.name)], nullptr, in, nullptr, s.cin, out, nullptr, s.cout, B, H >> s.level, W >> s.level, 1, s.pool, s.level);
+        rc = run_conv(c, k, s.name, &c->layers[c->index.at(s.name)], nullptr, in, nullptr, s.cin, out, nullptr, s.cout, B, H >> s.level, W >> s.level, 1, s.pool, s.level);
         std::swap(in, out);
     }
     return rc;
@@ -890,51 +890,52 @@ static int run_stem(pmx_ctx* c, int B, int H, int W, float* last_out = nullptr)
 // The stem of a forward that retains the trunk (BwState in pmx_ctx.h; include/pose_mi355x.h: pmx_backward_enable, mode 2): every layer
 // writes its post-ReLU output into its slot of the trunk store with its own launch, the three pooling layers un-pooled, and
 // maxpool_nhwc_kernel writes the pooled map the next layer reads.  conv4_2 writes x42, as in mode 1.
-static int run_stem_retaining(pmx_ctx* c, int B, int H, int W, float* x42)
+static int run_stem_retaining(pmx_ctx* c, const FwdCall& k, int B, int H, int W, float* x42)
 {
     BwState& bw = c->bw;
-    PMX_CHECK(!c->in_u8, PMX_ERR_STATE, "retaining stem: a uint8 input that no kernel preprocesses");
+    PMX_CHECK(!k.in_u8, PMX_ERR_STATE, "retaining stem: a uint8 input that no kernel preprocesses");
     PMX_CHECK((size_t)B * H * W <= bw.cap_px * 64, PMX_ERR_CAPACITY, "forward: %d x %d x %d input pixels, the trunk store holds %zu", B, H, W, bw.cap_px * 64);
-    const float* in = c->in16;
+    const float* in = k.ws.in16;
     int lda = PMX_IN_C, pools = 0, rc;
     for (int t = 0; t < PMX_TRUNK_LAYERS; ++t) {
         const TrunkDesc& d = pmx_trunk_desc[t];
         const int h = H >> d.level, w = W >> d.level;
         float* out = t == PMX_TRUNK_LAYERS - 1 ? x42 : bw.t_act + bw.t_a_off[t];
-        if ((rc = run_conv(c, d.name, &c->layers[bw.t_layer[t]], nullptr, in, nullptr, lda, out, nullptr, d.cout, B, h, w, 1, 0, d.level))) return rc;
+        if ((rc = run_conv(c, k, d.name, &c->layers[bw.t_layer[t]], nullptr, in, nullptr, lda, out, nullptr, d.cout, B, h, w, 1, 0, d.level))) return rc;
         in = out; lda = d.cout;
         if (!d.pool) continue;
         float* pooled = bw.t_act + bw.t_p_off[pools++];
         if (c->prof_on == 1) {
             const std::string label = std::string("pool:") + d.name + "|maxpool_nhwc";
-            if ((rc = prof_begin(c, label, 0, 4.0 * B * h * w * d.cout * 1.25))) return rc;
+            if ((rc = prof_begin(c, k, label, 0, 4.0 * B * h * w * d.cout * 1.25))) return rc;
         }
-        if ((rc = maxpool_nhwc_launch(out, d.cout, pooled, d.cout, B, h, w, d.cout, c->stream))) return rc;
-        if ((rc = prof_end(c))) return rc;
+        if ((rc = maxpool_nhwc_launch(out, d.cout, pooled, d.cout, B, h, w, d.cout, k.stream))) return rc;
+        if ((rc = prof_end(c, k))) return rc;
         in = pooled;
     }
     return PMX_OK;
 }
 
 // FaceNet / HandNet forward (models/FaceNet.py:78-160): one branch, groups = 1 everywhere
-static int forward_cpm(pmx_ctx* c, int B, int H, int W)
+static int forward_cpm(pmx_ctx* c, const FwdCall& k, int B, int H, int W)
 {
+    NetBufs& ws = k.ws;
     auto L = [&](const char* n) { return &c->layers[c->index.at(n)]; };
     int rc;
     const int H8 = H / 8, W8 = W / 8;
     const int CC = c->cat_c;
-    float* cat = c->cat;
+    float* cat = ws.cat;
     float* heat = cat + c->cat_heat;
 #define RUN1(name, in, lda, out, ldc) \
-    do { if ((rc = run_conv(c, name, L(name), nullptr, in, nullptr, lda, out, nullptr, ldc, B, H8, W8, 1, 0))) return rc; } while (0)
-    if ((rc = run_stem(c, B, H, W))) return rc;
-    RUN1("conv4_3", c->act1, 512, c->act0, 512);
-    RUN1("conv4_4", c->act0, 512, c->act1, 512);
-    RUN1("conv5_1", c->act1, 512, c->act0, 512);
-    RUN1("conv5_2", c->act0, 512, c->act1, 512);
-    RUN1("conv5_3_CPM", c->act1, 512, cat, CC);               // feature_map -> cat[:, 0:128]
+    do { if ((rc = run_conv(c, k, name, L(name), nullptr, in, nullptr, lda, out, nullptr, ldc, B, H8, W8, 1, 0))) return rc; } while (0)
+    if ((rc = run_stem(c, k, B, H, W))) return rc;
+    RUN1("conv4_3", ws.act1, 512, ws.act0, 512);
+    RUN1("conv4_4", ws.act0, 512, ws.act1, 512);
+    RUN1("conv5_1", ws.act1, 512, ws.act0, 512);
+    RUN1("conv5_2", ws.act0, 512, ws.act1, 512);
+    RUN1("conv5_3_CPM", ws.act1, 512, cat, CC);               // feature_map -> cat[:, 0:128]
     // conv6_1_CPM (reads the 128 feature channels) -> conv6_2_CPM (stage-1 heat maps -> cat[:, 128:128+C])
-    if ((rc = run_pair(c, "conv6_1_CPM", "conv6_2_CPM", L("conv6_1_CPM"), nullptr, L("conv6_2_CPM"), nullptr, cat, nullptr, CC, c->brT, nullptr, 512,
+    if ((rc = run_pair(c, k, "conv6_1_CPM", "conv6_2_CPM", L("conv6_1_CPM"), nullptr, L("conv6_2_CPM"), nullptr, cat, nullptr, CC, ws.brT, nullptr, 512,
                        heat, nullptr, CC, B, H8, W8, 0))) return rc;
     char nm[48], nm2[48];
     for (int s = 2; s <= 6 && s <= c->opt_stop_stage; ++s) {
@@ -942,14 +943,14 @@ static int forward_cpm(pmx_ctx* c, int B, int H, int W)
             snprintf(nm, sizeof nm, "Mconv%d_stage%d", i, s);
             const float* in; float* out; int lda;
             if (i == 1) { in = cat; lda = CC; }
-            else if (i % 2 == 0) { in = c->brA; lda = 128; }
-            else { in = c->brB; lda = 128; }
-            out = i % 2 == 1 ? c->brA : c->brB;
+            else if (i % 2 == 0) { in = ws.brA; lda = 128; }
+            else { in = ws.brB; lda = 128; }
+            out = i % 2 == 1 ? ws.brA : ws.brB;
             RUN1(nm, in, lda, out, 128);
         }
         snprintf(nm, sizeof nm, "Mconv6_stage%d", s);
         snprintf(nm2, sizeof nm2, "Mconv7_stage%d", s);
-        if ((rc = run_pair(c, nm, nm2, L(nm), nullptr, L(nm2), nullptr, c->brA, nullptr, 128, c->brB, nullptr, 128, heat, nullptr, CC, B, H8, W8, 0)))
+        if ((rc = run_pair(c, k, nm, nm2, L(nm), nullptr, L(nm2), nullptr, ws.brA, nullptr, 128, ws.brB, nullptr, 128, heat, nullptr, CC, B, H8, W8, 0)))
             return rc;
     }
 #undef RUN1
@@ -960,16 +961,19 @@ static int forward_cpm(pmx_ctx* c, int B, int H, int W)
     return PMX_OK;
 }
 
-int pmx_forward_from_in16(pmx_ctx* c, int B, int H, int W)
+int pmx_forward_from_in16(pmx_ctx* c, const FwdCall& k, int B, int H, int W)
 {
-    PMX_CHECK(c->segs.empty() || c->kind == NET_POSE, PMX_ERR_INVALID, "heterogeneous forward: posenet only");
-    if (c->kind != NET_POSE) return forward_cpm(c, B, H, W);
+    PMX_CHECK(!k.seg || c->kind == NET_POSE, PMX_ERR_INVALID, "heterogeneous forward: posenet only");
+    if (c->kind != NET_POSE) return forward_cpm(c, k, B, H, W);
+    NetBufs& ws = k.ws;
     auto L = [&](const char* n) { return &c->layers[c->index.at(n)]; };
     int rc;
     const int H8 = H / 8, W8 = W / 8;
-#define RUN(...) do { if ((rc = run_conv(c, __VA_ARGS__))) return rc; } while (0)
+#define RUN(...) do { if ((rc = run_conv(c, k, __VA_ARGS__))) return rc; } while (0)
     // validation-loss hook (pmx_loss.hip; uniform batches): the stage's outputs lie in the cat slices until the next stage's last launch
-    const bool hook = c->ls_on && c->segs.empty();
+    const bool hook = c->ls_on && !k.seg;
+    // (the hook and the retention read the context's own cat slices on the context's stream)
+    PMX_CHECK(!hook || (&ws == static_cast<NetBufs*>(c) && k.stream == c->stream), PMX_ERR_STATE, "forward: the validation-loss hook covers the context's own working set only");
     // retention (pmx_backward_enable; include/pose_mi355x.h): every layer writes where the backward will read it -- the slots of c->bw.act
     // instead of act1 / act0 / brA / brB / brT (same leading dimensions: same plans, same bits), the 1x1 pairs unfused
     BwState& bw = c->bw;
@@ -977,28 +981,28 @@ int pmx_forward_from_in16(pmx_ctx* c, int B, int H, int W)
     bw.valid = bw.done = bw.trunk_done = false;
     const long long npix8 = (long long)B * H8 * W8;
     PMX_CHECK(!keep || (size_t)npix8 <= bw.cap_px, PMX_ERR_CAPACITY, "forward: %lld map pixels, the backward store holds %zu", npix8, bw.cap_px);
-    auto slot = [&](int k, float* else_) { return keep ? bw.act + bw.slot[k].a_off : else_; };
-    float* const x42 = slot(PMX_BW_X42, c->act1);
-    float* const a43 = slot(PMX_BW_C43, c->act0);
-    auto keep_stage = [&](int k) {      // the stage's 57 (64) channels of cat -> the store
-        return keep ? bwd_copy_cols_launch(c->cat + PMX_CAT_PAF, PMX_CAT_C, bw.act + bw.slot[k].a_off, 64, npix8, 64, c->stream) : PMX_OK;
+    auto slot = [&](int sl, float* else_) { return keep ? bw.act + bw.slot[sl].a_off : else_; };
+    float* const x42 = slot(PMX_BW_X42, ws.act1);
+    float* const a43 = slot(PMX_BW_C43, ws.act0);
+    auto keep_stage = [&](int sl) {      // the stage's 57 (64) channels of cat -> the store
+        return keep ? bwd_copy_cols_launch(ws.cat + PMX_CAT_PAF, PMX_CAT_C, bw.act + bw.slot[sl].a_off, 64, npix8, 64, k.stream) : PMX_OK;
     };
     // stem (CocoPoseNet.py:136-151)
     // (the last argument = the resolution level, read only by a heterogeneous forward: pmx_multi.hip)
-    if ((rc = keep && bw.on == 2 ? run_stem_retaining(c, B, H, W, x42) : run_stem(c, B, H, W, keep ? x42 : nullptr))) return rc;
+    if ((rc = keep && bw.on == 2 ? run_stem_retaining(c, k, B, H, W, x42) : run_stem(c, k, B, H, W, keep ? x42 : nullptr))) return rc;
     RUN("conv4_3_CPM", L("conv4_3_CPM"), nullptr, x42, nullptr, 512, a43, nullptr, 256, B, H8, W8, 1, 0, 3);
-    RUN("conv4_4_CPM", L("conv4_4_CPM"), nullptr, a43, nullptr, 256, c->cat + PMX_CAT_FEAT, nullptr, PMX_CAT_C, B, H8, W8, 1, 0, 3);
+    RUN("conv4_4_CPM", L("conv4_4_CPM"), nullptr, a43, nullptr, 256, ws.cat + PMX_CAT_FEAT, nullptr, PMX_CAT_C, B, H8, W8, 1, 0, 3);
     // stage 1 (CocoPoseNet.py:154-165); L1 = PAF branch, L2 = heat-map branch
-    float* cat = c->cat;
-    float* const s51 = slot(PMX_BW_S1 + 0, c->brA);
-    float* const s52 = slot(PMX_BW_S1 + 1, c->brB);
-    float* const s53 = slot(PMX_BW_S1 + 2, c->brA);
-    float* const s54 = slot(PMX_BW_S1 + 3, c->brT);
+    float* cat = ws.cat;
+    float* const s51 = slot(PMX_BW_S1 + 0, ws.brA);
+    float* const s52 = slot(PMX_BW_S1 + 1, ws.brB);
+    float* const s53 = slot(PMX_BW_S1 + 2, ws.brA);
+    float* const s54 = slot(PMX_BW_S1 + 3, ws.brT);
     RUN("conv5_1_CPM", L("conv5_1_CPM_L1"), L("conv5_1_CPM_L2"), cat, cat, PMX_CAT_C, s51, s51 + 128, 256, B, H8, W8, 1, 0, 3);
     RUN("conv5_2_CPM", L("conv5_2_CPM_L1"), L("conv5_2_CPM_L2"), s51, s51 + 128, 256, s52, s52 + 128, 256, B, H8, W8, 1, 0, 3);
     RUN("conv5_3_CPM", L("conv5_3_CPM_L1"), L("conv5_3_CPM_L2"), s52, s52 + 128, 256, s53, s53 + 128, 256, B, H8, W8, 1, 0, 3);
     // conv5_4 (128 -> 512, ReLU) -> conv5_5 (512 -> 38 | 19): one launch
-    if ((rc = run_pair(c, "conv5_4_CPM", "conv5_5_CPM", L("conv5_4_CPM_L1"), L("conv5_4_CPM_L2"), L("conv5_5_CPM_L1"), L("conv5_5_CPM_L2"),
+    if ((rc = run_pair(c, k, "conv5_4_CPM", "conv5_5_CPM", L("conv5_4_CPM_L1"), L("conv5_4_CPM_L2"), L("conv5_5_CPM_L1"), L("conv5_5_CPM_L2"),
                        s53, s53 + 128, 256, s54, s54 + 512, 1024, cat + PMX_CAT_PAF, cat + PMX_CAT_HEAT, PMX_CAT_C, B, H8, W8, 0, 3, keep)))
         return rc;
     int n_stages = 1;
@@ -1012,7 +1016,7 @@ int pmx_forward_from_in16(pmx_ctx* c, int B, int H, int W)
             snprintf(n1, sizeof n1, "Mconv%d_stage%d_L1", i, s);
             snprintf(n2, sizeof n2, "Mconv%d_stage%d_L2", i, s);
             snprintf(lab, sizeof lab, "Mconv%d_stage%d", i, s);
-            float* const o = slot(PMX_BW_M(s, i), i % 2 == 1 ? c->brA : c->brB);
+            float* const o = slot(PMX_BW_M(s, i), i % 2 == 1 ? ws.brA : ws.brB);
             if (i == 1) RUN(lab, L(n1), L(n2), cat, cat, PMX_CAT_C, o, o + 128, 256, B, H8, W8, 1, 0, 3);
             else RUN(lab, L(n1), L(n2), in, in + 128, 256, o, o + 128, 256, B, H8, W8, 1, 0, 3);
             in = o;
@@ -1021,8 +1025,8 @@ int pmx_forward_from_in16(pmx_ctx* c, int B, int H, int W)
         snprintf(n1, sizeof n1, "Mconv6_stage%d_L1", s); snprintf(n2, sizeof n2, "Mconv6_stage%d_L2", s);
         snprintf(m1, sizeof m1, "Mconv7_stage%d_L1", s); snprintf(m2, sizeof m2, "Mconv7_stage%d_L2", s);
         snprintf(lab, sizeof lab, "Mconv6_stage%d", s); snprintf(lab2, sizeof lab2, "Mconv7_stage%d", s);
-        float* const m6 = slot(PMX_BW_M(s, 6), c->brB);
-        if ((rc = run_pair(c, lab, lab2, L(n1), L(n2), L(m1), L(m2), in, in + 128, 256, m6, m6 + 128, 256,
+        float* const m6 = slot(PMX_BW_M(s, 6), ws.brB);
+        if ((rc = run_pair(c, k, lab, lab2, L(n1), L(n2), L(m1), L(m2), in, in + 128, 256, m6, m6 + 128, 256,
                            cat + PMX_CAT_PAF, cat + PMX_CAT_HEAT, PMX_CAT_C, B, H8, W8, 0, 3, keep))) return rc;
         n_stages = s;
         if (hook && (rc = pmx_loss_stage(c, s, B, H8, W8))) return rc;
@@ -1033,7 +1037,7 @@ int pmx_forward_from_in16(pmx_ctx* c, int B, int H, int W)
 #undef RUN
     c->maps_valid = true; c->maps_external = false;
     c->cur_B = B; c->cur_fh = H8; c->cur_fw = W8;
-    c->cur_segs = c->segs;           // (empty for a uniform batch)
+    c->cur_segs.clear();             // (a heterogeneous forward: forward_segments installs the layout of its tables)
     c->pp_valid = false;
     return PMX_OK;
 }
@@ -1066,33 +1070,32 @@ extern "C" int pmx_forward_u8(pmx_ctx* c, const uint8_t* img, int B, int H, int 
         PMX_HIP(hipMemcpyAsync(c->u8_tmp, img, (size_t)B * H * W * 3, hipMemcpyHostToDevice, c->stream));
         d = c->u8_tmp;
     }
-    return pmx_forward_from_u8(c, d, B, H, W, c->kind == NET_POSE ? 255.0f : 256.0f);
+    return pmx_forward_from_u8(c, pmx_call(c), d, B, H, W, c->kind == NET_POSE ? 255.0f : 256.0f);
 }
 
-int pmx_forward_from_u8(pmx_ctx* c, const uint8_t* d, int B, int H, int W, float divisor)
+int pmx_forward_from_u8(pmx_ctx* c, const FwdCall& k, const uint8_t* d, int B, int H, int W, float divisor)
 {
     int rc;
-    if (!c->segs.empty() && c->opt_precision == 2) {
+    if (k.seg && c->opt_precision == 2) {
         // f16 mode, heterogeneous forward: the segments' uint8 pixels lie end to end in `d` (forward_segments), so the preprocessing is one
-        // per-pixel pass over the flat run of seg_pix[0] pixels; conv1_1 then reads in16 through the level-0 rectangle table
-        const long long np0 = c->seg_pix[0];
+        // per-pixel pass over the flat run of pix[0] pixels; conv1_1 then reads in16 through the level-0 rectangle table
+        const long long np0 = k.seg->pix[0];
         PMX_CHECK(np0 >= 1 && np0 <= (long long)c->max_batch * c->max_h * c->max_w && np0 < (1ll << 31), PMX_ERR_CAPACITY,
                   "heterogeneous forward: %lld input pixels", np0);
-        if (c->prof_on == 1 && (rc = prof_begin(c, "prep_u8|prep_u8", 0, (double)np0 * (3 + 64)))) return rc;
-        if ((rc = launch_prep_u8(d, c->in16, 1, 1, (int)np0, divisor, c->stream))) return rc;
-        if ((rc = prof_end(c))) return rc;
-        return pmx_forward_from_in16(c, B, H, W);
+        if (c->prof_on == 1 && (rc = prof_begin(c, k, "prep_u8|prep_u8", 0, (double)np0 * (3 + 64)))) return rc;
+        if ((rc = launch_prep_u8(d, k.ws.in16, 1, 1, (int)np0, divisor, k.stream))) return rc;
+        if ((rc = prof_end(c, k))) return rc;
+        return pmx_forward_from_in16(c, k, B, H, W);
     }
-    if (!c->segs.empty() || conv1_form(c, B, H, W, nullptr)) {                // conv1_wino_kernel reads the uint8 pixels and preprocesses them in its patch load
-        c->in_u8 = d; c->in_div = divisor;
-        rc = pmx_forward_from_in16(c, B, H, W);
-        c->in_u8 = nullptr;
-        return rc;
+    if (k.seg || conv1_form(c, k, B, H, W, nullptr)) {                        // conv1_wino_kernel reads the uint8 pixels and preprocesses them in its patch load
+        FwdCall ku = k;
+        ku.in_u8 = d; ku.in_div = divisor;
+        return pmx_forward_from_in16(c, ku, B, H, W);
     }
-    if (c->prof_on == 1 && (rc = prof_begin(c, "prep_u8|prep_u8", 0, (double)B * H * W * (3 + 64)))) return rc;
-    if ((rc = launch_prep_u8(d, c->in16, B, H, W, divisor, c->stream))) return rc;
-    if ((rc = prof_end(c))) return rc;
-    return pmx_forward_from_in16(c, B, H, W);
+    if (c->prof_on == 1 && (rc = prof_begin(c, k, "prep_u8|prep_u8", 0, (double)B * H * W * (3 + 64)))) return rc;
+    if ((rc = launch_prep_u8(d, k.ws.in16, B, H, W, divisor, k.stream))) return rc;
+    if ((rc = prof_end(c, k))) return rc;
+    return pmx_forward_from_in16(c, k, B, H, W);
 }
 
 extern "C" int pmx_forward_f32(pmx_ctx* c, const float* x, int B, int H, int W, int on_device)
@@ -1106,7 +1109,7 @@ extern "C" int pmx_forward_f32(pmx_ctx* c, const float* x, int B, int H, int W, 
         d = c->nchw_tmp;
     }
     if ((rc = launch_prep_f32(d, c->in16, B, H, W, c->stream))) return rc;
-    return pmx_forward_from_in16(c, B, H, W);
+    return pmx_forward_from_in16(c, pmx_call(c), B, H, W);
 }
 
 // OpenCV INTER_LINEAR uint8 tables for one axis: [idx0 | idx1 | coef0 | coef1], each `dst` ints.
@@ -1156,9 +1159,9 @@ extern "C" int pmx_forward_u8_resized(pmx_ctx* c, const uint8_t* img, int B, int
         PMX_HIP(hipMemcpy(c->rs_tab, tab.data(), ntab * sizeof(int), hipMemcpyHostToDevice));
         memcpy(c->rs_key, key, sizeof key);
     }
-    if (c->prof_on == 1 && (rc = prof_begin(c, "resize_u8|resize_linear_u8", 0, (double)nsrc + (double)B * h * w * 3))) return rc;
+    if ((rc = pmx_prof_begin(c, "resize_u8|resize_linear_u8", (double)nsrc + (double)B * h * w * 3))) return rc;
     if ((rc = launch_resize_linear_u8(d, c->u8_tmp, c->rs_tab, c->rs_tab + 4 * w, B, src_h, src_w, h, w, c->stream))) return rc;
-    if ((rc = prof_end(c))) return rc;
+    if ((rc = pmx_prof_end(c))) return rc;
     return pmx_forward_u8(c, c->u8_tmp, B, h, w, 1);
 }
 
@@ -1762,14 +1765,15 @@ extern "C" int pmx_conv2d(pmx_ctx* c, const float* x, const float* w, const floa
     // poison the output so that unwritten elements are caught by the test
     PMX_HIP(hipMemsetAsync(d_yn, 0xFF, ny * 4, c->stream));
     if ((rc = test_upload(c, x, d_x, d_xn, B, cin, H, W, L.cin_pad, 0))) return rc;
+    const FwdCall k = pmx_call(c);
     ConvPlan p;
-    if ((rc = plan_conv(c, p, nullptr, &L, nullptr, d_xn, nullptr, L.cin_pad, d_yn, nullptr, cout, B, H, W, relu, pool, -1))) return rc;
-    rc = launch_plan(c, p);
+    if ((rc = plan_conv(c, k, p, nullptr, &L, nullptr, d_xn, nullptr, L.cin_pad, d_yn, nullptr, cout, B, H, W, relu, pool, -1))) return rc;
+    rc = launch_plan(c, k, p);
     if (!rc && iters > 0) {
         Event e0, e1;
         if ((rc = e0.create(hipEventDefault)) || (rc = e1.create(hipEventDefault))) return rc;
         PMX_HIP(hipEventRecord(e0, c->stream));
-        for (int i = 0; i < iters && !rc; ++i) rc = launch_plan(c, p);
+        for (int i = 0; i < iters && !rc; ++i) rc = launch_plan(c, k, p);
         PMX_HIP(hipEventRecord(e1, c->stream));
         PMX_HIP(hipEventSynchronize(e1));
         float ms = 0.f;
@@ -1809,10 +1813,11 @@ extern "C" int pmx_conv2d_pair(pmx_ctx* c, const float* x0, const float* x1, con
         PMX_HIP(hipStreamSynchronize(c->stream));                               // (d_x is staged into again)
         if ((rc = test_upload(c, x1, d_x, d_xn, B, cin, H, W, lda, ioff[1]))) return rc;
     }
+    const FwdCall k = pmx_call(c);
     ConvPlan p;
-    if ((rc = plan_conv(c, p, nullptr, &L[0], &L[1], d_xn.get() + ioff[0], d_xn.get() + ioff[1], lda, d_yn.get() + ooff[0], d_yn.get() + ooff[1], ldc,
+    if ((rc = plan_conv(c, k, p, nullptr, &L[0], &L[1], d_xn.get() + ioff[0], d_xn.get() + ioff[1], lda, d_yn.get() + ooff[0], d_yn.get() + ooff[1], ldc,
                         B, H, W, relu, pool, -1))) return rc;
-    if ((rc = launch_plan(c, p))) return rc;
+    if ((rc = launch_plan(c, k, p))) return rc;
     if ((rc = test_fetch(c, "pmx_conv2d_pair", d_yn, d_y, y0, B, cout0, Ho, Wo, ldc, ooff[0]))) return rc;
     return test_fetch(c, "pmx_conv2d_pair", d_yn, d_y, y1, B, cout1, Ho, Wo, ldc, ooff[1]);
 }
@@ -1847,12 +1852,13 @@ extern "C" int pmx_conv2d_backward(pmx_ctx* c, const float* x, const float* w, c
         PMX_HIP(hipMemsetAsync(dst, 0, npix * ld * 4, c->stream));
         return launch_nchw_to_nhwc(d_x, dst, B, cin, H, W, ld, 0, c->stream);
     };
+    const FwdCall k = pmx_call(c);
     ConvPlan pz, pt;
     if (need_z) {
         if ((rc = test_layer(c, L, w, bias, cout, cin, ks)) || (rc = to_nhwc(d_xn, L.cin_pad)) || (rc = d_zn.alloc(nz))) return rc;
         PMX_HIP(hipMemsetAsync(d_zn, 0xFF, nz * 4, c->stream));
-        if ((rc = plan_conv(c, pz, nullptr, &L, nullptr, d_xn, nullptr, L.cin_pad, d_zn, nullptr, cout, B, H, W, 0, 0, -1))) return rc;
-        if ((rc = launch_plan(c, pz))) return rc;
+        if ((rc = plan_conv(c, k, pz, nullptr, &L, nullptr, d_xn, nullptr, L.cin_pad, d_zn, nullptr, cout, B, H, W, 0, 0, -1))) return rc;
+        if ((rc = launch_plan(c, k, pz))) return rc;
     }
     if (need_g) {
         if ((rc = d_dy.alloc(ndy)) || (rc = d_g.alloc(npix * cg))) return rc;
@@ -1868,7 +1874,7 @@ extern "C" int pmx_conv2d_backward(pmx_ctx* c, const float* x, const float* w, c
         Lt.set = true;
         PMX_HIP(hipMemsetAsync(d_dxn, 0xFF, nx * 4, c->stream));       // poison: an unwritten element is caught by the test
         // g has cg >= Lt.cin_pad channels per pixel, the padding channels zero
-        if ((rc = plan_conv(c, pt, nullptr, &Lt, nullptr, d_g, nullptr, cg, d_dxn, nullptr, cin, B, H, W, 0, 0, -1))) return rc;
+        if ((rc = plan_conv(c, k, pt, nullptr, &Lt, nullptr, d_g, nullptr, cg, d_dxn, nullptr, cin, B, H, W, 0, 0, -1))) return rc;
     }
     int strips = 0, rows = 0;
     if (dw) {
@@ -1882,7 +1888,7 @@ extern "C" int pmx_conv2d_backward(pmx_ctx* c, const float* x, const float* w, c
         if (int r = conv_bwd_mask_launch(d_dy, d_zn, cout, d_g, B, H, W, cout, cg, relu, pool, c->stream)) return r;
         return db ? conv_bwd_db_launch(d_g, cg, d_part, d_db, (long long)npix, cout, cg, c->stream) : PMX_OK;
     };
-    auto data_grad = [&]() -> int { return dx ? launch_plan(c, pt) : PMX_OK; };
+    auto data_grad = [&]() -> int { return dx ? launch_plan(c, k, pt) : PMX_OK; };
     auto weight_grad = [&]() -> int {
         return dw ? conv_wgrad_launch(d_g, cg, d_x32, cx, d_ws, d_dw, B, H, W, cout, cg, cin, cx, ks, strips, rows, nullptr, c->stream) : PMX_OK;
     };
@@ -1928,7 +1934,7 @@ extern "C" int pmx_conv2d_backward(pmx_ctx* c, const float* x, const float* w, c
 int pmx_run_conv(pmx_ctx* c, const char* label, PackedLayer* L0, PackedLayer* L1, const float* in0, const float* in1, int lda, float* out0,
                  float* out1, int ldc, int B, int H, int W, int relu)
 {
-    return run_conv(c, label, L0, L1, in0, in1, lda, out0, out1, ldc, B, H, W, relu, 0);
+    return run_conv(c, pmx_call(c), label, L0, L1, in0, in1, lda, out0, out1, ldc, B, H, W, relu, 0);
 }
 
 // The layer whose forward is the data gradient of table layer `layer` (pack_index.h: the transposed pack), packed like any layer, from the

@@ -151,21 +151,29 @@ struct ProfEntry {
 };
 struct ProfPending { int entry; Event e0, e1; };
 
+// The working set of one network forward: the padded float input, the activation ping-pong, the concat buffer and the branch buffers, the
+// uint8 network input, detect_precise's up-sampled maps of one scale (planar [n][38][ph][pw] | [n][19][ph][pw]) and the partial-sum
+// slabs of the split-K / unit-mode launches.  The context is one (its own: every forward that does not run on a lane, and what the
+// post-process, the loss, the backward and the box code mean by c->cat, c->act1, ...); every lane of detect_precise holds another.
+struct NetBufs {
+    DevBuf<float> in16, act0, act1, cat, brA, brB, brT;
+    DevBuf<uint8_t> u8_tmp;
+    DevBuf<float> pr_tmp, sk_scratch;
+};
+
 // detect_precise runs its inference scales CONCURRENTLY: one image at 0.5x / 1x / 1.5x is 12 ... 108 one-per-CU blocks per layer for 256
-// CUs, so the four forward passes go to four streams ("lanes"), each with its own working set; a lane's fields are swapped into the
-// context while its scale is enqueued (the forward code keeps using c->stream / c->act0 / ...).  The first scale enqueued in a
+// CUs, so the four forward passes go to four streams ("lanes"), each with its own working set; the forward of a scale is handed its
+// lane's set and stream in its FwdCall, the context's own stay what they are.  The first scale enqueued in a
 // sequence runs on lane 3 (highest stream priority), the others round-robin on the remaining lanes in use (pmx_precise.hip); the scale in
 // slot k leaves its maps, resized to the original size, in pr_part[k]; pmx_precise_finish adds the parts IN SLOT ORDER
 // (the reference's left-to-right sum, pose_detector.py:463,467) and divides.
 constexpr int PMX_PR_LANES = 4;
 constexpr int PMX_SK_ZERO_BIAS = 1024;      // floats of the shared zero-bias vector of the split-K / unit-mode launches
 struct PrLane {
-    Stream stream;                           // lanes 1 .. 3 (lane 0 runs on the context's stream)
+    Stream stream;                           // lanes 1 .. 3 (lane 0 runs on the context's stream, in the context's own set)
     Event done;
-    DevBuf<float> in16, act0, act1, cat, brA, brB, brT;
-    DevBuf<uint8_t> u8_tmp;
+    NetBufs ws;
     size_t cap_px = 0;                       // n * padded_h * padded_w the activation buffers hold
-    DevBuf<float> pr_tmp, sk_scratch;
 };
 
 // Heterogeneous batches (pmx_multi.hip): a SEGMENT = n images of one network-input size.  The segments of a forward lie end to end in
@@ -181,6 +189,25 @@ enum { PMX_SEG_CONV1 = 0, PMX_SEG_L1 = 1, PMX_SEG_L1P = 2, PMX_SEG_L2 = 3, PMX_S
                                    : (level) == 2 ? ((pool) ? PMX_SEG_L2P : PMX_SEG_L2) : PMX_SEG_L3)
 // the host description of one segment: n images of network input H x W (mh x mw: the up-sampled map size of pmx_detect_images, else 0)
 struct SegGeo { int n, H, W, mh, mw; };
+// the segment tables of ONE heterogeneous forward (build_seg_tables): the segments, tiles per launch per table, pixels of all segments per
+// level, and the device tables -- PMX_SEG_TABLES tables of segs.size() entries in c->d_segs, valid until the next build
+struct SegTables {
+    std::vector<SegDesc> segs;
+    int tiles[PMX_SEG_TABLES] = {};
+    long long pix[4] = {};
+    const ConvSeg* dev = nullptr;
+    const ConvSeg* table(int t) const { return dev + (size_t)t * segs.size(); }
+};
+// What one network forward runs on and over, handed from its entry down to every launch by const reference: nothing a forward needs to
+// know about its own call is a member of the context.  pmx_call(c) is the call of everything that runs on the context itself.
+struct FwdCall {
+    NetBufs& ws;                     // the working set: the context's own or a lane's
+    hipStream_t stream;              // what every launch and profile event of the forward is enqueued on
+    int conv_algo;                   // option "conv_algo" for this forward
+    const SegTables* seg = nullptr;  // a heterogeneous forward: its tables (null: a uniform batch)
+    const uint8_t* in_u8 = nullptr;  // conv1_wino_kernel preprocesses this uint8 batch itself (null: the float input in ws.in16)
+    float in_div = 255.0f;           // ... dividing by this
+};
 // one post-process launch set of the current results: a uniform batch is one call (base 0), a mixed batch one per segment
 struct PPCall { PPMaps maps; PPTables tab; int base, B, map_h, map_w; double img_len; bool has_scale; int limbs_slices; };
 
@@ -248,13 +275,10 @@ struct TrainState {
 };
 
 // ------------------------------------------------------------------------------------------- context
-struct pmx_ctx {
-    // heterogeneous forward / post-process state
-    std::vector<SegDesc> segs;       // non-empty only WHILE a heterogeneous forward is being enqueued (run_conv / run_pair / run_conv1 look at it)
+struct pmx_ctx : NetBufs {           // (the base: the context's own working set)
+    // heterogeneous forward / post-process state.  Whether a forward is heterogeneous is a property of its FwdCall (seg), not of the context
     std::vector<SegDesc> cur_segs;   // layout of the current network output when it came from a heterogeneous forward (else empty)
-    DevBuf<ConvSeg> d_segs;                               // device: PMX_SEG_TABLES tables of segs.size() entries
-    int seg_tiles[PMX_SEG_TABLES] = {};                   // tiles per launch, per table
-    long long seg_pix[4] = {};                            // pixels of all segments, per level
+    DevBuf<ConvSeg> d_segs;                               // device: the tables of the last build_seg_tables (SegTables::dev points here)
     std::vector<PPCall> pp_calls;                         // non-empty: the post-process of the current results ran per segment
     // table sets per (in_h, in_w, out_h, out_w) of the per-segment calls: the kernel-argument struct and the one allocation [grid | taps] it points into
     std::map<std::tuple<int, int, int, int>, std::pair<PPTables, DevBuf<char>>> tab_cache;
@@ -276,10 +300,9 @@ struct pmx_ctx {
     // detect_precise accumulation state (pmx_precise_*)
     int pr_h = 0, pr_w = 0, pr_scales = 0, pr_n = 0;      // original size, scales accumulated so far, images of the batch
     unsigned pr_mask = 0;                                 // slots (positions in the reference's scale loop) filled so far
-    DevBuf<float> pr_tmp;                                // x8 up-sampled maps of one scale, planar [n][38][ph][pw] | [n][19][ph][pw]
     std::map<std::tuple<int, int, int>, DevBuf<int>> pr_tabs; // cubic tables per axis, keyed (src, dst, fixed point?): built once, kept
     const uint8_t* pr_src = nullptr;                     // host images of the current begin / finish sequence already in u8_src
-    PrLane pr_lane[PMX_PR_LANES];                        // lanes 1 .. : own buffers; lane 0 = the context's own stream and buffers
+    PrLane pr_lane[PMX_PR_LANES];                        // lanes 1 .. : own streams and sets; lane 0 = the context's own (its ws stays empty)
     std::vector<DevBuf<float>> pr_part;                  // per scale: [n][57][orig_h][orig_w] (PAF planes, then heat planes of every image)
     Event pr_src_ready, pr_fin;                          // originals uploaded / parts consumed by the last finish
     int opt_precise_lanes = PMX_PR_LANES;                // 1: every scale on the context's own stream (A/B, tests)
@@ -296,12 +319,9 @@ struct pmx_ctx {
     std::vector<LayerDesc> table;
     std::map<std::string, int> index;
     std::vector<PackedLayer> layers;
-    // buffers
-    DevBuf<float> in16, act0, act1, cat, brA, brB, brT;
+    // buffers (besides the working set)
     DevBuf<float> nchw_tmp;          // staging for NCHW host <-> NHWC device conversions
-    DevBuf<uint8_t> u8_tmp;
-    const uint8_t* in_u8 = nullptr; float in_div = 255.0f;      // set for ONE forward: conv1_wino_kernel preprocesses this uint8 batch itself
-    DevBuf<uint8_t> u8_src;          // original-size images awaiting the on-device resize
+    DevBuf<uint8_t> u8_src;         // original-size images awaiting the on-device resize
     DevBuf<int> rs_tab;              // resize tables: x (4 * dw ints) then y (4 * dh ints)
     int rs_key[4] = {0, 0, 0, 0};    // (src_h, src_w, h, w) of the tables rs_tab holds; all 0: none
     // state of the last forward / set_maps
@@ -352,7 +372,6 @@ struct pmx_ctx {
     int opt_wino_tail_merge = 1;     // the tails of all images of a launch as one stream of tiles, 32 per block (0: one part-filled block per image)
     int opt_wino_tail_g = 0;         // tuning: chunks per pass-1 unit of the tail (0 = automatic)
     int opt_wino_split = 1;          // a batch whose plain launch ends in a part-filled round of the CUs is cut in two by images (0: never)
-    std::string split_suffix;        // run_conv inside a split: "@<first image>+<count>", appended to the profile labels
     int opt_wino_unit_g = 0;         // tuning: chunks per pass-1 unit of a launch in unit mode (0 = automatic, -1 = as many units as 8 slabs allow)
     int opt_precision = 0;           // 0: fp32 MFMA everywhere (the path whose results are specified); 1: bf16x3 kernels where a
                                      // v6 kernel would run (fp32-grade accuracy at 2.67x the matrix rate, NOT the fp32 FMA chain);
@@ -368,8 +387,8 @@ struct pmx_ctx {
     int opt_conv_v5_lds = 56 * 1024; // ... of the v5 / v8 kernels: 3 x 56 KB > 160 KB -> at most 2 blocks per CU
     int opt_pp_generic = 0;          // 1: always the generic-radius peaks kernel
     int opt_cubic_rows = 1;          // detect_precise's cubic resize: 1 the separable form through LDS, 0 one thread per element
-    // split-K scratch: partial-sum slabs of the current launch + a zero bias vector for the slice blocks
-    DevBuf<float> sk_scratch, sk_zero_bias;
+    // split-K: the zero bias vector of the slice blocks, shared by every working set (each has its own slabs, sk_scratch)
+    DevBuf<float> sk_zero_bias;
     // timing / profiling
     Event t0, t1;
     int prof_on = 0;                 // 0 off | 1 every launch | 2 only the 7x7 convolutions (the dominant kernel: fewest events in a timed region)
@@ -432,12 +451,14 @@ constexpr int PMX_LOSS_SLOTS = 7;
 constexpr int PMX_LOSS_MAX_BLOCKS = 256;
 
 #define PMX_DEV(c) PMX_HIP(hipSetDevice((c)->device))
+// the default call of a context: its own working set, its stream, its "conv_algo"
+static inline FwdCall pmx_call(pmx_ctx* c) { return FwdCall{*c, c->stream, c->opt_conv_algo}; }
 
 // pmx_api.hip
 // the network on a uint8 BGR batch on the device: preprocess (x / divisor - 0.5) + forward; where conv1 runs as conv1_wino_kernel the
-// preprocessing happens inside it (no float copy of the input), else prep_u8 fills c->in16 first
-int pmx_forward_from_u8(pmx_ctx* c, const uint8_t* d_u8, int B, int H, int W, float divisor);
-int pmx_forward_from_in16(pmx_ctx* c, int B, int H, int W);      // the network on the padded float input already in c->in16
+// preprocessing happens inside it (no float copy of the input), else prep_u8 fills k.ws.in16 first
+int pmx_forward_from_u8(pmx_ctx* c, const FwdCall& k, const uint8_t* d_u8, int B, int H, int W, float divisor);
+int pmx_forward_from_in16(pmx_ctx* c, const FwdCall& k, int B, int H, int W);      // the network on the padded float input already in k.ws.in16
 // up-sampling tables of the post-process.  On any failure the context stays consistent: c->tab points into whatever c->tab_store holds (or
 // nowhere) and tab_in_h is invalid, so the next call rebuilds
 int pmx_ensure_tables(pmx_ctx* c, int in_h, int in_w, int out_h, int out_w, int flip_x = 0);
@@ -457,7 +478,7 @@ PPMaps pmx_current_maps(const pmx_ctx* c);
 void pmx_cubic_table(int src, int dst, bool fixed, int* out);
 // pmx_multi.hip: the segment tables of a forward -> device (synchronises the stream once), and the network over the segments whose uint8
 // pixels lie end to end at d_u8 (on the device)
-int build_seg_tables(pmx_ctx* c, const std::vector<SegGeo>& g);
+int build_seg_tables(pmx_ctx* c, const std::vector<SegGeo>& g, SegTables& t);
 int forward_segments(pmx_ctx* c, const uint8_t* d_u8, const std::vector<SegGeo>& g, int B);
 // pmx_loss.hip: the hook of the uniform forward.  pmx_loss_check runs with the forward's argument checks (hook on: targets of this batch and
 // size, else PMX_ERR_STATE); pmx_loss_stage enqueues the loss launch of stage `stage` (1 .. 6) over the cat slices, pmx_loss_finish the

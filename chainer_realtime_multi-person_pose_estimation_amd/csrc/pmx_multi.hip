@@ -34,11 +34,12 @@ int seg_capacity_check(pmx_ctx* c, const std::vector<Geo>& g, int B)
 
 }  // namespace
 
-// the six segment tables of a forward (pmx_ctx.h) -> device
-int build_seg_tables(pmx_ctx* c, const std::vector<Geo>& g)
+// the segment tables of a forward (pmx_ctx.h) -> device; `st` describes them
+int build_seg_tables(pmx_ctx* c, const std::vector<Geo>& g, SegTables& st)
 {
     const size_t ns = g.size();
     std::vector<ConvSeg> t(PMX_SEG_TABLES * ns);
+    st.segs.clear();
     long long pix[5] = {0, 0, 0, 0, 0};
     int tiles[PMX_SEG_TABLES] = {};
     for (size_t s = 0; s < ns; ++s) {
@@ -59,10 +60,12 @@ int build_seg_tables(pmx_ctx* c, const std::vector<Geo>& g)
             tiles[tab] += q.tiles_img * q.n;
         }
         for (int level = 0; level < 4; ++level) pix[level] += (long long)g[s].n * (g[s].H >> level) * (g[s].W >> level);
+        st.segs.push_back(SegDesc{g[s].n, g[s].H, g[s].W});
     }
-    for (int tab = 0; tab < PMX_SEG_TABLES; ++tab) c->seg_tiles[tab] = tiles[tab];
-    for (int level = 0; level < 4; ++level) c->seg_pix[level] = pix[level];
+    for (int tab = 0; tab < PMX_SEG_TABLES; ++tab) st.tiles[tab] = tiles[tab];
+    for (int level = 0; level < 4; ++level) st.pix[level] = pix[level];
     if (int rc = c->d_segs.ensure(t.size(), c->stream)) return rc;
+    st.dev = c->d_segs;
     // (stream-ordered: the kernels of an earlier forward that still read the table run before this copy; the source is pageable
     //  memory, which the runtime stages before the call returns)
     PMX_HIP(hipMemcpyAsync(c->d_segs, t.data(), t.size() * sizeof(ConvSeg), hipMemcpyHostToDevice, c->stream));
@@ -119,15 +122,17 @@ std::vector<Geo> segments_of(const int* net_hw, const int* map_hw, int B)
 // network forward over the segments; d_u8: the images' uint8 pixels end to end, on the device
 int forward_segments(pmx_ctx* c, const uint8_t* d_u8, const std::vector<Geo>& g, int B)
 {
-    int rc = build_seg_tables(c, g);
+    SegTables st;
+    int rc = build_seg_tables(c, g, st);
     if (rc) return rc;
     int mh = 0, mw = 0;
-    c->segs.clear();
-    for (const Geo& s : g) { c->segs.push_back(SegDesc{s.n, s.H, s.W}); mh = std::max(mh, s.H); mw = std::max(mw, s.W); }
+    for (const Geo& s : g) { mh = std::max(mh, s.H); mw = std::max(mw, s.W); }
+    FwdCall k = pmx_call(c);
+    k.seg = &st;
     // (H, W of the call = the largest segment: what the launch checks bound; the geometry itself comes from the tables)
-    rc = pmx_forward_from_u8(c, d_u8, B, mh, mw, 255.0f);
-    c->segs.clear();                 // heterogeneous mode ends with the enqueue; cur_segs keeps the layout of the maps
+    rc = pmx_forward_from_u8(c, k, d_u8, B, mh, mw, 255.0f);
     if (rc) { c->cur_segs.clear(); c->maps_valid = false; }
+    else c->cur_segs = std::move(st.segs);      // the layout of the maps
     return rc;
 }
 

@@ -120,23 +120,13 @@ static int lane_ensure(pmx_ctx* c, int i, size_t n, size_t ph, size_t pw)
     l.cap_px = 0;
     const size_t px8 = px / 64;
     int rc;
-    if ((rc = l.in16.alloc(px * PMX_IN_C)) || (rc = l.act0.alloc(px * 64)) || (rc = l.act1.alloc(px * 16)) ||
-        (rc = l.cat.alloc(px8 * PMX_CAT_C)) || (rc = l.brA.alloc(px8 * 256)) || (rc = l.brB.alloc(px8 * 256)) ||
-        (rc = l.brT.alloc(px8 * 1024)) || (rc = l.u8_tmp.alloc(px * 3))) return rc;
-    PMX_HIP(hipMemsetAsync(l.cat, 0, px8 * PMX_CAT_C * sizeof(float), l.stream));      // pad channels stay zero (stream-ordered)
+    NetBufs& ws = l.ws;
+    if ((rc = ws.in16.alloc(px * PMX_IN_C)) || (rc = ws.act0.alloc(px * 64)) || (rc = ws.act1.alloc(px * 16)) ||
+        (rc = ws.cat.alloc(px8 * PMX_CAT_C)) || (rc = ws.brA.alloc(px8 * 256)) || (rc = ws.brB.alloc(px8 * 256)) ||
+        (rc = ws.brT.alloc(px8 * 1024)) || (rc = ws.u8_tmp.alloc(px * 3))) return rc;
+    PMX_HIP(hipMemsetAsync(ws.cat, 0, px8 * PMX_CAT_C * sizeof(float), l.stream));      // pad channels stay zero (stream-ordered)
     l.cap_px = px;
     return PMX_OK;
-}
-// the lane's working set <-> the context's, which then runs on `stream`: the lane's, afterwards the context's own again (called in pairs
-// around the enqueue of one scale; lane 0: nothing to do)
-static void lane_swap(pmx_ctx* c, int i, hipStream_t stream)
-{
-    if (i == 0) return;
-    PrLane& l = c->pr_lane[i];
-    c->stream = stream;
-    c->in16.swap(l.in16); c->act0.swap(l.act0); c->act1.swap(l.act1); c->cat.swap(l.cat);
-    c->brA.swap(l.brA); c->brB.swap(l.brB); c->brT.swap(l.brT); c->u8_tmp.swap(l.u8_tmp);
-    c->pr_tmp.swap(l.pr_tmp); c->sk_scratch.swap(l.sk_scratch);
 }
 
 // detect_precise (pose_detector.py:433-470) on the device, for a batch of n images of ONE original size (the reference handles one image
@@ -251,7 +241,7 @@ static int precise_add_scale(pmx_ctx* c, const uint8_t* imgs, int scaled_h, int 
     float* const part_heat = part_paf + opx * PMX_N_PAF * n;
     if ((rc = lane_ensure(c, li, (size_t)n, (size_t)ph, (size_t)pw))) return rc;
     const int *xi, *yi; const void *xc, *yc;
-    // cubic tables first (a cache miss is a blocking copy into fresh memory: before the swap, so that an error leaves the context intact)
+    // cubic tables first (a cache miss is a blocking copy into fresh memory: before anything of the scale is enqueued)
     const int *t1xi = nullptr, *t1yi = nullptr; const void *t1xc = nullptr, *t1yc = nullptr;
     const bool same = scaled_h == oh && scaled_w == ow;
     if (!same && ((rc = cubic_table(c, ow, scaled_w, true, &t1xi, &t1xc)) || (rc = cubic_table(c, oh, scaled_h, true, &t1yi, &t1yc)))) return rc;
@@ -261,53 +251,45 @@ static int precise_add_scale(pmx_ctx* c, const uint8_t* imgs, int scaled_h, int 
         (rc = cubic_table(c, scaled_w, ow, false, &t4xi, &t4xc)) || (rc = cubic_table(c, scaled_h, oh, false, &t4yi, &t4yc))) return rc;
     (void)xi; (void)yi; (void)xc; (void)yc;
 
-    lane_swap(c, li, c->pr_lane[li].stream);          // from here on c->stream / c->in16 / ... are the lane's; every exit swaps back
-    auto body = [&]() -> int {
-        int rc2;
-        PMX_HIP(hipStreamWaitEvent(c->stream, c->pr_src_ready, 0));      // the originals are on the device
-        PMX_HIP(hipStreamWaitEvent(c->stream, c->pr_fin, 0));            // the last finish has read this scale's part
-        // (1) uint8 cubic resize into the padded images (all images in one launch)
-        const size_t pad_bytes = (size_t)ph * pw * 3;
-        if ((rc2 = launch_fill_pad_bgr(c->u8_tmp, n, ph, pw, scaled_h, scaled_w, 104, 117, 123, c->stream))) return rc2;
-        if (same) {
-            for (int b = 0; b < n; ++b)
-                PMX_HIP(hipMemcpy2DAsync(c->u8_tmp + b * pad_bytes, (size_t)pw * 3, c->u8_src + b * img_bytes, (size_t)ow * 3, (size_t)ow * 3, oh,
-                                         hipMemcpyDeviceToDevice, c->stream));
-        } else if ((rc2 = launch_resize_cubic_u8(c->u8_src, ow, c->u8_tmp, scaled_h, scaled_w, pw, t1xi, (const int*)t1xc, t1yi, (const int*)t1yc, n,
-                                                 (long long)img_bytes, (long long)pad_bytes, c->stream))) return rc2;
-        // (2) network, the n images as one batch.  With several scales in flight the chip is shared: what counts is the CU time a scale
-        // consumes, not how fast it would finish alone -- so the lanes run the PLAIN Winograd kernel on every eligible layer ("conv_algo" 2:
-        // 0.83 of the matrix peak per block) instead of the unit-mode / split-K forms the selection gives a launch that has the chip to
-        // itself (0.45: they trade CU time for latency).  Round 6, 482 x 642 frame, lanes with priorities: 14.2 -> 13.5 ms per image
-        // (profiles/r06_precise_priority_ab.json).  Option "precise_plain": -1 (default) = when all four lanes are in use, 0 / 1 = never / always.
-        const int algo_saved = c->opt_conv_algo;
-        // (-1 = only with all four lanes in use: a lane that carries two scales one after the other wants the latency-oriented forms --
-        //  three lanes 15.0 -> 20.4 ms, two 16.0 -> 25.0 with the plain kernels, profiles/r06_precise_probe_lanes.json)
-        const bool plain = c->opt_precise_plain < 0 ? c->opt_precise_lanes >= PMX_PR_LANES : c->opt_precise_plain != 0;
-        if (plain && c->opt_conv_algo == 1) c->opt_conv_algo = 2;
-        rc2 = pmx_forward_from_u8(c, c->u8_tmp, n, ph, pw, 255.0f);
-        c->opt_conv_algo = algo_saved;
-        if (rc2) return rc2;
-        // (3) x8 cubic up-sampling of the PAF (38) and heat (19) channels of all images into PLANAR temporaries [n][38][ph][pw] | [n][19][ph][pw]
-        // (two cv2.resize calls per image in the reference; planar so that step (4) reads rows of one channel and both steps store full rows)
-        const size_t ppx = (size_t)ph * pw, ntmp = ppx * 57 * n;
-        if ((rc2 = c->pr_tmp.ensure(ntmp, c->stream))) return rc2;
-        float* const t_paf = c->pr_tmp;
-        float* const t_heat = c->pr_tmp + ppx * PMX_N_PAF * n;
-        const long long sy = (long long)fw * PMX_CAT_C, sx = PMX_CAT_C, sb = (long long)fh * fw * PMX_CAT_C;
-        if ((rc2 = launch_resize_cubic_f32_planar(c->cat + PMX_CAT_PAF, sb, 1, sy, sx, n, PMX_N_PAF, t_paf, ph, pw, t3xi, (const float*)t3xc, t3yi, (const float*)t3yc, 0, c->opt_cubic_rows, c->stream))) return rc2;
-        if ((rc2 = launch_resize_cubic_f32_planar(c->cat + PMX_CAT_HEAT, sb, 1, sy, sx, n, PMX_N_HEAT, t_heat, ph, pw, t3xi, (const float*)t3xc, t3yi, (const float*)t3yc, 0, c->opt_cubic_rows, c->stream))) return rc2;
-        // (4) crop the padding (source extent scaled_h x scaled_w of the padded maps) and cubic resize to the original size -> this scale's part
-        if ((rc2 = launch_resize_cubic_f32_planar(t_paf, (long long)ppx * PMX_N_PAF, (long long)ppx, pw, 1, n, PMX_N_PAF, part_paf, oh, ow, t4xi, (const float*)t4xc, t4yi,
-                                                  (const float*)t4yc, 0, c->opt_cubic_rows, c->stream))) return rc2;
-        if ((rc2 = launch_resize_cubic_f32_planar(t_heat, (long long)ppx * PMX_N_HEAT, (long long)ppx, pw, 1, n, PMX_N_HEAT, part_heat, oh, ow, t4xi, (const float*)t4xc, t4yi,
-                                                  (const float*)t4yc, 0, c->opt_cubic_rows, c->stream))) return rc2;
-        PMX_HIP(hipEventRecord(c->pr_lane[li].done, c->stream));
-        return PMX_OK;
-    };
-    rc = body();
-    lane_swap(c, li, main_stream);
-    if (rc) return rc;
+    // the scale's lane: its working set and stream (lane 0: the context's own); the context itself is not touched by the enqueue
+    NetBufs& ws = li ? c->pr_lane[li].ws : *c;
+    const hipStream_t st = li ? (hipStream_t)c->pr_lane[li].stream : main_stream;
+    PMX_HIP(hipStreamWaitEvent(st, c->pr_src_ready, 0));      // the originals are on the device
+    PMX_HIP(hipStreamWaitEvent(st, c->pr_fin, 0));            // the last finish has read this scale's part
+    // (1) uint8 cubic resize into the padded images (all images in one launch)
+    const size_t pad_bytes = (size_t)ph * pw * 3;
+    if ((rc = launch_fill_pad_bgr(ws.u8_tmp, n, ph, pw, scaled_h, scaled_w, 104, 117, 123, st))) return rc;
+    if (same) {
+        for (int b = 0; b < n; ++b)
+            PMX_HIP(hipMemcpy2DAsync(ws.u8_tmp + b * pad_bytes, (size_t)pw * 3, c->u8_src + b * img_bytes, (size_t)ow * 3, (size_t)ow * 3, oh,
+                                     hipMemcpyDeviceToDevice, st));
+    } else if ((rc = launch_resize_cubic_u8(c->u8_src, ow, ws.u8_tmp, scaled_h, scaled_w, pw, t1xi, (const int*)t1xc, t1yi, (const int*)t1yc, n,
+                                            (long long)img_bytes, (long long)pad_bytes, st))) return rc;
+    // (2) network, the n images as one batch.  With several scales in flight the chip is shared: what counts is the CU time a scale
+    // consumes, not how fast it would finish alone -- so the lanes run the PLAIN Winograd kernel on every eligible layer ("conv_algo" 2:
+    // 0.83 of the matrix peak per block) instead of the unit-mode / split-K forms the selection gives a launch that has the chip to
+    // itself (0.45: they trade CU time for latency).  Round 6, 482 x 642 frame, lanes with priorities: 14.2 -> 13.5 ms per image
+    // (profiles/r06_precise_priority_ab.json).  Option "precise_plain": -1 (default) = when all four lanes are in use, 0 / 1 = never / always.
+    // (-1 = only with all four lanes in use: a lane that carries two scales one after the other wants the latency-oriented forms --
+    //  three lanes 15.0 -> 20.4 ms, two 16.0 -> 25.0 with the plain kernels, profiles/r06_precise_probe_lanes.json)
+    const bool plain = c->opt_precise_plain < 0 ? c->opt_precise_lanes >= PMX_PR_LANES : c->opt_precise_plain != 0;
+    const FwdCall call{ws, st, plain && c->opt_conv_algo == 1 ? 2 : c->opt_conv_algo};
+    if ((rc = pmx_forward_from_u8(c, call, ws.u8_tmp, n, ph, pw, 255.0f))) return rc;
+    // (3) x8 cubic up-sampling of the PAF (38) and heat (19) channels of all images into PLANAR temporaries [n][38][ph][pw] | [n][19][ph][pw]
+    // (two cv2.resize calls per image in the reference; planar so that step (4) reads rows of one channel and both steps store full rows)
+    const size_t ppx = (size_t)ph * pw, ntmp = ppx * 57 * n;
+    if ((rc = ws.pr_tmp.ensure(ntmp, st))) return rc;
+    float* const t_paf = ws.pr_tmp;
+    float* const t_heat = ws.pr_tmp + ppx * PMX_N_PAF * n;
+    const long long sy = (long long)fw * PMX_CAT_C, sx = PMX_CAT_C, sb = (long long)fh * fw * PMX_CAT_C;
+    if ((rc = launch_resize_cubic_f32_planar(ws.cat + PMX_CAT_PAF, sb, 1, sy, sx, n, PMX_N_PAF, t_paf, ph, pw, t3xi, (const float*)t3xc, t3yi, (const float*)t3yc, 0, c->opt_cubic_rows, st))) return rc;
+    if ((rc = launch_resize_cubic_f32_planar(ws.cat + PMX_CAT_HEAT, sb, 1, sy, sx, n, PMX_N_HEAT, t_heat, ph, pw, t3xi, (const float*)t3xc, t3yi, (const float*)t3yc, 0, c->opt_cubic_rows, st))) return rc;
+    // (4) crop the padding (source extent scaled_h x scaled_w of the padded maps) and cubic resize to the original size -> this scale's part
+    if ((rc = launch_resize_cubic_f32_planar(t_paf, (long long)ppx * PMX_N_PAF, (long long)ppx, pw, 1, n, PMX_N_PAF, part_paf, oh, ow, t4xi, (const float*)t4xc, t4yi,
+                                             (const float*)t4yc, 0, c->opt_cubic_rows, st))) return rc;
+    if ((rc = launch_resize_cubic_f32_planar(t_heat, (long long)ppx * PMX_N_HEAT, (long long)ppx, pw, 1, n, PMX_N_HEAT, part_heat, oh, ow, t4xi, (const float*)t4xc, t4yi,
+                                             (const float*)t4yc, 0, c->opt_cubic_rows, st))) return rc;
+    PMX_HIP(hipEventRecord(c->pr_lane[li].done, st));
     c->pr_scales += 1;
     c->pr_mask |= 1u << slot;
     c->maps_valid = false;       // the cat buffers hold single scales only; the averaged maps become valid in pmx_precise_finish

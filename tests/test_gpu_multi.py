@@ -177,6 +177,43 @@ def test_mixed_batch_argument_errors(native):
     eng.close()
 
 
+def test_forward_error_after_first_launches_leaves_the_context_usable(native):
+    """A forward that returns an error AFTER conv1 and the stem have been enqueued: with `fuse_pairs` 0 a mixed batch stops at the first
+    1x1 pair, which has no unfused heterogeneous form (PMX_ERR_INVALID, a returned code: nothing faults).  The context then has no valid
+    maps, and the next forwards -- uniform and mixed -- compute bit for bit what a fresh context computes: nothing of the failed call
+    (its segment tables, its uint8 input, its stream) stays behind in the context."""
+    weights = pkg('weights').synthetic_weights(0)
+    rng = np.random.default_rng(11)
+    one = rng.integers(0, 256, (1, 32, 32, 3), dtype=np.uint8)
+    mixed = [rng.integers(0, 256, (32, 32, 3), dtype=np.uint8), rng.integers(0, 256, (32, 48, 3), dtype=np.uint8)]
+    eng = native.Engine(0, max_batch=2, max_h=64, max_w=64)
+    eng.set_weights(weights)
+    eng.forward_u8(one)                                                     # valid maps, which the failed call must take away
+    eng.get_maps()
+    eng.set_option('fuse_pairs', 0)
+    with pytest.raises(native.PmxError) as e:
+        eng.forward_u8_images(mixed)
+    assert e.value.code == 1 and 'has no fused form' in str(e.value), e.value
+    with pytest.raises(native.PmxError):
+        eng.get_maps()
+    with pytest.raises(native.PmxError):
+        eng.image_maps(0, 4, 4)
+    eng.set_option('fuse_pairs', 1)
+    fresh = native.Engine(0, max_batch=2, max_h=64, max_w=64)
+    fresh.set_weights(weights)
+    eng.forward_u8(one)
+    fresh.forward_u8(one)
+    for a, b in zip(eng.get_maps(), fresh.get_maps()):
+        assert np.array_equal(a, b)
+    eng.forward_u8_images(mixed)
+    fresh.forward_u8_images(mixed)
+    for i in range(2):
+        for a, b in zip(eng.image_maps(i), fresh.image_maps(i)):
+            assert np.array_equal(a, b), i
+    eng.close()
+    fresh.close()
+
+
 # ---- randomised: any list of sizes (deterministic example set by default; PMX_FUZZ=<n> draws n fresh random examples) ----------------------
 import os
 from hypothesis import given, settings, strategies as st, HealthCheck
