@@ -157,6 +157,25 @@ int wino_select(const WinoSelectOpts& o, int ks, int cin_pad, int cout_pad, int 
     return 0;
 }
 
+// Two half-batch chains on two streams (option "batch_chains" = -1; pmx_api.hip::pmx_detect_batch): a second, independent chain can only use
+// CUs that a launch leaves idle -- the short tail and post-process launches, the last round's skew -- if cutting the batch does not itself
+// open a part-filled round.  So the automatic rule wants of every 7x7 layer (nine tenths of a step) that its whole-batch form is the plain
+// kernel (mode 1 of wino_select, with its run / tail_g) and that the plain launch of EACH half, n0 and n1 images, is whole rounds of the CUs:
+// 32 frames of 368 x 368 are 16 full blocks x 16 images x 2 groups = 512 = two rounds per half; 8 frames would be half a round each.
+// (That no layer is cut by wino_split_images, the batch uniform, fp32 and conv_algo 1 is the caller's to check: it knows the network.)
+bool batch_chains_rounds(const WinoSelectOpts& o, int mode, int run, int tail_g, int cout_pad, int n0, int n1, int H, int W)
+{
+    if (mode != 1 || o.conv_algo != 1 || o.precision != 0) return false;
+    const long long nb = cout_pad / 128, grp = std::max(1, o.groups);
+    long long bpi;                   // blocks of the plain launch per image (all groups)
+    if (run) {
+        const int ntiles = PMX_WINO_RUN_TX * ((H + 1) / 2), nblk = (ntiles + PMX_WINO_RUN_TILES - 1) / PMX_WINO_RUN_TILES, nfull = ntiles / PMX_WINO_RUN_TILES;
+        bpi = (long long)(tail_g ? nfull : nblk) * (W / (PMX_WINO_RUN_TX * 2)) * nb * grp;
+    } else
+        bpi = (long long)((H + 7) / 8) * ((W + 15) / 16) * nb * grp;
+    return n0 >= 1 && n1 >= 1 && bpi * n0 % o.ncu == 0 && bpi * n1 % o.ncu == 0;
+}
+
 // A launch of the plain kernel whose last round of the CUs is part-filled pays a whole round for it (equal one-per-CU blocks).  Where that
 // costs more than running the images of that round in the finer-grained forms, run_conv cuts the batch in two: the first *n0 images --
 // whole rounds -- through the plain kernel, the rest through whatever the selection gives THEIR count (unit mode with the plan of

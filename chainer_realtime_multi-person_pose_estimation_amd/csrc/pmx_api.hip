@@ -323,6 +323,7 @@ extern "C" int pmx_synchronize(pmx_ctx* c)
 extern "C" int pmx_set_option(pmx_ctx* c, const char* key, int value)
 {
     PMX_CHECK(c && key, PMX_ERR_INVALID, "null arg");
+    c->opt_epoch += 1;
     if (!strcmp(key, "force_variant_k7")) c->opt_force[7] = value;
     else if (!strcmp(key, "force_variant_k3")) c->opt_force[3] = value;
     else if (!strcmp(key, "force_variant_k1")) c->opt_force[1] = value;
@@ -358,6 +359,10 @@ extern "C" int pmx_set_option(pmx_ctx* c, const char* key, int value)
     else if (!strcmp(key, "wino_unit_g")) c->opt_wino_unit_g = value;
     else if (!strcmp(key, "wino_split")) c->opt_wino_split = value;
     else if (!strcmp(key, "wino_tail_merge")) c->opt_wino_tail_merge = value;
+    else if (!strcmp(key, "batch_chains")) {
+        PMX_CHECK(value >= -1 && value <= 1, PMX_ERR_INVALID, "pmx_set_option: \"batch_chains\" = %d: 0 (off), 1 (wherever the plans allow) or -1 (automatic)", value);
+        c->opt_batch_chains = value;
+    }
     else if (!strcmp(key, "ksplit")) c->opt_ksplit = value;
     else if (!strcmp(key, "ksplit_plan")) c->opt_ksplit = value > 0 ? -value : 0;     // decimal digits = chunks per slice, e.g. 3221
     else if (!strcmp(key, "conv_min_lds")) c->opt_conv_min_lds = value;
@@ -444,15 +449,19 @@ static int ensure_f16_pack(hipStream_t st, PackedLayer& L) { return derive_on_de
 // produces the final result (slabs added in slice order, then bias, ReLU, pool).
 static const int SK_ZERO_BIAS = PMX_SK_ZERO_BIAS;
 // the slab scratch at `need` floats at least, and the zero bias vector of the slice blocks (made on first use)
+// (the second of two half-batch chains has both to itself: k.scratch)
+static DevBuf<float>& sk_slabs(const FwdCall& k) { return k.scratch ? k.scratch->sk_scratch : k.ws.sk_scratch; }
+static DevBuf<float>& sk_zeros(pmx_ctx* c, const FwdCall& k) { return k.scratch ? k.scratch->sk_zero_bias : c->sk_zero_bias; }
 static int sk_reserve(pmx_ctx* c, const FwdCall& k, size_t need)
 {
     int rc;
-    if ((rc = k.ws.sk_scratch.ensure(need, k.stream))) return rc;
-    if (!c->sk_zero_bias) {
-        if ((rc = c->sk_zero_bias.alloc(SK_ZERO_BIAS))) return rc;
+    if ((rc = sk_slabs(k).ensure(need, k.stream))) return rc;
+    DevBuf<float>& zero = sk_zeros(c, k);
+    if (!zero) {
+        if ((rc = zero.alloc(SK_ZERO_BIAS))) return rc;
         // stream-ordered: a null-stream hipMemset is not ordered against this (non-blocking) stream and may still be in flight
         // when the first slice kernel reads the vector
-        PMX_HIP(hipMemsetAsync(c->sk_zero_bias, 0, SK_ZERO_BIAS * sizeof(float), k.stream));
+        PMX_HIP(hipMemsetAsync(zero, 0, SK_ZERO_BIAS * sizeof(float), k.stream));
     }
     return PMX_OK;
 }
@@ -466,9 +475,9 @@ static int slab_redirect(pmx_ctx* c, const FwdCall& k, const ConvArgs& a0, int g
     if (int rc = sk_reserve(c, k, slab * S * groups)) return rc;
     memset(&r, 0, sizeof r);
     for (int g = 0; g < groups; ++g) {
-        float* base = k.ws.sk_scratch + (size_t)g * S * slab;
+        float* base = sk_slabs(k) + (size_t)g * S * slab;
         r.slabs[g] = base; r.bias[g] = a0.g[g].bias; r.out[g] = a0.g[g].out; r.cout[g] = a0.g[g].cout;
-        a.g[g].out = base; a.g[g].bias = c->sk_zero_bias; a.g[g].cout = a0.cout_pad;
+        a.g[g].out = base; a.g[g].bias = sk_zeros(c, k); a.g[g].cout = a0.cout_pad;
     }
     a.ldc = a0.cout_pad; a.relu = 0; a.pool = 0; a.ksplit = S; a.slab_stride = (long long)slab; a.kbounds = kbounds;
     r.slab_stride = (long long)slab; r.B = a0.B; r.H = a0.H; r.W = a0.W; r.ld_slab = a0.cout_pad; r.ldc = a0.ldc;
@@ -718,6 +727,62 @@ static int launch_plan(pmx_ctx* c, const FwdCall& k, const ConvPlan& p)
     return pf ? prof_end(c, k) : PMX_OK;
 }
 
+// ---- two half-batch chains (pmx_ctx.h: BatchChain, ChainSplit) ----
+// the call of chain i of a forward that runs as two, and its images [*first, *first + *n) of B
+static FwdCall chain_call(const FwdCall& k, int i, int B, int* first, int* n)
+{
+    FwdCall kc = k;
+    kc.split = nullptr;
+    *first = i ? k.split->n0 : 0;
+    *n = i ? B - k.split->n0 : k.split->n0;
+    if (i) { kc.stream = k.split->second->stream; kc.scratch = k.split->second; }
+    return kc;
+}
+static std::string chain_suffix(int first, int n) { return "@" + std::to_string(first) + "+" + std::to_string(n); }
+// The plan of the whole batch, launched once per chain on the chain's images.  Probe: whether a launch of either half is the launch the plan
+// describes (the merged tails are a property of the image count) and what the automatic rule says of a 7x7 layer.
+static int launch_plan_chains(pmx_ctx* c, const FwdCall& k, const ConvPlan& p)
+{
+    ChainSplit& s = *k.split;
+    const ConvArgs& a = p.a;
+    if (s.probe) {
+        if (p.form == FORM_WINO_RUN && p.tail_g)
+            for (int n : {s.n0, a.B - s.n0}) {
+                ConvArgs h = a;
+                h.B = n;
+                if (wino_tail_merged(c, h) != wino_tail_merged(c, a)) s.ok = false;
+            }
+        if (p.ks == 7 && !batch_chains_rounds(wino_opts(c, k, p.ks, p.groups, a.lda), p.form == FORM_WINO || p.form == FORM_WINO_RUN, p.form == FORM_WINO_RUN,
+                                              p.tail_g, a.cout_pad, s.n0, a.B - s.n0, a.H, a.W)) s.rounds = false;
+        return PMX_OK;
+    }
+    const size_t pin = (size_t)a.H * a.W * a.lda, pout = (size_t)(a.pool ? a.H / 2 : a.H) * (a.pool ? a.W / 2 : a.W) * a.ldc;
+    // Where the second chain's images start in the buffer `ptr` points into.  The chains drift apart by layers, and act0 / act1 hold layers of
+    // different sizes in turn: at the image offset of each layer, a later, smaller layer of one chain would land in what the other chain still
+    // reads of an earlier, larger one.  So there the second chain starts at a distance that no layer of the first reaches -- n0 images of the
+    // largest layer the buffer ever holds (act0: conv1_1's output, 64 floats per input pixel; act1: conv1_2's pooled output, 16); every other
+    // buffer holds layers of one size only (cat, brA, brB, brT at 1/8 resolution; in16) and keeps the image offset.
+    auto second = [&](const float* ptr, size_t per_image) {
+        const NetBufs& ws = k.ws;
+        if (ptr >= ws.act0 && ptr < ws.act0 + ws.act0.capacity()) return (size_t)s.n0 * s.net_px * 64;
+        if (ptr >= ws.act1 && ptr < ws.act1 + ws.act1.capacity()) return (size_t)s.n0 * s.net_px * 16;
+        return (size_t)s.n0 * per_image;
+    };
+    for (int i = 0; i < 2; ++i) {
+        int first, n;
+        const FwdCall kc = chain_call(k, i, a.B, &first, &n);
+        ConvPlan q = p;
+        q.a.B = n;
+        for (int g = 0; g < p.groups && i; ++g) { q.a.g[g].in += second(a.g[g].in, pin); q.a.g[g].out += second(a.g[g].out, pout); }
+        if (q.prof) {
+            const double share = (double)n / a.B;
+            q.pf.flops *= share; q.pf.bytes *= share; q.pf.issued *= share; q.pf.suffix = chain_suffix(first, n);
+        }
+        if (int rc = launch_plan(c, kc, q)) return rc;
+    }
+    return PMX_OK;
+}
+
 // one layer of a forward: plan + launch.  A batch whose plain launch would end in a part-filled round of the CUs is cut in two first: the
 // images of the whole rounds, then the rest through the selection of THEIR count (conv_select.hip::wino_split_images); each half is an
 // ordinary run_conv on its images, whose profile labels end in `half` = "@<first image>+<count>" (null: a whole batch)
@@ -728,6 +793,11 @@ static int run_conv(pmx_ctx* c, const FwdCall& k, const char* label, PackedLayer
     int rc;
     if (!seg && !half && c->opt_wino_split && B >= 2 && L0->ks > 1 && c->opt_precision != 2 && wino_layers_ok(L0, L1)) {
         const int n0 = wino_split_images(wino_opts(c, k, L0->ks, L1 ? 2 : 1, lda), L0->ks, L0->cin_pad, L0->cout_pad, L0->cout, ldc, B, L1 ? 2 : 1, H, W, pool);
+        if (n0 > 0 && n0 < B && k.split) {      // (a cut by images is a plan of its own per side: no chains over it)
+            PMX_CHECK(k.split->probe, PMX_ERR_STATE, "two chains: layer %s is cut in two by images", label ? label : "?");
+            k.split->ok = false;
+            return PMX_OK;
+        }
         if (n0 > 0 && n0 < B) {
             const size_t pin = (size_t)n0 * H * W * lda, pout = (size_t)n0 * (pool ? H / 2 : H) * (pool ? W / 2 : W) * ldc;
             const std::string h0 = "@0+" + std::to_string(n0), h1 = "@" + std::to_string(n0) + "+" + std::to_string(B - n0);
@@ -739,7 +809,7 @@ static int run_conv(pmx_ctx* c, const FwdCall& k, const char* label, PackedLayer
     ConvPlan p;
     if ((rc = plan_conv(c, k, p, label, L0, L1, in0, in1, lda, out0, out1, ldc, B, H, W, relu, pool, level))) return rc;
     if (half && p.prof) p.pf.suffix = half;
-    return launch_plan(c, k, p);
+    return k.split ? launch_plan_chains(c, k, p) : launch_plan(c, k, p);
 }
 
 // the two 1x1 layers that end a stage (A: 128 -> cmid + ReLU, B: cmid -> cout [+ ReLU]) as ONE launch when the shapes allow
@@ -773,10 +843,23 @@ static int run_pair(pmx_ctx* c, const FwdCall& k, const char* labelA, const char
         flops += 2.0 * (double)npix * ((double)A.cout * A.cin + (double)Bl.cout * Bl.cin);
     }
     p.npix = npix; p.lda = lda; p.ldc = ldc; p.cmid = LA.cout; p.cout_pad = LB.cout_pad; p.relu2 = reluB;
-    if (c->prof_on == 1) {
-        const std::string kn = "conv1x1_pair_c" + std::to_string(LA.cout) + "_n" + std::to_string(LB.cout_pad);
-        if ((rc = prof_begin(c, k, std::string(labelA) + "+" + labelB + "|" + kn, flops, 4.0 * (double)npix * groups * (LA.cin + LB.cout)))) return rc;
+    const std::string name = std::string(labelA) + "+" + labelB + "|conv1x1_pair_c" + std::to_string(LA.cout) + "_n" + std::to_string(LB.cout_pad);
+    const double bytes = 4.0 * (double)npix * groups * (LA.cin + LB.cout);
+    if (k.split) {                   // two chains: the launch over each chain's pixels
+        if (k.split->probe) return PMX_OK;
+        for (int i = 0; i < 2; ++i) {
+            int first, n;
+            const FwdCall kc = chain_call(k, i, B, &first, &n);
+            PairArgs q = p;
+            q.npix = (long long)n * H * W;
+            for (int g = 0; g < groups; ++g) { q.g[g].in += (size_t)first * H * W * lda; q.g[g].out += (size_t)first * H * W * ldc; }
+            const double share = (double)n / B;
+            if (c->prof_on == 1 && (rc = prof_begin(c, kc, name + chain_suffix(first, n), flops * share, bytes * share))) return rc;
+            if ((rc = conv_pair_launch(q, groups, kc.stream)) || (rc = prof_end(c, kc))) return rc;
+        }
+        return PMX_OK;
     }
+    if (c->prof_on == 1 && (rc = prof_begin(c, k, name, flops, bytes))) return rc;
     if ((rc = conv_pair_launch(p, groups, k.stream))) return rc;
     return prof_end(c, k);
 }
@@ -841,6 +924,30 @@ static int run_conv1(pmx_ctx* c, const FwdCall& k, int B, int H, int W)
     a.g[0].in = ws.in16; a.g[0].w = L2.d_w; a.g[0].bias = L2.d_b; a.g[0].out = ws.act1; a.g[0].cout = L2.cout;
     a.g[1].w = L1.d_w; a.g[1].bias = L1.d_b;
     a.B = B; a.H = H; a.W = W; a.lda = PMX_IN_C; a.ldc = 64; a.nch = L2.nch; a.cout_pad = L2.cout_pad; a.relu = 1; a.pool = 1;
+    if (k.split) {                   // two chains: the form of the whole batch, launched over each chain's images
+        if (k.split->probe) return PMX_OK;
+        if (wino1 && ((rc = ensure_wino_pack(k.stream, L2)) || (rc = ensure_conv1_pack(k.stream, L1)))) return rc;
+        if (wino1) { a.g[0].w = L2.d_ww; a.g[1].w = L1.d_ww; }
+        if (wino1 && in_u8) a.kbounds = (unsigned long long)__builtin_bit_cast(unsigned, k.in_div);
+        const double f1 = 2.0 * H * W * 9.0 * (double)L1.cout * L1.cin, f2 = 2.0 * H * W * 9.0 * (double)L2.cout * L2.cin;      // per image
+        for (int i = 0; i < 2; ++i) {
+            int first, n;
+            const FwdCall kc = chain_call(k, i, B, &first, &n);
+            ConvArgs q = a;
+            q.B = n;
+            q.g[0].in += (size_t)first * H * W * PMX_IN_C; q.g[0].out += (size_t)first * (H / 2) * (W / 2) * 64;
+            if (wino1 && in_u8) q.g[1].in = reinterpret_cast<const float*>(in_u8 + (size_t)first * H * W * 3);
+            if (c->prof_on == 1) {
+                const double np = (double)n * H * W;
+                rc = wino1 ? prof_begin(c, kc, "conv1_1+conv1_2|conv_wino1_f2x2_t16x16" + chain_suffix(first, n), n * (f1 + f2),
+                                        (in_u8 ? 3.0 : 4.0 * 3) * np + 4.0 * np * (64 / 4), n * (f1 + f2 * 16.0 / 36.0))
+                           : prof_begin(c, kc, "conv1_1+conv1_2|conv1_fused_t8x16_n64" + chain_suffix(first, n), n * (f1 + f2), 4.0 * np * (3 + 64 / 4));
+                if (rc) return rc;
+            }
+            if ((rc = wino1 ? conv1_wino_launch(q, kc.stream) : conv1_fused_launch(q, kc.stream)) || (rc = prof_end(c, kc))) return rc;
+        }
+        return PMX_OK;
+    }
     if (wino1) {
         if ((rc = ensure_wino_pack(k.stream, L2)) || (rc = ensure_conv1_pack(k.stream, L1))) return rc;
         a.g[0].w = L2.d_ww;
@@ -978,6 +1085,7 @@ int pmx_forward_from_in16(pmx_ctx* c, const FwdCall& k, int B, int H, int W)
     // instead of act1 / act0 / brA / brB / brT (same leading dimensions: same plans, same bits), the 1x1 pairs unfused
     BwState& bw = c->bw;
     const bool keep = bw.on && hook && c->lg_on && c->opt_precision == 0;
+    PMX_CHECK(!k.split || !hook, PMX_ERR_STATE, "forward: two chains under the validation-loss hook");
     bw.valid = bw.done = bw.trunk_done = false;
     const long long npix8 = (long long)B * H8 * W8;
     PMX_CHECK(!keep || (size_t)npix8 <= bw.cap_px, PMX_ERR_CAPACITY, "forward: %lld map pixels, the backward store holds %zu", npix8, bw.cap_px);
@@ -1035,6 +1143,7 @@ int pmx_forward_from_in16(pmx_ctx* c, const FwdCall& k, int B, int H, int W)
     if (hook && (rc = pmx_loss_finish(c, n_stages, B, H8, W8))) return rc;
     if (keep) { bw.valid = true; bw.stages = n_stages; bw.B = B; bw.fh = H8; bw.fw = W8; bw.t_H = H; bw.t_W = W; }
 #undef RUN
+    if (k.split && k.split->probe) return PMX_OK;      // (nothing ran)
     c->maps_valid = true; c->maps_external = false;
     c->cur_B = B; c->cur_fh = H8; c->cur_fw = W8;
     c->cur_segs.clear();             // (a heterogeneous forward: forward_segments installs the layout of its tables)
@@ -1091,6 +1200,16 @@ int pmx_forward_from_u8(pmx_ctx* c, const FwdCall& k, const uint8_t* d, int B, i
         FwdCall ku = k;
         ku.in_u8 = d; ku.in_div = divisor;
         return pmx_forward_from_in16(c, ku, B, H, W);
+    }
+    if (k.split) {                   // two chains: each preprocesses its own images
+        for (int i = 0; i < 2 && !k.split->probe; ++i) {
+            int first, n;
+            const FwdCall kc = chain_call(k, i, B, &first, &n);
+            if (c->prof_on == 1 && (rc = prof_begin(c, kc, "prep_u8|prep_u8" + chain_suffix(first, n), 0, (double)n * H * W * (3 + 64)))) return rc;
+            if ((rc = launch_prep_u8(d + (size_t)first * H * W * 3, k.ws.in16 + (size_t)first * H * W * PMX_IN_C, n, H, W, divisor, kc.stream))) return rc;
+            if ((rc = prof_end(c, kc))) return rc;
+        }
+        return pmx_forward_from_in16(c, k, B, H, W);
     }
     if (c->prof_on == 1 && (rc = prof_begin(c, k, "prep_u8|prep_u8", 0, (double)B * H * W * (3 + 64)))) return rc;
     if ((rc = launch_prep_u8(d, k.ws.in16, B, H, W, divisor, k.stream))) return rc;
@@ -1458,9 +1577,98 @@ extern "C" int pmx_get_capacities(pmx_ctx* c, int* peaks_per_joint, int* subsets
     return PMX_OK;
 }
 
+// Does pmx_detect_batch run this batch as two half-batch chains (option "batch_chains"; pmx_ctx.h: BatchChain)?  Only a uniform fp32 inference
+// batch of the pose network; then a probe walks the forward without launching anything: no layer cut in two by images, every launch of a
+// half the launch its whole-batch plan describes, and -- the automatic rule, under conv_algo 1 -- the halves of every 7x7 plain launch whole
+// rounds of the CUs.  The verdict is kept per (B, H, W) until an option changes.
+static int chains_wanted(pmx_ctx* c, const uint8_t* d, int B, int H, int W, bool* yes)
+{
+    *yes = false;
+    if (!c->opt_batch_chains || B < 2 || c->kind != NET_POSE || c->opt_precision != 0 || c->ls_on || c->bw.on || c->tr.on || c->opt_keep_smoothed) return PMX_OK;
+    // (automatic: not under the per-launch profiler -- its event pairs would time a launch's wait for CUs the other chain holds, and its
+    //  labels are the one plan per layer that the C twin reads; the 7x7-only profile of timed regions keeps the form that is being timed)
+    if (c->opt_batch_chains < 0 && (c->opt_conv_algo != 1 || c->prof_on == 1)) return PMX_OK;
+    const int key[4] = {B, H, W, c->opt_epoch};
+    if (memcmp(key, c->chains_key, sizeof key)) {
+        ChainSplit s;
+        s.n0 = B / 2; s.probe = true;
+        FwdCall k = pmx_call(c);
+        k.split = &s;
+        c->chains_key[3] = -1;
+        if (int rc = pmx_forward_from_u8(c, k, d, B, H, W, 255.0f)) return rc;
+        memcpy(c->chains_key, key, sizeof key);
+        c->chains_ok = s.ok; c->chains_rounds = s.rounds;
+    }
+    *yes = c->chains_ok && (c->opt_batch_chains > 0 || c->chains_rounds);
+    return PMX_OK;
+}
+
+// The batch as two chains: images [0, n0) on the context's stream, [n0, B) on the second stream, forked here and joined before the return --
+// network and post-process of a half never wait for the other half, and whatever is enqueued on the context's stream afterwards sees the
+// records of all B images.  No host synchronisation beyond what the one-chain call has (the tables of a new map size, buffers that grow).
+static int detect_batch_chains(pmx_ctx* c, const uint8_t* d, int B, int H, int W, int map_h, int map_w, double img_len, const double* scale_xy)
+{
+    BatchChain& ch = c->chain2;
+    int rc;
+    if ((rc = ch.stream.create(hipStreamNonBlocking)) || (rc = ch.fork.create(hipEventDisableTiming)) || (rc = ch.done.create(hipEventDisableTiming))) return rc;
+    if ((rc = pmx_ensure_tables(c, H / 8, W / 8, map_h, map_w))) return rc;
+    const double* dscale = nullptr;
+    if (scale_xy) {
+        PMX_HIP(hipMemcpyAsync(c->d_scale, scale_xy, sizeof(double) * 2 * B, hipMemcpyHostToDevice, c->stream));
+        dscale = c->d_scale;
+    }
+    PMX_HIP(hipEventRecord(ch.fork, c->stream));
+    PMX_HIP(hipStreamWaitEvent(ch.stream, ch.fork, 0));
+    ChainSplit s;
+    s.n0 = B / 2; s.net_px = (size_t)H * W; s.second = &ch;
+    FwdCall k = pmx_call(c);
+    k.split = &s;
+    rc = pmx_forward_from_u8(c, k, d, B, H, W, 255.0f);
+    const PPMaps m = pmx_current_maps(c);
+    c->pp_limbs_slices = c->opt_limbs_slices >= 0 ? c->opt_limbs_slices : 0;
+    struct ProfCtx { pmx_ctx* c; FwdCall k; std::string suffix; };
+    auto prof_cb = [](void* v, const char* name, int begin) {
+        ProfCtx* p = (ProfCtx*)v;
+        if (begin) (void)prof_begin(p->c, p->k, std::string(name) + "|" + name + p->suffix, 0, 0);
+        else (void)prof_end(p->c, p->k);
+    };
+    for (int i = 0; i < 2 && !rc; ++i) {
+        int first, n;
+        ProfCtx pc{c, chain_call(k, i, B, &first, &n), ""};
+        pc.suffix = chain_suffix(first, n);
+        PPMaps mi = m;
+        mi.heat += first * m.sbh; mi.paf += first * m.sbp;
+        rc = pp_launch(mi, c->tab, pmx_pp_view(c->pp, first), n, map_h, map_w, img_len, dscale ? dscale + 2 * first : nullptr, 0, c->opt_pp_generic, pc.k.stream,
+                       c->prof_on == 1 ? +prof_cb : nullptr, &pc, c->pp_limbs_slices);
+    }
+    // the join, whatever happened in between: the context's stream never runs ahead of the second chain
+    PMX_HIP(hipEventRecord(ch.done, ch.stream));
+    PMX_HIP(hipStreamWaitEvent(c->stream, ch.done, 0));
+    if (rc) return rc;
+    c->pp_valid = true; c->pp_final = false; c->pp_B = B; c->pp_h = map_h; c->pp_w = map_w;
+    c->pp_maps = m; c->pp_img_len = img_len; c->pp_has_scale = scale_xy != nullptr;
+    c->pp_calls.clear();
+    return PMX_OK;
+}
+
 extern "C" int pmx_detect_batch(pmx_ctx* c, const uint8_t* img, int B, int H, int W, int on_device, int map_h, int map_w,
                                 double img_len, const double* scale_xy)
 {
+    bool chains = false;
+    if (c && img && c->opt_batch_chains && map_h >= 1 && map_w >= 1 && (long long)map_h * map_w < (1ll << 31)) {
+        int rc = check_forward_args(c, img, B, H, W);
+        if (rc) return rc;
+        PMX_DEV(c);
+        if ((rc = chains_wanted(c, img, B, H, W, &chains))) return rc;
+        if (chains) {
+            const uint8_t* d = img;
+            if (!on_device) {
+                PMX_HIP(hipMemcpyAsync(c->u8_tmp, img, (size_t)B * H * W * 3, hipMemcpyHostToDevice, c->stream));
+                d = c->u8_tmp;
+            }
+            return detect_batch_chains(c, d, B, H, W, map_h, map_w, img_len, scale_xy);
+        }
+    }
     int rc = pmx_forward_u8(c, img, B, H, W, on_device);
     if (rc) return rc;
     return pmx_postprocess(c, B, map_h, map_w, img_len, scale_xy);

@@ -163,6 +163,9 @@ int wino_select(const WinoSelectOpts& o, int ks, int cin_pad, int cout_pad, int 
                 int* run, int* tail_g);
 // images [0, n0) of a batch of B through the plain kernel, the rest through the selection of their own count; 0 = the whole batch at once
 int wino_split_images(const WinoSelectOpts& o, int ks, int cin_pad, int cout_pad, int cout, int ldc, int B, int groups, int H, int W, int pool);
+// the automatic rule of the two half-batch chains for one 7x7 layer of whole-batch form (mode, run, tail_g): the plain launches of n0 and of
+// n1 images are both whole rounds of the CUs
+bool batch_chains_rounds(const WinoSelectOpts& o, int mode, int run, int tail_g, int cout_pad, int n0, int n1, int H, int W);
 struct SplitPlan { int S; unsigned long long bounds; int sizes[8]; };
 struct SplitKReduceArgs {
     const float* slabs[2];   // per group: ksplit slabs of B x H x W x ld_slab floats

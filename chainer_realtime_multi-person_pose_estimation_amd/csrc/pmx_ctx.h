@@ -200,6 +200,23 @@ struct SegTables {
 };
 // What one network forward runs on and over, handed from its entry down to every launch by const reference: nothing a forward needs to
 // know about its own call is a member of the context.  pmx_call(c) is the call of everything that runs on the context itself.
+// Two half-batch chains (option "batch_chains"; pmx_detect_batch): the images [0, n0) of a uniform batch run on the call's stream, the images
+// [n0, B) on the context's second stream, with every buffer that is indexed by image shared at the image offset and a scratch of its own
+// for what is not (the slabs of the split-K / unit-mode / tail launches and their zero bias).  Every layer is planned ONCE for the whole
+// batch and the plan launched per chain -- layer i of chain 0, then layer i of chain 1 -- so an image's arithmetic is that of the one-chain
+// form.  `probe`: nothing is launched; the forward only finds out whether every layer keeps its whole-batch plan on a half (ok) and whether
+// the halves of every 7x7 plain launch are whole rounds of the CUs (rounds: the automatic rule, conv_select.hip::batch_chains_rounds).
+struct BatchChain {
+    Stream stream;
+    Event fork, done;
+    DevBuf<float> sk_scratch, sk_zero_bias;
+};
+struct ChainSplit {
+    int n0 = 0;                      // images of the first chain
+    size_t net_px = 0;               // pixels of one network input (what places the second chain in act0 / act1: launch_plan_chains)
+    BatchChain* second = nullptr;
+    bool probe = false, ok = true, rounds = true;
+};
 struct FwdCall {
     NetBufs& ws;                     // the working set: the context's own or a lane's
     hipStream_t stream;              // what every launch and profile event of the forward is enqueued on
@@ -207,6 +224,8 @@ struct FwdCall {
     const SegTables* seg = nullptr;  // a heterogeneous forward: its tables (null: a uniform batch)
     const uint8_t* in_u8 = nullptr;  // conv1_wino_kernel preprocesses this uint8 batch itself (null: the float input in ws.in16)
     float in_div = 255.0f;           // ... dividing by this
+    ChainSplit* split = nullptr;     // the forward runs as two half-batch chains (null: one chain)
+    BatchChain* scratch = nullptr;   // the launches of the second chain: its slabs and zero bias (null: ws.sk_scratch, the context's zero bias)
 };
 // one post-process launch set of the current results: a uniform batch is one call (base 0), a mixed batch one per segment
 struct PPCall { PPMaps maps; PPTables tab; int base, B, map_h, map_w; double img_len; bool has_scale; int limbs_slices; };
@@ -372,6 +391,12 @@ struct pmx_ctx : NetBufs {           // (the base: the context's own working set
     int opt_wino_tail_merge = 1;     // the tails of all images of a launch as one stream of tiles, 32 per block (0: one part-filled block per image)
     int opt_wino_tail_g = 0;         // tuning: chunks per pass-1 unit of the tail (0 = automatic)
     int opt_wino_split = 1;          // a batch whose plain launch ends in a part-filled round of the CUs is cut in two by images (0: never)
+    int opt_batch_chains = -1;       // pmx_detect_batch on a uniform fp32 batch as two half-batch chains on two streams (BatchChain): 0 never, 1 wherever
+                                     // every layer keeps its whole-batch plan on a half, -1 (default) by the rule of conv_select.hip::batch_chains_rounds
+    BatchChain chain2;               // the second chain: stream, events and scratch, made on first use
+    int chains_key[4] = {0, 0, 0, -1};   // (B, H, W, opt_epoch) of the last probe, chains_ok / chains_rounds its verdict
+    bool chains_ok = false, chains_rounds = false;
+    int opt_epoch = 0;               // counts pmx_set_option calls: what was decided from the options is decided again
     int opt_wino_unit_g = 0;         // tuning: chunks per pass-1 unit of a launch in unit mode (0 = automatic, -1 = as many units as 8 slabs allow)
     int opt_precision = 0;           // 0: fp32 MFMA everywhere (the path whose results are specified); 1: bf16x3 kernels where a
                                      // v6 kernel would run (fp32-grade accuracy at 2.67x the matrix rate, NOT the fp32 FMA chain);

@@ -139,6 +139,18 @@ int pmx_synchronize(pmx_ctx* ctx);                    /* cuda.get_device_from_id
  *   "wino_tail_merge" 1 | 0    batches of 46-wide maps whose tail lies in one tile row (46 x 46: 17 tiles per image): 1 (default) = the
  *                              tails of all images of the launch as one stream of tiles, 32 per block (every MFMA row a real tile);
  *                              0 = one part-filled block per image.  Same units, same bits; profile label "...r/t<g>m"
+ *   "batch_chains" 0 | 1 | -1  pmx_detect_batch on a uniform fp32 batch of B images as two independent half-batch chains: images [0, B / 2) on
+ *                              the context's stream, the rest on a second stream of the context's own, network and post-process alike,
+ *                              forked at entry and joined before the call returns (whatever is enqueued on the context's stream afterwards
+ *                              sees all B records; no host synchronisation is added).  Every layer's form and plan is chosen once for the
+ *                              whole batch and launched per half, so maps and records are bit for bit those of the one-chain call; the
+ *                              profile labels of the halves end in "@<first image>+<count>".  0 = never; 1 = wherever every layer keeps
+ *                              its whole-batch plan on a half (no layer cut by "wino_split", the merged tails mergeable per half), else one
+ *                              chain; -1 (default) = automatic: under "conv_algo" 1, when in addition the plain launch of every 7x7 layer is whole
+ *                              rounds of the CUs for each half (32 or 16 frames of 368 x 368 on 256 CUs) and the per-launch profiler
+ *                              (pmx_profile_enable 1) is off: its event pairs would time a launch's wait for the other chain.  Mixed-size batches,
+ *                              pmx_detect_precise, "precision" 1 / 2, "keep_smoothed", the loss hook, backward and training contexts
+ *                              always run one chain.  The second chain holds slab scratch of its own
  *   "precision" 0 | 1 | 2      0 (default): every convolution is the fp32 FMA chain the parity tests specify.  1: the 3x3 / 7x7
  *                              layers that run on the one-block-per-CU kernels use the bf16 matrix cores with every fp32 value
  *                              split into three bf16 terms (six products, fp32 accumulate): fp32-grade accuracy, 2.67x the
