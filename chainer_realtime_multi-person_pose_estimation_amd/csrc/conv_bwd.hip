@@ -229,6 +229,14 @@ int conv_wgrad_trunk_strips(int B, int H, int cg, int cx, int forced, int* rows)
     return pmx_wgrad_strips_cap(B, H, cg, cx, 3, forced, PMX_WGRAD_TRUNK_MAX_STRIPS, 1, rows);
 }
 
+int conv_wgrad_combine_launch(const float* ws, float* dw, int strips, int ks, int cout, int cin, int cg, int cx, const int* cin_map, hipStream_t stream)
+{
+    const long long n = (long long)ks * ks * cout * cin;
+    hipLaunchKernelGGL(conv_wgrad_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ws, dw, strips, ks * ks, cout, cin, cg, cx, cin_map);
+    PMX_HIP(hipGetLastError());
+    return PMX_OK;
+}
+
 int conv_wgrad_launch(const float* g, int ldg, const float* x, int ldx, float* ws, float* dw, int B, int H, int W, int cout, int cg, int cin, int cx,
                       int ks, int strips, int rows, const int* cin_map, hipStream_t stream, int max_strips)
 {
@@ -246,10 +254,7 @@ int conv_wgrad_launch(const float* g, int ldg, const float* x, int ldx, float* w
     else if (ks == 3) hipLaunchKernelGGL((conv_wgrad_kernel<3, 2>), grid, dim3(256), 0, stream, a);
     else hipLaunchKernelGGL((conv_wgrad_kernel<1, 4>), grid, dim3(256), 0, stream, a);
     PMX_HIP(hipGetLastError());
-    const long long n = (long long)ks * ks * cout * cin;
-    hipLaunchKernelGGL(conv_wgrad_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const float*)ws, dw, strips, ks * ks, cout, cin, cg, cx, cin_map);
-    PMX_HIP(hipGetLastError());
-    return PMX_OK;
+    return conv_wgrad_combine_launch(ws, dw, strips, ks, cout, cin, cg, cx, cin_map, stream);
 }
 
 // ------------------------------------------------------------------------------------------ head backward (pmx_backward.hip)

@@ -16,9 +16,7 @@
 // the f16 packer of pmx_packs.hip, [tap][chunk][cout_pad][16] f16 = the fp32 pack's layout) come straight from L2, one tap ahead.
 // LDS per MFMA (BN = 128): 1 KiB of A per wave and MFMA, 4 waves -> 4 KiB per 32 cycles = 128 B/clk/CU, half the 256 B/clk of ds_read_b128.
 #include "conv_direct.h"
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+#include "f16_sat.h"
 
 template <int KS>
 struct F16Cfg {
@@ -30,22 +28,7 @@ struct F16Cfg {
     static constexpr int NHF = (UNITS + 255) / 256;
 };
 
-// saturating round-to-nearest-even fp32 -> f16 of a staged float4 (the clamp first: v_cvt_f16_f32 would turn |v| >= 65520 into inf).  NaN stays
-// NaN, as in the host's f16_rn_sat: a clamp alone makes a finite value of it (fmaxf / fminf and v_med3_f32 return a non-NaN operand), so the
-// rare float4 that holds one converts those elements again, unclamped.  One v_med3_f32 per element, one unordered compare per pair
-__device__ __forceinline__ f16x4 f16_sat4(const float4 v)
-{
-    f16x4 h = {(_Float16)__builtin_amdgcn_fmed3f(v.x, -65504.f, 65504.f), (_Float16)__builtin_amdgcn_fmed3f(v.y, -65504.f, 65504.f),
-               (_Float16)__builtin_amdgcn_fmed3f(v.z, -65504.f, 65504.f), (_Float16)__builtin_amdgcn_fmed3f(v.w, -65504.f, 65504.f)};
-    if (__builtin_expect((v.x != v.x) | (v.y != v.y) | (v.z != v.z) | (v.w != v.w), 0)) {
-        if (v.x != v.x) h.x = (_Float16)v.x;
-        if (v.y != v.y) h.y = (_Float16)v.y;
-        if (v.z != v.z) h.z = (_Float16)v.z;
-        if (v.w != v.w) h.w = (_Float16)v.w;
-    }
-    return h;
-}
-
+// (the fp32 -> f16 conversion of the staged halo: f16_sat.h::f16_sat4)
 template <int KS, typename OP, int BN>
 __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvArgs a)
 {

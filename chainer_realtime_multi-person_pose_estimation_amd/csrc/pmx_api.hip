@@ -372,6 +372,11 @@ extern "C" int pmx_set_option(pmx_ctx* c, const char* key, int value)
     else if (!strcmp(key, "peaks_gpu_branch")) { c->opt_gpu_branch_peaks = value; c->tab_in_h = -1; }
     else if (!strcmp(key, "kp_flip_x")) c->opt_kp_flip_x = value != 0;
     else if (!strcmp(key, "wgrad_strips")) c->opt_wgrad_strips = value;
+    else if (!strcmp(key, "grad_precision")) {
+        PMX_CHECK(value == 0 || value == 2, PMX_ERR_INVALID,
+                  "pmx_set_option: \"grad_precision\" = %d: 0 (fp32 gradients) or 2 (f16 operands, fp32 sums; pmx_conv2d_backward only)", value);
+        c->opt_grad_precision = value;
+    }
     else if (!strcmp(key, "trunk_keep_g")) c->opt_trunk_keep_g = value != 0;
     else { pmx_set_error("pmx_set_option: unknown key '%s'", key); return PMX_ERR_INVALID; }
     return PMX_OK;
@@ -582,7 +587,7 @@ static int launch_wino_run(pmx_ctx* c, const FwdCall& k, const ConvArgs& a0, int
 static WinoSelectOpts wino_opts(const pmx_ctx* c, const FwdCall& k, int ks, int groups, int lda)
 {
     WinoSelectOpts o;
-    o.conv_algo = k.conv_algo; o.precision = c->opt_precision; o.forced_variant = c->opt_force[ks]; o.ksplit = c->opt_ksplit;
+    o.conv_algo = k.conv_algo; o.precision = k.precision; o.forced_variant = c->opt_force[ks]; o.ksplit = c->opt_ksplit;
     o.wino_unit_eff = c->opt_wino_unit_eff; o.wino_min_fill = c->opt_wino_min_fill; o.wino_geom = c->opt_wino_geom; o.wino_tail = c->opt_wino_tail;
     o.wino_tail_g = c->opt_wino_tail_g; o.wino_tail_merge = c->opt_wino_tail_merge; o.groups = groups; o.lda = lda; o.wino_unit_g = c->opt_wino_unit_g;
     o.wino_split = c->opt_wino_split; o.ncu = c->num_cus;
@@ -601,7 +606,7 @@ static bool wino_layers_ok(const PackedLayer* L0, const PackedLayer* L1)
 //   FORM_WINO        the Winograd kernel on 8 x 16 rectangles (a heterogeneous forward: over the segment table of the level)
 //   FORM_WINO_RUN    ... in the run geometry; tail_g > 0: the part-filled last blocks in unit mode, tail_g chunks per pass-1 unit
 //   FORM_WINO_UNITS  ... in unit mode, unit_g chunks per pass-1 unit
-//   FORM_F16         f16 mode (option "precision" = 2): a 3x3 / 7x7 layer as ONE conv_f16_kernel launch, whatever the batch (no Winograd, no
+//   FORM_F16         f16 mode (the call's precision = 2): a 3x3 / 7x7 layer as ONE conv_f16_kernel launch, whatever the batch (no Winograd, no
 //                    split-K, no cut by images: the per-output summation order must not depend on the launch)
 enum ConvForm { FORM_DIRECT, FORM_WINO, FORM_WINO_RUN, FORM_WINO_UNITS, FORM_F16 };
 struct ConvPlan {
@@ -639,7 +644,8 @@ static int plan_conv(pmx_ctx* c, const FwdCall& k, ConvPlan& p, const char* labe
         flops += 2.0 * npix * (double)G.cout * G.cin * G.ks * G.ks;
     }
     int rc;
-    if (c->opt_precision == 2 && ks > 1) {
+    const int precision = k.precision;       // the call's, not the context's: pmx_conv2d_backward plans z and dx under different ones
+    if (precision == 2 && ks > 1) {
         p.form = FORM_F16;
         PMX_CHECK(!k.seg || seg, PMX_ERR_INVALID, "heterogeneous forward: layer %s without a resolution level", who);
         PMX_CHECK(!L1 || (L1->ks == ks && L1->nch == L.nch && L1->cout_pad == L.cout_pad), PMX_ERR_INVALID, "conv f16: the two groups of %s differ in shape", who);
@@ -648,13 +654,13 @@ static int plan_conv(pmx_ctx* c, const FwdCall& k, ConvPlan& p, const char* labe
     } else if (seg) {
         // heterogeneous launch: the plain Winograd kernel on 8 x 16 rectangles over all segments (every 3x3 / 7x7 layer of the pose network
         // qualifies; its per-pixel arithmetic is that of a plain launch of each image alone -- oracle/conv_fma_ref::conv_wino)
-        PMX_CHECK(wino_layers_ok(L0, L1) && (c->opt_precision == 0 || c->opt_precision == 2), PMX_ERR_INVALID,
+        PMX_CHECK(wino_layers_ok(L0, L1) && (precision == 0 || precision == 2), PMX_ERR_INVALID,
                   "heterogeneous forward: layer %s has no Winograd form", who);
         p.form = FORM_WINO;
     } else {
         p.variant = conv_pick_variant(ks, L.cout_pad, H, W, B * groups, c->opt_force[ks], c->opt_kernel_gen, pool, groups == 1 ? L.cin : 9999,
-                                      c->opt_precision == 1 && ks > 1, c->num_cus);
-        if (c->opt_precision == 1 && ks > 1 && conv_bf16x3_twin(p.variant) >= 0) {
+                                      precision == 1 && ks > 1, c->num_cus);
+        if (precision == 1 && ks > 1 && conv_bf16x3_twin(p.variant) >= 0) {
             if ((rc = ensure(ensure_bf16x3_pack))) return rc;
             p.variant = conv_bf16x3_twin(p.variant);
             for (int g = 0; g < groups; ++g) a.g[g].w = (const float*)Lg[g]->d_w3.get();
@@ -2060,7 +2066,11 @@ extern "C" int pmx_conv2d_backward(pmx_ctx* c, const float* x, const float* w, c
         PMX_HIP(hipMemsetAsync(dst, 0, npix * ld * 4, c->stream));
         return launch_nchw_to_nhwc(d_x, dst, B, cin, H, W, ld, 0, c->stream);
     };
+    // option "grad_precision" = 2: dw and dx of a 3x3 / 7x7 layer with f16 operands; z (k) stays under the context's own precision
+    const bool f16 = c->opt_grad_precision == 2 && ks > 1;
     const FwdCall k = pmx_call(c);
+    FwdCall kt = k;
+    if (f16) kt.precision = 2;
     ConvPlan pz, pt;
     if (need_z) {
         if ((rc = test_layer(c, L, w, bias, cout, cin, ks)) || (rc = to_nhwc(d_xn, L.cin_pad)) || (rc = d_zn.alloc(nz))) return rc;
@@ -2082,11 +2092,11 @@ extern "C" int pmx_conv2d_backward(pmx_ctx* c, const float* x, const float* w, c
         Lt.set = true;
         PMX_HIP(hipMemsetAsync(d_dxn, 0xFF, nx * 4, c->stream));       // poison: an unwritten element is caught by the test
         // g has cg >= Lt.cin_pad channels per pixel, the padding channels zero
-        if ((rc = plan_conv(c, k, pt, nullptr, &Lt, nullptr, d_g, nullptr, cg, d_dxn, nullptr, cin, B, H, W, 0, 0, -1))) return rc;
+        if ((rc = plan_conv(c, kt, pt, nullptr, &Lt, nullptr, d_g, nullptr, cg, d_dxn, nullptr, cin, B, H, W, 0, 0, -1))) return rc;
     }
     int strips = 0, rows = 0;
     if (dw) {
-        strips = conv_wgrad_strips(B, H, cg, cx, ks, c->opt_wgrad_strips, &rows);
+        strips = f16 ? conv_wgrad_f16_strips(B, H, cg, cx, ks, c->opt_wgrad_strips, &rows) : conv_wgrad_strips(B, H, cg, cx, ks, c->opt_wgrad_strips, &rows);
         if ((rc = to_nhwc(d_x32, cx)) || (rc = d_ws.alloc((size_t)strips * T * cg * cx)) || (rc = d_dw.alloc(ndw))) return rc;
         PMX_HIP(hipMemsetAsync(d_dw, 0xFF, ndw * 4, c->stream));
     }
@@ -2096,9 +2106,11 @@ extern "C" int pmx_conv2d_backward(pmx_ctx* c, const float* x, const float* w, c
         if (int r = conv_bwd_mask_launch(d_dy, d_zn, cout, d_g, B, H, W, cout, cg, relu, pool, c->stream)) return r;
         return db ? conv_bwd_db_launch(d_g, cg, d_part, d_db, (long long)npix, cout, cg, c->stream) : PMX_OK;
     };
-    auto data_grad = [&]() -> int { return dx ? launch_plan(c, k, pt) : PMX_OK; };
+    auto data_grad = [&]() -> int { return dx ? launch_plan(c, kt, pt) : PMX_OK; };
     auto weight_grad = [&]() -> int {
-        return dw ? conv_wgrad_launch(d_g, cg, d_x32, cx, d_ws, d_dw, B, H, W, cout, cg, cin, cx, ks, strips, rows, nullptr, c->stream) : PMX_OK;
+        if (!dw) return PMX_OK;
+        return (f16 ? conv_wgrad_f16_launch : conv_wgrad_launch)(d_g, cg, d_x32, cx, d_ws, d_dw, B, H, W, cout, cg, cin, cx, ks, strips, rows, nullptr, c->stream,
+                                                                 PMX_WGRAD_MAX_STRIPS);
     };
     Event e0, e1;
     auto timed = [&](const std::function<int()>& part, double* ms_out) -> int {

@@ -221,6 +221,7 @@ struct FwdCall {
     NetBufs& ws;                     // the working set: the context's own or a lane's
     hipStream_t stream;              // what every launch and profile event of the forward is enqueued on
     int conv_algo;                   // option "conv_algo" for this forward
+    int precision;                   // option "precision" for this forward (pmx_conv2d_backward's data gradient under "grad_precision" 2: 2)
     const SegTables* seg = nullptr;  // a heterogeneous forward: its tables (null: a uniform batch)
     const uint8_t* in_u8 = nullptr;  // conv1_wino_kernel preprocesses this uint8 batch itself (null: the float input in ws.in16)
     float in_div = 255.0f;           // ... dividing by this
@@ -449,6 +450,8 @@ struct pmx_ctx : NetBufs {           // (the base: the context's own working set
     int lg_stages = 0, lg_B = 0, lg_fh = 0, lg_fw = 0;    // the hooked forward whose gradients ls_grad holds (lg_stages 0: none)
     // pmx_conv2d_backward: test-only, S0 of the weight-gradient strips (0: automatic); include/pose_mi355x.h
     int opt_wgrad_strips = 0;
+    // pmx_conv2d_backward: 0 fp32 gradients; 2: dw and dx of a 3x3 / 7x7 layer with f16 operands and fp32 sums (include/pose_mi355x.h)
+    int opt_grad_precision = 0;
     int opt_trunk_keep_g = 0;        // read by pmx_backward_enable(2): keep the masked gradient of every trunk layer for pmx_get_retained (tests)
     // pmx_samples.hip (sample preparation).  sp: [descriptors | resize tables | host sources]; sp_a: the resized intermediates of the
     // training samples; sp_out: max_batch x insize x insize x 3 prepared images; sp_mask_raw / sp_mask_tmp / sp_mask: the mask before, between
@@ -476,8 +479,8 @@ constexpr int PMX_LOSS_SLOTS = 7;
 constexpr int PMX_LOSS_MAX_BLOCKS = 256;
 
 #define PMX_DEV(c) PMX_HIP(hipSetDevice((c)->device))
-// the default call of a context: its own working set, its stream, its "conv_algo"
-static inline FwdCall pmx_call(pmx_ctx* c) { return FwdCall{*c, c->stream, c->opt_conv_algo}; }
+// the default call of a context: its own working set, its stream, its "conv_algo" and "precision"
+static inline FwdCall pmx_call(pmx_ctx* c) { return FwdCall{*c, c->stream, c->opt_conv_algo, c->opt_precision}; }
 
 // pmx_api.hip
 // the network on a uint8 BGR batch on the device: preprocess (x / divisor - 0.5) + forward; where conv1 runs as conv1_wino_kernel the
@@ -530,6 +533,13 @@ int conv_bwd_db_launch(const float* g, int ldg, double* part, float* db, long lo
 int conv_wgrad_launch(const float* g, int ldg, const float* x, int ldx, float* ws, float* dw, int B, int H, int W, int cout, int cg, int cin, int cx,
                       int ks, int strips, int rows, const int* cin_map, hipStream_t stream, int max_strips = PMX_WGRAD_MAX_STRIPS);
 int conv_wgrad_strips(int B, int H, int cg, int cx, int ks, int forced, int* rows);      // S and, in *rows, R of the header's rule
+// the combine of both weight-gradient kernels: dw (OIHW) = the strips' slots [strip][tap][cg][cx] of ws added left to right
+int conv_wgrad_combine_launch(const float* ws, float* dw, int strips, int ks, int cout, int cin, int cg, int cx, const int* cin_map, hipStream_t stream);
+// conv_wgrad_f16.hip: the weight gradient of a 3x3 / 7x7 layer with f16 operands (option "grad_precision" = 2): conv_wgrad_launch's arguments
+// and workspace, ldg / ldx multiples of 4 and g / x 16-byte aligned; (strips, rows) from conv_wgrad_f16_strips
+int conv_wgrad_f16_launch(const float* g, int ldg, const float* x, int ldx, float* ws, float* dw, int B, int H, int W, int cout, int cg, int cin, int cx,
+                          int ks, int strips, int rows, const int* cin_map, hipStream_t stream, int max_strips = PMX_WGRAD_MAX_STRIPS);
+int conv_wgrad_f16_strips(int B, int H, int cg, int cx, int ks, int forced, int* rows);
 int conv_wgrad_trunk_strips(int B, int H, int cg, int cx, int forced, int* rows);        // ... of the trunk chain's rule (3x3 layers)
 // conv_bwd.hip: the trunk backward's own launches (include/pose_mi355x.h: pmx_backward_trunk)
 //   conv1_wgrad  dw[64][3][3][3] of conv1_1 from g (ldg >= 64 floats per pixel) and the prepared input x16 (PMX_IN_C floats per pixel);

@@ -273,7 +273,7 @@ static int precise_add_scale(pmx_ctx* c, const uint8_t* imgs, int scaled_h, int 
     // (-1 = only with all four lanes in use: a lane that carries two scales one after the other wants the latency-oriented forms --
     //  three lanes 15.0 -> 20.4 ms, two 16.0 -> 25.0 with the plain kernels, profiles/r06_precise_probe_lanes.json)
     const bool plain = c->opt_precise_plain < 0 ? c->opt_precise_lanes >= PMX_PR_LANES : c->opt_precise_plain != 0;
-    const FwdCall call{ws, st, plain && c->opt_conv_algo == 1 ? 2 : c->opt_conv_algo};
+    const FwdCall call{ws, st, plain && c->opt_conv_algo == 1 ? 2 : c->opt_conv_algo, c->opt_precision};
     if ((rc = pmx_forward_from_u8(c, call, ws.u8_tmp, n, ph, pw, 255.0f))) return rc;
     // (3) x8 cubic up-sampling of the PAF (38) and heat (19) channels of all images into PLANAR temporaries [n][38][ph][pw] | [n][19][ph][pw]
     // (two cv2.resize calls per image in the reference; planar so that step (4) reads rows of one channel and both steps store full rows)

@@ -39,6 +39,28 @@ static inline int pmx_wgrad_strips_cap(int B, int H, int cg, int cx, int ks, int
     return pmx_wgrad_cut((long long)B * H, s0, cap, round_down, rows);
 }
 
+/* the f16 kernel (conv_wgrad_f16.hip; option "grad_precision" = 2).  A block of four waves owns (tap row, 4 x 32 co, NCI x 32 ci), NCI = 1 / 2
+ * for 7x7 / 3x3.  Every image row is cut into ceil(W / 16) GROUPS of 16 consecutive pixels, the last one padded with zero operands; an
+ * accumulator sees one MFMA per group, the groups of a row left to right, the rows of its strip top to bottom.  The strips: as many as
+ * give PMX_WGRAD_F16_WAVES waves, R = ceil(B * H / S0) rows each, as the fp32 rule. */
+#define PMX_WGRAD_F16_WAVES 4096 /* 256 CUs x 4 SIMDs x 4: measured, EXPERIMENTS.md E54 */
+static inline int pmx_wgrad_f16_nci(int ks) { return ks == 7 ? 1 : 2; }
+static inline int pmx_wgrad_f16_blocks(int cg, int cx, int ks)
+{
+    const int per = pmx_wgrad_f16_nci(ks);
+    return (cg / 32 + 3) / 4 * ks * ((cx / 32 + per - 1) / per);
+}
+static inline int pmx_wgrad_f16_groups(int W) { return (W + 15) / 16; }
+static inline int pmx_wgrad_f16_strips(int B, int H, int cg, int cx, int ks, int forced, int cap, int* rows)
+{
+    long long s0 = forced;
+    if (s0 <= 0) {
+        const long long waves = 4ll * pmx_wgrad_f16_blocks(cg, cx, ks);
+        s0 = (PMX_WGRAD_F16_WAVES + waves - 1) / waves;
+    }
+    return pmx_wgrad_cut((long long)B * H, s0, cap, 0, rows);
+}
+
 /* conv1_1's kernel: one wave per strip, `cap` (PMX_WGRAD_CONV1_STRIPS = PMX_WGRAD_WAVES) strips asked for, rows rounded down: at least
  * PMX_WGRAD_WAVES strips whenever B * H >= PMX_WGRAD_WAVES, fewer than twice as many */
 static inline int pmx_wgrad_conv1_strips(int B, int H, int forced, int cap, int* rows)

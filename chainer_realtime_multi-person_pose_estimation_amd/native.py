@@ -27,7 +27,7 @@ LIB_PATH = os.path.join(CSRC, 'libpose_mi355x.so')
 HEADER = os.path.join(os.path.dirname(HERE), 'include', 'pose_mi355x.h')
 SOURCES = [('pmx_api.hip', []), ('pmx_precise.hip', []), ('pmx_multi.hip', []), ('pmx_precise_images.hip', ['-ffp-contract=off']), ('conv_mfma.hip', []), ('conv_wino.hip', ['-mllvm', '-pragma-unroll-threshold=200000']), ('conv1_wino.hip', []), ('conv_f16.hip', []), ('conv_select.hip', []), ('prep.hip', ['-ffp-contract=off']),
            ('postproc.hip', ['-ffp-contract=off']), ('pmx_boxes.hip', ['-ffp-contract=off']), ('pmx_loss.hip', ['-ffp-contract=off']),
-           ('pmx_samples.hip', ['-ffp-contract=off']), ('conv_bwd.hip', ['-ffp-contract=off']),
+           ('pmx_samples.hip', ['-ffp-contract=off']), ('conv_bwd.hip', ['-ffp-contract=off']), ('conv_wgrad_f16.hip', ['-ffp-contract=off']),
            ('pmx_backward.hip', ['-ffp-contract=off']), ('pmx_packs.hip', ['-ffp-contract=off']),
            ('pmx_train.hip', ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt']),
            ('pmx_render.hip', ['-ffp-contract=off']), ('pmx_masks.hip', ['-ffp-contract=off']),
@@ -37,7 +37,7 @@ SOURCES = [('pmx_api.hip', []), ('pmx_precise.hip', []), ('pmx_multi.hip', []), 
 # library is rebuilt when the variable changes)
 if os.environ.get('PMX_BUILD_BF16X3', '') not in ('', '0'):
     SOURCES.append(('conv_bf16x3.hip', []))
-HEADERS = ['pmx_common.h', 'pmx_ctx.h', 'pp_tables.h', 'wino_util.h', 'conv_direct.h', 'pp_smooth.h', 'pack_index.h', 'wgrad_strips.h', 'f16_round.h', HEADER]
+HEADERS = ['pmx_common.h', 'pmx_ctx.h', 'pp_tables.h', 'wino_util.h', 'conv_direct.h', 'pp_smooth.h', 'pack_index.h', 'wgrad_strips.h', 'f16_round.h', 'f16_sat.h', HEADER]
 
 N_JOINTS, N_LIMBS, N_PAF, N_HEAT = 18, 19, 38, 19
 # the detectors' precision= keyword -> engine option "precision" (include/pose_mi355x.h): fp32 (default), bf16x3 (opt-in build), f16 mode
@@ -1520,7 +1520,9 @@ class Engine(object):
     def conv2d_backward(self, x, W, b, dy, relu=False, pool=False, want=('dx', 'dw', 'db', 'z'), iters=0):
         """The gradients of one convolution layer (include/pose_mi355x.h::pmx_conv2d_backward): a dict with the arrays named in `want`
         ('dx' like x, 'dw' like W, 'db' (cout,), 'z' (B, cout, H, W): the convolution's output before ReLU and pool) and, with iters > 0,
-        'ms' = the mean milliseconds of (data gradient, weight gradient, mask + bias gradient)."""
+        'ms' = the mean milliseconds of (data gradient, weight gradient, mask + bias gradient).  Option "grad_precision" = 2
+        (set_option; default 0 = fp32) computes dw and dx of a 3x3 / 7x7 layer with f16 operands and fp32 sums; z, db and 1x1 layers keep
+        every bit."""
         x = np.ascontiguousarray(x, dtype=np.float32)
         W = np.ascontiguousarray(W, dtype=np.float32)
         dy = np.ascontiguousarray(dy, dtype=np.float32)

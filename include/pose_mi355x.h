@@ -178,6 +178,11 @@ int pmx_synchronize(pmx_ctx* ctx);                    /* cuda.get_device_from_id
  *                              layers whose padded channel count is a multiple of 128; the others stay at 64).  Same bits either way
  *                              (the order above does not depend on it); per context; profile labels unchanged.  Any other value:
  *                              PMX_ERR_INVALID, the option unchanged
+ *   "grad_precision" 0 | 2     pmx_conv2d_backward only (the values are named like "precision"): 0 (default) fp32 gradients; 2: dw and dx of
+ *                              a 3x3 / 7x7 layer with f16 operands and fp32 sums (the f16 paragraph of pmx_conv2d_backward).  z, g, db
+ *                              and the 1x1 layers keep every bit.  pmx_backward_head, pmx_backward_trunk and the train steps do NOT read
+ *                              it: they stay fp32.  Per context.  Any other value (1, bf16x3, included): PMX_ERR_INVALID, the option
+ *                              unchanged
  *   "fuse_conv1" 1 | 0         conv1_1 recomputed on conv1_2's halo tiles, one launch instead of two (default 1); identical bits
  *   "precise_lanes" 1..4       detect_precise: inference scales in flight at once, each on its own stream and working set (default 4;
  *                              1: one after the other on the context's stream); same bits
@@ -726,12 +731,40 @@ int pmx_conv2d_pair(pmx_ctx* ctx, const float* x0_nchw, const float* x1_nchw, co
  *                                     part[s] = acc;
  *            dw = part[0];  for s = 1 .. S-1: dw = dw + part[s];                                            (float32 adds, left to right)
  *   db   db[co] = sum over (n, y, x) of g[n,co,y,x]: float64 sums in fixed slots added in slot order, cast to float32.
+ * Option "grad_precision" = 2 (default 0: everything above): dw and dx of a 3x3 / 7x7 layer with f16 operands and fp32 sums.  z is still
+ * computed under the context's own options in fp32, the mask and db do not change: z, g and db keep every bit, and so does all of a 1x1
+ * layer.  f16(v) is csrc/f16_round.h::f16_rn_sat: round to nearest even, saturating at +-65504, subnormals and NaN kept.
+ *   dw   dw[co][ci][ky][kx] = sum over (n, y, x) of f16(g[n,co,y,x]) * f16(x[n,ci,y+ky-p,x+kx-p]), out-of-image taps as zeros.  Every product
+ *        is exact in fp32; the products are summed in fp32 in a fixed order.  One launch of conv_wgrad_f16_kernel
+ *        (csrc/conv_wgrad_f16.hip, v_mfma_f32_32x32x16_f16; g and x are rounded while they are staged, no f16 copy of an activation is
+ *        written) + the combine launch of the fp32 path.  THE GROUPS: every image row of w pixels is cut into ceil(w / 16) groups of 16
+ *        consecutive pixels; the last group of a row is padded with zero operands (a group never crosses a row, so a tap shift is one
+ *        uniform pixel offset).  THE STRIPS: the B*h image rows are cut into S strips of R = ceil(B*h / S0) consecutive rows, S0 =
+ *        option "wgrad_strips" if > 0, else ceil(4096 / (4 * blocks)) with blocks = ceil(round_up(cout, 32) / 128) * ksize *
+ *        ceil(round_up(cin, 32) / (ksize == 7 ? 32 : 64)), the blocks of four waves one strip takes; S0 <= PMX_WGRAD_MAX_STRIPS and
+ *        <= B*h; S = ceil(B*h / R) (csrc/wgrad_strips.h: pmx_wgrad_f16_strips; the workspace is the fp32 path's).  THE ORDER, per
+ *        (co, ci, ky, kx): within a strip one MFMA per group adds the group's 16 products to the accumulator, the groups of a row left to
+ *        right, the rows top to bottom; each strip's accumulator goes to its own workspace slot and the slots are added left to right
+ *        in float32.  The order of the 16 products inside one MFMA belongs to the hardware, so there is no bit-exact host twin for
+ *        arbitrary inputs: |dw - the float64 sum of the same products| <= (16 + R * ceil(w / 16) + S) * 2^-23 * sum |f16(g) * f16(x)|,
+ *        and inputs on which every partial sum is exact give the exact result (tests/f16_grad_emulation.py).  No atomics: the same
+ *        bits on every run and under every forward option.
+ *        Non-finite operands: f16() saturates, so an infinity in g or x enters the sums as +-65504 and dw stays finite (db, a float64
+ *        sum of the unrounded g, does not).  A NaN in g[., co, ., .] (in x[., ci, ., .]) makes NaN every dw[co][.][.][.] (every
+ *        dw[.][ci][.][.]) whose sum holds it, and leaves every other co (ci) untouched.  Pad pixels and out-of-image taps are ZERO
+ *        OPERANDS, not skipped products, and 0 * NaN = NaN: for a NaN at a pixel closer than p to the image border, or to the pad
+ *        pixels of a row's last group, the elements of the same co (ci) whose exact sum pairs it with an out-of-image tap or a pad
+ *        pixel are NaN as well.
+ *   dx   the f16 form of the dispatcher (the f16 inference contract above, applied to (g, w')): ONE conv_f16_kernel launch on the f16 pack
+ *        of the transposed layer, which rounds g while staging; option "f16_bn" applies as to a forward, with the same bits either way.
+ * Loss scaling is deliberately not part of any kernel: everything after the mask is linear in dy and the masks do not depend on dy, so a
+ * caller whose gradients would fall below the f16 range scales dy by 2^k and un-scales dx, dw and db by 2^-k (exact in fp32).
  * Each of dx, dw, db, z may be NULL; a NULL output's work is skipped (z is still computed when relu or pool need it).  avg_ms3 may be NULL;
  * with iters > 0 it receives the mean time over `iters` repetitions of [0] the data-gradient plan, [1] the weight-gradient launches
  * (combine included), [2] the mask + bias-gradient launches, each timed on its own between two events (0 for a part that was skipped).
  * Errors, checked before anything is enqueued (the context stays usable): PMX_ERR_INVALID for a null x, w or dy, for all four outputs NULL,
  * for ksize outside {1, 3, 7}, for a non-positive shape or pool with odd h or w; PMX_ERR_STATE when option "precision" is not 0 (the f16
- * and bf16x3 modes are inference modes).  Option "wgrad_strips" (0 = automatic) exists for the tests: it only moves the strip borders. */
+ * and bf16x3 modes are inference modes), whatever "grad_precision" is.  Option "wgrad_strips" (0 = automatic) exists for the tests: it only moves the strip borders. */
 #define PMX_WGRAD_MAX_STRIPS 32
 int pmx_conv2d_backward(pmx_ctx* ctx, const float* x_nchw, const float* w_oihw, const float* bias, const float* dy_nchw,
                         int batch, int cin, int h, int w, int cout, int ksize, int relu, int pool,
