@@ -109,13 +109,7 @@ __global__ __launch_bounds__(256) void kp_tiles_kernel(PPMaps maps, const KpCrop
         const int r = i / PK_TS, c = i - r * PK_TS;
         const int y = y0 + r, x = x0 + c;
         if (y < map_h && x < map_w) {
-            const float v = sS[(r + 1) * SW + (c + 1)];
-            const int idx = y * map_w + x;
-            if (v > a.v) { a.v = v; a.cnt = 1; a.i0 = idx; a.i1 = INT_MAX; }
-            else if (v == a.v) {
-                a.cnt += 1;
-                if (idx < a.i0) { a.i1 = a.i0; a.i0 = idx; } else if (idx < a.i1) a.i1 = idx;
-            }
+            argmax_take(a, sS[(r + 1) * SW + (c + 1)], y * map_w + x);        // (a NaN makes the record NaN: pp_smooth.h)
         }
     }
     const int lane = tid & 63, wave = tid >> 6;

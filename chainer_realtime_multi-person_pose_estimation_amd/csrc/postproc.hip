@@ -654,9 +654,7 @@ __global__ __launch_bounds__(256) void pp_argmax_kernel(const float* __restrict_
     ArgMax a;
     a.v = -INFINITY; a.cnt = 0; a.i0 = 0x7fffffff; a.i1 = 0x7fffffff;
     for (int i = tid; i < n; i += 256) {
-        const float v = m[i];
-        if (v > a.v) { a.v = v; a.cnt = 1; a.i0 = i; a.i1 = 0x7fffffff; }
-        else if (v == a.v) { a.cnt += 1; if (a.i1 == 0x7fffffff) a.i1 = i; }     // own indices ascend
+        argmax_take(a, m[i], i);        // (a NaN makes the record NaN: pp_smooth.h)
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {
@@ -670,7 +668,7 @@ __global__ __launch_bounds__(256) void pp_argmax_kernel(const float* __restrict_
         ArgMax r = sred[0];
         for (int w = 1; w < 4; ++w) r = argmax_merge(r, sred[w]);
         double* o = out + ((long long)b * n_ch + ch) * 4;
-        const bool valid = (double)r.v > thresh;        // np.float32 scalar > python float: float64 comparison
+        const bool valid = (double)r.v > thresh;        // np.float32 scalar > python float: float64 comparison; false for a NaN maximum
         int x = r.i0 % map_w, y = r.i0 / map_w;
         if (r.cnt >= 2) { x = r.i1 / map_w; }            // (sic) coords[1] is the SECOND maximum's row when k >= 2
         o[0] = valid ? (double)x : 0.0;

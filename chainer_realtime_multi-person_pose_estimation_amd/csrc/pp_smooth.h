@@ -177,10 +177,33 @@ _Pragma("unroll")                                                               
 // Per-channel arg-max of the key-point nets (postproc.hip::pp_argmax_kernel, pmx_boxes.hip): the reference's
 // `np.where(heatmap == max_value)` needs the maximum, its multiplicity and the two smallest row-major indices.  The merge is exact,
 // commutative and associative: partial records of any partition of a map merge to the record of the whole map.
-struct ArgMax { float v; int cnt; int i0; int i1; };   // max value, multiplicity, two smallest row-major indices
+// NaN: `heatmap.max()` of a map that holds a NaN anywhere is NaN, `max_value > thresh` is then false and the key point is None.  A plain
+// '>' / '==' scan skips a NaN, so the scans call argmax_take, which turns the record into the one NaN record (argmax_nan: the same bits
+// whatever the NaN's payload and wherever it was met), and the merge lets that record absorb any other: still exact, commutative and
+// associative.
+struct ArgMax { float v; int cnt; int i0; int i1; };   // max value, multiplicity, two smallest row-major indices (16 bytes)
+
+__device__ __forceinline__ ArgMax argmax_nan()
+{
+    ArgMax r;
+    r.v = __builtin_nanf(""); r.cnt = 0; r.i0 = 0x7fffffff; r.i1 = 0x7fffffff;
+    return r;
+}
+
+// one more value of a scan whose indices are unique (ascending or not)
+__device__ __forceinline__ void argmax_take(ArgMax& a, float v, int idx)
+{
+    if (v != v || a.v != a.v) { a = argmax_nan(); return; }
+    if (v > a.v) { a.v = v; a.cnt = 1; a.i0 = idx; a.i1 = 0x7fffffff; }
+    else if (v == a.v) {
+        a.cnt += 1;
+        if (idx < a.i0) { a.i1 = a.i0; a.i0 = idx; } else if (idx < a.i1) a.i1 = idx;
+    }
+}
 
 __device__ __forceinline__ ArgMax argmax_merge(const ArgMax& a, const ArgMax& b)
 {
+    if (a.v != a.v || b.v != b.v) return argmax_nan();
     if (a.v > b.v) return a;
     if (b.v > a.v) return b;
     ArgMax r;

@@ -243,7 +243,22 @@ int pmx_set_maps(pmx_ctx* ctx, const float* paf_nchw, const float* heat_nchw, in
  * image pixels (:513-514) + subsets_to_pose_array (:252-265), all on the device.
  * img_len: :511 passes map_w (fast path), :478 orig_img_w (precise path).
  * scale_xy: per image (sx, sy) = (orig_w / map_w, orig_h / map_h) as float64, or NULL for (1, 1).
- * gauss_w: the 2*radius+1 float64 taps scipy's gaussian_filter(sigma=2.5) uses (NULL -> computed in C). */
+ * gauss_w: the 2*radius+1 float64 taps scipy's gaussian_filter(sigma=2.5) uses (NULL -> computed in C).
+ * Radii and sizes: pmx_set_gaussian takes radius 0 .. 16 (sigma up to 4.0 at SciPy's truncate = 4; radius 0 is the identity filter),
+ * PMX_ERR_INVALID beyond.  Radius 10 without "pp_generic" runs the fast peak kernel, every other radius the generic one: same bits.
+ * map_h x map_w may be any size from 1 x 1 with map_h * map_w < 2^31, whatever the size of the network output: larger (the usual
+ * up-sampling), equal (the resize is then the identity, except that a zero weight next to an infinity gives NaN, as in the reference),
+ * smaller (down-sampling), narrower than the filter radius on either axis (SciPy's 'reflect' then wraps more than once), one pixel wide.
+ * Non-finite maps (pmx_postprocess, pmx_postprocess_images, pmx_detect_batch, pmx_detect_images, detect_precise; the forward's contract
+ * is under option "precision"): the resize and the filter follow IEEE arithmetic in the reference's order, so the smoothed maps are
+ * non-finite exactly where the reference's are.  Every comparison is the reference's ordered one: a non-finite smoothed value is never a
+ * peak (NaN > x is false; -inf exceeds nothing; a filter of radius >= 1 spreads +inf to the neighbours, which it then does not exceed
+ * -- only at radius 0 can a lone +inf be a peak, as in the reference), and neither is a pixel with a NaN 4-neighbour; the rest of the
+ * channel and the other channels are not affected.  A limb score that is NaN (a NaN sample, or +inf and -inf samples together) is
+ * never a candidate; +inf scores are kept, sort first among the candidates (ties by pair index, as the reference's stable sort) and
+ * reach the connection, subset and person scores as +inf.  The threshold pruning of the
+ * fast peak kernel ignores NaN pixels (fmaxf): no peak can exist where it exits, so the result is the reference's.  status stays 0.
+ * tests/test_gpu_postprocess_edges.py; the oracle is pinned to the verbatim reference on the same inputs. */
 int pmx_set_gaussian(pmx_ctx* ctx, const double* taps, int radius);
 int pmx_postprocess(pmx_ctx* ctx, int batch, int map_h, int map_w, double img_len, const double* scale_xy);
 
@@ -274,7 +289,12 @@ int pmx_precise_table_stats(pmx_ctx* ctx, int* cached, int* trims);
 
 /* FaceDetector / HandDetector post-process (face_detector.py:37-38,58-68; hand_detector.py:41,68-78) for facenet / handnet
  * contexts: F.resize_images(hs[-1], (out_h, out_w)) + gaussian_filter + per-channel arg-max.  out: batch x (maps - 1) x 4
- * float64 rows (x, y, confidence, valid); valid = 0 where the reference appends None.  Synchronises. */
+ * float64 rows (x, y, confidence, valid); valid = 0 where the reference appends None.  Synchronises.
+ * Non-finite maps (pmx_keypoints, pmx_keypoints_images, pmx_keypoints_boxes, pmx_keypoints_boxes_images): `heatmap.max()` of a smoothed
+ * channel that holds a NaN anywhere is NaN and `max_value > thresh` is false, so such a channel yields no key point: valid = 0, x = y = 0
+ * and confidence = NaN, however large its finite values are.  A channel whose maximum is +inf yields the key point of its +inf pixels
+ * (the tie rule for equal maxima applies) with confidence +inf; -inf pixels never win.  The other channels are not affected.  Sizes and
+ * radii as for pmx_postprocess. */
 int pmx_keypoints(pmx_ctx* ctx, int batch, int out_h, int out_w, double thresh, double* out);
 
 /* ---- face / hand key points for many boxes of ONE image (demo.py:30-55: per person a face crop and two hand crops) ------------------

@@ -1,6 +1,6 @@
 """TEST INFRASTRUCTURE -- runs the *verbatim* reference code from /root/reference (read-only, imported where it lies).
 
-Used only by the golden generators (`oracle/make_golden.py`, `oracle/make_golden_net.py`, `oracle/ref_goldens.py`) and
+Used only by the golden generators (`oracle/make_golden.py`, `oracle/make_golden_net.py`, `oracle/ref_goldens.py`, `oracle/ref_edge_goldens.py`) and
 `tools/time_reference_cpu.py`, and only where the reference exists (REFERENCE_DIR below).  The tests read what those generators recorded under tests/golden/; neither
 they nor the product package import this module.
 

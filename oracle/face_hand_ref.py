@@ -61,11 +61,11 @@ def cpm_forward(weights, x):
     return [o.numpy() for o in outs]
 
 
-def compute_keypoints(heatmaps, thresh):
+def compute_keypoints(heatmaps, thresh, sigma=P.GAUSSIAN_SIGMA):
     """heatmaps (n_maps, H, W) float32 already resized to the crop -> list of [x, y, conf] | None (last channel dropped)"""
     out = []
     for i in range(heatmaps.shape[0] - 1):
-        hm = P.gaussian_filter_ref(heatmaps[i])
+        hm = P.gaussian_filter_ref(heatmaps[i], sigma)
         max_value = hm.max()
         if float(max_value) > thresh:
             coords = np.array(np.where(hm == max_value)).flatten().tolist()
