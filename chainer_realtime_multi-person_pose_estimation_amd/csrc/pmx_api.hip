@@ -520,12 +520,8 @@ static int launch_wino_units(pmx_ctx* c, const FwdCall& k, const ConvArgs& a0, i
     return conv_splitk_reduce(r, groups, k.stream);
 }
 
-// Run geometry of the Winograd kernel (46-pixel-wide maps): the full blocks [0, nfull) of every image as one plain launch; the part-filled
-// last block of every image in unit mode (S units of g pass-1 chunks (+ row 6, column 6, tap (6, 6)) writing compact slabs) + the combine
-// kernel.  B = 32 at 46 x 46: 16 x 32 x 2 = 1024 full blocks = exactly 4 rounds of the 256 CUs, then 64 x 7 short unit blocks, instead of
-// 5 rounds of 18 x 32 x 2 rectangles.  tail_g = 0: every block (also the part-filled one) in the plain launch.
-// profile entry of a layer's launch.  suffix: "@<first image>+<count>" on one half of a batch cut in two by images (run_conv), the last
-// thing of every label of the launch
+// profile entry of a layer's launch.  suffix: "@<first image>+<count>" on a part of a batch cut by images (run_conv, for_each_part), the
+// last thing of every label of the launch
 struct ConvProf {
     std::string name; double flops, bytes, issued; std::string suffix;
     std::string label(const char* part = "") const { return name + part + suffix; }
@@ -535,6 +531,10 @@ static bool wino_tail_merged(const pmx_ctx* c, const ConvArgs& a)
 {
     return c->opt_wino_tail_merge != 0 && wino_tail_mergeable(a.B, a.H, a.W, a.lda);
 }
+// Run geometry of the Winograd kernel (46-pixel-wide maps): the full blocks [0, nfull) of every image as one plain launch; the part-filled
+// last block of every image in unit mode (S units of g pass-1 chunks (+ row 6, column 6, tap (6, 6)) writing compact slabs) + the combine
+// kernel.  B = 32 at 46 x 46: 16 x 32 x 2 = 1024 full blocks = exactly 4 rounds of the 256 CUs, then 64 x 7 short unit blocks, instead of
+// 5 rounds of 18 x 32 x 2 rectangles.  tail_g = 0: every block (also the part-filled one) in the plain launch.
 static int launch_wino_run(pmx_ctx* c, const FwdCall& k, const ConvArgs& a0, int ks, int groups, int tail_g, const ConvProf* pf)      // (pf null: not profiled)
 {
     const int ntiles = PMX_WINO_RUN_TX * ((a0.H + 1) / 2), nblk = (ntiles + PMX_WINO_RUN_TILES - 1) / PMX_WINO_RUN_TILES, nfull = ntiles / PMX_WINO_RUN_TILES;
@@ -611,6 +611,7 @@ static bool wino_layers_ok(const PackedLayer* L0, const PackedLayer* L1)
 enum ConvForm { FORM_DIRECT, FORM_WINO, FORM_WINO_RUN, FORM_WINO_UNITS, FORM_F16 };
 struct ConvPlan {
     ConvForm form = FORM_DIRECT;
+    ConvIO io;                       // what the caller said (launch_plan_chains slices it by images)
     ConvArgs a;                      // the FINAL result (real bias, ReLU, pool, output slices), weights = the pack of the form
     int ks = 0, groups = 1, variant = 0, unit_g = 0, tail_g = 0;
     SplitPlan split{};
@@ -618,29 +619,34 @@ struct ConvPlan {
     ConvProf pf;
 };
 
-// in/out pointers are already offset to the group's channels; L1 null: one group; label null: never profiled
-// `level` (heterogeneous forward only, k.seg set): the resolution level of the layer's input, 0 = network input .. 3 = 1/8; B, H, W
-// then carry the image count and the LARGEST map of the level (launch checks), the geometry comes from the segment table of the level.
-// Makes sure the derived pack of the form exists.
-static int plan_conv(pmx_ctx* c, const FwdCall& k, ConvPlan& p, const char* label, PackedLayer* L0, PackedLayer* L1, const float* in0, const float* in1, int lda,
-                     float* out0, float* out1, int ldc, int B, int H, int W, int relu, int pool, int level)
+// what `io` says, in the launch arguments (the weights, and whatever else the kernel form decides, are the caller's)
+static void args_io(ConvArgs& a, const ConvIO& io)
+{
+    a.B = io.B; a.H = io.H; a.W = io.W; a.lda = io.lda; a.ldc = io.ldc; a.relu = io.relu; a.pool = io.pool;
+    for (int g = 0; g < 2; ++g) { a.g[g].in = io.in[g]; a.g[g].out = io.out[g]; }
+}
+
+// L1 null: one group (io.in[1], io.out[1] unused); label null: never profiled.  Makes sure the derived pack of the form exists.
+static int plan_conv(pmx_ctx* c, const FwdCall& k, ConvPlan& p, const char* label, PackedLayer* L0, PackedLayer* L1, const ConvIO& io)
 {
     const PackedLayer& L = *L0;
     const int ks = L.ks, groups = L1 ? 2 : 1;
+    const int lda = io.lda, ldc = io.ldc, B = io.B, H = io.H, W = io.W, pool = io.pool, level = io.level;
     const char* who = label ? label : "pmx_conv2d";
     const bool seg = k.seg && level >= 0;
     const double npix = seg ? (double)k.seg->pix[level] : (double)B * H * W;
     PackedLayer* const Lg[2] = {L0, L1};
     auto ensure = [&](int (*fn)(hipStream_t, PackedLayer&)) { const int rc = fn(k.stream, *L0); return rc || !L1 ? rc : fn(k.stream, *L1); };
-    p.ks = ks; p.groups = groups;
+    p.ks = ks; p.groups = groups; p.io = io;
     p.prof = label && (c->prof_on == 1 || (c->prof_on == 2 && ks == 7));
     ConvArgs& a = p.a;
     memset(&a, 0, sizeof a);
-    a.B = B; a.H = H; a.W = W; a.lda = lda; a.ldc = ldc; a.nch = L.nch; a.cout_pad = L.cout_pad; a.relu = relu; a.pool = pool;
+    args_io(a, io);
+    a.nch = L.nch; a.cout_pad = L.cout_pad;
     double flops = 0;
     for (int g = 0; g < groups; ++g) {
         const PackedLayer& G = *Lg[g];
-        a.g[g].in = g ? in1 : in0; a.g[g].w = G.d_w; a.g[g].bias = G.d_b; a.g[g].out = g ? out1 : out0; a.g[g].cout = G.cout;
+        a.g[g].w = G.d_w; a.g[g].bias = G.d_b; a.g[g].cout = G.cout;
         flops += 2.0 * npix * (double)G.cout * G.cin * G.ks * G.ks;
     }
     int rc;
@@ -733,18 +739,50 @@ static int launch_plan(pmx_ctx* c, const FwdCall& k, const ConvPlan& p)
     return pf ? prof_end(c, k) : PMX_OK;
 }
 
-// ---- two half-batch chains (pmx_ctx.h: BatchChain, ChainSplit) ----
-// the call of chain i of a forward that runs as two, and its images [*first, *first + *n) of B
-static FwdCall chain_call(const FwdCall& k, int i, int B, int* first, int* n)
+// ---- the parts of a launch: images [first, first + n) of its B ----
+// One part, the launch itself, unless the forward runs as two half-batch chains (pmx_ctx.h: BatchChain, ChainSplit): then the images of each
+// chain, on the chain's call.  `share` = n / B scales the profile figures of the whole launch, `suffix` ends the part's profile labels.
+struct LaunchPart { FwdCall k; int first, n; double share; std::string suffix; };
+static std::string part_suffix(int first, int n) { return "@" + std::to_string(first) + "+" + std::to_string(n); }
+template <typename F>
+static int for_each_part(const FwdCall& k, int B, F&& f)
 {
-    FwdCall kc = k;
-    kc.split = nullptr;
-    *first = i ? k.split->n0 : 0;
-    *n = i ? B - k.split->n0 : k.split->n0;
-    if (i) { kc.stream = k.split->second->stream; kc.scratch = k.split->second; }
-    return kc;
+    if (!k.split) return f(LaunchPart{k, 0, B, 1.0, ""});
+    for (int i = 0; i < 2; ++i) {
+        const int first = i ? k.split->n0 : 0, n = i ? B - k.split->n0 : k.split->n0;
+        LaunchPart part{k, first, n, (double)n / B, part_suffix(first, n)};
+        part.k.split = nullptr;
+        if (i) { part.k.stream = k.split->second->stream; part.k.scratch = k.split->second; }
+        if (int rc = f(part)) return rc;
+    }
+    return PMX_OK;
 }
-static std::string chain_suffix(int first, int n) { return "@" + std::to_string(first) + "+" + std::to_string(n); }
+// Where image `first` of a launch starts in the buffer `ptr` points into, `per_image` floats an image: first * per_image, except in act0 / act1
+// under two chains.  The chains drift apart by layers, and act0 / act1 hold layers of different sizes in turn: at the image offset of each
+// layer, a later, smaller layer of one chain would land in what the other chain still reads of an earlier, larger one.  So there the second
+// chain starts at a distance that no layer of the first reaches -- n0 images of the largest layer the buffer ever holds (act0: conv1_1's
+// output, 64 floats per input pixel; act1: conv1_2's pooled output, 16); every other buffer holds layers of one size only (cat, brA, brB,
+// brT at 1/8 resolution; in16) and keeps the image offset.
+static size_t image_offset(const FwdCall& k, int first, const float* ptr, size_t per_image)
+{
+    const NetBufs& ws = k.ws;
+    if (k.split && ptr >= ws.act0 && ptr < ws.act0 + ws.act0.capacity()) return (size_t)first * k.split->net_px * 64;
+    if (k.split && ptr >= ws.act1 && ptr < ws.act1 + ws.act1.capacity()) return (size_t)first * k.split->net_px * 16;
+    return (size_t)first * per_image;
+}
+// the operands of images [first, first + n) of the launch `io` describes (k: the call of the whole launch)
+static ConvIO conv_images(const FwdCall& k, const ConvIO& io, int first, int n)
+{
+    const size_t pin = (size_t)io.H * io.W * io.lda, pout = (size_t)(io.pool ? io.H / 2 : io.H) * (io.pool ? io.W / 2 : io.W) * io.ldc;
+    ConvIO s = io;
+    for (int g = 0; g < 2; ++g) {
+        if (io.in[g]) s.in[g] += image_offset(k, first, io.in[g], pin);
+        if (io.out[g]) s.out[g] += image_offset(k, first, io.out[g], pout);
+    }
+    s.B = n;
+    return s;
+}
+
 // The plan of the whole batch, launched once per chain on the chain's images.  Probe: whether a launch of either half is the launch the plan
 // describes (the merged tails are a property of the image count) and what the automatic rule says of a 7x7 layer.
 static int launch_plan_chains(pmx_ctx* c, const FwdCall& k, const ConvPlan& p)
@@ -762,117 +800,88 @@ static int launch_plan_chains(pmx_ctx* c, const FwdCall& k, const ConvPlan& p)
                                               p.tail_g, a.cout_pad, s.n0, a.B - s.n0, a.H, a.W)) s.rounds = false;
         return PMX_OK;
     }
-    const size_t pin = (size_t)a.H * a.W * a.lda, pout = (size_t)(a.pool ? a.H / 2 : a.H) * (a.pool ? a.W / 2 : a.W) * a.ldc;
-    // Where the second chain's images start in the buffer `ptr` points into.  The chains drift apart by layers, and act0 / act1 hold layers of
-    // different sizes in turn: at the image offset of each layer, a later, smaller layer of one chain would land in what the other chain still
-    // reads of an earlier, larger one.  So there the second chain starts at a distance that no layer of the first reaches -- n0 images of the
-    // largest layer the buffer ever holds (act0: conv1_1's output, 64 floats per input pixel; act1: conv1_2's pooled output, 16); every other
-    // buffer holds layers of one size only (cat, brA, brB, brT at 1/8 resolution; in16) and keeps the image offset.
-    auto second = [&](const float* ptr, size_t per_image) {
-        const NetBufs& ws = k.ws;
-        if (ptr >= ws.act0 && ptr < ws.act0 + ws.act0.capacity()) return (size_t)s.n0 * s.net_px * 64;
-        if (ptr >= ws.act1 && ptr < ws.act1 + ws.act1.capacity()) return (size_t)s.n0 * s.net_px * 16;
-        return (size_t)s.n0 * per_image;
-    };
-    for (int i = 0; i < 2; ++i) {
-        int first, n;
-        const FwdCall kc = chain_call(k, i, a.B, &first, &n);
+    return for_each_part(k, a.B, [&](const LaunchPart& part) {
         ConvPlan q = p;
-        q.a.B = n;
-        for (int g = 0; g < p.groups && i; ++g) { q.a.g[g].in += second(a.g[g].in, pin); q.a.g[g].out += second(a.g[g].out, pout); }
-        if (q.prof) {
-            const double share = (double)n / a.B;
-            q.pf.flops *= share; q.pf.bytes *= share; q.pf.issued *= share; q.pf.suffix = chain_suffix(first, n);
-        }
-        if (int rc = launch_plan(c, kc, q)) return rc;
-    }
-    return PMX_OK;
+        args_io(q.a, conv_images(k, p.io, part.first, part.n));
+        if (q.prof) { q.pf.flops *= part.share; q.pf.bytes *= part.share; q.pf.issued *= part.share; q.pf.suffix = part.suffix; }
+        return launch_plan(c, part.k, q);
+    });
 }
 
 // one layer of a forward: plan + launch.  A batch whose plain launch would end in a part-filled round of the CUs is cut in two first: the
 // images of the whole rounds, then the rest through the selection of THEIR count (conv_select.hip::wino_split_images); each half is an
 // ordinary run_conv on its images, whose profile labels end in `half` = "@<first image>+<count>" (null: a whole batch)
-static int run_conv(pmx_ctx* c, const FwdCall& k, const char* label, PackedLayer* L0, PackedLayer* L1, const float* in0, const float* in1, int lda,
-                    float* out0, float* out1, int ldc, int B, int H, int W, int relu, int pool, int level = -1, const char* half = nullptr)
+static int run_conv(pmx_ctx* c, const FwdCall& k, const char* label, PackedLayer* L0, PackedLayer* L1, const ConvIO& io, const char* half = nullptr)
 {
-    const bool seg = k.seg && level >= 0;
+    const bool seg = k.seg && io.level >= 0;
+    const int B = io.B, groups = L1 ? 2 : 1;
     int rc;
     if (!seg && !half && c->opt_wino_split && B >= 2 && L0->ks > 1 && c->opt_precision != 2 && wino_layers_ok(L0, L1)) {
-        const int n0 = wino_split_images(wino_opts(c, k, L0->ks, L1 ? 2 : 1, lda), L0->ks, L0->cin_pad, L0->cout_pad, L0->cout, ldc, B, L1 ? 2 : 1, H, W, pool);
+        const int n0 = wino_split_images(wino_opts(c, k, L0->ks, groups, io.lda), L0->ks, L0->cin_pad, L0->cout_pad, L0->cout, io.ldc, B, groups, io.H, io.W, io.pool);
         if (n0 > 0 && n0 < B && k.split) {      // (a cut by images is a plan of its own per side: no chains over it)
             PMX_CHECK(k.split->probe, PMX_ERR_STATE, "two chains: layer %s is cut in two by images", label ? label : "?");
             k.split->ok = false;
             return PMX_OK;
         }
         if (n0 > 0 && n0 < B) {
-            const size_t pin = (size_t)n0 * H * W * lda, pout = (size_t)n0 * (pool ? H / 2 : H) * (pool ? W / 2 : W) * ldc;
-            const std::string h0 = "@0+" + std::to_string(n0), h1 = "@" + std::to_string(n0) + "+" + std::to_string(B - n0);
-            if ((rc = run_conv(c, k, label, L0, L1, in0, in1, lda, out0, out1, ldc, n0, H, W, relu, pool, level, h0.c_str()))) return rc;
-            return run_conv(c, k, label, L0, L1, in0 + pin, in1 ? in1 + pin : nullptr, lda, out0 + pout, out1 ? out1 + pout : nullptr, ldc, B - n0, H, W, relu, pool, level,
-                            h1.c_str());
+            if ((rc = run_conv(c, k, label, L0, L1, conv_images(k, io, 0, n0), part_suffix(0, n0).c_str()))) return rc;
+            return run_conv(c, k, label, L0, L1, conv_images(k, io, n0, B - n0), part_suffix(n0, B - n0).c_str());
         }
     }
     ConvPlan p;
-    if ((rc = plan_conv(c, k, p, label, L0, L1, in0, in1, lda, out0, out1, ldc, B, H, W, relu, pool, level))) return rc;
+    if ((rc = plan_conv(c, k, p, label, L0, L1, io))) return rc;
     if (half && p.prof) p.pf.suffix = half;
     return k.split ? launch_plan_chains(c, k, p) : launch_plan(c, k, p);
 }
 
 // the two 1x1 layers that end a stage (A: 128 -> cmid + ReLU, B: cmid -> cout [+ ReLU]) as ONE launch when the shapes allow
-// (else, or with option fuse_pairs = 0, as two run_conv launches through `mid`): bit-identical either way
-static int run_pair(pmx_ctx* c, const FwdCall& k, const char* labelA, const char* labelB, PackedLayer* a0, PackedLayer* a1, PackedLayer* b0, PackedLayer* b1,
-                    const float* in0, const float* in1, int lda, float* mid0, float* mid1, int ldm, float* out0, float* out1, int ldc, int B,
-                    int H, int W, int reluB, int level = -1, bool keep_mid = false)      // keep_mid: `mid` must hold the middle activation: two launches
+// (else, or with option fuse_pairs = 0, as two run_conv launches through `mid`): bit-identical either way.  A, Bl: the (up to two) groups of
+// the two layers; io: A's input and B's output, io.relu = B's ReLU; keep_mid: `mid` must hold the middle activation: two launches
+static int run_pair(pmx_ctx* c, const FwdCall& k, const char* labelA, const char* labelB, PackedLayer* const (&A)[2], PackedLayer* const (&Bl)[2],
+                    const ConvIO& io, const ConvBuf& mid, bool keep_mid = false)
 {
-    const PackedLayer& LA = *a0;
-    const PackedLayer& LB = *b0;
-    const int groups = a1 ? 2 : 1;
+    const PackedLayer& LA = *A[0];
+    const PackedLayer& LB = *Bl[0];
+    const int groups = A[1] ? 2 : 1;
     // (heterogeneous forward: a 1x1 layer only sees pixels -- the segments' maps are one run of pix[level] pixels)
-    const bool seg = k.seg && level >= 0;
-    const long long npix = seg ? k.seg->pix[level] : (long long)B * H * W;
+    const bool seg = k.seg && io.level >= 0;
     const bool ok = !keep_mid && c->opt_fuse_pairs && c->opt_kernel_gen >= 6 && LA.ks == 1 && LB.ks == 1 && LA.cin_pad == 128 && LB.cin == LA.cout &&
-                    conv_pair_supported(LA.cin, LA.cout, LB.cout_pad) && (groups == 1 || b1->cout_pad == LB.cout_pad);
+                    conv_pair_supported(LA.cin, LA.cout, LB.cout_pad) && (groups == 1 || Bl[1]->cout_pad == LB.cout_pad);
     int rc;
     PMX_CHECK(ok || !seg, PMX_ERR_INVALID, "heterogeneous forward: the 1x1 pair %s + %s has no fused form", labelA, labelB);
     if (!ok) {
-        if ((rc = run_conv(c, k, labelA, a0, a1, in0, in1, lda, mid0, mid1, ldm, B, H, W, 1, 0))) return rc;
-        return run_conv(c, k, labelB, b0, b1, mid0, mid1, ldm, out0, out1, ldc, B, H, W, reluB, 0);
+        ConvIO a = io, b = io;
+        for (int g = 0; g < 2; ++g) a.out[g] = mid.p[g], b.in[g] = mid.p[g];
+        a.ldc = b.lda = mid.ld;
+        a.relu = 1;
+        if ((rc = run_conv(c, k, labelA, A[0], A[1], a))) return rc;
+        return run_conv(c, k, labelB, Bl[0], Bl[1], b);
     }
+    if (k.split && k.split->probe) return PMX_OK;
+    auto pixels = [&](int n) { return seg ? k.seg->pix[io.level] : (long long)n * io.H * io.W; };
+    const long long npix = pixels(io.B);
     PairArgs p;
     memset(&p, 0, sizeof p);
     double flops = 0;
     for (int g = 0; g < groups; ++g) {
-        const PackedLayer& A = *(g ? a1 : a0);
-        const PackedLayer& Bl = *(g ? b1 : b0);
-        p.g[g].in = g ? in1 : in0; p.g[g].w1 = A.d_w; p.g[g].b1 = A.d_b; p.g[g].w2 = Bl.d_w; p.g[g].b2 = Bl.d_b;
-        p.g[g].out = g ? out1 : out0; p.g[g].cout = Bl.cout;
-        flops += 2.0 * (double)npix * ((double)A.cout * A.cin + (double)Bl.cout * Bl.cin);
+        p.g[g].w1 = A[g]->d_w; p.g[g].b1 = A[g]->d_b; p.g[g].w2 = Bl[g]->d_w; p.g[g].b2 = Bl[g]->d_b; p.g[g].cout = Bl[g]->cout;
+        flops += 2.0 * (double)npix * ((double)A[g]->cout * A[g]->cin + (double)Bl[g]->cout * Bl[g]->cin);
     }
-    p.npix = npix; p.lda = lda; p.ldc = ldc; p.cmid = LA.cout; p.cout_pad = LB.cout_pad; p.relu2 = reluB;
+    p.lda = io.lda; p.ldc = io.ldc; p.cmid = LA.cout; p.cout_pad = LB.cout_pad; p.relu2 = io.relu;
     const std::string name = std::string(labelA) + "+" + labelB + "|conv1x1_pair_c" + std::to_string(LA.cout) + "_n" + std::to_string(LB.cout_pad);
     const double bytes = 4.0 * (double)npix * groups * (LA.cin + LB.cout);
-    if (k.split) {                   // two chains: the launch over each chain's pixels
-        if (k.split->probe) return PMX_OK;
-        for (int i = 0; i < 2; ++i) {
-            int first, n;
-            const FwdCall kc = chain_call(k, i, B, &first, &n);
-            PairArgs q = p;
-            q.npix = (long long)n * H * W;
-            for (int g = 0; g < groups; ++g) { q.g[g].in += (size_t)first * H * W * lda; q.g[g].out += (size_t)first * H * W * ldc; }
-            const double share = (double)n / B;
-            if (c->prof_on == 1 && (rc = prof_begin(c, kc, name + chain_suffix(first, n), flops * share, bytes * share))) return rc;
-            if ((rc = conv_pair_launch(q, groups, kc.stream)) || (rc = prof_end(c, kc))) return rc;
-        }
-        return PMX_OK;
-    }
-    if (c->prof_on == 1 && (rc = prof_begin(c, k, name, flops, bytes))) return rc;
-    if ((rc = conv_pair_launch(p, groups, k.stream))) return rc;
-    return prof_end(c, k);
+    return for_each_part(k, io.B, [&](const LaunchPart& part) {      // (two chains: the launch over each chain's pixels)
+        const ConvIO s = conv_images(k, io, part.first, part.n);
+        PairArgs q = p;
+        q.npix = pixels(part.n);
+        for (int g = 0; g < groups; ++g) { q.g[g].in = s.in[g]; q.g[g].out = s.out[g]; }
+        int rc;
+        if (c->prof_on == 1 && (rc = prof_begin(c, part.k, name + part.suffix, flops * part.share, bytes * part.share))) return rc;
+        if ((rc = conv_pair_launch(q, groups, part.k.stream))) return rc;
+        return prof_end(c, part.k);
+    });
 }
 
-// which form conv1_1 -> conv1_2 (+ pool) takes: *fuse: one launch (direct conv1_2 on 8 x 16 x 64 tiles: large maps); returns true for
-// conv1_2 as Winograd F(2x2, 3x3) on 16 x 16 squares (conv1_wino.hip): wherever the Winograd kernels are allowed (conv_algo >= 1) and the
-// launch has at least one block per CU (smaller launches: the 8 x 16 direct tiles give twice the blocks); conv1_wino = 2: always
 // conv1_1 + conv1_2 have the shapes conv1_wino_kernel is written for (3 -> 64 -> 64, fp32)?
 static bool conv1_pairable(const pmx_ctx* c)
 {
@@ -886,18 +895,19 @@ static bool trunk_retaining(const pmx_ctx* c, const FwdCall& k)
 {
     return c->bw.on == 2 && c->kind == NET_POSE && c->ls_on && c->lg_on && c->opt_precision == 0 && !k.seg;
 }
+// which form conv1_1 -> conv1_2 (+ pool) takes: *fuse: one launch (direct conv1_2 on 8 x 16 x 64 tiles: large maps); returns true for
+// conv1_2 as Winograd F(2x2, 3x3) on 16 x 16 squares (conv1_wino.hip): wherever the Winograd kernels are allowed (conv_algo >= 1) and the
+// launch has at least one block per CU (smaller launches: the 8 x 16 direct tiles give twice the blocks); conv1_wino = 2: always
 static bool conv1_form(const pmx_ctx* c, const FwdCall& k, int B, int H, int W, bool* fuse_out)
 {
     if (trunk_retaining(c, k)) {
         if (fuse_out) *fuse_out = false;
         return false;
     }
-    const PackedLayer& L1 = c->layers[c->index.at("conv1_1")];
     const PackedLayer& L2 = c->layers[c->index.at("conv1_2")];
     const int v2 = conv_pick_variant(3, L2.cout_pad, H, W, B, c->opt_force[3], c->opt_kernel_gen, 1, L2.cin, 0, c->num_cus);
-    const bool fuse = c->opt_fuse_conv1 && c->opt_kernel_gen >= 6 && c->opt_precision == 0 && c->opt_force[3] < 0 && L1.cin == 3 && L1.cout == 64 &&
-                      L2.cin == 64 && L2.cout == 64 && !strcmp(conv_variant(v2).name, "conv3x3_v5_t8x16_n64");
-    const bool pair_ok = c->opt_precision == 0 && c->opt_force[3] < 0 && L1.cin == 3 && L1.cout == 64 && L2.cin == 64 && L2.cout == 64 && H % 2 == 0 && W % 2 == 0;
+    const bool fuse = c->opt_fuse_conv1 && c->opt_kernel_gen >= 6 && conv1_pairable(c) && !strcmp(conv_variant(v2).name, "conv3x3_v5_t8x16_n64");
+    const bool pair_ok = conv1_pairable(c) && H % 2 == 0 && W % 2 == 0;
     if (fuse_out) *fuse_out = fuse;
     return pair_ok && c->opt_conv1_wino && k.conv_algo >= 1 &&
            (c->opt_conv1_wino == 2 || (fuse && (long long)B * ((H + 15) / 16) * ((W + 15) / 16) >= c->num_cus));
@@ -914,69 +924,46 @@ static int run_conv1(pmx_ctx* c, const FwdCall& k, int B, int H, int W)
     const uint8_t* const in_u8 = k.in_u8;
     PMX_CHECK(!in_u8 || wino1, PMX_ERR_STATE, "conv1: a uint8 input without the kernel that preprocesses it");
     int rc;
-    if (seg && c->opt_precision == 2) {
-        // f16 mode: pmx_forward_from_u8 has preprocessed the segments' pixels into in16; both layers on the level-0 rectangle tables
-        PMX_CHECK(!in_u8, PMX_ERR_STATE, "conv1: a uint8 input in f16 mode");
-        if ((rc = run_conv(c, k, "conv1_1", &L1, nullptr, ws.in16, nullptr, PMX_IN_C, ws.act0, nullptr, 64, B, H, W, 1, 0, 0))) return rc;
-        return run_conv(c, k, "conv1_2", &L2, nullptr, ws.act0, nullptr, 64, ws.act1, nullptr, 64, B, H, W, 1, 1, 0);
+    // f16 mode, heterogeneous: pmx_forward_from_u8 has preprocessed the segments' pixels into in16; both layers on the level-0 rectangle tables
+    const bool f16_seg = seg && c->opt_precision == 2;
+    PMX_CHECK(!f16_seg || !in_u8, PMX_ERR_STATE, "conv1: a uint8 input in f16 mode");
+    PMX_CHECK(!seg || f16_seg || (wino1 && in_u8), PMX_ERR_INVALID, "heterogeneous forward: needs conv1 as conv1_wino_kernel on a uint8 input");
+    const ConvBuf in16 = ConvBuf::one(ws.in16, PMX_IN_C), act0 = ConvBuf::one(ws.act0, 64), act1 = ConvBuf::one(ws.act1, 64);
+    if (f16_seg || (!fuse && !wino1)) {
+        if ((rc = run_conv(c, k, "conv1_1", &L1, nullptr, conv_io(in16, act0, B, H, W, 1, 0, 0)))) return rc;
+        return run_conv(c, k, "conv1_2", &L2, nullptr, conv_io(act0, act1, B, H, W, 1, 1, 0));
     }
-    PMX_CHECK(!seg || (wino1 && in_u8), PMX_ERR_INVALID, "heterogeneous forward: needs conv1 as conv1_wino_kernel on a uint8 input");
-    if (!fuse && !wino1) {
-        if ((rc = run_conv(c, k, "conv1_1", &L1, nullptr, ws.in16, nullptr, PMX_IN_C, ws.act0, nullptr, 64, B, H, W, 1, 0))) return rc;
-        return run_conv(c, k, "conv1_2", &L2, nullptr, ws.act0, nullptr, 64, ws.act1, nullptr, 64, B, H, W, 1, 1);
-    }
+    if (k.split && k.split->probe) return PMX_OK;
+    // one launch: group 0 is conv1_2 (in16 -> pooled act1), group 1 carries conv1_1's weights and, for the kernel that preprocesses the
+    // uint8 batch itself (pmx_forward_from_u8), the pixels and their divisor
+    const ConvIO io = conv_io(in16, act1, B, H, W, 1, 1);
     ConvArgs a;
     memset(&a, 0, sizeof a);
-    a.g[0].in = ws.in16; a.g[0].w = L2.d_w; a.g[0].bias = L2.d_b; a.g[0].out = ws.act1; a.g[0].cout = L2.cout;
-    a.g[1].w = L1.d_w; a.g[1].bias = L1.d_b;
-    a.B = B; a.H = H; a.W = W; a.lda = PMX_IN_C; a.ldc = 64; a.nch = L2.nch; a.cout_pad = L2.cout_pad; a.relu = 1; a.pool = 1;
-    if (k.split) {                   // two chains: the form of the whole batch, launched over each chain's images
-        if (k.split->probe) return PMX_OK;
-        if (wino1 && ((rc = ensure_wino_pack(k.stream, L2)) || (rc = ensure_conv1_pack(k.stream, L1)))) return rc;
-        if (wino1) { a.g[0].w = L2.d_ww; a.g[1].w = L1.d_ww; }
-        if (wino1 && in_u8) a.kbounds = (unsigned long long)__builtin_bit_cast(unsigned, k.in_div);
-        const double f1 = 2.0 * H * W * 9.0 * (double)L1.cout * L1.cin, f2 = 2.0 * H * W * 9.0 * (double)L2.cout * L2.cin;      // per image
-        for (int i = 0; i < 2; ++i) {
-            int first, n;
-            const FwdCall kc = chain_call(k, i, B, &first, &n);
-            ConvArgs q = a;
-            q.B = n;
-            q.g[0].in += (size_t)first * H * W * PMX_IN_C; q.g[0].out += (size_t)first * (H / 2) * (W / 2) * 64;
-            if (wino1 && in_u8) q.g[1].in = reinterpret_cast<const float*>(in_u8 + (size_t)first * H * W * 3);
-            if (c->prof_on == 1) {
-                const double np = (double)n * H * W;
-                rc = wino1 ? prof_begin(c, kc, "conv1_1+conv1_2|conv_wino1_f2x2_t16x16" + chain_suffix(first, n), n * (f1 + f2),
-                                        (in_u8 ? 3.0 : 4.0 * 3) * np + 4.0 * np * (64 / 4), n * (f1 + f2 * 16.0 / 36.0))
-                           : prof_begin(c, kc, "conv1_1+conv1_2|conv1_fused_t8x16_n64" + chain_suffix(first, n), n * (f1 + f2), 4.0 * np * (3 + 64 / 4));
-                if (rc) return rc;
-            }
-            if ((rc = wino1 ? conv1_wino_launch(q, kc.stream) : conv1_fused_launch(q, kc.stream)) || (rc = prof_end(c, kc))) return rc;
-        }
-        return PMX_OK;
-    }
+    args_io(a, io);
+    a.g[0].w = L2.d_w; a.g[0].bias = L2.d_b; a.g[0].cout = L2.cout; a.g[1].w = L1.d_w; a.g[1].bias = L1.d_b;
+    a.nch = L2.nch; a.cout_pad = L2.cout_pad;
     if (wino1) {
         if ((rc = ensure_wino_pack(k.stream, L2)) || (rc = ensure_conv1_pack(k.stream, L1))) return rc;
-        a.g[0].w = L2.d_ww;
-        a.g[1].w = L1.d_ww;
-        if (in_u8) {                                      // the kernel preprocesses the uint8 batch itself (pmx_forward_from_u8)
-            a.g[1].in = reinterpret_cast<const float*>(in_u8);
-            a.kbounds = (unsigned long long)__builtin_bit_cast(unsigned, k.in_div);
-        }
+        a.g[0].w = L2.d_ww; a.g[1].w = L1.d_ww;
+        if (in_u8) a.kbounds = (unsigned long long)__builtin_bit_cast(unsigned, k.in_div);
         if (seg) { a.nseg = (int)k.seg->segs.size(); a.segs = k.seg->table(PMX_SEG_CONV1); a.seg_tiles = k.seg->tiles[PMX_SEG_CONV1]; }
+    }
+    // the profile entry, per input pixel (whole numbers, so a part's figures are exact whichever way they are multiplied out)
+    const double f1 = 2.0 * 9.0 * (double)L1.cout * L1.cin, f2 = 2.0 * 9.0 * (double)L2.cout * L2.cin;
+    const ConvProf pf = wino1 ? ConvProf{"conv1_1+conv1_2|conv_wino1_f2x2_t16x16", f1 + f2, (in_u8 ? 3.0 : 4.0 * 3) + 4.0 * (64 / 4), f1 + f2 * 16.0 / 36.0, ""}
+                              : ConvProf{"conv1_1+conv1_2|conv1_fused_t8x16_n64", f1 + f2, 4.0 * (3 + 64 / 4), f1 + f2, ""};
+    return for_each_part(k, B, [&](const LaunchPart& part) {      // (two chains: the form of the whole batch over each chain's images)
+        ConvArgs q = a;
+        args_io(q, conv_images(k, io, part.first, part.n));
+        if (wino1 && in_u8) q.g[1].in = reinterpret_cast<const float*>(in_u8 + (size_t)part.first * H * W * 3);
+        int rc;
         if (c->prof_on == 1) {
-            const double np0 = seg ? (double)k.seg->pix[0] : (double)B * H * W;
-            const double f1 = 2.0 * np0 * 9.0 * (double)L1.cout * L1.cin, f2 = 2.0 * np0 * 9.0 * (double)L2.cout * L2.cin;
-            if ((rc = prof_begin(c, k, "conv1_1+conv1_2|conv_wino1_f2x2_t16x16", f1 + f2, (in_u8 ? 3.0 : 4.0 * 3) * np0 + 4.0 * np0 * (64 / 4), f1 + f2 * 16.0 / 36.0))) return rc;
+            const double np = seg ? (double)k.seg->pix[0] : (double)part.n * H * W;
+            if ((rc = prof_begin(c, part.k, pf.name + part.suffix, np * pf.flops, np * pf.bytes, np * pf.issued))) return rc;
         }
-        if ((rc = conv1_wino_launch(a, k.stream))) return rc;
-        return prof_end(c, k);
-    }
-    if (c->prof_on == 1) {
-        const double flops = 2.0 * B * H * W * 9.0 * ((double)L1.cout * L1.cin + (double)L2.cout * L2.cin);
-        if ((rc = prof_begin(c, k, "conv1_1+conv1_2|conv1_fused_t8x16_n64", flops, 4.0 * B * H * W * (3 + 64 / 4)))) return rc;
-    }
-    if ((rc = conv1_fused_launch(a, k.stream))) return rc;
-    return prof_end(c, k);
+        if ((rc = wino1 ? conv1_wino_launch(q, part.k.stream) : conv1_fused_launch(q, part.k.stream))) return rc;
+        return prof_end(c, part.k);
+    });
 }
 
 // conv1_1 ... conv4_2, the VGG stem all three networks share (CocoPoseNet.py:136-149, FaceNet.py:78-92): act1 and act0 in turn, the three
@@ -994,7 +981,8 @@ static int run_stem(pmx_ctx* c, const FwdCall& k, int B, int H, int W, float* la
     for (const auto& s : stem) {
         if (rc) break;
         if (last_out && &s == &stem[7]) out = last_out;
-        rc = run_conv(c, k, s.name, &c->layers[c->index.at(s.name)], nullptr, in, nullptr, s.cin, out, nullptr, s.cout, B, H >> s.level, W >> s.level, 1, s.pool, s.level);
+        rc = run_conv(c, k, s.name, &c->layers[c->index.at(s.name)], nullptr,
+                      conv_io(ConvBuf::one(in, s.cin), ConvBuf::one(out, s.cout), B, H >> s.level, W >> s.level, 1, s.pool, s.level));
         std::swap(in, out);
     }
     return rc;
@@ -1008,13 +996,13 @@ static int run_stem_retaining(pmx_ctx* c, const FwdCall& k, int B, int H, int W,
     BwState& bw = c->bw;
     PMX_CHECK(!k.in_u8, PMX_ERR_STATE, "retaining stem: a uint8 input that no kernel preprocesses");
     PMX_CHECK((size_t)B * H * W <= bw.cap_px * 64, PMX_ERR_CAPACITY, "forward: %d x %d x %d input pixels, the trunk store holds %zu", B, H, W, bw.cap_px * 64);
-    const float* in = k.ws.in16;
+    float* in = k.ws.in16;
     int lda = PMX_IN_C, pools = 0, rc;
     for (int t = 0; t < PMX_TRUNK_LAYERS; ++t) {
         const TrunkDesc& d = pmx_trunk_desc[t];
         const int h = H >> d.level, w = W >> d.level;
         float* out = t == PMX_TRUNK_LAYERS - 1 ? x42 : bw.t_act + bw.t_a_off[t];
-        if ((rc = run_conv(c, k, d.name, &c->layers[bw.t_layer[t]], nullptr, in, nullptr, lda, out, nullptr, d.cout, B, h, w, 1, 0, d.level))) return rc;
+        if ((rc = run_conv(c, k, d.name, &c->layers[bw.t_layer[t]], nullptr, conv_io(ConvBuf::one(in, lda), ConvBuf::one(out, d.cout), B, h, w, 1, 0, d.level)))) return rc;
         in = out; lda = d.cout;
         if (!d.pool) continue;
         float* pooled = bw.t_act + bw.t_p_off[pools++];
@@ -1037,36 +1025,27 @@ static int forward_cpm(pmx_ctx* c, const FwdCall& k, int B, int H, int W)
     int rc;
     const int H8 = H / 8, W8 = W / 8;
     const int CC = c->cat_c;
-    float* cat = ws.cat;
-    float* heat = cat + c->cat_heat;
-#define RUN1(name, in, lda, out, ldc) \
-    do { if ((rc = run_conv(c, k, name, L(name), nullptr, in, nullptr, lda, out, nullptr, ldc, B, H8, W8, 1, 0))) return rc; } while (0)
-    if ((rc = run_stem(c, k, B, H, W))) return rc;
-    RUN1("conv4_3", ws.act1, 512, ws.act0, 512);
-    RUN1("conv4_4", ws.act0, 512, ws.act1, 512);
-    RUN1("conv5_1", ws.act1, 512, ws.act0, 512);
-    RUN1("conv5_2", ws.act0, 512, ws.act1, 512);
-    RUN1("conv5_3_CPM", ws.act1, 512, cat, CC);               // feature_map -> cat[:, 0:128]
+    // the buffers of the graph: cat = [128 feature channels | the stage's heat maps]
+    const ConvBuf act0 = ConvBuf::one(ws.act0, 512), act1 = ConvBuf::one(ws.act1, 512), cat = ConvBuf::one(ws.cat, CC), heat = ConvBuf::one(ws.cat + c->cat_heat, CC);
+    const ConvBuf brA = ConvBuf::one(ws.brA, 128), brB = ConvBuf::one(ws.brB, 128), brT = ConvBuf::one(ws.brT, 512);
+    auto conv = [&](const char* name, const ConvBuf& in, const ConvBuf& out) { return run_conv(c, k, name, L(name), nullptr, conv_io(in, out, B, H8, W8, 1, 0)); };
+    auto pair = [&](const char* nameA, const char* nameB, const ConvBuf& in, const ConvBuf& mid) {
+        return run_pair(c, k, nameA, nameB, {L(nameA), nullptr}, {L(nameB), nullptr}, conv_io(in, heat, B, H8, W8, 0, 0), mid);
+    };
+    if ((rc = run_stem(c, k, B, H, W)) || (rc = conv("conv4_3", act1, act0)) || (rc = conv("conv4_4", act0, act1)) || (rc = conv("conv5_1", act1, act0)) ||
+        (rc = conv("conv5_2", act0, act1)) || (rc = conv("conv5_3_CPM", act1, cat))) return rc;               // feature_map -> cat[:, 0:128]
     // conv6_1_CPM (reads the 128 feature channels) -> conv6_2_CPM (stage-1 heat maps -> cat[:, 128:128+C])
-    if ((rc = run_pair(c, k, "conv6_1_CPM", "conv6_2_CPM", L("conv6_1_CPM"), nullptr, L("conv6_2_CPM"), nullptr, cat, nullptr, CC, ws.brT, nullptr, 512,
-                       heat, nullptr, CC, B, H8, W8, 0))) return rc;
+    if ((rc = pair("conv6_1_CPM", "conv6_2_CPM", cat, brT))) return rc;
     char nm[48], nm2[48];
     for (int s = 2; s <= 6 && s <= c->opt_stop_stage; ++s) {
         for (int i = 1; i <= 5; ++i) {
             snprintf(nm, sizeof nm, "Mconv%d_stage%d", i, s);
-            const float* in; float* out; int lda;
-            if (i == 1) { in = cat; lda = CC; }
-            else if (i % 2 == 0) { in = ws.brA; lda = 128; }
-            else { in = ws.brB; lda = 128; }
-            out = i % 2 == 1 ? ws.brA : ws.brB;
-            RUN1(nm, in, lda, out, 128);
+            if ((rc = conv(nm, i == 1 ? cat : i % 2 == 0 ? brA : brB, i % 2 == 1 ? brA : brB))) return rc;
         }
         snprintf(nm, sizeof nm, "Mconv6_stage%d", s);
         snprintf(nm2, sizeof nm2, "Mconv7_stage%d", s);
-        if ((rc = run_pair(c, k, nm, nm2, L(nm), nullptr, L(nm2), nullptr, ws.brA, nullptr, 128, ws.brB, nullptr, 128, heat, nullptr, CC, B, H8, W8, 0)))
-            return rc;
+        if ((rc = pair(nm, nm2, brA, brB))) return rc;
     }
-#undef RUN1
     c->maps_valid = true; c->maps_external = false;
     c->cur_B = B; c->cur_fh = H8; c->cur_fw = W8;
     c->cur_segs.clear();
@@ -1082,7 +1061,6 @@ int pmx_forward_from_in16(pmx_ctx* c, const FwdCall& k, int B, int H, int W)
     auto L = [&](const char* n) { return &c->layers[c->index.at(n)]; };
     int rc;
     const int H8 = H / 8, W8 = W / 8;
-#define RUN(...) do { if ((rc = run_conv(c, k, __VA_ARGS__))) return rc; } while (0)
     // validation-loss hook (pmx_loss.hip; uniform batches): the stage's outputs lie in the cat slices until the next stage's last launch
     const bool hook = c->ls_on && !k.seg;
     // (the hook and the retention read the context's own cat slices on the context's stream)
@@ -1102,53 +1080,54 @@ int pmx_forward_from_in16(pmx_ctx* c, const FwdCall& k, int B, int H, int W)
         return keep ? bwd_copy_cols_launch(ws.cat + PMX_CAT_PAF, PMX_CAT_C, bw.act + bw.slot[sl].a_off, 64, npix8, 64, k.stream) : PMX_OK;
     };
     // stem (CocoPoseNet.py:136-151)
-    // (the last argument = the resolution level, read only by a heterogeneous forward: pmx_multi.hip)
     if ((rc = keep && bw.on == 2 ? run_stem_retaining(c, k, B, H, W, x42) : run_stem(c, k, B, H, W, keep ? x42 : nullptr))) return rc;
-    RUN("conv4_3_CPM", L("conv4_3_CPM"), nullptr, x42, nullptr, 512, a43, nullptr, 256, B, H8, W8, 1, 0, 3);
-    RUN("conv4_4_CPM", L("conv4_4_CPM"), nullptr, a43, nullptr, 256, ws.cat + PMX_CAT_FEAT, nullptr, PMX_CAT_C, B, H8, W8, 1, 0, 3);
-    // stage 1 (CocoPoseNet.py:154-165); L1 = PAF branch, L2 = heat-map branch
-    float* cat = ws.cat;
+    // Everything below runs at 1/8 resolution (level 3: read only by a heterogeneous forward, pmx_multi.hip).  L1 = PAF branch, L2 = heat-map
+    // branch, the two groups of one launch: side by side in every buffer (br), both reading the whole concat buffer (cat_in), writing its
+    // PAF and heat-map slices (maps)
+    auto br = [](float* p, int ch = 128) { return ConvBuf::two(p, ch, 2 * ch); };
+    const ConvBuf cat_in = ConvBuf::two(ws.cat, 0, PMX_CAT_C), maps = ConvBuf::two(ws.cat + PMX_CAT_PAF, PMX_CAT_HEAT - PMX_CAT_PAF, PMX_CAT_C);
+    auto conv = [&](const char* label, PackedLayer* L0, PackedLayer* L1, const ConvBuf& in, const ConvBuf& out) {
+        return run_conv(c, k, label, L0, L1, conv_io(in, out, B, H8, W8, 1, 0, 3));
+    };
+    if ((rc = conv("conv4_3_CPM", L("conv4_3_CPM"), nullptr, ConvBuf::one(x42, 512), ConvBuf::one(a43, 256)))) return rc;
+    if ((rc = conv("conv4_4_CPM", L("conv4_4_CPM"), nullptr, ConvBuf::one(a43, 256), ConvBuf::one(ws.cat + PMX_CAT_FEAT, PMX_CAT_C)))) return rc;
+    // stage 1 (CocoPoseNet.py:154-165)
     float* const s51 = slot(PMX_BW_S1 + 0, ws.brA);
     float* const s52 = slot(PMX_BW_S1 + 1, ws.brB);
     float* const s53 = slot(PMX_BW_S1 + 2, ws.brA);
     float* const s54 = slot(PMX_BW_S1 + 3, ws.brT);
-    RUN("conv5_1_CPM", L("conv5_1_CPM_L1"), L("conv5_1_CPM_L2"), cat, cat, PMX_CAT_C, s51, s51 + 128, 256, B, H8, W8, 1, 0, 3);
-    RUN("conv5_2_CPM", L("conv5_2_CPM_L1"), L("conv5_2_CPM_L2"), s51, s51 + 128, 256, s52, s52 + 128, 256, B, H8, W8, 1, 0, 3);
-    RUN("conv5_3_CPM", L("conv5_3_CPM_L1"), L("conv5_3_CPM_L2"), s52, s52 + 128, 256, s53, s53 + 128, 256, B, H8, W8, 1, 0, 3);
+    if ((rc = conv("conv5_1_CPM", L("conv5_1_CPM_L1"), L("conv5_1_CPM_L2"), cat_in, br(s51)))) return rc;
+    if ((rc = conv("conv5_2_CPM", L("conv5_2_CPM_L1"), L("conv5_2_CPM_L2"), br(s51), br(s52)))) return rc;
+    if ((rc = conv("conv5_3_CPM", L("conv5_3_CPM_L1"), L("conv5_3_CPM_L2"), br(s52), br(s53)))) return rc;
     // conv5_4 (128 -> 512, ReLU) -> conv5_5 (512 -> 38 | 19): one launch
-    if ((rc = run_pair(c, k, "conv5_4_CPM", "conv5_5_CPM", L("conv5_4_CPM_L1"), L("conv5_4_CPM_L2"), L("conv5_5_CPM_L1"), L("conv5_5_CPM_L2"),
-                       s53, s53 + 128, 256, s54, s54 + 512, 1024, cat + PMX_CAT_PAF, cat + PMX_CAT_HEAT, PMX_CAT_C, B, H8, W8, 0, 3, keep)))
-        return rc;
+    if ((rc = run_pair(c, k, "conv5_4_CPM", "conv5_5_CPM", {L("conv5_4_CPM_L1"), L("conv5_4_CPM_L2")}, {L("conv5_5_CPM_L1"), L("conv5_5_CPM_L2")},
+                       conv_io(br(s53), maps, B, H8, W8, 0, 0, 3), br(s54, 512), keep))) return rc;
     int n_stages = 1;
     if (hook && (rc = pmx_loss_stage(c, 1, B, H8, W8))) return rc;
     if ((rc = keep_stage(PMX_BW_S1 + 4))) return rc;
     // stages 2-6 (CocoPoseNet.py:168-260)
     char n1[48], n2[48], m1[48], m2[48], lab[48], lab2[48];
     for (int s = 2; s <= 6 && s <= c->opt_stop_stage; ++s) {
-        const float* in = cat;
+        ConvBuf in = cat_in;
         for (int i = 1; i <= 5; ++i) {
             snprintf(n1, sizeof n1, "Mconv%d_stage%d_L1", i, s);
             snprintf(n2, sizeof n2, "Mconv%d_stage%d_L2", i, s);
             snprintf(lab, sizeof lab, "Mconv%d_stage%d", i, s);
-            float* const o = slot(PMX_BW_M(s, i), i % 2 == 1 ? ws.brA : ws.brB);
-            if (i == 1) RUN(lab, L(n1), L(n2), cat, cat, PMX_CAT_C, o, o + 128, 256, B, H8, W8, 1, 0, 3);
-            else RUN(lab, L(n1), L(n2), in, in + 128, 256, o, o + 128, 256, B, H8, W8, 1, 0, 3);
+            const ConvBuf o = br(slot(PMX_BW_M(s, i), i % 2 == 1 ? ws.brA : ws.brB));
+            if ((rc = conv(lab, L(n1), L(n2), in, o))) return rc;
             in = o;
         }
         // Mconv6 (1x1 128 -> 128, ReLU; reads Mconv5's output in brA) -> Mconv7 (1x1 128 -> 38 | 19, into the cat slices): one launch
         snprintf(n1, sizeof n1, "Mconv6_stage%d_L1", s); snprintf(n2, sizeof n2, "Mconv6_stage%d_L2", s);
         snprintf(m1, sizeof m1, "Mconv7_stage%d_L1", s); snprintf(m2, sizeof m2, "Mconv7_stage%d_L2", s);
         snprintf(lab, sizeof lab, "Mconv6_stage%d", s); snprintf(lab2, sizeof lab2, "Mconv7_stage%d", s);
-        float* const m6 = slot(PMX_BW_M(s, 6), ws.brB);
-        if ((rc = run_pair(c, k, lab, lab2, L(n1), L(n2), L(m1), L(m2), in, in + 128, 256, m6, m6 + 128, 256,
-                           cat + PMX_CAT_PAF, cat + PMX_CAT_HEAT, PMX_CAT_C, B, H8, W8, 0, 3, keep))) return rc;
+        if ((rc = run_pair(c, k, lab, lab2, {L(n1), L(n2)}, {L(m1), L(m2)}, conv_io(in, maps, B, H8, W8, 0, 0, 3), br(slot(PMX_BW_M(s, 6), ws.brB)), keep))) return rc;
         n_stages = s;
         if (hook && (rc = pmx_loss_stage(c, s, B, H8, W8))) return rc;
         if ((rc = keep_stage(PMX_BW_M(s, 7)))) return rc;
     }
     if (hook && (rc = pmx_loss_finish(c, n_stages, B, H8, W8))) return rc;
     if (keep) { bw.valid = true; bw.stages = n_stages; bw.B = B; bw.fh = H8; bw.fw = W8; bw.t_H = H; bw.t_W = W; }
-#undef RUN
     if (k.split && k.split->probe) return PMX_OK;      // (nothing ran)
     c->maps_valid = true; c->maps_external = false;
     c->cur_B = B; c->cur_fh = H8; c->cur_fw = W8;
@@ -1207,19 +1186,14 @@ int pmx_forward_from_u8(pmx_ctx* c, const FwdCall& k, const uint8_t* d, int B, i
         ku.in_u8 = d; ku.in_div = divisor;
         return pmx_forward_from_in16(c, ku, B, H, W);
     }
-    if (k.split) {                   // two chains: each preprocesses its own images
-        for (int i = 0; i < 2 && !k.split->probe; ++i) {
-            int first, n;
-            const FwdCall kc = chain_call(k, i, B, &first, &n);
-            if (c->prof_on == 1 && (rc = prof_begin(c, kc, "prep_u8|prep_u8" + chain_suffix(first, n), 0, (double)n * H * W * (3 + 64)))) return rc;
-            if ((rc = launch_prep_u8(d + (size_t)first * H * W * 3, k.ws.in16 + (size_t)first * H * W * PMX_IN_C, n, H, W, divisor, kc.stream))) return rc;
-            if ((rc = prof_end(c, kc))) return rc;
-        }
-        return pmx_forward_from_in16(c, k, B, H, W);
-    }
-    if (c->prof_on == 1 && (rc = prof_begin(c, k, "prep_u8|prep_u8", 0, (double)B * H * W * (3 + 64)))) return rc;
-    if ((rc = launch_prep_u8(d, k.ws.in16, B, H, W, divisor, k.stream))) return rc;
-    if ((rc = prof_end(c, k))) return rc;
+    auto prep = [&](const LaunchPart& part) {      // (two chains: each preprocesses its own images)
+        const size_t px0 = (size_t)part.first * H * W;
+        int rc;
+        if (c->prof_on == 1 && (rc = prof_begin(c, part.k, "prep_u8|prep_u8" + part.suffix, 0, (double)part.n * H * W * (3 + 64)))) return rc;
+        if ((rc = launch_prep_u8(d + px0 * 3, k.ws.in16 + px0 * PMX_IN_C, part.n, H, W, divisor, part.k.stream))) return rc;
+        return prof_end(c, part.k);
+    };
+    if (!(k.split && k.split->probe) && (rc = for_each_part(k, B, prep))) return rc;
     return pmx_forward_from_in16(c, k, B, H, W);
 }
 
@@ -1632,21 +1606,19 @@ static int detect_batch_chains(pmx_ctx* c, const uint8_t* d, int B, int H, int W
     rc = pmx_forward_from_u8(c, k, d, B, H, W, 255.0f);
     const PPMaps m = pmx_current_maps(c);
     c->pp_limbs_slices = c->opt_limbs_slices >= 0 ? c->opt_limbs_slices : 0;
-    struct ProfCtx { pmx_ctx* c; FwdCall k; std::string suffix; };
+    struct ProfCtx { pmx_ctx* c; const LaunchPart& part; };
     auto prof_cb = [](void* v, const char* name, int begin) {
         ProfCtx* p = (ProfCtx*)v;
-        if (begin) (void)prof_begin(p->c, p->k, std::string(name) + "|" + name + p->suffix, 0, 0);
-        else (void)prof_end(p->c, p->k);
+        if (begin) (void)prof_begin(p->c, p->part.k, std::string(name) + "|" + name + p->part.suffix, 0, 0);
+        else (void)prof_end(p->c, p->part.k);
     };
-    for (int i = 0; i < 2 && !rc; ++i) {
-        int first, n;
-        ProfCtx pc{c, chain_call(k, i, B, &first, &n), ""};
-        pc.suffix = chain_suffix(first, n);
+    if (!rc) rc = for_each_part(k, B, [&](const LaunchPart& part) {
+        ProfCtx pc{c, part};
         PPMaps mi = m;
-        mi.heat += first * m.sbh; mi.paf += first * m.sbp;
-        rc = pp_launch(mi, c->tab, pmx_pp_view(c->pp, first), n, map_h, map_w, img_len, dscale ? dscale + 2 * first : nullptr, 0, c->opt_pp_generic, pc.k.stream,
-                       c->prof_on == 1 ? +prof_cb : nullptr, &pc, c->pp_limbs_slices);
-    }
+        mi.heat += part.first * m.sbh; mi.paf += part.first * m.sbp;
+        return pp_launch(mi, c->tab, pmx_pp_view(c->pp, part.first), part.n, map_h, map_w, img_len, dscale ? dscale + 2 * part.first : nullptr, 0, c->opt_pp_generic,
+                         part.k.stream, c->prof_on == 1 ? +prof_cb : nullptr, &pc, c->pp_limbs_slices);
+    });
     // the join, whatever happened in between: the context's stream never runs ahead of the second chain
     PMX_HIP(hipEventRecord(ch.done, ch.stream));
     PMX_HIP(hipStreamWaitEvent(c->stream, ch.done, 0));
@@ -1981,7 +1953,7 @@ extern "C" int pmx_conv2d(pmx_ctx* c, const float* x, const float* w, const floa
     if ((rc = test_upload(c, x, d_x, d_xn, B, cin, H, W, L.cin_pad, 0))) return rc;
     const FwdCall k = pmx_call(c);
     ConvPlan p;
-    if ((rc = plan_conv(c, k, p, nullptr, &L, nullptr, d_xn, nullptr, L.cin_pad, d_yn, nullptr, cout, B, H, W, relu, pool, -1))) return rc;
+    if ((rc = plan_conv(c, k, p, nullptr, &L, nullptr, conv_io(ConvBuf::one(d_xn, L.cin_pad), ConvBuf::one(d_yn, cout), B, H, W, relu, pool)))) return rc;
     rc = launch_plan(c, k, p);
     if (!rc && iters > 0) {
         Event e0, e1;
@@ -2029,8 +2001,8 @@ extern "C" int pmx_conv2d_pair(pmx_ctx* c, const float* x0, const float* x1, con
     }
     const FwdCall k = pmx_call(c);
     ConvPlan p;
-    if ((rc = plan_conv(c, k, p, nullptr, &L[0], &L[1], d_xn.get() + ioff[0], d_xn.get() + ioff[1], lda, d_yn.get() + ooff[0], d_yn.get() + ooff[1], ldc,
-                        B, H, W, relu, pool, -1))) return rc;
+    if ((rc = plan_conv(c, k, p, nullptr, &L[0], &L[1], conv_io(ConvBuf::two(d_xn.get() + ioff[0], ioff[1] - ioff[0], lda), ConvBuf::two(d_yn.get(), ooff[1], ldc),
+                                                           B, H, W, relu, pool)))) return rc;
     if ((rc = launch_plan(c, k, p))) return rc;
     if ((rc = test_fetch(c, "pmx_conv2d_pair", d_yn, d_y, y0, B, cout0, Ho, Wo, ldc, ooff[0]))) return rc;
     return test_fetch(c, "pmx_conv2d_pair", d_yn, d_y, y1, B, cout1, Ho, Wo, ldc, ooff[1]);
@@ -2075,7 +2047,7 @@ extern "C" int pmx_conv2d_backward(pmx_ctx* c, const float* x, const float* w, c
     if (need_z) {
         if ((rc = test_layer(c, L, w, bias, cout, cin, ks)) || (rc = to_nhwc(d_xn, L.cin_pad)) || (rc = d_zn.alloc(nz))) return rc;
         PMX_HIP(hipMemsetAsync(d_zn, 0xFF, nz * 4, c->stream));
-        if ((rc = plan_conv(c, k, pz, nullptr, &L, nullptr, d_xn, nullptr, L.cin_pad, d_zn, nullptr, cout, B, H, W, 0, 0, -1))) return rc;
+        if ((rc = plan_conv(c, k, pz, nullptr, &L, nullptr, conv_io(ConvBuf::one(d_xn, L.cin_pad), ConvBuf::one(d_zn, cout), B, H, W, 0, 0)))) return rc;
         if ((rc = launch_plan(c, k, pz))) return rc;
     }
     if (need_g) {
@@ -2092,7 +2064,7 @@ extern "C" int pmx_conv2d_backward(pmx_ctx* c, const float* x, const float* w, c
         Lt.set = true;
         PMX_HIP(hipMemsetAsync(d_dxn, 0xFF, nx * 4, c->stream));       // poison: an unwritten element is caught by the test
         // g has cg >= Lt.cin_pad channels per pixel, the padding channels zero
-        if ((rc = plan_conv(c, kt, pt, nullptr, &Lt, nullptr, d_g, nullptr, cg, d_dxn, nullptr, cin, B, H, W, 0, 0, -1))) return rc;
+        if ((rc = plan_conv(c, kt, pt, nullptr, &Lt, nullptr, conv_io(ConvBuf::one(d_g, cg), ConvBuf::one(d_dxn, cin), B, H, W, 0, 0)))) return rc;
     }
     int strips = 0, rows = 0;
     if (dw) {
@@ -2151,11 +2123,7 @@ extern "C" int pmx_conv2d_backward(pmx_ctx* c, const float* x, const float* w, c
 }
 
 // ---------------------------------------------------------------------------- for pmx_backward.hip
-int pmx_run_conv(pmx_ctx* c, const char* label, PackedLayer* L0, PackedLayer* L1, const float* in0, const float* in1, int lda, float* out0,
-                 float* out1, int ldc, int B, int H, int W, int relu)
-{
-    return run_conv(c, pmx_call(c), label, L0, L1, in0, in1, lda, out0, out1, ldc, B, H, W, relu, 0);
-}
+int pmx_run_conv(pmx_ctx* c, const char* label, PackedLayer* L0, PackedLayer* L1, const ConvIO& io) { return run_conv(c, pmx_call(c), label, L0, L1, io); }
 
 // The layer whose forward is the data gradient of table layer `layer` (pack_index.h: the transposed pack), packed like any layer, from the
 // layer's master weights -- those of the training stores, else the layer's direct pack un-packed into a temporary (the context keeps no

@@ -243,7 +243,8 @@ extern "C" int pmx_backward_head(pmx_ctx* c)
         const int i0 = bw.slot_layer[k][0], i1 = bw.slot_layer[k][1];
         char label[64];
         snprintf(label, sizeof label, "bwd_dx:%s", c->table[i0].name.c_str());
-        return pmx_run_conv(c, label, &bw.tl[i0], o1 ? &bw.tl[i1] : nullptr, G(k), o1 ? G(k) + goff : nullptr, bw.slot[k].ldg, o0, o1, ldc, B, fh, fw, 0);
+        const ConvBuf g = o1 ? ConvBuf::two(G(k), goff, bw.slot[k].ldg) : ConvBuf::one(G(k), bw.slot[k].ldg);
+        return pmx_run_conv(c, label, &bw.tl[i0], o1 ? &bw.tl[i1] : nullptr, conv_io(g, ConvBuf{{o0, o1}, ldc}, B, fh, fw, 0, 0));
     };
     auto mask = [&](const float* u, int ldu, const float* a, int lda, int k) -> int {
         return bwd_mask_nhwc_launch(u, ldu, a, lda, G(k), bw.slot[k].ldg, npix, bw.slot[k].ldg, st);
@@ -357,7 +358,7 @@ extern "C" int pmx_backward_trunk(pmx_ctx* c)
         BW(pmx_prof_end(c));
         if (t == 0) break;
         snprintf(label, sizeof label, "bwd_dx:%s", d.name);
-        BW(pmx_run_conv(c, label, &bw.tl[idx], nullptr, g, nullptr, d.cout, bw.t_u, nullptr, d.cin, B, h, w, 0));
+        BW(pmx_run_conv(c, label, &bw.tl[idx], nullptr, conv_io(ConvBuf::one(g, d.cout), ConvBuf::one(bw.t_u, d.cin), B, h, w, 0, 0)));
         u = bw.t_u;
     }
 #undef BW

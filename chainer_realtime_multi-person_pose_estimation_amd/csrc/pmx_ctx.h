@@ -213,7 +213,7 @@ struct BatchChain {
 };
 struct ChainSplit {
     int n0 = 0;                      // images of the first chain
-    size_t net_px = 0;               // pixels of one network input (what places the second chain in act0 / act1: launch_plan_chains)
+    size_t net_px = 0;               // pixels of one network input (what places the second chain in act0 / act1: pmx_api.hip, image_offset)
     BatchChain* second = nullptr;
     bool probe = false, ok = true, rounds = true;
 };
@@ -228,6 +228,27 @@ struct FwdCall {
     ChainSplit* split = nullptr;     // the forward runs as two half-batch chains (null: one chain)
     BatchChain* scratch = nullptr;   // the launches of the second chain: its slabs and zero bias (null: ws.sk_scratch, the context's zero bias)
 };
+// The channel slices of one NHWC buffer that the (up to two) groups of a launch read or write, `ld` floats per pixel.  one: a single group;
+// two: both branches side by side in the buffer, the second `off` channels after the first (the pose network's brA / brB / brT / cat).
+struct ConvBuf {
+    float* p[2];
+    int ld;
+    static ConvBuf one(float* p, int ld) { return {{p, nullptr}, ld}; }
+    static ConvBuf two(float* p, int off, int ld) { return {{p, p + off}, ld}; }
+};
+// What a caller says about one layer launch: where its groups read and write (pointers already at the group's channels, [1] null: one
+// group), the batch, the INPUT map size and what follows the convolution.  `level` (heterogeneous forward only, FwdCall::seg set): the
+// resolution level of the layer's input, 0 = network input .. 3 = 1/8; B, H, W then carry the image count and the LARGEST map of the
+// level (launch checks), the geometry comes from the segment table of the level.
+struct ConvIO {
+    const float* in[2]; int lda;
+    float* out[2]; int ldc;
+    int B, H, W, relu, pool, level;
+};
+static inline ConvIO conv_io(const ConvBuf& in, const ConvBuf& out, int B, int H, int W, int relu, int pool, int level = -1)
+{
+    return {{in.p[0], in.p[1]}, in.ld, {out.p[0], out.p[1]}, out.ld, B, H, W, relu, pool, level};
+}
 // one post-process launch set of the current results: a uniform batch is one call (base 0), a mixed batch one per segment
 struct PPCall { PPMaps maps; PPTables tab; int base, B, map_h, map_w; double img_len; bool has_scale; int limbs_slices; };
 
@@ -561,8 +582,7 @@ int bwd_feat_sum_launch(float* fg, const float* a, const float* b, int ld, int f
 int bwd_copy_cols_launch(const float* src, int lds, float* dst, int ldd, long long npix, int nch, hipStream_t stream);
 // pmx_api.hip, for pmx_backward.hip: one layer (pair) through the forward's dispatcher (run_conv: plan_conv + launch_plan), and the pack of
 // c->bw.tl[layer] built from the layer's device weights (no-op when built)
-int pmx_run_conv(pmx_ctx* c, const char* label, PackedLayer* L0, PackedLayer* L1, const float* in0, const float* in1, int lda, float* out0,
-                 float* out1, int ldc, int B, int H, int W, int relu);
+int pmx_run_conv(pmx_ctx* c, const char* label, PackedLayer* L0, PackedLayer* L1, const ConvIO& io);
 int pmx_bw_transposed_pack(pmx_ctx* c, int layer);
 // c->smoothed (and c->pp.smoothed) at `floats` floats at least, grown to exactly that once the stream no longer uses the old maps
 int pmx_ensure_smoothed(pmx_ctx* c, size_t floats);

@@ -120,17 +120,26 @@ def test_no_stale_scratch_between_calls(small):
 
 
 def test_profile_labels_of_the_halves(small):
-    """every launch of the one-chain profile appears twice, "@0+2" and "@2+3", under the same form label"""
+    """every launch of the one-chain profile appears twice, "@0+2" and "@2+3", under the same form label, and the FLOP, issued FLOP and
+    bytes of the two halves (the one-chain figures scaled by 2/5 and 3/5 in double: a few ulps) add up to the one-chain figures"""
     imgs = images(5, seed=3)
     p0 = detect(small, imgs, 0, profile=True)[3]
     p1 = detect(small, imgs, 1, profile=True)[3]
     assert not halves(p0) and len(p0) >= 40
-    got = {(p['layer'], p['kernel']): p['launches'] for p in p1}
+    got = {(p['layer'], p['kernel']): p for p in p1}
     assert len(got) == 2 * len(p0)
     for p in p0:
-        for suffix in ('@0+2', '@2+3'):
-            assert got.get((p['layer'], p['kernel'] + suffix)) == p['launches'], (p['layer'], p['kernel'], suffix)
-    assert any('r/t' in p['kernel'] for p in p0)       # the run geometry with a unit-mode tail is among them
+        parts = [got.get((p['layer'], p['kernel'] + suffix)) for suffix in ('@0+2', '@2+3')]
+        for q in parts:
+            assert q is not None and q['launches'] == p['launches'], (p['layer'], p['kernel'])
+        for key in ('flop_per_launch', 'issued_flop_per_launch', 'bytes_per_launch'):
+            total = parts[0][key] + parts[1][key]
+            assert abs(total - p[key]) <= 1e-9 * abs(p[key]), (p['layer'], p['kernel'], key, parts[0][key], parts[1][key], p[key])
+    kernels = {p['layer']: p['kernel'] for p in p0}
+    assert 'conv1_1+conv1_2' in kernels and any('conv1x1_pair' in kn for kn in kernels.values())
+    # the run geometry with a unit-mode tail is among them, with its three entries
+    tails = [kn for kn in (p['kernel'] for p in p0) if 'r/t' in kn]
+    assert tails and any(kn.endswith(':units') for kn in tails) and any(kn.endswith(':combine') for kn in tails) and any(':' not in kn for kn in tails)
 
 
 def _hip():
