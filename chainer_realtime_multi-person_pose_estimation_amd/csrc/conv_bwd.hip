@@ -17,6 +17,7 @@
 //                    slots in order (pixel p, then p + 1) and consecutive MFMAs of an accumulator are consecutive pixel pairs.
 #include "pmx_ctx.h"
 #include "wgrad_strips.h"
+#include "f16_round.h"
 
 #pragma clang fp contract(off)
 
@@ -478,7 +479,47 @@ __global__ void __launch_bounds__(256) pool_bwd_nhwc_kernel(const float* u, int 
     for (int k = 0; k < 4; ++k) g[(base + (size_t)(k >> 1) * W + (k & 1)) * ldg + ch] = k == best && av[k] > 0.f ? d : 0.f;
 }
 
+// The range census of a g slice (pmx_backward_g_census): where the f16 kernels' conversion r = f16_rn_sat(v) puts the nch channels of every
+// pixel.  counts[0] v != 0, [1] v != 0 and r == 0, [2] r an f16 subnormal, [3] |v| > 65504, [4] NaN.  Every thread counts its elements of a
+// grid-stride loop, the block adds its threads' counts in LDS, and thread t < 5 adds the block's count t to counts[t] with one INTEGER atomic:
+// integer sums do not depend on the order, so the result is the same on every run.
+__global__ void __launch_bounds__(256) bwd_g_census_kernel(const float* g, int ldg, long long npix, int nch, unsigned long long* counts)
+{
+    unsigned n[5] = {0u, 0u, 0u, 0u, 0u};
+    const long long total = npix * nch, stride = (long long)gridDim.x * 256;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+        const long long pix = i / nch;
+        const float v = g[(size_t)pix * ldg + (int)(i - pix * nch)];
+        const unsigned mag = f16_rn_sat(v) & 0x7fffu;
+        n[0] += v != 0.f ? 1u : 0u;
+        n[1] += v != 0.f && mag == 0u ? 1u : 0u;
+        n[2] += mag > 0u && mag < 0x0400u ? 1u : 0u;
+        n[3] += fabsf(v) > 65504.f ? 1u : 0u;
+        n[4] += v != v ? 1u : 0u;
+    }
+    __shared__ unsigned long long lds[5][256];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) lds[k][threadIdx.x] = n[k];
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if ((int)threadIdx.x < w)
+#pragma unroll
+            for (int k = 0; k < 5; ++k) lds[k][threadIdx.x] += lds[k][threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x < 5 && lds[threadIdx.x][0]) atomicAdd(&counts[threadIdx.x], lds[threadIdx.x][0]);
+}
+
 }  // namespace
+
+int bwd_g_census_launch(const float* g, int ldg, long long npix, int nch, unsigned long long* counts, hipStream_t stream)
+{
+    PMX_CHECK(g && counts && npix >= 1 && nch >= 1 && ldg >= nch, PMX_ERR_INVALID, "g census: bad arguments");
+    const unsigned blocks = npix * nch < 1024ll * 256 ? bwd_blocks(npix * nch) : 1024u;
+    hipLaunchKernelGGL(bwd_g_census_kernel, dim3(blocks), dim3(256), 0, stream, g, ldg, npix, nch, counts);
+    PMX_HIP(hipGetLastError());
+    return PMX_OK;
+}
 
 int conv1_wgrad_strips(int B, int H, int forced, int* rows) { return pmx_wgrad_conv1_strips(B, H, forced, PMX_WGRAD_CONV1_STRIPS, rows); }
 

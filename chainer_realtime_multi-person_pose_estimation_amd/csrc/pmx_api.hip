@@ -374,8 +374,14 @@ extern "C" int pmx_set_option(pmx_ctx* c, const char* key, int value)
     else if (!strcmp(key, "wgrad_strips")) c->opt_wgrad_strips = value;
     else if (!strcmp(key, "grad_precision")) {
         PMX_CHECK(value == 0 || value == 2, PMX_ERR_INVALID,
-                  "pmx_set_option: \"grad_precision\" = %d: 0 (fp32 gradients) or 2 (f16 operands, fp32 sums; pmx_conv2d_backward only)", value);
+                  "pmx_set_option: \"grad_precision\" = %d: 0 (fp32 gradients) or 2 (f16 operands, fp32 sums: the 3x3 / 7x7 layers of "
+                  "pmx_conv2d_backward and pmx_backward_head)", value);
         c->opt_grad_precision = value;
+    }
+    else if (!strcmp(key, "loss_scale_log2")) {
+        PMX_CHECK(value >= 0 && value <= 24, PMX_ERR_INVALID,
+                  "pmx_set_option: \"loss_scale_log2\" = %d: k = 0 .. 24, the loss gradients of the next hooked forward times 2^k", value);
+        c->opt_loss_scale_log2 = value;
     }
     else if (!strcmp(key, "trunk_keep_g")) c->opt_trunk_keep_g = value != 0;
     else { pmx_set_error("pmx_set_option: unknown key '%s'", key); return PMX_ERR_INVALID; }
@@ -2123,18 +2129,24 @@ extern "C" int pmx_conv2d_backward(pmx_ctx* c, const float* x, const float* w, c
 }
 
 // ---------------------------------------------------------------------------- for pmx_backward.hip
-int pmx_run_conv(pmx_ctx* c, const char* label, PackedLayer* L0, PackedLayer* L1, const ConvIO& io) { return run_conv(c, pmx_call(c), label, L0, L1, io); }
+int pmx_run_conv(pmx_ctx* c, const char* label, PackedLayer* L0, PackedLayer* L1, const ConvIO& io, int precision)
+{
+    FwdCall k = pmx_call(c);
+    if (precision >= 0) k.precision = precision;
+    return run_conv(c, k, label, L0, L1, io);
+}
 
 // The layer whose forward is the data gradient of table layer `layer` (pack_index.h: the transposed pack), packed like any layer, from the
 // layer's master weights -- those of the training stores, else the layer's direct pack un-packed into a temporary (the context keeps no
 // other copy).  Its input is the layer's g: `cout` channels padded with zeros to 64 for the 38 / 19-channel outputs, so that both branches
 // of a launch have the same chunk count.  Its output has the layer's input channels -- for Mconv1_* the 192 channels of the concat buffer
 // in the buffer's order, the pad channels zero.
-int pmx_bw_transposed_pack(pmx_ctx* c, int layer)
+int pmx_bw_transposed_pack(pmx_ctx* c, int layer, bool f16)
 {
     PMX_CHECK(layer >= 0 && (size_t)layer < c->layers.size() && (size_t)layer < c->bw.tl.size(), PMX_ERR_INVALID, "backward pack: layer %d", layer);
     PackedLayer& Lt = c->bw.tl[layer];
-    if (Lt.set) return PMX_OK;
+    // (the f16 pack of the transposed layer: what the dispatcher's f16 form reads, built here so that the chain enqueues without a wait)
+    if (Lt.set) return f16 && Lt.ks > 1 ? ensure_f16_pack(c->stream, Lt) : PMX_OK;
     const PackedLayer& L = c->layers[layer];
     PMX_CHECK(L.set, PMX_ERR_WEIGHTS, "backward pack: layer '%s' has no weights", c->table[layer].name.c_str());
     if (L.busy) PMX_HIP(hipStreamSynchronize(L.busy_stream));      // a training step may still be writing d_w and the master weights
@@ -2151,5 +2163,5 @@ int pmx_bw_transposed_pack(pmx_ctx* c, int layer)
     if ((rc = build_transposed(P, L.cout, L.cin, L.ks, kind, master, c->stream))) return rc;
     P.set = true; P.busy = L.busy; P.busy_stream = L.busy_stream;
     Lt = std::move(P);
-    return PMX_OK;
+    return f16 && Lt.ks > 1 ? ensure_f16_pack(c->stream, Lt) : PMX_OK;
 }

@@ -202,17 +202,26 @@ extern "C" int pmx_backward_head(pmx_ctx* c)
     const int n = bw.stages, B = bw.B, fh = bw.fh, fw = bw.fw;
     const long long npix = (long long)B * fh * fw;
     hipStream_t st = c->stream;
-    // before anything is enqueued: the data-gradient packs and the workspace of the widest weight gradient
+    // option "grad_precision" = 2: dw and dx of the 3x3 / 7x7 layers with f16 operands (conv_wgrad_f16_launch; the dispatcher's f16 form on the
+    // transposed pack); the 1x1 layers, every db and every elementwise step keep their fp32 launches
+    auto f16_layer = [&](int idx) { return c->opt_grad_precision == 2 && c->table[idx].ks > 1; };
+    auto strips_of = [&](int idx, int cg, int cx, int* rows) {      // (the rule of the kernel that will run: the f16 rule gives more strips)
+        const LayerDesc& d = c->table[idx];
+        return f16_layer(idx) ? conv_wgrad_f16_strips(B, fh, cg, cx, d.ks, c->opt_wgrad_strips, rows)
+                              : conv_wgrad_strips(B, fh, cg, cx, d.ks, c->opt_wgrad_strips, rows);
+    };
+    // before anything is enqueued: the data-gradient packs (with their f16 packs where the f16 form will read them) and the workspace of the
+    // widest weight gradient
     size_t ws_need = 0;
     for (int k = 0; k < PMX_BW_X42; ++k) {
         if (slot_stage(k) > n) continue;
         for (int b = 0; b < 2; ++b) {
             const int idx = bw.slot_layer[k][b];
-            if ((rc = pmx_bw_transposed_pack(c, idx))) return rc;
+            if ((rc = pmx_bw_transposed_pack(c, idx, f16_layer(idx)))) return rc;
             const LayerDesc& d = c->table[idx];
             const int cg = round_up(d.cout, 32), cx = round_up(d.cin, 32);
             int rows = 0;
-            const int strips = conv_wgrad_strips(B, fh, cg, cx, d.ks, c->opt_wgrad_strips, &rows);
+            const int strips = strips_of(idx, cg, cx, &rows);
             ws_need = std::max(ws_need, (size_t)strips * d.ks * d.ks * cg * cx);
         }
     }
@@ -227,10 +236,10 @@ extern "C" int pmx_backward_head(pmx_ctx* c)
         float* dw = bw.grad + bw.grad_off[idx];
         float* db = dw + (size_t)d.cout * d.cin * d.ks * d.ks;
         int rows = 0;
-        const int strips = conv_wgrad_strips(B, fh, cg, cx, d.ks, c->opt_wgrad_strips, &rows);
+        const int strips = strips_of(idx, cg, cx, &rows);
         if (int r = conv_bwd_db_launch(g, ldg, bw.part, db, npix, d.cout, cg, st)) return r;
-        return conv_wgrad_launch(g, ldg, x, ldx, bw.ws, dw, B, fh, fw, d.cout, cg, d.cin, cx, d.ks, strips, rows,
-                                 d.cin == 185 ? bw.cat_of_ref.get() : nullptr, st);
+        return (f16_layer(idx) ? conv_wgrad_f16_launch : conv_wgrad_launch)(g, ldg, x, ldx, bw.ws, dw, B, fh, fw, d.cout, cg, d.cin, cx, d.ks, strips, rows,
+                                                                            d.cin == 185 ? bw.cat_of_ref.get() : nullptr, st, PMX_WGRAD_MAX_STRIPS);
     };
     // both branches of slot k: g at G(k) and G(k) + goff, x at x0 and x1
     auto grads2 = [&](int k, int goff, const float* x0, const float* x1, int ldx) -> int {
@@ -244,7 +253,7 @@ extern "C" int pmx_backward_head(pmx_ctx* c)
         char label[64];
         snprintf(label, sizeof label, "bwd_dx:%s", c->table[i0].name.c_str());
         const ConvBuf g = o1 ? ConvBuf::two(G(k), goff, bw.slot[k].ldg) : ConvBuf::one(G(k), bw.slot[k].ldg);
-        return pmx_run_conv(c, label, &bw.tl[i0], o1 ? &bw.tl[i1] : nullptr, conv_io(g, ConvBuf{{o0, o1}, ldc}, B, fh, fw, 0, 0));
+        return pmx_run_conv(c, label, &bw.tl[i0], o1 ? &bw.tl[i1] : nullptr, conv_io(g, ConvBuf{{o0, o1}, ldc}, B, fh, fw, 0, 0), f16_layer(i0) ? 2 : -1);
     };
     auto mask = [&](const float* u, int ldu, const float* a, int lda, int k) -> int {
         return bwd_mask_nhwc_launch(u, ldu, a, lda, G(k), bw.slot[k].ldg, npix, bw.slot[k].ldg, st);
@@ -436,6 +445,26 @@ extern "C" int pmx_get_retained(pmx_ctx* c, const char* name, int which, float* 
     if (which == 1) return fetch_nchw(c, bw.g + bw.slot[k].g_off + (size_t)b * (stage_out(k) ? 64 : C), bw.slot[k].ldg, C, out);
     if (k == PMX_BW_C44) return fetch_nchw(c, c->cat + PMX_CAT_FEAT, PMX_CAT_C, C, out);
     return fetch_nchw(c, bw.act + bw.slot[k].a_off + (size_t)b * (stage_out(k) ? PMX_CAT_HEAT - PMX_CAT_PAF : C), bw.slot[k].lda, C, out);
+}
+
+// The range census of one head layer's kept g (include/pose_mi355x.h): a launch of its own, on request only -- never part of the chain.
+extern "C" int pmx_backward_g_census(pmx_ctx* c, const char* name, unsigned long long counts[5])
+{
+    int rc, k, b;
+    if ((rc = bw_check(c, "pmx_backward_g_census", false))) return rc;
+    PMX_CHECK(counts, PMX_ERR_INVALID, "pmx_backward_g_census: null output");
+    if ((rc = bw_find(c, "pmx_backward_g_census", name, false, &k, &b)) || (rc = bw_check(c, "pmx_backward_g_census", true))) return rc;
+    PMX_DEV(c);
+    const BwState& bw = c->bw;
+    const int C = c->table[bw.slot_layer[k][b]].cout;
+    DevBuf<unsigned long long> d;
+    if ((rc = d.alloc(5))) return rc;
+    PMX_HIP(hipMemsetAsync(d, 0, 5 * sizeof(unsigned long long), c->stream));
+    rc = bwd_g_census_launch(bw.g + bw.slot[k].g_off + (size_t)b * (stage_out(k) ? 64 : C), bw.slot[k].ldg, (long long)bw.B * bw.fh * bw.fw, C, d, c->stream);
+    PMX_HIP(hipStreamSynchronize(c->stream));               // (nothing in flight may outlive the buffer)
+    if (rc) return rc;
+    PMX_HIP(hipMemcpy(counts, d, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return PMX_OK;
 }
 
 // ---- test entries: the trunk backward's own kernels on the caller's arrays (include/pose_mi355x.h) --------------------------------------

@@ -221,7 +221,8 @@ struct FwdCall {
     NetBufs& ws;                     // the working set: the context's own or a lane's
     hipStream_t stream;              // what every launch and profile event of the forward is enqueued on
     int conv_algo;                   // option "conv_algo" for this forward
-    int precision;                   // option "precision" for this forward (pmx_conv2d_backward's data gradient under "grad_precision" 2: 2)
+    int precision;                   // option "precision" for this forward (a data gradient of pmx_conv2d_backward or of the head chain under
+                                     // "grad_precision" 2: 2)
     const SegTables* seg = nullptr;  // a heterogeneous forward: its tables (null: a uniform batch)
     const uint8_t* in_u8 = nullptr;  // conv1_wino_kernel preprocesses this uint8 batch itself (null: the float input in ws.in16)
     float in_div = 255.0f;           // ... dividing by this
@@ -469,9 +470,12 @@ struct pmx_ctx : NetBufs {           // (the base: the context's own working set
     DevBuf<float> ls_grad;
     int lg_on = 0;
     int lg_stages = 0, lg_B = 0, lg_fh = 0, lg_fw = 0;    // the hooked forward whose gradients ls_grad holds (lg_stages 0: none)
+    int lg_scale_log2 = 0;                                // ... and the "loss_scale_log2" it ran under: ls_grad holds 2^k times the gradients
+    int opt_loss_scale_log2 = 0;                          // k = 0 .. 24: the next hooked forward hands loss_grad_kernel its two constants times 2^k
     // pmx_conv2d_backward: test-only, S0 of the weight-gradient strips (0: automatic); include/pose_mi355x.h
     int opt_wgrad_strips = 0;
-    // pmx_conv2d_backward: 0 fp32 gradients; 2: dw and dx of a 3x3 / 7x7 layer with f16 operands and fp32 sums (include/pose_mi355x.h)
+    // pmx_conv2d_backward and pmx_backward_head: 0 fp32 gradients; 2: dw and dx of a 3x3 / 7x7 layer with f16 operands and fp32 sums
+    // (include/pose_mi355x.h)
     int opt_grad_precision = 0;
     int opt_trunk_keep_g = 0;        // read by pmx_backward_enable(2): keep the masked gradient of every trunk layer for pmx_get_retained (tests)
     // pmx_samples.hip (sample preparation).  sp: [descriptors | resize tables | host sources]; sp_a: the resized intermediates of the
@@ -580,10 +584,14 @@ int bwd_mask_nhwc_launch(const float* u, int ldu, const float* a, int lda, float
 int bwd_stage_sum_launch(const float* lg, const float* d0, const float* d1, int ldd, float* g, long long npix, hipStream_t stream);
 int bwd_feat_sum_launch(float* fg, const float* a, const float* b, int ld, int first, long long npix, hipStream_t stream);
 int bwd_copy_cols_launch(const float* src, int lds, float* dst, int ldd, long long npix, int nch, hipStream_t stream);
+// conv_bwd.hip: the range census of one g slice (pmx_backward_g_census): counts[0 .. 4] += the pixels' nch channels that are non-zero, flushed
+// to zero by f16_rn_sat, f16 subnormals after it, above 65504 in magnitude, NaN.  counts: five device words, zeroed by the caller
+int bwd_g_census_launch(const float* g, int ldg, long long npix, int nch, unsigned long long* counts, hipStream_t stream);
 // pmx_api.hip, for pmx_backward.hip: one layer (pair) through the forward's dispatcher (run_conv: plan_conv + launch_plan), and the pack of
 // c->bw.tl[layer] built from the layer's device weights (no-op when built)
-int pmx_run_conv(pmx_ctx* c, const char* label, PackedLayer* L0, PackedLayer* L1, const ConvIO& io);
-int pmx_bw_transposed_pack(pmx_ctx* c, int layer);
+// (precision: the call's, as FwdCall::precision -- 2 for a data gradient of the head chain under "grad_precision" 2; -1: the context's own)
+int pmx_run_conv(pmx_ctx* c, const char* label, PackedLayer* L0, PackedLayer* L1, const ConvIO& io, int precision = -1);
+int pmx_bw_transposed_pack(pmx_ctx* c, int layer, bool f16 = false);      // (f16: a 3x3 / 7x7 layer's f16 pack of it as well)
 // c->smoothed (and c->pp.smoothed) at `floats` floats at least, grown to exactly that once the stream no longer uses the old maps
 int pmx_ensure_smoothed(pmx_ctx* c, size_t floats);
 // pmx_api.hip: the channel map kind of a layer's direct pack (pack_index.h).  pmx_train.hip: the master weights (w OIHW | b) of a layer with
@@ -598,9 +606,9 @@ void pmx_train_free(pmx_ctx* c);
 // as one of a device table's (pmx_pack_launch_table: the jobs' blk0 ascending, `blocks` their sum).  pmx_unpack_launch: L's direct pack and
 // bias -> (w OIHW | b).
 // The kinds in launch order: what reads a direct pack comes after PMX_PACK_DIRECT.  PMX_PACK_JOBS_PER_LAYER: the jobs of a kind one layer
-// gives a step's table at most (Winograd: its own pack and its transposed layer's); 0: one job per context (conv1_1's).
+// gives a step's table at most (f16, Winograd: its own pack and its transposed layer's); 0: one job per context (conv1_1's).
 enum { PMX_PACK_DIRECT = 0, PMX_PACK_F16, PMX_PACK_BF16X3, PMX_PACK_TRANSPOSED, PMX_PACK_WINO, PMX_PACK_CONV1, PMX_PACK_KINDS };
-constexpr int PMX_PACK_JOBS_PER_LAYER[PMX_PACK_KINDS] = {1, 1, 1, 1, 2, 0};
+constexpr int PMX_PACK_JOBS_PER_LAYER[PMX_PACK_KINDS] = {1, 2, 1, 1, 2, 0};
 void pmx_layer_geometry(PackedLayer& L, int cout, int cin, int ks, int cin_pad);
 PackJob pmx_pack_job_direct(const float* master, const PackedLayer& L, int kind);
 PackJob pmx_pack_job_f16(const PackedLayer& L, uint16_t* dst);

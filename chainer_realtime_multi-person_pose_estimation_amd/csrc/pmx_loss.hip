@@ -331,12 +331,15 @@ int pmx_loss_stage(pmx_ctx* c, int stage, int B, int fh, int fw)
     const long long npix = (long long)B * fhw;
     PMX_CHECK(c->ls_grad.capacity() >= (size_t)(PMX_LOSS_SLOTS - 1) * npix * N_CH, PMX_ERR_STATE, "pmx_loss_stage: no gradient buffer");
     if (stage == 1) c->lg_stages = 0;                       // until pmx_loss_finish: the buffer is being rewritten
+    // option "loss_scale_log2" = k: both constants times 2^k, on the host and exact (ldexpf of a normal float32 far from the range's ends);
+    // the kernel's one product c * d then carries the factor, and everything downstream is linear
+    const int k = c->opt_loss_scale_log2;
     snprintf(label, sizeof label, "loss_grad%d|pmx_loss_grad", stage);
     int rc;
     if ((rc = pmx_prof_begin(c, label, (double)npix * (3 * N_CH * 4 + 1)))) return rc;
     hipLaunchKernelGGL(loss_grad_kernel, dim3(blocks_for(npix * N_CH)), dim3(256), 0, c->stream, src, (const float*)c->ls_tgt,
                        (const uint8_t*)c->ls_mask, c->ls_grad + (size_t)(stage - 1) * npix * N_CH, npix, fh * fw,
-                       (float)(2.0 / ((double)npix * PMX_N_PAF)), (float)(2.0 / ((double)npix * PMX_N_HEAT)));
+                       ldexpf((float)(2.0 / ((double)npix * PMX_N_PAF)), k), ldexpf((float)(2.0 / ((double)npix * PMX_N_HEAT)), k));
     PMX_HIP(hipGetLastError());
     return pmx_prof_end(c);
 }
@@ -345,7 +348,7 @@ int pmx_loss_finish(pmx_ctx* c, int n_stages, int B, int fh, int fw)
 {
     if (int rc = launch_final(c, 0, PMX_LOSS_SLOTS - 1, n_stages, B, fh, fw)) return rc;
     c->ls_stages = n_stages;
-    if (c->lg_on) { c->lg_stages = n_stages; c->lg_B = B; c->lg_fh = fh; c->lg_fw = fw; }
+    if (c->lg_on) { c->lg_stages = n_stages; c->lg_B = B; c->lg_fh = fh; c->lg_fw = fw; c->lg_scale_log2 = c->opt_loss_scale_log2; }
     return PMX_OK;
 }
 
@@ -496,6 +499,17 @@ extern "C" int pmx_get_loss_grads(pmx_ctx* c, int stage, float* gpaf, float* ghe
             if (gpaf) for (int ch = 0; ch < PMX_N_PAF; ++ch) gpaf[(b * PMX_N_PAF + ch) * fhw + p] = q[ch];
             if (gheat) for (int ch = 0; ch < PMX_N_HEAT; ++ch) gheat[(b * PMX_N_HEAT + ch) * fhw + p] = q[PMX_N_PAF + ch];
         }
+    return PMX_OK;
+}
+
+// the "loss_scale_log2" the stored gradients carry: that of the hooked forward that wrote them, whatever the option says now
+extern "C" int pmx_get_loss_grad_scale(pmx_ctx* c, int* scale_log2)
+{
+    PMX_CHECK(c && scale_log2, PMX_ERR_INVALID, "pmx_get_loss_grad_scale: null arg");
+    LOSS_POSENET(c, "pmx_get_loss_grad_scale");
+    PMX_CHECK(c->lg_on && c->lg_stages > 0, PMX_ERR_STATE,
+              "pmx_get_loss_grad_scale: no forward with the validation-loss hook and the gradients on yet (pmx_loss_enable, pmx_loss_grad_enable)");
+    *scale_log2 = c->lg_scale_log2;
     return PMX_OK;
 }
 

@@ -1,5 +1,6 @@
 // pmx_train.hip -- the training steps of the C ABI: pmx_train_enable / pmx_train_set_adam / pmx_train_set_grad_scale /
-// pmx_train_step_head / pmx_train_step / pmx_get_layer / pmx_train_get_state / pmx_train_set_state / pmx_get_pack / pmx_adam_apply.  Semantics:
+// pmx_train_step_head / pmx_train_step / pmx_get_layer / pmx_train_get_state / pmx_train_set_state / pmx_get_pack /
+// pmx_get_transposed_f16_pack / pmx_adam_apply.  Semantics:
 // include/pose_mi355x.h; the stores' layout: pmx_ctx.h (TrainState, BwState::grad); every pack: pack_index.h, built by pmx_packs.hip.
 //
 // THE ADAM CONTRACT is this project's own restatement of Chainer's AdamRule (eta = 1, weight_decay_rate = 0) as a sequence of float32
@@ -157,6 +158,8 @@ int repack_jobs(pmx_ctx* c, int idx, const float* w, JobList* jl)
     PMX_CHECK(P.d_w.capacity() == jt.total && P.cout == pmx_pk_t_cout(kind, L.cin) && P.cin_pad == pmx_pk_t_cin_pad(L.cout), PMX_ERR_STATE,
               "training step: layer '%s': a transposed pack of another shape", c->table[idx].name.c_str());
     add_job(jl[PMX_PACK_TRANSPOSED], jt);
+    // (the f16 pack of the transposed layer exists once a head backward ran under "grad_precision" 2: the next one reads the new weights)
+    if (P.d_w16 && (rc = derived_job(jl[PMX_PACK_F16], pmx_pack_job_f16(P, P.d_w16), P.d_w16.capacity(), "a transposed f16"))) return rc;
     if (P.d_ww && (rc = wino_job(jl[PMX_PACK_WINO], P))) return rc;
     return PMX_OK;
 }
@@ -327,10 +330,12 @@ static int train_step(pmx_ctx* c, const char* who, bool full)
     if (int r = pmx_prof_end(c)) return r;
     if (rc) return rc;
     // the packers, in the order of their inputs: the direct and transposed packs read the master weights, the f16, bf16x3, Winograd and
-    // conv1_1 packs the direct packs just written (the order of PMX_PACK_*)
+    // conv1_1 packs the direct packs just written -- and the f16 and Winograd packs of a transposed layer the transposed pack just written,
+    // so the transposed packs go before the f16 ones
+    static const int order[PMX_PACK_KINDS] = {PMX_PACK_DIRECT, PMX_PACK_TRANSPOSED, PMX_PACK_F16, PMX_PACK_BF16X3, PMX_PACK_WINO, PMX_PACK_CONV1};
     if ((rc = pmx_prof_begin(c, "train_step|pack", 0))) return rc;
-    for (int k = 0; k < PMX_PACK_KINDS && !rc; ++k)
-        if (jl[k].n) rc = pmx_pack_launch_table(k, reinterpret_cast<const PackJob*>(dev + jobs_at(N, k)), jl[k].n, jl[k].blocks, st);
+    for (int i = 0; i < PMX_PACK_KINDS && !rc; ++i)
+        if (const int k = order[i]; jl[k].n) rc = pmx_pack_launch_table(k, reinterpret_cast<const PackJob*>(dev + jobs_at(N, k)), jl[k].n, jl[k].blocks, st);
     if (int r = pmx_prof_end(c)) return r;
     return rc;
 }
@@ -396,19 +401,19 @@ extern "C" int pmx_train_set_state(pmx_ctx* c, const char* name, const float* m_
     return PMX_OK;
 }
 
-extern "C" int pmx_get_pack(pmx_ctx* c, const char* name, int which, void* out, size_t cap_bytes, size_t* n_bytes)
+// which = 0 .. 6: pmx_get_pack's; 7: the f16 pack of the transposed layer (pmx_get_transposed_f16_pack)
+static int get_pack(pmx_ctx* c, const char* name, int which, void* out, size_t cap_bytes, size_t* n_bytes)
 {
     PMX_CHECK(c && name && n_bytes, PMX_ERR_INVALID, "pmx_get_pack: null arg");
-    PMX_CHECK(which >= 0 && which <= 6, PMX_ERR_INVALID, "pmx_get_pack: which = %d outside 0 .. 6", which);
     auto it = c->index.find(name);
     PMX_CHECK(it != c->index.end(), PMX_ERR_INVALID, "pmx_get_pack: unknown layer '%s'", name);
     const int idx = it->second;
     const PackedLayer* L = &c->layers[idx];
-    if (which == 3 || which == 4) {
+    if (which == 3 || which == 4 || which == 7) {
         PMX_CHECK((size_t)idx < c->bw.tl.size() && c->bw.tl[idx].set, PMX_ERR_STATE, "pmx_get_pack: layer '%s' has no transposed pack", name);
         L = &c->bw.tl[idx];
     }
-    const DevBuf<uint16_t>& h = which == 5 ? L->d_w16 : L->d_w3;
+    const DevBuf<uint16_t>& h = which == 5 || which == 7 ? L->d_w16 : L->d_w3;
     const DevBuf<float>& f = which == 0 || which == 3 ? L->d_w : which == 1 ? L->d_b : L->d_ww;
     const void* const b = which >= 5 ? (const void*)h.get() : (const void*)f.get();
     PMX_CHECK(L->set && b, PMX_ERR_STATE, "pmx_get_pack: pack %d of layer '%s' does not exist", which, name);
@@ -418,6 +423,17 @@ extern "C" int pmx_get_pack(pmx_ctx* c, const char* name, int which, void* out, 
     PMX_HIP(hipStreamSynchronize(c->stream));
     PMX_HIP(hipMemcpy(out, b, *n_bytes, hipMemcpyDeviceToHost));
     return PMX_OK;
+}
+
+extern "C" int pmx_get_pack(pmx_ctx* c, const char* name, int which, void* out, size_t cap_bytes, size_t* n_bytes)
+{
+    PMX_CHECK(which >= 0 && which <= 6, PMX_ERR_INVALID, "pmx_get_pack: which = %d outside 0 .. 6", which);
+    return get_pack(c, name, which, out, cap_bytes, n_bytes);
+}
+
+extern "C" int pmx_get_transposed_f16_pack(pmx_ctx* c, const char* name, void* out, size_t cap_bytes, size_t* n_bytes)
+{
+    return get_pack(c, name, 7, out, cap_bytes, n_bytes);
 }
 
 // test entry: the Adam launch on the caller's arrays (host, `total` floats each, updated in place); segment i covers floats

@@ -344,6 +344,7 @@ def load():
         'pmx_conv2d_backward': (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, dp]),
         'pmx_loss_grad_enable': (ci, [vp, ci]),
         'pmx_get_loss_grads': (ci, [vp, ci, vp, vp]),
+        'pmx_get_loss_grad_scale': (ci, [vp, ip]),
         'pmx_backward_enable': (ci, [vp, ci]),
         'pmx_backward_head': (ci, [vp]),
         'pmx_backward_trunk': (ci, [vp]),
@@ -352,6 +353,7 @@ def load():
         'pmx_get_layer_grad': (ci, [vp, C.c_char_p, vp, vp]),
         'pmx_get_trunk_grad': (ci, [vp, vp]),
         'pmx_get_retained': (ci, [vp, C.c_char_p, ci, vp]),
+        'pmx_backward_g_census': (ci, [vp, C.c_char_p, C.POINTER(C.c_ulonglong)]),
         'pmx_loss_set_poses': (ci, [vp, vp, vp, ci, ci, ci, vp, cd, cd]),
         'pmx_loss_set_targets': (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci]),
         'pmx_loss_enable': (ci, [vp, ci]),
@@ -373,6 +375,7 @@ def load():
         'pmx_train_get_state': (ci, [vp, C.c_char_p, vp, vp, vp, vp, ip]),
         'pmx_train_set_state': (ci, [vp, C.c_char_p, vp, vp, vp, vp, ci]),
         'pmx_get_pack': (ci, [vp, C.c_char_p, ci, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+        'pmx_get_transposed_f16_pack': (ci, [vp, C.c_char_p, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
         'pmx_adam_apply': (ci, [vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp, ci, C.c_float, C.c_float, C.c_float]),
     }
     for name, (res, args) in sig.items():
@@ -1171,6 +1174,13 @@ class Engine(object):
         self._check(self.lib.pmx_get_loss_grads(self._ctx, int(stage), _ptr(gp), _ptr(gh)))
         return gp, gh
 
+    def loss_grad_scale_log2(self):
+        """k of option 'loss_scale_log2' as it was when the last hooked forward with the gradients on ran: what loss_grads, layer_grad,
+        trunk_grad and retained(name, 1) return is 2^k times the gradient of the loss."""
+        k = C.c_int(0)
+        self._check(self.lib.pmx_get_loss_grad_scale(self._ctx, C.byref(k)))
+        return k.value
+
     # ---- head backward (include/pose_mi355x.h: pmx_backward_*) -----------------------------------------------------------
     TRUNK_LAYERS = ('conv1_1', 'conv1_2', 'conv2_1', 'conv2_2', 'conv3_1', 'conv3_2', 'conv3_3', 'conv3_4', 'conv4_1', 'conv4_2')
 
@@ -1241,8 +1251,18 @@ class Engine(object):
         self._check(self.lib.pmx_get_retained(self._ctx, name.encode(), int(which), _ptr(out)))
         return out
 
+    CENSUS = ('nonzero', 'flushed', 'subnormal', 'saturated', 'nan')
+
+    def g_census(self, name):
+        """Where the f16 conversion of the gradient kernels puts the kept g of one head layer after backward_head: {'nonzero', 'flushed'
+        (non-zero, rounds to zero), 'subnormal' (an f16 subnormal after rounding), 'saturated' (above 65504 in magnitude), 'nan'} -> count,
+        over what retained(name, 1) returns (synchronises)."""
+        counts = (C.c_ulonglong * 5)()
+        self._check(self.lib.pmx_backward_g_census(self._ctx, name.encode(), counts))
+        return dict(zip(self.CENSUS, (int(v) for v in counts)))
+
     # ---- training steps (include/pose_mi355x.h: pmx_train_*) ----- ------------------------------------------------------
-    PACKS = {'w': 0, 'b': 1, 'wino': 2, 't_w': 3, 't_wino': 4, 'f16': 5, 'bf16x3': 6}
+    PACKS = {'w': 0, 'b': 1, 'wino': 2, 't_w': 3, 't_wino': 4, 'f16': 5, 'bf16x3': 6, 't_f16': 7}
 
     def layer_shape(self, name):
         """(cout, cin, k, k) of layer `name` as installed (KeyError for a layer never set through this engine)."""
@@ -1298,16 +1318,21 @@ class Engine(object):
 
     def get_pack(self, name, which):
         """The raw contents of one device pack of a layer -- float32 for 'w', 'b', 'wino', 't_w', 't_wino' (or 0 .. 4), the uint16 words of
-        'f16' and 'bf16x3' (5, 6) -- None if that pack does not exist now (synchronises)."""
+        'f16', 'bf16x3' and 't_f16', the f16 pack of the transposed layer (5, 6, 7) -- None if that pack does not exist now (synchronises)."""
         which = self.PACKS.get(which, which)
         n = C.c_size_t(0)
-        rc = self.lib.pmx_get_pack(self._ctx, name.encode(), int(which), None, 0, C.byref(n))
+
+        def fetch(out, cap):          # (pack 7 has an entry of its own: pmx_get_pack's `which` ends at 6)
+            if which == 7:
+                return self.lib.pmx_get_transposed_f16_pack(self._ctx, name.encode(), out, cap, C.byref(n))
+            return self.lib.pmx_get_pack(self._ctx, name.encode(), int(which), out, cap, C.byref(n))
+        rc = fetch(None, 0)
         if rc == 6:          # PMX_ERR_STATE: no such pack now
             return None
         if rc != 5:          # (PMX_ERR_CAPACITY: the size query)
             self._check(rc)
         out = np.empty(n.value // 2, np.uint16) if which >= 5 else np.empty(n.value // 4, np.float32)
-        self._check(self.lib.pmx_get_pack(self._ctx, name.encode(), int(which), _ptr(out), out.nbytes, C.byref(n)))
+        self._check(fetch(_ptr(out), out.nbytes))
         return out
 
     def adam_apply(self, w, m, v, grad, off, n, scale, alpha_t, omb1, omb2, eps):

@@ -72,6 +72,8 @@ class PoseDetector(object):
         self._mode2 = False                        # training retains the trunk (engine backward mode 2); stays once the trunk was trainable
         self._adam = dict(alpha=1e-4, beta1=0.9, beta2=0.999, eps=1e-8)
         self._grad_scales = dict(self.REFERENCE_GRAD_SCALES)
+        self._grad_precision = 'f32'               # set_gradient_precision: engine option "grad_precision" of the head backward
+        self._loss_scale_log2 = 0                  # ... and k of the static loss scale 2^k (engine option "loss_scale_log2")
         self._make_engine(max_batch, mh, mw)
 
     def _make_engine(self, max_batch, mh, mw):
@@ -110,6 +112,7 @@ class PoseDetector(object):
                 eng.set_weights(self._weights)
             if self._precision != 'f32':
                 eng.set_option('precision', native.PRECISIONS[self._precision])
+            self._apply_gradient_settings(eng)
             if self._gpu_branch_peaks:
                 # the reference's own GPU branch of compute_peaks_from_heatmaps (:111-133): 17x17 un-normalised kernel, zero
                 # padding, '>=' NMS -- NOT the golden CPU semantics; off by default
@@ -118,6 +121,57 @@ class PoseDetector(object):
             eng.close()
             raise
         return eng
+
+    # ---- gradient precision and the static loss scale (include/pose_mi355x.h: options "grad_precision", "loss_scale_log2") -----------------
+    GRAD_PRECISIONS = {'f32': 0, 'f16': 2}
+
+    @classmethod
+    def _check_gradient_precision(cls, precision, loss_scale):
+        """-> k with loss_scale == 2^k, k = 0 .. 24; ValueError for anything else and for an unknown precision"""
+        if precision not in cls.GRAD_PRECISIONS:
+            raise ValueError("gradient precision must be 'f32' or 'f16', got %r" % (precision,))
+        try:
+            m, e = math.frexp(float(loss_scale))
+        except (TypeError, ValueError, OverflowError):
+            m, e = 0.0, 0
+        if m != 0.5 or not 0 <= e - 1 <= 24:
+            raise ValueError('loss_scale must be a power of two in [1, 2^24], got %r' % (loss_scale,))
+        return e - 1
+
+    def set_gradient_precision(self, precision='f32', loss_scale=1.0):
+        """How head_gradients, network_gradients, gradient_range and train_step compute the head's gradients.  precision 'f16': dw and dx of
+        the 58 3x3 / 7x7 layers after conv4_2 with f16 operands and fp32 sums on the f16 matrix cores ('f32', the default: everything fp32);
+        the trunk chain, the 1x1 layers, every db and Adam stay fp32 either way.  loss_scale, a power of two in [1, 2^24]: the loss gradients
+        are multiplied by it on the device, so that gradients below the f16 range are not flushed (gradient_range shows what a scale leaves
+        outside); it is taken out again exactly -- on the host in the arrays the *_gradients methods return, and in train_step through every
+        layer's gradient scale, scale * 2^-k.  The setting stays with the detector: it is applied to every engine it creates and whenever
+        training starts."""
+        k = self._check_gradient_precision(precision, loss_scale)
+        self._grad_precision, self._loss_scale_log2 = precision, k
+        if self.engine is not None:
+            self._apply_gradient_settings(self.engine)
+            if self._train_on:
+                self._fold_scales(self._trainable_layers())
+
+    def _apply_gradient_settings(self, eng):
+        eng.set_option('grad_precision', self.GRAD_PRECISIONS[self._grad_precision])
+        eng.set_option('loss_scale_log2', self._loss_scale_log2)
+
+    def _trainable_layers(self):
+        """the layers with Adam state in the engine: the 82 after conv4_2, in mode 2 the ten trunk layers as well"""
+        return (list(self.engine.TRUNK_LAYERS) if self._mode2 else []) + self.engine.head_layers()
+
+    def _fold_scales(self, names):
+        """the engine's gradient scale of each layer: the user's times 2^-k, which takes the loss scale out of the gradient in Adam's first
+        line (exact: a power of two)"""
+        unscale = 2.0 ** -self._loss_scale_log2
+        for name in names:
+            self.engine.train_set_grad_scale(name, self._grad_scales.get(name, 1.0) * unscale)
+
+    def _unscale(self, arr):
+        """the stored gradients are 2^k times the loss's, k that of the forward that made them: 2^-k times them, on the host (exact)"""
+        k = self.engine.loss_grad_scale_log2()
+        return arr if k == 0 else arr * np.float32(2.0 ** -k)
 
     # ---- host helpers with the reference's names and semantics -------------------------------------
     def compute_optimal_size(self, orig_img, img_size, stride=8):
@@ -604,7 +658,8 @@ class PoseDetector(object):
         """`validation_loss` plus where `loss.backward()` starts (train_coco_pose_estimation.py:90-126): the gradient of the total loss at
         the twelve stage outputs, on the device in the same forward.  Arguments as validation_loss.  -> its dictionary plus 'paf_grads' /
         'heat_grads': lists of six (B, 38 | 19, h/8, w/8) float32 arrays.  The gradient's scale 2 / N depends on the batch, so chunks
-        cannot be merged: more images than the engine's batch raise ValueError."""
+        cannot be merged: more images than the engine's batch raise ValueError.  The arrays are UN-SCALED: under a loss scale
+        (set_gradient_precision) the device's values are multiplied by 2^-k on the host."""
         imgs, poses, masks = self._check_validation_args(imgs, poses_per_image, ignore_masks)
         if self.model is not None:
             raise RuntimeError('loss_gradients runs the built-in network: not available with a model= callable')
@@ -619,7 +674,7 @@ class PoseDetector(object):
         self.engine.loss_grad_enable(True)
         try:
             total, paf, heat = self.engine.validate_batch(np.stack(imgs))
-            grads = [self.engine.loss_grads(s) for s in range(6)]
+            grads = [tuple(self._unscale(g) for g in self.engine.loss_grads(s)) for s in range(6)]
         finally:
             if not self._train_on:
                 self.engine.loss_grad_enable(False)
@@ -631,7 +686,8 @@ class PoseDetector(object):
         """`loss_gradients` plus the backward of the 82 layers after conv4_2 -- the layers the reference updates while conv1_1 .. conv4_2 are
         frozen (train_coco_pose_estimation.py:219-225) -- on the device.  Arguments as validation_loss.  -> loss_gradients' dictionary plus
         'grads': {layer name: (dW OIHW, db)} float32 and 'trunk_grad': (B, 512, h/8, w/8), the gradient at conv4_2's output.  More images
-        than the engine's batch raise ValueError."""
+        than the engine's batch raise ValueError.  Computed as set_gradient_precision says; every array is UN-SCALED (the device's values
+        times 2^-k on the host)."""
         imgs, poses, masks = self._check_validation_args(imgs, poses_per_image, ignore_masks)
         if self.model is not None:
             raise RuntimeError('head_gradients runs the built-in network: not available with a model= callable')
@@ -649,9 +705,9 @@ class PoseDetector(object):
             eng.backward_enable(True)
             total, paf, heat = eng.validate_batch(np.stack(imgs))
             eng.backward_head()
-            grads = [eng.loss_grads(s) for s in range(6)]
-            layer_grads = {name: eng.layer_grad(name) for name in eng.head_layers()}
-            trunk = eng.trunk_grad()
+            grads = [tuple(self._unscale(g) for g in eng.loss_grads(s)) for s in range(6)]
+            layer_grads = {name: tuple(self._unscale(g) for g in eng.layer_grad(name)) for name in eng.head_layers()}
+            trunk = self._unscale(eng.trunk_grad())
         finally:
             if not self._train_on:          # (training lives on the backward's stores: they stay while it is on)
                 eng.backward_enable(False)
@@ -664,7 +720,9 @@ class PoseDetector(object):
         """`head_gradients` continued through conv4_2 .. conv1_1: the gradients of all 92 layers, what the reference's loss.backward() gives
         once it has un-frozen the trunk (train_coco_pose_estimation.py:96-101, from iteration 2000 on).  Arguments and result as
         head_gradients, 'grads' with 92 entries.  The forward retains the trunk (engine mode 2), so its stem runs unfused.  More images than
-        the engine's batch raise ValueError; not available while training is on (stop_training first)."""
+        the engine's batch raise ValueError; not available while training is on (stop_training first).  The head as
+        set_gradient_precision says, the trunk chain in fp32 from the head's (scaled) trunk gradient; every array is UN-SCALED (times 2^-k
+        on the host)."""
         imgs, poses, masks = self._check_validation_args(imgs, poses_per_image, ignore_masks)
         if self.model is not None:
             raise RuntimeError('network_gradients runs the built-in network: not available with a model= callable')
@@ -685,15 +743,43 @@ class PoseDetector(object):
             total, paf, heat = eng.validate_batch(np.stack(imgs))
             eng.backward_head()
             eng.backward_trunk()
-            grads = [eng.loss_grads(s) for s in range(6)]
-            layer_grads = {name: eng.layer_grad(name) for name in list(eng.TRUNK_LAYERS) + eng.head_layers()}
-            trunk = eng.trunk_grad()
+            grads = [tuple(self._unscale(g) for g in eng.loss_grads(s)) for s in range(6)]
+            layer_grads = {name: tuple(self._unscale(g) for g in eng.layer_grad(name)) for name in list(eng.TRUNK_LAYERS) + eng.head_layers()}
+            trunk = self._unscale(eng.trunk_grad())
         finally:
             eng.backward_enable(False)
             eng.loss_grad_enable(False)
         return {'val/loss': float(total), 'val/paf': float(paf.sum()), 'val/heat': float(heat.sum()),
                 'paf_stages': [float(v) for v in paf], 'heat_stages': [float(v) for v in heat],
                 'paf_grads': [g[0] for g in grads], 'heat_grads': [g[1] for g in grads], 'grads': layer_grads, 'trunk_grad': trunk}
+
+    def gradient_range(self, imgs, poses_per_image, ignore_masks=None):
+        """Where the gradients of this batch fall in the f16 range at the current settings (set_gradient_precision): one retained forward
+        and head backward, then per layer after conv4_2 the census of its masked gradient g as the f16 kernels would round it ->
+        {layer: {'nonzero', 'flushed', 'subnormal', 'saturated', 'nan'}} (counts of elements: non-zero; non-zero but rounded to zero; f16
+        subnormals; above 65504 in magnitude; NaN).  The data for choosing loss_scale: raise it while 'flushed' falls and 'saturated'
+        stays 0.  Arguments as head_gradients."""
+        imgs, poses, masks = self._check_validation_args(imgs, poses_per_image, ignore_masks)
+        if self.model is not None:
+            raise RuntimeError('gradient_range runs the built-in network: not available with a model= callable')
+        if self.engine.weights_missing():
+            raise RuntimeError('PoseDetector has no weights: pass weights_file=, weights= or model=')
+        h, w = imgs[0].shape[:2]
+        self._grow(1, h, w)
+        if len(imgs) > self._cap[0]:
+            raise ValueError('gradient_range: %d images, the engine holds batches of %d' % (len(imgs), self._cap[0]))
+        eng = self.engine
+        eng.loss_set_poses(poses, h, w, None if masks is None else np.stack(masks), params['heatmap_sigma'], params['paf_sigma'])
+        eng.loss_grad_enable(True)
+        try:
+            eng.backward_enable(2 if self._train_on and self._mode2 else True)
+            eng.validate_batch(np.stack(imgs))
+            eng.backward_head()
+            return {name: eng.g_census(name) for name in eng.head_layers()}
+        finally:
+            if not self._train_on:
+                eng.backward_enable(False)
+                eng.loss_grad_enable(False)
 
     # ---- training (reference train_coco_pose_estimation.py:204-235; head only as in its first 2000 iterations, or all 92 layers) -----------
     REFERENCE_GRAD_SCALES = {'conv4_3_CPM': 0.25, 'conv4_4_CPM': 0.25}      # GradientScaling (train_coco_pose_estimation.py:222-223)
@@ -733,8 +819,10 @@ class PoseDetector(object):
             eng.backward_enable(2 if self._mode2 else True)
             eng.train_enable(True)
             eng.train_set_adam(**self._adam)
-            for name, sc in self._grad_scales.items():
-                eng.train_set_grad_scale(name, sc)
+            self._apply_gradient_settings(eng)
+            # every trainable layer's scale carries 2^-k of the loss scale; a layer named without being trainable is the engine's to refuse
+            trainable = self._trainable_layers()
+            self._fold_scales(trainable + sorted(set(self._grad_scales) - set(trainable)))
         except Exception:
             eng.backward_enable(False)
             eng.loss_grad_enable(False)
@@ -760,8 +848,7 @@ class PoseDetector(object):
         self._grad_scales = dict(default if grad_scales is None else grad_scales)
         if self._train_on:
             self.engine.train_set_adam(**self._adam)
-            for name in set(old) | set(self._grad_scales):
-                self.engine.train_set_grad_scale(name, self._grad_scales.get(name, 1.0))
+            self._fold_scales(sorted(set(old) | set(self._grad_scales) | set(self._trainable_layers() if self._loss_scale_log2 else ())))
 
     def train_step(self, imgs, poses_per_image, ignore_masks=None):
         """One iteration of the reference's training loop: the forward with compute_loss, the backward and Adam with the gradient scales,

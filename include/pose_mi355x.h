@@ -178,10 +178,21 @@ int pmx_synchronize(pmx_ctx* ctx);                    /* cuda.get_device_from_id
  *                              layers whose padded channel count is a multiple of 128; the others stay at 64).  Same bits either way
  *                              (the order above does not depend on it); per context; profile labels unchanged.  Any other value:
  *                              PMX_ERR_INVALID, the option unchanged
- *   "grad_precision" 0 | 2     pmx_conv2d_backward only (the values are named like "precision"): 0 (default) fp32 gradients; 2: dw and dx of
- *                              a 3x3 / 7x7 layer with f16 operands and fp32 sums (the f16 paragraph of pmx_conv2d_backward).  z, g, db
- *                              and the 1x1 layers keep every bit.  pmx_backward_head, pmx_backward_trunk and the train steps do NOT read
- *                              it: they stay fp32.  Per context.  Any other value (1, bf16x3, included): PMX_ERR_INVALID, the option
+ *   "grad_precision" 0 | 2     pmx_conv2d_backward and pmx_backward_head (the values are named like "precision"): 0 (default) fp32
+ *                              gradients; 2: dw and dx of a 3x3 / 7x7 layer with f16 operands and fp32 sums (the f16 paragraphs of
+ *                              pmx_conv2d_backward and pmx_backward_head).  z, db, the masks and the 1x1 layers keep their launches, and
+ *                              given the same inputs their bits.  pmx_backward_trunk does NOT read it: the trunk chain stays fp32 and
+ *                              continues from whatever gradient the head chain left at conv4_2's output.  The train steps take the
+ *                              gradient store as it is.  Per context.  Any other value (1, bf16x3, included): PMX_ERR_INVALID, the
+ *                              option unchanged
+ *   "loss_scale_log2" 0..24    k (default 0): a STATIC loss scale 2^k.  The next hooked forward with the loss gradients on multiplies the
+ *                              two constants c of pmx_loss_grad_enable by 2^k on the host (exact); the losses and the maps do not change.
+ *                              Everything downstream is linear, so the loss gradients, every g, dx, dw, db and the trunk gradient -- the
+ *                              trunk chain's results included -- carry the factor 2^k, and the accessors return the stored, SCALED
+ *                              values.  In fp32 the factor is exact bit for bit unless an unscaled intermediate is subnormal.  The value
+ *                              in force when a forward ran stays with that forward's gradients (pmx_get_loss_grad_scale); a later change
+ *                              relabels nothing.  The caller un-scales: by 2^-k on the host, or in a train step through the per-layer
+ *                              scale, scale * 2^-k (pmx_train_set_grad_scale; exact).  Any other value: PMX_ERR_INVALID, the option
  *                              unchanged
  *   "fuse_conv1" 1 | 0         conv1_1 recomputed on conv1_2's halo tiles, one launch instead of two (default 1); identical bits
  *   "precise_lanes" 1..4       detect_precise: inference scales in flight at once, each on its own stream and working set (default 4;
@@ -504,6 +515,9 @@ int pmx_loss_grad_enable(pmx_ctx* ctx, int on);
  * NULL.  PMX_ERR_INVALID for a stage outside 0 .. 5; PMX_ERR_STATE before a hooked forward with the gradients on, and for a stage that
  * forward did not run (option "stop_stage").  Synchronises. */
 int pmx_get_loss_grads(pmx_ctx* ctx, int stage, float* gpaf_nchw, float* gheat_nchw);
+/* k of option "loss_scale_log2" as it was when the last hooked forward with the gradients on ran: the stored loss gradients, and whatever a
+ * backward makes of them, are 2^k times the gradients of the loss.  PMX_ERR_STATE before such a forward. */
+int pmx_get_loss_grad_scale(pmx_ctx* ctx, int* scale_log2);
 
 /* ---- sample preparation: the pixel side of CocoDataLoader.generate_labels (coco_data_loader.py:72-205, 334-341) ---------------------
  * One call prepares up to max_batch samples from images of different sizes: one launch per step over all samples, every kernel a gather
@@ -778,7 +792,10 @@ int pmx_conv2d_pair(pmx_ctx* ctx, const float* x0_nchw, const float* x1_nchw, co
  *   dx   the f16 form of the dispatcher (the f16 inference contract above, applied to (g, w')): ONE conv_f16_kernel launch on the f16 pack
  *        of the transposed layer, which rounds g while staging; option "f16_bn" applies as to a forward, with the same bits either way.
  * Loss scaling is deliberately not part of any kernel: everything after the mask is linear in dy and the masks do not depend on dy, so a
- * caller whose gradients would fall below the f16 range scales dy by 2^k and un-scales dx, dw and db by 2^-k (exact in fp32).
+ * caller whose gradients would fall below the f16 range scales dy by 2^k and un-scales dx, dw and db by 2^-k (exact in fp32).  The chains
+ * get their dy from the loss gradients, so there the scale is option "loss_scale_log2": 2^k enters on the host, in the two constants the
+ * loss-gradient kernel is handed, and pmx_get_loss_grads, pmx_get_layer_grad, pmx_get_trunk_grad and pmx_get_retained(name, 1) return the
+ * stored, scaled values.
  * Each of dx, dw, db, z may be NULL; a NULL output's work is skipped (z is still computed when relu or pool need it).  avg_ms3 may be NULL;
  * with iters > 0 it receives the mean time over `iters` repetitions of [0] the data-gradient plan, [1] the weight-gradient launches
  * (combine included), [2] the mask + bias-gradient launches, each timed on its own between two events (0 for a part that was skipped).
@@ -823,6 +840,17 @@ int pmx_conv2d_backward(pmx_ctx* ctx, const float* x_nchw, const float* w_oihw, 
  *   elsewhere      u = dx of the one layer that reads the output
  * No floating-point atomics: every run gives the same bits.  The chain ends with dx of conv4_3_CPM, the gradient at conv4_2's output,
  * where a trunk backward would start (pmx_get_trunk_grad).  Asynchronous.
+ * Option "grad_precision" = 2: the 58 layers of the head with ksize > 1 -- conv4_3_CPM, conv4_4_CPM, conv5_1..3_CPM_*, Mconv1..5_stage*_* --
+ * take dw and dx with f16 operands and fp32 sums, by the contract of pmx_conv2d_backward's f16 paragraph:
+ *   dw   conv_wgrad_f16_kernel + the combine, on the same slices of the stores the fp32 kernel reads (g and x are rounded while they are
+ *        staged; Mconv1_* through the same channel map).  Groups of 16 pixels per map row of w/8 pixels, the batch * h/8 map rows cut into
+ *        strips by the f16 rule (option "wgrad_strips"), the bound (16 + R * ceil((w/8) / 16) + S) * 2^-23 * sum |f16(g) * f16(x)|.
+ *   dx   the dispatcher's f16 form on the f16 pack of the transposed layer (built with the transposed pack, kept per layer, dropped by
+ *        pmx_set_layer): one conv_f16_kernel launch per layer pair, whatever "conv_algo" and the batch are.
+ * The 24 1x1 layers (dw and dx), every db, every mask, the sums above and the copies keep their launches and, given the same inputs, their bits;
+ * the retained forward, the losses and the loss gradients do not depend on the option.  No atomics here either: the same bits on every
+ * run.  Gradients below the f16 range are flushed while staged (f16_rn_sat): option "loss_scale_log2" moves them into it, and
+ * pmx_backward_g_census counts what a given scale leaves outside.
  * PMX_ERR_STATE, before anything is enqueued: no retained forward yet, a forward since then that was not retained (any forward without
  * retention, the hook or the loss gradients), option "precision" != 0, a facenet / handnet context. */
 int pmx_backward_enable(pmx_ctx* ctx, int on);
@@ -837,6 +865,14 @@ int pmx_get_trunk_grad(pmx_ctx* ctx, float* g_nchw);
  * masked gradient g (after pmx_backward_head; not for "conv4_2"); NCHW float32 batch x cout x h/8 x w/8.  Errors as pmx_get_layer_grad;
  * which outside {0, 1}: PMX_ERR_INVALID.  Synchronises. */
 int pmx_get_retained(pmx_ctx* ctx, const char* name, int which, float* out_nchw);
+/* The range census of one head layer's kept g (what pmx_get_retained(name, 1) returns), over the layer's cout channels: with
+ * r = f16_rn_sat(g) (csrc/f16_round.h), counts[0] = elements with g != 0, [1] g != 0 and r == 0 (flushed), [2] 0 < |r| < 2^-14 (subnormal),
+ * [3] |g| > 65504 (saturated; infinities included), [4] NaN.  One launch of its own on the context's stream -- a block reduction, then one
+ * integer atomic add per block and counter, so the counts are the same on every run -- only on request, never inside the chain.  Head layers
+ * only: PMX_ERR_INVALID for an unknown name, for "conv4_2" and for every other trunk layer (in mode 2 as well, where
+ * pmx_get_retained(name, 1) takes them) and for a NULL counts; PMX_ERR_STATE without a retained forward, before pmx_backward_head has run
+ * for it, with option "precision" != 0, and for a layer of a stage that "stop_stage" cut off.  Synchronises. */
+int pmx_backward_g_census(pmx_ctx* ctx, const char* name, unsigned long long counts[5]);
 
 /* ---- trunk backward: the gradients of conv1_1 .. conv4_2 -----------------------------------------------------------------------------
  * From iteration 2000 on the reference updates all 92 layers (train_coco_pose_estimation.py:96-101: enable_update on the ten trunk
@@ -940,11 +976,15 @@ int pmx_pool_backward_test(pmx_ctx* ctx, const float* a_nchw, const float* u_nch
  *   2. Adam over all those layers in ONE launch (a per-segment table, sent through pinned memory; the call waits only if the previous
  *      step's table copy has not finished);
  *   3. the packers: every pack of an updated layer that EXISTS is rewritten in place, same pointer, with the bits a one-off build gives
- *      from the same OIHW weights (csrc/pack_index.h defines every float of every pack) -- the direct pack and bias (pmx_set_layer), the Winograd pack, the transposed 180-degree-rotated pack of
- *      the data gradient and its Winograd pack, the f16 and bf16x3 packs.  A pack that does not exist is not created: its lazy builder
- *      makes it on first use from the then-current direct pack, after waiting for the stream.  ONE launch per kind of pack serves all
- *      updated layers (direct + bias, f16, bf16x3, transposed, Winograd of both, conv1_1's fused-kernel pack): six launches at most, driven
+ *      from the same OIHW weights (csrc/pack_index.h defines every float of every pack) -- the direct pack and bias (pmx_set_layer),
+ *      the Winograd pack, the f16 and bf16x3 packs, the transposed 180-degree-rotated pack of the data gradient, its Winograd pack
+ *      and its f16 pack (pmx_get_transposed_f16_pack; it exists once a head backward ran under "grad_precision" 2).  A pack that
+ *      does not exist is not created: its lazy builder makes it on first use from the then-current direct pack, after waiting for
+ *      the stream.  ONE launch per kind of pack serves all updated layers (direct + bias, transposed, f16 of both, bf16x3, Winograd
+ *      of both, conv1_1's fused-kernel pack, in this order: a derived pack after the pack it reads): six launches at most, driven
  *      by per-layer tables that travel with Adam's in the same pinned copy.
+ * Under a loss scale ("loss_scale_log2" = k) the gradient store holds 2^k times the gradients; Adam's kernel and contract do not change:
+ * the caller sets every layer's scale to scale * 2^-k, which is exact, and line one of the contract, g = grad * scale, un-scales.
  * No host synchronisation, no host <-> device copy but the table.  The step CONSUMES the gradients: a second step without a new retained
  * forward + pmx_backward_head is PMX_ERR_STATE; pmx_get_layer_grad keeps working until the next forward.
  * Errors, before anything is enqueued: PMX_ERR_INVALID for a null context; PMX_ERR_STATE for a facenet / handnet context, "precision" != 0,
@@ -982,6 +1022,11 @@ int pmx_train_set_state(pmx_ctx* ctx, const char* name, const float* m_w, const 
  * (uint16 words).  *n_bytes is the pack's size whenever it exists; PMX_ERR_STATE if it does not exist now, PMX_ERR_INVALID for another
  * `which`, PMX_ERR_CAPACITY if out is NULL or cap_bytes too small.  Synchronises. */
 int pmx_get_pack(pmx_ctx* ctx, const char* name, int which, void* out, size_t cap_bytes, size_t* n_bytes);
+/* parity accessor, as pmx_get_pack: the f16 pack of the transposed layer of the data gradient (uint16 words), what dx of a 3x3 / 7x7 head
+ * layer reads under "grad_precision" 2 -- pack 7 of the Python binding; an entry of its own because pmx_get_pack's `which` ends at 6.
+ * It exists once a head backward ran under "grad_precision" 2 (never for a 1x1 layer) and is rewritten by every train step from then on.
+ * PMX_ERR_STATE if it does not exist now, PMX_ERR_INVALID for an unknown layer, PMX_ERR_CAPACITY as pmx_get_pack.  Synchronises. */
+int pmx_get_transposed_f16_pack(pmx_ctx* ctx, const char* name, void* out, size_t cap_bytes, size_t* n_bytes);
 /* test entry: the Adam launch of the training steps on the caller's host arrays of `total` floats each (w, m, v updated in place).  Segment
  * i covers floats [off[i], off[i] + n[i]); off[i] a multiple of 4, the segments in rising order and not sharing a 16-byte vector, else
  * PMX_ERR_INVALID.  Floats outside the segments keep their bits.  Synchronises. */

@@ -13,7 +13,13 @@ stream after `warmup` untimed ones (images on the device):
   (d) the host route the step replaces, by wall clock: every gradient fetched, Adam in NumPy, 82 x pmx_set_layer, and the next forward +
       backward, which rebuilds the derived packs (one-off launches of the device packers)
 
-    python tools/train_step_time.py [--full] [--no-host] [--iters N] [--warmup N] [--rounds N] [--batches 10,32] [--out PATH]"""
+--grad-precision 2 runs every leg with f16 head gradients (engine option "grad_precision" 2, loss scale 2^K folded into every layer's
+gradient scale); `both` measures legs (a) and (b) in both modes in the same process, alternated round by round (f16_* beside the fp32
+figures; (c) and (d) stay fp32, but from the first f16 round on every step, the fp32 ones included, also rewrites the 58 f16 packs of the
+transposed layers: packs_in_existence and pack_launches_per_step count them).
+
+    python tools/train_step_time.py [--full] [--no-host] [--iters N] [--warmup N] [--rounds N] [--batches 10,32]
+                                    [--grad-precision 0|2|both] [--loss-scale-log2 K] [--out PATH]"""
 import argparse
 import ctypes
 import importlib
@@ -58,6 +64,8 @@ def main():
     ap.add_argument('--out', default=None)
     ap.add_argument('--full', action='store_true', help='the step over all 92 layers (backward mode 2)')
     ap.add_argument('--no-host', action='store_true', help='leave out (d), the host route')
+    ap.add_argument('--grad-precision', choices=['0', '2', 'both'], default='0')
+    ap.add_argument('--loss-scale-log2', type=int, default=10, help='the loss scale of the f16 legs')
     args = ap.parse_args()
     if args.out is None:
         args.out = os.path.join(ROOT, 'profiles', 'train_step_full.json' if args.full else 'train_step.json')
@@ -91,9 +99,15 @@ def main():
         scales = {'conv4_3_CPM': 0.25, 'conv4_4_CPM': 0.25}
         if args.full:
             scales.update(dict.fromkeys(eng.TRUNK_LAYERS, 0.25))
-        for nm, sc in scales.items():
-            eng.train_set_grad_scale(nm, sc)
         stepped = (list(eng.TRUNK_LAYERS) if args.full else []) + head
+
+        def set_mode(gp):          # the gradients' precision, the loss scale and its inverse in every stepped layer's scale
+            k = args.loss_scale_log2 if gp else 0
+            eng.set_option('grad_precision', gp)
+            eng.set_option('loss_scale_log2', k)
+            for nm in stepped:
+                eng.train_set_grad_scale(nm, scales.get(nm, 1.0) * 2.0 ** -k)
+        set_mode(2 if args.grad_precision == '2' else 0)
         n_params = sum(int(np.prod(eng.layer_shape(nm))) + eng.layer_shape(nm)[0] for nm in stepped)
 
         def head_a():
@@ -112,10 +126,15 @@ def main():
         def leg_b():
             leg_a()
             eng.train_step() if args.full else eng.train_step_head()
-        a_ms, b_ms, ha_ms, hb_ms = [], [], [], []
+        a_ms, b_ms, ha_ms, hb_ms, fa_ms, fb_ms = [], [], [], [], [], []
         for _ in range(args.rounds):
             a_ms.append(timed(eng, leg_a, args.iters, args.warmup))
             b_ms.append(timed(eng, leg_b, args.iters, args.warmup))
+            if args.grad_precision == 'both':
+                set_mode(2)
+                fa_ms.append(timed(eng, leg_a, args.iters, args.warmup))
+                fb_ms.append(timed(eng, leg_b, args.iters, args.warmup))
+                set_mode(0)
             if args.full:          # the head step in mode 2, interleaved
                 ha_ms.append(timed(eng, head_a, args.iters, args.warmup))
                 hb_ms.append(timed(eng, head_b, args.iters, args.warmup))
@@ -146,11 +165,22 @@ def main():
         copy_ms = float(np.mean(copies))
         def exists(nm, k):          # (the size query of pmx_get_pack: PMX_ERR_CAPACITY where the pack exists, PMX_ERR_STATE where not)
             n = ctypes.c_size_t(0)
+            if k == 't_f16':        # (the f16 pack of the transposed layer has an entry of its own)
+                return eng.lib.pmx_get_transposed_f16_pack(eng._ctx, nm.encode(), None, 0, ctypes.byref(n)) == 5
             return eng.lib.pmx_get_pack(eng._ctx, nm.encode(), eng.PACKS[k], None, 0, ctypes.byref(n)) == 5
-        kinds = {k: sum(exists(nm, k) for nm in stepped) for k in ('w', 'wino', 't_w', 't_wino')}
+        # (the f16 packs of the transposed layers exist from the first f16 backward on: in mode `both` the fp32 legs of the later rounds, and
+        #  the profiled step of (c), rewrite them as well -- one more packer launch, counted here)
+        kinds = {k: sum(exists(nm, k) for nm in stepped) for k in ('w', 'wino', 't_w', 't_wino', 'f16', 't_f16')}
         fused = int(args.full and exists('conv1_1', 'wino'))
-        launches = int(kinds['w'] > 0) + int(kinds['t_w'] > 0) + int(kinds['wino'] - fused + kinds['t_wino'] > 0) + fused
+        launches = (int(kinds['w'] > 0) + int(kinds['t_w'] > 0) + int(kinds['f16'] + kinds['t_f16'] > 0) +
+                    int(kinds['wino'] - fused + kinds['t_wino'] > 0) + fused)
         extra = dict(packs_in_existence=kinds, pack_launches_per_step=launches, adam_launches_per_step=1)
+        if args.grad_precision != '0':
+            extra.update(grad_precision=args.grad_precision, loss_scale_log2=args.loss_scale_log2)
+        if fa_ms:
+            fa, fb = float(np.mean(fa_ms)), float(np.mean(fb_ms))
+            extra.update(f16_forward_backward_ms=fa, f16_forward_backward_rounds_ms=fa_ms, f16_with_step_ms=fb, f16_with_step_rounds_ms=fb_ms,
+                         f16_step_cost_ms=fb - fa)
         if args.full:
             ha, hb = float(np.mean(ha_ms)), float(np.mean(hb_ms))
             extra.update(head_forward_backward_ms=ha, head_forward_backward_rounds_ms=ha_ms, head_with_step_ms=hb, head_with_step_rounds_ms=hb_ms,
